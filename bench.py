@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X-native RGB-D front end (ORB extractor + surfel fusion).
 
-    python bench.py --gpus N --steps K --warmup W [--config frontend|2|3|4|5] [--io resident|host]
+    python bench.py --gpus N --steps K --warmup W [--config frontend|2|3|4|5] [--io resident|host] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -100,7 +100,13 @@ def parse(argv=None):
     ap.add_argument("--no-parity-gate", action="store_true", help="skip the parity gate behind the timed region (profiler passes: its few launches would enter the per-kernel "
                     "averages); the default line carries it and bench.py exits non-zero when it fails")
     ap.add_argument("--dry-run", action="store_true", help="launcher / aggregation / device-binding check on CPU (gloo), no GPU work, fabricated timings")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed (ORB keypoints, "
+                    "descriptors and counts, the surfel map, the plane membership) as DIR/<name>.npy in float32 / float64, at most 64 MB in all (fixed, "
+                    "seeded samples of the larger arrays): two builds run with the same arguments can be compared output for output")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def free_port():
@@ -280,6 +286,59 @@ def parity_gate(args, q, cfg, W, H, intr, kfe, B, nkf, local_rank):
     return res
 
 
+DUMP_BUDGET = 64 << 20     # bytes of all the .npy payloads --dump-outputs writes (every rank and sequence together)
+DUMP_SEED = 2024           # the samples of the larger outputs are drawn with this seed: the same rows from run to run
+DUMP_PEAC_KEYFRAMES = 4    # keyframes whose plane membership image is written in full
+
+
+def dump_outputs(out_dir, q, cfg, budget, prefix=""):
+    """--dump-outputs: what the last timed step of sequence q computed, as a caller of the timed path receives it, written as
+    <out_dir>/<prefix><name>.npy in float32 (ORB descriptor bytes) or float64 (every value of the int32 / float32 records, exactly).
+    The full arrays are larger than the budget, so fixed, seeded samples go out: the ORB outputs of a subset of the frames (chosen by
+    frame index), the surfel map's rows at seeded indices plus its size and per-field sums over ALL rows, the membership images of
+    DUMP_PEAC_KEYFRAMES keyframes.  Returns {name: bytes}."""
+    from manhattanslam_amd import KEYPOINT_DTYPE
+    rng = np.random.Generator(np.random.PCG64(DUMP_SEED))
+    arrays = {}
+    use_peac = bool(cfg.get("peac")) and cfg["sf"]
+    if use_peac:
+        member = q.peac_dev[0].cpu().numpy()                          # (keyframes of a pass, H / 2, W / 2) int32: the membership the last pass fused
+        kf = np.sort(rng.choice(len(member), min(DUMP_PEAC_KEYFRAMES, len(member)), replace=False))
+        arrays["peac_keyframes"] = kf.astype(np.float64)
+        arrays["peac_membership"] = member[kf].astype(np.float64)
+    left = budget - (64 << 10) - sum(a.nbytes for a in arrays.values())   # 64 KB kept for the .npy headers
+    share = left // (int(cfg["orb"]) + int(cfg["sf"]))
+    if cfg["orb"]:
+        F, cap = len(q.d_n), q.orb.capacity
+        n = q.d_n.cpu().numpy()
+        per_frame = cap * (7 * 8 + 32 * 4)                             # worst case: a full row of keypoints (7 x f64) and descriptors (32 x f32)
+        nf = max(1, min(F, (share - F * 8) // per_frame))
+        frames = np.sort(rng.choice(F, nf, replace=False))
+        kps = q.d_kps.cpu().numpy().view(KEYPOINT_DTYPE).reshape(F, cap)
+        desc = q.d_desc.cpu().numpy().reshape(F, cap, 32)
+        arrays["orb_keypoint_count"] = n.astype(np.float64)                                            # every frame
+        arrays["orb_frames"] = frames.astype(np.float64)
+        arrays["orb_keypoints"] = np.concatenate([np.stack([kps[f, :n[f]][c].astype(np.float64) for c in KEYPOINT_DTYPE.names], 1) for f in frames])
+        arrays["orb_descriptors"] = np.concatenate([desc[f, :n[f]].astype(np.float32) for f in frames])
+    if cfg["sf"]:
+        m = q.sf.map_download()
+        rows = np.stack([m[c].astype(np.float64) for c in m.dtype.names], 1) if len(m) else np.zeros((0, len(m.dtype.names)))
+        arrays["surfel_map_size"] = np.array([len(m)], np.float64)
+        arrays["surfel_map_field_sums"] = rows.sum(0)
+        k = max(0, min(len(m), (share - 1024) // (rows.shape[1] * 8 + 8)))
+        idx = np.sort(rng.choice(len(m), k, replace=False))
+        arrays["surfel_map_sample_index"] = idx.astype(np.float64)
+        arrays["surfel_map_sample"] = rows[idx]                        # fields in SURFEL_DTYPE order
+    os.makedirs(out_dir, exist_ok=True)
+    sizes = {}
+    for name, a in arrays.items():
+        path = os.path.join(out_dir, f"{prefix}{name}.npy")
+        np.save(path, a)
+        sizes[prefix + name] = os.path.getsize(path)
+    assert sum(sizes.values()) <= budget, f"--dump-outputs: {sum(sizes.values())} bytes over the {budget}-byte budget"
+    return sizes
+
+
 def geometry(args):
     cfg = CONFIGS[args.config]
     W, H = (int(v) for v in (args.size or cfg["size"]).lower().split("x"))
@@ -340,13 +399,9 @@ def main():
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: refusing to report a line whose n_gpus differs from --gpus")
     if args.dry_run:
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs needs the GPU path: --dry-run computes nothing")
         return dry_run(args, world, rank, local_rank)
-    if args.sequences_per_gpu > 1 or args.io == "host":
-        # every sequence brings six streams of three priorities (the streaming passes: a second ORB handle and three host threads); the runtime maps
-        # them onto GPU_MAX_HW_QUEUES (default 4) hardware queues, and streams that share a queue serialise: two sequences 15.8 k frames/s with 4
-        # queues, 19.9 k with 8 (16: the same); --io host 16.1 k -> 17.6 k.  One resident sequence -- `value` -- is the same with 4, 8 or 16
-        # (23.32 / 23.26 / 23.32 k).  Read when the runtime starts.
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
     import torch
     import torch.distributed as dist
     if not torch.cuda.is_available():
@@ -546,6 +601,13 @@ def main():
     frames_rank = args.steps * P * F * S
     counters = [frames_rank, n_kp_pass * args.steps * P, ctr["n_live_after"], ctr["n_new"], ctr["n_updated"], ctr["n_deleted"], int(local_ms * 1e6), n_live_start]
     total_ms, gathered = aggregate(local_ms, counters, world, dev)
+    dumped = None
+    if args.dump_outputs:
+        # before the parity gate and the breakdown passes touch the handles again
+        dumped = {}
+        for s_idx, q in enumerate(seqs):
+            dumped.update(dump_outputs(args.dump_outputs, q, cfg, DUMP_BUDGET // (world * S),
+                                       f"rank{rank}_seq{s_idx}_" if world * S > 1 else ""))
     # parity gate (outside the timed region): every rank checks its own sequence; the verdicts travel like the counters
     gate = None
     if not args.no_parity_gate:
@@ -634,6 +696,8 @@ def main():
         "counters_per_rank": gathered,
         "parity_gate": gate,
     }
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "bytes": sum(dumped.values()), "files": sorted(dumped)}
 
     if args.io == "host" and world == 1:
         out["streaming"] = streaming(args, cfg, grays, depths, member, poses, smap, W, H, intr, kfe, F, P, B, D, local_rank, value)
