@@ -388,6 +388,57 @@ MSL_API int msl_match_by_projection_batch(int device, int n_pairs, int cap, cons
                                           int32_t *nmatches, msl_mem out_mem) MSL_NOEXCEPT;
 MSL_API int msl_match_descriptor_distance(int device, const uint8_t *a32, const uint8_t *b32, int n, int32_t *dist_out) MSL_NOEXCEPT;
 
+/* ---- Matching the local map: Tracking::SearchLocalPoints (src/Tracking.cc:1654-1695) after its first loop ----
+ * n_frames independent calls of the visibility loop -- Frame::isInFrustum(pMP, view_cos_limit) (src/Frame.cc:204-259) with
+ * MapPoint::PredictScale (src/MapPoint.cc:350-364) for every candidate local map point -- followed by
+ *     int ORBmatcher::SearchByProjection(Frame &F, const vector<MapPoint*> &vpMapPoints, th)   (src/ORBmatcher.cc:40-117)
+ * for an ORBmatcher(nn_ratio), with RadiusByViewingCos (:119-124) and Frame::GetFeaturesInArea (src/Frame.cc:332-381).
+ * Current frame: exactly the msl_match_by_projection current-frame arrays (`cap` entries per frame), plus
+ *   cur_flags[i]     state of F.mvpMapPoints[i] after SearchLocalPoints' first loop (bad points NULLed):
+ *                    bit 0: != NULL, bit 1: its Observations() > 0.  A keypoint with both bits is never handed out; one held by a
+ *                    point without observations may be overwritten.
+ * Local map points (mvpLocalMapPoints in order, `mcap` entries per frame), per point j < n_local[f]:
+ *   mp_xyz[3 j..]    GetWorldPos()                      mp_normal[3 j..]  GetNormal()
+ *   mp_dist[2 j..]   mfMinDistance, mfMaxDistance (raw: the 0.8f / 1.2f invariance factors are applied inside)
+ *   mp_desc[32 j..]  GetDescriptor()
+ *   mp_flags[j]      bit 0: candidate (!isBad() && mnLastFrameSeen != F.mnId), bit 1: Observations() > 0
+ * Tcw: rows 0-2 of the CV_32F mTcw of each frame (12 floats); mOw is derived from it as Frame::UpdatePoseMatrices does.
+ * On return match_out[f * cap + i2] is the local index j this call wrote into F.mvpMapPoints[i2] (the last writer), or -1 (unchanged);
+ * n_to_match[f] is SearchLocalPoints' nToMatch (the in-view count: each such point gets IncreaseVisible()) and nmatches[f] the return
+ * value of SearchByProjection (0 when nToMatch is 0, as when the call is skipped).  Optional outputs (NULL = not wanted), per point:
+ * in_view[f * mcap + j] = mbTrackInView and track[f * mcap + j] = the tracking fields isInFrustum sets (all zero for points not in view).
+ * The greedy, order-dependent hand-out of the reference (a keypoint held by a point with observations is skipped, later points
+ * overwrite earlier ones, the best / second-best ratio test applies only when both are at the same octave) is reproduced exactly.
+ * Limits: cap <= 8192, mcap <= 32768, nlevels <= MSL_MATCH_MAX_LEVELS; larger values are refused with MSL_ERR_INVALID before any launch.
+ * Asynchronous on the handle's stream when inputs and outputs are device memory; with host memory on either side it returns when the
+ * caller's buffers are its own again (as msl_match_by_projection). */
+typedef struct msl_local_match_params {
+    msl_match_params base;            /* fx..cy, bf, image bounds, th (3, or 5 after a relocalisation), nlevels, scale_factors; check_orientation unused */
+    float log_scale_factor;           /* Frame::mfLogScaleFactor as the caller's Frame holds it */
+    float view_cos_limit;             /* isInFrustum's viewingCosLimit (0.5 at the call site) */
+    float nn_ratio;                   /* ORBmatcher::mfNNratio (0.8 at the call site) */
+} msl_local_match_params;
+typedef struct msl_local_track {
+    float proj_x, proj_y, proj_xr;    /* mTrackProjX, mTrackProjY, mTrackProjXR */
+    int32_t scale_level;              /* mnTrackScaleLevel */
+    float view_cos;                   /* mTrackViewCos */
+} msl_local_track;
+MSL_API int msl_match_local_points(msl_match *h, int n_frames, int cap, int mcap, const msl_local_match_params *params,
+                                   const msl_keypoint *cur_kps, const float *cur_un_xy, const float *cur_uright,
+                                   const int32_t *cur_grid_cell, const uint8_t *cur_desc, const int32_t *n_cur, const uint8_t *cur_flags,
+                                   const float *mp_xyz, const float *mp_normal, const float *mp_dist, const uint8_t *mp_desc,
+                                   const uint8_t *mp_flags, const int32_t *n_local, const float *Tcw, msl_mem mem,
+                                   int32_t *match_out, int32_t *n_to_match, int32_t *nmatches, uint8_t *in_view,
+                                   msl_local_track *track, msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device handle, always synchronous; see msl_match_by_projection_batch). */
+MSL_API int msl_match_local_points_batch(int device, int n_frames, int cap, int mcap, const msl_local_match_params *params,
+                                         const msl_keypoint *cur_kps, const float *cur_un_xy, const float *cur_uright,
+                                         const int32_t *cur_grid_cell, const uint8_t *cur_desc, const int32_t *n_cur, const uint8_t *cur_flags,
+                                         const float *mp_xyz, const float *mp_normal, const float *mp_dist, const uint8_t *mp_desc,
+                                         const uint8_t *mp_flags, const int32_t *n_local, const float *Tcw, msl_mem mem,
+                                         int32_t *match_out, int32_t *n_to_match, int32_t *nmatches, uint8_t *in_view,
+                                         msl_local_track *track, msl_mem out_mem) MSL_NOEXCEPT;
+
 /* Batched form: n_frames keyframes in order, semantically n_frames consecutive msl_sf_fuse_resident calls.
  * Keyframe f's images start at base + f * <frame_stride> bytes (member_frame_stride may be 0: one shared
  * membership image); refs[n_frames] and poses (16 * n_frames floats, column-major Twc each) are host arrays.

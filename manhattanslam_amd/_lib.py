@@ -32,6 +32,8 @@ PEAC_PLANE_DTYPE = np.dtype([("normal", "<f8", (3,)), ("center", "<f8", (3,)), (
 FRAME_PARAMS_DTYPE = np.dtype([(n, "<f4") for n in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3", "bf", "minX", "maxX", "minY", "maxY")])
 MATCH_PARAMS_DTYPE = np.dtype([(n, "<f4") for n in ("fx", "fy", "cx", "cy", "bf", "minX", "maxX", "minY", "maxY", "th")] +
                               [("check_orientation", "<i4"), ("nlevels", "<i4"), ("scale_factors", "<f4", (16,))])
+LOCAL_MATCH_PARAMS_DTYPE = np.dtype(MATCH_PARAMS_DTYPE.descr + [(n, "<f4") for n in ("log_scale_factor", "view_cos_limit", "nn_ratio")])   # msl_local_match_params
+LOCAL_TRACK_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr", "<f4"), ("scale_level", "<i4"), ("view_cos", "<f4")])       # msl_local_track
 assert KEYPOINT_DTYPE.itemsize == 28 and SURFEL_DTYPE.itemsize == 56 and SEED_DTYPE.itemsize == 64
 
 MSL_MEM_HOST, MSL_MEM_DEVICE = 0, 1
@@ -89,6 +91,8 @@ SIGNATURES = {
     "msl_match_set_stream": (_i, [_vp, _vp]),
     "msl_match_by_projection": (_i, [_vp, _i, _i] + [_vp] * 15 + [_i, _vp, _vp, _i]),
     "msl_match_descriptor_distances": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "msl_match_local_points": (_i, [_vp, _i, _i, _i] + [_vp] * 15 + [_i] + [_vp] * 5 + [_i]),
+    "msl_match_local_points_batch": (_i, [_i, _i, _i, _i] + [_vp] * 15 + [_i] + [_vp] * 5 + [_i]),
     "msl_sf_fuse_resident": (_i, [_vp, _i, _vp, _sz, _vp, _sz, _vp, _sz, _i, _vp]),
     "msl_sf_set_batch_capacity": (_i, [_vp, _i]),
     "msl_sf_fuse_resident_batch": (_i, [_vp, _i, _vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _sz, _sz, _i, _vp]),

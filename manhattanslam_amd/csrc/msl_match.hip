@@ -23,6 +23,7 @@
 // follow cv::gemm's float kernel (double accumulation, one rounding) -- pinned in DESIGN.md section 3.
 #include "msl_common.h"
 
+#include <climits>
 #include <mutex>
 #include <new>
 
@@ -98,7 +99,7 @@ __global__ __launch_bounds__(256) void k_match_grid(MatchDev P) {
     const unsigned total = s_start[NCELLS];
     for (unsigned i = threadIdx.x; i < total; i += 256) P.items[(size_t)pair * P.cap + i] = s_items[i];
     for (int c = threadIdx.x; c <= NCELLS; c += 256) P.cellStart[(size_t)pair * (NCELLS + 1) + c] = s_start[c];
-    if (threadIdx.x == 0) {   // bForward / bBackward (:560-571)
+    if (threadIdx.x == 0 && P.mode) {   // bForward / bBackward (:560-571); the local-map search has no last frame (mode == nullptr)
         const float *Tc = P.TcwCur + (size_t)pair * 12, *Tl = P.TcwLast + (size_t)pair * 12;
         const float tcw[3] = {Tc[3], Tc[7], Tc[11]}, tlw[3] = {Tl[3], Tl[7], Tl[11]};
         float twc[3], tlc[3];
@@ -110,10 +111,24 @@ __global__ __launch_bounds__(256) void k_match_grid(MatchDev P) {
 
 // ---- shared pieces of the candidate test ---------------------------------------------------------------------------------
 struct Query {
-    float u, v, invzc, radius;
+    float u, v, ur, radius;           // ur: abscissa of the projection in the right image (u - mbf * invz)
     int minLevel, maxLevel;
     int minCX, maxCX, minCY, maxCY;   // window in grid cells (empty when minCX > maxCX)
 };
+
+// Frame::GetFeaturesInArea window (src/Frame.cc:337-351) of (u, v, radius) into Q's cell range; false = no cell.  The float -> int
+// conversions are clamped so that they stay defined (a NaN coordinate gives an empty window, as the reference's conversion does on x86-64).
+__device__ __forceinline__ bool grid_window(const MatchDev &P, float u, float v, float radius, Query &Q) {
+    const float fx0 = floorf((u - P.prm.minX - radius) * P.gridWInv), fx1 = ceilf((u - P.prm.minX + radius) * P.gridWInv);
+    const float fy0 = floorf((v - P.prm.minY - radius) * P.gridHInv), fy1 = ceilf((v - P.prm.minY + radius) * P.gridHInv);
+    const int nMinCellX = max(0, (int)fminf(fmaxf(fx0, -1.0e6f), 1.0e6f));
+    const int nMaxCellX = min(GRID_COLS - 1, (int)fminf(fmaxf(fx1, -1.0e6f), 1.0e6f));
+    const int nMinCellY = max(0, (int)fminf(fmaxf(fy0, -1.0e6f), 1.0e6f));
+    const int nMaxCellY = min(GRID_ROWS - 1, (int)fminf(fmaxf(fy1, -1.0e6f), 1.0e6f));
+    if (nMinCellX >= GRID_COLS || nMaxCellX < 0 || nMinCellY >= GRID_ROWS || nMaxCellY < 0) return false;
+    Q.minCX = nMinCellX; Q.maxCX = nMaxCellX; Q.minCY = nMinCellY; Q.maxCY = nMaxCellY;
+    return nMinCellX <= nMaxCellX && nMinCellY <= nMaxCellY;
+}
 
 __device__ __forceinline__ bool project_query(const MatchDev &P, int pair, int q, int mode, Query &Q) {
     const float *Tc = P.TcwCur + (size_t)pair * 12;
@@ -132,20 +147,11 @@ __device__ __forceinline__ bool project_query(const MatchDev &P, int pair, int q
     const int nLastOctave = P.lastOctave[(size_t)pair * P.cap + q];
     if (nLastOctave < 0 || nLastOctave >= P.prm.nlevels) return false;   // not an octave of this pyramid (the reference would index out of bounds): no candidates
     const float radius = P.prm.th * P.prm.scale_factors[nLastOctave];
-    Q.u = u; Q.v = v; Q.invzc = invzc; Q.radius = radius;
+    Q.u = u; Q.v = v; Q.ur = u - P.prm.bf * invzc; Q.radius = radius;   // ur: :626
     if (mode == 1) { Q.minLevel = nLastOctave; Q.maxLevel = -1; }
     else if (mode == 2) { Q.minLevel = 0; Q.maxLevel = nLastOctave; }
     else { Q.minLevel = nLastOctave - 1; Q.maxLevel = nLastOctave + 1; }
-    // Frame::GetFeaturesInArea window (src/Frame.cc:337-351); float -> int conversions clamped so that they stay defined
-    const float fx0 = floorf((u - P.prm.minX - radius) * P.gridWInv), fx1 = ceilf((u - P.prm.minX + radius) * P.gridWInv);
-    const float fy0 = floorf((v - P.prm.minY - radius) * P.gridHInv), fy1 = ceilf((v - P.prm.minY + radius) * P.gridHInv);
-    const int nMinCellX = max(0, (int)fminf(fmaxf(fx0, -1.0e6f), 1.0e6f));
-    const int nMaxCellX = min(GRID_COLS - 1, (int)fminf(fmaxf(fx1, -1.0e6f), 1.0e6f));
-    const int nMinCellY = max(0, (int)fminf(fmaxf(fy0, -1.0e6f), 1.0e6f));
-    const int nMaxCellY = min(GRID_ROWS - 1, (int)fminf(fmaxf(fy1, -1.0e6f), 1.0e6f));
-    if (nMinCellX >= GRID_COLS || nMaxCellX < 0 || nMinCellY >= GRID_ROWS || nMaxCellY < 0) return false;
-    Q.minCX = nMinCellX; Q.maxCX = nMaxCellX; Q.minCY = nMinCellY; Q.maxCY = nMaxCellY;
-    return nMinCellX <= nMaxCellX && nMinCellY <= nMaxCellY;
+    return grid_window(P, u, v, radius, Q);
 }
 
 // filters of GetFeaturesInArea (:353-376) + the mvuRight test (:625-630) for item position p; returns the Hamming distance or -1
@@ -162,14 +168,37 @@ __device__ __forceinline__ int eval_item(const MatchDev &P, int pair, const Quer
     if (!(fabsf(distx) < Q.radius && fabsf(disty) < Q.radius)) return -1;
     const float uRight = P.curUright[base];
     if (uRight > 0) {
-        const float ur = Q.u - P.prm.bf * Q.invzc;
-        const float er = fabsf(ur - uRight);
+        const float er = fabsf(Q.ur - uRight);
         if (er > Q.radius) return -1;
     }
     const uint4 *dp = reinterpret_cast<const uint4 *>(P.curDesc + base * 32);
     const uint4 e0 = dp[0], e1 = dp[1];
     return __popc(d0.x ^ e0.x) + __popc(d0.y ^ e0.y) + __popc(d0.z ^ e0.z) + __popc(d0.w ^ e0.w) + __popc(d1.x ^ e1.x) +
            __popc(d1.y ^ e1.y) + __popc(d1.z ^ e1.z) + __popc(d1.w ^ e1.w);
+}
+
+// The window of Q walked by one wave (cells spread over the lanes): every item that passes eval_item with a distance below distCap is
+// stored as (dist << 16 | item position), the first CMAX of them in cand; *cnt (wave-shared, zero on entry) ends as the total.
+__device__ __forceinline__ void wave_candidates(const MatchDev &P, int pair, const Query &Q, const uint8_t *desc32, int distCap, unsigned *cand,
+                                                unsigned *cnt, int lane) {
+    const uint4 *dq = reinterpret_cast<const uint4 *>(desc32);
+    const uint4 d0 = dq[0], d1 = dq[1];
+    const unsigned *cellStart = P.cellStart + (size_t)pair * (NCELLS + 1);
+    const unsigned short *items = P.items + (size_t)pair * P.cap;
+    const int ny = Q.maxCY - Q.minCY + 1, C = (Q.maxCX - Q.minCX + 1) * ny;
+    for (int c0 = 0; c0 < C; c0 += 64) {
+        const int c = c0 + lane;
+        if (c >= C) continue;
+        const int cellId = (Q.minCX + c / ny) * GRID_ROWS + Q.minCY + c % ny;
+        const unsigned b = cellStart[cellId], e = cellStart[cellId + 1];
+        for (unsigned p = b; p < e; p++) {
+            const int dist = eval_item(P, pair, Q, items[p], d0, d1);
+            if (dist < 0 || dist >= distCap) continue;
+            const unsigned slot = atomicAdd(cnt, 1u);
+            if (slot < CMAX) cand[slot] = ((unsigned)dist << 16) | p;
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
 }
 
 // ---- k_match_candidates: one wave per last-frame point ----------------------------------------------------------------------
@@ -187,25 +216,7 @@ __global__ __launch_bounds__(256) void k_match_candidates(MatchDev P) {
         if (lane == 0) P.candCnt[qi] = 0;
         return;
     }
-    const uint4 *dq = reinterpret_cast<const uint4 *>(P.lastDesc + qi * 32);
-    const uint4 d0 = dq[0], d1 = dq[1];
-    const unsigned *cellStart = P.cellStart + (size_t)pair * (NCELLS + 1);
-    const unsigned short *items = P.items + (size_t)pair * P.cap;
-    unsigned *cand = P.cand + qi * CMAX;
-    const int ny = Q.maxCY - Q.minCY + 1, C = (Q.maxCX - Q.minCX + 1) * ny;
-    for (int c0 = 0; c0 < C; c0 += 64) {
-        const int c = c0 + lane;
-        if (c >= C) continue;
-        const int cellId = (Q.minCX + c / ny) * GRID_ROWS + Q.minCY + c % ny;
-        const unsigned b = cellStart[cellId], e = cellStart[cellId + 1];
-        for (unsigned p = b; p < e; p++) {
-            const int dist = eval_item(P, pair, Q, items[p], d0, d1);
-            if (dist < 0) continue;
-            const unsigned slot = atomicAdd(&s_cnt[wv], 1u);
-            if (slot < CMAX) cand[slot] = ((unsigned)dist << 16) | p;
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
+    wave_candidates(P, pair, Q, P.lastDesc + qi * 32, 257, P.cand + qi * CMAX, &s_cnt[wv], lane);
     if (lane == 0) P.candCnt[qi] = s_cnt[wv];
 }
 
@@ -324,6 +335,235 @@ __global__ __launch_bounds__(ASSIGN_NT) void k_match_assign(MatchDev P) {
     if (threadIdx.x == 0) P.nmatches[pair] = s_nm;
 }
 
+// ==== Matching the local map: Tracking::SearchLocalPoints (src/Tracking.cc:1654-1695) ======================================================
+// Frame-batched (blockIdx.y / blockIdx.x = frame), four launches per call, the first of them k_match_grid above (no last frame: mode == nullptr):
+//   k_local_frustum     one lane per local map point: Frame::isInFrustum (src/Frame.cc:204-259) + MapPoint::PredictScale (src/MapPoint.cc:350-364)
+//                       -> mbTrackInView and the track record (mTrackProjX / Y / XR, mnTrackScaleLevel, mTrackViewCos);
+//   k_local_candidates  one wave per point in view: window of RadiusByViewingCos (src/ORBmatcher.cc:119-124) * th * mvScaleFactors[L], levels
+//                       [L-1, L] (GetFeaturesInArea's bCheckLevels rule), the mvuRight test on mTrackProjXR (:84-88), Hamming distance; stored as
+//                       (dist << 16 | item position) by wave_candidates exactly as for the last-frame search;
+//   k_local_assign      one workgroup per frame: SearchByProjection's greedy hand-out (:51-112) as a min-fixpoint, then holder / nmatches / nToMatch.
+//
+// The fixpoint (point j = position in mvpLocalMapPoints; "held with observations" is what the skip at :81-83 tests):
+//   * Best / second best of point j.  Positions in the item list ascend in the reference's walk order (cell ix * 48 + iy, mGrid insertion order
+//     inside a cell), and the reference's update rule (:94-103: strict < for both) leaves (bestIdx, bestLevel) = the smallest (dist, position)
+//     key and (bestDist2, bestLevel2) = the second smallest among the candidates it did not skip, ignoring distance 256 (never < the initial
+//     256).  So pick(j) is a function of the set of keypoints point j skips, and of nothing else.
+//   * Point j skips i2 iff, when j runs, mvpMapPoints[i2] is a point with Observations() > 0.  Keypoints pre-held with observations (cur_flags 3)
+//     are skipped by every j (t = -1 below).  Otherwise let t(i2) = the first point WITH observations that picks i2: before t(i2) only points
+//     without observations (or the pre-held point without observations) can have written i2, so nothing skips it; from t(i2) on it is held
+//     with observations, every later point skips it and nobody overwrites it.  Hence: j skips i2  <=>  t(i2) < j.
+//   * Uniqueness and equality with the sequential loop: pick(j) depends only on t restricted to points < j, i.e. on pick(0 .. j-1).  By induction
+//     over j there is exactly one assignment that satisfies "pick(j) = choice of j given t computed from the picks", and it is the sequential one.
+//   * Round bound: each round recomputes every pick from the t of the previous round.  After round r the picks of points 0 .. r-1 are final
+//     (point 0's never depends on t; point r's depends only on points < r), so at most n_local + 1 rounds run; the loop stops at the first
+//     round that changes nothing (a few in practice, more in conflict-heavy windows).
+//   * Holder of i2 = the last picker (later points overwrite, :108); with t(i2) set nobody picks after it.  nmatches counts every accepted pick.
+// LDS of k_local_assign: t[cap] int + pick[mcap] short = 4 cap + 2 mcap bytes, 96 KB at the limits (cap 8192, mcap 32768): inside the 160 KB
+// of a CDNA4 CU, and no more than k_match_assign asks for at its own limit, so the scratch never spills to global memory.
+constexpr int MAX_MCAP = 32768;
+constexpr int LOCAL_NT = 1024;
+constexpr int T_FREE = 0x7FFFFFFF;                  // t(i2): nobody with observations picks i2
+
+struct LocalDev {
+    MatchDev m;                                     // current frame, grid scratch, candidates (per local point), params (m.prm = base), matchOut, nmatches
+    int mcap;
+    float logScale, viewCosLimit, nnRatio;
+    const uint8_t *curFlags;
+    const float *mpXyz, *mpNormal, *mpDist; const uint8_t *mpDesc, *mpFlags; const int32_t *nLocal;
+    uint8_t *inView; msl_local_track *track;        // [n][mcap] scratch read by the later launches
+    uint8_t *inViewOut; msl_local_track *trackOut;  // the caller's device arrays (or nullptr)
+    int32_t *nToMatch;
+};
+
+// ceil(log(ratio) / mfLogScaleFactor) clamped to [0, nlevels - 1] (src/MapPoint.cc:350-364).  log is glibc's logf in the reference; here the
+// double log of the float, rounded once.  A quotient that is not a finite int (NaN, +-inf) converts to INT_MIN as on
+// x86-64 and so gives level 0.
+__device__ __forceinline__ int predict_scale(float maxDistance, float dist, float logScale, int nlevels) {
+    const float ratio = maxDistance / dist;
+    const float q = ceilf((float)log((double)ratio) / logScale);
+    int nScale = (q >= -2147483648.0f && q < 2147483648.0f) ? (int)q : INT_MIN;
+    if (nScale < 0) nScale = 0;
+    else if (nScale >= nlevels) nScale = nlevels - 1;
+    return nScale;
+}
+
+// ---- k_local_frustum: one lane per local map point --------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_local_frustum(LocalDev L) {
+    const int f = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= min(L.nLocal[f], L.mcap)) return;
+    const MatchDev &P = L.m;
+    const size_t jj = (size_t)f * L.mcap + j;
+    msl_local_track t{0.0f, 0.0f, 0.0f, 0, 0.0f};
+    uint8_t in = 0;
+    if (L.mpFlags[jj] & 1) {   // SearchLocalPoints skips bad points and points already seen in this frame (:1672-1675)
+        const float *Tc = P.TcwCur + (size_t)f * 12;
+        const float tcw[3] = {Tc[3], Tc[7], Tc[11]};
+        const float Pw[3] = {L.mpXyz[3 * jj], L.mpXyz[3 * jj + 1], L.mpXyz[3 * jj + 2]};
+        float Pc[3];
+        gemm3(Tc, false, 1.0, Pw, tcw, Pc);                               // Pc = mRcw * P + mtcw (:211)
+        const float PcX = Pc[0], PcY = Pc[1], PcZ = Pc[2];
+        if (!(PcZ < 0.0f)) {                                              // :217-218
+            const float invz = 1.0f / PcZ;
+            const float u = P.prm.fx * PcX * invz + P.prm.cx;              // :221-223, left to right, no contraction
+            const float v = P.prm.fy * PcY * invz + P.prm.cy;
+            if (!(u < P.prm.minX || u > P.prm.maxX) && !(v < P.prm.minY || v > P.prm.maxY)) {   // :225-228 (a NaN passes, as there)
+                float Ow[3];
+                gemm3(Tc, true, -1.0, tcw, nullptr, Ow);                   // mOw = -mRcw.t() * mtcw (Frame::UpdatePoseMatrices)
+                const float PO[3] = {Pw[0] - Ow[0], Pw[1] - Ow[1], Pw[2] - Ow[2]};
+                double ss = 0.0;
+                for (int k = 0; k < 3; k++) ss += (double)PO[k] * (double)PO[k];
+                const float dist = (float)sqrt(ss);                         // cv::norm on CV_32F (:234)
+                const float dmin = L.mpDist[2 * jj], dmax = L.mpDist[2 * jj + 1];
+                const float maxDistance = 1.2f * dmax, minDistance = 0.8f * dmin;   // GetMax / GetMinDistanceInvariance
+                if (!(dist < minDistance || dist > maxDistance)) {          // :236-237
+                    double dot = 0.0;
+                    for (int k = 0; k < 3; k++) dot += (double)PO[k] * (double)L.mpNormal[3 * jj + k];   // Mat::dot: double accumulation
+                    const float viewCos = (float)(dot / (double)dist);     // :242
+                    if (!(viewCos < L.viewCosLimit)) {                      // :244-245
+                        in = 1;
+                        t.proj_x = u;
+                        t.proj_xr = u - P.prm.bf * invz;
+                        t.proj_y = v;
+                        t.scale_level = predict_scale(dmax, dist, L.logScale, P.prm.nlevels);
+                        t.view_cos = viewCos;
+                    }
+                }
+            }
+        }
+    }
+    L.inView[jj] = in; L.track[jj] = t;
+    if (L.inViewOut) L.inViewOut[jj] = in;
+    if (L.trackOut) L.trackOut[jj] = t;
+}
+
+// Query of an in-view point: window radius RadiusByViewingCos(viewCos) * th * mvScaleFactors[L] (:59-66), levels [L-1, L]
+__device__ __forceinline__ bool local_query(const LocalDev &L, size_t jj, Query &Q) {
+    const msl_local_track t = L.track[jj];
+    float r = ((double)t.view_cos > 0.998) ? 2.5f : 4.0f;                // float vs double constant, as in the reference
+    if (L.m.prm.th != 1.0f) r *= L.m.prm.th;                              // bFactor
+    const float radius = r * L.m.prm.scale_factors[t.scale_level];
+    Q.u = t.proj_x; Q.v = t.proj_y; Q.ur = t.proj_xr; Q.radius = radius;
+    Q.minLevel = t.scale_level - 1; Q.maxLevel = t.scale_level;
+    return grid_window(L.m, Q.u, Q.v, radius, Q);
+}
+
+// ---- k_local_candidates: one wave per local map point ------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_local_candidates(LocalDev L) {
+    __shared__ unsigned s_cnt[4];
+    const int f = blockIdx.y, wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int j = blockIdx.x * 4 + wv;
+    if (j >= min(L.nLocal[f], L.mcap)) return;
+    const size_t jj = (size_t)f * L.mcap + j;
+    if (lane == 0) s_cnt[wv] = 0;
+    __builtin_amdgcn_wave_barrier();
+    Query Q;
+    if (!L.inView[jj] || !local_query(L, jj, Q)) {
+        if (lane == 0) L.m.candCnt[jj] = 0;
+        return;
+    }
+    wave_candidates(L.m, f, Q, L.mpDesc + jj * 32, 256, L.m.cand + jj * CMAX, &s_cnt[wv], lane);   // distance 256 never becomes best or second
+    if (lane == 0) L.m.candCnt[jj] = s_cnt[wv];
+}
+
+// the two smallest keys offered so far: b1 < b2
+__device__ __forceinline__ void offer2(unsigned key, unsigned &b1, unsigned &b2) {
+    if (key < b1) { b2 = b1; b1 = key; }
+    else if (key < b2) b2 = key;
+}
+
+// ---- k_local_assign: one workgroup per frame -----------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(LOCAL_NT) void k_local_assign(LocalDev L) {
+    extern __shared__ int s_ldyn[];          // t[cap] int | pick[mcap] short (the keypoint point j picks, -1 = none, -2 = not evaluated yet)
+    __shared__ int s_nm, s_ntm;
+    const MatchDev &P = L.m;
+    const int f = blockIdx.x;
+    const int nLoc = min(L.nLocal[f], L.mcap), nCur = min(P.nCur[f], P.cap);
+    int *s_t = s_ldyn;
+    short *s_pick = reinterpret_cast<short *>(s_ldyn + P.cap);
+    const unsigned short *items = P.items + (size_t)f * P.cap;
+    const uint8_t *cflags = L.curFlags + (size_t)f * P.cap;
+    const uint8_t *mflags = L.mpFlags + (size_t)f * L.mcap;
+    const msl_keypoint *kps = P.curKps + (size_t)f * P.cap;
+    auto reset_t = [&]() {   // pre-held with observations: skipped by every point
+        for (int i = threadIdx.x; i < P.cap; i += LOCAL_NT) s_t[i] = (i < nCur && (cflags[i] & 3) == 3) ? -1 : T_FREE;
+    };
+    reset_t();
+    for (int j = threadIdx.x; j < nLoc; j += LOCAL_NT) s_pick[j] = -2;
+    if (threadIdx.x == 0) { s_nm = 0; s_ntm = 0; }
+    __syncthreads();
+
+    // point j's choice given the current t: best and second-best key over the candidates it does not skip, then :106-112
+    auto pick_of = [&](int j) -> int {
+        const size_t jj = (size_t)f * L.mcap + j;
+        const unsigned cnt = P.candCnt[jj];
+        if (cnt == 0) return -1;
+        unsigned b1 = T_NONE, b2 = T_NONE;
+        if (cnt <= CMAX) {
+            const unsigned *cand = P.cand + jj * CMAX;
+            for (unsigned k = 0; k < cnt; k++) {
+                const unsigned key = cand[k];
+                if (s_t[items[key & 0xFFFFu]] < j) continue;      // held by a point with observations (:81-83)
+                offer2(key, b1, b2);
+            }
+        } else {   // more candidates than stored: walk the window again (rare; any count stays exact)
+            Query Q;
+            if (!local_query(L, jj, Q)) return -1;
+            const uint4 *dq = reinterpret_cast<const uint4 *>(L.mpDesc + jj * 32);
+            const uint4 d0 = dq[0], d1 = dq[1];
+            const unsigned *cellStart = P.cellStart + (size_t)f * (NCELLS + 1);
+            for (int ix = Q.minCX; ix <= Q.maxCX; ix++)
+                for (int iy = Q.minCY; iy <= Q.maxCY; iy++) {
+                    const unsigned b = cellStart[ix * GRID_ROWS + iy], e = cellStart[ix * GRID_ROWS + iy + 1];
+                    for (unsigned p = b; p < e; p++) {
+                        const unsigned i2 = items[p];
+                        if (s_t[i2] < j) continue;
+                        const int dist = eval_item(P, f, Q, i2, d0, d1);
+                        if (dist >= 0 && dist < 256) offer2(((unsigned)dist << 16) | p, b1, b2);
+                    }
+                }
+        }
+        if (b1 == T_NONE) return -1;
+        const int bestDist = (int)(b1 >> 16);
+        if (bestDist > TH_HIGH) return -1;                                 // :106
+        const int bestLevel = kps[items[b1 & 0xFFFFu]].octave;
+        const int bestLevel2 = b2 == T_NONE ? -1 : kps[items[b2 & 0xFFFFu]].octave;
+        const int bestDist2 = b2 == T_NONE ? 256 : (int)(b2 >> 16);
+        if (bestLevel == bestLevel2 && (float)bestDist > L.nnRatio * (float)bestDist2) return -1;   // :107-108
+        return (int)items[b1 & 0xFFFFu];
+    };
+
+    for (int round = 0; round <= nLoc; round++) {
+        bool changed = false;
+        for (int j = threadIdx.x; j < nLoc; j += LOCAL_NT) {
+            const int np = pick_of(j);
+            changed |= np != s_pick[j];
+            s_pick[j] = (short)np;
+        }
+        if (!__syncthreads_or(changed ? 1 : 0)) break;
+        reset_t();
+        __syncthreads();
+        for (int j = threadIdx.x; j < nLoc; j += LOCAL_NT)
+            if (s_pick[j] >= 0 && (mflags[j] & 2)) atomicMin(&s_t[s_pick[j]], j);
+        __syncthreads();
+    }
+    // holder = the last point that picked the keypoint; t(.) is no longer needed and its storage holds it
+    __syncthreads();
+    for (int i = threadIdx.x; i < P.cap; i += LOCAL_NT) s_t[i] = -1;
+    __syncthreads();
+    int nm = 0, ntm = 0;
+    for (int j = threadIdx.x; j < nLoc; j += LOCAL_NT) {
+        const int pk = s_pick[j];
+        if (pk >= 0) { atomicMax(&s_t[pk], j); nm++; }
+        ntm += L.inView[(size_t)f * L.mcap + j];
+    }
+    if (nm) atomicAdd(&s_nm, nm);
+    if (ntm) atomicAdd(&s_ntm, ntm);
+    __syncthreads();
+    for (int i = threadIdx.x; i < P.cap; i += LOCAL_NT) P.matchOut[(size_t)f * P.cap + i] = i < nCur ? s_t[i] : -1;
+    if (threadIdx.x == 0) { P.nmatches[f] = s_nm; L.nToMatch[f] = s_ntm; }
+}
+
 __global__ void k_descriptor_distance(const uint8_t *a, const uint8_t *b, int n, int32_t *out) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -354,6 +594,8 @@ struct msl_match {
     hipStream_t stream = nullptr; bool ownStream = true;
     Buf in[14], items, cellStart, mode, cand, candCnt, outMatch, outN;   // staged inputs (host-memory calls), scratch, staged outputs
     Buf da, db, dout;                                                     // msl_match_descriptor_distance
+    Buf lin[14], trk, inView, outNtm;                                     // msl_match_local_points: staged inputs, per-point scratch, staged nToMatch
+    bool localAttrSet = false;
     bool attrSet = false;
 };
 
@@ -365,9 +607,10 @@ std::mutex g_mutex;
 #define M_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { set_error("msl_match: %s failed: %s", #expr, hipGetErrorString(e_)); return MSL_ERR_HIP; } } while (0)
 
 void free_handle(msl_match *h) {
-    Buf *all[] = {&h->items, &h->cellStart, &h->mode, &h->cand, &h->candCnt, &h->outMatch, &h->outN, &h->da, &h->db, &h->dout};
+    Buf *all[] = {&h->items, &h->cellStart, &h->mode, &h->cand, &h->candCnt, &h->outMatch, &h->outN, &h->da, &h->db, &h->dout, &h->trk, &h->inView, &h->outNtm};
     for (Buf *b : all) if (b->p) (void)hipFree(b->p);
     for (Buf &b : h->in) if (b.p) (void)hipFree(b.p);
+    for (Buf &b : h->lin) if (b.p) (void)hipFree(b.p);
     if (h->ownStream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -442,6 +685,87 @@ int run_projection(msl_match *h, int n_pairs, int cap, const msl_match_params *p
     if (out_mem == MSL_MEM_HOST) {
         M_TRY(hipMemcpyAsync(match_out, P.matchOut, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
         M_TRY(hipMemcpyAsync(nmatches, P.nmatches, sizeof(int32_t) * n_pairs, hipMemcpyDeviceToHost, st));
+    }
+    if (out_mem == MSL_MEM_HOST || mem == MSL_MEM_HOST) M_TRY(hipStreamSynchronize(st));   // host buffers are the caller's again on return
+    return MSL_OK;
+}
+
+int run_local(msl_match *h, int n_frames, int cap, int mcap, const msl_local_match_params *lp, const msl_keypoint *cur_kps, const float *cur_un_xy,
+              const float *cur_uright, const int32_t *cur_grid_cell, const uint8_t *cur_desc, const int32_t *n_cur, const uint8_t *cur_flags,
+              const float *mp_xyz, const float *mp_normal, const float *mp_dist, const uint8_t *mp_desc, const uint8_t *mp_flags, const int32_t *n_local,
+              const float *Tcw, msl_mem mem, int32_t *match_out, int32_t *n_to_match, int32_t *nmatches, uint8_t *in_view, msl_local_track *track,
+              msl_mem out_mem) {
+    const msl_match_params *params = lp ? &lp->base : nullptr;
+    if (!h || n_frames < 1 || cap < 1 || cap > MAX_CAP || mcap < 1 || mcap > MAX_MCAP || !lp || !cur_kps || !cur_un_xy || !cur_uright || !cur_grid_cell ||
+        !cur_desc || !n_cur || !cur_flags || !mp_xyz || !mp_normal || !mp_dist || !mp_desc || !mp_flags || !n_local || !Tcw || !match_out ||
+        !n_to_match || !nmatches || params->nlevels < 1 || params->nlevels > MSL_MATCH_MAX_LEVELS || !(params->maxX > params->minX) ||
+        !(params->maxY > params->minY) || params->fx == 0 || !(lp->log_scale_factor > 0)) {
+        set_error("msl_match_local_points: invalid argument (cap <= %d, mcap <= %d, nlevels <= %d, log_scale_factor > 0)", MAX_CAP, MAX_MCAP,
+                  MSL_MATCH_MAX_LEVELS);
+        return MSL_ERR_INVALID;
+    }
+    int rc = bind_device(h->device);
+    if (rc != MSL_OK) return rc;
+    hipStream_t st = h->stream;
+    const size_t n = (size_t)n_frames * cap, m = (size_t)n_frames * mcap, F = (size_t)n_frames;
+    LocalDev L{};
+    MatchDev &P = L.m;
+    P.nPairs = n_frames; P.cap = cap; P.prm = *params;
+    P.gridWInv = static_cast<float>(GRID_COLS) / static_cast<float>(params->maxX - params->minX);   // src/Frame.cc:137-138
+    P.gridHInv = static_cast<float>(GRID_ROWS) / static_cast<float>(params->maxY - params->minY);
+    L.mcap = mcap; L.logScale = lp->log_scale_factor; L.viewCosLimit = lp->view_cos_limit; L.nnRatio = lp->nn_ratio;
+    const void *src[14] = {cur_kps, cur_un_xy, cur_uright, cur_grid_cell, cur_desc, n_cur, cur_flags, mp_xyz, mp_normal, mp_dist, mp_desc, mp_flags,
+                           n_local, Tcw};
+    const size_t bytes[14] = {sizeof(msl_keypoint) * n, 8 * n, 4 * n, 4 * n, 32 * n, 4 * F, n, 12 * m, 12 * m, 8 * m, 32 * m, m, 4 * F, 48 * F};
+    const void *dev[14];
+    for (int i = 0; i < 14; i++) {
+        if (mem == MSL_MEM_HOST) {
+            if (bytes[i] > h->lin[i].cap) M_TRY(hipStreamSynchronize(st));   // an earlier asynchronous call may still read the buffer about to be replaced
+            M_TRY(grow(h->lin[i], bytes[i]));
+            M_TRY(hipMemcpyAsync(h->lin[i].p, src[i], bytes[i], hipMemcpyHostToDevice, st));
+            dev[i] = h->lin[i].p;
+        } else {
+            dev[i] = src[i];
+        }
+    }
+    P.curKps = (const msl_keypoint *)dev[0]; P.curUn = (const float *)dev[1]; P.curUright = (const float *)dev[2]; P.curCell = (const int32_t *)dev[3];
+    P.curDesc = (const uint8_t *)dev[4]; P.nCur = (const int32_t *)dev[5]; L.curFlags = (const uint8_t *)dev[6]; L.mpXyz = (const float *)dev[7];
+    L.mpNormal = (const float *)dev[8]; L.mpDist = (const float *)dev[9]; L.mpDesc = (const uint8_t *)dev[10]; L.mpFlags = (const uint8_t *)dev[11];
+    L.nLocal = (const int32_t *)dev[12]; P.TcwCur = (const float *)dev[13];
+    const size_t need[6] = {sizeof(unsigned short) * n, sizeof(unsigned) * (NCELLS + 1) * F, sizeof(unsigned) * CMAX * m, sizeof(unsigned) * m,
+                            sizeof(msl_local_track) * m, m};
+    Buf *scr[6] = {&h->items, &h->cellStart, &h->cand, &h->candCnt, &h->trk, &h->inView};
+    for (int i = 0; i < 6; i++) {
+        if (need[i] > scr[i]->cap) M_TRY(hipStreamSynchronize(st));
+        M_TRY(grow(*scr[i], need[i]));
+    }
+    P.items = (unsigned short *)h->items.p; P.cellStart = (unsigned *)h->cellStart.p; P.cand = (unsigned *)h->cand.p; P.candCnt = (unsigned *)h->candCnt.p;
+    P.mode = nullptr;
+    L.track = (msl_local_track *)h->trk.p; L.inView = (uint8_t *)h->inView.p;
+    if (out_mem == MSL_MEM_HOST) {   // (host-output calls end with a sync: nothing in flight reads these)
+        M_TRY(grow(h->outMatch, sizeof(int32_t) * n)); M_TRY(grow(h->outN, sizeof(int32_t) * F)); M_TRY(grow(h->outNtm, sizeof(int32_t) * F));
+        P.matchOut = (int32_t *)h->outMatch.p; P.nmatches = (int32_t *)h->outN.p; L.nToMatch = (int32_t *)h->outNtm.p;
+        L.inViewOut = nullptr; L.trackOut = nullptr;
+    } else {
+        P.matchOut = match_out; P.nmatches = nmatches; L.nToMatch = n_to_match; L.inViewOut = in_view; L.trackOut = track;
+    }
+    const size_t lds = sizeof(int) * (size_t)cap + sizeof(short) * (size_t)mcap;   // 96 KB at the limits (see k_local_assign)
+    if (!h->localAttrSet) {
+        M_TRY(hipFuncSetAttribute((const void *)k_local_assign, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)(sizeof(int) * MAX_CAP + sizeof(short) * MAX_MCAP)));
+        h->localAttrSet = true;
+    }
+    hipLaunchKernelGGL(k_match_grid, dim3((unsigned)n_frames), dim3(256), sizeof(unsigned short) * cap, st, P);
+    hipLaunchKernelGGL(k_local_frustum, dim3((unsigned)((mcap + 255) / 256), (unsigned)n_frames), dim3(256), 0, st, L);
+    hipLaunchKernelGGL(k_local_candidates, dim3((unsigned)((mcap + 3) / 4), (unsigned)n_frames), dim3(256), 0, st, L);
+    hipLaunchKernelGGL(k_local_assign, dim3((unsigned)n_frames), dim3(LOCAL_NT), lds, st, L);
+    M_TRY(hipGetLastError());
+    if (out_mem == MSL_MEM_HOST) {
+        M_TRY(hipMemcpyAsync(match_out, P.matchOut, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+        M_TRY(hipMemcpyAsync(nmatches, P.nmatches, sizeof(int32_t) * F, hipMemcpyDeviceToHost, st));
+        M_TRY(hipMemcpyAsync(n_to_match, L.nToMatch, sizeof(int32_t) * F, hipMemcpyDeviceToHost, st));
+        if (in_view) M_TRY(hipMemcpyAsync(in_view, L.inView, m, hipMemcpyDeviceToHost, st));
+        if (track) M_TRY(hipMemcpyAsync(track, L.track, sizeof(msl_local_track) * m, hipMemcpyDeviceToHost, st));
     }
     if (out_mem == MSL_MEM_HOST || mem == MSL_MEM_HOST) M_TRY(hipStreamSynchronize(st));   // host buffers are the caller's again on return
     return MSL_OK;
@@ -535,6 +859,35 @@ int msl_match_by_projection_batch(int device, int n_pairs, int cap, const msl_ma
     if (mem == MSL_MEM_DEVICE) { if (bind_device(device) == MSL_OK) (void)hipStreamSynchronize(0); }
     int rc = run_projection(h, n_pairs, cap, params, cur_kps, cur_un_xy, cur_uright, cur_grid_cell, cur_desc, n_cur, last_xyz, last_desc, last_flags,
                             last_octave, last_angle, n_last, Tcw_cur, Tcw_last, mem, match_out, nmatches, out_mem);
+    if (rc == MSL_OK) rc = msl_match_sync(h);
+    return rc;
+    } MSL_ABI_CATCH_INT
+}
+
+int msl_match_local_points(msl_match *h, int n_frames, int cap, int mcap, const msl_local_match_params *params, const msl_keypoint *cur_kps,
+                           const float *cur_un_xy, const float *cur_uright, const int32_t *cur_grid_cell, const uint8_t *cur_desc, const int32_t *n_cur,
+                           const uint8_t *cur_flags, const float *mp_xyz, const float *mp_normal, const float *mp_dist, const uint8_t *mp_desc,
+                           const uint8_t *mp_flags, const int32_t *n_local, const float *Tcw, msl_mem mem, int32_t *match_out, int32_t *n_to_match,
+                           int32_t *nmatches, uint8_t *in_view, msl_local_track *track, msl_mem out_mem) noexcept {
+    try {
+    return run_local(h, n_frames, cap, mcap, params, cur_kps, cur_un_xy, cur_uright, cur_grid_cell, cur_desc, n_cur, cur_flags, mp_xyz, mp_normal, mp_dist,
+                     mp_desc, mp_flags, n_local, Tcw, mem, match_out, n_to_match, nmatches, in_view, track, out_mem);
+    } MSL_ABI_CATCH_INT
+}
+
+int msl_match_local_points_batch(int device, int n_frames, int cap, int mcap, const msl_local_match_params *params, const msl_keypoint *cur_kps,
+                                 const float *cur_un_xy, const float *cur_uright, const int32_t *cur_grid_cell, const uint8_t *cur_desc,
+                                 const int32_t *n_cur, const uint8_t *cur_flags, const float *mp_xyz, const float *mp_normal, const float *mp_dist,
+                                 const uint8_t *mp_desc, const uint8_t *mp_flags, const int32_t *n_local, const float *Tcw, msl_mem mem,
+                                 int32_t *match_out, int32_t *n_to_match, int32_t *nmatches, uint8_t *in_view, msl_local_track *track,
+                                 msl_mem out_mem) noexcept {
+    try {
+    std::lock_guard<std::mutex> lock(g_mutex);
+    msl_match *h = default_handle(device);
+    if (!h) return MSL_ERR_NO_DEVICE;
+    if (mem == MSL_MEM_DEVICE) { if (bind_device(device) == MSL_OK) (void)hipStreamSynchronize(0); }   // as msl_match_by_projection_batch
+    int rc = run_local(h, n_frames, cap, mcap, params, cur_kps, cur_un_xy, cur_uright, cur_grid_cell, cur_desc, n_cur, cur_flags, mp_xyz, mp_normal,
+                       mp_dist, mp_desc, mp_flags, n_local, Tcw, mem, match_out, n_to_match, nmatches, in_view, track, out_mem);
     if (rc == MSL_OK) rc = msl_match_sync(h);
     return rc;
     } MSL_ABI_CATCH_INT

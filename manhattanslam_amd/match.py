@@ -1,8 +1,9 @@
 """Host mirror of ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th) (reference src/ORBmatcher.cc:547-678) through the
-C ABI, for a batch of independent frame pairs."""
+C ABI, for a batch of independent frame pairs, and of the local-map search Tracking::SearchLocalPoints
+(src/Tracking.cc:1654-1695: isInFrustum + SearchByProjection(Frame&, vector<MapPoint*>, th)) for a batch of frames."""
 import numpy as np
 
-from ._lib import KEYPOINT_DTYPE, MATCH_PARAMS_DTYPE, MSL_MEM_HOST, check, lib, ptr
+from ._lib import KEYPOINT_DTYPE, LOCAL_MATCH_PARAMS_DTYPE, LOCAL_TRACK_DTYPE, MATCH_PARAMS_DTYPE, MSL_MEM_HOST, check, lib, ptr
 
 
 def match_params(frame_params, scale_factors, th, check_orientation=True):
@@ -14,6 +15,17 @@ def match_params(frame_params, scale_factors, th, check_orientation=True):
     p["check_orientation"] = 1 if check_orientation else 0
     p["nlevels"] = len(scale_factors)
     p["scale_factors"][0, :len(scale_factors)] = scale_factors
+    return p
+
+
+def local_match_params(frame_params, scale_factors, th, log_scale_factor, view_cos_limit=0.5, nn_ratio=0.8):
+    """msl_local_match_params: match_params(...) plus Frame::mfLogScaleFactor, isInFrustum's viewingCosLimit and ORBmatcher's mfNNratio
+    (SearchLocalPoints calls isInFrustum(pMP, 0.5) and ORBmatcher(0.8), th = 3, or 5 right after a relocalisation)."""
+    p = np.zeros(1, LOCAL_MATCH_PARAMS_DTYPE)
+    b = match_params(frame_params, scale_factors, th, False)
+    for k in MATCH_PARAMS_DTYPE.names:
+        p[k] = b[k]
+    p["log_scale_factor"], p["view_cos_limit"], p["nn_ratio"] = log_scale_factor, view_cos_limit, nn_ratio
     return p
 
 
@@ -46,6 +58,15 @@ class Matcher:
     def search_by_projection_device(self, params, n_pairs, cap, arrays, match_out, nmatches):
         """Device-resident inputs and outputs (torch tensors / device pointers in msl.h's argument order): asynchronous on the handle's stream."""
         check(lib.msl_match_by_projection(self.h, n_pairs, cap, ptr(params), *[ptr(a) for a in arrays], 1, ptr(match_out), ptr(nmatches), 1), "msl_match_by_projection")
+
+    def search_local_points_batch(self, params, cur, local, Tcw):
+        return search_local_points_batch(params, cur, local, Tcw, handle=self)
+
+    def search_local_points_device(self, params, n_frames, cap, mcap, arrays, match_out, n_to_match, nmatches, in_view=None, track=None):
+        """Device-resident inputs and outputs (torch tensors / device pointers in msl.h's argument order, cur_kps .. Tcw): asynchronous on
+        the handle's stream.  in_view / track may be None."""
+        check(lib.msl_match_local_points(self.h, n_frames, cap, mcap, ptr(params), *[ptr(a) for a in arrays], 1, ptr(match_out), ptr(n_to_match),
+                                         ptr(nmatches), ptr(in_view), ptr(track), 1), "msl_match_local_points")
 
     def descriptor_distance(self, a, b):
         a = np.ascontiguousarray(a, np.uint8).reshape(-1, 32); b = np.ascontiguousarray(b, np.uint8).reshape(-1, 32)
@@ -89,3 +110,44 @@ def descriptor_distance(a, b, device=0):
     out = np.zeros(len(a), np.int32)
     check(lib.msl_match_descriptor_distance(device, ptr(a), ptr(b), len(a), ptr(out)), "msl_match_descriptor_distance")
     return out
+
+
+def pack_local_points(cur, local, Tcw, cap=None, mcap=None):
+    """Packs per-frame dicts into msl_match_local_points' [frames][cap] / [frames][mcap] arrays (its argument order, cur_kps .. Tcw).
+       cur:   kps (KEYPOINT_DTYPE), un_xy (N,2) f32, uright (N,) f32, grid_cell (N,) i32, desc (N,32) u8, flags (N,) u8
+       local: xyz (M,3) f32, normal (M,3) f32, dist (M,2) f32 (mfMinDistance, mfMaxDistance), desc (M,32) u8, flags (M,) u8
+       Tcw:   (n_frames, 4, 4) or (n_frames, 3, 4) float32, row-major."""
+    B = len(cur)
+    cap = cap or max(max(len(c["kps"]) for c in cur), 1)
+    mcap = mcap or max(max(len(l["xyz"]) for l in local), 1)
+    kps = np.zeros((B, cap), KEYPOINT_DTYPE); un = np.zeros((B, cap, 2), np.float32); ur = np.zeros((B, cap), np.float32)
+    cell = np.full((B, cap), -1, np.int32); cdesc = np.zeros((B, cap, 32), np.uint8); ncur = np.zeros(B, np.int32); cfl = np.zeros((B, cap), np.uint8)
+    xyz = np.zeros((B, mcap, 3), np.float32); nrm = np.zeros((B, mcap, 3), np.float32); dist = np.zeros((B, mcap, 2), np.float32)
+    mdesc = np.zeros((B, mcap, 32), np.uint8); mfl = np.zeros((B, mcap), np.uint8); nloc = np.zeros(B, np.int32)
+    for f in range(B):
+        n, m = len(cur[f]["kps"]), len(local[f]["xyz"])
+        ncur[f], nloc[f] = n, m
+        kps[f, :n] = cur[f]["kps"]; un[f, :n] = cur[f]["un_xy"]; ur[f, :n] = cur[f]["uright"]; cell[f, :n] = cur[f]["grid_cell"]
+        cdesc[f, :n] = cur[f]["desc"]; cfl[f, :n] = cur[f]["flags"]
+        xyz[f, :m] = local[f]["xyz"]; nrm[f, :m] = local[f]["normal"]; dist[f, :m] = local[f]["dist"]; mdesc[f, :m] = local[f]["desc"]
+        mfl[f, :m] = local[f]["flags"]
+    tc = np.ascontiguousarray(np.asarray(Tcw, np.float32)[:, :3, :4].reshape(B, 12))
+    return cap, mcap, [kps, un, ur, cell, cdesc, ncur, cfl, xyz, nrm, dist, mdesc, mfl, nloc, tc]
+
+
+def search_local_points_batch(params, cur, local, Tcw, device=0, handle=None, cap=None, mcap=None):
+    """Tracking::SearchLocalPoints after its first loop, for a batch of frames (host arrays, synchronous); see pack_local_points for the
+    inputs.  Returns (match: per frame (N,) i32 -- the local index written into mvpMapPoints[i2] or -1, n_to_match, nmatches,
+    in_view: per frame (M,) u8, track: per frame (M,) LOCAL_TRACK_DTYPE)."""
+    cap, mcap, arrays = pack_local_points(cur, local, Tcw, cap, mcap)
+    B = len(cur)
+    match = np.zeros((B, cap), np.int32); ntm = np.zeros(B, np.int32); nm = np.zeros(B, np.int32)
+    inv = np.zeros((B, mcap), np.uint8); trk = np.zeros((B, mcap), LOCAL_TRACK_DTYPE)
+    args = (B, cap, mcap, ptr(params), *[ptr(a) for a in arrays], MSL_MEM_HOST, ptr(match), ptr(ntm), ptr(nm), ptr(inv), ptr(trk), MSL_MEM_HOST)
+    if handle is not None:
+        check(lib.msl_match_local_points(handle.h, *args), "msl_match_local_points")
+    else:
+        check(lib.msl_match_local_points_batch(device, *args), "msl_match_local_points_batch")
+    ncur, nloc = arrays[5], arrays[12]
+    return ([match[f, :ncur[f]].copy() for f in range(B)], ntm, nm, [inv[f, :nloc[f]].copy() for f in range(B)],
+            [trk[f, :nloc[f]].copy() for f in range(B)])

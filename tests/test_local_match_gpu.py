@@ -1,0 +1,142 @@
+"""GPU parity: batched local-map matching (msl_match_local_points[_batch], Tracking::SearchLocalPoints) vs the sequential CPU model in
+tests/local_match_model.py.  Every output must be identical: match_out, nmatches, n_to_match, in_view, and the track records bit for bit."""
+import numpy as np
+import pytest
+
+from tests import local_match_model as lm
+from tests import local_match_scenes as ls
+from tests import match_scenes as ms
+
+pytestmark = pytest.mark.gpu
+
+
+def _check(p, cur, local, Tcw, got):
+    match, ntm, nm, inv, trk = got
+    tot = 0
+    for f in range(len(cur)):
+        wm, wntm, wnm, winv, wtrk = lm.search_local_points(p, cur[f], local[f], Tcw[f])
+        assert ntm[f] == wntm and nm[f] == wnm, (f, ntm[f], wntm, nm[f], wnm)
+        assert np.array_equal(match[f], wm), (f, np.flatnonzero(match[f] != wm)[:10])
+        assert np.array_equal(inv[f], winv), (f, np.flatnonzero(inv[f] != winv)[:10])
+        assert trk[f].tobytes() == wtrk.tobytes(), (f, np.flatnonzero(trk[f] != wtrk)[:10])
+        tot += wnm
+    return tot
+
+
+def _ragged(p):
+    specs = [dict(seed=21, n_cur=600, n_local=0),                          # empty local map
+             dict(seed=22, n_cur=1, n_local=300),                          # one keypoint
+             dict(seed=23, n_cur=0, n_local=200),                          # no keypoints at all
+             dict(seed=24, n_cur=800, n_local=2000),
+             dict(seed=25, n_cur=1000, n_local=2500, cluster=True),        # windows beyond the 32 stored candidates
+             dict(seed=26, n_cur=900, n_local=1500, preheld=0.6),
+             dict(seed=27, n_cur=1000, n_local=4000),                      # the top end
+             dict(seed=28, n_cur=700, n_local=3000, conflict=True),        # many points on a few keypoints: many fixpoint rounds
+             dict(seed=29, n_cur=300, n_local=1)]
+    cur, local, T = [], [], []
+    for s in specs:
+        seed, nl = s.pop("seed"), s.pop("n_local")
+        c, l, t = ls.random_frame(seed, p, n_local=max(nl, 1), **s)
+        cur.append(c); local.append(l if nl else ls.empty_local(l)); T.append(t)
+    return cur, local, np.stack(T)
+
+
+@pytest.mark.parametrize("th", [3.0, 5.0])
+def test_ragged_batch_matches_model(th):
+    """Nine ragged frames in one call of the device-indexed form (th 3, and 5 as after a relocalisation)."""
+    from manhattanslam_amd import match
+    p = ls.params(th)
+    cur, local, T = _ragged(p)
+    got = match.search_local_points_batch(p, cur, local, T)
+    assert _check(p, cur, local, T, got) > 1500
+    assert got[1][0] == 0 and got[2][0] == 0 and got[2][2] == 0       # empty local map / no keypoints: nothing to match
+    assert got[1][7] > 2000 and got[2][7] < got[1][7] // 4             # the conflict-heavy frame: most points lose
+
+
+def test_handle_device_form_chained_from_last_frame_search():
+    """The pipeline shape: msl_match_by_projection's device output becomes cur_flags on the device (bit 0 = a last-frame point was
+    written, bit 1 = that point has observations) and feeds msl_match_local_points on the same handle with device-resident current-frame
+    arrays.  Same result as the host form fed the same flags, and as the model."""
+    import torch
+    from manhattanslam_amd import KEYPOINT_DTYPE, LOCAL_TRACK_DTYPE, MATCH_PARAMS_DTYPE, match
+    from manhattanslam_amd.match import Matcher
+    p = ls.params(3.0)
+    pm = ms.params(None, 7.0, False, dtype=MATCH_PARAMS_DTYPE)
+    B = 4
+    frames = [ls.random_frame(40 + f, p, n_cur=900 + 30 * f, n_local=2500 + 400 * f) for f in range(B)]
+    cur = [c for c, _, _ in frames]; local = [l for _, l, _ in frames]; T = np.stack([t for _, _, t in frames])
+    # last frame: the first 900 local points seen from the same pose, with octaves near the keypoints'
+    rng = np.random.default_rng(9)
+    last = [dict(xyz=l["xyz"][:900], desc=l["desc"][:900], flags=l["flags"][:900], octave=rng.integers(0, 8, 900).astype(np.int32),
+                 angle=np.zeros(900, np.float32)) for l in local]
+    cap, mcap, arrays = match.pack_local_points(cur, local, T)
+    kps, un, ur, cell, cdesc, ncur, _, xyz, nrm, dist, mdesc, mfl, nloc, tc = arrays
+    lxyz = np.zeros((B, cap, 3), np.float32); ld = np.zeros((B, cap, 32), np.uint8); lfl = np.zeros((B, cap), np.uint8)
+    loc = np.zeros((B, cap), np.int32); lang = np.zeros((B, cap), np.float32); nlast = np.full(B, 900, np.int32)
+    for f in range(B):
+        lxyz[f, :900] = last[f]["xyz"]; ld[f, :900] = last[f]["desc"]; lfl[f, :900] = last[f]["flags"]; loc[f, :900] = last[f]["octave"]
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a.view(np.uint8) if a.dtype == KEYPOINT_DTYPE else a)).cuda()
+    d_kps, d_un, d_ur, d_cell, d_cdesc, d_ncur, d_tc = (dev(a) for a in (kps, un, ur, cell, cdesc, ncur, tc))
+    d_lfl = dev(lfl)
+    m = Matcher()
+    out = torch.full((B, cap), -7, dtype=torch.int32, device="cuda"); nmp = torch.zeros(B, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    m.search_by_projection_device(pm, B, cap, [d_kps, d_un, d_ur, d_cell, d_cdesc, d_ncur, dev(lxyz), dev(ld), d_lfl, dev(loc), dev(lang),
+                                               dev(nlast), d_tc, d_tc], out, nmp)
+    m.sync()
+    held = out >= 0
+    obs = torch.where(held, (torch.gather(d_lfl, 1, out.clamp(min=0).long()) >> 1) & 1, torch.zeros_like(d_lfl))
+    d_cfl = (held.to(torch.uint8) | (obs << 1)).contiguous()
+    mo = torch.full((B, cap), -7, dtype=torch.int32, device="cuda"); ntm = torch.zeros(B, dtype=torch.int32, device="cuda")
+    nm = torch.zeros(B, dtype=torch.int32, device="cuda"); inv = torch.zeros((B, mcap), dtype=torch.uint8, device="cuda")
+    trk = torch.zeros((B, mcap * LOCAL_TRACK_DTYPE.itemsize), dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    m.search_local_points_device(p, B, cap, mcap, [d_kps, d_un, d_ur, d_cell, d_cdesc, d_ncur, d_cfl, dev(xyz), dev(nrm), dev(dist), dev(mdesc),
+                                                   dev(mfl), dev(nloc), d_tc], mo, ntm, nm, inv, trk)
+    m.sync()
+    # the same flags through the host form of the same handle
+    cfl = d_cfl.cpu().numpy()
+    assert (cfl == 3).sum() > 200 and (cfl == 1).sum() > 50      # pre-held keypoints of both kinds
+    for f in range(B):
+        cur[f]["flags"] = cfl[f, :len(cur[f]["kps"])]
+    host = m.search_local_points_batch(p, cur, local, T)
+    mo, ntm, nm, inv = mo.cpu().numpy(), ntm.cpu().numpy(), nm.cpu().numpy(), inv.cpu().numpy()
+    trk = trk.cpu().numpy().view(LOCAL_TRACK_DTYPE)
+    for f in range(B):
+        n, k = len(cur[f]["kps"]), len(local[f]["xyz"])
+        assert np.array_equal(mo[f, :n], host[0][f]) and np.all(mo[f, n:] == -1)
+        assert ntm[f] == host[1][f] and nm[f] == host[2][f]
+        assert np.array_equal(inv[f, :k], host[3][f]) and trk[f, :k].tobytes() == host[4][f].tobytes()
+    assert _check(p, cur, local, T, host) > 1000
+    # optional outputs omitted: the same matches
+    mo2 = torch.full((B, cap), -7, dtype=torch.int32, device="cuda")
+    ntm2 = torch.zeros(B, dtype=torch.int32, device="cuda"); nm2 = torch.zeros(B, dtype=torch.int32, device="cuda")
+    m.search_local_points_device(p, B, cap, mcap, [d_kps, d_un, d_ur, d_cell, d_cdesc, d_ncur, d_cfl, dev(xyz), dev(nrm), dev(dist), dev(mdesc),
+                                                   dev(mfl), dev(nloc), d_tc], mo2, ntm2, nm2)
+    m.sync()
+    assert np.array_equal(mo2.cpu().numpy(), mo) and np.array_equal(ntm2.cpu().numpy(), ntm) and np.array_equal(nm2.cpu().numpy(), nm)
+    m.close()
+
+
+def test_limits_are_refused_without_a_launch():
+    """cap > 8192 or mcap > 32768: MSL_ERR_INVALID with a message, outputs untouched (both forms)."""
+    from manhattanslam_amd import LOCAL_TRACK_DTYPE, MslError, match
+    from manhattanslam_amd._lib import MSL_MEM_HOST, lib, ptr
+    from manhattanslam_amd.match import Matcher
+    p = ls.params(3.0)
+    c, l, t = ls.random_frame(50, p, n_cur=10, n_local=10)
+    m = Matcher()
+    for cap, mcap in ((8193, 16), (16, 32769)):
+        _, _, arrays = match.pack_local_points([c], [l], t[None], cap=cap, mcap=mcap)
+        mo = np.full(cap, -7, np.int32); ntm = np.full(1, -7, np.int32); nm = np.full(1, -7, np.int32)
+        inv = np.full(mcap, 7, np.uint8); trk = np.zeros(mcap, LOCAL_TRACK_DTYPE)
+        args = (1, cap, mcap, ptr(p), *[ptr(a) for a in arrays], MSL_MEM_HOST, ptr(mo), ptr(ntm), ptr(nm), ptr(inv), ptr(trk), MSL_MEM_HOST)
+        assert lib.msl_match_local_points(m.h, *args) == -1 and b"mcap <= 32768" in lib.msl_last_error()     # MSL_ERR_INVALID
+        assert lib.msl_match_local_points_batch(0, *args) == -1
+        assert np.all(mo == -7) and ntm[0] == -7 and nm[0] == -7 and np.all(inv == 7)
+        with pytest.raises(MslError, match="invalid argument"):
+            match.search_local_points_batch(p, [c], [l], t[None], cap=cap, mcap=mcap)
+    # the handle is still good afterwards
+    got = m.search_local_points_batch(p, [c], [l], t[None])
+    _check(p, [c], [l], t[None], got)
+    m.close()
