@@ -439,6 +439,47 @@ MSL_API int msl_match_local_points_batch(int device, int n_frames, int cap, int 
                                          int32_t *match_out, int32_t *n_to_match, int32_t *nmatches, uint8_t *in_view,
                                          msl_local_track *track, msl_mem out_mem) MSL_NOEXCEPT;
 
+/* ---- Pose-only optimisation: Optimizer::PoseOptimization (src/Optimizer.cc:53-590) ----
+ * n_frames independent calls of  int Optimizer::PoseOptimization(Frame *pFrame)  for an Optimizer(angleInfo, disInfo, parInfo, verInfo,
+ * planeChi, planeChiVP, aTh, parTh), with every edge type it creates: mono / stereo point edges, the two endpoint edges of a line, and
+ * plane, parallel-plane and vertical-plane edges; g2o's Levenberg-Marquardt (4 rounds x 10 iterations, outlier classification after
+ * each round) restated on the device in double.  Per frame f (arrays hold cap / xcap / lcap / pcap entries per frame):
+ *   kps[i]             mvKeysUn[i] (only .octave is read)      un_xy[2 i..]   mvKeysUn[i].pt      uright[i]  mvuRight[i]
+ *   pt_ref[i]          index into this frame's xyz of mvpMapPoints[i]->GetWorldPos(), or -1 for NULL (i < n_kps[f]; values outside
+ *                      [0, xcap) count as NULL).  match_out of msl_match_by_projection (with last_xyz) or of msl_match_local_points
+ *                      (with mp_xyz, after merging the points held before the call) feeds it directly.
+ *   line_fn[3 j..]     mvKeyLineFunctions[j]                   line_xyz[6 j..]  mvpMapLines[j]->mWorldPos (start, end)
+ *   line_has[j]        mvpMapLines[j] != NULL                  (j < n_lines[f])
+ *   plane_coef[4 k..]  mvPlaneCoefficients[k]                  plane_w[12 k + 4 s..]  GetWorldPos() of mvpMapPlanes[k] (s = 0),
+ *   plane_has[k]       bit s set: that plane is not NULL       mvpParallelPlanes[k] (s = 1), mvpVerticalPlanes[k] (s = 2)  (k < n_planes[f])
+ *   Tcw[12]            rows 0-2 of the CV_32F mTcw
+ * In/out (out_mem): outlier[i] = mvbOutlier, line_outlier[j] = mvbLineOutlier, plane_outlier[3 k + s] = mvbPlaneOutlier /
+ * mvbParPlaneOutlier / mvbVerPlaneOutlier: entries with an edge get the final classification, the others keep their value.
+ * Out: Tcw_out[12] the optimised pose (float, as Frame::SetPose stores it; the input pose when fewer than 3 correspondences),
+ * n_good[f] the return value (nInitialCorrespondences - nBad, or 0).  Octaves outside [0, nlevels) are clamped.
+ * Limits: cap <= 8192, xcap <= 32768, lcap <= 256, pcap <= 64, nlevels <= MSL_MATCH_MAX_LEVELS; larger values are refused with
+ * MSL_ERR_INVALID before any launch.  msl_pose_optimize is asynchronous on the matcher handle's stream when inputs and outputs are
+ * device memory; with host memory on either side it returns when the caller's buffers are its own again. */
+typedef struct msl_pose_params {
+    float fx, fy, cx, cy, bf;         /* Frame::fx .. cy, mbf */
+    int32_t nlevels;
+    float inv_level_sigma2[MSL_MATCH_MAX_LEVELS];   /* Frame::mvInvLevelSigma2 */
+    double angle_info, dis_info, par_info, ver_info, plane_chi, plane_chi_vp, a_th, par_th;   /* the Optimizer constructor arguments */
+} msl_pose_params;
+MSL_API int msl_pose_optimize(msl_match *h, int n_frames, int cap, int xcap, int lcap, int pcap, const msl_pose_params *params,
+                              const msl_keypoint *kps, const float *un_xy, const float *uright, const int32_t *pt_ref, const int32_t *n_kps,
+                              const float *xyz, const double *line_fn, const double *line_xyz, const uint8_t *line_has, const int32_t *n_lines,
+                              const float *plane_coef, const float *plane_w, const uint8_t *plane_has, const int32_t *n_planes,
+                              const float *Tcw, msl_mem mem, uint8_t *outlier, uint8_t *line_outlier, uint8_t *plane_outlier,
+                              float *Tcw_out, int32_t *n_good, msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device matcher handle, always synchronous; see msl_match_by_projection_batch). */
+MSL_API int msl_pose_optimize_batch(int device, int n_frames, int cap, int xcap, int lcap, int pcap, const msl_pose_params *params,
+                                    const msl_keypoint *kps, const float *un_xy, const float *uright, const int32_t *pt_ref,
+                                    const int32_t *n_kps, const float *xyz, const double *line_fn, const double *line_xyz,
+                                    const uint8_t *line_has, const int32_t *n_lines, const float *plane_coef, const float *plane_w,
+                                    const uint8_t *plane_has, const int32_t *n_planes, const float *Tcw, msl_mem mem, uint8_t *outlier,
+                                    uint8_t *line_outlier, uint8_t *plane_outlier, float *Tcw_out, int32_t *n_good, msl_mem out_mem) MSL_NOEXCEPT;
+
 /* Batched form: n_frames keyframes in order, semantically n_frames consecutive msl_sf_fuse_resident calls.
  * Keyframe f's images start at base + f * <frame_stride> bytes (member_frame_stride may be 0: one shared
  * membership image); refs[n_frames] and poses (16 * n_frames floats, column-major Twc each) are host arrays.

@@ -34,7 +34,10 @@ MATCH_PARAMS_DTYPE = np.dtype([(n, "<f4") for n in ("fx", "fy", "cx", "cy", "bf"
                               [("check_orientation", "<i4"), ("nlevels", "<i4"), ("scale_factors", "<f4", (16,))])
 LOCAL_MATCH_PARAMS_DTYPE = np.dtype(MATCH_PARAMS_DTYPE.descr + [(n, "<f4") for n in ("log_scale_factor", "view_cos_limit", "nn_ratio")])   # msl_local_match_params
 LOCAL_TRACK_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr", "<f4"), ("scale_level", "<i4"), ("view_cos", "<f4")])       # msl_local_track
-assert KEYPOINT_DTYPE.itemsize == 28 and SURFEL_DTYPE.itemsize == 56 and SEED_DTYPE.itemsize == 64
+POSE_PARAMS_DTYPE = np.dtype([(n, "<f4") for n in ("fx", "fy", "cx", "cy", "bf")] + [("nlevels", "<i4"), ("inv_level_sigma2", "<f4", (16,))] +
+                             [(n, "<f8") for n in ("angle_info", "dis_info", "par_info", "ver_info", "plane_chi", "plane_chi_vp", "a_th",
+                                                   "par_th")])                                                                        # msl_pose_params
+assert POSE_PARAMS_DTYPE.itemsize == 152 and KEYPOINT_DTYPE.itemsize == 28 and SURFEL_DTYPE.itemsize == 56 and SEED_DTYPE.itemsize == 64
 
 MSL_MEM_HOST, MSL_MEM_DEVICE = 0, 1
 
@@ -93,6 +96,8 @@ SIGNATURES = {
     "msl_match_descriptor_distances": (_i, [_vp, _vp, _vp, _i, _vp]),
     "msl_match_local_points": (_i, [_vp, _i, _i, _i] + [_vp] * 15 + [_i] + [_vp] * 5 + [_i]),
     "msl_match_local_points_batch": (_i, [_i, _i, _i, _i] + [_vp] * 15 + [_i] + [_vp] * 5 + [_i]),
+    "msl_pose_optimize": (_i, [_vp, _i, _i, _i, _i, _i] + [_vp] * 16 + [_i] + [_vp] * 5 + [_i]),
+    "msl_pose_optimize_batch": (_i, [_i, _i, _i, _i, _i, _i] + [_vp] * 16 + [_i] + [_vp] * 5 + [_i]),
     "msl_sf_fuse_resident": (_i, [_vp, _i, _vp, _sz, _vp, _sz, _vp, _sz, _i, _vp]),
     "msl_sf_set_batch_capacity": (_i, [_vp, _i]),
     "msl_sf_fuse_resident_batch": (_i, [_vp, _i, _vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _sz, _sz, _i, _vp]),

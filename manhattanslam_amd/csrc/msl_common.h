@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstring>
 #include <exception>
+#include <mutex>
 #include <new>
 
 #include "../../include/msl.h"
@@ -29,6 +30,15 @@ void set_error(const char *fmt, ...);
     } while (0)
 
 int bind_device(int device);  // hipSetDevice + gfx950 check; returns msl_status
+
+// The matcher handle (msl_match.hip) also carries msl_pose_optimize (msl_pose.hip): its device, stream and pose buffers, and the shared
+// per-device handle of the *_batch forms (match_default_handle with match_default_mutex() held).
+int match_device(const msl_match *h);
+hipStream_t match_stream(const msl_match *h);
+void *&match_pose_scratch(msl_match *h);
+void pose_scratch_free(void *p);
+msl_match *match_default_handle(int device);
+std::mutex &match_default_mutex();
 
 // Exception barrier of the C ABI: every extern "C" entry point is `noexcept { try { ... } MSL_ABI_CATCH_* }` -- the library uses std::vector,
 // new and std::thread behind it, and nothing may unwind into a C (cgo / JNI / ctypes) caller.

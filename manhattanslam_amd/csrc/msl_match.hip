@@ -597,7 +597,14 @@ struct msl_match {
     Buf lin[14], trk, inView, outNtm;                                     // msl_match_local_points: staged inputs, per-point scratch, staged nToMatch
     bool localAttrSet = false;
     bool attrSet = false;
+    void *pose = nullptr;                                                 // msl_pose_optimize's buffers (msl_pose.hip)
 };
+
+namespace msl {
+int match_device(const msl_match *h) { return h->device; }
+hipStream_t match_stream(const msl_match *h) { return h->stream; }
+void *&match_pose_scratch(msl_match *h) { return h->pose; }
+}  // namespace msl
 
 namespace {
 
@@ -611,6 +618,7 @@ void free_handle(msl_match *h) {
     for (Buf *b : all) if (b->p) (void)hipFree(b->p);
     for (Buf &b : h->in) if (b.p) (void)hipFree(b.p);
     for (Buf &b : h->lin) if (b.p) (void)hipFree(b.p);
+    pose_scratch_free(h->pose);
     if (h->ownStream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -620,6 +628,15 @@ msl_match *default_handle(int device) {   // g_mutex held
     if (!h) h = msl_match_create(device);
     return h;
 }
+
+}  // namespace
+
+namespace msl {
+std::mutex &match_default_mutex() { return g_mutex; }
+msl_match *match_default_handle(int device) { return default_handle(device); }
+}  // namespace msl
+
+namespace {
 
 int run_projection(msl_match *h, int n_pairs, int cap, const msl_match_params *params, const msl_keypoint *cur_kps, const float *cur_un_xy,
                    const float *cur_uright, const int32_t *cur_grid_cell, const uint8_t *cur_desc, const int32_t *n_cur, const float *last_xyz,
