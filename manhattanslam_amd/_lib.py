@@ -167,3 +167,19 @@ def ptr(a):
     if hasattr(a, "data_ptr"):
         return C.c_void_p(a.data_ptr())
     return a.ctypes.data_as(C.c_void_p)
+
+
+def pad(frames, key, cap, dtype, fill=0, shape=()):
+    """frames[f][key] (per frame: at most cap rows of `shape`) as the ABI's [frames][cap, *shape] layout, padded with fill."""
+    out = np.full((len(frames), cap) + shape, fill, dtype)
+    for f, fr in enumerate(frames):
+        out[f, :len(fr[key])] = fr[key]
+    return out
+
+
+def call(name, handle, device, *args):
+    """The handle form `name` on handle.h when a handle is given, else `name`_batch on the device's shared one."""
+    if handle is not None:
+        check(getattr(lib, name)(handle.h, *args), name)
+    else:
+        check(getattr(lib, name + "_batch")(device, *args), name + "_batch")

@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstring>
 #include <exception>
+#include <initializer_list>
 #include <mutex>
 #include <new>
 
@@ -31,14 +32,33 @@ void set_error(const char *fmt, ...);
 
 int bind_device(int device);  // hipSetDevice + gfx950 check; returns msl_status
 
-// The matcher handle (msl_match.hip) also carries msl_pose_optimize (msl_pose.hip): its device, stream and pose buffers, and the shared
-// per-device handle of the *_batch forms (match_default_handle with match_default_mutex() held).
-int match_device(const msl_match *h);
-hipStream_t match_stream(const msl_match *h);
-void *&match_pose_scratch(msl_match *h);
-void pose_scratch_free(void *p);
-msl_match *match_default_handle(int device);
-std::mutex &match_default_mutex();
+// ---- grow-only device buffers ----------------------------------------------------------------
+// Afterwards p holds at least `need` bytes (old contents not kept), or nothing (p = nullptr, cap = 0) when the allocation failed.
+hipError_t grow(void *&p, size_t &cap, size_t need);
+
+// A device buffer owned by a handle and freed with it (a per-frame caller pays no hipMalloc).  Never in static storage: a hipFree run by a
+// static destructor after the HIP runtime has been torn down crashes the process at exit.
+struct DevBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    // Growing waits for st first: an earlier asynchronous call may still use the memory about to be replaced.
+    hipError_t grow(size_t need, hipStream_t st);
+};
+
+struct Need { DevBuf &buf; size_t bytes; };
+hipError_t grow_all(hipStream_t st, std::initializer_list<Need> bufs);   // scratch: every buffer grown to its size
+
+// Device pointers dev[0 .. n) for n arrays of an entry point.  Device memory: the caller's arrays themselves.  Host memory: the handle's
+// buffers bufs[0 .. n), grown to bytes[i]; the first n_in receive the caller's contents (inputs, in/out arrays), the others are written
+// by the kernels and copied back by finish_call.
+hipError_t stage(const void *const user[], const size_t bytes[], int n, int n_in, msl_mem mem, DevBuf bufs[], hipStream_t st, void *dev[]);
+// The end of an entry point.  Host-memory outputs: dev[i] is copied back to user[i] for every non-null user[i] (a null one was not asked
+// for).  Host memory on either side: the stream is drained, so the caller's host arrays are theirs again on return.
+hipError_t finish_call(void *const user[], const void *const dev[], const size_t bytes[], int n, msl_mem mem, msl_mem out_mem, hipStream_t st);
 
 // Exception barrier of the C ABI: every extern "C" entry point is `noexcept { try { ... } MSL_ABI_CATCH_* }` -- the library uses std::vector,
 // new and std::thread behind it, and nothing may unwind into a C (cgo / JNI / ctypes) caller.

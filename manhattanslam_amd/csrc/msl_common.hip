@@ -32,6 +32,49 @@ int bind_device(int device) {
     return MSL_OK;
 }
 
+hipError_t grow(void *&p, size_t &cap, size_t need) {
+    if (need <= cap) return hipSuccess;
+    if (p) (void)hipFree(p);
+    p = nullptr; cap = 0;
+    const hipError_t e = hipMalloc(&p, need);
+    if (e == hipSuccess) cap = need;
+    return e;
+}
+
+hipError_t DevBuf::grow(size_t need, hipStream_t st) {
+    if (need <= cap) return hipSuccess;
+    const hipError_t e = hipStreamSynchronize(st);
+    return e != hipSuccess ? e : msl::grow(p, cap, need);
+}
+
+hipError_t grow_all(hipStream_t st, std::initializer_list<Need> bufs) {
+    for (const Need &b : bufs) {
+        const hipError_t e = b.buf.grow(b.bytes, st);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t stage(const void *const user[], const size_t bytes[], int n, int n_in, msl_mem mem, DevBuf bufs[], hipStream_t st, void *dev[]) {
+    for (int i = 0; i < n; i++) {
+        if (mem != MSL_MEM_HOST) { dev[i] = const_cast<void *>(user[i]); continue; }
+        hipError_t e = bufs[i].grow(bytes[i], st);
+        if (e == hipSuccess && i < n_in) e = hipMemcpyAsync(bufs[i].p, user[i], bytes[i], hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) return e;
+        dev[i] = bufs[i].p;
+    }
+    return hipSuccess;
+}
+
+hipError_t finish_call(void *const user[], const void *const dev[], const size_t bytes[], int n, msl_mem mem, msl_mem out_mem, hipStream_t st) {
+    for (int i = 0; out_mem == MSL_MEM_HOST && i < n; i++) {
+        if (!user[i]) continue;
+        const hipError_t e = hipMemcpyAsync(user[i], dev[i], bytes[i], hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess) return e;
+    }
+    return out_mem == MSL_MEM_HOST || mem == MSL_MEM_HOST ? hipStreamSynchronize(st) : hipSuccess;
+}
+
 void KernelProfiler::begin(int k, hipStream_t s) {
     open_ = false;
     if (!on || !((mask >> k) & 1u)) return;

@@ -21,13 +21,16 @@
 //
 // Integer / byte work, L2-resident gathers; no MFMA.  The float expressions keep the reference's order; the 3x3 cv::Mat products
 // follow cv::gemm's float kernel (double accumulation, one rounding) -- pinned in DESIGN.md section 3.
-#include "msl_common.h"
+#include "msl_match_handle.h"
 
 #include <climits>
 #include <mutex>
 #include <new>
 
 using namespace msl;
+
+msl_match *msl::g_default[16];
+std::mutex msl::g_default_mutex;
 
 namespace {
 
@@ -573,71 +576,6 @@ __global__ void k_descriptor_distance(const uint8_t *a, const uint8_t *b, int n,
              __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
 }
 
-// grow-only device buffers owned by a handle (a per-frame caller pays no hipMalloc)
-struct Buf { void *p = nullptr; size_t cap = 0; };
-
-hipError_t grow(Buf &b, size_t need) {
-    if (need <= b.cap) return hipSuccess;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr; b.cap = 0;
-    const hipError_t e = hipMalloc(&b.p, need);
-    if (e == hipSuccess) b.cap = need;
-    return e;
-}
-
-}  // namespace
-
-// One matcher object = one ORBmatcher of the reference (src/ORBmatcher.cc:41): its own stream and its own scratch, used by one thread at a time;
-// the device is re-bound at every entry like the other handles.
-struct msl_match {
-    int device = 0;
-    hipStream_t stream = nullptr; bool ownStream = true;
-    Buf in[14], items, cellStart, mode, cand, candCnt, outMatch, outN;   // staged inputs (host-memory calls), scratch, staged outputs
-    Buf da, db, dout;                                                     // msl_match_descriptor_distance
-    Buf lin[14], trk, inView, outNtm;                                     // msl_match_local_points: staged inputs, per-point scratch, staged nToMatch
-    bool localAttrSet = false;
-    bool attrSet = false;
-    void *pose = nullptr;                                                 // msl_pose_optimize's buffers (msl_pose.hip)
-};
-
-namespace msl {
-int match_device(const msl_match *h) { return h->device; }
-hipStream_t match_stream(const msl_match *h) { return h->stream; }
-void *&match_pose_scratch(msl_match *h) { return h->pose; }
-}  // namespace msl
-
-namespace {
-
-msl_match *g_default[16];      // the device-indexed convenience entry points share one lazily created handle per device
-std::mutex g_mutex;
-
-#define M_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { set_error("msl_match: %s failed: %s", #expr, hipGetErrorString(e_)); return MSL_ERR_HIP; } } while (0)
-
-void free_handle(msl_match *h) {
-    Buf *all[] = {&h->items, &h->cellStart, &h->mode, &h->cand, &h->candCnt, &h->outMatch, &h->outN, &h->da, &h->db, &h->dout, &h->trk, &h->inView, &h->outNtm};
-    for (Buf *b : all) if (b->p) (void)hipFree(b->p);
-    for (Buf &b : h->in) if (b.p) (void)hipFree(b.p);
-    for (Buf &b : h->lin) if (b.p) (void)hipFree(b.p);
-    pose_scratch_free(h->pose);
-    if (h->ownStream && h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
-
-msl_match *default_handle(int device) {   // g_mutex held
-    msl_match *&h = g_default[device & 15];
-    if (!h) h = msl_match_create(device);
-    return h;
-}
-
-}  // namespace
-
-namespace msl {
-std::mutex &match_default_mutex() { return g_mutex; }
-msl_match *match_default_handle(int device) { return default_handle(device); }
-}  // namespace msl
-
-namespace {
-
 int run_projection(msl_match *h, int n_pairs, int cap, const msl_match_params *params, const msl_keypoint *cur_kps, const float *cur_un_xy,
                    const float *cur_uright, const int32_t *cur_grid_cell, const uint8_t *cur_desc, const int32_t *n_cur, const float *last_xyz,
                    const uint8_t *last_desc, const uint8_t *last_flags, const int32_t *last_octave, const float *last_angle, const int32_t *n_last,
@@ -662,48 +600,29 @@ int run_projection(msl_match *h, int n_pairs, int cap, const msl_match_params *p
                            last_angle, n_last, Tcw_cur, Tcw_last};
     const size_t bytes[14] = {sizeof(msl_keypoint) * n, 8 * n, 4 * n, 4 * n, 32 * n, 4 * (size_t)n_pairs, 12 * n, 32 * n, n, 4 * n, 4 * n,
                               4 * (size_t)n_pairs, 48 * (size_t)n_pairs, 48 * (size_t)n_pairs};
-    const void *dev[14];
-    for (int i = 0; i < 14; i++) {
-        if (mem == MSL_MEM_HOST) {
-            if (bytes[i] > h->in[i].cap) M_TRY(hipStreamSynchronize(st));   // an earlier asynchronous call may still read the buffer about to be replaced
-            M_TRY(grow(h->in[i], bytes[i]));
-            M_TRY(hipMemcpyAsync(h->in[i].p, src[i], bytes[i], hipMemcpyHostToDevice, st));
-            dev[i] = h->in[i].p;
-        } else {
-            dev[i] = src[i];
-        }
-    }
+    void *dev[14];
+    MSL_HIP_TRY(stage(src, bytes, 14, 14, mem, h->in, st, dev));
     P.curKps = (const msl_keypoint *)dev[0]; P.curUn = (const float *)dev[1]; P.curUright = (const float *)dev[2]; P.curCell = (const int32_t *)dev[3];
     P.curDesc = (const uint8_t *)dev[4]; P.nCur = (const int32_t *)dev[5]; P.lastXyz = (const float *)dev[6]; P.lastDesc = (const uint8_t *)dev[7];
     P.lastFlags = (const uint8_t *)dev[8]; P.lastOctave = (const int32_t *)dev[9]; P.lastAngle = (const float *)dev[10];
     P.nLast = (const int32_t *)dev[11]; P.TcwCur = (const float *)dev[12]; P.TcwLast = (const float *)dev[13];
-    const size_t need[5] = {sizeof(unsigned short) * n, sizeof(unsigned) * (NCELLS + 1) * n_pairs, sizeof(int) * n_pairs, sizeof(unsigned) * CMAX * n, sizeof(unsigned) * n};
-    Buf *scr[5] = {&h->items, &h->cellStart, &h->mode, &h->cand, &h->candCnt};
-    for (int i = 0; i < 5; i++) {
-        if (need[i] > scr[i]->cap) M_TRY(hipStreamSynchronize(st));
-        M_TRY(grow(*scr[i], need[i]));
-    }
+    MSL_HIP_TRY(grow_all(st, {{h->items, sizeof(unsigned short) * n}, {h->cellStart, sizeof(unsigned) * (NCELLS + 1) * n_pairs},
+                              {h->mode, sizeof(int) * n_pairs}, {h->cand, sizeof(unsigned) * CMAX * n}, {h->candCnt, sizeof(unsigned) * n}}));
     P.items = (unsigned short *)h->items.p; P.cellStart = (unsigned *)h->cellStart.p; P.mode = (int *)h->mode.p; P.cand = (unsigned *)h->cand.p;
     P.candCnt = (unsigned *)h->candCnt.p;
-    if (out_mem == MSL_MEM_HOST) {
-        M_TRY(grow(h->outMatch, sizeof(int32_t) * n)); M_TRY(grow(h->outN, sizeof(int32_t) * n_pairs));   // (host-output calls end with a sync: nothing in flight reads these)
-        P.matchOut = (int32_t *)h->outMatch.p; P.nmatches = (int32_t *)h->outN.p;
-    } else {
-        P.matchOut = match_out; P.nmatches = nmatches;
-    }
+    void *out[2] = {match_out, nmatches}, *dout[2];
+    const size_t outBytes[2] = {sizeof(int32_t) * n, sizeof(int32_t) * n_pairs};
+    MSL_HIP_TRY(stage(out, outBytes, 2, 0, out_mem, h->out, st, dout));
+    P.matchOut = (int32_t *)dout[0]; P.nmatches = (int32_t *)dout[1];
     if (!h->attrSet) {
-        M_TRY(hipFuncSetAttribute((const void *)k_match_assign, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(3 * sizeof(unsigned) * MAX_CAP)));
+        MSL_HIP_TRY(hipFuncSetAttribute((const void *)k_match_assign, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(3 * sizeof(unsigned) * MAX_CAP)));
         h->attrSet = true;
     }
     hipLaunchKernelGGL(k_match_grid, dim3((unsigned)n_pairs), dim3(256), sizeof(unsigned short) * cap, st, P);
     hipLaunchKernelGGL(k_match_candidates, dim3((unsigned)((cap + 3) / 4), (unsigned)n_pairs), dim3(256), 0, st, P);
     hipLaunchKernelGGL(k_match_assign, dim3((unsigned)n_pairs), dim3(ASSIGN_NT), 3 * sizeof(unsigned) * cap, st, P);
-    M_TRY(hipGetLastError());
-    if (out_mem == MSL_MEM_HOST) {
-        M_TRY(hipMemcpyAsync(match_out, P.matchOut, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-        M_TRY(hipMemcpyAsync(nmatches, P.nmatches, sizeof(int32_t) * n_pairs, hipMemcpyDeviceToHost, st));
-    }
-    if (out_mem == MSL_MEM_HOST || mem == MSL_MEM_HOST) M_TRY(hipStreamSynchronize(st));   // host buffers are the caller's again on return
+    MSL_HIP_TRY(hipGetLastError());
+    MSL_HIP_TRY(finish_call(out, dout, outBytes, 2, mem, out_mem, st));
     return MSL_OK;
 }
 
@@ -734,57 +653,38 @@ int run_local(msl_match *h, int n_frames, int cap, int mcap, const msl_local_mat
     const void *src[14] = {cur_kps, cur_un_xy, cur_uright, cur_grid_cell, cur_desc, n_cur, cur_flags, mp_xyz, mp_normal, mp_dist, mp_desc, mp_flags,
                            n_local, Tcw};
     const size_t bytes[14] = {sizeof(msl_keypoint) * n, 8 * n, 4 * n, 4 * n, 32 * n, 4 * F, n, 12 * m, 12 * m, 8 * m, 32 * m, m, 4 * F, 48 * F};
-    const void *dev[14];
-    for (int i = 0; i < 14; i++) {
-        if (mem == MSL_MEM_HOST) {
-            if (bytes[i] > h->lin[i].cap) M_TRY(hipStreamSynchronize(st));   // an earlier asynchronous call may still read the buffer about to be replaced
-            M_TRY(grow(h->lin[i], bytes[i]));
-            M_TRY(hipMemcpyAsync(h->lin[i].p, src[i], bytes[i], hipMemcpyHostToDevice, st));
-            dev[i] = h->lin[i].p;
-        } else {
-            dev[i] = src[i];
-        }
-    }
+    void *dev[14];
+    MSL_HIP_TRY(stage(src, bytes, 14, 14, mem, h->lin, st, dev));
     P.curKps = (const msl_keypoint *)dev[0]; P.curUn = (const float *)dev[1]; P.curUright = (const float *)dev[2]; P.curCell = (const int32_t *)dev[3];
     P.curDesc = (const uint8_t *)dev[4]; P.nCur = (const int32_t *)dev[5]; L.curFlags = (const uint8_t *)dev[6]; L.mpXyz = (const float *)dev[7];
     L.mpNormal = (const float *)dev[8]; L.mpDist = (const float *)dev[9]; L.mpDesc = (const uint8_t *)dev[10]; L.mpFlags = (const uint8_t *)dev[11];
     L.nLocal = (const int32_t *)dev[12]; P.TcwCur = (const float *)dev[13];
-    const size_t need[6] = {sizeof(unsigned short) * n, sizeof(unsigned) * (NCELLS + 1) * F, sizeof(unsigned) * CMAX * m, sizeof(unsigned) * m,
-                            sizeof(msl_local_track) * m, m};
-    Buf *scr[6] = {&h->items, &h->cellStart, &h->cand, &h->candCnt, &h->trk, &h->inView};
-    for (int i = 0; i < 6; i++) {
-        if (need[i] > scr[i]->cap) M_TRY(hipStreamSynchronize(st));
-        M_TRY(grow(*scr[i], need[i]));
-    }
+    MSL_HIP_TRY(grow_all(st, {{h->items, sizeof(unsigned short) * n}, {h->cellStart, sizeof(unsigned) * (NCELLS + 1) * F},
+                              {h->cand, sizeof(unsigned) * CMAX * m}, {h->candCnt, sizeof(unsigned) * m}, {h->trk, sizeof(msl_local_track) * m},
+                              {h->inView, m}}));
     P.items = (unsigned short *)h->items.p; P.cellStart = (unsigned *)h->cellStart.p; P.cand = (unsigned *)h->cand.p; P.candCnt = (unsigned *)h->candCnt.p;
     P.mode = nullptr;
     L.track = (msl_local_track *)h->trk.p; L.inView = (uint8_t *)h->inView.p;
-    if (out_mem == MSL_MEM_HOST) {   // (host-output calls end with a sync: nothing in flight reads these)
-        M_TRY(grow(h->outMatch, sizeof(int32_t) * n)); M_TRY(grow(h->outN, sizeof(int32_t) * F)); M_TRY(grow(h->outNtm, sizeof(int32_t) * F));
-        P.matchOut = (int32_t *)h->outMatch.p; P.nmatches = (int32_t *)h->outN.p; L.nToMatch = (int32_t *)h->outNtm.p;
-        L.inViewOut = nullptr; L.trackOut = nullptr;
-    } else {
-        P.matchOut = match_out; P.nmatches = nmatches; L.nToMatch = n_to_match; L.inViewOut = in_view; L.trackOut = track;
-    }
+    void *out[5] = {match_out, nmatches, n_to_match, in_view, track}, *dout[5];
+    const size_t outBytes[5] = {sizeof(int32_t) * n, sizeof(int32_t) * F, sizeof(int32_t) * F, m, sizeof(msl_local_track) * m};
+    MSL_HIP_TRY(stage(out, outBytes, 3, 0, out_mem, h->out, st, dout));
+    P.matchOut = (int32_t *)dout[0]; P.nmatches = (int32_t *)dout[1]; L.nToMatch = (int32_t *)dout[2];
+    // the optional in_view / track: the kernels write device-memory ones, host-memory ones are copied back from the scratch
+    const bool devOut = out_mem != MSL_MEM_HOST;
+    L.inViewOut = devOut ? in_view : nullptr; L.trackOut = devOut ? track : nullptr;
+    dout[3] = L.inView; dout[4] = L.track;
     const size_t lds = sizeof(int) * (size_t)cap + sizeof(short) * (size_t)mcap;   // 96 KB at the limits (see k_local_assign)
     if (!h->localAttrSet) {
-        M_TRY(hipFuncSetAttribute((const void *)k_local_assign, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)(sizeof(int) * MAX_CAP + sizeof(short) * MAX_MCAP)));
+        MSL_HIP_TRY(hipFuncSetAttribute((const void *)k_local_assign, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)(sizeof(int) * MAX_CAP + sizeof(short) * MAX_MCAP)));
         h->localAttrSet = true;
     }
     hipLaunchKernelGGL(k_match_grid, dim3((unsigned)n_frames), dim3(256), sizeof(unsigned short) * cap, st, P);
     hipLaunchKernelGGL(k_local_frustum, dim3((unsigned)((mcap + 255) / 256), (unsigned)n_frames), dim3(256), 0, st, L);
     hipLaunchKernelGGL(k_local_candidates, dim3((unsigned)((mcap + 3) / 4), (unsigned)n_frames), dim3(256), 0, st, L);
     hipLaunchKernelGGL(k_local_assign, dim3((unsigned)n_frames), dim3(LOCAL_NT), lds, st, L);
-    M_TRY(hipGetLastError());
-    if (out_mem == MSL_MEM_HOST) {
-        M_TRY(hipMemcpyAsync(match_out, P.matchOut, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-        M_TRY(hipMemcpyAsync(nmatches, P.nmatches, sizeof(int32_t) * F, hipMemcpyDeviceToHost, st));
-        M_TRY(hipMemcpyAsync(n_to_match, L.nToMatch, sizeof(int32_t) * F, hipMemcpyDeviceToHost, st));
-        if (in_view) M_TRY(hipMemcpyAsync(in_view, L.inView, m, hipMemcpyDeviceToHost, st));
-        if (track) M_TRY(hipMemcpyAsync(track, L.track, sizeof(msl_local_track) * m, hipMemcpyDeviceToHost, st));
-    }
-    if (out_mem == MSL_MEM_HOST || mem == MSL_MEM_HOST) M_TRY(hipStreamSynchronize(st));   // host buffers are the caller's again on return
+    MSL_HIP_TRY(hipGetLastError());
+    MSL_HIP_TRY(finish_call(out, dout, outBytes, 5, mem, out_mem, st));
     return MSL_OK;
 }
 
@@ -794,12 +694,13 @@ int run_distance(msl_match *h, const uint8_t *a32, const uint8_t *b32, int n, in
     int rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
     hipStream_t st = h->stream;
-    M_TRY(grow(h->da, (size_t)n * 32)); M_TRY(grow(h->db, (size_t)n * 32)); M_TRY(grow(h->dout, sizeof(int32_t) * n));   // synchronous call: nothing in flight
-    M_TRY(hipMemcpyAsync(h->da.p, a32, (size_t)n * 32, hipMemcpyHostToDevice, st)); M_TRY(hipMemcpyAsync(h->db.p, b32, (size_t)n * 32, hipMemcpyHostToDevice, st));
+    MSL_HIP_TRY(grow_all(st, {{h->da, (size_t)n * 32}, {h->db, (size_t)n * 32}, {h->dout, sizeof(int32_t) * n}}));
+    MSL_HIP_TRY(hipMemcpyAsync(h->da.p, a32, (size_t)n * 32, hipMemcpyHostToDevice, st));
+    MSL_HIP_TRY(hipMemcpyAsync(h->db.p, b32, (size_t)n * 32, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_descriptor_distance, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint8_t *)h->da.p, (const uint8_t *)h->db.p, n, (int32_t *)h->dout.p);
-    M_TRY(hipGetLastError());
-    M_TRY(hipMemcpyAsync(dist_out, h->dout.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-    M_TRY(hipStreamSynchronize(st));
+    MSL_HIP_TRY(hipGetLastError());
+    MSL_HIP_TRY(hipMemcpyAsync(dist_out, h->dout.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+    MSL_HIP_TRY(hipStreamSynchronize(st));
     return MSL_OK;
 }
 
@@ -823,7 +724,9 @@ void msl_match_destroy(msl_match *h) noexcept {
     if (!h) return;
     (void)bind_device(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    free_handle(h);
+    const hipStream_t own = h->ownStream ? h->stream : nullptr;
+    delete h;                                    // frees the buffers
+    if (own) (void)hipStreamDestroy(own);
     } MSL_ABI_CATCH_VOID
 }
 
@@ -832,7 +735,7 @@ int msl_match_set_stream(msl_match *h, void *hip_stream) noexcept {
     if (!h) { set_error("msl_match_set_stream: null handle"); return MSL_ERR_INVALID; }
     int rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
-    M_TRY(hipStreamSynchronize(h->stream));
+    MSL_HIP_TRY(hipStreamSynchronize(h->stream));
     if (h->ownStream && h->stream) (void)hipStreamDestroy(h->stream);
     h->stream = (hipStream_t)hip_stream; h->ownStream = false;
     return MSL_OK;
@@ -844,7 +747,7 @@ int msl_match_sync(msl_match *h) noexcept {
     if (!h) { set_error("msl_match_sync: null handle"); return MSL_ERR_INVALID; }
     int rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
-    M_TRY(hipStreamSynchronize(h->stream));
+    MSL_HIP_TRY(hipStreamSynchronize(h->stream));
     return MSL_OK;
     } MSL_ABI_CATCH_INT
 }
@@ -862,22 +765,16 @@ int msl_match_by_projection(msl_match *h, int n_pairs, int cap, const msl_match_
 
 int msl_match_descriptor_distances(msl_match *h, const uint8_t *a32, const uint8_t *b32, int n, int32_t *dist_out) noexcept { try { return run_distance(h, a32, b32, n, dist_out); } MSL_ABI_CATCH_INT }
 
-// Device-indexed convenience forms: one lazily created handle per device, serialised by a mutex, always synchronous.
 int msl_match_by_projection_batch(int device, int n_pairs, int cap, const msl_match_params *params, const msl_keypoint *cur_kps,
                                   const float *cur_un_xy, const float *cur_uright, const int32_t *cur_grid_cell, const uint8_t *cur_desc,
                                   const int32_t *n_cur, const float *last_xyz, const uint8_t *last_desc, const uint8_t *last_flags,
                                   const int32_t *last_octave, const float *last_angle, const int32_t *n_last, const float *Tcw_cur,
                                   const float *Tcw_last, msl_mem mem, int32_t *match_out, int32_t *nmatches, msl_mem out_mem) noexcept {
     try {
-    std::lock_guard<std::mutex> lock(g_mutex);
-    msl_match *h = default_handle(device);
-    if (!h) return MSL_ERR_NO_DEVICE;
-    // device-resident inputs of this form are complete, or enqueued on the legacy default stream, when the call is made (as before the handle existed)
-    if (mem == MSL_MEM_DEVICE) { if (bind_device(device) == MSL_OK) (void)hipStreamSynchronize(0); }
-    int rc = run_projection(h, n_pairs, cap, params, cur_kps, cur_un_xy, cur_uright, cur_grid_cell, cur_desc, n_cur, last_xyz, last_desc, last_flags,
-                            last_octave, last_angle, n_last, Tcw_cur, Tcw_last, mem, match_out, nmatches, out_mem);
-    if (rc == MSL_OK) rc = msl_match_sync(h);
-    return rc;
+    return on_default_handle(device, mem == MSL_MEM_DEVICE, [&](msl_match *h) {
+        return run_projection(h, n_pairs, cap, params, cur_kps, cur_un_xy, cur_uright, cur_grid_cell, cur_desc, n_cur, last_xyz, last_desc, last_flags,
+                              last_octave, last_angle, n_last, Tcw_cur, Tcw_last, mem, match_out, nmatches, out_mem);
+    });
     } MSL_ABI_CATCH_INT
 }
 
@@ -899,25 +796,20 @@ int msl_match_local_points_batch(int device, int n_frames, int cap, int mcap, co
                                  int32_t *match_out, int32_t *n_to_match, int32_t *nmatches, uint8_t *in_view, msl_local_track *track,
                                  msl_mem out_mem) noexcept {
     try {
-    std::lock_guard<std::mutex> lock(g_mutex);
-    msl_match *h = default_handle(device);
-    if (!h) return MSL_ERR_NO_DEVICE;
-    if (mem == MSL_MEM_DEVICE) { if (bind_device(device) == MSL_OK) (void)hipStreamSynchronize(0); }   // as msl_match_by_projection_batch
-    int rc = run_local(h, n_frames, cap, mcap, params, cur_kps, cur_un_xy, cur_uright, cur_grid_cell, cur_desc, n_cur, cur_flags, mp_xyz, mp_normal,
-                       mp_dist, mp_desc, mp_flags, n_local, Tcw, mem, match_out, n_to_match, nmatches, in_view, track, out_mem);
-    if (rc == MSL_OK) rc = msl_match_sync(h);
-    return rc;
+    return on_default_handle(device, mem == MSL_MEM_DEVICE, [&](msl_match *h) {
+        return run_local(h, n_frames, cap, mcap, params, cur_kps, cur_un_xy, cur_uright, cur_grid_cell, cur_desc, n_cur, cur_flags, mp_xyz, mp_normal,
+                         mp_dist, mp_desc, mp_flags, n_local, Tcw, mem, match_out, n_to_match, nmatches, in_view, track, out_mem);
+    });
     } MSL_ABI_CATCH_INT
 }
 
 int msl_match_descriptor_distance(int device, const uint8_t *a32, const uint8_t *b32, int n, int32_t *dist_out) noexcept {
     try {
-    std::lock_guard<std::mutex> lock(g_mutex);
+    std::lock_guard<std::mutex> lock(g_default_mutex);   // synchronous already: no on_default_handle
     msl_match *h = default_handle(device);
     if (!h) return MSL_ERR_NO_DEVICE;
     return run_distance(h, a32, b32, n, dist_out);
     } MSL_ABI_CATCH_INT
 }
-#undef M_TRY
 
 }  // extern "C"

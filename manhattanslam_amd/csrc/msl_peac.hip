@@ -1231,17 +1231,6 @@ struct Scratch {
 Scratch g_scratch[16];
 std::mutex g_scratchMutex;
 
-hipError_t grow(void *&p, size_t &cap, size_t need) {
-    if (need <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    const hipError_t e = hipMalloc(&p, need);
-    if (e == hipSuccess) cap = need;
-    return e;
-}
-
-#define PEAC_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { set_error("msl_peac: %s", hipGetErrorString(e_)); return MSL_ERR_HIP; } } while (0)
-
 // cloud (optional) + block fit for n_frames images; dBlocksOut receives the device pointer of the [frames][Nh * Nw] blocks.
 // The caller holds g_scratchMutex.
 int device_fit(int device, const uint16_t *depth, size_t strideBytes, size_t frameStrideBytes, int width, int height, int n_frames, msl_mem mem, float fx,
@@ -1266,32 +1255,32 @@ int device_fit(int device, const uint16_t *depth, size_t strideBytes, size_t fra
     Scratch &sc = g_scratch[device & 15];
     if (!sc.stream) {
         int lo = 0, hi = 0;
-        PEAC_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        PEAC_TRY(hipStreamCreateWithPriority(&sc.stream, hipStreamNonBlocking, hi));
-        PEAC_TRY(hipEventCreateWithFlags(&sc.ev, hipEventDisableTiming));
+        MSL_HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
+        MSL_HIP_TRY(hipStreamCreateWithPriority(&sc.stream, hipStreamNonBlocking, hi));
+        MSL_HIP_TRY(hipEventCreateWithFlags(&sc.ev, hipEventDisableTiming));
     }
     const hipStream_t st = sc.stream;
-    if (mem == MSL_MEM_DEVICE) { PEAC_TRY(hipEventRecord(sc.ev, 0)); PEAC_TRY(hipStreamWaitEvent(st, sc.ev, 0)); }
+    if (mem == MSL_MEM_DEVICE) { MSL_HIP_TRY(hipEventRecord(sc.ev, 0)); MSL_HIP_TRY(hipStreamWaitEvent(st, sc.ev, 0)); }
     if (mem == MSL_MEM_HOST) {
         // bytes actually present in the caller's buffer: the last row carries no stride padding
         const size_t frameBytes = strideBytes * (size_t)(height - 1) + (size_t)width * 2, slot = (frameBytes + 255) & ~(size_t)255;
-        PEAC_TRY(grow(sc.depth, sc.depthCap, slot * n_frames));
+        MSL_HIP_TRY(grow(sc.depth, sc.depthCap, slot * n_frames));
         for (int f = 0; f < n_frames; f++)
-            PEAC_TRY(hipMemcpyAsync((uint8_t *)sc.depth + f * slot, (const uint8_t *)depth + f * frameStrideBytes, frameBytes, hipMemcpyHostToDevice, st));
+            MSL_HIP_TRY(hipMemcpyAsync((uint8_t *)sc.depth + f * slot, (const uint8_t *)depth + f * frameStrideBytes, frameBytes, hipMemcpyHostToDevice, st));
         P.depth = (const uint16_t *)sc.depth; P.frameStrideBytes = slot;
     } else {
         P.depth = depth;
     }
     if (blocksUser) P.blocks = blocksUser;
-    else { PEAC_TRY(grow(sc.blocks, sc.blocksCap, sizeof(msl_peac_block) * nBlocks * n_frames)); P.blocks = (msl_peac_block *)sc.blocks; }
+    else { MSL_HIP_TRY(grow(sc.blocks, sc.blocksCap, sizeof(msl_peac_block) * nBlocks * n_frames)); P.blocks = (msl_peac_block *)sc.blocks; }
     P.cloud = cloudDev;
     if (cloudDev) hipLaunchKernelGGL(k_peac_cloud, dim3((unsigned)((nVert + 255) / 256), (unsigned)n_frames), dim3(256), 0, st, P);
     hipLaunchKernelGGL(k_peac_fit, dim3((unsigned)nBlocks, (unsigned)n_frames), dim3(64), sizeof(double) * 9 * prm.window_w * prm.window_h, st, P);
-    PEAC_TRY(hipGetLastError());
+    MSL_HIP_TRY(hipGetLastError());
     if (dHalfOut) {
-        PEAC_TRY(grow(sc.half, sc.halfCap, sizeof(uint16_t) * nVert * n_frames));
+        MSL_HIP_TRY(grow(sc.half, sc.halfCap, sizeof(uint16_t) * nVert * n_frames));
         hipLaunchKernelGGL(k_peac_half, dim3((unsigned)((nVert + 255) / 256), (unsigned)n_frames), dim3(256), 0, st, P, (uint16_t *)sc.half);
-        PEAC_TRY(hipGetLastError());
+        MSL_HIP_TRY(hipGetLastError());
         *dHalfOut = (uint16_t *)sc.half;
     }
     *dBlocksOut = P.blocks;
@@ -1325,8 +1314,8 @@ int msl_peac_block_fit(int device, const uint16_t *depth, size_t depth_stride_by
     if (rc != MSL_OK) return rc;
     const size_t nBlocks = (size_t)(((width + 1) / 2) / params->window_w) * (((height + 1) / 2) / params->window_h);
     const hipStream_t st = g_scratch[device & 15].stream;
-    if (out_mem == MSL_MEM_HOST) PEAC_TRY(hipMemcpyAsync(blocks_out, dBlocks, sizeof(msl_peac_block) * nBlocks * n_frames, hipMemcpyDeviceToHost, st));
-    PEAC_TRY(hipStreamSynchronize(st));
+    if (out_mem == MSL_MEM_HOST) MSL_HIP_TRY(hipMemcpyAsync(blocks_out, dBlocks, sizeof(msl_peac_block) * nBlocks * n_frames, hipMemcpyDeviceToHost, st));
+    MSL_HIP_TRY(hipStreamSynchronize(st));
     return MSL_OK;
     } MSL_ABI_CATCH_INT
 }
@@ -1348,7 +1337,7 @@ int msl_peac_block_stats(int device, const uint16_t *depth, size_t depth_stride_
         if (out_mem == MSL_MEM_HOST) {
             if (bind_device(device) != MSL_OK) return MSL_ERR_NO_DEVICE;
             Scratch &sc = g_scratch[device & 15];
-            PEAC_TRY(grow(sc.cloud, sc.cloudCap, sizeof(double) * 3 * nVert * n_frames));
+            MSL_HIP_TRY(grow(sc.cloud, sc.cloudCap, sizeof(double) * 3 * nVert * n_frames));
             dCloud = (double *)sc.cloud;
         } else {
             dCloud = cloud_out;
@@ -1361,16 +1350,16 @@ int msl_peac_block_stats(int device, const uint16_t *depth, size_t depth_stride_
     // this entry point returns the Stats part only
     std::vector<msl_peac_block> hb(nBlocks * n_frames);
     const hipStream_t st = g_scratch[device & 15].stream;
-    PEAC_TRY(hipMemcpyAsync(hb.data(), dBlocks, sizeof(msl_peac_block) * hb.size(), hipMemcpyDeviceToHost, st));
-    PEAC_TRY(hipStreamSynchronize(st));
+    MSL_HIP_TRY(hipMemcpyAsync(hb.data(), dBlocks, sizeof(msl_peac_block) * hb.size(), hipMemcpyDeviceToHost, st));
+    MSL_HIP_TRY(hipStreamSynchronize(st));
     std::vector<msl_peac_stats> hs(hb.size());
     for (size_t i = 0; i < hb.size(); i++) hs[i] = hb[i].stats;
     if (out_mem == MSL_MEM_HOST) {
         memcpy(stats_out, hs.data(), sizeof(msl_peac_stats) * hs.size());
-        if (cloud_out) { PEAC_TRY(hipMemcpyAsync(cloud_out, dCloud, sizeof(double) * 3 * nVert * n_frames, hipMemcpyDeviceToHost, st)); PEAC_TRY(hipStreamSynchronize(st)); }
+        if (cloud_out) { MSL_HIP_TRY(hipMemcpyAsync(cloud_out, dCloud, sizeof(double) * 3 * nVert * n_frames, hipMemcpyDeviceToHost, st)); MSL_HIP_TRY(hipStreamSynchronize(st)); }
     } else {
-        PEAC_TRY(hipMemcpyAsync(stats_out, hs.data(), sizeof(msl_peac_stats) * hs.size(), hipMemcpyHostToDevice, st));
-        PEAC_TRY(hipStreamSynchronize(st));
+        MSL_HIP_TRY(hipMemcpyAsync(stats_out, hs.data(), sizeof(msl_peac_stats) * hs.size(), hipMemcpyHostToDevice, st));
+        MSL_HIP_TRY(hipStreamSynchronize(st));
     }
     return MSL_OK;
     } MSL_ABI_CATCH_INT
@@ -1426,8 +1415,8 @@ int membership_impl(int device, const uint16_t *depth, size_t depth_stride_bytes
         double *dCloud = nullptr;   // the organised cloud of PlaneDetection::readDepthImage, when the caller wants it (k_peac_cloud)
         if (cloud_out) {
             Scratch &sc0 = g_scratch[device & 15];
-            PEAC_TRY(hipSetDevice(device));
-            PEAC_TRY(grow(sc0.cloud, sc0.cloudCap, sizeof(double) * 3 * (size_t)cw * ch * n_frames));
+            MSL_HIP_TRY(hipSetDevice(device));
+            MSL_HIP_TRY(grow(sc0.cloud, sc0.cloudCap, sizeof(double) * 3 * (size_t)cw * ch * n_frames));
             dCloud = (double *)sc0.cloud;
         }
         int rc = device_fit(device, depth, depth_stride_bytes, frame_stride_bytes, width, height, n_frames, mem, fx, fy, cx, cy, depth_map_factor, *params, dCloud,
@@ -1437,10 +1426,10 @@ int membership_impl(int device, const uint16_t *depth, size_t depth_stride_bytes
         hb.resize(nBlocks * n_frames);
         half.resize((size_t)cw * ch * n_frames);
         const hipStream_t st = g_scratch[device & 15].stream;
-        PEAC_TRY(hipMemcpyAsync(hb.data(), dBlocks, sizeof(msl_peac_block) * hb.size(), hipMemcpyDeviceToHost, st));
-        PEAC_TRY(hipMemcpyAsync(half.data(), dHalf, sizeof(uint16_t) * half.size(), hipMemcpyDeviceToHost, st));
-        if (cloud_out) PEAC_TRY(hipMemcpyAsync(cloud_out, dCloud, sizeof(double) * 3 * (size_t)cw * ch * n_frames, hipMemcpyDeviceToHost, st));
-        PEAC_TRY(hipStreamSynchronize(st));
+        MSL_HIP_TRY(hipMemcpyAsync(hb.data(), dBlocks, sizeof(msl_peac_block) * hb.size(), hipMemcpyDeviceToHost, st));
+        MSL_HIP_TRY(hipMemcpyAsync(half.data(), dHalf, sizeof(uint16_t) * half.size(), hipMemcpyDeviceToHost, st));
+        if (cloud_out) MSL_HIP_TRY(hipMemcpyAsync(cloud_out, dCloud, sizeof(double) * 3 * (size_t)cw * ch * n_frames, hipMemcpyDeviceToHost, st));
+        MSL_HIP_TRY(hipStreamSynchronize(st));
         // Agglomerative clustering on the device (one wave per frame) when a frame's node data fits the LDS and the call is large enough;
         // MSL_PEAC_CLUSTER=host / device forces one side (same results: tests/test_peac_gpu.py runs both).
         const int maxN = 2 * (int)nBlocks, words = (maxN + 31) / 32;
@@ -1466,10 +1455,10 @@ int membership_impl(int device, const uint16_t *depth, size_t depth_stride_bytes
                 const size_t rowsB = sizeof(unsigned) * (size_t)n_frames * maxN * words, gstB = sizeof(double) * 9 * (size_t)n_frames * maxN,
                              gcxyB = sizeof(double) * 2 * (size_t)n_frames * maxN;
                 const size_t outInts = (size_t)n_frames * (1 + 2 * nBlocks), outB = sizeof(int) * ((outInts + 1) & ~(size_t)1) + sizeof(PlaneOut) * (size_t)n_frames * maxPl;
-                PEAC_TRY(grow(sc.rows, sc.rowsCap, rowsB)); PEAC_TRY(grow(sc.gst, sc.gstCap, gstB)); PEAC_TRY(grow(sc.gcxy, sc.gcxyCap, gcxyB));
-                PEAC_TRY(grow(sc.cin, sc.cinCap, sizeof(int) * inInts)); PEAC_TRY(grow(sc.cout, sc.coutCap, outB));
-                PEAC_TRY(hipMemcpyAsync(sc.cin, hIn.data(), sizeof(int) * inInts, hipMemcpyHostToDevice, st));
-                PEAC_TRY(hipMemsetAsync(sc.rows, 0, rowsB, st));
+                MSL_HIP_TRY(grow(sc.rows, sc.rowsCap, rowsB)); MSL_HIP_TRY(grow(sc.gst, sc.gstCap, gstB)); MSL_HIP_TRY(grow(sc.gcxy, sc.gcxyCap, gcxyB));
+                MSL_HIP_TRY(grow(sc.cin, sc.cinCap, sizeof(int) * inInts)); MSL_HIP_TRY(grow(sc.cout, sc.coutCap, outB));
+                MSL_HIP_TRY(hipMemcpyAsync(sc.cin, hIn.data(), sizeof(int) * inInts, hipMemcpyHostToDevice, st));
+                MSL_HIP_TRY(hipMemsetAsync(sc.rows, 0, rowsB, st));
                 ClusterDev C;
                 C.nB = (int)nBlocks; C.maxN = maxN; C.words = words; C.minSupport = params->min_support; C.maxStep = params->max_step; C.maxE = maxE; C.maxPl = maxPl;
                 C.depthSigma = params->depth_sigma; C.stdTolMerge = params->std_tol_merge; C.simMerge = params->similarity_th_merge;
@@ -1481,15 +1470,15 @@ int membership_impl(int device, const uint16_t *depth, size_t depth_stride_bytes
                 C.nPlanes = dOut; C.parent = dOut + n_frames; C.setSize = dOut + n_frames + (size_t)n_frames * nBlocks;
                 C.planes = reinterpret_cast<PlaneOut *>(dOut + ((outInts + 1) & ~(size_t)1));
                 if (!sc.clusterLdsSet) {
-                    PEAC_TRY(hipFuncSetAttribute((const void *)k_peac_cluster, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+                    MSL_HIP_TRY(hipFuncSetAttribute((const void *)k_peac_cluster, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
                     sc.clusterLdsSet = true;
                 }
                 hipLaunchKernelGGL(k_peac_cluster, dim3((unsigned)n_frames), dim3(64), ldsBytes, st, C);
-                PEAC_TRY(hipGetLastError());
+                MSL_HIP_TRY(hipGetLastError());
                 hOutI.resize(outInts); hPlanes.resize((size_t)n_frames * maxPl);
-                PEAC_TRY(hipMemcpyAsync(hOutI.data(), dOut, sizeof(int) * outInts, hipMemcpyDeviceToHost, st));
-                PEAC_TRY(hipMemcpyAsync(hPlanes.data(), C.planes, sizeof(PlaneOut) * hPlanes.size(), hipMemcpyDeviceToHost, st));
-                PEAC_TRY(hipStreamSynchronize(st));
+                MSL_HIP_TRY(hipMemcpyAsync(hOutI.data(), dOut, sizeof(int) * outInts, hipMemcpyDeviceToHost, st));
+                MSL_HIP_TRY(hipMemcpyAsync(hPlanes.data(), C.planes, sizeof(PlaneOut) * hPlanes.size(), hipMemcpyDeviceToHost, st));
+                MSL_HIP_TRY(hipStreamSynchronize(st));
                 usedDevice = true;
                 for (int f = 0; f < n_frames; f++) if (hOutI[f] < 0) usedDevice = false;   // more planes than the hand-over holds: host path for this call
             }

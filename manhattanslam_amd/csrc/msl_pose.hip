@@ -18,7 +18,7 @@
 // last trial it evaluated (nothing recomputes errors when optimize() returns), so the classification evaluates such an edge at that
 // trial's pose, kept in LDS.  Per-edge arithmetic follows tests/pose_model.py operation for operation; only the sums over edges differ
 // in order from g2o's sequential loop.  DESIGN.md section 3 lists what is pinned and what is not.
-#include "msl_common.h"
+#include "msl_match_handle.h"
 
 #include <cfloat>
 #include <cmath>
@@ -624,21 +624,6 @@ __global__ __launch_bounds__(NT) void k_pose(PoseDev P) {
     }
 }
 
-struct Buf { void *p = nullptr; size_t cap = 0; };
-
-struct Scratch { Buf in[16], out[5]; };
-
-hipError_t grow(Buf &b, size_t need) {
-    if (need <= b.cap) return hipSuccess;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr; b.cap = 0;
-    const hipError_t e = hipMalloc(&b.p, need);
-    if (e == hipSuccess) b.cap = need;
-    return e;
-}
-
-#define P_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { set_error("msl_pose_optimize: %s failed: %s", #expr, hipGetErrorString(e_)); return MSL_ERR_HIP; } } while (0)
-
 int run_pose(msl_match *h, int n_frames, int cap, int xcap, int lcap, int pcap, const msl_pose_params *prm, const msl_keypoint *kps,
              const float *un_xy, const float *uright, const int32_t *pt_ref, const int32_t *n_kps, const float *xyz, const double *line_fn,
              const double *line_xyz, const uint8_t *line_has, const int32_t *n_lines, const float *plane_coef, const float *plane_w,
@@ -652,72 +637,34 @@ int run_pose(msl_match *h, int n_frames, int cap, int xcap, int lcap, int pcap, 
                   MAX_LCAP, MAX_PCAP, MSL_MATCH_MAX_LEVELS);
         return MSL_ERR_INVALID;
     }
-    int rc = bind_device(match_device(h));
+    int rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
-    hipStream_t st = match_stream(h);
-    void *&slot = match_pose_scratch(h);
-    if (!slot) slot = new Scratch();
-    Scratch &S = *static_cast<Scratch *>(slot);
+    hipStream_t st = h->stream;
     const size_t F = (size_t)n_frames, n = F * cap, x = F * xcap, l = F * lcap, p = F * pcap;
     PoseDev D{};
     D.cap = cap; D.xcap = xcap; D.lcap = lcap; D.pcap = pcap; D.prm = *prm;
     D.deltaMono = (double)(float)std::sqrt(5.991); D.deltaStereo = (double)(float)std::sqrt(7.815);   // Optimizer.cc:88-89 (const float)
     D.deltaPlane = std::sqrt(prm->plane_chi); D.deltaPlaneVP = std::sqrt(prm->plane_chi_vp);
-    const void *src[16] = {kps, un_xy, uright, pt_ref, n_kps, xyz, line_fn, line_xyz, line_has, n_lines, plane_coef, plane_w, plane_has, n_planes, Tcw,
-                           nullptr};
-    const size_t bytes[16] = {sizeof(msl_keypoint) * n, 8 * n, 4 * n, 4 * n, 4 * F, 12 * x, 24 * l, 48 * l, l, 4 * F, 16 * p, 48 * p, p, 4 * F,
-                              48 * F, 0};
-    const void *dev[16];
-    for (int i = 0; i < 15; i++) {
-        if (mem == MSL_MEM_HOST) {
-            if (bytes[i] > S.in[i].cap) P_TRY(hipStreamSynchronize(st));   // an earlier asynchronous call may still read the buffer about to be replaced
-            P_TRY(grow(S.in[i], bytes[i]));
-            P_TRY(hipMemcpyAsync(S.in[i].p, src[i], bytes[i], hipMemcpyHostToDevice, st));
-            dev[i] = S.in[i].p;
-        } else {
-            dev[i] = src[i];
-        }
-    }
+    const void *src[15] = {kps, un_xy, uright, pt_ref, n_kps, xyz, line_fn, line_xyz, line_has, n_lines, plane_coef, plane_w, plane_has, n_planes, Tcw};
+    const size_t bytes[15] = {sizeof(msl_keypoint) * n, 8 * n, 4 * n, 4 * n, 4 * F, 12 * x, 24 * l, 48 * l, l, 4 * F, 16 * p, 48 * p, p, 4 * F, 48 * F};
+    void *dev[15];
+    MSL_HIP_TRY(stage(src, bytes, 15, 15, mem, h->poseIn, st, dev));
     D.kps = (const msl_keypoint *)dev[0]; D.unxy = (const float *)dev[1]; D.uright = (const float *)dev[2]; D.ptRef = (const int32_t *)dev[3];
     D.nKps = (const int32_t *)dev[4]; D.xyz = (const float *)dev[5]; D.lineFn = (const double *)dev[6]; D.lineXyz = (const double *)dev[7];
     D.lineHas = (const uint8_t *)dev[8]; D.nLines = (const int32_t *)dev[9]; D.planeCoef = (const float *)dev[10]; D.planeW = (const float *)dev[11];
     D.planeHas = (const uint8_t *)dev[12]; D.nPlanes = (const int32_t *)dev[13]; D.Tcw = (const float *)dev[14];
-    uint8_t *io[3] = {outlier, line_outlier, plane_outlier};
-    const size_t ioBytes[3] = {n, l, 3 * p};
-    if (out_mem == MSL_MEM_HOST) {   // (host-output calls end with a sync: nothing in flight reads these)
-        for (int i = 0; i < 3; i++) {
-            P_TRY(grow(S.out[i], ioBytes[i]));
-            P_TRY(hipMemcpyAsync(S.out[i].p, io[i], ioBytes[i], hipMemcpyHostToDevice, st));
-        }
-        P_TRY(grow(S.out[3], 48 * F)); P_TRY(grow(S.out[4], 4 * F));
-        D.outlier = (uint8_t *)S.out[0].p; D.lineOutlier = (uint8_t *)S.out[1].p; D.planeOutlier = (uint8_t *)S.out[2].p;
-        D.TcwOut = (float *)S.out[3].p; D.nGood = (int32_t *)S.out[4].p;
-    } else {
-        D.outlier = outlier; D.lineOutlier = line_outlier; D.planeOutlier = plane_outlier; D.TcwOut = Tcw_out; D.nGood = n_good;
-    }
+    void *out[5] = {outlier, line_outlier, plane_outlier, Tcw_out, n_good}, *dout[5];
+    const size_t outBytes[5] = {n, l, 3 * p, 48 * F, 4 * F};
+    MSL_HIP_TRY(stage(out, outBytes, 5, 3, out_mem, h->poseOut, st, dout));   // the outlier flags are in/out
+    D.outlier = (uint8_t *)dout[0]; D.lineOutlier = (uint8_t *)dout[1]; D.planeOutlier = (uint8_t *)dout[2];
+    D.TcwOut = (float *)dout[3]; D.nGood = (int32_t *)dout[4];
     hipLaunchKernelGGL(k_pose, dim3((unsigned)n_frames), dim3(NT), 0, st, D);
-    P_TRY(hipGetLastError());
-    if (out_mem == MSL_MEM_HOST) {
-        for (int i = 0; i < 3; i++) P_TRY(hipMemcpyAsync(io[i], S.out[i].p, ioBytes[i], hipMemcpyDeviceToHost, st));
-        P_TRY(hipMemcpyAsync(Tcw_out, D.TcwOut, 48 * F, hipMemcpyDeviceToHost, st));
-        P_TRY(hipMemcpyAsync(n_good, D.nGood, 4 * F, hipMemcpyDeviceToHost, st));
-    }
-    if (out_mem == MSL_MEM_HOST || mem == MSL_MEM_HOST) P_TRY(hipStreamSynchronize(st));   // host buffers are the caller's again on return
+    MSL_HIP_TRY(hipGetLastError());
+    MSL_HIP_TRY(finish_call(out, dout, outBytes, 5, mem, out_mem, st));
     return MSL_OK;
 }
-#undef P_TRY
 
 }  // namespace
-
-namespace msl {
-void pose_scratch_free(void *p) {
-    if (!p) return;
-    Scratch *S = static_cast<Scratch *>(p);
-    for (Buf &b : S->in) if (b.p) (void)hipFree(b.p);
-    for (Buf &b : S->out) if (b.p) (void)hipFree(b.p);
-    delete S;
-}
-}  // namespace msl
 
 extern "C" {
 
@@ -739,14 +686,11 @@ int msl_pose_optimize_batch(int device, int n_frames, int cap, int xcap, int lca
                             msl_mem mem, uint8_t *outlier, uint8_t *line_outlier, uint8_t *plane_outlier, float *Tcw_out, int32_t *n_good,
                             msl_mem out_mem) noexcept {
     try {
-    std::lock_guard<std::mutex> lock(match_default_mutex());
-    msl_match *h = match_default_handle(device);
-    if (!h) return MSL_ERR_NO_DEVICE;
-    if (mem == MSL_MEM_DEVICE || out_mem == MSL_MEM_DEVICE) { if (bind_device(device) == MSL_OK) (void)hipStreamSynchronize(0); }   // as msl_match_by_projection_batch
-    int rc = run_pose(h, n_frames, cap, xcap, lcap, pcap, params, kps, un_xy, uright, pt_ref, n_kps, xyz, line_fn, line_xyz, line_has, n_lines,
-                      plane_coef, plane_w, plane_has, n_planes, Tcw, mem, outlier, line_outlier, plane_outlier, Tcw_out, n_good, out_mem);
-    if (rc == MSL_OK) rc = msl_match_sync(h);
-    return rc;
+    // the outlier flags are inputs too: device-memory ones are read as well
+    return on_default_handle(device, mem == MSL_MEM_DEVICE || out_mem == MSL_MEM_DEVICE, [&](msl_match *h) {
+        return run_pose(h, n_frames, cap, xcap, lcap, pcap, params, kps, un_xy, uright, pt_ref, n_kps, xyz, line_fn, line_xyz, line_has, n_lines,
+                        plane_coef, plane_w, plane_has, n_planes, Tcw, mem, outlier, line_outlier, plane_outlier, Tcw_out, n_good, out_mem);
+    });
     } MSL_ABI_CATCH_INT
 }
 

@@ -3,7 +3,7 @@ C ABI, for a batch of independent frame pairs, and of th
 (src/Tracking.cc:1654-1695: isInFrustum + SearchByProjection(Frame&, vector<MapPoint*>, th)) for a batch of frames."""
 import numpy as np
 
-from ._lib import KEYPOINT_DTYPE, LOCAL_MATCH_PARAMS_DTYPE, LOCAL_TRACK_DTYPE, MATCH_PARAMS_DTYPE, MSL_MEM_HOST, check, lib, ptr
+from ._lib import KEYPOINT_DTYPE, LOCAL_MATCH_PARAMS_DTYPE, LOCAL_TRACK_DTYPE, MATCH_PARAMS_DTYPE, MSL_MEM_HOST, call, check, lib, pad, ptr
 
 
 def match_params(frame_params, scale_factors, th, check_orientation=True):
@@ -82,27 +82,27 @@ def search_by_projection_batch(params, cur, last, Tcw_cur, Tcw_last, device=0, h
        Tcw_*: (n_pairs, 4, 4) or (n_pairs, 3, 4) float32, row-major.  Returns (match [n_pairs][N] i32 lists, nmatches)."""
     B = len(cur)
     cap = max(max(len(c["kps"]) for c in cur), max(len(l["xyz"]) for l in last), 1)
-    kps = np.zeros((B, cap), KEYPOINT_DTYPE); un = np.zeros((B, cap, 2), np.float32); ur = np.zeros((B, cap), np.float32)
-    cell = np.full((B, cap), -1, np.int32); cdesc = np.zeros((B, cap, 32), np.uint8); ncur = np.zeros(B, np.int32)
-    xyz = np.zeros((B, cap, 3), np.float32); ldesc = np.zeros((B, cap, 32), np.uint8); flags = np.zeros((B, cap), np.uint8)
-    octv = np.zeros((B, cap), np.int32); ang = np.zeros((B, cap), np.float32); nlast = np.zeros(B, np.int32)
-    for f in range(B):
-        n, m = len(cur[f]["kps"]), len(last[f]["xyz"])
-        ncur[f], nlast[f] = n, m
-        kps[f, :n] = cur[f]["kps"]; un[f, :n] = cur[f]["un_xy"]; ur[f, :n] = cur[f]["uright"]; cell[f, :n] = cur[f]["grid_cell"]
-        cdesc[f, :n] = cur[f]["desc"]
-        xyz[f, :m] = last[f]["xyz"]; ldesc[f, :m] = last[f]["desc"]; flags[f, :m] = last[f]["flags"]; octv[f, :m] = last[f]["octave"]
-        ang[f, :m] = last[f]["angle"]
-    tc = np.ascontiguousarray(np.asarray(Tcw_cur, np.float32)[:, :3, :4].reshape(B, 12))
-    tl = np.ascontiguousarray(np.asarray(Tcw_last, np.float32)[:, :3, :4].reshape(B, 12))
+    arrays = _pack_cur(cur, cap) + [
+        pad(last, "xyz", cap, np.float32, shape=(3,)), pad(last, "desc", cap, np.uint8, shape=(32,)), pad(last, "flags", cap, np.uint8),
+        pad(last, "octave", cap, np.int32), pad(last, "angle", cap, np.float32), np.array([len(l["xyz"]) for l in last], np.int32),
+        _rows3x4(Tcw_cur, B), _rows3x4(Tcw_last, B)]
     match = np.zeros((B, cap), np.int32); nm = np.zeros(B, np.int32)
-    args = (B, cap, ptr(params), ptr(kps), ptr(un), ptr(ur), ptr(cell), ptr(cdesc), ptr(ncur), ptr(xyz), ptr(ldesc), ptr(flags), ptr(octv), ptr(ang),
-            ptr(nlast), ptr(tc), ptr(tl), MSL_MEM_HOST, ptr(match), ptr(nm), MSL_MEM_HOST)
-    if handle is not None:
-        check(lib.msl_match_by_projection(handle.h, *args), "msl_match_by_projection")
-    else:
-        check(lib.msl_match_by_projection_batch(device, *args), "msl_match_by_projection_batch")
+    call("msl_match_by_projection", handle, device, B, cap, ptr(params), *[ptr(a) for a in arrays], MSL_MEM_HOST, ptr(match), ptr(nm),
+         MSL_MEM_HOST)
+    ncur = arrays[5]
     return [match[f, :ncur[f]].copy() for f in range(B)], nm
+
+
+def _pack_cur(cur, cap):
+    """cur_kps .. n_cur, the current-frame arrays both searches take."""
+    return [pad(cur, "kps", cap, KEYPOINT_DTYPE), pad(cur, "un_xy", cap, np.float32, shape=(2,)), pad(cur, "uright", cap, np.float32),
+            pad(cur, "grid_cell", cap, np.int32, -1), pad(cur, "desc", cap, np.uint8, shape=(32,)),
+            np.array([len(c["kps"]) for c in cur], np.int32)]
+
+
+def _rows3x4(Tcw, n_frames):
+    """Rows 0-2 of each (4, 4) or (3, 4) mTcw, as the ABI's [frames][12] float32."""
+    return np.ascontiguousarray(np.asarray(Tcw, np.float32)[:, :3, :4].reshape(n_frames, 12))
 
 
 def descriptor_distance(a, b, device=0):
@@ -117,22 +117,13 @@ def pack_local_points(cur, local, Tcw, cap=None, mcap=None):
        cur:   kps (KEYPOINT_DTYPE), un_xy (N,2) f32, uright (N,) f32, grid_cell (N,) i32, desc (N,32) u8, flags (N,) u8
        local: xyz (M,3) f32, normal (M,3) f32, dist (M,2) f32 (mfMinDistance, mfMaxDistance), desc (M,32) u8, flags (M,) u8
        Tcw:   (n_frames, 4, 4) or (n_frames, 3, 4) float32, row-major."""
-    B = len(cur)
     cap = cap or max(max(len(c["kps"]) for c in cur), 1)
     mcap = mcap or max(max(len(l["xyz"]) for l in local), 1)
-    kps = np.zeros((B, cap), KEYPOINT_DTYPE); un = np.zeros((B, cap, 2), np.float32); ur = np.zeros((B, cap), np.float32)
-    cell = np.full((B, cap), -1, np.int32); cdesc = np.zeros((B, cap, 32), np.uint8); ncur = np.zeros(B, np.int32); cfl = np.zeros((B, cap), np.uint8)
-    xyz = np.zeros((B, mcap, 3), np.float32); nrm = np.zeros((B, mcap, 3), np.float32); dist = np.zeros((B, mcap, 2), np.float32)
-    mdesc = np.zeros((B, mcap, 32), np.uint8); mfl = np.zeros((B, mcap), np.uint8); nloc = np.zeros(B, np.int32)
-    for f in range(B):
-        n, m = len(cur[f]["kps"]), len(local[f]["xyz"])
-        ncur[f], nloc[f] = n, m
-        kps[f, :n] = cur[f]["kps"]; un[f, :n] = cur[f]["un_xy"]; ur[f, :n] = cur[f]["uright"]; cell[f, :n] = cur[f]["grid_cell"]
-        cdesc[f, :n] = cur[f]["desc"]; cfl[f, :n] = cur[f]["flags"]
-        xyz[f, :m] = local[f]["xyz"]; nrm[f, :m] = local[f]["normal"]; dist[f, :m] = local[f]["dist"]; mdesc[f, :m] = local[f]["desc"]
-        mfl[f, :m] = local[f]["flags"]
-    tc = np.ascontiguousarray(np.asarray(Tcw, np.float32)[:, :3, :4].reshape(B, 12))
-    return cap, mcap, [kps, un, ur, cell, cdesc, ncur, cfl, xyz, nrm, dist, mdesc, mfl, nloc, tc]
+    return cap, mcap, _pack_cur(cur, cap) + [
+        pad(cur, "flags", cap, np.uint8),
+        pad(local, "xyz", mcap, np.float32, shape=(3,)), pad(local, "normal", mcap, np.float32, shape=(3,)),
+        pad(local, "dist", mcap, np.float32, shape=(2,)), pad(local, "desc", mcap, np.uint8, shape=(32,)), pad(local, "flags", mcap, np.uint8),
+        np.array([len(l["xyz"]) for l in local], np.int32), _rows3x4(Tcw, len(cur))]
 
 
 def search_local_points_batch(params, cur, local, Tcw, device=0, handle=None, cap=None, mcap=None):
@@ -143,11 +134,8 @@ def search_local_points_batch(params, cur, local, Tcw, device=0, handle=None, ca
     B = len(cur)
     match = np.zeros((B, cap), np.int32); ntm = np.zeros(B, np.int32); nm = np.zeros(B, np.int32)
     inv = np.zeros((B, mcap), np.uint8); trk = np.zeros((B, mcap), LOCAL_TRACK_DTYPE)
-    args = (B, cap, mcap, ptr(params), *[ptr(a) for a in arrays], MSL_MEM_HOST, ptr(match), ptr(ntm), ptr(nm), ptr(inv), ptr(trk), MSL_MEM_HOST)
-    if handle is not None:
-        check(lib.msl_match_local_points(handle.h, *args), "msl_match_local_points")
-    else:
-        check(lib.msl_match_local_points_batch(device, *args), "msl_match_local_points_batch")
+    call("msl_match_local_points", handle, device, B, cap, mcap, ptr(params), *[ptr(a) for a in arrays], MSL_MEM_HOST, ptr(match), ptr(ntm), ptr(nm),
+         ptr(inv), ptr(trk), MSL_MEM_HOST)
     ncur, nloc = arrays[5], arrays[12]
     return ([match[f, :ncur[f]].copy() for f in range(B)], ntm, nm, [inv[f, :nloc[f]].copy() for f in range(B)],
             [trk[f, :nloc[f]].copy() for f in range(B)])

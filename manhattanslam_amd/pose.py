@@ -6,7 +6,7 @@ of independent frames.  A frame is a dict of numpy arrays -- the per-frame input
   plane_outlier / par_outlier / ver_outlier (M,) u8, Tcw (12,) f32 (rows 0-2 of mTcw)."""
 import numpy as np
 
-from ._lib import KEYPOINT_DTYPE, MSL_MEM_HOST, POSE_PARAMS_DTYPE, check, lib, ptr
+from ._lib import KEYPOINT_DTYPE, MSL_MEM_HOST, POSE_PARAMS_DTYPE, call, check, lib, pad, ptr
 
 KINDS = ("plane", "par", "ver")
 
@@ -34,24 +34,21 @@ def pack(frames, cap=None, xcap=None, lcap=None, pcap=None):
     lcap = lcap or max(max(len(f["line_has"]) for f in frames), 1)
     pcap = pcap or max(max(len(f["plane_coef"]) for f in frames), 1)
     kps = np.zeros((F, cap), KEYPOINT_DTYPE)
-    un = np.zeros((F, cap, 2), np.float32); ur = np.full((F, cap), -1, np.float32); ref = np.full((F, cap), -1, np.int32)
-    nk = np.zeros(F, np.int32); xyz = np.zeros((F, xcap, 3), np.float32)
-    lfn = np.zeros((F, lcap, 3)); lxyz = np.zeros((F, lcap, 6)); lhas = np.zeros((F, lcap), np.uint8); nl = np.zeros(F, np.int32)
-    pc = np.zeros((F, pcap, 4), np.float32); pw = np.zeros((F, pcap, 3, 4), np.float32); phas = np.zeros((F, pcap), np.uint8)
-    npl = np.zeros(F, np.int32); T = np.zeros((F, 12), np.float32)
-    out = np.zeros((F, cap), np.uint8); lout = np.zeros((F, lcap), np.uint8); pout = np.zeros((F, pcap, 3), np.uint8)
+    kps["octave"] = pad(frames, "octave", cap, np.int32)
+    phas = np.zeros((F, pcap), np.uint8)
     for f, fr in enumerate(frames):
-        n, x, l, m = len(fr["pt_ref"]), len(fr["xyz"]), len(fr["line_has"]), len(fr["plane_coef"])
-        kps["octave"][f, :n] = fr["octave"]; un[f, :n] = fr["un_xy"]; ur[f, :n] = fr["uright"]; ref[f, :n] = fr["pt_ref"]; nk[f] = n
-        xyz[f, :x] = fr["xyz"]; out[f, :n] = fr["outlier"]
-        lfn[f, :l] = fr["line_fn"]; lxyz[f, :l] = fr["line_xyz"]; lhas[f, :l] = fr["line_has"]; lout[f, :l] = fr["line_outlier"]; nl[f] = l
-        pc[f, :m] = fr["plane_coef"]; npl[f] = m
         for s, k in enumerate(KINDS):
-            pw[f, :m, s] = fr[k + "_w"]
-            phas[f, :m] |= (np.asarray(fr[k + "_has"], np.uint8) != 0).astype(np.uint8) << s
-            pout[f, :m, s] = fr[k + "_outlier"]
-        T[f] = fr["Tcw"]
-    return (cap, xcap, lcap, pcap), [kps, un, ur, ref, nk, xyz, lfn, lxyz, lhas, nl, pc, pw, phas, npl, T], [out, lout, pout]
+            phas[f, :len(fr["plane_coef"])] |= (np.asarray(fr[k + "_has"], np.uint8) != 0).astype(np.uint8) << s
+    count = lambda key: np.array([len(fr[key]) for fr in frames], np.int32)
+    kinds = lambda suffix, dtype, shape=(): np.stack([pad(frames, k + suffix, pcap, dtype, shape=shape) for k in KINDS], 2)   # [frames][pcap][3 ...]
+    inputs = [kps, pad(frames, "un_xy", cap, np.float32, shape=(2,)), pad(frames, "uright", cap, np.float32, -1),
+              pad(frames, "pt_ref", cap, np.int32, -1), count("pt_ref"), pad(frames, "xyz", xcap, np.float32, shape=(3,)),
+              pad(frames, "line_fn", lcap, np.float64, shape=(3,)), pad(frames, "line_xyz", lcap, np.float64, shape=(6,)),
+              pad(frames, "line_has", lcap, np.uint8), count("line_has"),
+              pad(frames, "plane_coef", pcap, np.float32, shape=(4,)), kinds("_w", np.float32, (4,)), phas, count("plane_coef"),
+              np.array([fr["Tcw"] for fr in frames], np.float32)]
+    io = [pad(frames, "outlier", cap, np.uint8), pad(frames, "line_outlier", lcap, np.uint8), kinds("_outlier", np.uint8)]
+    return (cap, xcap, lcap, pcap), inputs, io
 
 
 def unpack(frames, io, Tcw_out, n_good):
@@ -74,12 +71,8 @@ def pose_optimization_batch(params, frames, device=0, handle=None, caps=None):
     F = len(frames)
     Tout = np.zeros((F, 12), np.float32)
     ng = np.zeros(F, np.int32)
-    args = [F, cap, xcap, lcap, pcap, ptr(params)] + [ptr(a) for a in arrays] + [MSL_MEM_HOST] + [ptr(a) for a in io] + \
-        [ptr(Tout), ptr(ng), MSL_MEM_HOST]
-    if handle is not None:
-        check(lib.msl_pose_optimize(handle.h, *args), "msl_pose_optimize")
-    else:
-        check(lib.msl_pose_optimize_batch(device, *args), "msl_pose_optimize_batch")
+    call("msl_pose_optimize", handle, device, F, cap, xcap, lcap, pcap, ptr(params), *[ptr(a) for a in arrays], MSL_MEM_HOST,
+         *[ptr(a) for a in io], ptr(Tout), ptr(ng), MSL_MEM_HOST)
     return unpack(frames, io, Tout, ng)
 
 

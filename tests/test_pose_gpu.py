@@ -144,6 +144,41 @@ def test_device_form_chained_from_local_map_search():
     m.close()
 
 
+def test_one_handle_grows_its_buffers_across_stages(oracle):
+    """One Matcher and host-form calls only: last-frame matching, local-map matching and pose optimisation take turns on it, and every call
+    is larger (cap / mcap / xcap) than the last call of its kind, so each one grows buffers of the shared handle.  Every result is the
+    oracle's or the sequential model's."""
+    from manhattanslam_amd import MATCH_PARAMS_DTYPE, match, pose
+    from manhattanslam_amd.match import Matcher
+    from tests import match_scenes as ms
+    from tests import oracle_lib
+    from tests.test_local_match_gpu import _check as check_local
+    c = ps.params()
+    pp, pl, pbp = pose.pose_params(c), ls.params(3.0), ms.params(None, 15, True, dtype=MATCH_PARAMS_DTYPE)
+    caps = {"projection": [], "local": [], "pose": []}
+    m = Matcher()
+    for r, (n_cur, n_local, n_pts) in enumerate(((200, 300, 80), (600, 1500, 400), (1016, 4000, 1500))):
+        pairs = [ms.random_pair(400 + 10 * r + j, pbp, n_cur=n_cur - 40 * j, n_last=n_cur - 60 * j) for j in range(2)]
+        cur = [q[0] for q in pairs]; last = [q[1] for q in pairs]; Tc = np.stack([q[2] for q in pairs]); Tl = np.stack([q[3] for q in pairs])
+        caps["projection"].append(max(max(len(x["kps"]) for x in cur), max(len(x["xyz"]) for x in last)))
+        got, nm = m.search_by_projection_batch(pbp, cur, last, Tc, Tl)
+        for f in range(2):
+            want, n = oracle_lib.search_by_projection(pbp, cur[f], last[f], Tc[f], Tl[f])
+            assert nm[f] == n and np.array_equal(got[f], want), (r, f)
+
+        frames = [ls.random_frame(420 + 10 * r + j, pl, n_cur=n_cur - 30 * j, n_local=n_local - 100 * j) for j in range(2)]
+        cur = [x for x, _, _ in frames]; local = [l for _, l, _ in frames]; T = np.stack([t for _, _, t in frames])
+        caps["local"].append(match.pack_local_points(cur, local, T)[:2])
+        assert check_local(pl, cur, local, T, m.search_local_points_batch(pl, cur, local, T)) > 0
+
+        frames = [ps.scene(440 + 10 * r + j, n_pts=n_pts - 20 * j, n_lines=4 * (r + 1), n_planes=r + 1, c=c)[0] for j in range(2)]
+        caps["pose"].append(pose.pack(frames)[0])
+        _check(c, frames, pose.pose_optimization_batch(pp, frames, handle=m))
+    m.close()
+    for kind, seq in caps.items():                                                   # the premise: every call grew the handle's buffers
+        assert all(np.all(np.greater(b, a)) for a, b in zip(seq, seq[1:])), (kind, seq)
+
+
 @pytest.mark.parametrize("what", ["cap", "xcap", "lcap", "pcap", "nlevels"])
 def test_limits_are_refused_without_a_launch(what):
     from manhattanslam_amd import MslError, pose
