@@ -439,6 +439,83 @@ MSL_API int msl_match_local_points_batch(int device, int n_frames, int cap, int 
                                          int32_t *match_out, int32_t *n_to_match, int32_t *nmatches, uint8_t *in_view,
                                          msl_local_track *track, msl_mem out_mem) MSL_NOEXCEPT;
 
+/* ---- Matching map lines: LSDmatcher::SearchByProjection, both overloads (src/LSDmatcher.cpp:21-198) ----
+ * Keylines come from the caller (LSD / LBD extraction is not part of this library).  Current frame, `lcap` entries per frame, keyline
+ * j < n_cur_lines[f]:  cur_kl[j] = mvKeylinesUn[j] (pt.x, pt.y, angle, octave), cur_ldesc[32 j..] = mLdesc.row(j).
+ * Both calls return match_out[f * lcap + j] = the index of the line this call wrote last into CurrentFrame.mvpMapLines[j], or -1, and
+ * nmatches[f] = the function's return value (every accepted line counts, overwritten ones included).  The greedy, order-dependent hand-out
+ * (a keyline held by a line with Observations() > 0 is skipped, later lines overwrite earlier ones) is reproduced exactly.
+ * Optional pose-layout outputs (NULL = not wanted, out_mem like match_out): line_xyz[6 j..] (double) and line_has[j] exactly as
+ * msl_pose_optimize reads them.  A slot the call writes gets the writer's world position, copied bit for bit, and line_has = 1.
+ * msl_match_lines_by_projection also sets line_has = 0 for every other j < n_cur_lines[f] (its entry state is all NULL);
+ * msl_match_local_lines leaves every other slot as it was.  Other bytes are not touched.
+ * Asynchronous on the handle's stream when inputs and outputs are device memory; with host memory on either side it returns when the
+ * caller's buffers are its own again (as msl_match_by_projection).  Limits: lcap <= 256, llcap <= 256, mlcap <= 32768,
+ * nlevels <= MSL_MATCH_MAX_LEVELS; larger values are refused with MSL_ERR_INVALID before any launch. */
+typedef struct msl_keyline {
+    float x, y;                       /* KeyLine::pt */
+    float angle;                      /* KeyLine::angle */
+    int32_t octave;                   /* KeyLine::octave */
+} msl_keyline;
+typedef struct msl_line_match_params {
+    msl_match_params base;            /* fx..cy, bf, image bounds, th (15 last frame; 1, or 5 after a relocalisation, local map), nlevels,
+                                         scale_factors; check_orientation unused */
+    float log_scale_factor;           /* Frame::mfLogScaleFactor (local map only) */
+    float view_cos_limit;             /* isInFrustum's viewingCosLimit (0.6 at the call site; local map only) */
+    float nn_ratio;                   /* LSDmatcher::mfNNratio (0.6, the constructor's default) */
+} msl_line_match_params;
+typedef struct msl_line_track {
+    float proj_x1, proj_y1, proj_x2, proj_y2;   /* mTrackProjX1, mTrackProjY1, mTrackProjX2, mTrackProjY2 */
+    int32_t scale_level;              /* mnTrackScaleLevel (MapLine::PredictScale is not clamped) */
+    float view_cos;                   /* mTrackViewCos */
+} msl_line_track;
+/* msl_match_lines_by_projection: n_frames independent calls of
+ *     int LSDmatcher::SearchByProjection(Frame &CurrentFrame, const Frame &LastFrame, const float th)   (src/LSDmatcher.cpp:21-134)
+ * with Frame::GetLinesInArea (src/Frame.cc:384-415).  CurrentFrame.mvpMapLines is all NULL on entry (src/Tracking.cc:1255).
+ * Last frame, `llcap` entries per frame, line i < n_last_lines[f]:
+ *   last_line_xyz[6 i..]  mvpMapLines[i]->GetWorldPos() (Vector6d)        last_ldesc[32 i..]  ->GetDescriptor()
+ *   last_line_flags[i]    bit 0: mvpMapLines[i] && !isBad() && !mvbLineOutlier[i]; bit 1: ->Observations() > 0
+ *   last_line_octave[i]   LastFrame.mvKeylinesUn[i].octave (clamped to [0, nlevels) for the mvScaleFactors lookup)
+ * Tcw_cur / Tcw_last as for msl_match_by_projection. */
+MSL_API int msl_match_lines_by_projection(msl_match *h, int n_frames, int lcap, int llcap, const msl_line_match_params *params,
+                                          const msl_keyline *cur_kl, const uint8_t *cur_ldesc, const int32_t *n_cur_lines,
+                                          const double *last_line_xyz, const uint8_t *last_ldesc, const uint8_t *last_line_flags,
+                                          const int32_t *last_line_octave, const int32_t *n_last_lines, const float *Tcw_cur,
+                                          const float *Tcw_last, msl_mem mem, int32_t *match_out, int32_t *nmatches, double *line_xyz,
+                                          uint8_t *line_has, msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device handle, always synchronous; see msl_match_by_projection_batch). */
+MSL_API int msl_match_lines_by_projection_batch(int device, int n_frames, int lcap, int llcap, const msl_line_match_params *params,
+                                                const msl_keyline *cur_kl, const uint8_t *cur_ldesc, const int32_t *n_cur_lines,
+                                                const double *last_line_xyz, const uint8_t *last_ldesc, const uint8_t *last_line_flags,
+                                                const int32_t *last_line_octave, const int32_t *n_last_lines, const float *Tcw_cur,
+                                                const float *Tcw_last, msl_mem mem, int32_t *match_out, int32_t *nmatches, double *line_xyz,
+                                                uint8_t *line_has, msl_mem out_mem) MSL_NOEXCEPT;
+/* msl_match_local_lines: Tracking::SearchLocalLines (src/Tracking.cc:1697-1737) after its first loop -- Frame::isInFrustum(pML,
+ * view_cos_limit) (src/Frame.cc:261-327) with MapLine::PredictScale (src/MapLine.cpp:320-328) for every candidate local map line, then
+ *     int LSDmatcher::SearchByProjection(Frame &F, const vector<MapLine*> &vpMapLines, th)   (src/LSDmatcher.cpp:137-198)
+ * with RadiusByViewingCos (:252-257) when nToMatch > 0.  Current frame: the arrays above plus
+ *   cur_line_flags[j]  state of F.mvpMapLines[j] after the first loop: bit 0: held, bit 1: the holder has Observations() > 0
+ * Local map lines (mvpLocalMapLines in order, `mlcap` entries per frame), line i < n_local_lines[f]:
+ *   ml_xyz[6 i..]  GetWorldPos() (double)            ml_normal[3 i..]  GetNormal() (double)
+ *   ml_dist[2 i..] mfMinDistance, mfMaxDistance (raw: the 0.8f / 1.2f invariance factors are applied inside)
+ *   ml_desc[32 i..] GetDescriptor()                   ml_flags[i]  bit 0: candidate (!isBad() && mnLastFrameSeen != F.mnId),
+ *                                                                  bit 1: Observations() > 0
+ * Tcw: rows 0-2 of the CV_32F mTcw (12 floats); mOw is derived from it.  Out: n_to_match[f] = nToMatch, and optionally in_view[f * mlcap + i]
+ * = mbTrackInView and track[f * mlcap + i] = the tracking fields isInFrustum sets (all zero for lines not in view). */
+MSL_API int msl_match_local_lines(msl_match *h, int n_frames, int lcap, int mlcap, const msl_line_match_params *params,
+                                  const msl_keyline *cur_kl, const uint8_t *cur_ldesc, const int32_t *n_cur_lines, const uint8_t *cur_line_flags,
+                                  const double *ml_xyz, const double *ml_normal, const float *ml_dist, const uint8_t *ml_desc,
+                                  const uint8_t *ml_flags, const int32_t *n_local_lines, const float *Tcw, msl_mem mem, int32_t *match_out,
+                                  int32_t *n_to_match, int32_t *nmatches, uint8_t *in_view, msl_line_track *track, double *line_xyz,
+                                  uint8_t *line_has, msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device handle, always synchronous; see msl_match_by_projection_batch). */
+MSL_API int msl_match_local_lines_batch(int device, int n_frames, int lcap, int mlcap, const msl_line_match_params *params,
+                                        const msl_keyline *cur_kl, const uint8_t *cur_ldesc, const int32_t *n_cur_lines,
+                                        const uint8_t *cur_line_flags, const double *ml_xyz, const double *ml_normal, const float *ml_dist,
+                                        const uint8_t *ml_desc, const uint8_t *ml_flags, const int32_t *n_local_lines, const float *Tcw,
+                                        msl_mem mem, int32_t *match_out, int32_t *n_to_match, int32_t *nmatches, uint8_t *in_view,
+                                        msl_line_track *track, double *line_xyz, uint8_t *line_has, msl_mem out_mem) MSL_NOEXCEPT;
+
 /* ---- Pose-only optimisation: Optimizer::PoseOptimization (src/Optimizer.cc:53-590) ----
  * n_frames independent calls of  int Optimizer::PoseOptimization(Frame *pFrame)  for an Optimizer(angleInfo, disInfo, parInfo, verInfo,
  * planeChi, planeChiVP, aTh, parTh), with every edge type it creates: mono / stereo point edges, the two endpoint edges of a line, and

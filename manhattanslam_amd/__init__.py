@@ -12,5 +12,6 @@ from . import peac  # noqa: F401
 from ._lib import PEAC_STATS_DTYPE  # noqa: F401
 from . import match  # noqa: F401
 from ._lib import MATCH_PARAMS_DTYPE, LOCAL_MATCH_PARAMS_DTYPE, LOCAL_TRACK_DTYPE  # noqa: F401
+from ._lib import LINE_MATCH_PARAMS_DTYPE, KEYLINE_DTYPE, LINE_TRACK_DTYPE  # noqa: F401
 from . import pose  # noqa: F401
 from ._lib import POSE_PARAMS_DTYPE  # noqa: F401

@@ -34,6 +34,9 @@ MATCH_PARAMS_DTYPE = np.dtype([(n, "<f4") for n in ("fx", "fy", "cx", "cy", "bf"
                               [("check_orientation", "<i4"), ("nlevels", "<i4"), ("scale_factors", "<f4", (16,))])
 LOCAL_MATCH_PARAMS_DTYPE = np.dtype(MATCH_PARAMS_DTYPE.descr + [(n, "<f4") for n in ("log_scale_factor", "view_cos_limit", "nn_ratio")])   # msl_local_match_params
 LOCAL_TRACK_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr", "<f4"), ("scale_level", "<i4"), ("view_cos", "<f4")])       # msl_local_track
+LINE_MATCH_PARAMS_DTYPE = LOCAL_MATCH_PARAMS_DTYPE                                                                                            # msl_line_match_params
+KEYLINE_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("angle", "<f4"), ("octave", "<i4")])                                                 # msl_keyline
+LINE_TRACK_DTYPE = np.dtype([(n, "<f4") for n in ("proj_x1", "proj_y1", "proj_x2", "proj_y2")] + [("scale_level", "<i4"), ("view_cos", "<f4")])   # msl_line_track
 POSE_PARAMS_DTYPE = np.dtype([(n, "<f4") for n in ("fx", "fy", "cx", "cy", "bf")] + [("nlevels", "<i4"), ("inv_level_sigma2", "<f4", (16,))] +
                              [(n, "<f8") for n in ("angle_info", "dis_info", "par_info", "ver_info", "plane_chi", "plane_chi_vp", "a_th",
                                                    "par_th")])                                                                        # msl_pose_params
@@ -96,6 +99,10 @@ SIGNATURES = {
     "msl_match_descriptor_distances": (_i, [_vp, _vp, _vp, _i, _vp]),
     "msl_match_local_points": (_i, [_vp, _i, _i, _i] + [_vp] * 15 + [_i] + [_vp] * 5 + [_i]),
     "msl_match_local_points_batch": (_i, [_i, _i, _i, _i] + [_vp] * 15 + [_i] + [_vp] * 5 + [_i]),
+    "msl_match_lines_by_projection": (_i, [_vp, _i, _i, _i] + [_vp] * 11 + [_i] + [_vp] * 4 + [_i]),
+    "msl_match_lines_by_projection_batch": (_i, [_i, _i, _i, _i] + [_vp] * 11 + [_i] + [_vp] * 4 + [_i]),
+    "msl_match_local_lines": (_i, [_vp, _i, _i, _i] + [_vp] * 12 + [_i] + [_vp] * 7 + [_i]),
+    "msl_match_local_lines_batch": (_i, [_i, _i, _i, _i] + [_vp] * 12 + [_i] + [_vp] * 7 + [_i]),
     "msl_pose_optimize": (_i, [_vp, _i, _i, _i, _i, _i] + [_vp] * 16 + [_i] + [_vp] * 5 + [_i]),
     "msl_pose_optimize_batch": (_i, [_i, _i, _i, _i, _i, _i] + [_vp] * 16 + [_i] + [_vp] * 5 + [_i]),
     "msl_sf_fuse_resident": (_i, [_vp, _i, _vp, _sz, _vp, _sz, _vp, _sz, _i, _vp]),

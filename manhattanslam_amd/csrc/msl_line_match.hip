@@ -1,0 +1,450 @@
+// msl_line_match.hip -- batched map-line matching by projection for gfx950: both overloads of LSDmatcher::SearchByProjection.
+//
+// msl_match_lines_by_projection  LSDmatcher::SearchByProjection(Frame &CurrentFrame, const Frame &LastFrame, th)  (reference src/LSDmatcher.cpp:21-134)
+// msl_match_local_lines          Tracking::SearchLocalLines after its first loop (src/Tracking.cc:1697-1737): Frame::isInFrustum(MapLine*)
+//                                (src/Frame.cc:261-327) + MapLine::PredictScale (src/MapLine.cpp:320-328), then
+//                                LSDmatcher::SearchByProjection(Frame &F, const vector<MapLine*> &, th)  (src/LSDmatcher.cpp:137-198)
+// both with Frame::GetLinesInArea (src/Frame.cc:384-415), a brute-force scan over the frame's keylines (no grid).
+//
+// Frame batched, two launches per call; the two searches share the candidate test and the assignment and differ in their query:
+//   k_line_query   one lane per line (last-frame line or local map line): the window of the line -- projected endpoints, radius, octave range --
+//                  stored as a LineQ.  last_query: the endpoint projection, th * mvScaleFactors[nLastOctave], the forward / backward / both-ways
+//                  octave range of the frame pair (search_mode).  local_query: isInFrustum (writes mbTrackInView and the track record), then
+//                  RadiusByViewingCos * th * mvScaleFactors[level], octaves [level - 1, level].
+//   k_line_assign  one workgroup per frame: the frame's keylines (16 B) and descriptors (32 B) staged once in LDS (12 KB at lcap = 256); every
+//                  line scans them against its window (GetLinesInArea) and the reference's greedy hand-out is solved as the min-fixpoint of
+//                  k_local_assign (argument below); then holder / nmatches / nToMatch and the pose-layout line_xyz / line_has.
+// Arithmetic follows the reference's float / double mix literally (DESIGN.md section 3 lists the pins); gemm3, search_mode, hamming256 and
+// predict_level are the point matcher's (msl_match_math.h).
+#include "msl_match_handle.h"
+#include "msl_match_math.h"
+
+#include <climits>
+#include <mutex>
+
+using namespace msl;
+
+namespace {
+
+constexpr int TH_HIGH = 100;                       // src/LSDmatcher.cpp:15
+constexpr int MAX_LCAP = 256, MAX_LLCAP = 256, MAX_MLCAP = 32768;
+constexpr int LINE_NT = 1024;
+constexpr int T_FREE = 0x7FFFFFFF;                 // t(k): no line with observations picks keyline k
+constexpr unsigned K_NONE = 0xFFFFFFFFu;
+
+// The GetLinesInArea call of one line: endpoints, radius and octave range.  ok == 0: the line has no window (skipped before the call).
+struct LineQ {
+    float x1, y1, x2, y2, r;
+    int minLevel, maxLevel, ok;
+};
+
+struct LineDev {
+    int lcap, ncap;                                 // keylines per frame; lines per frame (llcap or mlcap)
+    msl_line_match_params prm;
+    float mb;                                       // mbf / fx (last-frame search)
+    const msl_keyline *curKl; const uint8_t *curDesc; const int32_t *nCur; const uint8_t *curFlags;   // curFlags: local search only
+    const double *xyz; const uint8_t *desc, *flags; const int32_t *nLines;                          // the lines (last frame or local map)
+    const int32_t *octave;                                                                           // last-frame search only
+    const double *normal; const float *dist;                                                         // local search only
+    const float *TcwCur, *TcwLast;
+    LineQ *q;                                       // [n][ncap] scratch written by k_line_query
+    uint8_t *inView; msl_line_track *track;         // [n][mlcap] scratch (local search)
+    uint8_t *inViewOut; msl_line_track *trackOut;   // the caller's device arrays (or nullptr)
+    int32_t *matchOut, *nmatches, *nToMatch;
+    double *lineXyz; uint8_t *lineHas;              // optional, [n][lcap] in msl_pose_optimize's layout
+};
+
+__device__ __forceinline__ int clamp_level(int l, int nlevels) { return l < 0 ? 0 : (l >= nlevels ? nlevels - 1 : l); }
+__device__ __forceinline__ int wrap_add(int a, int b) { return (int)((unsigned)a + (unsigned)b); }   // x86-64's int wrap, without UB
+
+// The endpoint projection both searches share (src/LSDmatcher.cpp:43-79 = src/Frame.cc:264-297): the Vector6d converted to float as
+// Mat_<float> << does, Rcw * P + tcw through cv::gemm's float kernel, both depths tested before projecting (Z == 0 passes), u / v left to
+// right without contraction, bounds tests that a NaN passes.
+__device__ __forceinline__ bool project_line(const msl_match_params &b, const float *Tc, const double *P, float SP[3], float EP[3], LineQ &q) {
+    const float tcw[3] = {Tc[3], Tc[7], Tc[11]};
+    for (int k = 0; k < 3; k++) { SP[k] = (float)P[k]; EP[k] = (float)P[3 + k]; }
+    float SPc[3], EPc[3];
+    gemm3(Tc, false, 1.0, SP, tcw, SPc);
+    gemm3(Tc, false, 1.0, EP, tcw, EPc);
+    if (SPc[2] < 0.0f || EPc[2] < 0.0f) return false;
+    const float invz1 = 1.0f / SPc[2];
+    const float u1 = b.fx * SPc[0] * invz1 + b.cx;
+    const float v1 = b.fy * SPc[1] * invz1 + b.cy;
+    if (u1 < b.minX || u1 > b.maxX) return false;
+    if (v1 < b.minY || v1 > b.maxY) return false;
+    const float invz2 = 1.0f / EPc[2];
+    const float u2 = b.fx * EPc[0] * invz2 + b.cx;
+    const float v2 = b.fy * EPc[1] * invz2 + b.cy;
+    if (u2 < b.minX || u2 > b.maxX) return false;
+    if (v2 < b.minY || v2 > b.maxY) return false;
+    q.x1 = u1; q.y1 = v1; q.x2 = u2; q.y2 = v2;
+    return true;
+}
+
+// last-frame line i (src/LSDmatcher.cpp:37-91)
+__device__ __forceinline__ bool last_query(const LineDev &D, int f, int i, LineQ &q) {
+    const size_t ii = (size_t)f * D.ncap + i;
+    if (!(D.flags[ii] & 1)) return false;                                   // :40 NULL, bad or an outlier
+    const float *Tc = D.TcwCur + (size_t)f * 12;
+    float SP[3], EP[3];
+    if (!project_line(D.prm.base, Tc, D.xyz + ii * 6, SP, EP, q)) return false;
+    const int o = D.octave[ii];
+    q.r = D.prm.base.th * D.prm.base.scale_factors[clamp_level(o, D.prm.base.nlevels)];   // :82 (octave clamped for the lookup)
+    const int mode = search_mode(Tc, D.TcwLast + (size_t)f * 12, D.mb);
+    if (mode == 1) { q.minLevel = o; q.maxLevel = -1; }                     // :86-91, GetLinesInArea's default maxLevel = -1
+    else if (mode == 2) { q.minLevel = 0; q.maxLevel = o; }
+    else { q.minLevel = wrap_add(o, -1); q.maxLevel = wrap_add(o, 1); }
+    return true;
+}
+
+// local map line i: isInFrustum (src/Frame.cc:261-327) -> mbTrackInView + track, then the window of src/LSDmatcher.cpp:143-157
+__device__ __forceinline__ bool local_query(const LineDev &D, int f, int i, LineQ &q, msl_line_track &t) {
+    const size_t ii = (size_t)f * D.ncap + i;
+    if (!(D.flags[ii] & 1)) return false;                                   // SearchLocalLines: seen in this frame, or bad
+    const msl_match_params &b = D.prm.base;
+    const float *Tc = D.TcwCur + (size_t)f * 12;
+    float SP[3], EP[3];
+    if (!project_line(b, Tc, D.xyz + ii * 6, SP, EP, q)) return false;
+    const float dmin = D.dist[2 * ii], dmax = D.dist[2 * ii + 1];
+    const float maxDistance = 1.2f * dmax, minDistance = 0.8f * dmin;     // GetMax / GetMinDistanceInvariance (src/MapLine.cpp:310-318)
+    const float tcw[3] = {Tc[3], Tc[7], Tc[11]};
+    float Ow[3];
+    gemm3(Tc, true, -1.0, tcw, nullptr, Ow);                                // mOw = -mRcw.t() * mtcw
+    float OM[3];
+    for (int k = 0; k < 3; k++) OM[k] = (SP[k] * 0.5f + EP[k] * 0.5f + 0.0f) - Ow[k];   // :302 addWeighted(SP, .5, EP, .5, 0) - mOw, float
+    double ss = 0.0;
+    for (int k = 0; k < 3; k++) ss += (double)OM[k] * (double)OM[k];
+    const float dist = (float)sqrt(ss);                                     // :303 cv::norm
+    if (dist < minDistance || dist > maxDistance) return false;             // :305
+    const double *Pn = D.normal + ii * 3;
+    double dot = 0.0;
+    for (int k = 0; k < 3; k++) dot += (double)OM[k] * (double)(float)Pn[k];   // :309-310 Mat_<float> normal, Mat::dot in double
+    const float viewCos = (float)(dot / (double)dist);
+    if (viewCos < D.prm.view_cos_limit) return false;                       // :312
+    const int L = predict_level(dmax, dist, D.prm.log_scale_factor);       // :315, not clamped
+    t.proj_x1 = q.x1; t.proj_y1 = q.y1; t.proj_x2 = q.x2; t.proj_y2 = q.y2; t.scale_level = L; t.view_cos = viewCos;
+    float r = ((double)viewCos > 0.998) ? 5.0f : 8.0f;                      // RadiusByViewingCos: float vs double constant
+    if (b.th != 1.0f) r *= b.th;                                            // bFactor (:140, :149-150)
+    q.r = r * b.scale_factors[clamp_level(L, b.nlevels)];                   // :153 (level clamped for the lookup only)
+    q.minLevel = wrap_add(L, -1); q.maxLevel = L;
+    return true;
+}
+
+// ---- k_line_query: one lane per line ---------------------------------------------------------------------------------------------------------
+template <bool LOCAL>
+__global__ __launch_bounds__(256) void k_line_query(LineDev D) {
+    const int f = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= min(max(D.nLines[f], 0), D.ncap)) return;
+    const size_t ii = (size_t)f * D.ncap + i;
+    LineQ q{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0, 0, 0};
+    if (LOCAL) {
+        msl_line_track t{0.0f, 0.0f, 0.0f, 0.0f, 0, 0.0f};
+        const bool in = local_query(D, f, i, q, t);
+        if (!in) t = msl_line_track{0.0f, 0.0f, 0.0f, 0.0f, 0, 0.0f};
+        q.ok = in;
+        D.inView[ii] = in; D.track[ii] = t;
+        if (D.inViewOut) D.inViewOut[ii] = in;
+        if (D.trackOut) D.trackOut[ii] = t;
+    } else {
+        q.ok = last_query(D, f, i, q);
+    }
+    D.q[ii] = q;
+}
+
+// ---- k_line_assign: one workgroup per frame -----------------------------------------------------------------------------------------------------
+// The reference walks the lines in order; line i scans GetLinesInArea's indices (ascending keyline index k), skips a keyline whose
+// mvpMapLines[k] has Observations() > 0, keeps (bestDist, bestLevel, bestIdx) and (bestDist2, bestLevel2) with strict < updates from 256 / -1,
+// and writes mvpMapLines[bestIdx] = line i when bestDist <= TH_HIGH and not (bestLevel == bestLevel2 && bestDist > mfNNratio * bestDist2).
+//   * Best / second best.  With the key (dist << 16 | k), the strict-< updates leave bestIdx / bestLevel = the smallest key and
+//     bestDist2 / bestLevel2 = the second smallest among the keylines line i does not skip (distance 256 never passes < 256 and is dropped).
+//     So pick(i) is a function of the set of keylines line i skips, and of nothing else.
+//   * Line i skips k iff, when i runs, mvpMapLines[k] is a line with observations.  Keylines held with observations on entry (cur_line_flags 3,
+//     local search only) are skipped by every line (t = -1).  Otherwise let t(k) = the first line WITH observations that picks k: before t(k)
+//     only lines without observations (or the holder on entry, without observations) can have written k, so nobody skips it; from t(k) on it is
+//     held with observations, every later line skips it and nobody overwrites it.  Hence: i skips k  <=>  t(k) < i.
+//   * Uniqueness and equality with the sequential loop: pick(i) depends only on t restricted to lines < i, i.e. on pick(0 .. i-1).  By induction
+//     over i exactly one assignment satisfies "pick(i) = choice of i given the t of the picks", and it is the sequential one.
+//   * Round bound: each round recomputes every pick from the t of the previous round.  After round r the picks of lines 0 .. r-1 are final
+//     (line 0's never depends on t; line r's only on lines < r), so at most n_lines + 1 rounds run; the loop stops at the first round that
+//     changes nothing.
+//   * Holder of k = the last picker (later lines overwrite); with t(k) set nobody picks after it.  nmatches counts every accepted pick.
+// LDS: keylines 4 KB + descriptors 8 KB + t 1 KB static, pick[ncap] short dynamic (64 KB at mlcap = 32768): 77 KB at the limits.
+template <bool LOCAL>
+__global__ __launch_bounds__(LINE_NT) void k_line_assign(LineDev D) {
+    __shared__ msl_keyline s_kl[MAX_LCAP];
+    __shared__ uint4 s_desc[2 * MAX_LCAP];
+    __shared__ int s_t[MAX_LCAP];
+    __shared__ int s_nm, s_ntm;
+    extern __shared__ short s_pick[];               // [ncap]: the keyline line i picks, -1 = none, -2 = not evaluated yet
+    const int f = blockIdx.x;
+    const int nCur = min(max(D.nCur[f], 0), D.lcap), nL = min(max(D.nLines[f], 0), D.ncap);
+    const size_t kb = (size_t)f * D.lcap, lb = (size_t)f * D.ncap;
+    for (int k = threadIdx.x; k < nCur; k += LINE_NT) {
+        s_kl[k] = D.curKl[kb + k];
+        const uint4 *d = reinterpret_cast<const uint4 *>(D.curDesc + (kb + k) * 32);
+        s_desc[2 * k] = d[0]; s_desc[2 * k + 1] = d[1];
+    }
+    auto reset_t = [&]() {
+        for (int k = threadIdx.x; k < nCur; k += LINE_NT) s_t[k] = (LOCAL && (D.curFlags[kb + k] & 3) == 3) ? -1 : T_FREE;
+    };
+    reset_t();
+    for (int i = threadIdx.x; i < nL; i += LINE_NT) s_pick[i] = -2;
+    if (threadIdx.x == 0) { s_nm = 0; s_ntm = 0; }
+    __syncthreads();
+
+    // line i's choice given the current t: GetLinesInArea (src/Frame.cc:384-415) over the keylines it does not skip, then :117-129 / :183-191
+    auto pick_of = [&](int i) -> int {
+        const LineQ q = D.q[lb + i];
+        if (!q.ok) return -1;
+        const uint4 *dq = reinterpret_cast<const uint4 *>(D.desc + (lb + i) * 32);
+        const uint4 d0 = dq[0], d1 = dq[1];
+        const double mx = 0.5 * (double)(q.x1 + q.x2), my = 0.5 * (double)(q.y1 + q.y2);   // float sums, then double
+        const float slope0 = (q.y1 - q.y2) / (q.x1 - q.x2);
+        const float rr = q.r * q.r;
+        const double rs = (double)q.r * 0.01;
+        const bool bCheckLevels = (q.minLevel > 0) || (q.maxLevel > 0);
+        unsigned b1 = K_NONE, b2 = K_NONE;
+        for (int k = 0; k < nCur; k++) {
+            if (s_t[k] < i) continue;                                       // held by a line with observations
+            const msl_keyline kl = s_kl[k];
+            const double dx = mx - (double)kl.x, dy = my - (double)kl.y;
+            const float distance = (float)(dx * dx + dy * dy);
+            if (distance > rr) continue;
+            const float slope = slope0 - kl.angle;                          // no fabs: a negative difference, or NaN, passes
+            if ((double)slope > rs) continue;
+            if (bCheckLevels) {
+                if (kl.octave < q.minLevel) continue;
+                if (q.maxLevel >= 0 && kl.octave > q.maxLevel) continue;
+            }
+            const int dist = hamming256(d0, d1, s_desc[2 * k], s_desc[2 * k + 1]);
+            if (dist < 256) {                                               // the two smallest keys so far, b1 < b2 (branch-free: no private array)
+                const unsigned key = ((unsigned)dist << 16) | (unsigned)k;
+                b2 = min(b2, max(key, b1));
+                b1 = min(b1, key);
+            }
+        }
+        if (b1 == K_NONE) return -1;
+        const int bestDist = (int)(b1 >> 16);
+        if (bestDist > TH_HIGH) return -1;
+        const int bestLevel = s_kl[b1 & 0xFFFFu].octave;
+        const int bestLevel2 = b2 == K_NONE ? -1 : s_kl[b2 & 0xFFFFu].octave;
+        const int bestDist2 = b2 == K_NONE ? 256 : (int)(b2 >> 16);
+        if (bestLevel == bestLevel2 && (float)bestDist > D.prm.nn_ratio * (float)bestDist2) return -1;
+        return (int)(b1 & 0xFFFFu);
+    };
+
+    for (int round = 0; round <= nL; round++) {
+        bool changed = false;
+        for (int i = threadIdx.x; i < nL; i += LINE_NT) {
+            const int np = pick_of(i);
+            changed |= np != s_pick[i];
+            s_pick[i] = (short)np;
+        }
+        if (!__syncthreads_or(changed ? 1 : 0)) break;
+        reset_t();
+        __syncthreads();
+        for (int i = threadIdx.x; i < nL; i += LINE_NT)
+            if (s_pick[i] >= 0 && (D.flags[lb + i] & 2)) atomicMin(&s_t[s_pick[i]], i);
+        __syncthreads();
+    }
+    // holder = the last line that picked the keyline; t(.) is no longer needed and its storage holds it
+    __syncthreads();
+    for (int k = threadIdx.x; k < nCur; k += LINE_NT) s_t[k] = -1;
+    __syncthreads();
+    int nm = 0, ntm = 0;
+    for (int i = threadIdx.x; i < nL; i += LINE_NT) {
+        const int pk = s_pick[i];
+        if (pk >= 0) { atomicMax(&s_t[pk], i); nm++; }
+        if (LOCAL) ntm += D.inView[lb + i];
+    }
+    if (nm) atomicAdd(&s_nm, nm);
+    if (ntm) atomicAdd(&s_ntm, ntm);
+    __syncthreads();
+    for (int k = threadIdx.x; k < D.lcap; k += LINE_NT) {
+        const int h = k < nCur ? s_t[k] : -1;
+        D.matchOut[kb + k] = h;
+        if (k >= nCur) continue;
+        if (h >= 0) {
+            if (D.lineXyz)
+                for (int c = 0; c < 6; c++) D.lineXyz[(kb + k) * 6 + c] = D.xyz[(lb + h) * 6 + c];
+            if (D.lineHas) D.lineHas[kb + k] = 1;
+        } else if (!LOCAL && D.lineHas) {
+            D.lineHas[kb + k] = 0;                                          // the last-frame search starts from all NULL
+        }
+    }
+    if (threadIdx.x == 0) {
+        D.nmatches[f] = s_nm;
+        if (LOCAL) D.nToMatch[f] = s_ntm;
+    }
+}
+
+bool bad_base(const msl_match_params &b) {
+    return b.nlevels < 1 || b.nlevels > MSL_MATCH_MAX_LEVELS || !(b.maxX > b.minX) || !(b.maxY > b.minY) || b.fx == 0;
+}
+
+// The optional line_xyz / line_has arrays are in/out (untouched slots keep their bytes): staged from host memory like inputs.
+hipError_t stage_line_io(msl_match *h, double *line_xyz, uint8_t *line_has, size_t l, msl_mem out_mem, void *user[2], void *dev[2],
+                         size_t bytes[2]) {
+    user[0] = line_xyz; user[1] = line_has; bytes[0] = sizeof(double) * 6 * l; bytes[1] = l;
+    for (int i = 0; i < 2; i++) {
+        dev[i] = nullptr;
+        if (!user[i]) continue;
+        const hipError_t e = stage(&user[i], &bytes[i], 1, 1, out_mem, &h->lineIo[i], h->stream, &dev[i]);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t set_assign_lds(msl_match *h) {
+    if (h->lineAttrSet) return hipSuccess;
+    hipError_t e = hipFuncSetAttribute((const void *)k_line_assign<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(short) * MAX_LLCAP));
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void *)k_line_assign<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(short) * MAX_MLCAP));
+    if (e == hipSuccess) h->lineAttrSet = true;
+    return e;
+}
+
+int run_lines_last(msl_match *h, int n_frames, int lcap, int llcap, const msl_line_match_params *params, const msl_keyline *cur_kl,
+                   const uint8_t *cur_ldesc, const int32_t *n_cur_lines, const double *last_line_xyz, const uint8_t *last_ldesc,
+                   const uint8_t *last_line_flags, const int32_t *last_line_octave, const int32_t *n_last_lines, const float *Tcw_cur,
+                   const float *Tcw_last, msl_mem mem, int32_t *match_out, int32_t *nmatches, double *line_xyz, uint8_t *line_has, msl_mem out_mem) {
+    if (!h || n_frames < 1 || lcap < 1 || lcap > MAX_LCAP || llcap < 1 || llcap > MAX_LLCAP || !params || !cur_kl || !cur_ldesc || !n_cur_lines ||
+        !last_line_xyz || !last_ldesc || !last_line_flags || !last_line_octave || !n_last_lines || !Tcw_cur || !Tcw_last || !match_out || !nmatches ||
+        bad_base(params->base)) {
+        set_error("msl_match_lines_by_projection: invalid argument (lcap <= %d, llcap <= %d, nlevels <= %d)", MAX_LCAP, MAX_LLCAP, MSL_MATCH_MAX_LEVELS);
+        return MSL_ERR_INVALID;
+    }
+    int rc = bind_device(h->device);
+    if (rc != MSL_OK) return rc;
+    hipStream_t st = h->stream;
+    const size_t F = (size_t)n_frames, l = F * lcap, n = F * llcap;
+    LineDev D{};
+    D.lcap = lcap; D.ncap = llcap; D.prm = *params; D.mb = params->base.bf / params->base.fx;   // src/Frame.cc:150
+    const void *src[10] = {cur_kl, cur_ldesc, n_cur_lines, last_line_xyz, last_ldesc, last_line_flags, last_line_octave, n_last_lines, Tcw_cur, Tcw_last};
+    const size_t bytes[10] = {sizeof(msl_keyline) * l, 32 * l, 4 * F, sizeof(double) * 6 * n, 32 * n, n, 4 * n, 4 * F, 48 * F, 48 * F};
+    void *dev[10];
+    MSL_HIP_TRY(stage(src, bytes, 10, 10, mem, h->lineIn, st, dev));
+    D.curKl = (const msl_keyline *)dev[0]; D.curDesc = (const uint8_t *)dev[1]; D.nCur = (const int32_t *)dev[2]; D.xyz = (const double *)dev[3];
+    D.desc = (const uint8_t *)dev[4]; D.flags = (const uint8_t *)dev[5]; D.octave = (const int32_t *)dev[6]; D.nLines = (const int32_t *)dev[7];
+    D.TcwCur = (const float *)dev[8]; D.TcwLast = (const float *)dev[9];
+    MSL_HIP_TRY(grow_all(st, {{h->lineQ, sizeof(LineQ) * n}}));
+    D.q = (LineQ *)h->lineQ.p;
+    void *out[2] = {match_out, nmatches}, *dout[2];
+    const size_t outBytes[2] = {sizeof(int32_t) * l, sizeof(int32_t) * F};
+    MSL_HIP_TRY(stage(out, outBytes, 2, 0, out_mem, h->out, st, dout));
+    D.matchOut = (int32_t *)dout[0]; D.nmatches = (int32_t *)dout[1];
+    void *io[2], *dio[2]; size_t ioBytes[2];
+    MSL_HIP_TRY(stage_line_io(h, line_xyz, line_has, l, out_mem, io, dio, ioBytes));
+    D.lineXyz = (double *)dio[0]; D.lineHas = (uint8_t *)dio[1];
+    MSL_HIP_TRY(set_assign_lds(h));
+    hipLaunchKernelGGL(k_line_query<false>, dim3((unsigned)((llcap + 255) / 256), (unsigned)n_frames), dim3(256), 0, st, D);
+    hipLaunchKernelGGL(k_line_assign<false>, dim3((unsigned)n_frames), dim3(LINE_NT), sizeof(short) * llcap, st, D);
+    MSL_HIP_TRY(hipGetLastError());
+    void *user[4] = {match_out, nmatches, io[0], io[1]};
+    const void *devp[4] = {dout[0], dout[1], dio[0], dio[1]};
+    const size_t ub[4] = {outBytes[0], outBytes[1], ioBytes[0], ioBytes[1]};
+    MSL_HIP_TRY(finish_call(user, devp, ub, 4, mem, out_mem, st));
+    return MSL_OK;
+}
+
+int run_lines_local(msl_match *h, int n_frames, int lcap, int mlcap, const msl_line_match_params *params, const msl_keyline *cur_kl,
+                    const uint8_t *cur_ldesc, const int32_t *n_cur_lines, const uint8_t *cur_line_flags, const double *ml_xyz, const double *ml_normal,
+                    const float *ml_dist, const uint8_t *ml_desc, const uint8_t *ml_flags, const int32_t *n_local_lines, const float *Tcw, msl_mem mem,
+                    int32_t *match_out, int32_t *n_to_match, int32_t *nmatches, uint8_t *in_view, msl_line_track *track, double *line_xyz,
+                    uint8_t *line_has, msl_mem out_mem) {
+    if (!h || n_frames < 1 || lcap < 1 || lcap > MAX_LCAP || mlcap < 1 || mlcap > MAX_MLCAP || !params || !cur_kl || !cur_ldesc || !n_cur_lines ||
+        !cur_line_flags || !ml_xyz || !ml_normal || !ml_dist || !ml_desc || !ml_flags || !n_local_lines || !Tcw || !match_out || !n_to_match ||
+        !nmatches || bad_base(params->base) || !(params->log_scale_factor > 0)) {
+        set_error("msl_match_local_lines: invalid argument (lcap <= %d, mlcap <= %d, nlevels <= %d, log_scale_factor > 0)", MAX_LCAP, MAX_MLCAP,
+                  MSL_MATCH_MAX_LEVELS);
+        return MSL_ERR_INVALID;
+    }
+    int rc = bind_device(h->device);
+    if (rc != MSL_OK) return rc;
+    hipStream_t st = h->stream;
+    const size_t F = (size_t)n_frames, l = F * lcap, m = F * mlcap;
+    LineDev D{};
+    D.lcap = lcap; D.ncap = mlcap; D.prm = *params;
+    const void *src[11] = {cur_kl, cur_ldesc, n_cur_lines, cur_line_flags, ml_xyz, ml_normal, ml_dist, ml_desc, ml_flags, n_local_lines, Tcw};
+    const size_t bytes[11] = {sizeof(msl_keyline) * l, 32 * l, 4 * F, l, sizeof(double) * 6 * m, sizeof(double) * 3 * m, 8 * m, 32 * m, m, 4 * F, 48 * F};
+    void *dev[11];
+    MSL_HIP_TRY(stage(src, bytes, 11, 11, mem, h->lineIn, st, dev));
+    D.curKl = (const msl_keyline *)dev[0]; D.curDesc = (const uint8_t *)dev[1]; D.nCur = (const int32_t *)dev[2]; D.curFlags = (const uint8_t *)dev[3];
+    D.xyz = (const double *)dev[4]; D.normal = (const double *)dev[5]; D.dist = (const float *)dev[6]; D.desc = (const uint8_t *)dev[7];
+    D.flags = (const uint8_t *)dev[8]; D.nLines = (const int32_t *)dev[9]; D.TcwCur = (const float *)dev[10];
+    MSL_HIP_TRY(grow_all(st, {{h->lineQ, sizeof(LineQ) * m}, {h->lineTrk, sizeof(msl_line_track) * m}, {h->lineView, m}}));
+    D.q = (LineQ *)h->lineQ.p; D.track = (msl_line_track *)h->lineTrk.p; D.inView = (uint8_t *)h->lineView.p;
+    void *out[3] = {match_out, nmatches, n_to_match}, *dout[3];
+    const size_t outBytes[3] = {sizeof(int32_t) * l, sizeof(int32_t) * F, sizeof(int32_t) * F};
+    MSL_HIP_TRY(stage(out, outBytes, 3, 0, out_mem, h->out, st, dout));
+    D.matchOut = (int32_t *)dout[0]; D.nmatches = (int32_t *)dout[1]; D.nToMatch = (int32_t *)dout[2];
+    // the optional in_view / track: the kernels write device-memory ones, host-memory ones are copied back from the scratch
+    const bool devOut = out_mem != MSL_MEM_HOST;
+    D.inViewOut = devOut ? in_view : nullptr; D.trackOut = devOut ? track : nullptr;
+    void *io[2], *dio[2]; size_t ioBytes[2];
+    MSL_HIP_TRY(stage_line_io(h, line_xyz, line_has, l, out_mem, io, dio, ioBytes));
+    D.lineXyz = (double *)dio[0]; D.lineHas = (uint8_t *)dio[1];
+    MSL_HIP_TRY(set_assign_lds(h));
+    hipLaunchKernelGGL(k_line_query<true>, dim3((unsigned)((mlcap + 255) / 256), (unsigned)n_frames), dim3(256), 0, st, D);
+    hipLaunchKernelGGL(k_line_assign<true>, dim3((unsigned)n_frames), dim3(LINE_NT), sizeof(short) * mlcap, st, D);
+    MSL_HIP_TRY(hipGetLastError());
+    void *user[7] = {match_out, nmatches, n_to_match, in_view, track, io[0], io[1]};
+    const void *devp[7] = {dout[0], dout[1], dout[2], D.inView, D.track, dio[0], dio[1]};
+    const size_t ub[7] = {outBytes[0], outBytes[1], outBytes[2], m, sizeof(msl_line_track) * m, ioBytes[0], ioBytes[1]};
+    MSL_HIP_TRY(finish_call(user, devp, ub, 7, mem, out_mem, st));
+    return MSL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int msl_match_lines_by_projection(msl_match *h, int n_frames, int lcap, int llcap, const msl_line_match_params *params, const msl_keyline *cur_kl,
+                                  const uint8_t *cur_ldesc, const int32_t *n_cur_lines, const double *last_line_xyz, const uint8_t *last_ldesc,
+                                  const uint8_t *last_line_flags, const int32_t *last_line_octave, const int32_t *n_last_lines, const float *Tcw_cur,
+                                  const float *Tcw_last, msl_mem mem, int32_t *match_out, int32_t *nmatches, double *line_xyz, uint8_t *line_has,
+                                  msl_mem out_mem) noexcept {
+    try {
+    return run_lines_last(h, n_frames, lcap, llcap, params, cur_kl, cur_ldesc, n_cur_lines, last_line_xyz, last_ldesc, last_line_flags, last_line_octave,
+                          n_last_lines, Tcw_cur, Tcw_last, mem, match_out, nmatches, line_xyz, line_has, out_mem);
+    } MSL_ABI_CATCH_INT
+}
+
+int msl_match_lines_by_projection_batch(int device, int n_frames, int lcap, int llcap, const msl_line_match_params *params, const msl_keyline *cur_kl,
+                                        const uint8_t *cur_ldesc, const int32_t *n_cur_lines, const double *last_line_xyz, const uint8_t *last_ldesc,
+                                        const uint8_t *last_line_flags, const int32_t *last_line_octave, const int32_t *n_last_lines,
+                                        const float *Tcw_cur, const float *Tcw_last, msl_mem mem, int32_t *match_out, int32_t *nmatches,
+                                        double *line_xyz, uint8_t *line_has, msl_mem out_mem) noexcept {
+    try {
+    return on_default_handle(device, mem == MSL_MEM_DEVICE, [&](msl_match *h) {
+        return run_lines_last(h, n_frames, lcap, llcap, params, cur_kl, cur_ldesc, n_cur_lines, last_line_xyz, last_ldesc, last_line_flags,
+                              last_line_octave, n_last_lines, Tcw_cur, Tcw_last, mem, match_out, nmatches, line_xyz, line_has, out_mem);
+    });
+    } MSL_ABI_CATCH_INT
+}
+
+int msl_match_local_lines(msl_match *h, int n_frames, int lcap, int mlcap, const msl_line_match_params *params, const msl_keyline *cur_kl,
+                          const uint8_t *cur_ldesc, const int32_t *n_cur_lines, const uint8_t *cur_line_flags, const double *ml_xyz,
+                          const double *ml_normal, const float *ml_dist, const uint8_t *ml_desc, const uint8_t *ml_flags, const int32_t *n_local_lines,
+                          const float *Tcw, msl_mem mem, int32_t *match_out, int32_t *n_to_match, int32_t *nmatches, uint8_t *in_view,
+                          msl_line_track *track, double *line_xyz, uint8_t *line_has, msl_mem out_mem) noexcept {
+    try {
+    return run_lines_local(h, n_frames, lcap, mlcap, params, cur_kl, cur_ldesc, n_cur_lines, cur_line_flags, ml_xyz, ml_normal, ml_dist, ml_desc,
+                           ml_flags, n_local_lines, Tcw, mem, match_out, n_to_match, nmatches, in_view, track, line_xyz, line_has, out_mem);
+    } MSL_ABI_CATCH_INT
+}
+
+int msl_match_local_lines_batch(int device, int n_frames, int lcap, int mlcap, const msl_line_match_params *params, const msl_keyline *cur_kl,
+                                const uint8_t *cur_ldesc, const int32_t *n_cur_lines, const uint8_t *cur_line_flags, const double *ml_xyz,
+                                const double *ml_normal, const float *ml_dist, const uint8_t *ml_desc, const uint8_t *ml_flags,
+                                const int32_t *n_local_lines, const float *Tcw, msl_mem mem, int32_t *match_out, int32_t *n_to_match, int32_t *nmatches,
+                                uint8_t *in_view, msl_line_track *track, double *line_xyz, uint8_t *line_has, msl_mem out_mem) noexcept {
+    try {
+    return on_default_handle(device, mem == MSL_MEM_DEVICE, [&](msl_match *h) {
+        return run_lines_local(h, n_frames, lcap, mlcap, params, cur_kl, cur_ldesc, n_cur_lines, cur_line_flags, ml_xyz, ml_normal, ml_dist, ml_desc,
+                               ml_flags, n_local_lines, Tcw, mem, match_out, n_to_match, nmatches, in_view, track, line_xyz, line_has, out_mem);
+    });
+    } MSL_ABI_CATCH_INT
+}
+
+}  // extern "C"

@@ -20,8 +20,10 @@
 //                       (bounded by n_last).  Then holder = last picker, rotation histogram, three maxima, NULLing (:657-674).
 //
 // Integer / byte work, L2-resident gathers; no MFMA.  The float expressions keep the reference's order; the 3x3 cv::Mat products
-// follow cv::gemm's float kernel (double accumulation, one rounding) -- pinned in DESIGN.md section 3.
+// follow cv::gemm's float kernel (double accumulation, one rounding) -- pinned in DESIGN.md section 3; gemm3, the search mode, the popcount
+// and predict_scale live in msl_match_math.h, shared with the line matcher (msl_line_match.hip).
 #include "msl_match_handle.h"
+#include "msl_match_math.h"
 
 #include <climits>
 #include <mutex>
@@ -55,17 +57,6 @@ struct MatchDev {
     unsigned *candCnt;         // [nPairs][cap]      total candidates of the point (may exceed CMAX)
     int32_t *matchOut, *nmatches;
 };
-
-// d[r] = (float)(alpha * sum_k A(r, k) b[k] + c[r]) with double accumulation: cv::gemm's CV_32F kernel
-__device__ __forceinline__ void gemm3(const float *A, bool transA, double alpha, const float b[3], const float *c, float d[3]) {
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-        double s = 0;
-#pragma unroll
-        for (int k = 0; k < 3; k++) s += (double)(transA ? A[k * 4 + r] : A[r * 4 + k]) * (double)b[k];
-        d[r] = (float)(s * alpha + (c ? (double)c[r] : 0.0));
-    }
-}
 
 // ---- k_match_grid ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_match_grid(MatchDev P) {
@@ -103,12 +94,7 @@ __global__ __launch_bounds__(256) void k_match_grid(MatchDev P) {
     for (unsigned i = threadIdx.x; i < total; i += 256) P.items[(size_t)pair * P.cap + i] = s_items[i];
     for (int c = threadIdx.x; c <= NCELLS; c += 256) P.cellStart[(size_t)pair * (NCELLS + 1) + c] = s_start[c];
     if (threadIdx.x == 0 && P.mode) {   // bForward / bBackward (:560-571); the local-map search has no last frame (mode == nullptr)
-        const float *Tc = P.TcwCur + (size_t)pair * 12, *Tl = P.TcwLast + (size_t)pair * 12;
-        const float tcw[3] = {Tc[3], Tc[7], Tc[11]}, tlw[3] = {Tl[3], Tl[7], Tl[11]};
-        float twc[3], tlc[3];
-        gemm3(Tc, true, -1.0, tcw, nullptr, twc);      // twc = -Rcw.t() * tcw
-        gemm3(Tl, false, 1.0, twc, tlw, tlc);          // tlc = Rlw * twc + tlw
-        P.mode[pair] = tlc[2] > P.mb ? 1 : (-tlc[2] > P.mb ? 2 : 0);
+        P.mode[pair] = search_mode(P.TcwCur + (size_t)pair * 12, P.TcwLast + (size_t)pair * 12, P.mb);
     }
 }
 
@@ -176,8 +162,7 @@ __device__ __forceinline__ int eval_item(const MatchDev &P, int pair, const Quer
     }
     const uint4 *dp = reinterpret_cast<const uint4 *>(P.curDesc + base * 32);
     const uint4 e0 = dp[0], e1 = dp[1];
-    return __popc(d0.x ^ e0.x) + __popc(d0.y ^ e0.y) + __popc(d0.z ^ e0.z) + __popc(d0.w ^ e0.w) + __popc(d1.x ^ e1.x) +
-           __popc(d1.y ^ e1.y) + __popc(d1.z ^ e1.z) + __popc(d1.w ^ e1.w);
+    return hamming256(d0, d1, e0, e1);
 }
 
 // The window of Q walked by one wave (cells spread over the lanes): every item that passes eval_item with a distance below distCap is
@@ -379,18 +364,6 @@ struct LocalDev {
     int32_t *nToMatch;
 };
 
-// ceil(log(ratio) / mfLogScaleFactor) clamped to [0, nlevels - 1] (src/MapPoint.cc:350-364).  log is glibc's logf in the reference; here the
-// double log of the float, rounded once.  A quotient that is not a finite int (NaN, +-inf) converts to INT_MIN as on
-// x86-64 and so gives level 0.
-__device__ __forceinline__ int predict_scale(float maxDistance, float dist, float logScale, int nlevels) {
-    const float ratio = maxDistance / dist;
-    const float q = ceilf((float)log((double)ratio) / logScale);
-    int nScale = (q >= -2147483648.0f && q < 2147483648.0f) ? (int)q : INT_MIN;
-    if (nScale < 0) nScale = 0;
-    else if (nScale >= nlevels) nScale = nlevels - 1;
-    return nScale;
-}
-
 // ---- k_local_frustum: one lane per local map point --------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_local_frustum(LocalDev L) {
     const int f = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
@@ -572,8 +545,7 @@ __global__ void k_descriptor_distance(const uint8_t *a, const uint8_t *b, int n,
     if (i >= n) return;
     const uint4 *pa = reinterpret_cast<const uint4 *>(a + (size_t)i * 32), *pb = reinterpret_cast<const uint4 *>(b + (size_t)i * 32);
     const uint4 a0 = pa[0], a1 = pa[1], b0 = pb[0], b1 = pb[1];
-    out[i] = __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) + __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) +
-             __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
+    out[i] = hamming256(a0, a1, b0, b1);
 }
 
 int run_projection(msl_match *h, int n_pairs, int cap, const msl_match_params *params, const msl_keypoint *cur_kps, const float *cur_un_xy,

@@ -4,7 +4,7 @@
 #include "msl_common.h"
 
 // One matcher object = one ORBmatcher of the reference (src/ORBmatcher.cc:41): its own stream and its own scratch, used by one thread at a time;
-// the device is re-bound at every entry like the other handles.  msl_pose_optimize runs on it too.
+// the device is re-bound at every entry like the other handles.  The line searches (= the tracker's LSDmatcher) and msl_pose_optimize run on it too.
 struct msl_match {
     int device = 0;
     hipStream_t stream = nullptr; bool ownStream = true;
@@ -12,6 +12,8 @@ struct msl_match {
     msl::DevBuf da, db, dout;                                          // msl_match_descriptor_distance
     msl::DevBuf lin[14], trk, inView;                                  // msl_match_local_points: staged inputs, per-point scratch
     msl::DevBuf poseIn[15], poseOut[5];                                // msl_pose_optimize: staged inputs, staged in/out flags and outputs
+    msl::DevBuf lineIn[11], lineQ, lineTrk, lineView, lineIo[2];       // the line searches: staged inputs, per-line queries / tracks / in-view, line_xyz / line_has
+    bool lineAttrSet = false;
     bool localAttrSet = false;
     bool attrSet = false;
 };

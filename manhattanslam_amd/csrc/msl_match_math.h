@@ -1,0 +1,54 @@
+// msl_match_math.h -- device arithmetic the point and line matchers share, each piece pinned once (internal).
+#pragma once
+
+#include "msl_common.h"
+
+#include <climits>
+
+namespace msl {
+
+// d[r] = (float)(alpha * sum_k A(r, k) b[k] + c[r]) with double accumulation: cv::gemm's CV_32F kernel
+__device__ __forceinline__ void gemm3(const float *A, bool transA, double alpha, const float b[3], const float *c, float d[3]) {
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        double s = 0;
+#pragma unroll
+        for (int k = 0; k < 3; k++) s += (double)(transA ? A[k * 4 + r] : A[r * 4 + k]) * (double)b[k];
+        d[r] = (float)(s * alpha + (c ? (double)c[r] : 0.0));
+    }
+}
+
+// bForward / bBackward of the two last-frame searches (src/ORBmatcher.cc:560-571, src/LSDmatcher.cpp:24-35): 0 = neither, 1 = forward,
+// 2 = backward.  Tc / Tl: rows 0-2 of the current / last mTcw.
+__device__ __forceinline__ int search_mode(const float *Tc, const float *Tl, float mb) {
+    const float tcw[3] = {Tc[3], Tc[7], Tc[11]}, tlw[3] = {Tl[3], Tl[7], Tl[11]};
+    float twc[3], tlc[3];
+    gemm3(Tc, true, -1.0, tcw, nullptr, twc);      // twc = -Rcw.t() * tcw
+    gemm3(Tl, false, 1.0, twc, tlw, tlc);          // tlc = Rlw * twc + tlw
+    return tlc[2] > mb ? 1 : (-tlc[2] > mb ? 2 : 0);
+}
+
+// DescriptorDistance of two 256-bit descriptors (src/ORBmatcher.cc:835-849 and src/LSDmatcher.cpp:236-249 are the same popcount)
+__device__ __forceinline__ int hamming256(const uint4 &a0, const uint4 &a1, const uint4 &b0, const uint4 &b1) {
+    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) + __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) +
+           __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
+}
+
+// ceil(log(maxDistance / dist) / logScale) as an int, not clamped (MapLine::PredictScale, src/MapLine.cpp:320-328).  log is glibc's logf in
+// the reference; here the double log of the float, rounded once.  A quotient that is not a finite int (NaN, +-inf)
+// converts to INT_MIN as on x86-64.
+__device__ __forceinline__ int predict_level(float maxDistance, float dist, float logScale) {
+    const float ratio = maxDistance / dist;
+    const float q = ceilf((float)log((double)ratio) / logScale);
+    return (q >= -2147483648.0f && q < 2147483648.0f) ? (int)q : INT_MIN;
+}
+
+// MapPoint::PredictScale (src/MapPoint.cc:350-364): the same level clamped to [0, nlevels - 1]
+__device__ __forceinline__ int predict_scale(float maxDistance, float dist, float logScale, int nlevels) {
+    int nScale = predict_level(maxDistance, dist, logScale);
+    if (nScale < 0) nScale = 0;
+    else if (nScale >= nlevels) nScale = nlevels - 1;
+    return nScale;
+}
+
+}  // namespace msl

@@ -1,9 +1,11 @@
 """Host mirror of ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th) (reference src/ORBmatcher.cc:547-678) through the
 C ABI, for a batch of independent frame pairs, and of the local-map search Tracking::SearchLocalPoints
-(src/Tracking.cc:1654-1695: isInFrustum + SearchByProjection(Frame&, vector<MapPoint*>, th)) for a batch of frames."""
+(src/Tracking.cc:1654-1695: isInFrustum + SearchByProjection(Frame&, vector<MapPoint*>, th)) for a batch of frames, and of the two map-line
+searches LSDmatcher::SearchByProjection (src/LSDmatcher.cpp:21-198: the last frame's lines, and Tracking::SearchLocalLines' local map lines)."""
 import numpy as np
 
-from ._lib import KEYPOINT_DTYPE, LOCAL_MATCH_PARAMS_DTYPE, LOCAL_TRACK_DTYPE, MATCH_PARAMS_DTYPE, MSL_MEM_HOST, call, check, lib, pad, ptr
+from ._lib import (KEYLINE_DTYPE, KEYPOINT_DTYPE, LINE_TRACK_DTYPE, LOCAL_MATCH_PARAMS_DTYPE, LOCAL_TRACK_DTYPE, MATCH_PARAMS_DTYPE, MSL_MEM_HOST, call,
+                   check, lib, pad, ptr)
 
 
 def match_params(frame_params, scale_factors, th, check_orientation=True):
@@ -27,6 +29,12 @@ def local_match_params(frame_params, scale_factors, th, log_scale_factor, view_c
         p[k] = b[k]
     p["log_scale_factor"], p["view_cos_limit"], p["nn_ratio"] = log_scale_factor, view_cos_limit, nn_ratio
     return p
+
+
+def line_match_params(frame_params, scale_factors, th, log_scale_factor, view_cos_limit=0.6, nn_ratio=0.6):
+    """msl_line_match_params (the layout of msl_local_match_params): th = 15 for the last-frame search, 1 (5 right after a relocalisation)
+    for SearchLocalLines; isInFrustum(pML, 0.6) and LSDmatcher()'s default mfNNratio 0.6."""
+    return local_match_params(frame_params, scale_factors, th, log_scale_factor, view_cos_limit, nn_ratio)
 
 
 class Matcher:
@@ -67,6 +75,23 @@ class Matcher:
         the handle's stream.  in_view / track may be None."""
         check(lib.msl_match_local_points(self.h, n_frames, cap, mcap, ptr(params), *[ptr(a) for a in arrays], 1, ptr(match_out), ptr(n_to_match),
                                          ptr(nmatches), ptr(in_view), ptr(track), 1), "msl_match_local_points")
+
+    def search_lines_by_projection_batch(self, params, cur, last, Tcw_cur, Tcw_last, **kw):
+        return search_lines_by_projection_batch(params, cur, last, Tcw_cur, Tcw_last, handle=self, **kw)
+
+    def search_local_lines_batch(self, params, cur, local, Tcw, **kw):
+        return search_local_lines_batch(params, cur, local, Tcw, handle=self, **kw)
+
+    def search_lines_by_projection_device(self, params, n_frames, lcap, llcap, arrays, match_out, nmatches, line_xyz=None, line_has=None):
+        """Device-resident inputs and outputs (pack_lines_last's order, cur_kl .. Tcw_last): asynchronous on the handle's stream."""
+        check(lib.msl_match_lines_by_projection(self.h, n_frames, lcap, llcap, ptr(params), *[ptr(a) for a in arrays], 1, ptr(match_out),
+                                                ptr(nmatches), ptr(line_xyz), ptr(line_has), 1), "msl_match_lines_by_projection")
+
+    def search_local_lines_device(self, params, n_frames, lcap, mlcap, arrays, match_out, n_to_match, nmatches, in_view=None, track=None,
+                                  line_xyz=None, line_has=None):
+        """Device-resident inputs and outputs (pack_local_lines' order, cur_kl .. Tcw): asynchronous on the handle's stream."""
+        check(lib.msl_match_local_lines(self.h, n_frames, lcap, mlcap, ptr(params), *[ptr(a) for a in arrays], 1, ptr(match_out), ptr(n_to_match),
+                                        ptr(nmatches), ptr(in_view), ptr(track), ptr(line_xyz), ptr(line_has), 1), "msl_match_local_lines")
 
     def descriptor_distance(self, a, b):
         a = np.ascontiguousarray(a, np.uint8).reshape(-1, 32); b = np.ascontiguousarray(b, np.uint8).reshape(-1, 32)
@@ -139,3 +164,70 @@ def search_local_points_batch(params, cur, local, Tcw, device=0, handle=None, ca
     ncur, nloc = arrays[5], arrays[12]
     return ([match[f, :ncur[f]].copy() for f in range(B)], ntm, nm, [inv[f, :nloc[f]].copy() for f in range(B)],
             [trk[f, :nloc[f]].copy() for f in range(B)])
+
+
+def _pack_lines_cur(cur, lcap):
+    """cur_kl, cur_ldesc, n_cur_lines: the current-frame arrays both line searches take."""
+    return [pad(cur, "kl", lcap, KEYLINE_DTYPE), pad(cur, "desc", lcap, np.uint8, shape=(32,)), np.array([len(c["kl"]) for c in cur], np.int32)]
+
+
+def _line_io(B, lcap, line_xyz, line_has):
+    """The in/out pose-layout arrays: the caller's initial contents, or zeros."""
+    lx = np.zeros((B, lcap, 6), np.float64) if line_xyz is None else np.array(line_xyz, np.float64).reshape(B, lcap, 6)
+    lh = np.zeros((B, lcap), np.uint8) if line_has is None else np.array(line_has, np.uint8).reshape(B, lcap)
+    return lx, lh
+
+
+def pack_lines_last(cur, last, Tcw_cur, Tcw_last, lcap=None, llcap=None):
+    """msl_match_lines_by_projection's inputs in its argument order (cur_kl .. Tcw_last).
+       cur:  kl (N,) KEYLINE_DTYPE (mvKeylinesUn), desc (N,32) u8 (mLdesc)
+       last: xyz (M,6) f64 (GetWorldPos), desc (M,32) u8, flags (M,) u8, octave (M,) i32"""
+    B = len(cur)
+    lcap = lcap or max(max(len(c["kl"]) for c in cur), 1)
+    llcap = llcap or max(max(len(l["xyz"]) for l in last), 1)
+    return lcap, llcap, _pack_lines_cur(cur, lcap) + [
+        pad(last, "xyz", llcap, np.float64, shape=(6,)), pad(last, "desc", llcap, np.uint8, shape=(32,)), pad(last, "flags", llcap, np.uint8),
+        pad(last, "octave", llcap, np.int32), np.array([len(l["xyz"]) for l in last], np.int32), _rows3x4(Tcw_cur, B), _rows3x4(Tcw_last, B)]
+
+
+def search_lines_by_projection_batch(params, cur, last, Tcw_cur, Tcw_last, device=0, handle=None, lcap=None, llcap=None, line_xyz=None,
+                                     line_has=None):
+    """LSDmatcher::SearchByProjection(CurrentFrame, LastFrame, th) for a batch of frame pairs (host arrays, synchronous); see pack_lines_last.
+    line_xyz / line_has: initial contents of the pose-layout outputs (default zeros).  Returns (match: per frame (N,) i32, nmatches,
+    line_xyz [B][lcap][6] f64, line_has [B][lcap] u8)."""
+    lcap, llcap, arrays = pack_lines_last(cur, last, Tcw_cur, Tcw_last, lcap, llcap)
+    B = len(cur)
+    match = np.zeros((B, lcap), np.int32); nm = np.zeros(B, np.int32)
+    lx, lh = _line_io(B, lcap, line_xyz, line_has)
+    call("msl_match_lines_by_projection", handle, device, B, lcap, llcap, ptr(params), *[ptr(a) for a in arrays], MSL_MEM_HOST, ptr(match), ptr(nm),
+         ptr(lx), ptr(lh), MSL_MEM_HOST)
+    ncur = arrays[2]
+    return [match[f, :ncur[f]].copy() for f in range(B)], nm, lx, lh
+
+
+def pack_local_lines(cur, local, Tcw, lcap=None, mlcap=None):
+    """msl_match_local_lines' inputs in its argument order (cur_kl .. Tcw).
+       cur:   kl (N,) KEYLINE_DTYPE, desc (N,32) u8, flags (N,) u8 (bit 0 held, bit 1 the holder has observations)
+       local: xyz (M,6) f64, normal (M,3) f64, dist (M,2) f32 (mfMinDistance, mfMaxDistance), desc (M,32) u8, flags (M,) u8"""
+    lcap = lcap or max(max(len(c["kl"]) for c in cur), 1)
+    mlcap = mlcap or max(max(len(l["xyz"]) for l in local), 1)
+    return lcap, mlcap, _pack_lines_cur(cur, lcap) + [
+        pad(cur, "flags", lcap, np.uint8), pad(local, "xyz", mlcap, np.float64, shape=(6,)), pad(local, "normal", mlcap, np.float64, shape=(3,)),
+        pad(local, "dist", mlcap, np.float32, shape=(2,)), pad(local, "desc", mlcap, np.uint8, shape=(32,)), pad(local, "flags", mlcap, np.uint8),
+        np.array([len(l["xyz"]) for l in local], np.int32), _rows3x4(Tcw, len(cur))]
+
+
+def search_local_lines_batch(params, cur, local, Tcw, device=0, handle=None, lcap=None, mlcap=None, line_xyz=None, line_has=None):
+    """Tracking::SearchLocalLines after its first loop for a batch of frames (host arrays, synchronous); see pack_local_lines.  Returns
+    (match: per frame (N,) i32, n_to_match, nmatches, in_view: per frame (M,) u8, track: per frame (M,) LINE_TRACK_DTYPE,
+    line_xyz [B][lcap][6] f64, line_has [B][lcap] u8)."""
+    lcap, mlcap, arrays = pack_local_lines(cur, local, Tcw, lcap, mlcap)
+    B = len(cur)
+    match = np.zeros((B, lcap), np.int32); ntm = np.zeros(B, np.int32); nm = np.zeros(B, np.int32)
+    inv = np.zeros((B, mlcap), np.uint8); trk = np.zeros((B, mlcap), LINE_TRACK_DTYPE)
+    lx, lh = _line_io(B, lcap, line_xyz, line_has)
+    call("msl_match_local_lines", handle, device, B, lcap, mlcap, ptr(params), *[ptr(a) for a in arrays], MSL_MEM_HOST, ptr(match), ptr(ntm), ptr(nm),
+         ptr(inv), ptr(trk), ptr(lx), ptr(lh), MSL_MEM_HOST)
+    ncur, nloc = arrays[2], arrays[9]
+    return ([match[f, :ncur[f]].copy() for f in range(B)], ntm, nm, [inv[f, :nloc[f]].copy() for f in range(B)],
+            [trk[f, :nloc[f]].copy() for f in range(B)], lx, lh)

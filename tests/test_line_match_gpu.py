@@ -1,0 +1,324 @@
+"""GPU parity: batched map-line matching (msl_match_lines_by_projection[_batch], msl_match_local_lines[_batch]) vs the sequential CPU model in
+tests/line_match_model.py.  Every output must be identical: match_out, nmatches, n_to_match, in_view, the track records, line_xyz and line_has
+bit for bit.  Then the device chain point match -> line match -> local line match -> pose optimisation on one handle."""
+import numpy as np
+import pytest
+
+from tests import line_match_model as lmm
+from tests import line_match_scenes as lsc
+
+pytestmark = pytest.mark.gpu
+
+
+def _init_io(B, lcap, seed):
+    """Random initial line_xyz / line_has contents: slots a call does not write must keep them."""
+    rng = np.random.default_rng(seed)
+    return rng.normal(size=(B, lcap, 6)), rng.integers(0, 2, (B, lcap)).astype(np.uint8)
+
+
+def _check_last(p, cur, last, Tc, Tl, got, init):
+    match, nm, lx, lh = got
+    lcap = lx.shape[1]
+    tot = 0
+    for f in range(len(cur)):
+        wm, wnm = lmm.search_lines_by_projection(p, cur[f], last[f], Tc[f], Tl[f])
+        assert nm[f] == wnm and np.array_equal(match[f], wm), (f, nm[f], wnm, np.flatnonzero(match[f] != wm)[:10])
+        wx, wh = lmm.pose_layout(wm, last[f]["xyz"], lcap, init[0][f], init[1][f], clear=True)
+        assert lx[f].tobytes() == wx.tobytes() and np.array_equal(lh[f], wh), f
+        tot += wnm
+    return tot
+
+
+def _check_local(p, cur, local, T, got, init):
+    match, ntm, nm, inv, trk, lx, lh = got
+    lcap = lx.shape[1]
+    tot = 0
+    for f in range(len(cur)):
+        wm, wntm, wnm, winv, wtrk = lmm.search_local_lines(p, cur[f], local[f], T[f])
+        assert ntm[f] == wntm and nm[f] == wnm, (f, ntm[f], wntm, nm[f], wnm)
+        assert np.array_equal(match[f], wm), (f, np.flatnonzero(match[f] != wm)[:10])
+        assert np.array_equal(inv[f], winv), (f, np.flatnonzero(inv[f] != winv)[:10])
+        assert trk[f].tobytes() == wtrk.tobytes(), (f, np.flatnonzero(trk[f] != wtrk)[:10])
+        wx, wh = lmm.pose_layout(wm, local[f]["xyz"], lcap, init[0][f], init[1][f], clear=False)
+        assert lx[f].tobytes() == wx.tobytes() and np.array_equal(lh[f], wh), f
+        tot += wnm
+    return tot
+
+
+def _ragged_last(p):
+    specs = [dict(seed=501, n_last=0),                                  # empty last frame
+             dict(seed=502, n_kl=0),                                    # no keylines
+             dict(seed=503, n_kl=256, n_last=256),                      # lcap = llcap = 256
+             dict(seed=504, vertical=12),                               # x1 == x2: a NaN / inf slope
+             dict(seed=505, fwd=0.5),                                   # forward search mode
+             dict(seed=506, fwd=-0.5),                                  # backward search mode
+             dict(seed=507, few=3, n_last=120),                         # many lines on a few keylines
+             dict(seed=508, angle_mode="atan", octaves=1),              # LSD-like angles, octave 0 only
+             dict(seed=509, n_kl=1, n_last=30)]
+    cur, last, Tc, Tl = [], [], [], []
+    for s in specs:
+        s = dict(s)
+        seed, nl = s.pop("seed"), s.pop("n_last", 40)
+        c, l, t, tl = lsc.frame_pair(seed, p, n_last=max(nl, 1), **s)
+        cur.append(c); last.append(l if nl else lsc.empty(l)); Tc.append(t); Tl.append(tl)
+    return cur, last, np.stack(Tc), np.stack(Tl)
+
+
+def _ragged_local(p):
+    specs = [dict(seed=601, n_local=0),                                 # empty local map
+             dict(seed=602, n_kl=0, n_local=300),                       # no keylines
+             dict(seed=603, n_kl=256, n_local=3000),                    # lcap = 256
+             dict(seed=604, n_local=4000),
+             dict(seed=605, few=3, n_local=2000),                       # many lines on a few keylines: a deep fixpoint
+             dict(seed=606, preheld=0.7, n_local=1500),                 # pre-held keylines with and without observations
+             dict(seed=607, n_kl=1, n_local=500),
+             dict(seed=608, octaves=1, n_local=2500),                   # octave 0 only
+             dict(seed=609, n_local=1)]
+    cur, local, T = [], [], []
+    for s in specs:
+        s = dict(s)
+        seed, nl = s.pop("seed"), s.pop("n_local")
+        c, l, t = lsc.local_frame(seed, p, n_local=max(nl, 1), **s)
+        cur.append(c); local.append(l if nl else lsc.empty(l)); T.append(t)
+    return cur, local, np.stack(T)
+
+
+def test_last_frame_ragged_batch_matches_model():
+    """Nine ragged frame pairs in one call of the device-indexed form, th = 15 (TrackWithMotionModel)."""
+    from manhattanslam_amd import match
+    p = lsc.params(15.0)
+    cur, last, Tc, Tl = _ragged_last(p)
+    init = _init_io(len(cur), 256, 1)
+    got = match.search_lines_by_projection_batch(p, cur, last, Tc, Tl, line_xyz=init[0], line_has=init[1])
+    assert _check_last(p, cur, last, Tc, Tl, got, init) > 100
+    assert got[1][0] == 0 and got[1][1] == 0 and got[1][2] > 30            # empty last frame / no keylines; 256 x 256
+    assert got[1][6] < 60                                                   # the few-keylines frame: most lines lose
+
+
+@pytest.mark.parametrize("th", [1.0, 5.0])
+def test_local_ragged_batch_matches_model(th):
+    """Nine ragged frames in one call of the device-indexed form (th 1, and 5 as after a relocalisation)."""
+    from manhattanslam_amd import match
+    p = lsc.params(th)
+    cur, local, T = _ragged_local(p)
+    init = _init_io(len(cur), 256, 2)
+    got = match.search_local_lines_batch(p, cur, local, T, line_xyz=init[0], line_has=init[1])
+    assert _check_local(p, cur, local, T, got, init) > 30
+    assert got[1][0] == 0 and got[2][0] == 0 and got[2][1] == 0 and got[1][3] > 2000
+    levels = np.concatenate([t["scale_level"][v == 1] for t, v in zip(got[4], got[3])])
+    assert {-1, 8, 9} <= set(levels.tolist())                               # the distance-window ends are in view
+
+
+def test_deterministic_and_independent_of_the_batch():
+    """The same frames give the same bytes twice, on a handle, and inside a batch of another composition."""
+    from manhattanslam_amd import match
+    from manhattanslam_amd.match import Matcher
+    p, pl = lsc.params(15.0), lsc.params(5.0)
+    cur, last, Tc, Tl = _ragged_last(p)
+    a = match.search_lines_by_projection_batch(p, cur, last, Tc, Tl, lcap=256, llcap=256)
+    m = Matcher()
+    b = m.search_lines_by_projection_batch(p, cur, last, Tc, Tl, lcap=256, llcap=256)
+    idx = [6, 2, 4]
+    c = m.search_lines_by_projection_batch(p, [cur[i] for i in idx], [last[i] for i in idx], Tc[idx], Tl[idx], lcap=256, llcap=256)
+    for f in range(len(cur)):
+        assert np.array_equal(a[0][f], b[0][f]) and a[2][f].tobytes() == b[2][f].tobytes()
+    for k, i in enumerate(idx):
+        assert np.array_equal(a[0][i], c[0][k]) and a[1][i] == c[1][k] and a[2][i].tobytes() == c[2][k].tobytes()
+    cur, local, T = _ragged_local(pl)
+    a = match.search_local_lines_batch(pl, cur, local, T, mlcap=4000)
+    b = m.search_local_lines_batch(pl, cur, local, T, mlcap=4000)
+    c = m.search_local_lines_batch(pl, [cur[i] for i in idx], [local[i] for i in idx], T[idx], mlcap=4000)
+    for f in range(len(cur)):
+        assert np.array_equal(a[0][f], b[0][f]) and a[4][f].tobytes() == b[4][f].tobytes() and a[5][f].tobytes() == b[5][f].tobytes()
+    for k, i in enumerate(idx):
+        assert np.array_equal(a[0][i], c[0][k]) and a[2][i] == c[2][k] and a[4][i].tobytes() == c[4][k].tobytes()
+    m.close()
+
+
+@pytest.mark.parametrize("what", ["lcap", "llcap", "mlcap", "nlevels"])
+def test_limits_are_refused_without_a_launch(what):
+    """lcap > 256, llcap > 256, mlcap > 32768 or nlevels > 16: MSL_ERR_INVALID with a message, outputs untouched (both forms)."""
+    from manhattanslam_amd import LINE_TRACK_DTYPE, match
+    from manhattanslam_amd._lib import MSL_MEM_HOST, lib, ptr
+    from manhattanslam_amd.match import Matcher
+    p, pl = lsc.params(15.0), lsc.params(1.0)
+    if what == "nlevels":
+        p["nlevels"] = 17; pl["nlevels"] = 17
+    c, l, t, tl = lsc.frame_pair(700, p, n_kl=8, n_last=8)
+    cl, ll, tt = lsc.local_frame(701, pl, n_kl=8, n_local=8)
+    lcap = 257 if what == "lcap" else 8
+    llcap = 257 if what == "llcap" else 8
+    mlcap = 32769 if what == "mlcap" else 8
+    m = Matcher()
+    mo = np.full(lcap, -7, np.int32); nm = np.full(1, -7, np.int32); ntm = np.full(1, -7, np.int32)
+    lx = np.full((lcap, 6), 7.0); lh = np.full(lcap, 7, np.uint8); inv = np.full(mlcap, 7, np.uint8); trk = np.zeros(mlcap, LINE_TRACK_DTYPE)
+    if what != "mlcap":
+        _, _, arrays = match.pack_lines_last([c], [l], t[None], tl[None], lcap=lcap, llcap=llcap)
+        args = (1, lcap, llcap, ptr(p), *[ptr(a) for a in arrays], MSL_MEM_HOST, ptr(mo), ptr(nm), ptr(lx), ptr(lh), MSL_MEM_HOST)
+        assert lib.msl_match_lines_by_projection(m.h, *args) == -1 and b"llcap <= 256" in lib.msl_last_error()
+        assert lib.msl_match_lines_by_projection_batch(0, *args) == -1
+    if what != "llcap":
+        _, _, arrays = match.pack_local_lines([cl], [ll], tt[None], lcap=lcap, mlcap=mlcap)
+        args = (1, lcap, mlcap, ptr(pl), *[ptr(a) for a in arrays], MSL_MEM_HOST, ptr(mo), ptr(ntm), ptr(nm), ptr(inv), ptr(trk), ptr(lx), ptr(lh),
+                MSL_MEM_HOST)
+        assert lib.msl_match_local_lines(m.h, *args) == -1 and b"mlcap <= 32768" in lib.msl_last_error()
+        assert lib.msl_match_local_lines_batch(0, *args) == -1
+    assert np.all(mo == -7) and nm[0] == -7 and ntm[0] == -7 and np.all(lx == 7.0) and np.all(lh == 7) and np.all(inv == 7)
+    # the handle is still good afterwards
+    p = lsc.params(15.0)
+    _check_last(p, [c], [l], t[None], tl[None], m.search_lines_by_projection_batch(p, [c], [l], t[None], tl[None]),
+                (np.zeros((1, 8, 6)), np.zeros((1, 8), np.uint8)))
+    m.close()
+
+
+def _line_fn(ends):
+    """Frame::mvKeyLineFunctions: the normalised line through the two endpoints (homogeneous)."""
+    a = np.concatenate([ends[:, :2], np.ones((len(ends), 1))], 1)
+    b = np.concatenate([ends[:, 2:], np.ones((len(ends), 1))], 1)
+    l = np.cross(a, b)
+    return l / np.hypot(l[:, 0], l[:, 1])[:, None]
+
+
+def test_device_chain_points_and_lines_into_pose():
+    """One handle, device-resident tensors, in order: msl_match_by_projection -> msl_match_lines_by_projection -> cur_line_flags derived on the
+    device -> msl_match_local_lines (line_xyz / line_has in place) -> msl_pose_optimize with line_xyz / line_has straight from the matcher.
+    Every matcher output equals the model; n_good, the point and line outlier flags and Tcw_out equal tests/pose_model.py fed the same arrays."""
+    import torch
+    from manhattanslam_amd import KEYLINE_DTYPE, KEYPOINT_DTYPE, MATCH_PARAMS_DTYPE, match, pose
+    from manhattanslam_amd.match import Matcher
+    from tests import local_match_scenes as ls
+    from tests import match_scenes as ms
+    from tests import pose_scenes as ps
+    from tests.test_pose_gpu import _check as check_pose
+    p = ls.params(3.0)
+    pll, plo = lsc.params(15.0), lsc.params(1.0)
+    c = ps.params(); c.update(fx=float(p["fx"][0]), fy=float(p["fy"][0]), cx=float(p["cx"][0]), cy=float(p["cy"][0]), bf=float(p["bf"][0]))
+    pm_ = ms.params(None, 7.0, False, dtype=MATCH_PARAMS_DTYPE)
+    B = 3
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a.view(np.uint8) if a.dtype in (KEYPOINT_DTYPE, KEYLINE_DTYPE) else a)).cuda()
+    # points: the current frame and its local points through the true pose; the last frame = the first 900 of them
+    frames = [ls.random_frame(80 + f, p, n_cur=800 + 50 * f, n_local=1200) for f in range(B)]
+    cur = [x for x, _, _ in frames]; T = np.stack([t for _, _, t in frames])
+    cap, _, arrays = match.pack_local_points(cur, [l for _, l, _ in frames], T)
+    kps, un, ur, cell, cdesc, ncur = arrays[:6]
+    rng = np.random.default_rng(11)
+    lxyz = np.zeros((B, cap, 3), np.float32); ld = np.zeros((B, cap, 32), np.uint8); lfl = np.zeros((B, cap), np.uint8)
+    loc = np.zeros((B, cap), np.int32)
+    for f, (_, l, _) in enumerate(frames):
+        lxyz[f, :900] = l["xyz"][:900]; ld[f, :900] = l["desc"][:900]; lfl[f, :900] = l["flags"][:900] | 1; loc[f, :900] = rng.integers(0, 8, 900)
+    # lines: last-frame lines and local map lines seen from the same poses
+    lp = [lsc.frame_pair(90 + f, pll, n_kl=40, n_last=40, noise=0.3, angle_mode="slope", T=T[f]) for f in range(B)]
+    lcur = [q[0] for q in lp]; llast = [q[1] for q in lp]
+    # local map lines: the last frame's lines (candidates unless this frame holds them) followed by 600 others
+    lloc = []
+    for f in range(B):
+        _, lo, _ = lsc.local_frame(95 + f, plo, n_kl=40, n_local=600, T=T[f])
+        held, _ = lmm.search_lines_by_projection(pll, lcur[f], llast[f], T[f], T[f])
+        Ow = -T[f][:3, :3].astype(np.float64).T @ T[f][:3, 3].astype(np.float64)
+        mid = 0.5 * (llast[f]["xyz"][:, :3] + llast[f]["xyz"][:, 3:]) - Ow
+        dist = np.linalg.norm(mid, axis=1)
+        seen = np.isin(np.arange(len(mid)), held[held >= 0])
+        lloc.append(dict(xyz=np.concatenate([llast[f]["xyz"], lo["xyz"]]), normal=np.concatenate([mid / dist[:, None], lo["normal"]]),
+                         dist=np.concatenate([np.stack([dist * 0.2, dist * 1.1], 1).astype(np.float32), lo["dist"]]),
+                         desc=np.concatenate([llast[f]["desc"], lo["desc"]]),
+                         flags=np.concatenate([np.where(seen, 2, 3).astype(np.uint8), lo["flags"]])))
+    lcap, llcap, larr = match.pack_lines_last(lcur, llast, T, T)
+    d_kl, d_ldesc, d_nkl = dev(larr[0]), dev(larr[1]), dev(larr[2])
+    d_llast_fl = dev(larr[5])
+    m = Matcher()
+    zeros = lambda shape, dt: torch.zeros(shape, dtype=dt, device="cuda")
+    out = torch.full((B, cap), -7, dtype=torch.int32, device="cuda"); nmp = zeros(B, torch.int32)
+    lmo = torch.full((B, lcap), -7, dtype=torch.int32, device="cuda"); lnm = zeros(B, torch.int32)
+    line_xyz = zeros((B, lcap, 6), torch.float64); line_has = zeros((B, lcap), torch.uint8); d_angle = zeros((B, cap), torch.float32)
+    torch.cuda.synchronize()
+    m.search_by_projection_device(pm_, B, cap, [dev(kps), dev(un), dev(ur), dev(cell), dev(cdesc), dev(ncur), dev(lxyz), dev(ld), dev(lfl),
+                                                dev(loc), d_angle, dev(np.full(B, 900, np.int32)), dev(T[:, :3, :4].copy()),
+                                                dev(T[:, :3, :4].copy())], out, nmp)
+    m.search_lines_by_projection_device(pll, B, lcap, llcap, [d_kl, d_ldesc, d_nkl] + [dev(a) for a in larr[3:5]] + [d_llast_fl] +
+                                        [dev(a) for a in larr[6:]], lmo, lnm, line_xyz, line_has)
+    m.sync()                                                         # torch reads lmo on its own stream
+    held = lmo >= 0
+    obs = torch.where(held, (torch.gather(d_llast_fl, 1, lmo.clamp(min=0).long()) >> 1) & 1, torch.zeros_like(line_has))
+    d_cfl = (held.to(torch.uint8) | (obs << 1)).contiguous()
+    _, mlcap, loarr = match.pack_local_lines([dict(x, flags=np.zeros(len(x["kl"]), np.uint8)) for x in lcur], lloc, T, lcap=lcap)
+    lo_mo = torch.full((B, lcap), -7, dtype=torch.int32, device="cuda"); lo_ntm = zeros(B, torch.int32); lo_nm = zeros(B, torch.int32)
+    torch.cuda.synchronize()                                         # d_cfl and the fills are done before the matcher's stream reads them
+    lx_after_last = (line_xyz.cpu().numpy().copy(), line_has.cpu().numpy().copy())
+    m.search_local_lines_device(plo, B, lcap, mlcap, [d_kl, d_ldesc, d_nkl, d_cfl] + [dev(a) for a in loarr[4:]], lo_mo, lo_ntm, lo_nm,
+                                line_xyz=line_xyz, line_has=line_has)
+    # pose: points through pt_ref = the last-frame match, lines straight from the matcher
+    rngp = np.random.default_rng(5)
+    Tin = np.zeros((B, 12), np.float32)
+    for f in range(B):
+        R0 = ps.rot(rngp.normal(size=3), 1.0) @ T[f][:3, :3].astype(np.float64)
+        Tin[f] = ps.tcw12(R0, T[f][:3, 3] + rngp.normal(size=3) * 0.02)
+    line_fn = np.zeros((B, lcap, 3))
+    for f in range(B):
+        line_fn[f, :len(lcur[f]["kl"])] = _line_fn(lcur[f]["ends"])
+    pcap = 1
+    inputs = [dev(kps), dev(un), dev(ur), out, dev(ncur), dev(lxyz), dev(line_fn), line_xyz, line_has, d_nkl, zeros((B, pcap, 4), torch.float32),
+              zeros((B, pcap, 12), torch.float32), zeros((B, pcap), torch.uint8), zeros(B, torch.int32), dev(Tin)]
+    io = [zeros((B, cap), torch.uint8), zeros((B, lcap), torch.uint8), zeros((B, pcap, 3), torch.uint8)]
+    Tout = zeros((B, 12), torch.float32); ng = zeros(B, torch.int32)
+    torch.cuda.synchronize()                                         # the zero fills above ran on torch's stream
+    pose.pose_optimization_device(m, pose.pose_params(c), B, (cap, cap, lcap, pcap), inputs, io, Tout, ng)
+    m.sync()
+    # the matcher stages against the model
+    lmo_h, lnm_h = lmo.cpu().numpy(), lnm.cpu().numpy()
+    _check_last(pll, lcur, llast, T, T, ([lmo_h[f, :40] for f in range(B)], lnm_h, *lx_after_last), (np.zeros((B, lcap, 6)), np.zeros((B, lcap), np.uint8)))
+    cfl = d_cfl.cpu().numpy()
+    lcur_l = [dict(x, flags=cfl[f, :len(x["kl"])]) for f, x in enumerate(lcur)]
+    lx_h, lh_h = line_xyz.cpu().numpy(), line_has.cpu().numpy()
+    for f in range(B):
+        wm, wntm, wnm, _, _ = lmm.search_local_lines(plo, lcur_l[f], lloc[f], T[f])
+        assert np.array_equal(lo_mo.cpu().numpy()[f, :40], wm) and lo_nm.cpu().numpy()[f] == wnm and lo_ntm.cpu().numpy()[f] == wntm
+        wx, wh = lmm.pose_layout(wm, lloc[f]["xyz"], lcap, lx_after_last[0][f], lx_after_last[1][f], clear=False)
+        assert lx_h[f].tobytes() == wx.tobytes() and np.array_equal(lh_h[f], wh)
+    # the pose stage against the model fed the same arrays
+    ref_h, out_h, lout_h = out.cpu().numpy(), io[0].cpu().numpy(), io[1].cpu().numpy()
+    model_frames, got = [], []
+    for f in range(B):
+        n, nl = len(cur[f]["kps"]), len(lcur[f]["kl"])
+        fr = ps.empty(n, nl, 0, cap)
+        fr.update(octave=cur[f]["kps"]["octave"].astype(np.int32), un_xy=cur[f]["un_xy"], uright=cur[f]["uright"], pt_ref=ref_h[f, :n],
+                  xyz=lxyz[f], line_fn=line_fn[f, :nl], line_xyz=lx_h[f, :nl], line_has=lh_h[f, :nl], Tcw=Tin[f])
+        ps.check_margin(fr, c)
+        model_frames.append(fr)
+        got.append((int(ng[f]), Tout[f].cpu().numpy(), dict(outlier=out_h[f, :n], line_outlier=lout_h[f, :nl], plane_outlier=np.zeros(0, np.uint8),
+                                                           par_outlier=np.zeros(0, np.uint8), ver_outlier=np.zeros(0, np.uint8))))
+        assert lh_h[f, :nl].sum() >= 10 and (ref_h[f, :n] >= 0).sum() > 150          # line and point edges in every frame
+        assert (lo_mo.cpu().numpy()[f] >= 0).sum() + (lmo_h[f] >= 0).sum() >= 10
+    check_pose(c, model_frames, got)
+    m.close()
+
+
+def test_one_handle_grows_its_buffers_across_point_line_and_pose_calls(oracle):
+    """Host-form calls on one Matcher: last-frame points, last-frame lines, local lines and pose take turns, each call larger than the last of
+    its kind, so each grows buffers of the shared handle.  Every result is the oracle's or the model's."""
+    from manhattanslam_amd import MATCH_PARAMS_DTYPE, pose
+    from manhattanslam_amd.match import Matcher
+    from tests import match_scenes as ms
+    from tests import oracle_lib
+    from tests import pose_scenes as ps
+    from tests.test_pose_gpu import _check as check_pose
+    c = ps.params()
+    pp, pbp, pll, plo = pose.pose_params(c), ms.params(None, 15, True, dtype=MATCH_PARAMS_DTYPE), lsc.params(15.0), lsc.params(1.0)
+    m = Matcher()
+    for r, (n_cur, n_kl, n_loc, n_pts) in enumerate(((200, 10, 300, 80), (600, 60, 1500, 400), (1016, 200, 5000, 1500))):
+        pairs = [ms.random_pair(800 + 10 * r + j, pbp, n_cur=n_cur - 40 * j, n_last=n_cur - 60 * j) for j in range(2)]
+        cur = [q[0] for q in pairs]; last = [q[1] for q in pairs]; Tc = np.stack([q[2] for q in pairs]); Tl = np.stack([q[3] for q in pairs])
+        got, nm = m.search_by_projection_batch(pbp, cur, last, Tc, Tl)
+        for f in range(2):
+            want, n = oracle_lib.search_by_projection(pbp, cur[f], last[f], Tc[f], Tl[f])
+            assert nm[f] == n and np.array_equal(got[f], want), (r, f)
+        lp = [lsc.frame_pair(820 + 10 * r + j, pll, n_kl=n_kl, n_last=n_kl + 10 * r) for j in range(2)]
+        lc = [q[0] for q in lp]; ll = [q[1] for q in lp]
+        zero = (np.zeros((2, n_kl, 6)), np.zeros((2, n_kl), np.uint8))
+        _check_last(pll, lc, ll, np.stack([q[2] for q in lp]), np.stack([q[3] for q in lp]),
+                    m.search_lines_by_projection_batch(pll, lc, ll, np.stack([q[2] for q in lp]), np.stack([q[3] for q in lp])), zero)
+        fr = [lsc.local_frame(840 + 10 * r + j, plo, n_kl=n_kl, n_local=n_loc) for j in range(2)]
+        lc = [q[0] for q in fr]; lo = [q[1] for q in fr]; T = np.stack([q[2] for q in fr])
+        _check_local(plo, lc, lo, T, m.search_local_lines_batch(plo, lc, lo, T), zero)
+        frames = [ps.scene(860 + 10 * r + j, n_pts=n_pts - 20 * j, n_lines=4 * (r + 1), n_planes=r + 1, c=c)[0] for j in range(2)]
+        check_pose(c, frames, pose.pose_optimization_batch(pp, frames, handle=m))
+    m.close()
