@@ -557,6 +557,39 @@ MSL_API int msl_pose_optimize_batch(int device, int n_frames, int cap, int xcap,
                                     const uint8_t *plane_has, const int32_t *n_planes, const float *Tcw, msl_mem mem, uint8_t *outlier,
                                     uint8_t *line_outlier, uint8_t *plane_outlier, float *Tcw_out, int32_t *n_good, msl_mem out_mem) MSL_NOEXCEPT;
 
+/* ---- Translation-only optimisation (Manhattan mode): Optimizer::TranslationOptimization (src/Optimizer.cc:592-1009) ----
+ * n_frames independent calls of  int Optimizer::TranslationOptimization(Frame *pFrame), the optimiser of
+ * Tracking::TranslationWithMotionModel (src/Tracking.cc:946-1050), on the same solver as msl_pose_optimize.  Every input has the
+ * layout, meaning and limits of msl_pose_optimize, so the matchers' outputs and manhattanslam_amd.pose.pack feed it unchanged, except:
+ *   Rcw[9 f..]  optional (NULL = absent): the CV_32F manhattanRcw of frame f, row-major.  It replaces rows 0-2 / columns 0-2 of that
+ *               frame's Tcw before anything else, as mTcw's rotation block is overwritten at src/Tracking.cc:974.
+ *   Planes      only plane_has bit 0 and plane_w[12 k + 0..3] (mvpMapPlanes) are read; only plane_outlier[3 k + 0] is written.  The
+ *               bytes s = 1, 2 are left untouched (no parallel or vertical plane edges are created here).
+ * Edges: EdgeSE3ProjectXYZOnlyTranslation / EdgeStereoSE3ProjectXYZOnlyTranslation / EdgeLineProjectXYZOnlyTranslation with
+ * Xc = R_cw * Xw as a float product (line endpoints rounded to float first, :755-756 / :781-782), EdgePlaneOnlyTranslation with the
+ * world plane flipped against the initial pose and rotated by R_cw (:836-853).  Only points count in nInitialCorrespondences; below 3 the
+ * call returns 0 (:796) after clearing the point and line flags and before any plane edge exists, so the plane flags are untouched.  The
+ * classification (:880-1000) recomputes line errors only for flagged lines and does not count bad lines; bad planes count in nBad.
+ * Out: n_good[f] = nInitialCorrespondences - nBad (it can be negative), or 0; Tcw_out[12] the optimised pose as Frame::SetPose stores
+ * it (the rotation has been through the quaternion round trip), or on the early return the input pose with Rcw written in.
+ * Asynchronous on the matcher handle's stream when inputs and outputs are device memory; with host memory on either side it returns
+ * when the caller's buffers are its own again.  Rcw is in `mem` memory like the other inputs. */
+MSL_API int msl_pose_optimize_translation(msl_match *h, int n_frames, int cap, int xcap, int lcap, int pcap, const msl_pose_params *params,
+                                          const msl_keypoint *kps, const float *un_xy, const float *uright, const int32_t *pt_ref,
+                                          const int32_t *n_kps, const float *xyz, const double *line_fn, const double *line_xyz,
+                                          const uint8_t *line_has, const int32_t *n_lines, const float *plane_coef, const float *plane_w,
+                                          const uint8_t *plane_has, const int32_t *n_planes, const float *Tcw, const float *Rcw, msl_mem mem,
+                                          uint8_t *outlier, uint8_t *line_outlier, uint8_t *plane_outlier, float *Tcw_out, int32_t *n_good,
+                                          msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device matcher handle, always synchronous; see msl_match_by_projection_batch). */
+MSL_API int msl_pose_optimize_translation_batch(int device, int n_frames, int cap, int xcap, int lcap, int pcap, const msl_pose_params *params,
+                                                const msl_keypoint *kps, const float *un_xy, const float *uright, const int32_t *pt_ref,
+                                                const int32_t *n_kps, const float *xyz, const double *line_fn, const double *line_xyz,
+                                                const uint8_t *line_has, const int32_t *n_lines, const float *plane_coef, const float *plane_w,
+                                                const uint8_t *plane_has, const int32_t *n_planes, const float *Tcw, const float *Rcw,
+                                                msl_mem mem, uint8_t *outlier, uint8_t *line_outlier, uint8_t *plane_outlier, float *Tcw_out,
+                                                int32_t *n_good, msl_mem out_mem) MSL_NOEXCEPT;
+
 /* Batched form: n_frames keyframes in order, semantically n_frames consecutive msl_sf_fuse_resident calls.
  * Keyframe f's images start at base + f * <frame_stride> bytes (member_frame_stride may be 0: one shared
  * membership image); refs[n_frames] and poses (16 * n_frames floats, column-major Twc each) are host arrays.

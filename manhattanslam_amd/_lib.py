@@ -105,6 +105,8 @@ SIGNATURES = {
     "msl_match_local_lines_batch": (_i, [_i, _i, _i, _i] + [_vp] * 12 + [_i] + [_vp] * 7 + [_i]),
     "msl_pose_optimize": (_i, [_vp, _i, _i, _i, _i, _i] + [_vp] * 16 + [_i] + [_vp] * 5 + [_i]),
     "msl_pose_optimize_batch": (_i, [_i, _i, _i, _i, _i, _i] + [_vp] * 16 + [_i] + [_vp] * 5 + [_i]),
+    "msl_pose_optimize_translation": (_i, [_vp, _i, _i, _i, _i, _i] + [_vp] * 17 + [_i] + [_vp] * 5 + [_i]),
+    "msl_pose_optimize_translation_batch": (_i, [_i, _i, _i, _i, _i, _i] + [_vp] * 17 + [_i] + [_vp] * 5 + [_i]),
     "msl_sf_fuse_resident": (_i, [_vp, _i, _vp, _sz, _vp, _sz, _vp, _sz, _i, _vp]),
     "msl_sf_set_batch_capacity": (_i, [_vp, _i]),
     "msl_sf_fuse_resident_batch": (_i, [_vp, _i, _vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _sz, _sz, _i, _vp]),

@@ -11,7 +11,7 @@ struct msl_match {
     msl::DevBuf in[14], items, cellStart, mode, cand, candCnt, out[3];   // staged inputs (host-memory calls), scratch, staged outputs
     msl::DevBuf da, db, dout;                                          // msl_match_descriptor_distance
     msl::DevBuf lin[14], trk, inView;                                  // msl_match_local_points: staged inputs, per-point scratch
-    msl::DevBuf poseIn[15], poseOut[5];                                // msl_pose_optimize: staged inputs, staged in/out flags and outputs
+    msl::DevBuf poseIn[16], poseOut[5];                                // msl_pose_optimize[_translation]: staged inputs (+ Rcw), in/out flags, outputs
     msl::DevBuf lineIn[11], lineQ, lineTrk, lineView, lineIo[2];       // the line searches: staged inputs, per-line queries / tracks / in-view, line_xyz / line_has
     bool lineAttrSet = false;
     bool localAttrSet = false;

@@ -1,5 +1,5 @@
-"""Host mirror of Optimizer::PoseOptimization (reference src/Optimizer.cc:53-590) through the C ABI (msl_pose_optimize[_batch]) for a batch
-of independent frames.  A frame is a dict of numpy arrays -- the per-frame inputs of include/msl.h, named as in tests/pose_model.py:
+"""Host mirror of Optimizer::PoseOptimization (reference src/Optimizer.cc:53-590) and of Optimizer::TranslationOptimization (:592-1009,
+Manhattan mode) through the C ABI (msl_pose_optimize[_batch], msl_pose_optimize_translation[_batch]) for a batch of independent frames.  A frame is a dict of numpy arrays -- the per-frame inputs of include/msl.h, named as in tests/pose_model.py:
   octave (N,) i32, un_xy (N,2) f32, uright (N,) f32, pt_ref (N,) i32 (-1 = no MapPoint), xyz (X,3) f32, outlier (N,) u8
   line_fn (NL,3) f64, line_xyz (NL,6) f64, line_has (NL,) u8, line_outlier (NL,) u8
   plane_coef (M,4) f32, plane_w / par_w / ver_w (M,4) f32, plane_has / par_has / ver_has (M,) u8,
@@ -82,3 +82,33 @@ def pose_optimization_device(handle, params, n_frames, caps, arrays, io, Tcw_out
     cap, xcap, lcap, pcap = caps
     check(lib.msl_pose_optimize(handle.h, n_frames, cap, xcap, lcap, pcap, ptr(params), *[ptr(a) for a in arrays], 1,
                                 *[ptr(a) for a in io], ptr(Tcw_out), ptr(n_good), 1), "msl_pose_optimize")
+
+
+def _rcw(rcw, n_frames):
+    """None, or the Manhattan rotations as a contiguous (n_frames, 9) float32 array (row-major 3 x 3 per frame)."""
+    if rcw is None:
+        return None
+    return np.ascontiguousarray(np.asarray(rcw, np.float32).reshape(n_frames, 9))
+
+
+def translation_optimization_batch(params, frames, rcw=None, device=0, handle=None, caps=None):
+    """Optimizer::TranslationOptimization for a batch of frames (host arrays, synchronous).  rcw: None (each frame's Tcw is used as given)
+    or the frames' manhattanRcw, (n_frames, 3, 3) or (n_frames, 9) float32, written into Tcw's rotation block first (src/Tracking.cc:974).
+    Only plane_has / plane_w / plane_outlier of the mvpMapPlanes kind are used.  Returns unpack(...) as pose_optimization_batch does."""
+    (cap, xcap, lcap, pcap), arrays, io = pack(frames, *(caps or ()))
+    F = len(frames)
+    r = _rcw(rcw, F)
+    Tout = np.zeros((F, 12), np.float32)
+    ng = np.zeros(F, np.int32)
+    call("msl_pose_optimize_translation", handle, device, F, cap, xcap, lcap, pcap, ptr(params), *[ptr(a) for a in arrays],
+         ptr(r), MSL_MEM_HOST, *[ptr(a) for a in io], ptr(Tout), ptr(ng), MSL_MEM_HOST)
+    return unpack(frames, io, Tout, ng)
+
+
+def translation_optimization_device(handle, params, n_frames, caps, arrays, io, Tcw_out, n_good, rcw=None):
+    """The device form on a match.Matcher handle, as pose_optimization_device; rcw is None or a (n_frames, 9) float32 tensor on the
+    handle's device.  Asynchronous on the handle's stream (handle.sync())."""
+    cap, xcap, lcap, pcap = caps
+    check(lib.msl_pose_optimize_translation(handle.h, n_frames, cap, xcap, lcap, pcap, ptr(params), *[ptr(a) for a in arrays],
+                                            ptr(rcw), 1, *[ptr(a) for a in io], ptr(Tcw_out), ptr(n_good), 1),
+          "msl_pose_optimize_translation")
