@@ -622,8 +622,11 @@ MSL_API int msl_sf_set_stream(msl_sf *h, void *hip_stream) MSL_NOEXCEPT;
  * call staged (frame f at *gray_dev + f * *frame_stride, rows *row_stride bytes apart) and a hipEvent_t, owned by the handle, that completes when
  * their copy has.  msl_orb_wait_event makes the extractor's stream wait for such an event; msl_orb_extract_batch(..., MSL_MEM_DEVICE, ...) then reads
  * the images in place.  The staged images stay valid until the SECOND next host-image batch is enqueued on the surfel handle: the caller lets the
- * extraction of batch k return before it enqueues batch k + 2 (msl_orb_extract_batch with host outputs is synchronous).  MSL_ERR_INVALID when the
- * handle's last batch had no host images. */
+ * extraction of batch k return before it enqueues batch k + 2 (msl_orb_extract_batch with host outputs is synchronous).  Three calls free them
+ * sooner: msl_sf_set_batch_capacity with a new capacity, a host-image batch whose images take more bytes per frame than the staged ones, and a
+ * device-memory msl_sf_fuse_resident_batch_d16 batch whose converted depth does not fit the staged depth slots.  Each waits for the surfel
+ * handle's own streams only, not for work another handle enqueued on the images: the caller lets that work return first.  MSL_ERR_INVALID when
+ * the handle's last batch had no host images. */
 MSL_API int msl_sf_staged_gray(msl_sf *h, const uint8_t **gray_dev, size_t *row_stride, size_t *frame_stride, void **uploaded_event) MSL_NOEXCEPT;
 
 

@@ -36,18 +36,30 @@ int bind_device(int device);  // hipSetDevice + gfx950 check; returns msl_status
 // Afterwards p holds at least `need` bytes (old contents not kept), or nothing (p = nullptr, cap = 0) when the allocation failed.
 hipError_t grow(void *&p, size_t &cap, size_t need);
 
-// A device buffer owned by a handle and freed with it (a per-frame caller pays no hipMalloc).  Never in static storage: a hipFree run by a
-// static destructor after the HIP runtime has been torn down crashes the process at exit.
-struct DevBuf {
+// A device (DevBuf) or pinned host (PinBuf) buffer owned by a handle and freed with it (a per-frame caller pays no allocation).  Never in static
+// storage: a free run by a static destructor after the HIP runtime has been torn down crashes the process at exit.  Moving leaves the source
+// empty; assigning an empty buffer (`b = DevBuf()`) releases the memory.
+enum class Mem { Device, Pinned };
+template <Mem M>
+struct Buf {
     void *p = nullptr;
     size_t cap = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { if (p) (void)hipFree(p); }
+    Buf() = default;
+    Buf(Buf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    Buf &operator=(Buf &&o) noexcept {
+        if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~Buf() { release(); }
     // Growing waits for st first: an earlier asynchronous call may still use the memory about to be replaced.
     hipError_t grow(size_t need, hipStream_t st);
+  private:
+    void release();
 };
+extern template struct Buf<Mem::Device>;   // (both defined in msl_common.hip)
+extern template struct Buf<Mem::Pinned>;
+using DevBuf = Buf<Mem::Device>;
+using PinBuf = Buf<Mem::Pinned>;
 
 struct Need { DevBuf &buf; size_t bytes; };
 hipError_t grow_all(hipStream_t st, std::initializer_list<Need> bufs);   // scratch: every buffer grown to its size

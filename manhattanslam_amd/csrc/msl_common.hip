@@ -41,11 +41,26 @@ hipError_t grow(void *&p, size_t &cap, size_t need) {
     return e;
 }
 
-hipError_t DevBuf::grow(size_t need, hipStream_t st) {
-    if (need <= cap) return hipSuccess;
-    const hipError_t e = hipStreamSynchronize(st);
-    return e != hipSuccess ? e : msl::grow(p, cap, need);
+template <Mem M>
+void Buf<M>::release() {
+    if (p) (void)(M == Mem::Device ? hipFree(p) : hipHostFree(p));
+    p = nullptr; cap = 0;
 }
+
+template <Mem M>
+hipError_t Buf<M>::grow(size_t need, hipStream_t st) {
+    if (need <= cap) return hipSuccess;
+    hipError_t e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return e;
+    release();
+    e = M == Mem::Device ? hipMalloc(&p, need) : hipHostMalloc(&p, need, hipHostMallocDefault);
+    if (e == hipSuccess) cap = need;
+    else p = nullptr;
+    return e;
+}
+
+template struct Buf<Mem::Device>;
+template struct Buf<Mem::Pinned>;
 
 hipError_t grow_all(hipStream_t st, std::initializer_list<Need> bufs) {
     for (const Need &b : bufs) {

@@ -1109,36 +1109,34 @@ struct msl_orb {
     int geomW = 0, geomH = 0;
     OrbDev dev{};
     hipStream_t stream = nullptr; bool ownStream = true;
-    // device allocations
-    uint8_t *d_in = nullptr; size_t inPitch = 0;
-    uint8_t *d_pyr = nullptr, *d_blur = nullptr;
-    CellDev *d_cells = nullptr; ResizeTap *d_taps = nullptr; PyrRange *d_pyrRanges = nullptr; size_t pyrLds = 0;
-    uint32_t *d_cellCnt = nullptr, *d_cellKeys = nullptr, *d_keys = nullptr; uint16_t *d_knode = nullptr;
-    uint32_t *d_sel = nullptr; int *d_nsel = nullptr, *d_ncand = nullptr;
-    msl_keypoint *d_kps = nullptr; uint8_t *d_desc = nullptr; int *d_nout = nullptr; int *d_err = nullptr;
-    int *h_err = nullptr;  // pinned
-    uint8_t *d_outBlock = nullptr; size_t outBlockBytes = 0, outKpsOff = 0, outDescOff = 0;   // [nout[B] | kps[B][cap] | desc[B][cap]] in one allocation
-    uint8_t *h_pinIn = nullptr, *h_pinOut = nullptr; size_t pinInBytes = 0, pinOutBytes = 0;   // pinned staging of the single-frame drop-in call
+    // device allocations of the current geometry (build_geometry); outBlock = [nout[B] | kps[B][cap] | desc[B][cap]], d_nout / d_kps / d_desc point into it
+    struct Geometry { DevBuf in, pyr, blur, cells, taps, pyrRanges, cellCnt, cellKeys, keys, knode, sel, nsel, ncand, outBlock; } geo;
+    size_t inPitch = 0, pyrLds = 0, outKpsOff = 0, outDescOff = 0;
+    msl_keypoint *d_kps = nullptr; uint8_t *d_desc = nullptr; int *d_nout = nullptr;
+    DevBuf d_err; PinBuf h_err;
+    PinBuf h_pinIn, h_pinOut;   // staging of the single-frame drop-in call
     hipStream_t sideStream = nullptr; hipEvent_t evFork = nullptr, evJoin = nullptr;             // single-frame calls: the blur runs beside FAST + quadtree
-    float *d_depthIn = nullptr; size_t depthInCap = 0;     // staged depth frames (host input)
-    float *d_unXY = nullptr, *d_depthOut = nullptr, *d_uRight = nullptr; int *d_gridCell = nullptr; bool frameBufs = false;
+    DevBuf d_depthIn;           // staged depth frames (host input)
+    DevBuf d_unXY, d_depthOut, d_uRight, d_gridCell;   // outputs of the frame epilogue
     int lastFrames = 0;
     KernelProfiler prof;
 };
 
 namespace {
 
-void free_geometry(msl_orb *h) {
-    auto F = [](auto *&p) { if (p) { (void)hipFree(p); p = nullptr; } };
-    F(h->d_in); F(h->d_pyr); F(h->d_blur); F(h->d_cells); F(h->d_taps); F(h->d_pyrRanges); F(h->d_cellCnt); F(h->d_cellKeys);
-    F(h->d_keys); F(h->d_knode); F(h->d_sel); F(h->d_nsel); F(h->d_ncand); F(h->d_outBlock); h->d_kps = nullptr; h->d_desc = nullptr; h->d_nout = nullptr;
+// Waits for the work that may still use the geometry buffers (the side stream's is joined into h->stream by evJoin), then frees them.
+int free_geometry(msl_orb *h) {
+    MSL_HIP_TRY(hipStreamSynchronize(h->stream));
+    h->geo = msl_orb::Geometry();
+    h->d_kps = nullptr; h->d_desc = nullptr; h->d_nout = nullptr;
     h->geomW = h->geomH = 0;
+    return MSL_OK;
 }
 
 // Level sizes, FAST cell grid, quadtree roots, resize taps, blur tiling for a w x h frame.
 int build_geometry(msl_orb *h, int W, int H) {
     if (h->geomW == W && h->geomH == H) return MSL_OK;
-    free_geometry(h);
+    { const int rc = free_geometry(h); if (rc != MSL_OK) return rc; }
     OrbDev &D = h->dev;
     memset(&D, 0, sizeof(D));
     const int L = h->nlevels, B = h->maxBatch;
@@ -1309,38 +1307,33 @@ int build_geometry(msl_orb *h, int W, int H) {
     D.blurStride = (blurOff + 255) & ~(size_t)255;
     h->inPitch = (size_t)((W + 63) & ~63);
 
-    MSL_HIP_TRY(hipMalloc(&h->d_in, h->inPitch * H * B));
-    MSL_HIP_TRY(hipMalloc(&h->d_pyr, std::max<size_t>(D.pyrStride, 256) * B));
-    MSL_HIP_TRY(hipMalloc(&h->d_blur, D.blurStride * B));
-    MSL_HIP_TRY(hipMalloc(&h->d_cells, sizeof(CellDev) * cells.size()));
-    MSL_HIP_TRY(hipMalloc(&h->d_taps, sizeof(ResizeTap) * std::max<size_t>(taps.size(), 1)));
-    if (D.pyrTX) {
-        MSL_HIP_TRY(hipMalloc(&h->d_pyrRanges, sizeof(PyrRange) * (pyrX.size() + pyrY.size())));
-        MSL_HIP_TRY(hipMemcpy(h->d_pyrRanges, pyrX.data(), sizeof(PyrRange) * pyrX.size(), hipMemcpyHostToDevice));
-        MSL_HIP_TRY(hipMemcpy(h->d_pyrRanges + pyrX.size(), pyrY.data(), sizeof(PyrRange) * pyrY.size(), hipMemcpyHostToDevice));
-        D.pyrX = h->d_pyrRanges; D.pyrY = h->d_pyrRanges + pyrX.size();
-    }
-    MSL_HIP_TRY(hipMalloc(&h->d_cellCnt, sizeof(uint32_t) * cells.size() * B));
-    MSL_HIP_TRY(hipMalloc(&h->d_cellKeys, sizeof(uint32_t) * (size_t)keyOff * B));
-    MSL_HIP_TRY(hipMalloc(&h->d_keys, sizeof(uint32_t) * (size_t)keyOff * B));
-    MSL_HIP_TRY(hipMalloc(&h->d_knode, sizeof(uint16_t) * (size_t)keyOff * B));
-    MSL_HIP_TRY(hipMalloc(&h->d_sel, sizeof(uint32_t) * (size_t)D.selCap * L * B));
-    MSL_HIP_TRY(hipMalloc(&h->d_nsel, sizeof(int) * L * B));
-    MSL_HIP_TRY(hipMalloc(&h->d_ncand, sizeof(int) * L * B));
     // outputs of a call in ONE allocation, counts first: the single-frame drop-in call fetches everything with one copy
     h->outKpsOff = (sizeof(int) * (size_t)B + 255) & ~(size_t)255;
     h->outDescOff = h->outKpsOff + ((sizeof(msl_keypoint) * (size_t)D.outCap * B + 255) & ~(size_t)255);
-    h->outBlockBytes = h->outDescOff + (size_t)32 * D.outCap * B;
-    MSL_HIP_TRY(hipMalloc(&h->d_outBlock, h->outBlockBytes));
-    h->d_nout = reinterpret_cast<int *>(h->d_outBlock);
-    h->d_kps = reinterpret_cast<msl_keypoint *>(h->d_outBlock + h->outKpsOff);
-    h->d_desc = h->d_outBlock + h->outDescOff;
-    MSL_HIP_TRY(hipMemcpy(h->d_cells, cells.data(), sizeof(CellDev) * cells.size(), hipMemcpyHostToDevice));
+    msl_orb::Geometry &g = h->geo;
+    MSL_HIP_TRY(grow_all(h->stream, {{g.in, h->inPitch * H * B}, {g.pyr, std::max<size_t>(D.pyrStride, 256) * B}, {g.blur, D.blurStride * B},
+                                     {g.cells, sizeof(CellDev) * cells.size()}, {g.taps, sizeof(ResizeTap) * std::max<size_t>(taps.size(), 1)},
+                                     {g.pyrRanges, D.pyrTX ? sizeof(PyrRange) * (pyrX.size() + pyrY.size()) : 0},
+                                     {g.cellCnt, sizeof(uint32_t) * cells.size() * B}, {g.cellKeys, sizeof(uint32_t) * (size_t)keyOff * B},
+                                     {g.keys, sizeof(uint32_t) * (size_t)keyOff * B}, {g.knode, sizeof(uint16_t) * (size_t)keyOff * B},
+                                     {g.sel, sizeof(uint32_t) * (size_t)D.selCap * L * B}, {g.nsel, sizeof(int) * L * B}, {g.ncand, sizeof(int) * L * B},
+                                     {g.outBlock, h->outDescOff + (size_t)32 * D.outCap * B}}));
+    if (D.pyrTX) {
+        PyrRange *ranges = (PyrRange *)g.pyrRanges.p;
+        MSL_HIP_TRY(hipMemcpy(ranges, pyrX.data(), sizeof(PyrRange) * pyrX.size(), hipMemcpyHostToDevice));
+        MSL_HIP_TRY(hipMemcpy(ranges + pyrX.size(), pyrY.data(), sizeof(PyrRange) * pyrY.size(), hipMemcpyHostToDevice));
+        D.pyrX = ranges; D.pyrY = ranges + pyrX.size();
+    }
+    uint8_t *out = (uint8_t *)g.outBlock.p;
+    h->d_nout = reinterpret_cast<int *>(out);
+    h->d_kps = reinterpret_cast<msl_keypoint *>(out + h->outKpsOff);
+    h->d_desc = out + h->outDescOff;
+    MSL_HIP_TRY(hipMemcpy(g.cells.p, cells.data(), sizeof(CellDev) * cells.size(), hipMemcpyHostToDevice));
     if (!taps.empty())
-        MSL_HIP_TRY(hipMemcpy(h->d_taps, taps.data(), sizeof(ResizeTap) * taps.size(), hipMemcpyHostToDevice));
-    D.pyr = h->d_pyr; D.blur = h->d_blur; D.cells = h->d_cells; D.taps = h->d_taps;
-    D.cellCnt = h->d_cellCnt; D.cellKeys = h->d_cellKeys; D.keys = h->d_keys; D.knode = h->d_knode;
-    D.sel = h->d_sel; D.nsel = h->d_nsel; D.ncand = h->d_ncand; D.err = h->d_err;
+        MSL_HIP_TRY(hipMemcpy(g.taps.p, taps.data(), sizeof(ResizeTap) * taps.size(), hipMemcpyHostToDevice));
+    D.pyr = (uint8_t *)g.pyr.p; D.blur = (uint8_t *)g.blur.p; D.cells = (const CellDev *)g.cells.p; D.taps = (const ResizeTap *)g.taps.p;
+    D.cellCnt = (uint32_t *)g.cellCnt.p; D.cellKeys = (uint32_t *)g.cellKeys.p; D.keys = (uint32_t *)g.keys.p; D.knode = (uint16_t *)g.knode.p;
+    D.sel = (uint32_t *)g.sel.p; D.nsel = (int *)g.nsel.p; D.ncand = (int *)g.ncand.p; D.err = (int *)h->d_err.p;
     h->geomW = W; h->geomH = H;
     return MSL_OK;
 }
@@ -1412,12 +1405,12 @@ int launch_pipeline(msl_orb *h, const uint8_t *d_gray, size_t rowStride, size_t 
 }
 
 int check_device_error(msl_orb *h) {
-    MSL_HIP_TRY(hipMemcpyAsync(h->h_err, h->d_err, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    MSL_HIP_TRY(hipMemcpyAsync(h->h_err.p, h->d_err.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     MSL_HIP_TRY(hipStreamSynchronize(h->stream));
     h->prof.drain();
-    if (*h->h_err) {
-        const int e = *h->h_err;
-        (void)hipMemsetAsync(h->d_err, 0, sizeof(int), h->stream);
+    const int e = *(const int *)h->h_err.p;
+    if (e) {
+        (void)hipMemsetAsync(h->d_err.p, 0, sizeof(int), h->stream);
         set_error("device-side bound exceeded in ORB pipeline (code %d)", e);
         return MSL_ERR_OVERFLOW;
     }
@@ -1477,8 +1470,8 @@ msl_orb *msl_orb_create(int nfeatures, float scaleFactorF, int nlevels, int iniT
     int prLo = 0, prHi = 0;   // frame-batched throughput work: lowest priority, so latency-critical streams of the process go first
     (void)hipDeviceGetStreamPriorityRange(&prLo, &prHi);
     if (hipStreamCreateWithPriority(&h->stream, hipStreamNonBlocking, prLo) != hipSuccess ||
-        hipMalloc(&h->d_err, 2048) != hipSuccess || hipMemset(h->d_err, 0, 2048) != hipSuccess ||   // [0] deferred error; from byte 128: 200 device-clock stamps of experiment builds
-        hipHostMalloc(&h->h_err, sizeof(int)) != hipSuccess ||
+        h->d_err.grow(2048, h->stream) != hipSuccess || hipMemset(h->d_err.p, 0, 2048) != hipSuccess ||   // [0] deferred error; from byte 128: 200 device-clock stamps of experiment builds
+        h->h_err.grow(sizeof(int), h->stream) != hipSuccess ||
         hipStreamCreateWithPriority(&h->sideStream, hipStreamNonBlocking, prLo) != hipSuccess ||
         hipEventCreateWithFlags(&h->evFork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&h->evJoin, hipEventDisableTiming) != hipSuccess) {
         set_error("msl_orb_create: HIP resource allocation failed");
@@ -1495,22 +1488,13 @@ void msl_orb_destroy(msl_orb *h) noexcept {
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
+    if (h->sideStream) (void)hipStreamSynchronize(h->sideStream);
     h->prof.destroy();
-    free_geometry(h);
-    if (h->d_err) (void)hipFree(h->d_err);
-    if (h->h_err) (void)hipHostFree(h->h_err);
-    if (h->h_pinIn) (void)hipHostFree(h->h_pinIn);
-    if (h->h_pinOut) (void)hipHostFree(h->h_pinOut);
-    if (h->d_depthIn) (void)hipFree(h->d_depthIn);
-    if (h->d_unXY) (void)hipFree(h->d_unXY);
-    if (h->d_depthOut) (void)hipFree(h->d_depthOut);
-    if (h->d_uRight) (void)hipFree(h->d_uRight);
-    if (h->d_gridCell) (void)hipFree(h->d_gridCell);
-    if (h->sideStream) { (void)hipStreamSynchronize(h->sideStream); (void)hipStreamDestroy(h->sideStream); }
     if (h->evFork) (void)hipEventDestroy(h->evFork);
     if (h->evJoin) (void)hipEventDestroy(h->evJoin);
-    if (h->stream && h->ownStream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    const hipStream_t streams[2] = {h->sideStream, h->ownStream ? h->stream : nullptr};
+    delete h;   // frees the buffers
+    for (hipStream_t st : streams) if (st) (void)hipStreamDestroy(st);
     } MSL_ABI_CATCH_VOID
 }
 
@@ -1590,14 +1574,14 @@ int msl_orb_extract_batch(msl_orb *h, const uint8_t *gray, int n_frames, int wid
         h->prof.begin(KID_COPY, h->stream);
         if (row_stride == (size_t)width && h->inPitch == (size_t)width && frame_stride == (size_t)width * height) {
             // tightly packed frames (the streaming case): one copy for the whole batch
-            MSL_HIP_TRY(hipMemcpyAsync(h->d_in, gray, (size_t)width * height * n_frames, hipMemcpyHostToDevice, h->stream));
+            MSL_HIP_TRY(hipMemcpyAsync(h->geo.in.p, gray, (size_t)width * height * n_frames, hipMemcpyHostToDevice, h->stream));
         } else {
             for (int f = 0; f < n_frames; f++)
-                MSL_HIP_TRY(hipMemcpy2DAsync(h->d_in + (size_t)f * h->inPitch * height, h->inPitch, gray + (size_t)f * frame_stride,
+                MSL_HIP_TRY(hipMemcpy2DAsync((uint8_t *)h->geo.in.p + (size_t)f * h->inPitch * height, h->inPitch, gray + (size_t)f * frame_stride,
                                              row_stride, width, height, hipMemcpyHostToDevice, h->stream));
         }
         h->prof.end(h->stream);
-        d_gray = h->d_in; rs = h->inPitch; fs = h->inPitch * height;
+        d_gray = (const uint8_t *)h->geo.in.p; rs = h->inPitch; fs = h->inPitch * height;
     }
     if (out_mem == MSL_MEM_DEVICE && cap == outCap) {
         return launch_pipeline(h, d_gray, rs, fs, n_frames, kps, desc32, n_out);
@@ -1627,42 +1611,32 @@ static int extract_one_host(msl_orb *h, const uint8_t *gray, int width, int heig
     if (cap < outCap) { set_error("msl_orb_extract: cap %d < required %d", cap, outCap); return MSL_ERR_CAPACITY; }
     const size_t inBytes = h->inPitch * (size_t)height;
     // frame 0's share of the output block: counts (all B of them: a few bytes), its keypoints and -- B == 1 only -- its descriptors contiguous
-    const size_t outBytes = h->maxBatch == 1 ? h->outBlockBytes : 0;
-    if (inBytes > h->pinInBytes) {
-        if (h->h_pinIn) (void)hipHostFree(h->h_pinIn);
-        h->h_pinIn = nullptr; h->pinInBytes = 0;
-        MSL_HIP_TRY(hipHostMalloc(&h->h_pinIn, inBytes));
-        h->pinInBytes = inBytes;
-    }
-    const size_t needOut = h->outKpsOff + sizeof(msl_keypoint) * (size_t)outCap + (size_t)32 * outCap + 256;
-    if (needOut > h->pinOutBytes) {
-        if (h->h_pinOut) (void)hipHostFree(h->h_pinOut);
-        h->h_pinOut = nullptr; h->pinOutBytes = 0;
-        MSL_HIP_TRY(hipHostMalloc(&h->h_pinOut, needOut));
-        h->pinOutBytes = needOut;
-    }
+    const size_t outBytes = h->maxBatch == 1 ? h->geo.outBlock.cap : 0;
     hipStream_t s = h->stream;
+    MSL_HIP_TRY(h->h_pinIn.grow(inBytes, s));
+    MSL_HIP_TRY(h->h_pinOut.grow(h->outKpsOff + sizeof(msl_keypoint) * (size_t)outCap + (size_t)32 * outCap + 256, s));
+    uint8_t *pinIn = (uint8_t *)h->h_pinIn.p, *pinOut = (uint8_t *)h->h_pinOut.p, *d_in = (uint8_t *)h->geo.in.p;
     h->prof.begin(KID_COPY, s);
     // (one copy: splitting it so that the DMA of the first half overlaps the CPU copy of the second measured 6 us SLOWER -- an enqueue costs more than it hides)
-    if (stride == h->inPitch) memcpy(h->h_pinIn, gray, stride * (size_t)(height - 1) + width);
-    else for (int y = 0; y < height; y++) memcpy(h->h_pinIn + (size_t)y * h->inPitch, gray + (size_t)y * stride, (size_t)width);
-    MSL_HIP_TRY(hipMemcpyAsync(h->d_in, h->h_pinIn, inBytes, hipMemcpyHostToDevice, s));
+    if (stride == h->inPitch) memcpy(pinIn, gray, stride * (size_t)(height - 1) + width);
+    else for (int y = 0; y < height; y++) memcpy(pinIn + (size_t)y * h->inPitch, gray + (size_t)y * stride, (size_t)width);
+    MSL_HIP_TRY(hipMemcpyAsync(d_in, pinIn, inBytes, hipMemcpyHostToDevice, s));
     h->prof.end(s);
-    rc = launch_pipeline(h, h->d_in, h->inPitch, inBytes, 1, h->d_kps, h->d_desc, h->d_nout);
+    rc = launch_pipeline(h, d_in, h->inPitch, inBytes, 1, h->d_kps, h->d_desc, h->d_nout);
     if (rc != MSL_OK) return rc;
     const size_t kpsBytes = sizeof(msl_keypoint) * (size_t)outCap, descBytes = (size_t)32 * outCap;
-    uint8_t *hk = h->h_pinOut + h->outKpsOff, *hd = hk + ((kpsBytes + 255) & ~(size_t)255);
+    uint8_t *hk = pinOut + h->outKpsOff, *hd = hk + ((kpsBytes + 255) & ~(size_t)255);
     if (outBytes) {   // a one-frame handle: counts | keypoints | descriptors are one contiguous block
-        MSL_HIP_TRY(hipMemcpyAsync(h->h_pinOut, h->d_outBlock, outBytes, hipMemcpyDeviceToHost, s));
-        hd = h->h_pinOut + h->outDescOff;
+        MSL_HIP_TRY(hipMemcpyAsync(pinOut, h->geo.outBlock.p, outBytes, hipMemcpyDeviceToHost, s));
+        hd = pinOut + h->outDescOff;
     } else {
-        MSL_HIP_TRY(hipMemcpyAsync(h->h_pinOut, h->d_nout, sizeof(int), hipMemcpyDeviceToHost, s));
+        MSL_HIP_TRY(hipMemcpyAsync(pinOut, h->d_nout, sizeof(int), hipMemcpyDeviceToHost, s));
         MSL_HIP_TRY(hipMemcpyAsync(hk, h->d_kps, kpsBytes, hipMemcpyDeviceToHost, s));
         MSL_HIP_TRY(hipMemcpyAsync(hd, h->d_desc, descBytes, hipMemcpyDeviceToHost, s));
     }
     rc = check_device_error(h);   // error word into pinned memory, then the call's only synchronisation
     if (rc != MSL_OK) { *n_out = 0; return rc; }
-    const int n = *reinterpret_cast<const int *>(h->h_pinOut);
+    const int n = *reinterpret_cast<const int *>(pinOut);
     memcpy(kps, hk, sizeof(msl_keypoint) * (size_t)n);
     memcpy(desc32, hd, (size_t)32 * n);
     *n_out = n;
@@ -1738,35 +1712,27 @@ int msl_orb_extract_frame_batch(msl_orb *h, const uint8_t *gray, const float *de
     int rc = build_geometry(h, width, height);
     if (rc != MSL_OK) return rc;
     const size_t B = (size_t)h->maxBatch;
-    if (!h->frameBufs) {
-        MSL_HIP_TRY(hipMalloc(&h->d_unXY, sizeof(float) * 2 * outCap * B)); MSL_HIP_TRY(hipMalloc(&h->d_depthOut, sizeof(float) * outCap * B));
-        MSL_HIP_TRY(hipMalloc(&h->d_uRight, sizeof(float) * outCap * B)); MSL_HIP_TRY(hipMalloc(&h->d_gridCell, sizeof(int) * outCap * B));
-        h->frameBufs = true;
-    }
+    MSL_HIP_TRY(grow_all(h->stream, {{h->d_unXY, sizeof(float) * 2 * outCap * B}, {h->d_depthOut, sizeof(float) * outCap * B},   // (sized once: outCap and B are fixed)
+                                     {h->d_uRight, sizeof(float) * outCap * B}, {h->d_gridCell, sizeof(int) * outCap * B}}));
     const uint8_t *d_gray = gray; size_t rs = gray_row_stride, fs = gray_frame_stride;
     FrameEpilogue ep{};
     ep.fp = *params; ep.depth = depth; ep.depthRowStride = depth_row_stride; ep.depthFrameStride = depth_frame_stride;
     if (in_mem == MSL_MEM_HOST) {
         const size_t dpitch = (size_t)width * 4, dframe = dpitch * height;
-        if (dframe * B > h->depthInCap) {
-            MSL_HIP_TRY(hipStreamSynchronize(h->stream));
-            if (h->d_depthIn) (void)hipFree(h->d_depthIn);
-            h->d_depthIn = nullptr; h->depthInCap = 0;
-            MSL_HIP_TRY(hipMalloc(&h->d_depthIn, dframe * B));
-            h->depthInCap = dframe * B;
-        }
+        MSL_HIP_TRY(h->d_depthIn.grow(dframe * B, h->stream));
+        uint8_t *d_in = (uint8_t *)h->geo.in.p, *d_depthIn = (uint8_t *)h->d_depthIn.p;
         for (int f = 0; f < n_frames; f++) {
-            MSL_HIP_TRY(hipMemcpy2DAsync(h->d_in + (size_t)f * h->inPitch * height, h->inPitch, gray + (size_t)f * gray_frame_stride, gray_row_stride,
+            MSL_HIP_TRY(hipMemcpy2DAsync(d_in + (size_t)f * h->inPitch * height, h->inPitch, gray + (size_t)f * gray_frame_stride, gray_row_stride,
                                          width, height, hipMemcpyHostToDevice, h->stream));
-            MSL_HIP_TRY(hipMemcpy2DAsync((uint8_t *)h->d_depthIn + (size_t)f * dframe, dpitch, (const uint8_t *)depth + (size_t)f * depth_frame_stride,
+            MSL_HIP_TRY(hipMemcpy2DAsync(d_depthIn + (size_t)f * dframe, dpitch, (const uint8_t *)depth + (size_t)f * depth_frame_stride,
                                          depth_row_stride, dpitch, height, hipMemcpyHostToDevice, h->stream));
         }
-        d_gray = h->d_in; rs = h->inPitch; fs = h->inPitch * height;
-        ep.depth = h->d_depthIn; ep.depthRowStride = dpitch; ep.depthFrameStride = dframe;
+        d_gray = d_in; rs = h->inPitch; fs = h->inPitch * height;
+        ep.depth = (const float *)d_depthIn; ep.depthRowStride = dpitch; ep.depthFrameStride = dframe;
     }
     const bool direct = out_mem == MSL_MEM_DEVICE && cap == outCap;
-    ep.unXY = direct ? kps_un_xy : h->d_unXY; ep.depthOut = direct ? depth_out : h->d_depthOut;
-    ep.uRight = direct ? uright_out : h->d_uRight; ep.gridCell = direct ? grid_cell : h->d_gridCell;
+    ep.unXY = direct ? kps_un_xy : (float *)h->d_unXY.p; ep.depthOut = direct ? depth_out : (float *)h->d_depthOut.p;
+    ep.uRight = direct ? uright_out : (float *)h->d_uRight.p; ep.gridCell = direct ? grid_cell : (int *)h->d_gridCell.p;
     if (direct) return launch_pipeline(h, d_gray, rs, fs, n_frames, kps, desc32, n_out, &ep);
     rc = launch_pipeline(h, d_gray, rs, fs, n_frames, h->d_kps, h->d_desc, h->d_nout, &ep);
     if (rc != MSL_OK) return rc;
@@ -1774,10 +1740,10 @@ int msl_orb_extract_frame_batch(msl_orb *h, const uint8_t *gray, const float *de
     MSL_HIP_TRY(hipMemcpyAsync(n_out, h->d_nout, sizeof(int) * n_frames, kind, h->stream));
     MSL_HIP_TRY(hipMemcpy2DAsync(kps, sizeof(msl_keypoint) * cap, h->d_kps, sizeof(msl_keypoint) * outCap, sizeof(msl_keypoint) * outCap, n_frames, kind, h->stream));
     MSL_HIP_TRY(hipMemcpy2DAsync(desc32, (size_t)32 * cap, h->d_desc, (size_t)32 * outCap, (size_t)32 * outCap, n_frames, kind, h->stream));
-    MSL_HIP_TRY(hipMemcpy2DAsync(kps_un_xy, sizeof(float) * 2 * cap, h->d_unXY, sizeof(float) * 2 * outCap, sizeof(float) * 2 * outCap, n_frames, kind, h->stream));
-    MSL_HIP_TRY(hipMemcpy2DAsync(depth_out, sizeof(float) * cap, h->d_depthOut, sizeof(float) * outCap, sizeof(float) * outCap, n_frames, kind, h->stream));
-    MSL_HIP_TRY(hipMemcpy2DAsync(uright_out, sizeof(float) * cap, h->d_uRight, sizeof(float) * outCap, sizeof(float) * outCap, n_frames, kind, h->stream));
-    MSL_HIP_TRY(hipMemcpy2DAsync(grid_cell, sizeof(int) * cap, h->d_gridCell, sizeof(int) * outCap, sizeof(int) * outCap, n_frames, kind, h->stream));
+    MSL_HIP_TRY(hipMemcpy2DAsync(kps_un_xy, sizeof(float) * 2 * cap, h->d_unXY.p, sizeof(float) * 2 * outCap, sizeof(float) * 2 * outCap, n_frames, kind, h->stream));
+    MSL_HIP_TRY(hipMemcpy2DAsync(depth_out, sizeof(float) * cap, h->d_depthOut.p, sizeof(float) * outCap, sizeof(float) * outCap, n_frames, kind, h->stream));
+    MSL_HIP_TRY(hipMemcpy2DAsync(uright_out, sizeof(float) * cap, h->d_uRight.p, sizeof(float) * outCap, sizeof(float) * outCap, n_frames, kind, h->stream));
+    MSL_HIP_TRY(hipMemcpy2DAsync(grid_cell, sizeof(int) * cap, h->d_gridCell.p, sizeof(int) * outCap, sizeof(int) * outCap, n_frames, kind, h->stream));
     if (out_mem == MSL_MEM_HOST) return check_device_error(h);
     return MSL_OK;
     } MSL_ABI_CATCH_INT
@@ -1788,7 +1754,7 @@ int msl_orb_debug_stamps(msl_orb *h, uint64_t *out, int n) noexcept {
     if (!h || !out || n < 0 || n > 200) return MSL_ERR_INVALID;
     MSL_HIP_TRY(hipSetDevice(h->device));
     MSL_HIP_TRY(hipStreamSynchronize(h->stream));
-    MSL_HIP_TRY(hipMemcpy(out, reinterpret_cast<unsigned char *>(h->d_err) + 128, sizeof(uint64_t) * n, hipMemcpyDeviceToHost));
+    MSL_HIP_TRY(hipMemcpy(out, (const uint8_t *)h->d_err.p + 128, sizeof(uint64_t) * n, hipMemcpyDeviceToHost));
     return MSL_OK;
     } MSL_ABI_CATCH_INT
 }
@@ -1808,8 +1774,8 @@ int msl_orb_debug_level(msl_orb *h, int frame, int level, int blurred, uint8_t *
     MSL_HIP_TRY(hipSetDevice(h->device));
     MSL_HIP_TRY(hipStreamSynchronize(h->stream));
     const LevelDev &G = h->dev.lv[level];
-    const uint8_t *src = blurred ? h->d_blur + (size_t)frame * h->dev.blurStride + G.boff
-                                 : h->d_pyr + (size_t)frame * h->dev.pyrStride + G.off;
+    const uint8_t *src = blurred ? h->dev.blur + (size_t)frame * h->dev.blurStride + G.boff
+                                 : h->dev.pyr + (size_t)frame * h->dev.pyrStride + G.off;
     MSL_HIP_TRY(hipMemcpy2D(out, G.w, src, G.pitch, G.w, G.h, hipMemcpyDeviceToHost));
     return MSL_OK;
     } MSL_ABI_CATCH_INT
@@ -1821,11 +1787,11 @@ int msl_orb_debug_candidates(msl_orb *h, int frame, int level, int32_t *xys, int
     MSL_HIP_TRY(hipSetDevice(h->device));
     MSL_HIP_TRY(hipStreamSynchronize(h->stream));
     int n = 0;
-    MSL_HIP_TRY(hipMemcpy(&n, h->d_ncand + frame * h->nlevels + level, sizeof(int), hipMemcpyDeviceToHost));
+    MSL_HIP_TRY(hipMemcpy(&n, h->dev.ncand + frame * h->nlevels + level, sizeof(int), hipMemcpyDeviceToHost));
     *n_out = n;
     if (n > cap) return MSL_ERR_CAPACITY;
     std::vector<uint32_t> k(n);
-    if (n) MSL_HIP_TRY(hipMemcpy(k.data(), h->d_keys + (size_t)frame * h->dev.keysPerFrame + h->dev.lv[level].keyBase,
+    if (n) MSL_HIP_TRY(hipMemcpy(k.data(), h->dev.keys + (size_t)frame * h->dev.keysPerFrame + h->dev.lv[level].keyBase,
                                  sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
     for (int i = 0; i < n; i++) {
         xys[3 * i] = (int)(k[i] & 0xFFF) + 16; xys[3 * i + 1] = (int)((k[i] >> 12) & 0xFFF) + 16; xys[3 * i + 2] = (int)(k[i] >> 24);

@@ -1549,27 +1549,15 @@ void map_launch_deal(hipStream_t st, const SfDev &P) { hipLaunchKernelGGL(k_deal
 // Test hook: the dealing of G sub-blocks (a multiple of 8) with the given screen keys, host arrays, synchronous.
 int map_debug_deal(const uint32_t *keys_host, int G, uint32_t *deal_host) {
     if (!keys_host || !deal_host || G < 8 || (G & 7)) return MSL_ERR_INVALID;
-    unsigned *dk = nullptr, *dd = nullptr;
     const size_t pad = (size_t)G + 8192;   // the key plane of a handle is padded the same way (whole chunks are loaded)
-    MSL_HIP_TRY(hipMalloc(&dk, sizeof(unsigned) * pad)); MSL_HIP_TRY(hipMalloc(&dd, sizeof(unsigned) * (G + 64)));
+    DevBuf keys, deal;
+    MSL_HIP_TRY(grow_all(0, {{keys, sizeof(unsigned) * pad}, {deal, sizeof(unsigned) * (G + 64)}}));
+    unsigned *dk = (unsigned *)keys.p, *dd = (unsigned *)deal.p;
     MSL_HIP_TRY(hipMemset(dk, 0xFF, sizeof(unsigned) * pad)); MSL_HIP_TRY(hipMemset(dd, 0xFF, sizeof(unsigned) * G));
     MSL_HIP_TRY(hipMemcpy(dk, keys_host, sizeof(unsigned) * G, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_deal, dim3(1), dim3(256), 0, 0, dk, G, dd);
+    MSL_HIP_TRY(hipGetLastError());
     MSL_HIP_TRY(hipMemcpy(deal_host, dd, sizeof(unsigned) * G, hipMemcpyDeviceToHost));
-    if (const char *reps = getenv("MSL_DEAL_REPS")) {   // experiment: mean time of the dealing kernel alone (HIP events around back-to-back launches)
-        const int n = atoi(reps);
-        hipEvent_t a, b;
-        MSL_HIP_TRY(hipEventCreate(&a)); MSL_HIP_TRY(hipEventCreate(&b));
-        for (int w = 0; w < 20; w++) hipLaunchKernelGGL(k_deal, dim3(1), dim3(256), 0, 0, dk, G, dd);
-        MSL_HIP_TRY(hipEventRecord(a, 0));
-        for (int i = 0; i < n; i++) hipLaunchKernelGGL(k_deal, dim3(1), dim3(256), 0, 0, dk, G, dd);
-        MSL_HIP_TRY(hipEventRecord(b, 0));
-        MSL_HIP_TRY(hipEventSynchronize(b));
-        float ms = 0; MSL_HIP_TRY(hipEventElapsedTime(&ms, a, b));
-        fprintf(stderr, "k_deal G=%d: %.2f us per launch (back to back, %d launches)\n", G, ms * 1e3f / n, n);
-        (void)hipEventDestroy(a); (void)hipEventDestroy(b);
-    }
-    (void)hipFree(dk); (void)hipFree(dd);
     return MSL_OK;
 }
 void map_launch_fuse(KernelProfiler &prof, hipStream_t st, const SfDev &P, int slot, const FrameDev &F, int nSubGrid, int nSubHint, bool deferred, bool dealt) {

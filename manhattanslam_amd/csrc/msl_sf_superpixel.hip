@@ -1232,25 +1232,23 @@ int sp_debug_chain(const float *x_host, const int32_t *n_host, int lists, int hu
     if (lists <= 0) return MSL_OK;
     if (!x_host || !n_host || !out_host) return MSL_ERR_INVALID;
     for (int q = 0; q < lists; q++) if (n_host[q] < 0 || n_host[q] > 256) return MSL_ERR_INVALID;
-    float *dx = nullptr, *dout = nullptr; int *dn = nullptr;
-    MSL_HIP_TRY(hipMalloc(&dx, sizeof(float) * 256 * (size_t)lists)); MSL_HIP_TRY(hipMalloc(&dn, sizeof(int) * (size_t)lists)); MSL_HIP_TRY(hipMalloc(&dout, sizeof(float) * (size_t)lists));
-    MSL_HIP_TRY(hipMemcpy(dx, x_host, sizeof(float) * 256 * (size_t)lists, hipMemcpyHostToDevice));
-    MSL_HIP_TRY(hipMemcpy(dn, n_host, sizeof(int) * (size_t)lists, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_debug_chain, dim3((unsigned)((lists + 3) / 4)), dim3(64), 0, 0, dx, dn, dout, lists, huber);
-    MSL_HIP_TRY(hipMemcpy(out_host, dout, sizeof(float) * (size_t)lists, hipMemcpyDeviceToHost));
-    (void)hipFree(dx); (void)hipFree(dn); (void)hipFree(dout);
+    DevBuf x, cnt, out;
+    MSL_HIP_TRY(grow_all(0, {{x, sizeof(float) * 256 * (size_t)lists}, {cnt, sizeof(int) * (size_t)lists}, {out, sizeof(float) * (size_t)lists}}));
+    MSL_HIP_TRY(hipMemcpy(x.p, x_host, sizeof(float) * 256 * (size_t)lists, hipMemcpyHostToDevice));
+    MSL_HIP_TRY(hipMemcpy(cnt.p, n_host, sizeof(int) * (size_t)lists, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_debug_chain, dim3((unsigned)((lists + 3) / 4)), dim3(64), 0, 0, (const float *)x.p, (const int *)cnt.p, (float *)out.p, lists, huber);
+    MSL_HIP_TRY(hipMemcpy(out_host, out.p, sizeof(float) * (size_t)lists, hipMemcpyDeviceToHost));
     return MSL_OK;
 }
 
 int sp_debug_div100(const float *x_host, double *out_host, size_t n) {
     if (n == 0) return MSL_OK;
     if (!x_host || !out_host) return MSL_ERR_INVALID;
-    float *dx = nullptr; double *dout = nullptr;
-    MSL_HIP_TRY(hipMalloc(&dx, sizeof(float) * n)); MSL_HIP_TRY(hipMalloc(&dout, sizeof(double) * n));
-    MSL_HIP_TRY(hipMemcpy(dx, x_host, sizeof(float) * n, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_debug_div100, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dx, dout, (long long)n);
-    MSL_HIP_TRY(hipMemcpy(out_host, dout, sizeof(double) * n, hipMemcpyDeviceToHost));
-    (void)hipFree(dx); (void)hipFree(dout);
+    DevBuf x, out;
+    MSL_HIP_TRY(grow_all(0, {{x, sizeof(float) * n}, {out, sizeof(double) * n}}));
+    MSL_HIP_TRY(hipMemcpy(x.p, x_host, sizeof(float) * n, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_debug_div100, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (const float *)x.p, (double *)out.p, (long long)n);
+    MSL_HIP_TRY(hipMemcpy(out_host, out.p, sizeof(double) * n, hipMemcpyDeviceToHost));
     return MSL_OK;
 }
 

@@ -43,26 +43,24 @@ struct msl_sf {
     unsigned long long batchNo = 0;
     int stagedSet = -1; size_t stagedGs = 0;   // slot set / row stride of the gray images the last host-image batch staged (msl_sf_staged_gray); -1: none
     int lastSlot = 0;
-    // per-slot device buffers
-    FrameDev *d_frames = nullptr; FrameDev *h_frames = nullptr;  // pinned host staging [slots]
-    msl_seed *d_seeds = nullptr, *d_seedsTmp = nullptr; msl_surfel *d_cand = nullptr; uint8_t *d_candOk = nullptr, *d_fused = nullptr; uint2 *d_tex = nullptr; float4 *d_fuseRec = nullptr;
-    unsigned short *d_index = nullptr, *d_amap = nullptr; unsigned *d_tmin = nullptr; int *d_chunkAbort = nullptr, *d_changed = nullptr;
-    AssignRec *d_arec = nullptr; unsigned *d_wl = nullptr, *d_wlCount = nullptr;
-    float *d_pxInv = nullptr;
-    // staged images (host input mode), per slot
-    uint8_t *d_gray = nullptr; float *d_depth = nullptr; int32_t *d_member = nullptr;
-    size_t grayCap = 0, depthCap = 0, memberCap = 0;  // bytes per slot
-    uint8_t *d_depth16 = nullptr; size_t depth16Cap = 0;   // raw 16-bit depth of host-image calls (msl_sf_fuse_resident_batch_d16), bytes per slot
-    long long *d_ctr = nullptr; long long *h_ctr = nullptr;
-    unsigned *d_tickets = nullptr, *d_delU = nullptr;
-    DeferCtl *d_dc = nullptr;
-    float *d_projTab = nullptr;
+    // The slot set, allocated to exactly 2 * maxBatch slots by alloc_slots: the per-slot arrays behind SfDev's bases, the pinned FrameDev staging,
+    // and the images of host-image calls (staged per slot, allocated by the first such call; the ...Cap are their per-slot strides in bytes)
+    struct Slots {
+        DevBuf frames, seeds, seedsTmp, cand, candOk, fused, tex, fuseRec, index, amap, tmin, arec, pxInv, wl, wlCount, chunkAbort, changed;
+        PinBuf hFrames;
+        DevBuf gray, depth, member;
+        size_t grayCap = 0, depthCap = 0, memberCap = 0;
+        DevBuf depth16; size_t depth16Cap = 0;   // raw 16-bit depth of host-image calls (msl_sf_fuse_resident_batch_d16)
+    } slot;
+    DevBuf d_ctr; PinBuf h_ctr;
+    DevBuf d_tickets, d_delU, d_dc, d_projTab;
     bool propLds = false;        // t(s) of one keyframe fits the LDS: single-launch relaxation
     bool classicNext = true;     // the map was replaced from outside the keyframe chain (upload / restore / append / detach): its first keyframe takes the classic
                                  // pair of launches, whose compaction handles any number of stale or deleted slots at full speed
-    msl_surfel *d_new = nullptr;
-    float *d_mapStore = nullptr; size_t mapCap = 0;
-    unsigned *d_rpStore = nullptr;   // deferred compaction: move lists, dense replay tables, staging (see set_map_ptrs)
+    DevBuf d_new;
+    // The resident map, replaced as a whole by map_realloc (layout: set_map_ptrs; its capacity in surfels: dev.cap).  rp: deferred compaction's
+    // move lists, dense replay tables and staging
+    struct MapBufs { DevBuf store, blockSums, blockUpd, delList, srcOf, rp; } map;
     size_t liveBound = 0;        // host-side upper bound of the live count: last known count + nseeds per keyframe enqueued since
     size_t liveKnown = 0;        // the most recent live count the host has seen (exact at that time; only a hint for k_fuse's speculative loads)
     unsigned long long liveKnownKf = 0;   // ... and the number of keyframes that had been enqueued when it was exact: an older snapshot never replaces a newer one
@@ -71,42 +69,41 @@ struct msl_sf {
     // every capacity / nseeds keyframes
     static constexpr int NSNAP = 4;
     static constexpr int SNAPW = 16;   // counters per snapshot: ctr[0 .. 15]
-    long long *h_snap = nullptr; hipEvent_t snapEv[NSNAP] = {}; unsigned long long snapKf[NSNAP] = {}; bool snapBusy[NSNAP] = {};
+    PinBuf h_snap; hipEvent_t snapEv[NSNAP] = {}; unsigned long long snapKf[NSNAP] = {}; bool snapBusy[NSNAP] = {};
     bool snapLive[NSNAP] = {};   // the snapshot's live count still describes the resident map (no upload / restore since it was taken)
     unsigned long long kfEnq = 0; int snapNext = 0;
     // churn = surfels spawned + deleted per keyframe over the most recent batch the host has seen (from the running totals of two snapshots):
     // the deferred compaction is built for the steady state (a replay by ONE wave per window); under heavy churn the classic chain, whose
     // compaction works with all its workgroups, is faster
     long long churnNew = -1, churnDel = 0, churnKf = 0; unsigned long long churnAt = 0; double churn = 0.0;
-    unsigned *d_blockSums = nullptr, *d_blockUpd = nullptr, *d_delList = nullptr, *d_srcOf = nullptr;
-    msl_surfel *d_aos = nullptr; size_t aosCap = 0;
-    float *d_snapStore = nullptr; size_t snapCap = 0, snapN = 0; bool snapValid = false; long long snapWide = 0;   // msl_sf_map_snapshot / _restore
+    DevBuf d_aos;
+    DevBuf d_snapStore; size_t snapN = 0; bool snapValid = false; long long snapWide = 0;   // msl_sf_map_snapshot / _restore (same layout as the map store)
     // host-vector mode (msl_sf_fuse_ex): the device map equals the caller's vector as the last call left it
     bool mirrorValid = false; size_t mirrorN = 0;
-    unsigned *h_blk = nullptr; size_t blkCap = 0;   // pinned: per-sub-block deleted / updated counts of the call's k_fuse launch
-    uint8_t *h_list = nullptr; size_t listCap = 0;  // pinned: {count | indices | records} of the sparse download
+    PinBuf h_blk;    // per-sub-block deleted / updated counts of the call's k_fuse launch: two halves of h_blk.cap / 8 entries
+    PinBuf h_list;   // {count | indices | records} of the sparse download
     KernelProfiler prof;
 };
 
 namespace {
 
 // Map storage, in 4-byte words per surfel of capacity c (c is a multiple of 4096, so every array starts 32-byte aligned):
-//   d_mapStore: hot 4 | cold 8 | rgbWide 3 | utlWide 2                                                               = 17 c
-//   d_rpStore : moveDst 1 | loc64 2 | vposD 1 | locKeys 1 | vposKeys 1 | dBig 1 | stageHot 4 | stageCold 8 | stageRgb 3 | stageUtl 2 | bitmap c / 32 + 64
+//   map.store: hot 4 | cold 8 | rgbWide 3 | utlWide 2                                                               = 17 c
+//   map.rp   : moveDst 1 | loc64 2 | vposD 1 | locKeys 1 | vposKeys 1 | dBig 1 | stageHot 4 | stageCold 8 | stageRgb 3 | stageUtl 2 | bitmap c / 32 + 64
 constexpr size_t MAP_WORDS = 17, RP_WORDS = 24;
-void set_map_ptrs(msl_sf *h) {
-    const size_t c = h->mapCap;
+void set_map_ptrs(msl_sf *h, size_t c) {
     MapSoA &M = h->dev.map;
-    M.hot = reinterpret_cast<HotPk *>(h->d_mapStore);
-    M.cold = reinterpret_cast<ColdRec *>(h->d_mapStore + 4 * c);
-    M.rgbWide = reinterpret_cast<int *>(h->d_mapStore + 12 * c);        // exact ints of the COLD_WIDE records (untouched otherwise)
-    M.utlWide = reinterpret_cast<int *>(h->d_mapStore + 15 * c);        // exact ints of the HOT_WIDE records
-    M.wideFlag = h->d_ctr + 13;
+    float *store = (float *)h->map.store.p;
+    M.hot = reinterpret_cast<HotPk *>(store);
+    M.cold = reinterpret_cast<ColdRec *>(store + 4 * c);
+    M.rgbWide = reinterpret_cast<int *>(store + 12 * c);        // exact ints of the COLD_WIDE records (untouched otherwise)
+    M.utlWide = reinterpret_cast<int *>(store + 15 * c);        // exact ints of the HOT_WIDE records
+    M.wideFlag = h->dev.ctr + 13;
     SfDev &D = h->dev;
     D.cap = c;
-    D.blockSums = h->d_blockSums; D.blockUpd = h->d_blockUpd; D.delList = h->d_delList; D.srcOf = h->d_srcOf;
-    D.sbKeys = h->d_blockSums + h->blkStride; D.deal = h->d_blockSums + 2 * h->blkStride; D.dealG = 0;   // (three planes of one allocation: counts, screen keys, dealing table)
-    unsigned *r = h->d_rpStore;
+    D.blockSums = (unsigned *)h->map.blockSums.p; D.blockUpd = (unsigned *)h->map.blockUpd.p; D.delList = (unsigned *)h->map.delList.p; D.srcOf = (unsigned *)h->map.srcOf.p;
+    D.sbKeys = D.blockSums + h->blkStride; D.deal = D.blockSums + 2 * h->blkStride; D.dealG = 0;   // (three planes of one allocation: counts, screen keys, dealing table)
+    unsigned *r = (unsigned *)h->map.rp.p;
     D.loc64 = reinterpret_cast<unsigned long long *>(r);            // (first: 8-byte aligned)
     D.stageCold = reinterpret_cast<ColdRec *>(r + 2 * c);
     D.stageHot = reinterpret_cast<HotPk *>(r + 10 * c);
@@ -135,103 +132,73 @@ int write_ctl(msl_sf *h) {
     DeferCtl dc;
     memset(&dc, 0, sizeof(dc));
     const SfDev &D = h->dev;
-    dc.flagStride = D.flagStride; dc.candOk = h->d_candOk; dc.fused = h->d_fused; dc.cand = h->d_cand;
+    dc.flagStride = D.flagStride; dc.candOk = D.candOk; dc.fused = D.fused; dc.cand = D.cand;
     dc.aux.map = D.map; dc.aux.cap = D.cap; dc.aux.delU = D.delU; dc.aux.delUCount = D.delUCount; dc.aux.delList = D.delList;
-    MSL_HIP_TRY(hipMemcpy(h->d_dc, &dc, sizeof(dc), hipMemcpyHostToDevice));
+    MSL_HIP_TRY(hipMemcpy(D.dc, &dc, sizeof(dc), hipMemcpyHostToDevice));
     return MSL_OK;
 }
 
-// (Re)allocate the resident map for `cap` surfels, preserving the first `keep` entries.
+// (Re)allocate the resident map for `cap` surfels, preserving the first `keep` entries.  The new set is built beside the old one: a failed
+// attempt frees itself and leaves the old map untouched.
 int map_realloc(msl_sf *h, size_t cap, size_t keep) {
     cap = (cap + 4095) & ~(size_t)4095;
-    float *nstore = nullptr; unsigned *nbs = nullptr, *nbu = nullptr, *ndl = nullptr, *nso = nullptr, *nrp = nullptr;
     const size_t bst = cap / SUB_ITEMS + 8200;   // per slice; >= 1024 / 8192 padding entries: the compaction reads its first tiles unconditionally
-    auto attempt = [&]() -> int {
-        MSL_HIP_TRY(hipMalloc(&nstore, sizeof(float) * MAP_WORDS * cap));
-        MSL_HIP_TRY(hipMalloc(&nbs, sizeof(unsigned) * 3 * bst));           // deleted counts | screen keys | dealing table (SfDev::sbKeys, ::deal)
-        MSL_HIP_TRY(hipMalloc(&nbu, sizeof(unsigned) * DEFER_WIN * bst));   // one slice per keyframe of a deferred window (classic: the first)
-        MSL_HIP_TRY(hipMemset(nbs, 0, sizeof(unsigned) * bst));
-        MSL_HIP_TRY(hipMemset(nbs + bst, 0xFF, sizeof(unsigned) * bst));    // no key yet: "nothing in view"
-        MSL_HIP_TRY(hipMemset(nbu, 0, sizeof(unsigned) * DEFER_WIN * bst));
-        MSL_HIP_TRY(hipMalloc(&ndl, sizeof(unsigned) * cap));
-        MSL_HIP_TRY(hipMalloc(&nso, sizeof(unsigned) * cap));
-        const size_t rpWords = RP_WORDS * cap + cap / 32 + 64;
-        MSL_HIP_TRY(hipMalloc(&nrp, sizeof(unsigned) * rpWords));
-        MSL_HIP_TRY(hipMemset(nrp, 0, sizeof(unsigned) * 2 * cap));                              // loc64: empty (the replay leaves it clean)
-        MSL_HIP_TRY(hipMemset(nrp + 15 * cap, 0, sizeof(unsigned) * cap));                       // vposD
-        MSL_HIP_TRY(hipMemset(nrp + 24 * cap, 0, sizeof(unsigned) * (cap / 32 + 64)));           // bitmap
-        if (keep && h->d_mapStore) {
-            int rc = sync_all(h);
-            if (rc != MSL_OK) return rc;
-            const size_t oc = h->mapCap;
-            MSL_HIP_TRY(hipMemcpy(nstore, h->d_mapStore, sizeof(HotPk) * keep, hipMemcpyDeviceToDevice));
-            MSL_HIP_TRY(hipMemcpy(nstore + 4 * cap, h->d_mapStore + 4 * oc, sizeof(ColdRec) * keep, hipMemcpyDeviceToDevice));
-            MSL_HIP_TRY(hipMemcpy(nstore + 12 * cap, h->d_mapStore + 12 * oc, sizeof(int) * 3 * keep, hipMemcpyDeviceToDevice));   // (rare path: no need to know whether any record is wide)
-            MSL_HIP_TRY(hipMemcpy(nstore + 15 * cap, h->d_mapStore + 15 * oc, sizeof(int) * 2 * keep, hipMemcpyDeviceToDevice));
-        }
-        return MSL_OK;
-    };
-    const int arc = attempt();
-    if (arc != MSL_OK) {   // nothing of a failed attempt stays allocated; the old map is untouched
-        if (nstore) (void)hipFree(nstore);
-        if (nbs) (void)hipFree(nbs);
-        if (nbu) (void)hipFree(nbu);
-        if (ndl) (void)hipFree(ndl);
-        if (nso) (void)hipFree(nso);
-        if (nrp) (void)hipFree(nrp);
-        return arc;
+    const size_t rpWords = RP_WORDS * cap + cap / 32 + 64;
+    msl_sf::MapBufs m;
+    MSL_HIP_TRY(grow_all(h->mapStream, {{m.store, sizeof(float) * MAP_WORDS * cap},
+                                        {m.blockSums, sizeof(unsigned) * 3 * bst},           // deleted counts | screen keys | dealing table (SfDev::sbKeys, ::deal)
+                                        {m.blockUpd, sizeof(unsigned) * DEFER_WIN * bst},    // one slice per keyframe of a deferred window (classic: the first)
+                                        {m.delList, sizeof(unsigned) * cap}, {m.srcOf, sizeof(unsigned) * cap}, {m.rp, sizeof(unsigned) * rpWords}}));
+    unsigned *nbs = (unsigned *)m.blockSums.p, *nrp = (unsigned *)m.rp.p;
+    MSL_HIP_TRY(hipMemset(nbs, 0, sizeof(unsigned) * bst));
+    MSL_HIP_TRY(hipMemset(nbs + bst, 0xFF, sizeof(unsigned) * bst));    // no key yet: "nothing in view"
+    MSL_HIP_TRY(hipMemset(m.blockUpd.p, 0, sizeof(unsigned) * DEFER_WIN * bst));
+    MSL_HIP_TRY(hipMemset(nrp, 0, sizeof(unsigned) * 2 * cap));                              // loc64: empty (the replay leaves it clean)
+    MSL_HIP_TRY(hipMemset(nrp + 15 * cap, 0, sizeof(unsigned) * cap));                       // vposD
+    MSL_HIP_TRY(hipMemset(nrp + 24 * cap, 0, sizeof(unsigned) * (cap / 32 + 64)));           // bitmap
+    if (keep && h->map.store.p) {
+        const int rc = sync_all(h);
+        if (rc != MSL_OK) return rc;
+        const size_t oc = h->dev.cap;
+        float *nstore = (float *)m.store.p;
+        const float *ostore = (const float *)h->map.store.p;
+        MSL_HIP_TRY(hipMemcpy(nstore, ostore, sizeof(HotPk) * keep, hipMemcpyDeviceToDevice));
+        MSL_HIP_TRY(hipMemcpy(nstore + 4 * cap, ostore + 4 * oc, sizeof(ColdRec) * keep, hipMemcpyDeviceToDevice));
+        MSL_HIP_TRY(hipMemcpy(nstore + 12 * cap, ostore + 12 * oc, sizeof(int) * 3 * keep, hipMemcpyDeviceToDevice));   // (rare path: no need to know whether any record is wide)
+        MSL_HIP_TRY(hipMemcpy(nstore + 15 * cap, ostore + 15 * oc, sizeof(int) * 2 * keep, hipMemcpyDeviceToDevice));
     }
-    if (h->d_mapStore) {
-        (void)hipFree(h->d_mapStore); (void)hipFree(h->d_blockSums); (void)hipFree(h->d_blockUpd); (void)hipFree(h->d_delList); (void)hipFree(h->d_srcOf); (void)hipFree(h->d_rpStore);
-    }
-    h->d_mapStore = nstore; h->d_blockSums = nbs; h->d_blockUpd = nbu; h->d_delList = ndl; h->d_srcOf = nso; h->d_rpStore = nrp; h->mapCap = cap;
+    h->map = std::move(m);
     h->blkStride = bst;
     h->dealG = 0;              // (the dealing table went with the old allocation)
-    set_map_ptrs(h);
+    set_map_ptrs(h, cap);
     return write_ctl(h);
 }
 
-void free_slots(msl_sf *h) {
-    auto F = [](auto *&p) { if (p) { (void)hipFree(p); p = nullptr; } };
-    F(h->d_frames); F(h->d_seeds); F(h->d_seedsTmp); F(h->d_cand); F(h->d_candOk); F(h->d_fused); F(h->d_tex); F(h->d_fuseRec); F(h->d_index); F(h->d_amap); F(h->d_tmin);
-    F(h->d_chunkAbort); F(h->d_changed); F(h->d_arec); F(h->d_pxInv); F(h->d_wl); F(h->d_wlCount); F(h->d_gray); F(h->d_depth); F(h->d_member); F(h->d_depth16);
-    if (h->h_frames) { (void)hipHostFree(h->h_frames); h->h_frames = nullptr; }
-    h->grayCap = h->depthCap = h->memberCap = 0; h->depth16Cap = 0;
-}
-
 int alloc_slots(msl_sf *h, int maxBatch) {
-    free_slots(h);
+    h->slot = msl_sf::Slots();   // (the old set goes first)
+    msl_sf::Slots &S = h->slot;
     SfDev &D = h->dev;
     const size_t slots = 2 * (size_t)maxBatch, ns = D.nseeds, npx = D.pxStride, fs = D.flagStride;
-    MSL_HIP_TRY(hipMalloc(&h->d_frames, sizeof(FrameDev) * slots));
-    MSL_HIP_TRY(hipHostMalloc(&h->h_frames, sizeof(FrameDev) * slots));
-    MSL_HIP_TRY(hipMalloc(&h->d_seeds, sizeof(msl_seed) * ns * slots));
-    MSL_HIP_TRY(hipMalloc(&h->d_seedsTmp, sizeof(msl_seed) * ns * slots));
-    MSL_HIP_TRY(hipMalloc(&h->d_cand, sizeof(msl_surfel) * ns * slots));
-    MSL_HIP_TRY(hipMalloc(&h->d_candOk, fs * slots));
-    MSL_HIP_TRY(hipMalloc(&h->d_fused, fs * slots));
-    MSL_HIP_TRY(hipMalloc(&h->d_tex, sizeof(uint2) * npx * slots));
-    MSL_HIP_TRY(hipMalloc(&h->d_fuseRec, sizeof(float4) * 3 * ns * slots));
-    MSL_HIP_TRY(hipMemset(h->d_tex, 0, sizeof(uint2) * npx * slots));
-    MSL_HIP_TRY(hipMemset(h->d_fuseRec, 0, sizeof(float4) * 3 * ns * slots));
-    MSL_HIP_TRY(hipMalloc(&h->d_index, sizeof(unsigned short) * npx * slots));
-    MSL_HIP_TRY(hipMalloc(&h->d_amap, sizeof(unsigned short) * npx * slots));
-    MSL_HIP_TRY(hipMalloc(&h->d_tmin, sizeof(unsigned) * ns * slots));
-    MSL_HIP_TRY(hipMalloc(&h->d_arec, sizeof(AssignRec) * (ns * slots + 2)));   // + a record either side: kb_assign loads row pairs that may start one before / end one after
-    MSL_HIP_TRY(hipMalloc(&h->d_pxInv, sizeof(float) * npx * slots));
-    MSL_HIP_TRY(hipMalloc(&h->d_wl, sizeof(unsigned) * npx * slots));
-    MSL_HIP_TRY(hipMalloc(&h->d_wlCount, sizeof(unsigned) * slots));
-    MSL_HIP_TRY(hipMemset(h->d_wlCount, 0, sizeof(unsigned) * slots));
-    MSL_HIP_TRY(hipMemset(h->d_arec, 0, sizeof(AssignRec) * (ns * slots + 2)));
-    MSL_HIP_TRY(hipMalloc(&h->d_chunkAbort, sizeof(int) * 32 * slots));
-    MSL_HIP_TRY(hipMalloc(&h->d_changed, sizeof(int) * 8 * slots));
-    MSL_HIP_TRY(hipMemset(h->d_seeds, 0, sizeof(msl_seed) * ns * slots));
-    MSL_HIP_TRY(hipMemset(h->d_index, 0, sizeof(unsigned short) * npx * slots));
-    MSL_HIP_TRY(hipMemset(h->d_fused, 1, fs * slots));     // (the bytes behind the lattice stay 1 = "spawns nothing": the map stage scans whole 16-byte words)
-    MSL_HIP_TRY(hipMemset(h->d_candOk, 0, fs * slots));
-    D.frames = h->d_frames; D.seeds = h->d_seeds; D.seedsTmp = h->d_seedsTmp; D.cand = h->d_cand; D.candOk = h->d_candOk; D.fused = h->d_fused; D.tex = h->d_tex; D.fuseRec = h->d_fuseRec;
-    D.index = h->d_index; D.amap = h->d_amap; D.tmin = h->d_tmin; D.chunkAbort = h->d_chunkAbort; D.changed = h->d_changed;
-    D.arec = h->d_arec + 1; D.pxInv = h->d_pxInv; D.wl = h->d_wl; D.wlCount = h->d_wlCount;
+    MSL_HIP_TRY(grow_all(h->mapStream, {{S.frames, sizeof(FrameDev) * slots}, {S.seeds, sizeof(msl_seed) * ns * slots}, {S.seedsTmp, sizeof(msl_seed) * ns * slots},
+                                        {S.cand, sizeof(msl_surfel) * ns * slots}, {S.candOk, fs * slots}, {S.fused, fs * slots},
+                                        {S.tex, sizeof(uint2) * npx * slots}, {S.fuseRec, sizeof(float4) * 3 * ns * slots},
+                                        {S.index, sizeof(unsigned short) * npx * slots}, {S.amap, sizeof(unsigned short) * npx * slots}, {S.tmin, sizeof(unsigned) * ns * slots},
+                                        {S.arec, sizeof(AssignRec) * (ns * slots + 2)},   // + a record either side: kb_assign loads row pairs that may start one before / end one after
+                                        {S.pxInv, sizeof(float) * npx * slots}, {S.wl, sizeof(unsigned) * npx * slots}, {S.wlCount, sizeof(unsigned) * slots},
+                                        {S.chunkAbort, sizeof(int) * 32 * slots}, {S.changed, sizeof(int) * 8 * slots}}));
+    MSL_HIP_TRY(S.hFrames.grow(sizeof(FrameDev) * slots, h->mapStream));
+    MSL_HIP_TRY(hipMemset(S.tex.p, 0, S.tex.cap));
+    MSL_HIP_TRY(hipMemset(S.fuseRec.p, 0, S.fuseRec.cap));
+    MSL_HIP_TRY(hipMemset(S.wlCount.p, 0, S.wlCount.cap));
+    MSL_HIP_TRY(hipMemset(S.arec.p, 0, S.arec.cap));
+    MSL_HIP_TRY(hipMemset(S.seeds.p, 0, S.seeds.cap));
+    MSL_HIP_TRY(hipMemset(S.index.p, 0, S.index.cap));
+    MSL_HIP_TRY(hipMemset(S.fused.p, 1, S.fused.cap));     // (the bytes behind the lattice stay 1 = "spawns nothing": the map stage scans whole 16-byte words)
+    MSL_HIP_TRY(hipMemset(S.candOk.p, 0, S.candOk.cap));
+    D.frames = (FrameDev *)S.frames.p; D.seeds = (msl_seed *)S.seeds.p; D.seedsTmp = (msl_seed *)S.seedsTmp.p; D.cand = (msl_surfel *)S.cand.p;
+    D.candOk = (uint8_t *)S.candOk.p; D.fused = (uint8_t *)S.fused.p; D.tex = (uint2 *)S.tex.p; D.fuseRec = (float4 *)S.fuseRec.p;
+    D.index = (unsigned short *)S.index.p; D.amap = (unsigned short *)S.amap.p; D.tmin = (unsigned *)S.tmin.p; D.chunkAbort = (int *)S.chunkAbort.p; D.changed = (int *)S.changed.p;
+    D.arec = (AssignRec *)S.arec.p + 1; D.pxInv = (float *)S.pxInv.p; D.wl = (unsigned *)S.wl.p; D.wlCount = (unsigned *)S.wlCount.p;
     { const int rc = write_ctl(h); if (rc != MSL_OK) return rc; }
     h->maxBatch = maxBatch;
     h->lastSlot = 0;            // the debug accessors must never index beyond the reallocated slot buffers
@@ -247,7 +214,7 @@ void consume_snapshots(msl_sf *h, size_t nseeds) {
     for (int i = 0; i < msl_sf::NSNAP; i++)
         if (h->snapBusy[i] && hipEventQuery(h->snapEv[i]) == hipSuccess) {
             h->snapBusy[i] = false;
-            const long long *sn = h->h_snap + (size_t)i * msl_sf::SNAPW;
+            const long long *sn = (const long long *)h->h_snap.p + (size_t)i * msl_sf::SNAPW;
             if (h->snapLive[i]) {
                 const size_t cand = (size_t)sn[0] + (size_t)(h->kfEnq - h->snapKf[i]) * nseeds;   // count then + what was enqueued since
                 if (cand < h->liveBound) h->liveBound = cand;
@@ -263,20 +230,20 @@ void consume_snapshots(msl_sf *h, size_t nseeds) {
 int read_ctr(msl_sf *h) {
     if (h->ownStreams && h->copyStream) MSL_HIP_TRY(hipStreamSynchronize(h->copyStream));
     MSL_HIP_TRY(hipStreamSynchronize(h->preStream));
-    MSL_HIP_TRY(hipMemcpyAsync(h->h_ctr, h->d_ctr, sizeof(long long) * 16, hipMemcpyDeviceToHost, h->mapStream));
+    MSL_HIP_TRY(hipMemcpyAsync(h->h_ctr.p, h->dev.ctr, sizeof(long long) * 16, hipMemcpyDeviceToHost, h->mapStream));
     MSL_HIP_TRY(hipStreamSynchronize(h->mapStream));
     h->prof.drain();
     consume_snapshots(h, (size_t)h->dev.nseeds);   // (all pending snapshots have arrived: their churn information is kept, the live count below is newer)
-    h->liveBound = (size_t)h->h_ctr[0];   // both streams are idle: the count is exact
+    h->liveBound = (size_t)((const long long *)h->h_ctr.p)[0];   // both streams are idle: the count is exact
     h->liveKnown = h->liveBound; h->liveKnownKf = h->kfEnq;
     for (int i = 0; i < msl_sf::NSNAP; i++) h->snapBusy[i] = false;   // (their events have fired: the stream is idle)
     return MSL_OK;
 }
 
 int check_err(msl_sf *h) {
-    if (h->h_ctr[5]) {
-        const long long e = h->h_ctr[5];
-        (void)hipMemsetAsync(h->d_ctr + 5, 0, sizeof(long long), h->mapStream);
+    const long long e = ((const long long *)h->h_ctr.p)[5];
+    if (e) {
+        (void)hipMemsetAsync(h->dev.ctr + 5, 0, sizeof(long long), h->mapStream);
         if (e == 20) set_error("resident surfel map capacity exceeded (reserve more with msl_sf_map_reserve)");
         else set_error("surfel pipeline device-side bound exceeded (code %lld)", e);
         return MSL_ERR_OVERFLOW;
@@ -312,12 +279,12 @@ int run_batch(msl_sf *h, int n, const int32_t *refs, const uint8_t *gray, size_t
         // exact count is read back (one sync) only when that bound reaches the capacity.
         const size_t need = (size_t)n * (size_t)D.nseeds;
         consume_snapshots(h, (size_t)D.nseeds);
-        if (h->liveBound + need > h->mapCap) {
+        if (h->liveBound + need > D.cap) {
             int rc = read_ctr(h);
             if (rc != MSL_OK) return rc;
             rc = check_err(h);
             if (rc != MSL_OK) return rc;
-            if (h->liveBound + need > h->mapCap) {
+            if (h->liveBound + need > D.cap) {
                 rc = map_realloc(h, 2 * h->liveBound + 2 * need + 65536, h->liveBound);
                 if (rc != MSL_OK) return rc;
             }
@@ -334,27 +301,24 @@ int run_batch(msl_sf *h, int n, const int32_t *refs, const uint8_t *gray, size_t
     // bytes actually present in the caller's buffers: the last row carries no stride padding
     const size_t d16b = d16 ? d16s * (size_t)(H - 1) + (size_t)W * 2 : 0;
     const size_t gb = gs * (size_t)(H - 1) + W, db = ds * (size_t)(H - 1) + (size_t)W * 4, mb = ms * (size_t)((H + 1) / 2 - 1) + (size_t)((W + 1) / 2) * 4;   // the membership image is ceil(H / 2) x ceil(W / 2) (PlaneDetection's cloud size)
+    msl_sf::Slots &S = h->slot;
+    const size_t slots = 2 * (size_t)h->maxBatch;
     if (mem == MSL_MEM_HOST) {
-        const size_t slots = 2 * (size_t)h->maxBatch;
-        if (gb > h->grayCap || db > h->depthCap || mb > h->memberCap) {
+        if (gb > S.grayCap || db > S.depthCap || mb > S.memberCap) {
             int rc = sync_all(h);
             if (rc != MSL_OK) return rc;
-            if (h->d_gray) (void)hipFree(h->d_gray);
-            if (h->d_depth) (void)hipFree(h->d_depth);
-            if (h->d_member) (void)hipFree(h->d_member);
-            h->d_gray = nullptr; h->d_depth = nullptr; h->d_member = nullptr;
-            h->grayCap = h->depthCap = h->memberCap = 0;
-            MSL_HIP_TRY(hipMalloc(&h->d_gray, gb * slots)); MSL_HIP_TRY(hipMalloc(&h->d_depth, db * slots)); MSL_HIP_TRY(hipMalloc(&h->d_member, mb * slots));
-            h->grayCap = gb; h->depthCap = db; h->memberCap = mb;
+            S.gray = DevBuf(); S.depth = DevBuf(); S.member = DevBuf(); S.grayCap = S.depthCap = S.memberCap = 0;
+            MSL_HIP_TRY(grow_all(sm, {{S.gray, gb * slots}, {S.depth, db * slots}, {S.member, mb * slots}}));
+            S.grayCap = gb; S.depthCap = db; S.memberCap = mb;
         }
-        if (d16 && d16b > h->depth16Cap) {
+        if (d16 && d16b > S.depth16Cap) {
             int rc = sync_all(h);
             if (rc != MSL_OK) return rc;
-            if (h->d_depth16) (void)hipFree(h->d_depth16);
-            h->d_depth16 = nullptr; h->depth16Cap = 0;
-            MSL_HIP_TRY(hipMalloc(&h->d_depth16, d16b * slots));
-            h->depth16Cap = d16b;
+            S.depth16Cap = 0;
+            MSL_HIP_TRY(S.depth16.grow(d16b * slots, sm));
+            S.depth16Cap = d16b;
         }
+        uint8_t *sg = (uint8_t *)S.gray.p, *sd = (uint8_t *)S.depth.p, *smb = (uint8_t *)S.member.p, *s16 = (uint8_t *)S.depth16.p;
         // The images travel on their own stream so that they overlap the superpixel kernels of the previous call (the other slot set);
         // with caller-provided streams (msl_sf_set_stream) everything stays on that one stream.
         hipStream_t sc = (h->ownStreams && h->copyStream) ? h->copyStream : sp;
@@ -366,60 +330,56 @@ int run_batch(msl_sf *h, int n, const int32_t *refs, const uint8_t *gray, size_t
         h->prof.begin(SK_COPY, sc);
         // Tightly packed frame arrays (the streaming case) travel as ONE copy per image kind instead of one per frame; a membership image
         // shared by all keyframes of the call (member_frame_stride == 0) is staged once.
-        const bool packedG = n > 1 && gfs == gb && h->grayCap == gb, packedD = !d16 && n > 1 && dfs == db && h->depthCap == db;
-        const bool packed16 = d16 && n > 1 && d16fs == d16b && h->depth16Cap == d16b;
-        const bool packedM = n > 1 && mfs == mb && h->memberCap == mb;
-        if (packedG) MSL_HIP_TRY(hipMemcpyAsync(h->d_gray + (size_t)slot0 * h->grayCap, gray, gb * (size_t)n, hipMemcpyHostToDevice, sc));
-        if (packedD) MSL_HIP_TRY(hipMemcpyAsync((uint8_t *)h->d_depth + (size_t)slot0 * h->depthCap, depth, db * (size_t)n, hipMemcpyHostToDevice, sc));
-        if (packed16) MSL_HIP_TRY(hipMemcpyAsync(h->d_depth16 + (size_t)slot0 * h->depth16Cap, depth16, d16b * (size_t)n, hipMemcpyHostToDevice, sc));
-        if (packedM) MSL_HIP_TRY(hipMemcpyAsync((uint8_t *)h->d_member + (size_t)slot0 * h->memberCap, member, mb * (size_t)n, hipMemcpyHostToDevice, sc));
-        if (mfs == 0) MSL_HIP_TRY(hipMemcpyAsync((uint8_t *)h->d_member + (size_t)slot0 * h->memberCap, member, mb, hipMemcpyHostToDevice, sc));
+        const bool packedG = n > 1 && gfs == gb && S.grayCap == gb, packedD = !d16 && n > 1 && dfs == db && S.depthCap == db;
+        const bool packed16 = d16 && n > 1 && d16fs == d16b && S.depth16Cap == d16b;
+        const bool packedM = n > 1 && mfs == mb && S.memberCap == mb;
+        if (packedG) MSL_HIP_TRY(hipMemcpyAsync(sg + (size_t)slot0 * S.grayCap, gray, gb * (size_t)n, hipMemcpyHostToDevice, sc));
+        if (packedD) MSL_HIP_TRY(hipMemcpyAsync(sd + (size_t)slot0 * S.depthCap, depth, db * (size_t)n, hipMemcpyHostToDevice, sc));
+        if (packed16) MSL_HIP_TRY(hipMemcpyAsync(s16 + (size_t)slot0 * S.depth16Cap, depth16, d16b * (size_t)n, hipMemcpyHostToDevice, sc));
+        if (packedM) MSL_HIP_TRY(hipMemcpyAsync(smb + (size_t)slot0 * S.memberCap, member, mb * (size_t)n, hipMemcpyHostToDevice, sc));
+        if (mfs == 0) MSL_HIP_TRY(hipMemcpyAsync(smb + (size_t)slot0 * S.memberCap, member, mb, hipMemcpyHostToDevice, sc));
         for (int f = 0; f < n; f++) {
             const size_t s = slot0 + f;
-            if (!packedG) MSL_HIP_TRY(hipMemcpyAsync(h->d_gray + s * h->grayCap, gray + f * gfs, gb, hipMemcpyHostToDevice, sc));
-            if (!d16 && !packedD) MSL_HIP_TRY(hipMemcpyAsync((uint8_t *)h->d_depth + s * h->depthCap, (const uint8_t *)depth + f * dfs, db, hipMemcpyHostToDevice, sc));
-            if (d16 && !packed16) MSL_HIP_TRY(hipMemcpyAsync(h->d_depth16 + s * h->depth16Cap, (const uint8_t *)depth16 + f * d16fs, d16b, hipMemcpyHostToDevice, sc));
-            if (!packedM && mfs != 0) MSL_HIP_TRY(hipMemcpyAsync((uint8_t *)h->d_member + s * h->memberCap, (const uint8_t *)member + f * mfs, mb, hipMemcpyHostToDevice, sc));
+            if (!packedG) MSL_HIP_TRY(hipMemcpyAsync(sg + s * S.grayCap, gray + f * gfs, gb, hipMemcpyHostToDevice, sc));
+            if (!d16 && !packedD) MSL_HIP_TRY(hipMemcpyAsync(sd + s * S.depthCap, (const uint8_t *)depth + f * dfs, db, hipMemcpyHostToDevice, sc));
+            if (d16 && !packed16) MSL_HIP_TRY(hipMemcpyAsync(s16 + s * S.depth16Cap, (const uint8_t *)depth16 + f * d16fs, d16b, hipMemcpyHostToDevice, sc));
+            if (!packedM && mfs != 0) MSL_HIP_TRY(hipMemcpyAsync(smb + s * S.memberCap, (const uint8_t *)member + f * mfs, mb, hipMemcpyHostToDevice, sc));
         }
         if (d16)   // raw -> metres behind the copies, on their stream (same rows of stride d16s in the staging slots; frames depth16Cap bytes apart)
-            sp_launch_depth_u16(sc, h->d_depth16 + (size_t)slot0 * h->depth16Cap, d16s, h->depth16Cap, (float *)((uint8_t *)h->d_depth + (size_t)slot0 * h->depthCap),
-                                h->depthCap / 4, W, H, n, depthFactor);
+            sp_launch_depth_u16(sc, s16 + (size_t)slot0 * S.depth16Cap, d16s, S.depth16Cap, (float *)(sd + (size_t)slot0 * S.depthCap), S.depthCap / 4, W, H, n, depthFactor);
         h->prof.end(sc);
         MSL_HIP_TRY(hipEventRecord(h->evH2D[set], sc));   // (always: msl_sf_staged_gray hands it to other handles)
         if (sc != sp) MSL_HIP_TRY(hipStreamWaitEvent(sp, h->evH2D[set], 0));
         h->stagedSet = set; h->stagedGs = gs;
     }
     if (d16 && mem != MSL_MEM_HOST) {   // device-resident raw depth: converted into the handle's float slots on the superpixel stream
-        const size_t slots = 2 * (size_t)h->maxBatch;
-        if (db > h->depthCap || !h->d_depth) {
+        if (db > S.depthCap) {
             int rc = sync_all(h);
             if (rc != MSL_OK) return rc;
-            if (h->d_gray) (void)hipFree(h->d_gray);
-            if (h->d_depth) (void)hipFree(h->d_depth);
-            if (h->d_member) (void)hipFree(h->d_member);
-            h->d_gray = nullptr; h->d_depth = nullptr; h->d_member = nullptr;
-            h->grayCap = h->depthCap = h->memberCap = 0;     // (a later host-image call allocates all three anew)
-            MSL_HIP_TRY(hipMalloc(&h->d_depth, db * slots));
-            h->depthCap = db;
+            S.gray = DevBuf(); S.depth = DevBuf(); S.member = DevBuf(); S.grayCap = S.depthCap = S.memberCap = 0;   // (a later host-image call allocates all three anew)
+            MSL_HIP_TRY(S.depth.grow(db * slots, sm));
+            S.depthCap = db;
         }
-        sp_launch_depth_u16(sp, depth16, d16s, d16fs, (float *)((uint8_t *)h->d_depth + (size_t)slot0 * h->depthCap), h->depthCap / 4, W, H, n, depthFactor);
+        sp_launch_depth_u16(sp, depth16, d16s, d16fs, (float *)((uint8_t *)S.depth.p + (size_t)slot0 * S.depthCap), S.depthCap / 4, W, H, n, depthFactor);
     }
+    const uint8_t *sd = (const uint8_t *)S.depth.p;
     if (h->evCopyValid[set]) MSL_HIP_TRY(hipEventSynchronize(h->evCopy[set]));   // pinned staging of this set is free again
+    FrameDev *hf = (FrameDev *)S.hFrames.p;
     for (int f = 0; f < n; f++) {
-        FrameDev &F = h->h_frames[slot0 + f];
+        FrameDev &F = hf[slot0 + f];
+        const size_t s = slot0 + f;
         if (mem == MSL_MEM_HOST) {
-            const size_t s = slot0 + f;
-            F.gray = h->d_gray + s * h->grayCap; F.depth = (const float *)((uint8_t *)h->d_depth + s * h->depthCap);
-            F.member = (const int32_t *)((uint8_t *)h->d_member + (mfs == 0 ? (size_t)slot0 : s) * h->memberCap);
+            F.gray = (const uint8_t *)S.gray.p + s * S.grayCap; F.depth = (const float *)(sd + s * S.depthCap);
+            F.member = (const int32_t *)((const uint8_t *)S.member.p + (mfs == 0 ? (size_t)slot0 : s) * S.memberCap);
         } else {
             F.gray = gray + f * gfs; F.member = (const int32_t *)((const uint8_t *)member + f * mfs);
-            F.depth = d16 ? (const float *)((uint8_t *)h->d_depth + (size_t)(slot0 + f) * h->depthCap) : (const float *)((const uint8_t *)depth + f * dfs);
+            F.depth = d16 ? (const float *)(sd + s * S.depthCap) : (const float *)((const uint8_t *)depth + f * dfs);
         }
         memcpy(F.pose, poses + 16 * f, sizeof(float) * 16);
         inverse4<float>(F.pose, F.invPose);   // pose.inverse() (:59), adjugate/determinant in float
         F.ref = refs[f]; F._pad = 0;
     }
-    MSL_HIP_TRY(hipMemcpyAsync(h->d_frames + slot0, h->h_frames + slot0, sizeof(FrameDev) * n, hipMemcpyHostToDevice, sp));
+    MSL_HIP_TRY(hipMemcpyAsync((FrameDev *)S.frames.p + slot0, hf + slot0, sizeof(FrameDev) * n, hipMemcpyHostToDevice, sp));
     MSL_HIP_TRY(hipEventRecord(h->evCopy[set], sp));
     h->evCopyValid[set] = true;
 
@@ -437,7 +397,7 @@ int run_batch(msl_sf *h, int n, const int32_t *refs, const uint8_t *gray, size_t
         h->evPreValid[set] = true;
         MSL_HIP_TRY(hipStreamWaitEvent(sm, h->evPre[set], 0));
     }
-    const size_t boundLive = compact ? h->liveBound : h->mapCap;
+    const size_t boundLive = compact ? h->liveBound : D.cap;
     // grid: the last known live count plus a margin (k_fuse is grid-stride, so a map that outgrew it is still covered), never beyond the upper
     // bound; hint: the sub-blocks that were full at the last known count load without waiting for the live count
     const size_t known = std::min(h->liveKnown, boundLive);
@@ -468,7 +428,7 @@ int run_batch(msl_sf *h, int n, const int32_t *refs, const uint8_t *gray, size_t
     const bool churny = !deferForce && (h->churn > CHURN_MAX || sp != sm);
     auto classic = [&](int f) {
         P.kf = 0;
-        map_launch_fuse(h->prof, sm, P, f, h->h_frames[slot0 + f], nSubGrid, nSubHint, false, dealOn && h->dealG == nSubGrid);
+        map_launch_fuse(h->prof, sm, P, f, hf[slot0 + f], nSubGrid, nSubHint, false, dealOn && h->dealG == nSubGrid);
         // k_compact's second workgroup deals the sub-blocks for the launches that follow (resident mode: 128 workgroups) -- on every DEAL_EVERY-th
         // keyframe of a call and whenever the table does not fit the grid: the pass takes one workgroup ~10 us against the compaction's ~6 beside it
         // (32 keys per thread through LDS atomics and scattered stores), and a table a few keyframes old still has nearly every sub-block in the
@@ -488,7 +448,7 @@ int run_batch(msl_sf *h, int n, const int32_t *refs, const uint8_t *gray, size_t
             const int w = std::min(DEFER_WIN, n - f);
             for (int q = 0; q < w; q++) {
                 P.kf = q; P.prevSlotAbs = slot0 + f + q - 1;
-                map_launch_fuse(h->prof, sm, P, f + q, h->h_frames[slot0 + f + q], nSubGrid, nSubHint, true, dealOn && h->dealG == nSubGrid);
+                map_launch_fuse(h->prof, sm, P, f + q, hf[slot0 + f + q], nSubGrid, nSubHint, true, dealOn && h->dealG == nSubGrid);
                 if (f + q == fProbe) map_launch_empty_pair(h->prof, sm);
             }
             P.kf = w; P.prevSlotAbs = slot0 + f + w - 1;
@@ -500,10 +460,10 @@ int run_batch(msl_sf *h, int n, const int32_t *refs, const uint8_t *gray, size_t
     }
     if (compact) h->classicNext = false;
     if (sp != sm) { MSL_HIP_TRY(hipEventRecord(h->evMap[set], sm)); h->evMapValid[set] = true; }
-    if (compact && h->h_snap) {   // snapshot of the live count after this batch (picked up by a later call, never waited for)
+    if (compact && h->h_snap.p) {   // snapshot of the live count after this batch (picked up by a later call, never waited for)
         const int i = h->snapNext;
         if (!h->snapBusy[i]) {
-            MSL_HIP_TRY(hipMemcpyAsync(h->h_snap + (size_t)i * msl_sf::SNAPW, h->d_ctr, sizeof(long long) * msl_sf::SNAPW, hipMemcpyDeviceToHost, sm));
+            MSL_HIP_TRY(hipMemcpyAsync((long long *)h->h_snap.p + (size_t)i * msl_sf::SNAPW, D.ctr, sizeof(long long) * msl_sf::SNAPW, hipMemcpyDeviceToHost, sm));
             MSL_HIP_TRY(hipEventRecord(h->snapEv[i], sm));
             h->snapKf[i] = h->kfEnq; h->snapBusy[i] = true; h->snapLive[i] = true; h->snapNext = (i + 1) % msl_sf::NSNAP;
         }
@@ -548,29 +508,30 @@ msl_sf *msl_sf_create(int width, int height, float fx, float fy, float cx, float
         ok = hipEventCreateWithFlags(&h->evPre[i], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&h->evMap[i], hipEventDisableTiming) == hipSuccess &&
              hipEventCreateWithFlags(&h->evCopy[i], hipEventDisableTiming) == hipSuccess &&
              hipEventCreateWithFlags(&h->evH2D[i], hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipMalloc(&h->d_ctr, sizeof(long long) * 32) == hipSuccess;   // 16 counters (read_ctr) + [16..18] the published live counts
-    ok = ok && hipMemset(h->d_ctr, 0, sizeof(long long) * 32) == hipSuccess;
-    ok = ok && hipHostMalloc(&h->h_ctr, sizeof(long long) * 16) == hipSuccess;
-    ok = ok && hipHostMalloc(&h->h_snap, sizeof(long long) * msl_sf::NSNAP * msl_sf::SNAPW) == hipSuccess;
+    const hipStream_t sm = h->mapStream;
+    ok = ok && h->d_ctr.grow(sizeof(long long) * 32, sm) == hipSuccess;   // 16 counters (read_ctr) + [16..18] the published live counts
+    ok = ok && hipMemset(h->d_ctr.p, 0, sizeof(long long) * 32) == hipSuccess;
+    ok = ok && h->h_ctr.grow(sizeof(long long) * 16, sm) == hipSuccess;
+    ok = ok && h->h_snap.grow(sizeof(long long) * msl_sf::NSNAP * msl_sf::SNAPW, sm) == hipSuccess;
     for (int i = 0; i < msl_sf::NSNAP && ok; i++) ok = hipEventCreateWithFlags(&h->snapEv[i], hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipMalloc(&h->d_new, sizeof(msl_surfel) * D.nseeds) == hipSuccess;
-    ok = ok && hipMalloc(&h->d_tickets, sizeof(unsigned) * 8) == hipSuccess && hipMemset(h->d_tickets, 0, sizeof(unsigned) * 8) == hipSuccess;   // [0..1] tickets, [3] change-list length, [4..6] the rotating hand-over counts
-    ok = ok && hipMalloc(&h->d_delU, sizeof(unsigned) * LIST_D) == hipSuccess;
-    ok = ok && hipMalloc(&h->d_dc, sizeof(DeferCtl)) == hipSuccess && hipMemset(h->d_dc, 0, sizeof(DeferCtl)) == hipSuccess;
+    ok = ok && h->d_new.grow(sizeof(msl_surfel) * D.nseeds, sm) == hipSuccess;
+    ok = ok && h->d_tickets.grow(sizeof(unsigned) * 8, sm) == hipSuccess && hipMemset(h->d_tickets.p, 0, sizeof(unsigned) * 8) == hipSuccess;   // [0..1] tickets, [3] change-list length, [4..6] the rotating hand-over counts
+    ok = ok && h->d_delU.grow(sizeof(unsigned) * LIST_D, sm) == hipSuccess;
+    ok = ok && h->d_dc.grow(sizeof(DeferCtl), sm) == hipSuccess && hipMemset(h->d_dc.p, 0, sizeof(DeferCtl)) == hipSuccess;
     {   // (u - cx) / fx and (v - cy) / fy of every integer pixel coordinate: the float expression of back_project
         // (src/SurfelFusion.cpp:80-85) evaluated once here instead of six divisions per pixel in kb_seed_plane
         std::vector<float> tab((size_t)width + 1 + height + 1);
         for (int u = 0; u <= width; u++) tab[u] = ((float)u - cx) / fx;
         for (int v = 0; v <= height; v++) tab[(size_t)width + 1 + v] = ((float)v - cy) / fy;
-        ok = ok && hipMalloc(&h->d_projTab, sizeof(float) * tab.size()) == hipSuccess;
-        ok = ok && hipMemcpy(h->d_projTab, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice) == hipSuccess;
-        D.colX = h->d_projTab; D.rowY = h->d_projTab + width + 1;
+        ok = ok && h->d_projTab.grow(sizeof(float) * tab.size(), sm) == hipSuccess;
+        ok = ok && hipMemcpy(h->d_projTab.p, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice) == hipSuccess;
+        D.colX = (const float *)h->d_projTab.p; D.rowY = D.colX + width + 1;
     }
     if (ok) h->propLds = sp_init_attributes(D.nseeds);
     if (!ok) { set_error("msl_sf_create: HIP allocation failed"); return nullptr; }
-    memset(h->h_ctr, 0, sizeof(long long) * 16);
-    D.ctr = h->d_ctr; D.newSurfels = h->d_new; D.tickets = h->d_tickets; D.delU = h->d_delU; D.delUCount = h->d_tickets + 4;
-    D.dc = h->d_dc; D.kf = 0; D.prevSlotAbs = 0;
+    memset(h->h_ctr.p, 0, sizeof(long long) * 16);
+    D.ctr = (long long *)h->d_ctr.p; D.newSurfels = (msl_surfel *)h->d_new.p; D.tickets = (unsigned *)h->d_tickets.p; D.delU = (unsigned *)h->d_delU.p;
+    D.delUCount = D.tickets + 4; D.dc = (DeferCtl *)h->d_dc.p; D.kf = 0; D.prevSlotAbs = 0;
     h->prof.nk = MSL_SF_NKERNELS;
     if (alloc_slots(h, 1) != MSL_OK || map_realloc(h, 1 << 16, 0) != MSL_OK) return nullptr;
     return guard.release();
@@ -585,27 +546,20 @@ void msl_sf_destroy(msl_sf *h) noexcept {
     if (h->preStream) (void)hipStreamSynchronize(h->preStream);
     if (h->mapStream) (void)hipStreamSynchronize(h->mapStream);
     h->prof.destroy();
-    free_slots(h);
-    auto F = [](auto *p) { if (p) (void)hipFree(p); };
-    F(h->d_ctr); F(h->d_tickets); F(h->d_delU); F(h->d_dc); F(h->d_rpStore); F(h->d_projTab); F(h->d_new); F(h->d_mapStore); F(h->d_blockSums); F(h->d_blockUpd); F(h->d_delList); F(h->d_srcOf); F(h->d_aos); F(h->d_snapStore);
-    if (h->h_ctr) (void)hipHostFree(h->h_ctr);
-    if (h->h_snap) (void)hipHostFree(h->h_snap);
-    if (h->h_blk) (void)hipHostFree(h->h_blk);
-    if (h->h_list) (void)hipHostFree(h->h_list);
     for (int i = 0; i < msl_sf::NSNAP; i++) if (h->snapEv[i]) (void)hipEventDestroy(h->snapEv[i]);
     for (int i = 0; i < 2; i++) { if (h->evPre[i]) (void)hipEventDestroy(h->evPre[i]); if (h->evMap[i]) (void)hipEventDestroy(h->evMap[i]); if (h->evCopy[i]) (void)hipEventDestroy(h->evCopy[i]); if (h->evH2D[i]) (void)hipEventDestroy(h->evH2D[i]); }
-    if (h->copyStream) (void)hipStreamDestroy(h->copyStream);
-    if (h->ownStreams) { if (h->preStream) (void)hipStreamDestroy(h->preStream); if (h->mapStream) (void)hipStreamDestroy(h->mapStream); }
-    delete h;
+    const hipStream_t streams[3] = {h->copyStream, h->ownStreams ? h->preStream : nullptr, h->ownStreams ? h->mapStream : nullptr};
+    delete h;   // frees the buffers
+    for (hipStream_t st : streams) if (st) (void)hipStreamDestroy(st);
     } MSL_ABI_CATCH_VOID
 }
 
 int msl_sf_staged_gray(msl_sf *h, const uint8_t **gray_dev, size_t *row_stride, size_t *frame_stride, void **uploaded_event) noexcept {
     try {
     if (!h || !gray_dev || !row_stride || !frame_stride || !uploaded_event) return MSL_ERR_INVALID;
-    if (h->stagedSet < 0 || !h->d_gray) { set_error("msl_sf_staged_gray: the last batch had no host images"); return MSL_ERR_INVALID; }
-    *gray_dev = h->d_gray + (size_t)h->stagedSet * (size_t)h->maxBatch * h->grayCap;
-    *row_stride = h->stagedGs; *frame_stride = h->grayCap; *uploaded_event = (void *)h->evH2D[h->stagedSet];
+    if (h->stagedSet < 0 || !h->slot.gray.p) { set_error("msl_sf_staged_gray: the last batch had no host images"); return MSL_ERR_INVALID; }
+    *gray_dev = (const uint8_t *)h->slot.gray.p + (size_t)h->stagedSet * (size_t)h->maxBatch * h->slot.grayCap;
+    *row_stride = h->stagedGs; *frame_stride = h->slot.grayCap; *uploaded_event = (void *)h->evH2D[h->stagedSet];
     return MSL_OK;
     } MSL_ABI_CATCH_INT
 }
@@ -647,21 +601,11 @@ int msl_sf_map_reserve(msl_sf *h, size_t capacity) noexcept {
     try {
     if (!h) return MSL_ERR_INVALID;
     MSL_HIP_TRY(hipSetDevice(h->device));
-    if (capacity <= h->mapCap) return MSL_OK;
+    if (capacity <= h->dev.cap) return MSL_OK;
     int rc = read_ctr(h);
     if (rc != MSL_OK) return rc;
-    return map_realloc(h, capacity, (size_t)h->h_ctr[0]);
+    return map_realloc(h, capacity, (size_t)((const long long *)h->h_ctr.p)[0]);
     } MSL_ABI_CATCH_INT
-}
-
-static int ensure_aos(msl_sf *h, size_t n) {
-    if (n > h->aosCap) {
-        if (h->d_aos) (void)hipFree(h->d_aos);
-        h->d_aos = nullptr; h->aosCap = 0;
-        MSL_HIP_TRY(hipMalloc(&h->d_aos, sizeof(msl_surfel) * n));
-        h->aosCap = n;
-    }
-    return MSL_OK;
 }
 
 int msl_sf_map_upload(msl_sf *h, const msl_surfel *host, size_t n) noexcept {
@@ -671,17 +615,16 @@ int msl_sf_map_upload(msl_sf *h, const msl_surfel *host, size_t n) noexcept {
     MSL_HIP_TRY(hipSetDevice(h->device));
     int rc = sync_all(h);
     if (rc != MSL_OK) return rc;
-    if (n + (size_t)h->dev.nseeds > h->mapCap) {
+    if (n + (size_t)h->dev.nseeds > h->dev.cap) {
         rc = map_realloc(h, n + n / 4 + 4 * (size_t)h->dev.nseeds, 0);
         if (rc != MSL_OK) return rc;
     }
     hipStream_t s = h->mapStream;
-    MSL_HIP_TRY(hipMemsetAsync(h->d_ctr + 13, 0, sizeof(long long), s));   // a fresh map: no wide r, g, b records yet
+    MSL_HIP_TRY(hipMemsetAsync(h->dev.ctr + 13, 0, sizeof(long long), s));   // a fresh map: no wide r, g, b records yet
     if (n) {
-        rc = ensure_aos(h, n);
-        if (rc != MSL_OK) return rc;
-        MSL_HIP_TRY(hipMemcpyAsync(h->d_aos, host, sizeof(msl_surfel) * n, hipMemcpyHostToDevice, s));
-        map_launch_aos_to_soa(h->prof, s, h->dev, h->d_aos, (long long)n, false);
+        MSL_HIP_TRY(h->d_aos.grow(sizeof(msl_surfel) * n, s));
+        MSL_HIP_TRY(hipMemcpyAsync(h->d_aos.p, host, sizeof(msl_surfel) * n, hipMemcpyHostToDevice, s));
+        map_launch_aos_to_soa(h->prof, s, h->dev, (const msl_surfel *)h->d_aos.p, (long long)n, false);
     }
     map_launch_set_ctr(s, h->dev, (long long)n, -1);
     MSL_HIP_TRY(hipStreamSynchronize(s));
@@ -699,21 +642,19 @@ int msl_sf_map_snapshot(msl_sf *h) noexcept {
     if (rc != MSL_OK) return rc;
     rc = check_err(h);
     if (rc != MSL_OK) return rc;
-    const size_t n = (size_t)h->h_ctr[0];
-    if (n > h->snapCap) {
-        if (h->d_snapStore) (void)hipFree(h->d_snapStore);
-        h->d_snapStore = nullptr; h->snapCap = 0; h->snapValid = false;
-        const size_t c = (n + 4095) & ~(size_t)4095;
-        MSL_HIP_TRY(hipMalloc(&h->d_snapStore, sizeof(float) * MAP_WORDS * c));
-        h->snapCap = c;
-    }
+    const long long *ctr = (const long long *)h->h_ctr.p;
+    const size_t n = (size_t)ctr[0];
+    h->snapValid = false;   // (until the copies below are complete)
+    MSL_HIP_TRY(h->d_snapStore.grow(sizeof(float) * MAP_WORDS * ((n + 4095) & ~(size_t)4095), h->mapStream));
     if (n) {
-        MSL_HIP_TRY(hipMemcpy(h->d_snapStore, h->dev.map.hot, sizeof(HotPk) * n, hipMemcpyDeviceToDevice));
-        MSL_HIP_TRY(hipMemcpy(h->d_snapStore + 4 * h->snapCap, h->dev.map.cold, sizeof(ColdRec) * n, hipMemcpyDeviceToDevice));
-        if (h->h_ctr[13] & 1) MSL_HIP_TRY(hipMemcpy(h->d_snapStore + 12 * h->snapCap, h->dev.map.rgbWide, sizeof(int) * 3 * n, hipMemcpyDeviceToDevice));
-        if (h->h_ctr[13] & 2) MSL_HIP_TRY(hipMemcpy(h->d_snapStore + 15 * h->snapCap, h->dev.map.utlWide, sizeof(int) * 2 * n, hipMemcpyDeviceToDevice));
+        float *snap = (float *)h->d_snapStore.p;
+        const size_t sc = h->d_snapStore.cap / (sizeof(float) * MAP_WORDS);   // surfels the store is laid out for
+        MSL_HIP_TRY(hipMemcpy(snap, h->dev.map.hot, sizeof(HotPk) * n, hipMemcpyDeviceToDevice));
+        MSL_HIP_TRY(hipMemcpy(snap + 4 * sc, h->dev.map.cold, sizeof(ColdRec) * n, hipMemcpyDeviceToDevice));
+        if (ctr[13] & 1) MSL_HIP_TRY(hipMemcpy(snap + 12 * sc, h->dev.map.rgbWide, sizeof(int) * 3 * n, hipMemcpyDeviceToDevice));
+        if (ctr[13] & 2) MSL_HIP_TRY(hipMemcpy(snap + 15 * sc, h->dev.map.utlWide, sizeof(int) * 2 * n, hipMemcpyDeviceToDevice));
     }
-    h->snapN = n; h->snapValid = true; h->snapWide = h->h_ctr[13];
+    h->snapN = n; h->snapValid = true; h->snapWide = ctr[13];
     return MSL_OK;
     } MSL_ABI_CATCH_INT
 }
@@ -724,7 +665,7 @@ int msl_sf_map_restore(msl_sf *h) noexcept {
     h->mirrorValid = false;
     MSL_HIP_TRY(hipSetDevice(h->device));
     const size_t n = h->snapN;
-    if (n + (size_t)h->dev.nseeds > h->mapCap) {   // the map was reallocated smaller than the snapshot (upload of a small map): grow again
+    if (n + (size_t)h->dev.nseeds > h->dev.cap) {   // the map was reallocated smaller than the snapshot (upload of a small map): grow again
         int rc = read_ctr(h);
         if (rc != MSL_OK) return rc;
         rc = map_realloc(h, n + n / 4 + 4 * (size_t)h->dev.nseeds, 0);
@@ -732,10 +673,12 @@ int msl_sf_map_restore(msl_sf *h) noexcept {
     }
     hipStream_t s = h->mapStream;   // ordered after every keyframe enqueued so far; the superpixel stream never touches the map
     if (n) {
-        MSL_HIP_TRY(hipMemcpyAsync(h->dev.map.hot, h->d_snapStore, sizeof(HotPk) * n, hipMemcpyDeviceToDevice, s));
-        MSL_HIP_TRY(hipMemcpyAsync(h->dev.map.cold, h->d_snapStore + 4 * h->snapCap, sizeof(ColdRec) * n, hipMemcpyDeviceToDevice, s));
-        if (h->snapWide & 1) MSL_HIP_TRY(hipMemcpyAsync(h->dev.map.rgbWide, h->d_snapStore + 12 * h->snapCap, sizeof(int) * 3 * n, hipMemcpyDeviceToDevice, s));
-        if (h->snapWide & 2) MSL_HIP_TRY(hipMemcpyAsync(h->dev.map.utlWide, h->d_snapStore + 15 * h->snapCap, sizeof(int) * 2 * n, hipMemcpyDeviceToDevice, s));
+        const float *snap = (const float *)h->d_snapStore.p;
+        const size_t sc = h->d_snapStore.cap / (sizeof(float) * MAP_WORDS);
+        MSL_HIP_TRY(hipMemcpyAsync(h->dev.map.hot, snap, sizeof(HotPk) * n, hipMemcpyDeviceToDevice, s));
+        MSL_HIP_TRY(hipMemcpyAsync(h->dev.map.cold, snap + 4 * sc, sizeof(ColdRec) * n, hipMemcpyDeviceToDevice, s));
+        if (h->snapWide & 1) MSL_HIP_TRY(hipMemcpyAsync(h->dev.map.rgbWide, snap + 12 * sc, sizeof(int) * 3 * n, hipMemcpyDeviceToDevice, s));
+        if (h->snapWide & 2) MSL_HIP_TRY(hipMemcpyAsync(h->dev.map.utlWide, snap + 15 * sc, sizeof(int) * 2 * n, hipMemcpyDeviceToDevice, s));
     }
     // the restored map has exactly the snapshot's wide-rgb state: without the flag a later snapshot would skip rgbWide and a restore of THAT
     // one would bring COLD_WIDE records back without their exact ints
@@ -753,7 +696,7 @@ int msl_sf_map_size(msl_sf *h, size_t *n_out) noexcept {
     MSL_HIP_TRY(hipSetDevice(h->device));
     int rc = read_ctr(h);
     if (rc != MSL_OK) return rc;
-    *n_out = (size_t)h->h_ctr[0];
+    *n_out = (size_t)((const long long *)h->h_ctr.p)[0];
     return check_err(h);
     } MSL_ABI_CATCH_INT
 }
@@ -764,15 +707,14 @@ int msl_sf_map_download(msl_sf *h, msl_surfel *host, size_t cap, size_t *n_out) 
     MSL_HIP_TRY(hipSetDevice(h->device));
     int rc = read_ctr(h);
     if (rc != MSL_OK) return rc;
-    const size_t n = (size_t)h->h_ctr[0];
+    const size_t n = (size_t)((const long long *)h->h_ctr.p)[0];
     *n_out = n;
     if (n > cap || (n && !host)) { set_error("msl_sf_map_download: capacity %zu < map size %zu", cap, n); return MSL_ERR_CAPACITY; }
     if (n) {
-        rc = ensure_aos(h, n);
-        if (rc != MSL_OK) return rc;
         hipStream_t s = h->mapStream;
-        map_launch_soa_to_aos(h->prof, s, h->dev, h->d_aos, (long long)n);
-        MSL_HIP_TRY(hipMemcpyAsync(host, h->d_aos, sizeof(msl_surfel) * n, hipMemcpyDeviceToHost, s));
+        MSL_HIP_TRY(h->d_aos.grow(sizeof(msl_surfel) * n, s));
+        map_launch_soa_to_aos(h->prof, s, h->dev, (msl_surfel *)h->d_aos.p, (long long)n);
+        MSL_HIP_TRY(hipMemcpyAsync(host, h->d_aos.p, sizeof(msl_surfel) * n, hipMemcpyDeviceToHost, s));
         MSL_HIP_TRY(hipStreamSynchronize(s));
     }
     return check_err(h);
@@ -787,7 +729,7 @@ static int map_select(msl_sf *h, int mode, int arg, bool mark, msl_surfel *out, 
     if (rc != MSL_OK) return rc;
     rc = check_err(h);
     if (rc != MSL_OK) return rc;
-    const size_t n = (size_t)h->h_ctr[0];
+    const size_t n = (size_t)((const long long *)h->h_ctr.p)[0];
     *n_out = 0;
     if (n == 0) return MSL_OK;
     hipStream_t s = h->mapStream;
@@ -795,15 +737,14 @@ static int map_select(msl_sf *h, int mode, int arg, bool mark, msl_surfel *out, 
     map_launch_select_count(s, P, mode, arg);
     rc = read_ctr(h);
     if (rc != MSL_OK) return rc;
-    const size_t m = (size_t)h->h_ctr[7];
+    const size_t m = (size_t)((const long long *)h->h_ctr.p)[7];
     *n_out = m;
-    (void)hipMemsetAsync(h->d_ctr + 7, 0, sizeof(long long), s);
+    (void)hipMemsetAsync(h->dev.ctr + 7, 0, sizeof(long long), s);
     if (m > cap || (m && !out)) { set_error("%s: %zu surfels selected, capacity %zu", what, m, cap); return MSL_ERR_CAPACITY; }
     if (m == 0) return MSL_OK;
-    rc = ensure_aos(h, m);
-    if (rc != MSL_OK) return rc;
-    map_launch_select_write(s, P, mode, arg, h->d_aos, mark ? 1 : 0);
-    MSL_HIP_TRY(hipMemcpyAsync(out, h->d_aos, sizeof(msl_surfel) * m, hipMemcpyDeviceToHost, s));
+    MSL_HIP_TRY(h->d_aos.grow(sizeof(msl_surfel) * m, s));
+    map_launch_select_write(s, P, mode, arg, (msl_surfel *)h->d_aos.p, mark ? 1 : 0);
+    MSL_HIP_TRY(hipMemcpyAsync(out, h->d_aos.p, sizeof(msl_surfel) * m, hipMemcpyDeviceToHost, s));
     MSL_HIP_TRY(hipStreamSynchronize(s));
     return MSL_OK;
 }
@@ -856,16 +797,15 @@ int msl_sf_map_append(msl_sf *h, const msl_surfel *surfels, size_t n) noexcept {
     int rc = read_ctr(h);
     if (rc != MSL_OK) return rc;
     if (n == 0) return MSL_OK;
-    const size_t cur = (size_t)h->h_ctr[0];
-    if (cur + n + (size_t)h->dev.nseeds > h->mapCap) {
+    const size_t cur = (size_t)((const long long *)h->h_ctr.p)[0];
+    if (cur + n + (size_t)h->dev.nseeds > h->dev.cap) {
         rc = map_realloc(h, cur + n + (cur + n) / 4 + 4 * (size_t)h->dev.nseeds, cur);
         if (rc != MSL_OK) return rc;
     }
-    rc = ensure_aos(h, n);
-    if (rc != MSL_OK) return rc;
     hipStream_t s = h->mapStream;
-    MSL_HIP_TRY(hipMemcpyAsync(h->d_aos, surfels, sizeof(msl_surfel) * n, hipMemcpyHostToDevice, s));
-    map_launch_aos_to_soa(h->prof, s, h->dev, h->d_aos, (long long)n, true);
+    MSL_HIP_TRY(h->d_aos.grow(sizeof(msl_surfel) * n, s));
+    MSL_HIP_TRY(hipMemcpyAsync(h->d_aos.p, surfels, sizeof(msl_surfel) * n, hipMemcpyHostToDevice, s));
+    map_launch_aos_to_soa(h->prof, s, h->dev, (const msl_surfel *)h->d_aos.p, (long long)n, true);
     map_launch_add_ctr(s, h->dev, (long long)n);
     MSL_HIP_TRY(hipStreamSynchronize(s));
     h->liveBound = cur + n; h->liveKnown = cur + n; h->liveKnownKf = h->kfEnq; h->classicNext = true;
@@ -915,7 +855,8 @@ int msl_sf_last_counters(msl_sf *h, int64_t counters[5]) noexcept {
     MSL_HIP_TRY(hipSetDevice(h->device));
     int rc = read_ctr(h);
     if (rc != MSL_OK) return rc;
-    counters[0] = h->h_ctr[4]; counters[1] = h->h_ctr[1]; counters[2] = h->h_ctr[2]; counters[3] = h->h_ctr[3]; counters[4] = h->h_ctr[0];
+    const long long *ctr = (const long long *)h->h_ctr.p;
+    counters[0] = ctr[4]; counters[1] = ctr[1]; counters[2] = ctr[2]; counters[3] = ctr[3]; counters[4] = ctr[0];
     return check_err(h);
     } MSL_ABI_CATCH_INT
 }
@@ -949,31 +890,28 @@ int msl_sf_fuse_ex(msl_sf *h, int referenceFrameIndex, const uint8_t *gray, size
     if (rc != MSL_OK) return rc;
     hipStream_t s = h->mapStream;
     const size_t nblk = (n_local + SUB_ITEMS - 1) / SUB_ITEMS;
-    if (nblk > h->blkCap) {
-        if (h->h_blk) (void)hipHostFree(h->h_blk);
-        h->h_blk = nullptr; h->blkCap = 0;
-        MSL_HIP_TRY(hipHostMalloc(&h->h_blk, sizeof(unsigned) * 2 * (nblk + 1024)));
-        h->blkCap = nblk + 1024;
-    }
+    if (nblk > h->h_blk.cap / (2 * sizeof(unsigned))) MSL_HIP_TRY(h->h_blk.grow(sizeof(unsigned) * 2 * (nblk + 1024), s));
+    const size_t blkHalf = h->h_blk.cap / (2 * sizeof(unsigned));   // deleted counts | updated counts
+    const unsigned *blk = (const unsigned *)h->h_blk.p;
     if (nblk) {
-        MSL_HIP_TRY(hipMemcpyAsync(h->h_blk, h->dev.blockSums, sizeof(unsigned) * nblk, hipMemcpyDeviceToHost, s));
-        MSL_HIP_TRY(hipMemcpyAsync(h->h_blk + h->blkCap, h->dev.blockUpd, sizeof(unsigned) * nblk, hipMemcpyDeviceToHost, s));
+        MSL_HIP_TRY(hipMemcpyAsync(h->h_blk.p, h->dev.blockSums, sizeof(unsigned) * nblk, hipMemcpyDeviceToHost, s));
+        MSL_HIP_TRY(hipMemcpyAsync((unsigned *)h->h_blk.p + blkHalf, h->dev.blockUpd, sizeof(unsigned) * nblk, hipMemcpyDeviceToHost, s));
     }
     rc = read_ctr(h);   // the call's first synchronisation: counters and the per-sub-block counts are on the host
     if (rc != MSL_OK) return rc;
     rc = check_err(h);
     if (rc != MSL_OK) return rc;
-    const size_t K = (size_t)h->h_ctr[1];
+    const size_t K = (size_t)((const long long *)h->h_ctr.p)[1];
     *n_new = K;
     // what was touched, and where
     struct Run { size_t b0, b1; };
     std::vector<Run> runs;
     size_t touched = 0, runSurfels = 0;
-    for (size_t b = 0; b < nblk; b++) touched += (size_t)h->h_blk[b] + h->h_blk[h->blkCap + b];
+    for (size_t b = 0; b < nblk; b++) touched += (size_t)blk[b] + blk[blkHalf + b];
     for (size_t gapMax = 4; ; gapMax *= 4) {
         runs.clear();
         for (size_t b = 0; b < nblk; b++) {
-            if (!(h->h_blk[b] | h->h_blk[h->blkCap + b])) continue;
+            if (!(blk[b] | blk[blkHalf + b])) continue;
             if (!runs.empty() && b - runs.back().b1 <= gapMax) runs.back().b1 = b + 1;
             else runs.push_back({b, b + 1});
         }
@@ -983,22 +921,19 @@ int msl_sf_fuse_ex(msl_sf *h, int referenceFrameIndex, const uint8_t *gray, size
     // Two ways back.  Runs of touched sub-blocks copied straight into the caller's vector (~45 GB/s), or -- when few surfels in many sub-blocks
     // changed (a map in no particular order) -- a compact {index, record} list scattered by the CPU (~6 ns per record on top of its 60 bytes).
     const size_t listLimit = n_local / 8;
+    msl_surfel *aos = (msl_surfel *)h->d_aos.p;   // (>= n_local entries: msl_sf_map_upload, or the call before that one)
     const double costRuns = 56.0 * (double)runSurfels / 45e9, costList = (double)touched * (60.0 / 45e9 + 6e-9);
     if (touched && touched <= listLimit && costList < costRuns) {
         const size_t need = 256 + (sizeof(unsigned) + sizeof(msl_surfel)) * listLimit;
-        if (need > h->listCap) {
-            if (h->h_list) (void)hipHostFree(h->h_list);
-            h->h_list = nullptr; h->listCap = 0;
-            MSL_HIP_TRY(hipHostMalloc(&h->h_list, need));
-            h->listCap = need;
-        }
+        MSL_HIP_TRY(h->h_list.grow(need, s));
         // device side: the count sits in tickets[3], indices in delList, records in the AoS buffer (both >= n_local entries)
-        unsigned *d_count = h->d_tickets + 3;
+        unsigned *d_count = h->dev.tickets + 3;
         MSL_HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned), s));
-        map_launch_collect_changed(s, h->dev, (int)ref, (long long)n_local, d_count, h->dev.delList, h->d_aos, (unsigned)listLimit);
-        unsigned *hc = reinterpret_cast<unsigned *>(h->h_list);
-        unsigned *hi = reinterpret_cast<unsigned *>(h->h_list + 256);
-        msl_surfel *hr = reinterpret_cast<msl_surfel *>(h->h_list + 256 + sizeof(unsigned) * listLimit);
+        map_launch_collect_changed(s, h->dev, (int)ref, (long long)n_local, d_count, h->dev.delList, aos, (unsigned)listLimit);
+        uint8_t *list = (uint8_t *)h->h_list.p;
+        unsigned *hc = reinterpret_cast<unsigned *>(list);
+        unsigned *hi = reinterpret_cast<unsigned *>(list + 256);
+        msl_surfel *hr = reinterpret_cast<msl_surfel *>(list + 256 + sizeof(unsigned) * listLimit);
         MSL_HIP_TRY(hipMemcpyAsync(hc, d_count, sizeof(unsigned), hipMemcpyDeviceToHost, s));
         MSL_HIP_TRY(hipStreamSynchronize(s));
         // (the list may be longer than `touched`: a surfel that carried lastUpdate == ref before the call is listed as well -- harmless, its
@@ -1006,8 +941,8 @@ int msl_sf_fuse_ex(msl_sf *h, int referenceFrameIndex, const uint8_t *gray, size
         const size_t cnt = *hc;
         if (cnt <= listLimit) {
             MSL_HIP_TRY(hipMemcpyAsync(hi, h->dev.delList, sizeof(unsigned) * cnt, hipMemcpyDeviceToHost, s));
-            MSL_HIP_TRY(hipMemcpyAsync(hr, h->d_aos, sizeof(msl_surfel) * cnt, hipMemcpyDeviceToHost, s));
-            if (K) MSL_HIP_TRY(hipMemcpyAsync(new_out, h->d_new, sizeof(msl_surfel) * K, hipMemcpyDeviceToHost, s));
+            MSL_HIP_TRY(hipMemcpyAsync(hr, aos, sizeof(msl_surfel) * cnt, hipMemcpyDeviceToHost, s));
+            if (K) MSL_HIP_TRY(hipMemcpyAsync(new_out, h->dev.newSurfels, sizeof(msl_surfel) * K, hipMemcpyDeviceToHost, s));
             MSL_HIP_TRY(hipStreamSynchronize(s));
             for (size_t j = 0; j < cnt; j++) local[hi[j]] = hr[j];
             h->mirrorValid = true; h->mirrorN = n_local;
@@ -1015,12 +950,12 @@ int msl_sf_fuse_ex(msl_sf *h, int referenceFrameIndex, const uint8_t *gray, size
         }
     }
     if (nblk && !runs.empty())
-        map_launch_soa_to_aos(h->prof, s, h->dev, h->d_aos, (long long)n_local);
+        map_launch_soa_to_aos(h->prof, s, h->dev, aos, (long long)n_local);
     for (const Run &r : runs) {
         const size_t i0 = r.b0 * SUB_ITEMS, i1 = std::min(r.b1 * SUB_ITEMS, n_local);
-        MSL_HIP_TRY(hipMemcpyAsync(local + i0, h->d_aos + i0, sizeof(msl_surfel) * (i1 - i0), hipMemcpyDeviceToHost, s));
+        MSL_HIP_TRY(hipMemcpyAsync(local + i0, aos + i0, sizeof(msl_surfel) * (i1 - i0), hipMemcpyDeviceToHost, s));
     }
-    if (K) MSL_HIP_TRY(hipMemcpyAsync(new_out, h->d_new, sizeof(msl_surfel) * K, hipMemcpyDeviceToHost, s));
+    if (K) MSL_HIP_TRY(hipMemcpyAsync(new_out, h->dev.newSurfels, sizeof(msl_surfel) * K, hipMemcpyDeviceToHost, s));
     MSL_HIP_TRY(hipStreamSynchronize(s));
     h->mirrorValid = true; h->mirrorN = n_local;
     return MSL_OK;
@@ -1043,9 +978,9 @@ int msl_sf_debug_seeds(msl_sf *h, msl_seed *out) noexcept {
     int rc = sync_all(h);
     if (rc != MSL_OK) return rc;
     const size_t ns = h->dev.nseeds;
-    MSL_HIP_TRY(hipMemcpy(out, h->d_seeds + ns * h->lastSlot, sizeof(msl_seed) * ns, hipMemcpyDeviceToHost));
+    MSL_HIP_TRY(hipMemcpy(out, h->dev.seeds + ns * h->lastSlot, sizeof(msl_seed) * ns, hipMemcpyDeviceToHost));
     std::vector<uint8_t> fused(ns);
-    MSL_HIP_TRY(hipMemcpy(fused.data(), h->d_fused + (size_t)h->dev.flagStride * h->lastSlot, ns, hipMemcpyDeviceToHost));
+    MSL_HIP_TRY(hipMemcpy(fused.data(), h->dev.fused + (size_t)h->dev.flagStride * h->lastSlot, ns, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < ns; i++) out[i].fused = fused[i] & 1;   // (2 = invalid candidate, not a fusion)
     return MSL_OK;
     } MSL_ABI_CATCH_INT
@@ -1056,7 +991,7 @@ int msl_sf_debug_ctr(msl_sf *h, int64_t out[16]) noexcept {
     MSL_HIP_TRY(hipSetDevice(h->device));
     int rc = read_ctr(h);
     if (rc != MSL_OK) return rc;
-    for (int i = 0; i < 16; i++) out[i] = h->h_ctr[i];
+    for (int i = 0; i < 16; i++) out[i] = ((const long long *)h->h_ctr.p)[i];
     return MSL_OK;
     } MSL_ABI_CATCH_INT
 }
@@ -1073,11 +1008,11 @@ int msl_sf_debug_scratch(msl_sf *h, int which, size_t offset_words, uint32_t *ou
         out[0] = (uint32_t)h->dealG;
         return MSL_OK;
     }
-    if (offset_words + n_words > (which < 2 ? h->mapCap : h->blkStride)) return MSL_ERR_INVALID;
+    if (offset_words + n_words > (which < 2 ? h->dev.cap : h->blkStride)) return MSL_ERR_INVALID;
     MSL_HIP_TRY(hipSetDevice(h->device));
     int rc = sync_all(h);
     if (rc != MSL_OK) return rc;
-    const uint32_t *src = which == 0 ? h->d_srcOf : which == 1 ? h->d_delList : which == 2 ? h->dev.sbKeys : h->dev.deal;
+    const uint32_t *src = which == 0 ? h->dev.srcOf : which == 1 ? h->dev.delList : which == 2 ? h->dev.sbKeys : h->dev.deal;
     MSL_HIP_TRY(hipMemcpy(out, src + offset_words, sizeof(uint32_t) * n_words, hipMemcpyDeviceToHost));
     return MSL_OK;
     } MSL_ABI_CATCH_INT
@@ -1110,7 +1045,7 @@ int msl_sf_debug_index(msl_sf *h, int32_t *out) noexcept {
     if (rc != MSL_OK) return rc;
     const size_t npx = h->dev.npx;
     std::vector<unsigned short> tmp(npx);
-    MSL_HIP_TRY(hipMemcpy(tmp.data(), h->d_index + (size_t)h->dev.pxStride * h->lastSlot, sizeof(unsigned short) * npx, hipMemcpyDeviceToHost));
+    MSL_HIP_TRY(hipMemcpy(tmp.data(), h->dev.index + (size_t)h->dev.pxStride * h->lastSlot, sizeof(unsigned short) * npx, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < npx; i++) out[i] = tmp[i];
     return MSL_OK;
     } MSL_ABI_CATCH_INT

@@ -152,6 +152,29 @@ def test_quadtree_node_bound_over_geometries(oracle, w, h, nf, levels, scale):
     ex.close()
 
 
+
+def test_one_extractor_across_frame_sizes():
+    """Frame size A, then B, then A on ONE extractor: its geometry buffers are released and rebuilt at every change (the pinned staging of the
+    single-frame call and the frame epilogue's buffers stay), and every result -- the single-frame call and the batched frame epilogue -- is that of
+    a fresh extractor created for the size.  (The sizes share one aspect ratio: the keypoint capacity of the first fits the second.)"""
+    from manhattanslam_amd import ORBextractor, frame_params, synth
+    I = synth.TUM1
+    ex = ORBextractor(1000, 1.2, 8, 20, 7, max_width=640, max_height=480, max_batch=2)
+    for w, h in ((640, 480), (480, 360), (640, 480)):
+        imgs = synth.orb_frames(2, seed=700 + w, w=w, h=h)
+        depths = np.stack([synth.surfel_frame(k, w=w, h=h)[1] for k in range(2)])
+        params = frame_params(I["fx"], I["fy"], I["cx"], I["cy"], 40.0, w, h)
+        fresh = ORBextractor(1000, 1.2, 8, 20, 7, max_width=w, max_height=h, max_batch=2)
+        kg, dg = ex(imgs[0])
+        kf, df = fresh(imgs[0])
+        assert len(kg) > 100
+        _assert_same(kg, dg, kf, df)
+        for got, want in zip(ex.extract_frames(imgs, depths, params), fresh.extract_frames(imgs, depths, params)):
+            _assert_same(got[0], got[1], want[0], want[1])
+            assert all(x.tobytes() == y.tobytes() for x, y in zip(got[2:], want[2:]))
+        fresh.close()
+    ex.close()
+
 def test_device_resident_batch(oracle):
     """Asynchronous batch path with inputs and outputs resident in HBM (the bench.py path)."""
     import torch

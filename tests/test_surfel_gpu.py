@@ -348,6 +348,63 @@ def test_raw_depth16_batches_match_the_float_path(oracle):
         assert np.array_equal(idx[k], idx[0]), k
 
 
+
+def test_one_handle_releases_and_regrows_its_staging(oracle):
+    """ONE handle through every call that releases or regrows its staged images or its slot set: host-image batches (float and raw 16-bit depth),
+    a device-memory raw-depth batch, a host batch with wider gray rows, the batch capacity lowered (a device batch at that size) and raised again,
+    one more host batch.  Map and seeds are byte-identical to a second handle fed the same keyframes, partition and capacity changes as float host
+    images only, the map is the sequential oracle's, and msl_sf_staged_gray refuses after the device batch and after a capacity change."""
+    import torch
+    from manhattanslam_amd import lib, synth, SURFEL_DTYPE
+    from manhattanslam_amd._lib import MslError, check, ptr
+    from manhattanslam_amd.surfel import _pose16
+    W, H, n = 640, 480, 11
+    a = np.float32(1.0) / np.float32(5000.0)
+    frames = [synth.clutter_frame(3 * j) for j in range(n)]
+    raw = np.stack([synth.depth_u16(f[1]) for f in frames]); d32 = raw.astype(np.float32) * a
+    grays = np.stack([f[0] for f in frames]); member = np.stack([f[2] for f in frames]); poses = [f[3] for f in frames]
+    wide = np.full((n, H, W + 32), 17, np.uint8); wide[:, :, :W] = grays   # gray rows W + 32 bytes apart: larger than the slots staged so far
+    m = synth.surfel_map_dense(120000, ref=0, scene=synth.clutter_scene(), k_lo=-40, k_hi=60, min_update_times=1).astype(SURFEL_DTYPE)
+    # (first, last keyframe + 1, kind) with the batch capacity changes in between; the reference handle gets every batch as float host images
+    plan = [(0, 2, "f32"), (2, 4, "raw"), (4, 6, "device"), (6, 8, "wide"), 1, (8, 9, "device"), 2, (9, 11, "raw")]
+    maps, seeds = [], []
+    for reference in (False, True):
+        g, o = _mk(synth.TUM1)
+        g.set_batch_capacity(2); g.map_reserve(300000); g.map_upload(m)
+        for step in plan:
+            if isinstance(step, int):
+                g.set_batch_capacity(step)
+                with pytest.raises(MslError):
+                    g.staged_gray()
+                continue
+            j0, j1, kind = step
+            sl, refs = slice(j0, j1), list(range(j0, j1))
+            if kind == "wide":
+                pz = np.ascontiguousarray(np.stack([_pose16(p) for p in poses[sl]]), np.float32)
+                gb, db, mb, rb = (np.ascontiguousarray(x[sl]) for x in (wide, d32, member, np.array(refs, np.int32)))
+                check(lib.msl_sf_fuse_resident_batch(g._h, len(refs), ptr(rb), ptr(gb), W + 32, (W + 32) * H, ptr(db), 4 * W, 4 * W * H, ptr(mb),
+                                                     4 * (W // 2), 4 * (W // 2) * (H // 2), 0, ptr(pz)), "wide gray rows")
+                assert g.staged_gray()[1] == W + 32
+            elif reference or kind == "f32":
+                g.fuse_resident_batch(refs, grays[sl], d32[sl], member[sl], poses[sl])
+            elif kind == "raw":
+                g.fuse_resident_batch(refs, grays[sl], raw[sl], member[sl], poses[sl], depth_factor=float(a))
+            else:
+                tg, tr, tm = (torch.from_numpy(np.ascontiguousarray(x[sl])).cuda() for x in (grays, raw.view(np.int16), member))
+                g.fuse_resident_batch(refs, tg, tr, tm, poses[sl], device=True, depth_factor=float(a))
+                with pytest.raises(MslError):
+                    g.staged_gray()
+                g.sync()
+        maps.append(g.map_download()); seeds.append(g.debug_seeds())
+        if reference:
+            o.map_set(m)
+            for j in range(n):   # (the oracle gets the wide rows where the handles did: the colour lookup depends on the row stride)
+                o.fuse_map(j, wide[j, :, :W] if 6 <= j < 8 else grays[j], d32[j], member[j], poses[j])
+            assert_surfels_close(maps[1], o.map_get(), "float host batches against the oracle")
+        g.close()
+    assert maps[0].tobytes() == maps[1].tobytes()
+    assert seeds[0].tobytes() == seeds[1].tobytes()
+
 def test_rotating_chain_is_the_left_to_right_float_sum():
     """kb_update_seeds evaluates the reference's sequential float sums (depth mean and Huber / Newton numerator, src/SurfelFusion.cpp:486-503) as a
     chain that rotates over 16 lanes (round 5).  On adversarial lists -- every length 0..256, values spread over 20 binades with heavy cancellation,
