@@ -343,6 +343,7 @@ MSL_API int msl_peac_extract_from_blocks(const msl_peac_block *blocks, const uin
  *   last_xyz[3 i..]  LastFrame.mvpMapPoints[i]->GetWorldPos()          last_desc[32 i..]  ->GetDescriptor()
  *   last_flags[i]    bit 0: mvpMapPoints[i] != NULL && !mvbOutlier[i]; bit 1: ->Observations() > 0
  *   last_octave[i]   LastFrame.mvKeys[i].octave                        last_angle[i]      LastFrame.mvKeysUn[i].angle
+ *                    (a last_octave outside [0, nlevels) finds no candidates: that point matches nothing)
  * Tcw_cur / Tcw_last: rows 0-2 of the CV_32F 4x4 mTcw of the two frames, row-major (12 floats per pair).
  * CurrentFrame.mvpMapPoints is all NULL on entry (src/Tracking.cc:1252); on return match_out[f * cap + i2] is the index i of the
  * last-frame keypoint whose MapPoint current keypoint i2 holds, or -1 (NULL); nmatches[f] is the function's return value.

@@ -156,6 +156,8 @@ MSLO_API int mslo_search_by_projection(const msl_match_params *P, int n_cur, con
         if (!(u >= CurrentFrame.mnMinX && u <= CurrentFrame.mnMaxX)) continue;   // (NaN: see header)
         if (!(v >= CurrentFrame.mnMinY && v <= CurrentFrame.mnMaxY)) continue;
         int nLastOctave = last_octave[i];
+        // msl.h: an octave outside [0, nlevels) finds no candidates.  The reference would read mvScaleFactors[nLastOctave] out of bounds.
+        if (nLastOctave < 0 || nLastOctave >= P->nlevels) continue;
         float radius = th * CurrentFrame.mvScaleFactors[nLastOctave];
         std::vector<size_t> vIndices2;
         if (bForward) vIndices2 = CurrentFrame.GetFeaturesInArea(u, v, radius, nLastOctave, -1);

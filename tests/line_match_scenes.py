@@ -1,5 +1,5 @@
 """Seeded synthetic inputs for the map-line matching tests (LSDmatcher::SearchByProjection, both overloads): 3-D lines projected to keylines
-with pixel noise, LBD-sized (32-byte) descriptors at controlled Hamming distances, octaves 0-3, near-vertical lines (x1 == x2), lines behind
+with pixel noise, LBD-sized (32-byte) descriptors at controlled Hamming distances, octaves 0-3 (0 .. octaves - 1), near-vertical lines (x1 == x2), lines behind
 the camera, lines at the ends of their distance window (predicted level -1, nlevels, nlevels + 1), many lines on a few keylines, pre-held
 keylines with and without observations, and same-level / different-level ties.  Per-frame dicts as manhattanslam_amd.match.pack_lines_last /
 pack_local_lines take them."""
@@ -13,9 +13,9 @@ from tests import local_match_scenes as ls
 F32 = np.float32
 
 
-def params(th=15.0, view_cos_limit=0.6, nn_ratio=0.6):
-    """msl_line_match_params for the TUM-like camera of the point tests (8 levels of 1.2, 640 x 480)."""
-    return ls.params(th, view_cos_limit=view_cos_limit, nn_ratio=nn_ratio)
+def params(th=15.0, view_cos_limit=0.6, nn_ratio=0.6, nlevels=8, scale=1.2):
+    """msl_line_match_params for the TUM-like camera of the point tests (640 x 480; by default 8 levels of 1.2)."""
+    return ls.params(th, view_cos_limit=view_cos_limit, nn_ratio=nn_ratio, nlevels=nlevels, scale=scale)
 
 
 def desc_flip(rng, d, nbits):
@@ -62,12 +62,14 @@ def _project(p, T, xyz6):
     return None if res is None else np.array([float(x) for x in res[:4]])
 
 
-def frame_pair(seed, p, n_kl=40, n_last=40, obs_frac=0.7, flag_frac=0.9, vertical=0, behind=0.05, fwd=0.0, octaves=4, noise=1.0,
+def frame_pair(seed, p, n_kl=40, n_last=40, obs_frac=0.7, flag_frac=0.9, vertical=0, behind=0.05, fwd=0.0, octaves=None, noise=1.0,
                angle_mode="mixed", few=0, T=None):
     """A current frame of n_kl keylines and a last frame of n_last map lines.  Most last-frame lines project (through the current pose) next
     to a keyline whose descriptor is a noisy copy of theirs.  vertical: that many lines with x1 == x2 exactly (identity pose);
-    fwd: camera motion along z (positive: forward, negative: backward search mode); few: every line near one of `few` keylines."""
+    fwd: camera motion along z (positive: forward, negative: backward search mode); few: every line near one of `few` keylines;
+    octaves: keyline and last-line octaves are drawn from [0, octaves), by default min(4, nlevels)."""
     rng = np.random.Generator(np.random.PCG64(seed))
+    octaves = octaves or min(4, int(lmm._p(p)["nlevels"]))
     T = (np.eye(4, dtype=np.float32) if vertical else pose(rng)) if T is None else np.asarray(T, np.float32)
     Tl = T.copy()
     Tl[2, 3] += F32(fwd)
@@ -128,16 +130,17 @@ def _window_end(p, T, xyz6, level, nlevels):
             if not (dist > F32(1.2) * dmax) and lmm.predict_level(dmax, dist, ls_) == -1:
                 return F32(0.0), dmax
         return None
-    dmax = F32(float(dist) * 1.2 ** (level - 0.5))
+    dmax = F32(float(dist) * ls.ms.level_scale(p) ** (level - 0.5))
     return (F32(0.0), dmax) if lmm.predict_level(dmax, dist, ls_) == level else None
 
 
-def local_frame(seed, p, n_kl=40, n_local=2000, preheld=0.3, few=0, ends=True, octaves=4, noise=1.0, T=None):
+def local_frame(seed, p, n_kl=40, n_local=2000, preheld=0.3, few=0, ends=True, octaves=None, noise=1.0, T=None):
     """A current frame of n_kl keylines and n_local local map lines under a random pose.  Most lines project near a keyline (a noisy copy of
     its descriptor); some are unrelated, behind the camera, outside their distance window, seen too obliquely or exactly head-on (viewCos
     > 0.998 for the 5-pixel radius); with ends, some sit at the distance-window ends (levels -1, nlevels, nlevels + 1).  few: all lines
     around `few` keylines (a deep fixpoint)."""
     rng = np.random.Generator(np.random.PCG64(seed))
+    octaves = octaves or min(4, int(lmm._p(p)["nlevels"]))
     T = pose(rng) if T is None else np.asarray(T, np.float32)
     m = max(n_local, 1)
     A, B = _lines_in_camera(rng, m)
@@ -157,15 +160,16 @@ def local_frame(seed, p, n_kl=40, n_local=2000, preheld=0.3, few=0, ends=True, o
     tilt = np.radians(np.where(rng.random(m) < 0.25, 0.0, rng.uniform(0, 60, m)))   # 0: viewCos ~ 1 (> 0.998)
     perp = np.cross(dirn, rng.normal(size=(m, 3))); perp /= np.linalg.norm(perp, axis=1, keepdims=True)
     normal = dirn * np.cos(tilt)[:, None] + perp * np.sin(tilt)[:, None]
+    nlevels, scale = int(lmm._p(p)["nlevels"]), ls.ms.level_scale(p)
     lvl = rng.integers(0, octaves, m) + rng.integers(0, 2, m)
-    dmax = dist * 1.2 ** (lvl - rng.uniform(0.05, 0.95, m))
-    dmin = dmax / 1.2 ** 7
+    dmax = dist * scale ** (lvl - rng.uniform(0.05, 0.95, m))
+    dmin = dmax / scale ** (nlevels - 1)
     out = (kind >= 0.05) & (kind < 0.07)
     dmax[out] = dist[out] / 1.3
     dd = np.stack([dmin, dmax], 1).astype(F32)
     if ends:
-        for j, level in zip(range(0, min(m, 60), 1), [-1, 8, 9] * 20):
-            w = _window_end(p, Tm, xyz[j], level, 8)
+        for j, level in zip(range(0, min(m, 60), 1), [-1, nlevels, nlevels + 1] * 20):
+            w = _window_end(p, Tm, xyz[j], level, nlevels)
             if w is not None:
                 dd[j] = w
     # keylines

@@ -10,10 +10,10 @@ KEYPOINT_DTYPE = ms.KEYPOINT_DTYPE
 LOG_SCALE = np.float32(math.log(1.2))          # Frame::mfLogScaleFactor = log(mfScaleFactor), a float
 
 
-def params(th=3.0, w=640, h=480, fx=517.3, fy=516.5, cx=318.6, cy=255.3, bf=40.0, view_cos_limit=0.5, nn_ratio=0.8):
+def params(th=3.0, w=640, h=480, fx=517.3, fy=516.5, cx=318.6, cy=255.3, bf=40.0, view_cos_limit=0.5, nn_ratio=0.8, nlevels=8, scale=1.2):
     from manhattanslam_amd import LOCAL_MATCH_PARAMS_DTYPE
-    p = ms.params(None, th, False, w=w, h=h, fx=fx, fy=fy, cx=cx, cy=cy, bf=bf, dtype=LOCAL_MATCH_PARAMS_DTYPE)
-    p["log_scale_factor"], p["view_cos_limit"], p["nn_ratio"] = LOG_SCALE, view_cos_limit, nn_ratio
+    p = ms.params(None, th, False, w=w, h=h, fx=fx, fy=fy, cx=cx, cy=cy, bf=bf, dtype=LOCAL_MATCH_PARAMS_DTYPE, nlevels=nlevels, scale=scale)
+    p["log_scale_factor"], p["view_cos_limit"], p["nn_ratio"] = np.float32(math.log(scale)), view_cos_limit, nn_ratio
     return p
 
 
@@ -64,6 +64,7 @@ def random_frame(seed, p, n_cur=1000, n_local=4000, preheld=0.3, cluster=False, 
     rng = np.random.Generator(np.random.PCG64(seed))
     fx, fy, cx, cy, bf = (float(p[k][0]) for k in ("fx", "fy", "cx", "cy", "bf"))
     W, H = float(p["maxX"][0]), float(p["maxY"][0])
+    nlevels, scale = int(p["nlevels"][0]), ms.level_scale(p)
     R = rotation(rng, 8.0)
     t = rng.normal(0, 0.3, 3)
     T = np.eye(4, dtype=np.float32)
@@ -78,7 +79,7 @@ def random_frame(seed, p, n_cur=1000, n_local=4000, preheld=0.3, cluster=False, 
     depth = rng.uniform(0.8, 6.0, n_cur)
     kps = np.zeros(n_cur, KEYPOINT_DTYPE)
     kps["x"], kps["y"] = xy[:, 0], xy[:, 1]
-    kps["octave"] = rng.integers(0, 8, n_cur)
+    kps["octave"] = rng.integers(0, nlevels, n_cur)
     kps["class_id"] = -1
     desc = rng.integers(0, 256, (n_cur, 32), dtype=np.uint8)
     if conflict:   # a handful of distinct descriptors: every point's best is one of few keypoints
@@ -106,10 +107,11 @@ def random_frame(seed, p, n_cur=1000, n_local=4000, preheld=0.3, cluster=False, 
     perp = np.cross(dirn, rng.normal(size=(n_local, 3)))
     perp /= np.linalg.norm(perp, axis=1, keepdims=True)
     normal = dirn * np.cos(tilt)[:, None] + perp * np.sin(tilt)[:, None]
-    # distance range: a level near the keypoint's octave: mfMaxDistance = dist * 1.2^level (+ jitter), mfMinDistance = mfMaxDistance / 1.2^7
-    lvl = np.clip(kps["octave"][src] + rng.integers(0, 2, n_local), 0, 7) if n_cur else rng.integers(0, 8, n_local)
-    dmax = dist * 1.2 ** (lvl - rng.uniform(0.05, 0.95, n_local))
-    dmin = dmax / 1.2 ** 7
+    # distance range: a level near the keypoint's octave: mfMaxDistance = dist * scale^level (+ jitter),
+    # mfMinDistance = mfMaxDistance / scale^(nlevels - 1)
+    lvl = np.clip(kps["octave"][src] + rng.integers(0, 2, n_local), 0, nlevels - 1) if n_cur else rng.integers(0, nlevels, n_local)
+    dmax = dist * scale ** (lvl - rng.uniform(0.05, 0.95, n_local))
+    dmin = dmax / scale ** (nlevels - 1)
     out_range = (kind >= 0.04) & (kind < 0.06)
     dmax[out_range] = dist[out_range] / 1.3                               # beyond 1.2 * mfMaxDistance
     mdesc = desc[src].copy() if n_cur else rng.integers(0, 256, (n_local, 32), dtype=np.uint8)

@@ -4,16 +4,35 @@ import numpy as np
 KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
                            ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
 SCALE = np.cumprod(np.concatenate([[1.0], np.full(7, 1.2)]).astype(np.float32)).astype(np.float32)
+MAX_LEVELS = 16                                   # MSL_MATCH_MAX_LEVELS
 
 
-def params(oracle_lib_or_none, th, check_orientation=True, w=640, h=480, fx=517.3, fy=516.5, cx=318.6, cy=255.3, bf=40.0, dtype=None):
+def orb_tables(nlevels=8, scale=1.2):
+    """(mvScaleFactors, mvInvLevelSigma2) as msl_orb_scale_tables returns them for ORBextractor(.., scale, nlevels, ..): the float factor
+    chain scale[i] = float(scale[i-1] * (double)scaleFactor) with scaleFactor the float argument, sigma2 = scale * scale, 1 / sigma2."""
+    sf = np.ones(nlevels, np.float32)
+    for i in range(1, nlevels):
+        sf[i] = np.float32(np.float64(sf[i - 1]) * np.float64(np.float32(scale)))
+    return sf, (np.float32(1) / (sf * sf)).astype(np.float32)
+
+
+def level_scale(p):
+    """The pyramid's scale factor as the scene generators use it (a Python float: 1.2 for the default tables), from a params record."""
+    return round(float(p["scale_factors"][0][1]), 6) if int(p["nlevels"][0]) > 1 else 1.2
+
+
+def params(oracle_lib_or_none, th, check_orientation=True, w=640, h=480, fx=517.3, fy=516.5, cx=318.6, cy=255.3, bf=40.0, dtype=None,
+           nlevels=8, scale=1.2):
+    """msl_match_params (or the record of `dtype` that starts with its fields) for a w x h TUM-like camera and an nlevels pyramid of
+    `scale`; scale_factors[nlevels:] stay zero."""
+    assert 1 <= nlevels <= MAX_LEVELS
     p = np.zeros(1, dtype)
     p["fx"], p["fy"], p["cx"], p["cy"], p["bf"] = fx, fy, cx, cy, bf
     p["minX"], p["maxX"], p["minY"], p["maxY"] = 0.0, float(w), 0.0, float(h)     # ComputeImageBounds without distortion
     p["th"] = th
     p["check_orientation"] = 1 if check_orientation else 0
-    p["nlevels"] = 8
-    p["scale_factors"][0, :8] = SCALE
+    p["nlevels"] = nlevels
+    p["scale_factors"][0, :nlevels] = orb_tables(nlevels, scale)[0]
     return p
 
 
@@ -32,6 +51,7 @@ def random_pair(seed, p, n_cur=900, n_last=850, shift=(6.0, -4.0), tz=0.0, z=2.0
     rng = np.random.Generator(np.random.PCG64(seed))
     fx, fy, cx, cy = (float(p[k][0]) for k in ("fx", "fy", "cx", "cy"))
     W, H = float(p["maxX"][0]), float(p["maxY"][0])
+    nlevels = int(p["nlevels"][0])
     kps = np.zeros(n_cur, KEYPOINT_DTYPE)
     if cluster:   # everything inside a small region: dozens of candidates per window
         xy = np.stack([rng.uniform(200, 330, n_cur), rng.uniform(150, 250, n_cur)], 1)
@@ -39,7 +59,7 @@ def random_pair(seed, p, n_cur=900, n_last=850, shift=(6.0, -4.0), tz=0.0, z=2.0
         xy = np.stack([rng.uniform(16, W - 16, n_cur), rng.uniform(16, H - 16, n_cur)], 1)
     xy = np.round(xy).astype(np.float32)   # level-0-like integer coordinates (several keypoints may share a pixel: ties)
     kps["x"], kps["y"] = xy[:, 0], xy[:, 1]
-    kps["octave"] = rng.integers(0, 8, n_cur)
+    kps["octave"] = rng.integers(0, nlevels, n_cur)
     kps["angle"] = rng.uniform(0, 360, n_cur).astype(np.float32)
     kps["class_id"] = -1
     desc = rng.integers(0, 256, (n_cur, 32), dtype=np.uint8)
@@ -59,7 +79,7 @@ def random_pair(seed, p, n_cur=900, n_last=850, shift=(6.0, -4.0), tz=0.0, z=2.0
     for k in range(desc_noise):
         ld[np.arange(n_last), flip[:, k] // 8] ^= (1 << (flip[:, k] % 8)).astype(np.uint8)
     ld[unrelated] = rng.integers(0, 256, (int(unrelated.sum()), 32), dtype=np.uint8)
-    octave = np.clip(kps["octave"][src] + rng.integers(-1, 2, n_last), 0, 7).astype(np.int32)
+    octave = np.clip(kps["octave"][src] + rng.integers(-1, 2, n_last), 0, nlevels - 1).astype(np.int32)
     angle = (kps["angle"][src] + np.where(rng.random(n_last) < 0.8, rng.normal(3.0, 2.0, n_last), rng.uniform(0, 360, n_last))) % 360
     flags = ((rng.random(n_last) < 0.92).astype(np.uint8)) | ((rng.random(n_last) < obs_frac).astype(np.uint8) << 1)
     xyz[rng.random(n_last) < 0.01, 2] *= -1          # a few points behind the camera (invzc < 0)

@@ -502,19 +502,31 @@ def optimize(edges, T, c, iterations=10):
     return T
 
 
-def build_edges(fr, c):
+def point_ref(fr, c, i, xcap=None):
+    """The map point keypoint i refers to and the weight of its octave, as msl.h states them: (row of xyz, mvInvLevelSigma2 entry) or None.
+    pt_ref values outside [0, xcap) (xcap: the ABI's row count per frame, default len(xyz)) count as NULL; the octave is clamped to
+    [0, nlevels), nlevels = len(c["inv_level_sigma2"])."""
+    r = int(fr["pt_ref"][i])
+    if r < 0 or r >= (len(fr["xyz"]) if xcap is None else xcap):
+        return None
+    inv = c["inv_level_sigma2"]
+    return r, float(inv[min(max(int(fr["octave"][i]), 0), len(inv) - 1)])
+
+
+def build_edges(fr, c, xcap=None):
     """Optimizer.cc:74-377 in insertion order: points by keypoint index (mono when mvuRight < 0, else stereo), then per line its
-    start-point and end-point edges, then planes, parallel planes, vertical planes.  Returns (edges, per-kind edge lists, nInitial)."""
+    start-point and end-point edges, then planes, parallel planes, vertical planes.  Point references as point_ref reads them.
+    Returns (edges, nInitial)."""
     T0 = to_se3(fr["Tcw"])
     edges = []
     n0 = 0
     for i in range(len(fr["pt_ref"])):
-        r = int(fr["pt_ref"][i])
-        if r < 0:
+        ref = point_ref(fr, c, i, xcap)
+        if ref is None:
             continue
+        r, inv = ref
         n0 += 1
         X = tuple(float(v) for v in fr["xyz"][r])
-        inv = float(c["inv_level_sigma2"][int(fr["octave"][i])])
         u, v = float(fr["un_xy"][i][0]), float(fr["un_xy"][i][1])
         if fr["uright"][i] < 0:
             edges.append(Edge(MONO, i, (u, v), X, (inv, inv), DELTA_MONO))
@@ -550,13 +562,14 @@ def build_edges(fr, c):
 OUT_KEYS = {MONO: "outlier", STEREO: "outlier", LINE: "line_outlier", PLANE: "plane_outlier", PAR: "par_outlier", VER: "ver_outlier"}
 
 
-def pose_optimization(fr, c, rows=None):
+def pose_optimization(fr, c, rows=None, xcap=None):
     """int Optimizer::PoseOptimization(Frame*) for one frame.  c: fx, fy, cx, cy, bf (float values as double), inv_level_sigma2 (floats),
     angleInfo, disInfo, parInfo, verInfo, planeChi, planeChiVP, aTh, parTh.  Returns (n_good, Tcw_out (12,) f32, outlier arrays dict).
     rows (a list, optional) receives every comparison of the last classification as (kind, index, chi2 as compared, threshold): flag
-    equality between two summation orders is only well defined away from the thresholds, which the scene generator checks."""
+    equality between two summation orders is only well defined away from the thresholds, which the scene generator checks.
+    xcap: the rows of xyz a pt_ref may name (build_edges); default len(xyz)."""
     out = {k: np.array(fr[k], np.uint8, copy=True) for k in set(OUT_KEYS.values())}
-    edges, n0 = build_edges(fr, c)
+    edges, n0 = build_edges(fr, c, xcap)
     for e in edges:                                                       # mvbOutlier[i] = false for every edge created
         out[OUT_KEYS[e.kind]][e.idx] = 0
     if n0 < 3:

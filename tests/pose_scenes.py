@@ -11,10 +11,15 @@ FX, FY, CX, CY, BF = 517.3, 516.5, 318.6, 255.3, 40.0
 NLEVELS, SCALE = 8, 1.2
 
 
-def params(angleInfo=0.5, disInfo=50.0, parInfo=0.5, verInfo=0.5, planeChi=100.0, planeChiVP=50.0, aTh=0.86, parTh=0.9):
-    """Model constants c (see pose_model.pose_optimization); the msl_pose_params record is manhattanslam_amd.pose.pose_params(c)."""
+def params(angleInfo=0.5, disInfo=50.0, parInfo=0.5, verInfo=0.5, planeChi=100.0, planeChiVP=50.0, aTh=0.86, parTh=0.9, nlevels=NLEVELS,
+           scale=SCALE, inv_level_sigma2=None):
+    """Model constants c (see pose_model.pose_optimization); the msl_pose_params record is manhattanslam_amd.pose.pose_params(c).
+    inv_level_sigma2 (mvInvLevelSigma2, nlevels floats): by default 1 / scale^(2 l) rounded from double; pass match_scenes.orb_tables(..)[1]
+    for the table msl_orb_scale_tables gives."""
     f = lambda x: float(np.float32(x))
-    inv = np.array([1.0 / (SCALE ** (2 * l)) for l in range(NLEVELS)], np.float32)   # mvInvLevelSigma2
+    inv = np.array([1.0 / (scale ** (2 * l)) for l in range(nlevels)], np.float32) if inv_level_sigma2 is None else \
+        np.asarray(inv_level_sigma2, np.float32)
+    assert 1 <= len(inv) <= 16
     return dict(fx=f(FX), fy=f(FY), cx=f(CX), cy=f(CY), bf=f(BF), inv_level_sigma2=[float(v) for v in inv], angleInfo=angleInfo,
                 disInfo=disInfo, parInfo=parInfo, verInfo=verInfo, planeChi=planeChi, planeChiVP=planeChiVP, aTh=aTh, parTh=parTh)
 
@@ -42,10 +47,13 @@ def empty(n=0, nl=0, m=0, x=0):
 
 
 def scene(seed, n_pts=300, n_lines=10, n_planes=3, stereo=0.6, noise=0.5, outliers=0.0, line_outliers=0.0, rot_deg=2.0, trans=0.05,
-          null_frac=0.1, par=True, ver=True, margin=1e-4, c=None):
+          null_frac=0.1, par=True, ver=True, margin=1e-4, c=None, nlevels=NLEVELS, scale=SCALE, xcap=None):
     """One frame.  Returns (fr, Rtrue, ttrue).  noise: pixel sigma of the point / line observations (0 = noiseless); outliers: fraction of
-    points whose observation is replaced by a random pixel; null_frac: keypoints without a MapPoint.  When margin is set, asserts that
-    every edge's final chi2 in the model lies more than margin (relative) away from its threshold."""
+    points whose observation is replaced by a random pixel; null_frac: keypoints without a MapPoint; octaves are drawn from [0, nlevels) and
+    scale the noise by scale^octave.  xcap: xyz gets xcap rows instead of n_pts, the referenced points scattered over them (slot xcap - 1
+    always referenced) with unrelated filler rows in between.  When margin is set, asserts that every edge's final chi2 in the model lies
+    more than margin (relative) away from its threshold."""
+    c = c or params(nlevels=nlevels, scale=scale)
     rng = np.random.default_rng(seed)
     R = rot(rng.normal(size=3), rng.uniform(0, 40))
     t = rng.normal(size=3)
@@ -58,8 +66,8 @@ def scene(seed, n_pts=300, n_lines=10, n_planes=3, stereo=0.6, noise=0.5, outlie
     pw = (pc - t) @ R
     fr["xyz"][:] = pw.astype(np.float32)
     pcf = (fr["xyz"].astype(np.float64) @ R.T) + t
-    fr["octave"][:] = rng.integers(0, NLEVELS, n_pts)
-    sig = np.array([SCALE ** l for l in range(NLEVELS)])[fr["octave"]]
+    fr["octave"][:] = rng.integers(0, nlevels, n_pts)
+    sig = np.array([scale ** l for l in range(nlevels)])[fr["octave"]]
     u = pcf[:, 0] / pcf[:, 2] * FX + CX + rng.normal(size=n_pts) * noise * sig
     v = pcf[:, 1] / pcf[:, 2] * FY + CY + rng.normal(size=n_pts) * noise * sig
     ur = u - BF / pcf[:, 2] + rng.normal(size=n_pts) * noise * sig
@@ -111,9 +119,27 @@ def scene(seed, n_pts=300, n_lines=10, n_planes=3, stereo=0.6, noise=0.5, outlie
     R0 = rot(rng.normal(size=3), rot_deg) @ R
     t0 = t + rng.normal(size=3) / math.sqrt(3) * trans
     fr["Tcw"][:] = tcw12(R0, t0)
+    if xcap is not None:
+        scatter(fr, xcap, seed)
     if margin is not None:
-        check_margin(fr, c or params(), margin)
+        check_margin(fr, c, margin)
     return fr, R, t
+
+
+def scatter(fr, xcap, seed):
+    """Moves fr's xyz rows to distinct slots of an xcap-row xyz (the last keypoint's point to slot xcap - 1) and rewrites pt_ref; the other
+    rows are filler points nobody references.  Draws from its own generator, so the rest of the scene is unchanged."""
+    n = len(fr["xyz"])
+    assert n < xcap
+    rng = np.random.default_rng(seed + 104729)
+    slot = rng.choice(xcap - 1, n, replace=False)
+    ok = fr["pt_ref"] >= 0
+    if ok.any():
+        slot[fr["pt_ref"][ok][-1]] = xcap - 1
+    xyz = rng.normal(0, 3, (xcap, 3)).astype(np.float32)
+    xyz[slot] = fr["xyz"]
+    fr["pt_ref"][ok] = slot[fr["pt_ref"][ok]]
+    fr["xyz"] = xyz
 
 
 def check_margin(fr, c, margin=1e-4):

@@ -55,6 +55,8 @@ def brute_force(p, cur, last, Tc, Tl):
         if not (u >= minX and u <= maxX and v >= minY and v <= maxY):
             continue
         o = int(last["octave"][i])
+        if not 0 <= o < int(p["nlevels"][0]):        # msl.h: an octave outside [0, nlevels) finds no candidates
+            continue
         r = th * sf[o]
         lo, hi = (o, -1) if fwd else ((0, o) if bwd else (o - 1, o + 1))
         x0 = max(0, int(math.floor((u - minX - r) * wInv))); x1 = min(63, int(math.ceil((u - minX + r) * wInv)))
@@ -117,6 +119,28 @@ def test_oracle_matches_brute_force_model(oracle):
         mb, nb = brute_force(p, cur, last, Tc, Tl)
         assert no == nb and np.array_equal(mo, mb), (seed, no, nb)
         assert no > 30
+
+
+def test_last_octave_outside_the_pyramid_finds_no_candidates(oracle):
+    """msl.h: a last_octave outside [0, nlevels) finds no candidates (the reference would index mvScaleFactors out of bounds).  Octaves -1,
+    nlevels, 16, 1000 and INT_MIN give exactly the result of clearing those points' bit 0 (no candidate search at all), at 8, 16 and 1 levels;
+    12 levels of 1.1; the brute-force model agrees."""
+    for nlevels, scale, tz in ((8, 1.2, 0.0), (16, 1.2, 0.3), (1, 1.2, -0.3), (12, 1.1, 0.0)):
+        p = ms.params(None, 15, True, dtype=oracle_lib.MATCH_PARAMS_DTYPE, nlevels=nlevels, scale=scale)
+        cur, last, Tc, Tl = ms.random_pair(40 + nlevels, p, n_cur=400, n_last=380, tz=tz)
+        m0, n0 = oracle_lib.search_by_projection(p, cur, last, Tc, Tl)
+        held = np.flatnonzero(m0 >= 0)
+        bad = np.unique(m0[held][::3])[:5]                    # points that do match with their own octave
+        skip = dict(last, flags=last["flags"].copy())
+        skip["flags"][bad] &= 0xFE
+        out = dict(last, octave=last["octave"].copy())
+        out["octave"][bad] = [-1, nlevels, 16, 1000, -2 ** 31][:len(bad)]
+        want, nw = oracle_lib.search_by_projection(p, cur, skip, Tc, Tl)
+        got, ng = oracle_lib.search_by_projection(p, cur, out, Tc, Tl)
+        assert len(bad) == 5 and ng == nw and np.array_equal(got, want), nlevels
+        assert not np.isin(got, bad).any() and not np.array_equal(got, m0)
+        mb, nb = brute_force(p, cur, out, Tc, Tl)
+        assert nb == ng and np.array_equal(mb, got)
 
 
 def test_greedy_blocking_and_overwrite_known_answer(oracle):

@@ -138,3 +138,48 @@ def test_stale_chi2_of_a_rejected_last_trial():
     # the model classifies with the stale values: flipping to fresh errors changes at least one chi2
     assert any(pm.chi2(type("E", (), {"err": s, "info": e.info})) != pm.chi2(type("E", (), {"err": f, "info": e.info}))
                for s, f, e in zip(stale, fresh, edges))
+
+
+def _same_result(a, b):
+    assert a[0] == b[0] and np.array_equal(a[1], b[1]), (a[0], b[0])
+    for k in a[2]:
+        assert np.array_equal(a[2][k], b[2][k]), k
+
+
+def test_out_of_range_octaves_are_clamped():
+    """msl.h: octaves outside [0, nlevels) are clamped.  Octave -1 weighs like octave 0 and octave 99 like nlevels - 1, for every outcome
+    (pose, n_good and flags), on an 8-level and a 3-level table."""
+    for nlevels in (8, 3):
+        c = ps.params(nlevels=nlevels)
+        fr, _, _ = ps.scene(31, n_pts=120, n_lines=4, n_planes=2, outliers=0.1, margin=None, c=c, nlevels=nlevels)
+        ok = np.flatnonzero(fr["pt_ref"] >= 0)
+        lo, hi = ok[::7], ok[3::7]
+        clean = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in fr.items()}
+        clean["octave"][lo], clean["octave"][hi] = 0, nlevels - 1
+        fr["octave"][lo], fr["octave"][hi] = -1, 99
+        _same_result(pm.pose_optimization(fr, c), pm.pose_optimization(clean, c))
+        edges, _ = pm.build_edges(fr, c)
+        w = {e.idx: e.info[0] for e in edges if e.kind in (pm.MONO, pm.STEREO)}
+        assert all(w[i] == c["inv_level_sigma2"][0] for i in lo) and all(w[i] == c["inv_level_sigma2"][-1] for i in hi)
+
+
+def test_out_of_range_point_references_are_null():
+    """msl.h: pt_ref values outside [0, xcap) count as NULL: no edge, no correspondence, the outlier byte kept.  xcap, INT_MAX, -2 and
+    INT_MIN give exactly the result of -1 in those slots; with an explicit xcap smaller than len(xyz), references at and above it are NULL."""
+    c = ps.params()
+    fr, _, _ = ps.scene(32, n_pts=100, n_lines=3, n_planes=2, margin=None, c=c)
+    ok = np.flatnonzero(fr["pt_ref"] >= 0)
+    slots = ok[[2, 9, 17, 40]]
+    null = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in fr.items()}
+    null["pt_ref"][slots] = -1
+    fr["pt_ref"][slots] = [len(fr["xyz"]), 2 ** 31 - 1, -2, -2 ** 31]
+    fr["outlier"][slots] = [1, 0, 1, 1]
+    null["outlier"][slots] = [1, 0, 1, 1]
+    got, want = pm.pose_optimization(fr, c), pm.pose_optimization(null, c)
+    _same_result(got, want)
+    assert list(got[2]["outlier"][slots]) == [1, 0, 1, 1]
+    assert pm.build_edges(fr, c)[1] == pm.build_edges(null, c)[1] == len(ok) - 4 + 3 + 3 * 2
+    xcap = 60                                                                     # references >= 60 are NULL under this xcap
+    cut = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in null.items()}
+    cut["pt_ref"][cut["pt_ref"] >= xcap] = -1
+    _same_result(pm.pose_optimization(null, c, xcap=xcap), pm.pose_optimization(cut, c))

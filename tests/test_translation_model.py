@@ -133,3 +133,24 @@ def test_model_restores_pose_model_edges():
             raise RuntimeError
     assert (pm.compute_error, pm.jacobian) == before
     assert math.isfinite(ps.params()["planeChi"])
+
+
+def test_point_edges_follow_the_octave_and_reference_rules():
+    """The point edges obey msl.h's rules as in pose_model: octaves -1 / 99 give exactly the result of 0 / nlevels - 1, and pt_ref values
+    xcap, INT_MAX, -2 and INT_MIN exactly the result of -1 (no edge, not counted, outlier byte kept)."""
+    c = ps.params()
+    fr, rcw, _, _ = ts.scene(33, n_pts=100, n_lines=3, n_planes=2, margin=None, c=c)
+    ok = np.flatnonzero(fr["pt_ref"] >= 0)
+    want = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in fr.items()}
+    want["octave"][ok[::6]], want["octave"][ok[1::6]] = 0, 7
+    fr["octave"][ok[::6]], fr["octave"][ok[1::6]] = -1, 99
+    slots = ok[[3, 10, 22, 45]]
+    want["pt_ref"][slots] = -1
+    fr["pt_ref"][slots] = [len(fr["xyz"]), 2 ** 31 - 1, -2, -2 ** 31]
+    fr["outlier"][slots] = want["outlier"][slots] = [1, 1, 0, 1]
+    a, b = tm.translation_optimization(fr, c, rcw), tm.translation_optimization(want, c, rcw)
+    assert a[0] == b[0] and np.array_equal(a[1], b[1])
+    for k in a[2]:
+        assert np.array_equal(a[2][k], b[2][k]), k
+    assert list(a[2]["outlier"][slots]) == [1, 1, 0, 1]
+    assert tm.build_edges(fr, c, tm.effective_tcw(fr["Tcw"], rcw))[1] == len(ok) - 4

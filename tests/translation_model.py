@@ -108,18 +108,18 @@ def rotate(Tf, X):
     return tuple(float(v) for v in gemm3(np.asarray(Tf, np.float32).reshape(3, 4), False, 1.0, np.asarray(X, np.float32)))
 
 
-def build_edges(fr, c, Tf):
+def build_edges(fr, c, Tf, xcap=None):
     """Optimizer.cc:635-793: point edges by keypoint index (mono when mvuRight < 0), then per line its start and end edges.  Only points
-    count in nInitialCorrespondences.  Returns (edges, nInitial)."""
+    count in nInitialCorrespondences.  Point references and octaves as pose_model.point_ref reads them.  Returns (edges, nInitial)."""
     edges = []
     n0 = 0
     for i in range(len(fr["pt_ref"])):
-        r = int(fr["pt_ref"][i])
-        if r < 0:
+        ref = pm.point_ref(fr, c, i, xcap)
+        if ref is None:
             continue
+        r, inv = ref
         n0 += 1
         X = rotate(Tf, fr["xyz"][r])
-        inv = float(c["inv_level_sigma2"][int(fr["octave"][i])])
         u, v = float(fr["un_xy"][i][0]), float(fr["un_xy"][i][1])
         if fr["uright"][i] < 0:
             edges.append(pm.Edge(MONO, i, (u, v), X, (inv, inv), pm.DELTA_MONO))
@@ -200,13 +200,13 @@ def classify(edges, out, T, c, rows=None):
     return nbad
 
 
-def translation_optimization(fr, c, rcw=None, rows=None):
+def translation_optimization(fr, c, rcw=None, rows=None, xcap=None):
     """int Optimizer::TranslationOptimization(Frame*) for one frame; c as for pose_model.pose_optimization.  Returns (n_good, Tcw_out (12,)
     f32, outlier arrays dict).  rows (a list, optional) receives every comparison of the last classification as (kind, index, chi2 as
-    compared, threshold), for the margin check of tests/translation_scenes.py."""
+    compared, threshold), for the margin check of tests/translation_scenes.py.  xcap as for pose_model.pose_optimization."""
     out = {k: np.array(fr[k], np.uint8, copy=True) for k in set(pm.OUT_KEYS.values())}
     Tf = effective_tcw(fr["Tcw"], rcw)
-    edges, n0 = build_edges(fr, c, Tf)
+    edges, n0 = build_edges(fr, c, Tf, xcap)
     for e in edges:                                                           # mvbOutlier / mvbLineOutlier = false
         out[pm.OUT_KEYS[e.kind]][e.idx] = 0
     if n0 < 3:                                                                # :796, before any plane edge: plane flags untouched

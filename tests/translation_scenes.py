@@ -9,11 +9,12 @@ from tests import translation_model as tm
 def scene(seed, max_rot_deg=0.5, margin=1e-4, c=None, **kw):
     """One frame.  Returns (fr, rcw (9,) f32, Rtrue, ttrue); kw goes to pose_scenes.scene.  When margin is set, asserts that every
     comparison of the model's last classification lies more than margin (relative) away from its threshold."""
+    c = c or ps.params(nlevels=kw.get("nlevels", ps.NLEVELS), scale=kw.get("scale", ps.SCALE))
     fr, R, t = ps.scene(seed, margin=None, c=c, **kw)
     rng = np.random.default_rng(seed + 7919)
     rcw = (ps.rot(rng.normal(size=3), rng.uniform(0, max_rot_deg)) @ R).astype(np.float32).reshape(9)
     if margin is not None:
-        check_margin(fr, c or ps.params(), rcw, margin)
+        check_margin(fr, c, rcw, margin)
     return fr, rcw, R, t
 
 
