@@ -591,6 +591,84 @@ MSL_API int msl_pose_optimize_translation_batch(int device, int n_frames, int ca
                                                 msl_mem mem, uint8_t *outlier, uint8_t *line_outlier, uint8_t *plane_outlier, float *Tcw_out,
                                                 int32_t *n_good, msl_mem out_mem) MSL_NOEXCEPT;
 
+/* ---- Plane association: PlaneMatcher::SearchMapByCoefficients (src/PlaneMatcher.cpp:31-106) ----
+ * n_frames independent calls of  int PlaneMatcher::SearchMapByCoefficients(Frame &pF, const vector<MapPlane*> &vpMapPlanes)  for a
+ * PlaneMatcher(d_th, a_th, ver_th, par_th), with Frame::ComputePlaneWorldCoeff (src/Frame.cc:656-660).  Per frame f:
+ *   plane_coef[4 k..]  mvPlaneCoefficients[k] (k < n_planes[f], `pcap` per frame)    Tcw[12]  rows 0-2 of the CV_32F mTcw
+ * Map planes in GetAllMapPlanes() order (`mcap` per frame), j < n_map[f]:
+ *   mp_w[4 j..]        GetWorldPos()                 mp_flags[j]  bit 0: !isBad()
+ *   mp_pt_off[j], mp_pt_off[j + 1]  (mcap + 1 per frame): mvPlanePoints of plane j are points [off[j], off[j + 1]) of mp_pts[3 n..]
+ *                      (x, y, z; `ptcap` points per frame; offsets are clamped to [0, ptcap])
+ * In/out (out_mem): plane_match[3 k + s] = the index j of mvpMapPlanes[k] (s = 0), mvpParallelPlanes[k] (s = 1), mvpVerticalPlanes[k]
+ * (s = 2), or -1 for NULL.  The reference never clears these pointers: a slot the call does not write keeps its value.
+ * Out: nmatches[f] the return value; plane_w[12 k + 4 s..] / plane_has[k] for every k < n_planes[f] in exactly the layout
+ * msl_pose_optimize[_translation] reads: bit s set and the world position of the plane copied bit for bit when slot s holds an index in
+ * [0, n_map[f]), bit s clear and zeros otherwise.  Optional pM_out[4 k..] (NULL = not wanted): the world coefficients mTcw^T * coef.
+ * Exactly reproduced: pM as a cv::Mat CV_32F product (double accumulation, one rounding per element); angle a float dot product, left to
+ * right; PointDistanceFromPlane a float |a x + b y + c z + d| whose minimum starts at 100 and skips NaN points (an empty cloud gives 100);
+ * the walk over the map planes with its tightening thresholds -- bad planes skipped, `angle > a_th && dis < ldTh` matches and continues,
+ * a plane failing only the distance test falls through to the vertical (|angle| < lverTh) and then the parallel (|angle| > lparTh) test;
+ * strict comparisons, so the first of equal candidates wins.  Two launches (distances, then the walk).
+ * Limits: pcap <= 64, mcap <= 4096, ptcap <= 2^22; larger values are refused with MSL_ERR_INVALID before any launch.  Asynchronous on the
+ * matcher handle's stream when inputs and outputs are device memory; with host memory on either side it returns when the caller's buffers
+ * are its own again. */
+typedef struct msl_plane_params {
+    float d_th, a_th, ver_th, par_th;   /* Plane.AssociationDisRef, AssociationAngRef, VerticalThreshold, ParallelThreshold (src/Tracking.cc:144-154) */
+    float mf_ver_th;                    /* Plane.MFVerticalThreshold: msl_manhattan_detect only */
+} msl_plane_params;
+MSL_API int msl_plane_associate(msl_match *h, int n_frames, int pcap, int mcap, int ptcap, const msl_plane_params *params,
+                                const float *plane_coef, const int32_t *n_planes, const float *Tcw, const float *mp_w, const uint8_t *mp_flags,
+                                const int32_t *mp_pt_off, const float *mp_pts, const int32_t *n_map, msl_mem mem, int32_t *plane_match,
+                                int32_t *nmatches, float *plane_w, uint8_t *plane_has, float *pM_out, msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device matcher handle, always synchronous; see msl_match_by_projection_batch). */
+MSL_API int msl_plane_associate_batch(int device, int n_frames, int pcap, int mcap, int ptcap, const msl_plane_params *params,
+                                      const float *plane_coef, const int32_t *n_planes, const float *Tcw, const float *mp_w,
+                                      const uint8_t *mp_flags, const int32_t *mp_pt_off, const float *mp_pts, const int32_t *n_map,
+                                      msl_mem mem, int32_t *plane_match, int32_t *nmatches, float *plane_w, uint8_t *plane_has,
+                                      float *pM_out, msl_mem out_mem) MSL_NOEXCEPT;
+
+/* ---- Manhattan-frame detection: Tracking::DetectManhattan (src/Tracking.cc:651-844) ----
+ * n_frames independent calls.  Per frame f: plane_coef and n_planes as for msl_plane_associate, plane_npts[k] = mvPlanePoints[k].size(),
+ * plane_match in msl_plane_associate's layout (only slot s = 0, mvpMapPlanes, is read; indices outside [0, n_map[f]) count as NULL),
+ * mp_flags / n_map as for msl_plane_associate (`mcap` per frame; bit 0 = !isBad()).
+ * The Manhattan observation tables of Map, flattened by the caller (`fcap` / `qcap` entries per frame):
+ *   full_tab[7 e..]  {a, b, c, kf, ia, ib, ic}  e < n_full[f]   map-plane indices a <= b <= c, the keyframe slot kf, and
+ *                                                               GetIndexInKeyFrame(pKF) of planes a, b, c (-1 allowed)
+ *   part_tab[5 e..]  {a, b, kf, ia, ib}         e < n_part[f]   the same for GetPartialManhattanObservation
+ *   Both sorted ascending by their keys ((a, b, c) resp. (a, b), lexicographic).  Map hashes and compares its keys as unordered sets
+ *   (src/Map.cc:32-123), so a sorted index tuple is an exact stand-in.  Host-memory tables are checked and refused (MSL_ERR_INVALID) when
+ *   unsorted; sorting device-memory tables is the caller's contract.  An entry with an index -1 (or outside [0, pcap), or a slot outside
+ *   [0, kcap)) is no candidate, as at :713 / :752.
+ * Per keyframe slot r (`kcap` per frame): kf_Rwc[9 r..] = GetPoseInverse() rows / columns 0-2 (row-major), kf_coef[4 (r pcap + q)..] =
+ *   mvPlaneCoefficients[q], kf_npts[r pcap + q] = mvPlanePoints[q].size().
+ * Out: found[f] the return value, full[f] = fullManhattanFound, Rcw[9 f..] = manhattanRcw (row-major, the layout
+ * msl_pose_optimize_translation reads) -- written only where found, the member is left unchanged otherwise (Rcw is in/out) -- and
+ * optionally (NULL = not wanted) choice[6 f..] = {i, j, k (-1 for a partial pair), table entry, score, kf}, {-1, -1, -1, -1, 0, -1} when
+ * nothing is found.
+ * Exactly reproduced: the candidate order (for i, for j > i: the triples k > j, then the pair (i, j)), the gates (held, not bad,
+ * the float dot products against +-mf_ver_th) and the choice -- the first candidate in that order reaching the largest score, if > 0, a
+ * later pair replacing a triple.  The rotation: the partial case's third columns as float cross products, the column flipped only in the
+ * partial case when |det + 1| < 0.5 (det in double), MFc and MFm replaced by their polar factors, Rwc = (kf_Rwc * MFm) * MFc^T as two
+ * float products with double accumulation, Rcw = Rwc^T.  The polar factor U * Vt is not OpenCV's float Jacobi SVD: it is computed in
+ * double by Newton's iteration X <- (X + X^-T) / 2 and rounded to float, so Rcw agrees with the reference within about 2e-6 per entry;
+ * every integer output is exact.  One launch (one workgroup per frame).
+ * Limits: pcap <= 64, mcap <= 4096, fcap <= 65536, qcap <= 65536, kcap <= 4096; larger values are refused with MSL_ERR_INVALID before any
+ * launch.  Asynchronous on the matcher handle's stream when inputs and outputs are device memory; with host memory on either side it
+ * returns when the caller's buffers are its own again. */
+MSL_API int msl_manhattan_detect(msl_match *h, int n_frames, int pcap, int mcap, int fcap, int qcap, int kcap, const msl_plane_params *params,
+                                 const float *plane_coef, const int32_t *plane_npts, const int32_t *n_planes, const int32_t *plane_match,
+                                 const uint8_t *mp_flags, const int32_t *n_map, const int32_t *full_tab, const int32_t *n_full,
+                                 const int32_t *part_tab, const int32_t *n_part, const float *kf_Rwc, const float *kf_coef,
+                                 const int32_t *kf_npts, msl_mem mem, int32_t *found, int32_t *full, float *Rcw, int32_t *choice,
+                                 msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device matcher handle, always synchronous; see msl_match_by_projection_batch). */
+MSL_API int msl_manhattan_detect_batch(int device, int n_frames, int pcap, int mcap, int fcap, int qcap, int kcap,
+                                       const msl_plane_params *params, const float *plane_coef, const int32_t *plane_npts,
+                                       const int32_t *n_planes, const int32_t *plane_match, const uint8_t *mp_flags, const int32_t *n_map,
+                                       const int32_t *full_tab, const int32_t *n_full, const int32_t *part_tab, const int32_t *n_part,
+                                       const float *kf_Rwc, const float *kf_coef, const int32_t *kf_npts, msl_mem mem, int32_t *found,
+                                       int32_t *full, float *Rcw, int32_t *choice, msl_mem out_mem) MSL_NOEXCEPT;
+
 /* Batched form: n_frames keyframes in order, semantically n_frames consecutive msl_sf_fuse_resident calls.
  * Keyframe f's images start at base + f * <frame_stride> bytes (member_frame_stride may be 0: one shared
  * membership image); refs[n_frames] and poses (16 * n_frames floats, column-major Twc each) are host arrays.

@@ -15,3 +15,5 @@ from ._lib import MATCH_PARAMS_DTYPE, LOCAL_MATCH_PARAMS_DTYPE, LOCAL_TRACK_DTYP
 from ._lib import LINE_MATCH_PARAMS_DTYPE, KEYLINE_DTYPE, LINE_TRACK_DTYPE  # noqa: F401
 from . import pose  # noqa: F401
 from ._lib import POSE_PARAMS_DTYPE  # noqa: F401
+from . import plane  # noqa: F401
+from ._lib import PLANE_PARAMS_DTYPE  # noqa: F401

@@ -40,6 +40,7 @@ LINE_TRACK_DTYPE = np.dtype([(n, "<f4") for n in ("proj_x1", "proj_y1", "proj_x2
 POSE_PARAMS_DTYPE = np.dtype([(n, "<f4") for n in ("fx", "fy", "cx", "cy", "bf")] + [("nlevels", "<i4"), ("inv_level_sigma2", "<f4", (16,))] +
                              [(n, "<f8") for n in ("angle_info", "dis_info", "par_info", "ver_info", "plane_chi", "plane_chi_vp", "a_th",
                                                    "par_th")])                                                                        # msl_pose_params
+PLANE_PARAMS_DTYPE = np.dtype([(n, "<f4") for n in ("d_th", "a_th", "ver_th", "par_th", "mf_ver_th")])                             # msl_plane_params
 assert POSE_PARAMS_DTYPE.itemsize == 152 and KEYPOINT_DTYPE.itemsize == 28 and SURFEL_DTYPE.itemsize == 56 and SEED_DTYPE.itemsize == 64
 
 MSL_MEM_HOST, MSL_MEM_DEVICE = 0, 1
@@ -107,6 +108,10 @@ SIGNATURES = {
     "msl_pose_optimize_batch": (_i, [_i, _i, _i, _i, _i, _i] + [_vp] * 16 + [_i] + [_vp] * 5 + [_i]),
     "msl_pose_optimize_translation": (_i, [_vp, _i, _i, _i, _i, _i] + [_vp] * 17 + [_i] + [_vp] * 5 + [_i]),
     "msl_pose_optimize_translation_batch": (_i, [_i, _i, _i, _i, _i, _i] + [_vp] * 17 + [_i] + [_vp] * 5 + [_i]),
+    "msl_plane_associate": (_i, [_vp, _i, _i, _i, _i] + [_vp] * 9 + [_i] + [_vp] * 5 + [_i]),
+    "msl_plane_associate_batch": (_i, [_i, _i, _i, _i, _i] + [_vp] * 9 + [_i] + [_vp] * 5 + [_i]),
+    "msl_manhattan_detect": (_i, [_vp, _i, _i, _i, _i, _i, _i] + [_vp] * 14 + [_i] + [_vp] * 4 + [_i]),
+    "msl_manhattan_detect_batch": (_i, [_i, _i, _i, _i, _i, _i, _i] + [_vp] * 14 + [_i] + [_vp] * 4 + [_i]),
     "msl_sf_fuse_resident": (_i, [_vp, _i, _vp, _sz, _vp, _sz, _vp, _sz, _i, _vp]),
     "msl_sf_set_batch_capacity": (_i, [_vp, _i]),
     "msl_sf_fuse_resident_batch": (_i, [_vp, _i, _vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _sz, _sz, _i, _vp]),

@@ -1,4 +1,4 @@
-// msl_match_handle.h -- the matcher handle, shared by msl_match.hip and msl_pose.hip (internal).
+// msl_match_handle.h -- the matcher handle, shared by msl_match.hip, msl_line_match.hip, msl_pose.hip and msl_plane.hip (internal).
 #pragma once
 
 #include "msl_common.h"
@@ -13,6 +13,8 @@ struct msl_match {
     msl::DevBuf lin[14], trk, inView;                                  // msl_match_local_points: staged inputs, per-point scratch
     msl::DevBuf poseIn[16], poseOut[5];                                // msl_pose_optimize[_translation]: staged inputs (+ Rcw), in/out flags, outputs
     msl::DevBuf lineIn[11], lineQ, lineTrk, lineView, lineIo[2];       // the line searches: staged inputs, per-line queries / tracks / in-view, line_xyz / line_has
+    msl::DevBuf planeIn[8], planeDis, planeOut[5];                     // msl_plane_associate: staged inputs, [frame][map plane][64] distances, outputs
+    msl::DevBuf mfIn[13], mfOut[4];                                    // msl_manhattan_detect: staged inputs, Rcw (in/out) and outputs
     bool lineAttrSet = false;
     bool localAttrSet = false;
     bool attrSet = false;
