@@ -669,6 +669,106 @@ MSL_API int msl_manhattan_detect_batch(int device, int n_frames, int pcap, int m
                                        const float *kf_Rwc, const float *kf_coef, const int32_t *kf_npts, msl_mem mem, int32_t *found,
                                        int32_t *full, float *Rcw, int32_t *choice, msl_mem out_mem) MSL_NOEXCEPT;
 
+/* ---- Bag of words: the vocabulary, Frame::ComputeBoW / KeyFrame::ComputeBoW, and the reference-keyframe searches ----
+ * The searches that open Tracking::TrackReferenceKeyFrame (src/Tracking.cc:1146-1175) and Tracking::TranslationEstimation (:846-877).
+ *
+ * msl_vocab: a DBoW2 TemplatedVocabulary<FORB::TDescriptor, FORB> on one device, as loadFromTextFile builds it
+ * (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1338-1420).  Node table of n_nodes entries, entry 0 the root (its values are not read),
+ * nodes 1 .. n_nodes - 1 in file order: parent[i] (in [0, i), else refused), is_leaf_flag[i] (the file's isLeaf > 0), desc32[32 i..],
+ * weight[i].  Children belong to their parent in file order; word ids go to the flagged nodes in file order; every other node has word
+ * id 0.  The children of each node are packed contiguously on the device as 32-byte records.  Limits: 2 <= k <= 20, 1 <= L <= 10,
+ * scoring 0..5 (L1_NORM, L2_NORM, CHI_SQUARE, KL, BHATTACHARYYA, DOT_PRODUCT), weighting 0..3 (TF_IDF, TF, IDF, BINARY), 1 <= n_nodes < 2^31;
+ * NULL with msl_last_error() otherwise, and with no usable device (no CPU fallback).
+ * msl_vocab_load_text parses DBoW2's text format: a header line "k L scoring weighting", then one line per node
+ * "parent isLeaf d0 .. d31 weight".  Refused as the reference refuses a header (k, L, scoring, weighting outside the limits above; the reference
+ * accepts k = 0 and 1, where its node-count arithmetic divides by zero), and a malformed node line.  Blank lines are skipped: the reference
+ * loops on !eof(), so a file ending in a newline gives its root one more childless child (parent 0 from a failed parse, an uninitialised
+ * descriptor, weight 0) -- undefined behaviour this loader does not reproduce.
+ * msl_vocab_info: info[7] = {k, L, scoring, weighting, n_nodes, n_words, device}. */
+typedef struct msl_vocab msl_vocab;
+MSL_API msl_vocab *msl_vocab_create(int device, int k, int L, int scoring, int weighting, int n_nodes, const int32_t *parent,
+                                    const uint8_t *is_leaf_flag, const uint8_t *desc32, const double *weight) MSL_NOEXCEPT;
+MSL_API msl_vocab *msl_vocab_load_text(int device, const char *path) MSL_NOEXCEPT;
+MSL_API void msl_vocab_destroy(msl_vocab *v) MSL_NOEXCEPT;
+MSL_API int msl_vocab_info(const msl_vocab *v, int32_t info[7]) MSL_NOEXCEPT;
+
+/* msl_bow_transform: n_frames independent calls of
+ *     void TemplatedVocabulary::transform(const vector<TDescriptor>&, BowVector&, FeatureVector&, int levelsup)   (TemplatedVocabulary.h:1126-1192)
+ * with the per-feature descent (:1217-1255): Frame::ComputeBoW / KeyFrame::ComputeBoW call it with levelsup = 4.  desc[32 (f cap + i)..] and
+ * n_desc[f] are msl_orb_extract_frame_batch's desc32 / n_out (`cap` keypoints per frame).  Per feature (all cap entries written):
+ * word_out the word id, node_out the FeatureVector node at level L - levelsup (0, the root, when L - levelsup <= 0); both -1 when the
+ * feature is stopped (word weight not > 0), when i >= n_desc[f], and for every feature of a vocabulary without words (DBoW2's empty()).
+ * Feature i is in fv[node_out[i]]; each list is in ascending feature order by construction.  Optional (all three or none; NULL skips the
+ * per-frame sort): the BowVector as ascending word ids bow_word[f cap + j] with bow_value (double), j < n_words[f]; -1 / 0 beyond.
+ * Exactly reproduced: the descent -- the first child holds the initial best, a later child replaces it only at a strictly smaller Hamming
+ * distance (ties to the earliest child in file order) -- stops at a node without children (a childless node that is not flagged keeps word
+ * id 0 and its file weight); TF / TF_IDF accumulate v[id] += w in feature order, IDF / BINARY keep the first weight; every scoring but
+ * DOT_PRODUCT normalises (L1: sum of fabs, L2_NORM: sqrt of the sum of squares, both in ascending word order, only when the norm is > 0),
+ * otherwise TF / TF_IDF divide by v.size().  When the descent stops above level L - levelsup the reference leaves nid uninitialised;
+ * node_out is then the node where the descent stopped.  The vocabulary must live on the handle's device (MSL_ERR_INVALID otherwise).
+ * Limits: cap <= 8192.  Asynchronous on the matcher handle's stream when inputs and outputs are device memory; with host memory on either
+ * side it returns when the caller's buffers are its own again. */
+MSL_API int msl_bow_transform(msl_match *h, const msl_vocab *v, int n_frames, int cap, int levelsup, const uint8_t *desc, const int32_t *n_desc,
+                              msl_mem mem, int32_t *word_out, int32_t *node_out, int32_t *bow_word, double *bow_value, int32_t *n_words,
+                              msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device matcher handle, always synchronous; see msl_match_by_projection_batch). */
+MSL_API int msl_bow_transform_batch(int device, const msl_vocab *v, int n_frames, int cap, int levelsup, const uint8_t *desc,
+                                    const int32_t *n_desc, msl_mem mem, int32_t *word_out, int32_t *node_out, int32_t *bow_word,
+                                    double *bow_value, int32_t *n_words, msl_mem out_mem) MSL_NOEXCEPT;
+
+/* msl_match_by_bow: n_pairs independent calls of
+ *     int ORBmatcher::SearchByBoW(KeyFrame *pKF, Frame &F, vector<MapPoint*> &vpMapPointMatches)   (src/ORBmatcher.cc:146-247)
+ * for an ORBmatcher(nn_ratio, check_orientation): 0.7 at both tracking sites, 0.75 in Tracking::Relocalization.  Per pair f, `cap`
+ * entries per side:
+ *   keyframe  kf_desc[32 i..] mDescriptors, kf_angle[i] mvKeysUn[i].angle, kf_node[i] its node_out (an earlier msl_bow_transform),
+ *             kf_flags[i] bit 0: GetMapPointMatches()[i] && !isBad(), i < n_kf[f]
+ *   frame     cur_kps[i] mvKeys (the angle is read), cur_desc, cur_node (its node_out), i < n_cur[f]
+ * Out: match_out[f cap + iF] = the keyframe keypoint index whose map point vpMapPointMatches[iF] holds, or -1; nmatches[f] the return value.
+ * match_out feeds msl_pose_optimize[_translation] as pt_ref directly, with the keyframe's map-point positions per keyframe keypoint as xyz.
+ * Exactly reproduced: only nodes present on both sides are visited; in a node the keyframe features run in ascending order and a frame
+ * feature matched earlier is skipped; bestDist1 is the first minimum over ascending frame indices, bestDist2 the second smallest distance
+ * (equal to bestDist1 on a tie), both starting at 256; accepted when bestDist1 <= TH_LOW (50) and (float)bestDist1 < nn_ratio *
+ * (float)bestDist2; the rotation histogram (HISTO_LENGTH 30, bin round(rot / 30), bin 30 -> 0) with ComputeThreeMaxima, every match outside
+ * the kept bins NULLed.  Limits: cap <= 8192.  Memory and synchronisation as msl_bow_transform. */
+typedef struct msl_bow_match_params {
+    float nn_ratio;                   /* ORBmatcher::mfNNratio */
+    int32_t check_orientation;        /* ORBmatcher::mbCheckOrientation */
+} msl_bow_match_params;
+MSL_API int msl_match_by_bow(msl_match *h, int n_pairs, int cap, const msl_bow_match_params *params, const uint8_t *kf_desc,
+                             const float *kf_angle, const int32_t *kf_node, const uint8_t *kf_flags, const int32_t *n_kf,
+                             const msl_keypoint *cur_kps, const uint8_t *cur_desc, const int32_t *cur_node, const int32_t *n_cur, msl_mem mem,
+                             int32_t *match_out, int32_t *nmatches, msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device matcher handle, always synchronous; see msl_match_by_projection_batch). */
+MSL_API int msl_match_by_bow_batch(int device, int n_pairs, int cap, const msl_bow_match_params *params, const uint8_t *kf_desc,
+                                   const float *kf_angle, const int32_t *kf_node, const uint8_t *kf_flags, const int32_t *n_kf,
+                                   const msl_keypoint *cur_kps, const uint8_t *cur_desc, const int32_t *cur_node, const int32_t *n_cur,
+                                   msl_mem mem, int32_t *match_out, int32_t *nmatches, msl_mem out_mem) MSL_NOEXCEPT;
+
+/* msl_match_lines_by_descriptor: n_pairs independent calls of
+ *     int LSDmatcher::SearchByDescriptor(KeyFrame *pKF, Frame &currentF, vector<MapLine*> &vpMapLineMatches)   (src/LSDmatcher.cpp:201-234)
+ * Keyframe lines (`klcap` per pair), q < n_kf_lines[f]: kf_ldesc[32 q..] mLineDescriptors, kf_line_flags[q] bit 0:
+ * GetMapLineMatches()[q] != NULL (the reference does not test isBad() here), optional kf_line_xyz[6 q..] GetWorldPos() (double).
+ * Current lines (`lcap` per pair), t < n_cur_lines[f]: cur_ldesc[32 t..] mLdesc.
+ * Out: match_out[f lcap + t] = the last query q written into slot t, or -1; nmatches[f] the return value (every accepted write counts,
+ * overwritten ones included).  Optional (both or neither, with kf_line_xyz): line_xyz[6 t..] / line_has[t] in the layout
+ * msl_match_lines_by_projection writes for msl_pose_optimize -- a written slot gets the keyframe line's position bit for bit and
+ * line_has = 1, every other t < n_cur_lines[f] line_has = 0; other bytes are not touched.
+ * BFMatcher(NORM_HAMMING).knnMatch(kf, cur, 2) is restated, not linked: best = the lowest distance, the lowest train index on ties; second =
+ * the next in (distance, train index) order, so an equal distance at a later index is the second (OpenCV's insertion order; parity with
+ * OpenCV is unpinned).  Queries in ascending order; accepted when (float)d0 / (float)d1 < (float)(1.0f / 1.5f)
+ * (0 / 0 is NaN and rejected) and bit 0 is set.  lineDescriptorMAD's results are dead in the reference and not computed.  With
+ * n_kf_lines == 0 or n_cur_lines < 2 the reference reads past a vector's end (undefined); here the result is 0 matches, everything NULL.
+ * Limits: lcap <= 256, klcap <= 256.  Memory and synchronisation as msl_bow_transform; line_xyz is in/out. */
+MSL_API int msl_match_lines_by_descriptor(msl_match *h, int n_pairs, int lcap, int klcap, const uint8_t *kf_ldesc, const uint8_t *kf_line_flags,
+                                          const double *kf_line_xyz, const int32_t *n_kf_lines, const uint8_t *cur_ldesc,
+                                          const int32_t *n_cur_lines, msl_mem mem, int32_t *match_out, int32_t *nmatches, double *line_xyz,
+                                          uint8_t *line_has, msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device matcher handle, always synchronous; see msl_match_by_projection_batch). */
+MSL_API int msl_match_lines_by_descriptor_batch(int device, int n_pairs, int lcap, int klcap, const uint8_t *kf_ldesc,
+                                                const uint8_t *kf_line_flags, const double *kf_line_xyz, const int32_t *n_kf_lines,
+                                                const uint8_t *cur_ldesc, const int32_t *n_cur_lines, msl_mem mem, int32_t *match_out,
+                                                int32_t *nmatches, double *line_xyz, uint8_t *line_has, msl_mem out_mem) MSL_NOEXCEPT;
+
 /* Batched form: n_frames keyframes in order, semantically n_frames consecutive msl_sf_fuse_resident calls.
  * Keyframe f's images start at base + f * <frame_stride> bytes (member_frame_stride may be 0: one shared
  * membership image); refs[n_frames] and poses (16 * n_frames floats, column-major Twc each) are host arrays.

@@ -17,3 +17,5 @@ from . import pose  # noqa: F401
 from ._lib import POSE_PARAMS_DTYPE  # noqa: F401
 from . import plane  # noqa: F401
 from ._lib import PLANE_PARAMS_DTYPE  # noqa: F401
+from . import bow  # noqa: F401
+from ._lib import BOW_MATCH_PARAMS_DTYPE  # noqa: F401

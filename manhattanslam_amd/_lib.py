@@ -41,6 +41,7 @@ POSE_PARAMS_DTYPE = np.dtype([(n, "<f4") for n in ("fx", "fy", "cx", "cy", "bf")
                              [(n, "<f8") for n in ("angle_info", "dis_info", "par_info", "ver_info", "plane_chi", "plane_chi_vp", "a_th",
                                                    "par_th")])                                                                        # msl_pose_params
 PLANE_PARAMS_DTYPE = np.dtype([(n, "<f4") for n in ("d_th", "a_th", "ver_th", "par_th", "mf_ver_th")])                             # msl_plane_params
+BOW_MATCH_PARAMS_DTYPE = np.dtype([("nn_ratio", "<f4"), ("check_orientation", "<i4")])                                               # msl_bow_match_params
 assert POSE_PARAMS_DTYPE.itemsize == 152 and KEYPOINT_DTYPE.itemsize == 28 and SURFEL_DTYPE.itemsize == 56 and SEED_DTYPE.itemsize == 64
 
 MSL_MEM_HOST, MSL_MEM_DEVICE = 0, 1
@@ -112,6 +113,16 @@ SIGNATURES = {
     "msl_plane_associate_batch": (_i, [_i, _i, _i, _i, _i] + [_vp] * 9 + [_i] + [_vp] * 5 + [_i]),
     "msl_manhattan_detect": (_i, [_vp, _i, _i, _i, _i, _i, _i] + [_vp] * 14 + [_i] + [_vp] * 4 + [_i]),
     "msl_manhattan_detect_batch": (_i, [_i, _i, _i, _i, _i, _i, _i] + [_vp] * 14 + [_i] + [_vp] * 4 + [_i]),
+    "msl_vocab_create": (_vp, [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "msl_vocab_load_text": (_vp, [_i, C.c_char_p]),
+    "msl_vocab_destroy": (None, [_vp]),
+    "msl_vocab_info": (_i, [_vp, _vp]),
+    "msl_bow_transform": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i] + [_vp] * 5 + [_i]),
+    "msl_bow_transform_batch": (_i, [_i, _vp, _i, _i, _i, _vp, _vp, _i] + [_vp] * 5 + [_i]),
+    "msl_match_by_bow": (_i, [_vp, _i, _i] + [_vp] * 10 + [_i, _vp, _vp, _i]),
+    "msl_match_by_bow_batch": (_i, [_i, _i, _i] + [_vp] * 10 + [_i, _vp, _vp, _i]),
+    "msl_match_lines_by_descriptor": (_i, [_vp, _i, _i, _i] + [_vp] * 6 + [_i] + [_vp] * 4 + [_i]),
+    "msl_match_lines_by_descriptor_batch": (_i, [_i, _i, _i, _i] + [_vp] * 6 + [_i] + [_vp] * 4 + [_i]),
     "msl_sf_fuse_resident": (_i, [_vp, _i, _vp, _sz, _vp, _sz, _vp, _sz, _i, _vp]),
     "msl_sf_set_batch_capacity": (_i, [_vp, _i]),
     "msl_sf_fuse_resident_batch": (_i, [_vp, _i, _vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _sz, _sz, _i, _vp]),

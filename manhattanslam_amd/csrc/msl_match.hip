@@ -38,6 +38,7 @@ namespace {
 
 constexpr int GRID_ROWS = MSL_FRAME_GRID_ROWS, GRID_COLS = MSL_FRAME_GRID_COLS, NCELLS = GRID_ROWS * GRID_COLS;
 constexpr int TH_HIGH = 100, HISTO_LENGTH = 30;     // src/ORBmatcher.cc:33-35
+static_assert(HISTO_LENGTH == ROT_HISTO_LENGTH, "rot_bin / three_maxima (msl_match_math.h) use the same histogram");
 constexpr int CMAX = 32;                            // stored candidates per point; more are re-enumerated by k_match_assign
 constexpr int MAX_CAP = 8192;
 constexpr unsigned T_NONE = 0xFFFFFFFFu;
@@ -286,29 +287,15 @@ __global__ __launch_bounds__(ASSIGN_NT) void k_match_assign(MatchDev P) {
             atomicMax(&s_holder[pk], q);
             atomicAdd(&s_nm, 1);
             if (P.prm.check_orientation) {
-                float rot = P.lastAngle[(size_t)pair * P.cap + q] - P.curKps[(size_t)pair * P.cap + pk].angle;   // :643-649
-                if (rot < 0.0) rot += 360.0f;
-                b = (int)roundf(rot * (1.0f / HISTO_LENGTH));
-                if (b == HISTO_LENGTH) b = 0;
-                if (b >= 0 && b < HISTO_LENGTH) atomicAdd(&s_hist[b], 1); else b = -1;
+                b = rot_bin(P.lastAngle[(size_t)pair * P.cap + q] - P.curKps[(size_t)pair * P.cap + pk].angle);   // :643-649
+                if (b >= 0) atomicAdd(&s_hist[b], 1);
             }
         }
         s_bin[q] = b;
     }
     __syncthreads();
     if (P.prm.check_orientation) {
-        if (threadIdx.x == 0) {   // ComputeThreeMaxima (:799-830)
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-            for (int i = 0; i < HISTO_LENGTH; i++) {
-                const int s = s_hist[i];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-                else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-                else if (s > max3) { max3 = s; ind3 = i; }
-            }
-            if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-            else if ((float)max3 < 0.1f * (float)max1) { ind3 = -1; }
-            s_keep[0] = ind1; s_keep[1] = ind2; s_keep[2] = ind3;
-        }
+        if (threadIdx.x == 0) three_maxima(s_hist, s_keep);   // ComputeThreeMaxima (:799-830)
         __syncthreads();
         for (int q = threadIdx.x; q < nLast; q += ASSIGN_NT) {
             const int b = s_bin[q];

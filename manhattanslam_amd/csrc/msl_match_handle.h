@@ -1,4 +1,4 @@
-// msl_match_handle.h -- the matcher handle, shared by msl_match.hip, msl_line_match.hip, msl_pose.hip and msl_plane.hip (internal).
+// msl_match_handle.h -- the matcher handle, shared by msl_match.hip, msl_line_match.hip, msl_pose.hip, msl_plane.hip and msl_bow.hip (internal).
 #pragma once
 
 #include "msl_common.h"
@@ -15,6 +15,10 @@ struct msl_match {
     msl::DevBuf lineIn[11], lineQ, lineTrk, lineView, lineIo[2];       // the line searches: staged inputs, per-line queries / tracks / in-view, line_xyz / line_has
     msl::DevBuf planeIn[8], planeDis, planeOut[5];                     // msl_plane_associate: staged inputs, [frame][map plane][64] distances, outputs
     msl::DevBuf mfIn[13], mfOut[4];                                    // msl_manhattan_detect: staged inputs, Rcw (in/out) and outputs
+    msl::DevBuf bowIn[2], bowOut[5], bowW;                             // msl_bow_transform: staged inputs, outputs, per-feature word weights
+    msl::DevBuf bmIn[9], bmOut[2];                                     // msl_match_by_bow
+    msl::DevBuf ldIn[6], ldOut[4];                                     // msl_match_lines_by_descriptor (line_xyz in/out)
+    bool bowAttrSet = false;
     bool lineAttrSet = false;
     bool localAttrSet = false;
     bool attrSet = false;

@@ -34,6 +34,31 @@ __device__ __forceinline__ int hamming256(const uint4 &a0, const uint4 &a1, cons
            __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
 }
 
+// The rotation-consistency histogram of the point searches (src/ORBmatcher.cc:33-35, e.g. :643-649 and :199-206): HISTO_LENGTH bins, the bin of
+// a rotation is round(rot * (1 / HISTO_LENGTH)) after rot += 360 for rot < 0, bin HISTO_LENGTH folds to 0 (so only bins 0..12 occur, as in
+// ORB-SLAM2).  Returns -1 for a value outside [0, HISTO_LENGTH).
+constexpr int ROT_HISTO_LENGTH = 30;
+__device__ __forceinline__ int rot_bin(float rot) {
+    if (rot < 0.0) rot += 360.0f;
+    int b = (int)roundf(rot * (1.0f / ROT_HISTO_LENGTH));
+    if (b == ROT_HISTO_LENGTH) b = 0;
+    return b >= 0 && b < ROT_HISTO_LENGTH ? b : -1;
+}
+
+// ORBmatcher::ComputeThreeMaxima (src/ORBmatcher.cc:799-830) on bin counts: keep[0..2] = ind1, ind2, ind3 (-1 = none)
+__device__ __forceinline__ void three_maxima(const int *hist, int keep[3]) {
+    int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
+    for (int i = 0; i < ROT_HISTO_LENGTH; i++) {
+        const int s = hist[i];
+        if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
+        else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
+        else if (s > max3) { max3 = s; ind3 = i; }
+    }
+    if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
+    else if ((float)max3 < 0.1f * (float)max1) { ind3 = -1; }
+    keep[0] = ind1; keep[1] = ind2; keep[2] = ind3;
+}
+
 // ceil(log(maxDistance / dist) / logScale) as an int, not clamped (MapLine::PredictScale, src/MapLine.cpp:320-328).  log is glibc's logf in
 // the reference; here the double log of the float, rounded once.  A quotient that is not a finite int (NaN, +-inf)
 // converts to INT_MIN as on x86-64.
