@@ -82,27 +82,6 @@ struct LdescDev {
     int32_t *matchOut, *nmatches; double *lineXyz; uint8_t *lineHas;
 };
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-__device__ __forceinline__ void load_desc(const uint8_t *p, uint4 &a, uint4 &b) {
-    const uint4 *q = reinterpret_cast<const uint4 *>(p);
-    a = q[0]; b = q[1];
-}
-
-// The two smallest of the keys held by the lanes of a width-W group (every lane gets both): merging (a1 <= a2) with (b1 <= b2).
-template <typename T>
-__device__ __forceinline__ void two_min(T &m1, T &m2, int width) {
-    for (int o = 1; o < width; o <<= 1) {
-        const T b1 = __shfl_xor(m1, o, width), b2 = __shfl_xor(m2, o, width);
-        const T lo = m1 < b1 ? m1 : b1, hi = m1 < b1 ? b1 : m1;
-        const T s = m2 < b2 ? m2 : b2;
-        m1 = lo; m2 = hi < s ? hi : s;
-    }
-}
-__device__ __forceinline__ void push_key(unsigned long long &m1, unsigned long long &m2, unsigned long long k) {
-    if (k < m1) { m2 = m1; m1 = k; } else if (k < m2) m2 = k;
-}
-
 // Ascending bitonic sort of n (a power of two) 64-bit keys in LDS by the whole block.
 __device__ void bitonic_sort(unsigned long long *a, int n) {
     for (int size = 2; size <= n; size <<= 1)
@@ -281,7 +260,7 @@ __global__ __launch_bounds__(BOW_NT) void k_match_bow(BowMatchDev M) {
                 uint4 c0, c1;
                 load_desc(M.curDesc + (base + iF) * 32, c0, c1);
                 const unsigned d = (unsigned)hamming256(k0, k1, c0, c1);
-                push_key(m1, m2, ((unsigned long long)d << IDX_BITS) | (unsigned)iF);
+                two_smallest(((unsigned long long)d << IDX_BITS) | (unsigned)iF, m1, m2);
             }
             two_min(m1, m2, 64);
             // bestDist1 / bestDist2 start at 256, and a distance of 256 never replaces them
@@ -294,27 +273,14 @@ __global__ __launch_bounds__(BOW_NT) void k_match_bow(BowMatchDev M) {
         }
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < nCur; i += BOW_NT) {
-        const int iKF = s_m[i];
-        if (iKF < 0) continue;
-        atomicAdd(&s_nm, 1);
-        if (M.checkOrientation) {
-            const int b = rot_bin(M.kfAngle[base + iKF] - M.curKps[base + i].angle);
-            if (b >= 0) atomicAdd(&s_hist[b], 1);
-        }
-    }
+    int nm = 0;
+    for (int i = threadIdx.x; i < nCur; i += BOW_NT) nm += s_m[i] >= 0;
+    if (nm) atomicAdd(&s_nm, nm);
     __syncthreads();
-    if (M.checkOrientation) {
-        if (threadIdx.x == 0) three_maxima(s_hist, s_keep);
-        __syncthreads();
-        for (int i = threadIdx.x; i < nCur; i += BOW_NT) {
-            const int iKF = s_m[i];
-            if (iKF < 0) continue;
-            const int b = rot_bin(M.kfAngle[base + iKF] - M.curKps[base + i].angle);
-            if (b >= 0 && b != s_keep[0] && b != s_keep[1] && b != s_keep[2]) { s_m[i] = -1; atomicSub(&s_nm, 1); }
-        }
-        __syncthreads();
-    }
+    if (M.checkOrientation)                                    // rotation histogram, three maxima, NULLing (:199-206, :226-243)
+        rotation_cull<BOW_NT>(nCur, s_hist, s_keep,
+                              [&](int i) { return s_m[i] >= 0 ? rot_bin(M.kfAngle[base + s_m[i]] - M.curKps[base + i].angle) : -1; },
+                              [&](int i) { s_m[i] = -1; atomicSub(&s_nm, 1); });
     for (int i = threadIdx.x; i < cap; i += BOW_NT) M.matchOut[base + i] = i < nCur ? s_m[i] : -1;
     if (threadIdx.x == 0) M.nmatches[f] = s_nm;
 }
@@ -346,8 +312,7 @@ __global__ __launch_bounds__(LD_NT) void k_match_ldesc(LdescDev L) {
             for (int r = 0; r < 4; r++) {
                 const int t = lane + 64 * r;
                 if (t >= nCur) continue;
-                const unsigned key = ((unsigned)hamming256(k0, k1, c[r][0], c[r][1]) << 9) | (unsigned)t;   // lowest train index first on ties
-                if (key < m1) { m2 = m1; m1 = key; } else if (key < m2) m2 = key;
+                two_smallest(((unsigned)hamming256(k0, k1, c[r][0], c[r][1]) << 9) | (unsigned)t, m1, m2);   // lowest train index first on ties
             }
             two_min(m1, m2, 64);
             if (lane == 0) {
@@ -496,23 +461,15 @@ int run_transform(msl_match *h, const msl_vocab *v, int n_frames, int cap, int l
     D.nidLevel = (int)std::min<long long>((long long)v->L - levelsup, INT_MAX);   // <= 0: the root
     D.V = VocabDev{(const uint4 *)v->rec.p, (const int32_t *)v->recNode.p, (const int2 *)v->child.p, (const int32_t *)v->word.p,
                    (const double *)v->weight.p, v->nWords};
-    const void *src[2] = {desc, n_desc};
-    const size_t bytes[2] = {32 * n, 4 * F};
-    void *dev[2];
-    MSL_HIP_TRY(stage(src, bytes, 2, 2, mem, h->bowIn, st, dev));
-    D.desc = (const uint8_t *)dev[0]; D.nDesc = (const int32_t *)dev[1];
-    void *out[5] = {word_out, node_out, bow_word, bow_value, n_words}, *dout[5];
-    const size_t outBytes[5] = {4 * n, 4 * n, 4 * n, 8 * n, 4 * F};
-    MSL_HIP_TRY(stage(out, outBytes, vec ? 5 : 2, 0, out_mem, h->bowOut, st, dout));
-    D.wordOut = (int32_t *)dout[0]; D.nodeOut = (int32_t *)dout[1];
+    Stage S(h, mem, out_mem);
+    D.desc = S.in(desc, 32 * n); D.nDesc = S.in(n_desc, F);
+    D.wordOut = S.out(word_out, n); D.nodeOut = S.out(node_out, n);
+    D.bowWord = S.out(bow_word, n); D.bowValue = S.out(bow_value, n); D.nWordsOut = S.out(n_words, F);   // all three or none
+    MSL_HIP_TRY(S.error());
     if (vec) {
         MSL_HIP_TRY(h->bowW.grow(8 * n, st));
-        D.fw = (double *)h->bowW.p; D.bowWord = (int32_t *)dout[2]; D.bowValue = (double *)dout[3]; D.nWordsOut = (int32_t *)dout[4];
-        if (!h->bowAttrSet) {
-            MSL_HIP_TRY(hipFuncSetAttribute((const void *)k_bow_vector, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(8 * MAX_CAP)));
-            MSL_HIP_TRY(hipFuncSetAttribute((const void *)k_match_bow, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(18 * MAX_CAP)));
-            h->bowAttrSet = true;
-        }
+        D.fw = (double *)h->bowW.p;
+        MSL_HIP_TRY(allow_lds(h, LDS_BOW_VECTOR, k_bow_vector, 8 * MAX_CAP));
     }
     if (v->maxChildren <= 16)
         hipLaunchKernelGGL(k_bow_descend<16>, dim3((unsigned)((cap + 15) / 16), (unsigned)n_frames), dim3(256), 0, st, D);
@@ -523,7 +480,7 @@ int run_transform(msl_match *h, const msl_vocab *v, int n_frames, int cap, int l
         hipLaunchKernelGGL(k_bow_vector, dim3((unsigned)n_frames), dim3(VEC_NT), 8 * (size_t)pow2_at_least(std::max(cap, 2)), st, D);
         MSL_HIP_TRY(hipGetLastError());
     }
-    MSL_HIP_TRY(finish_call(out, dout, outBytes, vec ? 5 : 2, mem, out_mem, st));
+    MSL_HIP_TRY(S.finish());
     return MSL_OK;
 }
 
@@ -541,26 +498,16 @@ int run_match_bow(msl_match *h, int n_pairs, int cap, const msl_bow_match_params
     const size_t F = (size_t)n_pairs, n = F * cap;
     BowMatchDev M{};
     M.cap = cap; M.nnRatio = prm->nn_ratio; M.checkOrientation = prm->check_orientation;
-    const void *src[9] = {kf_desc, kf_angle, kf_node, kf_flags, n_kf, cur_kps, cur_desc, cur_node, n_cur};
-    const size_t bytes[9] = {32 * n, 4 * n, 4 * n, n, 4 * F, sizeof(msl_keypoint) * n, 32 * n, 4 * n, 4 * F};
-    void *dev[9];
-    MSL_HIP_TRY(stage(src, bytes, 9, 9, mem, h->bmIn, st, dev));
-    M.kfDesc = (const uint8_t *)dev[0]; M.kfAngle = (const float *)dev[1]; M.kfNode = (const int32_t *)dev[2]; M.kfFlags = (const uint8_t *)dev[3];
-    M.nKf = (const int32_t *)dev[4]; M.curKps = (const msl_keypoint *)dev[5]; M.curDesc = (const uint8_t *)dev[6]; M.curNode = (const int32_t *)dev[7];
-    M.nCur = (const int32_t *)dev[8];
-    void *out[2] = {match_out, nmatches}, *dout[2];
-    const size_t outBytes[2] = {4 * n, 4 * F};
-    MSL_HIP_TRY(stage(out, outBytes, 2, 0, out_mem, h->bmOut, st, dout));
-    M.matchOut = (int32_t *)dout[0]; M.nmatches = (int32_t *)dout[1];
-    if (!h->bowAttrSet) {
-        MSL_HIP_TRY(hipFuncSetAttribute((const void *)k_bow_vector, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(8 * MAX_CAP)));
-        MSL_HIP_TRY(hipFuncSetAttribute((const void *)k_match_bow, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(18 * MAX_CAP)));
-        h->bowAttrSet = true;
-    }
+    Stage S(h, mem, out_mem);
+    M.kfDesc = S.in(kf_desc, 32 * n); M.kfAngle = S.in(kf_angle, n); M.kfNode = S.in(kf_node, n); M.kfFlags = S.in(kf_flags, n); M.nKf = S.in(n_kf, F);
+    M.curKps = S.in(cur_kps, n); M.curDesc = S.in(cur_desc, 32 * n); M.curNode = S.in(cur_node, n); M.nCur = S.in(n_cur, F);
+    M.matchOut = S.out(match_out, n); M.nmatches = S.out(nmatches, F);
+    MSL_HIP_TRY(S.error());
+    MSL_HIP_TRY(allow_lds(h, LDS_MATCH_BOW, k_match_bow, 18 * MAX_CAP));
     const size_t P = (size_t)pow2_at_least(std::max(cap, 2));
     hipLaunchKernelGGL(k_match_bow, dim3((unsigned)n_pairs), dim3(BOW_NT), 16 * P + 2 * P, st, M);
     MSL_HIP_TRY(hipGetLastError());
-    MSL_HIP_TRY(finish_call(out, dout, outBytes, 2, mem, out_mem, st));
+    MSL_HIP_TRY(S.finish());
     return MSL_OK;
 }
 
@@ -579,26 +526,15 @@ int run_match_ldesc(msl_match *h, int n_pairs, int lcap, int klcap, const uint8_
     const size_t F = (size_t)n_pairs, nk = F * klcap, nc = F * lcap;
     LdescDev L{};
     L.lcap = lcap; L.klcap = klcap;
-    const void *src[6] = {kf_ldesc, kf_line_flags, n_kf_lines, cur_ldesc, n_cur_lines, kf_line_xyz};
-    const size_t bytes[6] = {32 * nk, nk, 4 * F, 32 * nc, 4 * F, 48 * nk};
-    void *dev[6] = {};
-    MSL_HIP_TRY(stage(src, bytes, kf_line_xyz ? 6 : 5, kf_line_xyz ? 6 : 5, mem, h->ldIn, st, dev));
-    L.kfLdesc = (const uint8_t *)dev[0]; L.kfFlags = (const uint8_t *)dev[1]; L.nKf = (const int32_t *)dev[2]; L.curLdesc = (const uint8_t *)dev[3];
-    L.nCur = (const int32_t *)dev[4]; L.kfXyz = kf_line_xyz ? (const double *)dev[5] : nullptr;
-    // line_xyz is in/out (a slot without a match keeps its bytes), so it is staged first, as an input
-    const bool pose = line_xyz != nullptr;
-    void *out[4] = {line_xyz, line_has, match_out, nmatches}, *dout[4];
-    const size_t outBytes[4] = {48 * nc, nc, 4 * nc, 4 * F};
-    void *const *o = pose ? out : out + 2;
-    void **d = pose ? dout : dout + 2;
-    const size_t *ob = pose ? outBytes : outBytes + 2;
-    const int no = pose ? 4 : 2;
-    MSL_HIP_TRY(stage(o, ob, no, pose ? 1 : 0, out_mem, pose ? h->ldOut : h->ldOut + 2, st, d));
-    L.lineXyz = pose ? (double *)dout[0] : nullptr; L.lineHas = pose ? (uint8_t *)dout[1] : nullptr;
-    L.matchOut = (int32_t *)dout[2]; L.nmatches = (int32_t *)dout[3];
+    Stage S(h, mem, out_mem);
+    L.kfLdesc = S.in(kf_ldesc, 32 * nk); L.kfFlags = S.in(kf_line_flags, nk); L.nKf = S.in(n_kf_lines, F); L.curLdesc = S.in(cur_ldesc, 32 * nc);
+    L.nCur = S.in(n_cur_lines, F); L.kfXyz = S.in(kf_line_xyz, 6 * nk);
+    L.lineXyz = S.inout(line_xyz, 6 * nc);                     // in/out: a slot without a match keeps its bytes
+    L.lineHas = S.out(line_has, nc); L.matchOut = S.out(match_out, nc); L.nmatches = S.out(nmatches, F);
+    MSL_HIP_TRY(S.error());
     hipLaunchKernelGGL(k_match_ldesc, dim3((unsigned)n_pairs), dim3(LD_NT), 0, st, L);
     MSL_HIP_TRY(hipGetLastError());
-    MSL_HIP_TRY(finish_call(o, d, ob, no, mem, out_mem, st));
+    MSL_HIP_TRY(S.finish());
     return MSL_OK;
 }
 
@@ -646,9 +582,8 @@ int msl_bow_transform_batch(int device, const msl_vocab *v, int n_frames, int ca
                             msl_mem mem, int32_t *word_out, int32_t *node_out, int32_t *bow_word, double *bow_value, int32_t *n_words,
                             msl_mem out_mem) noexcept {
     try {
-    return on_default_handle(device, mem == MSL_MEM_DEVICE, [&](msl_match *h) {
-        return run_transform(h, v, n_frames, cap, levelsup, desc, n_desc, mem, word_out, node_out, bow_word, bow_value, n_words, out_mem);
-    });
+    return abi_call_default(run_transform, device, mem == MSL_MEM_DEVICE, v, n_frames, cap, levelsup, desc, n_desc, mem, word_out, node_out, bow_word,
+                            bow_value, n_words, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -656,8 +591,8 @@ int msl_match_by_bow(msl_match *h, int n_pairs, int cap, const msl_bow_match_par
                      const int32_t *kf_node, const uint8_t *kf_flags, const int32_t *n_kf, const msl_keypoint *cur_kps, const uint8_t *cur_desc,
                      const int32_t *cur_node, const int32_t *n_cur, msl_mem mem, int32_t *match_out, int32_t *nmatches, msl_mem out_mem) noexcept {
     try {
-    return run_match_bow(h, n_pairs, cap, params, kf_desc, kf_angle, kf_node, kf_flags, n_kf, cur_kps, cur_desc, cur_node, n_cur, mem, match_out,
-                         nmatches, out_mem);
+    return run_match_bow(h, n_pairs, cap, params, kf_desc, kf_angle, kf_node, kf_flags, n_kf, cur_kps, cur_desc, cur_node, n_cur, mem, match_out, nmatches,
+                         out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -666,10 +601,8 @@ int msl_match_by_bow_batch(int device, int n_pairs, int cap, const msl_bow_match
                            const uint8_t *cur_desc, const int32_t *cur_node, const int32_t *n_cur, msl_mem mem, int32_t *match_out,
                            int32_t *nmatches, msl_mem out_mem) noexcept {
     try {
-    return on_default_handle(device, mem == MSL_MEM_DEVICE, [&](msl_match *h) {
-        return run_match_bow(h, n_pairs, cap, params, kf_desc, kf_angle, kf_node, kf_flags, n_kf, cur_kps, cur_desc, cur_node, n_cur, mem,
-                             match_out, nmatches, out_mem);
-    });
+    return abi_call_default(run_match_bow, device, mem == MSL_MEM_DEVICE, n_pairs, cap, params, kf_desc, kf_angle, kf_node, kf_flags, n_kf, cur_kps, cur_desc,
+                            cur_node, n_cur, mem, match_out, nmatches, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -678,8 +611,8 @@ int msl_match_lines_by_descriptor(msl_match *h, int n_pairs, int lcap, int klcap
                                   msl_mem mem, int32_t *match_out, int32_t *nmatches, double *line_xyz, uint8_t *line_has,
                                   msl_mem out_mem) noexcept {
     try {
-    return run_match_ldesc(h, n_pairs, lcap, klcap, kf_ldesc, kf_line_flags, kf_line_xyz, n_kf_lines, cur_ldesc, n_cur_lines, mem, match_out,
-                           nmatches, line_xyz, line_has, out_mem);
+    return run_match_ldesc(h, n_pairs, lcap, klcap, kf_ldesc, kf_line_flags, kf_line_xyz, n_kf_lines, cur_ldesc, n_cur_lines, mem, match_out, nmatches,
+                           line_xyz, line_has, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -687,12 +620,10 @@ int msl_match_lines_by_descriptor_batch(int device, int n_pairs, int lcap, int k
                                         const double *kf_line_xyz, const int32_t *n_kf_lines, const uint8_t *cur_ldesc,
                                         const int32_t *n_cur_lines, msl_mem mem, int32_t *match_out, int32_t *nmatches, double *line_xyz,
                                         uint8_t *line_has, msl_mem out_mem) noexcept {
-    try {
     // line_xyz is in/out: device-memory outputs are read as well
-    return on_default_handle(device, mem == MSL_MEM_DEVICE || out_mem == MSL_MEM_DEVICE, [&](msl_match *h) {
-        return run_match_ldesc(h, n_pairs, lcap, klcap, kf_ldesc, kf_line_flags, kf_line_xyz, n_kf_lines, cur_ldesc, n_cur_lines, mem,
-                               match_out, nmatches, line_xyz, line_has, out_mem);
-    });
+    try {
+    return abi_call_default(run_match_ldesc, device, mem == MSL_MEM_DEVICE || out_mem == MSL_MEM_DEVICE, n_pairs, lcap, klcap, kf_ldesc, kf_line_flags,
+                            kf_line_xyz, n_kf_lines, cur_ldesc, n_cur_lines, mem, match_out, nmatches, line_xyz, line_has, out_mem);
     } MSL_ABI_CATCH_INT
 }
 

@@ -64,14 +64,6 @@ using PinBuf = Buf<Mem::Pinned>;
 struct Need { DevBuf &buf; size_t bytes; };
 hipError_t grow_all(hipStream_t st, std::initializer_list<Need> bufs);   // scratch: every buffer grown to its size
 
-// Device pointers dev[0 .. n) for n arrays of an entry point.  Device memory: the caller's arrays themselves.  Host memory: the handle's
-// buffers bufs[0 .. n), grown to bytes[i]; the first n_in receive the caller's contents (inputs, in/out arrays), the others are written
-// by the kernels and copied back by finish_call.
-hipError_t stage(const void *const user[], const size_t bytes[], int n, int n_in, msl_mem mem, DevBuf bufs[], hipStream_t st, void *dev[]);
-// The end of an entry point.  Host-memory outputs: dev[i] is copied back to user[i] for every non-null user[i] (a null one was not asked
-// for).  Host memory on either side: the stream is drained, so the caller's host arrays are theirs again on return.
-hipError_t finish_call(void *const user[], const void *const dev[], const size_t bytes[], int n, msl_mem mem, msl_mem out_mem, hipStream_t st);
-
 // Exception barrier of the C ABI: every extern "C" entry point is `noexcept { try { ... } MSL_ABI_CATCH_* }` -- the library uses std::vector,
 // new and std::thread behind it, and nothing may unwind into a C (cgo / JNI / ctypes) caller.
 #define MSL_ABI_CATCH_(fail)                                                                                                       \

@@ -70,26 +70,6 @@ hipError_t grow_all(hipStream_t st, std::initializer_list<Need> bufs) {
     return hipSuccess;
 }
 
-hipError_t stage(const void *const user[], const size_t bytes[], int n, int n_in, msl_mem mem, DevBuf bufs[], hipStream_t st, void *dev[]) {
-    for (int i = 0; i < n; i++) {
-        if (mem != MSL_MEM_HOST) { dev[i] = const_cast<void *>(user[i]); continue; }
-        hipError_t e = bufs[i].grow(bytes[i], st);
-        if (e == hipSuccess && i < n_in) e = hipMemcpyAsync(bufs[i].p, user[i], bytes[i], hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) return e;
-        dev[i] = bufs[i].p;
-    }
-    return hipSuccess;
-}
-
-hipError_t finish_call(void *const user[], const void *const dev[], const size_t bytes[], int n, msl_mem mem, msl_mem out_mem, hipStream_t st) {
-    for (int i = 0; out_mem == MSL_MEM_HOST && i < n; i++) {
-        if (!user[i]) continue;
-        const hipError_t e = hipMemcpyAsync(user[i], dev[i], bytes[i], hipMemcpyDeviceToHost, st);
-        if (e != hipSuccess) return e;
-    }
-    return out_mem == MSL_MEM_HOST || mem == MSL_MEM_HOST ? hipStreamSynchronize(st) : hipSuccess;
-}
-
 void KernelProfiler::begin(int k, hipStream_t s) {
     open_ = false;
     if (!on || !((mask >> k) & 1u)) return;

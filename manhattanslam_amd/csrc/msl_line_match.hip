@@ -13,9 +13,11 @@
 //                  RadiusByViewingCos * th * mvScaleFactors[level], octaves [level - 1, level].
 //   k_line_assign  one workgroup per frame: the frame's keylines (16 B) and descriptors (32 B) staged once in LDS (12 KB at lcap = 256); every
 //                  line scans them against its window (GetLinesInArea) and the reference's greedy hand-out is solved as the min-fixpoint of
-//                  k_local_assign (argument below); then holder / nmatches / nToMatch and the pose-layout line_xyz / line_has.
+//                  msl_assign.h; then nToMatch and the pose-layout line_xyz / line_has.
 // Arithmetic follows the reference's float / double mix literally (DESIGN.md section 3 lists the pins); gemm3, search_mode, hamming256 and
-// predict_level are the point matcher's (msl_match_math.h).
+// predict_level are the point matcher's (msl_match_math.h).  The optional line_xyz / line_has arrays are in/out (untouched slots keep
+// their bytes): staged from host memory like inputs, and a reason for the _batch forms to wait for the legacy stream.
+#include "msl_assign.h"
 #include "msl_match_handle.h"
 #include "msl_match_math.h"
 
@@ -29,7 +31,6 @@ namespace {
 constexpr int TH_HIGH = 100;                       // src/LSDmatcher.cpp:15
 constexpr int MAX_LCAP = 256, MAX_LLCAP = 256, MAX_MLCAP = 32768;
 constexpr int LINE_NT = 1024;
-constexpr int T_FREE = 0x7FFFFFFF;                 // t(k): no line with observations picks keyline k
 constexpr unsigned K_NONE = 0xFFFFFFFFu;
 
 // The GetLinesInArea call of one line: endpoints, radius and octave range.  ok == 0: the line has no window (skipped before the call).
@@ -54,7 +55,6 @@ struct LineDev {
     double *lineXyz; uint8_t *lineHas;              // optional, [n][lcap] in msl_pose_optimize's layout
 };
 
-__device__ __forceinline__ int clamp_level(int l, int nlevels) { return l < 0 ? 0 : (l >= nlevels ? nlevels - 1 : l); }
 __device__ __forceinline__ int wrap_add(int a, int b) { return (int)((unsigned)a + (unsigned)b); }   // x86-64's int wrap, without UB
 
 // The endpoint projection both searches share (src/LSDmatcher.cpp:43-79 = src/Frame.cc:264-297): the Vector6d converted to float as
@@ -89,7 +89,7 @@ __device__ __forceinline__ bool last_query(const LineDev &D, int f, int i, LineQ
     float SP[3], EP[3];
     if (!project_line(D.prm.base, Tc, D.xyz + ii * 6, SP, EP, q)) return false;
     const int o = D.octave[ii];
-    q.r = D.prm.base.th * D.prm.base.scale_factors[clamp_level(o, D.prm.base.nlevels)];   // :82 (octave clamped for the lookup)
+    q.r = D.prm.base.th * D.prm.base.scale_factors[clampi(o, 0, D.prm.base.nlevels - 1)];   // :82 (octave clamped for the lookup)
     const int mode = search_mode(Tc, D.TcwLast + (size_t)f * 12, D.mb);
     if (mode == 1) { q.minLevel = o; q.maxLevel = -1; }                     // :86-91, GetLinesInArea's default maxLevel = -1
     else if (mode == 2) { q.minLevel = 0; q.maxLevel = o; }
@@ -125,7 +125,7 @@ __device__ __forceinline__ bool local_query(const LineDev &D, int f, int i, Line
     t.proj_x1 = q.x1; t.proj_y1 = q.y1; t.proj_x2 = q.x2; t.proj_y2 = q.y2; t.scale_level = L; t.view_cos = viewCos;
     float r = ((double)viewCos > 0.998) ? 5.0f : 8.0f;                      // RadiusByViewingCos: float vs double constant
     if (b.th != 1.0f) r *= b.th;                                            // bFactor (:140, :149-150)
-    q.r = r * b.scale_factors[clamp_level(L, b.nlevels)];                   // :153 (level clamped for the lookup only)
+    q.r = r * b.scale_factors[clampi(L, 0, b.nlevels - 1)];                   // :153 (level clamped for the lookup only)
     q.minLevel = wrap_add(L, -1); q.maxLevel = L;
     return true;
 }
@@ -154,20 +154,10 @@ __global__ __launch_bounds__(256) void k_line_query(LineDev D) {
 // ---- k_line_assign: one workgroup per frame -----------------------------------------------------------------------------------------------------
 // The reference walks the lines in order; line i scans GetLinesInArea's indices (ascending keyline index k), skips a keyline whose
 // mvpMapLines[k] has Observations() > 0, keeps (bestDist, bestLevel, bestIdx) and (bestDist2, bestLevel2) with strict < updates from 256 / -1,
-// and writes mvpMapLines[bestIdx] = line i when bestDist <= TH_HIGH and not (bestLevel == bestLevel2 && bestDist > mfNNratio * bestDist2).
-//   * Best / second best.  With the key (dist << 16 | k), the strict-< updates leave bestIdx / bestLevel = the smallest key and
-//     bestDist2 / bestLevel2 = the second smallest among the keylines line i does not skip (distance 256 never passes < 256 and is dropped).
-//     So pick(i) is a function of the set of keylines line i skips, and of nothing else.
-//   * Line i skips k iff, when i runs, mvpMapLines[k] is a line with observations.  Keylines held with observations on entry (cur_line_flags 3,
-//     local search only) are skipped by every line (t = -1).  Otherwise let t(k) = the first line WITH observations that picks k: before t(k)
-//     only lines without observations (or the holder on entry, without observations) can have written k, so nobody skips it; from t(k) on it is
-//     held with observations, every later line skips it and nobody overwrites it.  Hence: i skips k  <=>  t(k) < i.
-//   * Uniqueness and equality with the sequential loop: pick(i) depends only on t restricted to lines < i, i.e. on pick(0 .. i-1).  By induction
-//     over i exactly one assignment satisfies "pick(i) = choice of i given the t of the picks", and it is the sequential one.
-//   * Round bound: each round recomputes every pick from the t of the previous round.  After round r the picks of lines 0 .. r-1 are final
-//     (line 0's never depends on t; line r's only on lines < r), so at most n_lines + 1 rounds run; the loop stops at the first round that
-//     changes nothing.
-//   * Holder of k = the last picker (later lines overwrite); with t(k) set nobody picks after it.  nmatches counts every accepted pick.
+// and writes mvpMapLines[bestIdx] = line i when bestDist <= TH_HIGH and not (bestLevel == bestLevel2 && bestDist > mfNNratio * bestDist2):
+// the greedy hand-out of msl_assign.h with lines as queries and keylines as targets.  With the key (dist << 16 | k), the strict-< updates
+// leave bestIdx / bestLevel = the smallest key and bestDist2 / bestLevel2 = the second smallest among the keylines line i does not skip
+// (distance 256 never passes < 256 and is dropped), so pick(i) is a function of the set of keylines line i skips, as the hand-out requires.
 // LDS: keylines 4 KB + descriptors 8 KB + t 1 KB static, pick[ncap] short dynamic (64 KB at mlcap = 32768): 77 KB at the limits.
 template <bool LOCAL>
 __global__ __launch_bounds__(LINE_NT) void k_line_assign(LineDev D) {
@@ -175,29 +165,22 @@ __global__ __launch_bounds__(LINE_NT) void k_line_assign(LineDev D) {
     __shared__ uint4 s_desc[2 * MAX_LCAP];
     __shared__ int s_t[MAX_LCAP];
     __shared__ int s_nm, s_ntm;
-    extern __shared__ short s_pick[];               // [ncap]: the keyline line i picks, -1 = none, -2 = not evaluated yet
+    extern __shared__ short s_pick[];               // [ncap]
     const int f = blockIdx.x;
     const int nCur = min(max(D.nCur[f], 0), D.lcap), nL = min(max(D.nLines[f], 0), D.ncap);
     const size_t kb = (size_t)f * D.lcap, lb = (size_t)f * D.ncap;
     for (int k = threadIdx.x; k < nCur; k += LINE_NT) {
         s_kl[k] = D.curKl[kb + k];
-        const uint4 *d = reinterpret_cast<const uint4 *>(D.curDesc + (kb + k) * 32);
-        s_desc[2 * k] = d[0]; s_desc[2 * k + 1] = d[1];
+        load_desc(D.curDesc + (kb + k) * 32, s_desc[2 * k], s_desc[2 * k + 1]);
     }
-    auto reset_t = [&]() {
-        for (int k = threadIdx.x; k < nCur; k += LINE_NT) s_t[k] = (LOCAL && (D.curFlags[kb + k] & 3) == 3) ? -1 : T_FREE;
-    };
-    reset_t();
-    for (int i = threadIdx.x; i < nL; i += LINE_NT) s_pick[i] = -2;
-    if (threadIdx.x == 0) { s_nm = 0; s_ntm = 0; }
-    __syncthreads();
+    if (threadIdx.x == 0) s_ntm = 0;
 
     // line i's choice given the current t: GetLinesInArea (src/Frame.cc:384-415) over the keylines it does not skip, then :117-129 / :183-191
     auto pick_of = [&](int i) -> int {
         const LineQ q = D.q[lb + i];
         if (!q.ok) return -1;
-        const uint4 *dq = reinterpret_cast<const uint4 *>(D.desc + (lb + i) * 32);
-        const uint4 d0 = dq[0], d1 = dq[1];
+        uint4 d0, d1;
+        load_desc(D.desc + (lb + i) * 32, d0, d1);
         const double mx = 0.5 * (double)(q.x1 + q.x2), my = 0.5 * (double)(q.y1 + q.y2);   // float sums, then double
         const float slope0 = (q.y1 - q.y2) / (q.x1 - q.x2);
         const float rr = q.r * q.r;
@@ -217,11 +200,7 @@ __global__ __launch_bounds__(LINE_NT) void k_line_assign(LineDev D) {
                 if (q.maxLevel >= 0 && kl.octave > q.maxLevel) continue;
             }
             const int dist = hamming256(d0, d1, s_desc[2 * k], s_desc[2 * k + 1]);
-            if (dist < 256) {                                               // the two smallest keys so far, b1 < b2 (branch-free: no private array)
-                const unsigned key = ((unsigned)dist << 16) | (unsigned)k;
-                b2 = min(b2, max(key, b1));
-                b1 = min(b1, key);
-            }
+            if (dist < 256) two_smallest(((unsigned)dist << 16) | (unsigned)k, b1, b2);
         }
         if (b1 == K_NONE) return -1;
         const int bestDist = (int)(b1 >> 16);
@@ -232,34 +211,15 @@ __global__ __launch_bounds__(LINE_NT) void k_line_assign(LineDev D) {
         if (bestLevel == bestLevel2 && (float)bestDist > D.prm.nn_ratio * (float)bestDist2) return -1;
         return (int)(b1 & 0xFFFFu);
     };
-
-    for (int round = 0; round <= nL; round++) {
-        bool changed = false;
-        for (int i = threadIdx.x; i < nL; i += LINE_NT) {
-            const int np = pick_of(i);
-            changed |= np != s_pick[i];
-            s_pick[i] = (short)np;
-        }
-        if (!__syncthreads_or(changed ? 1 : 0)) break;
-        reset_t();
-        __syncthreads();
-        for (int i = threadIdx.x; i < nL; i += LINE_NT)
-            if (s_pick[i] >= 0 && (D.flags[lb + i] & 2)) atomicMin(&s_t[s_pick[i]], i);
+    // keylines held with observations on entry (cur_line_flags 3, local search only) are skipped by every line
+    greedy_assign<LINE_NT>(nL, nCur, s_t, s_pick, &s_nm, pick_of, [&](int i) { return (D.flags[lb + i] & 2) != 0; },
+                           [&](int k) { return (LOCAL && (D.curFlags[kb + k] & 3) == 3) ? -1 : T_FREE; });
+    if (LOCAL) {
+        int ntm = 0;
+        for (int i = threadIdx.x; i < nL; i += LINE_NT) ntm += D.inView[lb + i];
+        if (ntm) atomicAdd(&s_ntm, ntm);
         __syncthreads();
     }
-    // holder = the last line that picked the keyline; t(.) is no longer needed and its storage holds it
-    __syncthreads();
-    for (int k = threadIdx.x; k < nCur; k += LINE_NT) s_t[k] = -1;
-    __syncthreads();
-    int nm = 0, ntm = 0;
-    for (int i = threadIdx.x; i < nL; i += LINE_NT) {
-        const int pk = s_pick[i];
-        if (pk >= 0) { atomicMax(&s_t[pk], i); nm++; }
-        if (LOCAL) ntm += D.inView[lb + i];
-    }
-    if (nm) atomicAdd(&s_nm, nm);
-    if (ntm) atomicAdd(&s_ntm, ntm);
-    __syncthreads();
     for (int k = threadIdx.x; k < D.lcap; k += LINE_NT) {
         const int h = k < nCur ? s_t[k] : -1;
         D.matchOut[kb + k] = h;
@@ -278,30 +238,14 @@ __global__ __launch_bounds__(LINE_NT) void k_line_assign(LineDev D) {
     }
 }
 
+// Whether a _batch form reads device memory the caller may still have enqueued on the legacy stream: its inputs, or the in/out line_xyz /
+// line_has (they live in out_mem memory).
+bool reads_device(msl_mem mem, const double *line_xyz, const uint8_t *line_has, msl_mem out_mem) {
+    return mem == MSL_MEM_DEVICE || ((line_xyz || line_has) && out_mem == MSL_MEM_DEVICE);
+}
+
 bool bad_base(const msl_match_params &b) {
     return b.nlevels < 1 || b.nlevels > MSL_MATCH_MAX_LEVELS || !(b.maxX > b.minX) || !(b.maxY > b.minY) || b.fx == 0;
-}
-
-// The optional line_xyz / line_has arrays are in/out (untouched slots keep their bytes): staged from host memory like inputs.
-hipError_t stage_line_io(msl_match *h, double *line_xyz, uint8_t *line_has, size_t l, msl_mem out_mem, void *user[2], void *dev[2],
-                         size_t bytes[2]) {
-    user[0] = line_xyz; user[1] = line_has; bytes[0] = sizeof(double) * 6 * l; bytes[1] = l;
-    for (int i = 0; i < 2; i++) {
-        dev[i] = nullptr;
-        if (!user[i]) continue;
-        const hipError_t e = stage(&user[i], &bytes[i], 1, 1, out_mem, &h->lineIo[i], h->stream, &dev[i]);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-hipError_t set_assign_lds(msl_match *h) {
-    if (h->lineAttrSet) return hipSuccess;
-    hipError_t e = hipFuncSetAttribute((const void *)k_line_assign<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(short) * MAX_LLCAP));
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void *)k_line_assign<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(short) * MAX_MLCAP));
-    if (e == hipSuccess) h->lineAttrSet = true;
-    return e;
 }
 
 int run_lines_last(msl_match *h, int n_frames, int lcap, int llcap, const msl_line_match_params *params, const msl_keyline *cur_kl,
@@ -318,32 +262,22 @@ int run_lines_last(msl_match *h, int n_frames, int lcap, int llcap, const msl_li
     if (rc != MSL_OK) return rc;
     hipStream_t st = h->stream;
     const size_t F = (size_t)n_frames, l = F * lcap, n = F * llcap;
+    Stage S(h, mem, out_mem);
     LineDev D{};
     D.lcap = lcap; D.ncap = llcap; D.prm = *params; D.mb = params->base.bf / params->base.fx;   // src/Frame.cc:150
-    const void *src[10] = {cur_kl, cur_ldesc, n_cur_lines, last_line_xyz, last_ldesc, last_line_flags, last_line_octave, n_last_lines, Tcw_cur, Tcw_last};
-    const size_t bytes[10] = {sizeof(msl_keyline) * l, 32 * l, 4 * F, sizeof(double) * 6 * n, 32 * n, n, 4 * n, 4 * F, 48 * F, 48 * F};
-    void *dev[10];
-    MSL_HIP_TRY(stage(src, bytes, 10, 10, mem, h->lineIn, st, dev));
-    D.curKl = (const msl_keyline *)dev[0]; D.curDesc = (const uint8_t *)dev[1]; D.nCur = (const int32_t *)dev[2]; D.xyz = (const double *)dev[3];
-    D.desc = (const uint8_t *)dev[4]; D.flags = (const uint8_t *)dev[5]; D.octave = (const int32_t *)dev[6]; D.nLines = (const int32_t *)dev[7];
-    D.TcwCur = (const float *)dev[8]; D.TcwLast = (const float *)dev[9];
+    D.curKl = S.in(cur_kl, l); D.curDesc = S.in(cur_ldesc, 32 * l); D.nCur = S.in(n_cur_lines, F); D.xyz = S.in(last_line_xyz, 6 * n);
+    D.desc = S.in(last_ldesc, 32 * n); D.flags = S.in(last_line_flags, n); D.octave = S.in(last_line_octave, n); D.nLines = S.in(n_last_lines, F);
+    D.TcwCur = S.in(Tcw_cur, 12 * F); D.TcwLast = S.in(Tcw_last, 12 * F);
+    D.matchOut = S.out(match_out, l); D.nmatches = S.out(nmatches, F);
+    D.lineXyz = S.inout(line_xyz, 6 * l); D.lineHas = S.inout(line_has, l);
+    MSL_HIP_TRY(S.error());
     MSL_HIP_TRY(grow_all(st, {{h->lineQ, sizeof(LineQ) * n}}));
     D.q = (LineQ *)h->lineQ.p;
-    void *out[2] = {match_out, nmatches}, *dout[2];
-    const size_t outBytes[2] = {sizeof(int32_t) * l, sizeof(int32_t) * F};
-    MSL_HIP_TRY(stage(out, outBytes, 2, 0, out_mem, h->out, st, dout));
-    D.matchOut = (int32_t *)dout[0]; D.nmatches = (int32_t *)dout[1];
-    void *io[2], *dio[2]; size_t ioBytes[2];
-    MSL_HIP_TRY(stage_line_io(h, line_xyz, line_has, l, out_mem, io, dio, ioBytes));
-    D.lineXyz = (double *)dio[0]; D.lineHas = (uint8_t *)dio[1];
-    MSL_HIP_TRY(set_assign_lds(h));
+    MSL_HIP_TRY(allow_lds(h, LDS_LINE_ASSIGN_LAST, k_line_assign<false>, sizeof(short) * MAX_LLCAP));
     hipLaunchKernelGGL(k_line_query<false>, dim3((unsigned)((llcap + 255) / 256), (unsigned)n_frames), dim3(256), 0, st, D);
     hipLaunchKernelGGL(k_line_assign<false>, dim3((unsigned)n_frames), dim3(LINE_NT), sizeof(short) * llcap, st, D);
     MSL_HIP_TRY(hipGetLastError());
-    void *user[4] = {match_out, nmatches, io[0], io[1]};
-    const void *devp[4] = {dout[0], dout[1], dio[0], dio[1]};
-    const size_t ub[4] = {outBytes[0], outBytes[1], ioBytes[0], ioBytes[1]};
-    MSL_HIP_TRY(finish_call(user, devp, ub, 4, mem, out_mem, st));
+    MSL_HIP_TRY(S.finish());
     return MSL_OK;
 }
 
@@ -363,35 +297,23 @@ int run_lines_local(msl_match *h, int n_frames, int lcap, int mlcap, const msl_l
     if (rc != MSL_OK) return rc;
     hipStream_t st = h->stream;
     const size_t F = (size_t)n_frames, l = F * lcap, m = F * mlcap;
+    Stage S(h, mem, out_mem);
     LineDev D{};
     D.lcap = lcap; D.ncap = mlcap; D.prm = *params;
-    const void *src[11] = {cur_kl, cur_ldesc, n_cur_lines, cur_line_flags, ml_xyz, ml_normal, ml_dist, ml_desc, ml_flags, n_local_lines, Tcw};
-    const size_t bytes[11] = {sizeof(msl_keyline) * l, 32 * l, 4 * F, l, sizeof(double) * 6 * m, sizeof(double) * 3 * m, 8 * m, 32 * m, m, 4 * F, 48 * F};
-    void *dev[11];
-    MSL_HIP_TRY(stage(src, bytes, 11, 11, mem, h->lineIn, st, dev));
-    D.curKl = (const msl_keyline *)dev[0]; D.curDesc = (const uint8_t *)dev[1]; D.nCur = (const int32_t *)dev[2]; D.curFlags = (const uint8_t *)dev[3];
-    D.xyz = (const double *)dev[4]; D.normal = (const double *)dev[5]; D.dist = (const float *)dev[6]; D.desc = (const uint8_t *)dev[7];
-    D.flags = (const uint8_t *)dev[8]; D.nLines = (const int32_t *)dev[9]; D.TcwCur = (const float *)dev[10];
+    D.curKl = S.in(cur_kl, l); D.curDesc = S.in(cur_ldesc, 32 * l); D.nCur = S.in(n_cur_lines, F); D.curFlags = S.in(cur_line_flags, l);
+    D.xyz = S.in(ml_xyz, 6 * m); D.normal = S.in(ml_normal, 3 * m); D.dist = S.in(ml_dist, 2 * m); D.desc = S.in(ml_desc, 32 * m);
+    D.flags = S.in(ml_flags, m); D.nLines = S.in(n_local_lines, F); D.TcwCur = S.in(Tcw, 12 * F);
+    D.matchOut = S.out(match_out, l); D.nmatches = S.out(nmatches, F); D.nToMatch = S.out(n_to_match, F);
+    D.lineXyz = S.inout(line_xyz, 6 * l); D.lineHas = S.inout(line_has, l);
+    MSL_HIP_TRY(S.error());
     MSL_HIP_TRY(grow_all(st, {{h->lineQ, sizeof(LineQ) * m}, {h->lineTrk, sizeof(msl_line_track) * m}, {h->lineView, m}}));
     D.q = (LineQ *)h->lineQ.p; D.track = (msl_line_track *)h->lineTrk.p; D.inView = (uint8_t *)h->lineView.p;
-    void *out[3] = {match_out, nmatches, n_to_match}, *dout[3];
-    const size_t outBytes[3] = {sizeof(int32_t) * l, sizeof(int32_t) * F, sizeof(int32_t) * F};
-    MSL_HIP_TRY(stage(out, outBytes, 3, 0, out_mem, h->out, st, dout));
-    D.matchOut = (int32_t *)dout[0]; D.nmatches = (int32_t *)dout[1]; D.nToMatch = (int32_t *)dout[2];
-    // the optional in_view / track: the kernels write device-memory ones, host-memory ones are copied back from the scratch
-    const bool devOut = out_mem != MSL_MEM_HOST;
-    D.inViewOut = devOut ? in_view : nullptr; D.trackOut = devOut ? track : nullptr;
-    void *io[2], *dio[2]; size_t ioBytes[2];
-    MSL_HIP_TRY(stage_line_io(h, line_xyz, line_has, l, out_mem, io, dio, ioBytes));
-    D.lineXyz = (double *)dio[0]; D.lineHas = (uint8_t *)dio[1];
-    MSL_HIP_TRY(set_assign_lds(h));
+    D.inViewOut = S.out_of_scratch(in_view, D.inView, m); D.trackOut = S.out_of_scratch(track, D.track, m);   // the optional in_view / track
+    MSL_HIP_TRY(allow_lds(h, LDS_LINE_ASSIGN_LOCAL, k_line_assign<true>, sizeof(short) * MAX_MLCAP));
     hipLaunchKernelGGL(k_line_query<true>, dim3((unsigned)((mlcap + 255) / 256), (unsigned)n_frames), dim3(256), 0, st, D);
     hipLaunchKernelGGL(k_line_assign<true>, dim3((unsigned)n_frames), dim3(LINE_NT), sizeof(short) * mlcap, st, D);
     MSL_HIP_TRY(hipGetLastError());
-    void *user[7] = {match_out, nmatches, n_to_match, in_view, track, io[0], io[1]};
-    const void *devp[7] = {dout[0], dout[1], dout[2], D.inView, D.track, dio[0], dio[1]};
-    const size_t ub[7] = {outBytes[0], outBytes[1], outBytes[2], m, sizeof(msl_line_track) * m, ioBytes[0], ioBytes[1]};
-    MSL_HIP_TRY(finish_call(user, devp, ub, 7, mem, out_mem, st));
+    MSL_HIP_TRY(S.finish());
     return MSL_OK;
 }
 
@@ -416,10 +338,9 @@ int msl_match_lines_by_projection_batch(int device, int n_frames, int lcap, int 
                                         const float *Tcw_cur, const float *Tcw_last, msl_mem mem, int32_t *match_out, int32_t *nmatches,
                                         double *line_xyz, uint8_t *line_has, msl_mem out_mem) noexcept {
     try {
-    return on_default_handle(device, mem == MSL_MEM_DEVICE, [&](msl_match *h) {
-        return run_lines_last(h, n_frames, lcap, llcap, params, cur_kl, cur_ldesc, n_cur_lines, last_line_xyz, last_ldesc, last_line_flags,
-                              last_line_octave, n_last_lines, Tcw_cur, Tcw_last, mem, match_out, nmatches, line_xyz, line_has, out_mem);
-    });
+    return abi_call_default(run_lines_last, device, reads_device(mem, line_xyz, line_has, out_mem), n_frames, lcap, llcap, params, cur_kl, cur_ldesc,
+                            n_cur_lines, last_line_xyz, last_ldesc, last_line_flags, last_line_octave, n_last_lines, Tcw_cur, Tcw_last, mem, match_out,
+                            nmatches, line_xyz, line_has, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -429,8 +350,8 @@ int msl_match_local_lines(msl_match *h, int n_frames, int lcap, int mlcap, const
                           const float *Tcw, msl_mem mem, int32_t *match_out, int32_t *n_to_match, int32_t *nmatches, uint8_t *in_view,
                           msl_line_track *track, double *line_xyz, uint8_t *line_has, msl_mem out_mem) noexcept {
     try {
-    return run_lines_local(h, n_frames, lcap, mlcap, params, cur_kl, cur_ldesc, n_cur_lines, cur_line_flags, ml_xyz, ml_normal, ml_dist, ml_desc,
-                           ml_flags, n_local_lines, Tcw, mem, match_out, n_to_match, nmatches, in_view, track, line_xyz, line_has, out_mem);
+    return run_lines_local(h, n_frames, lcap, mlcap, params, cur_kl, cur_ldesc, n_cur_lines, cur_line_flags, ml_xyz, ml_normal, ml_dist, ml_desc, ml_flags,
+                           n_local_lines, Tcw, mem, match_out, n_to_match, nmatches, in_view, track, line_xyz, line_has, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -440,10 +361,9 @@ int msl_match_local_lines_batch(int device, int n_frames, int lcap, int mlcap, c
                                 const int32_t *n_local_lines, const float *Tcw, msl_mem mem, int32_t *match_out, int32_t *n_to_match, int32_t *nmatches,
                                 uint8_t *in_view, msl_line_track *track, double *line_xyz, uint8_t *line_has, msl_mem out_mem) noexcept {
     try {
-    return on_default_handle(device, mem == MSL_MEM_DEVICE, [&](msl_match *h) {
-        return run_lines_local(h, n_frames, lcap, mlcap, params, cur_kl, cur_ldesc, n_cur_lines, cur_line_flags, ml_xyz, ml_normal, ml_dist, ml_desc,
-                               ml_flags, n_local_lines, Tcw, mem, match_out, n_to_match, nmatches, in_view, track, line_xyz, line_has, out_mem);
-    });
+    return abi_call_default(run_lines_local, device, reads_device(mem, line_xyz, line_has, out_mem), n_frames, lcap, mlcap, params, cur_kl, cur_ldesc,
+                            n_cur_lines, cur_line_flags, ml_xyz, ml_normal, ml_dist, ml_desc, ml_flags, n_local_lines, Tcw, mem, match_out, n_to_match,
+                            nmatches, in_view, track, line_xyz, line_has, out_mem);
     } MSL_ABI_CATCH_INT
 }
 

@@ -14,14 +14,15 @@
 //                       ascending cell id and a cell's items in insertion order, so "first candidate wins ties" (:635) is the
 //                       minimum of that packed key and the candidates need not be stored in order;
 //   k_match_assign      one workgroup per pair: the reference's greedy, order dependent assignment (:621-623: a candidate held by
-//                       a point with Observations() > 0 is skipped; :638: later points overwrite earlier ones) as a min-fixpoint:
-//                       t(i2) = first point with observations that picks i2; point i skips candidates with t < i.  By induction
-//                       over i the fixpoint is unique and equals the sequential result; it is reached in a handful of rounds
-//                       (bounded by n_last).  Then holder = last picker, rotation histogram, three maxima, NULLing (:657-674).
+//                       a point with Observations() > 0 is skipped; :638: later points overwrite earlier ones) as the min-fixpoint
+//                       of msl_assign.h (greedy_assign: round loop, holder = last picker, match count; the argument is there).
+//                       Then rotation histogram, three maxima, NULLing (:657-674; rotation_cull in msl_match_math.h).
 //
 // Integer / byte work, L2-resident gathers; no MFMA.  The float expressions keep the reference's order; the 3x3 cv::Mat products
 // follow cv::gemm's float kernel (double accumulation, one rounding) -- pinned in DESIGN.md section 3; gemm3, the search mode, the popcount
-// and predict_scale live in msl_match_math.h, shared with the line matcher (msl_line_match.hip).
+// and predict_scale live in msl_match_math.h, shared with the line matcher (msl_line_match.hip).  This file also defines msl::Stage
+// (msl_match_handle.h), the staging of host-memory arguments every entry point on the handle uses.
+#include "msl_assign.h"
 #include "msl_match_handle.h"
 #include "msl_match_math.h"
 
@@ -41,7 +42,8 @@ constexpr int TH_HIGH = 100, HISTO_LENGTH = 30;     // src/ORBmatcher.cc:33-35
 static_assert(HISTO_LENGTH == ROT_HISTO_LENGTH, "rot_bin / three_maxima (msl_match_math.h) use the same histogram");
 constexpr int CMAX = 32;                            // stored candidates per point; more are re-enumerated by k_match_assign
 constexpr int MAX_CAP = 8192;
-constexpr unsigned T_NONE = 0xFFFFFFFFu;
+constexpr unsigned KEY_NONE = 0xFFFFFFFFu;          // no candidate key (dist << 16 | item position)
+constexpr int DIST_ANY = 257, DIST_BELOW_256 = 256; // distance caps of a candidate: the local search drops 256 (never best nor second)
 
 struct MatchDev {
     int nPairs, cap;
@@ -161,25 +163,42 @@ __device__ __forceinline__ int eval_item(const MatchDev &P, int pair, const Quer
         const float er = fabsf(Q.ur - uRight);
         if (er > Q.radius) return -1;
     }
-    const uint4 *dp = reinterpret_cast<const uint4 *>(P.curDesc + base * 32);
-    const uint4 e0 = dp[0], e1 = dp[1];
+    uint4 e0, e1;
+    load_desc(P.curDesc + base * 32, e0, e1);
     return hamming256(d0, d1, e0, e1);
+}
+
+// The window of Q holds window_cells(Q) cells; cell c of them in the reference's walk order (ascending ix, then iy) holds the item
+// positions [b, e), which ascend in that order too (a cell's items in mGrid insertion order).
+__device__ __forceinline__ int window_cells(const Query &Q) { return (Q.maxCX - Q.minCX + 1) * (Q.maxCY - Q.minCY + 1); }
+__device__ __forceinline__ void window_cell(const MatchDev &P, int pair, const Query &Q, int c, unsigned &b, unsigned &e) {
+    const int ny = Q.maxCY - Q.minCY + 1;
+    const unsigned *cs = P.cellStart + (size_t)pair * (NCELLS + 1) + (Q.minCX + c / ny) * GRID_ROWS + Q.minCY + c % ny;
+    b = cs[0]; e = cs[1];
+}
+
+// The window walked by one thread in reference order: item(p) for every item position p.
+template <class Item>
+__device__ __forceinline__ void walk_window(const MatchDev &P, int pair, const Query &Q, Item item) {
+    const int C = window_cells(Q);
+    for (int c = 0; c < C; c++) {
+        unsigned b, e;
+        window_cell(P, pair, Q, c, b, e);
+        for (unsigned p = b; p < e; p++) item(p);
+    }
 }
 
 // The window of Q walked by one wave (cells spread over the lanes): every item that passes eval_item with a distance below distCap is
 // stored as (dist << 16 | item position), the first CMAX of them in cand; *cnt (wave-shared, zero on entry) ends as the total.
 __device__ __forceinline__ void wave_candidates(const MatchDev &P, int pair, const Query &Q, const uint8_t *desc32, int distCap, unsigned *cand,
                                                 unsigned *cnt, int lane) {
-    const uint4 *dq = reinterpret_cast<const uint4 *>(desc32);
-    const uint4 d0 = dq[0], d1 = dq[1];
-    const unsigned *cellStart = P.cellStart + (size_t)pair * (NCELLS + 1);
+    uint4 d0, d1;
+    load_desc(desc32, d0, d1);
     const unsigned short *items = P.items + (size_t)pair * P.cap;
-    const int ny = Q.maxCY - Q.minCY + 1, C = (Q.maxCX - Q.minCX + 1) * ny;
-    for (int c0 = 0; c0 < C; c0 += 64) {
-        const int c = c0 + lane;
-        if (c >= C) continue;
-        const int cellId = (Q.minCX + c / ny) * GRID_ROWS + Q.minCY + c % ny;
-        const unsigned b = cellStart[cellId], e = cellStart[cellId + 1];
+    const int C = window_cells(Q);
+    for (int c = lane; c < C; c += 64) {
+        unsigned b, e;
+        window_cell(P, pair, Q, c, b, e);
         for (unsigned p = b; p < e; p++) {
             const int dist = eval_item(P, pair, Q, items[p], d0, d1);
             if (dist < 0 || dist >= distCap) continue;
@@ -188,6 +207,35 @@ __device__ __forceinline__ void wave_candidates(const MatchDev &P, int pair, con
         }
     }
     __builtin_amdgcn_wave_barrier();
+}
+
+// Every candidate key (dist << 16 | item position) of query q (row qi of cand / candCnt) that q does not skip under s_t (msl_assign.h),
+// to offer(key): the stored candidates, or, when the wave found more than the CMAX it stored, the window of make_query(Q) walked again
+// with the filters of wave_candidates (rare; any count stays exact).
+template <class MakeQuery, class Offer>
+__device__ __forceinline__ void unskipped_candidates(const MatchDev &P, int pair, size_t qi, int q, const uint8_t *desc32, int distCap, const int *s_t,
+                                                     MakeQuery make_query, Offer offer) {
+    const unsigned short *items = P.items + (size_t)pair * P.cap;
+    const unsigned cnt = P.candCnt[qi];
+    if (cnt <= CMAX) {
+        const unsigned *cand = P.cand + qi * CMAX;
+        for (unsigned k = 0; k < cnt; k++) {
+            const unsigned key = cand[k];
+            if (s_t[items[key & 0xFFFFu]] < q) continue;
+            offer(key);
+        }
+        return;
+    }
+    Query Q;
+    if (!make_query(Q)) return;
+    uint4 d0, d1;
+    load_desc(desc32, d0, d1);
+    walk_window(P, pair, Q, [&](unsigned p) {
+        const unsigned i2 = items[p];
+        if (s_t[i2] < q) return;
+        const int dist = eval_item(P, pair, Q, i2, d0, d1);
+        if (dist >= 0 && dist < distCap) offer(((unsigned)dist << 16) | p);
+    });
 }
 
 // ---- k_match_candidates: one wave per last-frame point ----------------------------------------------------------------------
@@ -205,7 +253,7 @@ __global__ __launch_bounds__(256) void k_match_candidates(MatchDev P) {
         if (lane == 0) P.candCnt[qi] = 0;
         return;
     }
-    wave_candidates(P, pair, Q, P.lastDesc + qi * 32, 257, P.cand + qi * CMAX, &s_cnt[wv], lane);
+    wave_candidates(P, pair, Q, P.lastDesc + qi * 32, DIST_ANY, P.cand + qi * CMAX, &s_cnt[wv], lane);
     if (lane == 0) P.candCnt[qi] = s_cnt[wv];
 }
 
@@ -213,100 +261,35 @@ __global__ __launch_bounds__(256) void k_match_candidates(MatchDev P) {
 constexpr int ASSIGN_NT = 1024;
 
 __global__ __launch_bounds__(ASSIGN_NT) void k_match_assign(MatchDev P) {
-    extern __shared__ unsigned s_dyn[];     // t[cap] | holder[cap] | pick[cap]
+    extern __shared__ int s_dyn[];          // t[cap], then the holder | rotation bin[cap] | pick[cap] short (inside the third int[cap])
     __shared__ int s_hist[HISTO_LENGTH], s_keep[3], s_nm;
     const int pair = blockIdx.x;
     const int nLast = min(P.nLast[pair], P.cap), nCur = min(P.nCur[pair], P.cap), mode = P.mode[pair];
-    unsigned *s_t = s_dyn;
-    int *s_holder = reinterpret_cast<int *>(s_dyn + P.cap);
-    int *s_pick = reinterpret_cast<int *>(s_dyn + 2 * P.cap);   // current-frame keypoint picked by each point, -1 = none
+    int *s_t = s_dyn, *s_bin = s_dyn + P.cap;
+    short *s_pick = reinterpret_cast<short *>(s_dyn + 2 * P.cap);   // current-frame keypoint picked by each point, -1 = none
     const unsigned short *items = P.items + (size_t)pair * P.cap;
-    for (int i = threadIdx.x; i < P.cap; i += ASSIGN_NT) { s_t[i] = T_NONE; s_holder[i] = -1; }
+    const size_t base = (size_t)pair * P.cap;
     if (threadIdx.x < HISTO_LENGTH) s_hist[threadIdx.x] = 0;
-    if (threadIdx.x == 0) s_nm = 0;
-    __syncthreads();
 
-    // best unblocked candidate of point q: minimum of (dist << 16 | item position); 0xFFFFFFFF = none
-    auto best_of = [&](int q) -> unsigned {
-        const size_t qi = (size_t)pair * P.cap + q;
-        const unsigned cnt = P.candCnt[qi];
-        unsigned best = T_NONE;
-        if (cnt == 0) return best;
-        if (cnt <= CMAX) {
-            const unsigned *cand = P.cand + qi * CMAX;
-            for (unsigned k = 0; k < cnt; k++) {
-                const unsigned key = cand[k];
-                if (s_t[items[key & 0xFFFFu]] < (unsigned)q) continue;   // held by an earlier point with observations (:621-623)
-                best = min(best, key);
-            }
-            return best;
-        }
-        // more candidates than stored: walk the window again (rare; any count stays exact)
-        Query Q;
-        if (!project_query(P, pair, q, mode, Q)) return best;
-        const uint4 *dq = reinterpret_cast<const uint4 *>(P.lastDesc + qi * 32);
-        const uint4 d0 = dq[0], d1 = dq[1];
-        const unsigned *cellStart = P.cellStart + (size_t)pair * (NCELLS + 1);
-        for (int ix = Q.minCX; ix <= Q.maxCX; ix++)
-            for (int iy = Q.minCY; iy <= Q.maxCY; iy++) {
-                const unsigned b = cellStart[ix * GRID_ROWS + iy], e = cellStart[ix * GRID_ROWS + iy + 1];
-                for (unsigned p = b; p < e; p++) {
-                    const unsigned i2 = items[p];
-                    if (s_t[i2] < (unsigned)q) continue;
-                    const int dist = eval_item(P, pair, Q, i2, d0, d1);
-                    if (dist >= 0) best = min(best, ((unsigned)dist << 16) | p);
-                }
-            }
-        return best;
+    // point q's choice given the current t: the minimum of (dist << 16 | item position) over the candidates it does not skip, bestDist <= TH_HIGH (:637)
+    auto pick_of = [&](int q) -> int {
+        unsigned best = KEY_NONE;
+        unskipped_candidates(P, pair, base + q, q, P.lastDesc + (base + q) * 32, DIST_ANY, s_t,
+                             [&](Query &Q) { return project_query(P, pair, q, mode, Q); }, [&](unsigned key) { best = min(best, key); });
+        return (best != KEY_NONE && (int)(best >> 16) <= TH_HIGH) ? (int)items[best & 0xFFFFu] : -1;
     };
-
-    for (int q = threadIdx.x; q < nLast; q += ASSIGN_NT) s_pick[q] = -2;      // -2: not evaluated yet (forces a first round)
-    for (int round = 0; round <= nLast; round++) {
-        bool changed = false;
-        for (int q = threadIdx.x; q < nLast; q += ASSIGN_NT) {
-            const unsigned key = best_of(q);
-            const int np = (key != T_NONE && (int)(key >> 16) <= TH_HIGH) ? (int)items[key & 0xFFFFu] : -1;   // bestDist <= TH_HIGH (:637)
-            changed |= np != s_pick[q];
-            s_pick[q] = np;
-        }
-        if (!__syncthreads_or(changed ? 1 : 0)) break;
-        for (int i = threadIdx.x; i < nCur; i += ASSIGN_NT) s_t[i] = T_NONE;
-        __syncthreads();
+    // the greedy hand-out of :621-623 / :638 (msl_assign.h); nothing is held on entry
+    greedy_assign<ASSIGN_NT>(nLast, nCur, s_t, s_pick, &s_nm, pick_of, [&](int q) { return (P.lastFlags[base + q] & 2) != 0; },
+                             [](int) { return T_FREE; });
+    if (P.prm.check_orientation) {          // rotation histogram, three maxima, NULLing (:643-649, :657-674)
         for (int q = threadIdx.x; q < nLast; q += ASSIGN_NT)
-            if (s_pick[q] >= 0 && (P.lastFlags[(size_t)pair * P.cap + q] & 2)) atomicMin(&s_t[s_pick[q]], (unsigned)q);
-        __syncthreads();
+            s_bin[q] = s_pick[q] >= 0 ? rot_bin(P.lastAngle[base + q] - P.curKps[base + s_pick[q]].angle) : -1;
+        rotation_cull<ASSIGN_NT>(nLast, s_hist, s_keep, [&](int q) { return s_bin[q]; }, [&](int q) {
+            s_t[s_pick[q]] = -1;
+            atomicSub(&s_nm, 1);
+        });
     }
-    // holder = the last point that picked the keypoint (:638 overwrites); nmatches counts every assignment (:639).
-    // t(.) is no longer needed: its storage now holds each point's rotation bin (-1 = no match).
-    __syncthreads();
-    int *s_bin = reinterpret_cast<int *>(s_t);
-    for (int q = threadIdx.x; q < nLast; q += ASSIGN_NT) {
-        int b = -1;
-        const int pk = s_pick[q];
-        if (pk >= 0) {
-            atomicMax(&s_holder[pk], q);
-            atomicAdd(&s_nm, 1);
-            if (P.prm.check_orientation) {
-                b = rot_bin(P.lastAngle[(size_t)pair * P.cap + q] - P.curKps[(size_t)pair * P.cap + pk].angle);   // :643-649
-                if (b >= 0) atomicAdd(&s_hist[b], 1);
-            }
-        }
-        s_bin[q] = b;
-    }
-    __syncthreads();
-    if (P.prm.check_orientation) {
-        if (threadIdx.x == 0) three_maxima(s_hist, s_keep);   // ComputeThreeMaxima (:799-830)
-        __syncthreads();
-        for (int q = threadIdx.x; q < nLast; q += ASSIGN_NT) {
-            const int b = s_bin[q];
-            if (b >= 0 && b != s_keep[0] && b != s_keep[1] && b != s_keep[2]) {   // :664-672
-                s_holder[s_pick[q]] = -1;
-                atomicSub(&s_nm, 1);
-            }
-        }
-        __syncthreads();
-    }
-    for (int i = threadIdx.x; i < P.cap; i += ASSIGN_NT) P.matchOut[(size_t)pair * P.cap + i] = i < nCur ? s_holder[i] : -1;
+    for (int i = threadIdx.x; i < P.cap; i += ASSIGN_NT) P.matchOut[base + i] = i < nCur ? s_t[i] : -1;
     if (threadIdx.x == 0) P.nmatches[pair] = s_nm;
 }
 
@@ -317,28 +300,16 @@ __global__ __launch_bounds__(ASSIGN_NT) void k_match_assign(MatchDev P) {
 //   k_local_candidates  one wave per point in view: window of RadiusByViewingCos (src/ORBmatcher.cc:119-124) * th * mvScaleFactors[L], levels
 //                       [L-1, L] (GetFeaturesInArea's bCheckLevels rule), the mvuRight test on mTrackProjXR (:84-88), Hamming distance; stored as
 //                       (dist << 16 | item position) by wave_candidates exactly as for the last-frame search;
-//   k_local_assign      one workgroup per frame: SearchByProjection's greedy hand-out (:51-112) as a min-fixpoint, then holder / nmatches / nToMatch.
-//
-// The fixpoint (point j = position in mvpLocalMapPoints; "held with observations" is what the skip at :81-83 tests):
-//   * Best / second best of point j.  Positions in the item list ascend in the reference's walk order (cell ix * 48 + iy, mGrid insertion order
-//     inside a cell), and the reference's update rule (:94-103: strict < for both) leaves (bestIdx, bestLevel) = the smallest (dist, position)
-//     key and (bestDist2, bestLevel2) = the second smallest among the candidates it did not skip, ignoring distance 256 (never < the initial
-//     256).  So pick(j) is a function of the set of keypoints point j skips, and of nothing else.
-//   * Point j skips i2 iff, when j runs, mvpMapPoints[i2] is a point with Observations() > 0.  Keypoints pre-held with observations (cur_flags 3)
-//     are skipped by every j (t = -1 below).  Otherwise let t(i2) = the first point WITH observations that picks i2: before t(i2) only points
-//     without observations (or the pre-held point without observations) can have written i2, so nothing skips it; from t(i2) on it is held
-//     with observations, every later point skips it and nobody overwrites it.  Hence: j skips i2  <=>  t(i2) < j.
-//   * Uniqueness and equality with the sequential loop: pick(j) depends only on t restricted to points < j, i.e. on pick(0 .. j-1).  By induction
-//     over j there is exactly one assignment that satisfies "pick(j) = choice of j given t computed from the picks", and it is the sequential one.
-//   * Round bound: each round recomputes every pick from the t of the previous round.  After round r the picks of points 0 .. r-1 are final
-//     (point 0's never depends on t; point r's depends only on points < r), so at most n_local + 1 rounds run; the loop stops at the first
-//     round that changes nothing (a few in practice, more in conflict-heavy windows).
-//   * Holder of i2 = the last picker (later points overwrite, :108); with t(i2) set nobody picks after it.  nmatches counts every accepted pick.
+//   k_local_assign      one workgroup per frame: SearchByProjection's greedy hand-out (:51-112) as the min-fixpoint of msl_assign.h (point j =
+//                       position in mvpLocalMapPoints), then nToMatch.
+// Best / second best of point j.  Positions in the item list ascend in the reference's walk order (cell ix * 48 + iy, mGrid insertion order
+// inside a cell), and the reference's update rule (:94-103: strict < for both) leaves (bestIdx, bestLevel) = the smallest (dist, position)
+// key and (bestDist2, bestLevel2) = the second smallest among the candidates it did not skip, ignoring distance 256 (never < the initial
+// 256).  So pick(j) is a function of the set of keypoints point j skips, as the hand-out requires.
 // LDS of k_local_assign: t[cap] int + pick[mcap] short = 4 cap + 2 mcap bytes, 96 KB at the limits (cap 8192, mcap 32768): inside the 160 KB
 // of a CDNA4 CU, and no more than k_match_assign asks for at its own limit, so the scratch never spills to global memory.
 constexpr int MAX_MCAP = 32768;
 constexpr int LOCAL_NT = 1024;
-constexpr int T_FREE = 0x7FFFFFFF;                  // t(i2): nobody with observations picks i2
 
 struct LocalDev {
     MatchDev m;                                     // current frame, grid scratch, candidates (per local point), params (m.prm = base), matchOut, nmatches
@@ -425,19 +396,13 @@ __global__ __launch_bounds__(256) void k_local_candidates(LocalDev L) {
         if (lane == 0) L.m.candCnt[jj] = 0;
         return;
     }
-    wave_candidates(L.m, f, Q, L.mpDesc + jj * 32, 256, L.m.cand + jj * CMAX, &s_cnt[wv], lane);   // distance 256 never becomes best or second
+    wave_candidates(L.m, f, Q, L.mpDesc + jj * 32, DIST_BELOW_256, L.m.cand + jj * CMAX, &s_cnt[wv], lane);   // distance 256 never becomes best or second
     if (lane == 0) L.m.candCnt[jj] = s_cnt[wv];
-}
-
-// the two smallest keys offered so far: b1 < b2
-__device__ __forceinline__ void offer2(unsigned key, unsigned &b1, unsigned &b2) {
-    if (key < b1) { b2 = b1; b1 = key; }
-    else if (key < b2) b2 = key;
 }
 
 // ---- k_local_assign: one workgroup per frame -----------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(LOCAL_NT) void k_local_assign(LocalDev L) {
-    extern __shared__ int s_ldyn[];          // t[cap] int | pick[mcap] short (the keypoint point j picks, -1 = none, -2 = not evaluated yet)
+    extern __shared__ int s_ldyn[];          // t[cap] int | pick[mcap] short
     __shared__ int s_nm, s_ntm;
     const MatchDev &P = L.m;
     const int f = blockIdx.x;
@@ -448,79 +413,28 @@ __global__ __launch_bounds__(LOCAL_NT) void k_local_assign(LocalDev L) {
     const uint8_t *cflags = L.curFlags + (size_t)f * P.cap;
     const uint8_t *mflags = L.mpFlags + (size_t)f * L.mcap;
     const msl_keypoint *kps = P.curKps + (size_t)f * P.cap;
-    auto reset_t = [&]() {   // pre-held with observations: skipped by every point
-        for (int i = threadIdx.x; i < P.cap; i += LOCAL_NT) s_t[i] = (i < nCur && (cflags[i] & 3) == 3) ? -1 : T_FREE;
-    };
-    reset_t();
-    for (int j = threadIdx.x; j < nLoc; j += LOCAL_NT) s_pick[j] = -2;
-    if (threadIdx.x == 0) { s_nm = 0; s_ntm = 0; }
-    __syncthreads();
+    if (threadIdx.x == 0) s_ntm = 0;
 
     // point j's choice given the current t: best and second-best key over the candidates it does not skip, then :106-112
     auto pick_of = [&](int j) -> int {
         const size_t jj = (size_t)f * L.mcap + j;
-        const unsigned cnt = P.candCnt[jj];
-        if (cnt == 0) return -1;
-        unsigned b1 = T_NONE, b2 = T_NONE;
-        if (cnt <= CMAX) {
-            const unsigned *cand = P.cand + jj * CMAX;
-            for (unsigned k = 0; k < cnt; k++) {
-                const unsigned key = cand[k];
-                if (s_t[items[key & 0xFFFFu]] < j) continue;      // held by a point with observations (:81-83)
-                offer2(key, b1, b2);
-            }
-        } else {   // more candidates than stored: walk the window again (rare; any count stays exact)
-            Query Q;
-            if (!local_query(L, jj, Q)) return -1;
-            const uint4 *dq = reinterpret_cast<const uint4 *>(L.mpDesc + jj * 32);
-            const uint4 d0 = dq[0], d1 = dq[1];
-            const unsigned *cellStart = P.cellStart + (size_t)f * (NCELLS + 1);
-            for (int ix = Q.minCX; ix <= Q.maxCX; ix++)
-                for (int iy = Q.minCY; iy <= Q.maxCY; iy++) {
-                    const unsigned b = cellStart[ix * GRID_ROWS + iy], e = cellStart[ix * GRID_ROWS + iy + 1];
-                    for (unsigned p = b; p < e; p++) {
-                        const unsigned i2 = items[p];
-                        if (s_t[i2] < j) continue;
-                        const int dist = eval_item(P, f, Q, i2, d0, d1);
-                        if (dist >= 0 && dist < 256) offer2(((unsigned)dist << 16) | p, b1, b2);
-                    }
-                }
-        }
-        if (b1 == T_NONE) return -1;
+        unsigned b1 = KEY_NONE, b2 = KEY_NONE;
+        unskipped_candidates(P, f, jj, j, L.mpDesc + jj * 32, DIST_BELOW_256, s_t, [&](Query &Q) { return local_query(L, jj, Q); },
+                             [&](unsigned key) { two_smallest(key, b1, b2); });
+        if (b1 == KEY_NONE) return -1;
         const int bestDist = (int)(b1 >> 16);
         if (bestDist > TH_HIGH) return -1;                                 // :106
         const int bestLevel = kps[items[b1 & 0xFFFFu]].octave;
-        const int bestLevel2 = b2 == T_NONE ? -1 : kps[items[b2 & 0xFFFFu]].octave;
-        const int bestDist2 = b2 == T_NONE ? 256 : (int)(b2 >> 16);
+        const int bestLevel2 = b2 == KEY_NONE ? -1 : kps[items[b2 & 0xFFFFu]].octave;
+        const int bestDist2 = b2 == KEY_NONE ? 256 : (int)(b2 >> 16);
         if (bestLevel == bestLevel2 && (float)bestDist > L.nnRatio * (float)bestDist2) return -1;   // :107-108
         return (int)items[b1 & 0xFFFFu];
     };
-
-    for (int round = 0; round <= nLoc; round++) {
-        bool changed = false;
-        for (int j = threadIdx.x; j < nLoc; j += LOCAL_NT) {
-            const int np = pick_of(j);
-            changed |= np != s_pick[j];
-            s_pick[j] = (short)np;
-        }
-        if (!__syncthreads_or(changed ? 1 : 0)) break;
-        reset_t();
-        __syncthreads();
-        for (int j = threadIdx.x; j < nLoc; j += LOCAL_NT)
-            if (s_pick[j] >= 0 && (mflags[j] & 2)) atomicMin(&s_t[s_pick[j]], j);
-        __syncthreads();
-    }
-    // holder = the last point that picked the keypoint; t(.) is no longer needed and its storage holds it
-    __syncthreads();
-    for (int i = threadIdx.x; i < P.cap; i += LOCAL_NT) s_t[i] = -1;
-    __syncthreads();
-    int nm = 0, ntm = 0;
-    for (int j = threadIdx.x; j < nLoc; j += LOCAL_NT) {
-        const int pk = s_pick[j];
-        if (pk >= 0) { atomicMax(&s_t[pk], j); nm++; }
-        ntm += L.inView[(size_t)f * L.mcap + j];
-    }
-    if (nm) atomicAdd(&s_nm, nm);
+    // keypoints pre-held with observations (cur_flags 3) are skipped by every point
+    greedy_assign<LOCAL_NT>(nLoc, nCur, s_t, s_pick, &s_nm, pick_of, [&](int j) { return (mflags[j] & 2) != 0; },
+                            [&](int i) { return (cflags[i] & 3) == 3 ? -1 : T_FREE; });
+    int ntm = 0;
+    for (int j = threadIdx.x; j < nLoc; j += LOCAL_NT) ntm += L.inView[(size_t)f * L.mcap + j];
     if (ntm) atomicAdd(&s_ntm, ntm);
     __syncthreads();
     for (int i = threadIdx.x; i < P.cap; i += LOCAL_NT) P.matchOut[(size_t)f * P.cap + i] = i < nCur ? s_t[i] : -1;
@@ -530,9 +444,21 @@ __global__ __launch_bounds__(LOCAL_NT) void k_local_assign(LocalDev L) {
 __global__ void k_descriptor_distance(const uint8_t *a, const uint8_t *b, int n, int32_t *out) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const uint4 *pa = reinterpret_cast<const uint4 *>(a + (size_t)i * 32), *pb = reinterpret_cast<const uint4 *>(b + (size_t)i * 32);
-    const uint4 a0 = pa[0], a1 = pa[1], b0 = pb[0], b1 = pb[1];
+    uint4 a0, a1, b0, b1;
+    load_desc(a + (size_t)i * 32, a0, a1);
+    load_desc(b + (size_t)i * 32, b0, b1);
     out[i] = hamming256(a0, a1, b0, b1);
+}
+
+// The current-frame part of a point search (both of them): sizes, parameters, the grid pitch and the six current-frame arrays.
+void stage_current_frame(Stage &S, MatchDev &P, int n_frames, int cap, const msl_match_params &prm, const msl_keypoint *cur_kps, const float *cur_un_xy,
+                         const float *cur_uright, const int32_t *cur_grid_cell, const uint8_t *cur_desc, const int32_t *n_cur) {
+    const size_t n = (size_t)n_frames * cap;
+    P.nPairs = n_frames; P.cap = cap; P.prm = prm;
+    P.gridWInv = static_cast<float>(GRID_COLS) / static_cast<float>(prm.maxX - prm.minX);   // src/Frame.cc:137-138
+    P.gridHInv = static_cast<float>(GRID_ROWS) / static_cast<float>(prm.maxY - prm.minY);
+    P.curKps = S.in(cur_kps, n); P.curUn = S.in(cur_un_xy, 2 * n); P.curUright = S.in(cur_uright, n); P.curCell = S.in(cur_grid_cell, n);
+    P.curDesc = S.in(cur_desc, 32 * n); P.nCur = S.in(n_cur, (size_t)n_frames);
 }
 
 int run_projection(msl_match *h, int n_pairs, int cap, const msl_match_params *params, const msl_keypoint *cur_kps, const float *cur_un_xy,
@@ -549,39 +475,25 @@ int run_projection(msl_match *h, int n_pairs, int cap, const msl_match_params *p
     int rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
     hipStream_t st = h->stream;
-    const size_t n = (size_t)n_pairs * cap;
+    const size_t F = (size_t)n_pairs, n = F * cap;
+    Stage S(h, mem, out_mem);
     MatchDev P{};
-    P.nPairs = n_pairs; P.cap = cap; P.prm = *params;
-    P.gridWInv = static_cast<float>(GRID_COLS) / static_cast<float>(params->maxX - params->minX);   // src/Frame.cc:137-138
-    P.gridHInv = static_cast<float>(GRID_ROWS) / static_cast<float>(params->maxY - params->minY);
+    stage_current_frame(S, P, n_pairs, cap, *params, cur_kps, cur_un_xy, cur_uright, cur_grid_cell, cur_desc, n_cur);
     P.mb = params->bf / params->fx;                                                                  // :150
-    const void *src[14] = {cur_kps, cur_un_xy, cur_uright, cur_grid_cell, cur_desc, n_cur, last_xyz, last_desc, last_flags, last_octave,
-                           last_angle, n_last, Tcw_cur, Tcw_last};
-    const size_t bytes[14] = {sizeof(msl_keypoint) * n, 8 * n, 4 * n, 4 * n, 32 * n, 4 * (size_t)n_pairs, 12 * n, 32 * n, n, 4 * n, 4 * n,
-                              4 * (size_t)n_pairs, 48 * (size_t)n_pairs, 48 * (size_t)n_pairs};
-    void *dev[14];
-    MSL_HIP_TRY(stage(src, bytes, 14, 14, mem, h->in, st, dev));
-    P.curKps = (const msl_keypoint *)dev[0]; P.curUn = (const float *)dev[1]; P.curUright = (const float *)dev[2]; P.curCell = (const int32_t *)dev[3];
-    P.curDesc = (const uint8_t *)dev[4]; P.nCur = (const int32_t *)dev[5]; P.lastXyz = (const float *)dev[6]; P.lastDesc = (const uint8_t *)dev[7];
-    P.lastFlags = (const uint8_t *)dev[8]; P.lastOctave = (const int32_t *)dev[9]; P.lastAngle = (const float *)dev[10];
-    P.nLast = (const int32_t *)dev[11]; P.TcwCur = (const float *)dev[12]; P.TcwLast = (const float *)dev[13];
+    P.lastXyz = S.in(last_xyz, 3 * n); P.lastDesc = S.in(last_desc, 32 * n); P.lastFlags = S.in(last_flags, n); P.lastOctave = S.in(last_octave, n);
+    P.lastAngle = S.in(last_angle, n); P.nLast = S.in(n_last, F); P.TcwCur = S.in(Tcw_cur, 12 * F); P.TcwLast = S.in(Tcw_last, 12 * F);
+    P.matchOut = S.out(match_out, n); P.nmatches = S.out(nmatches, F);
+    MSL_HIP_TRY(S.error());
     MSL_HIP_TRY(grow_all(st, {{h->items, sizeof(unsigned short) * n}, {h->cellStart, sizeof(unsigned) * (NCELLS + 1) * n_pairs},
                               {h->mode, sizeof(int) * n_pairs}, {h->cand, sizeof(unsigned) * CMAX * n}, {h->candCnt, sizeof(unsigned) * n}}));
     P.items = (unsigned short *)h->items.p; P.cellStart = (unsigned *)h->cellStart.p; P.mode = (int *)h->mode.p; P.cand = (unsigned *)h->cand.p;
     P.candCnt = (unsigned *)h->candCnt.p;
-    void *out[2] = {match_out, nmatches}, *dout[2];
-    const size_t outBytes[2] = {sizeof(int32_t) * n, sizeof(int32_t) * n_pairs};
-    MSL_HIP_TRY(stage(out, outBytes, 2, 0, out_mem, h->out, st, dout));
-    P.matchOut = (int32_t *)dout[0]; P.nmatches = (int32_t *)dout[1];
-    if (!h->attrSet) {
-        MSL_HIP_TRY(hipFuncSetAttribute((const void *)k_match_assign, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(3 * sizeof(unsigned) * MAX_CAP)));
-        h->attrSet = true;
-    }
+    MSL_HIP_TRY(allow_lds(h, LDS_MATCH_ASSIGN, k_match_assign, 3 * sizeof(int) * MAX_CAP));
     hipLaunchKernelGGL(k_match_grid, dim3((unsigned)n_pairs), dim3(256), sizeof(unsigned short) * cap, st, P);
     hipLaunchKernelGGL(k_match_candidates, dim3((unsigned)((cap + 3) / 4), (unsigned)n_pairs), dim3(256), 0, st, P);
-    hipLaunchKernelGGL(k_match_assign, dim3((unsigned)n_pairs), dim3(ASSIGN_NT), 3 * sizeof(unsigned) * cap, st, P);
+    hipLaunchKernelGGL(k_match_assign, dim3((unsigned)n_pairs), dim3(ASSIGN_NT), 3 * sizeof(int) * cap, st, P);
     MSL_HIP_TRY(hipGetLastError());
-    MSL_HIP_TRY(finish_call(out, dout, outBytes, 2, mem, out_mem, st));
+    MSL_HIP_TRY(S.finish());
     return MSL_OK;
 }
 
@@ -603,47 +515,30 @@ int run_local(msl_match *h, int n_frames, int cap, int mcap, const msl_local_mat
     if (rc != MSL_OK) return rc;
     hipStream_t st = h->stream;
     const size_t n = (size_t)n_frames * cap, m = (size_t)n_frames * mcap, F = (size_t)n_frames;
+    Stage S(h, mem, out_mem);
     LocalDev L{};
     MatchDev &P = L.m;
-    P.nPairs = n_frames; P.cap = cap; P.prm = *params;
-    P.gridWInv = static_cast<float>(GRID_COLS) / static_cast<float>(params->maxX - params->minX);   // src/Frame.cc:137-138
-    P.gridHInv = static_cast<float>(GRID_ROWS) / static_cast<float>(params->maxY - params->minY);
+    stage_current_frame(S, P, n_frames, cap, *params, cur_kps, cur_un_xy, cur_uright, cur_grid_cell, cur_desc, n_cur);
     L.mcap = mcap; L.logScale = lp->log_scale_factor; L.viewCosLimit = lp->view_cos_limit; L.nnRatio = lp->nn_ratio;
-    const void *src[14] = {cur_kps, cur_un_xy, cur_uright, cur_grid_cell, cur_desc, n_cur, cur_flags, mp_xyz, mp_normal, mp_dist, mp_desc, mp_flags,
-                           n_local, Tcw};
-    const size_t bytes[14] = {sizeof(msl_keypoint) * n, 8 * n, 4 * n, 4 * n, 32 * n, 4 * F, n, 12 * m, 12 * m, 8 * m, 32 * m, m, 4 * F, 48 * F};
-    void *dev[14];
-    MSL_HIP_TRY(stage(src, bytes, 14, 14, mem, h->lin, st, dev));
-    P.curKps = (const msl_keypoint *)dev[0]; P.curUn = (const float *)dev[1]; P.curUright = (const float *)dev[2]; P.curCell = (const int32_t *)dev[3];
-    P.curDesc = (const uint8_t *)dev[4]; P.nCur = (const int32_t *)dev[5]; L.curFlags = (const uint8_t *)dev[6]; L.mpXyz = (const float *)dev[7];
-    L.mpNormal = (const float *)dev[8]; L.mpDist = (const float *)dev[9]; L.mpDesc = (const uint8_t *)dev[10]; L.mpFlags = (const uint8_t *)dev[11];
-    L.nLocal = (const int32_t *)dev[12]; P.TcwCur = (const float *)dev[13];
+    L.curFlags = S.in(cur_flags, n); L.mpXyz = S.in(mp_xyz, 3 * m); L.mpNormal = S.in(mp_normal, 3 * m); L.mpDist = S.in(mp_dist, 2 * m);
+    L.mpDesc = S.in(mp_desc, 32 * m); L.mpFlags = S.in(mp_flags, m); L.nLocal = S.in(n_local, F); P.TcwCur = S.in(Tcw, 12 * F);
+    P.matchOut = S.out(match_out, n); P.nmatches = S.out(nmatches, F); L.nToMatch = S.out(n_to_match, F);
+    MSL_HIP_TRY(S.error());
     MSL_HIP_TRY(grow_all(st, {{h->items, sizeof(unsigned short) * n}, {h->cellStart, sizeof(unsigned) * (NCELLS + 1) * F},
                               {h->cand, sizeof(unsigned) * CMAX * m}, {h->candCnt, sizeof(unsigned) * m}, {h->trk, sizeof(msl_local_track) * m},
                               {h->inView, m}}));
     P.items = (unsigned short *)h->items.p; P.cellStart = (unsigned *)h->cellStart.p; P.cand = (unsigned *)h->cand.p; P.candCnt = (unsigned *)h->candCnt.p;
     P.mode = nullptr;
     L.track = (msl_local_track *)h->trk.p; L.inView = (uint8_t *)h->inView.p;
-    void *out[5] = {match_out, nmatches, n_to_match, in_view, track}, *dout[5];
-    const size_t outBytes[5] = {sizeof(int32_t) * n, sizeof(int32_t) * F, sizeof(int32_t) * F, m, sizeof(msl_local_track) * m};
-    MSL_HIP_TRY(stage(out, outBytes, 3, 0, out_mem, h->out, st, dout));
-    P.matchOut = (int32_t *)dout[0]; P.nmatches = (int32_t *)dout[1]; L.nToMatch = (int32_t *)dout[2];
-    // the optional in_view / track: the kernels write device-memory ones, host-memory ones are copied back from the scratch
-    const bool devOut = out_mem != MSL_MEM_HOST;
-    L.inViewOut = devOut ? in_view : nullptr; L.trackOut = devOut ? track : nullptr;
-    dout[3] = L.inView; dout[4] = L.track;
+    L.inViewOut = S.out_of_scratch(in_view, L.inView, m); L.trackOut = S.out_of_scratch(track, L.track, m);   // the optional in_view / track
     const size_t lds = sizeof(int) * (size_t)cap + sizeof(short) * (size_t)mcap;   // 96 KB at the limits (see k_local_assign)
-    if (!h->localAttrSet) {
-        MSL_HIP_TRY(hipFuncSetAttribute((const void *)k_local_assign, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)(sizeof(int) * MAX_CAP + sizeof(short) * MAX_MCAP)));
-        h->localAttrSet = true;
-    }
+    MSL_HIP_TRY(allow_lds(h, LDS_LOCAL_ASSIGN, k_local_assign, sizeof(int) * MAX_CAP + sizeof(short) * MAX_MCAP));
     hipLaunchKernelGGL(k_match_grid, dim3((unsigned)n_frames), dim3(256), sizeof(unsigned short) * cap, st, P);
     hipLaunchKernelGGL(k_local_frustum, dim3((unsigned)((mcap + 255) / 256), (unsigned)n_frames), dim3(256), 0, st, L);
     hipLaunchKernelGGL(k_local_candidates, dim3((unsigned)((mcap + 3) / 4), (unsigned)n_frames), dim3(256), 0, st, L);
     hipLaunchKernelGGL(k_local_assign, dim3((unsigned)n_frames), dim3(LOCAL_NT), lds, st, L);
     MSL_HIP_TRY(hipGetLastError());
-    MSL_HIP_TRY(finish_call(out, dout, outBytes, 5, mem, out_mem, st));
+    MSL_HIP_TRY(S.finish());
     return MSL_OK;
 }
 
@@ -652,18 +547,42 @@ int run_distance(msl_match *h, const uint8_t *a32, const uint8_t *b32, int n, in
     if (n == 0) return MSL_OK;
     int rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
-    hipStream_t st = h->stream;
-    MSL_HIP_TRY(grow_all(st, {{h->da, (size_t)n * 32}, {h->db, (size_t)n * 32}, {h->dout, sizeof(int32_t) * n}}));
-    MSL_HIP_TRY(hipMemcpyAsync(h->da.p, a32, (size_t)n * 32, hipMemcpyHostToDevice, st));
-    MSL_HIP_TRY(hipMemcpyAsync(h->db.p, b32, (size_t)n * 32, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_descriptor_distance, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint8_t *)h->da.p, (const uint8_t *)h->db.p, n, (int32_t *)h->dout.p);
+    Stage S(h, MSL_MEM_HOST, MSL_MEM_HOST);
+    const uint8_t *a = S.in(a32, (size_t)n * 32), *b = S.in(b32, (size_t)n * 32);
+    int32_t *out = S.out(dist_out, (size_t)n);
+    MSL_HIP_TRY(S.error());
+    hipLaunchKernelGGL(k_descriptor_distance, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, a, b, n, out);
     MSL_HIP_TRY(hipGetLastError());
-    MSL_HIP_TRY(hipMemcpyAsync(dist_out, h->dout.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-    MSL_HIP_TRY(hipStreamSynchronize(st));
+    MSL_HIP_TRY(S.finish());
     return MSL_OK;
 }
 
 }  // namespace
+
+void *msl::Stage::take(void *user, size_t bytes, msl_mem side, bool copy_in, bool back) {
+    if (!user || err_ != hipSuccess) return nullptr;
+    if (side != MSL_MEM_HOST) return user;
+    if (used_ == msl_match::STAGE_SLOTS) { err_ = hipErrorOutOfMemory; return nullptr; }   // an entry point outgrew STAGE_SLOTS
+    DevBuf &b = h_->stage[used_++];
+    err_ = b.grow(bytes, h_->stream);
+    if (err_ == hipSuccess && copy_in) err_ = hipMemcpyAsync(b.p, user, bytes, hipMemcpyHostToDevice, h_->stream);
+    if (err_ != hipSuccess) return nullptr;
+    if (back) copy_back(user, b.p, bytes);
+    return b.p;
+}
+
+void msl::Stage::copy_back(void *user, const void *dev, size_t bytes) {
+    if (nBack_ == msl_match::STAGE_SLOTS) { err_ = hipErrorOutOfMemory; return; }
+    back_[nBack_++] = Back{user, dev, bytes};
+}
+
+hipError_t msl::Stage::finish() {
+    for (int i = 0; i < nBack_; i++) {
+        const hipError_t e = hipMemcpyAsync(back_[i].user, back_[i].dev, back_[i].bytes, hipMemcpyDeviceToHost, h_->stream);
+        if (e != hipSuccess) return e;
+    }
+    return outMem_ == MSL_MEM_HOST || mem_ == MSL_MEM_HOST ? hipStreamSynchronize(h_->stream) : hipSuccess;
+}
 
 extern "C" {
 
@@ -717,12 +636,16 @@ int msl_match_by_projection(msl_match *h, int n_pairs, int cap, const msl_match_
                             const int32_t *last_octave, const float *last_angle, const int32_t *n_last, const float *Tcw_cur,
                             const float *Tcw_last, msl_mem mem, int32_t *match_out, int32_t *nmatches, msl_mem out_mem) noexcept {
     try {
-    return run_projection(h, n_pairs, cap, params, cur_kps, cur_un_xy, cur_uright, cur_grid_cell, cur_desc, n_cur, last_xyz, last_desc, last_flags,
-                          last_octave, last_angle, n_last, Tcw_cur, Tcw_last, mem, match_out, nmatches, out_mem);
+    return run_projection(h, n_pairs, cap, params, cur_kps, cur_un_xy, cur_uright, cur_grid_cell, cur_desc, n_cur, last_xyz, last_desc, last_flags, last_octave,
+                          last_angle, n_last, Tcw_cur, Tcw_last, mem, match_out, nmatches, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
-int msl_match_descriptor_distances(msl_match *h, const uint8_t *a32, const uint8_t *b32, int n, int32_t *dist_out) noexcept { try { return run_distance(h, a32, b32, n, dist_out); } MSL_ABI_CATCH_INT }
+int msl_match_descriptor_distances(msl_match *h, const uint8_t *a32, const uint8_t *b32, int n, int32_t *dist_out) noexcept {
+    try {
+    return run_distance(h, a32, b32, n, dist_out);
+    } MSL_ABI_CATCH_INT
+}
 
 int msl_match_by_projection_batch(int device, int n_pairs, int cap, const msl_match_params *params, const msl_keypoint *cur_kps,
                                   const float *cur_un_xy, const float *cur_uright, const int32_t *cur_grid_cell, const uint8_t *cur_desc,
@@ -730,10 +653,8 @@ int msl_match_by_projection_batch(int device, int n_pairs, int cap, const msl_ma
                                   const int32_t *last_octave, const float *last_angle, const int32_t *n_last, const float *Tcw_cur,
                                   const float *Tcw_last, msl_mem mem, int32_t *match_out, int32_t *nmatches, msl_mem out_mem) noexcept {
     try {
-    return on_default_handle(device, mem == MSL_MEM_DEVICE, [&](msl_match *h) {
-        return run_projection(h, n_pairs, cap, params, cur_kps, cur_un_xy, cur_uright, cur_grid_cell, cur_desc, n_cur, last_xyz, last_desc, last_flags,
-                              last_octave, last_angle, n_last, Tcw_cur, Tcw_last, mem, match_out, nmatches, out_mem);
-    });
+    return abi_call_default(run_projection, device, mem == MSL_MEM_DEVICE, n_pairs, cap, params, cur_kps, cur_un_xy, cur_uright, cur_grid_cell, cur_desc, n_cur,
+                            last_xyz, last_desc, last_flags, last_octave, last_angle, n_last, Tcw_cur, Tcw_last, mem, match_out, nmatches, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -755,19 +676,15 @@ int msl_match_local_points_batch(int device, int n_frames, int cap, int mcap, co
                                  int32_t *match_out, int32_t *n_to_match, int32_t *nmatches, uint8_t *in_view, msl_local_track *track,
                                  msl_mem out_mem) noexcept {
     try {
-    return on_default_handle(device, mem == MSL_MEM_DEVICE, [&](msl_match *h) {
-        return run_local(h, n_frames, cap, mcap, params, cur_kps, cur_un_xy, cur_uright, cur_grid_cell, cur_desc, n_cur, cur_flags, mp_xyz, mp_normal,
-                         mp_dist, mp_desc, mp_flags, n_local, Tcw, mem, match_out, n_to_match, nmatches, in_view, track, out_mem);
-    });
+    return abi_call_default(run_local, device, mem == MSL_MEM_DEVICE, n_frames, cap, mcap, params, cur_kps, cur_un_xy, cur_uright, cur_grid_cell, cur_desc,
+                            n_cur, cur_flags, mp_xyz, mp_normal, mp_dist, mp_desc, mp_flags, n_local, Tcw, mem, match_out, n_to_match, nmatches, in_view, track,
+                            out_mem);
     } MSL_ABI_CATCH_INT
 }
 
 int msl_match_descriptor_distance(int device, const uint8_t *a32, const uint8_t *b32, int n, int32_t *dist_out) noexcept {
     try {
-    std::lock_guard<std::mutex> lock(g_default_mutex);   // synchronous already: no on_default_handle
-    msl_match *h = default_handle(device);
-    if (!h) return MSL_ERR_NO_DEVICE;
-    return run_distance(h, a32, b32, n, dist_out);
+    return abi_call_default(run_distance, device, false, a32, b32, n, dist_out);
     } MSL_ABI_CATCH_INT
 }
 

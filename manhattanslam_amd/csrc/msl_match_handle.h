@@ -1,27 +1,29 @@
-// msl_match_handle.h -- the matcher handle, shared by msl_match.hip, msl_line_match.hip, msl_pose.hip, msl_plane.hip and msl_bow.hip (internal).
+// msl_match_handle.h -- the matcher handle, its staging of caller arrays (Stage) and the forwarder of the *_batch entry points; shared by
+// msl_match.hip, msl_line_match.hip, msl_pose.hip, msl_plane.hip and msl_bow.hip (internal).
 #pragma once
 
 #include "msl_common.h"
 
 // One matcher object = one ORBmatcher of the reference (src/ORBmatcher.cc:41): its own stream and its own scratch, used by one thread at a time;
-// the device is re-bound at every entry like the other handles.  The line searches (= the tracker's LSDmatcher) and msl_pose_optimize run on it too.
+// the device is re-bound at every entry like the other handles.  The line searches (= the tracker's LSDmatcher), msl_pose_optimize, the
+// plane association and the bag-of-words calls run on it too.
 struct msl_match {
+    // The most arrays one entry point stages: msl_pose_optimize_translation (16 inputs, 3 in/out outlier flags, 2 outputs).
+    static constexpr int STAGE_SLOTS = 21;
     int device = 0;
     hipStream_t stream = nullptr; bool ownStream = true;
-    msl::DevBuf in[14], items, cellStart, mode, cand, candCnt, out[3];   // staged inputs (host-memory calls), scratch, staged outputs
-    msl::DevBuf da, db, dout;                                          // msl_match_descriptor_distance
-    msl::DevBuf lin[14], trk, inView;                                  // msl_match_local_points: staged inputs, per-point scratch
-    msl::DevBuf poseIn[16], poseOut[5];                                // msl_pose_optimize[_translation]: staged inputs (+ Rcw), in/out flags, outputs
-    msl::DevBuf lineIn[11], lineQ, lineTrk, lineView, lineIo[2];       // the line searches: staged inputs, per-line queries / tracks / in-view, line_xyz / line_has
-    msl::DevBuf planeIn[8], planeDis, planeOut[5];                     // msl_plane_associate: staged inputs, [frame][map plane][64] distances, outputs
-    msl::DevBuf mfIn[13], mfOut[4];                                    // msl_manhattan_detect: staged inputs, Rcw (in/out) and outputs
-    msl::DevBuf bowIn[2], bowOut[5], bowW;                             // msl_bow_transform: staged inputs, outputs, per-feature word weights
-    msl::DevBuf bmIn[9], bmOut[2];                                     // msl_match_by_bow
-    msl::DevBuf ldIn[6], ldOut[4];                                     // msl_match_lines_by_descriptor (line_xyz in/out)
-    bool bowAttrSet = false;
-    bool lineAttrSet = false;
-    bool localAttrSet = false;
-    bool attrSet = false;
+    // Scratch the kernels of a call hand to one another.  Device-memory calls are asynchronous and ordered only by the stream, so each
+    // buffer keeps its one role.
+    msl::DevBuf items, cellStart, mode, cand, candCnt;                 // the point searches: grid, search mode, candidates
+    msl::DevBuf trk, inView;                                           // msl_match_local_points: per-point track / in-view
+    msl::DevBuf lineQ, lineTrk, lineView;                              // the line searches: per-line queries / tracks / in-view
+    msl::DevBuf planeDis;                                              // msl_plane_associate: [frame][map plane][64] distances
+    msl::DevBuf bowW;                                                  // msl_bow_transform: per-feature word weights
+    // Device copies of host-memory arguments, one pool for every entry point (msl::Stage deals the slots out in declaration order).
+    // Sharing is sound because every call that touches the pool returns with the stream drained (Stage::finish synchronises whenever
+    // either side is host memory, and only then is a slot used), so no slot is live when the next call starts.
+    msl::DevBuf stage[STAGE_SLOTS];
+    unsigned ldsSet = 0;                                               // bit k: kernel k's dynamic-LDS limit is raised (msl::allow_lds)
 };
 
 namespace msl {
@@ -37,17 +39,59 @@ inline msl_match *default_handle(int device) {   // g_default_mutex held
     return h;
 }
 
-// A *_batch form: run(h) on the device's shared handle, synchronous.  sync_legacy: the call reads device memory that is complete, or
-// enqueued on the legacy default stream, when the call is made (as before the handle existed).
-template <class Run>
-int on_default_handle(int device, bool sync_legacy, Run run) {
+// The body of a *_batch form: run_x(h, args...) on the device's shared handle, synchronous.  sync_legacy: the call reads device memory
+// that is complete, or enqueued on the legacy default stream, when the call is made (as before the handle existed).
+template <class Run, class... A>
+int abi_call_default(Run run, int device, bool sync_legacy, A... a) {
     std::lock_guard<std::mutex> lock(g_default_mutex);
     msl_match *h = default_handle(device);
     if (!h) return MSL_ERR_NO_DEVICE;
     if (sync_legacy) { if (bind_device(device) == MSL_OK) (void)hipStreamSynchronize(0); }
-    int rc = run(h);
+    int rc = run(h, a...);
     if (rc == MSL_OK) rc = msl_match_sync(h);
     return rc;
 }
+
+// Kernels that ask for more dynamic LDS than the default limit: the limit is raised once per handle (= per device) and kernel.
+enum LdsKernel { LDS_MATCH_ASSIGN, LDS_LOCAL_ASSIGN, LDS_LINE_ASSIGN_LAST, LDS_LINE_ASSIGN_LOCAL, LDS_BOW_VECTOR, LDS_MATCH_BOW };
+template <class K>
+hipError_t allow_lds(msl_match *h, LdsKernel k, K kernel, size_t max_bytes) {
+    if (h->ldsSet >> k & 1u) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_bytes);
+    if (e == hipSuccess) h->ldsSet |= 1u << k;
+    return e;
+}
+
+// The caller's arrays of one entry point as device pointers.  Each array is declared once, with its element count: inputs live in `mem`
+// memory, in/out arrays and outputs in `out_mem` memory.  Device memory: the declaration returns the caller's own pointer.  Host memory:
+// a slot of the handle's pool, grown to the array's size; inputs and in/outs are already enqueued for copy, in/outs and outputs are
+// copied back by finish().  A null (optional) array returns null.  Errors are kept: check error() once before launching.
+class Stage {
+  public:
+    Stage(msl_match *h, msl_mem mem, msl_mem out_mem) : h_(h), mem_(mem), outMem_(out_mem) {}
+    template <class T> const T *in(const T *user, size_t count) { return (const T *)take(const_cast<T *>(user), sizeof(T) * count, mem_, true, false); }
+    template <class T> T *inout(T *user, size_t count) { return (T *)take(user, sizeof(T) * count, outMem_, true, true); }
+    template <class T> T *out(T *user, size_t count) { return (T *)take(user, sizeof(T) * count, outMem_, false, true); }
+    // An optional output the kernels always write to the handle's scratch `dev`: the pointer they write as well (device memory: the
+    // caller's array, or null), while a host-memory array is copied back from the scratch by finish().
+    template <class T> T *out_of_scratch(T *user, const T *dev, size_t count) {
+        if (outMem_ != MSL_MEM_HOST) return user;
+        if (user) copy_back(user, dev, sizeof(T) * count);
+        return nullptr;
+    }
+    hipError_t error() const { return err_; }
+    // The end of the entry point.  Host-memory outputs are copied back; with host memory on either side the stream is drained, so the
+    // caller's host arrays are theirs again (and the pool is free) on return.
+    hipError_t finish();
+
+  private:
+    void *take(void *user, size_t bytes, msl_mem side, bool copy_in, bool back);
+    void copy_back(void *user, const void *dev, size_t bytes);
+    struct Back { void *user; const void *dev; size_t bytes; };
+    msl_match *h_; msl_mem mem_, outMem_;
+    hipError_t err_ = hipSuccess;
+    int used_ = 0, nBack_ = 0;
+    Back back_[msl_match::STAGE_SLOTS];
+};
 
 }  // namespace msl

@@ -1,4 +1,6 @@
-// msl_match_math.h -- device arithmetic the point and line matchers share, each piece pinned once (internal).
+// msl_match_math.h -- device arithmetic the searches on the matcher handle share, each piece pinned or written once
+// (internal): cv::gemm's 3x3 float kernel, the search mode, the popcount distance and descriptor load, the two-smallest-keys pair and its
+// wave reduction, the rotation-consistency cull, the scale prediction.
 #pragma once
 
 #include "msl_common.h"
@@ -18,6 +20,8 @@ __device__ __forceinline__ void gemm3(const float *A, bool transA, double alpha,
     }
 }
 
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
 // bForward / bBackward of the two last-frame searches (src/ORBmatcher.cc:560-571, src/LSDmatcher.cpp:24-35): 0 = neither, 1 = forward,
 // 2 = backward.  Tc / Tl: rows 0-2 of the current / last mTcw.
 __device__ __forceinline__ int search_mode(const float *Tc, const float *Tl, float mb) {
@@ -32,6 +36,32 @@ __device__ __forceinline__ int search_mode(const float *Tc, const float *Tl, flo
 __device__ __forceinline__ int hamming256(const uint4 &a0, const uint4 &a1, const uint4 &b0, const uint4 &b1) {
     return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) + __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) +
            __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
+}
+
+// The 32 bytes of a descriptor as two 16-byte loads
+__device__ __forceinline__ void load_desc(const uint8_t *p, uint4 &a, uint4 &b) {
+    const uint4 *q = reinterpret_cast<const uint4 *>(p);
+    a = q[0]; b = q[1];
+}
+
+// The two smallest keys offered so far, b1 <= b2 (both start at the type's maximum = none).  Branch-free, so b1 / b2 stay in registers
+// (no private array).  With (distance << bits | index) keys this is the reference's strict-< best / second-best update in walk order.
+template <typename T>
+__device__ __forceinline__ void two_smallest(T key, T &b1, T &b2) {
+    const T hi = key < b1 ? b1 : key;
+    b2 = hi < b2 ? hi : b2;
+    b1 = key < b1 ? key : b1;
+}
+
+// The two smallest of the keys held by the lanes of a width-W group (every lane gets both): merging (a1 <= a2) with (b1 <= b2).
+template <typename T>
+__device__ __forceinline__ void two_min(T &m1, T &m2, int width) {
+    for (int o = 1; o < width; o <<= 1) {
+        const T b1 = __shfl_xor(m1, o, width), b2 = __shfl_xor(m2, o, width);
+        const T lo = m1 < b1 ? m1 : b1, hi = m1 < b1 ? b1 : m1;
+        const T s = m2 < b2 ? m2 : b2;
+        m1 = lo; m2 = hi < s ? hi : s;
+    }
 }
 
 // The rotation-consistency histogram of the point searches (src/ORBmatcher.cc:33-35, e.g. :643-649 and :199-206): HISTO_LENGTH bins, the bin of
@@ -59,6 +89,25 @@ __device__ __forceinline__ void three_maxima(const int *hist, int keep[3]) {
     keep[0] = ind1; keep[1] = ind2; keep[2] = ind3;
 }
 
+// The rotation-consistency cull of a workgroup of NT threads (src/ORBmatcher.cc:643-674, :199-243): bin(i) is the rot_bin of match i, or -1
+// when i holds no match (or its rotation has no bin); every match outside the three kept bins goes to drop(i).  s_hist[ROT_HISTO_LENGTH] is
+// zero and visible on entry; returns behind a barrier.
+template <int NT, class Bin, class Drop>
+__device__ __forceinline__ void rotation_cull(int n, int *s_hist, int *s_keep, Bin bin, Drop drop) {
+    for (int i = threadIdx.x; i < n; i += NT) {
+        const int b = bin(i);
+        if (b >= 0) atomicAdd(&s_hist[b], 1);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) three_maxima(s_hist, s_keep);
+    __syncthreads();
+    for (int i = threadIdx.x; i < n; i += NT) {
+        const int b = bin(i);
+        if (b >= 0 && b != s_keep[0] && b != s_keep[1] && b != s_keep[2]) drop(i);
+    }
+    __syncthreads();
+}
+
 // ceil(log(maxDistance / dist) / logScale) as an int, not clamped (MapLine::PredictScale, src/MapLine.cpp:320-328).  log is glibc's logf in
 // the reference; here the double log of the float, rounded once.  A quotient that is not a finite int (NaN, +-inf)
 // converts to INT_MIN as on x86-64.
@@ -70,10 +119,7 @@ __device__ __forceinline__ int predict_level(float maxDistance, float dist, floa
 
 // MapPoint::PredictScale (src/MapPoint.cc:350-364): the same level clamped to [0, nlevels - 1]
 __device__ __forceinline__ int predict_scale(float maxDistance, float dist, float logScale, int nlevels) {
-    int nScale = predict_level(maxDistance, dist, logScale);
-    if (nScale < 0) nScale = 0;
-    else if (nScale >= nlevels) nScale = nlevels - 1;
-    return nScale;
+    return clampi(predict_level(maxDistance, dist, logScale), 0, nlevels - 1);
 }
 
 }  // namespace msl

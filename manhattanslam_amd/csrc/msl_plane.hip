@@ -15,6 +15,7 @@
 //   k_manhattan     one workgroup per frame: every (i, j, k) triple and (i, j) pair is scored independently, the reference's "first candidate
 //                   with the largest score > 0" is a 64-bit max of (score, ~order); lane 0 builds manhattanRcw from the winner.
 #include "msl_match_handle.h"
+#include "msl_match_math.h"
 
 #include <algorithm>
 #include <cmath>
@@ -44,8 +45,6 @@ struct MfDev {
     const float *kfRwc, *kfCoef; const int32_t *kfNpts;
     float *Rcw; int32_t *found, *full, *choice;
 };
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // pM = mTcw^T * coef (cv::Mat CV_32F product): double accumulation in k order, one rounding; row 3 of mTcw is 0 0 0 1.
 __device__ __forceinline__ void world_coef(const float *T, const float *c, float *pM) {
@@ -382,24 +381,19 @@ int run_associate(msl_match *h, int n_frames, int pcap, int mcap, int ptcap, con
     const size_t F = (size_t)n_frames, p = F * pcap, m = F * mcap;
     AssocDev D{};
     D.pcap = pcap; D.mcap = mcap; D.ptcap = ptcap; D.prm = *prm;
-    const void *src[8] = {plane_coef, n_planes, Tcw, mp_w, mp_flags, mp_pt_off, mp_pts, n_map};
-    const size_t bytes[8] = {16 * p, 4 * F, 48 * F, 16 * m, m, 4 * (m + F), 12 * F * ptcap, 4 * F};
-    void *dev[8];
-    MSL_HIP_TRY(stage(src, bytes, 8, 8, mem, h->planeIn, st, dev));
-    D.coef = (const float *)dev[0]; D.nPlanes = (const int32_t *)dev[1]; D.Tcw = (const float *)dev[2]; D.mpW = (const float *)dev[3];
-    D.mpFlags = (const uint8_t *)dev[4]; D.mpOff = (const int32_t *)dev[5]; D.mpPts = (const float *)dev[6]; D.nMap = (const int32_t *)dev[7];
+    Stage S(h, mem, out_mem);
+    D.coef = S.in(plane_coef, 4 * p); D.nPlanes = S.in(n_planes, F); D.Tcw = S.in(Tcw, 12 * F); D.mpW = S.in(mp_w, 4 * m);
+    D.mpFlags = S.in(mp_flags, m); D.mpOff = S.in(mp_pt_off, m + F); D.mpPts = S.in(mp_pts, 3 * F * ptcap); D.nMap = S.in(n_map, F);
+    D.match = S.inout(plane_match, 3 * p);                                     // the entries a search does not replace stay
+    D.nmatches = S.out(nmatches, F); D.planeW = S.out(plane_w, 12 * p); D.planeHas = S.out(plane_has, p); D.pMOut = S.out(pM_out, 4 * p);
+    MSL_HIP_TRY(S.error());
     MSL_HIP_TRY(h->planeDis.grow(sizeof(float) * m * MAX_PCAP, st));
     D.dis = (float *)h->planeDis.p;
-    void *out[5] = {plane_match, nmatches, plane_w, plane_has, pM_out}, *dout[5];
-    const size_t outBytes[5] = {12 * p, 4 * F, 48 * p, p, 16 * p};
-    MSL_HIP_TRY(stage(out, outBytes, 5, 1, out_mem, h->planeOut, st, dout));   // plane_match is in/out
-    D.match = (int32_t *)dout[0]; D.nmatches = (int32_t *)dout[1]; D.planeW = (float *)dout[2]; D.planeHas = (uint8_t *)dout[3];
-    D.pMOut = pM_out ? (float *)dout[4] : nullptr;
     hipLaunchKernelGGL(k_plane_dis, dim3((unsigned)n_frames, (unsigned)mcap), dim3(64), 0, st, D);
     MSL_HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_plane_assign, dim3((unsigned)n_frames), dim3(64), 0, st, D);
     MSL_HIP_TRY(hipGetLastError());
-    MSL_HIP_TRY(finish_call(out, dout, outBytes, 5, mem, out_mem, st));
+    MSL_HIP_TRY(S.finish());
     return MSL_OK;
 }
 
@@ -429,23 +423,17 @@ int run_manhattan(msl_match *h, int n_frames, int pcap, int mcap, int fcap, int 
     const size_t F = (size_t)n_frames, p = F * pcap, m = F * mcap, k = F * kcap;
     MfDev D{};
     D.pcap = pcap; D.mcap = mcap; D.fcap = fcap; D.qcap = qcap; D.kcap = kcap; D.prm = *prm;
-    const void *src[13] = {plane_coef, plane_npts, n_planes, plane_match, mp_flags, n_map, full_tab, n_full, part_tab, n_part, kf_Rwc,
-                           kf_coef, kf_npts};
-    const size_t bytes[13] = {16 * p, 4 * p, 4 * F, 12 * p, m, 4 * F, 28 * F * fcap, 4 * F, 20 * F * qcap, 4 * F, 36 * k, 16 * k * pcap,
-                              4 * k * pcap};
-    void *dev[13];
-    MSL_HIP_TRY(stage(src, bytes, 13, 13, mem, h->mfIn, st, dev));
-    D.coef = (const float *)dev[0]; D.npts = (const int32_t *)dev[1]; D.nPlanes = (const int32_t *)dev[2]; D.match = (const int32_t *)dev[3];
-    D.mpFlags = (const uint8_t *)dev[4]; D.nMap = (const int32_t *)dev[5]; D.fullTab = (const int32_t *)dev[6]; D.nFull = (const int32_t *)dev[7];
-    D.partTab = (const int32_t *)dev[8]; D.nPart = (const int32_t *)dev[9]; D.kfRwc = (const float *)dev[10]; D.kfCoef = (const float *)dev[11];
-    D.kfNpts = (const int32_t *)dev[12];
-    void *out[4] = {Rcw, found, full, choice}, *dout[4];
-    const size_t outBytes[4] = {36 * F, 4 * F, 4 * F, 24 * F};
-    MSL_HIP_TRY(stage(out, outBytes, 4, 1, out_mem, h->mfOut, st, dout));   // Rcw is in/out: written only where found
-    D.Rcw = (float *)dout[0]; D.found = (int32_t *)dout[1]; D.full = (int32_t *)dout[2]; D.choice = choice ? (int32_t *)dout[3] : nullptr;
+    Stage S(h, mem, out_mem);
+    D.coef = S.in(plane_coef, 4 * p); D.npts = S.in(plane_npts, p); D.nPlanes = S.in(n_planes, F); D.match = S.in(plane_match, 3 * p);
+    D.mpFlags = S.in(mp_flags, m); D.nMap = S.in(n_map, F); D.fullTab = S.in(full_tab, 7 * F * fcap); D.nFull = S.in(n_full, F);
+    D.partTab = S.in(part_tab, 5 * F * qcap); D.nPart = S.in(n_part, F); D.kfRwc = S.in(kf_Rwc, 9 * k); D.kfCoef = S.in(kf_coef, 4 * k * pcap);
+    D.kfNpts = S.in(kf_npts, k * pcap);
+    D.Rcw = S.inout(Rcw, 9 * F);                                               // written only where found
+    D.found = S.out(found, F); D.full = S.out(full, F); D.choice = S.out(choice, 6 * F);
+    MSL_HIP_TRY(S.error());
     hipLaunchKernelGGL(k_manhattan, dim3((unsigned)n_frames), dim3(MF_NT), 0, st, D);
     MSL_HIP_TRY(hipGetLastError());
-    MSL_HIP_TRY(finish_call(out, dout, outBytes, 4, mem, out_mem, st));
+    MSL_HIP_TRY(S.finish());
     return MSL_OK;
 }
 
@@ -458,8 +446,8 @@ int msl_plane_associate(msl_match *h, int n_frames, int pcap, int mcap, int ptca
                         const float *mp_pts, const int32_t *n_map, msl_mem mem, int32_t *plane_match, int32_t *nmatches, float *plane_w,
                         uint8_t *plane_has, float *pM_out, msl_mem out_mem) noexcept {
     try {
-    return run_associate(h, n_frames, pcap, mcap, ptcap, params, plane_coef, n_planes, Tcw, mp_w, mp_flags, mp_pt_off, mp_pts, n_map, mem,
-                         plane_match, nmatches, plane_w, plane_has, pM_out, out_mem);
+    return run_associate(h, n_frames, pcap, mcap, ptcap, params, plane_coef, n_planes, Tcw, mp_w, mp_flags, mp_pt_off, mp_pts, n_map, mem, plane_match,
+                         nmatches, plane_w, plane_has, pM_out, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -467,12 +455,10 @@ int msl_plane_associate_batch(int device, int n_frames, int pcap, int mcap, int 
                               const float *plane_coef, const int32_t *n_planes, const float *Tcw, const float *mp_w, const uint8_t *mp_flags,
                               const int32_t *mp_pt_off, const float *mp_pts, const int32_t *n_map, msl_mem mem, int32_t *plane_match,
                               int32_t *nmatches, float *plane_w, uint8_t *plane_has, float *pM_out, msl_mem out_mem) noexcept {
-    try {
     // plane_match is an input too: device-memory outputs are read as well
-    return on_default_handle(device, mem == MSL_MEM_DEVICE || out_mem == MSL_MEM_DEVICE, [&](msl_match *h) {
-        return run_associate(h, n_frames, pcap, mcap, ptcap, params, plane_coef, n_planes, Tcw, mp_w, mp_flags, mp_pt_off, mp_pts, n_map,
-                             mem, plane_match, nmatches, plane_w, plane_has, pM_out, out_mem);
-    });
+    try {
+    return abi_call_default(run_associate, device, mem == MSL_MEM_DEVICE || out_mem == MSL_MEM_DEVICE, n_frames, pcap, mcap, ptcap, params, plane_coef,
+                            n_planes, Tcw, mp_w, mp_flags, mp_pt_off, mp_pts, n_map, mem, plane_match, nmatches, plane_w, plane_has, pM_out, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -482,8 +468,8 @@ int msl_manhattan_detect(msl_match *h, int n_frames, int pcap, int mcap, int fca
                          const int32_t *part_tab, const int32_t *n_part, const float *kf_Rwc, const float *kf_coef, const int32_t *kf_npts,
                          msl_mem mem, int32_t *found, int32_t *full, float *Rcw, int32_t *choice, msl_mem out_mem) noexcept {
     try {
-    return run_manhattan(h, n_frames, pcap, mcap, fcap, qcap, kcap, params, plane_coef, plane_npts, n_planes, plane_match, mp_flags, n_map,
-                         full_tab, n_full, part_tab, n_part, kf_Rwc, kf_coef, kf_npts, mem, found, full, Rcw, choice, out_mem);
+    return run_manhattan(h, n_frames, pcap, mcap, fcap, qcap, kcap, params, plane_coef, plane_npts, n_planes, plane_match, mp_flags, n_map, full_tab, n_full,
+                         part_tab, n_part, kf_Rwc, kf_coef, kf_npts, mem, found, full, Rcw, choice, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -493,11 +479,11 @@ int msl_manhattan_detect_batch(int device, int n_frames, int pcap, int mcap, int
                                const int32_t *part_tab, const int32_t *n_part, const float *kf_Rwc, const float *kf_coef,
                                const int32_t *kf_npts, msl_mem mem, int32_t *found, int32_t *full, float *Rcw, int32_t *choice,
                                msl_mem out_mem) noexcept {
+    // Rcw is in/out: device-memory outputs are read as well
     try {
-    return on_default_handle(device, mem == MSL_MEM_DEVICE || out_mem == MSL_MEM_DEVICE, [&](msl_match *h) {
-        return run_manhattan(h, n_frames, pcap, mcap, fcap, qcap, kcap, params, plane_coef, plane_npts, n_planes, plane_match, mp_flags,
-                             n_map, full_tab, n_full, part_tab, n_part, kf_Rwc, kf_coef, kf_npts, mem, found, full, Rcw, choice, out_mem);
-    });
+    return abi_call_default(run_manhattan, device, mem == MSL_MEM_DEVICE || out_mem == MSL_MEM_DEVICE, n_frames, pcap, mcap, fcap, qcap, kcap, params,
+                            plane_coef, plane_npts, n_planes, plane_match, mp_flags, n_map, full_tab, n_full, part_tab, n_part, kf_Rwc, kf_coef, kf_npts, mem,
+                            found, full, Rcw, choice, out_mem);
     } MSL_ABI_CATCH_INT
 }
 

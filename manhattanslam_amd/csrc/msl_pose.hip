@@ -27,35 +27,26 @@ int run_pose(msl_match *h, int n_frames, int cap, int xcap, int lcap, int pcap, 
     D.cap = cap; D.xcap = xcap; D.lcap = lcap; D.pcap = pcap; D.prm = *prm;
     D.deltaMono = (double)(float)std::sqrt(5.991); D.deltaStereo = (double)(float)std::sqrt(7.815);   // Optimizer.cc:88-89 (const float)
     D.deltaPlane = std::sqrt(prm->plane_chi); D.deltaPlaneVP = std::sqrt(prm->plane_chi_vp);
-    const void *src[15] = {kps, un_xy, uright, pt_ref, n_kps, xyz, line_fn, line_xyz, line_has, n_lines, plane_coef, plane_w, plane_has, n_planes, Tcw};
-    const size_t bytes[15] = {sizeof(msl_keypoint) * n, 8 * n, 4 * n, 4 * n, 4 * F, 12 * x, 24 * l, 48 * l, l, 4 * F, 16 * p, 48 * p, p, 4 * F, 48 * F};
-    void *dev[15];
-    MSL_HIP_TRY(stage(src, bytes, 15, 15, mem, h->poseIn, st, dev));
-    D.kps = (const msl_keypoint *)dev[0]; D.unxy = (const float *)dev[1]; D.uright = (const float *)dev[2]; D.ptRef = (const int32_t *)dev[3];
-    D.nKps = (const int32_t *)dev[4]; D.xyz = (const float *)dev[5]; D.lineFn = (const double *)dev[6]; D.lineXyz = (const double *)dev[7];
-    D.lineHas = (const uint8_t *)dev[8]; D.nLines = (const int32_t *)dev[9]; D.planeCoef = (const float *)dev[10]; D.planeW = (const float *)dev[11];
-    D.planeHas = (const uint8_t *)dev[12]; D.nPlanes = (const int32_t *)dev[13]; D.Tcw = (const float *)dev[14];
-    if (Rcw) {                                                                   // optional: staged like the other inputs
-        const void *r[1] = {Rcw};
-        const size_t rb[1] = {36 * F};
-        void *dr[1];
-        MSL_HIP_TRY(stage(r, rb, 1, 1, mem, &h->poseIn[15], st, dr));
-        D.Rcw = (const float *)dr[0];
-    }
-    void *out[5] = {outlier, line_outlier, plane_outlier, Tcw_out, n_good}, *dout[5];
-    const size_t outBytes[5] = {n, l, 3 * p, 48 * F, 4 * F};
-    MSL_HIP_TRY(stage(out, outBytes, 5, 3, out_mem, h->poseOut, st, dout));   // the outlier flags are in/out
-    D.outlier = (uint8_t *)dout[0]; D.lineOutlier = (uint8_t *)dout[1]; D.planeOutlier = (uint8_t *)dout[2];
-    D.TcwOut = (float *)dout[3]; D.nGood = (int32_t *)dout[4];
+    Stage S(h, mem, out_mem);
+    D.kps = S.in(kps, n); D.unxy = S.in(un_xy, 2 * n); D.uright = S.in(uright, n); D.ptRef = S.in(pt_ref, n); D.nKps = S.in(n_kps, F);
+    D.xyz = S.in(xyz, 3 * x); D.lineFn = S.in(line_fn, 3 * l); D.lineXyz = S.in(line_xyz, 6 * l); D.lineHas = S.in(line_has, l);
+    D.nLines = S.in(n_lines, F); D.planeCoef = S.in(plane_coef, 4 * p); D.planeW = S.in(plane_w, 12 * p); D.planeHas = S.in(plane_has, p);
+    D.nPlanes = S.in(n_planes, F); D.Tcw = S.in(Tcw, 12 * F);
+    D.Rcw = S.in(Rcw, 9 * F);                                                    // optional
+    D.outlier = S.inout(outlier, n); D.lineOutlier = S.inout(line_outlier, l); D.planeOutlier = S.inout(plane_outlier, 3 * p);
+    D.TcwOut = S.out(Tcw_out, 12 * F); D.nGood = S.out(n_good, F);
+    MSL_HIP_TRY(S.error());
     if (trans) {
         MSL_HIP_TRY(launch_pose_translation(D, n_frames, st));
     } else {
         hipLaunchKernelGGL(k_pose<false>, dim3((unsigned)n_frames), dim3(NT), 0, st, static_cast<const PoseDev &>(D));
         MSL_HIP_TRY(hipGetLastError());
     }
-    MSL_HIP_TRY(finish_call(out, dout, outBytes, 5, mem, out_mem, st));
+    MSL_HIP_TRY(S.finish());
     return MSL_OK;
 }
+
+constexpr const float *NO_RCW = nullptr;   // msl_pose_optimize has no Manhattan rotation
 
 }  // namespace
 
@@ -67,12 +58,12 @@ int msl_pose_optimize(msl_match *h, int n_frames, int cap, int xcap, int lcap, i
                       const uint8_t *plane_has, const int32_t *n_planes, const float *Tcw, msl_mem mem, uint8_t *outlier, uint8_t *line_outlier,
                       uint8_t *plane_outlier, float *Tcw_out, int32_t *n_good, msl_mem out_mem) noexcept {
     try {
-    return run_pose(h, n_frames, cap, xcap, lcap, pcap, params, kps, un_xy, uright, pt_ref, n_kps, xyz, line_fn, line_xyz, line_has, n_lines,
-                    plane_coef, plane_w, plane_has, n_planes, Tcw, nullptr, false, mem, outlier, line_outlier, plane_outlier, Tcw_out, n_good,
-                    out_mem);
+    return run_pose(h, n_frames, cap, xcap, lcap, pcap, params, kps, un_xy, uright, pt_ref, n_kps, xyz, line_fn, line_xyz, line_has, n_lines, plane_coef,
+                    plane_w, plane_has, n_planes, Tcw, NO_RCW, false, mem, outlier, line_outlier, plane_outlier, Tcw_out, n_good, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
+// In the _batch forms the outlier flags are inputs too: device-memory ones are read as well.
 int msl_pose_optimize_batch(int device, int n_frames, int cap, int xcap, int lcap, int pcap, const msl_pose_params *params,
                             const msl_keypoint *kps, const float *un_xy, const float *uright, const int32_t *pt_ref, const int32_t *n_kps,
                             const float *xyz, const double *line_fn, const double *line_xyz, const uint8_t *line_has, const int32_t *n_lines,
@@ -80,12 +71,9 @@ int msl_pose_optimize_batch(int device, int n_frames, int cap, int xcap, int lca
                             msl_mem mem, uint8_t *outlier, uint8_t *line_outlier, uint8_t *plane_outlier, float *Tcw_out, int32_t *n_good,
                             msl_mem out_mem) noexcept {
     try {
-    // the outlier flags are inputs too: device-memory ones are read as well
-    return on_default_handle(device, mem == MSL_MEM_DEVICE || out_mem == MSL_MEM_DEVICE, [&](msl_match *h) {
-        return run_pose(h, n_frames, cap, xcap, lcap, pcap, params, kps, un_xy, uright, pt_ref, n_kps, xyz, line_fn, line_xyz, line_has, n_lines,
-                        plane_coef, plane_w, plane_has, n_planes, Tcw, nullptr, false, mem, outlier, line_outlier, plane_outlier, Tcw_out, n_good,
-                        out_mem);
-    });
+    return abi_call_default(run_pose, device, mem == MSL_MEM_DEVICE || out_mem == MSL_MEM_DEVICE, n_frames, cap, xcap, lcap, pcap, params, kps, un_xy, uright,
+                            pt_ref, n_kps, xyz, line_fn, line_xyz, line_has, n_lines, plane_coef, plane_w, plane_has, n_planes, Tcw, NO_RCW, false, mem,
+                            outlier, line_outlier, plane_outlier, Tcw_out, n_good, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -96,8 +84,8 @@ int msl_pose_optimize_translation(msl_match *h, int n_frames, int cap, int xcap,
                                   const float *Tcw, const float *Rcw, msl_mem mem, uint8_t *outlier, uint8_t *line_outlier,
                                   uint8_t *plane_outlier, float *Tcw_out, int32_t *n_good, msl_mem out_mem) noexcept {
     try {
-    return run_pose(h, n_frames, cap, xcap, lcap, pcap, params, kps, un_xy, uright, pt_ref, n_kps, xyz, line_fn, line_xyz, line_has, n_lines,
-                    plane_coef, plane_w, plane_has, n_planes, Tcw, Rcw, true, mem, outlier, line_outlier, plane_outlier, Tcw_out, n_good, out_mem);
+    return run_pose(h, n_frames, cap, xcap, lcap, pcap, params, kps, un_xy, uright, pt_ref, n_kps, xyz, line_fn, line_xyz, line_has, n_lines, plane_coef,
+                    plane_w, plane_has, n_planes, Tcw, Rcw, true, mem, outlier, line_outlier, plane_outlier, Tcw_out, n_good, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -109,11 +97,9 @@ int msl_pose_optimize_translation_batch(int device, int n_frames, int cap, int x
                                         uint8_t *outlier, uint8_t *line_outlier, uint8_t *plane_outlier, float *Tcw_out, int32_t *n_good,
                                         msl_mem out_mem) noexcept {
     try {
-    return on_default_handle(device, mem == MSL_MEM_DEVICE || out_mem == MSL_MEM_DEVICE, [&](msl_match *h) {
-        return run_pose(h, n_frames, cap, xcap, lcap, pcap, params, kps, un_xy, uright, pt_ref, n_kps, xyz, line_fn, line_xyz, line_has, n_lines,
-                        plane_coef, plane_w, plane_has, n_planes, Tcw, Rcw, true, mem, outlier, line_outlier, plane_outlier, Tcw_out, n_good,
-                        out_mem);
-    });
+    return abi_call_default(run_pose, device, mem == MSL_MEM_DEVICE || out_mem == MSL_MEM_DEVICE, n_frames, cap, xcap, lcap, pcap, params, kps, un_xy, uright,
+                            pt_ref, n_kps, xyz, line_fn, line_xyz, line_has, n_lines, plane_coef, plane_w, plane_has, n_planes, Tcw, Rcw, true, mem, outlier,
+                            line_outlier, plane_outlier, Tcw_out, n_good, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
