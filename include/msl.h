@@ -805,7 +805,7 @@ MSL_API int msl_sf_set_stream(msl_sf *h, void *hip_stream) MSL_NOEXCEPT;
  * sooner: msl_sf_set_batch_capacity with a new capacity, a host-image batch whose images take more bytes per frame than the staged ones, and a
  * device-memory msl_sf_fuse_resident_batch_d16 batch whose converted depth does not fit the staged depth slots.  Each waits for the surfel
  * handle's own streams only, not for work another handle enqueued on the images: the caller lets that work return first.  MSL_ERR_INVALID when
- * the handle's last batch had no host images. */
+ * the handle's last batch had no host images, and after any of those three releases until the next host-image batch has run. */
 MSL_API int msl_sf_staged_gray(msl_sf *h, const uint8_t **gray_dev, size_t *row_stride, size_t *frame_stride, void **uploaded_event) MSL_NOEXCEPT;
 
 

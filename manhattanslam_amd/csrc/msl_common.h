@@ -96,6 +96,7 @@ struct KernelProfiler {
     // (the events then carry the dispatch's own start/end timestamps), or false when kernel k is not being timed.
     bool kernel_pair(int k, hipEvent_t *a, hipEvent_t *b);
     void drain();  // requires the stream to be idle
+    Pair *next_pair(int k);  // the pair the next timed launch of kernel k takes (not yet counted), growing the pool; null when that fails
     void set_mode(int m) { on = m != 0; mask = (unsigned)m; for (int i = 0; i < 16; i++) { ms[i] = 0; launches[i] = 0; tick[i] = 0; } }
     void destroy();
 };

@@ -70,18 +70,23 @@ hipError_t grow_all(hipStream_t st, std::initializer_list<Need> bufs) {
     return hipSuccess;
 }
 
-void KernelProfiler::begin(int k, hipStream_t s) {
-    open_ = false;
-    if (!on || !((mask >> k) & 1u)) return;
+KernelProfiler::Pair *KernelProfiler::next_pair(int k) {
     if (npairs == cap) {
         int ncap = cap ? cap * 2 : 256;
         Pair *np = (Pair *)realloc(pairs, sizeof(Pair) * ncap);
-        if (!np) return;
+        if (!np) return nullptr;
         for (int i = cap; i < ncap; i++) { (void)hipEventCreate(&np[i].a); (void)hipEventCreate(&np[i].b); }
         pairs = np; cap = ncap;
     }
     pairs[npairs].k = k;
-    (void)hipEventRecord(pairs[npairs].a, s);
+    return &pairs[npairs];
+}
+void KernelProfiler::begin(int k, hipStream_t s) {
+    open_ = false;
+    if (!on || !((mask >> k) & 1u)) return;
+    Pair *p = next_pair(k);
+    if (!p) return;
+    (void)hipEventRecord(p->a, s);
     open_ = true;
 }
 void KernelProfiler::end(hipStream_t s) {
@@ -93,15 +98,9 @@ void KernelProfiler::end(hipStream_t s) {
 bool KernelProfiler::kernel_pair(int k, hipEvent_t *a, hipEvent_t *b) {
     if (!on || !((mask >> k) & 1u)) return false;
     if (stride > 1 && (tick[k & 15]++ % (unsigned)stride) != 0) return false;
-    if (npairs == cap) {
-        int ncap = cap ? cap * 2 : 256;
-        Pair *np = (Pair *)realloc(pairs, sizeof(Pair) * ncap);
-        if (!np) return false;
-        for (int i = cap; i < ncap; i++) { (void)hipEventCreate(&np[i].a); (void)hipEventCreate(&np[i].b); }
-        pairs = np; cap = ncap;
-    }
-    pairs[npairs].k = k;
-    *a = pairs[npairs].a; *b = pairs[npairs].b;
+    Pair *p = next_pair(k);
+    if (!p) return false;
+    *a = p->a; *b = p->b;
     npairs++;
     return true;
 }

@@ -37,20 +37,23 @@ struct msl_sf {
     unsigned long long kfClassic = 0, kfDeferred = 0;   // keyframes that went through the classic pair of launches / through deferred windows (msl_sf_debug_scratch, which = 5)
     int dealG = 0;                 // the k_fuse grid SfDev::deal currently is a permutation for (0: none yet) -- screen-position dealing, msl_sf_map.hip
     hipStream_t copyStream = nullptr;   // host-image mode: the H2D copies of slot set i + 1 run beside the superpixel kernels of set i
-    hipEvent_t evH2D[2] = {nullptr, nullptr};
-    hipEvent_t evPre[2] = {nullptr, nullptr}, evMap[2] = {nullptr, nullptr}, evCopy[2] = {nullptr, nullptr};
-    bool evMapValid[2] = {false, false}, evCopyValid[2] = {false, false}, evPreValid[2] = {false, false};
+    // Synchronisation state of one of the two slot sets.  h2d: the set's staged images have arrived (recorded by every host-image batch; msl_sf_staged_gray
+    // hands it to other handles); pre / map: the set's last superpixel stage / map stage is done; copy: its pinned FrameDev staging has been read
+    struct SlotSet { hipEvent_t h2d = nullptr, pre = nullptr, map = nullptr, copy = nullptr; bool preValid = false, mapValid = false, copyValid = false; } sets[2];
     unsigned long long batchNo = 0;
     int stagedSet = -1; size_t stagedGs = 0;   // slot set / row stride of the gray images the last host-image batch staged (msl_sf_staged_gray); -1: none
     int lastSlot = 0;
+    // One image kind of host-image calls, staged per slot: 2 * maxBatch slots of `stride` bytes each
+    struct ImageSlots {
+        DevBuf buf; size_t stride = 0;
+        uint8_t *at(size_t slot) const { return (uint8_t *)buf.p + slot * stride; }
+    };
     // The slot set, allocated to exactly 2 * maxBatch slots by alloc_slots: the per-slot arrays behind SfDev's bases, the pinned FrameDev staging,
-    // and the images of host-image calls (staged per slot, allocated by the first such call; the ...Cap are their per-slot strides in bytes)
+    // and the images of host-image calls (allocated by the first such call; depth16: the raw 16-bit depth of msl_sf_fuse_resident_batch_d16)
     struct Slots {
         DevBuf frames, seeds, seedsTmp, cand, candOk, fused, tex, fuseRec, index, amap, tmin, arec, pxInv, wl, wlCount, chunkAbort, changed;
         PinBuf hFrames;
-        DevBuf gray, depth, member;
-        size_t grayCap = 0, depthCap = 0, memberCap = 0;
-        DevBuf depth16; size_t depth16Cap = 0;   // raw 16-bit depth of host-image calls (msl_sf_fuse_resident_batch_d16)
+        ImageSlots gray, depth, member, depth16;
     } slot;
     DevBuf d_ctr; PinBuf h_ctr;
     DevBuf d_tickets, d_delU, d_dc, d_projTab;
@@ -174,7 +177,16 @@ int map_realloc(msl_sf *h, size_t cap, size_t keep) {
     return write_ctl(h);
 }
 
+// The staged gray, depth and member images go together (a later host-image call allocates all three anew), and msl_sf_staged_gray has
+// nothing to hand out until that call has run.  Every path that frees them comes through here.
+void release_staged_images(msl_sf *h) {
+    msl_sf::Slots &S = h->slot;
+    S.gray = msl_sf::ImageSlots(); S.depth = msl_sf::ImageSlots(); S.member = msl_sf::ImageSlots();
+    h->stagedSet = -1;
+}
+
 int alloc_slots(msl_sf *h, int maxBatch) {
+    release_staged_images(h);
     h->slot = msl_sf::Slots();   // (the old set goes first)
     msl_sf::Slots &S = h->slot;
     SfDev &D = h->dev;
@@ -202,9 +214,7 @@ int alloc_slots(msl_sf *h, int maxBatch) {
     { const int rc = write_ctl(h); if (rc != MSL_OK) return rc; }
     h->maxBatch = maxBatch;
     h->lastSlot = 0;            // the debug accessors must never index beyond the reallocated slot buffers
-    h->evMapValid[0] = h->evMapValid[1] = false;
-    h->evPreValid[0] = h->evPreValid[1] = false;
-    h->evCopyValid[0] = h->evCopyValid[1] = false;
+    for (msl_sf::SlotSet &t : h->sets) t.preValid = t.mapValid = t.copyValid = false;
     return MSL_OK;
 }
 
@@ -250,197 +260,240 @@ int check_err(msl_sf *h) {
     }
     return MSL_OK;
 }
-// Superpixel stage for slots [slot0, slot0+n) on the pre stream, then the map stage per keyframe on the map stream.
-// depth16 != nullptr: the depth images are raw 16-bit values (rows d16s bytes apart, frames d16fs bytes apart) that become metres on the device,
-// (float)raw * depthFactor (src/Frame.cc:96-97); `depth` / ds / dfs are ignored then.
-int run_batch(msl_sf *h, int n, const int32_t *refs, const uint8_t *gray, size_t gs, size_t gfs, const float *depth, size_t ds, size_t dfs,
-              const int32_t *member, size_t ms, size_t mfs, msl_mem mem, const float *poses, bool compact, const uint16_t *depth16 = nullptr,
-              size_t d16s = 0, size_t d16fs = 0, float depthFactor = 1.0f) {
-    SfDev &D = h->dev;
-    const int W = D.W, H = D.H;
+// The images of one batch as the caller handed them over.  Per kind: base pointer, row stride and frame stride in bytes, and (from check_images) the
+// bytes actually present in one image -- the last row carries no stride padding.
+struct ImageArg { const void *p = nullptr; size_t row = 0, frame = 0, bytes = 0; };
+struct BatchImages {
+    ImageArg gray, depth, depth16, member;   // (a frame stride left out is 0: one keyframe)
+    msl_mem mem = MSL_MEM_HOST; float depthFactor = 1.0f;
+    // the depth images are raw 16-bit values that become metres on the device, (float)raw * depthFactor (src/Frame.cc:96-97); `depth` is ignored then
+    bool d16() const { return depth16.p != nullptr; }
+};
+
+int check_images(const msl_sf *h, int n, const int32_t *refs, const float *poses, BatchImages &I) {
+    const size_t W = (size_t)h->dev.W, H = (size_t)h->dev.H;
+    ImageArg &g = I.gray, &d = I.depth, &r = I.depth16, &m = I.member;
     if (n < 1 || n > h->maxBatch) { set_error("msl_sf: batch of %d keyframes exceeds the batch capacity %d", n, h->maxBatch); return MSL_ERR_INVALID; }
-    const bool d16 = depth16 != nullptr;
-    if (d16) {
-        if (d16s < (size_t)W * 2 || (d16s & 1) || (d16fs & 1) || ((uintptr_t)depth16 & 1)) { set_error("msl_sf: bad 16-bit depth pointer or strides"); return MSL_ERR_INVALID; }
-        ds = (size_t)W * 4; dfs = ds * (size_t)H;   // the converted images are tightly packed
+    if (I.d16()) {
+        if (r.row < W * 2 || (r.row & 1) || (r.frame & 1) || ((uintptr_t)r.p & 1)) { set_error("msl_sf: bad 16-bit depth pointer or strides"); return MSL_ERR_INVALID; }
+        d.row = W * 4; d.frame = d.row * H;   // the converted images are tightly packed
     }
-    if (!gray || (!depth && !d16) || !member || !poses || !refs || gs < (size_t)W || ds < (size_t)W * 4 || ms < (size_t)((W + 1) / 2) * 4 || (ds & 3) || (ms & 3)) {
+    if (!g.p || (!d.p && !I.d16()) || !m.p || !poses || !refs || g.row < W || d.row < W * 4 || m.row < ((W + 1) / 2) * 4 || (d.row & 3) || (m.row & 3)) {
         set_error("msl_sf: bad image pointers or strides");
         return MSL_ERR_INVALID;
     }
-    if (gs * (size_t)H >= (1ull << 32) || ds * (size_t)H >= (1ull << 32) || ms * (size_t)((H + 1) / 2) >= (1ull << 32)) {   // (the kernels address an image with 32-bit byte offsets)
+    if (g.row * H >= (1ull << 32) || d.row * H >= (1ull << 32) || m.row * ((H + 1) / 2) >= (1ull << 32)) {   // (the kernels address an image with 32-bit byte offsets)
         set_error("msl_sf: image rows span 4 GB or more");
         return MSL_ERR_INVALID;
     }
-    if (compact) {
-        h->mirrorValid = false;   // the resident map moves on without the host-vector caller
-        // The reference's mvLocalSurfels is an unbounded std::vector (include/Map.h:130): grow the resident map before a batch could
-        // overflow it.  Every keyframe adds at most nseeds surfels, so the host only needs an upper bound of the live count; the
-        // exact count is read back (one sync) only when that bound reaches the capacity.
-        const size_t need = (size_t)n * (size_t)D.nseeds;
-        consume_snapshots(h, (size_t)D.nseeds);
+    g.bytes = g.row * (H - 1) + W; d.bytes = d.row * (H - 1) + W * 4;
+    m.bytes = m.row * ((H + 1) / 2 - 1) + ((W + 1) / 2) * 4;   // the membership image is ceil(H / 2) x ceil(W / 2) (PlaneDetection's cloud size)
+    r.bytes = I.d16() ? r.row * (H - 1) + W * 2 : 0;
+    return MSL_OK;
+}
+
+// Room in the resident map for n more keyframes.  The reference's mvLocalSurfels is an unbounded std::vector (include/Map.h:130): grow the resident
+// map before a batch could overflow it.  Every keyframe adds at most nseeds surfels, so the host only needs an upper bound of the live count; the
+// exact count is read back (one sync) only when that bound reaches the capacity.
+int reserve_map(msl_sf *h, int n) {
+    const SfDev &D = h->dev;
+    h->mirrorValid = false;   // the resident map moves on without the host-vector caller
+    const size_t need = (size_t)n * (size_t)D.nseeds;
+    consume_snapshots(h, (size_t)D.nseeds);
+    if (h->liveBound + need > D.cap) {
+        int rc = read_ctr(h);
+        if (rc != MSL_OK) return rc;
+        rc = check_err(h);
+        if (rc != MSL_OK) return rc;
         if (h->liveBound + need > D.cap) {
-            int rc = read_ctr(h);
+            rc = map_realloc(h, 2 * h->liveBound + 2 * need + 65536, h->liveBound);
             if (rc != MSL_OK) return rc;
-            rc = check_err(h);
-            if (rc != MSL_OK) return rc;
-            if (h->liveBound + need > D.cap) {
-                rc = map_realloc(h, 2 * h->liveBound + 2 * need + 65536, h->liveBound);
-                if (rc != MSL_OK) return rc;
-            }
         }
-        h->liveBound += need;
-        h->kfEnq += (unsigned long long)n;
     }
-    const int set = (int)(h->batchNo & 1), slot0 = set * h->maxBatch;
-    if (mem != MSL_MEM_HOST) h->stagedSet = -1;
-    hipStream_t sp = h->preStream, sm = h->mapStream;
-    if (h->evMapValid[set] && sp != sm) MSL_HIP_TRY(hipStreamWaitEvent(sp, h->evMap[set], 0));   // the set's previous user is done
-    D.gstride = gs; D.gbytes = gs * (size_t)(H - 1) + W; D.dstride = ds / 4; D.mstride = ms / 4;
-    D.gsB = (unsigned)gs; D.dsB = (unsigned)ds; D.msB = (unsigned)ms;
-    // bytes actually present in the caller's buffers: the last row carries no stride padding
-    const size_t d16b = d16 ? d16s * (size_t)(H - 1) + (size_t)W * 2 : 0;
-    const size_t gb = gs * (size_t)(H - 1) + W, db = ds * (size_t)(H - 1) + (size_t)W * 4, mb = ms * (size_t)((H + 1) / 2 - 1) + (size_t)((W + 1) / 2) * 4;   // the membership image is ceil(H / 2) x ceil(W / 2) (PlaneDetection's cloud size)
+    h->liveBound += need;
+    h->kfEnq += (unsigned long long)n;
+    return MSL_OK;
+}
+
+// n frames of one image kind into slots dstStride bytes apart: tightly packed frames of exactly the slot stride (the streaming case) travel as ONE
+// copy, otherwise one copy per frame
+int copy_frames(uint8_t *dst, size_t dstStride, int n, const void *src, size_t frameStride, size_t bytes, hipStream_t st) {
+    if (frameStride == bytes && dstStride == bytes) {
+        MSL_HIP_TRY(hipMemcpyAsync(dst, src, bytes * (size_t)n, hipMemcpyHostToDevice, st));
+        return MSL_OK;
+    }
+    for (int f = 0; f < n; f++) MSL_HIP_TRY(hipMemcpyAsync(dst + f * dstStride, (const uint8_t *)src + f * frameStride, bytes, hipMemcpyHostToDevice, st));
+    return MSL_OK;
+}
+
+// Where the images of a batch lie on the device: frame f of a kind at its base + f * its step (bytes)
+struct FrameSrc { const uint8_t *gray, *depth, *member; size_t grayStep, depthStep, memberStep; };
+
+// Host images are staged in the set's slots (copy stream), device-resident raw depth is converted into the handle's float slots (superpixel
+// stream); every other device image is read where the caller has it.
+int stage_images(msl_sf *h, int set, int n, const BatchImages &I, FrameSrc &src) {
     msl_sf::Slots &S = h->slot;
-    const size_t slots = 2 * (size_t)h->maxBatch;
-    if (mem == MSL_MEM_HOST) {
-        if (gb > S.grayCap || db > S.depthCap || mb > S.memberCap) {
-            int rc = sync_all(h);
+    msl_sf::SlotSet &T = h->sets[set];
+    const ImageArg &g = I.gray, &d = I.depth, &r = I.depth16, &m = I.member;
+    const int W = h->dev.W, H = h->dev.H;
+    const size_t slot0 = (size_t)set * (size_t)h->maxBatch, slots = 2 * (size_t)h->maxBatch;
+    const hipStream_t sp = h->preStream, sm = h->mapStream;
+    if (I.mem != MSL_MEM_HOST) {
+        h->stagedSet = -1;
+        src = {(const uint8_t *)g.p, (const uint8_t *)d.p, (const uint8_t *)m.p, g.frame, d.frame, m.frame};
+        if (!I.d16()) return MSL_OK;
+        if (d.bytes > S.depth.stride) {
+            const int rc = sync_all(h);
             if (rc != MSL_OK) return rc;
-            S.gray = DevBuf(); S.depth = DevBuf(); S.member = DevBuf(); S.grayCap = S.depthCap = S.memberCap = 0;
-            MSL_HIP_TRY(grow_all(sm, {{S.gray, gb * slots}, {S.depth, db * slots}, {S.member, mb * slots}}));
-            S.grayCap = gb; S.depthCap = db; S.memberCap = mb;
+            release_staged_images(h);
+            MSL_HIP_TRY(S.depth.buf.grow(d.bytes * slots, sm));
+            S.depth.stride = d.bytes;
         }
-        if (d16 && d16b > S.depth16Cap) {
-            int rc = sync_all(h);
-            if (rc != MSL_OK) return rc;
-            S.depth16Cap = 0;
-            MSL_HIP_TRY(S.depth16.grow(d16b * slots, sm));
-            S.depth16Cap = d16b;
-        }
-        uint8_t *sg = (uint8_t *)S.gray.p, *sd = (uint8_t *)S.depth.p, *smb = (uint8_t *)S.member.p, *s16 = (uint8_t *)S.depth16.p;
-        // The images travel on their own stream so that they overlap the superpixel kernels of the previous call (the other slot set);
-        // with caller-provided streams (msl_sf_set_stream) everything stays on that one stream.
-        hipStream_t sc = (h->ownStreams && h->copyStream) ? h->copyStream : sp;
-        // (round 6) the staged images of a set are read by the SUPERPIXEL stage only -- the map stage works on the slot arrays (texels, seed records,
-        // candidates) -- so the copies of call k wait for the superpixel stage of call k - 2 (evPre), not for its map stage (evMap, which the
-        // superpixel stage of call k still waits for): the link runs up to two calls ahead of the map chain instead of in step with it
-        // (A/B on one box, bench.py --io host: 17.6 k -> 19.0 k frames/s with f32 depth, 18.8 k -> 20.1 k with raw 16-bit depth)
-        if (sc != sp && h->evPreValid[set]) MSL_HIP_TRY(hipStreamWaitEvent(sc, h->evPre[set], 0));
-        h->prof.begin(SK_COPY, sc);
-        // Tightly packed frame arrays (the streaming case) travel as ONE copy per image kind instead of one per frame; a membership image
-        // shared by all keyframes of the call (member_frame_stride == 0) is staged once.
-        const bool packedG = n > 1 && gfs == gb && S.grayCap == gb, packedD = !d16 && n > 1 && dfs == db && S.depthCap == db;
-        const bool packed16 = d16 && n > 1 && d16fs == d16b && S.depth16Cap == d16b;
-        const bool packedM = n > 1 && mfs == mb && S.memberCap == mb;
-        if (packedG) MSL_HIP_TRY(hipMemcpyAsync(sg + (size_t)slot0 * S.grayCap, gray, gb * (size_t)n, hipMemcpyHostToDevice, sc));
-        if (packedD) MSL_HIP_TRY(hipMemcpyAsync(sd + (size_t)slot0 * S.depthCap, depth, db * (size_t)n, hipMemcpyHostToDevice, sc));
-        if (packed16) MSL_HIP_TRY(hipMemcpyAsync(s16 + (size_t)slot0 * S.depth16Cap, depth16, d16b * (size_t)n, hipMemcpyHostToDevice, sc));
-        if (packedM) MSL_HIP_TRY(hipMemcpyAsync(smb + (size_t)slot0 * S.memberCap, member, mb * (size_t)n, hipMemcpyHostToDevice, sc));
-        if (mfs == 0) MSL_HIP_TRY(hipMemcpyAsync(smb + (size_t)slot0 * S.memberCap, member, mb, hipMemcpyHostToDevice, sc));
-        for (int f = 0; f < n; f++) {
-            const size_t s = slot0 + f;
-            if (!packedG) MSL_HIP_TRY(hipMemcpyAsync(sg + s * S.grayCap, gray + f * gfs, gb, hipMemcpyHostToDevice, sc));
-            if (!d16 && !packedD) MSL_HIP_TRY(hipMemcpyAsync(sd + s * S.depthCap, (const uint8_t *)depth + f * dfs, db, hipMemcpyHostToDevice, sc));
-            if (d16 && !packed16) MSL_HIP_TRY(hipMemcpyAsync(s16 + s * S.depth16Cap, (const uint8_t *)depth16 + f * d16fs, d16b, hipMemcpyHostToDevice, sc));
-            if (!packedM && mfs != 0) MSL_HIP_TRY(hipMemcpyAsync(smb + s * S.memberCap, (const uint8_t *)member + f * mfs, mb, hipMemcpyHostToDevice, sc));
-        }
-        if (d16)   // raw -> metres behind the copies, on their stream (same rows of stride d16s in the staging slots; frames depth16Cap bytes apart)
-            sp_launch_depth_u16(sc, s16 + (size_t)slot0 * S.depth16Cap, d16s, S.depth16Cap, (float *)(sd + (size_t)slot0 * S.depthCap), S.depthCap / 4, W, H, n, depthFactor);
-        h->prof.end(sc);
-        MSL_HIP_TRY(hipEventRecord(h->evH2D[set], sc));   // (always: msl_sf_staged_gray hands it to other handles)
-        if (sc != sp) MSL_HIP_TRY(hipStreamWaitEvent(sp, h->evH2D[set], 0));
-        h->stagedSet = set; h->stagedGs = gs;
+        sp_launch_depth_u16(sp, r.p, r.row, r.frame, (float *)S.depth.at(slot0), S.depth.stride / 4, W, H, n, I.depthFactor);
+        src.depth = S.depth.at(slot0); src.depthStep = S.depth.stride;
+        return MSL_OK;
     }
-    if (d16 && mem != MSL_MEM_HOST) {   // device-resident raw depth: converted into the handle's float slots on the superpixel stream
-        if (db > S.depthCap) {
-            int rc = sync_all(h);
-            if (rc != MSL_OK) return rc;
-            S.gray = DevBuf(); S.depth = DevBuf(); S.member = DevBuf(); S.grayCap = S.depthCap = S.memberCap = 0;   // (a later host-image call allocates all three anew)
-            MSL_HIP_TRY(S.depth.grow(db * slots, sm));
-            S.depthCap = db;
-        }
-        sp_launch_depth_u16(sp, depth16, d16s, d16fs, (float *)((uint8_t *)S.depth.p + (size_t)slot0 * S.depthCap), S.depthCap / 4, W, H, n, depthFactor);
+    if (g.bytes > S.gray.stride || d.bytes > S.depth.stride || m.bytes > S.member.stride) {
+        const int rc = sync_all(h);
+        if (rc != MSL_OK) return rc;
+        release_staged_images(h);
+        MSL_HIP_TRY(grow_all(sm, {{S.gray.buf, g.bytes * slots}, {S.depth.buf, d.bytes * slots}, {S.member.buf, m.bytes * slots}}));
+        S.gray.stride = g.bytes; S.depth.stride = d.bytes; S.member.stride = m.bytes;
     }
-    const uint8_t *sd = (const uint8_t *)S.depth.p;
-    if (h->evCopyValid[set]) MSL_HIP_TRY(hipEventSynchronize(h->evCopy[set]));   // pinned staging of this set is free again
-    FrameDev *hf = (FrameDev *)S.hFrames.p;
+    if (r.bytes > S.depth16.stride) {
+        const int rc = sync_all(h);
+        if (rc != MSL_OK) return rc;
+        S.depth16.stride = 0;
+        MSL_HIP_TRY(S.depth16.buf.grow(r.bytes * slots, sm));
+        S.depth16.stride = r.bytes;
+    }
+    // The images travel on their own stream so that they overlap the superpixel kernels of the previous call (the other slot set);
+    // with caller-provided streams (msl_sf_set_stream) everything stays on that one stream.
+    const hipStream_t sc = (h->ownStreams && h->copyStream) ? h->copyStream : sp;
+    // The staged images of a set are read by the SUPERPIXEL stage only -- the map stage works on the slot arrays (texels, seed records, candidates) --
+    // so the copies of call k wait for the superpixel stage of call k - 2 (pre), not for its map stage (map, which the superpixel stage of call k
+    // still waits for): the link runs up to two calls ahead of the map chain (bench.py --io host: 17.6 k -> 19.0 k frames/s with f32 depth,
+    // 18.8 k -> 20.1 k with raw 16-bit depth)
+    if (sc != sp && T.preValid) MSL_HIP_TRY(hipStreamWaitEvent(sc, T.pre, 0));
+    h->prof.begin(SK_COPY, sc);
+    int rc = copy_frames(S.gray.at(slot0), S.gray.stride, n, g.p, g.frame, g.bytes, sc);
+    if (rc == MSL_OK) rc = I.d16() ? copy_frames(S.depth16.at(slot0), S.depth16.stride, n, r.p, r.frame, r.bytes, sc)
+                                   : copy_frames(S.depth.at(slot0), S.depth.stride, n, d.p, d.frame, d.bytes, sc);
+    // a membership image shared by all keyframes of the call (member_frame_stride == 0) is staged once, in the set's first slot
+    if (rc == MSL_OK) rc = copy_frames(S.member.at(slot0), S.member.stride, m.frame == 0 ? 1 : n, m.p, m.frame, m.bytes, sc);
+    if (rc != MSL_OK) return rc;
+    if (I.d16())   // raw -> metres behind the copies, on their stream (same rows of stride r.row in the staging slots)
+        sp_launch_depth_u16(sc, S.depth16.at(slot0), r.row, S.depth16.stride, (float *)S.depth.at(slot0), S.depth.stride / 4, W, H, n, I.depthFactor);
+    h->prof.end(sc);
+    MSL_HIP_TRY(hipEventRecord(T.h2d, sc));   // (always: msl_sf_staged_gray hands it to other handles)
+    if (sc != sp) MSL_HIP_TRY(hipStreamWaitEvent(sp, T.h2d, 0));
+    h->stagedSet = set; h->stagedGs = g.row;
+    src = {S.gray.at(slot0), S.depth.at(slot0), S.member.at(slot0), S.gray.stride, S.depth.stride, m.frame == 0 ? 0 : S.member.stride};
+    return MSL_OK;
+}
+
+// The set's pinned FrameDev table (image addresses, pose and its inverse, reference index) and its one copy to the device
+int fill_frames(msl_sf *h, int set, int n, const FrameSrc &src, const int32_t *refs, const float *poses) {
+    msl_sf::SlotSet &T = h->sets[set];
+    const size_t slot0 = (size_t)set * (size_t)h->maxBatch;
+    if (T.copyValid) MSL_HIP_TRY(hipEventSynchronize(T.copy));   // pinned staging of this set is free again
+    FrameDev *hf = (FrameDev *)h->slot.hFrames.p + slot0;
     for (int f = 0; f < n; f++) {
-        FrameDev &F = hf[slot0 + f];
-        const size_t s = slot0 + f;
-        if (mem == MSL_MEM_HOST) {
-            F.gray = (const uint8_t *)S.gray.p + s * S.grayCap; F.depth = (const float *)(sd + s * S.depthCap);
-            F.member = (const int32_t *)((const uint8_t *)S.member.p + (mfs == 0 ? (size_t)slot0 : s) * S.memberCap);
-        } else {
-            F.gray = gray + f * gfs; F.member = (const int32_t *)((const uint8_t *)member + f * mfs);
-            F.depth = d16 ? (const float *)(sd + s * S.depthCap) : (const float *)((const uint8_t *)depth + f * dfs);
-        }
+        FrameDev &F = hf[f];
+        F.gray = src.gray + f * src.grayStep;
+        F.depth = (const float *)(src.depth + f * src.depthStep);
+        F.member = (const int32_t *)(src.member + f * src.memberStep);
         memcpy(F.pose, poses + 16 * f, sizeof(float) * 16);
         inverse4<float>(F.pose, F.invPose);   // pose.inverse() (:59), adjugate/determinant in float
         F.ref = refs[f]; F._pad = 0;
     }
-    MSL_HIP_TRY(hipMemcpyAsync((FrameDev *)S.frames.p + slot0, hf + slot0, sizeof(FrameDev) * n, hipMemcpyHostToDevice, sp));
-    MSL_HIP_TRY(hipEventRecord(h->evCopy[set], sp));
-    h->evCopyValid[set] = true;
+    MSL_HIP_TRY(hipMemcpyAsync((FrameDev *)h->slot.frames.p + slot0, hf, sizeof(FrameDev) * n, hipMemcpyHostToDevice, h->preStream));
+    MSL_HIP_TRY(hipEventRecord(T.copy, h->preStream));
+    T.copyValid = true;
+    return MSL_OK;
+}
 
+// D with every per-slot base shifted so that blockIdx.y/z == 0 addresses slot0
+SfDev slot_view(const SfDev &D, int slot0) {
     SfDev P = D;
-    // shift every per-slot base so that blockIdx.y/z == 0 addresses slot0
     P.frames = D.frames + slot0; P.seeds = D.seeds + (size_t)slot0 * D.nseeds; P.seedsTmp = D.seedsTmp + (size_t)slot0 * D.nseeds;
     P.cand = D.cand + (size_t)slot0 * D.nseeds; P.candOk = D.candOk + (size_t)slot0 * D.flagStride; P.fused = D.fused + (size_t)slot0 * D.flagStride;
     P.tex = D.tex + (size_t)slot0 * D.pxStride; P.fuseRec = D.fuseRec + (size_t)slot0 * D.nseeds * 3;
     P.index = D.index + (size_t)slot0 * D.pxStride; P.amap = D.amap + (size_t)slot0 * D.pxStride; P.tmin = D.tmin + (size_t)slot0 * D.nseeds;
     P.arec = D.arec + (size_t)slot0 * D.nseeds; P.pxInv = D.pxInv + (size_t)slot0 * D.pxStride; P.wl = D.wl + (size_t)slot0 * D.pxStride; P.wlCount = D.wlCount + slot0;
     P.chunkAbort = D.chunkAbort + slot0 * 32; P.changed = D.changed + slot0 * 8;
-    sp_launch_stage(h->prof, sp, P, n, h->propLds);
-    if (sp != sm) {
-        MSL_HIP_TRY(hipEventRecord(h->evPre[set], sp));
-        h->evPreValid[set] = true;
-        MSL_HIP_TRY(hipStreamWaitEvent(sm, h->evPre[set], 0));
-    }
+    return P;
+}
+
+// The switches of the map chain, read from the environment once per process (by the first batch)
+struct SfPolicy {
+    int dealEvery;               // MSL_SF_DEAL_EVERY (default 4, at least 1): the classic chain deals on every dealEvery-th keyframe of a call
+    bool dealOff;                // MSL_SF_DEAL=0: sub-blocks in array order, for A/B measurements
+    bool deferOff, deferForce;   // MSL_SF_DEFER=0: never a deferred window; =1: always (the parity tests); unset: the policy of launch_map_chain
+};
+const SfPolicy &sf_policy() {
+    static const SfPolicy p = [] {
+        const char *every = getenv("MSL_SF_DEAL_EVERY"), *deal = getenv("MSL_SF_DEAL"), *defer = getenv("MSL_SF_DEFER");
+        return SfPolicy{every ? std::max(1, atoi(every)) : 4, deal && !strcmp(deal, "0"), defer && !strcmp(defer, "0"), defer && !strcmp(defer, "1")};
+    }();
+    return p;
+}
+constexpr double CHURN_MAX = 96.0;   // spawned + deleted surfels per keyframe up to which the one-wave replay beats k_compact (bench.py --map moving: 670)
+// Dealing only while the map (48 bytes per surfel) fits the 256 MB Infinity Cache: a larger map is streamed from HBM, where waves that walk the array in
+// order keep DRAM pages open -- 8 M surfels: k_fuse 76.9 us in array order, 80.5 us dealt (bench.py --surfels 8000000, A/B on one box)
+constexpr int DEAL_MAX_GRID = (4 << 20) / SUB_ITEMS;
+
+// The k_fuse launches of one batch: grid and load hint in sub-blocks, and whether the sub-blocks are dealt by screen position
+struct FuseGrid { int nSubGrid, nSubHint; bool dealOn; };
+FuseGrid fuse_grid(const msl_sf *h, bool compact) {
+    const SfDev &D = h->dev;
     const size_t boundLive = compact ? h->liveBound : D.cap;
     // grid: the last known live count plus a margin (k_fuse is grid-stride, so a map that outgrew it is still covered), never beyond the upper
     // bound; hint: the sub-blocks that were full at the last known count load without waiting for the live count
     const size_t known = std::min(h->liveKnown, boundLive);
-    // (round 6) ... rounded up to a multiple of 64 sub-blocks inside the capacity (a multiple of 32 sub-blocks): the dealing table of the launch before is
+    // ... rounded up to a multiple of 64 sub-blocks inside the capacity (a multiple of 32 sub-blocks): the dealing table of the launch before is
     // a permutation for ONE grid size, so the grid should change rarely -- a wave beyond the live count costs one load
     const size_t subWant = (std::min(known + 2 * (size_t)D.nseeds, boundLive) + SUB_ITEMS - 1) / SUB_ITEMS;
-    const int nSubGrid = (int)std::max<size_t>(8, std::min((subWant + 63) & ~(size_t)63, (size_t)D.cap / SUB_ITEMS));
-    const int nSubHint = (int)(known / SUB_ITEMS);
-    static const int DEAL_EVERY = getenv("MSL_SF_DEAL_EVERY") ? std::max(1, atoi(getenv("MSL_SF_DEAL_EVERY"))) : 4;
-    static const char *dealEnv = getenv("MSL_SF_DEAL");   // "0": sub-blocks in array order (rounds 1-5), for A/B measurements
-    // ... and only while the map (48 bytes per surfel) fits the 256 MB Infinity Cache: a larger map is streamed from HBM, where waves that walk the array in
-    // order keep DRAM pages open -- 8 M surfels: k_fuse 76.9 us in array order, 80.5 us dealt (bench.py --surfels 8000000, A/B on one box)
-    constexpr int DEAL_MAX_GRID = (4 << 20) / SUB_ITEMS;
-    const bool dealOn = !(dealEnv && !strcmp(dealEnv, "0")) && (nSubGrid & 7) == 0 && (size_t)nSubGrid <= h->blkStride && nSubGrid <= DEAL_MAX_GRID;
-    // Map stage.  Deferred compaction (MSL_SF_DEFER=0 turns it off, =1 forces it; unset: the policy below): windows of <= DEFER_WIN keyframes, ONE
-    // launch per keyframe, the window's compactions replayed at its end (msl_sf_map.hip).  Classic (k_fuse + k_compact per keyframe): single
-    // keyframes, the host-vector drop-in, the first keyframe after the map was replaced from outside, and batches enqueued while the recent
-    // churn (spawned + deleted surfels per keyframe, from the asynchronous counter snapshots) is high -- k_compact takes any number of stale or
-    // deleted slots with all its workgroups, the replay's single wave is built for the steady state.  Both leave identical maps.
-    static const char *deferEnv = getenv("MSL_SF_DEFER");   // "0": never; "1": always (the parity tests); unset: the policy below
-    static const bool deferOff = deferEnv && !strcmp(deferEnv, "0"), deferForce = deferEnv && !strcmp(deferEnv, "1");
-    constexpr double CHURN_MAX = 96.0;   // spawned + deleted surfels per keyframe up to which the one-wave replay beats k_compact (bench.py --map moving: 670)
+    FuseGrid g;
+    g.nSubGrid = (int)std::max<size_t>(8, std::min((subWant + 63) & ~(size_t)63, (size_t)D.cap / SUB_ITEMS));
+    g.nSubHint = (int)(known / SUB_ITEMS);
+    g.dealOn = !sf_policy().dealOff && (g.nSubGrid & 7) == 0 && (size_t)g.nSubGrid <= h->blkStride && g.nSubGrid <= DEAL_MAX_GRID;
+    return g;
+}
+
+// Map stage of the n keyframes in `set`, on the map stream.  Deferred compaction (MSL_SF_DEFER=0 turns it off, =1 forces it; unset: the policy
+// below): windows of <= DEFER_WIN keyframes, ONE launch per keyframe, the window's compactions replayed at its end (msl_sf_map.hip).  Classic
+// (k_fuse + k_compact per keyframe): single keyframes, the host-vector drop-in, the first keyframe after the map was replaced from outside, and
+// batches enqueued while the recent churn (spawned + deleted surfels per keyframe, from the asynchronous counter snapshots) is high -- k_compact
+// takes any number of stale or deleted slots with all its workgroups, the replay's single wave is built for the steady state.  Both leave
+// identical maps.
+int launch_map_chain(msl_sf *h, SfDev &P, int set, int n, bool compact) {
+    const SfPolicy &pol = sf_policy();
+    const hipStream_t sp = h->preStream, sm = h->mapStream;
+    const int slot0 = set * h->maxBatch;
+    const FrameDev *hf = (const FrameDev *)h->slot.hFrames.p + slot0;
+    const FuseGrid g = fuse_grid(h, compact);
     // Policy.  The deferred chain is 8 us per keyframe shorter (22.6 against 31 us alone), which pays exactly when the map chain is the critical
     // path: a handle on ONE caller-provided stream (superpixel stage and map stage back to back: 20.8 k against 19.0 k keyframes/s).  With the
     // handle's own two streams the frame-batched superpixel stage is the longer one; k_fuse launches that follow each other without the idle
     // stretch of k_compact in between only take issue slots from it (front end 22 010 against 22 330 frames/s, k_fuse 18.8 against 16.3 us in the
     // timed region), so that shape keeps the classic pair.
-    const bool churny = !deferForce && (h->churn > CHURN_MAX || sp != sm);
+    const bool churny = !pol.deferForce && (h->churn > CHURN_MAX || sp != sm);
     auto classic = [&](int f) {
         P.kf = 0;
-        map_launch_fuse(h->prof, sm, P, f, hf[slot0 + f], nSubGrid, nSubHint, false, dealOn && h->dealG == nSubGrid);
-        // k_compact's second workgroup deals the sub-blocks for the launches that follow (resident mode: 128 workgroups) -- on every DEAL_EVERY-th
+        map_launch_fuse(h->prof, sm, P, f, hf[f], g.nSubGrid, g.nSubHint, false, g.dealOn && h->dealG == g.nSubGrid);
+        // k_compact's second workgroup deals the sub-blocks for the launches that follow (resident mode: 128 workgroups) -- on every dealEvery-th
         // keyframe of a call and whenever the table does not fit the grid: the pass takes one workgroup ~10 us against the compaction's ~6 beside it
         // (32 keys per thread through LDS atomics and scattered stores), and a table a few keyframes old still has nearly every sub-block in the
         // right band (the view moves a fraction of a band per keyframe; a misplaced sub-block only costs its XCD some extra lines)
-        P.dealG = dealOn && compact && (f % DEAL_EVERY == 0 || h->dealG != nSubGrid) ? nSubGrid : 0;
+        P.dealG = g.dealOn && compact && (f % pol.dealEvery == 0 || h->dealG != g.nSubGrid) ? g.nSubGrid : 0;
         map_launch_compact(h->prof, sm, P, f, compact);
-        if (P.dealG) h->dealG = nSubGrid;
+        if (P.dealG) h->dealG = g.nSubGrid;
         h->kfClassic++;
     };
     int f = 0;
     const int fProbe = n / 2;   // only when its profiler slot is enabled: what an event pair reports for an EMPTY dispatch at this place of the chain
-    if (!compact || deferOff || churny || n < 2) {
+    if (!compact || pol.deferOff || churny || n < 2) {
         for (; f < n; f++) { classic(f); if (f == fProbe) map_launch_empty_pair(h->prof, sm); }
     } else {
         if (h->classicNext) { classic(0); f = 1; if (fProbe == 0) map_launch_empty_pair(h->prof, sm); }
@@ -448,22 +501,22 @@ int run_batch(msl_sf *h, int n, const int32_t *refs, const uint8_t *gray, size_t
             const int w = std::min(DEFER_WIN, n - f);
             for (int q = 0; q < w; q++) {
                 P.kf = q; P.prevSlotAbs = slot0 + f + q - 1;
-                map_launch_fuse(h->prof, sm, P, f + q, hf[slot0 + f + q], nSubGrid, nSubHint, true, dealOn && h->dealG == nSubGrid);
+                map_launch_fuse(h->prof, sm, P, f + q, hf[f + q], g.nSubGrid, g.nSubHint, true, g.dealOn && h->dealG == g.nSubGrid);
                 if (f + q == fProbe) map_launch_empty_pair(h->prof, sm);
             }
             P.kf = w; P.prevSlotAbs = slot0 + f + w - 1;
             map_launch_replay(h->prof, sm, P, w, (unsigned)h->blkStride);
             h->kfDeferred += (unsigned long long)w;
-            if (dealOn) { P.dealG = nSubGrid; map_launch_deal(sm, P); h->dealG = nSubGrid; }   // one dealing per window, from the keys of its last keyframe
+            if (g.dealOn) { P.dealG = g.nSubGrid; map_launch_deal(sm, P); h->dealG = g.nSubGrid; }   // one dealing per window, from the keys of its last keyframe
             f += w;
         }
     }
     if (compact) h->classicNext = false;
-    if (sp != sm) { MSL_HIP_TRY(hipEventRecord(h->evMap[set], sm)); h->evMapValid[set] = true; }
+    if (sp != sm) { MSL_HIP_TRY(hipEventRecord(h->sets[set].map, sm)); h->sets[set].mapValid = true; }
     if (compact && h->h_snap.p) {   // snapshot of the live count after this batch (picked up by a later call, never waited for)
         const int i = h->snapNext;
         if (!h->snapBusy[i]) {
-            MSL_HIP_TRY(hipMemcpyAsync((long long *)h->h_snap.p + (size_t)i * msl_sf::SNAPW, D.ctr, sizeof(long long) * msl_sf::SNAPW, hipMemcpyDeviceToHost, sm));
+            MSL_HIP_TRY(hipMemcpyAsync((long long *)h->h_snap.p + (size_t)i * msl_sf::SNAPW, h->dev.ctr, sizeof(long long) * msl_sf::SNAPW, hipMemcpyDeviceToHost, sm));
             MSL_HIP_TRY(hipEventRecord(h->snapEv[i], sm));
             h->snapKf[i] = h->kfEnq; h->snapBusy[i] = true; h->snapLive[i] = true; h->snapNext = (i + 1) % msl_sf::NSNAP;
         }
@@ -472,6 +525,37 @@ int run_batch(msl_sf *h, int n, const int32_t *refs, const uint8_t *gray, size_t
     h->lastSlot = slot0 + n - 1;
     h->batchNo++;
     return MSL_OK;
+}
+
+// One batch of n keyframes: their images staged in the slot set of this batch, the superpixel stage for all of them on the pre stream, then the
+// map stage per keyframe on the map stream.  compact: the resident map (false: the host-vector drop-in, whose map is the caller's vector).
+int run_batch(msl_sf *h, int n, const int32_t *refs, const float *poses, BatchImages I, bool compact) {
+    int rc = check_images(h, n, refs, poses, I);
+    if (rc != MSL_OK) return rc;
+    if (compact) {
+        rc = reserve_map(h, n);
+        if (rc != MSL_OK) return rc;
+    }
+    SfDev &D = h->dev;
+    const int set = (int)(h->batchNo & 1);
+    msl_sf::SlotSet &T = h->sets[set];
+    const hipStream_t sp = h->preStream, sm = h->mapStream;
+    if (T.mapValid && sp != sm) MSL_HIP_TRY(hipStreamWaitEvent(sp, T.map, 0));   // the set's previous user is done
+    D.gstride = I.gray.row; D.gbytes = I.gray.bytes; D.dstride = I.depth.row / 4; D.mstride = I.member.row / 4;
+    D.gsB = (unsigned)I.gray.row; D.dsB = (unsigned)I.depth.row; D.msB = (unsigned)I.member.row;
+    FrameSrc src;
+    rc = stage_images(h, set, n, I, src);
+    if (rc != MSL_OK) return rc;
+    rc = fill_frames(h, set, n, src, refs, poses);
+    if (rc != MSL_OK) return rc;
+    SfDev P = slot_view(D, set * h->maxBatch);
+    sp_launch_stage(h->prof, sp, P, n, h->propLds);
+    if (sp != sm) {
+        MSL_HIP_TRY(hipEventRecord(T.pre, sp));
+        T.preValid = true;
+        MSL_HIP_TRY(hipStreamWaitEvent(sm, T.pre, 0));
+    }
+    return launch_map_chain(h, P, set, n, compact);
 }
 
 }  // namespace
@@ -504,10 +588,8 @@ msl_sf *msl_sf_create(int width, int height, float fx, float fy, float cx, float
         ok = ok && hipStreamCreateWithPriority(&h->mapStream, hipStreamNonBlocking, hi) == hipSuccess;
         ok = ok && hipStreamCreateWithFlags(&h->copyStream, hipStreamNonBlocking) == hipSuccess;
     }
-    for (int i = 0; i < 2 && ok; i++)
-        ok = hipEventCreateWithFlags(&h->evPre[i], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&h->evMap[i], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&h->evCopy[i], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&h->evH2D[i], hipEventDisableTiming) == hipSuccess;
+    for (msl_sf::SlotSet &t : h->sets)
+        for (hipEvent_t *e : {&t.pre, &t.map, &t.copy, &t.h2d}) ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
     const hipStream_t sm = h->mapStream;
     ok = ok && h->d_ctr.grow(sizeof(long long) * 32, sm) == hipSuccess;   // 16 counters (read_ctr) + [16..18] the published live counts
     ok = ok && hipMemset(h->d_ctr.p, 0, sizeof(long long) * 32) == hipSuccess;
@@ -547,7 +629,8 @@ void msl_sf_destroy(msl_sf *h) noexcept {
     if (h->mapStream) (void)hipStreamSynchronize(h->mapStream);
     h->prof.destroy();
     for (int i = 0; i < msl_sf::NSNAP; i++) if (h->snapEv[i]) (void)hipEventDestroy(h->snapEv[i]);
-    for (int i = 0; i < 2; i++) { if (h->evPre[i]) (void)hipEventDestroy(h->evPre[i]); if (h->evMap[i]) (void)hipEventDestroy(h->evMap[i]); if (h->evCopy[i]) (void)hipEventDestroy(h->evCopy[i]); if (h->evH2D[i]) (void)hipEventDestroy(h->evH2D[i]); }
+    for (const msl_sf::SlotSet &t : h->sets)
+        for (hipEvent_t e : {t.pre, t.map, t.copy, t.h2d}) if (e) (void)hipEventDestroy(e);
     const hipStream_t streams[3] = {h->copyStream, h->ownStreams ? h->preStream : nullptr, h->ownStreams ? h->mapStream : nullptr};
     delete h;   // frees the buffers
     for (hipStream_t st : streams) if (st) (void)hipStreamDestroy(st);
@@ -557,9 +640,9 @@ void msl_sf_destroy(msl_sf *h) noexcept {
 int msl_sf_staged_gray(msl_sf *h, const uint8_t **gray_dev, size_t *row_stride, size_t *frame_stride, void **uploaded_event) noexcept {
     try {
     if (!h || !gray_dev || !row_stride || !frame_stride || !uploaded_event) return MSL_ERR_INVALID;
-    if (h->stagedSet < 0 || !h->slot.gray.p) { set_error("msl_sf_staged_gray: the last batch had no host images"); return MSL_ERR_INVALID; }
-    *gray_dev = (const uint8_t *)h->slot.gray.p + (size_t)h->stagedSet * (size_t)h->maxBatch * h->slot.grayCap;
-    *row_stride = h->stagedGs; *frame_stride = h->slot.grayCap; *uploaded_event = (void *)h->evH2D[h->stagedSet];
+    if (h->stagedSet < 0) { set_error("msl_sf_staged_gray: the last batch had no host images"); return MSL_ERR_INVALID; }   // (or release_staged_images freed them since)
+    *gray_dev = h->slot.gray.at((size_t)h->stagedSet * (size_t)h->maxBatch);
+    *row_stride = h->stagedGs; *frame_stride = h->slot.gray.stride; *uploaded_event = (void *)h->sets[h->stagedSet].h2d;
     return MSL_OK;
     } MSL_ABI_CATCH_INT
 }
@@ -820,8 +903,8 @@ int msl_sf_fuse_resident_batch(msl_sf *h, int n_frames, const int32_t *refs, con
     try {
     if (!h) { set_error("msl_sf_fuse_resident_batch: NULL handle"); return MSL_ERR_INVALID; }
     MSL_HIP_TRY(hipSetDevice(h->device));
-    return run_batch(h, n_frames, refs, gray, gray_stride, gray_frame_stride, depth, depth_stride, depth_frame_stride, member, member_stride,
-                     member_frame_stride, img_mem, poses_colmajor, true);
+    return run_batch(h, n_frames, refs, poses_colmajor, {{gray, gray_stride, gray_frame_stride}, {depth, depth_stride, depth_frame_stride}, {},
+                                                         {member, member_stride, member_frame_stride}, img_mem}, true);
     } MSL_ABI_CATCH_INT
 }
 
@@ -833,8 +916,8 @@ int msl_sf_fuse_resident_batch_d16(msl_sf *h, int n_frames, const int32_t *refs,
     if (!h) { set_error("msl_sf_fuse_resident_batch_d16: NULL handle"); return MSL_ERR_INVALID; }
     if (!depth16) { set_error("msl_sf_fuse_resident_batch_d16: NULL depth"); return MSL_ERR_INVALID; }
     MSL_HIP_TRY(hipSetDevice(h->device));
-    return run_batch(h, n_frames, refs, gray, gray_stride, gray_frame_stride, nullptr, 0, 0, member, member_stride, member_frame_stride, img_mem, poses_colmajor,
-                     true, depth16, depth16_stride, depth16_frame_stride, depth_factor);
+    return run_batch(h, n_frames, refs, poses_colmajor, {{gray, gray_stride, gray_frame_stride}, {}, {depth16, depth16_stride, depth16_frame_stride},
+                                                         {member, member_stride, member_frame_stride}, img_mem, depth_factor}, true);
     } MSL_ABI_CATCH_INT
 }
 
@@ -845,7 +928,7 @@ int msl_sf_fuse_resident(msl_sf *h, int referenceFrameIndex, const uint8_t *gray
     if (!h) { set_error("msl_sf_fuse_resident: NULL handle"); return MSL_ERR_INVALID; }
     MSL_HIP_TRY(hipSetDevice(h->device));
     const int32_t ref = referenceFrameIndex;
-    return run_batch(h, 1, &ref, gray, gray_stride, 0, depth, depth_stride, 0, member, member_stride, 0, img_mem, pose_colmajor, true);
+    return run_batch(h, 1, &ref, pose_colmajor, {{gray, gray_stride}, {depth, depth_stride}, {}, {member, member_stride}, img_mem}, true);
     } MSL_ABI_CATCH_INT
 }
 
@@ -886,7 +969,7 @@ int msl_sf_fuse_ex(msl_sf *h, int referenceFrameIndex, const uint8_t *gray, size
     }
     h->mirrorValid = false;   // (until this call has completed)
     const int32_t ref = referenceFrameIndex;
-    rc = run_batch(h, 1, &ref, gray, gray_stride, 0, depth, depth_stride, 0, member, member_stride, 0, MSL_MEM_HOST, pose_colmajor, false);
+    rc = run_batch(h, 1, &ref, pose_colmajor, {{gray, gray_stride}, {depth, depth_stride}, {}, {member, member_stride}, MSL_MEM_HOST}, false);
     if (rc != MSL_OK) return rc;
     hipStream_t s = h->mapStream;
     const size_t nblk = (n_local + SUB_ITEMS - 1) / SUB_ITEMS;

@@ -1087,3 +1087,101 @@ def test_one_gray_upload_for_both_handles(oracle):
     with pytest.raises(MslError):
         sf.staged_gray()
     sf.sync(); sf.close(); ex.close(); ref.close()
+
+
+def test_host_batches_in_every_copy_shape_equal_device_fed_batches(oracle):
+    """The staging of host-image batches, shape by shape, on ONE 64x48 handle with three keyframes per batch, so that both slot sets are used twice:
+    (a) tight rows, tightly packed frames (one copy per image kind); (b) rows padded by 64 bytes (larger than the slots: they are released and
+    regrown); (c) tight again (the slot stride is now larger than the image: one copy per frame); (d) frames two rows further apart than they are high,
+    one membership image for the three (member_frame_stride = 0); then the batch capacity lowered to 2 (a new slot set) and (e) two more keyframes.
+    With f32 depth and through _d16, after every batch: map, seeds and index map are bit-identical to those of a second handle fed the same buffers,
+    with the same strides, from device memory, and both are the oracle's.  msl_sf_staged_gray refuses with "no host images" after a capacity change until
+    the next host-image batch has run, and after every host-image batch -- between (a) and (b) included, where the handle has just run one, and after
+    (b), whose regrow released the slots before it staged -- it reports that batch's row stride and the first row it hands out is that batch's.
+    (test_one_handle_releases_and_regrows_its_staging covers the refusal after a device-memory batch, test_six_host_image_calls_in_flight the overlap
+    of the two sets.)"""
+    import torch
+    from manhattanslam_amd import lib, synth, SURFEL_DTYPE
+    from manhattanslam_amd._lib import MslError, check, ptr
+    from manhattanslam_amd.surfel import _pose16
+    W, H, mw, mh = 64, 48, 32, 24
+    intr = {k: v * (W / 640.0) for k, v in synth.TUM1.items()}
+    a = np.float32(1.0) / np.float32(5000.0)
+    frames = [synth.surfel_frame(k, W, H, intr=intr, variant="B" if k % 4 == 1 else "A") for k in range(14)]
+    raw = [synth.depth_u16(f[1]) for f in frames]
+    m = synth.surfel_map(20000, ref=0).astype(SURFEL_DTYPE)
+    # (first keyframe, keyframes, padding of every row in bytes, rows between two frames beyond the image, shared membership image) or a new batch capacity
+    plan = [(0, 3, 0, 0, False), (3, 3, 64, 0, False), (6, 3, 0, 0, False), (9, 3, 0, 2, True), 2, (12, 2, 0, 0, False)]
+
+    def padded(images, dtype, pad_bytes, extra_rows, fill):
+        h, w = images[0].shape
+        out = np.full((len(images), h + extra_rows, w + pad_bytes // np.dtype(dtype).itemsize), fill, dtype)
+        out[:, :h, :w] = np.stack(images)
+        return out
+
+    def buffers(step, raw16):   # gray, depth (f32: what the device makes of the raw values), member as the caller holds them
+        j0, n, pad, rows, shared = step
+        G = padded([f[0] for f in frames[j0:j0 + n]], np.uint8, pad, rows, 17)
+        D = padded(raw[j0:j0 + n], np.uint16, pad, rows, 0xFFFF) if raw16 else padded([r.astype(np.float32) * a for r in raw[j0:j0 + n]], np.float32, pad, rows, 9.0)
+        M = padded([f[2] for f in frames[j0:j0 + (1 if shared else n)]], np.int32, pad, rows, 5)
+        return G, D, M
+
+    def no_host_images(g):
+        with pytest.raises(MslError, match=r"\(-1\): msl_sf_staged_gray: the last batch had no host images"):
+            g.staged_gray()
+
+    from tests.oracle_lib import OracleSurfel
+    o = OracleSurfel(W, H, intr["fx"], intr["fy"], intr["cx"], intr["cy"], 30.0, 0.5)
+    o.map_set(m)
+    want = []
+    for step in plan:
+        if isinstance(step, int):
+            continue
+        G, D, M = buffers(step, False)
+        for f in range(step[1]):
+            o.fuse_map(step[0] + f, G[f, :H, :W], D[f, :H, :W], M[0 if step[4] else f, :mh, :mw], frames[step[0] + f][3])
+        want.append((o.map_get().copy(), o.seeds().copy(), o.index().copy()))
+        assert (want[-1][0]["lastUpdate"] == step[0] + step[1] - 1).sum() > 20   # (the batch's last keyframe fused or spawned surfels)
+
+    class DeviceRow:   # W bytes at a device address, for torch.as_tensor
+        def __init__(self, address):
+            self.__cuda_array_interface__ = {"shape": (W,), "typestr": "|u1", "data": (address, False), "version": 2}
+
+    for raw16 in (False, True):
+        got = {}
+        for device in (False, True):
+            g, _ = _mk(intr, W, H)
+            g.set_batch_capacity(3); g.map_upload(m)
+            no_host_images(g)
+            got[device] = []
+            for step in plan:
+                if isinstance(step, int):
+                    g.set_batch_capacity(step)
+                    no_host_images(g)
+                    continue
+                j0, n, pad, rows, shared = step
+                G, D, M = buffers(step, raw16)
+                gs, ds, ms = G.strides[1], D.strides[1], M.strides[1]
+                refs = np.arange(j0, j0 + n, dtype=np.int32)
+                pz = np.ascontiguousarray(np.stack([_pose16(f[3]) for f in frames[j0:j0 + n]]), np.float32)
+                src = [torch.from_numpy(x.view(np.int16) if x.dtype == np.uint16 else x).cuda() for x in (G, D, M)] if device else [G, D, M]
+                if raw16:
+                    check(lib.msl_sf_fuse_resident_batch_d16(g._h, n, ptr(refs), ptr(src[0]), gs, G.strides[0], ptr(src[1]), ds, D.strides[0], float(a), ptr(src[2]), ms,
+                                                             0 if shared else M.strides[0], int(device), ptr(pz)), "d16 batch")
+                else:
+                    check(lib.msl_sf_fuse_resident_batch(g._h, n, ptr(refs), ptr(src[0]), gs, G.strides[0], ptr(src[1]), ds, D.strides[0], ptr(src[2]), ms,
+                                                         0 if shared else M.strides[0], int(device), ptr(pz)), "f32 batch")
+                got[device].append((g.map_download(), g.debug_seeds(), g.debug_index()))   # (the download waits for the batch)
+                if device:
+                    no_host_images(g)
+                else:
+                    address, row_stride, frame_stride, _ = g.staged_gray()
+                    assert row_stride == gs and frame_stride >= gs * (H - 1) + W, (step, row_stride, frame_stride)
+                    assert np.array_equal(torch.as_tensor(DeviceRow(address), device="cuda").cpu().numpy(), G[0, 0, :W]), step
+            g.close()
+        for b, ((mh_, sh, ih), (md, sd, idd), (mo, so, io)) in enumerate(zip(got[False], got[True], want)):
+            what = f"raw16={raw16}, batch {b}"
+            assert mh_.tobytes() == md.tobytes() and sh.tobytes() == sd.tobytes() and np.array_equal(ih, idd), what
+            assert_surfels_close(mh_, mo, what)
+            assert_seeds_close(sh, so)
+            assert np.array_equal(ih, io), what
