@@ -769,6 +769,97 @@ MSL_API int msl_match_lines_by_descriptor_batch(int device, int n_pairs, int lca
                                                 const uint8_t *cur_ldesc, const int32_t *n_cur_lines, msl_mem mem, int32_t *match_out,
                                                 int32_t *nmatches, double *line_xyz, uint8_t *line_has, msl_mem out_mem) MSL_NOEXCEPT;
 
+/* ---- Relocalisation: the keyframe search of Tracking::Relocalization (src/Tracking.cc:1909-2055) ----
+ * msl_match_keyframe_points: n_pairs independent calls of
+ *     int ORBmatcher::SearchByProjection(Frame &CurrentFrame, KeyFrame *pKF, const set<MapPoint*> &sAlreadyFound, th, ORBdist)
+ * (src/ORBmatcher.cc:680-797): th 10 / ORBdist 100 after the first pose optimisation, th 3 / ORBdist 64 after the second.
+ * Current frame: the msl_match_by_projection current-frame arrays without mvuRight (`cap` entries per pair), plus
+ *   cur_held[i]      CurrentFrame.mvpMapPoints[i] != NULL on entry (any non-zero byte).  A held keypoint is never handed out.
+ * Keyframe (`kcap` entries per pair), per keypoint i < n_kf[f]:
+ *   kf_xyz[3 i..]    GetMapPointMatches()[i]->GetWorldPos()
+ *   kf_dist[2 i..]   its mfMinDistance, mfMaxDistance (raw: the 0.8f / 1.2f invariance factors are applied inside)
+ *   kf_desc[32 i..]  its GetDescriptor()               kf_angle[i]  pKF->mvKeysUn[i].angle
+ *   kf_flags[i]      bit 0: pMP && !pMP->isBad() && !sAlreadyFound.count(pMP)
+ * Tcw: rows 0-2 of CurrentFrame.mTcw (12 floats per pair); Ow is derived from it as Frame::UpdatePoseMatrices does.
+ * Out: match_out[f cap + i2] = the keyframe keypoint index this call wrote into CurrentFrame.mvpMapPoints[i2], or -1 (untouched, or
+ * NULLed again by the rotation check); nmatches[f] the return value.  Keyframe-indexed like msl_match_by_bow's match_out, so one `where`
+ * merges it into the pt_ref of the next msl_pose_optimize.
+ * Exactly reproduced: there is no positive-depth test (a point behind the camera that projects into the image bounds is searched);
+ * invzc is divided in double and rounded to float; dist3D is cv::norm (double accumulation and sqrt); PredictScale is clamped to
+ * [0, nlevels - 1]; window radius th * scale_factors[level] over levels [level - 1, level + 1] with GetFeaturesInArea's level rule; the
+ * best is the first minimum in walk order among the keypoints not held at that moment (dist < bestDist from 256), accepted when
+ * bestDist <= orb_dist; keyframe keypoints run in ascending order, nothing is ever overwritten; the rotation histogram as in
+ * msl_match_by_projection.  One divergence: with zc == 0 the projection is NaN or infinite; a NaN passes the reference's bounds test and
+ * is then converted to int (undefined) -- here a non-finite u or v matches nothing.
+ * Limits: cap <= 8192, kcap <= 8192, nlevels <= MSL_MATCH_MAX_LEVELS, 0 <= orb_dist <= 255 (from 256 up the reference would write
+ * mvpMapPoints[-1]); anything else is refused with MSL_ERR_INVALID before any launch.  Memory and synchronisation as
+ * msl_match_local_points.  Parity is relative to a sequential CPU model. */
+typedef struct msl_keyframe_match_params {
+    msl_match_params base;            /* fx..cy, image bounds, th (10, then 3), check_orientation, nlevels, scale_factors; bf unused */
+    float log_scale_factor;           /* Frame::mfLogScaleFactor as the caller's Frame holds it */
+    int32_t orb_dist;                 /* ORBdist (100, then 64) */
+} msl_keyframe_match_params;
+MSL_API int msl_match_keyframe_points(msl_match *h, int n_pairs, int cap, int kcap, const msl_keyframe_match_params *params,
+                                      const msl_keypoint *cur_kps, const float *cur_un_xy, const int32_t *cur_grid_cell,
+                                      const uint8_t *cur_desc, const int32_t *n_cur, const uint8_t *cur_held, const float *kf_xyz,
+                                      const float *kf_dist, const uint8_t *kf_desc, const float *kf_angle, const uint8_t *kf_flags,
+                                      const int32_t *n_kf, const float *Tcw, msl_mem mem, int32_t *match_out, int32_t *nmatches,
+                                      msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device matcher handle, always synchronous; see msl_match_by_projection_batch). */
+MSL_API int msl_match_keyframe_points_batch(int device, int n_pairs, int cap, int kcap, const msl_keyframe_match_params *params,
+                                            const msl_keypoint *cur_kps, const float *cur_un_xy, const int32_t *cur_grid_cell,
+                                            const uint8_t *cur_desc, const int32_t *n_cur, const uint8_t *cur_held, const float *kf_xyz,
+                                            const float *kf_dist, const uint8_t *kf_desc, const float *kf_angle, const uint8_t *kf_flags,
+                                            const int32_t *n_kf, const float *Tcw, msl_mem mem, int32_t *match_out, int32_t *nmatches,
+                                            msl_mem out_mem) MSL_NOEXCEPT;
+
+/* msl_kfdb: a KeyFrameDatabase (src/KeyFrameDatabase.cc:38-66) on one device.  msl_kfdb_create returns NULL with msl_last_error() when no
+ * device is usable.  msl_kfdb_add stores the BowVector of one keyframe exactly as msl_bow_transform wrote it (ascending int32 words, double
+ * values, the count -- on the device for MSL_MEM_DEVICE) and returns its slot when the vector is stored; with device memory `h` is the
+ * matcher handle that produced it and the call waits for h's stream, because it needs the count on the host (keyframe insertion is rare;
+ * h may be NULL for host memory).  Slots are handed out in add order and never reused before msl_kfdb_clear, so the slot number is the
+ * keyframe's position in every inverted list of the reference, which the order of the results depends on.  msl_kfdb_erase leaves a dead
+ * slot; its storage comes back only at msl_kfdb_clear.  At most 8192 slots: the add beyond that is refused with MSL_ERR_OVERFLOW and
+ * changes nothing.  add, erase, clear and the enqueueing of a query are serialised by a mutex inside (the reference's mMutex) and the
+ * first three wait for the queries in flight; the database may be shared by threads and matcher handles of its device.  Waits, in full:
+ * add / erase / clear block the caller (mutex held) on the last query's event and on the database's own copy stream, add with device
+ * memory also on h's stream; no other stream of the device is stalled.
+ * msl_kfdb_size: slots handed out since the last clear, and how many of them are live. */
+typedef struct msl_kfdb msl_kfdb;
+MSL_API msl_kfdb *msl_kfdb_create(int device) MSL_NOEXCEPT;
+MSL_API void msl_kfdb_destroy(msl_kfdb *db) MSL_NOEXCEPT;
+MSL_API int msl_kfdb_add(msl_kfdb *db, msl_match *h, const int32_t *bow_word, const double *bow_value, const int32_t *n_words, msl_mem mem,
+                         int32_t *slot) MSL_NOEXCEPT;
+MSL_API int msl_kfdb_erase(msl_kfdb *db, int slot) MSL_NOEXCEPT;
+MSL_API int msl_kfdb_clear(msl_kfdb *db) MSL_NOEXCEPT;
+MSL_API int msl_kfdb_size(msl_kfdb *db, int32_t *n_slots, int32_t *n_live) MSL_NOEXCEPT;
+/* msl_reloc_candidates: n_frames consecutive calls of
+ *     vector<KeyFrame*> KeyFrameDatabase::DetectRelocalizationCandidates(Frame *F)   (src/KeyFrameDatabase.cc:68-170)
+ * with DBoW2's L1Scoring::score (Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68).  bow_word / bow_value / n_words: msl_bow_transform's
+ * BowVector outputs of the query frames (`cap` entries per frame).  covis[s * 10 ..]: GetBestCovisibilityKeyFrames(10) of the keyframe in
+ * slot s as slots, in order, -1 terminated (n_slots rows; dead or out-of-range slots are skipped, as the reference skips a keyframe whose
+ * mnRelocQuery differs).  Out: cand_out[f ccap ..] = vpRelocCandidates as slots in the reference's order, n_cand[f] the full count (only
+ * the first ccap are written).  Optional (NULL = not wanted), n_slots entries per frame: words_out = mnRelocWords (0 for a keyframe
+ * sharing no word), score_out = the float mRelocScore of this query (-1 for a keyframe not scored in it).
+ * Exactly reproduced: lKFsSharingWords ordered by (first shared word, slot); minCommonWords = (int)(maxCommonWords * 0.8f), scored iff
+ * mnRelocWords > minCommonWords; the L1 score summed in double over the common words in ascending order, -score / 2.0 rounded to float;
+ * the covisibility accumulation in float in neighbour order over every neighbour that shares a word with this query, scored or not;
+ * bestAccScore from 0 raised by >; retained when accScore > 0.75f * bestAccScore; each pBestKF emitted at its first occurrence.
+ * The stale score: a neighbour that shares words but was not scored contributes the mRelocScore of the last query that scored it, so the
+ * database keeps one float per slot across frames and calls (frame f sees what frames < f and earlier calls left).  A keyframe never scored
+ * reads uninitialised memory in the reference; here it reads 0.0f.
+ * Only L1_NORM is built (ORBvoc and the reference's configuration): a vocabulary of another scoring, or one on another device than the
+ * handle's, is refused with MSL_ERR_INVALID.  Memory and synchronisation as msl_match_local_points; queries on one database are ordered
+ * among themselves even across handles.  Parity is relative to a sequential CPU model. */
+MSL_API int msl_reloc_candidates(msl_match *h, msl_kfdb *db, const msl_vocab *voc, int n_frames, int cap, int ccap, const int32_t *bow_word,
+                                 const double *bow_value, const int32_t *n_words, const int32_t *covis, msl_mem mem, int32_t *cand_out,
+                                 int32_t *n_cand, int32_t *words_out, float *score_out, msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device matcher handle, always synchronous; see msl_match_by_projection_batch). */
+MSL_API int msl_reloc_candidates_batch(int device, msl_kfdb *db, const msl_vocab *voc, int n_frames, int cap, int ccap,
+                                       const int32_t *bow_word, const double *bow_value, const int32_t *n_words, const int32_t *covis,
+                                       msl_mem mem, int32_t *cand_out, int32_t *n_cand, int32_t *words_out, float *score_out,
+                                       msl_mem out_mem) MSL_NOEXCEPT;
+
 /* Batched form: n_frames keyframes in order, semantically n_frames consecutive msl_sf_fuse_resident calls.
  * Keyframe f's images start at base + f * <frame_stride> bytes (member_frame_stride may be 0: one shared
  * membership image); refs[n_frames] and poses (16 * n_frames floats, column-major Twc each) are host arrays.

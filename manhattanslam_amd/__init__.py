@@ -19,3 +19,5 @@ from . import plane  # noqa: F401
 from ._lib import PLANE_PARAMS_DTYPE  # noqa: F401
 from . import bow  # noqa: F401
 from ._lib import BOW_MATCH_PARAMS_DTYPE  # noqa: F401
+from . import reloc  # noqa: F401
+from ._lib import KEYFRAME_MATCH_PARAMS_DTYPE  # noqa: F401

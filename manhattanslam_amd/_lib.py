@@ -42,6 +42,7 @@ POSE_PARAMS_DTYPE = np.dtype([(n, "<f4") for n in ("fx", "fy", "cx", "cy", "bf")
                                                    "par_th")])                                                                        # msl_pose_params
 PLANE_PARAMS_DTYPE = np.dtype([(n, "<f4") for n in ("d_th", "a_th", "ver_th", "par_th", "mf_ver_th")])                             # msl_plane_params
 BOW_MATCH_PARAMS_DTYPE = np.dtype([("nn_ratio", "<f4"), ("check_orientation", "<i4")])                                               # msl_bow_match_params
+KEYFRAME_MATCH_PARAMS_DTYPE = np.dtype(MATCH_PARAMS_DTYPE.descr + [("log_scale_factor", "<f4"), ("orb_dist", "<i4")])                          # msl_keyframe_match_params
 assert POSE_PARAMS_DTYPE.itemsize == 152 and KEYPOINT_DTYPE.itemsize == 28 and SURFEL_DTYPE.itemsize == 56 and SEED_DTYPE.itemsize == 64
 
 MSL_MEM_HOST, MSL_MEM_DEVICE = 0, 1
@@ -123,6 +124,16 @@ SIGNATURES = {
     "msl_match_by_bow_batch": (_i, [_i, _i, _i] + [_vp] * 10 + [_i, _vp, _vp, _i]),
     "msl_match_lines_by_descriptor": (_i, [_vp, _i, _i, _i] + [_vp] * 6 + [_i] + [_vp] * 4 + [_i]),
     "msl_match_lines_by_descriptor_batch": (_i, [_i, _i, _i, _i] + [_vp] * 6 + [_i] + [_vp] * 4 + [_i]),
+    "msl_match_keyframe_points": (_i, [_vp, _i, _i, _i] + [_vp] * 14 + [_i, _vp, _vp, _i]),
+    "msl_match_keyframe_points_batch": (_i, [_i, _i, _i, _i] + [_vp] * 14 + [_i, _vp, _vp, _i]),
+    "msl_kfdb_create": (_vp, [_i]),
+    "msl_kfdb_destroy": (None, [_vp]),
+    "msl_kfdb_add": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "msl_kfdb_erase": (_i, [_vp, _i]),
+    "msl_kfdb_clear": (_i, [_vp]),
+    "msl_kfdb_size": (_i, [_vp, _vp, _vp]),
+    "msl_reloc_candidates": (_i, [_vp, _vp, _vp, _i, _i, _i] + [_vp] * 4 + [_i] + [_vp] * 4 + [_i]),
+    "msl_reloc_candidates_batch": (_i, [_i, _vp, _vp, _i, _i, _i] + [_vp] * 4 + [_i] + [_vp] * 4 + [_i]),
     "msl_sf_fuse_resident": (_i, [_vp, _i, _vp, _sz, _vp, _sz, _vp, _sz, _i, _vp]),
     "msl_sf_set_batch_capacity": (_i, [_vp, _i]),
     "msl_sf_fuse_resident_batch": (_i, [_vp, _i, _vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _sz, _sz, _i, _vp]),

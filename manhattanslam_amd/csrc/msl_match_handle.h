@@ -1,5 +1,5 @@
 // msl_match_handle.h -- the matcher handle, its staging of caller arrays (Stage) and the forwarder of the *_batch entry points; shared by
-// msl_match.hip, msl_line_match.hip, msl_pose.hip, msl_plane.hip and msl_bow.hip (internal).
+// msl_match.hip, msl_line_match.hip, msl_pose.hip, msl_plane.hip, msl_bow.hip and msl_reloc.hip (internal).
 #pragma once
 
 #include "msl_common.h"
@@ -19,6 +19,7 @@ struct msl_match {
     msl::DevBuf lineQ, lineTrk, lineView;                              // the line searches: per-line queries / tracks / in-view
     msl::DevBuf planeDis;                                              // msl_plane_associate: [frame][map plane][64] distances
     msl::DevBuf bowW;                                                  // msl_bow_transform: per-feature word weights
+    msl::DevBuf relocCnt, relocFirst, relocScore;                      // msl_reloc_candidates: [frame][slot] shared words / first shared word / L1 score
     // Device copies of host-memory arguments, one pool for every entry point (msl::Stage deals the slots out in declaration order).
     // Sharing is sound because every call that touches the pool returns with the stream drained (Stage::finish synchronises whenever
     // either side is host memory, and only then is a slot used), so no slot is live when the next call starts.
@@ -53,7 +54,7 @@ int abi_call_default(Run run, int device, bool sync_legacy, A... a) {
 }
 
 // Kernels that ask for more dynamic LDS than the default limit: the limit is raised once per handle (= per device) and kernel.
-enum LdsKernel { LDS_MATCH_ASSIGN, LDS_LOCAL_ASSIGN, LDS_LINE_ASSIGN_LAST, LDS_LINE_ASSIGN_LOCAL, LDS_BOW_VECTOR, LDS_MATCH_BOW };
+enum LdsKernel { LDS_MATCH_ASSIGN, LDS_LOCAL_ASSIGN, LDS_LINE_ASSIGN_LAST, LDS_LINE_ASSIGN_LOCAL, LDS_BOW_VECTOR, LDS_MATCH_BOW, LDS_KF_ASSIGN, LDS_RELOC_SELECT };
 template <class K>
 hipError_t allow_lds(msl_match *h, LdsKernel k, K kernel, size_t max_bytes) {
     if (h->ldsSet >> k & 1u) return hipSuccess;
