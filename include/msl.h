@@ -813,6 +813,52 @@ MSL_API int msl_match_keyframe_points_batch(int device, int n_pairs, int cap, in
                                             const int32_t *n_kf, const float *Tcw, msl_mem mem, int32_t *match_out, int32_t *nmatches,
                                             msl_mem out_mem) MSL_NOEXCEPT;
 
+/* msl_pnp_ransac: PnPsolver (src/PnPsolver.cc) as Tracking::Relocalization uses it (src/Tracking.cc:1960-2000) for n_pairs independent
+ * (frame, candidate keyframe) pairs: each pair is one PnPsolver built from the pair's matches, SetRansacParameters(probability, min_inliers,
+ * max_iterations, min_set, epsilon, th2) and ONE call iterate(n_iterations) on that fresh solver.  Because of the || in the loop condition
+ * (:174) that call runs max(mRansacMaxIts, n_iterations) iterations unless Refine() succeeds earlier, and always ends with bNoMore.
+ *
+ * Correspondences (:76-96): for a current-frame keypoint i < n_kps[f], match[f][i] indexes the pair's xyz[f][kcap]; a value outside
+ * [0, kcap) is NULL (the rule of msl_pose_optimize's pt_ref, so msl_match_by_bow's match_out feeds this call directly).  The valid entries
+ * are taken in ascending i: mvP2D = un_xy[i], mvSigma2 = level_sigma2[octave] (octave clamped to [0, nlevels)), mvMaxError = sigma2 * th2.
+ * mRansacMinInliers and mRansacMaxIts follow from their count N as in :128-147, evaluated on the host with its libm for every N <= cap and
+ * uploaded as a table (rebuilt only when the RANSAC parameters or cap change).  N < mRansacMinInliers: no pose.
+ *
+ * Outputs per pair: status (0 none, 1 the first Refine() that succeeded -- refined count > mRansacMinInliers, :271 --, 2 the best unrefined
+ * hypothesis), Tcw_out (rows 0-2 of the pose, converted to float as :205-211 / :272-278 do; the identity rows when status is 0), inlier[i]
+ * per current keypoint (vbInliers), n_inliers, and pt_ref_out[i] = inlier[i] ? match[i] : -1, the `where` of Tracking.cc:1985-1994, so that
+ * msl_pose_optimize follows with no element-wise step.  compute_pose runs in double and CheckInliers keeps its float / double mix (:286-312).
+ *
+ * Pinned where the reference is undefined or not restated (tests/pnp_model.py is the sequential model):
+ *   - DUtils::Random (unseeded rand()): draw j of iteration k is fmix32(fmix32(seed[f] ^ k * 0x9E3779B1) ^ (j + 1) * 0x85EBCA77) with
+ *     murmur3's 32-bit finaliser, randi = mulhi32(hash, available); the swap-with-back removal of :185-190 is kept.  seed is per pair.
+ *   - cvSVD / cvSolve(CV_SVD) / cvInvert(CV_SVD): a cyclic Jacobi eigen-solver on the symmetric matrix (A^T A for the solves, the inverse
+ *     and the 3x3 SVD) with a fixed round-robin pair order, 16 sweeps, no convergence branch, eigenpairs sorted by descending eigenvalue
+ *     (lower index first on ties), no sign normalisation; eigenvalues at or below 1e-12 of the largest are dropped by the pseudo-inverse.
+ *   - every sum over correspondences runs left to right; gauss_newton's X starts as zeros.
+ * Limits: cap <= 8192, kcap <= 32768, 1 <= max_iterations <= 1024, 0 <= n_iterations <= 1024, nlevels <= MSL_MATCH_MAX_LEVELS, min_set == 4
+ * (the reference's only use); anything else is refused with MSL_ERR_INVALID and msl_last_error() naming the field, before any launch.
+ * Synchronisation: as msl_match_by_projection (asynchronous on the handle's stream with device memory on both sides; the first call with
+ * new RANSAC parameters drains the stream once to upload the table). */
+typedef struct msl_pnp_params {
+    float fx, fy, cx, cy;
+    int32_t nlevels;
+    float level_sigma2[MSL_MATCH_MAX_LEVELS];    /* Frame::mvLevelSigma2 */
+    double probability;                          /* SetRansacParameters: Tracking passes (0.99, 10, 300, 4, 0.5, 5.991) */
+    int32_t min_inliers, max_iterations, min_set;
+    float epsilon, th2;
+    int32_t n_iterations;                        /* the argument of iterate(): Tracking passes 5 */
+} msl_pnp_params;
+MSL_API int msl_pnp_ransac(msl_match *h, int n_pairs, int cap, int kcap, const msl_pnp_params *params, const msl_keypoint *kps,
+                           const float *un_xy, const int32_t *match, const int32_t *n_kps, const float *xyz, const uint32_t *seed, msl_mem mem,
+                           float *Tcw_out, uint8_t *inlier, int32_t *pt_ref_out, int32_t *n_inliers, int32_t *status,
+                           msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device matcher handle, always synchronous; see msl_match_by_projection_batch). */
+MSL_API int msl_pnp_ransac_batch(int device, int n_pairs, int cap, int kcap, const msl_pnp_params *params, const msl_keypoint *kps,
+                                 const float *un_xy, const int32_t *match, const int32_t *n_kps, const float *xyz, const uint32_t *seed,
+                                 msl_mem mem, float *Tcw_out, uint8_t *inlier, int32_t *pt_ref_out, int32_t *n_inliers, int32_t *status,
+                                 msl_mem out_mem) MSL_NOEXCEPT;
+
 /* msl_kfdb: a KeyFrameDatabase (src/KeyFrameDatabase.cc:38-66) on one device.  msl_kfdb_create returns NULL with msl_last_error() when no
  * device is usable.  msl_kfdb_add stores the BowVector of one keyframe exactly as msl_bow_transform wrote it (ascending int32 words, double
  * values, the count -- on the device for MSL_MEM_DEVICE) and returns its slot when the vector is stored; with device memory `h` is the

@@ -75,6 +75,12 @@ MSL_API int msl_debug_div100(const float *x_host, double *out_host, size_t n) MS
  * +-0.4 (src/SurfelFusion.cpp:494-503).  Host arrays; synchronous. */
 MSL_API int msl_debug_chain_sum(const float *x_host, const int32_t *n_host, int lists, int huber, float *out_host) MSL_NOEXCEPT;
 
+/* The per-hypothesis stage of the last msl_pnp_ransac call on h (host output, synchronous): *n_out = the iterations pair `pair` ran
+ * (max(mRansacMaxIts, n_iterations), 0 when N < mRansacMinInliers); for the first min(*n_out, k_cap) of them the double pose compute_pose
+ * returned (R [k][9] row-major, t [k][3]), the branch whose reprojection error won (1 / 2 / 3) and CheckInliers' count. */
+MSL_API int msl_pnp_debug_hypotheses(msl_match *h, int pair, int k_cap, double *R, double *t, int32_t *branch, int32_t *count,
+                                     int32_t *n_out) MSL_NOEXCEPT;
+
 #define MSL_SF_NKERNELS 12
 MSL_API int msl_sf_profile_enable(msl_sf *h, int mode) MSL_NOEXCEPT;
 /* Sampling for the per-dispatch event pairs: only every stride-th launch of a timed kernel carries events (default 1 = every launch).  A

@@ -21,3 +21,5 @@ from . import bow  # noqa: F401
 from ._lib import BOW_MATCH_PARAMS_DTYPE  # noqa: F401
 from . import reloc  # noqa: F401
 from ._lib import KEYFRAME_MATCH_PARAMS_DTYPE  # noqa: F401
+from . import pnp  # noqa: F401
+from ._lib import PNP_PARAMS_DTYPE  # noqa: F401

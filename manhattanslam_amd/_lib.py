@@ -43,6 +43,10 @@ POSE_PARAMS_DTYPE = np.dtype([(n, "<f4") for n in ("fx", "fy", "cx", "cy", "bf")
 PLANE_PARAMS_DTYPE = np.dtype([(n, "<f4") for n in ("d_th", "a_th", "ver_th", "par_th", "mf_ver_th")])                             # msl_plane_params
 BOW_MATCH_PARAMS_DTYPE = np.dtype([("nn_ratio", "<f4"), ("check_orientation", "<i4")])                                               # msl_bow_match_params
 KEYFRAME_MATCH_PARAMS_DTYPE = np.dtype(MATCH_PARAMS_DTYPE.descr + [("log_scale_factor", "<f4"), ("orb_dist", "<i4")])                          # msl_keyframe_match_params
+PNP_PARAMS_DTYPE = np.dtype([(n, "<f4") for n in ("fx", "fy", "cx", "cy")] + [("nlevels", "<i4"), ("level_sigma2", "<f4", (16,)), ("probability", "<f8")] +
+                            [(n, "<i4") for n in ("min_inliers", "max_iterations", "min_set")] + [("epsilon", "<f4"), ("th2", "<f4"),
+                                                                                                  ("n_iterations", "<i4")], align=True)   # msl_pnp_params
+assert PNP_PARAMS_DTYPE.itemsize == 120 and PNP_PARAMS_DTYPE.fields["probability"][1] == 88
 assert POSE_PARAMS_DTYPE.itemsize == 152 and KEYPOINT_DTYPE.itemsize == 28 and SURFEL_DTYPE.itemsize == 56 and SEED_DTYPE.itemsize == 64
 
 MSL_MEM_HOST, MSL_MEM_DEVICE = 0, 1
@@ -134,6 +138,9 @@ SIGNATURES = {
     "msl_kfdb_size": (_i, [_vp, _vp, _vp]),
     "msl_reloc_candidates": (_i, [_vp, _vp, _vp, _i, _i, _i] + [_vp] * 4 + [_i] + [_vp] * 4 + [_i]),
     "msl_reloc_candidates_batch": (_i, [_i, _vp, _vp, _i, _i, _i] + [_vp] * 4 + [_i] + [_vp] * 4 + [_i]),
+    "msl_pnp_ransac": (_i, [_vp, _i, _i, _i] + [_vp] * 7 + [_i] + [_vp] * 5 + [_i]),
+    "msl_pnp_ransac_batch": (_i, [_i, _i, _i, _i] + [_vp] * 7 + [_i] + [_vp] * 5 + [_i]),
+    "msl_pnp_debug_hypotheses": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "msl_sf_fuse_resident": (_i, [_vp, _i, _vp, _sz, _vp, _sz, _vp, _sz, _i, _vp]),
     "msl_sf_set_batch_capacity": (_i, [_vp, _i]),
     "msl_sf_fuse_resident_batch": (_i, [_vp, _i, _vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _sz, _sz, _i, _vp]),

@@ -1,8 +1,13 @@
 // msl_match_handle.h -- the matcher handle, its staging of caller arrays (Stage) and the forwarder of the *_batch entry points; shared by
-// msl_match.hip, msl_line_match.hip, msl_pose.hip, msl_plane.hip, msl_bow.hip and msl_reloc.hip (internal).
+// msl_match.hip, msl_line_match.hip, msl_pose.hip, msl_plane.hip, msl_bow.hip, msl_reloc.hip and msl_pnp.hip (internal).
 #pragma once
 
 #include "msl_common.h"
+
+namespace msl {
+// What msl_pnp_ransac's table N -> (minInliers, maxIts) was built from (no padding: compared bytewise).
+struct PnpKey { double probability; int32_t min_inliers, max_iterations, min_set; float epsilon; int32_t cap, zero; };
+}  // namespace msl
 
 // One matcher object = one ORBmatcher of the reference (src/ORBmatcher.cc:41): its own stream and its own scratch, used by one thread at a time;
 // the device is re-bound at every entry like the other handles.  The line searches (= the tracker's LSDmatcher), msl_pose_optimize, the
@@ -20,6 +25,11 @@ struct msl_match {
     msl::DevBuf planeDis;                                              // msl_plane_associate: [frame][map plane][64] distances
     msl::DevBuf bowW;                                                  // msl_bow_transform: per-feature word weights
     msl::DevBuf relocCnt, relocFirst, relocScore;                      // msl_reloc_candidates: [frame][slot] shared words / first shared word / L1 score
+    // msl_pnp_ransac: the compacted correspondences, per-hypothesis counts / masks / poses and Refine()'s lists in one buffer (the offsets of
+    // the last call's per-hypothesis arrays are kept for msl_pnp_debug_hypotheses); the SetRansacParameters table and what it was built from.
+    msl::DevBuf pnp, pnpTable;
+    msl::PnpKey pnpKey{}; bool pnpTableValid = false;
+    int pnpPairs = 0, pnpKmax = 0; size_t pnpOffK = 0, pnpOffCnt = 0, pnpOffRt = 0, pnpOffBr = 0;
     // Device copies of host-memory arguments, one pool for every entry point (msl::Stage deals the slots out in declaration order).
     // Sharing is sound because every call that touches the pool returns with the stream drained (Stage::finish synchronises whenever
     // either side is host memory, and only then is a slot used), so no slot is live when the next call starts.
