@@ -33,9 +33,6 @@ void set_error(const char *fmt, ...);
 int bind_device(int device);  // hipSetDevice + gfx950 check; returns msl_status
 
 // ---- grow-only device buffers ----------------------------------------------------------------
-// Afterwards p holds at least `need` bytes (old contents not kept), or nothing (p = nullptr, cap = 0) when the allocation failed.
-hipError_t grow(void *&p, size_t &cap, size_t need);
-
 // A device (DevBuf) or pinned host (PinBuf) buffer owned by a handle and freed with it (a per-frame caller pays no allocation).  Never in static
 // storage: a free run by a static destructor after the HIP runtime has been torn down crashes the process at exit.  Moving leaves the source
 // empty; assigning an empty buffer (`b = DevBuf()`) releases the memory.

@@ -32,15 +32,6 @@ int bind_device(int device) {
     return MSL_OK;
 }
 
-hipError_t grow(void *&p, size_t &cap, size_t need) {
-    if (need <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    const hipError_t e = hipMalloc(&p, need);
-    if (e == hipSuccess) cap = need;
-    return e;
-}
-
 template <Mem M>
 void Buf<M>::release() {
     if (p) (void)(M == Mem::Device ? hipFree(p) : hipHostFree(p));

@@ -149,3 +149,73 @@ def test_extract_planes_and_vertex_lists(oracle, monkeypatch):
         assert cloud[f].tobytes() == np.ascontiguousarray(want_cloud).reshape(-1, 3).tobytes(), f
         assert np.array_equal(got[f], ref[f][0])
 
+
+def _check_small_call(shape, device_tensor=False):
+    """One membership call and one block fit of a small shape's five scenes against the oracle."""
+    from manhattanslam_amd import peac
+    from tests.test_peac_host import SMALL_SHAPES, small_reference
+    I, frames, p, ref = small_reference(shape)
+    fac = np.float32(1 / 5000.0)
+    if device_tensor:   # the same frames as MSL_MEM_DEVICE input
+        import torch
+        w, h = shape[:2]
+        d16 = torch.from_numpy(frames.view(np.int16).copy()).cuda().contiguous()
+        got = np.zeros((len(frames), (h + 1) // 2, (w + 1) // 2), np.int32); n = np.zeros(len(frames), np.int32)
+        peac.plane_membership_device(d16, 1, len(frames), w, h, I["fx"], I["fy"], I["cx"], I["cy"], fac, p, got, n)
+    else:
+        got, n = peac.plane_membership(frames, I["fx"], I["fy"], I["cx"], I["cy"], fac, params=p)
+    blocks = peac.block_fit(frames, I["fx"], I["fy"], I["cx"], I["cy"], fac, params=p)
+    assert tuple(n) == SMALL_SHAPES[shape][1], (shape, n)
+    for f, (want, nw, wb) in enumerate(ref):
+        assert n[f] == nw and np.array_equal(got[f], want), (shape, f, np.argwhere(got[f] != want)[:5])
+        assert blocks[f].tobytes() == wb.tobytes(), (shape, f)
+
+
+def test_state_survives_changing_calls(oracle, monkeypatch):
+    """The extractor keeps one state per device (stream, scratch buffers) across calls: small calls, then larger ones that make every buffer grow,
+    then small ones again in buffers larger than needed, with the clustering on either side, host and device input, with and without the cloud."""
+    from manhattanslam_amd import peac
+    from tests import oracle_lib
+    from tests.test_peac_host import SMALL_SHAPES, small_reference
+    s64, s161, s160 = list(SMALL_SHAPES)
+    for mode in ("device", "host"):
+        monkeypatch.setenv("MSL_PEAC_CLUSTER", mode)
+        _check_small_call(s64)
+        _check_small_call(s161)
+        _check_small_call(s161, device_tensor=True)
+        _check_small_call(s64)
+    monkeypatch.delenv("MSL_PEAC_CLUSTER", raising=False)
+    I, frames, p, ref = small_reference(s160)
+    fac = np.float32(1 / 5000.0)
+    d, (want, nw, _) = frames[1], ref[1]
+    assert nw == 2
+    got, n, planes, cloud = peac.extract(d, I["fx"], I["fy"], I["cx"], I["cy"], fac, params=p, with_cloud=True)
+    want_cloud, _ = oracle_lib.peac_block_stats(d, I["fx"], I["fy"], I["cx"], I["cy"], fac)
+    assert cloud[0].tobytes() == np.ascontiguousarray(want_cloud).reshape(-1, 3).tobytes()
+    assert n[0] == nw and len(planes[0][0]) == nw and np.array_equal(got[0], want)
+    got, n, planes = peac.extract(d, I["fx"], I["fy"], I["cx"], I["cy"], fac, params=p)
+    assert n[0] == nw and len(planes[0][0]) == nw and np.array_equal(got[0], want)
+
+
+def test_bad_device_is_refused(oracle):
+    """A device outside 0 .. 15 is an argument error of every entry point that takes one (no state is looked up for it), and leaves the
+    extractor usable."""
+    from manhattanslam_amd import peac, PEAC_STATS_DTYPE
+    from manhattanslam_amd._lib import lib, ptr, MSL_MEM_HOST
+    from tests.test_peac_host import SMALL_SHAPES, small_reference
+    shape = list(SMALL_SHAPES)[0]
+    I, frames, p, ref = small_reference(shape)
+    w, h, ww, wh, _ = shape
+    fac = np.float32(1 / 5000.0)
+    F = len(frames)
+    member = np.zeros((F, (h + 1) // 2, (w + 1) // 2), np.int32); n = np.zeros(F, np.int32)
+    stats = np.zeros((F, SMALL_SHAPES[shape][0]), PEAC_STATS_DTYPE)
+    for device in (-1, 16):
+        rc = lib.msl_peac_membership_batch(device, ptr(frames), frames.strides[1], frames.strides[0], w, h, F, MSL_MEM_HOST, I["fx"], I["fy"], I["cx"], I["cy"], fac,
+                                           ptr(p), ptr(member), ptr(n))
+        assert rc == -1 and str(device) in lib.msl_last_error().decode(), (device, rc)   # MSL_ERR_INVALID
+        rc = lib.msl_peac_block_stats(device, ptr(frames), frames.strides[1], frames.strides[0], w, h, F, MSL_MEM_HOST, I["fx"], I["fy"], I["cx"], I["cy"], fac,
+                                      ww, wh, 0.04, 0.02, 0, None, ptr(stats), MSL_MEM_HOST)
+        assert rc == -1 and str(device) in lib.msl_last_error().decode(), (device, rc)
+    assert not member.any() and not n.any()
+    _check_small_call(shape)

@@ -36,6 +36,52 @@ def test_host_stage_matches_oracle(oracle, intr_name):
     assert sum(r[1] for r in ref) >= 6 and n[5] == 0
 
 
+# Small calls that still meet every path: more than one window row and column, an odd image (161x121: the half-resolution cloud is ceil(w / 2) x
+# ceil(h / 2) and its last column and row belong to no window), windows that are not square, and a frame without any plane.
+SMALL_SCENES = ((0, 0.0), (100, 0.001), (170, 0.0), (250, 0.003), (300, 0.02))   # (keyframe, dropout)
+# (width, height, window_w, window_h, min_support): windows per frame, the oracle's plane count of every scene
+SMALL_SHAPES = {(64, 48, 4, 4, 40): (48, (1, 2, 1, 2, 1)),
+                (161, 121, 5, 4, 100): (240, (1, 2, 1, 3, 1)),
+                (160, 120, 10, 10, 100): (48, (1, 2, 1, 2, 0))}
+_small = {}
+
+
+def small_reference(shape):
+    """The scenes of one small shape and what the oracle makes of them, computed once per process and read-only:
+    (intrinsics, frames [5, h, w] uint16, library params, [(membership, plane count, blocks) per scene])."""
+    if shape not in _small:
+        from manhattanslam_amd import peac, synth
+        from tests import oracle_lib
+        w, h, ww, wh, support = shape
+        I = synth.scaled_intrinsics(synth.ICL, w)
+        frames = np.stack([_depth(k, I, dr, w, h) for k, dr in SMALL_SCENES])
+        p = peac.default_params(); po = oracle_lib.peac_default_params()
+        for q in (p, po):
+            q["window_w"] = ww; q["window_h"] = wh; q["min_support"] = support
+        ref = [oracle_lib.peac_run(d, I["fx"], I["fy"], I["cx"], I["cy"], np.float32(1 / 5000.0), params=po) for d in frames]
+        nb, counts = SMALL_SHAPES[shape]
+        assert tuple(r[1] for r in ref) == counts and all(len(r[2]) == nb for r in ref), (shape, [r[1] for r in ref])   # never a pass on empty images
+        for a in [frames, p] + [x for r in ref for x in (r[0], r[2])]:
+            a.flags.writeable = False
+        _small[shape] = (I, frames, p, ref)
+    return _small[shape]
+
+
+@pytest.mark.parametrize("shape", list(SMALL_SHAPES), ids=lambda s: "%dx%d" % s[:2])
+def test_host_stage_matches_oracle_on_small_shapes(oracle, shape):
+    """The host stage on the oracle's own block fits: membership images and plane counts are the oracle's, in one call of five frames and frame by frame."""
+    from manhattanslam_amd import peac
+    I, frames, p, ref = small_reference(shape)
+    fac = np.float32(1 / 5000.0)
+    blocks = np.stack([r[2] for r in ref])
+    got, n = peac.plane_membership_from_blocks(blocks, frames, I["fx"], I["fy"], I["cx"], I["cy"], fac, params=p)
+    assert tuple(n) == SMALL_SHAPES[shape][1]
+    for f, (want, nw, _) in enumerate(ref):
+        assert n[f] == nw and np.array_equal(got[f], want), (f, np.argwhere(got[f] != want)[:5])
+        one, n1 = peac.plane_membership_from_blocks(blocks[f:f + 1], frames[f], I["fx"], I["fy"], I["cx"], I["cy"], fac, params=p)
+        assert n1[0] == nw and np.array_equal(one[0], want), f
+
+
 def test_worker_workspaces_are_reusable(oracle):
     """The worker threads keep their workspaces between calls: a frame gives the same image whatever was segmented before it, in calls of
     different sizes, geometries and parameters."""
