@@ -1,4 +1,4 @@
-// msl_orb.hip -- ORB extractor for gfx950 (MI355X): kernels + C ABI.
+// msl_orb.hip -- ORB extractor for gfx950 (MI355X): kernels + device driver (host plan, handle and C ABI: msl_orb_host.hip).
 //
 // Replaces ORB_SLAM2::ORBextractor (reference src/ORBextractor.cc).  Frame-batched pipeline, all
 // integer/byte work, HBM/L2-bound; no MFMA (nothing here is a contraction).  Per batch of B frames:
@@ -14,75 +14,18 @@
 // Float expressions that feed a rounding (angle, rotated pattern coordinates) are written in the
 // reference's order and this file is compiled with -ffp-contract=off.
 
-#include "msl_common.h"
+#include "msl_orb_dev.h"
 
 #include <type_traits>
 
-#include <algorithm>
 #include <cfloat>
 #include <cmath>
-#include <memory>
-#include <vector>
+#include <cstdlib>
 
 using namespace msl;
+using namespace msl::orb;
 
 namespace {
-
-constexpr int ML = 12;          // max pyramid levels
-constexpr int MAXCELL = 64;     // max FAST cell extent (pixels)
-constexpr int MAXNODE = 1024;   // max quadtree list length per level
-constexpr int OCT_NT = 512;     // threads of the quadtree workgroup
-constexpr int OCT_NODE_BYTES = 66;   // k_octree's LDS per node slot
-
-struct LevelDev {
-    int w, h, pitch;
-    unsigned off;       // byte offset inside one frame's pyramid store (levels >= 1)
-    unsigned boff;      // byte offset inside one frame's blurred store
-    int nCols, nRows, wCell, hCell;
-    int cellBase, nCells;
-    int keyBase, keyCap;
-    int quota;
-    int nIni; float hX;
-    float scale; int patch;
-    unsigned xtabOff, ytabOff;  // element offsets into the resize tables
-    int tileBase, tilesX, tilesY;  // blur tiling
-};
-
-struct CellDev {
-    short level, x0, y0, cw, ch, _pad;
-    unsigned keyOff;  // first key slot of the cell (frame relative)
-};
-
-struct ResizeTap { short s0, s1, c0, c1; };
-// one axis of one tile on one level of the fused pyramid: the pixels the tile owns (writes to HBM) and the pixels it has to compute
-// because its share of the next level reads them (level 0: the input pixels it loads)
-struct PyrRange { short ownLo, ownHi, needLo, needHi; };
-
-struct OrbDev {
-    int nlevels, iniTh, minTh;
-    int cellsPerFrame, keysPerFrame, selCap, outCap, blurTiles;
-    unsigned long long pyrStride, blurStride;
-    LevelDev lv[ML];
-    int umax[16];
-    const uint8_t *in; unsigned long long inRowStride, inFrameStride;
-    uint8_t *pyr, *blur;
-    const CellDev *cells;
-    const ResizeTap *taps;
-    const PyrRange *pyrX, *pyrY;   // fused pyramid: [level][tile column] / [level][tile row] ranges (pyrTX == 0: one launch per level)
-    int pyrTX, pyrTY; unsigned pyrBuf0;   // bytes of the first LDS buffer
-    uint32_t *cellCnt, *cellKeys, *keys;
-    uint16_t *knode;
-    uint32_t *sel; int *nsel, *ncand;
-    msl_keypoint *kps; uint8_t *desc; int *nout; int *err;
-    // Frame post-ORB epilogue; frameOn == 0: plain extractor
-    int frameOn;
-    msl_frame_params fp; float gridWInv, gridHInv;
-    const float *depth; unsigned long long depthRowStride, depthFrameStride;   // bytes
-    float *unXY, *depthOut, *uRight; int *gridCell;
-    int nFrames;   // frames of this launch sequence (the kernels run 1-D, XCD-aware grids: xcd_item)
-    int maxNode;   // k_octree: node-array length
-    int octLds;    // k_octree: dynamic LDS bytes = max(OCT_NODE_BYTES * maxNode, 8 * (cells of the largest level + 1))
-};
 
 __constant__ int8_t c_pattern[1024] = {
 #include "../../include/msl_orb_pattern.inc"
@@ -789,7 +732,6 @@ __global__ __launch_bounds__(OCT_NT) void k_octree(OrbDev P) {
 // k_blur: GaussianBlur 7x7 sigma 2 (integer kernel {18,34,49,55,49,34,18} by default, >>16 with rounding),
 // reflect-101 on the level's own borders.  Tile 64 x 32 outputs per workgroup.
 // ---------------------------------------------------------------------------------------------
-constexpr int BT_W = 64, BT_H = 32;
 // Which OpenCV generation's 8-bit Gaussian kernel is pinned: 0 = per-coefficient rounding {18,34,49,55,..}
 // (OpenCV 3.x, sum 257), 1 = error-diffused "bit-exact" kernel {18,34,48,56,..} (later releases, sum 256).  Row sums stay <= 65535.
 #ifndef MSL_BLUR_VARIANT
@@ -1083,270 +1025,32 @@ __global__ __launch_bounds__(256) void k_describe(OrbDev P) {
     }
 }
 
-// =============================================================================================
-// Host side
-// =============================================================================================
-inline int cv_round_f(float v) { return (int)lrintf(v); }
-inline int cv_round_d(double v) { return (int)lrint(v); }
-inline int cv_floor_d(double v) { int i = (int)v; return i - (i > v); }
-inline int cv_ceil_d(double v) { int i = (int)v; return i + (i < v); }
-
-enum { KID_RESIZE = 0, KID_FAST, KID_OCTREE, KID_BLUR, KID_DESCRIBE, KID_COPY };
 const char *kKernelNames[MSL_ORB_NKERNELS] = {"k_pyramid", "k_fast", "k_octree", "k_blur", "k_describe", "copy"};
 
 }  // namespace
 
-struct msl_orb {
-    int device = 0;
-    int nfeatures = 0, nlevels = 0, iniTh = 0, minTh = 0, maxW = 0, maxH = 0, maxBatch = 0;
-    bool octBig = false;   // frames of more than 640 x 480 x 1.5 pixels: level 0 may hold more than 8192 FAST candidates -> k_octree<32>
-    int outCap = 0;   // keypoints per frame the outputs are sized for: fixed by the creation geometry (msl_orb_capacity)
-    double scaleFactor = 0;
-    std::vector<float> scale, invScale, sigma2, invSigma2;
-    std::vector<int> perLevel;
-    int umax[16];
-    // geometry is built for one frame size at a time (rebuilt if the size changes)
-    int geomW = 0, geomH = 0;
-    OrbDev dev{};
-    hipStream_t stream = nullptr; bool ownStream = true;
-    // device allocations of the current geometry (build_geometry); outBlock = [nout[B] | kps[B][cap] | desc[B][cap]], d_nout / d_kps / d_desc point into it
-    struct Geometry { DevBuf in, pyr, blur, cells, taps, pyrRanges, cellCnt, cellKeys, keys, knode, sel, nsel, ncand, outBlock; } geo;
-    size_t inPitch = 0, pyrLds = 0, outKpsOff = 0, outDescOff = 0;
-    msl_keypoint *d_kps = nullptr; uint8_t *d_desc = nullptr; int *d_nout = nullptr;
-    DevBuf d_err; PinBuf h_err;
-    PinBuf h_pinIn, h_pinOut;   // staging of the single-frame drop-in call
-    hipStream_t sideStream = nullptr; hipEvent_t evFork = nullptr, evJoin = nullptr;             // single-frame calls: the blur runs beside FAST + quadtree
-    DevBuf d_depthIn;           // staged depth frames (host input)
-    DevBuf d_unXY, d_depthOut, d_uRight, d_gridCell;   // outputs of the frame epilogue
-    int lastFrames = 0;
-    KernelProfiler prof;
-};
+// =============================================================================================
+// Device driver
+// =============================================================================================
+namespace msl {
+namespace orb {
 
-namespace {
+const char *kernel_name(int kid) { return kKernelNames[kid]; }
 
-// Waits for the work that may still use the geometry buffers (the side stream's is joined into h->stream by evJoin), then frees them.
-int free_geometry(msl_orb *h) {
-    MSL_HIP_TRY(hipStreamSynchronize(h->stream));
-    h->geo = msl_orb::Geometry();
-    h->d_kps = nullptr; h->d_desc = nullptr; h->d_nout = nullptr;
-    h->geomW = h->geomH = 0;
+int allow_octree_lds(int octLds) {
+    if (octLds <= 32 * 1024) return MSL_OK;
+    MSL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_octree<16>), hipFuncAttributeMaxDynamicSharedMemorySize, octLds));
+    MSL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_octree<32>), hipFuncAttributeMaxDynamicSharedMemorySize, octLds));
     return MSL_OK;
 }
 
-// Level sizes, FAST cell grid, quadtree roots, resize taps, blur tiling for a w x h frame.
-int build_geometry(msl_orb *h, int W, int H) {
-    if (h->geomW == W && h->geomH == H) return MSL_OK;
-    { const int rc = free_geometry(h); if (rc != MSL_OK) return rc; }
-    OrbDev &D = h->dev;
-    memset(&D, 0, sizeof(D));
-    const int L = h->nlevels, B = h->maxBatch;
-    D.nlevels = L; D.iniTh = h->iniTh; D.minTh = h->minTh;
-    for (int i = 0; i < 16; i++) D.umax[i] = h->umax[i];
-    std::vector<CellDev> cells;
-    std::vector<ResizeTap> taps;
-    size_t pyrOff = 0, blurOff = 0;
-    unsigned keyOff = 0;
-    int tileBase = 0, maxQuota = 0, maxList = 0, needCap = 0, maxSel = 0;
-    for (int l = 0; l < L; l++) {
-        LevelDev &G = D.lv[l];
-        const float s = h->invScale[l];
-        G.w = cv_round_f((float)W * s); G.h = cv_round_f((float)H * s);    // src/ORBextractor.cc:875
-        G.pitch = (G.w + 63) & ~63;
-        G.scale = h->scale[l];
-        G.patch = (int)(31 * h->scale[l]);                                  // :788
-        G.quota = h->perLevel[l];
-        maxQuota = std::max(maxQuota, G.quota);
-        if (l > 0) { G.off = (unsigned)pyrOff; pyrOff += (size_t)G.pitch * G.h; }
-        G.boff = (unsigned)blurOff; blurOff += (size_t)G.pitch * G.h;
-        // FAST cell grid (:728-743)
-        const int minB = 16, maxBX = G.w - 16, maxBY = G.h - 16;
-        const float width = (float)(maxBX - minB), height = (float)(maxBY - minB);
-        const float Wc = 30;
-        G.nCols = (int)(width / Wc); G.nRows = (int)(height / Wc);
-        if (G.nCols < 1 || G.nRows < 1) {
-            set_error("level %d (%dx%d) is too small for the 30-px FAST grid", l, G.w, G.h);
-            return MSL_ERR_INVALID;
-        }
-        G.wCell = (int)ceilf(width / G.nCols); G.hCell = (int)ceilf(height / G.nRows);
-        if (G.wCell > MAXCELL || G.hCell > MAXCELL || G.w > 4095 + 16 || G.h > 4095 + 16) {
-            set_error("unsupported level geometry %dx%d (cell %dx%d)", G.w, G.h, G.wCell, G.hCell);
-            return MSL_ERR_INVALID;
-        }
-        G.cellBase = (int)cells.size(); G.nCells = G.nRows * G.nCols;
-        G.keyBase = (int)keyOff;
-        for (int i = 0; i < G.nRows; i++)
-            for (int j = 0; j < G.nCols; j++) {
-                // view = rows [iniY,maxY) x cols [iniX,maxX); cv::FAST computes its inner 3-px-inset region
-                const float iniY = (float)(minB + i * G.hCell), iniX = (float)(minB + j * G.wCell);
-                float maxY = iniY + G.hCell + 6, maxX = iniX + G.wCell + 6;
-                CellDev c{}; c.level = (short)l; c.keyOff = keyOff;
-                const bool skip = (iniY >= maxBY - 3) || (iniX >= maxBX - 6);
-                if (maxY > maxBY) maxY = (float)maxBY;
-                if (maxX > maxBX) maxX = (float)maxBX;
-                const int cw = (int)maxX - (int)iniX - 6, chh = (int)maxY - (int)iniY - 6;
-                if (!skip && cw > 0 && chh > 0) {
-                    c.x0 = (short)((int)iniX + 3); c.y0 = (short)((int)iniY + 3); c.cw = (short)cw; c.ch = (short)chh;
-                    keyOff += (unsigned)(((cw + 1) / 2) * ((chh + 1) / 2));  // strict 3x3 maxima are non-adjacent
-                }
-                cells.push_back(c);
-            }
-        G.keyCap = (int)keyOff - G.keyBase;
-        if (G.keyCap >= (1 << 24)) { set_error("level too large"); return MSL_ERR_INVALID; }
-        // quadtree roots (:536-552)
-        G.nIni = (int)roundf((float)(maxBX - minB) / (maxBY - minB));
-        if (G.nIni < 1) { set_error("unsupported aspect ratio (nIni = 0)"); return MSL_ERR_INVALID; }
-        G.hX = (float)(maxBX - minB) / G.nIni;
-        // longest quadtree list of this level: a full round only runs when its outcome stays <= quota (the first one makes <= 4 nIni nodes), the
-        // one-by-one phase stops at the first length >= quota and every expansion adds <= 3
-        if (std::max(G.quota, 4 * G.nIni) + 2 > MAXNODE) { set_error("per-level quota %d exceeds %d", G.quota, MAXNODE - 2); return MSL_ERR_INVALID; }
-        maxList = std::max(maxList, std::max(G.quota, 4 * G.nIni) + 2);
-        // keypoints this level can return: quota + 2 from the one-by-one phase (:691-696), or the <= 4 nIni nodes of the first full round when
-        // that already reaches the quota (wide images with a small budget: nIni = round(width / height) roots, :536-552)
-        needCap += std::max(G.quota + 2, 4 * G.nIni); maxSel = std::max(maxSel, std::max(G.quota + 2, 4 * G.nIni));
-        // blur tiles
-        G.tilesX = (G.w + BT_W - 1) / BT_W; G.tilesY = (G.h + BT_H - 1) / BT_H;
-        G.tileBase = tileBase; tileBase += G.tilesX * G.tilesY;
-        // resize taps (cv::resize INTER_LINEAR 8U tables)
-        if (l > 0) {
-            const int sw = D.lv[l - 1].w, sh = D.lv[l - 1].h;
-            const double scale_x = 1. / ((double)G.w / sw), scale_y = 1. / ((double)G.h / sh);
-            G.xtabOff = (unsigned)taps.size();
-            for (int dx = 0; dx < G.w; dx++) {
-                float fx = (float)((dx + 0.5) * scale_x - 0.5);
-                int sx = cv_floor_d(fx);
-                fx -= sx;
-                if (sx < 0) { fx = 0; sx = 0; }
-                if (sx >= sw - 1) { fx = 0; sx = sw - 1; }
-                ResizeTap t;
-                t.s0 = (short)sx; t.s1 = (short)std::min(sx + 1, sw - 1);
-                t.c0 = (short)std::min(std::max(cv_round_f((1.f - fx) * 2048), -32768), 32767);
-                t.c1 = (short)std::min(std::max(cv_round_f(fx * 2048), -32768), 32767);
-                if (sx + 1 >= sw) { t.c0 = 2048; t.c1 = 0; }
-                taps.push_back(t);
-            }
-            G.ytabOff = (unsigned)taps.size();
-            for (int dy = 0; dy < G.h; dy++) {
-                float fy = (float)((dy + 0.5) * scale_y - 0.5);
-                int sy = cv_floor_d(fy);
-                fy -= sy;
-                ResizeTap t;
-                t.s0 = (short)std::min(std::max(sy, 0), sh - 1); t.s1 = (short)std::min(std::max(sy + 1, 0), sh - 1);
-                t.c0 = (short)std::min(std::max(cv_round_f((1.f - fy) * 2048), -32768), 32767);
-                t.c1 = (short)std::min(std::max(cv_round_f(fy * 2048), -32768), 32767);
-                taps.push_back(t);
-            }
-        }
-    }
-    // ---- fused pyramid (k_pyramid): one tile grid for all levels, ranges per axis ----
-    std::vector<PyrRange> pyrX, pyrY;
-    D.pyrTX = D.pyrTY = 0;
-    if (L >= 2) {
-        const int TX = std::max(1, D.lv[L - 1].w / 22), TY = std::max(1, D.lv[L - 1].h / 22);
-        auto axis = [&](int T, bool isX, std::vector<PyrRange> &out, std::vector<int> &extent) {
-            out.assign((size_t)L * T, PyrRange{0, 0, 0, 0});
-            extent.assign(L, 0);
-            for (int i = 0; i < T; i++) {
-                for (int l = 1; l < L; l++) {
-                    const int n = isX ? D.lv[l].w : D.lv[l].h;
-                    PyrRange &r = out[(size_t)l * T + i];
-                    r.ownLo = (short)((long long)i * n / T); r.ownHi = (short)((long long)(i + 1) * n / T);
-                }
-                int lo = out[(size_t)(L - 1) * T + i].ownLo, hi = out[(size_t)(L - 1) * T + i].ownHi;
-                for (int l = L - 1; l >= 1; l--) {
-                    PyrRange &r = out[(size_t)l * T + i];
-                    r.needLo = (short)lo; r.needHi = (short)hi;
-                    extent[l] = std::max(extent[l], hi - lo);
-                    const ResizeTap *tab = taps.data() + (isX ? D.lv[l].xtabOff : D.lv[l].ytabOff);
-                    int slo = tab[lo].s0, shi = tab[hi - 1].s1 + 1;   // source pixels of level l-1 this range reads (taps are monotone)
-                    for (int q = lo; q < hi; q++) { slo = std::min(slo, (int)std::min(tab[q].s0, tab[q].s1)); shi = std::max(shi, (int)std::max(tab[q].s0, tab[q].s1) + 1); }
-                    if (l - 1 >= 1) { const PyrRange &o = out[(size_t)(l - 1) * T + i]; lo = std::min(slo, (int)o.ownLo); hi = std::max(shi, (int)o.ownHi); }
-                    else { lo = slo; hi = shi; }
-                }
-                PyrRange &r0 = out[i];
-                r0.ownLo = r0.ownHi = 0; r0.needLo = (short)lo; r0.needHi = (short)hi;
-                extent[0] = std::max(extent[0], hi - lo);
-            }
-        };
-        std::vector<int> ex, ey;
-        axis(TX, true, pyrX, ex); axis(TY, false, pyrY, ey);
-        size_t b0 = 0, b1 = 0;
-        bool ok = true;
-        for (int l = 0; l < L; l++) {
-            const size_t a = (size_t)(l == 0 ? (ex[l] + 3) & ~3 : ex[l]) * ey[l];   // (k_pyramid stages the input region with a dword pitch)
-            if (l & 1) b1 = std::max(b1, a); else b0 = std::max(b0, a);
-            if (l >= 1 && (D.lv[l].w < TX || D.lv[l].h < TY)) ok = false;
-        }
-        b0 = (b0 + 15) & ~(size_t)15;
-        for (int l = 0; l < L; l++) if (ex[l] >= 128 || (size_t)ex[l] * ey[l] >= (1u << 15)) ok = false;   // k_pyramid's multiply-shift row index
-        if (ok && b0 + b1 <= 48 * 1024) { D.pyrTX = TX; D.pyrTY = TY; D.pyrBuf0 = (unsigned)b0; h->pyrLds = b0 + b1; }
-    }
-    D.cellsPerFrame = (int)cells.size();
-    D.keysPerFrame = (int)keyOff;
-    D.selCap = maxSel;
-    D.maxNode = ((maxList + 63) & ~63) + 64;   // the analytic bound, rounded up, plus one 64-node block of slack (4 KB): an overrun would zero a whole level (P.err)
-    {
-        int maxCells = 0;
-        for (int l = 0; l < L; l++) maxCells = std::max(maxCells, D.lv[l].nCells);
-        D.octLds = (int)((std::max<size_t>((size_t)OCT_NODE_BYTES * D.maxNode, 2 * sizeof(unsigned) * (size_t)(maxCells + 1)) + 15) & ~(size_t)15);
-    }
-    if (D.octLds > 32 * 1024)   // (a large feature budget: more dynamic LDS than a launch gets by default)
-    {
-        MSL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_octree<16>), hipFuncAttributeMaxDynamicSharedMemorySize, D.octLds));
-        MSL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_octree<32>), hipFuncAttributeMaxDynamicSharedMemorySize, D.octLds));
-    }
-    if (h->outCap == 0) h->outCap = std::max(h->nfeatures + 2 * L, needCap);   // creation: the handle's capacity follows its (max_width, max_height) geometry
-    if (needCap > h->outCap) {
-        set_error("frame %dx%d can return %d keypoints (aspect ratio: %d quadtree roots), the extractor was created for %d; create it with this frame size", W, H,
-                  needCap, D.lv[0].nIni, h->outCap);
-        return MSL_ERR_INVALID;
-    }
-    D.outCap = h->outCap;
-    h->octBig = (long long)W * H > 640ll * 480 * 3 / 2;
-    D.blurTiles = tileBase;
-    D.pyrStride = (pyrOff + 255) & ~(size_t)255;
-    D.blurStride = (blurOff + 255) & ~(size_t)255;
-    h->inPitch = (size_t)((W + 63) & ~63);
+}  // namespace orb
+}  // namespace msl
 
-    // outputs of a call in ONE allocation, counts first: the single-frame drop-in call fetches everything with one copy
-    h->outKpsOff = (sizeof(int) * (size_t)B + 255) & ~(size_t)255;
-    h->outDescOff = h->outKpsOff + ((sizeof(msl_keypoint) * (size_t)D.outCap * B + 255) & ~(size_t)255);
-    msl_orb::Geometry &g = h->geo;
-    MSL_HIP_TRY(grow_all(h->stream, {{g.in, h->inPitch * H * B}, {g.pyr, std::max<size_t>(D.pyrStride, 256) * B}, {g.blur, D.blurStride * B},
-                                     {g.cells, sizeof(CellDev) * cells.size()}, {g.taps, sizeof(ResizeTap) * std::max<size_t>(taps.size(), 1)},
-                                     {g.pyrRanges, D.pyrTX ? sizeof(PyrRange) * (pyrX.size() + pyrY.size()) : 0},
-                                     {g.cellCnt, sizeof(uint32_t) * cells.size() * B}, {g.cellKeys, sizeof(uint32_t) * (size_t)keyOff * B},
-                                     {g.keys, sizeof(uint32_t) * (size_t)keyOff * B}, {g.knode, sizeof(uint16_t) * (size_t)keyOff * B},
-                                     {g.sel, sizeof(uint32_t) * (size_t)D.selCap * L * B}, {g.nsel, sizeof(int) * L * B}, {g.ncand, sizeof(int) * L * B},
-                                     {g.outBlock, h->outDescOff + (size_t)32 * D.outCap * B}}));
-    if (D.pyrTX) {
-        PyrRange *ranges = (PyrRange *)g.pyrRanges.p;
-        MSL_HIP_TRY(hipMemcpy(ranges, pyrX.data(), sizeof(PyrRange) * pyrX.size(), hipMemcpyHostToDevice));
-        MSL_HIP_TRY(hipMemcpy(ranges + pyrX.size(), pyrY.data(), sizeof(PyrRange) * pyrY.size(), hipMemcpyHostToDevice));
-        D.pyrX = ranges; D.pyrY = ranges + pyrX.size();
-    }
-    uint8_t *out = (uint8_t *)g.outBlock.p;
-    h->d_nout = reinterpret_cast<int *>(out);
-    h->d_kps = reinterpret_cast<msl_keypoint *>(out + h->outKpsOff);
-    h->d_desc = out + h->outDescOff;
-    MSL_HIP_TRY(hipMemcpy(g.cells.p, cells.data(), sizeof(CellDev) * cells.size(), hipMemcpyHostToDevice));
-    if (!taps.empty())
-        MSL_HIP_TRY(hipMemcpy(g.taps.p, taps.data(), sizeof(ResizeTap) * taps.size(), hipMemcpyHostToDevice));
-    D.pyr = (uint8_t *)g.pyr.p; D.blur = (uint8_t *)g.blur.p; D.cells = (const CellDev *)g.cells.p; D.taps = (const ResizeTap *)g.taps.p;
-    D.cellCnt = (uint32_t *)g.cellCnt.p; D.cellKeys = (uint32_t *)g.cellKeys.p; D.keys = (uint32_t *)g.keys.p; D.knode = (uint16_t *)g.knode.p;
-    D.sel = (uint32_t *)g.sel.p; D.nsel = (int *)g.nsel.p; D.ncand = (int *)g.ncand.p; D.err = (int *)h->d_err.p;
-    h->geomW = W; h->geomH = H;
-    return MSL_OK;
-}
-
-// Launch the whole pipeline for n frames whose pixels are already on the device.
-struct FrameEpilogue {
-    msl_frame_params fp; const float *depth; size_t depthRowStride, depthFrameStride;
-    float *unXY, *depthOut, *uRight; int *gridCell;
-};
-
-int launch_pipeline(msl_orb *h, const uint8_t *d_gray, size_t rowStride, size_t frameStride, int n,
-                    msl_keypoint *d_kps, uint8_t *d_desc, int *d_nout, const FrameEpilogue *ep = nullptr) {
-    OrbDev P = h->dev;
+int orb_launch_pipeline(const OrbDev *dev, OrbLaunch *launch, const uint8_t *d_gray, size_t rowStride, size_t frameStride, int n,
+                        msl_keypoint *d_kps, uint8_t *d_desc, int *d_nout, const FrameEpilogue *ep) {
+    OrbLaunch &q = *launch;
+    OrbDev P = *dev;
     P.in = d_gray; P.inRowStride = rowStride; P.inFrameStride = frameStride;
     P.kps = d_kps; P.desc = d_desc; P.nout = d_nout;
     P.frameOn = ep ? 1 : 0;
@@ -1358,468 +1062,47 @@ int launch_pipeline(msl_orb *h, const uint8_t *d_gray, size_t rowStride, size_t 
         P.depth = ep->depth; P.depthRowStride = ep->depthRowStride; P.depthFrameStride = ep->depthFrameStride;
         P.unXY = ep->unXY; P.depthOut = ep->depthOut; P.uRight = ep->uRight; P.gridCell = ep->gridCell;
     }
-    hipStream_t s = h->stream;
-    const int L = h->nlevels;
+    hipStream_t s = q.stream;
+    const int L = P.nlevels;
     static const bool perLevel = getenv("MSL_ORB_PYRAMID") && !strcmp(getenv("MSL_ORB_PYRAMID"), "levels");
     if (P.pyrTX && !perLevel) {
-        h->prof.begin(KID_RESIZE, s);
-        hipLaunchKernelGGL(k_pyramid, dim3(xcd_grid1((long long)P.pyrTX * P.pyrTY * n)), dim3(256), h->pyrLds, s, P);
-        h->prof.end(s);
+        q.prof.begin(KID_RESIZE, s);
+        hipLaunchKernelGGL(k_pyramid, dim3(xcd_grid1((long long)P.pyrTX * P.pyrTY * n)), dim3(256), q.pyrLds, s, P);
+        q.prof.end(s);
     } else {
         for (int l = 1; l < L; l++) {
             const LevelDev &G = P.lv[l];
-            h->prof.begin(KID_RESIZE, s);
+            q.prof.begin(KID_RESIZE, s);
             hipLaunchKernelGGL(k_resize, dim3((G.w + 63) / 64, (G.h + 3) / 4, n), dim3(256), 0, s, P, l);
-            h->prof.end(s);
+            q.prof.end(s);
         }
     }
     // One frame cannot fill the GPU and every kernel is a dependent launch: the blur (needs the pyramid only) then runs on a side stream beside
     // FAST + quadtree instead of behind them.  Batched calls keep one stream: their kernels fill the GPU and the order keeps each frame's data warm.
-    const bool fork = n == 1 && h->sideStream && !h->prof.on;
+    const bool fork = n == 1 && q.sideStream && !q.prof.on;
     if (fork) {
-        MSL_HIP_TRY(hipEventRecord(h->evFork, s));
-        MSL_HIP_TRY(hipStreamWaitEvent(h->sideStream, h->evFork, 0));
-        hipLaunchKernelGGL(k_blur, dim3(xcd_grid1((long long)P.blurTiles * n)), dim3(256), 0, h->sideStream, P);
-        MSL_HIP_TRY(hipEventRecord(h->evJoin, h->sideStream));
+        MSL_HIP_TRY(hipEventRecord(q.evFork, s));
+        MSL_HIP_TRY(hipStreamWaitEvent(q.sideStream, q.evFork, 0));
+        hipLaunchKernelGGL(k_blur, dim3(xcd_grid1((long long)P.blurTiles * n)), dim3(256), 0, q.sideStream, P);
+        MSL_HIP_TRY(hipEventRecord(q.evJoin, q.sideStream));
     }
-    h->prof.begin(KID_FAST, s);
+    q.prof.begin(KID_FAST, s);
     hipLaunchKernelGGL(k_fast, dim3(xcd_grid1((long long)P.cellsPerFrame * n)), dim3(256), 0, s, P);
-    h->prof.end(s);
-    h->prof.begin(KID_OCTREE, s);
-    if (h->octBig) hipLaunchKernelGGL(k_octree<32>, dim3(xcd_grid1((long long)L * n)), dim3(OCT_NT), (size_t)P.octLds, s, P);
+    q.prof.end(s);
+    q.prof.begin(KID_OCTREE, s);
+    if (q.octBig) hipLaunchKernelGGL(k_octree<32>, dim3(xcd_grid1((long long)L * n)), dim3(OCT_NT), (size_t)P.octLds, s, P);
     else hipLaunchKernelGGL(k_octree<16>, dim3(xcd_grid1((long long)L * n)), dim3(OCT_NT), (size_t)P.octLds, s, P);
-    h->prof.end(s);
+    q.prof.end(s);
     if (fork) {
-        MSL_HIP_TRY(hipStreamWaitEvent(s, h->evJoin, 0));
+        MSL_HIP_TRY(hipStreamWaitEvent(s, q.evJoin, 0));
     } else {
-        h->prof.begin(KID_BLUR, s);
+        q.prof.begin(KID_BLUR, s);
         hipLaunchKernelGGL(k_blur, dim3(xcd_grid1((long long)P.blurTiles * n)), dim3(256), 0, s, P);
-        h->prof.end(s);
+        q.prof.end(s);
     }
-    h->prof.begin(KID_DESCRIBE, s);
+    q.prof.begin(KID_DESCRIBE, s);
     hipLaunchKernelGGL(k_describe, dim3(xcd_grid1((long long)((P.selCap + 3) / 4) * L * n)), dim3(256), 0, s, P);
-    h->prof.end(s);
+    q.prof.end(s);
     MSL_HIP_TRY(hipGetLastError());
-    h->lastFrames = n;
     return MSL_OK;
 }
-
-int check_device_error(msl_orb *h) {
-    MSL_HIP_TRY(hipMemcpyAsync(h->h_err.p, h->d_err.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    MSL_HIP_TRY(hipStreamSynchronize(h->stream));
-    h->prof.drain();
-    const int e = *(const int *)h->h_err.p;
-    if (e) {
-        (void)hipMemsetAsync(h->d_err.p, 0, sizeof(int), h->stream);
-        set_error("device-side bound exceeded in ORB pipeline (code %d)", e);
-        return MSL_ERR_OVERFLOW;
-    }
-    return MSL_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-msl_orb *msl_orb_create(int nfeatures, float scaleFactorF, int nlevels, int iniThFAST, int minThFAST, int max_width,
-                        int max_height, int max_batch, int device) noexcept {
-    try {
-    if (nfeatures < 1 || nlevels < 1 || nlevels > ML || !(scaleFactorF > 1.0f) || iniThFAST < 1 || iniThFAST > 255 ||
-        minThFAST < 1 || minThFAST > 255 || max_width < 1 || max_height < 1 || max_batch < 1) {
-        set_error("msl_orb_create: invalid argument");
-        return nullptr;
-    }
-    if (bind_device(device) != MSL_OK) return nullptr;
-    // (owned by a guard until the handle is complete: an exception from the containers below -- std::bad_alloc -- lands in the catch barrier, and the
-    // streams, events and device buffers created so far must go with it)
-    std::unique_ptr<msl_orb, void (*)(msl_orb *)> guard(new msl_orb, [](msl_orb *p) { msl_orb_destroy(p); });
-    msl_orb *h = guard.get();
-    h->device = device; h->nfeatures = nfeatures; h->nlevels = nlevels; h->iniTh = iniThFAST; h->minTh = minThFAST;
-    h->maxW = max_width; h->maxH = max_height; h->maxBatch = max_batch;
-    h->scaleFactor = scaleFactorF;  // include/ORBextractor.h:97 keeps it as double
-    // scale tables and per-level quotas, src/ORBextractor.cc:416-445
-    h->scale.resize(nlevels); h->sigma2.resize(nlevels); h->invScale.resize(nlevels); h->invSigma2.resize(nlevels);
-    h->scale[0] = 1.0f; h->sigma2[0] = 1.0f;
-    for (int i = 1; i < nlevels; i++) {
-        h->scale[i] = (float)(h->scale[i - 1] * h->scaleFactor);
-        h->sigma2[i] = h->scale[i] * h->scale[i];
-    }
-    for (int i = 0; i < nlevels; i++) { h->invScale[i] = 1.0f / h->scale[i]; h->invSigma2[i] = 1.0f / h->sigma2[i]; }
-    h->perLevel.resize(nlevels);
-    const float factor = (float)(1.0f / h->scaleFactor);
-    float nDesired = nfeatures * (1 - factor) / (1 - (float)pow((double)factor, (double)nlevels));
-    int sum = 0;
-    for (int level = 0; level < nlevels - 1; level++) {
-        h->perLevel[level] = cv_round_f(nDesired);
-        sum += h->perLevel[level];
-        nDesired *= factor;
-    }
-    h->perLevel[nlevels - 1] = std::max(nfeatures - sum, 0);
-    // circular patch row ends, :453-467
-    {
-        int v, v0;
-        const int vmax = cv_floor_d(15 * sqrtf(2.f) / 2 + 1), vmin = cv_ceil_d(15 * sqrtf(2.f) / 2);
-        for (v = 0; v < 16; v++) h->umax[v] = 0;
-        for (v = 0; v <= vmax; ++v) h->umax[v] = cv_round_d(sqrt(225.0 - v * v));
-        for (v = 15, v0 = 0; v >= vmin; --v) {
-            while (h->umax[v0] == h->umax[v0 + 1]) ++v0;
-            h->umax[v] = v0;
-            ++v0;
-        }
-    }
-    int prLo = 0, prHi = 0;   // frame-batched throughput work: lowest priority, so latency-critical streams of the process go first
-    (void)hipDeviceGetStreamPriorityRange(&prLo, &prHi);
-    if (hipStreamCreateWithPriority(&h->stream, hipStreamNonBlocking, prLo) != hipSuccess ||
-        h->d_err.grow(2048, h->stream) != hipSuccess || hipMemset(h->d_err.p, 0, 2048) != hipSuccess ||   // [0] deferred error; from byte 128: 200 device-clock stamps of experiment builds
-        h->h_err.grow(sizeof(int), h->stream) != hipSuccess ||
-        hipStreamCreateWithPriority(&h->sideStream, hipStreamNonBlocking, prLo) != hipSuccess ||
-        hipEventCreateWithFlags(&h->evFork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&h->evJoin, hipEventDisableTiming) != hipSuccess) {
-        set_error("msl_orb_create: HIP resource allocation failed");
-        return nullptr;
-    }
-    h->prof.nk = MSL_ORB_NKERNELS;
-    if (build_geometry(h, max_width, max_height) != MSL_OK) return nullptr;
-    return guard.release();
-    } MSL_ABI_CATCH_PTR
-}
-
-void msl_orb_destroy(msl_orb *h) noexcept {
-    try {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->sideStream) (void)hipStreamSynchronize(h->sideStream);
-    h->prof.destroy();
-    if (h->evFork) (void)hipEventDestroy(h->evFork);
-    if (h->evJoin) (void)hipEventDestroy(h->evJoin);
-    const hipStream_t streams[2] = {h->sideStream, h->ownStream ? h->stream : nullptr};
-    delete h;   // frees the buffers
-    for (hipStream_t st : streams) if (st) (void)hipStreamDestroy(st);
-    } MSL_ABI_CATCH_VOID
-}
-
-int msl_orb_scale_tables(const msl_orb *h, float *sf, float *isf, float *s2, float *is2) noexcept {
-    try {
-    if (!h) return MSL_ERR_INVALID;
-    for (int i = 0; i < h->nlevels; i++) {
-        if (sf) sf[i] = h->scale[i];
-        if (isf) isf[i] = h->invScale[i];
-        if (s2) s2[i] = h->sigma2[i];
-        if (is2) is2[i] = h->invSigma2[i];
-    }
-    return MSL_OK;
-    } MSL_ABI_CATCH_INT
-}
-int msl_orb_features_per_level(const msl_orb *h, int32_t *out) noexcept {
-    try {
-    if (!h || !out) return MSL_ERR_INVALID;
-    for (int i = 0; i < h->nlevels; i++) out[i] = h->perLevel[i];
-    return MSL_OK;
-    } MSL_ABI_CATCH_INT
-}
-int msl_orb_capacity(const msl_orb *h) noexcept { try { return h ? h->outCap : MSL_ERR_INVALID; } MSL_ABI_CATCH_INT }
-int msl_orb_levels(const msl_orb *h) noexcept { try { return h ? h->nlevels : MSL_ERR_INVALID; } MSL_ABI_CATCH_INT }
-
-int msl_orb_set_stream(msl_orb *h, void *hip_stream) noexcept {
-    try {
-    if (!h) return MSL_ERR_INVALID;
-    MSL_HIP_TRY(hipSetDevice(h->device));
-    MSL_HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->ownStream) (void)hipStreamDestroy(h->stream);
-    h->stream = (hipStream_t)hip_stream; h->ownStream = false;
-    return MSL_OK;
-    } MSL_ABI_CATCH_INT
-}
-
-int msl_orb_wait_event(msl_orb *h, void *hip_event) noexcept {
-    try {
-    if (!h || !hip_event) return MSL_ERR_INVALID;
-    MSL_HIP_TRY(hipSetDevice(h->device));
-    MSL_HIP_TRY(hipStreamWaitEvent(h->stream, (hipEvent_t)hip_event, 0));   // (the side stream forks from this one inside every call)
-    return MSL_OK;
-    } MSL_ABI_CATCH_INT
-}
-
-int msl_orb_sync(msl_orb *h) noexcept {
-    try {
-    if (!h) return MSL_ERR_INVALID;
-    MSL_HIP_TRY(hipSetDevice(h->device));
-    return check_device_error(h);
-    } MSL_ABI_CATCH_INT
-}
-
-int msl_orb_extract_batch(msl_orb *h, const uint8_t *gray, int n_frames, int width, int height, size_t row_stride,
-                          size_t frame_stride, msl_mem in_mem, msl_keypoint *kps, uint8_t *desc32, int cap,
-                          int32_t *n_out, msl_mem out_mem) noexcept {
-    try {
-    if (!h || !n_out || n_frames < 0) { set_error("msl_orb_extract_batch: invalid argument"); return MSL_ERR_INVALID; }
-    if (n_frames == 0) return MSL_OK;
-    if (!gray || width == 0 || height == 0) {  // empty image: silent return (src/ORBextractor.cc:815-816)
-        if (out_mem == MSL_MEM_HOST) for (int f = 0; f < n_frames; f++) n_out[f] = 0;
-        else { MSL_HIP_TRY(hipSetDevice(h->device)); MSL_HIP_TRY(hipMemsetAsync(n_out, 0, sizeof(int) * n_frames, h->stream)); }
-        return MSL_OK;
-    }
-    if (n_frames > h->maxBatch || width > h->maxW || height > h->maxH || row_stride < (size_t)width || !kps || !desc32) {
-        set_error("msl_orb_extract_batch: frame %dx%d x%d exceeds the handle's limits (%dx%d x%d) or bad pointers", width,
-                  height, n_frames, h->maxW, h->maxH, h->maxBatch);
-        return MSL_ERR_INVALID;
-    }
-    const int outCap = h->outCap;
-    if (cap < outCap) { set_error("msl_orb_extract_batch: cap %d < required %d", cap, outCap); return MSL_ERR_CAPACITY; }
-    MSL_HIP_TRY(hipSetDevice(h->device));
-    int rc = build_geometry(h, width, height);
-    if (rc != MSL_OK) return rc;
-    const uint8_t *d_gray = gray; size_t rs = row_stride, fs = frame_stride;
-    if (in_mem == MSL_MEM_HOST) {
-        h->prof.begin(KID_COPY, h->stream);
-        if (row_stride == (size_t)width && h->inPitch == (size_t)width && frame_stride == (size_t)width * height) {
-            // tightly packed frames (the streaming case): one copy for the whole batch
-            MSL_HIP_TRY(hipMemcpyAsync(h->geo.in.p, gray, (size_t)width * height * n_frames, hipMemcpyHostToDevice, h->stream));
-        } else {
-            for (int f = 0; f < n_frames; f++)
-                MSL_HIP_TRY(hipMemcpy2DAsync((uint8_t *)h->geo.in.p + (size_t)f * h->inPitch * height, h->inPitch, gray + (size_t)f * frame_stride,
-                                             row_stride, width, height, hipMemcpyHostToDevice, h->stream));
-        }
-        h->prof.end(h->stream);
-        d_gray = (const uint8_t *)h->geo.in.p; rs = h->inPitch; fs = h->inPitch * height;
-    }
-    if (out_mem == MSL_MEM_DEVICE && cap == outCap) {
-        return launch_pipeline(h, d_gray, rs, fs, n_frames, kps, desc32, n_out);
-    }
-    rc = launch_pipeline(h, d_gray, rs, fs, n_frames, h->d_kps, h->d_desc, h->d_nout);
-    if (rc != MSL_OK) return rc;
-    const hipMemcpyKind kind = out_mem == MSL_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    MSL_HIP_TRY(hipMemcpyAsync(n_out, h->d_nout, sizeof(int) * n_frames, kind, h->stream));
-    MSL_HIP_TRY(hipMemcpy2DAsync(kps, sizeof(msl_keypoint) * cap, h->d_kps, sizeof(msl_keypoint) * outCap,
-                                 sizeof(msl_keypoint) * outCap, n_frames, kind, h->stream));
-    MSL_HIP_TRY(hipMemcpy2DAsync(desc32, (size_t)32 * cap, h->d_desc, (size_t)32 * outCap, (size_t)32 * outCap, n_frames, kind,
-                                 h->stream));
-    if (out_mem == MSL_MEM_HOST) return check_device_error(h);
-    return MSL_OK;
-    } MSL_ABI_CATCH_INT
-}
-
-// The reference's call pattern: one frame per call, host buffers in and out, the result needed before the caller goes on (src/Frame.cc:100,
-// 175-177).  Latency is everything here, so this form avoids every pageable-memory transfer: the frame goes through a pinned staging buffer
-// (one CPU copy, one DMA), the counts, keypoints and descriptors come back as ONE copy of the output block into pinned memory next to the
-// error word, and a single stream synchronisation ends the call (the batch form issues four device-to-host copies into pageable memory).
-static int extract_one_host(msl_orb *h, const uint8_t *gray, int width, int height, size_t stride, msl_keypoint *kps, uint8_t *desc32, int cap, int *n_out) {
-    MSL_HIP_TRY(hipSetDevice(h->device));
-    int rc = build_geometry(h, width, height);
-    if (rc != MSL_OK) return rc;
-    const int outCap = h->outCap;
-    if (cap < outCap) { set_error("msl_orb_extract: cap %d < required %d", cap, outCap); return MSL_ERR_CAPACITY; }
-    const size_t inBytes = h->inPitch * (size_t)height;
-    // frame 0's share of the output block: counts (all B of them: a few bytes), its keypoints and -- B == 1 only -- its descriptors contiguous
-    const size_t outBytes = h->maxBatch == 1 ? h->geo.outBlock.cap : 0;
-    hipStream_t s = h->stream;
-    MSL_HIP_TRY(h->h_pinIn.grow(inBytes, s));
-    MSL_HIP_TRY(h->h_pinOut.grow(h->outKpsOff + sizeof(msl_keypoint) * (size_t)outCap + (size_t)32 * outCap + 256, s));
-    uint8_t *pinIn = (uint8_t *)h->h_pinIn.p, *pinOut = (uint8_t *)h->h_pinOut.p, *d_in = (uint8_t *)h->geo.in.p;
-    h->prof.begin(KID_COPY, s);
-    // (one copy: splitting it so that the DMA of the first half overlaps the CPU copy of the second measured 6 us SLOWER -- an enqueue costs more than it hides)
-    if (stride == h->inPitch) memcpy(pinIn, gray, stride * (size_t)(height - 1) + width);
-    else for (int y = 0; y < height; y++) memcpy(pinIn + (size_t)y * h->inPitch, gray + (size_t)y * stride, (size_t)width);
-    MSL_HIP_TRY(hipMemcpyAsync(d_in, pinIn, inBytes, hipMemcpyHostToDevice, s));
-    h->prof.end(s);
-    rc = launch_pipeline(h, d_in, h->inPitch, inBytes, 1, h->d_kps, h->d_desc, h->d_nout);
-    if (rc != MSL_OK) return rc;
-    const size_t kpsBytes = sizeof(msl_keypoint) * (size_t)outCap, descBytes = (size_t)32 * outCap;
-    uint8_t *hk = pinOut + h->outKpsOff, *hd = hk + ((kpsBytes + 255) & ~(size_t)255);
-    if (outBytes) {   // a one-frame handle: counts | keypoints | descriptors are one contiguous block
-        MSL_HIP_TRY(hipMemcpyAsync(pinOut, h->geo.outBlock.p, outBytes, hipMemcpyDeviceToHost, s));
-        hd = pinOut + h->outDescOff;
-    } else {
-        MSL_HIP_TRY(hipMemcpyAsync(pinOut, h->d_nout, sizeof(int), hipMemcpyDeviceToHost, s));
-        MSL_HIP_TRY(hipMemcpyAsync(hk, h->d_kps, kpsBytes, hipMemcpyDeviceToHost, s));
-        MSL_HIP_TRY(hipMemcpyAsync(hd, h->d_desc, descBytes, hipMemcpyDeviceToHost, s));
-    }
-    rc = check_device_error(h);   // error word into pinned memory, then the call's only synchronisation
-    if (rc != MSL_OK) { *n_out = 0; return rc; }
-    const int n = *reinterpret_cast<const int *>(pinOut);
-    memcpy(kps, hk, sizeof(msl_keypoint) * (size_t)n);
-    memcpy(desc32, hd, (size_t)32 * n);
-    *n_out = n;
-    return MSL_OK;
-}
-
-int msl_orb_extract(msl_orb *h, const uint8_t *gray, int width, int height, size_t stride, msl_keypoint *kps,
-                    uint8_t *desc32, int cap, int *n_out) noexcept {
-    try {
-    if (!n_out) { set_error("msl_orb_extract: n_out is NULL"); return MSL_ERR_INVALID; }
-    if (h && gray && width > 0 && height > 0 && width <= h->maxW && height <= h->maxH && stride >= (size_t)width && kps && desc32)
-        return extract_one_host(h, gray, width, height, stride, kps, desc32, cap, n_out);
-    int32_t n = 0;
-    const int rc = msl_orb_extract_batch(h, gray, 1, width, height, stride, stride * (size_t)height, MSL_MEM_HOST, kps, desc32,
-                                         cap, &n, MSL_MEM_HOST);
-    *n_out = n;
-    return rc;
-    } MSL_ABI_CATCH_INT
-}
-
-// host twin of the device undistortion (same expression order), used by ComputeImageBounds only
-static void undistort_point_host(const msl_frame_params &p, float xin, float yin, float *xo, float *yo) {
-    const double fx = p.fx, fy = p.fy, cx = p.cx, cy = p.cy, ifx = 1. / fx, ify = 1. / fy;
-    const double k0 = p.k1, k1 = p.k2, k2 = p.p1, k3 = p.p2, k4 = p.k3, kz = 0.0;
-    double x = xin, y = yin;
-    x = (x - cx) * ifx;
-    y = (y - cy) * ify;
-    const double x0 = x, y0 = y;
-    for (int j = 0; j < 5; j++) {
-        const double r2 = x * x + y * y;
-        const double icdist = (1 + ((kz * r2 + kz) * r2 + kz) * r2) / (1 + ((k4 * r2 + k1) * r2 + k0) * r2);
-        const double deltaX = 2 * k2 * x * y + k3 * (r2 + 2 * x * x) + kz * r2 + kz * r2 * r2;
-        const double deltaY = k2 * (r2 + 2 * y * y) + 2 * k3 * x * y + kz * r2 + kz * r2 * r2;
-        x = (x0 - deltaX) * icdist;
-        y = (y0 - deltaY) * icdist;
-    }
-    const double xx = fx * x + 0.0 * y + cx, yy = 0.0 * x + fy * y + cy, ww = 1. / (0.0 * x + 0.0 * y + 1.0);
-    *xo = (float)(xx * ww);
-    *yo = (float)(yy * ww);
-}
-
-int msl_frame_image_bounds(msl_frame_params *p, int width, int height) noexcept {
-    try {   // ComputeImageBounds, src/Frame.cc:465-494
-    if (!p || width < 1 || height < 1 || p->fx == 0 || p->fy == 0) { set_error("msl_frame_image_bounds: invalid argument"); return MSL_ERR_INVALID; }
-    if (p->k1 != 0.0) {
-        const float c[4][2] = {{0.f, 0.f}, {(float)width, 0.f}, {0.f, (float)height}, {(float)width, (float)height}};
-        float u[4][2];
-        for (int i = 0; i < 4; i++) undistort_point_host(*p, c[i][0], c[i][1], &u[i][0], &u[i][1]);
-        p->minX = std::min(u[0][0], u[2][0]); p->maxX = std::max(u[1][0], u[3][0]);
-        p->minY = std::min(u[0][1], u[1][1]); p->maxY = std::max(u[2][1], u[3][1]);
-    } else {
-        p->minX = 0.0f; p->maxX = (float)width; p->minY = 0.0f; p->maxY = (float)height;
-    }
-    return MSL_OK;
-    } MSL_ABI_CATCH_INT
-}
-
-int msl_orb_extract_frame_batch(msl_orb *h, const uint8_t *gray, const float *depth, int n_frames, int width, int height,
-                                size_t gray_row_stride, size_t gray_frame_stride, size_t depth_row_stride, size_t depth_frame_stride,
-                                msl_mem in_mem, const msl_frame_params *params, msl_keypoint *kps, uint8_t *desc32, float *kps_un_xy,
-                                float *depth_out, float *uright_out, int32_t *grid_cell, int cap, int32_t *n_out, msl_mem out_mem) noexcept {
-    try {
-    if (!h || !gray || !depth || !params || !kps || !desc32 || !kps_un_xy || !depth_out || !uright_out || !grid_cell || !n_out ||
-        n_frames < 1 || n_frames > h->maxBatch || width < 1 || height < 1 || width > h->maxW || height > h->maxH ||
-        gray_row_stride < (size_t)width || depth_row_stride < (size_t)width * 4 || (depth_row_stride & 3) ||
-        !(params->maxX > params->minX) || !(params->maxY > params->minY) || params->fx == 0 || params->fy == 0) {
-        set_error("msl_orb_extract_frame_batch: invalid argument (call msl_frame_image_bounds first?)");
-        return MSL_ERR_INVALID;
-    }
-    const int outCap = h->outCap;
-    if (cap < outCap) { set_error("msl_orb_extract_frame_batch: cap %d < required %d", cap, outCap); return MSL_ERR_CAPACITY; }
-    MSL_HIP_TRY(hipSetDevice(h->device));
-    int rc = build_geometry(h, width, height);
-    if (rc != MSL_OK) return rc;
-    const size_t B = (size_t)h->maxBatch;
-    MSL_HIP_TRY(grow_all(h->stream, {{h->d_unXY, sizeof(float) * 2 * outCap * B}, {h->d_depthOut, sizeof(float) * outCap * B},   // (sized once: outCap and B are fixed)
-                                     {h->d_uRight, sizeof(float) * outCap * B}, {h->d_gridCell, sizeof(int) * outCap * B}}));
-    const uint8_t *d_gray = gray; size_t rs = gray_row_stride, fs = gray_frame_stride;
-    FrameEpilogue ep{};
-    ep.fp = *params; ep.depth = depth; ep.depthRowStride = depth_row_stride; ep.depthFrameStride = depth_frame_stride;
-    if (in_mem == MSL_MEM_HOST) {
-        const size_t dpitch = (size_t)width * 4, dframe = dpitch * height;
-        MSL_HIP_TRY(h->d_depthIn.grow(dframe * B, h->stream));
-        uint8_t *d_in = (uint8_t *)h->geo.in.p, *d_depthIn = (uint8_t *)h->d_depthIn.p;
-        for (int f = 0; f < n_frames; f++) {
-            MSL_HIP_TRY(hipMemcpy2DAsync(d_in + (size_t)f * h->inPitch * height, h->inPitch, gray + (size_t)f * gray_frame_stride, gray_row_stride,
-                                         width, height, hipMemcpyHostToDevice, h->stream));
-            MSL_HIP_TRY(hipMemcpy2DAsync(d_depthIn + (size_t)f * dframe, dpitch, (const uint8_t *)depth + (size_t)f * depth_frame_stride,
-                                         depth_row_stride, dpitch, height, hipMemcpyHostToDevice, h->stream));
-        }
-        d_gray = d_in; rs = h->inPitch; fs = h->inPitch * height;
-        ep.depth = (const float *)d_depthIn; ep.depthRowStride = dpitch; ep.depthFrameStride = dframe;
-    }
-    const bool direct = out_mem == MSL_MEM_DEVICE && cap == outCap;
-    ep.unXY = direct ? kps_un_xy : (float *)h->d_unXY.p; ep.depthOut = direct ? depth_out : (float *)h->d_depthOut.p;
-    ep.uRight = direct ? uright_out : (float *)h->d_uRight.p; ep.gridCell = direct ? grid_cell : (int *)h->d_gridCell.p;
-    if (direct) return launch_pipeline(h, d_gray, rs, fs, n_frames, kps, desc32, n_out, &ep);
-    rc = launch_pipeline(h, d_gray, rs, fs, n_frames, h->d_kps, h->d_desc, h->d_nout, &ep);
-    if (rc != MSL_OK) return rc;
-    const hipMemcpyKind kind = out_mem == MSL_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    MSL_HIP_TRY(hipMemcpyAsync(n_out, h->d_nout, sizeof(int) * n_frames, kind, h->stream));
-    MSL_HIP_TRY(hipMemcpy2DAsync(kps, sizeof(msl_keypoint) * cap, h->d_kps, sizeof(msl_keypoint) * outCap, sizeof(msl_keypoint) * outCap, n_frames, kind, h->stream));
-    MSL_HIP_TRY(hipMemcpy2DAsync(desc32, (size_t)32 * cap, h->d_desc, (size_t)32 * outCap, (size_t)32 * outCap, n_frames, kind, h->stream));
-    MSL_HIP_TRY(hipMemcpy2DAsync(kps_un_xy, sizeof(float) * 2 * cap, h->d_unXY.p, sizeof(float) * 2 * outCap, sizeof(float) * 2 * outCap, n_frames, kind, h->stream));
-    MSL_HIP_TRY(hipMemcpy2DAsync(depth_out, sizeof(float) * cap, h->d_depthOut.p, sizeof(float) * outCap, sizeof(float) * outCap, n_frames, kind, h->stream));
-    MSL_HIP_TRY(hipMemcpy2DAsync(uright_out, sizeof(float) * cap, h->d_uRight.p, sizeof(float) * outCap, sizeof(float) * outCap, n_frames, kind, h->stream));
-    MSL_HIP_TRY(hipMemcpy2DAsync(grid_cell, sizeof(int) * cap, h->d_gridCell.p, sizeof(int) * outCap, sizeof(int) * outCap, n_frames, kind, h->stream));
-    if (out_mem == MSL_MEM_HOST) return check_device_error(h);
-    return MSL_OK;
-    } MSL_ABI_CATCH_INT
-}
-
-int msl_orb_debug_stamps(msl_orb *h, uint64_t *out, int n) noexcept {
-    try {
-    if (!h || !out || n < 0 || n > 200) return MSL_ERR_INVALID;
-    MSL_HIP_TRY(hipSetDevice(h->device));
-    MSL_HIP_TRY(hipStreamSynchronize(h->stream));
-    MSL_HIP_TRY(hipMemcpy(out, (const uint8_t *)h->d_err.p + 128, sizeof(uint64_t) * n, hipMemcpyDeviceToHost));
-    return MSL_OK;
-    } MSL_ABI_CATCH_INT
-}
-
-int msl_orb_debug_level_size(const msl_orb *h, int level, int *w, int *h_out) noexcept {
-    try {
-    if (!h || level < 0 || level >= h->nlevels) return MSL_ERR_INVALID;
-    *w = h->dev.lv[level].w; *h_out = h->dev.lv[level].h;
-    return MSL_OK;
-    } MSL_ABI_CATCH_INT
-}
-
-int msl_orb_debug_level(msl_orb *h, int frame, int level, int blurred, uint8_t *out) noexcept {
-    try {
-    if (!h || level < 0 || level >= h->nlevels || frame < 0 || frame >= h->lastFrames) return MSL_ERR_INVALID;
-    if (level == 0 && !blurred) { set_error("level 0 is the caller's image"); return MSL_ERR_INVALID; }
-    MSL_HIP_TRY(hipSetDevice(h->device));
-    MSL_HIP_TRY(hipStreamSynchronize(h->stream));
-    const LevelDev &G = h->dev.lv[level];
-    const uint8_t *src = blurred ? h->dev.blur + (size_t)frame * h->dev.blurStride + G.boff
-                                 : h->dev.pyr + (size_t)frame * h->dev.pyrStride + G.off;
-    MSL_HIP_TRY(hipMemcpy2D(out, G.w, src, G.pitch, G.w, G.h, hipMemcpyDeviceToHost));
-    return MSL_OK;
-    } MSL_ABI_CATCH_INT
-}
-
-int msl_orb_debug_candidates(msl_orb *h, int frame, int level, int32_t *xys, int cap, int *n_out) noexcept {
-    try {
-    if (!h || level < 0 || level >= h->nlevels || frame < 0 || frame >= h->lastFrames) return MSL_ERR_INVALID;
-    MSL_HIP_TRY(hipSetDevice(h->device));
-    MSL_HIP_TRY(hipStreamSynchronize(h->stream));
-    int n = 0;
-    MSL_HIP_TRY(hipMemcpy(&n, h->dev.ncand + frame * h->nlevels + level, sizeof(int), hipMemcpyDeviceToHost));
-    *n_out = n;
-    if (n > cap) return MSL_ERR_CAPACITY;
-    std::vector<uint32_t> k(n);
-    if (n) MSL_HIP_TRY(hipMemcpy(k.data(), h->dev.keys + (size_t)frame * h->dev.keysPerFrame + h->dev.lv[level].keyBase,
-                                 sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
-    for (int i = 0; i < n; i++) {
-        xys[3 * i] = (int)(k[i] & 0xFFF) + 16; xys[3 * i + 1] = (int)((k[i] >> 12) & 0xFFF) + 16; xys[3 * i + 2] = (int)(k[i] >> 24);
-    }
-    return MSL_OK;
-    } MSL_ABI_CATCH_INT
-}
-
-int msl_orb_profile_enable(msl_orb *h, int on) noexcept {
-    try {
-    if (!h) return MSL_ERR_INVALID;
-    MSL_HIP_TRY(hipSetDevice(h->device));
-    MSL_HIP_TRY(hipStreamSynchronize(h->stream));
-    h->prof.drain();
-    h->prof.set_mode(on);
-    return MSL_OK;
-    } MSL_ABI_CATCH_INT
-}
-int msl_orb_profile_read(msl_orb *h, float *ms, int32_t *launches) noexcept {
-    try {
-    if (!h) return MSL_ERR_INVALID;
-    MSL_HIP_TRY(hipSetDevice(h->device));
-    MSL_HIP_TRY(hipStreamSynchronize(h->stream));
-    h->prof.drain();
-    for (int i = 0; i < MSL_ORB_NKERNELS; i++) { if (ms) ms[i] = h->prof.ms[i]; if (launches) launches[i] = h->prof.launches[i]; }
-    return MSL_OK;
-    } MSL_ABI_CATCH_INT
-}
-const char *msl_orb_kernel_name(int k) noexcept { try { return (k >= 0 && k < MSL_ORB_NKERNELS) ? kKernelNames[k] : ""; } MSL_ABI_CATCH_PTR }
-
-}  // extern "C"

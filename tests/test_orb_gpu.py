@@ -175,6 +175,110 @@ def test_one_extractor_across_frame_sizes():
         fresh.close()
     ex.close()
 
+# The smallest geometry the extractor accepts with two levels: 96 x 80 at scale 1.2 makes level 1 80 x 67, both axes above the 62 px one 30-px FAST
+# cell needs; low thresholds so that both levels return keypoints.
+_SMALL = dict(w=96, h=80, args=(100, 1.2, 2, 7, 5))
+
+
+def _small_frames(n=3):
+    from manhattanslam_amd import synth
+    full = synth.orb_frame(4100)          # (the generator needs room for its rectangles: cut the small frames out of one 640 x 480 frame)
+    imgs = np.stack([full[60 + 90 * i:60 + 90 * i + _SMALL["h"], 100 + 150 * i:100 + 150 * i + _SMALL["w"]] for i in range(n)])
+    rng = np.random.default_rng(41)
+    depths = rng.uniform(0.5, 4.0, imgs.shape).astype(np.float32)
+    depths[rng.random(imgs.shape) < 0.2] = 0.0          # pixels without depth
+    return imgs, depths
+
+
+def test_copy_out_paths_are_the_direct_path():
+    """Host or device frames in (padded or tightly packed), host or device arrays out, rows of the handle's capacity or longer ones: every way
+    through msl_orb_extract_batch and msl_orb_extract_frame_batch gives the bytes of the direct device path and of the single-frame call, and
+    the slots of a longer row beyond the capacity are not written."""
+    import torch
+    from manhattanslam_amd import ORBextractor, frame_params, synth
+    from manhattanslam_amd._lib import MSL_MEM_DEVICE, MSL_MEM_HOST, check, lib, ptr
+    W, H, B = _SMALL["w"], _SMALL["h"], 3
+    imgs, depths = _small_frames(B)
+    I = synth.TUM1
+    params = frame_params(I["fx"] * W / 640, I["fy"] * H / 480, I["cx"] * W / 640, I["cy"] * H / 480, 40.0, W, H)
+    ex = ORBextractor(*_SMALL["args"], max_width=W, max_height=H, max_batch=B)
+    C = ex.capacity
+    single = [ex(imgs[f]) for f in range(B)]
+    assert all(len(k) > 0 for k, _ in single) and all(set(k["octave"]) == {0, 1} for k, _ in single)
+    # padded host input: rows of W + 13 bytes, frames 2 rows further apart than they are long
+    rs, fs = W + 13, (W + 13) * (H + 2)
+    padded = np.full(B * fs, 0xCD, np.uint8)
+    dpad = np.full(B * fs, -7.0, np.float32)
+    for f in range(B):
+        padded[f * fs:f * fs + rs * H].reshape(H, rs)[:, :W] = imgs[f]
+        dpad[f * fs:f * fs + rs * H].reshape(H, rs)[:, :W] = depths[f]
+    elem = (("kps", 28), ("desc", 32), ("un", 8), ("dep", 4), ("ur", 4), ("cell", 4))
+    FILL = 0xA5
+
+    def run(frame, dev, cap, pad):
+        names = elem if frame else elem[:2]
+        mem = MSL_MEM_DEVICE if dev else MSL_MEM_HOST
+        if dev:
+            out = {k: torch.full((B, cap * b), FILL, dtype=torch.uint8, device="cuda") for k, b in names}
+            n = torch.full((B,), -1, dtype=torch.int32, device="cuda")
+            g, d = torch.from_numpy(imgs).cuda(), torch.from_numpy(depths).cuda()
+            torch.cuda.synchronize()          # the prefill runs on torch's stream, the extractor on its own
+        else:
+            out = {k: np.full((B, cap * b), FILL, np.uint8) for k, b in names}
+            n = np.full(B, -1, np.int32)
+            g, d = (padded, dpad) if pad else (imgs, depths)
+        grs, gfs = (rs, fs) if pad else (W, W * H)
+        if frame:
+            check(lib.msl_orb_extract_frame_batch(ex._h, ptr(g), ptr(d), B, W, H, grs, gfs, 4 * grs, 4 * gfs, mem, ptr(params), ptr(out["kps"]), ptr(out["desc"]),
+                                                  ptr(out["un"]), ptr(out["dep"]), ptr(out["ur"]), ptr(out["cell"]), cap, ptr(n), mem), "msl_orb_extract_frame_batch")
+        else:
+            check(lib.msl_orb_extract_batch(ex._h, ptr(g), B, W, H, grs, gfs, mem, ptr(out["kps"]), ptr(out["desc"]), cap, ptr(n), mem), "msl_orb_extract_batch")
+        ex.sync()
+        if dev:
+            out = {k: v.cpu().numpy() for k, v in out.items()}
+            n = n.cpu().numpy()
+        return n, out
+
+    for frame in (False, True):
+        cases = {"a": run(frame, False, C + 7, True), "b": run(frame, False, C, False), "c": run(frame, True, C, False), "d": run(frame, True, C + 7, False)}
+        n0, direct = cases["c"]
+        assert (n0 > 0).all()
+        for f in range(B):
+            ks, ds = single[f]
+            assert n0[f] == len(ks) and direct["kps"][f, :28 * n0[f]].tobytes() == ks.tobytes() and direct["desc"][f, :32 * n0[f]].tobytes() == ds.tobytes()
+        for name, (n, out) in cases.items():
+            cap = C + 7 if name in "ad" else C
+            assert n.tobytes() == n0.tobytes(), (frame, name)
+            for k, b in (elem if frame else elem[:2]):
+                for f in range(B):
+                    assert out[k][f, :b * n[f]].tobytes() == direct[k][f, :b * n[f]].tobytes(), (frame, name, k, f)
+                assert (out[k][:, b * C:b * cap] == FILL).all(), (frame, name, k)          # beyond the capacity: the caller's prefill
+    ex.close()
+
+
+def test_rejected_size_leaves_the_handle_intact():
+    """A frame size the geometry plan rejects (70 x 64: level 1 is 58 x 53, too small for one 30-px FAST cell) costs the handle nothing: the
+    geometry it had, its level sizes and its results stay."""
+    import ctypes as C
+    from manhattanslam_amd import ORBextractor, KEYPOINT_DTYPE
+    from manhattanslam_amd._lib import lib, ptr
+    W, H = _SMALL["w"], _SMALL["h"]
+    img = _small_frames(1)[0][0]
+    ex = ORBextractor(*_SMALL["args"], max_width=W, max_height=H, max_batch=3)
+    sizes = [ex.level_size(l) for l in range(2)]
+    assert sizes == [(96, 80), (80, 67)]
+    k0, d0 = ex(img)
+    assert len(k0) > 0
+    small = np.ascontiguousarray(img[:64, :70])
+    kps = np.zeros(ex.capacity, KEYPOINT_DTYPE); desc = np.zeros((ex.capacity, 32), np.uint8); n = C.c_int(-1)
+    rc = lib.msl_orb_extract(ex._h, ptr(small), 70, 64, 70, ptr(kps), ptr(desc), ex.capacity, C.byref(n))
+    assert rc == -1 and "level 1 (58x53) is too small for the 30-px FAST grid" in lib.msl_last_error().decode()          # MSL_ERR_INVALID
+    assert [ex.level_size(l) for l in range(2)] == sizes
+    k1, d1 = ex(img)
+    assert k1.tobytes() == k0.tobytes() and d1.tobytes() == d0.tobytes()
+    ex.close()
+
+
 def test_device_resident_batch(oracle):
     """Asynchronous batch path with inputs and outputs resident in HBM (the bench.py path)."""
     import torch

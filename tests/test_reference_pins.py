@@ -38,7 +38,8 @@ def test_orb_constants(pins):
     o = pins["orb"]
     assert (o["PATCH_SIZE"], o["HALF_PATCH_SIZE"], o["EDGE_THRESHOLD"]) == (31, 15, 19)
     assert o["W"] == 30                                            # FAST cell size, src/ORBextractor.cc:726
-    hip = open(os.path.join(ROOT, "manhattanslam_amd", "csrc", "msl_orb.hip")).read()
+    csrc = os.path.join(ROOT, "manhattanslam_amd", "csrc")
+    hip = "".join(open(os.path.join(csrc, f)).read() for f in ("msl_orb_dev.h", "msl_orb.hip", "msl_orb_host.hip"))
     assert "const float Wc = 30;" in hip and "(int)(31 * h->scale[l])" in hip
     hdr = open(os.path.join(ROOT, "include", "msl.h")).read()
     assert int(o["FRAME_GRID_ROWS"]) == int(_const(hdr, "MSL_FRAME_GRID_ROWS")) == 48
