@@ -609,6 +609,9 @@ MSL_API int msl_pose_optimize_translation_batch(int device, int n_frames, int ca
  * the walk over the map planes with its tightening thresholds -- bad planes skipped, `angle > a_th && dis < ldTh` matches and continues,
  * a plane failing only the distance test falls through to the vertical (|angle| < lverTh) and then the parallel (|angle| > lparTh) test;
  * strict comparisons, so the first of equal candidates wins.  Two launches (distances, then the walk).
+ * Counts: n_planes[f] is clamped to [0, pcap] and n_map[f] to [0, mcap]; entries beyond the clamped counts and points outside every
+ * clamped offset range are never read, and no kernel writes rows k >= n_planes[f] of plane_match, plane_w, plane_has and pM_out:
+ * device-memory arrays keep their bytes there (host-memory outputs other than plane_match are copied back whole: unspecified there).
  * Limits: pcap <= 64, mcap <= 4096, ptcap <= 2^22; larger values are refused with MSL_ERR_INVALID before any launch.  Asynchronous on the
  * matcher handle's stream when inputs and outputs are device memory; with host memory on either side it returns when the caller's buffers
  * are its own again. */
@@ -652,6 +655,8 @@ MSL_API int msl_plane_associate_batch(int device, int n_frames, int pcap, int mc
  * float products with double accumulation, Rcw = Rwc^T.  The polar factor U * Vt is not OpenCV's float Jacobi SVD: it is computed in
  * double by Newton's iteration X <- (X + X^-T) / 2 and rounded to float, so Rcw agrees with the reference within about 2e-6 per entry;
  * every integer output is exact.  One launch (one workgroup per frame).
+ * Counts: n_planes[f], n_map[f], n_full[f] and n_part[f] are clamped to [0, pcap], [0, mcap], [0, fcap] and [0, qcap]; entries beyond
+ * the clamped counts are never read (host-memory tables are sort-checked over the clamped counts).
  * Limits: pcap <= 64, mcap <= 4096, fcap <= 65536, qcap <= 65536, kcap <= 4096; larger values are refused with MSL_ERR_INVALID before any
  * launch.  Asynchronous on the matcher handle's stream when inputs and outputs are device memory; with host memory on either side it
  * returns when the caller's buffers are its own again. */

@@ -8,7 +8,10 @@ here: the device computes the same polar factor U * Vt in double, so Rcw is comp
 kernel (double accumulation, one rounding per element).  A frame is a dict of manhattanslam_amd.plane; only slot 0 of plane_match is read.
 
 first_maximum is an independent formulation of the choice (every candidate scored, then the first one with the largest score > 0) used
-only to cross-check the literal loop."""
+only to cross-check the literal loop.  candidates_fast is the same loop with the table scan replaced by a dictionary built once per frame
+and the dot products taken from one float Gram matrix (the same left-to-right expression): tests/test_plane_model.py asserts it equal to
+the literal one; it exists because _lookup's scan is unusable on a 65536-row table.  polar64 is the polar factor by a float64 SVD, the
+tight reference of the device's double Newton iteration."""
 import numpy as np
 
 F32 = np.float32
@@ -31,6 +34,20 @@ def _index_in_kf(e, w, m):
     return -1
 
 
+def _kf_counts(fr, kf, idx, caps):
+    """The keyframe point counts of an entry's planes, or None when the entry is no candidate: an index -1 (:713 / :752), and -- as
+    include/msl.h defines the flattened tables -- an index outside [0, pcap) or a keyframe slot outside [0, kcap).  caps = (pcap, kcap);
+    by default the frame's own extents (its keyframes, and the planes keyframe kf records).  Counts beyond a keyframe's planes are 0."""
+    kcap = len(fr["kf_Rwc"]) if caps is None else caps[1]
+    if kf < 0 or kf >= kcap:
+        return None
+    kn = fr["kf_npts"][kf] if kf < len(fr["kf_npts"]) else ()
+    pcap = len(kn) if caps is None else caps[0]
+    if any(q < 0 or q >= pcap for q in idx):
+        return None
+    return [int(kn[q]) if q < len(kn) else 0 for q in idx]
+
+
 def _held(fr, i):
     m = int(np.asarray(fr["plane_match"]).reshape(-1, 3)[i, 0])
     if m < 0 or m >= len(fr["mp_w"]) or not (fr["mp_flags"][m] & 1):
@@ -42,8 +59,8 @@ def _dot(a, b):
     return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]
 
 
-def candidates(fr, mf_ver_th):
-    """Every candidate of the loop in order: (i, j, k or -1, entry, score, kf) with score > 0 or not."""
+def candidates(fr, mf_ver_th, caps=None):
+    """Every candidate of the loop in order: (i, j, k or -1, entry, score, kf, idx) with score > 0 or not."""
     th = F32(mf_ver_th)
     coef = np.asarray(fr["plane_coef"], F32).reshape(-1, 4)
     npts = np.asarray(fr["plane_npts"])
@@ -73,28 +90,82 @@ def candidates(fr, mf_ver_th):
                     continue
                 kf = int(e[3])
                 idx = [_index_in_kf(e, 3, m) for m in (m1, m2, m3)]
-                if -1 in idx:                                               # :712-714
+                kn = _kf_counts(fr, kf, idx, caps)                          # :712-714
+                if kn is None:
                     continue
-                kn = fr["kf_npts"][kf]
-                score = int(kn[idx[0]]) + int(kn[idx[1]]) + int(kn[idx[2]]) + int(npts[i]) + int(npts[j]) + int(npts[k])
+                score = kn[0] + kn[1] + kn[2] + int(npts[i]) + int(npts[j]) + int(npts[k])
                 out.append((i, j, k, e, score, kf, idx))
             e = _lookup(fr["part"], 2, (m1, m2))                            # :741
             if e is None:
                 continue
             kf = int(e[2])
             idx = [_index_in_kf(e, 2, m) for m in (m1, m2)]
-            if -1 in idx:                                                   # :750-752
+            kn = _kf_counts(fr, kf, idx, caps)                              # :750-752
+            if kn is None:
                 continue
-            kn = fr["kf_npts"][kf]
-            score = int(kn[idx[0]]) + int(kn[idx[1]]) + int(npts[i]) + int(npts[j])
+            score = kn[0] + kn[1] + int(npts[i]) + int(npts[j])
             out.append((i, j, -1, e, score, kf, idx))
     return out
 
 
-def detect_manhattan(fr, mf_ver_th, rcw_in=None):
-    """(found, full, Rcw (9,) f32, choice (i, j, k, entry-as-array, score, kf) or None).  Rcw is rcw_in (default zeros) when not found."""
+def _table_dict(table, w):
+    """Sorted key tuple -> the first entry holding that key set (what _lookup's scan returns)."""
+    d = {}
+    for e in np.asarray(table, np.int32).reshape(-1, w + 1 + w):
+        d.setdefault(tuple(sorted(e[:w].tolist())), e)
+    return d
+
+
+def candidates_fast(fr, mf_ver_th, caps=None):
+    """candidates() with a dictionary lookup, the held planes and the dot products computed once."""
+    th = F32(mf_ver_th)
+    coef = np.asarray(fr["plane_coef"], F32).reshape(-1, 4)
+    npts = [int(x) for x in np.asarray(fr["plane_npts"])]
+    n = len(coef)
+    held = [_held(fr, i) for i in range(n)]
+    a, b = coef[:, None, :], coef[None, :, :]
+    G = (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
+    ok = ~((G > th) | (G < -th))                                            # the literal gate: NaN passes
+    full, part = _table_dict(fr["full"], 3), _table_dict(fr["part"], 2)
+    out = []
+    for i in range(n):
+        m1 = held[i]
+        if m1 is None:
+            continue
+        for j in range(i + 1, n):
+            m2 = held[j]
+            if m2 is None or not ok[i, j]:
+                continue
+            for k in range(j + 1, n):
+                m3 = held[k]
+                if m3 is None or not ok[i, k] or not ok[j, k]:
+                    continue
+                e = full.get(tuple(sorted((m1, m2, m3))))
+                if e is None:
+                    continue
+                kf = int(e[3])
+                idx = [_index_in_kf(e, 3, m) for m in (m1, m2, m3)]
+                kn = _kf_counts(fr, kf, idx, caps)
+                if kn is None:
+                    continue
+                out.append((i, j, k, e, kn[0] + kn[1] + kn[2] + npts[i] + npts[j] + npts[k], kf, idx))
+            e = part.get(tuple(sorted((m1, m2))))
+            if e is None:
+                continue
+            kf = int(e[2])
+            idx = [_index_in_kf(e, 2, m) for m in (m1, m2)]
+            kn = _kf_counts(fr, kf, idx, caps)
+            if kn is None:
+                continue
+            out.append((i, j, -1, e, kn[0] + kn[1] + npts[i] + npts[j], kf, idx))
+    return out
+
+
+def detect_manhattan(fr, mf_ver_th, rcw_in=None, caps=None, fast=False, polar_fn=None):
+    """(found, full, Rcw (9,) f32, choice (i, j, k, entry-as-array, score, kf, idx) or None).  Rcw is rcw_in (default zeros) when not
+    found.  fast: candidates_fast in place of candidates; polar_fn: polar (default) or polar64."""
     best, maxScore, full = None, 0, False
-    for cand in candidates(fr, mf_ver_th):                                  # the literal "score > maxScore" of :718 / :758
+    for cand in (candidates_fast if fast else candidates)(fr, mf_ver_th, caps):                                  # the literal "score > maxScore" of :718 / :758
         if cand[4] > maxScore:
             maxScore = cand[4]
             best = cand
@@ -102,12 +173,12 @@ def detect_manhattan(fr, mf_ver_th, rcw_in=None):
     R0 = np.zeros(9, F32) if rcw_in is None else np.array(rcw_in, F32).reshape(9)
     if best is None:                                                        # :778-780
         return 0, 0, R0, None
-    return 1, int(full), rotation(fr, best), best
+    return 1, int(full), rotation(fr, best, polar_fn or polar), best
 
 
-def first_maximum(fr, mf_ver_th):
+def first_maximum(fr, mf_ver_th, caps=None, fast=False):
     """The choice as the first candidate in loop order that reaches the largest score, when that score is > 0."""
-    c = candidates(fr, mf_ver_th)
+    c = (candidates_fast if fast else candidates)(fr, mf_ver_th, caps)
     if not c or max(x[4] for x in c) <= 0:
         return None
     top = max(x[4] for x in c)
@@ -146,6 +217,12 @@ def polar(M):
     return gemm33(U.astype(F32), Vt.astype(F32))
 
 
+def polar64(M):
+    """The same polar factor from a float64 SVD of the same float matrix, U * Vt rounded to float once."""
+    U, _, Vt = np.linalg.svd(np.asarray(M, F32).astype(np.float64))
+    return (U @ Vt).astype(F32)
+
+
 def frames_of(fr, cand):
     """MFc, MFm (3x3 f32, columns = the plane normals) before the polar step, with the partial case's cross product and flip."""
     i, j, k, e, _, kf, idx = cand
@@ -167,10 +244,10 @@ def frames_of(fr, cand):
     return MFc, MFm
 
 
-def rotation(fr, cand):
+def rotation(fr, cand, polar_fn=polar):
     """manhattanRcw (9,) f32 of a chosen candidate (:772-840)."""
     MFc, MFm = frames_of(fr, cand)
-    MFc, MFm = polar(MFc), polar(MFm)                                       # :792-796, :814-818
+    MFc, MFm = polar_fn(MFc), polar_fn(MFm)                                       # :792-796, :814-818
     kR = np.asarray(fr["kf_Rwc"][cand[5]], F32).reshape(3, 3)
     Rwc = gemm33(gemm33(kR, MFm), MFc.T)                                    # :820
     return np.ascontiguousarray(Rwc.T).reshape(9)                           # :821

@@ -7,7 +7,9 @@ value is compared as double against a running double that starts at 100; ldTh / 
 manhattanslam_amd.plane (plane_coef, Tcw, plane_match, mp_w, mp_flags, mp_clouds).
 
 search_prefix_scan is an independent formulation of the same loop (the three running thresholds as exclusive prefix minima / maxima)
-used only to cross-check the literal one."""
+used only to cross-check the literal one.  search_fast is the literal walk fed with distances and angles computed for all frame planes
+at once in numpy float32 (the same left-to-right expressions): tests/test_plane_model.py asserts it equal to the literal one; it exists
+for the scenes with 4096 map planes or millions of cloud points."""
 import numpy as np
 
 F32 = np.float32
@@ -126,3 +128,61 @@ def search_prefix_scan(fr, prm):
                 match[i, s] = np.flatnonzero(sel)[-1]
         nmatches += int(hit.any())
     return nmatches, match, np.array(pMs, F32).reshape(-1, 4)
+
+
+def cloud_distances(pMs, cloud):
+    """point_distance_from_plane of every row of pMs (K,4) f32 against one cloud, vectorised: (K,) float64."""
+    c = np.asarray(cloud, F32).reshape(-1, 3)
+    out = np.full(len(pMs), 100.0)
+    if len(c) == 0:
+        return out
+    with np.errstate(invalid="ignore", over="ignore"):
+        for k0 in range(0, len(pMs), max(1, (1 << 22) // len(c))):           # blocks of frame planes, to bound the temporaries
+            p = pMs[k0:k0 + max(1, (1 << 22) // len(c))]
+            d = np.abs(((p[:, 0:1] * c[:, 0] + p[:, 1:2] * c[:, 1]) + p[:, 2:3] * c[:, 2]) + p[:, 3:4])
+            m = np.fmin.reduce(d, axis=1)                                    # NaN distances never replace the minimum
+            out[k0:k0 + len(p)] = np.where(m < 100.0, m, 100.0)
+    return out
+
+
+def search_fast(fr, prm):
+    """search_map_by_coefficients with the distances and angles precomputed; the walk itself is the literal one."""
+    match = np.array(fr["plane_match"], np.int32, copy=True).reshape(-1, 3)
+    K, M = len(fr["plane_coef"]), len(fr["mp_w"])
+    pMs = np.array([world_coef(fr["Tcw"], c) for c in fr["plane_coef"]], F32).reshape(-1, 4)
+    if K == 0 or M == 0:
+        return 0, match, pMs
+    W = np.asarray(fr["mp_w"], F32).reshape(M, 4)
+    good = [bool(x & 1) for x in np.asarray(fr["mp_flags"]).tolist()]
+    with np.errstate(invalid="ignore", over="ignore"):
+        ang = (pMs[:, None, 0] * W[None, :, 0] + pMs[:, None, 1] * W[None, :, 1]) + pMs[:, None, 2] * W[None, :, 2]
+    aTh = float(F32(prm["a_th"]))
+    dis = np.full((K, M), 100.0)
+    need = np.flatnonzero((ang > F32(prm["a_th"])).any(0) & np.array(good))
+    for j in need:
+        dis[:, j] = cloud_distances(pMs, fr["mp_clouds"][j])
+    ang, dis = ang.astype(np.float64).tolist(), dis.tolist()                  # floats widen exactly
+    nmatches = 0
+    for i in range(K):
+        ldTh, lverTh, lparTh = float(F32(prm["d_th"])), float(F32(prm["ver_th"])), float(F32(prm["par_th"]))
+        found = False
+        ai, di = ang[i], dis[i]
+        for j in range(M):
+            if not good[j]:
+                continue
+            angle = ai[j]
+            if angle > aTh:
+                if di[j] < ldTh:
+                    ldTh = di[j]
+                    match[i, 0] = j
+                    found = True
+                    continue
+            if angle < lverTh and angle > -lverTh:
+                lverTh = abs(angle)
+                match[i, 2] = j
+                continue
+            if angle > lparTh or angle < -lparTh:
+                lparTh = abs(angle)
+                match[i, 1] = j
+        nmatches += found
+    return nmatches, match, pMs
