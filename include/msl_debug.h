@@ -65,7 +65,7 @@ MSL_API int msl_debug_peac_cluster_on_device(int n_frames) MSL_NOEXCEPT;
 MSL_API long long msl_debug_peac_thread_shortfall(void) MSL_NOEXCEPT;
 MSL_API int msl_debug_peac_mse(const msl_peac_stats *stats, size_t n, int lanes, double *mse_out) MSL_NOEXCEPT;
 /* Test hook: the dealing of n_subblocks (a multiple of 8) k_fuse sub-blocks to the eight XCDs by screen key (0 .. 254: mean image row of the
- * sub-block's in-view surfels, >= 255: nothing in view), as k_compact / k_deal build it (msl_sf_map.hip, deal_subblocks): deal[x * n / 8 + j] = the
+ * sub-block's in-view surfels, >= 255: nothing in view), as k_compact / k_deal build it (msl_sf_compact.hip, deal_subblocks): deal[x * n / 8 + j] = the
  * sub-block wave 8 j + x takes.  Host arrays; synchronous. */
 MSL_API int msl_debug_deal(const uint32_t *keys_host, int n_subblocks, uint32_t *deal_host) MSL_NOEXCEPT;
 /* Test hook: out[i] = the kernels' division-free evaluation of (double)(x[i]*x[i]) / 100.0 (host arrays). */

@@ -1,7 +1,11 @@
-// msl_sf.h -- types and device helpers shared by the three translation units of the surfel-fusion path (internal):
+// msl_sf.h -- types and device helpers shared by the translation units of the surfel-fusion path (internal):
 //   msl_sf_superpixel.hip  frame-batched superpixel stage (generateSuperPixels, src/SurfelFusion.cpp:333-773)
-//   msl_sf_map.hip         map stage: fusion (:167-283), new surfels (:285-331), compaction (src/SurfelMapping.cpp:366-391)
+//   msl_sf_fuse.hip        map stage: fusion (:167-283)
+//   msl_sf_compact.hip     map stage: new surfels (:285-331), compaction (src/SurfelMapping.cpp:366-391), dealing of the sub-blocks
+//   msl_sf_replay.hip      map stage: the end of a deferred-compaction window
+//   msl_sf_map.hip         map maintenance: selection, AoS <-> SoA, counters
 //   msl_surfel.hip         handle, streams, batching, the C ABI
+// (what only the four map-stage units share, and the stage's overview: msl_sf_map_dev.h)
 #pragma once
 
 #include "msl_common.h"
@@ -146,11 +150,12 @@ struct SfDev {
     long long *ctr;
     msl_surfel *newSurfels;
     unsigned *blockSums, *blockUpd, *delList, *srcOf;
-    // Dealing of the sub-blocks to the XCDs by SCREEN position (round 6; msl_sf_map.hip, deal_subblocks): every k_fuse wave leaves the screen key of
+    // Dealing of the sub-blocks to the XCDs by SCREEN position (round 6; msl_sf_compact.hip, deal_subblocks): every k_fuse wave leaves the screen key of
     // its sub-block (mean image row of its in-view surfels, 0 .. 254; 255 = nothing in view) in sbKeys[]; the launch that follows k_fuse on the map
     // stream (k_compact's second workgroup; k_deal behind a deferred window) turns them into deal[]: wave w of the next k_fuse launch takes the
-    // sub-block deal[(w & 7) * (G / 8) + (w >> 3)], so that XCD x works on the sub-blocks that project into the x-th band of image rows and its L2
-    // fetches that band of the texel map and of the seed records instead of all of them.  Hints only: any permutation of 0 .. G - 1 is correct.
+    // sub-block deal[(w & 7) * (G / 8) + (w >> 3)], so that ONE XCD works on the sub-blocks that project into the (w & 7)-th band of image rows and
+    // its L2 fetches that band of the texel map and of the seed records instead of all of them: XCD w & 7 in a classic launch, XCD (w + 1) % 8 in a
+    // deferred one, whose workgroup 0 is the spawn wave (wave w = workgroup w + 1).  Hints only: any permutation of 0 .. G - 1 is correct.
     unsigned *sbKeys, *deal;     // [blkStride] each
     int dealG;                   // k_compact / k_deal: the grid (sub-blocks, a multiple of 8) to build deal[] for; 0 = leave it alone
     unsigned *tickets;           // [0..1] hand-off counters, [3] change-list length, [4] delUCount
@@ -283,7 +288,7 @@ enum { SK_SEED_INIT = 0, SK_ASSIGN, SK_PROP, SK_COMMIT_PX, SK_UPDATE_SEEDS, SK_C
     } while (0)
 #define MSL_SF_LAUNCH(prof, kid, st, kern, grid, block, ...) MSL_SF_LAUNCH_LDS(prof, kid, st, kern, grid, block, 0, __VA_ARGS__)
 
-// ---- host entry points of the two kernel translation units (all asynchronous on the given stream) ----
+// ---- host entry points of the kernel translation units (all asynchronous on the given stream) ----
 // msl_sf_superpixel.hip
 bool sp_init_attributes(int nseeds);   // true: one keyframe's t(s) fits the LDS (single-launch relaxation)
 void sp_launch_stage(KernelProfiler &prof, hipStream_t st, const SfDev &P, int nFrames, bool propLds);
@@ -291,11 +296,17 @@ void sp_launch_stage(KernelProfiler &prof, hipStream_t st, const SfDev &P, int n
 // packed rows of W floats, frames dstFrameStride floats apart
 void sp_launch_depth_u16(hipStream_t st, const void *src, size_t srcStride, size_t srcFrameStride, float *dst, size_t dstFrameStride, int W, int H, int nFrames,
                          float factor);
-// msl_sf_map.hip
-void map_launch_fuse(KernelProfiler &prof, hipStream_t st, const SfDev &P, int slot, const FrameDev &F, int nSubGrid, int nSubHint, bool deferred, bool dealt);
+int sp_debug_div100(const float *x_host, double *out_host, size_t n);
+int sp_debug_chain(const float *x_host, const int32_t *n_host, int lists, int huber, float *out_host);
+// msl_sf_fuse.hip (blkStride: entries per per-sub-block count slice, msl_sf::blkStride)
+void map_launch_fuse(KernelProfiler &prof, hipStream_t st, const SfDev &P, int slot, const FrameDev &F, int nSubGrid, int nSubHint, bool deferred, bool dealt, unsigned blkStride);
+// msl_sf_compact.hip
 void map_launch_compact(KernelProfiler &prof, hipStream_t st, const SfDev &P, int slot, bool resident);
-void map_launch_replay(KernelProfiler &prof, hipStream_t st, const SfDev &P, int nFrames, unsigned blkStride);   // closes a deferred window of nFrames keyframes
 void map_launch_deal(hipStream_t st, const SfDev &P);   // builds P.deal for a grid of P.dealG sub-blocks from the screen keys the last k_fuse launch left
+int map_debug_deal(const uint32_t *keys_host, int G, uint32_t *deal_host);
+// msl_sf_replay.hip
+void map_launch_replay(KernelProfiler &prof, hipStream_t st, const SfDev &P, int nFrames, unsigned blkStride);   // closes a deferred window of nFrames keyframes
+// msl_sf_map.hip
 void map_launch_empty_pair(KernelProfiler &prof, hipStream_t st);                   // the profiler's empty-kernel event pair (SK_NEW)
 void map_launch_set_ctr(hipStream_t st, const SfDev &P, long long n, int wide);
 void map_launch_add_ctr(hipStream_t st, const SfDev &P, long long add);
@@ -305,9 +316,6 @@ void map_launch_select_count(hipStream_t st, const SfDev &P, int mode, int arg);
 void map_launch_select_write(hipStream_t st, const SfDev &P, int mode, int arg, msl_surfel *out, int markDeleted);
 void map_launch_collect_changed(hipStream_t st, const SfDev &P, int ref, long long n, unsigned *count, unsigned *idxOut, msl_surfel *recOut, unsigned capOut);
 void map_launch_empty(hipStream_t st, int grid, hipEvent_t a, hipEvent_t b);
-int sp_debug_div100(const float *x_host, double *out_host, size_t n);
-int map_debug_deal(const uint32_t *keys_host, int G, uint32_t *deal_host);
-int sp_debug_chain(const float *x_host, const int32_t *n_host, int lists, int huber, float *out_host);
 
 }  // namespace sf
 }  // namespace msl

@@ -1,10 +1,11 @@
 // msl_surfel.hip -- surfel fusion for gfx950 (MI355X): the handle, streams and batching, and the C ABI.
 //
 // Replaces SurfelFusion (reference src/SurfelFusion.cpp) and the slot refill / tail compaction of
-// SurfelMapping::fuseMap (src/SurfelMapping.cpp:353-392).  The kernels live in two other translation units:
+// SurfelMapping::fuseMap (src/SurfelMapping.cpp:353-392).  The kernels live in other translation units:
 //   msl_sf_superpixel.hip   generateSuperPixels() of a keyframe depends only on that keyframe's images, never on the map, so it is
 //                           FRAME-BATCHED on the "pre" stream (kb_* kernels, one launch sequence per batch of F keyframes);
-//   msl_sf_map.hip          the map stage (fusion -> new surfels -> compaction) is sequential per keyframe, on the "map" stream:
+//   msl_sf_fuse.hip, msl_sf_compact.hip, msl_sf_replay.hip, msl_sf_map.hip (maintenance)
+//                           the map stage (fusion -> new surfels -> compaction) is sequential per keyframe, on the "map" stream:
 //                           k_fuse + k_compact per keyframe (classic), or ONE k_fuse launch per keyframe with the compactions of a
 //                           window of <= 32 keyframes replayed at its end (deferred); run_batch picks per batch: deferred for a handle on ONE
 //                           caller-provided stream under low churn, classic otherwise (a handle with its own two streams: always classic);
@@ -35,7 +36,7 @@ struct msl_sf {
     hipStream_t preStream = nullptr, mapStream = nullptr; bool ownStreams = true;
     size_t blkStride = 0;          // entries per per-sub-block count slice (blockSums: one slice; blockUpd: DEFER_WIN slices, one per keyframe of a window)
     unsigned long long kfClassic = 0, kfDeferred = 0;   // keyframes that went through the classic pair of launches / through deferred windows (msl_sf_debug_scratch, which = 5)
-    int dealG = 0;                 // the k_fuse grid SfDev::deal currently is a permutation for (0: none yet) -- screen-position dealing, msl_sf_map.hip
+    int dealG = 0;                 // the k_fuse grid SfDev::deal currently is a permutation for (0: none yet) -- screen-position dealing, msl_sf_compact.hip
     hipStream_t copyStream = nullptr;   // host-image mode: the H2D copies of slot set i + 1 run beside the superpixel kernels of set i
     // Synchronisation state of one of the two slot sets.  h2d: the set's staged images have arrived (recorded by every host-image batch; msl_sf_staged_gray
     // hands it to other handles); pre / map: the set's last superpixel stage / map stage is done; copy: its pinned FrameDev staging has been read
@@ -90,29 +91,38 @@ struct msl_sf {
 
 namespace {
 
-// Map storage, in 4-byte words per surfel of capacity c (c is a multiple of 4096, so every array starts 32-byte aligned):
-//   map.store: hot 4 | cold 8 | rgbWide 3 | utlWide 2                                                               = 17 c
-//   map.rp   : moveDst 1 | loc64 2 | vposD 1 | locKeys 1 | vposKeys 1 | dBig 1 | stageHot 4 | stageCold 8 | stageRgb 3 | stageUtl 2 | bitmap c / 32 + 64
-constexpr size_t MAP_WORDS = 17, RP_WORDS = 24;
+// Map storage, in 4-byte words per surfel of capacity c (c is a multiple of 4096, so every array starts 32-byte aligned).  Each array's word
+// offset is the one before it plus that one's record; array X of a store laid out for c surfels starts at word X * c.
+//   map.store: hot | cold | rgbWide (3 ints) | utlWide (2 ints)
+//   map.rp   : loc64 (first: 8-byte aligned) | stageCold | stageHot | moveDst | vposD | locKeys | vposKeys | dBig | stageRgb | stageUtl | bitmap c / 32 + 64
+constexpr size_t HOT_W = sizeof(HotPk) / 4, COLD_W = sizeof(ColdRec) / 4;
+constexpr size_t ST_HOT = 0, ST_COLD = ST_HOT + HOT_W, ST_RGB = ST_COLD + COLD_W, ST_UTL = ST_RGB + 3, MAP_WORDS = ST_UTL + 2;
+constexpr size_t RP_LOC64 = 0, RP_STAGE_COLD = RP_LOC64 + 2, RP_STAGE_HOT = RP_STAGE_COLD + COLD_W, RP_MOVE_DST = RP_STAGE_HOT + HOT_W, RP_VPOS_D = RP_MOVE_DST + 1,
+                 RP_LOC_KEYS = RP_VPOS_D + 1, RP_VPOS_KEYS = RP_LOC_KEYS + 1, RP_DBIG = RP_VPOS_KEYS + 1, RP_STAGE_RGB = RP_DBIG + 1, RP_STAGE_UTL = RP_STAGE_RGB + 3,
+                 RP_BITMAP = RP_STAGE_UTL + 2, RP_WORDS = RP_BITMAP;   // (the bitmap is not per surfel: it follows the RP_WORDS * c words of the others)
+constexpr size_t rp_bitmap_words(size_t c) { return c / 32 + 64; }
+static_assert(ST_HOT == 0 && ST_COLD == 4 && ST_RGB == 12 && ST_UTL == 15 && MAP_WORDS == 17, "layout of map.store");
+static_assert(RP_LOC64 == 0 && RP_STAGE_COLD == 2 && RP_STAGE_HOT == 10 && RP_MOVE_DST == 14 && RP_VPOS_D == 15 && RP_LOC_KEYS == 16 && RP_VPOS_KEYS == 17 &&
+              RP_DBIG == 18 && RP_STAGE_RGB == 19 && RP_STAGE_UTL == 22 && RP_BITMAP == 24 && RP_WORDS == 24, "layout of map.rp");
 void set_map_ptrs(msl_sf *h, size_t c) {
     MapSoA &M = h->dev.map;
     float *store = (float *)h->map.store.p;
-    M.hot = reinterpret_cast<HotPk *>(store);
-    M.cold = reinterpret_cast<ColdRec *>(store + 4 * c);
-    M.rgbWide = reinterpret_cast<int *>(store + 12 * c);        // exact ints of the COLD_WIDE records (untouched otherwise)
-    M.utlWide = reinterpret_cast<int *>(store + 15 * c);        // exact ints of the HOT_WIDE records
+    M.hot = reinterpret_cast<HotPk *>(store + ST_HOT * c);
+    M.cold = reinterpret_cast<ColdRec *>(store + ST_COLD * c);
+    M.rgbWide = reinterpret_cast<int *>(store + ST_RGB * c);    // exact ints of the COLD_WIDE records (untouched otherwise)
+    M.utlWide = reinterpret_cast<int *>(store + ST_UTL * c);    // exact ints of the HOT_WIDE records
     M.wideFlag = h->dev.ctr + 13;
     SfDev &D = h->dev;
     D.cap = c;
     D.blockSums = (unsigned *)h->map.blockSums.p; D.blockUpd = (unsigned *)h->map.blockUpd.p; D.delList = (unsigned *)h->map.delList.p; D.srcOf = (unsigned *)h->map.srcOf.p;
     D.sbKeys = D.blockSums + h->blkStride; D.deal = D.blockSums + 2 * h->blkStride; D.dealG = 0;   // (three planes of one allocation: counts, screen keys, dealing table)
     unsigned *r = (unsigned *)h->map.rp.p;
-    D.loc64 = reinterpret_cast<unsigned long long *>(r);            // (first: 8-byte aligned)
-    D.stageCold = reinterpret_cast<ColdRec *>(r + 2 * c);
-    D.stageHot = reinterpret_cast<HotPk *>(r + 10 * c);
-    D.moveDst = r + 14 * c; D.vposD = r + 15 * c; D.locKeys = r + 16 * c; D.vposKeys = r + 17 * c; D.dBig = r + 18 * c;
-    D.stageRgb = reinterpret_cast<int *>(r + 19 * c); D.stageUtl = reinterpret_cast<int *>(r + 22 * c);
-    D.bitmap = r + 24 * c;
+    D.loc64 = reinterpret_cast<unsigned long long *>(r + RP_LOC64 * c);
+    D.stageCold = reinterpret_cast<ColdRec *>(r + RP_STAGE_COLD * c);
+    D.stageHot = reinterpret_cast<HotPk *>(r + RP_STAGE_HOT * c);
+    D.moveDst = r + RP_MOVE_DST * c; D.vposD = r + RP_VPOS_D * c; D.locKeys = r + RP_LOC_KEYS * c; D.vposKeys = r + RP_VPOS_KEYS * c; D.dBig = r + RP_DBIG * c;
+    D.stageRgb = reinterpret_cast<int *>(r + RP_STAGE_RGB * c); D.stageUtl = reinterpret_cast<int *>(r + RP_STAGE_UTL * c);
+    D.bitmap = r + RP_BITMAP * c;
 }
 
 // The asynchronous live-count snapshots only ever LOWER liveBound; whenever the map is replaced from outside the keyframe chain
@@ -146,7 +156,7 @@ int write_ctl(msl_sf *h) {
 int map_realloc(msl_sf *h, size_t cap, size_t keep) {
     cap = (cap + 4095) & ~(size_t)4095;
     const size_t bst = cap / SUB_ITEMS + 8200;   // per slice; >= 1024 / 8192 padding entries: the compaction reads its first tiles unconditionally
-    const size_t rpWords = RP_WORDS * cap + cap / 32 + 64;
+    const size_t rpWords = RP_WORDS * cap + rp_bitmap_words(cap);
     msl_sf::MapBufs m;
     MSL_HIP_TRY(grow_all(h->mapStream, {{m.store, sizeof(float) * MAP_WORDS * cap},
                                         {m.blockSums, sizeof(unsigned) * 3 * bst},           // deleted counts | screen keys | dealing table (SfDev::sbKeys, ::deal)
@@ -156,19 +166,19 @@ int map_realloc(msl_sf *h, size_t cap, size_t keep) {
     MSL_HIP_TRY(hipMemset(nbs, 0, sizeof(unsigned) * bst));
     MSL_HIP_TRY(hipMemset(nbs + bst, 0xFF, sizeof(unsigned) * bst));    // no key yet: "nothing in view"
     MSL_HIP_TRY(hipMemset(m.blockUpd.p, 0, sizeof(unsigned) * DEFER_WIN * bst));
-    MSL_HIP_TRY(hipMemset(nrp, 0, sizeof(unsigned) * 2 * cap));                              // loc64: empty (the replay leaves it clean)
-    MSL_HIP_TRY(hipMemset(nrp + 15 * cap, 0, sizeof(unsigned) * cap));                       // vposD
-    MSL_HIP_TRY(hipMemset(nrp + 24 * cap, 0, sizeof(unsigned) * (cap / 32 + 64)));           // bitmap
+    MSL_HIP_TRY(hipMemset(nrp + RP_LOC64 * cap, 0, sizeof(unsigned long long) * cap));         // loc64: empty (the replay leaves it clean)
+    MSL_HIP_TRY(hipMemset(nrp + RP_VPOS_D * cap, 0, sizeof(unsigned) * cap));                  // vposD
+    MSL_HIP_TRY(hipMemset(nrp + RP_BITMAP * cap, 0, sizeof(unsigned) * rp_bitmap_words(cap))); // bitmap
     if (keep && h->map.store.p) {
         const int rc = sync_all(h);
         if (rc != MSL_OK) return rc;
         const size_t oc = h->dev.cap;
         float *nstore = (float *)m.store.p;
         const float *ostore = (const float *)h->map.store.p;
-        MSL_HIP_TRY(hipMemcpy(nstore, ostore, sizeof(HotPk) * keep, hipMemcpyDeviceToDevice));
-        MSL_HIP_TRY(hipMemcpy(nstore + 4 * cap, ostore + 4 * oc, sizeof(ColdRec) * keep, hipMemcpyDeviceToDevice));
-        MSL_HIP_TRY(hipMemcpy(nstore + 12 * cap, ostore + 12 * oc, sizeof(int) * 3 * keep, hipMemcpyDeviceToDevice));   // (rare path: no need to know whether any record is wide)
-        MSL_HIP_TRY(hipMemcpy(nstore + 15 * cap, ostore + 15 * oc, sizeof(int) * 2 * keep, hipMemcpyDeviceToDevice));
+        MSL_HIP_TRY(hipMemcpy(nstore + ST_HOT * cap, ostore + ST_HOT * oc, sizeof(HotPk) * keep, hipMemcpyDeviceToDevice));
+        MSL_HIP_TRY(hipMemcpy(nstore + ST_COLD * cap, ostore + ST_COLD * oc, sizeof(ColdRec) * keep, hipMemcpyDeviceToDevice));
+        MSL_HIP_TRY(hipMemcpy(nstore + ST_RGB * cap, ostore + ST_RGB * oc, sizeof(int) * 3 * keep, hipMemcpyDeviceToDevice));   // (rare path: no need to know whether any record is wide)
+        MSL_HIP_TRY(hipMemcpy(nstore + ST_UTL * cap, ostore + ST_UTL * oc, sizeof(int) * 2 * keep, hipMemcpyDeviceToDevice));
     }
     h->map = std::move(m);
     h->blkStride = bst;
@@ -462,7 +472,7 @@ FuseGrid fuse_grid(const msl_sf *h, bool compact) {
 }
 
 // Map stage of the n keyframes in `set`, on the map stream.  Deferred compaction (MSL_SF_DEFER=0 turns it off, =1 forces it; unset: the policy
-// below): windows of <= DEFER_WIN keyframes, ONE launch per keyframe, the window's compactions replayed at its end (msl_sf_map.hip).  Classic
+// below): windows of <= DEFER_WIN keyframes, ONE launch per keyframe, the window's compactions replayed at its end (msl_sf_replay.hip).  Classic
 // (k_fuse + k_compact per keyframe): single keyframes, the host-vector drop-in, the first keyframe after the map was replaced from outside, and
 // batches enqueued while the recent churn (spawned + deleted surfels per keyframe, from the asynchronous counter snapshots) is high -- k_compact
 // takes any number of stale or deleted slots with all its workgroups, the replay's single wave is built for the steady state.  Both leave
@@ -481,7 +491,7 @@ int launch_map_chain(msl_sf *h, SfDev &P, int set, int n, bool compact) {
     const bool churny = !pol.deferForce && (h->churn > CHURN_MAX || sp != sm);
     auto classic = [&](int f) {
         P.kf = 0;
-        map_launch_fuse(h->prof, sm, P, f, hf[f], g.nSubGrid, g.nSubHint, false, g.dealOn && h->dealG == g.nSubGrid);
+        map_launch_fuse(h->prof, sm, P, f, hf[f], g.nSubGrid, g.nSubHint, false, g.dealOn && h->dealG == g.nSubGrid, (unsigned)h->blkStride);
         // k_compact's second workgroup deals the sub-blocks for the launches that follow (resident mode: 128 workgroups) -- on every dealEvery-th
         // keyframe of a call and whenever the table does not fit the grid: the pass takes one workgroup ~10 us against the compaction's ~6 beside it
         // (32 keys per thread through LDS atomics and scattered stores), and a table a few keyframes old still has nearly every sub-block in the
@@ -501,7 +511,7 @@ int launch_map_chain(msl_sf *h, SfDev &P, int set, int n, bool compact) {
             const int w = std::min(DEFER_WIN, n - f);
             for (int q = 0; q < w; q++) {
                 P.kf = q; P.prevSlotAbs = slot0 + f + q - 1;
-                map_launch_fuse(h->prof, sm, P, f + q, hf[f + q], g.nSubGrid, g.nSubHint, true, g.dealOn && h->dealG == g.nSubGrid);
+                map_launch_fuse(h->prof, sm, P, f + q, hf[f + q], g.nSubGrid, g.nSubHint, true, g.dealOn && h->dealG == g.nSubGrid, (unsigned)h->blkStride);
                 if (f + q == fProbe) map_launch_empty_pair(h->prof, sm);
             }
             P.kf = w; P.prevSlotAbs = slot0 + f + w - 1;
@@ -732,10 +742,10 @@ int msl_sf_map_snapshot(msl_sf *h) noexcept {
     if (n) {
         float *snap = (float *)h->d_snapStore.p;
         const size_t sc = h->d_snapStore.cap / (sizeof(float) * MAP_WORDS);   // surfels the store is laid out for
-        MSL_HIP_TRY(hipMemcpy(snap, h->dev.map.hot, sizeof(HotPk) * n, hipMemcpyDeviceToDevice));
-        MSL_HIP_TRY(hipMemcpy(snap + 4 * sc, h->dev.map.cold, sizeof(ColdRec) * n, hipMemcpyDeviceToDevice));
-        if (ctr[13] & 1) MSL_HIP_TRY(hipMemcpy(snap + 12 * sc, h->dev.map.rgbWide, sizeof(int) * 3 * n, hipMemcpyDeviceToDevice));
-        if (ctr[13] & 2) MSL_HIP_TRY(hipMemcpy(snap + 15 * sc, h->dev.map.utlWide, sizeof(int) * 2 * n, hipMemcpyDeviceToDevice));
+        MSL_HIP_TRY(hipMemcpy(snap + ST_HOT * sc, h->dev.map.hot, sizeof(HotPk) * n, hipMemcpyDeviceToDevice));
+        MSL_HIP_TRY(hipMemcpy(snap + ST_COLD * sc, h->dev.map.cold, sizeof(ColdRec) * n, hipMemcpyDeviceToDevice));
+        if (ctr[13] & 1) MSL_HIP_TRY(hipMemcpy(snap + ST_RGB * sc, h->dev.map.rgbWide, sizeof(int) * 3 * n, hipMemcpyDeviceToDevice));
+        if (ctr[13] & 2) MSL_HIP_TRY(hipMemcpy(snap + ST_UTL * sc, h->dev.map.utlWide, sizeof(int) * 2 * n, hipMemcpyDeviceToDevice));
     }
     h->snapN = n; h->snapValid = true; h->snapWide = ctr[13];
     return MSL_OK;
@@ -758,10 +768,10 @@ int msl_sf_map_restore(msl_sf *h) noexcept {
     if (n) {
         const float *snap = (const float *)h->d_snapStore.p;
         const size_t sc = h->d_snapStore.cap / (sizeof(float) * MAP_WORDS);
-        MSL_HIP_TRY(hipMemcpyAsync(h->dev.map.hot, snap, sizeof(HotPk) * n, hipMemcpyDeviceToDevice, s));
-        MSL_HIP_TRY(hipMemcpyAsync(h->dev.map.cold, snap + 4 * sc, sizeof(ColdRec) * n, hipMemcpyDeviceToDevice, s));
-        if (h->snapWide & 1) MSL_HIP_TRY(hipMemcpyAsync(h->dev.map.rgbWide, snap + 12 * sc, sizeof(int) * 3 * n, hipMemcpyDeviceToDevice, s));
-        if (h->snapWide & 2) MSL_HIP_TRY(hipMemcpyAsync(h->dev.map.utlWide, snap + 15 * sc, sizeof(int) * 2 * n, hipMemcpyDeviceToDevice, s));
+        MSL_HIP_TRY(hipMemcpyAsync(h->dev.map.hot, snap + ST_HOT * sc, sizeof(HotPk) * n, hipMemcpyDeviceToDevice, s));
+        MSL_HIP_TRY(hipMemcpyAsync(h->dev.map.cold, snap + ST_COLD * sc, sizeof(ColdRec) * n, hipMemcpyDeviceToDevice, s));
+        if (h->snapWide & 1) MSL_HIP_TRY(hipMemcpyAsync(h->dev.map.rgbWide, snap + ST_RGB * sc, sizeof(int) * 3 * n, hipMemcpyDeviceToDevice, s));
+        if (h->snapWide & 2) MSL_HIP_TRY(hipMemcpyAsync(h->dev.map.utlWide, snap + ST_UTL * sc, sizeof(int) * 2 * n, hipMemcpyDeviceToDevice, s));
     }
     // the restored map has exactly the snapshot's wide-rgb state: without the flag a later snapshot would skip rgbWide and a restore of THAT
     // one would bring COLD_WIDE records back without their exact ints

@@ -1,4 +1,4 @@
-"""GPU tests of the screen-position dealing of k_fuse's sub-blocks to the eight XCDs (round 6; msl_sf_map.hip: deal_subblocks).
+"""GPU tests of the screen-position dealing of k_fuse's sub-blocks to the eight XCDs (round 6; msl_sf_compact.hip: deal_subblocks).
 
 The dealing is a HINT for speed -- workgroup g runs on XCD g % 8, and an XCD whose waves all project into one band of image rows fetches that band
 of the texel map and of the seed records instead of the whole screen -- but the table must be a permutation of the grid whatever the keys are,

@@ -1,4 +1,4 @@
-"""Host model of the deferred compaction's symbolic replay (manhattanslam_amd/csrc/msl_sf_map.hip, k_replay) against the literal per-keyframe
+"""Host model of the deferred compaction's symbolic replay (manhattanslam_amd/csrc/msl_sf_replay.hip, k_replay) against the literal per-keyframe
 algorithm (new surfel k -> k-th largest hole else appended; back-to-front refill of the leftover holes: reference src/SurfelMapping.cpp:366-391).
 
 Inside a window of keyframes the device moves nothing: elements keep their physical slot (base elements 0 .. n0 - 1, the k-th new surfel of keyframe

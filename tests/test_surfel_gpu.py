@@ -934,7 +934,7 @@ def test_host_vector_sparse_change_list(oracle):
 
 def test_classic_chain_gives_identical_maps():
     """The parity suite pins the DEFERRED compaction (tests/conftest.py: MSL_SF_DEFER=1; round 5: one k_fuse launch per keyframe, new surfels appended
-    physically, the window's placements and tail moves replayed at its end, msl_sf_map.hip).  MSL_SF_DEFER=0 sends every keyframe through the classic pair
+    physically, the window's placements and tail moves replayed at its end, msl_sf_replay.hip).  MSL_SF_DEFER=0 sends every keyframe through the classic pair
     k_fuse + k_compact instead.  The flag is read once per process, so the batched / resident parity tests run again in a child process with
     it set: both chains leave the oracle's maps, counters and new-surfel lists."""
     import os
