@@ -864,6 +864,69 @@ MSL_API int msl_pnp_ransac_batch(int device, int n_pairs, int cap, int kcap, con
                                  msl_mem mem, float *Tcw_out, uint8_t *inlier, int32_t *pt_ref_out, int32_t *n_inliers, int32_t *status,
                                  msl_mem out_mem) MSL_NOEXCEPT;
 
+/* ---- 3-D line reconstruction: Frame::GetLineDepth + Frame::Obtain3DLine (src/Frame.cc:179-186, :528-603, src/3DLineExtractor.cpp) ----
+ * msl_lines_3d: for n_frames independent frames, the end-point depths of every keyline and, for every candidate keyline, one call of
+ * Frame::Obtain3DLine(i, imDepth) -- the <= max_samples + 1 depth samples along the keyline, their covariances (compPt3dCov), the
+ * Mahalanobis RANSAC with verify3dLine, the refit loop and the end points (extract3dline_mahdist), the acceptance test and the transform to
+ * the world -- in double where the reference is in double; then the line half of the call site named by `order`, which decides where a
+ * MapLine is constructed.  Per frame f (`lcap` entries per frame, keyline j < n_lines[f]):
+ *   line_ends[4 j..]   mvKeylinesUn[j].startPointX, startPointY, endPointX, endPointY
+ *   depth              mImDepth of the frame (CV_32F, already scaled): row r of frame f starts depth_frame_stride * f + depth_row_stride * r
+ *                      BYTES after `depth`; width x height pixels
+ *   line_flags[j]      bit 0: mvpMapLines[j] != NULL, bit 1: its Observations() > 0 (NULL = all 0; not read with MSL_LINE3D_ALL)
+ *   Tcw[12]            rows 0-2 of the CV_32F mTcw; mRwc and mOw are derived from it (Frame::UpdatePoseMatrices)
+ *   seed[j]            the sampler's seed of the keyline
+ * Out, for every j < lcap (entries at or beyond n_lines[f] get -1 depths and zeros):
+ *   line_depth[2 j..]  mvDepthLine[j]
+ *   line_ok[j]         1 where the keyline is a candidate and Obtain3DLine returned a line; line_xyz[6 j..] its world end points A, B
+ *                      (float values widened to double, as the reference stores them), six zeros otherwise
+ *   n_support[j]       the supporting samples extract3dline_mahdist returned (0 when it was not reached)
+ *   line_new[j]        1 where the call site constructs a MapLine from that line;  n_new[f] their number
+ * Candidates have both end depths > 0 and, in the two ordered modes, are not held by a line with Observations() > 0.  A keyline's result
+ * never depends on the others, so all candidates are computed and the walk is applied afterwards: in index order or in ascending
+ * (min end depth, index) order, a keyline held with observations and a new line both count, a failed keyline does not, and the walk stops
+ * once the count exceeds max_new_lines.  line_ok / line_xyz do not depend on the walk.
+ * line_xyz and line_ok have the layout msl_match_lines_by_projection reads as last_line_xyz / bit 0 of last_line_flags, and
+ * msl_pose_optimize as line_xyz / line_has.
+ *
+ * Pinned where the reference is undefined or not restated (tests/line3d_model.py is the sequential model):
+ *   - cv::SVD: the cyclic Jacobi eigen-solver of msl_pnp_ransac (16 sweeps, round-robin pair order, descending eigenvalues, no sign
+ *     normalisation) on the symmetric 3x3 matrix -- cov0 itself (its upper triangle) for a sample, P^T P of the centred inliers (sums left
+ *     to right in ascending sample order) for the refit.  The Mahalanobis distance does not depend on the order or signs of DU's rows;
+ *     the sign of the refit direction only swaps A and B, so the order of the end points is defined by this solver.
+ *   - rand() % left: draw j of iteration k of a keyline is fmix32(fmix32(seed ^ k * 0x9E3779B1) ^ (j + 1) * 0x85EBCA77), the index
+ *     mulhi32(hash, left), as in msl_pnp_ransac.
+ *   - the comparison with static_cast<Vector6d>(NULL) is line_ok; numSmp == 0 and fewer than min_points samples are "no line".
+ *   - GetLineDepth: an end point whose truncated coordinates fall outside the image has depth -1.0f.
+ *   - non-finite values propagate by IEEE rules (a sample depth near 0.345 m makes sigma(z) zero); a NaN distance is not an inlier.
+ * Limits: lcap <= 256, 1 <= max_samples <= 127, 0 <= max_iterations <= 64, min_points >= 2, order one of MSL_LINE3D_*, strides that are
+ * multiples of 4 with depth_row_stride >= 4 * width; anything else is refused with MSL_ERR_INVALID and msl_last_error() naming the field,
+ * before any launch.  Synchronisation: as msl_match_by_projection. */
+typedef struct msl_line3d_params {
+    float fx, fy, cx, cy;          /* Frame::fx .. cy; invfx = 1.0f / fx, invfy = 1.0f / fy are formed by the library in float */
+    int32_t max_samples;           /* 100 */
+    int32_t min_points;            /* 10  */
+    int32_t max_iterations;        /* 10  */
+    int32_t max_new_lines;         /* 30: the walk stops once the count exceeds it */
+    double dist_thresh;            /* 1.5 (Mahalanobis) */
+    double min_support;            /* 0.4: supporting samples / 2-D length */
+    double min_length;             /* 0.02 m */
+} msl_line3d_params;
+#define MSL_LINE3D_ALL          0  /* StereoInitialization: every keyline with both end depths > 0 */
+#define MSL_LINE3D_INDEX_ORDER  1  /* UpdateLastFrame: index order, the nLines > max_new_lines stop */
+#define MSL_LINE3D_DEPTH_ORDER  2  /* CreateNewKeyFrame: ascending (min end depth, index), the same stop */
+MSL_API int msl_lines_3d(msl_match *h, int n_frames, int lcap, int order, const msl_line3d_params *params, const float *line_ends,
+                         const int32_t *n_lines, const float *depth, size_t depth_row_stride, size_t depth_frame_stride, int width,
+                         int height, const uint8_t *line_flags, const float *Tcw, const uint32_t *seed, msl_mem mem, float *line_depth,
+                         double *line_xyz, uint8_t *line_ok, uint8_t *line_new, int32_t *n_support, int32_t *n_new,
+                         msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device matcher handle, always synchronous; see msl_match_by_projection_batch). */
+MSL_API int msl_lines_3d_batch(int device, int n_frames, int lcap, int order, const msl_line3d_params *params, const float *line_ends,
+                               const int32_t *n_lines, const float *depth, size_t depth_row_stride, size_t depth_frame_stride, int width,
+                               int height, const uint8_t *line_flags, const float *Tcw, const uint32_t *seed, msl_mem mem,
+                               float *line_depth, double *line_xyz, uint8_t *line_ok, uint8_t *line_new, int32_t *n_support, int32_t *n_new,
+                               msl_mem out_mem) MSL_NOEXCEPT;
+
 /* msl_kfdb: a KeyFrameDatabase (src/KeyFrameDatabase.cc:38-66) on one device.  msl_kfdb_create returns NULL with msl_last_error() when no
  * device is usable.  msl_kfdb_add stores the BowVector of one keyframe exactly as msl_bow_transform wrote it (ascending int32 words, double
  * values, the count -- on the device for MSL_MEM_DEVICE) and returns its slot when the vector is stored; with device memory `h` is the

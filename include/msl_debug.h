@@ -81,6 +81,12 @@ MSL_API int msl_debug_chain_sum(const float *x_host, const int32_t *n_host, int 
 MSL_API int msl_pnp_debug_hypotheses(msl_match *h, int pair, int k_cap, double *R, double *t, int32_t *branch, int32_t *count,
                                      int32_t *n_out) MSL_NOEXCEPT;
 
+/* One keyline of the last msl_lines_3d call on h (host output, synchronous): counts[5] = the samples kept, the RANSAC iterations run, the
+ * rounds of the refit loop, the sample indices of the end points A and B; iterations[64][4] = per iteration the two drawn sample indices,
+ * the inlier count (-1 where |B - A| < EPS used the iteration up) and whether it became the record (zeros beyond the iterations run);
+ * md[6] = the final m and d of extract3dline_mahdist. */
+MSL_API int msl_lines_3d_debug(msl_match *h, int frame, int line, int32_t *counts, int32_t *iterations, double *md) MSL_NOEXCEPT;
+
 #define MSL_SF_NKERNELS 12
 MSL_API int msl_sf_profile_enable(msl_sf *h, int mode) MSL_NOEXCEPT;
 /* Sampling for the per-dispatch event pairs: only every stride-th launch of a timed kernel carries events (default 1 = every launch).  A

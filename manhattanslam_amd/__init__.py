@@ -23,3 +23,5 @@ from . import reloc  # noqa: F401
 from ._lib import KEYFRAME_MATCH_PARAMS_DTYPE  # noqa: F401
 from . import pnp  # noqa: F401
 from ._lib import PNP_PARAMS_DTYPE  # noqa: F401
+from . import line3d  # noqa: F401
+from ._lib import LINE3D_PARAMS_DTYPE  # noqa: F401

@@ -46,6 +46,10 @@ KEYFRAME_MATCH_PARAMS_DTYPE = np.dtype(MATCH_PARAMS_DTYPE.descr + [("log_scale_f
 PNP_PARAMS_DTYPE = np.dtype([(n, "<f4") for n in ("fx", "fy", "cx", "cy")] + [("nlevels", "<i4"), ("level_sigma2", "<f4", (16,)), ("probability", "<f8")] +
                             [(n, "<i4") for n in ("min_inliers", "max_iterations", "min_set")] + [("epsilon", "<f4"), ("th2", "<f4"),
                                                                                                   ("n_iterations", "<i4")], align=True)   # msl_pnp_params
+LINE3D_PARAMS_DTYPE = np.dtype([(n, "<f4") for n in ("fx", "fy", "cx", "cy")] + [(n, "<i4") for n in ("max_samples", "min_points", "max_iterations",
+                                                                                            "max_new_lines")] +
+                               [(n, "<f8") for n in ("dist_thresh", "min_support", "min_length")])                                  # msl_line3d_params
+assert LINE3D_PARAMS_DTYPE.itemsize == 56
 assert PNP_PARAMS_DTYPE.itemsize == 120 and PNP_PARAMS_DTYPE.fields["probability"][1] == 88
 assert POSE_PARAMS_DTYPE.itemsize == 152 and KEYPOINT_DTYPE.itemsize == 28 and SURFEL_DTYPE.itemsize == 56 and SEED_DTYPE.itemsize == 64
 
@@ -141,6 +145,9 @@ SIGNATURES = {
     "msl_pnp_ransac": (_i, [_vp, _i, _i, _i] + [_vp] * 7 + [_i] + [_vp] * 5 + [_i]),
     "msl_pnp_ransac_batch": (_i, [_i, _i, _i, _i] + [_vp] * 7 + [_i] + [_vp] * 5 + [_i]),
     "msl_pnp_debug_hypotheses": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "msl_lines_3d": (_i, [_vp, _i, _i, _i] + [_vp] * 4 + [_sz, _sz, _i, _i] + [_vp] * 3 + [_i] + [_vp] * 6 + [_i]),
+    "msl_lines_3d_batch": (_i, [_i, _i, _i, _i] + [_vp] * 4 + [_sz, _sz, _i, _i] + [_vp] * 3 + [_i] + [_vp] * 6 + [_i]),
+    "msl_lines_3d_debug": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "msl_sf_fuse_resident": (_i, [_vp, _i, _vp, _sz, _vp, _sz, _vp, _sz, _i, _vp]),
     "msl_sf_set_batch_capacity": (_i, [_vp, _i]),
     "msl_sf_fuse_resident_batch": (_i, [_vp, _i, _vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _sz, _sz, _i, _vp]),

@@ -1,5 +1,5 @@
 // msl_match_handle.h -- the matcher handle, its staging of caller arrays (Stage) and the forwarder of the *_batch entry points; shared by
-// msl_match.hip, msl_line_match.hip, msl_pose.hip, msl_plane.hip, msl_bow.hip, msl_reloc.hip and msl_pnp.hip (internal).
+// msl_match.hip, msl_line_match.hip, msl_pose.hip, msl_plane.hip, msl_bow.hip, msl_reloc.hip, msl_pnp.hip and msl_line3d.hip (internal).
 #pragma once
 
 #include "msl_common.h"
@@ -30,6 +30,8 @@ struct msl_match {
     msl::DevBuf pnp, pnpTable;
     msl::PnpKey pnpKey{}; bool pnpTableValid = false;
     int pnpPairs = 0, pnpKmax = 0; size_t pnpOffK = 0, pnpOffCnt = 0, pnpOffRt = 0, pnpOffBr = 0;
+    msl::DevBuf line3d;                                                // msl_lines_3d: per keyline the record msl_lines_3d_debug reads
+    int line3dFrames = 0, line3dLcap = 0;                              // the shape of the last call
     // Device copies of host-memory arguments, one pool for every entry point (msl::Stage deals the slots out in declaration order).
     // Sharing is sound because every call that touches the pool returns with the stream drained (Stage::finish synchronises whenever
     // either side is host memory, and only then is a slot used), so no slot is live when the next call starts.
