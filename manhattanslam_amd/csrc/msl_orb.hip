@@ -4,8 +4,8 @@
 // integer/byte work, HBM/L2-bound; no MFMA (nothing here is a contraction).  Per batch of B frames:
 //
 //   k_pyramid  x1      all levels, tile chains through LDS (k_resize x(L-1) as fallback): OpenCV 11-bit fixed-point bilinear   (:872-893, cv::resize)
-//   k_fast     x1      one workgroup per 30-px FAST cell: LDS-staged tile, FAST-9/16 score,
-//                      in-cell 3x3 NMS, iniTh->minTh fallback, ordered ballot compaction (:745-780)
+//   k_fast     x1      one wave per 30-px FAST cell: LDS-staged tile, packed quick test, FAST-9/16 score,
+//                      in-cell 3x3 NMS, at iniTh and only then at minTh, ordered ballot compaction (:745-780)
 //   k_octree   x1      one workgroup per (frame, level): quadtree distribution, LDS resident (:531-721)
 //   k_blur     x1      7x7 sigma-2 fixed-point separable Gaussian, LDS tile             (:851-852)
 //   k_describe x1      one wave per keypoint: IC_Angle + steered BRIEF-256, output assembly
@@ -15,6 +15,7 @@
 // reference's order and this file is compiled with -ffp-contract=off.
 
 #include "msl_orb_dev.h"
+#include "msl_orb_fast.h"
 
 #include <type_traits>
 
@@ -133,144 +134,137 @@ __global__ __launch_bounds__(256) void k_pyramid(OrbDev P) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// k_fast: one workgroup (256 threads) per FAST cell.
+// k_fast: one wave (64 threads) per FAST cell; the integer pieces are msl_orb_fast.h.  Nothing here waits for another wave: no __syncthreads(),
+// no LDS atomics.  Orderings come from ballots and mbcnt ranks, and LDS written by other lanes is read behind wave_lds_sync().
+//   tile     (cw + 6) x (ch + 6) pixels into LDS, four bytes per load and store
+//   stage    at a threshold: quick test -> list -> score -> 3x3 suppression inside the cell -> keys
+//     quick test   a lane owns groups of four horizontally adjacent pixels, enumerated over a row pitch padded to four (the columns >= cw are masked):
+//                  13 word reads, byte offsets by v_alignbyte, then fast_quick4 on 16-bit pairs.  The groups' (row, group, element) order is
+//                  the cell's row-major order; four ballots give every passing pixel its place in the list
+//     score        64 list entries at a time: full lanes whatever the candidates' density (fast_score16)
+//     suppression  over the list again; a ballot orders the kept pixels, which go straight to cellKeys (row-major order, as k_octree reads them)
+//   The stage runs at iniTh.  Only a cell that keeps nothing there -- no corner at iniTh, or none that is a strict local maximum, e.g. two adjacent
+//   equal maxima -- runs it again at minTh (:766-769); the branch is uniform over the wave.  A cell with corners at iniTh therefore never scores
+//   the pixels that pass at minTh only.  That is exact: a pixel kept at iniTh scores above any neighbour that fails the quick test at iniTh,
+//   whether that neighbour's score is stored or left 0 (fast_quick4).
+// LDS is dynamic and sized by the largest cell of the geometry (fast_lds, OrbLaunch::fastLds): 5.8 KB for a 640 x 480 frame (the 37 x 34 cells of its last level).
 // ---------------------------------------------------------------------------------------------
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ s16x2 pk_min(s16x2 a, s16x2 b) { return __builtin_elementwise_min(a, b); }
-__device__ __forceinline__ s16x2 pk_max(s16x2 a, s16x2 b) { return __builtin_elementwise_max(a, b); }
-__device__ __forceinline__ int fast_score16(const uint8_t *t, int tp) {
-    // t points at the centre pixel inside the LDS tile (pitch tp).
-    // score = max(a, -b) - 1 with a = max over the 16 nine-arcs of min(d), b = min over arcs of max(d); since
-    // -b = max over arcs of min(-d), both halves are the same min/max network: run it once on packed (d, -d) pairs.
-    const int v = t[0];
-    const int ring[16] = {t[3 * tp], t[3 * tp + 1], t[2 * tp + 2], t[tp + 3], t[3], t[-tp + 3], t[-2 * tp + 2], t[-3 * tp + 1],
-                          t[-3 * tp], t[-3 * tp - 1], t[-2 * tp - 2], t[-tp - 3], t[-3], t[tp - 3], t[2 * tp - 2], t[3 * tp - 1]};
-    s16x2 x[16], lo2[16], lo4[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) { const int d = v - ring[k]; x[k] = (s16x2){(short)d, (short)-d}; }
-#pragma unroll
-    for (int k = 0; k < 16; k++) lo2[k] = pk_min(x[k], x[(k + 1) & 15]);
-#pragma unroll
-    for (int k = 0; k < 16; k++) lo4[k] = pk_min(lo2[k], lo2[(k + 2) & 15]);
-    s16x2 a = (s16x2){(short)-256, (short)-256};
-#pragma unroll
-    for (int k = 0; k < 16; k++) a = pk_max(a, pk_min(pk_min(lo4[k], lo4[(k + 4) & 15]), x[(k + 8) & 15]));
-    return max((int)a.x, (int)a.y) - 1;
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// number of set bits of m below this lane
+__device__ __forceinline__ unsigned lanes_below(unsigned long long m, unsigned add = 0) {
+    return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, add));
 }
 
-// Quick rejection (the classic FAST high-speed test on the 4 even opposite pairs): a 9-arc of 16 contains at least one pixel
-// of every opposite pair, so a pixel whose score reaches th has, for each pair, one member brighter (or darker) than th.
-// Pixels that fail cannot score >= th; their score is stored as 0, which changes neither the threshold tests nor the
-// non-maximum suppression of any kept pixel (a kept pixel scores >= th, above every such neighbour either way).
-__device__ __forceinline__ bool fast_candidate(const uint8_t *t, int tp, int th) {
-    const int v = t[0];
-    const int d0 = v - t[3 * tp], d8 = v - t[-3 * tp], d4 = v - t[3], d12 = v - t[-3];
-    const int d2 = v - t[2 * tp + 2], d10 = v - t[-2 * tp - 2], d6 = v - t[-2 * tp + 2], d14 = v - t[2 * tp - 2];
-    const bool bright = (d0 > th || d8 > th) && (d4 > th || d12 > th) && (d2 > th || d10 > th) && (d6 > th || d14 > th);
-    const bool dark = (d0 < -th || d8 < -th) && (d4 < -th || d12 < -th) && (d2 < -th || d10 < -th) && (d6 < -th || d14 < -th);
-    return bright || dark;
-}
-
-__global__ __launch_bounds__(256) void k_fast(OrbDev P) {
-    __shared__ __attribute__((aligned(4))) uint8_t s_tile[(MAXCELL + 6) * (MAXCELL + 8)];
-    __shared__ __attribute__((aligned(4))) uint8_t s_score[(MAXCELL + 2) * (MAXCELL + 2)];
-    __shared__ unsigned s_bits[2][MAXCELL * MAXCELL / 32];   // kept-pixel bitmaps: [0] at iniTh, [1] at minTh
-    __shared__ unsigned short s_list[MAXCELL * MAXCELL];   // pixels that pass the quick test
-    __shared__ unsigned s_wave[17];
-    __shared__ unsigned s_cnt[3];
-
+__global__ __launch_bounds__(64) void k_fast(OrbDev P) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t s_fast[];
     int cellI, frame;
     if (!xcd_item(P.cellsPerFrame, P.nFrames, cellI, frame)) return;
     const CellDev C = P.cells[cellI];
-    const int tid = threadIdx.x;
+    const int lane = threadIdx.x;
     uint32_t *cnt_out = P.cellCnt + (size_t)frame * P.cellsPerFrame + cellI;
     const int cw = C.cw, ch = C.ch;
-    if (cw <= 0 || ch <= 0) { if (tid == 0) *cnt_out = 0; return; }
+    if (cw <= 0 || ch <= 0) { if (lane == 0) *cnt_out = 0; return; }
     int pitch;
     const uint8_t *img = level_ptr(P, frame, C.level, pitch);
+    const FastLds F = fast_lds(cw, ch);
+    const int tp = F.tp, sp = F.sp;
+    uint8_t *const s_tile = s_fast;                                                           // rows y0-3.., cols x0-3..
+    uint8_t *const s_score = s_fast + F.scoreOff;                                             // pixel (r, c) at (r + 1) * sp + c + 1
+    unsigned short *const s_list = reinterpret_cast<unsigned short *>(s_fast + F.listOff);    // r << 8 | c
 
-    // stage (cw+6) x (ch+6) pixels: rows y0-3.., cols x0-3..
-    const int tw = cw + 6, th = ch + 6, tp = (tw + 3) & ~3;
-    // exact floor(i / w) for i < 2^13, w <= 2^7 by multiply-shift: one division per thread instead of one per pixel
-    const unsigned mCw = ((1u << 20) + cw - 1) / cw;
     {   // four bytes per load and LDS store (the tile's rows start at any byte; a row's last word may reach 3 bytes past the tile, still inside
-        // the image row: the cells end 13 px before the level's right edge)
-        const int nw = tp >> 2;
-        const unsigned mNw = ((1u << 20) + nw - 1) / nw;
+        // the image row: the cells end 13 px before the level's right edge).  The words of a row beyond these are never written: only masked
+        // columns read them.
+        const int nw = (cw + 6 + 3) >> 2;
+        const unsigned mNw = ((1u << 20) + nw - 1) / nw;   // exact floor(i / w) for i < 2^13, w <= 2^7 by multiply-shift
         const uint8_t *src = img + (size_t)(C.y0 - 3) * pitch + (C.x0 - 3);
-        for (int i = tid; i < nw * th; i += 256) {
+        for (int i = lane; i < nw * (ch + 6); i += 64) {
             const int r = (int)(((unsigned)i * mNw) >> 20), q = i - r * nw;
             uint32_t w4;
             __builtin_memcpy(&w4, src + (size_t)r * pitch + 4 * q, 4);
             *reinterpret_cast<uint32_t *>(&s_tile[r * tp + 4 * q]) = w4;
         }
     }
-    const int sp = cw + 2;
-    for (int i = tid; i < (sp * (ch + 2) + 3) >> 2; i += 256) reinterpret_cast<uint32_t *>(s_score)[i] = 0u;
-    if (tid < MAXCELL * MAXCELL / 32) { s_bits[0][tid] = 0; s_bits[1][tid] = 0; }
-    if (tid < 3) s_cnt[tid] = 0;
-    __syncthreads();
-    const int npx = cw * ch;
-    const int thQuick = min(P.iniTh, P.minTh);
-    for (int i0 = 0; i0 < npx; i0 += 256) {
-        const int i = i0 + tid;
-        bool cand = false;
-        if (i < npx) {
-            const int r = (int)(((unsigned)i * mCw) >> 20), c = i - r * cw;
-            cand = fast_candidate(&s_tile[(r + 3) * tp + c + 3], tp, thQuick);
-        }
-        const unsigned long long m = __ballot(cand);
-        if (m) {
-            unsigned base = 0;
-            if ((tid & 63) == 0) base = atomicAdd(&s_cnt[2], (unsigned)__popcll(m));
-            base = (unsigned)__builtin_amdgcn_readlane((int)base, 0);
-            if (cand) s_list[base + __popcll(m & ((1ull << (tid & 63)) - 1ull))] = (unsigned short)i;
-        }
-    }
-    __syncthreads();
-    const int nlist = (int)s_cnt[2];
-    for (int j = tid; j < nlist; j += 256) {
-        const int i = s_list[j];
-        const int r = (int)(((unsigned)i * mCw) >> 20), c = i - r * cw;
-        const int s = fast_score16(&s_tile[(r + 3) * tp + c + 3], tp);
-        s_score[(r + 1) * sp + c + 1] = (uint8_t)max(s, 0);
-    }
-    __syncthreads();
-    // NMS + threshold flags over the candidates only (everything else scores 0): one bit per pixel and threshold
-    unsigned c_ini = 0, c_min = 0;
-    for (int j = tid; j < nlist; j += 256) {
-        const int i = s_list[j];
-        const int r = (int)(((unsigned)i * mCw) >> 20), c = i - r * cw;
-        const uint8_t *q = &s_score[(r + 1) * sp + c + 1];
-        const int s = q[0];
-        if (s < thQuick) continue;
-        const bool lm = s > q[-1] && s > q[1] && s > q[-sp - 1] && s > q[-sp] && s > q[-sp + 1] &&
-                        s > q[sp - 1] && s > q[sp] && s > q[sp + 1];
-        if (!lm) continue;
-        if (s >= P.iniTh) { atomicOr(&s_bits[0][i >> 5], 1u << (i & 31)); c_ini++; }   // kept at iniTh
-        if (s >= P.minTh) { atomicOr(&s_bits[1][i >> 5], 1u << (i & 31)); c_min++; }   // kept at minTh
-    }
-    if (c_ini) atomicAdd(&s_cnt[0], c_ini);
-    if (c_min) atomicAdd(&s_cnt[1], c_min);
-    __syncthreads();
-    const int sel = s_cnt[0] ? 0 : 1;  // fallback to minTh when nothing survives at iniTh (:766-769)
-    const unsigned total = s_cnt[0] ? s_cnt[0] : s_cnt[1];
-    if (tid == 0) *cnt_out = total;
-    if (total == 0) return;
-    // ordered compaction, row-major inside the cell: thread t owns the 32 pixels of bitmap word t; its keys follow those
-    // of the lower words (one scan of the word popcounts) in ascending bit order
+    for (int i = lane; i < (sp * (ch + 2) + 3) >> 2; i += 64) reinterpret_cast<uint32_t *>(s_score)[i] = 0u;
+    wave_lds_sync();
+
+    const int ngr = (cw + 3) >> 2, nGroups = ngr * ch, wp = tp >> 2;
+    const unsigned mG = ((1u << 20) + ngr - 1) / ngr;
     uint32_t *out = P.cellKeys + (size_t)frame * P.keysPerFrame + C.keyOff;
-    static_assert(MAXCELL * MAXCELL / 32 <= 256, "one bitmap word per thread");
-    unsigned word = tid < MAXCELL * MAXCELL / 32 ? s_bits[sel][tid] : 0u;
-    unsigned tot;
-    unsigned pos = block_excl_scan((unsigned)__popc(word), s_wave, &tot);
-    while (word) {
-        const int i = tid * 32 + __builtin_ctz(word);
-        word &= word - 1;
-        const int r = (int)(((unsigned)i * mCw) >> 20), c = i - r * cw;
-        const unsigned kx = C.x0 + c - 16, ky = C.y0 + r - 16;  // border-frame coordinates (:773-774)
-        out[pos++] = kx | (ky << 12) | ((unsigned)s_score[(r + 1) * sp + c + 1] << 24);
+
+    // quick test at thQuick, score, suppression; keeps the strict 3x3 maxima that score >= thKeep and returns their number
+    auto stage = [&](int thQuick, int thKeep) -> unsigned {
+        unsigned nlist = 0;
+        for (int g0 = 0; g0 < nGroups; g0 += 64) {
+            const int g = g0 + lane;
+            unsigned m4 = 0;
+            int r = 0, c0 = 0;
+            if (g < nGroups) {
+                r = (int)(((unsigned)g * mG) >> 20); c0 = 4 * (g - r * ngr);
+                // tile rows r .. r + 6 are the centre row - 3 .. + 3; the words start at tile column c0 = the centres' column - 3
+                const uint32_t *w = reinterpret_cast<const uint32_t *>(s_tile + r * tp + c0);
+                const uint32_t u0 = w[0], u1 = w[1];                                                    // 3 rows up
+                const uint32_t a0 = w[wp], a1 = w[wp + 1], a2 = w[wp + 2];                              // 2 rows up
+                const uint32_t b0 = w[3 * wp], b1 = w[3 * wp + 1], b2 = w[3 * wp + 2];                  // the centre row
+                const uint32_t d0 = w[5 * wp], d1 = w[5 * wp + 1], d2 = w[5 * wp + 2];                  // 2 rows down
+                const uint32_t e0 = w[6 * wp], e1 = w[6 * wp + 1];                                      // 3 rows down
+                m4 = fast_quick4(fast_bytes(b0, b1, 3), /*0*/ fast_bytes(e0, e1, 3), /*8*/ fast_bytes(u0, u1, 3), /*4*/ fast_bytes(b1, b2, 2), /*12*/ b0,
+                                 /*2*/ fast_bytes(d1, d2, 1), /*10*/ fast_bytes(a0, a1, 1), /*6*/ fast_bytes(a1, a2, 1), /*14*/ fast_bytes(d0, d1, 1), thQuick);
+                if (cw - c0 < 4) m4 &= (1u << (cw - c0)) - 1u;
+            }
+            const unsigned long long q0 = __ballot(m4 & 1u), q1 = __ballot(m4 & 2u), q2 = __ballot(m4 & 4u), q3 = __ballot(m4 & 8u);
+            if (q0 | q1 | q2 | q3) {
+                unsigned pos = nlist + lanes_below(q3, lanes_below(q2, lanes_below(q1, lanes_below(q0))));
+                const unsigned rc = ((unsigned)r << 8) | (unsigned)c0;
+                if (m4 & 1u) s_list[pos++] = (unsigned short)rc;
+                if (m4 & 2u) s_list[pos++] = (unsigned short)(rc + 1);
+                if (m4 & 4u) s_list[pos++] = (unsigned short)(rc + 2);
+                if (m4 & 8u) s_list[pos++] = (unsigned short)(rc + 3);
+                nlist += (unsigned)(__popcll(q0) + __popcll(q1) + __popcll(q2) + __popcll(q3));
+            }
+        }
+        wave_lds_sync();
+        for (unsigned j = lane; j < nlist; j += 64) {
+            const unsigned rc = s_list[j];
+            const int r = (int)(rc >> 8), c = (int)(rc & 255u);
+            const uint8_t *t = &s_tile[(r + 3) * tp + c + 3];
+            const int ring[16] = {t[3 * tp], t[3 * tp + 1], t[2 * tp + 2], t[tp + 3], t[3], t[-tp + 3], t[-2 * tp + 2], t[-3 * tp + 1],
+                                  t[-3 * tp], t[-3 * tp - 1], t[-2 * tp - 2], t[-tp - 3], t[-3], t[tp - 3], t[2 * tp - 2], t[3 * tp - 1]};
+            s_score[(r + 1) * sp + c + 1] = (uint8_t)max(fast_score16((int)t[0], ring), 0);
+        }
+        wave_lds_sync();
+        unsigned kept = 0;
+        for (unsigned j0 = 0; j0 < nlist; j0 += 64) {
+            const unsigned j = j0 + lane;
+            bool keep = false;
+            uint32_t key = 0;
+            if (j < nlist) {
+                const unsigned rc = s_list[j];
+                const int r = (int)(rc >> 8), c = (int)(rc & 255u);
+                const uint8_t *q = &s_score[(r + 1) * sp + c + 1];
+                const int s = q[0];
+                keep = s >= thKeep && s > q[-1] && s > q[1] && s > q[-sp - 1] && s > q[-sp] && s > q[-sp + 1] && s > q[sp - 1] && s > q[sp] && s > q[sp + 1];
+                const unsigned kx = C.x0 + c - 16, ky = C.y0 + r - 16;  // border-frame coordinates (:773-774)
+                key = kx | (ky << 12) | ((unsigned)s << 24);
+            }
+            const unsigned long long m = __ballot(keep);
+            if (keep) out[kept + lanes_below(m)] = key;
+            kept += (unsigned)__popcll(m);
+        }
+        return kept;
+    };
+
+    const int thIni = min(P.iniTh, 256), thMin = min(P.minTh, 256);   // (a score is at most 254)
+    unsigned total = stage(thIni, thIni);
+    if (total == 0) {   // fallback to minTh when nothing survives at iniTh (:766-769)
+        wave_lds_sync();
+        total = stage(min(thIni, thMin), thMin);
     }
+    if (lane == 0) *cnt_out = total;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1087,7 +1081,7 @@ int orb_launch_pipeline(const OrbDev *dev, OrbLaunch *launch, const uint8_t *d_g
         MSL_HIP_TRY(hipEventRecord(q.evJoin, q.sideStream));
     }
     q.prof.begin(KID_FAST, s);
-    hipLaunchKernelGGL(k_fast, dim3(xcd_grid1((long long)P.cellsPerFrame * n)), dim3(256), 0, s, P);
+    hipLaunchKernelGGL(k_fast, dim3(xcd_grid1((long long)P.cellsPerFrame * n)), dim3(64), q.fastLds, s, P);
     q.prof.end(s);
     q.prof.begin(KID_OCTREE, s);
     if (q.octBig) hipLaunchKernelGGL(k_octree<32>, dim3(xcd_grid1((long long)L * n)), dim3(OCT_NT), (size_t)P.octLds, s, P);

@@ -29,8 +29,23 @@ struct OrbLaunch {
     hipStream_t sideStream = nullptr; hipEvent_t evFork = nullptr, evJoin = nullptr;   // single-frame calls: the blur runs beside FAST + quadtree
     KernelProfiler prof;
     size_t pyrLds = 0;     // k_pyramid: dynamic LDS bytes
+    size_t fastLds = 0;    // k_fast: dynamic LDS bytes (the largest cell of the geometry)
     bool octBig = false;   // frames of more than 640 x 480 x 1.5 pixels: level 0 may hold more than 8192 FAST candidates -> k_octree<32>
 };
+
+// k_fast's LDS for one cw x ch cell (one wave): the (ch + 6)-row pixel tile with a word pitch of tp bytes, the (cw + 2) x (ch + 2) score image
+// with its zero border, and the list of the pixels that pass the quick test (two bytes each, at most all of them).  tp leaves two words beyond
+// the last group of four pixels: the quick test reads three words per row.  Every part grows with cw and ch, so the level's wCell x hCell bounds
+// all of its cells.
+struct FastLds { int tp, sp, scoreOff, listOff, bytes; };
+__host__ __device__ inline FastLds fast_lds(int cw, int ch) {
+    FastLds f;
+    f.tp = 4 * ((cw + 3) >> 2) + 8; f.sp = cw + 2;
+    f.scoreOff = f.tp * (ch + 6);
+    f.listOff = (f.scoreOff + f.sp * (ch + 2) + 3) & ~3;
+    f.bytes = f.listOff + 2 * cw * ch;
+    return f;
+}
 
 // k_octree's dynamic LDS beyond what a launch gets by default (a large feature budget); called when a geometry is committed.
 int allow_octree_lds(int octLds);

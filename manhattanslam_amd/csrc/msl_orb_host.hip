@@ -61,7 +61,7 @@ struct OrbPlan {
     std::vector<CellDev> cells;
     std::vector<ResizeTap> taps;
     std::vector<PyrRange> pyrX, pyrY;
-    size_t pyrLds = 0, inPitch = 0, outKpsOff = 0, outDescOff = 0;
+    size_t pyrLds = 0, fastLds = 0, inPitch = 0, outKpsOff = 0, outDescOff = 0;
     int needCap = 0, outCap = 0;
     bool octBig = false;
     // running totals of the level loop
@@ -94,6 +94,7 @@ int plan_level_grid(const OrbConfig *h, OrbPlan &P, int l) {
         set_error("unsupported level geometry %dx%d (cell %dx%d)", G.w, G.h, G.wCell, G.hCell);
         return MSL_ERR_INVALID;
     }
+    P.fastLds = std::max(P.fastLds, (size_t)fast_lds(G.wCell, G.hCell).bytes);   // (a cell is at most wCell x hCell)
     G.cellBase = (int)P.cells.size(); G.nCells = G.nRows * G.nCols;
     G.keyBase = (int)P.keyOff;
     for (int i = 0; i < G.nRows; i++)
@@ -294,7 +295,7 @@ int commit_geometry(msl_orb *h, const OrbPlan &P) {
     h->d_kps = reinterpret_cast<msl_keypoint *>(out + P.outKpsOff);
     h->d_desc = out + P.outDescOff;
     h->outCap = P.outCap; h->inPitch = P.inPitch; h->outKpsOff = P.outKpsOff; h->outDescOff = P.outDescOff;
-    h->pyrLds = P.pyrLds; h->octBig = P.octBig;
+    h->pyrLds = P.pyrLds; h->fastLds = P.fastLds; h->octBig = P.octBig;
     { const int rc = allow_octree_lds(D.octLds); if (rc != MSL_OK) return rc; }
     h->geomW = P.W; h->geomH = P.H;
     return MSL_OK;
