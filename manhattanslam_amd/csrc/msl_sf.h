@@ -4,7 +4,11 @@
 //   msl_sf_compact.hip     map stage: new surfels (:285-331), compaction (src/SurfelMapping.cpp:366-391), dealing of the sub-blocks
 //   msl_sf_replay.hip      map stage: the end of a deferred-compaction window
 //   msl_sf_map.hip         map maintenance: selection, AoS <-> SoA, counters
-//   msl_surfel.hip         handle, streams, batching, the C ABI
+// and by the host units, none of which holds a kernel (what they share beyond this file: msl_sf_handle.h):
+//   msl_surfel.hip         the handle's lifecycle and streams, slot allocation and image staging, the batch driver, the profiler calls
+//   msl_sf_store.hip       the resident map as the host sees it: layout, live-count bookkeeping, the map-exchange ABI
+//   msl_sf_hostvec.hip     the host-vector drop-in msl_sf_fuse / msl_sf_fuse_ex (its transfer planner: msl_sf_plan.h)
+//   msl_sf_debug.hip       debug accessors, kernel names
 // (what only the four map-stage units share, and the stage's overview: msl_sf_map_dev.h)
 #pragma once
 
@@ -44,6 +48,22 @@ __host__ __device__ inline size_t fuserec_index(int nseeds, unsigned seed, int w
 #endif
 }
 
+// The map's counters, SfDev::ctr[] (64-bit each; "last": of the most recent keyframe).
+enum SfCtr {
+    CTR_LIVE = 0,          // surfels in the map
+    CTR_NEW = 1,           // K, surfels spawned (last)
+    CTR_DELETED = 2,       // D, surfels deleted (last)
+    CTR_UPDATED = 3,       // surfels fused (last)
+    CTR_BEFORE = 4,        // live count before (last)
+    CTR_ERR = 5,           // device-side error code (20: capacity exceeded); check_err reads and clears it
+    CTR_AFTER = 6,         // live count after (last)
+    CTR_TAIL_FLAG = 7,     // tail fallback flag of the last compaction: k_compact keeps it in LDS now, what is left is k_set_ctr's reset -- and
+    CTR_SELECTED = 7,      // ... the same slot as the selection count of detach / export: k_select_scan writes it, the host reads and clears it
+    CTR_TOT_NEW = 8, CTR_TOT_DELETED = 9, CTR_TOT_UPDATED = 10, CTR_TOT_KF = 11, CTR_TOT_BEFORE = 12,   // running totals: new, deleted, updated, keyframes, live-before
+    CTR_WIDE = 13,         // wide-record flags (MapSoA::wideFlag)
+    CTR_COUNT = 16         // what the host reads back (14, 15: unused)
+};
+
 // Device-resident surfel map, split hot/cold.  The fuse kernel streams only the hot records (what decides a surfel's fate for the ones that
 // leave early) and touches the cold record of those it updates.
 // Hot record, 16 bytes (round 5; 20 bytes before): position + ONE word for updateTimes / lastUpdate, so that a record is one aligned
@@ -71,7 +91,7 @@ struct MapSoA {
     ColdRec *cold;         // [cap]
     int *rgbWide;          // [cap][3]
     int *utlWide;          // [cap][2]
-    long long *wideFlag;   // ctr[13]: bit 0 set once any COLD_WIDE record has been stored, bit 1 once any HOT_WIDE one (map copies then carry the side arrays along)
+    long long *wideFlag;   // &ctr[CTR_WIDE]: bit 0 set once any COLD_WIDE record has been stored, bit 1 once any HOT_WIDE one (map copies then carry the side arrays along)
 };
 __host__ __device__ inline bool rgb_fits(int r, int g, int b) { return ((unsigned)r | (unsigned)g | (unsigned)b) < 256u; }
 __host__ __device__ inline unsigned rgb_pack(int r, int g, int b) { return (unsigned)r | ((unsigned)g << 8) | ((unsigned)b << 16); }
@@ -145,9 +165,7 @@ struct SfDev {
     int *changed;                // [slots][8]
     MapSoA map;
     unsigned long long cap;
-    // ctr[0]=n_live  [1]=K new (last)  [2]=D deleted (last)  [3]=updated (last)  [4]=n before (last)  [5]=err  [6]=n after (last)  [7]=tail fallback flag
-    // ctr[8..12] = running totals: new, deleted, updated, keyframes, live-before   ctr[13] = wide-record flags
-    long long *ctr;
+    long long *ctr;              // [CTR_COUNT] the map's counters (enum SfCtr)
     msl_surfel *newSurfels;
     unsigned *blockSums, *blockUpd, *delList, *srcOf;
     // Dealing of the sub-blocks to the XCDs by SCREEN position (round 6; msl_sf_compact.hip, deal_subblocks): every k_fuse wave leaves the screen key of
@@ -271,7 +289,7 @@ __device__ __forceinline__ bool xcd_slot(int blocksPerFrame, int nSlots, int &sl
 #endif
 inline unsigned xcd_grid(int blocksPerFrame, int nSlots) { return 8u * (unsigned)((nSlots + 7) / 8) * (unsigned)blocksPerFrame; }
 
-// Kernel ids of the event profiler (msl_sf_profile_*; names in msl_surfel.hip)
+// Kernel ids of the event profiler (msl_sf_profile_*; names in msl_sf_debug.hip)
 enum { SK_SEED_INIT = 0, SK_ASSIGN, SK_PROP, SK_COMMIT_PX, SK_UPDATE_SEEDS, SK_COMMIT_SEEDS, SK_SEED_PLANE, SK_FUSE, SK_NEW, SK_COMPACT,
        SK_CONVERT, SK_COPY };
 

@@ -212,8 +212,8 @@ __global__ __launch_bounds__(256) void k_compact(CompactArgs P, int mode) {
     static_assert(LIST_D == NT, "one hand-over entry per thread");
     const unsigned du = P.delU[threadIdx.x];
     const unsigned dHand = *P.delUCount;   // k_fuse's running total of deleted slots = D of this keyframe
-    const long long n = P.ctr[0];
-    const bool bad = P.ctr[5] == 20;
+    const long long n = P.ctr[CTR_LIVE];
+    const bool bad = P.ctr[CTR_ERR] == 20;
     const uint8_t *candOk = P.candOk, *fused = P.fused;
     const int per = (((P.nseeds + NT - 1) / NT) + 3) & ~3;      // seeds per thread, multiple of 4: aligned 32-bit flag loads
     const int s0 = threadIdx.x * per, s1 = min(s0 + per, P.nseeds);
@@ -398,11 +398,11 @@ __global__ __launch_bounds__(256) void k_compact(CompactArgs P, int mode) {
     }
     __syncthreads();   // s_upd complete; new-surfel stores ordered before the tail moves below (same workgroup)
     if (threadIdx.x == 0) {
-        P.ctr[1] = K; P.ctr[2] = D; P.ctr[3] = s_upd; P.ctr[4] = n; P.ctr[6] = nAfter;
+        P.ctr[CTR_NEW] = K; P.ctr[CTR_DELETED] = D; P.ctr[CTR_UPDATED] = s_upd; P.ctr[CTR_BEFORE] = n; P.ctr[CTR_AFTER] = nAfter;
         // running totals over all keyframes of this handle (one writer per launch, launches are ordered): bench.py derives the
         // per-keyframe averages of a timed region from their differences
-        P.ctr[8] += K; P.ctr[9] += D; P.ctr[10] += s_upd; P.ctr[11] += 1; P.ctr[12] += n;
-        if ((unsigned long long)nAfter > P.cap) P.ctr[5] = 20;  // capacity exceeded
+        P.ctr[CTR_TOT_NEW] += K; P.ctr[CTR_TOT_DELETED] += D; P.ctr[CTR_TOT_UPDATED] += s_upd; P.ctr[CTR_TOT_KF] += 1; P.ctr[CTR_TOT_BEFORE] += n;
+        if ((unsigned long long)nAfter > P.cap) P.ctr[CTR_ERR] = 20;  // capacity exceeded
     }
     if (!place) { if (threadIdx.x == 0) *P.delUCount = 0; return; }   // (host-vector mode, or the deferred capacity error: the live count stays)
     const long long t0 = threadIdx.x, stride = blockDim.x;
@@ -436,7 +436,7 @@ __global__ __launch_bounds__(256) void k_compact(CompactArgs P, int mode) {
             for (long long a = t0; a < cntLow; a += stride) move_surfel(P.map, (long long)DL(a), (long long)P.srcOf[a]);
         }
     }
-    if (threadIdx.x == 0) { P.ctr[0] = nAfter; *P.delUCount = 0; }   // publish the new live count, re-arm the hand-over list
+    if (threadIdx.x == 0) { P.ctr[CTR_LIVE] = nAfter; *P.delUCount = 0; }   // publish the new live count, re-arm the hand-over list
 }
 }  // namespace
 

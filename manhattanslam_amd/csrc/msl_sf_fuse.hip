@@ -51,7 +51,7 @@ __device__ __forceinline__ void fuse_body(const FuseArgs &P, const FuseFrame &F,
     long long E0 = 0;
     if (DEFER && spawnWave) E0 = ((long long)__builtin_amdgcn_readfirstlane((int)(E0v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)E0v);
     if (spawnWave && !pending) return;   // (the first keyframe of a window has nothing to materialise)
-    if (DEFER && !pending && waveIdx == 0 && lane0 == 0) P.dc->ext[0] = P.ctr[0];
+    if (DEFER && !pending && waveIdx == 0 && lane0 == 0) P.dc->ext[0] = P.ctr[CTR_LIVE];
     if (DEFER && !spawnWave && waveIdx == 0 && lane0 == 0) P.dc->logBase[P.kf] = P.kf > 0 ? P.dc->logBase[P.kf - 1] + P.dc->delCnt[P.kf - 1] : 0u;   // where this keyframe's log entries start
     // The spawn wave (deferred, one per launch, dispatched first): the new surfels of keyframe kf - 1 go to the physical slots E0, E0 + 1, ...; this
     // wave counts them (one trip over the lattice's flag words), publishes the extent for the next launch, and -- only if there are any -- writes
@@ -119,14 +119,14 @@ __device__ __forceinline__ void fuse_body(const FuseArgs &P, const FuseFrame &F,
                     E0 = ((long long)__builtin_amdgcn_readfirstlane((int)(E0v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)E0v);
                     if (c0 >= E0) return;
                 }
-            } else if (sb >= nSubHint && c0 >= __hip_atomic_load(&P.ctr[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+            } else if (sb >= nSubHint && c0 >= __hip_atomic_load(&P.ctr[CTR_LIVE], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
         }
         // lane l owns records l, 64 + l, 128 + l, 192 + l of the sub-block: the survivors' rank order (k, lane) is then the array order, so
         // neighbouring lanes of phase B work on neighbouring records and their gathers and stores share cache lines
         HotPk hq[KPL];
 #pragma unroll
         for (int k = 0; k < KPL; k++) hq[k] = M.hot[c0 + REC_LOCAL(k)];
-        if (!pending) n = P.ctr[0];
+        if (!pending) n = P.ctr[CTR_LIVE];
         else if (!spawnWave) {
             E0 = ((long long)__builtin_amdgcn_readfirstlane((int)(E0v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)E0v);
             if (c0 >= E0) return;

@@ -12,7 +12,7 @@ __device__ __forceinline__ bool select_pred(const HotRec &h, int mode, int arg) 
 }
 __global__ __launch_bounds__(256) void k_select_count(SfDev P, int mode, int arg) {
     __shared__ unsigned s_c;
-    const long long n = P.ctr[0];
+    const long long n = P.ctr[CTR_LIVE];
     const long long nblk = (n + SCAN_ITEMS - 1) / SCAN_ITEMS;
     for (long long b = blockIdx.x; b < nblk; b += gridDim.x) {
         if (threadIdx.x == 0) s_c = 0;
@@ -28,9 +28,9 @@ __global__ __launch_bounds__(256) void k_select_count(SfDev P, int mode, int arg
         __syncthreads();
     }
 }
-__global__ __launch_bounds__(1024) void k_select_scan(SfDev P) {   // one workgroup: exclusive scan of the chunk counts, total -> ctr[7]
+__global__ __launch_bounds__(1024) void k_select_scan(SfDev P) {   // one workgroup: exclusive scan of the chunk counts, total -> CTR_SELECTED
     __shared__ unsigned s_wave[17];
-    const long long n = P.ctr[0];
+    const long long n = P.ctr[CTR_LIVE];
     const int nblk = (int)((n + SCAN_ITEMS - 1) / SCAN_ITEMS);
     unsigned carry = 0;
     for (int b0 = 0; b0 < nblk; b0 += 1024) {
@@ -41,11 +41,11 @@ __global__ __launch_bounds__(1024) void k_select_scan(SfDev P) {   // one workgr
         if (b < nblk) P.blockSums[b] = ex;
         carry += tot;
     }
-    if (threadIdx.x == 0) P.ctr[7] = carry;
+    if (threadIdx.x == 0) P.ctr[CTR_SELECTED] = carry;
 }
 __global__ __launch_bounds__(256) void k_select_write(SfDev P, int mode, int arg, msl_surfel *out, int markDeleted) {
     __shared__ unsigned s_wave[17];
-    const long long n = P.ctr[0];
+    const long long n = P.ctr[CTR_LIVE];
     const long long nblk = (n + SCAN_ITEMS - 1) / SCAN_ITEMS;
     for (long long b = blockIdx.x; b < nblk; b += gridDim.x) {
         unsigned base = P.blockSums[b];
@@ -68,11 +68,11 @@ __global__ __launch_bounds__(256) void k_select_write(SfDev P, int mode, int arg
     }
 }
 __global__ void k_add_ctr(long long *ctr, long long add) {
-    if (threadIdx.x == 0) { ctr[0] += add; ctr[4] = ctr[0]; ctr[6] = ctr[0]; }
+    if (threadIdx.x == 0) { ctr[CTR_LIVE] += add; ctr[CTR_BEFORE] = ctr[CTR_LIVE]; ctr[CTR_AFTER] = ctr[CTR_LIVE]; }
 }
 __global__ __launch_bounds__(256) void k_aos_to_soa_at(MapSoA M, const msl_surfel *src, long long n, const long long *ctr) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) store_surfel(M, ctr[0] + i, src[i]);
+    if (i < n) store_surfel(M, ctr[CTR_LIVE] + i, src[i]);
 }
 
 // AoS <-> SoA conversion for upload / download / host-vector mode
@@ -88,12 +88,12 @@ __global__ __launch_bounds__(256) void k_soa_to_aos(MapSoA M, msl_surfel *dst, l
     load_surfel(M, i, h, e);
     dst[i] = e;
 }
-// wide: -1 = leave the wide-record flags ctr[13] alone (upload: k_aos_to_soa has just set them if needed), otherwise the restored snapshot's flags
+// wide: -1 = leave the wide-record flags (CTR_WIDE) alone (upload: k_aos_to_soa has just set them if needed), otherwise the restored snapshot's flags
 __global__ void k_set_ctr(long long *ctr, long long n, unsigned *delUCount, int wide) {
     if (threadIdx.x == 0) {
         delUCount[0] = 0;
-        ctr[0] = n; ctr[1] = 0; ctr[2] = 0; ctr[3] = 0; ctr[4] = n; ctr[6] = n; ctr[7] = 0;
-        if (wide >= 0) ctr[13] = wide;
+        ctr[CTR_LIVE] = n; ctr[CTR_NEW] = 0; ctr[CTR_DELETED] = 0; ctr[CTR_UPDATED] = 0; ctr[CTR_BEFORE] = n; ctr[CTR_AFTER] = n; ctr[CTR_TAIL_FLAG] = 0;
+        if (wide >= 0) ctr[CTR_WIDE] = wide;
     }
 }
 

@@ -264,7 +264,7 @@ __device__ __forceinline__ void emit_records(const FuseArgs &P, long long E0, lo
         }
         if (on && seed >= 0) {
             if ((unsigned long long)i < dc->aux.cap) store_surfel(dc->aux.map, i, cand[seed]);
-            else { long long code = 20; asm volatile("" : "+v"(code)); P.ctr[5] = code; }   // capacity exceeded (the host reserves nseeds slots per keyframe: never
+            else { long long code = 20; asm volatile("" : "+v"(code)); P.ctr[CTR_ERR] = code; }   // capacity exceeded (the host reserves nseeds slots per keyframe: never
                                                                                           // happens; the constant is kept out of the loop-invariant registers)
         }
     }

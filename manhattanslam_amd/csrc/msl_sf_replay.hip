@@ -8,7 +8,7 @@ namespace {
 // Deferred compaction: the end of a window
 // =============================================================================================
 // k_defer_tail: what is left to do per keyframe once the window's F fuse launches are through.
-//   workgroups 0 .. F - 1          : the updated-surfel count of keyframe f (sum of its per-sub-block counts) -> running total, ctr[3] for the last
+//   workgroups 0 .. F - 1          : the updated-surfel count of keyframe f (sum of its per-sub-block counts) -> running total, CTR_UPDATED for the last
 //   workgroups F .. F + NFRONT - 1 : the new surfels of the LAST keyframe (there is no next fuse launch to materialise them)
 __global__ __launch_bounds__(64) void k_defer_tail(SfDev P, FuseArgs A, int F, unsigned blkStride) {   // A.kf = F
     __builtin_amdgcn_s_setprio(3);
@@ -25,8 +25,8 @@ __global__ __launch_bounds__(64) void k_defer_tail(SfDev P, FuseArgs A, int F, u
         for (long long b = x0 + lane; b < x1; b += 64) u += bu[b];
         u = wave_incl_scan(u);
         if (lane == 63) {
-            atomicAdd(reinterpret_cast<unsigned long long *>(&P.ctr[10]), (unsigned long long)u);
-            if (f == F - 1) P.ctr[3] = u;
+            atomicAdd(reinterpret_cast<unsigned long long *>(&P.ctr[CTR_TOT_UPDATED]), (unsigned long long)u);
+            if (f == F - 1) P.ctr[CTR_UPDATED] = u;
         }
         return;
     }
@@ -299,8 +299,8 @@ __device__ __forceinline__ void replay_body(const SfDev &P, int F, ReplayLds &S)
     if (lane < DEFER_WIN) dc->delCnt[lane] = 0;   // the next window starts with empty logs
     if (lane == 0) {
         dc->nMoves = nMoves;
-        P.ctr[0] = nF; P.ctr[1] = lastK; P.ctr[2] = lastD; P.ctr[4] = lastNb; P.ctr[6] = nF;
-        P.ctr[8] += totK; P.ctr[9] += totD; P.ctr[11] += F; P.ctr[12] += totNb;
+        P.ctr[CTR_LIVE] = nF; P.ctr[CTR_NEW] = lastK; P.ctr[CTR_DELETED] = lastD; P.ctr[CTR_BEFORE] = lastNb; P.ctr[CTR_AFTER] = nF;
+        P.ctr[CTR_TOT_NEW] += totK; P.ctr[CTR_TOT_DELETED] += totD; P.ctr[CTR_TOT_KF] += F; P.ctr[CTR_TOT_BEFORE] += totNb;
     }
 }
 

@@ -1,4 +1,5 @@
-// msl_surfel.hip -- surfel fusion for gfx950 (MI355X): the handle, streams and batching, and the C ABI.
+// msl_surfel.hip -- surfel fusion for gfx950 (MI355X): the handle's lifecycle and streams, slot allocation and image staging, the batch driver,
+// the resident entry points and the profiler calls (the other host units: msl_sf_handle.h).
 //
 // Replaces SurfelFusion (reference src/SurfelFusion.cpp) and the slot refill / tail compaction of
 // SurfelMapping::fuseMap (src/SurfelMapping.cpp:353-392).  The kernels live in other translation units:
@@ -11,125 +12,15 @@
 //                           caller-provided stream under low churn, classic otherwise (a handle with its own two streams: always classic);
 // the two stages overlap across batches (double-buffered slot sets).
 
-#include "msl_sf.h"
+#include "msl_sf_handle.h"
 
 #include <algorithm>
-#include <cmath>
 #include <cstdlib>
-#include <fstream>
 #include <memory>
-#include <new>
 #include <vector>
 
-using namespace msl;
-using namespace msl::sf;
-
-namespace {
-const char *kSfNames[MSL_SF_NKERNELS] = {"kb_seed_init", "kb_assign", "kb_prop", "kb_commit_px", "kb_update_seeds", "kb_commit_seeds",
-                                         "kb_seed_plane", "k_fuse", "k_empty", "k_compact", "k_convert", "copy"};
-}  // namespace
-
-struct msl_sf {
-    int device = 0;
-    SfDev dev{};
-    int maxBatch = 1;              // keyframes per batch; slots = 2 * maxBatch (double-buffered sets)
-    hipStream_t preStream = nullptr, mapStream = nullptr; bool ownStreams = true;
-    size_t blkStride = 0;          // entries per per-sub-block count slice (blockSums: one slice; blockUpd: DEFER_WIN slices, one per keyframe of a window)
-    unsigned long long kfClassic = 0, kfDeferred = 0;   // keyframes that went through the classic pair of launches / through deferred windows (msl_sf_debug_scratch, which = 5)
-    int dealG = 0;                 // the k_fuse grid SfDev::deal currently is a permutation for (0: none yet) -- screen-position dealing, msl_sf_compact.hip
-    hipStream_t copyStream = nullptr;   // host-image mode: the H2D copies of slot set i + 1 run beside the superpixel kernels of set i
-    // Synchronisation state of one of the two slot sets.  h2d: the set's staged images have arrived (recorded by every host-image batch; msl_sf_staged_gray
-    // hands it to other handles); pre / map: the set's last superpixel stage / map stage is done; copy: its pinned FrameDev staging has been read
-    struct SlotSet { hipEvent_t h2d = nullptr, pre = nullptr, map = nullptr, copy = nullptr; bool preValid = false, mapValid = false, copyValid = false; } sets[2];
-    unsigned long long batchNo = 0;
-    int stagedSet = -1; size_t stagedGs = 0;   // slot set / row stride of the gray images the last host-image batch staged (msl_sf_staged_gray); -1: none
-    int lastSlot = 0;
-    // One image kind of host-image calls, staged per slot: 2 * maxBatch slots of `stride` bytes each
-    struct ImageSlots {
-        DevBuf buf; size_t stride = 0;
-        uint8_t *at(size_t slot) const { return (uint8_t *)buf.p + slot * stride; }
-    };
-    // The slot set, allocated to exactly 2 * maxBatch slots by alloc_slots: the per-slot arrays behind SfDev's bases, the pinned FrameDev staging,
-    // and the images of host-image calls (allocated by the first such call; depth16: the raw 16-bit depth of msl_sf_fuse_resident_batch_d16)
-    struct Slots {
-        DevBuf frames, seeds, seedsTmp, cand, candOk, fused, tex, fuseRec, index, amap, tmin, arec, pxInv, wl, wlCount, chunkAbort, changed;
-        PinBuf hFrames;
-        ImageSlots gray, depth, member, depth16;
-    } slot;
-    DevBuf d_ctr; PinBuf h_ctr;
-    DevBuf d_tickets, d_delU, d_dc, d_projTab;
-    bool propLds = false;        // t(s) of one keyframe fits the LDS: single-launch relaxation
-    bool classicNext = true;     // the map was replaced from outside the keyframe chain (upload / restore / append / detach): its first keyframe takes the classic
-                                 // pair of launches, whose compaction handles any number of stale or deleted slots at full speed
-    DevBuf d_new;
-    // The resident map, replaced as a whole by map_realloc (layout: set_map_ptrs; its capacity in surfels: dev.cap).  rp: deferred compaction's
-    // move lists, dense replay tables and staging
-    struct MapBufs { DevBuf store, blockSums, blockUpd, delList, srcOf, rp; } map;
-    size_t liveBound = 0;        // host-side upper bound of the live count: last known count + nseeds per keyframe enqueued since
-    size_t liveKnown = 0;        // the most recent live count the host has seen (exact at that time; only a hint for k_fuse's speculative loads)
-    unsigned long long liveKnownKf = 0;   // ... and the number of keyframes that had been enqueued when it was exact: an older snapshot never replaces a newer one
-    // asynchronous refresh of that bound: after every batch the live count is copied to pinned memory behind an event; a later call picks
-    // up whatever has arrived, so the bound follows the real count a couple of batches late instead of forcing a pipeline drain
-    // every capacity / nseeds keyframes
-    static constexpr int NSNAP = 4;
-    static constexpr int SNAPW = 16;   // counters per snapshot: ctr[0 .. 15]
-    PinBuf h_snap; hipEvent_t snapEv[NSNAP] = {}; unsigned long long snapKf[NSNAP] = {}; bool snapBusy[NSNAP] = {};
-    bool snapLive[NSNAP] = {};   // the snapshot's live count still describes the resident map (no upload / restore since it was taken)
-    unsigned long long kfEnq = 0; int snapNext = 0;
-    // churn = surfels spawned + deleted per keyframe over the most recent batch the host has seen (from the running totals of two snapshots):
-    // the deferred compaction is built for the steady state (a replay by ONE wave per window); under heavy churn the classic chain, whose
-    // compaction works with all its workgroups, is faster
-    long long churnNew = -1, churnDel = 0, churnKf = 0; unsigned long long churnAt = 0; double churn = 0.0;
-    DevBuf d_aos;
-    DevBuf d_snapStore; size_t snapN = 0; bool snapValid = false; long long snapWide = 0;   // msl_sf_map_snapshot / _restore (same layout as the map store)
-    // host-vector mode (msl_sf_fuse_ex): the device map equals the caller's vector as the last call left it
-    bool mirrorValid = false; size_t mirrorN = 0;
-    PinBuf h_blk;    // per-sub-block deleted / updated counts of the call's k_fuse launch: two halves of h_blk.cap / 8 entries
-    PinBuf h_list;   // {count | indices | records} of the sparse download
-    KernelProfiler prof;
-};
-
-namespace {
-
-// Map storage, in 4-byte words per surfel of capacity c (c is a multiple of 4096, so every array starts 32-byte aligned).  Each array's word
-// offset is the one before it plus that one's record; array X of a store laid out for c surfels starts at word X * c.
-//   map.store: hot | cold | rgbWide (3 ints) | utlWide (2 ints)
-//   map.rp   : loc64 (first: 8-byte aligned) | stageCold | stageHot | moveDst | vposD | locKeys | vposKeys | dBig | stageRgb | stageUtl | bitmap c / 32 + 64
-constexpr size_t HOT_W = sizeof(HotPk) / 4, COLD_W = sizeof(ColdRec) / 4;
-constexpr size_t ST_HOT = 0, ST_COLD = ST_HOT + HOT_W, ST_RGB = ST_COLD + COLD_W, ST_UTL = ST_RGB + 3, MAP_WORDS = ST_UTL + 2;
-constexpr size_t RP_LOC64 = 0, RP_STAGE_COLD = RP_LOC64 + 2, RP_STAGE_HOT = RP_STAGE_COLD + COLD_W, RP_MOVE_DST = RP_STAGE_HOT + HOT_W, RP_VPOS_D = RP_MOVE_DST + 1,
-                 RP_LOC_KEYS = RP_VPOS_D + 1, RP_VPOS_KEYS = RP_LOC_KEYS + 1, RP_DBIG = RP_VPOS_KEYS + 1, RP_STAGE_RGB = RP_DBIG + 1, RP_STAGE_UTL = RP_STAGE_RGB + 3,
-                 RP_BITMAP = RP_STAGE_UTL + 2, RP_WORDS = RP_BITMAP;   // (the bitmap is not per surfel: it follows the RP_WORDS * c words of the others)
-constexpr size_t rp_bitmap_words(size_t c) { return c / 32 + 64; }
-static_assert(ST_HOT == 0 && ST_COLD == 4 && ST_RGB == 12 && ST_UTL == 15 && MAP_WORDS == 17, "layout of map.store");
-static_assert(RP_LOC64 == 0 && RP_STAGE_COLD == 2 && RP_STAGE_HOT == 10 && RP_MOVE_DST == 14 && RP_VPOS_D == 15 && RP_LOC_KEYS == 16 && RP_VPOS_KEYS == 17 &&
-              RP_DBIG == 18 && RP_STAGE_RGB == 19 && RP_STAGE_UTL == 22 && RP_BITMAP == 24 && RP_WORDS == 24, "layout of map.rp");
-void set_map_ptrs(msl_sf *h, size_t c) {
-    MapSoA &M = h->dev.map;
-    float *store = (float *)h->map.store.p;
-    M.hot = reinterpret_cast<HotPk *>(store + ST_HOT * c);
-    M.cold = reinterpret_cast<ColdRec *>(store + ST_COLD * c);
-    M.rgbWide = reinterpret_cast<int *>(store + ST_RGB * c);    // exact ints of the COLD_WIDE records (untouched otherwise)
-    M.utlWide = reinterpret_cast<int *>(store + ST_UTL * c);    // exact ints of the HOT_WIDE records
-    M.wideFlag = h->dev.ctr + 13;
-    SfDev &D = h->dev;
-    D.cap = c;
-    D.blockSums = (unsigned *)h->map.blockSums.p; D.blockUpd = (unsigned *)h->map.blockUpd.p; D.delList = (unsigned *)h->map.delList.p; D.srcOf = (unsigned *)h->map.srcOf.p;
-    D.sbKeys = D.blockSums + h->blkStride; D.deal = D.blockSums + 2 * h->blkStride; D.dealG = 0;   // (three planes of one allocation: counts, screen keys, dealing table)
-    unsigned *r = (unsigned *)h->map.rp.p;
-    D.loc64 = reinterpret_cast<unsigned long long *>(r + RP_LOC64 * c);
-    D.stageCold = reinterpret_cast<ColdRec *>(r + RP_STAGE_COLD * c);
-    D.stageHot = reinterpret_cast<HotPk *>(r + RP_STAGE_HOT * c);
-    D.moveDst = r + RP_MOVE_DST * c; D.vposD = r + RP_VPOS_D * c; D.locKeys = r + RP_LOC_KEYS * c; D.vposKeys = r + RP_VPOS_KEYS * c; D.dBig = r + RP_DBIG * c;
-    D.stageRgb = reinterpret_cast<int *>(r + RP_STAGE_RGB * c); D.stageUtl = reinterpret_cast<int *>(r + RP_STAGE_UTL * c);
-    D.bitmap = r + RP_BITMAP * c;
-}
-
-// The asynchronous live-count snapshots only ever LOWER liveBound; whenever the map is replaced from outside the keyframe chain
-// (upload, restore) the ones still pending describe the old map and must be ignored.
-void drop_live_snapshots(msl_sf *h) {
-    for (int i = 0; i < msl_sf::NSNAP; i++) h->snapLive[i] = false;   // (their running totals -- the churn estimate -- stay valid)
-}
+namespace msl {
+namespace sf {
 
 int sync_all(msl_sf *h) {
     if (h->ownStreams && h->copyStream) MSL_HIP_TRY(hipStreamSynchronize(h->copyStream));
@@ -138,57 +29,6 @@ int sync_all(msl_sf *h) {
     return MSL_OK;
 }
 
-// The device-side control block of the map stage: bases of the slot arrays and of the map's side arrays / lists (what only a few waves of a
-// k_fuse launch read).  Rewritten whenever one of them is reallocated; the streams are idle then, and the window state it also holds
-// (extents, deletion counts) is all zero between windows.
-int write_ctl(msl_sf *h) {
-    DeferCtl dc;
-    memset(&dc, 0, sizeof(dc));
-    const SfDev &D = h->dev;
-    dc.flagStride = D.flagStride; dc.candOk = D.candOk; dc.fused = D.fused; dc.cand = D.cand;
-    dc.aux.map = D.map; dc.aux.cap = D.cap; dc.aux.delU = D.delU; dc.aux.delUCount = D.delUCount; dc.aux.delList = D.delList;
-    MSL_HIP_TRY(hipMemcpy(D.dc, &dc, sizeof(dc), hipMemcpyHostToDevice));
-    return MSL_OK;
-}
-
-// (Re)allocate the resident map for `cap` surfels, preserving the first `keep` entries.  The new set is built beside the old one: a failed
-// attempt frees itself and leaves the old map untouched.
-int map_realloc(msl_sf *h, size_t cap, size_t keep) {
-    cap = (cap + 4095) & ~(size_t)4095;
-    const size_t bst = cap / SUB_ITEMS + 8200;   // per slice; >= 1024 / 8192 padding entries: the compaction reads its first tiles unconditionally
-    const size_t rpWords = RP_WORDS * cap + rp_bitmap_words(cap);
-    msl_sf::MapBufs m;
-    MSL_HIP_TRY(grow_all(h->mapStream, {{m.store, sizeof(float) * MAP_WORDS * cap},
-                                        {m.blockSums, sizeof(unsigned) * 3 * bst},           // deleted counts | screen keys | dealing table (SfDev::sbKeys, ::deal)
-                                        {m.blockUpd, sizeof(unsigned) * DEFER_WIN * bst},    // one slice per keyframe of a deferred window (classic: the first)
-                                        {m.delList, sizeof(unsigned) * cap}, {m.srcOf, sizeof(unsigned) * cap}, {m.rp, sizeof(unsigned) * rpWords}}));
-    unsigned *nbs = (unsigned *)m.blockSums.p, *nrp = (unsigned *)m.rp.p;
-    MSL_HIP_TRY(hipMemset(nbs, 0, sizeof(unsigned) * bst));
-    MSL_HIP_TRY(hipMemset(nbs + bst, 0xFF, sizeof(unsigned) * bst));    // no key yet: "nothing in view"
-    MSL_HIP_TRY(hipMemset(m.blockUpd.p, 0, sizeof(unsigned) * DEFER_WIN * bst));
-    MSL_HIP_TRY(hipMemset(nrp + RP_LOC64 * cap, 0, sizeof(unsigned long long) * cap));         // loc64: empty (the replay leaves it clean)
-    MSL_HIP_TRY(hipMemset(nrp + RP_VPOS_D * cap, 0, sizeof(unsigned) * cap));                  // vposD
-    MSL_HIP_TRY(hipMemset(nrp + RP_BITMAP * cap, 0, sizeof(unsigned) * rp_bitmap_words(cap))); // bitmap
-    if (keep && h->map.store.p) {
-        const int rc = sync_all(h);
-        if (rc != MSL_OK) return rc;
-        const size_t oc = h->dev.cap;
-        float *nstore = (float *)m.store.p;
-        const float *ostore = (const float *)h->map.store.p;
-        MSL_HIP_TRY(hipMemcpy(nstore + ST_HOT * cap, ostore + ST_HOT * oc, sizeof(HotPk) * keep, hipMemcpyDeviceToDevice));
-        MSL_HIP_TRY(hipMemcpy(nstore + ST_COLD * cap, ostore + ST_COLD * oc, sizeof(ColdRec) * keep, hipMemcpyDeviceToDevice));
-        MSL_HIP_TRY(hipMemcpy(nstore + ST_RGB * cap, ostore + ST_RGB * oc, sizeof(int) * 3 * keep, hipMemcpyDeviceToDevice));   // (rare path: no need to know whether any record is wide)
-        MSL_HIP_TRY(hipMemcpy(nstore + ST_UTL * cap, ostore + ST_UTL * oc, sizeof(int) * 2 * keep, hipMemcpyDeviceToDevice));
-    }
-    h->map = std::move(m);
-    h->blkStride = bst;
-    h->dealG = 0;              // (the dealing table went with the old allocation)
-    set_map_ptrs(h, cap);
-    return write_ctl(h);
-}
-
-// The staged gray, depth and member images go together (a later host-image call allocates all three anew), and msl_sf_staged_gray has
-// nothing to hand out until that call has run.  Every path that frees them comes through here.
 void release_staged_images(msl_sf *h) {
     msl_sf::Slots &S = h->slot;
     S.gray = msl_sf::ImageSlots(); S.depth = msl_sf::ImageSlots(); S.member = msl_sf::ImageSlots();
@@ -228,57 +68,7 @@ int alloc_slots(msl_sf *h, int maxBatch) {
     return MSL_OK;
 }
 
-// Counter snapshots that have arrived (their event has fired): a tighter bound / a fresher value of the live count, and the churn estimate -- spawned +
-// deleted surfels per keyframe between two snapshots, from the running totals.
-void consume_snapshots(msl_sf *h, size_t nseeds) {
-    for (int i = 0; i < msl_sf::NSNAP; i++)
-        if (h->snapBusy[i] && hipEventQuery(h->snapEv[i]) == hipSuccess) {
-            h->snapBusy[i] = false;
-            const long long *sn = (const long long *)h->h_snap.p + (size_t)i * msl_sf::SNAPW;
-            if (h->snapLive[i]) {
-                const size_t cand = (size_t)sn[0] + (size_t)(h->kfEnq - h->snapKf[i]) * nseeds;   // count then + what was enqueued since
-                if (cand < h->liveBound) h->liveBound = cand;
-                if (h->snapKf[i] >= h->liveKnownKf) { h->liveKnown = (size_t)sn[0]; h->liveKnownKf = h->snapKf[i]; }   // completed snapshots are visited in array order, not age order
-            }
-            if (h->snapKf[i] > h->churnAt) {   // running totals: new ctr[8], deleted ctr[9], keyframes ctr[11]
-                if (h->churnNew >= 0 && sn[11] > h->churnKf) h->churn = (double)((sn[8] - h->churnNew) + (sn[9] - h->churnDel)) / (double)(sn[11] - h->churnKf);
-                h->churnNew = sn[8]; h->churnDel = sn[9]; h->churnKf = sn[11]; h->churnAt = h->snapKf[i];
-            }
-        }
-}
-
-int read_ctr(msl_sf *h) {
-    if (h->ownStreams && h->copyStream) MSL_HIP_TRY(hipStreamSynchronize(h->copyStream));
-    MSL_HIP_TRY(hipStreamSynchronize(h->preStream));
-    MSL_HIP_TRY(hipMemcpyAsync(h->h_ctr.p, h->dev.ctr, sizeof(long long) * 16, hipMemcpyDeviceToHost, h->mapStream));
-    MSL_HIP_TRY(hipStreamSynchronize(h->mapStream));
-    h->prof.drain();
-    consume_snapshots(h, (size_t)h->dev.nseeds);   // (all pending snapshots have arrived: their churn information is kept, the live count below is newer)
-    h->liveBound = (size_t)((const long long *)h->h_ctr.p)[0];   // both streams are idle: the count is exact
-    h->liveKnown = h->liveBound; h->liveKnownKf = h->kfEnq;
-    for (int i = 0; i < msl_sf::NSNAP; i++) h->snapBusy[i] = false;   // (their events have fired: the stream is idle)
-    return MSL_OK;
-}
-
-int check_err(msl_sf *h) {
-    const long long e = ((const long long *)h->h_ctr.p)[5];
-    if (e) {
-        (void)hipMemsetAsync(h->dev.ctr + 5, 0, sizeof(long long), h->mapStream);
-        if (e == 20) set_error("resident surfel map capacity exceeded (reserve more with msl_sf_map_reserve)");
-        else set_error("surfel pipeline device-side bound exceeded (code %lld)", e);
-        return MSL_ERR_OVERFLOW;
-    }
-    return MSL_OK;
-}
-// The images of one batch as the caller handed them over.  Per kind: base pointer, row stride and frame stride in bytes, and (from check_images) the
-// bytes actually present in one image -- the last row carries no stride padding.
-struct ImageArg { const void *p = nullptr; size_t row = 0, frame = 0, bytes = 0; };
-struct BatchImages {
-    ImageArg gray, depth, depth16, member;   // (a frame stride left out is 0: one keyframe)
-    msl_mem mem = MSL_MEM_HOST; float depthFactor = 1.0f;
-    // the depth images are raw 16-bit values that become metres on the device, (float)raw * depthFactor (src/Frame.cc:96-97); `depth` is ignored then
-    bool d16() const { return depth16.p != nullptr; }
-};
+namespace {
 
 int check_images(const msl_sf *h, int n, const int32_t *refs, const float *poses, BatchImages &I) {
     const size_t W = (size_t)h->dev.W, H = (size_t)h->dev.H;
@@ -299,29 +89,6 @@ int check_images(const msl_sf *h, int n, const int32_t *refs, const float *poses
     g.bytes = g.row * (H - 1) + W; d.bytes = d.row * (H - 1) + W * 4;
     m.bytes = m.row * ((H + 1) / 2 - 1) + ((W + 1) / 2) * 4;   // the membership image is ceil(H / 2) x ceil(W / 2) (PlaneDetection's cloud size)
     r.bytes = I.d16() ? r.row * (H - 1) + W * 2 : 0;
-    return MSL_OK;
-}
-
-// Room in the resident map for n more keyframes.  The reference's mvLocalSurfels is an unbounded std::vector (include/Map.h:130): grow the resident
-// map before a batch could overflow it.  Every keyframe adds at most nseeds surfels, so the host only needs an upper bound of the live count; the
-// exact count is read back (one sync) only when that bound reaches the capacity.
-int reserve_map(msl_sf *h, int n) {
-    const SfDev &D = h->dev;
-    h->mirrorValid = false;   // the resident map moves on without the host-vector caller
-    const size_t need = (size_t)n * (size_t)D.nseeds;
-    consume_snapshots(h, (size_t)D.nseeds);
-    if (h->liveBound + need > D.cap) {
-        int rc = read_ctr(h);
-        if (rc != MSL_OK) return rc;
-        rc = check_err(h);
-        if (rc != MSL_OK) return rc;
-        if (h->liveBound + need > D.cap) {
-            rc = map_realloc(h, 2 * h->liveBound + 2 * need + 65536, h->liveBound);
-            if (rc != MSL_OK) return rc;
-        }
-    }
-    h->liveBound += need;
-    h->kfEnq += (unsigned long long)n;
     return MSL_OK;
 }
 
@@ -537,8 +304,8 @@ int launch_map_chain(msl_sf *h, SfDev &P, int set, int n, bool compact) {
     return MSL_OK;
 }
 
-// One batch of n keyframes: their images staged in the slot set of this batch, the superpixel stage for all of them on the pre stream, then the
-// map stage per keyframe on the map stream.  compact: the resident map (false: the host-vector drop-in, whose map is the caller's vector).
+}  // namespace
+
 int run_batch(msl_sf *h, int n, const int32_t *refs, const float *poses, BatchImages I, bool compact) {
     int rc = check_images(h, n, refs, poses, I);
     if (rc != MSL_OK) return rc;
@@ -568,7 +335,11 @@ int run_batch(msl_sf *h, int n, const int32_t *refs, const float *poses, BatchIm
     return launch_map_chain(h, P, set, n, compact);
 }
 
-}  // namespace
+}  // namespace sf
+}  // namespace msl
+
+using namespace msl;
+using namespace msl::sf;
 
 extern "C" {
 
@@ -684,225 +455,7 @@ int msl_sf_sync(msl_sf *h) noexcept {
     try {
     if (!h) return MSL_ERR_INVALID;
     MSL_HIP_TRY(hipSetDevice(h->device));
-    int rc = read_ctr(h);
-    if (rc != MSL_OK) return rc;
-    return check_err(h);
-    } MSL_ABI_CATCH_INT
-}
-
-int msl_sf_map_reserve(msl_sf *h, size_t capacity) noexcept {
-    try {
-    if (!h) return MSL_ERR_INVALID;
-    MSL_HIP_TRY(hipSetDevice(h->device));
-    if (capacity <= h->dev.cap) return MSL_OK;
-    int rc = read_ctr(h);
-    if (rc != MSL_OK) return rc;
-    return map_realloc(h, capacity, (size_t)((const long long *)h->h_ctr.p)[0]);
-    } MSL_ABI_CATCH_INT
-}
-
-int msl_sf_map_upload(msl_sf *h, const msl_surfel *host, size_t n) noexcept {
-    try {
-    if (!h || (n && !host)) return MSL_ERR_INVALID;
-    h->mirrorValid = false;
-    MSL_HIP_TRY(hipSetDevice(h->device));
-    int rc = sync_all(h);
-    if (rc != MSL_OK) return rc;
-    if (n + (size_t)h->dev.nseeds > h->dev.cap) {
-        rc = map_realloc(h, n + n / 4 + 4 * (size_t)h->dev.nseeds, 0);
-        if (rc != MSL_OK) return rc;
-    }
-    hipStream_t s = h->mapStream;
-    MSL_HIP_TRY(hipMemsetAsync(h->dev.ctr + 13, 0, sizeof(long long), s));   // a fresh map: no wide r, g, b records yet
-    if (n) {
-        MSL_HIP_TRY(h->d_aos.grow(sizeof(msl_surfel) * n, s));
-        MSL_HIP_TRY(hipMemcpyAsync(h->d_aos.p, host, sizeof(msl_surfel) * n, hipMemcpyHostToDevice, s));
-        map_launch_aos_to_soa(h->prof, s, h->dev, (const msl_surfel *)h->d_aos.p, (long long)n, false);
-    }
-    map_launch_set_ctr(s, h->dev, (long long)n, -1);
-    MSL_HIP_TRY(hipStreamSynchronize(s));
-    h->liveBound = n; h->liveKnown = n; h->liveKnownKf = h->kfEnq; h->classicNext = true;
-    drop_live_snapshots(h);   // a count recorded before the upload would otherwise lower the bound below n
-    return MSL_OK;
-    } MSL_ABI_CATCH_INT
-}
-
-int msl_sf_map_snapshot(msl_sf *h) noexcept {
-    try {
-    if (!h) return MSL_ERR_INVALID;
-    MSL_HIP_TRY(hipSetDevice(h->device));
-    int rc = read_ctr(h);
-    if (rc != MSL_OK) return rc;
-    rc = check_err(h);
-    if (rc != MSL_OK) return rc;
-    const long long *ctr = (const long long *)h->h_ctr.p;
-    const size_t n = (size_t)ctr[0];
-    h->snapValid = false;   // (until the copies below are complete)
-    MSL_HIP_TRY(h->d_snapStore.grow(sizeof(float) * MAP_WORDS * ((n + 4095) & ~(size_t)4095), h->mapStream));
-    if (n) {
-        float *snap = (float *)h->d_snapStore.p;
-        const size_t sc = h->d_snapStore.cap / (sizeof(float) * MAP_WORDS);   // surfels the store is laid out for
-        MSL_HIP_TRY(hipMemcpy(snap + ST_HOT * sc, h->dev.map.hot, sizeof(HotPk) * n, hipMemcpyDeviceToDevice));
-        MSL_HIP_TRY(hipMemcpy(snap + ST_COLD * sc, h->dev.map.cold, sizeof(ColdRec) * n, hipMemcpyDeviceToDevice));
-        if (ctr[13] & 1) MSL_HIP_TRY(hipMemcpy(snap + ST_RGB * sc, h->dev.map.rgbWide, sizeof(int) * 3 * n, hipMemcpyDeviceToDevice));
-        if (ctr[13] & 2) MSL_HIP_TRY(hipMemcpy(snap + ST_UTL * sc, h->dev.map.utlWide, sizeof(int) * 2 * n, hipMemcpyDeviceToDevice));
-    }
-    h->snapN = n; h->snapValid = true; h->snapWide = ctr[13];
-    return MSL_OK;
-    } MSL_ABI_CATCH_INT
-}
-
-int msl_sf_map_restore(msl_sf *h) noexcept {
-    try {
-    if (!h || !h->snapValid) { set_error("msl_sf_map_restore: no snapshot"); return MSL_ERR_INVALID; }
-    h->mirrorValid = false;
-    MSL_HIP_TRY(hipSetDevice(h->device));
-    const size_t n = h->snapN;
-    if (n + (size_t)h->dev.nseeds > h->dev.cap) {   // the map was reallocated smaller than the snapshot (upload of a small map): grow again
-        int rc = read_ctr(h);
-        if (rc != MSL_OK) return rc;
-        rc = map_realloc(h, n + n / 4 + 4 * (size_t)h->dev.nseeds, 0);
-        if (rc != MSL_OK) return rc;
-    }
-    hipStream_t s = h->mapStream;   // ordered after every keyframe enqueued so far; the superpixel stream never touches the map
-    if (n) {
-        const float *snap = (const float *)h->d_snapStore.p;
-        const size_t sc = h->d_snapStore.cap / (sizeof(float) * MAP_WORDS);
-        MSL_HIP_TRY(hipMemcpyAsync(h->dev.map.hot, snap + ST_HOT * sc, sizeof(HotPk) * n, hipMemcpyDeviceToDevice, s));
-        MSL_HIP_TRY(hipMemcpyAsync(h->dev.map.cold, snap + ST_COLD * sc, sizeof(ColdRec) * n, hipMemcpyDeviceToDevice, s));
-        if (h->snapWide & 1) MSL_HIP_TRY(hipMemcpyAsync(h->dev.map.rgbWide, snap + ST_RGB * sc, sizeof(int) * 3 * n, hipMemcpyDeviceToDevice, s));
-        if (h->snapWide & 2) MSL_HIP_TRY(hipMemcpyAsync(h->dev.map.utlWide, snap + ST_UTL * sc, sizeof(int) * 2 * n, hipMemcpyDeviceToDevice, s));
-    }
-    // the restored map has exactly the snapshot's wide-rgb state: without the flag a later snapshot would skip rgbWide and a restore of THAT
-    // one would bring COLD_WIDE records back without their exact ints
-    map_launch_set_ctr(s, h->dev, (long long)n, (int)h->snapWide);
-    MSL_HIP_TRY(hipGetLastError());
-    h->liveBound = n; h->liveKnown = n; h->liveKnownKf = h->kfEnq; h->classicNext = true;
-    drop_live_snapshots(h);
-    return MSL_OK;
-    } MSL_ABI_CATCH_INT
-}
-
-int msl_sf_map_size(msl_sf *h, size_t *n_out) noexcept {
-    try {
-    if (!h || !n_out) return MSL_ERR_INVALID;
-    MSL_HIP_TRY(hipSetDevice(h->device));
-    int rc = read_ctr(h);
-    if (rc != MSL_OK) return rc;
-    *n_out = (size_t)((const long long *)h->h_ctr.p)[0];
-    return check_err(h);
-    } MSL_ABI_CATCH_INT
-}
-
-int msl_sf_map_download(msl_sf *h, msl_surfel *host, size_t cap, size_t *n_out) noexcept {
-    try {
-    if (!h || !n_out) return MSL_ERR_INVALID;
-    MSL_HIP_TRY(hipSetDevice(h->device));
-    int rc = read_ctr(h);
-    if (rc != MSL_OK) return rc;
-    const size_t n = (size_t)((const long long *)h->h_ctr.p)[0];
-    *n_out = n;
-    if (n > cap || (n && !host)) { set_error("msl_sf_map_download: capacity %zu < map size %zu", cap, n); return MSL_ERR_CAPACITY; }
-    if (n) {
-        hipStream_t s = h->mapStream;
-        MSL_HIP_TRY(h->d_aos.grow(sizeof(msl_surfel) * n, s));
-        map_launch_soa_to_aos(h->prof, s, h->dev, (msl_surfel *)h->d_aos.p, (long long)n);
-        MSL_HIP_TRY(hipMemcpyAsync(host, h->d_aos.p, sizeof(msl_surfel) * n, hipMemcpyDeviceToHost, s));
-        MSL_HIP_TRY(hipStreamSynchronize(s));
-    }
-    return check_err(h);
-    } MSL_ABI_CATCH_INT
-}
-
-static int map_select(msl_sf *h, int mode, int arg, bool mark, msl_surfel *out, size_t cap, size_t *n_out, const char *what) {
-    if (!h || !n_out) { set_error("%s: invalid argument", what); return MSL_ERR_INVALID; }
-    if (mark) { h->mirrorValid = false; h->classicNext = true; }
-    MSL_HIP_TRY(hipSetDevice(h->device));
-    int rc = read_ctr(h);                       // waits for both streams
-    if (rc != MSL_OK) return rc;
-    rc = check_err(h);
-    if (rc != MSL_OK) return rc;
-    const size_t n = (size_t)((const long long *)h->h_ctr.p)[0];
-    *n_out = 0;
-    if (n == 0) return MSL_OK;
-    hipStream_t s = h->mapStream;
-    const SfDev P = h->dev;
-    map_launch_select_count(s, P, mode, arg);
-    rc = read_ctr(h);
-    if (rc != MSL_OK) return rc;
-    const size_t m = (size_t)((const long long *)h->h_ctr.p)[7];
-    *n_out = m;
-    (void)hipMemsetAsync(h->dev.ctr + 7, 0, sizeof(long long), s);
-    if (m > cap || (m && !out)) { set_error("%s: %zu surfels selected, capacity %zu", what, m, cap); return MSL_ERR_CAPACITY; }
-    if (m == 0) return MSL_OK;
-    MSL_HIP_TRY(h->d_aos.grow(sizeof(msl_surfel) * m, s));
-    map_launch_select_write(s, P, mode, arg, (msl_surfel *)h->d_aos.p, mark ? 1 : 0);
-    MSL_HIP_TRY(hipMemcpyAsync(out, h->d_aos.p, sizeof(msl_surfel) * m, hipMemcpyDeviceToHost, s));
-    MSL_HIP_TRY(hipStreamSynchronize(s));
-    return MSL_OK;
-}
-
-int msl_sf_map_detach(msl_sf *h, int pose_index, msl_surfel *out, size_t cap, size_t *n_out) noexcept { try {
-    return map_select(h, 0, pose_index, true, out, cap, n_out, "msl_sf_map_detach"); } MSL_ABI_CATCH_INT }
-int msl_sf_map_export(msl_sf *h, int min_update_times, msl_surfel *out, size_t cap, size_t *n_out) noexcept { try {
-    return map_select(h, 1, min_update_times, false, out, cap, n_out, "msl_sf_map_export"); } MSL_ABI_CATCH_INT }
-// System::saveSurfels (src/System.cc:296-382) for the cloud SurfelMapping::Stop builds (src/SurfelMapping.cpp:62-104): the local surfels
-// seen at least min_update_times times (filtered on the device, map order), then the caller's inactive surfels.  ASCII PLY with the
-// element / property layout the reference hands to tinyply; NaN positions are skipped (:311-312); alpha = 1, quality = weight,
-// radius = size * 1000 (SurfelMapping.cpp:80).  Number formatting is that of a default std::ostream (tinyply itself is a third party).
-int msl_sf_export_ply(msl_sf *h, int min_update_times, const msl_surfel *inactive, size_t n_inactive, const char *path) noexcept {
-    try {
-    if (!h || !path || (n_inactive && !inactive)) { set_error("msl_sf_export_ply: invalid argument"); return MSL_ERR_INVALID; }
-    size_t n = 0;
-    int rc = msl_sf_map_export(h, min_update_times, nullptr, 0, &n);
-    if (rc != MSL_OK && rc != MSL_ERR_CAPACITY) return rc;
-    std::vector<msl_surfel> pts(n + n_inactive);
-    if (n) { rc = msl_sf_map_export(h, min_update_times, pts.data(), n, &n); if (rc != MSL_OK) return rc; }
-    for (size_t i = 0; i < n_inactive; i++) pts[n + i] = inactive[i];
-    size_t count = 0;
-    for (const msl_surfel &e : pts) count += std::isnan(e.px) ? 0 : 1;
-    std::ofstream os(path, std::ios::out);
-    if (os.fail()) { set_error("msl_sf_export_ply: cannot open %s", path); return MSL_ERR_INVALID; }
-    os << "ply\nformat ascii 1.0\nelement vertex " << count << "\n";
-    for (const char *p : {"x", "y", "z", "nx", "ny", "nz"}) os << "property float " << p << "\n";
-    for (const char *p : {"red", "green", "blue", "alpha"}) os << "property uchar " << p << "\n";
-    for (const char *p : {"quality", "radius"}) os << "property float " << p << "\n";
-    os << "element camera 1\n";
-    for (const char *p : {"view_px", "view_py", "view_pz", "x_axisx", "x_axisy", "x_axisz", "y_axisx", "y_axisy", "y_axisz", "z_axisx", "z_axisy", "z_axisz",
-                          "focal", "scalex", "scaley", "centerx", "centery"})
-        os << "property float " << p << "\n";
-    os << "property int viewportx\nproperty int viewporty\nproperty float k1\nproperty float k2\nend_header\n";
-    for (const msl_surfel &e : pts) {
-        if (std::isnan(e.px)) continue;
-        os << e.px << " " << e.py << " " << e.pz << " " << e.nx << " " << e.ny << " " << e.nz << " " << (unsigned)(uint8_t)e.r << " " << (unsigned)(uint8_t)e.g << " "
-           << (unsigned)(uint8_t)e.b << " 1 " << e.weight << " " << e.size * 1000 << "\n";
-    }
-    os << "0 0 0 1 0 0 0 1 0 0 0 1 0 0 0 0 0 " << (int)count << " 1 0 0\n";
-    return os.fail() ? MSL_ERR_INVALID : MSL_OK;
-    } MSL_ABI_CATCH_INT
-}
-
-int msl_sf_map_append(msl_sf *h, const msl_surfel *surfels, size_t n) noexcept {
-    try {
-    if (!h || (n && !surfels)) { set_error("msl_sf_map_append: invalid argument"); return MSL_ERR_INVALID; }
-    h->mirrorValid = false;
-    MSL_HIP_TRY(hipSetDevice(h->device));
-    int rc = read_ctr(h);
-    if (rc != MSL_OK) return rc;
-    if (n == 0) return MSL_OK;
-    const size_t cur = (size_t)((const long long *)h->h_ctr.p)[0];
-    if (cur + n + (size_t)h->dev.nseeds > h->dev.cap) {
-        rc = map_realloc(h, cur + n + (cur + n) / 4 + 4 * (size_t)h->dev.nseeds, cur);
-        if (rc != MSL_OK) return rc;
-    }
-    hipStream_t s = h->mapStream;
-    MSL_HIP_TRY(h->d_aos.grow(sizeof(msl_surfel) * n, s));
-    MSL_HIP_TRY(hipMemcpyAsync(h->d_aos.p, surfels, sizeof(msl_surfel) * n, hipMemcpyHostToDevice, s));
-    map_launch_aos_to_soa(h->prof, s, h->dev, (const msl_surfel *)h->d_aos.p, (long long)n, true);
-    map_launch_add_ctr(s, h->dev, (long long)n);
-    MSL_HIP_TRY(hipStreamSynchronize(s));
-    h->liveBound = cur + n; h->liveKnown = cur + n; h->liveKnownKf = h->kfEnq; h->classicNext = true;
-    return MSL_OK;
+    return settle(h);
     } MSL_ABI_CATCH_INT
 }
 
@@ -942,208 +495,6 @@ int msl_sf_fuse_resident(msl_sf *h, int referenceFrameIndex, const uint8_t *gray
     } MSL_ABI_CATCH_INT
 }
 
-int msl_sf_last_counters(msl_sf *h, int64_t counters[5]) noexcept {
-    try {
-    if (!h || !counters) return MSL_ERR_INVALID;
-    MSL_HIP_TRY(hipSetDevice(h->device));
-    int rc = read_ctr(h);
-    if (rc != MSL_OK) return rc;
-    const long long *ctr = (const long long *)h->h_ctr.p;
-    counters[0] = ctr[4]; counters[1] = ctr[1]; counters[2] = ctr[2]; counters[3] = ctr[3]; counters[4] = ctr[0];
-    return check_err(h);
-    } MSL_ABI_CATCH_INT
-}
-
-// Host-vector mode.  The caller's vector is the map for this call; what travels is kept to what has to:
-//   in : the whole vector (56 B per surfel) -- unless MSL_SF_LOCAL_UNCHANGED says it still is what the previous call on this handle left there, in
-//        which case the device copy of that call is used as it stands (checked: same length, no other map operation on the handle in between);
-//   out: only the stretches of the vector that hold surfels this keyframe touched.  k_fuse leaves a deleted and an updated count per SUB_ITEMS-surfel
-//        sub-block; sub-blocks with neither are byte-identical to the caller's copy and are not sent back (runs of touched sub-blocks travel as
-//        one copy each, small gaps bridged; more than 64 runs collapse into fewer by bridging larger gaps).
-int msl_sf_fuse_ex(msl_sf *h, int referenceFrameIndex, const uint8_t *gray, size_t gray_stride, const float *depth, size_t depth_stride,
-                   const int32_t *member, size_t member_stride, const float pose_colmajor[16], msl_surfel *local, size_t n_local,
-                   msl_surfel *new_out, size_t new_cap, size_t *n_new, unsigned flags) noexcept {
-    try {
-    if (!h || !pose_colmajor || !n_new || (n_local && !local)) { set_error("msl_sf_fuse: invalid argument"); return MSL_ERR_INVALID; }
-    if (new_cap < (size_t)h->dev.nseeds || !new_out) { set_error("msl_sf_fuse: new_cap must be >= (w/8)*(h/8) = %d", h->dev.nseeds); return MSL_ERR_CAPACITY; }
-    MSL_HIP_TRY(hipSetDevice(h->device));
-    int rc;
-    const bool reuse = (flags & MSL_SF_LOCAL_UNCHANGED) && h->mirrorValid && h->mirrorN == n_local;
-    if (reuse) {
-        // the device map is the caller's vector already: only the per-call counters start over
-        map_launch_set_ctr(h->mapStream, h->dev, (long long)n_local, -1);
-        h->liveBound = n_local; h->liveKnown = n_local; h->liveKnownKf = h->kfEnq;
-    } else {
-        rc = msl_sf_map_upload(h, local, n_local);
-        if (rc != MSL_OK) return rc;
-    }
-    h->mirrorValid = false;   // (until this call has completed)
-    const int32_t ref = referenceFrameIndex;
-    rc = run_batch(h, 1, &ref, pose_colmajor, {{gray, gray_stride}, {depth, depth_stride}, {}, {member, member_stride}, MSL_MEM_HOST}, false);
-    if (rc != MSL_OK) return rc;
-    hipStream_t s = h->mapStream;
-    const size_t nblk = (n_local + SUB_ITEMS - 1) / SUB_ITEMS;
-    if (nblk > h->h_blk.cap / (2 * sizeof(unsigned))) MSL_HIP_TRY(h->h_blk.grow(sizeof(unsigned) * 2 * (nblk + 1024), s));
-    const size_t blkHalf = h->h_blk.cap / (2 * sizeof(unsigned));   // deleted counts | updated counts
-    const unsigned *blk = (const unsigned *)h->h_blk.p;
-    if (nblk) {
-        MSL_HIP_TRY(hipMemcpyAsync(h->h_blk.p, h->dev.blockSums, sizeof(unsigned) * nblk, hipMemcpyDeviceToHost, s));
-        MSL_HIP_TRY(hipMemcpyAsync((unsigned *)h->h_blk.p + blkHalf, h->dev.blockUpd, sizeof(unsigned) * nblk, hipMemcpyDeviceToHost, s));
-    }
-    rc = read_ctr(h);   // the call's first synchronisation: counters and the per-sub-block counts are on the host
-    if (rc != MSL_OK) return rc;
-    rc = check_err(h);
-    if (rc != MSL_OK) return rc;
-    const size_t K = (size_t)((const long long *)h->h_ctr.p)[1];
-    *n_new = K;
-    // what was touched, and where
-    struct Run { size_t b0, b1; };
-    std::vector<Run> runs;
-    size_t touched = 0, runSurfels = 0;
-    for (size_t b = 0; b < nblk; b++) touched += (size_t)blk[b] + blk[blkHalf + b];
-    for (size_t gapMax = 4; ; gapMax *= 4) {
-        runs.clear();
-        for (size_t b = 0; b < nblk; b++) {
-            if (!(blk[b] | blk[blkHalf + b])) continue;
-            if (!runs.empty() && b - runs.back().b1 <= gapMax) runs.back().b1 = b + 1;
-            else runs.push_back({b, b + 1});
-        }
-        if (runs.size() <= 64) break;
-    }
-    for (const Run &r : runs) runSurfels += std::min(r.b1 * SUB_ITEMS, n_local) - r.b0 * SUB_ITEMS;
-    // Two ways back.  Runs of touched sub-blocks copied straight into the caller's vector (~45 GB/s), or -- when few surfels in many sub-blocks
-    // changed (a map in no particular order) -- a compact {index, record} list scattered by the CPU (~6 ns per record on top of its 60 bytes).
-    const size_t listLimit = n_local / 8;
-    msl_surfel *aos = (msl_surfel *)h->d_aos.p;   // (>= n_local entries: msl_sf_map_upload, or the call before that one)
-    const double costRuns = 56.0 * (double)runSurfels / 45e9, costList = (double)touched * (60.0 / 45e9 + 6e-9);
-    if (touched && touched <= listLimit && costList < costRuns) {
-        const size_t need = 256 + (sizeof(unsigned) + sizeof(msl_surfel)) * listLimit;
-        MSL_HIP_TRY(h->h_list.grow(need, s));
-        // device side: the count sits in tickets[3], indices in delList, records in the AoS buffer (both >= n_local entries)
-        unsigned *d_count = h->dev.tickets + 3;
-        MSL_HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned), s));
-        map_launch_collect_changed(s, h->dev, (int)ref, (long long)n_local, d_count, h->dev.delList, aos, (unsigned)listLimit);
-        uint8_t *list = (uint8_t *)h->h_list.p;
-        unsigned *hc = reinterpret_cast<unsigned *>(list);
-        unsigned *hi = reinterpret_cast<unsigned *>(list + 256);
-        msl_surfel *hr = reinterpret_cast<msl_surfel *>(list + 256 + sizeof(unsigned) * listLimit);
-        MSL_HIP_TRY(hipMemcpyAsync(hc, d_count, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        MSL_HIP_TRY(hipStreamSynchronize(s));
-        // (the list may be longer than `touched`: a surfel that carried lastUpdate == ref before the call is listed as well -- harmless, its
-        // record is unchanged -- so the length is read first; a list beyond the staging size falls back to the runs)
-        const size_t cnt = *hc;
-        if (cnt <= listLimit) {
-            MSL_HIP_TRY(hipMemcpyAsync(hi, h->dev.delList, sizeof(unsigned) * cnt, hipMemcpyDeviceToHost, s));
-            MSL_HIP_TRY(hipMemcpyAsync(hr, aos, sizeof(msl_surfel) * cnt, hipMemcpyDeviceToHost, s));
-            if (K) MSL_HIP_TRY(hipMemcpyAsync(new_out, h->dev.newSurfels, sizeof(msl_surfel) * K, hipMemcpyDeviceToHost, s));
-            MSL_HIP_TRY(hipStreamSynchronize(s));
-            for (size_t j = 0; j < cnt; j++) local[hi[j]] = hr[j];
-            h->mirrorValid = true; h->mirrorN = n_local;
-            return MSL_OK;
-        }
-    }
-    if (nblk && !runs.empty())
-        map_launch_soa_to_aos(h->prof, s, h->dev, aos, (long long)n_local);
-    for (const Run &r : runs) {
-        const size_t i0 = r.b0 * SUB_ITEMS, i1 = std::min(r.b1 * SUB_ITEMS, n_local);
-        MSL_HIP_TRY(hipMemcpyAsync(local + i0, aos + i0, sizeof(msl_surfel) * (i1 - i0), hipMemcpyDeviceToHost, s));
-    }
-    if (K) MSL_HIP_TRY(hipMemcpyAsync(new_out, h->dev.newSurfels, sizeof(msl_surfel) * K, hipMemcpyDeviceToHost, s));
-    MSL_HIP_TRY(hipStreamSynchronize(s));
-    h->mirrorValid = true; h->mirrorN = n_local;
-    return MSL_OK;
-    } MSL_ABI_CATCH_INT
-}
-
-int msl_sf_fuse(msl_sf *h, int referenceFrameIndex, const uint8_t *gray, size_t gray_stride, const float *depth, size_t depth_stride,
-                const int32_t *member, size_t member_stride, const float pose_colmajor[16], msl_surfel *local, size_t n_local,
-                msl_surfel *new_out, size_t new_cap, size_t *n_new) noexcept {
-    try {
-    return msl_sf_fuse_ex(h, referenceFrameIndex, gray, gray_stride, depth, depth_stride, member, member_stride, pose_colmajor, local, n_local, new_out,
-                          new_cap, n_new, 0u);
-    } MSL_ABI_CATCH_INT
-}
-
-int msl_sf_debug_seeds(msl_sf *h, msl_seed *out) noexcept {
-    try {
-    if (!h || !out) return MSL_ERR_INVALID;
-    MSL_HIP_TRY(hipSetDevice(h->device));
-    int rc = sync_all(h);
-    if (rc != MSL_OK) return rc;
-    const size_t ns = h->dev.nseeds;
-    MSL_HIP_TRY(hipMemcpy(out, h->dev.seeds + ns * h->lastSlot, sizeof(msl_seed) * ns, hipMemcpyDeviceToHost));
-    std::vector<uint8_t> fused(ns);
-    MSL_HIP_TRY(hipMemcpy(fused.data(), h->dev.fused + (size_t)h->dev.flagStride * h->lastSlot, ns, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < ns; i++) out[i].fused = fused[i] & 1;   // (2 = invalid candidate, not a fusion)
-    return MSL_OK;
-    } MSL_ABI_CATCH_INT
-}
-int msl_sf_debug_ctr(msl_sf *h, int64_t out[16]) noexcept {
-    try {
-    if (!h || !out) return MSL_ERR_INVALID;
-    MSL_HIP_TRY(hipSetDevice(h->device));
-    int rc = read_ctr(h);
-    if (rc != MSL_OK) return rc;
-    for (int i = 0; i < 16; i++) out[i] = ((const long long *)h->h_ctr.p)[i];
-    return MSL_OK;
-    } MSL_ABI_CATCH_INT
-}
-int msl_sf_debug_scratch(msl_sf *h, int which, size_t offset_words, uint32_t *out, size_t n_words) noexcept {
-    try {
-    if (!h || !out || which < 0 || which > 5) return MSL_ERR_INVALID;
-    if (which == 5) {   // keyframes this handle sent through the classic chain / through deferred windows (host state)
-        if (n_words < 2) return MSL_ERR_INVALID;
-        out[0] = (uint32_t)h->kfClassic; out[1] = (uint32_t)h->kfDeferred;
-        return MSL_OK;
-    }
-    if (which == 4) {   // the grid the dealing table currently is a permutation for (host state; 0: none)
-        if (n_words < 1) return MSL_ERR_INVALID;
-        out[0] = (uint32_t)h->dealG;
-        return MSL_OK;
-    }
-    if (offset_words + n_words > (which < 2 ? h->dev.cap : h->blkStride)) return MSL_ERR_INVALID;
-    MSL_HIP_TRY(hipSetDevice(h->device));
-    int rc = sync_all(h);
-    if (rc != MSL_OK) return rc;
-    const uint32_t *src = which == 0 ? h->dev.srcOf : which == 1 ? h->dev.delList : which == 2 ? h->dev.sbKeys : h->dev.deal;
-    MSL_HIP_TRY(hipMemcpy(out, src + offset_words, sizeof(uint32_t) * n_words, hipMemcpyDeviceToHost));
-    return MSL_OK;
-    } MSL_ABI_CATCH_INT
-}
-// What an event pair carried by a dispatch (hipExtLaunchKernelGGL) reports for a kernel that does nothing: n launches of an empty kernel with
-// `grid` single-wave workgroups on the map stream.  bench.py quotes it next to the roofline kernel's event time: rocprofv3's kernel duration
-// (first wave start to last wave end) is shorter than the event time by about this much.
-int msl_sf_debug_event_overhead(msl_sf *h, int grid, int n, float *mean_us) noexcept {
-    try {
-    if (!h || !mean_us || n < 1 || grid < 1) return MSL_ERR_INVALID;
-    MSL_HIP_TRY(hipSetDevice(h->device));
-    int rc = sync_all(h);
-    if (rc != MSL_OK) return rc;
-    std::vector<hipEvent_t> ev(2 * (size_t)n);
-    for (auto &e : ev) MSL_HIP_TRY(hipEventCreate(&e));
-    for (int i = 0; i < n; i++) map_launch_empty(h->mapStream, grid, ev[2 * i], ev[2 * i + 1]);
-    MSL_HIP_TRY(hipStreamSynchronize(h->mapStream));
-    double tot = 0;
-    for (int i = 0; i < n; i++) { float ms = 0; MSL_HIP_TRY(hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1])); tot += ms; }
-    for (auto &e : ev) (void)hipEventDestroy(e);
-    *mean_us = (float)(tot * 1e3 / n);
-    return MSL_OK;
-    } MSL_ABI_CATCH_INT
-}
-int msl_sf_debug_index(msl_sf *h, int32_t *out) noexcept {
-    try {
-    if (!h || !out) return MSL_ERR_INVALID;
-    MSL_HIP_TRY(hipSetDevice(h->device));
-    int rc = sync_all(h);
-    if (rc != MSL_OK) return rc;
-    const size_t npx = h->dev.npx;
-    std::vector<unsigned short> tmp(npx);
-    MSL_HIP_TRY(hipMemcpy(tmp.data(), h->dev.index + (size_t)h->dev.pxStride * h->lastSlot, sizeof(unsigned short) * npx, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < npx; i++) out[i] = tmp[i];
-    return MSL_OK;
-    } MSL_ABI_CATCH_INT
-}
-
 int msl_sf_profile_enable(msl_sf *h, int on) noexcept {
     try {
     if (!h) return MSL_ERR_INVALID;
@@ -1173,9 +524,5 @@ int msl_sf_profile_read(msl_sf *h, float *ms, int32_t *launches) noexcept {
     return MSL_OK;
     } MSL_ABI_CATCH_INT
 }
-int msl_debug_deal(const uint32_t *keys_host, int n_subblocks, uint32_t *deal_host) noexcept { try { return map_debug_deal(keys_host, n_subblocks, deal_host); } MSL_ABI_CATCH_INT }
-int msl_debug_div100(const float *x_host, double *out_host, size_t n) noexcept { try { return sp_debug_div100(x_host, out_host, n); } MSL_ABI_CATCH_INT }
-int msl_debug_chain_sum(const float *x_host, const int32_t *n_host, int lists, int huber, float *out_host) noexcept { try { return sp_debug_chain(x_host, n_host, lists, huber, out_host); } MSL_ABI_CATCH_INT }
-const char *msl_sf_kernel_name(int k) noexcept { try { return (k >= 0 && k < MSL_SF_NKERNELS) ? kSfNames[k] : ""; } MSL_ABI_CATCH_PTR }
 
 }  // extern "C"

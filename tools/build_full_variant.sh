@@ -1,5 +1,5 @@
 #!/bin/bash
-# Build a whole-library variant with extra preprocessor flags (every surfel translation unit: all of them see MSL_SUB_ITEMS, MSL_FUSE_CHUNK, MSL_FUSEREC_PLANES): tools/build_full_variant.sh <name> [hipcc flags]
+# Build a whole-library variant with extra preprocessor flags (every surfel translation unit, kernels and host side -- msl_sf_*.hip and msl_surfel.hip: all of them see MSL_SUB_ITEMS, MSL_FUSE_CHUNK, MSL_FUSEREC_PLANES): tools/build_full_variant.sh <name> [hipcc flags]
 # -> scratch/libmsl_<name>.so (MSL_LIB selects it).  Experiments only.
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd); NAME=$1; shift
