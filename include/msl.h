@@ -927,6 +927,87 @@ MSL_API int msl_lines_3d_batch(int device, int n_frames, int lcap, int order, co
                                float *line_depth, double *line_xyz, uint8_t *line_ok, uint8_t *line_new, int32_t *n_support, int32_t *n_new,
                                msl_mem out_mem) MSL_NOEXCEPT;
 
+/* ---- New map points: LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:303-522) ----
+ * msl_triangulate_new_points: for n_items independent current keyframes KF1, each with up to ncap neighbour keyframes KF2 in covisibility
+ * order: the baseline test, LocalMapping::ComputeF12 (:624-640), ORBmatcher::SearchForTriangulation (src/ORBmatcher.cc:257-406, with
+ * CheckDistEpipolarLine, :127-144) and the triangulation loop with all its tests; for every created point what the MapPoint constructor,
+ * ComputeDistinctiveDescriptors and UpdateNormalAndDepth (src/MapPoint.cc:282-322) give it.  Fuse / SearchInNeighbors, the cullings and
+ * all MapPoint / KeyFrame bookkeeping stay with the caller.
+ * Keyframes are passed once, as a table of n_tab keyframes with `cap` keypoints each; per keypoint i < n_kps[k] of keyframe k:
+ *   kps_un[i]        mvKeysUn[i] (pt, angle, octave are read)         raw_xy[2 i..]  mvKeys[i].pt (UnprojectStereo reads the distorted point)
+ *   uright[i]        mvuRight[i] (>= 0: a stereo keypoint)            depth[i]       mvDepth[i]
+ *   desc[32 i..]     mDescriptors.row(i)                              node[i]        node_out of msl_bow_transform (-1: in no list)
+ *   held[i]          any non-zero byte: GetMapPoint(i) != NULL (no isBad() test, as in the reference)
+ *   Tcw[12 k..]      rows 0-2 of the CV_32F Tcw; Rwc, Ow and Twc are derived as KeyFrame::SetPose does
+ * Items: cur[f] is the table index of KF1, neigh[f * ncap + r] those of its neighbours, r < n_neigh[f].  An item's neighbours are distinct
+ * keyframes and none is cur[f]; items are independent and every item reads `held` as it was on entry.  A host-memory call checks all of
+ * this (and the index ranges) and refuses a violation; with device memory it is the caller's contract -- an index outside the table, or
+ * a neighbour equal to cur[f], is then treated as a neighbour skipped for its baseline (an invalid cur[f] as a keyframe without keypoints),
+ * a repeated neighbour goes unnoticed.
+ * Out, per (item f, neighbour r, idx1) at [(f * ncap + r) * cap + idx1]:
+ *   match12          vMatches12[idx1] of SearchForTriangulation after the rotation cull, -1 = none
+ *   status           one MSL_TRI_* code: what became of the pair (idx1, match12)
+ *   nmatches[f * ncap + r]  the return value of SearchForTriangulation
+ * per (item f, idx1) at [f * cap + idx1] -- every idx1 gets a point at most once per item, because the created point occupies it:
+ *   new_neigh        the r whose pair created the point, -1 = none     new_idx2       its idx2 in that neighbour (-1)
+ *   new_xyz[3 ..]    GetWorldPos()     new_normal[3 ..]  GetNormal()    new_dist[2 ..]  mfMinDistance, mfMaxDistance (raw)
+ *   new_desc[32 ..]  GetDescriptor(): with two observations the first in creation order, the neighbour's row idx2
+ *   (the layouts msl_match_local_points reads as mp_xyz, mp_normal, mp_dist, mp_desc; zeros where no point was created)
+ * per item: new_order[f * cap + j], j < n_new[f] = the idx1 of the created points in creation order (neighbour order, then ascending
+ * idx1), -1 beyond.  Slots beyond n_kps / n_neigh are -1 (indices) and 0 (everything else).
+ * As in this reference (not upstream ORB-SLAM2) vbMatched2 is never set: every idx1 is searched on its own, two idx1 may take the same
+ * idx2 and both be created; among equal distances the later idx2 wins.  The chain across neighbours is reproduced: an idx1 that got a
+ * point is not searched against the later neighbours, which changes their rotation histograms.
+ * Pinned where the reference is undefined or not restated (tests/triangulate_model.py is the sequential model):
+ *   - cv::Mat products as cv::gemm's float kernel (double accumulation, one rounding); Mat::dot and cv::norm accumulate in double
+ *   - K.inv(), K.t().inv(): the closed 3x3 form in double, each element rounded; F12 = ((K1^-T t12x) R12) K2^-1 left to right
+ *   - cos(2 atan2(b / 2, depth)) = (d^2 - a^2) / (d^2 + a^2), a = b / 2, evaluated in double
+ *   - cv::SVD: the cyclic Jacobi eigen-solver of msl_pnp_ransac on A^T A (double, n = 4); vt.row(3) = the eigenvector of the smallest
+ *     eigenvalue, cast to float, then a float division by its fourth component
+ *   - UnprojectStereo of a stereo keypoint with depth <= 0 (an empty Mat in the reference): MSL_TRI_LOW_PARALLAX
+ *   - a keypoint whose octave is outside [0, nlevels) is never searched, on either side
+ * Limits: cap <= 8192, ncap <= 16, nlevels <= MSL_MATCH_MAX_LEVELS, n_items <= 65535; anything else is refused with MSL_ERR_INVALID before
+ * any launch, and nothing is written.  Memory and synchronisation as msl_bow_transform: device pointers run asynchronously on the handle's
+ * stream, with host memory on either side the call returns when the caller's buffers are its own again. */
+typedef struct msl_triangulate_params {
+    float fx, fy, cx, cy, invfx, invfy;          /* KeyFrame::fx .. invfy (one camera for every keyframe) */
+    float bf, b;                                 /* mbf, mb */
+    int32_t nlevels;                             /* mnScaleLevels */
+    float scale_factors[MSL_MATCH_MAX_LEVELS];   /* mvScaleFactors */
+    float level_sigma2[MSL_MATCH_MAX_LEVELS];    /* mvLevelSigma2 */
+    float scale_factor;                          /* mfScaleFactor: ratioFactor = 1.5f * scale_factor */
+    int32_t check_orientation;                   /* ORBmatcher::mbCheckOrientation (false at the call site) */
+    int32_t only_stereo;                         /* bOnlyStereo (false at the call site) */
+} msl_triangulate_params;
+#define MSL_TRI_NO_MATCH           0   /* no match12 (also: idx1 taken by an earlier neighbour, or culled by the rotation histogram) */
+#define MSL_TRI_TRIANGULATED       1   /* created by linear triangulation */
+#define MSL_TRI_STEREO1            2   /* created by UnprojectStereo of KF1's keypoint */
+#define MSL_TRI_STEREO2            3   /* created by UnprojectStereo of KF2's keypoint */
+#define MSL_TRI_NEIGHBOUR_SKIPPED  4   /* baseline < b: the whole neighbour */
+#define MSL_TRI_LOW_PARALLAX       5   /* no stereo and very low parallax */
+#define MSL_TRI_W_ZERO             6   /* x3D(3) == 0 */
+#define MSL_TRI_Z1                 7   /* z1 <= 0 */
+#define MSL_TRI_Z2                 8   /* z2 <= 0 */
+#define MSL_TRI_REPROJ1            9   /* reprojection error in KF1 */
+#define MSL_TRI_REPROJ2           10   /* reprojection error in KF2 */
+#define MSL_TRI_ZERO_DIST         11   /* dist1 == 0 || dist2 == 0 */
+#define MSL_TRI_SCALE             12   /* scale consistency */
+MSL_API int msl_triangulate_new_points(msl_match *h, int n_tab, int cap, int n_items, int ncap, const msl_triangulate_params *params,
+                                       const msl_keypoint *kps_un, const float *raw_xy, const float *uright, const float *depth,
+                                       const uint8_t *desc, const int32_t *node, const uint8_t *held, const int32_t *n_kps, const float *Tcw,
+                                       const int32_t *cur, const int32_t *neigh, const int32_t *n_neigh, msl_mem mem, int32_t *match12,
+                                       uint8_t *status, int32_t *nmatches, int32_t *new_neigh, int32_t *new_idx2, float *new_xyz,
+                                       float *new_normal, float *new_dist, uint8_t *new_desc, int32_t *new_order, int32_t *n_new,
+                                       msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device matcher handle, always synchronous; see msl_match_by_projection_batch). */
+MSL_API int msl_triangulate_new_points_batch(int device, int n_tab, int cap, int n_items, int ncap, const msl_triangulate_params *params,
+                                             const msl_keypoint *kps_un, const float *raw_xy, const float *uright, const float *depth,
+                                             const uint8_t *desc, const int32_t *node, const uint8_t *held, const int32_t *n_kps,
+                                             const float *Tcw, const int32_t *cur, const int32_t *neigh, const int32_t *n_neigh, msl_mem mem,
+                                             int32_t *match12, uint8_t *status, int32_t *nmatches, int32_t *new_neigh, int32_t *new_idx2,
+                                             float *new_xyz, float *new_normal, float *new_dist, uint8_t *new_desc, int32_t *new_order,
+                                             int32_t *n_new, msl_mem out_mem) MSL_NOEXCEPT;
+
 /* msl_kfdb: a KeyFrameDatabase (src/KeyFrameDatabase.cc:38-66) on one device.  msl_kfdb_create returns NULL with msl_last_error() when no
  * device is usable.  msl_kfdb_add stores the BowVector of one keyframe exactly as msl_bow_transform wrote it (ascending int32 words, double
  * values, the count -- on the device for MSL_MEM_DEVICE) and returns its slot when the vector is stored; with device memory `h` is the

@@ -87,6 +87,12 @@ MSL_API int msl_pnp_debug_hypotheses(msl_match *h, int pair, int k_cap, double *
  * md[6] = the final m and d of extract3dline_mahdist. */
 MSL_API int msl_lines_3d_debug(msl_match *h, int frame, int line, int32_t *counts, int32_t *iterations, double *md) MSL_NOEXCEPT;
 
+/* One (item, neighbour) pair of the last msl_triangulate_new_points call on h (host output, synchronous): pair[12] = the device's F12 (9,
+ * row-major), the epipole ex, ey and the baseline (zeros for a pair that was not formed); per idx1 < cap of that call the candidate match
+ * BEFORE the rotation cull and the chain -- cand[2 idx1..] = idx2 (-1: none) and its rotation bin, cosines[3 idx1..] = cosParallaxRays,
+ * cosParallaxStereo1, cosParallaxStereo2, x3d[4 idx1..] = the homogeneous x3D before the division (zeros unless triangulated). */
+MSL_API int msl_debug_triangulate(msl_match *h, int item, int neigh, float *pair, int32_t *cand, float *cosines, float *x3d) MSL_NOEXCEPT;
+
 #define MSL_SF_NKERNELS 12
 MSL_API int msl_sf_profile_enable(msl_sf *h, int mode) MSL_NOEXCEPT;
 /* Sampling for the per-dispatch event pairs: only every stride-th launch of a timed kernel carries events (default 1 = every launch).  A

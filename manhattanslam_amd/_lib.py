@@ -49,7 +49,10 @@ PNP_PARAMS_DTYPE = np.dtype([(n, "<f4") for n in ("fx", "fy", "cx", "cy")] + [("
 LINE3D_PARAMS_DTYPE = np.dtype([(n, "<f4") for n in ("fx", "fy", "cx", "cy")] + [(n, "<i4") for n in ("max_samples", "min_points", "max_iterations",
                                                                                             "max_new_lines")] +
                                [(n, "<f8") for n in ("dist_thresh", "min_support", "min_length")])                                  # msl_line3d_params
-assert LINE3D_PARAMS_DTYPE.itemsize == 56
+TRIANGULATE_PARAMS_DTYPE = np.dtype([(n, "<f4") for n in ("fx", "fy", "cx", "cy", "invfx", "invfy", "bf", "b")] + [("nlevels", "<i4"),
+                                    ("scale_factors", "<f4", (16,)), ("level_sigma2", "<f4", (16,)), ("scale_factor", "<f4"),
+                                    ("check_orientation", "<i4"), ("only_stereo", "<i4")])                                     # msl_triangulate_params
+assert LINE3D_PARAMS_DTYPE.itemsize == 56 and TRIANGULATE_PARAMS_DTYPE.itemsize == 176
 assert PNP_PARAMS_DTYPE.itemsize == 120 and PNP_PARAMS_DTYPE.fields["probability"][1] == 88
 assert POSE_PARAMS_DTYPE.itemsize == 152 and KEYPOINT_DTYPE.itemsize == 28 and SURFEL_DTYPE.itemsize == 56 and SEED_DTYPE.itemsize == 64
 
@@ -148,6 +151,9 @@ SIGNATURES = {
     "msl_lines_3d": (_i, [_vp, _i, _i, _i] + [_vp] * 4 + [_sz, _sz, _i, _i] + [_vp] * 3 + [_i] + [_vp] * 6 + [_i]),
     "msl_lines_3d_batch": (_i, [_i, _i, _i, _i] + [_vp] * 4 + [_sz, _sz, _i, _i] + [_vp] * 3 + [_i] + [_vp] * 6 + [_i]),
     "msl_lines_3d_debug": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "msl_triangulate_new_points": (_i, [_vp, _i, _i, _i, _i] + [_vp] * 13 + [_i] + [_vp] * 11 + [_i]),
+    "msl_triangulate_new_points_batch": (_i, [_i, _i, _i, _i, _i] + [_vp] * 13 + [_i] + [_vp] * 11 + [_i]),
+    "msl_debug_triangulate": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     "msl_sf_fuse_resident": (_i, [_vp, _i, _vp, _sz, _vp, _sz, _vp, _sz, _i, _vp]),
     "msl_sf_set_batch_capacity": (_i, [_vp, _i]),
     "msl_sf_fuse_resident_batch": (_i, [_vp, _i, _vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _sz, _sz, _i, _vp]),

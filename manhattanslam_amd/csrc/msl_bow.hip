@@ -45,7 +45,6 @@ struct msl_vocab {
 namespace {
 
 constexpr int MAX_CAP = 8192, MAX_LCAP = 256, MAX_K = 20, MAX_L = 10;
-constexpr int TH_LOW = 50;                         // src/ORBmatcher.cc:33
 constexpr int IDX_BITS = 13;                       // feature index < MAX_CAP
 constexpr int VEC_NT = 1024, BOW_NT = 1024, LD_NT = 256;
 constexpr unsigned long long KEY_NONE = ~0ull;
@@ -81,27 +80,6 @@ struct LdescDev {
     const uint8_t *curLdesc; const int32_t *nCur;
     int32_t *matchOut, *nmatches; double *lineXyz; uint8_t *lineHas;
 };
-
-// Ascending bitonic sort of n (a power of two) 64-bit keys in LDS by the whole block.
-__device__ void bitonic_sort(unsigned long long *a, int n) {
-    for (int size = 2; size <= n; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            __syncthreads();
-            for (int t = threadIdx.x; t < (n >> 1); t += blockDim.x) {
-                const int i = 2 * t - (t & (stride - 1)), j = i + stride;
-                const bool up = (i & size) == 0;
-                const unsigned long long x = a[i], y = a[j];
-                if ((x > y) == up) { a[i] = y; a[j] = x; }
-            }
-        }
-    __syncthreads();
-}
-
-__host__ __device__ __forceinline__ int pow2_at_least(int n) {
-    int p = 1;
-    while (p < n) p <<= 1;
-    return p;
-}
 
 // ==== Transform: the descent ===============================================================================================================
 template <int G>

@@ -1,5 +1,5 @@
 // msl_match_handle.h -- the matcher handle, its staging of caller arrays (Stage) and the forwarder of the *_batch entry points; shared by
-// msl_match.hip, msl_line_match.hip, msl_pose.hip, msl_plane.hip, msl_bow.hip, msl_reloc.hip, msl_pnp.hip and msl_line3d.hip (internal).
+// msl_match.hip, msl_line_match.hip, msl_pose.hip, msl_plane.hip, msl_bow.hip, msl_reloc.hip, msl_pnp.hip, msl_line3d.hip and msl_triangulate.hip (internal).
 #pragma once
 
 #include "msl_common.h"
@@ -13,8 +13,8 @@ struct PnpKey { double probability; int32_t min_inliers, max_iterations, min_set
 // the device is re-bound at every entry like the other handles.  The line searches (= the tracker's LSDmatcher), msl_pose_optimize, the
 // plane association and the bag-of-words calls run on it too.
 struct msl_match {
-    // The most arrays one entry point stages: msl_pose_optimize_translation (16 inputs, 3 in/out outlier flags, 2 outputs).
-    static constexpr int STAGE_SLOTS = 21;
+    // The most arrays one entry point stages: msl_triangulate_new_points (12 inputs, 11 outputs).
+    static constexpr int STAGE_SLOTS = 23;
     int device = 0;
     hipStream_t stream = nullptr; bool ownStream = true;
     // Scratch the kernels of a call hand to one another.  Device-memory calls are asynchronous and ordered only by the stream, so each
@@ -32,6 +32,10 @@ struct msl_match {
     int pnpPairs = 0, pnpKmax = 0; size_t pnpOffK = 0, pnpOffCnt = 0, pnpOffRt = 0, pnpOffBr = 0;
     msl::DevBuf line3d;                                                // msl_lines_3d: per keyline the record msl_lines_3d_debug reads
     int line3dFrames = 0, line3dLcap = 0;                              // the shape of the last call
+    // msl_triangulate_new_points: per table keyframe the sorted (node, feature) keys, per (item, neighbour) the pair geometry, per
+    // (item, neighbour, idx1) the candidate with its verdict (msl_debug_triangulate reads the last two)
+    msl::DevBuf triKeys, triPair, triRec;
+    int triItems = 0, triNcap = 0, triCap = 0;                         // the shape of the last call
     // Device copies of host-memory arguments, one pool for every entry point (msl::Stage deals the slots out in declaration order).
     // Sharing is sound because every call that touches the pool returns with the stream drained (Stage::finish synchronises whenever
     // either side is host memory, and only then is a slot used), so no slot is live when the next call starts.
@@ -66,7 +70,7 @@ int abi_call_default(Run run, int device, bool sync_legacy, A... a) {
 }
 
 // Kernels that ask for more dynamic LDS than the default limit: the limit is raised once per handle (= per device) and kernel.
-enum LdsKernel { LDS_MATCH_ASSIGN, LDS_LOCAL_ASSIGN, LDS_LINE_ASSIGN_LAST, LDS_LINE_ASSIGN_LOCAL, LDS_BOW_VECTOR, LDS_MATCH_BOW, LDS_KF_ASSIGN, LDS_RELOC_SELECT };
+enum LdsKernel { LDS_MATCH_ASSIGN, LDS_LOCAL_ASSIGN, LDS_LINE_ASSIGN_LAST, LDS_LINE_ASSIGN_LOCAL, LDS_BOW_VECTOR, LDS_MATCH_BOW, LDS_KF_ASSIGN, LDS_RELOC_SELECT, LDS_TRI_GROUP };
 template <class K>
 hipError_t allow_lds(msl_match *h, LdsKernel k, K kernel, size_t max_bytes) {
     if (h->ldsSet >> k & 1u) return hipSuccess;

@@ -1,6 +1,6 @@
 // msl_match_math.h -- device arithmetic the searches on the matcher handle share, each piece pinned or written once
 // (internal): cv::gemm's 3x3 float kernel, the search mode, the popcount distance and descriptor load, the two-smallest-keys pair and its
-// wave reduction, the rotation-consistency cull, the scale prediction.
+// wave reduction, the LDS key sort that groups features by vocabulary node, the rotation-consistency cull, the scale prediction.
 #pragma once
 
 #include "msl_common.h"
@@ -9,13 +9,17 @@
 
 namespace msl {
 
-// d[r] = (float)(alpha * sum_k A(r, k) b[k] + c[r]) with double accumulation: cv::gemm's CV_32F kernel
+constexpr int TH_LOW = 50;                         // src/ORBmatcher.cc:33
+
+// d[r] = (float)(alpha * sum_k A(r, k) b[k] + c[r]) with double accumulation: cv::gemm's CV_32F kernel.  S: the row stride of A (4: the
+// rotation inside rows 0-2 of a 4x4 pose)
+template <int S = 4>
 __device__ __forceinline__ void gemm3(const float *A, bool transA, double alpha, const float b[3], const float *c, float d[3]) {
 #pragma unroll
     for (int r = 0; r < 3; r++) {
         double s = 0;
 #pragma unroll
-        for (int k = 0; k < 3; k++) s += (double)(transA ? A[k * 4 + r] : A[r * 4 + k]) * (double)b[k];
+        for (int k = 0; k < 3; k++) s += (double)(transA ? A[k * S + r] : A[r * S + k]) * (double)b[k];
         d[r] = (float)(s * alpha + (c ? (double)c[r] : 0.0));
     }
 }
@@ -62,6 +66,28 @@ __device__ __forceinline__ void two_min(T &m1, T &m2, int width) {
         const T s = m2 < b2 ? m2 : b2;
         m1 = lo; m2 = hi < s ? hi : s;
     }
+}
+
+// Ascending bitonic sort of n (a power of two) 64-bit keys in LDS by the whole block.  With (node << bits | feature) keys this is the
+// grouping of a FeatureVector: the features of a node are contiguous and ascending, the nodes ascending.
+__device__ __forceinline__ void bitonic_sort(unsigned long long *a, int n) {
+    for (int size = 2; size <= n; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            __syncthreads();
+            for (int t = threadIdx.x; t < (n >> 1); t += blockDim.x) {
+                const int i = 2 * t - (t & (stride - 1)), j = i + stride;
+                const bool up = (i & size) == 0;
+                const unsigned long long x = a[i], y = a[j];
+                if ((x > y) == up) { a[i] = y; a[j] = x; }
+            }
+        }
+    __syncthreads();
+}
+
+__host__ __device__ __forceinline__ int pow2_at_least(int n) {
+    int p = 1;
+    while (p < n) p <<= 1;
+    return p;
 }
 
 // The rotation-consistency histogram of the point searches (src/ORBmatcher.cc:33-35, e.g. :643-649 and :199-206): HISTO_LENGTH bins, the bin of
