@@ -931,8 +931,9 @@ MSL_API int msl_lines_3d_batch(int device, int n_frames, int lcap, int order, co
  * msl_triangulate_new_points: for n_items independent current keyframes KF1, each with up to ncap neighbour keyframes KF2 in covisibility
  * order: the baseline test, LocalMapping::ComputeF12 (:624-640), ORBmatcher::SearchForTriangulation (src/ORBmatcher.cc:257-406, with
  * CheckDistEpipolarLine, :127-144) and the triangulation loop with all its tests; for every created point what the MapPoint constructor,
- * ComputeDistinctiveDescriptors and UpdateNormalAndDepth (src/MapPoint.cc:282-322) give it.  Fuse / SearchInNeighbors, the cullings and
- * all MapPoint / KeyFrame bookkeeping stay with the caller.
+ * ComputeDistinctiveDescriptors and UpdateNormalAndDepth (src/MapPoint.cc:282-322) give it.  The point half of SearchInNeighbors is
+ * msl_fuse_candidates / msl_fuse_map_points below; the cullings and all MapPoint / KeyFrame bookkeeping stay with the caller
+ * (INTEGRATION.md sections 3l, 3m).
  * Keyframes are passed once, as a table of n_tab keyframes with `cap` keypoints each; per keypoint i < n_kps[k] of keyframe k:
  *   kps_un[i]        mvKeysUn[i] (pt, angle, octave are read)         raw_xy[2 i..]  mvKeys[i].pt (UnprojectStereo reads the distorted point)
  *   uright[i]        mvuRight[i] (>= 0: a stereo keypoint)            depth[i]       mvDepth[i]
@@ -1007,6 +1008,105 @@ MSL_API int msl_triangulate_new_points_batch(int device, int n_tab, int cap, int
                                              int32_t *match12, uint8_t *status, int32_t *nmatches, int32_t *new_neigh, int32_t *new_idx2,
                                              float *new_xyz, float *new_normal, float *new_dist, uint8_t *new_desc, int32_t *new_order,
                                              int32_t *n_new, msl_mem out_mem) MSL_NOEXCEPT;
+
+/* ---- Fusing map points into neighbouring keyframes: LocalMapping::SearchInNeighbors, point half (src/LocalMapping.cc:545-569) ----
+ * msl_fuse_map_points: n_items independent calls of ORBmatcher::Fuse(pKF, vpMapPoints, th) (src/ORBmatcher.cc:408-546), each from the
+ * state on entry.  msl_fuse_candidates: the de-duplicated vpFuseCandidates of :553-567.
+ * Keyframes are a table of n_tab keyframes with `cap` keypoints each, as for msl_triangulate_new_points; per keypoint i < n_kps[k]:
+ *   kps_un[i]        mvKeysUn[i] (pt and octave are read)              uright[i]      mvuRight[i] (>= 0: the stereo chi-square form)
+ *   grid_cell[i]     the `cell` output of msl_orb_extract_frame_batch (KeyFrame::mGrid is the frame's)
+ *   desc[32 i..]     mDescriptors.row(i)                                Tcw[12 k..]    rows 0-2 of the CV_32F Tcw; Ow as KeyFrame::SetPose
+ *   held_id[i]       the id of GetMapPoint(i), -1 for NULL; a bad point that is still in the slot keeps its id
+ * Map points are a table of n_pts points indexed by id (the layouts msl_match_local_points reads and msl_triangulate_new_points writes:
+ * one item's slice of its output is a point table with id = idx1, its new_order a candidate list):
+ *   pt_xyz[3 id..]   GetWorldPos()    pt_normal[3 id..]  GetNormal()    pt_dist[2 id..]  mfMinDistance, mfMaxDistance (raw; 0.8f / 1.2f inside)
+ *   pt_desc[32 id..] GetDescriptor()  pt_flags[id]       bit 0: !isBad()    pt_nobs[id]   Observations()
+ * msl_fuse_candidates: item f names n_targets[f] <= tcap target keyframes targets[f * tcap + t] in order.  cand[f * lcap + j] = the ids
+ * held by the targets, targets in order and slots ascending, NULL and bad points left out, every id at its first occurrence only (the
+ * mnFuseCandidateForKF rule).  n_cand[f] is the full count: entries beyond lcap are dropped, so the caller compares n_cand with lcap; slots
+ * beyond the count are -1.
+ * msl_fuse_map_points: item f fuses list[f] (a row of cand[n_lists][lcap] with n_cand[n_lists] entries; items may share a row) into the
+ * keyframe tgt[f].  A list entry is a point id or -1 (NULL); the ids of one list are distinct (a second occurrence never does anything in
+ * the reference -- by then the point is in the keyframe, bad, or unmatched exactly as before -- so a caller passes -1 for later duplicates
+ * of GetMapPointMatches(), and that is exact).  Out, per (item f, candidate j) at [f * lcap + j]:
+ *   best_idx, best_dist   bestIdx / bestDist of the search (-1 / 256 when nothing passed the filters, or the candidate left before the
+ *                         search); written for every candidate that reaches the search, one that lands above th_low included
+ *   status                one MSL_FUSE_* code: the exit of the loop body the candidate took
+ *   other                 the id that held slot best_idx at that moment, -1 for none (and for every status below MSL_FUSE_ADDED)
+ * per item: n_fused[f] = the return value.  Slots j >= n_cand[list[f]] are -1 (best_idx, other) and 0 (best_dist, status).
+ * What is resolved: the search of every candidate depends only on the keyframe and the point, so it is exact whatever the order.  The
+ * add / replace choice is resolved from the state on entry, candidates in ascending j, one state per slot s (holder, bad, nobs, stale):
+ *   empty                   MSL_FUSE_ADDED, the holder becomes p with nobs = pt_nobs[p] + (uright[s] >= 0 ? 2 : 1) (src/MapPoint.cc:83-93)
+ *   holder bad              MSL_FUSE_HELD_BAD, unchanged
+ *   holder stale            MSL_FUSE_UNRESOLVED, unchanged
+ *   nobs(h) > pt_nobs[p]    MSL_FUSE_REPLACED_BY_HELD, the holder is stale
+ *   otherwise               MSL_FUSE_REPLACES_HELD, the holder becomes p, stale
+ * Stale: the survivor's Observations() is the union of two observation sets, which the library does not know; from the third hit on one
+ * slot the direction is the caller's to take from its live objects (rare).  The caller replays the results in order against its objects
+ * and searches again only a survivor whose descriptor a Replace changed (tests/fuse_model.py proves the replay
+ * equal to the sequential function).
+ * Reproduced exactly (tests/fuse_model.py is the sequential model): p3Dc as cv::gemm's float kernel (double accumulation, one rounding);
+ * invz = 1 / z a float division; x = X * invz, u = fx * x + cx, ur = u - bf * invz in float, no contraction; IsInImage with half-open
+ * bounds (a non-finite projection fails it); dist3D = cv::norm and PO.dot(Pn) accumulated in double, dot < 0.5 * dist3D in double;
+ * PredictScale with the raw mfMaxDistance (as msl_match_local_points); KeyFrame::GetFeaturesInArea (src/KeyFrame.cc:469-504) without a
+ * level filter, walked ix, then iy, then ascending index inside a cell; octave in [level - 1, level]; the chi-square tests compare the
+ * float product e2 * inv_level_sigma2 with the doubles 7.8 (uright >= 0) and 5.99; dist < bestDist from 256, the first minimum in walk
+ * order wins.
+ * Pins: IsInKeyFrame(pKF) is read from the table, id in held_id[tgt][:n_kps] -- the caller keeps mObservations and mvpMapPoints
+ * consistent or NULLs the candidate; a keypoint whose octave is outside [0, nlevels) is never a candidate; a held_id outside [0, n_pts)
+ * is an empty slot.
+ * Limits: cap <= 8192, n_tab <= 4096, n_pts <= 1048576, lcap <= 65536, tcap <= 64, n_items <= 4096, nlevels <= MSL_MATCH_MAX_LEVELS,
+ * 0 <= th_low <= 255; anything else is refused with MSL_ERR_INVALID before any launch, and nothing is written.  A host-memory call also
+ * checks the index ranges (tgt, list, targets, n_targets, n_cand, every list entry) and the distinctness of each list, and refuses a
+ * violation; with device memory these are the caller's contract: an index outside its table is treated as NULL, a bad tgt or list as a
+ * keyframe without keypoints / an empty list, a repeated id goes unnoticed.  Memory and synchronisation as msl_bow_transform. */
+typedef struct msl_fuse_params {
+    float fx, fy, cx, cy, bf;                        /* KeyFrame::fx .. cy, mbf */
+    float minX, maxX, minY, maxY;                    /* mnMinX .. mnMaxY (msl_frame_image_bounds) */
+    float th;                                        /* 3.0 at both call sites */
+    int32_t nlevels;                                 /* mnScaleLevels */
+    float scale_factors[MSL_MATCH_MAX_LEVELS];       /* mvScaleFactors */
+    float inv_level_sigma2[MSL_MATCH_MAX_LEVELS];    /* mvInvLevelSigma2 */
+    float log_scale_factor;                          /* mfLogScaleFactor */
+    int32_t th_low;                                  /* ORBmatcher::TH_LOW (50) */
+} msl_fuse_params;
+#define MSL_FUSE_NULL               0   /* NULL candidate (also: a slot beyond the list) */
+#define MSL_FUSE_BAD                1   /* isBad() */
+#define MSL_FUSE_IN_KEYFRAME        2   /* IsInKeyFrame(pKF) */
+#define MSL_FUSE_BEHIND             3   /* p3Dc.z < 0 */
+#define MSL_FUSE_OUT_OF_IMAGE       4   /* !IsInImage(u, v) */
+#define MSL_FUSE_DISTANCE           5   /* dist3D outside [minDistance, maxDistance] */
+#define MSL_FUSE_VIEW_ANGLE         6   /* PO.dot(Pn) < 0.5 * dist3D */
+#define MSL_FUSE_NO_FEATURE         7   /* vIndices.empty() */
+#define MSL_FUSE_NO_CANDIDATE       8   /* every index filtered out, bestDist still 256 */
+#define MSL_FUSE_ABOVE_TH_LOW       9   /* bestDist > th_low */
+#define MSL_FUSE_ADDED             10   /* the slot was empty: AddObservation + AddMapPoint */
+#define MSL_FUSE_REPLACED_BY_HELD  11   /* pMP->Replace(pMPinKF) */
+#define MSL_FUSE_REPLACES_HELD     12   /* pMPinKF->Replace(pMP) */
+#define MSL_FUSE_HELD_BAD          13   /* the slot holds a bad point: counted, nothing done */
+#define MSL_FUSE_UNRESOLVED        14   /* counted; the direction is the caller's (a stale holder) */
+MSL_API int msl_fuse_candidates(msl_match *h, int n_tab, int cap, int n_pts, int n_items, int tcap, int lcap, const int32_t *held_id,
+                                const int32_t *n_kps, const uint8_t *pt_flags, const int32_t *targets, const int32_t *n_targets, msl_mem mem,
+                                int32_t *cand, int32_t *n_cand, msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device matcher handle, always synchronous; see msl_match_by_projection_batch). */
+MSL_API int msl_fuse_candidates_batch(int device, int n_tab, int cap, int n_pts, int n_items, int tcap, int lcap, const int32_t *held_id,
+                                      const int32_t *n_kps, const uint8_t *pt_flags, const int32_t *targets, const int32_t *n_targets,
+                                      msl_mem mem, int32_t *cand, int32_t *n_cand, msl_mem out_mem) MSL_NOEXCEPT;
+MSL_API int msl_fuse_map_points(msl_match *h, int n_tab, int cap, int n_pts, int n_items, int n_lists, int lcap, const msl_fuse_params *params,
+                                const msl_keypoint *kps_un, const float *uright, const int32_t *grid_cell, const uint8_t *desc,
+                                const int32_t *n_kps, const float *Tcw, const int32_t *held_id, const float *pt_xyz, const float *pt_normal,
+                                const float *pt_dist, const uint8_t *pt_desc, const uint8_t *pt_flags, const int32_t *pt_nobs,
+                                const int32_t *tgt, const int32_t *list, const int32_t *cand, const int32_t *n_cand, msl_mem mem,
+                                int32_t *best_idx, int32_t *best_dist, uint8_t *status, int32_t *other, int32_t *n_fused,
+                                msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device matcher handle, always synchronous). */
+MSL_API int msl_fuse_map_points_batch(int device, int n_tab, int cap, int n_pts, int n_items, int n_lists, int lcap,
+                                      const msl_fuse_params *params, const msl_keypoint *kps_un, const float *uright, const int32_t *grid_cell,
+                                      const uint8_t *desc, const int32_t *n_kps, const float *Tcw, const int32_t *held_id, const float *pt_xyz,
+                                      const float *pt_normal, const float *pt_dist, const uint8_t *pt_desc, const uint8_t *pt_flags,
+                                      const int32_t *pt_nobs, const int32_t *tgt, const int32_t *list, const int32_t *cand,
+                                      const int32_t *n_cand, msl_mem mem, int32_t *best_idx, int32_t *best_dist, uint8_t *status,
+                                      int32_t *other, int32_t *n_fused, msl_mem out_mem) MSL_NOEXCEPT;
 
 /* msl_kfdb: a KeyFrameDatabase (src/KeyFrameDatabase.cc:38-66) on one device.  msl_kfdb_create returns NULL with msl_last_error() when no
  * device is usable.  msl_kfdb_add stores the BowVector of one keyframe exactly as msl_bow_transform wrote it (ascending int32 words, double

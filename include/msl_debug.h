@@ -93,6 +93,11 @@ MSL_API int msl_lines_3d_debug(msl_match *h, int frame, int line, int32_t *count
  * cosParallaxStereo1, cosParallaxStereo2, x3d[4 idx1..] = the homogeneous x3D before the division (zeros unless triangulated). */
 MSL_API int msl_debug_triangulate(msl_match *h, int item, int neigh, float *pair, int32_t *cand, float *cosines, float *x3d) MSL_NOEXCEPT;
 
+/* One item of the last msl_fuse_map_points call on h (host output, synchronous), per candidate j < lcap of that call: uvr[3 j..] = u, v
+ * (set once the point is not behind the camera) and ur (set once the projection is inside the image); level_n[2 j..] = nPredictedLevel
+ * and vIndices.size() (set once the view-angle test passed).  Zeros where the candidate left earlier. */
+MSL_API int msl_debug_fuse(msl_match *h, int item, float *uvr, int32_t *level_n) MSL_NOEXCEPT;
+
 #define MSL_SF_NKERNELS 12
 MSL_API int msl_sf_profile_enable(msl_sf *h, int mode) MSL_NOEXCEPT;
 /* Sampling for the per-dispatch event pairs: only every stride-th launch of a timed kernel carries events (default 1 = every launch).  A

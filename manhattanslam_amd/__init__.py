@@ -27,3 +27,5 @@ from . import line3d  # noqa: F401
 from ._lib import LINE3D_PARAMS_DTYPE  # noqa: F401
 from . import triangulate  # noqa: F401
 from ._lib import TRIANGULATE_PARAMS_DTYPE  # noqa: F401
+from . import fuse  # noqa: F401
+from ._lib import FUSE_PARAMS_DTYPE  # noqa: F401

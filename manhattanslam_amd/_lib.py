@@ -52,7 +52,10 @@ LINE3D_PARAMS_DTYPE = np.dtype([(n, "<f4") for n in ("fx", "fy", "cx", "cy")] + 
 TRIANGULATE_PARAMS_DTYPE = np.dtype([(n, "<f4") for n in ("fx", "fy", "cx", "cy", "invfx", "invfy", "bf", "b")] + [("nlevels", "<i4"),
                                     ("scale_factors", "<f4", (16,)), ("level_sigma2", "<f4", (16,)), ("scale_factor", "<f4"),
                                     ("check_orientation", "<i4"), ("only_stereo", "<i4")])                                     # msl_triangulate_params
-assert LINE3D_PARAMS_DTYPE.itemsize == 56 and TRIANGULATE_PARAMS_DTYPE.itemsize == 176
+FUSE_PARAMS_DTYPE = np.dtype([(n, "<f4") for n in ("fx", "fy", "cx", "cy", "bf", "minX", "maxX", "minY", "maxY", "th")] + [("nlevels", "<i4"),
+                             ("scale_factors", "<f4", (16,)), ("inv_level_sigma2", "<f4", (16,)), ("log_scale_factor", "<f4"),
+                             ("th_low", "<i4")])                                                                                # msl_fuse_params
+assert LINE3D_PARAMS_DTYPE.itemsize == 56 and TRIANGULATE_PARAMS_DTYPE.itemsize == 176 and FUSE_PARAMS_DTYPE.itemsize == 180
 assert PNP_PARAMS_DTYPE.itemsize == 120 and PNP_PARAMS_DTYPE.fields["probability"][1] == 88
 assert POSE_PARAMS_DTYPE.itemsize == 152 and KEYPOINT_DTYPE.itemsize == 28 and SURFEL_DTYPE.itemsize == 56 and SEED_DTYPE.itemsize == 64
 
@@ -154,6 +157,11 @@ SIGNATURES = {
     "msl_triangulate_new_points": (_i, [_vp, _i, _i, _i, _i] + [_vp] * 13 + [_i] + [_vp] * 11 + [_i]),
     "msl_triangulate_new_points_batch": (_i, [_i, _i, _i, _i, _i] + [_vp] * 13 + [_i] + [_vp] * 11 + [_i]),
     "msl_debug_triangulate": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "msl_fuse_candidates": (_i, [_vp] + [_i] * 6 + [_vp] * 5 + [_i] + [_vp] * 2 + [_i]),
+    "msl_fuse_candidates_batch": (_i, [_i] + [_i] * 6 + [_vp] * 5 + [_i] + [_vp] * 2 + [_i]),
+    "msl_fuse_map_points": (_i, [_vp] + [_i] * 6 + [_vp] * 18 + [_i] + [_vp] * 5 + [_i]),
+    "msl_fuse_map_points_batch": (_i, [_i] + [_i] * 6 + [_vp] * 18 + [_i] + [_vp] * 5 + [_i]),
+    "msl_debug_fuse": (_i, [_vp, _i, _vp, _vp]),
     "msl_sf_fuse_resident": (_i, [_vp, _i, _vp, _sz, _vp, _sz, _vp, _sz, _i, _vp]),
     "msl_sf_set_batch_capacity": (_i, [_vp, _i]),
     "msl_sf_fuse_resident_batch": (_i, [_vp, _i, _vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _sz, _sz, _i, _vp]),

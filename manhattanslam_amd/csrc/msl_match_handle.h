@@ -1,5 +1,5 @@
 // msl_match_handle.h -- the matcher handle, its staging of caller arrays (Stage) and the forwarder of the *_batch entry points; shared by
-// msl_match.hip, msl_line_match.hip, msl_pose.hip, msl_plane.hip, msl_bow.hip, msl_reloc.hip, msl_pnp.hip, msl_line3d.hip and msl_triangulate.hip (internal).
+// msl_match.hip, msl_line_match.hip, msl_pose.hip, msl_plane.hip, msl_bow.hip, msl_reloc.hip, msl_pnp.hip, msl_line3d.hip, msl_triangulate.hip and msl_fuse.hip (internal).
 #pragma once
 
 #include "msl_common.h"
@@ -36,6 +36,10 @@ struct msl_match {
     // (item, neighbour, idx1) the candidate with its verdict (msl_debug_triangulate reads the last two)
     msl::DevBuf triKeys, triPair, triRec;
     int triItems = 0, triNcap = 0, triCap = 0;                         // the shape of the last call
+    // msl_fuse_map_points: per table keyframe the sorted ids its slots hold, per (item, candidate) the projection msl_debug_fuse reads;
+    // msl_fuse_candidates: per item in flight the first position of every point id
+    msl::DevBuf fuseHeld, fuseRec, fuseFirst;
+    int fuseItems = 0, fuseLcap = 0;                                   // the shape of the last msl_fuse_map_points call
     // Device copies of host-memory arguments, one pool for every entry point (msl::Stage deals the slots out in declaration order).
     // Sharing is sound because every call that touches the pool returns with the stream drained (Stage::finish synchronises whenever
     // either side is host memory, and only then is a slot used), so no slot is live when the next call starts.
@@ -70,7 +74,7 @@ int abi_call_default(Run run, int device, bool sync_legacy, A... a) {
 }
 
 // Kernels that ask for more dynamic LDS than the default limit: the limit is raised once per handle (= per device) and kernel.
-enum LdsKernel { LDS_MATCH_ASSIGN, LDS_LOCAL_ASSIGN, LDS_LINE_ASSIGN_LAST, LDS_LINE_ASSIGN_LOCAL, LDS_BOW_VECTOR, LDS_MATCH_BOW, LDS_KF_ASSIGN, LDS_RELOC_SELECT, LDS_TRI_GROUP };
+enum LdsKernel { LDS_MATCH_ASSIGN, LDS_LOCAL_ASSIGN, LDS_LINE_ASSIGN_LAST, LDS_LINE_ASSIGN_LOCAL, LDS_BOW_VECTOR, LDS_MATCH_BOW, LDS_KF_ASSIGN, LDS_RELOC_SELECT, LDS_TRI_GROUP, LDS_FUSE_HELD, LDS_FUSE_RESOLVE };
 template <class K>
 hipError_t allow_lds(msl_match *h, LdsKernel k, K kernel, size_t max_bytes) {
     if (h->ldsSet >> k & 1u) return hipSuccess;

@@ -1,7 +1,7 @@
 // msl_match_window.h -- the pieces every point search on the matcher handle shares (internal): the current frame's 64 x 48 feature grid
 // as a cell-sorted item list (k_match_grid), Frame::GetFeaturesInArea's window (src/Frame.cc:332-381) walked by one thread or one wave, the
-// candidate keys (dist << 16 | item position) and their staging.  Used by msl_match.hip (last-frame and local-map search) and
-// msl_reloc.hip (keyframe search); each translation unit gets its own copy of k_match_grid.
+// candidate keys (dist << 16 | item position) and their staging.  Used by msl_match.hip (last-frame and local-map search),
+// msl_reloc.hip (keyframe search) and msl_fuse.hip (the grid of a keyframe table); each translation unit gets its own copy of k_match_grid.
 #pragma once
 
 #include "msl_match_handle.h"
