@@ -1108,6 +1108,105 @@ MSL_API int msl_fuse_map_points_batch(int device, int n_tab, int cap, int n_pts,
                                       const int32_t *n_cand, msl_mem mem, int32_t *best_idx, int32_t *best_dist, uint8_t *status,
                                       int32_t *other, int32_t *n_fused, msl_mem out_mem) MSL_NOEXCEPT;
 
+/* ---- Refreshing map points and the covisibility of a keyframe: what LocalMapping runs right after the fusion ----
+ * msl_refresh_map_points: MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:210-270) and MapPoint::UpdateNormalAndDepth (:282-322)
+ * for n_items distinct point ids ids[f] -- the loops of src/LocalMapping.cc:127-141 and :573-581, and as a one-item call the
+ * ComputeDistinctiveDescriptors inside MapPoint::Replace.  It is the producer of pt_desc, pt_normal and pt_dist, which
+ * msl_match_local_points and msl_fuse_map_points read, so the point table can stay in device memory from one keyframe to the next.
+ * msl_covisibility: the counting and ordering of KeyFrame::UpdateConnections (src/KeyFrame.cc:230-299) for n_items keyframes kf[f] (table
+ * indices) with threshold th (15 at the call site, :621 and :221 of src/LocalMapping.cc).
+ * The observations of all points are one table in CSR form over the point table (n_pts points indexed by id, as for msl_fuse_map_points):
+ *   obs_off[n_pts + 1]   the range of point id is [obs_off[id], obs_off[id + 1]); obs_off[n_pts] == n_obs_total
+ *   obs_kf[o]            the keyframe table index of observation o         obs_idx[o]   its keypoint index in that keyframe
+ * The order inside a range is the iteration order of mObservations (pointer order in the reference; a caller pins it, e.g. to keyframe
+ * creation order).  The library never sorts it: the caller's order decides ties and the order of the float sum.
+ * The keyframe table is the one of msl_fuse_map_points (kps_un: the octave is read; desc; n_kps; Tcw; held_id) with cap keypoints per
+ * keyframe, plus kf_flags[k], bit 0: !isBad().  Point table: pt_xyz, pt_flags (bit 0: !isBad()) and pt_ref[id], the table index of mpRefKF.
+ * msl_refresh_map_points.  what: MSL_REFRESH_DESC | MSL_REFRESH_NORMAL, at least one.  With MSL_REFRESH_DESC alone kps_un, Tcw, pt_xyz and
+ * pt_ref may be NULL and desc may be any [n_tab][cap][32] descriptor table: with mLineDescriptors it is MapLine::
+ * ComputeDistinctiveDescriptors (src/MapLine.cpp:195-255), the same selection over 32-byte rows (ids are then line ids, n_kps line counts).
+ * Out, per item f:
+ *   out_desc[32 f..], out_normal[3 f..], out_dist[2 f..]   mDescriptor; mNormalVector; mfMinDistance, mfMaxDistance -- zeros for a field
+ *                                                          the reference leaves unchanged
+ *   best_obs[f]      the position, in the point's own observation range, of the observation whose descriptor was chosen; -1 for none
+ *   best_median[f]   its median distance (0 for none)        status[f]   MSL_REFRESH_* bits
+ * pt_desc, pt_normal, pt_dist (each may be NULL; in out_mem memory): the point table.  A field that is written (status) is also written at
+ * row ids[f], and only there: every other row, and the row of a field the reference leaves unchanged, keeps its bytes (a host-memory
+ * table is staged whole and copied back whole; the device-memory form touches the rows alone).
+ * Reproduced exactly (tests/mappoint_model.py is the sequential model):
+ *   descriptor   the descriptors of the observations whose keyframe is not bad, in list order, N of them; the median of row i is the
+ *                element (int)(0.5 * (N - 1)) of its sorted distances, the 0 on the diagonal included; the first i with a strictly
+ *                smaller median wins (N = 1, 2: the first).  More than MSL_OBS_MAX live observations: MSL_REFRESH_TOO_MANY, the
+ *                descriptor is unchanged and the caller does this point itself (the limit is the LDS budget of the selection).
+ *   normal       every observation counts, bad keyframes included (UpdateNormalAndDepth has no isBad test): Ow from Tcw as KeyFrame::
+ *                SetPose (cv::gemm's float kernel); normali = xyz - Ow in float; its norm the square root of a double sum; acc = acc +
+ *                (float)((double)normali[a] * (1.0 / norm)) in list order from 0.0f; normal[a] = (float)((double)acc * (1.0 / n)) -- the
+ *                two-observation form of msl_triangulate_new_points extended to n terms
+ *   distances    max = (float)norm(xyz - Ow_ref) * scale_factors[level], min = max / scale_factors[nlevels - 1]; level = the octave of
+ *                keypoint observations[pRefKF] of the reference keyframe
+ * Pins: a pt_ref that is not among the point's observations has keypoint index 0 (map::operator[]); an octave outside [0, nlevels) is
+ * MSL_REFRESH_BAD_OCTAVE and leaves normal and distances unchanged; non-finite values propagate by IEEE rules (a point at a camera
+ * centre has a NaN normal).
+ * msl_covisibility.  For every slot i < n_kps[k] of keyframe k = kf[f] whose held_id is a point of the table that is not bad, every
+ * observation of that point in a keyframe other than k adds one to that keyframe's counter (a bad observer counts, the reference has no
+ * test; a point held in two slots counts twice, as in the reference's slot loop).  obs_idx is not read.  Out:
+ *   weight[f * n_tab + j]          KFcounter, 0 = absent
+ *   conn, conn_w [f * ccap + r]    mvpOrderedConnectedKeyFrames / mvOrderedWeights: the keyframes with weight >= th by descending weight,
+ *                                  equal weights by descending table index (sort of pair<int, KeyFrame*> + push_front, pointer order
+ *                                  pinned to table order); if none reaches th, the single keyframe of maximum weight, the lowest index
+ *                                  among equal maxima (strict > in ascending order)
+ *   n_conn[f]                      the full count: entries beyond ccap are dropped, so the caller compares n_conn with ccap; slots beyond
+ *                                  the count are -1 (conn) and 0 (conn_w)
+ * An empty counter gives n_conn = 0 and an all-zero weight row: the reference's early return, the caller leaves its connections alone.
+ * AddConnection on the other keyframes, the parent / child link and the assignment of the maps stay with the caller, which reads them
+ * from weight and conn.
+ * Limits: n_tab <= 4096, cap <= 8192, n_pts <= 1048576, n_items <= n_pts (refresh) / <= n_tab (covisibility), ccap <= n_tab, nlevels <=
+ * MSL_MATCH_MAX_LEVELS, what non-zero and inside the mask; anything else is refused with MSL_ERR_INVALID before any launch, with
+ * msl_last_error() naming the field, and nothing is written.  A host-memory call (mem) also checks the index arrays and refuses a
+ * violation: obs_off ascending with obs_off[n_pts] == n_obs_total, obs_kf inside the table, obs_idx < n_kps[obs_kf], ids / kf in range,
+ * ids distinct, pt_ref of every item in range.  With device memory these are the caller's contract: an observation whose obs_kf is outside
+ * the table is skipped by both entries as if absent, one whose obs_idx is outside [0, cap) has no descriptor, an id outside the point table
+ * is a bad point, a kf outside the table has an empty counter, a pt_ref outside the table is MSL_REFRESH_BAD_OCTAVE, a repeated id goes
+ * unnoticed (its table row is written twice).  Memory and synchronisation as msl_bow_transform. */
+typedef struct msl_refresh_params {
+    int32_t nlevels;                                 /* mnScaleLevels */
+    float scale_factors[MSL_MATCH_MAX_LEVELS];       /* mvScaleFactors */
+} msl_refresh_params;
+#define MSL_OBS_MAX                 256   /* the most live observations msl_refresh_map_points selects a descriptor from */
+#define MSL_REFRESH_DESC              1   /* what: ComputeDistinctiveDescriptors */
+#define MSL_REFRESH_NORMAL            2   /* what: UpdateNormalAndDepth */
+#define MSL_REFRESH_DESC_WRITTEN      1   /* status: descriptor written */
+#define MSL_REFRESH_NORMAL_WRITTEN    2   /* normal and distances written */
+#define MSL_REFRESH_BAD               4   /* the point is bad: nothing */
+#define MSL_REFRESH_NO_OBS            8   /* no observations: nothing */
+#define MSL_REFRESH_NO_LIVE_KF       16   /* every observing keyframe is bad: descriptor unchanged (normal and distances still written) */
+#define MSL_REFRESH_TOO_MANY         32   /* more than MSL_OBS_MAX observations in live keyframes: descriptor unchanged */
+#define MSL_REFRESH_BAD_OCTAVE       64   /* the reference keypoint's octave is outside [0, nlevels): normal and distances unchanged */
+MSL_API int msl_refresh_map_points(msl_match *h, int n_tab, int cap, int n_pts, int n_items, int n_obs_total, int what,
+                                   const msl_refresh_params *params, const msl_keypoint *kps_un, const uint8_t *desc, const int32_t *n_kps,
+                                   const float *Tcw, const uint8_t *kf_flags, const int32_t *obs_off, const int32_t *obs_kf,
+                                   const int32_t *obs_idx, const float *pt_xyz, const uint8_t *pt_flags, const int32_t *pt_ref,
+                                   const int32_t *ids, msl_mem mem, uint8_t *out_desc, float *out_normal, float *out_dist, int32_t *best_obs,
+                                   int32_t *best_median, uint8_t *status, uint8_t *pt_desc, float *pt_normal, float *pt_dist,
+                                   msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device matcher handle, always synchronous; see msl_match_by_projection_batch). */
+MSL_API int msl_refresh_map_points_batch(int device, int n_tab, int cap, int n_pts, int n_items, int n_obs_total, int what,
+                                         const msl_refresh_params *params, const msl_keypoint *kps_un, const uint8_t *desc,
+                                         const int32_t *n_kps, const float *Tcw, const uint8_t *kf_flags, const int32_t *obs_off,
+                                         const int32_t *obs_kf, const int32_t *obs_idx, const float *pt_xyz, const uint8_t *pt_flags,
+                                         const int32_t *pt_ref, const int32_t *ids, msl_mem mem, uint8_t *out_desc, float *out_normal,
+                                         float *out_dist, int32_t *best_obs, int32_t *best_median, uint8_t *status, uint8_t *pt_desc,
+                                         float *pt_normal, float *pt_dist, msl_mem out_mem) MSL_NOEXCEPT;
+MSL_API int msl_covisibility(msl_match *h, int n_tab, int cap, int n_pts, int n_items, int n_obs_total, int ccap, int th,
+                             const int32_t *held_id, const int32_t *n_kps, const uint8_t *pt_flags, const int32_t *obs_off,
+                             const int32_t *obs_kf, const int32_t *kf, msl_mem mem, int32_t *weight, int32_t *conn, int32_t *conn_w,
+                             int32_t *n_conn, msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device matcher handle, always synchronous). */
+MSL_API int msl_covisibility_batch(int device, int n_tab, int cap, int n_pts, int n_items, int n_obs_total, int ccap, int th,
+                                   const int32_t *held_id, const int32_t *n_kps, const uint8_t *pt_flags, const int32_t *obs_off,
+                                   const int32_t *obs_kf, const int32_t *kf, msl_mem mem, int32_t *weight, int32_t *conn, int32_t *conn_w,
+                                   int32_t *n_conn, msl_mem out_mem) MSL_NOEXCEPT;
+
 /* msl_kfdb: a KeyFrameDatabase (src/KeyFrameDatabase.cc:38-66) on one device.  msl_kfdb_create returns NULL with msl_last_error() when no
  * device is usable.  msl_kfdb_add stores the BowVector of one keyframe exactly as msl_bow_transform wrote it (ascending int32 words, double
  * values, the count -- on the device for MSL_MEM_DEVICE) and returns its slot when the vector is stored; with device memory `h` is the

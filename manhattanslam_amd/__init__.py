@@ -29,3 +29,5 @@ from . import triangulate  # noqa: F401
 from ._lib import TRIANGULATE_PARAMS_DTYPE  # noqa: F401
 from . import fuse  # noqa: F401
 from ._lib import FUSE_PARAMS_DTYPE  # noqa: F401
+from . import mappoint  # noqa: F401
+from ._lib import REFRESH_PARAMS_DTYPE  # noqa: F401
