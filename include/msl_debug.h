@@ -71,7 +71,7 @@ MSL_API int msl_debug_deal(const uint32_t *keys_host, int n_subblocks, uint32_t 
 /* Test hook: out[i] = the kernels' division-free evaluation of (double)(x[i]*x[i]) / 100.0 (host arrays). */
 MSL_API int msl_debug_div100(const float *x_host, double *out_host, size_t n) MSL_NOEXCEPT;
 /* Test hook: out[q] = the strictly sequential (left-to-right) float sum of the first n[q] <= 256 entries of list q (256 floats each) as the superpixel
- * kernels evaluate it -- a rotating chain over 16 lanes (msl_sf_superpixel.hip); huber != 0: entries +-inf stand for the Huber tail's DOUBLE constant
+ * kernels evaluate it -- a rotating chain over 16 lanes (msl_sf_sp_dev.h); huber != 0: entries +-inf stand for the Huber tail's DOUBLE constant
  * +-0.4 (src/SurfelFusion.cpp:494-503).  Host arrays; synchronous. */
 MSL_API int msl_debug_chain_sum(const float *x_host, const int32_t *n_host, int lists, int huber, float *out_host) MSL_NOEXCEPT;
 

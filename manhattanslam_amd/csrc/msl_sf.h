@@ -1,5 +1,8 @@
 // msl_sf.h -- types and device helpers shared by the translation units of the surfel-fusion path (internal):
-//   msl_sf_superpixel.hip  frame-batched superpixel stage (generateSuperPixels, src/SurfelFusion.cpp:333-773)
+//   msl_sf_superpixel.hip  frame-batched superpixel stage (generateSuperPixels, src/SurfelFusion.cpp:333-773): launch sequence, raw-depth conversion
+//   msl_sf_sp_assign.hip   superpixel stage: seed initialisation, pixel assignment and relaxation
+//   msl_sf_sp_seeds.hip    superpixel stage: seed update
+//   msl_sf_sp_plane.hip    superpixel stage: plane fit, FuseRec, candidate surfels
 //   msl_sf_fuse.hip        map stage: fusion (:167-283)
 //   msl_sf_compact.hip     map stage: new surfels (:285-331), compaction (src/SurfelMapping.cpp:366-391), dealing of the sub-blocks
 //   msl_sf_replay.hip      map stage: the end of a deferred-compaction window
@@ -9,7 +12,7 @@
 //   msl_sf_store.hip       the resident map as the host sees it: layout, live-count bookkeeping, the map-exchange ABI
 //   msl_sf_hostvec.hip     the host-vector drop-in msl_sf_fuse / msl_sf_fuse_ex (its transfer planner: msl_sf_plan.h)
 //   msl_sf_debug.hip       debug accessors, kernel names
-// (what only the four map-stage units share, and the stage's overview: msl_sf_map_dev.h)
+// (what only the four map-stage units share, and the stage's overview: msl_sf_map_dev.h; what only the four superpixel units share: msl_sf_sp_dev.h)
 #pragma once
 
 #include "msl_common.h"
@@ -154,7 +157,7 @@ struct SfDev {
     uint8_t *candOk;             // [slots][flagStride]
     uint8_t *fused;              // [slots][flagStride] 1: seed consumed by a fusion; 2: invalid candidate (kb_seed_plane); 0: the seed spawns a surfel
     uint2 *tex;                  // [slots][npx] {depth bits, final superpixel index} of every pixel: k_fuse's ONE gather per in-view surfel
-    float4 *fuseRec;             // [slots][3][nseeds] what k_fuse needs of a seed (FuseRec, msl_sf_superpixel.hip), three planes of 16-byte words
+    float4 *fuseRec;             // [slots][3][nseeds] what k_fuse needs of a seed (FuseRec, msl_sf_sp_plane.hip), three planes of 16-byte words
     unsigned short *index, *amap;  // [slots][npx]
     unsigned *tmin;              // [slots][nseeds]
     AssignRec *arec;             // [slots][nseeds] (+ one record of padding at either end) what kb_assign reads of a seed
@@ -307,7 +310,7 @@ enum { SK_SEED_INIT = 0, SK_ASSIGN, SK_PROP, SK_COMMIT_PX, SK_UPDATE_SEEDS, SK_C
 #define MSL_SF_LAUNCH(prof, kid, st, kern, grid, block, ...) MSL_SF_LAUNCH_LDS(prof, kid, st, kern, grid, block, 0, __VA_ARGS__)
 
 // ---- host entry points of the kernel translation units (all asynchronous on the given stream) ----
-// msl_sf_superpixel.hip
+// msl_sf_superpixel.hip, msl_sf_sp_assign.hip (sp_init_attributes, sp_debug_div100), msl_sf_sp_seeds.hip (sp_debug_chain)
 bool sp_init_attributes(int nseeds);   // true: one keyframe's t(s) fits the LDS (single-launch relaxation)
 void sp_launch_stage(KernelProfiler &prof, hipStream_t st, const SfDev &P, int nFrames, bool propLds);
 // raw 16-bit depth -> float metres (src/Frame.cc:96-97) for nFrames images: src rows srcStride bytes apart, frames srcFrameStride bytes apart; dst tightly

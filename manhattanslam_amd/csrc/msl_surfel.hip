@@ -3,8 +3,8 @@
 //
 // Replaces SurfelFusion (reference src/SurfelFusion.cpp) and the slot refill / tail compaction of
 // SurfelMapping::fuseMap (src/SurfelMapping.cpp:353-392).  The kernels live in other translation units:
-//   msl_sf_superpixel.hip   generateSuperPixels() of a keyframe depends only on that keyframe's images, never on the map, so it is
-//                           FRAME-BATCHED on the "pre" stream (kb_* kernels, one launch sequence per batch of F keyframes);
+//   msl_sf_superpixel.hip   generateSuperPixels() of a keyframe depends only on that keyframe's images, never on the map, so it is FRAME-BATCHED on the
+//                           "pre" stream (one launch sequence per batch of F keyframes; its kb_* kernels by role: msl_sf_sp_assign / _seeds / _plane.hip);
 //   msl_sf_fuse.hip, msl_sf_compact.hip, msl_sf_replay.hip, msl_sf_map.hip (maintenance)
 //                           the map stage (fusion -> new surfels -> compaction) is sequential per keyframe, on the "map" stream:
 //                           k_fuse + k_compact per keyframe (classic), or ONE k_fuse launch per keyframe with the compactions of a

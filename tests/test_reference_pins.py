@@ -50,9 +50,9 @@ def test_surfel_fusion_macros(pins):
     assert pins["surfel_fusion"] == {"ITERATION_NUM": 3, "THREAD_NUM": 10, "SP_SIZE": 8, "MAX_ANGLE_COS": 0.1, "HUBER_RANGE": 0.4, "BASELINE": 0.5,
                                      "DISPARITY_ERROR": 4.0, "MIN_TOLERATE_DIFF": 0.1}
     csrc = os.path.join(ROOT, "manhattanslam_amd", "csrc")
-    hip = "".join(open(os.path.join(csrc, f)).read() for f in ("msl_sf.h", "msl_sf_map_dev.h", "msl_sf_superpixel.hip", "msl_sf_fuse.hip", "msl_sf_compact.hip", "msl_sf_replay.hip",
-                                                                    "msl_sf_map.hip", "msl_sf_handle.h", "msl_sf_plan.h", "msl_surfel.hip", "msl_sf_store.hip", "msl_sf_hostvec.hip",
-                                                                    "msl_sf_debug.hip"))
+    hip = "".join(open(os.path.join(csrc, f)).read() for f in ("msl_sf.h", "msl_sf_map_dev.h", "msl_sf_sp_dev.h", "msl_sf_superpixel.hip", "msl_sf_sp_assign.hip", "msl_sf_sp_seeds.hip",
+                                                                    "msl_sf_sp_plane.hip", "msl_sf_fuse.hip", "msl_sf_compact.hip", "msl_sf_replay.hip", "msl_sf_map.hip", "msl_sf_handle.h",
+                                                                    "msl_sf_plan.h", "msl_surfel.hip", "msl_sf_store.hip", "msl_sf_hostvec.hip", "msl_sf_debug.hip"))
     assert "constexpr int SP = 8;" in hip and "constexpr int NCHUNK = 10;" in hip
     assert "MAX_ANGLE_COS = 0.1, HUBER_RANGE = 0.4, MIN_TOLERATE_DIFF = 0.1" in hip
     assert "halfF = 0.5f * cameraF" in hip and "/ halfF * 4.0f" in hip          # BASELINE and DISPARITY_ERROR as exact float factors in k_fuse

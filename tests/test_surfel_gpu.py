@@ -554,6 +554,30 @@ def test_odd_seed_lattices_and_small_images(oracle, w, h):
     g.close()
 
 
+def test_superpixel_launch_sequence():
+    """The stage's host launch sequence, by the profiler's launch counts: seed init, 3 x (pixel pass, seed pass), plane stage -- the same for one
+    resident keyframe and for one batch of two (72 x 64: a 9 x 8 seed lattice, the single-launch relaxation)."""
+    from manhattanslam_amd import synth, SurfelFusion, SURFEL_DTYPE
+    w, h = 72, 64
+    intr = {k: v * (w / 640.0) for k, v in synth.TUM1.items()}
+    want = {"kb_seed_init": 1, "kb_assign": 3, "kb_prop": 2, "kb_commit_px": 2, "kb_update_seeds": 3, "kb_commit_seeds": 3, "kb_seed_plane": 1}
+    frames = [synth.surfel_frame(k, w, h, intr=intr) for k in range(2)]
+    for batch in (False, True):
+        g = SurfelFusion(w, h, intr["fx"], intr["fy"], intr["cx"], intr["cy"], 30.0, 0.5)
+        g.map_upload(synth.surfel_map(2000, ref=0).astype(SURFEL_DTYPE))
+        g.set_batch_capacity(2)
+        g.profile_stride(1)
+        g.profile_enable(-1)
+        if batch:
+            g.fuse_resident_batch([0, 1], *(np.stack([f[i] for f in frames]) for i in range(3)), [f[3] for f in frames])
+        else:
+            g.fuse_resident(0, *frames[0])
+        got = {k: c for k, (ms, c) in g.profile_read().items() if k in want}
+        print("batch" if batch else "single", got)
+        assert got == want, (batch, got)
+        g.close()
+
+
 def test_large_image_uses_relaxation_fallback(oracle):
     """2048 x 1536: 49 152 seeds exceed the LDS-resident relaxation kernel, so the multi-launch fallback runs (two keyframes)."""
     from manhattanslam_amd import synth, SURFEL_DTYPE
