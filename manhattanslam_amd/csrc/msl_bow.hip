@@ -44,7 +44,7 @@ struct msl_vocab {
 
 namespace {
 
-constexpr int MAX_CAP = 8192, MAX_LCAP = 256, MAX_K = 20, MAX_L = 10;
+constexpr int MAX_LCAP = 256, MAX_K = 20, MAX_L = 10;
 constexpr int IDX_BITS = 13;                       // feature index < MAX_CAP
 constexpr int VEC_NT = 1024, BOW_NT = 1024, LD_NT = 256;
 constexpr unsigned long long KEY_NONE = ~0ull;

@@ -118,6 +118,19 @@ __device__ __forceinline__ unsigned wave_incl_scan(unsigned v) {
     return (unsigned)x;
 }
 
+// The smallest key / the sum over the 64 lanes, in every lane (butterfly of __shfl_xor).  With (distance << bits | index) keys the minimum
+// is the smallest distance, the lowest index on ties.
+__device__ __forceinline__ unsigned wave_min(unsigned key) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) { const unsigned o = (unsigned)__shfl_xor((int)key, off); key = o < key ? o : key; }
+    return key;
+}
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
 // Block-wide exclusive scan of one value per thread (blockDim.x multiple of 64, <= 1024).
 // s_wave must hold >= 17 unsigned. Returns the exclusive prefix; *total gets the block sum.
 // Two barriers, no serial section: every thread folds the <= 16 wave totals itself (LDS broadcast reads).

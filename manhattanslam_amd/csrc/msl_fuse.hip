@@ -29,7 +29,7 @@ namespace {
 
 using namespace msl;
 
-constexpr int MAX_TAB = 4096, MAX_PTS = 1 << 20, MAX_LCAP = 65536, MAX_TCAP = 64, MAX_ITEMS = 4096;
+constexpr int MAX_LCAP = 65536, MAX_TCAP = 64, MAX_ITEMS = 4096;
 constexpr int HELD_NT = 1024, SEARCH_NT = 256, RESOLVE_NT = 1024, CAND_NT = 1024;
 constexpr unsigned ID_NONE = 0xFFFFFFFFu;
 constexpr size_t CAND_SCRATCH = (size_t)1 << 24;   // entries of msl_fuse_candidates' scratch: the items in flight share it
@@ -117,11 +117,12 @@ __global__ __launch_bounds__(SEARCH_NT) void k_fuse_search(FuseDev D) {
             R.ur = ur;
             const float maxDistance = 1.2f * D.dist[2 * (size_t)id + 1], minDistance = 0.8f * D.dist[2 * (size_t)id];
             float Ow[3];
-            gemm3(T, true, -1.0, tcw, nullptr, Ow);                            // KeyFrame::SetPose: Ow = -Rwc * tcw
+            camera_centre(T, Ow);
             const float PO[3] = {p3Dw[0] - Ow[0], p3Dw[1] - Ow[1], p3Dw[2] - Ow[2]};
-            double s2 = 0.0, dot = 0.0;
+            double s2 = 0.0;                                                   // cv::norm(PO): norm3_dacc, written out (k_fuse_search's text)
 #pragma unroll
-            for (int a = 0; a < 3; a++) { s2 += (double)PO[a] * (double)PO[a]; dot += (double)PO[a] * (double)D.normal[3 * (size_t)id + a]; }
+            for (int a = 0; a < 3; a++) s2 += (double)PO[a] * (double)PO[a];
+            const double dot = dot3_dacc(PO, D.normal + 3 * (size_t)id);
             const float dist3D = (float)sqrt(s2);
             status = MSL_FUSE_DISTANCE;
             if (dist3D < minDistance || dist3D > maxDistance) break;           // :459
@@ -169,7 +170,7 @@ __global__ __launch_bounds__(SEARCH_NT) void k_fuse_search(FuseDev D) {
                 }
             }
 #pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) {
+            for (int off = 32; off >= 1; off >>= 1) {                          // wave_min and wave_sum, one shuffle pair per offset
                 const unsigned ok = (unsigned)__shfl_xor((int)key, off);
                 key = ok < key ? ok : key;
                 cnt += __shfl_xor(cnt, off);
@@ -233,8 +234,7 @@ __global__ __launch_bounds__(RESOLVE_NT) void k_fuse_resolve(FuseDev D) {
         }
         D.status[fb + j] = (uint8_t)st; D.other[fb + j] = oth;
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) mine += __shfl_xor(mine, off);
+    mine = wave_sum(mine);
     __syncthreads();                                                           // the hits are read: s_hit[0] becomes the count
     if (threadIdx.x == 0) s_hit[0] = 0;
     __syncthreads();
@@ -300,9 +300,7 @@ __global__ __launch_bounds__(CAND_NT) void k_fuse_cand(CandDev D) {
 
 // ==== host side ==============================================================================================================================
 bool common_limits(const char *who, int n_tab, int cap, int n_pts, int n_items, int lcap) {
-    if (n_tab < 1 || n_tab > MAX_TAB) { set_error("%s: n_tab %d outside 1 .. %d", who, n_tab, MAX_TAB); return false; }
-    if (cap < 1 || cap > MAX_CAP) { set_error("%s: cap %d outside 1 .. %d", who, cap, MAX_CAP); return false; }
-    if (n_pts < 1 || n_pts > MAX_PTS) { set_error("%s: n_pts %d outside 1 .. %d", who, n_pts, MAX_PTS); return false; }
+    if (!table_limits(who, n_tab, cap, n_pts)) return false;
     if (n_items < 1 || n_items > MAX_ITEMS) { set_error("%s: n_items %d outside 1 .. %d", who, n_items, MAX_ITEMS); return false; }
     if (lcap < 1 || lcap > MAX_LCAP) { set_error("%s: lcap %d outside 1 .. %d", who, lcap, MAX_LCAP); return false; }
     return true;

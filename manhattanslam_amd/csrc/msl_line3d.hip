@@ -11,16 +11,16 @@
 //
 // Pins where the reference is undefined or not restated (tests/line3d_model.py is the
 // sequential model and the kernel runs every sum in the order that model states):
-//   * cv::SVD: both uses are the cyclic Jacobi eigen-solver of msl_pnp.hip on a symmetric 3x3 matrix (n = 3: the round-robin steps are the
-//     pairs (1,2), (0,2), (0,1); 16 sweeps; eigenpairs by descending eigenvalue, no sign normalisation), here in registers.  For a sample
+//   * cv::SVD: both uses are the cyclic Jacobi eigen-solver of msl_jacobi.h on a symmetric 3x3 matrix (jacobi_sweep<3>, in registers: the
+//     round-robin steps are the pairs (1,2), (0,2), (0,1); 16 sweeps; eigenpairs by descending eigenvalue, no sign normalisation).  For a sample
 //     the matrix is cov0 (its upper triangle mirrored), DU = diag(1 / sqrt(w)) U^T; for the refit it is P^T P of the centred inliers with
 //     left-to-right sums in ascending sample order, the direction its top eigenvector.  The sign of d only swaps A and B.
-//   * rand() % left: draw j of iteration k = fmix32(fmix32(seed ^ k * 0x9E3779B1) ^ (j + 1) * 0x85EBCA77), mulhi32(hash, left); one seed
-//     per keyline
+//   * rand() % left: draw j of iteration k = msl_match_math.h's sampler_draw (the sampler of msl_pnp_ransac); one seed per keyline
 //   * the "NULL" Vector6d: line_ok says whether a line was returned; line_xyz of a failed keyline is six zeros
 //   * numSmp == 0 (a division by zero) and fewer than min_points samples: no line
 //   * GetLineDepth outside the image: -1.0f
 //   * non-finite values propagate by IEEE rules; a NaN distance is not an inlier; a NaN sample position is dropped by the bounds test
+#include "msl_jacobi.h"
 #include "msl_match_handle.h"
 #include "msl_match_math.h"
 
@@ -33,7 +33,6 @@ namespace {
 using namespace msl;
 
 constexpr int MAX_LCAP = 256, MAX_SAMPLES = 127, MAX_ITERS = 64, NS = 128;
-constexpr int L3_SWEEPS = 16;                // as PNP_SWEEPS
 constexpr double L3_EPS = 1e-10;             // 3DLineExtractor.h's EPS
 
 // What msl_lines_3d_debug reads back per keyline.
@@ -70,45 +69,12 @@ struct L3Work {
 
 __device__ __forceinline__ V3 sample(const L3Work &W, int k) { return {W.pos[k][0], W.pos[k][1], W.pos[k][2]}; }
 
-__device__ __forceinline__ unsigned fmix32(unsigned h) {
-    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
-    return h;
-}
-
-// One Jacobi rotation of the pair (P, Q): the angle from A, rows P and Q of A, then columns P and Q of A and of V (msl_pnp.hip's step).
-template <int P, int Q>
-__device__ __forceinline__ void rot3(double (&A)[9], double (&V)[9]) {
-    const double app = A[P * 3 + P], aqq = A[Q * 3 + Q], apq = A[P * 3 + Q];
-    if (apq == 0) return;
-    const double theta = (aqq - app) / (2.0 * apq);
-    const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        const double x = A[P * 3 + j], y = A[Q * 3 + j];
-        A[P * 3 + j] = c * x - s * y; A[Q * 3 + j] = s * x + c * y;
-    }
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        const double x = A[i * 3 + P], y = A[i * 3 + Q];
-        A[i * 3 + P] = c * x - s * y; A[i * 3 + Q] = s * x + c * y;
-    }
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        const double x = V[i * 3 + P], y = V[i * 3 + Q];
-        V[i * 3 + P] = c * x - s * y; V[i * 3 + Q] = s * x + c * y;
-    }
-}
-
 // Eigenpairs of the symmetric 3x3 A, in registers: d[3] descending (the lower index first on ties), ut[3][3] with the eigenvectors as rows.
+// msl_jacobi.h's sweeps from V = identity, then the ranking by counting.
 __device__ __forceinline__ void jacobi3(double (&A)[9], double (&d)[3], double (&ut)[9]) {
     double V[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
 #pragma unroll 1
-    for (int sw = 0; sw < L3_SWEEPS; sw++) {
-        rot3<1, 2>(A, V);
-        rot3<0, 2>(A, V);
-        rot3<0, 1>(A, V);
-    }
+    for (int sw = 0; sw < JACOBI_SWEEPS; sw++) jacobi_sweep<3>(A, V);
     const double d0 = A[0], d1 = A[4], d2 = A[8];
     const int r0 = (d1 > d0 ? 1 : 0) + (d2 > d0 ? 1 : 0);
     const int r1 = ((d0 > d1 || d0 == d1) ? 1 : 0) + (d2 > d1 ? 1 : 0);
@@ -302,10 +268,10 @@ __global__ __launch_bounds__(WAVE) void k_line3d(Line3dDev D) {
         for (int it = 0; it < maxIt; it++) {
             nIter = it + 1;
             if (lane == 0) {                                                       // random_unique(indexes, 2)
-                const unsigned h0 = fmix32(seed ^ (unsigned)it * 0x9E3779B1u);
+                const unsigned h0 = fmix32(seed ^ (unsigned)it * 0x9E3779B1u);    // = sampler_iteration(seed, it)
 #pragma unroll
                 for (int u = 0; u < 2; u++) {
-                    const int r = (int)__umulhi(fmix32(h0 ^ (unsigned)(u + 1) * 0x85EBCA77u), (unsigned)(n - u));
+                    const int r = sampler_draw(h0, u, (unsigned)(n - u));
                     const int t = W.idx[u]; W.idx[u] = W.idx[u + r]; W.idx[u + r] = t;
                 }
                 W.ia = W.idx[0]; W.ib = W.idx[1];
@@ -367,9 +333,8 @@ __global__ __launch_bounds__(WAVE) void k_line3d(Line3dDev D) {
         if ((double)best / len > D.minSupport && norm(A - B) > D.minLength) {
             ok = 1;
             const float *Tc = D.Tcw + f * 12;
-            const float tcw[3] = {Tc[3], Tc[7], Tc[11]};
             float Ow[3];
-            gemm3(Tc, true, -1.0, tcw, nullptr, Ow);                               // mOw = -mRcw.t() * mtcw
+            camera_centre(Tc, Ow);                                                 // mOw = -mRcw.t() * mtcw
             const float Ac[3] = {(float)A.x, (float)A.y, (float)A.z}, Bc[3] = {(float)B.x, (float)B.y, (float)B.z};
             gemm3(Tc, true, 1.0, Ac, Ow, Aw);                                      // mRwc * Ac + mOw
             gemm3(Tc, true, 1.0, Bc, Ow, Bw);

@@ -22,7 +22,7 @@ namespace {
 
 using namespace msl;
 
-constexpr int MAX_TAB = 4096, MAX_CAP = 8192, MAX_PTS = 1 << 20, COVIS_NT = 1024, IDX_BITS = 12;
+constexpr int COVIS_NT = 1024, IDX_BITS = 12;
 static_assert(MAX_TAB == 1 << IDX_BITS && (MSL_OBS_MAX & (MSL_OBS_MAX - 1)) == 0 && MSL_OBS_MAX <= 256, "key layouts");
 
 struct RefreshDev {
@@ -35,19 +35,13 @@ struct RefreshDev {
     uint8_t *ptDesc; float *ptNormal, *ptDist;
 };
 
-__device__ __forceinline__ void camera_centre(const float *T, float Ow[3]) {
-    const float tcw[3] = {T[3], T[7], T[11]};
-    gemm3(T, true, -1.0, tcw, nullptr, Ow);                                    // Ow = -Rwc * tcw (KeyFrame::SetPose)
-}
-
 // v = X - Ow of keyframe pose T, in float; returns cv::norm(v), the square root of a double sum
 __device__ __forceinline__ double view_vector(const float *T, const float X[3], float v[3]) {
     float Ow[3];
     camera_centre(T, Ow);
-    double s = 0;
 #pragma unroll
-    for (int a = 0; a < 3; a++) { v[a] = X[a] - Ow[a]; s += (double)v[a] * (double)v[a]; }
-    return sqrt(s);
+    for (int a = 0; a < 3; a++) v[a] = X[a] - Ow[a];
+    return norm3_dacc(v);
 }
 
 // ==== ComputeDistinctiveDescriptors and UpdateNormalAndDepth of one point ====================================================================
@@ -124,11 +118,7 @@ __global__ __launch_bounds__(WAVE) void k_refresh(RefreshDev D) {
                     const unsigned kk = ((unsigned)lo << 8) | (unsigned)r;
                     key = kk < key ? kk : key;
                 }
-#pragma unroll
-                for (int off = 32; off >= 1; off >>= 1) {
-                    const unsigned ok = (unsigned)__shfl_xor((int)key, off);
-                    key = ok < key ? ok : key;
-                }
+                key = wave_min(key);
                 const int best = (int)(key & 255u);
                 bestMedian = (int)(key >> 8); bestObs = s_pos[best];
                 d0 = s_desc[2 * best]; d1 = s_desc[2 * best + 1];
@@ -227,10 +217,8 @@ __global__ __launch_bounds__(COVIS_NT) void k_covis(CovisDev D) {
 }
 
 // ==== host side ==============================================================================================================================
-bool table_limits(const char *who, int n_tab, int cap, int n_pts, int n_obs_total) {
-    if (n_tab < 1 || n_tab > MAX_TAB) { set_error("%s: n_tab %d outside 1 .. %d", who, n_tab, MAX_TAB); return false; }
-    if (cap < 1 || cap > MAX_CAP) { set_error("%s: cap %d outside 1 .. %d", who, cap, MAX_CAP); return false; }
-    if (n_pts < 1 || n_pts > MAX_PTS) { set_error("%s: n_pts %d outside 1 .. %d", who, n_pts, MAX_PTS); return false; }
+bool csr_limits(const char *who, int n_tab, int cap, int n_pts, int n_obs_total) {
+    if (!table_limits(who, n_tab, cap, n_pts)) return false;
     if (n_obs_total < 0) { set_error("%s: n_obs_total %d below 0", who, n_obs_total); return false; }
     return true;
 }
@@ -248,7 +236,7 @@ int run_refresh(msl_match *h, int n_tab, int cap, int n_pts, int n_items, int n_
         set_error("%s: invalid argument (null pointer)", who);
         return MSL_ERR_INVALID;
     }
-    if (!table_limits(who, n_tab, cap, n_pts, n_obs_total)) return MSL_ERR_INVALID;
+    if (!csr_limits(who, n_tab, cap, n_pts, n_obs_total)) return MSL_ERR_INVALID;
     if (n_items < 1 || n_items > n_pts) { set_error("%s: n_items %d outside 1 .. n_pts = %d", who, n_items, n_pts); return MSL_ERR_INVALID; }
     if (wantN && (prm->nlevels < 1 || prm->nlevels > MSL_MATCH_MAX_LEVELS)) { set_error("%s: nlevels %d outside 1 .. %d", who, prm->nlevels, MSL_MATCH_MAX_LEVELS); return MSL_ERR_INVALID; }
     if (mem == MSL_MEM_HOST) {
@@ -290,7 +278,7 @@ int run_covisibility(msl_match *h, int n_tab, int cap, int n_pts, int n_items, i
         set_error("%s: invalid argument (null pointer)", who);
         return MSL_ERR_INVALID;
     }
-    if (!table_limits(who, n_tab, cap, n_pts, n_obs_total)) return MSL_ERR_INVALID;
+    if (!csr_limits(who, n_tab, cap, n_pts, n_obs_total)) return MSL_ERR_INVALID;
     if (n_items < 1 || n_items > n_tab) { set_error("%s: n_items %d outside 1 .. n_tab = %d", who, n_items, n_tab); return MSL_ERR_INVALID; }
     if (ccap < 1 || ccap > n_tab) { set_error("%s: ccap %d outside 1 .. n_tab = %d", who, ccap, n_tab); return MSL_ERR_INVALID; }
     if (mem == MSL_MEM_HOST) {

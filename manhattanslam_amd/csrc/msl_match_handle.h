@@ -7,6 +7,18 @@
 namespace msl {
 // What msl_pnp_ransac's table N -> (minInliers, maxIts) was built from (no padding: compared bytewise).
 struct PnpKey { double probability; int32_t min_inliers, max_iterations, min_set; float epsilon; int32_t cap, zero; };
+
+// Limits that several entry points share: keypoints of a frame or keyframe (feature indices fit 13 bits, item positions 16), keyframes of
+// a keyframe table, points of a point table.
+constexpr int MAX_CAP = 8192, MAX_TAB = 4096, MAX_PTS = 1 << 20;
+
+// The limits of a call that takes a keyframe table and a point table; false with the error set.
+inline bool table_limits(const char *who, int n_tab, int cap, int n_pts) {
+    if (n_tab < 1 || n_tab > MAX_TAB) { set_error("%s: n_tab %d outside 1 .. %d", who, n_tab, MAX_TAB); return false; }
+    if (cap < 1 || cap > MAX_CAP) { set_error("%s: cap %d outside 1 .. %d", who, cap, MAX_CAP); return false; }
+    if (n_pts < 1 || n_pts > MAX_PTS) { set_error("%s: n_pts %d outside 1 .. %d", who, n_pts, MAX_PTS); return false; }
+    return true;
+}
 }  // namespace msl
 
 // One matcher object = one ORBmatcher of the reference (src/ORBmatcher.cc:41): its own stream and its own scratch, used by one thread at a time;

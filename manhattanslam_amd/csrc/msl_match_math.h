@@ -1,6 +1,7 @@
 // msl_match_math.h -- device arithmetic the searches on the matcher handle share, each piece pinned or written once
-// (internal): cv::gemm's 3x3 float kernel, the search mode, the popcount distance and descriptor load, the two-smallest-keys pair and its
-// wave reduction, the LDS key sort that groups features by vocabulary node, the rotation-consistency cull, the scale prediction.
+// (internal): cv::gemm's 3x3 float kernels, cv::invert, Mat::dot and cv::norm of float 3-vectors, the camera centre, the counter-based
+// sampler, the search mode, the popcount distance and descriptor load, the two-smallest-keys pair and its wave reduction, the LDS key sort
+// that groups features by vocabulary node, the rotation-consistency cull, the scale prediction.
 #pragma once
 
 #include "msl_common.h"
@@ -22,6 +23,57 @@ __device__ __forceinline__ void gemm3(const float *A, bool transA, double alpha,
         for (int k = 0; k < 3; k++) s += (double)(transA ? A[k * S + r] : A[r * S + k]) * (double)b[k];
         d[r] = (float)(s * alpha + (c ? (double)c[r] : 0.0));
     }
+}
+
+// D = alpha * op(A) op(B) for 3x3 float matrices of row stride SA / SB (D: stride 3): cv::gemm's float kernel, as gemm3
+template <int SA, int SB>
+__device__ __forceinline__ void gemm33(const float *A, bool tA, const float *B, bool tB, double alpha, float *Dm) {
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            double s = 0;
+#pragma unroll
+            for (int k = 0; k < 3; k++) s += (double)(tA ? A[k * SA + r] : A[r * SA + k]) * (double)(tB ? B[c * SB + k] : B[k * SB + c]);
+            Dm[r * 3 + c] = (float)(s * alpha + 0.0);
+        }
+}
+
+// cv::invert of a 3x3 float matrix (the closed form): determinant and cofactors in double, times 1 / det, each element rounded
+__device__ __forceinline__ void inv33(const float *m, float *o) {
+    const double m00 = m[0], m01 = m[1], m02 = m[2], m10 = m[3], m11 = m[4], m12 = m[5], m20 = m[6], m21 = m[7], m22 = m[8];
+    double d = m00 * (m11 * m22 - m12 * m21) - m01 * (m10 * m22 - m12 * m20) + m02 * (m10 * m21 - m11 * m20);
+    d = 1.0 / d;
+    o[0] = (float)((m11 * m22 - m12 * m21) * d); o[1] = (float)((m02 * m21 - m01 * m22) * d); o[2] = (float)((m01 * m12 - m02 * m11) * d);
+    o[3] = (float)((m12 * m20 - m10 * m22) * d); o[4] = (float)((m00 * m22 - m02 * m20) * d); o[5] = (float)((m02 * m10 - m00 * m12) * d);
+    o[6] = (float)((m10 * m21 - m11 * m20) * d); o[7] = (float)((m01 * m20 - m00 * m21) * d); o[8] = (float)((m00 * m11 - m01 * m10) * d);
+}
+
+// Mat::dot and cv::norm of float 3-vectors: double products summed in double from 0 in index order, sqrt in double; the caller rounds where
+// the reference assigns to float
+__device__ __forceinline__ double dot3_dacc(const float a[3], const float b[3]) {
+    double s = 0;
+#pragma unroll
+    for (int k = 0; k < 3; k++) s += (double)a[k] * (double)b[k];
+    return s;
+}
+__device__ __forceinline__ double norm3_dacc(const float v[3]) { return sqrt(dot3_dacc(v, v)); }
+
+// Ow = -Rwc * tcw of the pose T (rows 0-2 of Tcw): KeyFrame::SetPose
+__device__ __forceinline__ void camera_centre(const float *T, float Ow[3]) {
+    const float tcw[3] = {T[3], T[7], T[11]};
+    gemm3(T, true, -1.0, tcw, nullptr, Ow);
+}
+
+// The counter-based sampler of the RANSAC loops: draw j of iteration k, a value in [0, left) =
+// mulhi32(fmix32(fmix32(seed ^ k * 0x9E3779B1) ^ (j + 1) * 0x85EBCA77), left).  sampler_iteration is the inner hash, the same for every j.
+__device__ __forceinline__ unsigned fmix32(unsigned h) {
+    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
+    return h;
+}
+__device__ __forceinline__ unsigned sampler_iteration(unsigned seed, int k) { return fmix32(seed ^ (unsigned)k * 0x9E3779B1u); }
+__device__ __forceinline__ int sampler_draw(unsigned h0, int j, unsigned left) {
+    return (int)__umulhi(fmix32(h0 ^ (unsigned)(j + 1) * 0x85EBCA77u), left);
 }
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }

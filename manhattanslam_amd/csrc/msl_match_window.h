@@ -11,7 +11,6 @@ namespace msl {
 namespace {
 constexpr int GRID_ROWS = MSL_FRAME_GRID_ROWS, GRID_COLS = MSL_FRAME_GRID_COLS, NCELLS = GRID_ROWS * GRID_COLS;
 constexpr int CMAX = 32;                            // stored candidates per point; more are re-enumerated by k_match_assign
-constexpr int MAX_CAP = 8192;
 constexpr unsigned KEY_NONE = 0xFFFFFFFFu;          // no candidate key (dist << 16 | item position)
 constexpr int DIST_ANY = 257, DIST_BELOW_256 = 256; // distance caps of a candidate: the local search drops 256 (never best nor second)
 

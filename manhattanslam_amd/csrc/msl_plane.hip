@@ -156,7 +156,7 @@ __global__ __launch_bounds__(64) void k_plane_assign(AssocDev D) {
 
 // ---- DetectManhattan ----
 
-__device__ __forceinline__ float dot3(const float *a, const float *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+__device__ __forceinline__ float dot3_f32(const float *a, const float *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 __device__ __forceinline__ bool mf_vertical(float a, float th) { return !(a > th || a < -th); }
 
 // The map plane held by frame plane i (mvpMapPlanes[i]) when it is not NULL and not bad, else -1.
@@ -208,13 +208,13 @@ __device__ int score_of(const MfDev &D, const MfFrame &S, int f, int i, int j, i
     if (m1 < 0 || m2 < 0) return 0;
     const float *c1 = S.coef[i], *c2 = S.coef[j];
     const float th = D.prm.mf_ver_th;
-    if (!mf_vertical(dot3(c1, c2), th)) return 0;                                    // angle12 (:675-681)
+    if (!mf_vertical(dot3_f32(c1, c2), th)) return 0;                                    // angle12 (:675-681)
     const int kcap = D.kcap, pcap = D.pcap;
     if (c < np) {
         const int m3 = S.held[c];
         if (m3 < 0) return 0;
         const float *c3 = S.coef[c];
-        if (!mf_vertical(dot3(c1, c3), th) || !mf_vertical(dot3(c2, c3), th)) return 0;   // (:691-701)
+        if (!mf_vertical(dot3_f32(c1, c3), th) || !mf_vertical(dot3_f32(c2, c3), th)) return 0;   // (:691-701)
         int key[3] = {m1, m2, m3};
         sort3(key[0], key[1], key[2]);
         const int32_t *tab = D.fullTab + (size_t)f * D.fcap * 7;

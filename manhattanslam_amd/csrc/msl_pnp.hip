@@ -10,13 +10,16 @@
 //
 // Pins where the reference is undefined or not restated (tests/pnp_model.py is the sequential model):
 //   * sampling: draw j of iteration k = fmix32(fmix32(seed ^ k * 0x9E3779B1) ^ (j + 1) * 0x85EBCA77), randi = mulhi32(hash, available)
+//     (msl_match_math.h: sampler_draw)
 //   * cvSVD / cvSolve / cvInvert: a cyclic Jacobi method on the symmetric matrix (A^T A for the least-squares solves, the inverse and the
-//     3x3 SVD): round-robin steps of disjoint pairs, the angles of a step from the matrix before it, all row updates, then all column
-//     updates; PNP_SWEEPS sweeps, no convergence branch; a pair with a_pq == 0 is skipped; eigenpairs sorted by descending eigenvalue, the
-//     lower index first on ties, no sign normalisation; + - * / sqrt only
+//     3x3 SVD), msl_jacobi.h's schedule and rotation run by the whole wave: round-robin steps of disjoint pairs, the angles of a step from
+//     the matrix before it, all row updates, then all column updates; JACOBI_SWEEPS sweeps, no convergence branch; a pair with a_pq == 0
+//     is skipped; eigenpairs sorted by descending eigenvalue, the lower index first on ties, no sign normalisation; + - * / sqrt only
 //   * every sum over correspondences runs left to right from 0.0 in one lane; the lanes share out the ENTRIES (the 78 of M^T M, the 9 of ABt)
 //   * gauss_newton's X starts as zeros (qr_solve's singular early-out leaves it as it was)
+#include "msl_jacobi.h"
 #include "msl_match_handle.h"
+#include "msl_match_math.h"
 
 #include <cmath>
 #include <cstring>
@@ -26,8 +29,7 @@ namespace {
 
 using namespace msl;
 
-constexpr int MAX_CAP = 8192, MAX_KCAP = 32768, MAX_ITS = 1024;
-constexpr int PNP_SWEEPS = 16;               // the measurement behind the number
+constexpr int MAX_KCAP = 32768, MAX_ITS = 1024;
 constexpr double PINV_TOL = 1e-12;           // eigenvalues of A^T A at or below PINV_TOL * the largest are dropped by the pseudo-inverse
 
 struct PnpDev {
@@ -68,31 +70,26 @@ struct Work {
     int idx[4];
 };
 
-__device__ __forceinline__ double dot3(const double *a, const double *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+__device__ __forceinline__ double dot3_f64(const double *a, const double *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 
 // Eigenpairs of the symmetric n x n matrix in W.A (n <= 12): d[n] descending, ut[n][n] with the eigenvectors as rows.  Whole wave.
 __device__ __forceinline__ void jacobi(Work &W, int n, double *d, double *ut) {
     const int lane = threadIdx.x;
     for (int e = lane; e < n * n; e += WAVE) W.V[e] = (e / n == e % n) ? 1.0 : 0.0;
-    const int m = n + (n & 1), half = m / 2;
+    const int steps = jacobi_steps(n), half = jacobi_slots(n);
     __syncthreads();
-    for (int sw = 0; sw < PNP_SWEEPS; sw++)
-        for (int r = 0; r < m - 1; r++) {
+    for (int sw = 0; sw < JACOBI_SWEEPS; sw++)
+        for (int r = 0; r < steps; r++) {
             if (lane < half) {
-                const int a = lane == 0 ? m - 1 : (r + lane) % (m - 1), b = lane == 0 ? r : (r - lane + m - 1) % (m - 1);
-                int p = a < b ? a : b, q = a < b ? b : a;
+                const JacobiPair pq = jacobi_pair(n, r, lane);
+                int p = pq.p;
+                const int q = pq.q;
                 if (q < n) {
-                    const double app = W.A[p * n + p], aqq = W.A[q * n + q], apq = W.A[p * n + q];
-                    if (apq == 0) {
-                        p = -1;
-                    } else {
-                        const double theta = (aqq - app) / (2.0 * apq);
-                        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                        const double c = 1.0 / sqrt(t * t + 1.0);
-                        W.c[lane] = c; W.s[lane] = t * c;
-                    }
+                    const JacobiRot R = jacobi_rotation(W.A[p * n + p], W.A[q * n + q], W.A[p * n + q]);
+                    if (R.skip) p = -1;                                       // a_pq == 0
+                    else { W.c[lane] = R.c; W.s[lane] = R.s; }
                 } else {
-                    p = -1;
+                    p = -1;                                                   // the padding index
                 }
                 W.jp[lane] = p; W.jq[lane] = q;
             }
@@ -303,20 +300,20 @@ __device__ __forceinline__ void compute_pose(Work &W, const Corr &C, double fu, 
             for (int c = 0; c < 3; c++) dv[i][c] = v[3 * pa + c] - v[3 * pb + c];
         }
         double *row = W.L + 10 * lane;
-        row[0] = dot3(dv[0], dv[0]);
-        row[1] = 2.0 * dot3(dv[0], dv[1]);
-        row[2] = dot3(dv[1], dv[1]);
-        row[3] = 2.0 * dot3(dv[0], dv[2]);
-        row[4] = 2.0 * dot3(dv[1], dv[2]);
-        row[5] = dot3(dv[2], dv[2]);
-        row[6] = 2.0 * dot3(dv[0], dv[3]);
-        row[7] = 2.0 * dot3(dv[1], dv[3]);
-        row[8] = 2.0 * dot3(dv[2], dv[3]);
-        row[9] = dot3(dv[3], dv[3]);
+        row[0] = dot3_f64(dv[0], dv[0]);
+        row[1] = 2.0 * dot3_f64(dv[0], dv[1]);
+        row[2] = dot3_f64(dv[1], dv[1]);
+        row[3] = 2.0 * dot3_f64(dv[0], dv[2]);
+        row[4] = 2.0 * dot3_f64(dv[1], dv[2]);
+        row[5] = dot3_f64(dv[2], dv[2]);
+        row[6] = 2.0 * dot3_f64(dv[0], dv[3]);
+        row[7] = 2.0 * dot3_f64(dv[1], dv[3]);
+        row[8] = 2.0 * dot3_f64(dv[2], dv[3]);
+        row[9] = dot3_f64(dv[3], dv[3]);
         double d[3];
 #pragma unroll
         for (int c = 0; c < 3; c++) d[c] = W.cws[pa][c] - W.cws[pb][c];
-        W.rho[lane] = dot3(d, d);
+        W.rho[lane] = dot3_f64(d, d);
     }
     __syncthreads();
 #pragma unroll 1
@@ -406,12 +403,12 @@ __device__ __forceinline__ void compute_pose(Work &W, const Corr &C, double fu, 
             double *R = W.R[br], *t = W.t[br];
             const double det = R[0] * R[4] * R[8] + R[1] * R[5] * R[6] + R[2] * R[3] * R[7] - R[2] * R[4] * R[6] - R[1] * R[3] * R[8] - R[0] * R[5] * R[7];
             if (det < 0) { R[6] = -R[6]; R[7] = -R[7]; R[8] = -R[8]; }
-            t[0] = W.pc0[0] - dot3(R, W.cws[0]); t[1] = W.pc0[1] - dot3(R + 3, W.cws[0]); t[2] = W.pc0[2] - dot3(R + 6, W.cws[0]);
+            t[0] = W.pc0[0] - dot3_f64(R, W.cws[0]); t[1] = W.pc0[1] - dot3_f64(R + 3, W.cws[0]); t[2] = W.pc0[2] - dot3_f64(R + 6, W.cws[0]);
             // reprojection_error
             double sum2 = 0.0;
             for (int i = 0; i < n; i++) {
                 C.load(i, pw, u);
-                const double Xc = dot3(R, pw) + t[0], Yc = dot3(R + 3, pw) + t[1], inv_Zc = 1.0 / (dot3(R + 6, pw) + t[2]);
+                const double Xc = dot3_f64(R, pw) + t[0], Yc = dot3_f64(R + 3, pw) + t[1], inv_Zc = 1.0 / (dot3_f64(R + 6, pw) + t[2]);
                 const double ue = uc + fu * Xc * inv_Zc, ve = vc + fv * Yc * inv_Zc;
                 sum2 = sum2 + sqrt((u[0] - ue) * (u[0] - ue) + (u[1] - ve) * (u[1] - ve));
             }
@@ -488,11 +485,6 @@ __global__ __launch_bounds__(WAVE) void k_pnp_gather(PnpDev D) {
     }
 }
 
-__device__ __forceinline__ unsigned fmix32(unsigned h) {
-    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
-    return h;
-}
-
 __global__ __launch_bounds__(WAVE) void k_pnp_hypothesis(PnpDev D) {
     __shared__ Work W;
     const size_t f = blockIdx.y;
@@ -500,12 +492,11 @@ __global__ __launch_bounds__(WAVE) void k_pnp_hypothesis(PnpDev D) {
     const int N = D.N[f];
     if (k >= D.Kit[f]) return;
     if (lane == 0) {                                                           // the sample: swap-with-back removal without the list
-        const unsigned h0 = fmix32(D.seed[f] ^ (unsigned)k * 0x9E3779B1u);
+        const unsigned h0 = sampler_iteration(D.seed[f], k);
         int pos[4], val[4];
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-            const unsigned avail = (unsigned)(N - j);
-            const int r = (int)__umulhi(fmix32(h0 ^ (unsigned)(j + 1) * 0x85EBCA77u), avail);
+            const int r = sampler_draw(h0, j, (unsigned)(N - j));
             int v = r, back = N - 1 - j;
 #pragma unroll
             for (int q = 0; q < 4; q++) {                                      // later replacements shadow earlier ones

@@ -64,7 +64,7 @@ using namespace msl;
 namespace {
 
 
-constexpr int MAX_CAP = 8192, MAX_XCAP = 32768, MAX_LCAP = 256, MAX_PCAP = 64;
+constexpr int MAX_XCAP = 32768, MAX_LCAP = 256, MAX_PCAP = 64;
 constexpr int NT = 256;                       // four waves per frame
 constexpr int NRED = 28;                      // 21 H (lower triangle) + 6 b + robust chi2
 constexpr int MONO = 0, STEREO = 1, LINE = 2, PLANE = 3, PAR = 4, VER = 5;

@@ -27,8 +27,8 @@
 //   * comparisons against double literals (3.84, 5.991, 7.8, 0.9998) in double on the float operands; 100 * scaleFactor in float
 //   * cos(2 atan2(b / 2, depth)) = (d^2 - a^2) / (d^2 + a^2), a = b / 2 in float, the quotient in double, rounded to float
 //   * rows of A: a float multiply, then a float subtract
-//   * cv::SVD: the cyclic Jacobi eigen-solver of msl_pnp_ransac (16 sweeps, round-robin steps {(0,3),(1,2)}, {(1,3),(0,2)}, {(2,3),(0,1)},
-//     the angles of a step from the matrix before it, rows then columns) on A^T A in double (sums over the rows of A in order); vt.row(3) =
+//   * cv::SVD: the cyclic Jacobi eigen-solver of msl_jacobi.h (jacobi_sweep<4>: 16 sweeps, round-robin steps {(0,3),(1,2)}, {(1,3),(0,2)},
+//     {(2,3),(0,1)}, the angles of a step from the matrix before it, rows then columns) on A^T A in double (sums over the rows of A in order); vt.row(3) =
 //     the eigenvector of the smallest eigenvalue (the highest index on ties) cast to float; then == 0 on its fourth component and a float
 //     division
 //   * invz = (float)(1.0 / z); u = fx * x * invz + cx in float, left to right
@@ -37,6 +37,7 @@
 //   * a keypoint whose octave is outside [0, nlevels) is never searched, on either side
 //   * a table index outside [0, n_tab), or a neighbour equal to the current keyframe, that only the device can see: that neighbour is
 //     skipped (an invalid current keyframe has no keypoints)
+#include "msl_jacobi.h"
 #include "msl_match_handle.h"
 #include "msl_match_math.h"
 
@@ -46,9 +47,8 @@ namespace {
 
 using namespace msl;
 
-constexpr int MAX_CAP = 8192, MAX_NCAP = 16, IDX_BITS = 13;
+constexpr int MAX_NCAP = 16, IDX_BITS = 13;
 constexpr int GROUP_NT = 1024, SEARCH_NT = 256, VERDICT_NT = 64;
-constexpr int TRI_SWEEPS = 16;                     // as PNP_SWEEPS
 constexpr unsigned long long KEY_NONE = ~0ull;
 
 // What the geometry kernel leaves per (item, neighbour); msl_debug_triangulate reads F12, ex, ey, baseline.
@@ -99,50 +99,6 @@ __global__ __launch_bounds__(GROUP_NT) void k_tri_group(TriDev D) {
 }
 
 // ==== pair geometry ==========================================================================================================================
-// D = alpha * op(A) op(B) for 3x3 float matrices of row stride SA / SB (D: stride 3): cv::gemm's float kernel, as gemm3
-template <int SA, int SB>
-__device__ __forceinline__ void gemm33(const float *A, bool tA, const float *B, bool tB, double alpha, float *Dm) {
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            double s = 0;
-#pragma unroll
-            for (int k = 0; k < 3; k++) s += (double)(tA ? A[k * SA + r] : A[r * SA + k]) * (double)(tB ? B[c * SB + k] : B[k * SB + c]);
-            Dm[r * 3 + c] = (float)(s * alpha + 0.0);
-        }
-}
-
-// cv::invert of a 3x3 float matrix (the closed form): determinant and cofactors in double, times 1 / det, each element rounded
-__device__ __forceinline__ void inv33(const float *m, float *o) {
-    const double m00 = m[0], m01 = m[1], m02 = m[2], m10 = m[3], m11 = m[4], m12 = m[5], m20 = m[6], m21 = m[7], m22 = m[8];
-    double d = m00 * (m11 * m22 - m12 * m21) - m01 * (m10 * m22 - m12 * m20) + m02 * (m10 * m21 - m11 * m20);
-    d = 1.0 / d;
-    o[0] = (float)((m11 * m22 - m12 * m21) * d); o[1] = (float)((m02 * m21 - m01 * m22) * d); o[2] = (float)((m01 * m12 - m02 * m11) * d);
-    o[3] = (float)((m12 * m20 - m10 * m22) * d); o[4] = (float)((m00 * m22 - m02 * m20) * d); o[5] = (float)((m02 * m10 - m00 * m12) * d);
-    o[6] = (float)((m10 * m21 - m11 * m20) * d); o[7] = (float)((m01 * m20 - m00 * m21) * d); o[8] = (float)((m00 * m11 - m01 * m10) * d);
-}
-
-// (float)cv::norm of a float 3-vector
-__device__ __forceinline__ double norm3(const float v[3]) {
-    double s = 0;
-#pragma unroll
-    for (int k = 0; k < 3; k++) s += (double)v[k] * (double)v[k];
-    return sqrt(s);
-}
-
-__device__ __forceinline__ double dot3(const float a[3], const float b[3]) {
-    double s = 0;
-#pragma unroll
-    for (int k = 0; k < 3; k++) s += (double)a[k] * (double)b[k];
-    return s;
-}
-
-__device__ __forceinline__ void camera_centre(const float *T, float Ow[3]) {
-    const float tcw[3] = {T[3], T[7], T[11]};
-    gemm3(T, true, -1.0, tcw, nullptr, Ow);                                   // Ow = -Rwc * tcw (KeyFrame::SetPose)
-}
-
 __global__ __launch_bounds__(64) void k_tri_pair(TriDev D) {
     const int g = blockIdx.x * 64 + threadIdx.x;
     if (g >= D.nItems * D.ncap) return;
@@ -160,7 +116,7 @@ __global__ __launch_bounds__(64) void k_tri_pair(TriDev D) {
         const float *T1 = D.Tcw + (size_t)G.k1 * 12, *T2 = D.Tcw + (size_t)G.k2 * 12;
         camera_centre(T1, G.Ow1); camera_centre(T2, G.Ow2);
         const float vb[3] = {G.Ow2[0] - G.Ow1[0], G.Ow2[1] - G.Ow1[1], G.Ow2[2] - G.Ow1[2]};
-        G.baseline = (float)norm3(vb);
+        G.baseline = (float)norm3_dacc(vb);
         G.skip = G.baseline < D.prm.b ? 1 : 0;
         // ComputeF12
         const float t1w[3] = {T1[3], T1[7], T1[11]}, t2w[3] = {T2[3], T2[7], T2[11]};
@@ -250,8 +206,7 @@ __global__ __launch_bounds__(SEARCH_NT) void k_tri_search(TriDev D) {
                 }
                 if (__ballot(in) != ~0ull) break;                              // the node's run ended inside this chunk
             }
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) { const unsigned o = (unsigned)__shfl_xor((int)key, off); key = o < key ? o : key; }
+            key = wave_min(key);
             if (key != 0xFFFFFFFFu) {
                 best = MAX_CAP - 1 - (int)(key & (MAX_CAP - 1));
                 bin = rot_bin(kp1.angle - D.kps[b2 + best].angle);
@@ -262,37 +217,6 @@ __global__ __launch_bounds__(SEARCH_NT) void k_tri_search(TriDev D) {
 }
 
 // ==== triangulation verdict ==================================================================================================================
-// One step of the round-robin Jacobi sweep on the symmetric 4x4 A (with V): the angles of both disjoint pairs from the matrix before the
-// step, both row updates, then the column updates of A and V (msl_pnp.hip's step, in registers).
-template <int P, int Q>
-__device__ __forceinline__ bool jac_angle(const double (&A)[16], double &c, double &s) {
-    const double app = A[P * 4 + P], aqq = A[Q * 4 + Q], apq = A[P * 4 + Q];
-    if (apq == 0) return false;
-    const double theta = (aqq - app) / (2.0 * apq);
-    const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-    c = 1.0 / sqrt(t * t + 1.0); s = t * c;
-    return true;
-}
-template <int P, int Q>
-__device__ __forceinline__ void jac_rows(double (&A)[16], double c, double s) {
-#pragma unroll
-    for (int j = 0; j < 4; j++) { const double x = A[P * 4 + j], y = A[Q * 4 + j]; A[P * 4 + j] = c * x - s * y; A[Q * 4 + j] = s * x + c * y; }
-}
-template <int P, int Q>
-__device__ __forceinline__ void jac_cols(double (&X)[16], double c, double s) {
-#pragma unroll
-    for (int i = 0; i < 4; i++) { const double x = X[i * 4 + P], y = X[i * 4 + Q]; X[i * 4 + P] = c * x - s * y; X[i * 4 + Q] = s * x + c * y; }
-}
-template <int P0, int Q0, int P1, int Q1>
-__device__ __forceinline__ void jac_step(double (&A)[16], double (&V)[16]) {
-    double c0 = 1.0, s0 = 0.0, c1 = 1.0, s1 = 0.0;
-    const bool on0 = jac_angle<P0, Q0>(A, c0, s0), on1 = jac_angle<P1, Q1>(A, c1, s1);
-    if (on0) jac_rows<P0, Q0>(A, c0, s0);
-    if (on1) jac_rows<P1, Q1>(A, c1, s1);
-    if (on0) { jac_cols<P0, Q0>(A, c0, s0); jac_cols<P0, Q0>(V, c0, s0); }
-    if (on1) { jac_cols<P1, Q1>(A, c1, s1); jac_cols<P1, Q1>(V, c1, s1); }
-}
-
 // vt.row(3) of cv::SVD of the 4x4 float A (rows r0..r3), pinned: the eigenvector of the smallest eigenvalue of A^T A, cast to float
 __device__ __forceinline__ void null_vector(const float (&Am)[16], float x[4]) {
     double G[16], V[16];
@@ -307,11 +231,7 @@ __device__ __forceinline__ void null_vector(const float (&Am)[16], float x[4]) {
             V[i * 4 + j] = i == j ? 1.0 : 0.0;
         }
 #pragma unroll 1
-    for (int sw = 0; sw < TRI_SWEEPS; sw++) {
-        jac_step<0, 3, 1, 2>(G, V);
-        jac_step<1, 3, 0, 2>(G, V);
-        jac_step<2, 3, 0, 1>(G, V);
-    }
+    for (int sw = 0; sw < JACOBI_SWEEPS; sw++) jacobi_sweep<4>(G, V);
     // descending order with the lower index first on ties: the last is the smallest, the highest index among equals
     int m = 0; double dm = G[0];
     if (G[5] <= dm) { dm = G[5]; m = 1; }
@@ -341,7 +261,7 @@ __device__ __forceinline__ bool unproject(const TriDev &D, const float *T, const
 __device__ __forceinline__ bool reproj_bad(const msl_triangulate_params &K, const float *T, const float X[3], float z, const msl_keypoint &kp,
                                            float ur, bool stereo) {
     const float sigma2 = K.level_sigma2[kp.octave];
-    const float x = (float)(dot3(T, X) + (double)T[3]), y = (float)(dot3(T + 4, X) + (double)T[7]);
+    const float x = (float)(dot3_dacc(T, X) + (double)T[3]), y = (float)(dot3_dacc(T + 4, X) + (double)T[7]);
     const float invz = (float)(1.0 / (double)z);
     const float u = K.fx * x * invz + K.cx, v = K.fy * y * invz + K.cy;
     const float errX = u - kp.x, errY = v - kp.y;
@@ -371,7 +291,7 @@ __global__ __launch_bounds__(VERDICT_NT) void k_tri_verdict(TriDev D) {
     float ray1[3], ray2[3];
     gemm3(T1, true, 1.0, xn1, nullptr, ray1);
     gemm3(T2, true, 1.0, xn2, nullptr, ray2);
-    const float cosRays = (float)(dot3(ray1, ray2) / (norm3(ray1) * norm3(ray2)));
+    const float cosRays = (float)(dot3_dacc(ray1, ray2) / (norm3_dacc(ray1) * norm3_dacc(ray2)));
     float cosStereo = cosRays + 1;
     float cos1 = cosStereo, cos2 = cosStereo;
     if (s1) cos1 = cos_stereo(K.b, D.depth[i1]);
@@ -402,17 +322,17 @@ __global__ __launch_bounds__(VERDICT_NT) void k_tri_verdict(TriDev D) {
     if (status >= MSL_TRI_TRIANGULATED && status <= MSL_TRI_STEREO2) {
         const int made = status;
         // in front of both cameras, then the reprojection error in each
-        const float z1 = (float)(dot3(T1 + 8, X) + (double)T1[11]);
+        const float z1 = (float)(dot3_dacc(T1 + 8, X) + (double)T1[11]);
         if (z1 <= 0) status = MSL_TRI_Z1;
         else {
-            const float z2 = (float)(dot3(T2 + 8, X) + (double)T2[11]);
+            const float z2 = (float)(dot3_dacc(T2 + 8, X) + (double)T2[11]);
             if (z2 <= 0) status = MSL_TRI_Z2;
             else if (reproj_bad(K, T1, X, z1, kp1, ur1, s1)) status = MSL_TRI_REPROJ1;
             else if (reproj_bad(K, T2, X, z2, kp2, ur2, s2)) status = MSL_TRI_REPROJ2;
         }
         if (status == made) {
             const float n1v[3] = {X[0] - G.Ow1[0], X[1] - G.Ow1[1], X[2] - G.Ow1[2]}, n2v[3] = {X[0] - G.Ow2[0], X[1] - G.Ow2[1], X[2] - G.Ow2[2]};
-            const double nd1 = norm3(n1v), nd2 = norm3(n2v);
+            const double nd1 = norm3_dacc(n1v), nd2 = norm3_dacc(n2v);
             const float dist1 = (float)nd1, dist2 = (float)nd2;
             if (dist1 == 0 || dist2 == 0) status = MSL_TRI_ZERO_DIST;
             else {
