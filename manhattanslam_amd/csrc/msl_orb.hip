@@ -16,6 +16,7 @@
 
 #include "msl_orb_dev.h"
 #include "msl_orb_fast.h"
+#include "msl_orb_sums.h"
 
 #include <type_traits>
 
@@ -82,24 +83,37 @@ __global__ __launch_bounds__(256) void k_resize(OrbDev P, int l) {
 // the same source values, so the levels are the same bytes; every pixel of a level is written by exactly one workgroup.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_pyramid(OrbDev P) {
-    extern __shared__ uint8_t s_pyr[];
+    extern __shared__ __attribute__((aligned(16))) uint8_t s_pyr[];
     int tileI, frame;
     if (!xcd_item(P.pyrTX * P.pyrTY, P.nFrames, tileI, frame)) return;
     const int ti = tileI % P.pyrTX, tj = tileI / P.pyrTX;
     const int L = P.nlevels;
     PyrRange rx = P.pyrX[ti], ry = P.pyrY[tj];   // level 0: the input region
-    int sx0 = rx.needLo, sy0 = ry.needLo, sw = rx.needHi - rx.needLo, sh = ry.needHi - ry.needLo;
-    int spitch = (sw + 3) & ~3;   // row pitch of the level held in the source buffer: the input region is staged with whole dwords (round 6: four bytes per load --
-                                  // the byte-wise loop was 40 trips of a 64-bit address computation and one byte per thread), later levels are packed (pitch = width)
+    // The level held in the source buffer: pixel (x, y) at (y - soy) * spitch + (x - sox).  Every pitch is a multiple of four: the input region is
+    // staged with whole dwords (round 6: four bytes per load -- the byte-wise loop was 40 trips of a 64-bit address computation and one byte per
+    // thread), and a later level starts at the column needLo & ~3, so that a lane's run of four pixels is one aligned dword in LDS and in memory.
+    int sox = rx.needLo, soy = ry.needLo, spitch = (rx.needHi - rx.needLo + 3) & ~3;
+    // The column taps of a level's runs are read from LDS: staged (coalesced, once per workgroup) while the level before is computed, two rows of
+    // PYR_TAPS entries in turn.  Fetched from the table by each lane, four adjacent entries at a lane stride of 32 bytes, they cost four times the
+    // cache lines per load instruction of the one-pixel form, and the kernel took twice as long.
+    ResizeTap *const s_tx = reinterpret_cast<ResizeTap *>(s_pyr + P.pyrTapOff);
+    auto stage_taps = [&](int l) {   // level l's entries for the columns needLo & ~3 .. + 4 ng (those beyond the level's last column are the first of its row table)
+        const PyrRange r = P.pyrX[l * P.pyrTX + ti];
+        const int lo = r.needLo & ~3, n = (r.needHi - lo + 3) & ~3;
+        const ResizeTap *xtab = P.taps + P.lv[l].xtabOff + lo;
+        for (int c = threadIdx.x; c < n; c += 256) s_tx[(l & 1) * PYR_TAPS + c] = xtab[c];
+    };
+    if (L > 1) stage_taps(1);
     {
+        const int sh = ry.needHi - ry.needLo;
         int pitch;
         const uint8_t *img = level_ptr(P, frame, 0, pitch);
         const int nw = spitch >> 2, imgW = P.lv[0].w;
         const unsigned m = ((1u << 22) + nw - 1) / nw;   // exact floor(i / nw) for i < 2^15, nw < 2^7
         for (int i = threadIdx.x; i < nw * sh; i += 256) {
             const int r = (int)__umulhi((unsigned)i << 10, m), q = i - r * nw;   // (i m) >> 22
-            const int x = sx0 + 4 * q;
-            const uint8_t *src = img + (unsigned)((sy0 + r) * pitch + x);
+            const int x = sox + 4 * q;
+            const uint8_t *src = img + (unsigned)((soy + r) * pitch + x);
             unsigned v = 0;
             if (x + 3 < imgW) __builtin_memcpy(&v, src, 4);   // (bytes beyond the region but inside the image row: staged, never read)
             else
@@ -111,24 +125,49 @@ __global__ __launch_bounds__(256) void k_pyramid(OrbDev P) {
     for (int l = 1; l < L; l++) {
         const LevelDev &D = P.lv[l];
         const uint8_t *src = s_pyr + (((l - 1) & 1) ? P.pyrBuf0 : 0u);
-        uint8_t *dst = s_pyr + ((l & 1) ? P.pyrBuf0 : 0u);
+        unsigned *dst = reinterpret_cast<unsigned *>(s_pyr + ((l & 1) ? P.pyrBuf0 : 0u));
         rx = P.pyrX[l * P.pyrTX + ti]; ry = P.pyrY[l * P.pyrTY + tj];
-        const int dx0 = rx.needLo, dy0 = ry.needLo, dw = rx.needHi - rx.needLo, dh = ry.needHi - ry.needLo;
+        // A lane computes a run of four adjacent pixels of one row (the needed rectangle, widened to whole runs): one row tap and four column taps
+        // (adjacent entries of the staged table: 32 contiguous bytes of LDS) per run, the source bytes as aligned LDS words, one dword to LDS and -- where the run is
+        // owned -- one to memory.  The pixels are k_resize's, by the same expression (resize_px, msl_orb_sums.h).
+        const int dox = rx.needLo & ~3, doy = ry.needLo, ng = (rx.needHi - dox + 3) >> 2, dh = ry.needHi - ry.needLo;
         uint8_t *out = P.pyr + (size_t)frame * P.pyrStride + D.off;
-        const unsigned m = ((1u << 22) + dw - 1) / dw;
-        for (int i = threadIdx.x; i < dw * dh; i += 256) {
-            const int r = (int)__umulhi((unsigned)i << 10, m), c = i - r * dw;   // (i m) >> 22 without the 64-bit product
-            const int dx = dx0 + c, dy = dy0 + r;
-            const ResizeTap tx = P.taps[D.xtabOff + dx], ty = P.taps[D.ytabOff + dy];
-            const uint8_t *r0 = src + (ty.s0 - sy0) * spitch - sx0, *r1 = src + (ty.s1 - sy0) * spitch - sx0;
-            const int h0 = r0[tx.s0] * tx.c0 + r0[tx.s1] * tx.c1;
-            const int h1 = r1[tx.s0] * tx.c0 + r1[tx.s1] * tx.c1;
-            int v = (((ty.c0 * (h0 >> 4)) >> 16) + ((ty.c1 * (h1 >> 4)) >> 16) + 2) >> 2;
-            v = min(max(v, 0), 255);
-            dst[i] = (uint8_t)v;
-            if (dx >= rx.ownLo && dx < rx.ownHi && dy >= ry.ownLo && dy < ry.ownHi) out[(size_t)dy * D.pitch + dx] = (uint8_t)v;
+        const ResizeTap *ytab = P.taps + D.ytabOff, *xtap = s_tx + (l & 1) * PYR_TAPS;
+        if (l + 1 < L) stage_taps(l + 1);
+        const unsigned m = ((1u << 22) + ng - 1) / ng;
+        for (int i = threadIdx.x; i < ng * dh; i += 256) {
+            const int r = (int)__umulhi((unsigned)i << 10, m), g = i - r * ng;   // (i m) >> 22 without the 64-bit product
+            const int dx = dox + 4 * g, dy = doy + r;
+            const ResizeTap ty = ytab[dy];
+            ResizeTap tx[4];
+            __builtin_memcpy(tx, xtap + 4 * g, sizeof tx);
+            const int rb0 = (ty.s0 - soy) * spitch - sox, rb1 = (ty.s1 - soy) * spitch - sox;
+            // All four pixels are computed, without a branch: the words of the eight source pairs leave together.  A column outside the needed range
+            // (the run was widened to whole dwords) has its tap clamped into the source row, so that every address is a staged one; its byte is
+            // never read by the next level and never stored to memory.
+            unsigned pr0[4], pr1[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int s0 = min(max((int)tx[k].s0, sox), sox + spitch - 1);
+                const int a0 = rb0 + s0, a1 = rb1 + s0;   // (the same byte offset in their words: the pitch is a multiple of four)
+                const unsigned *w0 = reinterpret_cast<const unsigned *>(src + (a0 & ~3)), *w1 = reinterpret_cast<const unsigned *>(src + (a1 & ~3));
+                pr0[k] = resize_pair(w0[0], w0[1], a0 & 3); pr1[k] = resize_pair(w1[0], w1[1], a0 & 3);
+            }
+            unsigned run = 0;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const unsigned cx = (unsigned)(unsigned short)tx[k].c0 | ((unsigned)(unsigned short)tx[k].c1 << 16);
+                run |= resize_px(pr0[k], pr1[k], cx, ty.c0, ty.c1) << (8 * k);
+            }
+            dst[i] = run;
+            if (dy >= ry.ownLo && dy < ry.ownHi) {
+                uint8_t *o = out + (size_t)dy * D.pitch + dx;   // (dx is a multiple of four, and so are the level's offset and pitch)
+                if (dx >= rx.ownLo && dx + 3 < rx.ownHi) *reinterpret_cast<unsigned *>(o) = run;
+                else
+                    for (int k = 0; k < 4; k++) if (dx + k >= rx.ownLo && dx + k < rx.ownHi) o[k] = (uint8_t)(run >> (8 * k));
+            }
         }
-        sx0 = dx0; sy0 = dy0; sw = dw; sh = dh; spitch = dw;
+        sox = dox; soy = doy; spitch = 4 * ng;
         __syncthreads();
     }
 }
@@ -314,14 +353,18 @@ template <int KPT> struct OctKeys {
     unsigned node[OCT_KPT], quad[OCT_KPT];
     uint32_t *gkeys; uint16_t *gnode; unsigned n; int tid;
     unsigned per;   // REG: a thread owns the `per` CONSECUTIVE keys k = tid * per + j -- neighbours in FAST-cell order, i.e. mostly in the same node
+    unsigned cnt;   // REG: how many of them exist: min(per, n - tid * per), 0 beyond the list's end
+    // The number of keys this thread holds, as a value the compiler takes for new in every pass.  `j < cnt` is then one compare where it is used;
+    // as loop invariants the sixteen (thirty-two) lane masks of `j < per && k < n` stayed in SGPRs across the whole kernel (k_octree<32>: 47
+    // SGPRs spilled into VGPR lanes for them).
+    __device__ __forceinline__ unsigned held() const { unsigned c = cnt; asm volatile("" : "+v"(c)); return c; }
     // f(k, key, node&, quad&): quad is scratch that survives between two passes of one round (REG only; recomputed otherwise)
     template <typename F> __device__ __forceinline__ void for_each(F f) {
         if constexpr (REG) {
+            const unsigned c = held(), k0 = (unsigned)tid * per;
 #pragma unroll
-            for (int j = 0; j < OCT_KPT; j++) {
-                const unsigned k = (unsigned)tid * per + (unsigned)j;
-                if ((unsigned)j < per && k < n) f(k, key[j], node[j], quad[j]);
-            }
+            for (int j = 0; j < OCT_KPT; j++)
+                if ((unsigned)j < c) f(k0 + (unsigned)j, key[j], node[j], quad[j]);
         } else {
             for (unsigned k = tid; k < n; k += OCT_NT) {
                 unsigned nd = gnode[k], q = 0xFFFFFFFFu;
@@ -333,8 +376,42 @@ template <int KPT> struct OctKeys {
     }
 };
 
+// Exclusive scans over the quadtree workgroup (OCT_NT threads, a compile-time number of waves).  As msl_common.h's block_excl_scan, but the
+// wave totals are folded by one more wave scan and two lane reads instead of sixteen selects per thread: written for any block size, those
+// selects kept 32 lane masks (`i < waves`, `i < my wave`) alive in SGPRs for the whole kernel, the larger part of its 249 spilled SGPRs.
+// Integer sums: the same values.  s_wave: 32 entries (the pair form keeps its second row from entry 16 on).
+constexpr int OCT_NW = OCT_NT / 64;
+static_assert(OCT_NW <= 8, "the pair scan folds both rows of wave totals in lanes 0 .. 15");
+__device__ __forceinline__ unsigned oct_excl_scan(unsigned v, unsigned *s_wave, unsigned *total) {
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const unsigned inc = wave_incl_scan(v);
+    __syncthreads();  // protect s_wave reuse
+    if (lane == 63) s_wave[w] = inc;
+    __syncthreads();
+    const unsigned ts = wave_incl_scan(lane < OCT_NW ? s_wave[lane] : 0u);
+    *total = (unsigned)__builtin_amdgcn_readlane((int)ts, OCT_NW - 1);
+    const unsigned before = (unsigned)__builtin_amdgcn_readlane((int)ts, max(w - 1, 0));
+    return (w ? before : 0u) + inc - v;
+}
+__device__ __forceinline__ void oct_excl_scan_pair(unsigned a, unsigned b, unsigned *s_wave, unsigned *totalA, unsigned *totalB, unsigned &exA, unsigned &exB) {
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const unsigned ia = wave_incl_scan(a), ib = wave_incl_scan(b);
+    __syncthreads();
+    if (lane == 63) { s_wave[w] = ia; s_wave[16 + w] = ib; }
+    __syncthreads();
+    // lanes 0 .. 7: the first row's totals, lanes 8 .. 15: the second row's; one scan over both
+    const unsigned ts = wave_incl_scan(lane < OCT_NW ? s_wave[lane] : lane < 8 + OCT_NW && lane >= 8 ? s_wave[8 + lane] : 0u);
+    const unsigned allA = (unsigned)__builtin_amdgcn_readlane((int)ts, 7), endB = (unsigned)__builtin_amdgcn_readlane((int)ts, 15);
+    const unsigned beforeA = (unsigned)__builtin_amdgcn_readlane((int)ts, max(w - 1, 0)), uptoB = (unsigned)__builtin_amdgcn_readlane((int)ts, 7 + w);
+    *totalA = allA; *totalB = endB - allA;
+    exA = (w ? beforeA : 0u) + ia - a; exB = (uptoB - allA) + ib - b;
+}
+
+// The fields of its level's LevelDev record that k_octree reads, fetched once (scalar loads: the level is the workgroup's).
+struct OctLevel { int h, quota, nIni, nCells, cellBase, keyBase; float hX; };
+
 template <int KPT>
-__device__ __forceinline__ void octree_body(const OrbDev &P, const LevelDev &G, OctKeys<KPT> &K, unsigned char *s_dyn, unsigned *s_wave, int *s_misc, int frame,
+__device__ __forceinline__ void octree_body(const OctArgs &P, const OctLevel &G, OctKeys<KPT> &K, unsigned char *s_dyn, unsigned *s_wave, int *s_misc, int frame,
                                             int level) {
     constexpr bool REG = KPT > 0;
     constexpr int OCT_KPT = KPT > 0 ? KPT : 1;
@@ -371,10 +448,11 @@ __device__ __forceinline__ void octree_body(const OrbDev &P, const LevelDev &G, 
     auto for_each_hist = [&](unsigned *ctr, auto f) {
         if constexpr (REG) {
             unsigned curQ = 0xFFFFFFFFu, curC = 0;
+            const unsigned c = K.held();
 #pragma unroll
             for (int j = 0; j < OCT_KPT; j++) {
                 const unsigned k = (unsigned)tid * K.per + (unsigned)j;
-                if ((unsigned)j < K.per && k < n) {
+                if ((unsigned)j < c) {
                     const unsigned q = f(k, K.key[j], K.node[j], K.quad[j]);
                     if (q != curQ) {
                         if (curQ != 0xFFFFFFFFu) atomicAdd(&ctr[curQ], curC);
@@ -462,7 +540,7 @@ __device__ __forceinline__ void octree_body(const OrbDev &P, const LevelDev &G, 
             }
         }
         unsigned totFG, totL, exFG, exL;
-        block_excl_scan_pair(sumFG, sumL, s_wave, &totFG, &totL, exFG, exL);
+        oct_excl_scan_pair(sumFG, sumL, s_wave, &totFG, &totL, exFG, exL);
         OCT_STAMP(P, level, frame, stampNo++);
         const int Ctot = (int)(totFG & 0xFFFFu), nToExpand = (int)(totFG >> 16), Ltot = (int)totL;
         const int S2 = Ctot + Ltot;
@@ -534,7 +612,7 @@ __device__ __forceinline__ void octree_body(const OrbDev &P, const LevelDev &G, 
         }
         if (tid == 0) s_misc[2] = 0x7FFFFFFF;
         unsigned mTot, exUnused;
-        exUnused = block_excl_scan(nMine, s_wave, &mTot);   // (its barriers also complete s_cc, s_order, s_rankOf)
+        exUnused = oct_excl_scan(nMine, s_wave, &mTot);   // (its barriers also complete s_cc, s_order, s_rankOf)
         (void)exUnused;
         const int m = (int)mTot;
         OCT_STAMP(P, level, frame, stampNo++);
@@ -547,7 +625,7 @@ __device__ __forceinline__ void octree_body(const OrbDev &P, const LevelDev &G, 
             if (r < m) { const int i = s_order[r]; sumG += (s_cc[4 * i] > 0) + (s_cc[4 * i + 1] > 0) + (s_cc[4 * i + 2] > 0) + (s_cc[4 * i + 3] > 0); }
         }
         unsigned totG, exG;
-        exG = block_excl_scan(sumG, s_wave, &totG);
+        exG = oct_excl_scan(sumG, s_wave, &totG);
         for (int p = 0; p < perR; p++) {
             const int r = r0 + p;
             if (r < m) {
@@ -568,7 +646,7 @@ __device__ __forceinline__ void octree_body(const OrbDev &P, const LevelDev &G, 
         }
         for (int p = 0; p < perS; p++) { const int i = i0 + p; if (i < S) sumL += !(s_rankOf[i] < J) ? 1u : 0u; }
         unsigned totFG, totL, exFG, exL;
-        block_excl_scan_pair(sumFG, sumL, s_wave, &totFG, &totL, exFG, exL);
+        oct_excl_scan_pair(sumFG, sumL, s_wave, &totFG, &totL, exFG, exL);
         OCT_STAMP(P, level, frame, stampNo++);
         const int Ctot = (int)(totFG & 0xFFFFu);
         const int S2 = Ctot + (S - J);
@@ -640,7 +718,7 @@ __device__ __forceinline__ void octree_body(const OrbDev &P, const LevelDev &G, 
 // MAXKPT: the largest register-resident form this instantiation carries.  The 32-keys-per-thread form needs 239 VGPRs (a 512-thread workgroup then
 // fills its CU's register files), so launches for ordinary frame sizes use k_octree<16> (133 VGPRs) and only large frames k_octree<32>.
 template <int MAXKPT>
-__global__ __launch_bounds__(OCT_NT) void k_octree(OrbDev P) {
+__global__ __launch_bounds__(OCT_NT) void k_octree(OctArgs P) {
     // Node arrays sized for THIS extractor's longest possible list (P.maxNode = max over levels of max(quota, 4 nIni) + 2, rounded up to 64, plus
     // one block of slack; 66 bytes per node: 21 KB for 1000 features instead of a fixed 66 KB for MAXNODE = 1024), so that the frame-batched kernels
     // of the other streams keep their LDS -- and with it their occupancy -- while this latency-bound kernel runs.  The same memory first holds
@@ -652,7 +730,11 @@ __global__ __launch_bounds__(OCT_NT) void k_octree(OrbDev P) {
     int level, frame;
     if (!xcd_item(P.nlevels, P.nFrames, level, frame)) return;
     OCT_STAMP(P, level, frame, 0);
-    const LevelDev &G = P.lv[level];
+    OctLevel G;
+    {
+        const LevelDev &T = P.lv[level];
+        G.h = T.h; G.quota = T.quota; G.nIni = T.nIni; G.nCells = T.nCells; G.cellBase = T.cellBase; G.keyBase = T.keyBase; G.hX = T.hX;
+    }
     uint32_t *keys = P.keys + (size_t)frame * P.keysPerFrame + G.keyBase;
     uint16_t *knode = P.knode + (size_t)frame * P.keysPerFrame + G.keyBase;
 
@@ -669,7 +751,7 @@ __global__ __launch_bounds__(OCT_NT) void k_octree(OrbDev P) {
             const unsigned cnt = c < G.nCells ? cellCnt[c] : 0;
             const unsigned ko = c < G.nCells ? P.cells[G.cellBase + c].keyOff : 0;   // (in flight together with the count)
             unsigned tot;
-            const unsigned off = carry + block_excl_scan(cnt, s_wave, &tot);
+            const unsigned off = carry + oct_excl_scan(cnt, s_wave, &tot);
             if (c < G.nCells) { s_off[c] = off; s_koff[c] = ko; }
             carry += tot;
         }
@@ -688,6 +770,7 @@ __global__ __launch_bounds__(OCT_NT) void k_octree(OrbDev P) {
         constexpr int OCT_KPT = decltype(kptTag)::value;
         OctKeys<OCT_KPT> K;
         K.n = n; K.tid = tid; K.gkeys = keys; K.gnode = knode; K.per = (n + OCT_NT - 1) / OCT_NT;
+        K.cnt = (unsigned)tid * K.per < n ? min(K.per, n - (unsigned)tid * K.per) : 0u;
         int c = 0;
 #pragma unroll
         for (int j = 0; j < OCT_KPT; j++) {
@@ -715,7 +798,7 @@ __global__ __launch_bounds__(OCT_NT) void k_octree(OrbDev P) {
         if constexpr (MAXKPT >= 32) run_in_registers(std::integral_constant<int, 32>{});
     } else {
         OctKeys<0> K;
-        K.n = n; K.tid = tid; K.gkeys = keys; K.gnode = knode; K.per = 0;
+        K.n = n; K.tid = tid; K.gkeys = keys; K.gnode = knode; K.per = 0; K.cnt = 0;
         for (unsigned k = tid; k < n; k += OCT_NT) { const int c = cell_of(k); keys[k] = cellKeys[s_koff[c] + (k - s_off[c])]; knode[k] = 0; }
         __syncthreads();
         octree_body<0>(P, G, K, s_dyn, s_wave, s_misc, frame, level);
@@ -905,38 +988,39 @@ __device__ __forceinline__ void undistort_point(const msl_frame_params &p, float
 }
 
 __global__ __launch_bounds__(256) void k_describe(OrbDev P) {
-    int item, frame;
-    const int perLevel = (P.selCap + 3) / 4;
-    if (!xcd_item(perLevel * P.nlevels, P.nFrames, item, frame)) return;
-    const int level = item / perLevel, blockX = item % perLevel;
-    const int lane = threadIdx.x & 63;
-    const int idx = blockX * 4 + (threadIdx.x >> 6);
+    // The grid is indexed by OUTPUT keypoint: wave o of a frame (four per workgroup, ceil(outCap / 4) workgroups) finds its level and its index
+    // in the level's selection from the running sums of the frame's nsel[] (scalar loads: <= 12 values), so the waves that exist are the
+    // keypoints that exist, rounded up to a workgroup -- not selCap slots on every level.  The output order is the levels' order, as before.
+    int blockX, frame;
+    if (!xcd_item((P.outCap + 3) / 4, P.nFrames, blockX, frame)) return;
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int outIdx = blockX * 4 + wv;
     const int *nsel = P.nsel + frame * P.nlevels;
-    if (blockX == 0 && level == 0 && threadIdx.x == 0) {
-        int tot = 0;
-        for (int l = 0; l < P.nlevels; l++) tot += nsel[l];
+    int tot = 0, level = 0, idx = outIdx;
+    for (int l = 0; l < P.nlevels; l++) {
+        const int c = nsel[l];
+        if (outIdx >= tot + c) { level = l + 1; idx = outIdx - (tot + c); }
+        tot += c;
+    }
+    if (blockX == 0 && threadIdx.x == 0) {
         P.nout[frame] = min(tot, P.outCap);
         if (tot > P.outCap) atomicExch(P.err, 3);
     }
-    if (idx >= nsel[level]) return;
-    int outIdx = idx;
-    for (int l = 0; l < level; l++) outIdx += nsel[l];
-    if (outIdx >= P.outCap) return;
+    if (outIdx >= min(tot, P.outCap)) return;
     const LevelDev &D = P.lv[level];
     const unsigned key = P.sel[((size_t)frame * P.nlevels + level) * P.selCap + idx];
     const int x = (int)(key & 0xFFF) + 16, y = (int)((key >> 12) & 0xFFF) + 16;  // :793-794
     const int score = key >> 24;
     int pitch;
     const uint8_t *img = level_ptr(P, frame, level, pitch);
-    // Stage the keypoint's neighbourhoods in LDS with row-wise dword loads (10 per lane) instead of ~20 scattered byte gathers per
-    // lane: the 31 x 31 patch of the level (IC_Angle, |u|, |v| <= 15; columns x-16 .. x+15 are staged) and the 37 x 37 patch of the
-    // blurred level (rotated BRIEF samples, |offset| <= 18; columns x-20 .. x+19).  A keypoint lies at least 19 px inside the level
-    // (FAST cells start 16 + 3 px in), so every staged byte exists.
-    constexpr int PW = 32, PH = 31, BW = 40, BH = 37;
-    __shared__ __attribute__((aligned(16))) uint8_t s_patch[4][PH * PW];
+    // Fetch the keypoint's neighbourhoods with row-wise dword loads (10 per lane) instead of ~20 scattered byte gathers per lane: the
+    // 31 x 31 patch of the level (IC_Angle, |u|, |v| <= 15; columns x-16 .. x+15 are read), which is summed where it lands, in registers, and
+    // the 37 x 37 patch of the blurred level (rotated BRIEF samples, |offset| <= 18; columns x-20 .. x+19), which goes to LDS.  A keypoint
+    // lies at least 19 px inside the level (FAST cells start 16 + 3 px in), so every byte exists.
+    constexpr int PW = 4 * IC_ROW_WORDS, PH = IC_ROWS, BW = 40, BH = 37;
     __shared__ __attribute__((aligned(16))) uint8_t s_blurp[4][BH * BW];
-    const int wv = threadIdx.x >> 6;
     const uint8_t *bl = P.blur + (size_t)frame * P.blurStride + D.boff + (size_t)y * D.pitch + x;
+    int m10 = 0, m01 = 0;
     {
         unsigned pv[4], bv[6];
 #pragma unroll
@@ -952,30 +1036,20 @@ __global__ __launch_bounds__(256) void k_describe(OrbDev P) {
             if (i < BH * (BW / 4)) __builtin_memcpy(&bv[k], bl + (i / (BW / 4) - 18) * D.pitch + (4 * (i % (BW / 4)) - 20), 4);
         }
 #pragma unroll
-        for (int k = 0; k < 4; k++) { const int i = lane + 64 * k; if (i < PH * (PW / 4)) reinterpret_cast<unsigned *>(s_patch[wv])[i] = pv[k]; }
-#pragma unroll
         for (int k = 0; k < 6; k++) { const int i = lane + 64 * k; if (i < BH * (BW / 4)) reinterpret_cast<unsigned *>(s_blurp[wv])[i] = bv[k]; }
-    }
-    __builtin_amdgcn_wave_barrier();
-    // IC_Angle (:75-99): m10 = sum u*I, m01 = sum v*I over the circular patch
-    int m10 = 0, m01 = 0;
-    {
-        const int u = (lane & 31) - 15;
-        const int au = u < 0 ? -u : u;
-#pragma unroll 4
-        for (int it = 0; it < 16; it++) {
-            const int v = -15 + 2 * it + (lane >> 5);
-            const int av = v < 0 ? -v : v;
-            if (av <= 15 && au <= 15 && au <= P.umax[av]) {
-                const int val = s_patch[wv][(v + 15) * PW + u + 16];
-                m10 += u * val;
-                m01 += v * val;
-            }
-        }
+        // IC_Angle (:75-99): m10 = sum u*I, m01 = sum v*I over the circular patch, from the patch words in registers (msl_orb_sums.h): two
+        // v_dot4_u32_u8 per word against weight words built from umax[], instead of one byte per lane and trip through LDS.  The missing words
+        // (i >= 248) are 0.
+        const uint64_t umaxNib = ic_pack_umax(P.umax);
+        uint32_t sI = 0, sCI = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) ic_add_word(pv[k], min(lane + 64 * k, IC_WORDS - 1), umaxNib, sI, sCI, m01);
+        m10 = ic_m10(sI, sCI);
         // wave totals in the VALU (DPP row scan + row broadcasts, msl_common.h) instead of six rounds of ds_bpermute per sum; integer sums: any order
         m10 = __builtin_amdgcn_readlane((int)wave_incl_scan((unsigned)m10), 63);
         m01 = __builtin_amdgcn_readlane((int)wave_incl_scan((unsigned)m01), 63);
     }
+    __builtin_amdgcn_wave_barrier();
     const float angle = fast_atan2_deg((float)m01, (float)m10);
     const float factorPI = (float)(M_PI / 180.f);
     float a, b;
@@ -1084,8 +1158,12 @@ int orb_launch_pipeline(const OrbDev *dev, OrbLaunch *launch, const uint8_t *d_g
     hipLaunchKernelGGL(k_fast, dim3(xcd_grid1((long long)P.cellsPerFrame * n)), dim3(64), q.fastLds, s, P);
     q.prof.end(s);
     q.prof.begin(KID_OCTREE, s);
-    if (q.octBig) hipLaunchKernelGGL(k_octree<32>, dim3(xcd_grid1((long long)L * n)), dim3(OCT_NT), (size_t)P.octLds, s, P);
-    else hipLaunchKernelGGL(k_octree<16>, dim3(xcd_grid1((long long)L * n)), dim3(OCT_NT), (size_t)P.octLds, s, P);
+    OctArgs A;
+    A.cellCnt = P.cellCnt; A.cellKeys = P.cellKeys; A.cells = P.cells; A.lv = P.lvDev; A.keys = P.keys; A.knode = P.knode; A.sel = P.sel;
+    A.nsel = P.nsel; A.ncand = P.ncand; A.err = P.err;
+    A.cellsPerFrame = P.cellsPerFrame; A.keysPerFrame = P.keysPerFrame; A.nlevels = L; A.nFrames = n; A.selCap = P.selCap; A.maxNode = P.maxNode;
+    if (q.octBig) hipLaunchKernelGGL(k_octree<32>, dim3(xcd_grid1((long long)L * n)), dim3(OCT_NT), (size_t)P.octLds, s, A);
+    else hipLaunchKernelGGL(k_octree<16>, dim3(xcd_grid1((long long)L * n)), dim3(OCT_NT), (size_t)P.octLds, s, A);
     q.prof.end(s);
     if (fork) {
         MSL_HIP_TRY(hipStreamWaitEvent(s, q.evJoin, 0));
@@ -1095,7 +1173,7 @@ int orb_launch_pipeline(const OrbDev *dev, OrbLaunch *launch, const uint8_t *d_g
         q.prof.end(s);
     }
     q.prof.begin(KID_DESCRIBE, s);
-    hipLaunchKernelGGL(k_describe, dim3(xcd_grid1((long long)((P.selCap + 3) / 4) * L * n)), dim3(256), 0, s, P);
+    hipLaunchKernelGGL(k_describe, dim3(xcd_grid1((long long)((P.outCap + 3) / 4) * n)), dim3(256), 0, s, P);
     q.prof.end(s);
     MSL_HIP_TRY(hipGetLastError());
     return MSL_OK;

@@ -13,6 +13,7 @@ constexpr int MAXNODE = 1024;   // max quadtree list length per level
 constexpr int OCT_NT = 512;     // threads of the quadtree workgroup
 constexpr int OCT_NODE_BYTES = 66;   // k_octree's LDS per node slot
 constexpr int BT_W = 64, BT_H = 32;  // k_blur's output tile
+constexpr int PYR_TAPS = 128;       // k_pyramid: column taps staged per level (a tile's row pitch is below 128 pixels)
 
 // The frame epilogue of one call: intrinsics, the depth frames on the device, and where its four outputs go.
 struct FrameEpilogue {
@@ -77,7 +78,7 @@ struct CellDev {
     unsigned keyOff;  // first key slot of the cell (frame relative)
 };
 
-struct ResizeTap { short s0, s1, c0, c1; };
+struct alignas(8) ResizeTap { short s0, s1, c0, c1; };   // (8-byte loads: k_pyramid fetches four adjacent entries per lane)
 // one axis of one tile on one level of the fused pyramid: the pixels the tile owns (writes to HBM) and the pixels it has to compute
 // because its share of the next level reads them (level 0: the input pixels it loads)
 struct PyrRange { short ownLo, ownHi, needLo, needHi; };
@@ -93,7 +94,7 @@ struct OrbDev {
     const CellDev *cells;
     const ResizeTap *taps;
     const PyrRange *pyrX, *pyrY;   // fused pyramid: [level][tile column] / [level][tile row] ranges (pyrTX == 0: one launch per level)
-    int pyrTX, pyrTY; unsigned pyrBuf0;   // bytes of the first LDS buffer
+    int pyrTX, pyrTY; unsigned pyrBuf0, pyrTapOff;   // bytes of the first LDS buffer; where the staged column taps start (behind the second)
     uint32_t *cellCnt, *cellKeys, *keys;
     uint16_t *knode;
     uint32_t *sel; int *nsel, *ncand;
@@ -106,6 +107,15 @@ struct OrbDev {
     int nFrames;   // frames of this launch sequence (the kernels run 1-D, XCD-aware grids: xcd_item)
     int maxNode;   // k_octree: node-array length
     int octLds;    // k_octree: dynamic LDS bytes = max(OCT_NODE_BYTES * maxNode, 8 * (cells of the largest level + 1))
+    const LevelDev *lvDev;   // lv[] on the device (uploaded once per geometry): for kernels that take slim arguments
+};
+
+// What k_octree takes instead of the whole OrbDev (1.3 KB): the arrays it touches and a few scalars.  A workgroup reads its level's record from
+// lv with scalar loads.
+struct OctArgs {
+    const uint32_t *cellCnt, *cellKeys; const CellDev *cells; const LevelDev *lv;
+    uint32_t *keys; uint16_t *knode; uint32_t *sel; int *nsel, *ncand, *err;
+    int cellsPerFrame, keysPerFrame, nlevels, nFrames, selCap, maxNode;
 };
 
 }  // namespace

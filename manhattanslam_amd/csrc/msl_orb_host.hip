@@ -40,7 +40,7 @@ struct msl_orb : OrbConfig, OrbLaunch {
     OrbDev dev{};
     bool ownStream = true;
     // device allocations of the current geometry (commit_geometry); outBlock = [nout[B] | kps[B][cap] | desc[B][cap]], d_nout / d_kps / d_desc point into it
-    struct Geometry { DevBuf in, pyr, blur, cells, taps, pyrRanges, cellCnt, cellKeys, keys, knode, sel, nsel, ncand, outBlock; } geo;
+    struct Geometry { DevBuf in, pyr, blur, cells, levels, taps, pyrRanges, cellCnt, cellKeys, keys, knode, sel, nsel, ncand, outBlock; } geo;
     size_t inPitch = 0, outKpsOff = 0, outDescOff = 0;
     msl_keypoint *d_kps = nullptr; uint8_t *d_desc = nullptr; int *d_nout = nullptr;
     DevBuf d_err; PinBuf h_err;
@@ -207,16 +207,31 @@ void plan_pyramid(OrbPlan &P) {
     };
     std::vector<int> ex, ey;
     axis(TX, true, P.pyrX, ex); axis(TY, false, P.pyrY, ey);
+    // k_pyramid's row pitches: the input region rounded up to whole dwords; a later level starts at the column needLo & ~3 and ends on a whole run of four
+    ex[0] = (ex[0] + 3) & ~3;
+    for (int l = 1; l < L; l++) {
+        ex[l] = 0;
+        for (int i = 0; i < TX; i++) { const PyrRange &r = P.pyrX[(size_t)l * TX + i]; ex[l] = std::max(ex[l], ((r.needHi - (r.needLo & ~3)) + 3) & ~3); }
+    }
     size_t b0 = 0, b1 = 0;
     bool ok = true;
     for (int l = 0; l < L; l++) {
-        const size_t a = (size_t)(l == 0 ? (ex[l] + 3) & ~3 : ex[l]) * ey[l];   // (k_pyramid stages the input region with a dword pitch)
+        const size_t a = (size_t)ex[l] * ey[l] + 8;   // (+ 8: a pixel's source pair is cut from two aligned words, the second of which may lie past the last row)
         if (l & 1) b1 = std::max(b1, a); else b0 = std::max(b0, a);
         if (l >= 1 && (D.lv[l].w < TX || D.lv[l].h < TY)) ok = false;
     }
     b0 = (b0 + 15) & ~(size_t)15;
     for (int l = 0; l < L; l++) if (ex[l] >= 128 || (size_t)ex[l] * ey[l] >= (1u << 15)) ok = false;   // k_pyramid's multiply-shift row index
-    if (ok && b0 + b1 <= 48 * 1024) { D.pyrTX = TX; D.pyrTY = TY; D.pyrBuf0 = (unsigned)b0; P.pyrLds = b0 + b1; }
+    // k_pyramid reads a pixel's two source columns as one pair of adjacent bytes and multiplies unsigned 16-bit fields (resize_px): true of every
+    // column tap cv::resize's rule makes (s1 = s0 + 1, or the clamped last column with c1 = 0); a table that broke it would fall back to k_resize
+    for (int l = 1; l < L && ok; l++)
+        for (int x = 0; x < D.lv[l].w; x++) {
+            const ResizeTap &t = taps[D.lv[l].xtabOff + x];
+            if (t.c0 < 0 || t.c1 < 0 || !(t.s1 == t.s0 + 1 || t.c1 == 0)) ok = false;
+        }
+    b1 = (b1 + 15) & ~(size_t)15;
+    const size_t tapBytes = 2 * PYR_TAPS * sizeof(ResizeTap);   // two levels' column taps in turn (ex[l] < 128 = PYR_TAPS)
+    if (ok && b0 + b1 + tapBytes <= 48 * 1024) { D.pyrTX = TX; D.pyrTY = TY; D.pyrBuf0 = (unsigned)b0; D.pyrTapOff = (unsigned)(b0 + b1); P.pyrLds = b0 + b1 + tapBytes; }
 }
 
 int plan_geometry(const OrbConfig *h, int W, int H, OrbPlan &P) {
@@ -272,13 +287,14 @@ int commit_geometry(msl_orb *h, const OrbPlan &P) {
     D = P.dev;
     const size_t B = (size_t)h->maxBatch, L = (size_t)D.nlevels, nCells = P.cells.size(), nKeys = P.keyOff;
     MSL_HIP_TRY(grow_all(h->stream, {{g.in, P.inPitch * P.H * B}, {g.pyr, std::max<size_t>(D.pyrStride, 256) * B}, {g.blur, D.blurStride * B},
-                                     {g.cells, sizeof(CellDev) * nCells}, {g.taps, sizeof(ResizeTap) * std::max<size_t>(P.taps.size(), 1)},
+                                     {g.cells, sizeof(CellDev) * nCells}, {g.levels, sizeof(LevelDev) * L}, {g.taps, sizeof(ResizeTap) * std::max<size_t>(P.taps.size(), 1)},
                                      {g.pyrRanges, D.pyrTX ? sizeof(PyrRange) * (P.pyrX.size() + P.pyrY.size()) : 0},
                                      {g.cellCnt, sizeof(uint32_t) * nCells * B}, {g.cellKeys, sizeof(uint32_t) * nKeys * B},
                                      {g.keys, sizeof(uint32_t) * nKeys * B}, {g.knode, sizeof(uint16_t) * nKeys * B},
                                      {g.sel, sizeof(uint32_t) * (size_t)D.selCap * L * B}, {g.nsel, sizeof(int) * L * B}, {g.ncand, sizeof(int) * L * B},
                                      {g.outBlock, P.outDescOff + (size_t)32 * D.outCap * B}}));
     MSL_HIP_TRY(hipMemcpy(g.cells.p, P.cells.data(), sizeof(CellDev) * nCells, hipMemcpyHostToDevice));
+    MSL_HIP_TRY(hipMemcpy(g.levels.p, D.lv, sizeof(LevelDev) * L, hipMemcpyHostToDevice));   // (the level table is complete in the plan: no field of it is a device pointer)
     if (!P.taps.empty())
         MSL_HIP_TRY(hipMemcpy(g.taps.p, P.taps.data(), sizeof(ResizeTap) * P.taps.size(), hipMemcpyHostToDevice));
     if (D.pyrTX) {
@@ -287,7 +303,7 @@ int commit_geometry(msl_orb *h, const OrbPlan &P) {
         MSL_HIP_TRY(hipMemcpy(ranges + P.pyrX.size(), P.pyrY.data(), sizeof(PyrRange) * P.pyrY.size(), hipMemcpyHostToDevice));
         D.pyrX = ranges; D.pyrY = ranges + P.pyrX.size();
     }
-    D.pyr = (uint8_t *)g.pyr.p; D.blur = (uint8_t *)g.blur.p; D.cells = (const CellDev *)g.cells.p; D.taps = (const ResizeTap *)g.taps.p;
+    D.pyr = (uint8_t *)g.pyr.p; D.blur = (uint8_t *)g.blur.p; D.cells = (const CellDev *)g.cells.p; D.lvDev = (const LevelDev *)g.levels.p; D.taps = (const ResizeTap *)g.taps.p;
     D.cellCnt = (uint32_t *)g.cellCnt.p; D.cellKeys = (uint32_t *)g.cellKeys.p; D.keys = (uint32_t *)g.keys.p; D.knode = (uint16_t *)g.knode.p;
     D.sel = (uint32_t *)g.sel.p; D.nsel = (int *)g.nsel.p; D.ncand = (int *)g.ncand.p; D.err = (int *)h->d_err.p;
     uint8_t *out = (uint8_t *)g.outBlock.p;
