@@ -1207,6 +1207,132 @@ MSL_API int msl_covisibility_batch(int device, int n_tab, int cap, int n_pts, in
                                    const int32_t *obs_kf, const int32_t *kf, msl_mem mem, int32_t *weight, int32_t *conn, int32_t *conn_w,
                                    int32_t *n_conn, msl_mem out_mem) MSL_NOEXCEPT;
 
+/* ---- Fusing map lines into neighbouring keyframes and refreshing them: LocalMapping::SearchInNeighbors, line half (src/LocalMapping.cc:583-618) ----
+ * msl_fuse_map_lines: n_items independent calls of LSDmatcher::Fuse(pKF, vpMapLines, th) (src/LSDmatcher.cpp:259-382), each from the state
+ * on entry.  msl_refresh_map_lines: MapLine::UpdateAverageDir (src/MapLine.cpp:262-308) for a batch of line ids, the only producer of the
+ * ln_normal / ln_dist that msl_match_local_lines and msl_fuse_map_lines read, so the line table can stay in device memory from one keyframe
+ * to the next.  The other two pieces of :583-618 are existing entries: vpLineFuseCandidates (:589-605) is msl_fuse_candidates over the line
+ * held_id and ln_flags with cap = klcap; MapLine::ComputeDistinctiveDescriptors is msl_refresh_map_points with MSL_REFRESH_DESC alone.
+ * Keyframes are a table of n_tab keyframes with klcap keylines each, as for msl_match_local_lines; per keyline i < n_kl[k]:
+ *   kl[i]            mvKeyLines[i]: pt, angle, octave (KeyFrame::GetLinesInArea reads mvKeyLines, not the undistorted ones)
+ *   ldesc[32 i..]    mLineDescriptors.row(i)                            Tcw[12 k..]    rows 0-2 of the CV_32F Tcw; Ow as KeyFrame::SetPose
+ *   held_id[i]       the id of GetMapLine(i), -1 for NULL; a bad line that is still in the slot keeps its id
+ * Map lines are a table of n_lines lines indexed by id, in the layouts msl_match_local_lines reads:
+ *   ln_xyz[6 id..]   GetWorldPos() (double)   ln_normal[3 id..]  GetNormal() (double)   ln_dist[2 id..]  mfMinDistance, mfMaxDistance (raw;
+ *   ln_desc[32 id..] GetDescriptor()          ln_flags[id]       bit 0: !isBad()        0.8f / 1.2f inside)   ln_nobs[id]   Observations()
+ * msl_fuse_map_lines: tgt, list, cand[n_lists][lcap] and n_cand as for msl_fuse_map_points (items may share a row; an entry is a line id
+ * or -1).  The ids of one list are distinct and the caller passes -1 for later duplicates.  What that costs: unlike a point, a repeated
+ * line is searched again by the reference, can hit the slot it has just taken and add 1 to the return value (the self-hit below), which
+ * SearchInNeighbors ignores; no object state differs.  Out, per (item f, candidate j) at [f * lcap + j]:
+ *   best_idx, best_dist   bestIdx / bestDist of the search: -1 / INT_MAX when no keyline passed the level window, or the candidate left
+ *                         before the search; bestDist starts at INT_MAX because 256 is a distance two 256-bit rows can have
+ *   status                one MSL_LFUSE_* code: the exit of the loop body the candidate took
+ *   other                 the id that held slot best_idx at that moment, -1 for none (and for every status below MSL_LFUSE_ADDED)
+ * per item: n_fused[f] = the return value.  Slots j >= n_cand[list[f]] are -1 (best_idx, other) and 0 (best_dist, status).
+ * This is not ORBmatcher::Fuse with other names:
+ *   no IsInKeyFrame skip      only NULL and bad candidates leave early (:280); a line the keyframe already holds is searched again.  Best
+ *                             keyline = the slot that holds it: Replace returns at src/MapLine.cpp:140, nothing changes, nFused++
+ *                             (MSL_LFUSE_SELF).  Best keyline = an empty slot: AddObservation returns early (:77, nObs unchanged) but
+ *                             AddMapLine writes the slot, and the line sits in two slots (MSL_LFUSE_ADDED)
+ *   the projection            both depths are tested before anything is projected, with < 0.0f (Z == 0 passes, the projection is then
+ *                             infinite or NaN); closed bounds tests that a NaN passes (msl_match_local_lines' projection)
+ *   OM                        0.5 * (SP + EP) - Ow as the float addWeighted(SP, .5, EP, .5, 0) - Ow; dist = cv::norm, a double sum rounded
+ *                             to float; a NaN passes the distance test; OM.dot(pn) with pn = the double normal converted to float,
+ *                             accumulated in double, compared with 0.5 * dist in double
+ *   MapLine::PredictScale     not clamped; mvScaleFactors[nPredictedLevel] clamps the index for the lookup only (the reference reads out
+ *                             of bounds), the level window klLevel < L - 1 || klLevel > L uses the unclamped L with x86-64's int wrap
+ *   KeyFrame::GetLinesInArea  (src/KeyFrame.cc:506-538) without a level filter, every keyline in ascending index, Frame::GetLinesInArea's
+ *                             arithmetic: the double midpoint distance stored to float, slope > r * 0.01 in double without fabs, x1 == x2
+ *                             gives +-inf or NaN, which passes
+ *   the best keyline          strict <, so the first minimum in ascending keyline index; accepted when bestDist <= th_low
+ * The add / replace choice is resolved from the state on entry, candidates in ascending j, one state per slot s (holder, bad, nobs, stale):
+ *   empty                   MSL_LFUSE_ADDED, the holder becomes p with nobs = ln_nobs[p] + (p in held_id[tgt][:n_kl] ? 0 : 1); no stereo + 2
+ *   holder bad              MSL_LFUSE_HELD_BAD, unchanged
+ *   holder stale            MSL_LFUSE_UNRESOLVED, unchanged
+ *   holder == p             MSL_LFUSE_SELF, unchanged
+ *   nobs(h) > ln_nobs[p]    MSL_LFUSE_REPLACED_BY_HELD, the holder is stale
+ *   otherwise               MSL_LFUSE_REPLACES_HELD, the holder becomes p, stale
+ * Stale as for points.  Because nothing skips a line the keyframe holds, one line can be a candidate and a holder in the same item; its
+ * ln_nobs is then the entry value although an earlier Replace of the item changed it.  The codes from MSL_LFUSE_ADDED on are therefore
+ * the choice from the entry state: exact whenever neither the candidate nor the holder took part in an earlier Replace of the item, and
+ * the caller's replay takes the choice from its live objects in every case (tests/linefuse_model.py proves the
+ * replay equal to the sequential function).  The search (best_idx, best_dist and the codes below MSL_LFUSE_ADDED) is exact whatever the order.
+ * Pins: membership of a line in the keyframe is read from the table, id in held_id[tgt][:n_kl]; a held_id outside [0, n_lines) is an empty
+ * slot.
+ * Limits: klcap <= 256, n_tab <= 4096, n_lines <= 1048576, lcap <= 65536, n_items <= 4096, nlevels <= MSL_MATCH_MAX_LEVELS, 0 <= th_low <=
+ * 256; anything else is refused with MSL_ERR_INVALID before any launch, and nothing is written.  A host-memory call also checks the index
+ * ranges (tgt, list, n_cand, every list entry) and the distinctness of each list, and refuses a violation; with device memory these are
+ * the caller's contract: an index outside its table is treated as NULL, a bad tgt as a keyframe without keylines, a bad list as an empty
+ * list, a repeated id goes unnoticed; no index reads or writes outside its table.  Memory and synchronisation as msl_bow_transform.
+ * msl_refresh_map_lines: n_items distinct line ids ids[f].  The observations are the CSR table of msl_refresh_map_points over the line
+ * table (obs_off[n_lines + 1], obs_kf, obs_idx = the keyline index), in the caller's order inside a range (keyframe creation order pins the
+ * reference's pointer order); the library never sorts it.  ln_ref[id] = the table index of mpRefKF.  Out, per item f: out_normal[3 f..]
+ * (double), out_dist[2 f..] (mfMinDistance, mfMaxDistance) -- zeros where nothing was written -- and status[f], MSL_REFRESH_* bits:
+ * MSL_REFRESH_NORMAL_WRITTEN, or MSL_REFRESH_BAD (a bad line), MSL_REFRESH_NO_OBS, MSL_REFRESH_BAD_OCTAVE with nothing written.  ln_normal,
+ * ln_dist (each may be NULL; in out_mem memory): the line table; where the status says written, row ids[f] is written too, and only there.
+ * Reproduced exactly (tests/linefuse_model.py is the sequential model):
+ *   normal      OWi = the float camera centre (KeyFrame::SetPose, cv::gemm's float kernel) widened to double; middlePos = 0.5 * (head +
+ *               tail) in double; normali = middlePos - OWi; normali.norm() = sqrt(x0 * x0 + (x1 * x1 + x2 * x2)), Eigen 3's unrolled
+ *               reduction of a fixed 3-vector (a stated pin: parity with an Eigen build is unpinned); normal = normal + normali / norm in
+ *               observation order from (0, 0, 0), n counting every observation, bad keyframes included; the result is normal / n
+ *   distances   dist = the float cv::norm of (float addWeighted(SP, .5, EP, .5, 0)) - Ow(ref); mfMaxDistance = dist * scale_factors[level],
+ *               level = the octave of the reference keyframe's keyline observations[pRefKF] (index 0 when the reference keyframe is not
+ *               among the observations, as map::operator[] gives); mfMinDistance = mfMaxDistance / scale_factors[nlevels - 1]
+ * An octave outside [0, nlevels), a ln_ref outside the table or a reference keyline outside [0, klcap) is MSL_REFRESH_BAD_OCTAVE.
+ * Refresh limits: n_tab <= 4096, klcap <= 256, n_lines <= 1048576, n_items <= n_lines, nlevels <= MSL_MATCH_MAX_LEVELS; refused as above.
+ * A host-memory call checks the CSR table and ids (in range, distinct); with device memory an observation whose obs_kf is outside the
+ * table is skipped as if absent and an id outside the line table is a bad line. */
+typedef struct msl_line_fuse_params {
+    float fx, fy, cx, cy;                            /* KeyFrame::fx .. cy */
+    float minX, maxX, minY, maxY;                    /* mnMinX .. mnMaxY (msl_frame_image_bounds) */
+    float th;                                        /* 3.0 (include/LSDmatcher.h:50) */
+    int32_t nlevels;                                 /* mnScaleLevels */
+    float scale_factors[MSL_MATCH_MAX_LEVELS];       /* mvScaleFactors */
+    float log_scale_factor;                          /* mfLogScaleFactor */
+    int32_t th_low;                                  /* LSDmatcher::TH_LOW (50, src/LSDmatcher.cpp:16) */
+} msl_line_fuse_params;
+#define MSL_LFUSE_NULL               0   /* NULL candidate (also: a slot beyond the list) */
+#define MSL_LFUSE_BAD                1   /* isBad() */
+#define MSL_LFUSE_BEHIND             2   /* SPcZ < 0 || EPcZ < 0 */
+#define MSL_LFUSE_OUT_OF_IMAGE       3   /* an end point outside [mnMin, mnMax] */
+#define MSL_LFUSE_DISTANCE           4   /* dist outside [minDistance, maxDistance] */
+#define MSL_LFUSE_VIEW_ANGLE         5   /* OM.dot(pn) < 0.5 * dist */
+#define MSL_LFUSE_NO_FEATURE         6   /* vIndices.empty() */
+#define MSL_LFUSE_NO_CANDIDATE       7   /* no index inside the level window, bestDist still INT_MAX */
+#define MSL_LFUSE_ABOVE_TH_LOW       8   /* bestDist > th_low */
+#define MSL_LFUSE_ADDED              9   /* the slot was empty: AddObservation + AddMapLine */
+#define MSL_LFUSE_REPLACED_BY_HELD  10   /* pML->Replace(pMLinKF) */
+#define MSL_LFUSE_REPLACES_HELD     11   /* pMLinKF->Replace(pML) */
+#define MSL_LFUSE_HELD_BAD          12   /* the slot holds a bad line: counted, nothing done */
+#define MSL_LFUSE_UNRESOLVED        13   /* counted; the direction is the caller's (a stale holder) */
+#define MSL_LFUSE_SELF              14   /* the slot holds the candidate itself: counted, nothing done */
+MSL_API int msl_fuse_map_lines(msl_match *h, int n_tab, int klcap, int n_lines, int n_items, int n_lists, int lcap,
+                               const msl_line_fuse_params *params, const msl_keyline *kl, const uint8_t *ldesc, const int32_t *n_kl,
+                               const float *Tcw, const int32_t *held_id, const double *ln_xyz, const double *ln_normal, const float *ln_dist,
+                               const uint8_t *ln_desc, const uint8_t *ln_flags, const int32_t *ln_nobs, const int32_t *tgt,
+                               const int32_t *list, const int32_t *cand, const int32_t *n_cand, msl_mem mem, int32_t *best_idx,
+                               int32_t *best_dist, uint8_t *status, int32_t *other, int32_t *n_fused, msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device matcher handle, always synchronous; see msl_match_by_projection_batch). */
+MSL_API int msl_fuse_map_lines_batch(int device, int n_tab, int klcap, int n_lines, int n_items, int n_lists, int lcap,
+                                     const msl_line_fuse_params *params, const msl_keyline *kl, const uint8_t *ldesc, const int32_t *n_kl,
+                                     const float *Tcw, const int32_t *held_id, const double *ln_xyz, const double *ln_normal,
+                                     const float *ln_dist, const uint8_t *ln_desc, const uint8_t *ln_flags, const int32_t *ln_nobs,
+                                     const int32_t *tgt, const int32_t *list, const int32_t *cand, const int32_t *n_cand, msl_mem mem,
+                                     int32_t *best_idx, int32_t *best_dist, uint8_t *status, int32_t *other, int32_t *n_fused,
+                                     msl_mem out_mem) MSL_NOEXCEPT;
+MSL_API int msl_refresh_map_lines(msl_match *h, int n_tab, int klcap, int n_lines, int n_items, int n_obs_total,
+                                  const msl_refresh_params *params, const msl_keyline *kl, const int32_t *n_kl, const float *Tcw,
+                                  const int32_t *obs_off, const int32_t *obs_kf, const int32_t *obs_idx, const double *ln_xyz,
+                                  const uint8_t *ln_flags, const int32_t *ln_ref, const int32_t *ids, msl_mem mem, double *out_normal,
+                                  float *out_dist, uint8_t *status, double *ln_normal, float *ln_dist, msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device matcher handle, always synchronous). */
+MSL_API int msl_refresh_map_lines_batch(int device, int n_tab, int klcap, int n_lines, int n_items, int n_obs_total,
+                                        const msl_refresh_params *params, const msl_keyline *kl, const int32_t *n_kl, const float *Tcw,
+                                        const int32_t *obs_off, const int32_t *obs_kf, const int32_t *obs_idx, const double *ln_xyz,
+                                        const uint8_t *ln_flags, const int32_t *ln_ref, const int32_t *ids, msl_mem mem,
+                                        double *out_normal, float *out_dist, uint8_t *status, double *ln_normal, float *ln_dist,
+                                        msl_mem out_mem) MSL_NOEXCEPT;
+
 /* msl_kfdb: a KeyFrameDatabase (src/KeyFrameDatabase.cc:38-66) on one device.  msl_kfdb_create returns NULL with msl_last_error() when no
  * device is usable.  msl_kfdb_add stores the BowVector of one keyframe exactly as msl_bow_transform wrote it (ascending int32 words, double
  * values, the count -- on the device for MSL_MEM_DEVICE) and returns its slot when the vector is stored; with device memory `h` is the

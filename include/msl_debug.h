@@ -98,6 +98,11 @@ MSL_API int msl_debug_triangulate(msl_match *h, int item, int neigh, float *pair
  * and vIndices.size() (set once the view-angle test passed).  Zeros where the candidate left earlier. */
 MSL_API int msl_debug_fuse(msl_match *h, int item, float *uvr, int32_t *level_n) MSL_NOEXCEPT;
 
+/* One item of the last msl_fuse_map_lines call on h (host output, synchronous), per candidate j < lcap of that call: uvr[5 j..] = u1, v1,
+ * u2, v2 (set once both end points are inside the image) and radius (set once the view-angle test passed); level_n[2 j..] =
+ * nPredictedLevel (not clamped) and vIndices.size() (set with the radius).  Zeros where the candidate left earlier. */
+MSL_API int msl_debug_line_fuse(msl_match *h, int item, float *uvr, int32_t *level_n) MSL_NOEXCEPT;
+
 #define MSL_SF_NKERNELS 12
 MSL_API int msl_sf_profile_enable(msl_sf *h, int mode) MSL_NOEXCEPT;
 /* Sampling for the per-dispatch event pairs: only every stride-th launch of a timed kernel carries events (default 1 = every launch).  A

@@ -56,6 +56,9 @@ FUSE_PARAMS_DTYPE = np.dtype([(n, "<f4") for n in ("fx", "fy", "cx", "cy", "bf",
                              ("scale_factors", "<f4", (16,)), ("inv_level_sigma2", "<f4", (16,)), ("log_scale_factor", "<f4"),
                              ("th_low", "<i4")])                                                                                # msl_fuse_params
 REFRESH_PARAMS_DTYPE = np.dtype([("nlevels", "<i4"), ("scale_factors", "<f4", (16,))])                                          # msl_refresh_params
+LINE_FUSE_PARAMS_DTYPE = np.dtype([(n, "<f4") for n in ("fx", "fy", "cx", "cy", "minX", "maxX", "minY", "maxY", "th")] + [("nlevels", "<i4"),
+                                  ("scale_factors", "<f4", (16,)), ("log_scale_factor", "<f4"), ("th_low", "<i4")])                  # msl_line_fuse_params
+assert LINE_FUSE_PARAMS_DTYPE.itemsize == 112
 assert LINE3D_PARAMS_DTYPE.itemsize == 56 and TRIANGULATE_PARAMS_DTYPE.itemsize == 176 and FUSE_PARAMS_DTYPE.itemsize == 180 and REFRESH_PARAMS_DTYPE.itemsize == 68
 assert PNP_PARAMS_DTYPE.itemsize == 120 and PNP_PARAMS_DTYPE.fields["probability"][1] == 88
 assert POSE_PARAMS_DTYPE.itemsize == 152 and KEYPOINT_DTYPE.itemsize == 28 and SURFEL_DTYPE.itemsize == 56 and SEED_DTYPE.itemsize == 64
@@ -167,6 +170,11 @@ SIGNATURES = {
     "msl_refresh_map_points_batch": (_i, [_i] + [_i] * 6 + [_vp] * 13 + [_i] + [_vp] * 9 + [_i]),
     "msl_covisibility": (_i, [_vp] + [_i] * 7 + [_vp] * 6 + [_i] + [_vp] * 4 + [_i]),
     "msl_covisibility_batch": (_i, [_i] + [_i] * 7 + [_vp] * 6 + [_i] + [_vp] * 4 + [_i]),
+    "msl_fuse_map_lines": (_i, [_vp] + [_i] * 6 + [_vp] * 16 + [_i] + [_vp] * 5 + [_i]),
+    "msl_fuse_map_lines_batch": (_i, [_i] + [_i] * 6 + [_vp] * 16 + [_i] + [_vp] * 5 + [_i]),
+    "msl_debug_line_fuse": (_i, [_vp, _i, _vp, _vp]),
+    "msl_refresh_map_lines": (_i, [_vp] + [_i] * 5 + [_vp] * 11 + [_i] + [_vp] * 5 + [_i]),
+    "msl_refresh_map_lines_batch": (_i, [_i] + [_i] * 5 + [_vp] * 11 + [_i] + [_vp] * 5 + [_i]),
     "msl_sf_fuse_resident": (_i, [_vp, _i, _vp, _sz, _vp, _sz, _vp, _sz, _i, _vp]),
     "msl_sf_set_batch_capacity": (_i, [_vp, _i]),
     "msl_sf_fuse_resident_batch": (_i, [_vp, _i, _vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _sz, _sz, _i, _vp]),

@@ -1,5 +1,5 @@
 // msl_match_handle.h -- the matcher handle, its staging of caller arrays (Stage) and the forwarder of the *_batch entry points; shared by
-// msl_match.hip, msl_line_match.hip, msl_pose.hip, msl_plane.hip, msl_bow.hip, msl_reloc.hip, msl_pnp.hip, msl_line3d.hip, msl_triangulate.hip, msl_fuse.hip and msl_mappoint.hip (internal).
+// msl_match.hip, msl_line_match.hip, msl_pose.hip, msl_plane.hip, msl_bow.hip, msl_reloc.hip, msl_pnp.hip, msl_line3d.hip, msl_triangulate.hip, msl_fuse.hip, msl_mappoint.hip and msl_line_fuse.hip (internal).
 #pragma once
 
 #include "msl_common.h"
@@ -52,6 +52,8 @@ struct msl_match {
     // msl_fuse_candidates: per item in flight the first position of every point id
     msl::DevBuf fuseHeld, fuseRec, fuseFirst;
     int fuseItems = 0, fuseLcap = 0;                                   // the shape of the last msl_fuse_map_points call
+    msl::DevBuf lfuseRec;                                              // msl_fuse_map_lines: per (item, candidate) the query, which msl_debug_line_fuse reads
+    int lfuseItems = 0, lfuseLcap = 0;                                 // the shape of the last msl_fuse_map_lines call
     // Device copies of host-memory arguments, one pool for every entry point (msl::Stage deals the slots out in declaration order).
     // Sharing is sound because every call that touches the pool returns with the stream drained (Stage::finish synchronises whenever
     // either side is host memory, and only then is a slot used), so no slot is live when the next call starts.
