@@ -254,6 +254,16 @@ def pad(frames, key, cap, dtype, fill=0, shape=()):
     return out
 
 
+def fill_levels(p, **tables):
+    """nlevels and the per-level tables (field name = values, all of one length) of a params record; tables longer than the record's 16
+    entries are left unfilled for the library to refuse."""
+    n = len(next(iter(tables.values())))
+    p["nlevels"] = n
+    if n <= 16:
+        for k, v in tables.items():
+            p[k][0, :n] = v
+
+
 def call(name, handle, device, *args):
     """The handle form `name` on handle.h when a handle is given, else `name`_batch on the device's shared one."""
     if handle is not None:

@@ -20,18 +20,18 @@
 // Pins (tests/fuse_model.py is the sequential model; contraction off): the arithmetic of msl.h's "reproduced exactly" list; a keypoint
 // octave outside [0, nlevels) is never a candidate; a held_id outside [0, n_pts) is an empty slot; device-only: an id outside the point
 // table is NULL, a tgt outside the keyframe table has no pose, so its live candidates leave as NO_FEATURE, a list outside the lists is empty.
+#include "msl_fuse_list.h"
+#include "msl_mappoint_check.h"
 #include "msl_match_window.h"
 
 #include <algorithm>
-#include <vector>
 
 namespace {
 
 using namespace msl;
 
-constexpr int MAX_LCAP = 65536, MAX_TCAP = 64, MAX_ITEMS = 4096;
+constexpr int MAX_TCAP = 64;
 constexpr int HELD_NT = 1024, SEARCH_NT = 256, RESOLVE_NT = 1024, CAND_NT = 1024;
-constexpr unsigned ID_NONE = 0xFFFFFFFFu;
 constexpr size_t CAND_SCRATCH = (size_t)1 << 24;   // entries of msl_fuse_candidates' scratch: the items in flight share it
 
 // What msl_debug_fuse reads per (item, candidate)
@@ -62,15 +62,7 @@ __global__ __launch_bounds__(HELD_NT) void k_fuse_held(FuseDev D) {
         s_key[i] = key;
     }
     bitonic_sort(s_key, P);
-    for (int i = threadIdx.x; i < P; i += HELD_NT) D.heldSorted[(size_t)k * P + i] = s_key[i] == ~0ull ? ID_NONE : (unsigned)s_key[i];
-}
-
-// The list of item f: its row of cand and its length (0 for a list outside the lists)
-__device__ __forceinline__ int item_list(const FuseDev &D, int f, const int32_t *&row) {
-    const int li = D.list[f];
-    if (li < 0 || li >= D.nLists) { row = D.cand; return 0; }
-    row = D.cand + (size_t)li * D.lcap;
-    return clampi(D.nCand[li], 0, D.lcap);
+    for (int i = threadIdx.x; i < P; i += HELD_NT) D.heldSorted[(size_t)k * P + i] = s_key[i] == ~0ull ? NO_ENTRY : (unsigned)s_key[i];
 }
 
 // ==== the loop body of ORBmatcher::Fuse up to bestDist ========================================================================================
@@ -200,14 +192,9 @@ __global__ __launch_bounds__(RESOLVE_NT) void k_fuse_resolve(FuseDev D) {
     const int nc = item_list(D, f, row);
     const int k = D.tgt[f];
     const size_t fb = (size_t)f * D.lcap;
-    for (int s = threadIdx.x; s < 2 * cap; s += RESOLVE_NT) s_hit[s] = ID_NONE;
+    for (int s = threadIdx.x; s < 2 * cap; s += RESOLVE_NT) s_hit[s] = NO_ENTRY;
     __syncthreads();
-    for (int j = threadIdx.x; j < nc; j += RESOLVE_NT)
-        if (D.status[fb + j] == MSL_FUSE_ADDED) atomicMin(&first[D.bestIdx[fb + j]], (unsigned)j);
-    __syncthreads();
-    for (int j = threadIdx.x; j < nc; j += RESOLVE_NT)
-        if (D.status[fb + j] == MSL_FUSE_ADDED) { const int s = D.bestIdx[fb + j]; if (first[s] != (unsigned)j) atomicMin(&second[s], (unsigned)j); }
-    __syncthreads();
+    first_two_hits<RESOLVE_NT>(D.status, D.bestIdx, fb, MSL_FUSE_ADDED, nc, first, second, [](int, int) { return false; });
     int mine = 0;
     for (int j = threadIdx.x; j < nc; j += RESOLVE_NT) {
         if (D.status[fb + j] != MSL_FUSE_ADDED) continue;                      // a matched candidate: its tgt is a table keyframe
@@ -267,7 +254,7 @@ __global__ __launch_bounds__(CAND_NT) void k_fuse_cand(CandDev D) {
     const int total = clampi(D.nTargets[f], 0, D.tcap) * D.cap;
     for (int pos = threadIdx.x; pos < total; pos += CAND_NT) {
         const int id = cand_id(D, f, pos);
-        if (id >= 0) __hip_atomic_store(&first[id], ID_NONE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (id >= 0) __hip_atomic_store(&first[id], NO_ENTRY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     __threadfence(); __syncthreads();
     for (int pos = threadIdx.x; pos < total; pos += CAND_NT) {
@@ -299,26 +286,15 @@ __global__ __launch_bounds__(CAND_NT) void k_fuse_cand(CandDev D) {
 }
 
 // ==== host side ==============================================================================================================================
-bool common_limits(const char *who, int n_tab, int cap, int n_pts, int n_items, int lcap) {
-    if (!table_limits(who, n_tab, cap, n_pts)) return false;
-    if (n_items < 1 || n_items > MAX_ITEMS) { set_error("%s: n_items %d outside 1 .. %d", who, n_items, MAX_ITEMS); return false; }
-    if (lcap < 1 || lcap > MAX_LCAP) { set_error("%s: lcap %d outside 1 .. %d", who, lcap, MAX_LCAP); return false; }
-    return true;
-}
-
 int run_fuse_candidates(msl_match *h, int n_tab, int cap, int n_pts, int n_items, int tcap, int lcap, const int32_t *held_id, const int32_t *n_kps,
                         const uint8_t *pt_flags, const int32_t *targets, const int32_t *n_targets, msl_mem mem, int32_t *cand, int32_t *n_cand,
                         msl_mem out_mem) {
     const char *who = "msl_fuse_candidates";
     if (!h || !held_id || !n_kps || !pt_flags || !targets || !n_targets || !cand || !n_cand) { set_error("%s: invalid argument (null pointer)", who); return MSL_ERR_INVALID; }
-    if (!common_limits(who, n_tab, cap, n_pts, n_items, lcap)) return MSL_ERR_INVALID;
+    if (!table_limits(who, n_tab, cap, n_pts) || !item_limits(who, n_items, lcap)) return MSL_ERR_INVALID;
     if (tcap < 1 || tcap > MAX_TCAP) { set_error("%s: tcap %d outside 1 .. %d", who, tcap, MAX_TCAP); return MSL_ERR_INVALID; }
-    if (mem == MSL_MEM_HOST)
-        for (int f = 0; f < n_items; f++) {
-            bool ok = n_targets[f] >= 0 && n_targets[f] <= tcap;
-            for (int t = 0; ok && t < n_targets[f]; t++) ok = targets[(size_t)f * tcap + t] >= 0 && targets[(size_t)f * tcap + t] < n_tab;
-            if (!ok) { set_error("%s: item %d names a keyframe outside the table of %d, or has n_targets outside 0 .. %d", who, f, n_tab, tcap); return MSL_ERR_INVALID; }
-        }
+    char why[256];
+    if (mem == MSL_MEM_HOST && !mappoint::targets_ok(n_tab, n_items, tcap, targets, n_targets, why, sizeof(why))) return refuse(who, why);
     int rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
     hipStream_t st = h->stream;
@@ -343,28 +319,6 @@ int run_fuse_candidates(msl_match *h, int n_tab, int cap, int n_pts, int n_items
     return MSL_OK;
 }
 
-// The checks a host-memory call can make on the items and lists.  Returns false with the error set.
-bool lists_ok(int n_tab, int n_pts, int n_items, int n_lists, int lcap, const int32_t *tgt, const int32_t *list, const int32_t *cand, const int32_t *n_cand) {
-    const char *who = "msl_fuse_map_points";
-    for (int f = 0; f < n_items; f++)
-        if (tgt[f] < 0 || tgt[f] >= n_tab || list[f] < 0 || list[f] >= n_lists) {
-            set_error("%s: item %d names keyframe %d of %d or list %d of %d", who, f, tgt[f], n_tab, list[f], n_lists);
-            return false;
-        }
-    std::vector<int32_t> seen((size_t)n_pts, -1);
-    for (int l = 0; l < n_lists; l++) {
-        if (n_cand[l] < 0 || n_cand[l] > lcap) { set_error("%s: list %d has n_cand %d outside 0 .. %d", who, l, n_cand[l], lcap); return false; }
-        for (int j = 0; j < n_cand[l]; j++) {
-            const int id = cand[(size_t)l * lcap + j];
-            if (id == -1) continue;
-            if (id < 0 || id >= n_pts) { set_error("%s: list %d entry %d is point %d of %d", who, l, j, id, n_pts); return false; }
-            if (seen[(size_t)id] == l) { set_error("%s: list %d holds point %d twice (pass -1 for a later duplicate)", who, l, id); return false; }
-            seen[(size_t)id] = l;
-        }
-    }
-    return true;
-}
-
 int run_fuse(msl_match *h, int n_tab, int cap, int n_pts, int n_items, int n_lists, int lcap, const msl_fuse_params *prm, const msl_keypoint *kps_un,
              const float *uright, const int32_t *grid_cell, const uint8_t *desc, const int32_t *n_kps, const float *Tcw, const int32_t *held_id,
              const float *pt_xyz, const float *pt_normal, const float *pt_dist, const uint8_t *pt_desc, const uint8_t *pt_flags, const int32_t *pt_nobs,
@@ -376,11 +330,12 @@ int run_fuse(msl_match *h, int n_tab, int cap, int n_pts, int n_items, int n_lis
         set_error("%s: invalid argument (null pointer)", who);
         return MSL_ERR_INVALID;
     }
-    if (!common_limits(who, n_tab, cap, n_pts, n_items, lcap)) return MSL_ERR_INVALID;
+    if (!table_limits(who, n_tab, cap, n_pts) || !item_limits(who, n_items, lcap)) return MSL_ERR_INVALID;
     if (n_lists < 1) { set_error("%s: n_lists %d below 1", who, n_lists); return MSL_ERR_INVALID; }
-    if (prm->nlevels < 1 || prm->nlevels > MSL_MATCH_MAX_LEVELS) { set_error("%s: nlevels %d outside 1 .. %d", who, prm->nlevels, MSL_MATCH_MAX_LEVELS); return MSL_ERR_INVALID; }
+    if (!levels_ok(who, prm->nlevels)) return MSL_ERR_INVALID;
     if (prm->th_low < 0 || prm->th_low > 255) { set_error("%s: th_low %d outside 0 .. 255", who, prm->th_low); return MSL_ERR_INVALID; }
-    if (mem == MSL_MEM_HOST && !lists_ok(n_tab, n_pts, n_items, n_lists, lcap, tgt, list, cand, n_cand)) return MSL_ERR_INVALID;
+    char why[256];
+    if (mem == MSL_MEM_HOST && !mappoint::lists_ok("point", n_tab, n_pts, n_items, n_lists, lcap, tgt, list, cand, n_cand, why, sizeof(why))) return refuse(who, why);
     int rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
     hipStream_t st = h->stream;
@@ -476,11 +431,9 @@ int msl_debug_fuse(msl_match *h, int item, float *uvr, int32_t *level_n) noexcep
         set_error("msl_debug_fuse: invalid argument (item outside the last msl_fuse_map_points call?)");
         return MSL_ERR_INVALID;
     }
-    int rc = bind_device(h->device);
+    std::vector<FuseRec> rec;
+    int rc = last_call_row(h, h->fuseRec, (size_t)item, (size_t)h->fuseLcap, rec);
     if (rc != MSL_OK) return rc;
-    MSL_HIP_TRY(hipStreamSynchronize(h->stream));
-    std::vector<FuseRec> rec((size_t)h->fuseLcap);
-    MSL_HIP_TRY(hipMemcpy(rec.data(), (const FuseRec *)h->fuseRec.p + (size_t)item * h->fuseLcap, rec.size() * sizeof(FuseRec), hipMemcpyDeviceToHost));
     for (int j = 0; j < h->fuseLcap; j++) {
         const FuseRec &r = rec[(size_t)j];
         uvr[3 * j] = r.u; uvr[3 * j + 1] = r.v; uvr[3 * j + 2] = r.ur;

@@ -491,11 +491,9 @@ int msl_lines_3d_debug(msl_match *h, int frame, int line, int32_t *counts, int32
         set_error("msl_lines_3d_debug: invalid argument (keyline outside the last msl_lines_3d call?)");
         return MSL_ERR_INVALID;
     }
-    int rc = bind_device(h->device);
+    std::vector<LineDbg> rec;
+    int rc = last_call_row(h, h->line3d, (size_t)frame * h->line3dLcap + line, 1, rec);   // a row of one record
     if (rc != MSL_OK) return rc;
-    MSL_HIP_TRY(hipStreamSynchronize(h->stream));
-    std::vector<LineDbg> rec(1);
-    MSL_HIP_TRY(hipMemcpy(rec.data(), (const LineDbg *)h->line3d.p + ((size_t)frame * h->line3dLcap + line), sizeof(LineDbg), hipMemcpyDeviceToHost));
     const LineDbg &r = rec[0];
     counts[0] = r.nKept; counts[1] = r.nIter; counts[2] = r.refits; counts[3] = r.end[0]; counts[4] = r.end[1];
     for (int k = 0; k < MAX_ITERS; k++)

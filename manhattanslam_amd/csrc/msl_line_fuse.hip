@@ -18,21 +18,19 @@
 // Pins (tests/linefuse_model.py is the sequential model; contraction off): the arithmetic of msl.h's lists; device-only: an id outside the
 // line table is NULL, a tgt outside the keyframe table has no pose and no keylines, so its live candidates leave at the query as
 // NO_FEATURE, a list outside the lists is empty.
+#include "msl_fuse_list.h"
 #include "msl_line_project.h"
-#include "msl_match_handle.h"
 #include "msl_mappoint_check.h"
+#include "msl_obs_walk.h"
 
 #include <algorithm>
 #include <climits>
-#include <vector>
 
 namespace {
 
 using namespace msl;
 
-constexpr int MAX_KLCAP = 256, MAX_LCAP = 65536, MAX_ITEMS = 4096, MAX_LINES = 1 << 20;
 constexpr int QUERY_NT = 256, SEARCH_NT = 256, RESOLVE_NT = 1024;
-constexpr unsigned J_NONE = 0xFFFFFFFFu;
 constexpr int CODE_SEARCH = 255;                     // LfRec::code of a candidate that reaches GetLinesInArea
 
 // The query of one (item, candidate), and what msl_debug_line_fuse reads
@@ -47,14 +45,6 @@ struct LfDev {
     int32_t *bestIdx, *bestDist; uint8_t *status; int32_t *other, *nFused;
     LfRec *rec;
 };
-
-// The list of item f: its row of cand and its length (0 for a list outside the lists)
-__device__ __forceinline__ int item_list(const LfDev &D, int f, const int32_t *&row) {
-    const int li = D.list[f];
-    if (li < 0 || li >= D.nLists) { row = D.cand; return 0; }
-    row = D.cand + (size_t)li * D.lcap;
-    return clampi(D.nCand[li], 0, D.lcap);
-}
 
 // ==== the loop body of LSDmatcher::Fuse up to the radius (:277-336) ===========================================================================
 __global__ __launch_bounds__(QUERY_NT) void k_lfuse_query(LfDev D) {
@@ -142,7 +132,7 @@ __global__ __launch_bounds__(SEARCH_NT) void k_lfuse_search(LfDev D) {
             const float rr = R.r * R.r;
             const double rs = (double)R.r * 0.01;
             const int Lm1 = wrap_add(R.level, -1);
-            unsigned key = J_NONE;
+            unsigned key = NO_ENTRY;
             for (int i = lane; i < nkl; i += WAVE) {
                 const msl_keyline kl = s_kl[i];
                 const double dx = mx - (double)kl.x, dy = my - (double)kl.y;
@@ -159,7 +149,7 @@ __global__ __launch_bounds__(SEARCH_NT) void k_lfuse_search(LfDev D) {
             key = wave_min(key);
             cnt = wave_sum(cnt);
             if (cnt == 0) status = MSL_LFUSE_NO_FEATURE;                       // :340
-            else if (key == J_NONE) status = MSL_LFUSE_NO_CANDIDATE;
+            else if (key == NO_ENTRY) status = MSL_LFUSE_NO_CANDIDATE;
             else {
                 bestDist = (int)(key >> 8); bestIdx = (int)(key & 255u);
                 status = bestDist <= D.prm.th_low ? MSL_LFUSE_ADDED : MSL_LFUSE_ABOVE_TH_LOW;   // ADDED: matched; k_lfuse_resolve decides
@@ -188,27 +178,20 @@ __global__ __launch_bounds__(RESOLVE_NT) void k_lfuse_resolve(LfDev D) {
     for (int s = threadIdx.x; s < MAX_KLCAP; s += RESOLVE_NT) {
         int h = -1;
         if (s < nkl) { h = D.held[(size_t)k * D.klcap + s]; if (h < 0 || h >= D.nLines) h = -1; }
-        s_held[s] = h; s_first[s] = J_NONE; s_second[s] = J_NONE; s_hold[s] = -1; s_keeps[s] = 0;
+        s_held[s] = h; s_first[s] = NO_ENTRY; s_second[s] = NO_ENTRY; s_hold[s] = -1; s_keeps[s] = 0;
     }
     if (threadIdx.x == 0) s_count = 0;
     __syncthreads();
-    for (int j = threadIdx.x; j < nc; j += RESOLVE_NT)
-        if (D.status[fb + j] == MSL_LFUSE_ADDED) { const int s = D.bestIdx[fb + j]; if (row[j] != s_held[s]) atomicMin(&s_first[s], (unsigned)j); }
-    __syncthreads();
-    for (int j = threadIdx.x; j < nc; j += RESOLVE_NT)
-        if (D.status[fb + j] == MSL_LFUSE_ADDED) {
-            const int s = D.bestIdx[fb + j];
-            if (row[j] != s_held[s] && s_first[s] != (unsigned)j) atomicMin(&s_second[s], (unsigned)j);
-        }
-    __syncthreads();
+    first_two_hits<RESOLVE_NT>(D.status, D.bestIdx, fb, MSL_LFUSE_ADDED, nc, s_first, s_second,
+                               [&](int j, int s) { return row[j] == s_held[s]; });   // a self-hit changes nothing
     for (int s = threadIdx.x; s < nkl; s += RESOLVE_NT) {                      // the holder and the direction after the deciding hit
         const unsigned j1 = s_first[s], j2 = s_second[s];
-        if (j1 == J_NONE) continue;
+        if (j1 == NO_ENTRY) continue;
         const int h0 = s_held[s], p1 = row[j1];
         if (h0 >= 0) {
             const bool keeps = D.nobs[h0] > D.nobs[p1];
             s_keeps[s] = keeps; s_hold[s] = keeps ? h0 : p1;
-        } else if (j2 != J_NONE) {
+        } else if (j2 != NO_ENTRY) {
             const int p2 = row[j2];
             bool in = false;                                                   // AddObservation's early return: p1 is in the keyframe already
             for (int t = 0; t < nkl; t++) in = in || s_held[t] == p1;
@@ -263,7 +246,8 @@ __global__ __launch_bounds__(WAVE) void k_line_refresh(LrDev D) {
     double normal[3] = {0.0, 0.0, 0.0};
     float dist[2] = {0.0f, 0.0f};
     if (id >= 0 && id < D.nLines && (D.flags[id] & 1)) {                       // uniform, as every branch outside the lane loops
-        const int b = clampi(D.off[id], 0, D.nObs), e = clampi(D.off[id + 1], b, D.nObs);
+        int b, e;
+        obs_range(D, id, b, e);
         const int ref = D.ref[id];
         const double *P = D.xyz + (size_t)id * 6;
         double mid[3];
@@ -273,11 +257,9 @@ __global__ __launch_bounds__(WAVE) void k_line_refresh(LrDev D) {
         bool refSeen = false;
         double acc[3] = {0.0, 0.0, 0.0};
         for (int c = b; c < e; c += WAVE) {
-            const int o = c + lane;
-            int kk = -1, idx = -1;
-            if (o < e) { kk = D.okf[o]; idx = D.oidx[o]; }
-            const bool valid = kk >= 0 && kk < D.nTab;
-            unsigned long long m = __ballot(valid);
+            int kk, idx;
+            bool valid;
+            const unsigned long long m = obs_chunk(D, c + lane, e, kk, idx, valid);
             n += __popcll(m);
             double t[3] = {0.0, 0.0, 0.0};
             if (valid) {
@@ -290,14 +272,8 @@ __global__ __launch_bounds__(WAVE) void k_line_refresh(LrDev D) {
 #pragma unroll
                 for (int a = 0; a < 3; a++) t[a] = v[a] / nrm;
             }
-            const unsigned long long mr = __ballot(valid && kk == ref);
-            if (!refSeen && mr) { refIdx = __shfl(idx, __ffsll(mr) - 1); refSeen = true; }
-            while (m) {                                                        // normal = normal + normali / norm, in list order
-                const int j = __ffsll(m) - 1;
-                m &= m - 1;
-#pragma unroll
-                for (int a = 0; a < 3; a++) acc[a] = acc[a] + __shfl(t[a], j);
-            }
+            obs_ref_index(valid && kk == ref, idx, refSeen, refIdx);
+            obs_add_in_order(m, t, acc);                                       // normal = normal + normali / norm, in list order
         }
         status = MSL_REFRESH_NO_OBS;
         if (n > 0) {
@@ -322,49 +298,12 @@ __global__ __launch_bounds__(WAVE) void k_line_refresh(LrDev D) {
     if (lane == 0) {
         D.status[f] = (uint8_t)status;
         const bool wrote = status == MSL_REFRESH_NORMAL_WRITTEN;
-#pragma unroll
-        for (int a = 0; a < 3; a++) {
-            D.outNormal[3 * (size_t)f + a] = normal[a];
-            if (D.lnNormal && wrote) D.lnNormal[3 * (size_t)id + a] = normal[a];
-        }
-#pragma unroll
-        for (int a = 0; a < 2; a++) {
-            D.outDist[2 * (size_t)f + a] = dist[a];
-            if (D.lnDist && wrote) D.lnDist[2 * (size_t)id + a] = dist[a];
-        }
+        write_item_and_row(D.outNormal, D.lnNormal, wrote, f, id, normal);
+        write_item_and_row(D.outDist, D.lnDist, wrote, f, id, dist);
     }
 }
 
 // ==== host side ==============================================================================================================================
-bool line_table_limits(const char *who, int n_tab, int klcap, int n_lines) {
-    if (n_tab < 1 || n_tab > MAX_TAB) { set_error("%s: n_tab %d outside 1 .. %d", who, n_tab, MAX_TAB); return false; }
-    if (klcap < 1 || klcap > MAX_KLCAP) { set_error("%s: klcap %d outside 1 .. %d", who, klcap, MAX_KLCAP); return false; }
-    if (n_lines < 1 || n_lines > MAX_LINES) { set_error("%s: n_lines %d outside 1 .. %d", who, n_lines, MAX_LINES); return false; }
-    return true;
-}
-
-// The checks a host-memory call can make on the items and lists.  Returns false with the error set.
-bool lists_ok(const char *who, int n_tab, int n_lines, int n_items, int n_lists, int lcap, const int32_t *tgt, const int32_t *list,
-              const int32_t *cand, const int32_t *n_cand) {
-    for (int f = 0; f < n_items; f++)
-        if (tgt[f] < 0 || tgt[f] >= n_tab || list[f] < 0 || list[f] >= n_lists) {
-            set_error("%s: item %d names keyframe %d of %d or list %d of %d", who, f, tgt[f], n_tab, list[f], n_lists);
-            return false;
-        }
-    std::vector<int32_t> seen((size_t)n_lines, -1);
-    for (int l = 0; l < n_lists; l++) {
-        if (n_cand[l] < 0 || n_cand[l] > lcap) { set_error("%s: list %d has n_cand %d outside 0 .. %d", who, l, n_cand[l], lcap); return false; }
-        for (int j = 0; j < n_cand[l]; j++) {
-            const int id = cand[(size_t)l * lcap + j];
-            if (id == -1) continue;
-            if (id < 0 || id >= n_lines) { set_error("%s: list %d entry %d is line %d of %d", who, l, j, id, n_lines); return false; }
-            if (seen[(size_t)id] == l) { set_error("%s: list %d holds line %d twice (pass -1 for a later duplicate)", who, l, id); return false; }
-            seen[(size_t)id] = l;
-        }
-    }
-    return true;
-}
-
 int run_line_fuse(msl_match *h, int n_tab, int klcap, int n_lines, int n_items, int n_lists, int lcap, const msl_line_fuse_params *prm,
                   const msl_keyline *kl, const uint8_t *ldesc, const int32_t *n_kl, const float *Tcw, const int32_t *held_id, const double *ln_xyz,
                   const double *ln_normal, const float *ln_dist, const uint8_t *ln_desc, const uint8_t *ln_flags, const int32_t *ln_nobs,
@@ -376,13 +315,12 @@ int run_line_fuse(msl_match *h, int n_tab, int klcap, int n_lines, int n_items, 
         set_error("%s: invalid argument (null pointer)", who);
         return MSL_ERR_INVALID;
     }
-    if (!line_table_limits(who, n_tab, klcap, n_lines)) return MSL_ERR_INVALID;
-    if (n_items < 1 || n_items > MAX_ITEMS) { set_error("%s: n_items %d outside 1 .. %d", who, n_items, MAX_ITEMS); return MSL_ERR_INVALID; }
-    if (lcap < 1 || lcap > MAX_LCAP) { set_error("%s: lcap %d outside 1 .. %d", who, lcap, MAX_LCAP); return MSL_ERR_INVALID; }
+    if (!line_table_limits(who, n_tab, klcap, n_lines) || !item_limits(who, n_items, lcap)) return MSL_ERR_INVALID;
     if (n_lists < 1) { set_error("%s: n_lists %d below 1", who, n_lists); return MSL_ERR_INVALID; }
-    if (prm->nlevels < 1 || prm->nlevels > MSL_MATCH_MAX_LEVELS) { set_error("%s: nlevels %d outside 1 .. %d", who, prm->nlevels, MSL_MATCH_MAX_LEVELS); return MSL_ERR_INVALID; }
+    if (!levels_ok(who, prm->nlevels)) return MSL_ERR_INVALID;
     if (prm->th_low < 0 || prm->th_low > 256) { set_error("%s: th_low %d outside 0 .. 256", who, prm->th_low); return MSL_ERR_INVALID; }
-    if (mem == MSL_MEM_HOST && !lists_ok(who, n_tab, n_lines, n_items, n_lists, lcap, tgt, list, cand, n_cand)) return MSL_ERR_INVALID;
+    char why[256];
+    if (mem == MSL_MEM_HOST && !mappoint::lists_ok("line", n_tab, n_lines, n_items, n_lists, lcap, tgt, list, cand, n_cand, why, sizeof(why))) return refuse(who, why);
     int rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
     hipStream_t st = h->stream;
@@ -425,15 +363,10 @@ int run_line_refresh(msl_match *h, int n_tab, int klcap, int n_lines, int n_item
     if (!line_table_limits(who, n_tab, klcap, n_lines)) return MSL_ERR_INVALID;
     if (n_obs_total < 0) { set_error("%s: n_obs_total %d below 0", who, n_obs_total); return MSL_ERR_INVALID; }
     if (n_items < 1 || n_items > n_lines) { set_error("%s: n_items %d outside 1 .. n_lines = %d", who, n_items, n_lines); return MSL_ERR_INVALID; }
-    if (prm->nlevels < 1 || prm->nlevels > MSL_MATCH_MAX_LEVELS) { set_error("%s: nlevels %d outside 1 .. %d", who, prm->nlevels, MSL_MATCH_MAX_LEVELS); return MSL_ERR_INVALID; }
-    if (mem == MSL_MEM_HOST) {
-        char why[256];
-        if (!mappoint::csr_ok(n_tab, klcap, n_lines, n_obs_total, obs_off, obs_kf, obs_idx, n_kl, why, sizeof(why)) ||
-            !mappoint::items_ok("ids", n_lines, n_items, ids, true, why, sizeof(why))) {
-            set_error("%s: %s", who, why);
-            return MSL_ERR_INVALID;
-        }
-    }
+    if (!levels_ok(who, prm->nlevels)) return MSL_ERR_INVALID;
+    char why[256];
+    if (mem == MSL_MEM_HOST && (!mappoint::csr_ok(n_tab, klcap, n_lines, n_obs_total, obs_off, obs_kf, obs_idx, n_kl, why, sizeof(why)) ||
+                                !mappoint::items_ok("ids", n_lines, n_items, ids, true, why, sizeof(why)))) return refuse(who, why);
     int rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
     const size_t T = (size_t)n_tab, nt = T * klcap, F = (size_t)n_items, nl = (size_t)n_lines, no = (size_t)n_obs_total;
@@ -510,11 +443,9 @@ int msl_debug_line_fuse(msl_match *h, int item, float *uvr, int32_t *level_n) no
         set_error("msl_debug_line_fuse: invalid argument (item outside the last msl_fuse_map_lines call?)");
         return MSL_ERR_INVALID;
     }
-    int rc = bind_device(h->device);
+    std::vector<LfRec> rec;
+    int rc = last_call_row(h, h->lfuseRec, (size_t)item, (size_t)h->lfuseLcap, rec);
     if (rc != MSL_OK) return rc;
-    MSL_HIP_TRY(hipStreamSynchronize(h->stream));
-    std::vector<LfRec> rec((size_t)h->lfuseLcap);
-    MSL_HIP_TRY(hipMemcpy(rec.data(), (const LfRec *)h->lfuseRec.p + (size_t)item * h->lfuseLcap, rec.size() * sizeof(LfRec), hipMemcpyDeviceToHost));
     for (int j = 0; j < h->lfuseLcap; j++) {
         const LfRec &r = rec[(size_t)j];
         uvr[5 * j] = r.x1; uvr[5 * j + 1] = r.y1; uvr[5 * j + 2] = r.x2; uvr[5 * j + 3] = r.y2; uvr[5 * j + 4] = r.r;

@@ -15,8 +15,8 @@
 // keyframe is outside the table is skipped as if absent, one whose keypoint index is outside [0, cap) has no descriptor; an id outside the
 // point table is a bad point; a pt_ref outside the table, or a reference keypoint outside [0, cap), leaves as MSL_REFRESH_BAD_OCTAVE.
 #include "msl_match_handle.h"
-#include "msl_match_math.h"
 #include "msl_mappoint_check.h"
+#include "msl_obs_walk.h"
 
 namespace {
 
@@ -55,7 +55,8 @@ __global__ __launch_bounds__(WAVE) void k_refresh(RefreshDev D) {
     uint4 d0 = make_uint4(0, 0, 0, 0), d1 = d0;
     float normal[3] = {0.0f, 0.0f, 0.0f}, dist[2] = {0.0f, 0.0f};
     if (id >= 0 && id < D.nPts && (D.flags[id] & 1)) {                         // uniform, as every branch outside the lane loops
-        const int b = clampi(D.off[id], 0, D.nObs), e = clampi(D.off[id + 1], b, D.nObs);
+        int b, e;
+        obs_range(D, id, b, e);
         const int ref = wantN ? D.ref[id] : -1;
         float X[3] = {0.0f, 0.0f, 0.0f};
         if (wantN) { X[0] = D.xyz[3 * (size_t)id]; X[1] = D.xyz[3 * (size_t)id + 1]; X[2] = D.xyz[3 * (size_t)id + 2]; }
@@ -64,10 +65,11 @@ __global__ __launch_bounds__(WAVE) void k_refresh(RefreshDev D) {
         float acc[3] = {0.0f, 0.0f, 0.0f};
         for (int c = b; c < e; c += WAVE) {
             const int o = c + lane;
+            // obs_chunk of msl_obs_walk.h, written out: around the shared form the compiler swaps operands in this kernel's pinned text
             int k = -1, idx = -1;
             if (o < e) { k = D.okf[o]; idx = D.oidx[o]; }
             const bool valid = k >= 0 && k < D.nTab;
-            unsigned long long m = __ballot(valid);
+            const unsigned long long m = __ballot(valid);
             n += __popcll(m);
             if (wantD) {
                 const bool live = valid && (D.kfFlags[k] & 1) && idx >= 0 && idx < D.cap;
@@ -87,14 +89,9 @@ __global__ __launch_bounds__(WAVE) void k_refresh(RefreshDev D) {
 #pragma unroll
                     for (int a = 0; a < 3; a++) t[a] = (float)((double)v[a] * inv);
                 }
-                const unsigned long long mr = __ballot(valid && k == ref);
+                const unsigned long long mr = __ballot(valid && k == ref);     // obs_ref_index, written out as obs_chunk above
                 if (!refSeen && mr) { refIdx = __shfl(idx, __ffsll(mr) - 1); refSeen = true; }
-                while (m) {                                                    // normal = normal + normali / norm, in list order
-                    const int j = __ffsll(m) - 1;
-                    m &= m - 1;
-#pragma unroll
-                    for (int a = 0; a < 3; a++) acc[a] = acc[a] + __shfl(t[a], j);
-                }
+                obs_add_in_order(m, t, acc);                                   // normal = normal + normali / norm, in list order
             }
         }
         status = MSL_REFRESH_NO_OBS;
@@ -150,7 +147,7 @@ __global__ __launch_bounds__(WAVE) void k_refresh(RefreshDev D) {
         D.bestObs[f] = bestObs; D.bestMedian[f] = bestMedian; D.status[f] = (uint8_t)status;
         const bool wrote = status & MSL_REFRESH_NORMAL_WRITTEN;
 #pragma unroll
-        for (int a = 0; a < 3; a++) {
+        for (int a = 0; a < 3; a++) {                                          // write_item_and_row, written out as the other two
             D.outNormal[3 * (size_t)f + a] = normal[a];
             if (D.ptNormal && wrote) D.ptNormal[3 * (size_t)id + a] = normal[a];
         }
@@ -184,7 +181,7 @@ __global__ __launch_bounds__(COVIS_NT) void k_covis(CovisDev D) {
         for (int i = threadIdx.x; i < n; i += COVIS_NT) {
             const int id = D.held[(size_t)k * D.cap + i];
             if (id < 0 || id >= D.nPts || !(D.flags[id] & 1)) continue;
-            const int b = clampi(D.off[id], 0, D.nObs), e = clampi(D.off[id + 1], b, D.nObs);
+            const int b = clampi(D.off[id], 0, D.nObs), e = clampi(D.off[id + 1], b, D.nObs);   // obs_range, written out (msl_obs_walk.h)
             for (int o = b; o < e; o++) {
                 const int kk = D.okf[o];
                 if (kk >= 0 && kk < D.nTab && kk != k) atomicAdd(&s_cnt[kk], 1u);      // a bad observer counts: the reference has no test
@@ -238,16 +235,11 @@ int run_refresh(msl_match *h, int n_tab, int cap, int n_pts, int n_items, int n_
     }
     if (!csr_limits(who, n_tab, cap, n_pts, n_obs_total)) return MSL_ERR_INVALID;
     if (n_items < 1 || n_items > n_pts) { set_error("%s: n_items %d outside 1 .. n_pts = %d", who, n_items, n_pts); return MSL_ERR_INVALID; }
-    if (wantN && (prm->nlevels < 1 || prm->nlevels > MSL_MATCH_MAX_LEVELS)) { set_error("%s: nlevels %d outside 1 .. %d", who, prm->nlevels, MSL_MATCH_MAX_LEVELS); return MSL_ERR_INVALID; }
-    if (mem == MSL_MEM_HOST) {
-        char why[256];
-        if (!mappoint::csr_ok(n_tab, cap, n_pts, n_obs_total, obs_off, obs_kf, obs_idx, n_kps, why, sizeof(why)) ||
-            !mappoint::items_ok("ids", n_pts, n_items, ids, true, why, sizeof(why)) ||
-            (wantN && !mappoint::refs_ok(n_tab, n_items, ids, pt_ref, why, sizeof(why)))) {
-            set_error("%s: %s", who, why);
-            return MSL_ERR_INVALID;
-        }
-    }
+    if (wantN && !levels_ok(who, prm->nlevels)) return MSL_ERR_INVALID;
+    char why[256];
+    if (mem == MSL_MEM_HOST && (!mappoint::csr_ok(n_tab, cap, n_pts, n_obs_total, obs_off, obs_kf, obs_idx, n_kps, why, sizeof(why)) ||
+                                !mappoint::items_ok("ids", n_pts, n_items, ids, true, why, sizeof(why)) ||
+                                (wantN && !mappoint::refs_ok(n_tab, n_items, ids, pt_ref, why, sizeof(why))))) return refuse(who, why);
     int rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
     const size_t T = (size_t)n_tab, nt = T * cap, F = (size_t)n_items, np = (size_t)n_pts, no = (size_t)n_obs_total;
@@ -281,14 +273,9 @@ int run_covisibility(msl_match *h, int n_tab, int cap, int n_pts, int n_items, i
     if (!csr_limits(who, n_tab, cap, n_pts, n_obs_total)) return MSL_ERR_INVALID;
     if (n_items < 1 || n_items > n_tab) { set_error("%s: n_items %d outside 1 .. n_tab = %d", who, n_items, n_tab); return MSL_ERR_INVALID; }
     if (ccap < 1 || ccap > n_tab) { set_error("%s: ccap %d outside 1 .. n_tab = %d", who, ccap, n_tab); return MSL_ERR_INVALID; }
-    if (mem == MSL_MEM_HOST) {
-        char why[256];
-        if (!mappoint::csr_ok(n_tab, cap, n_pts, n_obs_total, obs_off, obs_kf, nullptr, n_kps, why, sizeof(why)) ||
-            !mappoint::items_ok("kf", n_tab, n_items, kf, false, why, sizeof(why))) {
-            set_error("%s: %s", who, why);
-            return MSL_ERR_INVALID;
-        }
-    }
+    char why[256];
+    if (mem == MSL_MEM_HOST && (!mappoint::csr_ok(n_tab, cap, n_pts, n_obs_total, obs_off, obs_kf, nullptr, n_kps, why, sizeof(why)) ||
+                                !mappoint::items_ok("kf", n_tab, n_items, kf, false, why, sizeof(why)))) return refuse(who, why);
     int rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
     const size_t T = (size_t)n_tab, F = (size_t)n_items, np = (size_t)n_pts, no = (size_t)n_obs_total;

@@ -1,7 +1,10 @@
-// msl_mappoint_check.h -- what a host-memory call of msl_refresh_map_points / msl_covisibility checks of its index arrays before any launch
-// (msl_mappoint.hip): the observation table (CSR over the point table), the reference keyframes and the item list.  Pure host functions on
-// plain arrays: no HIP call, no allocation through the library, no global state, so a plain C++ program can call them
-// (tests/mappoint_csr_host.cpp).  Each returns true, or false with a message that names the field in err.
+// msl_mappoint_check.h -- what a host-memory call of a LocalMapping entry point checks of its index arrays before any launch: the observation
+// table (CSR over the point table), the reference keyframes and the item list of msl_refresh_map_points / msl_covisibility / msl_refresh_map_lines
+// (msl_mappoint.hip, msl_line_fuse.hip), the items and candidate lists of msl_fuse_map_points / msl_fuse_map_lines, the targets of
+// msl_fuse_candidates (msl_fuse.hip) and the neighbours of msl_triangulate_new_points (msl_triangulate.hip).  Pure host functions on plain
+// arrays: no HIP call, no allocation through the library, no global state, so a plain C++ program can call them
+// (tests/mappoint_csr_host.cpp, tests/mapping_lists_host.cpp).  Each returns true, or false with a message that names the field in err; the
+// caller puts its own name in front ("%s: %s").
 #pragma once
 
 #include <stdint.h>
@@ -54,6 +57,63 @@ inline bool refs_ok(int n_tab, int n_items, const int32_t *ids, const int32_t *p
     for (int f = 0; f < n_items; f++) {
         const int r = pt_ref[ids[f]];
         if (r < 0 || r >= n_tab) { snprintf(err, err_len, "pt_ref[%d] is keyframe %d of %d", (int)ids[f], r, n_tab); return false; }
+    }
+    return true;
+}
+
+// The items and lists of a fusion call: every item's target keyframe inside the table of n_tab and its list inside the n_lists lists; every
+// list's length inside 0 .. lcap and, only then, its entries: -1 (as often as it likes) or an id of the table of n rows, no id twice in one
+// list.  noun: what the ids name, "point" or "line".
+inline bool lists_ok(const char *noun, int n_tab, int n, int n_items, int n_lists, int lcap, const int32_t *tgt, const int32_t *list,
+                     const int32_t *cand, const int32_t *n_cand, char *err, size_t err_len) {
+    for (int f = 0; f < n_items; f++)
+        if (tgt[f] < 0 || tgt[f] >= n_tab || list[f] < 0 || list[f] >= n_lists) {
+            snprintf(err, err_len, "item %d names keyframe %d of %d or list %d of %d", f, (int)tgt[f], n_tab, (int)list[f], n_lists);
+            return false;
+        }
+    std::vector<int32_t> seen((size_t)n, -1);
+    for (int l = 0; l < n_lists; l++) {
+        if (n_cand[l] < 0 || n_cand[l] > lcap) { snprintf(err, err_len, "list %d has n_cand %d outside 0 .. %d", l, (int)n_cand[l], lcap); return false; }
+        for (int j = 0; j < n_cand[l]; j++) {
+            const int id = cand[(size_t)l * lcap + j];
+            if (id == -1) continue;
+            if (id < 0 || id >= n) { snprintf(err, err_len, "list %d entry %d is %s %d of %d", l, j, noun, id, n); return false; }
+            if (seen[(size_t)id] == l) { snprintf(err, err_len, "list %d holds %s %d twice (pass -1 for a later duplicate)", l, noun, id); return false; }
+            seen[(size_t)id] = l;
+        }
+    }
+    return true;
+}
+
+// The items of msl_triangulate_new_points: the current keyframe inside the table, n_neigh inside 0 .. ncap, the neighbours inside the
+// table, distinct and none the current keyframe.
+inline bool neighbours_ok(int n_tab, int n_items, int ncap, const int32_t *cur, const int32_t *neigh, const int32_t *n_neigh, char *err,
+                          size_t err_len) {
+    for (int f = 0; f < n_items; f++) {
+        bool ok = cur[f] >= 0 && cur[f] < n_tab && n_neigh[f] >= 0 && n_neigh[f] <= ncap;
+        for (int r = 0; ok && r < n_neigh[f]; r++) {
+            const int k = neigh[(size_t)f * ncap + r];
+            ok = k >= 0 && k < n_tab && k != cur[f];
+            for (int q = 0; ok && q < r; q++) ok = neigh[(size_t)f * ncap + q] != k;
+        }
+        if (!ok) {
+            snprintf(err, err_len, "item %d names a keyframe outside the table of %d, repeats a neighbour, lists its current keyframe as a "
+                     "neighbour, or has n_neigh outside 0 .. %d", f, n_tab, ncap);
+            return false;
+        }
+    }
+    return true;
+}
+
+// The items of msl_fuse_candidates: n_targets inside 0 .. tcap and, only then, the targets inside the table
+inline bool targets_ok(int n_tab, int n_items, int tcap, const int32_t *targets, const int32_t *n_targets, char *err, size_t err_len) {
+    for (int f = 0; f < n_items; f++) {
+        bool ok = n_targets[f] >= 0 && n_targets[f] <= tcap;
+        for (int t = 0; ok && t < n_targets[f]; t++) ok = targets[(size_t)f * tcap + t] >= 0 && targets[(size_t)f * tcap + t] < n_tab;
+        if (!ok) {
+            snprintf(err, err_len, "item %d names a keyframe outside the table of %d, or has n_targets outside 0 .. %d", f, n_tab, tcap);
+            return false;
+        }
     }
     return true;
 }

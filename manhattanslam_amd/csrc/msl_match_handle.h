@@ -1,16 +1,21 @@
-// msl_match_handle.h -- the matcher handle, its staging of caller arrays (Stage) and the forwarder of the *_batch entry points; shared by
-// msl_match.hip, msl_line_match.hip, msl_pose.hip, msl_plane.hip, msl_bow.hip, msl_reloc.hip, msl_pnp.hip, msl_line3d.hip, msl_triangulate.hip, msl_fuse.hip, msl_mappoint.hip and msl_line_fuse.hip (internal).
+// msl_match_handle.h -- the matcher handle, its staging of caller arrays (Stage), the forwarder of the *_batch entry points, the limits
+// that several entry points share (table_limits, line_table_limits, levels_ok) and the row readback of the debug entry points (last_call_row);
+// shared by msl_match.hip, msl_line_match.hip, msl_pose.hip, msl_plane.hip, msl_bow.hip, msl_reloc.hip, msl_pnp.hip, msl_line3d.hip,
+// msl_triangulate.hip, msl_fuse.hip, msl_mappoint.hip and msl_line_fuse.hip (internal).
 #pragma once
 
 #include "msl_common.h"
+
+#include <vector>
 
 namespace msl {
 // What msl_pnp_ransac's table N -> (minInliers, maxIts) was built from (no padding: compared bytewise).
 struct PnpKey { double probability; int32_t min_inliers, max_iterations, min_set; float epsilon; int32_t cap, zero; };
 
 // Limits that several entry points share: keypoints of a frame or keyframe (feature indices fit 13 bits, item positions 16), keyframes of
-// a keyframe table, points of a point table.
+// a keyframe table, points of a point table; keylines of a keyframe (indices fit 8 bits), lines of a line table.
 constexpr int MAX_CAP = 8192, MAX_TAB = 4096, MAX_PTS = 1 << 20;
+constexpr int MAX_KLCAP = 256, MAX_LINES = 1 << 20;
 
 // The limits of a call that takes a keyframe table and a point table; false with the error set.
 inline bool table_limits(const char *who, int n_tab, int cap, int n_pts) {
@@ -19,6 +24,23 @@ inline bool table_limits(const char *who, int n_tab, int cap, int n_pts) {
     if (n_pts < 1 || n_pts > MAX_PTS) { set_error("%s: n_pts %d outside 1 .. %d", who, n_pts, MAX_PTS); return false; }
     return true;
 }
+
+// The same for a keyframe table of keylines and a line table
+inline bool line_table_limits(const char *who, int n_tab, int klcap, int n_lines) {
+    if (n_tab < 1 || n_tab > MAX_TAB) { set_error("%s: n_tab %d outside 1 .. %d", who, n_tab, MAX_TAB); return false; }
+    if (klcap < 1 || klcap > MAX_KLCAP) { set_error("%s: klcap %d outside 1 .. %d", who, klcap, MAX_KLCAP); return false; }
+    if (n_lines < 1 || n_lines > MAX_LINES) { set_error("%s: n_lines %d outside 1 .. %d", who, n_lines, MAX_LINES); return false; }
+    return true;
+}
+
+// The length of a call's scale tables; false with the error set.
+inline bool levels_ok(const char *who, int nlevels) {
+    if (nlevels < 1 || nlevels > MSL_MATCH_MAX_LEVELS) { set_error("%s: nlevels %d outside 1 .. %d", who, nlevels, MSL_MATCH_MAX_LEVELS); return false; }
+    return true;
+}
+
+// The refusal of a call whose host-side check (msl_mappoint_check.h) left its reason in why
+inline int refuse(const char *who, const char *why) { set_error("%s: %s", who, why); return MSL_ERR_INVALID; }
 }  // namespace msl
 
 // One matcher object = one ORBmatcher of the reference (src/ORBmatcher.cc:41): its own stream and its own scratch, used by one thread at a time;
@@ -85,6 +107,17 @@ int abi_call_default(Run run, int device, bool sync_legacy, A... a) {
     int rc = run(h, a...);
     if (rc == MSL_OK) rc = msl_match_sync(h);
     return rc;
+}
+
+// What a debug entry point reads of the handle's last call: row `row` of the scratch `buf`, n records long, once the stream is drained.
+template <class Rec>
+int last_call_row(msl_match *h, const DevBuf &buf, size_t row, size_t n, std::vector<Rec> &rec) {
+    int rc = bind_device(h->device);
+    if (rc != MSL_OK) return rc;
+    MSL_HIP_TRY(hipStreamSynchronize(h->stream));
+    rec.resize(n);
+    MSL_HIP_TRY(hipMemcpy(rec.data(), (const Rec *)buf.p + row * n, n * sizeof(Rec), hipMemcpyDeviceToHost));
+    return MSL_OK;
 }
 
 // Kernels that ask for more dynamic LDS than the default limit: the limit is raised once per handle (= per device) and kernel.

@@ -38,6 +38,7 @@
 //   * a table index outside [0, n_tab), or a neighbour equal to the current keyframe, that only the device can see: that neighbour is
 //     skipped (an invalid current keyframe has no keypoints)
 #include "msl_jacobi.h"
+#include "msl_mappoint_check.h"
 #include "msl_match_handle.h"
 #include "msl_match_math.h"
 
@@ -440,21 +441,6 @@ __global__ __launch_bounds__(WAVE) void k_tri_walk(TriDev D) {
 }
 
 // ==== host side ==============================================================================================================================
-// The checks a host-memory call can make on the item lists: every index inside the table, an item's neighbours distinct and none its
-// current keyframe.  Returns the offending item, or -1.
-int bad_item(int n_tab, int n_items, int ncap, const int32_t *cur, const int32_t *neigh, const int32_t *n_neigh) {
-    for (int f = 0; f < n_items; f++) {
-        if (cur[f] < 0 || cur[f] >= n_tab || n_neigh[f] < 0 || n_neigh[f] > ncap) return f;
-        for (int r = 0; r < n_neigh[f]; r++) {
-            const int k = neigh[(size_t)f * ncap + r];
-            if (k < 0 || k >= n_tab || k == cur[f]) return f;
-            for (int q = 0; q < r; q++)
-                if (neigh[(size_t)f * ncap + q] == k) return f;
-        }
-    }
-    return -1;
-}
-
 int run_triangulate(msl_match *h, int n_tab, int cap, int n_items, int ncap, const msl_triangulate_params *prm, const msl_keypoint *kps_un,
                     const float *raw_xy, const float *uright, const float *depth, const uint8_t *desc, const int32_t *node, const uint8_t *held,
                     const int32_t *n_kps, const float *Tcw, const int32_t *cur, const int32_t *neigh, const int32_t *n_neigh, msl_mem mem,
@@ -469,18 +455,10 @@ int run_triangulate(msl_match *h, int n_tab, int cap, int n_items, int ncap, con
     if (cap < 1 || cap > MAX_CAP) { set_error("msl_triangulate_new_points: cap %d outside 1 .. %d", cap, MAX_CAP); return MSL_ERR_INVALID; }
     if (ncap < 1 || ncap > MAX_NCAP) { set_error("msl_triangulate_new_points: ncap %d outside 1 .. %d", ncap, MAX_NCAP); return MSL_ERR_INVALID; }
     if (n_items > 65535) { set_error("msl_triangulate_new_points: n_items %d above 65535", n_items); return MSL_ERR_INVALID; }
-    if (prm->nlevels < 1 || prm->nlevels > MSL_MATCH_MAX_LEVELS) {
-        set_error("msl_triangulate_new_points: nlevels %d outside 1 .. %d", prm->nlevels, MSL_MATCH_MAX_LEVELS);
-        return MSL_ERR_INVALID;
-    }
-    if (mem == MSL_MEM_HOST) {
-        const int f = bad_item(n_tab, n_items, ncap, cur, neigh, n_neigh);
-        if (f >= 0) {
-            set_error("msl_triangulate_new_points: item %d names a keyframe outside the table of %d, repeats a neighbour, lists its current "
-                      "keyframe as a neighbour, or has n_neigh outside 0 .. %d", f, n_tab, ncap);
-            return MSL_ERR_INVALID;
-        }
-    }
+    if (!levels_ok("msl_triangulate_new_points", prm->nlevels)) return MSL_ERR_INVALID;
+    char why[256];
+    if (mem == MSL_MEM_HOST && !mappoint::neighbours_ok(n_tab, n_items, ncap, cur, neigh, n_neigh, why, sizeof(why)))
+        return refuse("msl_triangulate_new_points", why);
     int rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
     hipStream_t st = h->stream;
@@ -551,14 +529,12 @@ int msl_debug_triangulate(msl_match *h, int item, int neigh, float *pair, int32_
         set_error("msl_debug_triangulate: invalid argument (pair outside the last msl_triangulate_new_points call?)");
         return MSL_ERR_INVALID;
     }
-    int rc = bind_device(h->device);
-    if (rc != MSL_OK) return rc;
-    MSL_HIP_TRY(hipStreamSynchronize(h->stream));
     const size_t pr = (size_t)item * h->triNcap + neigh;
     TriPair G;
-    std::vector<TriRec> rec((size_t)h->triCap);
+    std::vector<TriRec> rec;
+    int rc = last_call_row(h, h->triRec, pr, (size_t)h->triCap, rec);
+    if (rc != MSL_OK) return rc;
     MSL_HIP_TRY(hipMemcpy(&G, (const TriPair *)h->triPair.p + pr, sizeof(TriPair), hipMemcpyDeviceToHost));
-    MSL_HIP_TRY(hipMemcpy(rec.data(), (const TriRec *)h->triRec.p + pr * h->triCap, rec.size() * sizeof(TriRec), hipMemcpyDeviceToHost));
     for (int i = 0; i < 9; i++) pair[i] = G.F12[i];
     pair[9] = G.ex; pair[10] = G.ey; pair[11] = G.baseline;
     for (int i = 0; i < h->triCap; i++) {

@@ -4,7 +4,7 @@ keyframe, candidate list) items from the state on entry (fuse_map_points), the d
 (debug_fuse)."""
 import numpy as np
 
-from ._lib import FUSE_PARAMS_DTYPE, KEYPOINT_DTYPE, MSL_MEM_DEVICE, MSL_MEM_HOST, call, check, lib, pad, ptr
+from ._lib import FUSE_PARAMS_DTYPE, KEYPOINT_DTYPE, MSL_MEM_DEVICE, MSL_MEM_HOST, call, check, fill_levels, lib, pad, ptr
 
 # MSL_FUSE_*: the exit of the loop body a candidate took
 (NULL, BAD, IN_KEYFRAME, BEHIND, OUT_OF_IMAGE, DISTANCE, VIEW_ANGLE, NO_FEATURE, NO_CANDIDATE, ABOVE_TH_LOW, ADDED, REPLACED_BY_HELD, REPLACES_HELD,
@@ -20,11 +20,7 @@ def fuse_params(fx, fy, cx, cy, bf, min_x, max_x, min_y, max_y, scale_factors, i
     p = np.zeros(1, FUSE_PARAMS_DTYPE)
     p["fx"], p["fy"], p["cx"], p["cy"], p["bf"] = fx, fy, cx, cy, bf
     p["minX"], p["maxX"], p["minY"], p["maxY"], p["th"] = min_x, max_x, min_y, max_y, th
-    n = len(scale_factors)
-    p["nlevels"] = n
-    if n <= 16:                                                   # a longer table is the library's to refuse
-        p["scale_factors"][0, :n] = scale_factors
-        p["inv_level_sigma2"][0, :n] = inv_level_sigma2
+    fill_levels(p, scale_factors=scale_factors, inv_level_sigma2=inv_level_sigma2)
     p["log_scale_factor"], p["th_low"] = log_scale_factor, th_low
     return p
 
@@ -62,7 +58,7 @@ def pack_lists(lists, lcap=None):
 
 
 def outputs(n_items, lcap, zeros=np.zeros):
-    """The output arrays of one msl_fuse_map_points call, in msl.h's order (zeros(shape, dtype) allocates)."""
+    """The output arrays of one msl_fuse_map_points or msl_fuse_map_lines call, in msl.h's order (zeros(shape, dtype) allocates)."""
     F, L = n_items, lcap
     return dict(best_idx=zeros((F, L), np.int32), best_dist=zeros((F, L), np.int32), status=zeros((F, L), np.uint8), other=zeros((F, L), np.int32),
                 n_fused=zeros((F,), np.int32))

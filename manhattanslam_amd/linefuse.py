@@ -5,8 +5,8 @@ and the query stage of the last fusion call (debug_line_fuse).  The candidate li
 held_id and flags; MapLine::ComputeDistinctiveDescriptors is mappoint.refresh_map_points with REFRESH_DESC alone."""
 import numpy as np
 
-from ._lib import KEYLINE_DTYPE, LINE_FUSE_PARAMS_DTYPE, MSL_MEM_DEVICE, MSL_MEM_HOST, call, check, lib, pad, ptr
-from .fuse import pack_lists
+from ._lib import KEYLINE_DTYPE, LINE_FUSE_PARAMS_DTYPE, MSL_MEM_DEVICE, MSL_MEM_HOST, call, check, fill_levels, lib, pad, ptr
+from .fuse import outputs, pack_lists
 from .mappoint import pack_observations
 
 # MSL_LFUSE_*: the exit of the loop body a candidate took
@@ -29,10 +29,7 @@ def line_fuse_params(fx, fy, cx, cy, min_x, max_x, min_y, max_y, scale_factors, 
     p = np.zeros(1, LINE_FUSE_PARAMS_DTYPE)
     p["fx"], p["fy"], p["cx"], p["cy"] = fx, fy, cx, cy
     p["minX"], p["maxX"], p["minY"], p["maxY"], p["th"] = min_x, max_x, min_y, max_y, th
-    n = len(scale_factors)
-    p["nlevels"] = n
-    if n <= 16:                                                        # a longer table is the library's to refuse
-        p["scale_factors"][0, :n] = scale_factors
+    fill_levels(p, scale_factors=scale_factors)
     p["log_scale_factor"], p["th_low"] = log_scale_factor, th_low
     return p
 
@@ -58,13 +55,6 @@ def pack_lines(lines):
         if lines.get(k) is not None:
             out["ln_" + k][:len(lines[k])] = lines[k]
     return n, out
-
-
-def outputs(n_items, lcap, zeros=np.zeros):
-    """The output arrays of one msl_fuse_map_lines call, in msl.h's order (zeros(shape, dtype) allocates)."""
-    F, L = n_items, lcap
-    return dict(best_idx=zeros((F, L), np.int32), best_dist=zeros((F, L), np.int32), status=zeros((F, L), np.uint8), other=zeros((F, L), np.int32),
-                n_fused=zeros((F,), np.int32))
 
 
 def refresh_outputs(n_items, zeros=np.zeros):

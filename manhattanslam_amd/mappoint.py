@@ -4,7 +4,7 @@ ComputeDistinctiveDescriptors (reference src/MapPoint.cc:210-270) and MapPoint::
 ordering of KeyFrame::UpdateConnections (src/KeyFrame.cc:230-299) for a batch of keyframes (covisibility), and the device-memory forms."""
 import numpy as np
 
-from ._lib import KEYPOINT_DTYPE, MSL_MEM_DEVICE, MSL_MEM_HOST, REFRESH_PARAMS_DTYPE, call, check, lib, pad, ptr
+from ._lib import KEYPOINT_DTYPE, MSL_MEM_DEVICE, MSL_MEM_HOST, REFRESH_PARAMS_DTYPE, call, check, fill_levels, lib, pad, ptr
 
 REFRESH_DESC, REFRESH_NORMAL = 1, 2                                  # `what`
 DESC_WRITTEN, NORMAL_WRITTEN, BAD, NO_OBS, NO_LIVE_KF, TOO_MANY, BAD_OCTAVE = 1, 2, 4, 8, 16, 32, 64   # MSL_REFRESH_* status bits
@@ -21,10 +21,7 @@ COVIS_KEYS = ("weight", "conn", "conn_w", "n_conn")
 def refresh_params(scale_factors):
     """msl_refresh_params from mvScaleFactors."""
     p = np.zeros(1, REFRESH_PARAMS_DTYPE)
-    n = len(scale_factors)
-    p["nlevels"] = n
-    if n <= 16:                                                      # a longer table is the library's to refuse
-        p["scale_factors"][0, :n] = scale_factors
+    fill_levels(p, scale_factors=scale_factors)
     return p
 
 

@@ -3,7 +3,7 @@
 (triangulate_new_points), the device-memory form (triangulate_new_points_device) and the per-pair stage of the last call (debug_triangulate)."""
 import numpy as np
 
-from ._lib import KEYPOINT_DTYPE, MSL_MEM_DEVICE, MSL_MEM_HOST, TRIANGULATE_PARAMS_DTYPE, call, check, lib, pad, ptr
+from ._lib import KEYPOINT_DTYPE, MSL_MEM_DEVICE, MSL_MEM_HOST, TRIANGULATE_PARAMS_DTYPE, call, check, fill_levels, lib, pad, ptr
 
 # MSL_TRI_*: what became of a pair (idx1, match12)
 (NO_MATCH, TRIANGULATED, STEREO1, STEREO2, NEIGHBOUR_SKIPPED, LOW_PARALLAX, W_ZERO, Z1, Z2, REPROJ1, REPROJ2, ZERO_DIST, SCALE) = range(13)
@@ -22,11 +22,7 @@ def triangulate_params(fx, fy, cx, cy, bf, scale_factors, level_sigma2, scale_fa
     p["invfx"] = f(1.0) / f(fx) if invfx is None else invfx
     p["invfy"] = f(1.0) / f(fy) if invfy is None else invfy
     p["b"] = f(bf) / f(fx) if b is None else b
-    n = len(scale_factors)
-    p["nlevels"] = n
-    if n <= 16:                                                   # a longer table is the library's to refuse
-        p["scale_factors"][0, :n] = scale_factors
-        p["level_sigma2"][0, :n] = level_sigma2
+    fill_levels(p, scale_factors=scale_factors, level_sigma2=level_sigma2)
     p["scale_factor"], p["check_orientation"], p["only_stereo"] = scale_factor, int(check_orientation), int(only_stereo)
     return p
 

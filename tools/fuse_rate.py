@@ -6,16 +6,15 @@ Clock: HIP events on the handle's stream around one call; the median of five cal
 process of its own under a time limit, and the steps stop at the first that fails.  Prints one JSON line per step.
 Kernel times: `rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- python tools/fuse_rate.py --inline` (a run of its own, all
 steps in one process; tracing slows the host, so the JSON lines of that run are not the rate)."""
-import argparse
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools.rate_common import main, time_calls, to_device as dev, zeros  # noqa: E402
 STEPS = ("targets", "candidates", "current")
 FX = FY = 517.3; CX, CY, BF, W, H = 318.6, 255.3, 40.0, 640.0, 480.0
 
@@ -74,15 +73,12 @@ def run_step(step, a):
     for i in range(1, 8):
         sf[i] = sf[i - 1] * np.float32(1.2)
     prm = fuse.fuse_params(FX, FY, CX, CY, BF, 0.0, W, 0.0, H, sf, np.float32(1.0) / (sf * sf), np.float32(np.log(1.2)))
-    dev = lambda v: torch.from_numpy(np.ascontiguousarray(v.view(np.uint8).reshape(v.shape + (v.dtype.itemsize,)) if v.dtype.names else v)).cuda()
     cap, t = fuse.pack_table(table)
     n_pts, p = fuse.pack_points(points)
     d_t = {k: dev(v) for k, v in t.items()}; d_p = {k: dev(v) for k, v in p.items()}
     m = match.Matcher()
     s = torch.cuda.Stream()
     m.set_stream(s.cuda_stream)
-    tdt = {np.dtype(np.int32): torch.int32, np.dtype(np.uint8): torch.uint8}
-    zeros = lambda shape, dt: torch.zeros(shape, dtype=tdt[np.dtype(dt)], device="cuda")
     T = a.targets
     targets = dev(np.arange(1, T + 1, dtype=np.int32)[None]); n_targets = dev(np.array([T], np.int32))
     cand = zeros((1, a.candidates), np.int32); n_cand = zeros((1,), np.int32)
@@ -115,17 +111,7 @@ def run_step(step, a):
         out = fuse.outputs(1, a.candidates, zeros=zeros)
         call = lambda: fuse.fuse_map_points_device(m, prm, T + 1, cap, n_pts, 1, 1, a.candidates, d_t, d_p, tgt, lst, cand, n_cand, out)
         shape = dict(items=1, candidates_per_item=int(n_cand.cpu()[0]), candidates_from_targets=from_targets)
-    times = []
-    with torch.cuda.stream(s):
-        call()                                                                 # warm-up: the scratch grows here
-        s.synchronize()
-        for _ in range(5):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(s); call(); e1.record(s)
-            e1.synchronize()
-            times.append(e0.elapsed_time(e1) * 1e3)
-    line = dict(tool="fuse_rate", step=step, n_kps=a.n_kps, **shape, us_per_call=round(float(np.median(times)), 2), us_calls=[round(x, 2) for x in times],
-                clock="HIP events on the handle's stream around one call, median of 5 after a warm-up call")
+    line = dict(tool="fuse_rate", step=step, n_kps=a.n_kps, **shape, **time_calls(s, call))
     if out is not None:
         st = out["status"].cpu().numpy()
         line["n_fused"] = int(out["n_fused"].sum())
@@ -136,28 +122,5 @@ def run_step(step, a):
     m.close()
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--n-kps", type=int, default=1000)
-    ap.add_argument("--targets", type=int, default=40)
-    ap.add_argument("--list", type=int, default=600)
-    ap.add_argument("--candidates", type=int, default=25000)
-    ap.add_argument("--step", choices=STEPS)
-    ap.add_argument("--inline", action="store_true", help="all steps in this process (for a profiler)")
-    ap.add_argument("--step-timeout", type=float, default=120.0)
-    a = ap.parse_args()
-    if a.step:
-        return run_step(a.step, a)
-    if a.inline:
-        for step in STEPS:
-            run_step(step, a)
-        return
-    for step in STEPS:                                                         # a fresh child per step; nothing more after a failure
-        rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--step", step, "--n-kps", str(a.n_kps), "--targets", str(a.targets), "--list",
-                             str(a.list), "--candidates", str(a.candidates)], timeout=a.step_timeout).returncode
-        if rc != 0:
-            sys.exit("step %s ended with %d" % (step, rc))
-
-
 if __name__ == "__main__":
-    main()
+    main(__file__, STEPS, run_step, (("n-kps", 1000), ("targets", 40), ("list", 600), ("candidates", 25000)))

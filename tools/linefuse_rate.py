@@ -6,16 +6,15 @@ Clock: HIP events on the handle's stream around one call; the median of five cal
 process of its own under a time limit, and the steps stop at the first that fails.  Prints one JSON line per step.
 Kernel times: `rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- python tools/linefuse_rate.py --inline` (a run of its own,
 all steps in one process; tracing slows the host, so the JSON lines of that run are not the rate)."""
-import argparse
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools.rate_common import main, time_calls, to_device as dev, zeros  # noqa: E402
 STEPS = ("targets", "current", "refresh")
 FX = FY = 517.3; CX, CY, W, H = 318.6, 255.3, 640.0, 480.0
 
@@ -73,9 +72,6 @@ def run_step(step, a):
     for i in range(1, 8):
         sf[i] = sf[i - 1] * np.float32(1.2)
     prm = linefuse.line_fuse_params(FX, FY, CX, CY, 0.0, W, 0.0, H, sf, np.float32(np.log(1.2)))
-    dev = lambda v: torch.from_numpy(np.ascontiguousarray(v.view(np.uint8).reshape(v.shape + (v.dtype.itemsize,)) if v.dtype.names else v)).cuda()
-    tdt = {np.dtype(np.int32): torch.int32, np.dtype(np.uint8): torch.uint8, np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64}
-    zeros = lambda shape, dt: torch.zeros(shape, dtype=tdt[np.dtype(dt)], device="cuda")
     m = match.Matcher()
     s = torch.cuda.Stream()
     m.set_stream(s.cuda_stream)
@@ -114,17 +110,7 @@ def run_step(step, a):
         rp = mappoint.refresh_params(sf)
         call = lambda: linefuse.refresh_map_lines_device(m, rp, 8, klcap, n_lines, a.refresh, int(o["obs_off"][-1]), d_t, d_o, d_p, ids, res, d_p)
         shape = dict(lines=a.refresh, observations_per_line=8)
-    times = []
-    with torch.cuda.stream(s):
-        call()                                                                 # warm-up: the scratch grows here
-        s.synchronize()
-        for _ in range(5):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(s); call(); e1.record(s)
-            e1.synchronize()
-            times.append(e0.elapsed_time(e1) * 1e3)
-    line = dict(tool="linefuse_rate", step=step, **shape, us_per_call=round(float(np.median(times)), 2), us_calls=[round(x, 2) for x in times],
-                clock="HIP events on the handle's stream around one call, median of 5 after a warm-up call")
+    line = dict(tool="linefuse_rate", step=step, **shape, **time_calls(s, call))
     if out is not None:
         line["n_fused"] = int(out["n_fused"].sum())
         line["status_counts"] = np.bincount(out["status"].cpu().numpy().reshape(-1), minlength=15).tolist()
@@ -134,28 +120,5 @@ def run_step(step, a):
     m.close()
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--n-kl", type=int, default=40)
-    ap.add_argument("--targets", type=int, default=40)
-    ap.add_argument("--candidates", type=int, default=25000)
-    ap.add_argument("--refresh", type=int, default=1000)
-    ap.add_argument("--step", choices=STEPS)
-    ap.add_argument("--inline", action="store_true", help="all steps in this process (for a profiler)")
-    ap.add_argument("--step-timeout", type=float, default=120.0)
-    a = ap.parse_args()
-    if a.step:
-        return run_step(a.step, a)
-    if a.inline:
-        for step in STEPS:
-            run_step(step, a)
-        return
-    for step in STEPS:                                                         # a fresh child per step; nothing more after a failure
-        rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--step", step, "--n-kl", str(a.n_kl), "--targets", str(a.targets),
-                             "--candidates", str(a.candidates), "--refresh", str(a.refresh)], timeout=a.step_timeout).returncode
-        if rc != 0:
-            sys.exit("step %s ended with %d" % (step, rc))
-
-
 if __name__ == "__main__":
-    main()
+    main(__file__, STEPS, run_step, (("n-kl", 40), ("targets", 40), ("candidates", 25000), ("refresh", 1000)))

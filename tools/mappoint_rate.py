@@ -6,16 +6,15 @@ Clock: HIP events on the handle's stream around one call; the median of five cal
 process of its own under a time limit, and the steps stop at the first that fails.  Prints one JSON line per step.
 Kernel times: `rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- python tools/mappoint_rate.py --inline` (a run of its own,
 all steps in one process; tracing slows the host, so the JSON lines of that run are not the rate)."""
-import argparse
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools.rate_common import main, time_calls, to_device as dev, zeros  # noqa: E402
 STEPS = ("refresh_1", "covisibility_1", "refresh_32", "covisibility_32")
 
 
@@ -56,13 +55,11 @@ def run_step(step, a):
     kind, n_kf = step.rsplit("_", 1)
     n_kf = int(n_kf)
     table, obs, points, n_obs = workload(a.n_tab, a.n_kps, 32, a.max_obs)
-    dev = lambda v: torch.from_numpy(np.ascontiguousarray(v.view(np.uint8).reshape(v.shape + (v.dtype.itemsize,)) if v.dtype.names else v)).cuda()
     d_t = {k: dev(v) for k, v in table.items()}; d_o = {k: dev(v) for k, v in obs.items()}; d_p = {k: dev(v) for k, v in points.items()}
     n_pts, total = len(points["pt_flags"]), int(obs["obs_off"][-1])
     m = match.Matcher()
     s = torch.cuda.Stream()
     m.set_stream(s.cuda_stream)
-    zeros = lambda shape, dt: torch.zeros(shape, dtype=getattr(torch, np.dtype(dt).name), device="cuda")
     sf = np.ones(8, np.float32)
     for i in range(1, 8):
         sf[i] = sf[i - 1] * np.float32(1.2)
@@ -81,17 +78,7 @@ def run_step(step, a):
         call = lambda: mappoint.covisibility_device(m, a.n_tab, a.n_kps, n_pts, n_kf, total, a.n_tab, 15, d_t["held_id"], d_t["n_kps"], d_p["pt_flags"],
                                                     d_o["obs_off"], d_o["obs_kf"], kf, out)
         shape = dict(items=n_kf, observations_walked=int(n_obs[:n_kf * a.n_kps].sum()))
-    times = []
-    with torch.cuda.stream(s):
-        call()                                                                 # warm-up
-        s.synchronize()
-        for _ in range(5):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(s); call(); e1.record(s)
-            e1.synchronize()
-            times.append(e0.elapsed_time(e1) * 1e3)
-    line = dict(tool="mappoint_rate", step=step, n_tab=a.n_tab, n_kps=a.n_kps, **shape, us_per_call=round(float(np.median(times)), 2),
-                us_calls=[round(x, 2) for x in times], clock="HIP events on the handle's stream around one call, median of 5 after a warm-up call")
+    line = dict(tool="mappoint_rate", step=step, n_tab=a.n_tab, n_kps=a.n_kps, **shape, **time_calls(s, call))
     if kind == "refresh":
         line["status_counts"] = np.bincount(out["status"].cpu().numpy(), minlength=4).tolist()
     else:
@@ -100,27 +87,5 @@ def run_step(step, a):
     m.close()
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--n-tab", type=int, default=100)
-    ap.add_argument("--n-kps", type=int, default=1000)
-    ap.add_argument("--max-obs", type=int, default=30)
-    ap.add_argument("--step", choices=STEPS)
-    ap.add_argument("--inline", action="store_true", help="all steps in this process (for a profiler)")
-    ap.add_argument("--step-timeout", type=float, default=120.0)
-    a = ap.parse_args()
-    if a.step:
-        return run_step(a.step, a)
-    if a.inline:
-        for step in STEPS:
-            run_step(step, a)
-        return
-    for step in STEPS:                                                         # a fresh child per step; nothing more after a failure
-        rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--step", step, "--n-tab", str(a.n_tab), "--n-kps", str(a.n_kps), "--max-obs",
-                             str(a.max_obs)], timeout=a.step_timeout).returncode
-        if rc != 0:
-            sys.exit("step %s ended with %d" % (step, rc))
-
-
 if __name__ == "__main__":
-    main()
+    main(__file__, STEPS, run_step, (("n-tab", 100), ("n-kps", 1000), ("max-obs", 30)))

@@ -14,6 +14,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools.rate_common import to_device  # noqa: E402
 
 
 def workload(n_kf, n_kps, n_nodes, seed=1):
@@ -48,7 +49,7 @@ def main():
     mp = ts.prm()
     prm = triangulate.triangulate_params(ts.FX, ts.FY, ts.CX, ts.CY, ts.BF, mp["scale_factors"], mp["level_sigma2"], 1.2)
     cap, t = triangulate.pack_table(table)
-    d_t = {k: torch.from_numpy(np.ascontiguousarray(v.view(np.uint8).reshape(v.shape + (28,)) if v.dtype.names else v)).cuda() for k, v in t.items()}
+    d_t = {k: to_device(v) for k, v in t.items()}
     m = match.Matcher()
     tdt = {np.dtype(np.int32): torch.int32, np.dtype(np.uint8): torch.uint8, np.dtype(np.float32): torch.float32}
     for F in (int(x) for x in a.items.split(",")):
