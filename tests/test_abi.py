@@ -10,15 +10,9 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _declared(header="msl.h"):
-    src = open(os.path.join(ROOT, "include", header)).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"MSL_API[^;(]*?\b(msl_\w+)\s*\(", src)))
-
-
 def test_every_declared_symbol_is_exported_and_bound():
-    from manhattanslam_amd import _lib
-    api, dbg = _declared("msl.h"), _declared("msl_debug.h")
+    from manhattanslam_amd import _header, _lib
+    api, dbg = (sorted(_header.declarations(_header.text(h))) for h in ("msl.h", "msl_debug.h"))
     assert len(api) >= 40 and len(dbg) >= 14
     # the drop-in header carries no debug / profiling / scratch-peek entry points, the debug header nothing else
     assert not [n for n in api if "debug" in n or "profile" in n or "kernel_name" in n], api
@@ -28,6 +22,54 @@ def test_every_declared_symbol_is_exported_and_bound():
     for n in names:
         assert hasattr(dll, n), f"{n} declared in include/ but not exported by libmsl.so"
     assert sorted(_lib.SIGNATURES) == names, set(names) ^ set(_lib.SIGNATURES)
+
+
+# What a ctypes type of the binding stands for, as a C++17 predicate on the type T the compiler sees in the header.
+CLASSES = {C.c_void_p: "std::is_pointer_v<T> && !is_char_p<T>", C.c_char_p: "is_char_p<T>",
+           C.c_int: "sizeof(T) == 4 && (std::is_enum_v<T> || (std::is_integral_v<T> && std::is_signed_v<T>))",
+           C.c_uint: "std::is_same_v<T, unsigned>", C.c_size_t: "std::is_same_v<T, size_t>", C.c_float: "std::is_same_v<T, float>",
+           C.c_double: "std::is_same_v<T, double>", C.c_longlong: "std::is_same_v<T, long long>", None: "std::is_void_v<T>"}
+
+
+def binding_check_source(signatures, records, constants):
+    """One C++17 translation unit whose static_asserts hold iff the binding (SIGNATURES, RECORDS, the constants) says what the two headers say."""
+    kinds = list(CLASSES)
+    out = ['#include <cstddef>\n#include <type_traits>\n#include "msl.h"\n#include "msl_debug.h"\n'
+           "template <class T> constexpr bool is_char_p = std::is_pointer_v<T> && std::is_same_v<std::remove_cv_t<std::remove_pointer_t<T>>, char>;\n"
+           "template <int K, class T> constexpr bool is() {\n"]
+    out += [f"    if constexpr (K == {k}) return {pred};\n" for k, pred in enumerate(CLASSES.values())]
+    out += ["    return false;\n}\n"
+            "template <int KR, int... K> struct as {      /* return class first, then one class per parameter */\n"
+            "    template <class R, class... A> static constexpr bool count(R (*)(A...) noexcept) { return sizeof...(A) == sizeof...(K); }\n"
+            "    template <class R, class... A> static constexpr bool types(R (*)(A...) noexcept) {\n"
+            "        if constexpr (sizeof...(A) == sizeof...(K)) return is<KR, R>() && (is<K, A>() && ...); else return false; }\n"
+            "};\n"]
+    for name, (res, args) in signatures.items():
+        ks = ", ".join(str(kinds.index(t)) for t in [res] + list(args))
+        out.append(f'static_assert(as<{ks}>::count(&{name}), "{name}: parameter count");\n'
+                   f'static_assert(as<{ks}>::types(&{name}), "{name}: a parameter or the return value is of another class");\n')
+    for name, d in records.items():
+        out.append(f'static_assert(sizeof({name}) == {d.itemsize}, "{name}: size");\n')
+        for field, path in zip(d.names, d.metadata["paths"]):
+            sub, off = d.fields[field][:2]
+            out.append(f'static_assert(offsetof({name}, {path}) == {off} && sizeof((({name} *)0)->{path}) == {sub.itemsize}, "{name}.{path}");\n')
+    out += [f'static_assert({k} == {v}, "{k}");\n' for k, v in constants.items()]
+    return "".join(out)
+
+
+def test_binding_agrees_with_the_compiler(tmp_path):
+    """Every function of SIGNATURES, every record and the constants of _lib against what g++ reads in include/msl.h and include/msl_debug.h:
+    parameter count and class of every parameter and return value, sizeof, offsetof and size of every (flattened) field."""
+    import subprocess
+    from manhattanslam_amd import _lib
+    assert len(_lib.SIGNATURES) >= 133 and len(_lib.RECORDS) >= 24
+    cpp = tmp_path / "binding_check.cpp"
+    cpp.write_text(binding_check_source(_lib.SIGNATURES, _lib.RECORDS, dict(
+        MSL_MEM_HOST=_lib.MSL_MEM_HOST, MSL_MEM_DEVICE=_lib.MSL_MEM_DEVICE, MSL_ORB_NKERNELS=_lib.MSL_ORB_NKERNELS,
+        MSL_SF_NKERNELS=_lib.MSL_SF_NKERNELS, MSL_MATCH_MAX_LEVELS=16)))
+    assert (_lib.MSL_MEM_HOST, _lib.MSL_MEM_DEVICE) == (0, 1)
+    r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(cpp)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]
 
 
 def test_struct_layouts_match_reference_types():
@@ -85,13 +127,13 @@ def test_no_exception_crosses_the_c_boundary(tmp_path):
     (3) failures raised INSIDE the library -- std::bad_alloc, another std::exception, a non-standard one, std::bad_alloc in a worker thread of the
     plane extractor's pool -- come back as MSL_ERR_NOMEM / MSL_ERR_INTERNAL with a message; the process lives on."""
     import subprocess
-    from manhattanslam_amd import _lib
+    from manhattanslam_amd import _header, _lib
     names = []
     for hname in ("msl.h", "msl_debug.h"):
-        src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", hname)).read(), flags=re.S)
+        src = _header.text(hname)
         decls = re.findall(r"^MSL_API[^;]*;", src, flags=re.M)
         assert decls and all(d.rstrip(";").rstrip().endswith("MSL_NOEXCEPT") for d in decls), [d for d in decls if "MSL_NOEXCEPT" not in d]
-        names += re.findall(r"MSL_API[^;(]*?\b(msl_\w+)\s*\(", src)
+        names += list(_header.declarations(src))
     cpp = tmp_path / "noexcept_check.cpp"
     cpp.write_text('#include "msl.h"\n#include "msl_debug.h"\n'
                    "template <class R, class... A> constexpr bool ne(R (*)(A...) noexcept) { return true; }\n"

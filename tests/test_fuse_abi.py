@@ -13,58 +13,44 @@ CODES = ("NULL", "BAD", "IN_KEYFRAME", "BEHIND", "OUT_OF_IMAGE", "DISTANCE", "VI
          "REPLACED_BY_HELD", "REPLACES_HELD", "HELD_BAD", "UNRESOLVED")
 
 
-def _header(name="msl.h"):
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", name)).read(), flags=re.S)
-
-
-def _args(src, n):
-    return [a.strip() for a in re.search(r"\b" + n + r"\s*\((.*?)\)\s*MSL_NOEXCEPT", src, flags=re.S).group(1).split(",")]
-
-
-def _argtypes(src, n):
-    """The ctypes argument types the header's declaration of n asks for."""
-    return [C.c_void_p if "*" in a else (C.c_size_t if re.match(r"size_t\b", a) else C.c_int) for a in _args(src, n)]
-
-
 def test_exported_declared_and_bound():
-    from manhattanslam_amd import _lib
+    from manhattanslam_amd import _header, _lib
     dll = C.CDLL(_lib.LIB_PATH)
-    src = _header()
+    src = _header.text("msl.h")
+    decl, dbg = _header.declarations(src), _header.declarations(_header.text("msl_debug.h"))
     for n, count in NAMES.items():
-        assert re.search(r"MSL_API\s+int\s+" + n + r"\s*\(", src), n
+        assert decl[n][0] == "int", n
         assert hasattr(dll, n), n
         res, args = _lib.SIGNATURES[n]
-        assert res is C.c_int and args == _argtypes(src, n) and len(args) == count, n
+        assert res is C.c_int and len(args) == len(decl[n][1]) == count, n        # the types: test_abi.py, against the compiler
         assert getattr(_lib.lib, n).argtypes == args
     n = "msl_debug_fuse"
-    assert hasattr(dll, n) and _lib.SIGNATURES[n][1] == _argtypes(_header("msl_debug.h"), n) and len(_lib.SIGNATURES[n][1]) == 4
+    assert hasattr(dll, n) and len(_lib.SIGNATURES[n][1]) == len(dbg[n][1]) == 4
     assert "fuse" not in " ".join(re.findall(r"msl_\w*debug\w*", src))                 # the accessor is not part of the drop-in header
 
 
 def test_argument_order_of_the_two_forms():
-    from manhattanslam_amd import fuse
-    src = _header()
-    a, b = _args(src, "msl_fuse_map_points"), _args(src, "msl_fuse_map_points_batch")
-    assert a[0] == "msl_match *h" and b[0] == "int device" and a[1:] == b[1:]
-    names = [re.search(r"(\w+)$", x).group(1) for x in a]
+    from manhattanslam_amd import _header, fuse
+    decl = _header.declarations(_header.text("msl.h"))
+    a, b = decl["msl_fuse_map_points"][1], decl["msl_fuse_map_points_batch"][1]
+    assert a[0] == ("msl_match *", "h") and b[0] == ("int", "device") and a[1:] == b[1:]
+    names = [x[1] for x in a]
     assert names[1:8] == ["n_tab", "cap", "n_pts", "n_items", "n_lists", "lcap", "params"]
     assert tuple(names[8:15]) == fuse.TABLE_KEYS and tuple(names[15:21]) == fuse.POINT_KEYS
     assert names[21:26] == ["tgt", "list", "cand", "n_cand", "mem"] and tuple(names[26:31]) == fuse.OUT_KEYS and names[31] == "out_mem"
-    assert a[8].startswith("const msl_keypoint *") and a[28].startswith("uint8_t *") and a[26].startswith("int32_t *")
-    a, b = _args(src, "msl_fuse_candidates"), _args(src, "msl_fuse_candidates_batch")
-    assert a[0] == "msl_match *h" and b[0] == "int device" and a[1:] == b[1:]
-    names = [re.search(r"(\w+)$", x).group(1) for x in a]
+    assert a[8][0] == "const msl_keypoint *" and a[28][0] == "uint8_t *" and a[26][0] == "int32_t *"
+    a, b = decl["msl_fuse_candidates"][1], decl["msl_fuse_candidates_batch"][1]
+    assert a[0] == ("msl_match *", "h") and b[0] == ("int", "device") and a[1:] == b[1:]
+    names = [x[1] for x in a]
     assert names[1:] == ["n_tab", "cap", "n_pts", "n_items", "tcap", "lcap", "held_id", "n_kps", "pt_flags", "targets", "n_targets", "mem", "cand",
                          "n_cand", "out_mem"]
 
 
 def test_params_record_and_status_codes():
-    from manhattanslam_amd import _lib, fuse
+    from manhattanslam_amd import _header, _lib, fuse
     d = _lib.FUSE_PARAMS_DTYPE
-    src = _header()
-    body = re.search(r"typedef struct msl_fuse_params \{(.*?)\} msl_fuse_params;", src, flags=re.S).group(1)
-    names = [n for decl in re.findall(r"[\w\s]+?([\w\s,\[\]]+);", body) for n in re.findall(r"(\w+)(?:\[\w+\])?\s*(?:,|$)", decl.strip())]
-    assert tuple(names) == d.names, (names, d.names)
+    src = _header.text("msl.h")
+    assert _header.records(src)["msl_fuse_params"].names == d.names
     off = {n: d.fields[n][1] for n in d.names}
     assert off == dict(fx=0, fy=4, cx=8, cy=12, bf=16, minX=20, maxX=24, minY=28, maxY=32, th=36, nlevels=40, scale_factors=44, inv_level_sigma2=108,
                        log_scale_factor=172, th_low=176) and d.itemsize == 180

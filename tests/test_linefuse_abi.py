@@ -13,61 +13,47 @@ CODES = ("NULL", "BAD", "BEHIND", "OUT_OF_IMAGE", "DISTANCE", "VIEW_ANGLE", "NO_
          "REPLACES_HELD", "HELD_BAD", "UNRESOLVED", "SELF")
 
 
-def _header(name="msl.h"):
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", name)).read(), flags=re.S)
-
-
-def _args(src, n):
-    return [a.strip() for a in re.search(r"\b" + n + r"\s*\((.*?)\)\s*MSL_NOEXCEPT", src, flags=re.S).group(1).split(",")]
-
-
-def _argtypes(src, n):
-    """The ctypes argument types the header's declaration of n asks for."""
-    return [C.c_void_p if "*" in a else (C.c_size_t if re.match(r"size_t\b", a) else C.c_int) for a in _args(src, n)]
-
-
 def test_exported_declared_and_bound():
-    from manhattanslam_amd import _lib
+    from manhattanslam_amd import _header, _lib
     dll = C.CDLL(_lib.LIB_PATH)
-    src = _header()
+    src = _header.text("msl.h")
+    decl, dbg = _header.declarations(src), _header.declarations(_header.text("msl_debug.h"))
     for n, count in NAMES.items():
-        assert re.search(r"MSL_API\s+int\s+" + n + r"\s*\(", src), n
+        assert decl[n][0] == "int", n
         assert hasattr(dll, n), n
         res, args = _lib.SIGNATURES[n]
-        assert res is C.c_int and args == _argtypes(src, n) and len(args) == count, n
+        assert res is C.c_int and len(args) == len(decl[n][1]) == count, n        # the types: test_abi.py, against the compiler
         assert getattr(_lib.lib, n).argtypes == args
     n = "msl_debug_line_fuse"
-    assert hasattr(dll, n) and _lib.SIGNATURES[n][1] == _argtypes(_header("msl_debug.h"), n) and len(_lib.SIGNATURES[n][1]) == 4
+    assert hasattr(dll, n) and len(_lib.SIGNATURES[n][1]) == len(dbg[n][1]) == 4
     assert not re.findall(r"msl_\w*debug\w*", src)                                   # the accessor is not part of the drop-in header
 
 
 def test_argument_order_of_the_two_forms():
-    from manhattanslam_amd import linefuse
-    src = _header()
-    a, b = _args(src, "msl_fuse_map_lines"), _args(src, "msl_fuse_map_lines_batch")
-    assert a[0] == "msl_match *h" and b[0] == "int device" and a[1:] == b[1:]
-    names = [re.search(r"(\w+)$", x).group(1) for x in a]
+    from manhattanslam_amd import _header, linefuse
+    decl = _header.declarations(_header.text("msl.h"))
+    a, b = decl["msl_fuse_map_lines"][1], decl["msl_fuse_map_lines_batch"][1]
+    assert a[0] == ("msl_match *", "h") and b[0] == ("int", "device") and a[1:] == b[1:]
+    names = [x[1] for x in a]
     assert names[1:8] == ["n_tab", "klcap", "n_lines", "n_items", "n_lists", "lcap", "params"]
     assert tuple(names[8:13]) == linefuse.TABLE_KEYS and tuple(names[13:19]) == linefuse.LINE_KEYS
     assert names[19:24] == ["tgt", "list", "cand", "n_cand", "mem"] and tuple(names[24:29]) == linefuse.OUT_KEYS and names[29] == "out_mem"
-    assert a[8].startswith("const msl_keyline *") and a[13].startswith("const double *") and a[26].startswith("uint8_t *")
-    a, b = _args(src, "msl_refresh_map_lines"), _args(src, "msl_refresh_map_lines_batch")
-    assert a[0] == "msl_match *h" and b[0] == "int device" and a[1:] == b[1:]
-    names = [re.search(r"(\w+)$", x).group(1) for x in a]
+    assert a[8][0] == "const msl_keyline *" and a[13][0] == "const double *" and a[26][0] == "uint8_t *"
+    a, b = decl["msl_refresh_map_lines"][1], decl["msl_refresh_map_lines_batch"][1]
+    assert a[0] == ("msl_match *", "h") and b[0] == ("int", "device") and a[1:] == b[1:]
+    names = [x[1] for x in a]
     assert names[1:7] == ["n_tab", "klcap", "n_lines", "n_items", "n_obs_total", "params"]
     assert tuple(names[7:10]) == linefuse.REFRESH_TABLE_KEYS and tuple(names[10:13]) == linefuse.OBS_KEYS
     assert tuple(names[13:16]) == linefuse.REFRESH_LINE_KEYS and names[16:18] == ["ids", "mem"]
     assert tuple(names[18:21]) == linefuse.REFRESH_OUT_KEYS and tuple(names[21:23]) == linefuse.ROW_KEYS and names[23] == "out_mem"
-    assert a[18].startswith("double *") and a[21].startswith("double *") and a[6].startswith("const msl_refresh_params *")
+    assert a[18][0] == "double *" and a[21][0] == "double *" and a[6][0] == "const msl_refresh_params *"
 
 
 def test_params_record_and_status_codes():
-    from manhattanslam_amd import _lib, linefuse
+    from manhattanslam_amd import _header, _lib, linefuse
     d = _lib.LINE_FUSE_PARAMS_DTYPE
-    src = _header()
-    body = re.search(r"typedef struct msl_line_fuse_params \{(.*?)\} msl_line_fuse_params;", src, flags=re.S).group(1)
-    names = [n for decl in re.findall(r"[\w\s]+?([\w\s,\[\]]+);", body) for n in re.findall(r"(\w+)(?:\[\w+\])?\s*(?:,|$)", decl.strip())]
-    assert tuple(names) == d.names, (names, d.names)
+    src = _header.text("msl.h")
+    assert _header.records(src)["msl_line_fuse_params"].names == d.names
     off = {n: d.fields[n][1] for n in d.names}
     assert off == dict(fx=0, fy=4, cx=8, cy=12, minX=16, maxX=20, minY=24, maxY=28, th=32, nlevels=36, scale_factors=40, log_scale_factor=104,
                        th_low=108) and d.itemsize == 112

@@ -11,58 +11,44 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = {"msl_refresh_map_points": 31, "msl_refresh_map_points_batch": 31, "msl_covisibility": 20, "msl_covisibility_batch": 20}
 
 
-def _header(name="msl.h"):
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", name)).read(), flags=re.S)
-
-
-def _args(src, n):
-    return [a.strip() for a in re.search(r"\b" + n + r"\s*\((.*?)\)\s*MSL_NOEXCEPT", src, flags=re.S).group(1).split(",")]
-
-
-def _argtypes(src, n):
-    """The ctypes argument types the header's declaration of n asks for."""
-    return [C.c_void_p if "*" in a else (C.c_size_t if re.match(r"size_t\b", a) else C.c_int) for a in _args(src, n)]
-
-
 def test_exported_declared_and_bound():
-    from manhattanslam_amd import _lib
+    from manhattanslam_amd import _header, _lib
     dll = C.CDLL(_lib.LIB_PATH)
-    src = _header()
+    src = _header.text("msl.h")
+    decl = _header.declarations(src)
     for n, count in NAMES.items():
-        assert re.search(r"MSL_API\s+int\s+" + n + r"\s*\(", src), n
+        assert decl[n][0] == "int", n
         assert hasattr(dll, n), n
         res, args = _lib.SIGNATURES[n]
-        assert res is C.c_int and args == _argtypes(src, n) and len(args) == count, n
+        assert res is C.c_int and len(args) == len(decl[n][1]) == count, n        # the types: test_abi.py, against the compiler
         assert getattr(_lib.lib, n).argtypes == args
 
 
 def test_argument_order_of_the_two_forms():
-    from manhattanslam_amd import mappoint
-    src = _header()
-    a, b = _args(src, "msl_refresh_map_points"), _args(src, "msl_refresh_map_points_batch")
-    assert a[0] == "msl_match *h" and b[0] == "int device" and a[1:] == b[1:]
-    names = [re.search(r"(\w+)$", x).group(1) for x in a]
+    from manhattanslam_amd import _header, mappoint
+    decl = _header.declarations(_header.text("msl.h"))
+    a, b = decl["msl_refresh_map_points"][1], decl["msl_refresh_map_points_batch"][1]
+    assert a[0] == ("msl_match *", "h") and b[0] == ("int", "device") and a[1:] == b[1:]
+    names = [x[1] for x in a]
     assert names[1:8] == ["n_tab", "cap", "n_pts", "n_items", "n_obs_total", "what", "params"]
     assert tuple(names[8:13]) == mappoint.TABLE_KEYS and tuple(names[13:16]) == mappoint.OBS_KEYS and tuple(names[16:19]) == mappoint.POINT_KEYS
     assert names[19:21] == ["ids", "mem"] and tuple(names[21:27]) == mappoint.OUT_KEYS and tuple(names[27:30]) == mappoint.ROW_KEYS
     assert names[30] == "out_mem"
-    assert a[8].startswith("const msl_keypoint *") and a[21].startswith("uint8_t *") and a[26].startswith("uint8_t *") and a[22].startswith("float *")
-    a, b = _args(src, "msl_covisibility"), _args(src, "msl_covisibility_batch")
-    assert a[0] == "msl_match *h" and b[0] == "int device" and a[1:] == b[1:]
-    names = [re.search(r"(\w+)$", x).group(1) for x in a]
+    assert a[8][0] == "const msl_keypoint *" and a[21][0] == "uint8_t *" and a[26][0] == "uint8_t *" and a[22][0] == "float *"
+    a, b = decl["msl_covisibility"][1], decl["msl_covisibility_batch"][1]
+    assert a[0] == ("msl_match *", "h") and b[0] == ("int", "device") and a[1:] == b[1:]
+    names = [x[1] for x in a]
     assert names[1:15] == ["n_tab", "cap", "n_pts", "n_items", "n_obs_total", "ccap", "th", "held_id", "n_kps", "pt_flags", "obs_off", "obs_kf", "kf",
                            "mem"]
     assert tuple(names[15:19]) == mappoint.COVIS_KEYS and names[19] == "out_mem"
 
 
 def test_params_record_mask_and_status_bits():
-    from manhattanslam_amd import _lib, mappoint
+    from manhattanslam_amd import _header, _lib, mappoint
     from tests import mappoint_model as mm
     d = _lib.REFRESH_PARAMS_DTYPE
-    src = _header()
-    body = re.search(r"typedef struct msl_refresh_params \{(.*?)\} msl_refresh_params;", src, flags=re.S).group(1)
-    names = [n for decl in re.findall(r"[\w\s]+?([\w\s,\[\]]+);", body) for n in re.findall(r"(\w+)(?:\[\w+\])?\s*(?:,|$)", decl.strip())]
-    assert tuple(names) == d.names == ("nlevels", "scale_factors")
+    src = _header.text("msl.h")
+    assert _header.records(src)["msl_refresh_params"].names == d.names == ("nlevels", "scale_factors")
     assert d.fields["nlevels"][1] == 0 and d.fields["scale_factors"][1] == 4 and d.itemsize == 68
     assert re.search(r"#define\s+MSL_MATCH_MAX_LEVELS\s+16\b", src) and d.fields["scale_factors"][0].shape == (16,)
     want = dict(DESC=1, NORMAL=2, DESC_WRITTEN=1, NORMAL_WRITTEN=2, BAD=4, NO_OBS=8, NO_LIVE_KF=16, TOO_MANY=32, BAD_OCTAVE=64)

@@ -1,46 +1,32 @@
 """msl_pnp_ransac is part of the C ABI: exported by libmsl.so, declared in include/msl.h (its debug accessor in include/msl_debug.h) and bound
 in _lib with matching argument types, and the params record has the header's layout.  No compute calls (no GPU needed)."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("msl_pnp_ransac", "msl_pnp_ransac_batch")
 
 
-def _header(name="msl.h"):
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", name)).read(), flags=re.S)
-
-
-def _argtypes(src, n):
-    """The ctypes argument types the header's declaration of n asks for."""
-    args = re.search(r"\b" + n + r"\s*\((.*?)\)\s*MSL_NOEXCEPT", src, flags=re.S).group(1)
-    return [C.c_void_p if "*" in a else C.c_int for a in args.split(",")]
-
-
 def test_exported_declared_and_bound():
-    from manhattanslam_amd import _lib
+    from manhattanslam_amd import _header, _lib
     dll = C.CDLL(_lib.LIB_PATH)
-    src = _header()
+    src = _header.text("msl.h")
+    decl, dbg = _header.declarations(src), _header.declarations(_header.text("msl_debug.h"))
     for n in NAMES:
-        assert re.search(r"MSL_API\s+int\s+" + n + r"\s*\(", src), n
+        assert decl[n][0] == "int", n
         assert hasattr(dll, n), n
         res, args = _lib.SIGNATURES[n]
-        assert res is C.c_int and args == _argtypes(src, n) and len(args) == 18, n
+        assert res is C.c_int and len(args) == len(decl[n][1]) == 18, n                 # the types: test_abi.py, against the compiler
         assert getattr(_lib.lib, n).argtypes == args
     n = "msl_pnp_debug_hypotheses"
-    assert hasattr(dll, n) and _lib.SIGNATURES[n][1] == _argtypes(_header("msl_debug.h"), n)
-    first = lambda n: re.search(r"\b" + n + r"\s*\(\s*([^,]*),", src).group(1).strip()
-    assert first(NAMES[0]) == "msl_match *h" and first(NAMES[1]) == "int device"
+    assert hasattr(dll, n) and len(_lib.SIGNATURES[n][1]) == len(dbg[n][1])
+    assert decl[NAMES[0]][1][0] == ("msl_match *", "h") and decl[NAMES[1]][1][0] == ("int", "device")
 
 
 def test_params_record_layout():
     from manhattanslam_amd import PNP_PARAMS_DTYPE as d
-    body = re.search(r"typedef struct msl_pnp_params \{(.*?)\} msl_pnp_params;", _header(), flags=re.S).group(1)
-    names = [n for decl in re.findall(r"[\w\s]+?([\w\s,\[\]]+);", body) for n in re.findall(r"(\w+)(?:\[\w+\])?\s*(?:,|$)", decl.strip())]
-    assert tuple(names) == d.names, (names, d.names)
+    from manhattanslam_amd import _header
+    assert _header.records(_header.text("msl.h"))["msl_pnp_params"].names == d.names
     off = {n: d.fields[n][1] for n in d.names}
     assert off == dict(fx=0, fy=4, cx=8, cy=12, nlevels=16, level_sigma2=20, probability=88, min_inliers=96, max_iterations=100, min_set=104,
                        epsilon=108, th2=112, n_iterations=116) and d.itemsize == 120

@@ -1,31 +1,24 @@
 """The keyframe-search entry points are part of the C ABI: exported by libmsl.so, declared in include/msl.h and bound in _lib, and the
 params record has the header's layout.  No compute calls (no GPU needed)."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("msl_match_keyframe_points", "msl_match_keyframe_points_batch", "msl_kfdb_add", "msl_kfdb_erase", "msl_kfdb_clear", "msl_kfdb_size",
          "msl_reloc_candidates", "msl_reloc_candidates_batch")
 COUNTS = dict(zip(NAMES, (22, 22, 7, 2, 1, 3, 16, 16)))
 
 
-def _header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "msl.h")).read(), flags=re.S)
-
-
 def test_exported_declared_and_bound():
-    from manhattanslam_amd import _lib
-    src = _header()
+    from manhattanslam_amd import _header, _lib
+    decl = _header.declarations(_header.text("msl.h"))
     dll = C.CDLL(_lib.LIB_PATH)
     for n in NAMES:
-        assert re.search(r"MSL_API\s+int\s+" + n + r"\s*\(", src), n
+        assert decl[n][0] == "int", n
         assert hasattr(dll, n), n
         assert n in _lib.SIGNATURES, n
-    assert re.search(r"MSL_API\s+msl_kfdb\s*\*\s*msl_kfdb_create\s*\(\s*int device\s*\)", src)
-    assert re.search(r"MSL_API\s+void\s+msl_kfdb_destroy\s*\(", src)
+    assert decl["msl_kfdb_create"] == ("msl_kfdb *", [("int", "device")])
+    assert decl["msl_kfdb_destroy"][0] == "void"
     for n in ("msl_kfdb_create", "msl_kfdb_destroy"):
         assert hasattr(dll, n) and n in _lib.SIGNATURES, n
 
@@ -42,11 +35,10 @@ def test_kfdb_without_a_device_fails():
 
 
 def test_argument_counts_match_the_header():
-    from manhattanslam_amd import _lib
-    src = _header()
+    from manhattanslam_amd import _header, _lib
+    decl = _header.declarations(_header.text("msl.h"))
     for n in NAMES:
-        args = re.search(r"\b" + n + r"\s*\((.*?)\)\s*MSL_NOEXCEPT", src, flags=re.S).group(1)
-        assert args.count(",") + 1 == len(_lib.SIGNATURES[n][1]) == COUNTS[n], n
+        assert len(decl[n][1]) == len(_lib.SIGNATURES[n][1]) == COUNTS[n], n
 
 
 def test_params_record_layout():
@@ -56,9 +48,8 @@ def test_params_record_layout():
     assert d.names[:len(MATCH_PARAMS_DTYPE.names)] == MATCH_PARAMS_DTYPE.names and d.names[-2:] == ("log_scale_factor", "orb_dist")
     assert d.fields["log_scale_factor"][1] == MATCH_PARAMS_DTYPE.itemsize == 112 and d.fields["orb_dist"][1] == 116 and d.itemsize == 120
     assert d.fields["orb_dist"][0] == np.dtype("<i4")
-    src = _header()
-    body = re.search(r"typedef struct msl_keyframe_match_params \{(.*?)\} msl_keyframe_match_params;", src, flags=re.S).group(1)
-    assert re.findall(r"(\w+)\s*;", body) == ["base", "log_scale_factor", "orb_dist"]
+    members = [p.split(".")[0] for p in d.metadata["paths"]]                 # the C members, `base` once per flattened field
+    assert members == ["base"] * len(MATCH_PARAMS_DTYPE.names) + ["log_scale_factor", "orb_dist"]
 
 
 def test_python_wrapper_is_exported():

@@ -1,19 +1,16 @@
 """msl_pose_optimize_translation[_batch] are part of the C ABI: exported by libmsl.so, declared in include/msl.h and bound in _lib with the
 argument list of msl_pose_optimize plus Rcw after Tcw.  No compute calls (no GPU needed)."""
 import ctypes as C
-import os
-import re
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("msl_pose_optimize_translation", "msl_pose_optimize_translation_batch")
 
 
 def test_exported_declared_and_bound():
-    from manhattanslam_amd import _lib
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "msl.h")).read(), flags=re.S)
+    from manhattanslam_amd import _header, _lib
+    decl = _header.declarations(_header.text("msl.h"))
     dll = C.CDLL(_lib.LIB_PATH)
     for n in NAMES:
-        assert re.search(r"MSL_API\s+int\s+" + n + r"\s*\(", src), n
+        assert decl[n][0] == "int", n
         assert hasattr(dll, n), n
         assert n in _lib.SIGNATURES, n
 

@@ -2,62 +2,44 @@
 include/msl_debug.h) and bound in _lib with matching argument types; the two forms differ in their first argument only; the params record
 and the status codes have the header's layout and values.  No compute calls (no GPU needed)."""
 import ctypes as C
-import os
 import re
 
-import numpy as np
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("msl_triangulate_new_points", "msl_triangulate_new_points_batch")
 
 
-def _header(name="msl.h"):
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", name)).read(), flags=re.S)
-
-
-def _args(src, n):
-    return [a.strip() for a in re.search(r"\b" + n + r"\s*\((.*?)\)\s*MSL_NOEXCEPT", src, flags=re.S).group(1).split(",")]
-
-
-def _argtypes(src, n):
-    """The ctypes argument types the header's declaration of n asks for."""
-    return [C.c_void_p if "*" in a else (C.c_size_t if re.match(r"size_t\b", a) else C.c_int) for a in _args(src, n)]
-
-
 def test_exported_declared_and_bound():
-    from manhattanslam_amd import _lib
+    from manhattanslam_amd import _header, _lib
     dll = C.CDLL(_lib.LIB_PATH)
-    src = _header()
+    src = _header.text("msl.h")
+    decl, dbg = _header.declarations(src), _header.declarations(_header.text("msl_debug.h"))
     for n in NAMES:
-        assert re.search(r"MSL_API\s+int\s+" + n + r"\s*\(", src), n
+        assert decl[n][0] == "int", n
         assert hasattr(dll, n), n
         res, args = _lib.SIGNATURES[n]
-        assert res is C.c_int and args == _argtypes(src, n) and len(args) == 31, n
+        assert res is C.c_int and len(args) == len(decl[n][1]) == 31, n             # the types: test_abi.py, against the compiler
         assert getattr(_lib.lib, n).argtypes == args
     n = "msl_debug_triangulate"
-    assert hasattr(dll, n) and _lib.SIGNATURES[n][1] == _argtypes(_header("msl_debug.h"), n) and len(_lib.SIGNATURES[n][1]) == 7
+    assert hasattr(dll, n) and len(_lib.SIGNATURES[n][1]) == len(dbg[n][1]) == 7
     assert "triangulate" not in " ".join(re.findall(r"msl_\w*debug\w*", src))          # the accessor is not part of the drop-in header
 
 
 def test_argument_order_of_the_two_forms():
-    from manhattanslam_amd import triangulate
-    src = _header()
-    a, b = _args(src, NAMES[0]), _args(src, NAMES[1])
-    assert a[0] == "msl_match *h" and b[0] == "int device" and a[1:] == b[1:]
-    names = [re.search(r"(\w+)$", x).group(1) for x in a]
+    from manhattanslam_amd import _header, triangulate
+    decl = _header.declarations(_header.text("msl.h"))
+    a, b = decl[NAMES[0]][1], decl[NAMES[1]][1]
+    assert a[0] == ("msl_match *", "h") and b[0] == ("int", "device") and a[1:] == b[1:]
+    names = [x[1] for x in a]
     assert names[1:6] == ["n_tab", "cap", "n_items", "ncap", "params"]
     assert tuple(names[6:15]) == triangulate.TABLE_KEYS and names[15:19] == ["cur", "neigh", "n_neigh", "mem"]
     assert tuple(names[19:30]) == triangulate.OUT_KEYS and names[30] == "out_mem"
-    assert a[19].startswith("int32_t *") and a[20].startswith("uint8_t *") and a[6].startswith("const msl_keypoint *")
+    assert a[19][0] == "int32_t *" and a[20][0] == "uint8_t *" and a[6][0] == "const msl_keypoint *"
 
 
 def test_params_record_and_status_codes():
-    from manhattanslam_amd import _lib, triangulate
+    from manhattanslam_amd import _header, _lib, triangulate
     d = _lib.TRIANGULATE_PARAMS_DTYPE
-    src = _header()
-    body = re.search(r"typedef struct msl_triangulate_params \{(.*?)\} msl_triangulate_params;", src, flags=re.S).group(1)
-    names = [n for decl in re.findall(r"[\w\s]+?([\w\s,\[\]]+);", body) for n in re.findall(r"(\w+)(?:\[\w+\])?\s*(?:,|$)", decl.strip())]
-    assert tuple(names) == d.names, (names, d.names)
+    src = _header.text("msl.h")
+    assert _header.records(src)["msl_triangulate_params"].names == d.names
     off = {n: d.fields[n][1] for n in d.names}
     assert off == dict(fx=0, fy=4, cx=8, cy=12, invfx=16, invfy=20, bf=24, b=28, nlevels=32, scale_factors=36, level_sigma2=100, scale_factor=164,
                        check_orientation=168, only_stereo=172) and d.itemsize == 176
