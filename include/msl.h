@@ -1333,6 +1333,105 @@ MSL_API int msl_refresh_map_lines_batch(int device, int n_tab, int klcap, int n_
                                         double *out_normal, float *out_dist, uint8_t *status, double *ln_normal, float *ln_dist,
                                         msl_mem out_mem) MSL_NOEXCEPT;
 
+/* ---- The local map of a frame: Tracking::UpdateLocalMap (src/Tracking.cc:1754-1764) ----
+ * The first step of Tracking::TrackLocalMap (:1350), for n_frames independent frames over one map: msl_local_keyframes is
+ * UpdateLocalKeyFrames (:1813-1907); msl_local_points is UpdateLocalPoints (:1789-1810) fused with the first loop of SearchLocalPoints
+ * (:1656-1668) and the gather of the rows out of the point table; msl_local_lines is UpdateLocalLines (:1766-1787) with the first loop of
+ * SearchLocalLines (:1698-1710) over the line table.  The outputs of the last two are the arrays msl_match_local_points /
+ * msl_match_local_lines take, so on device memory UpdateLocalMap -> SearchLocalPoints / SearchLocalLines is one chain on the handle's
+ * stream with nothing in between.  tests/localmap_model.py is the sequential model.
+ * The map is the tables of the LocalMapping entries: n_tab keyframes (kf_flags[k] bit 0: !isBad(); held_id[k][cap] / lheld_id[k][klcap] the
+ * ids their slots hold, -1 for NULL, a bad element keeps its id; n_kps / n_kl), the point table of n_pts and the line table of n_lines rows
+ * in the layouts of msl_fuse_map_points / msl_fuse_map_lines (pt_flags / ln_flags bit 0: !isBad(); pt_nobs / ln_nobs: Observations()), the
+ * CSR observation table obs_off[n_pts + 1] / obs_kf of msl_refresh_map_points (obs_idx is not read).  Per keyframe k also conn[k * ccap ..]
+ * and n_conn[k], exactly the rows msl_covisibility writes for kf = 0 .. n_tab - 1 (mvpOrderedConnectedKeyFrames; a ccap below 10 is the
+ * caller's choice of seeing fewer than GetBestCovisibilityKeyFrames(10) would, like msl_covisibility's dropped entries), and parent[k], the
+ * table index of mpParent, -1 for none.  The children of k are read as {c : parent[c] == k}.
+ * Per frame f: cur_held[f * cap + i] = the id of mvpMapPoints[i], -1 for NULL (i < n_cur[f]); cur_lheld[f * lcap + j], n_cur_lines the same
+ * for mvpMapLines.
+ * msl_local_keyframes.  prev_kf[f * n_tab ..] / n_prev[f] (both may be NULL: empty) are the caller's mvpLocalKeyFrames on entry.  Out:
+ *   votes[f * n_tab + k]     keyframeCounter, 0 = absent          ref_kf[f]     pKFmax, -1 = leave mpReferenceKF alone
+ *   local_kf[f * n_tab + r]  mvpLocalKeyFrames in push order, -1 beyond n_local_kf[f]; a keyframe enters at most once, so n_tab suffices
+ *   cur_cleared[f * cap + i] 1 where the slot holds a bad point: the caller NULLs it (:1825); 0 elsewhere, slots beyond n_cur included
+ *   status[f]                0, or MSL_LOCALMAP_NO_VOTES
+ * Reproduced exactly:
+ *   votes        for every slot i < n_cur[f] whose id is a live point, every observation adds one to its keyframe's counter: a point held
+ *                in two slots votes twice, a bad keyframe is counted here and filtered later
+ *   empty        no counter above 0 is the early return of :1830: local_kf is a copy of prev_kf (as it stands, unchecked with device
+ *                memory), ref_kf -1, MSL_LOCALMAP_NO_VOTES; UpdateLocalPoints then runs over the old list, as in the reference
+ *   first loop   map<KeyFrame*, int> order is pinned to ascending table index, as msl_covisibility pins it; bad keyframes are skipped; max
+ *                by strict >, so ref_kf is the lowest index among equal maxima of the live keyframes (-1 when every voted keyframe is
+ *                bad: the list is then empty with status 0); every live voted keyframe is pushed
+ *   second loop  walks the entries of the first loop only (the end iterator is taken before it) and stops at the top of an iteration once
+ *                the list holds more than 80, so a first loop that pushes 81 or more adds nothing and a list can end at 83.  Per keyframe
+ *                k: the first of conn[k][: min(10, n_conn[k], ccap)] that is live and not in the list; then the first live child not in
+ *                the list, set<KeyFrame*> order pinned to ascending table index; then the parent if it is not in the list, with no isBad
+ *                test -- and adding the parent leaves the whole walk (the break of :1897 is the outer loop's)
+ * msl_local_points.  local_kf / n_local_kf: the outputs above (n_tab slots per frame).  Out, mcap entries per frame:
+ *   local_id[f * mcap + j]   the ids of mvpLocalMapPoints in order: keyframes in list order, slots ascending below n_kps, first occurrence
+ *                            only, NULL and bad points skipped; -1 beyond the count
+ *   n_local[f]               the full count: entries beyond mcap are dropped and the caller compares, as with n_conn
+ *   mp_xyz, mp_normal, mp_dist, mp_desc   row local_id of pt_xyz .. pt_desc, copied bit for bit; rows beyond the count keep their bytes
+ *                            (a host-memory array is staged whole and copied back whole)
+ *   mp_flags[f * mcap + j]   bit 0: the id is not among the live ids the frame holds (mnLastFrameSeen != F.mnId after :1664; every entry is
+ *                            !isBad()), bit 1: pt_nobs > 0; 0 beyond the count
+ *   cur_flags[f * cap + i]   bit 0: the slot holds a point that is not bad, bit 1: its pt_nobs > 0; 0 beyond n_cur
+ * msl_local_lines: the same over lheld_id[k * klcap ..], n_kl, cur_lheld[f * lcap ..], n_cur_lines and the line table (ln_xyz double[6],
+ * ln_normal double[3]); it writes local_line_id, n_local_lines, ml_xyz .. ml_flags (mlcap per frame) and cur_line_flags.
+ * What stays with the caller: SetReferenceMapPoints / SetReferenceMapLines; mpReferenceKF = ref_kf; NULLing the slots cur_cleared names
+ * (and those cur_flags / cur_line_flags bit 0 leaves clear); IncreaseVisible() and mnLastFrameSeen of the held elements (cur_flags) and of
+ * the elements in view (in_view of the matchers); mnTrackReferenceForFrame is the call's own.
+ * Local-map limits: n_frames >= 1, n_tab <= 4096, cap <= 8192, klcap <= 256, lcap <= 256, n_pts <= 1048576, n_lines <= 1048576, mcap <= 32768,
+ * mlcap <= 32768, 1 <= ccap <= n_tab, n_obs_total >= 0; anything else, or a NULL array other than prev_kf / n_prev, is refused with
+ * MSL_ERR_INVALID before any launch, with msl_last_error() naming the field, and nothing is written (the _batch forms refuse before they
+ * touch a device).  A host-memory call (mem) also checks its index arrays and refuses a violation: the CSR table as msl_covisibility;
+ * n_cur / n_cur_lines inside 0 .. cap and the ids below them -1 or inside their table; n_conn inside 0 .. ccap and its entries inside the
+ * table; parent -1 or another keyframe of the table; n_prev / n_local_kf inside 0 .. n_tab and the lists' entries inside the table and
+ * distinct.  With device memory these are the caller's contract: an index outside its table is absent -- an id is NULL (not cleared), an
+ * obs_kf is skipped, a conn entry is no neighbour, a parent is none, a local_kf entry is a keyframe without slots; counts are clamped into
+ * 0 .. their capacity; a repeated local_kf entry adds nothing (first occurrence); nothing reads or writes outside its array.
+ * Scratch: a 32-bit stamp per (frame in flight, table row); frames run in groups whose stamps stay under 256 MiB.
+ * Memory and synchronisation as msl_bow_transform. */
+#define MSL_LOCALMAP_NO_VOTES 1   /* status: the counter was empty, local_kf is the list on entry */
+MSL_API int msl_local_keyframes(msl_match *h, int n_frames, int cap, int n_tab, int n_pts, int n_obs_total, int ccap, const int32_t *cur_held,
+                                const int32_t *n_cur, const uint8_t *pt_flags, const int32_t *obs_off, const int32_t *obs_kf,
+                                const uint8_t *kf_flags, const int32_t *conn, const int32_t *n_conn, const int32_t *parent,
+                                const int32_t *prev_kf, const int32_t *n_prev, msl_mem mem, int32_t *votes, int32_t *local_kf,
+                                int32_t *n_local_kf, int32_t *ref_kf, uint8_t *cur_cleared, uint8_t *status, msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device matcher handle, always synchronous; see msl_match_by_projection_batch). */
+MSL_API int msl_local_keyframes_batch(int device, int n_frames, int cap, int n_tab, int n_pts, int n_obs_total, int ccap,
+                                      const int32_t *cur_held, const int32_t *n_cur, const uint8_t *pt_flags, const int32_t *obs_off,
+                                      const int32_t *obs_kf, const uint8_t *kf_flags, const int32_t *conn, const int32_t *n_conn,
+                                      const int32_t *parent, const int32_t *prev_kf, const int32_t *n_prev, msl_mem mem, int32_t *votes,
+                                      int32_t *local_kf, int32_t *n_local_kf, int32_t *ref_kf, uint8_t *cur_cleared, uint8_t *status,
+                                      msl_mem out_mem) MSL_NOEXCEPT;
+MSL_API int msl_local_points(msl_match *h, int n_frames, int n_tab, int cap, int n_pts, int mcap, const int32_t *local_kf,
+                             const int32_t *n_local_kf, const int32_t *held_id, const int32_t *n_kps, const int32_t *cur_held,
+                             const int32_t *n_cur, const float *pt_xyz, const float *pt_normal, const float *pt_dist, const uint8_t *pt_desc,
+                             const uint8_t *pt_flags, const int32_t *pt_nobs, msl_mem mem, int32_t *local_id, int32_t *n_local, float *mp_xyz,
+                             float *mp_normal, float *mp_dist, uint8_t *mp_desc, uint8_t *mp_flags, uint8_t *cur_flags,
+                             msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device matcher handle, always synchronous). */
+MSL_API int msl_local_points_batch(int device, int n_frames, int n_tab, int cap, int n_pts, int mcap, const int32_t *local_kf,
+                                   const int32_t *n_local_kf, const int32_t *held_id, const int32_t *n_kps, const int32_t *cur_held,
+                                   const int32_t *n_cur, const float *pt_xyz, const float *pt_normal, const float *pt_dist,
+                                   const uint8_t *pt_desc, const uint8_t *pt_flags, const int32_t *pt_nobs, msl_mem mem, int32_t *local_id,
+                                   int32_t *n_local, float *mp_xyz, float *mp_normal, float *mp_dist, uint8_t *mp_desc, uint8_t *mp_flags,
+                                   uint8_t *cur_flags, msl_mem out_mem) MSL_NOEXCEPT;
+MSL_API int msl_local_lines(msl_match *h, int n_frames, int n_tab, int klcap, int lcap, int n_lines, int mlcap, const int32_t *local_kf,
+                            const int32_t *n_local_kf, const int32_t *lheld_id, const int32_t *n_kl, const int32_t *cur_lheld,
+                            const int32_t *n_cur_lines, const double *ln_xyz, const double *ln_normal, const float *ln_dist,
+                            const uint8_t *ln_desc, const uint8_t *ln_flags, const int32_t *ln_nobs, msl_mem mem, int32_t *local_line_id,
+                            int32_t *n_local_lines, double *ml_xyz, double *ml_normal, float *ml_dist, uint8_t *ml_desc, uint8_t *ml_flags,
+                            uint8_t *cur_line_flags, msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device matcher handle, always synchronous). */
+MSL_API int msl_local_lines_batch(int device, int n_frames, int n_tab, int klcap, int lcap, int n_lines, int mlcap, const int32_t *local_kf,
+                                  const int32_t *n_local_kf, const int32_t *lheld_id, const int32_t *n_kl, const int32_t *cur_lheld,
+                                  const int32_t *n_cur_lines, const double *ln_xyz, const double *ln_normal, const float *ln_dist,
+                                  const uint8_t *ln_desc, const uint8_t *ln_flags, const int32_t *ln_nobs, msl_mem mem,
+                                  int32_t *local_line_id, int32_t *n_local_lines, double *ml_xyz, double *ml_normal, float *ml_dist,
+                                  uint8_t *ml_desc, uint8_t *ml_flags, uint8_t *cur_line_flags, msl_mem out_mem) MSL_NOEXCEPT;
+
 /* msl_kfdb: a KeyFrameDatabase (src/KeyFrameDatabase.cc:38-66) on one device.  msl_kfdb_create returns NULL with msl_last_error() when no
  * device is usable.  msl_kfdb_add stores the BowVector of one keyframe exactly as msl_bow_transform wrote it (ascending int32 words, double
  * values, the count -- on the device for MSL_MEM_DEVICE) and returns its slot when the vector is stored; with device memory `h` is the

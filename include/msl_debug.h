@@ -103,6 +103,11 @@ MSL_API int msl_debug_fuse(msl_match *h, int item, float *uvr, int32_t *level_n)
  * nPredictedLevel (not clamped) and vIndices.size() (set with the radius).  Zeros where the candidate left earlier. */
 MSL_API int msl_debug_line_fuse(msl_match *h, int item, float *uvr, int32_t *level_n) MSL_NOEXCEPT;
 
+/* The scratch budget of msl_local_points / msl_local_lines on h, in bytes (default 256 MiB): the frames of a call run in groups of
+ * max(1, bytes / (4 * n_pts)) (n_lines for the line entry), one 32-bit stamp per (frame of the group, table row).  A test sets it low to cross a group
+ * boundary with a small table; the results do not depend on it.  At least 4. */
+MSL_API int msl_debug_local_map_budget(msl_match *h, size_t bytes) MSL_NOEXCEPT;
+
 #define MSL_SF_NKERNELS 12
 MSL_API int msl_sf_profile_enable(msl_sf *h, int mode) MSL_NOEXCEPT;
 /* Sampling for the per-dispatch event pairs: only every stride-th launch of a timed kernel carries events (default 1 = every launch).  A

@@ -33,3 +33,4 @@ from . import mappoint  # noqa: F401
 from ._lib import REFRESH_PARAMS_DTYPE  # noqa: F401
 from . import linefuse  # noqa: F401
 from ._lib import LINE_FUSE_PARAMS_DTYPE  # noqa: F401
+from . import localmap  # noqa: F401

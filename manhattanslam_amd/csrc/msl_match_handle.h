@@ -1,7 +1,7 @@
 // msl_match_handle.h -- the matcher handle, its staging of caller arrays (Stage), the forwarder of the *_batch entry points, the limits
 // that several entry points share (table_limits, line_table_limits, levels_ok) and the row readback of the debug entry points (last_call_row);
 // shared by msl_match.hip, msl_line_match.hip, msl_pose.hip, msl_plane.hip, msl_bow.hip, msl_reloc.hip, msl_pnp.hip, msl_line3d.hip,
-// msl_triangulate.hip, msl_fuse.hip, msl_mappoint.hip and msl_line_fuse.hip (internal).
+// msl_triangulate.hip, msl_fuse.hip, msl_mappoint.hip, msl_line_fuse.hip and msl_local_map.hip (internal).
 #pragma once
 
 #include "msl_common.h"
@@ -76,6 +76,10 @@ struct msl_match {
     int fuseItems = 0, fuseLcap = 0;                                   // the shape of the last msl_fuse_map_points call
     msl::DevBuf lfuseRec;                                              // msl_fuse_map_lines: per (item, candidate) the query, which msl_debug_line_fuse reads
     int lfuseItems = 0, lfuseLcap = 0;                                 // the shape of the last msl_fuse_map_lines call
+    // msl_local_points / msl_local_lines: per (frame in flight, table row) the stamp of the ordered compaction, per (frame in flight, list
+    // position) the kept count and its scan; the stamps of one group of frames stay under lmBudget bytes (msl_debug_local_map_budget)
+    msl::DevBuf lmStamp, lmCount;
+    size_t lmBudget = (size_t)256 << 20;
     // Device copies of host-memory arguments, one pool for every entry point (msl::Stage deals the slots out in declaration order).
     // Sharing is sound because every call that touches the pool returns with the stream drained (Stage::finish synchronises whenever
     // either side is host memory, and only then is a slot used), so no slot is live when the next call starts.
