@@ -1432,6 +1432,95 @@ MSL_API int msl_local_lines_batch(int device, int n_frames, int n_tab, int klcap
                                   int32_t *local_line_id, int32_t *n_local_lines, double *ml_xyz, double *ml_normal, float *ml_dist,
                                   uint8_t *ml_desc, uint8_t *ml_flags, uint8_t *cur_line_flags, msl_mem out_mem) MSL_NOEXCEPT;
 
+/* ---- The cullings of LocalMapping::Run: KeyFrameCulling (src/LocalMapping.cc:704-759) and the recent-element cullings (:227-301) ----
+ * msl_cull_keyframes: n_items independent calls of LocalMapping::KeyFrameCulling over one map, each from the state on entry.  The map is
+ * the tables of the other LocalMapping entries: the keyframe table of n_tab keyframes with cap keypoints each (kps_un: the octave is read;
+ * uright; depth = mvDepth; held_id; n_kps) with kf_flags[k], bit 0: !isBad() (not read: the reference has no isBad test on a candidate),
+ * bit 1: mbNotErase (set at src/Tracking.cc:1637 for a keyframe that created a map plane); the point table (pt_flags bit 0: !isBad(),
+ * pt_nobs: Observations()); the CSR observation table obs_off / obs_kf / obs_idx of msl_refresh_map_points (obs_idx is read).
+ * Item f: cand[f * ccap + r], r < n_cand[f] = GetVectorCovisibleKeyFrames() of the item's current keyframe in order -- exactly the conn /
+ * n_conn rows msl_covisibility writes (an n_cand above ccap is clamped, as n_conn is the full count).  origin: the table index of the
+ * keyframe with mnId == 0, or -1.  params->th_depth: mThDepth.  Out, per (item f, candidate r) at [f * ccap + r]:
+ *   n_mps, n_redundant   nMPs and nRedundantObservations of the candidate's turn
+ *   n_gone               the candidate's slots below n_kps whose point was live on entry and is bad at the candidate's turn
+ *   status               one MSL_CULL_* code
+ * Entries beyond n_cand are -1 (the counters) and 0 (status).
+ * Reproduced exactly (tests/cull_model.py is the sequential model, and its literal twin):
+ *   slot loop    slots i < n_kps[k]; a NULL or bad point is skipped; depth > th_depth || depth < 0 skips by the literal float tests, so a
+ *                NaN depth counts; then nMPs++; a point held in two slots counts twice
+ *   redundancy   only when the point's current Observations() > 3: its current observations in keyframes other than k whose keypoint
+ *                octave is <= octave(i) + 1 are counted, and 3 make it redundant (the break does not change the result)
+ *   verdict      (double)n_redundant > 0.9 * (double)n_mps, evaluated as 10 * n_redundant > 9 * n_mps in int, which is equal for every
+ *                n_mps <= 8192; n_mps == 0 keeps the keyframe
+ *   candidates   no isBad test: a bad candidate is counted and, if redundant, culled like any other; only origin is skipped without counting
+ *   the chain    culling c is EraseObservation(c) on every point c holds in a slot, bad or not, once per point: the point's observation by
+ *                c, if it has one, disappears and nObs drops by 2 when uright[c][obs_idx] >= 0, else by 1 (the observation's keypoint, not
+ *                the slot's); a point whose nObs is then <= 2 turns bad, leaves every later candidate's n_mps, and later erasures on it do
+ *                nothing.  A candidate with MSL_CULL_NOT_ERASE changes nothing for its successors
+ *   inconsistent tables (msl_triangulate_new_points produces them)   an observation (c, idx) of p is erased only if c holds p in some
+ *                slot below n_kps[c]; a held point that does not observe c is untouched; a point that is bad on entry has no observations,
+ *                whatever the table says
+ * Pin: MapPoint::SetBadFlag also NULLs slot obs_idx of every keyframe that still observes the point (EraseMapPointMatch).  Where that
+ * slot holds the point itself, is empty or holds a bad point this changes nothing here.  Where it holds another live point q, the reference
+ * takes q out of that keyframe's later walk; the entry does not follow that, and a caller whose tables can hold such a pair replays
+ * the culled keyframes against its objects.
+ * What stays with the caller: KeyFrame::SetBadFlag on the keyframes with MSL_CULL_CULLED, in order (the spanning tree, connections,
+ * database and map erasure, the line and plane observations), and rebuilding the CSR table afterwards; the device tables are not updated.
+ * msl_cull_recent: the verdict of MapPointCulling (:227-250), MapLineCulling (:252-275) and MapPlaneCulling (:277-301) for a list of n
+ * recent elements: found / visible = mnFound / mnVisible, first_kf_id = mnFirstKFid, nobs = Observations(), flags bit 0: !isBad();
+ * cur_kf_id = mpCurrentKeyFrame->mnId; th_obs = cnThObs (3 for points and lines, 2 for planes).  verdict[i] is the branch taken, tested in
+ * the reference's order: bad; ratio < 0.25f; cur_kf_id - first_kf_id >= 2 && nobs <= th_obs; cur_kf_id - first_kf_id >= 3; none.  ratio_form
+ * pins a real difference: MSL_RATIO_FLOAT is (float)found / visible (src/MapPoint.cc:205, src/MapPlane.cc:173), a float division whose
+ * IEEE results for visible == 0 (inf, NaN) compare as on the CPU; MSL_RATIO_INT is (float)(found / visible), the integer division of
+ * src/MapLine.cpp:190-193, which the reference divides by zero in when visible == 0 for an element that is not bad: a host-memory call
+ * refuses that, with device memory the element gets MSL_RECENT_INVALID.  Ids are non-negative and their difference is taken in int.  List
+ * surgery and SetBadFlag stay with the caller.
+ * Cull limits: n_tab <= 4096, cap <= 8192, n_pts <= 1048576, 1 <= n_items <= 4096, n_obs_total >= 0, 1 <= ccap <= n_tab; 1 <= n <= 1048576,
+ * cur_kf_id >= 0, th_obs >= 0, ratio_form one of the two; anything else, or a NULL argument, is refused with MSL_ERR_INVALID before any
+ * launch, with msl_last_error() naming the field, and nothing is written (the _batch forms refuse before they touch a device).  A
+ * host-memory call (mem) also checks its index arrays and refuses a violation: the CSR table as msl_covisibility, with obs_idx < n_kps;
+ * n_cand inside 0 .. ccap and the entries below it inside the table and distinct; origin -1 or inside the table; found, visible and
+ * first_kf_id not negative.  With device memory these are the caller's contract: an index outside its table is absent -- a cand entry gets
+ * MSL_CULL_ABSENT and zero counters, an observation whose obs_kf is outside the table or whose obs_idx is outside [0, cap) is skipped, a
+ * held_id outside the point table is NULL, an origin outside the table is none; a repeated candidate is walked again (its erasures are
+ * already done); nothing reads or writes outside its array.  Memory and synchronisation as msl_bow_transform. */
+typedef struct msl_cull_params {
+    float th_depth;                                  /* KeyFrame::mThDepth */
+} msl_cull_params;
+#define MSL_CULL_KEPT        1   /* not redundant */
+#define MSL_CULL_CULLED      2   /* redundant, SetBadFlag takes effect */
+#define MSL_CULL_ORIGIN      3   /* skipped by :715, counters 0 */
+#define MSL_CULL_NOT_ERASE   4   /* redundant, but SetBadFlag returned at src/KeyFrame.cc:354: no effect on later candidates */
+#define MSL_CULL_ABSENT      5   /* index outside the table (device memory only), counters 0 */
+#define MSL_RATIO_FLOAT      0   /* ratio_form: (float)found / visible -- points and planes */
+#define MSL_RATIO_INT        1   /* ratio_form: (float)(found / visible) -- lines */
+#define MSL_RECENT_KEEP        0   /* stays in the list */
+#define MSL_RECENT_ERASE_BAD   1   /* already bad: drop from the list */
+#define MSL_RECENT_CULL_RATIO  2   /* SetBadFlag, then drop */
+#define MSL_RECENT_CULL_OBS    3   /* SetBadFlag, then drop */
+#define MSL_RECENT_RETIRE      4   /* old enough: drop */
+#define MSL_RECENT_INVALID     5   /* the integer ratio form with visible == 0 (device memory only) */
+MSL_API int msl_cull_keyframes(msl_match *h, int n_tab, int cap, int n_pts, int n_items, int n_obs_total, int ccap, int origin,
+                               const msl_cull_params *params, const msl_keypoint *kps_un, const float *uright, const float *depth,
+                               const int32_t *held_id, const int32_t *n_kps, const uint8_t *kf_flags, const uint8_t *pt_flags,
+                               const int32_t *pt_nobs, const int32_t *obs_off, const int32_t *obs_kf, const int32_t *obs_idx,
+                               const int32_t *cand, const int32_t *n_cand, msl_mem mem, int32_t *n_mps, int32_t *n_redundant, int32_t *n_gone,
+                               uint8_t *status, msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device matcher handle, always synchronous; see msl_match_by_projection_batch). */
+MSL_API int msl_cull_keyframes_batch(int device, int n_tab, int cap, int n_pts, int n_items, int n_obs_total, int ccap, int origin,
+                                     const msl_cull_params *params, const msl_keypoint *kps_un, const float *uright, const float *depth,
+                                     const int32_t *held_id, const int32_t *n_kps, const uint8_t *kf_flags, const uint8_t *pt_flags,
+                                     const int32_t *pt_nobs, const int32_t *obs_off, const int32_t *obs_kf, const int32_t *obs_idx,
+                                     const int32_t *cand, const int32_t *n_cand, msl_mem mem, int32_t *n_mps, int32_t *n_redundant,
+                                     int32_t *n_gone, uint8_t *status, msl_mem out_mem) MSL_NOEXCEPT;
+MSL_API int msl_cull_recent(msl_match *h, int n, int cur_kf_id, int th_obs, int ratio_form, const int32_t *found, const int32_t *visible,
+                            const int32_t *first_kf_id, const int32_t *nobs, const uint8_t *flags, msl_mem mem, uint8_t *verdict,
+                            msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device matcher handle, always synchronous). */
+MSL_API int msl_cull_recent_batch(int device, int n, int cur_kf_id, int th_obs, int ratio_form, const int32_t *found, const int32_t *visible,
+                                  const int32_t *first_kf_id, const int32_t *nobs, const uint8_t *flags, msl_mem mem, uint8_t *verdict,
+                                  msl_mem out_mem) MSL_NOEXCEPT;
+
 /* msl_kfdb: a KeyFrameDatabase (src/KeyFrameDatabase.cc:38-66) on one device.  msl_kfdb_create returns NULL with msl_last_error() when no
  * device is usable.  msl_kfdb_add stores the BowVector of one keyframe exactly as msl_bow_transform wrote it (ascending int32 words, double
  * values, the count -- on the device for MSL_MEM_DEVICE) and returns its slot when the vector is stored; with device memory `h` is the

@@ -34,3 +34,4 @@ from ._lib import REFRESH_PARAMS_DTYPE  # noqa: F401
 from . import linefuse  # noqa: F401
 from ._lib import LINE_FUSE_PARAMS_DTYPE  # noqa: F401
 from . import localmap  # noqa: F401
+from . import cull  # noqa: F401
