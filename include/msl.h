@@ -967,9 +967,10 @@ MSL_API int msl_lines_3d_batch(int device, int n_frames, int lcap, int order, co
  *     eigenvalue, cast to float, then a float division by its fourth component
  *   - UnprojectStereo of a stereo keypoint with depth <= 0 (an empty Mat in the reference): MSL_TRI_LOW_PARALLAX
  *   - a keypoint whose octave is outside [0, nlevels) is never searched, on either side
- * Limits: cap <= 8192, ncap <= 16, nlevels <= MSL_MATCH_MAX_LEVELS, n_items <= 65535; anything else is refused with MSL_ERR_INVALID before
- * any launch, and nothing is written.  Memory and synchronisation as msl_bow_transform: device pointers run asynchronously on the handle's
- * stream, with host memory on either side the call returns when the caller's buffers are its own again. */
+ * Limits: cap <= 8192, ncap <= 16, n_tab <= 4096, nlevels <= MSL_MATCH_MAX_LEVELS, 1 <= n_items <= 65535; anything else, or a NULL
+ * argument, is refused with MSL_ERR_INVALID before any launch, with msl_last_error() naming the field, and nothing is written (the _batch
+ * form refuses before it touches a device).  Memory and synchronisation as msl_bow_transform: device pointers run asynchronously on the
+ * handle's stream, with host memory on either side the call returns when the caller's buffers are its own again. */
 typedef struct msl_triangulate_params {
     float fx, fy, cx, cy, invfx, invfy;          /* KeyFrame::fx .. invfy (one camera for every keyframe) */
     float bf, b;                                 /* mbf, mb */
@@ -1056,9 +1057,10 @@ MSL_API int msl_triangulate_new_points_batch(int device, int n_tab, int cap, int
  * consistent or NULLs the candidate; a keypoint whose octave is outside [0, nlevels) is never a candidate; a held_id outside [0, n_pts)
  * is an empty slot.
  * Limits: cap <= 8192, n_tab <= 4096, n_pts <= 1048576, lcap <= 65536, tcap <= 64, n_items <= 4096, nlevels <= MSL_MATCH_MAX_LEVELS,
- * 0 <= th_low <= 255; anything else is refused with MSL_ERR_INVALID before any launch, and nothing is written.  A host-memory call also
- * checks the index ranges (tgt, list, targets, n_targets, n_cand, every list entry) and the distinctness of each list, and refuses a
- * violation; with device memory these are the caller's contract: an index outside its table is treated as NULL, a bad tgt or list as a
+ * 0 <= th_low <= 255; anything else, or a NULL argument, is refused with MSL_ERR_INVALID before any launch, with msl_last_error() naming
+ * the field, and nothing is written (the _batch forms refuse before they touch a device).  A host-memory call also checks the index
+ * ranges (tgt, list, targets, n_targets, n_cand, every list entry) and the distinctness of each list, and refuses a violation; with device
+ * memory these are the caller's contract: an index outside its table is treated as NULL, a bad tgt or list as a
  * keyframe without keypoints / an empty list, a repeated id goes unnoticed.  Memory and synchronisation as msl_bow_transform. */
 typedef struct msl_fuse_params {
     float fx, fy, cx, cy, bf;                        /* KeyFrame::fx .. cy, mbf */
@@ -1161,8 +1163,10 @@ MSL_API int msl_fuse_map_points_batch(int device, int n_tab, int cap, int n_pts,
  * AddConnection on the other keyframes, the parent / child link and the assignment of the maps stay with the caller, which reads them
  * from weight and conn.
  * Limits: n_tab <= 4096, cap <= 8192, n_pts <= 1048576, n_items <= n_pts (refresh) / <= n_tab (covisibility), ccap <= n_tab, nlevels <=
- * MSL_MATCH_MAX_LEVELS, what non-zero and inside the mask; anything else is refused with MSL_ERR_INVALID before any launch, with
- * msl_last_error() naming the field, and nothing is written.  A host-memory call (mem) also checks the index arrays and refuses a
+ * MSL_MATCH_MAX_LEVELS, what non-zero and inside the mask; anything else, or a NULL array other than pt_desc / pt_normal / pt_dist and
+ * those MSL_REFRESH_DESC alone does without (what is tested first), is refused with MSL_ERR_INVALID before any launch, with
+ * msl_last_error() naming the field, and nothing is written (the _batch forms refuse before they touch a device).  A host-memory call
+ * (mem) also checks the index arrays and refuses a
  * violation: obs_off ascending with obs_off[n_pts] == n_obs_total, obs_kf inside the table, obs_idx < n_kps[obs_kf], ids / kf in range,
  * ids distinct, pt_ref of every item in range.  With device memory these are the caller's contract: an observation whose obs_kf is outside
  * the table is skipped by both entries as if absent, one whose obs_idx is outside [0, cap) has no descriptor, an id outside the point table
@@ -1260,8 +1264,9 @@ MSL_API int msl_covisibility_batch(int device, int n_tab, int cap, int n_pts, in
  * Pins: membership of a line in the keyframe is read from the table, id in held_id[tgt][:n_kl]; a held_id outside [0, n_lines) is an empty
  * slot.
  * Limits: klcap <= 256, n_tab <= 4096, n_lines <= 1048576, lcap <= 65536, n_items <= 4096, nlevels <= MSL_MATCH_MAX_LEVELS, 0 <= th_low <=
- * 256; anything else is refused with MSL_ERR_INVALID before any launch, and nothing is written.  A host-memory call also checks the index
- * ranges (tgt, list, n_cand, every list entry) and the distinctness of each list, and refuses a violation; with device memory these are
+ * 256; anything else, or a NULL argument, is refused with MSL_ERR_INVALID before any launch, with msl_last_error() naming the field, and
+ * nothing is written (the _batch forms refuse before they touch a device).  A host-memory call also checks the index ranges (tgt, list,
+ * n_cand, every list entry) and the distinctness of each list, and refuses a violation; with device memory these are
  * the caller's contract: an index outside its table is treated as NULL, a bad tgt as a keyframe without keylines, a bad list as an empty
  * list, a repeated id goes unnoticed; no index reads or writes outside its table.  Memory and synchronisation as msl_bow_transform.
  * msl_refresh_map_lines: n_items distinct line ids ids[f].  The observations are the CSR table of msl_refresh_map_points over the line
@@ -1279,8 +1284,8 @@ MSL_API int msl_covisibility_batch(int device, int n_tab, int cap, int n_pts, in
  *               level = the octave of the reference keyframe's keyline observations[pRefKF] (index 0 when the reference keyframe is not
  *               among the observations, as map::operator[] gives); mfMinDistance = mfMaxDistance / scale_factors[nlevels - 1]
  * An octave outside [0, nlevels), a ln_ref outside the table or a reference keyline outside [0, klcap) is MSL_REFRESH_BAD_OCTAVE.
- * Refresh limits: n_tab <= 4096, klcap <= 256, n_lines <= 1048576, n_items <= n_lines, nlevels <= MSL_MATCH_MAX_LEVELS; refused as above.
- * A host-memory call checks the CSR table and ids (in range, distinct); with device memory an observation whose obs_kf is outside the
+ * Refresh limits: n_tab <= 4096, klcap <= 256, n_lines <= 1048576, n_items <= n_lines, nlevels <= MSL_MATCH_MAX_LEVELS; refused as above,
+ * as is a NULL array other than ln_normal / ln_dist.  A host-memory call checks the CSR table and ids (in range, distinct); with device memory an observation whose obs_kf is outside the
  * table is skipped as if absent and an id outside the line table is a bad line. */
 typedef struct msl_line_fuse_params {
     float fx, fy, cx, cy;                            /* KeyFrame::fx .. cy */

@@ -10,8 +10,7 @@
 // "k holds p" is held_id[k][idx] == p at the observation's own index; only on a mismatch are k's slots scanned (inconsistent tables).
 // Pins (tests/cull_model.py is the sequential model): msl.h's list; device-only: an index outside its table is absent.
 #include "msl_match_handle.h"
-#include "msl_cull_check.h"
-#include "msl_mappoint_check.h"
+#include "msl_index_check.h"
 #include "msl_obs_walk.h"
 
 namespace {
@@ -133,15 +132,6 @@ __global__ __launch_bounds__(RECENT_NT) void k_cull_recent(RecentDev D) {
 }
 
 // ==== host side ==============================================================================================================================
-// none_null, handle_form and batch_form are msl_local_map.hip's, which keeps them file-local; they are restated here so that file stays as it is
-struct Named { const char *name; const void *p; };
-bool none_null(const char *who, std::initializer_list<Named> args) {
-    for (const Named &a : args)
-        if (!a.p) { set_error("%s: %s is NULL", who, a.name); return false; }
-    return true;
-}
-#define MSL_NAMED(x) Named{#x, x}
-
 const char *const WHO_KF = "msl_cull_keyframes", *const WHO_RECENT = "msl_cull_recent";
 
 int check_keyframes(int n_tab, int cap, int n_pts, int n_items, int n_obs_total, int ccap, int origin, const msl_cull_params *params,
@@ -159,9 +149,10 @@ int check_keyframes(int n_tab, int cap, int n_pts, int n_items, int n_obs_total,
     if (n_obs_total < 0) { set_error("%s: n_obs_total %d below 0", who, n_obs_total); return MSL_ERR_INVALID; }
     if (ccap < 1 || ccap > n_tab) { set_error("%s: ccap %d outside 1 .. n_tab = %d", who, ccap, n_tab); return MSL_ERR_INVALID; }
     char why[256];
-    if (mem == MSL_MEM_HOST && (!cull::origin_ok(n_tab, origin, why, sizeof(why)) ||
-                                !mappoint::csr_ok(n_tab, cap, n_pts, n_obs_total, obs_off, obs_kf, obs_idx, n_kps, why, sizeof(why)) ||
-                                !cull::cand_ok(n_items, n_tab, ccap, cand, n_cand, why, sizeof(why)))) return refuse(who, why);
+    if (mem == MSL_MEM_HOST && (!check::origin_ok(n_tab, origin, why, sizeof(why)) ||
+                                !check::csr_ok(n_tab, cap, n_pts, n_obs_total, obs_off, obs_kf, obs_idx, n_kps, why, sizeof(why)) ||
+                                !check::kf_rows_ok("cand", "n_cand", "ccap", n_items, n_tab, ccap, cand, n_cand, why, sizeof(why))))
+        return refuse(who, why);
     return MSL_OK;
 }
 
@@ -202,7 +193,7 @@ int check_recent(int n, int cur_kf_id, int th_obs, int ratio_form, const int32_t
         return MSL_ERR_INVALID;
     }
     char why[256];
-    if (mem == MSL_MEM_HOST && !cull::recent_ok(n, ratio_form == MSL_RATIO_INT, found, visible, first_kf_id, flags, why, sizeof(why)))
+    if (mem == MSL_MEM_HOST && !check::recent_ok(n, ratio_form == MSL_RATIO_INT, found, visible, first_kf_id, flags, why, sizeof(why)))
         return refuse(who, why);
     return MSL_OK;
 }
@@ -222,19 +213,6 @@ int launch_recent(msl_match *h, int n, int cur_kf_id, int th_obs, int ratio_form
     MSL_HIP_TRY(hipGetLastError());
     MSL_HIP_TRY(S.finish());
     return MSL_OK;
-}
-
-// The two forms of an entry: the checks come first and need no device, so a refusal is made before the handle is touched
-template <class Check, class Launch, class... A>
-int handle_form(const char *who, Check check, Launch launch, msl_match *h, A... a) {
-    if (!h) { set_error("%s: h is NULL", who); return MSL_ERR_INVALID; }
-    const int rc = check(a...);
-    return rc != MSL_OK ? rc : launch(h, a...);
-}
-template <class Check, class Launch, class... A>
-int batch_form(Check check, Launch launch, int device, bool sync_legacy, A... a) {
-    const int rc = check(a...);
-    return rc != MSL_OK ? rc : abi_call_default(launch, device, sync_legacy, a...);
 }
 
 }  // namespace

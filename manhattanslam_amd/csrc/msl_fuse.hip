@@ -21,7 +21,7 @@
 // octave outside [0, nlevels) is never a candidate; a held_id outside [0, n_pts) is an empty slot; device-only: an id outside the point
 // table is NULL, a tgt outside the keyframe table has no pose, so its live candidates leave as NO_FEATURE, a list outside the lists is empty.
 #include "msl_fuse_list.h"
-#include "msl_mappoint_check.h"
+#include "msl_index_check.h"
 #include "msl_match_window.h"
 
 #include <algorithm>
@@ -286,15 +286,24 @@ __global__ __launch_bounds__(CAND_NT) void k_fuse_cand(CandDev D) {
 }
 
 // ==== host side ==============================================================================================================================
-int run_fuse_candidates(msl_match *h, int n_tab, int cap, int n_pts, int n_items, int tcap, int lcap, const int32_t *held_id, const int32_t *n_kps,
-                        const uint8_t *pt_flags, const int32_t *targets, const int32_t *n_targets, msl_mem mem, int32_t *cand, int32_t *n_cand,
-                        msl_mem out_mem) {
-    const char *who = "msl_fuse_candidates";
-    if (!h || !held_id || !n_kps || !pt_flags || !targets || !n_targets || !cand || !n_cand) { set_error("%s: invalid argument (null pointer)", who); return MSL_ERR_INVALID; }
+const char *const WHO_CAND = "msl_fuse_candidates", *const WHO_FUSE = "msl_fuse_map_points";
+
+int check_fuse_candidates(int n_tab, int cap, int n_pts, int n_items, int tcap, int lcap, const int32_t *held_id, const int32_t *n_kps,
+                          const uint8_t *pt_flags, const int32_t *targets, const int32_t *n_targets, msl_mem mem, int32_t *cand, int32_t *n_cand,
+                          msl_mem) {
+    const char *who = WHO_CAND;
+    if (!none_null(who, {MSL_NAMED(held_id), MSL_NAMED(n_kps), MSL_NAMED(pt_flags), MSL_NAMED(targets), MSL_NAMED(n_targets), MSL_NAMED(cand),
+                         MSL_NAMED(n_cand)})) return MSL_ERR_INVALID;
     if (!table_limits(who, n_tab, cap, n_pts) || !item_limits(who, n_items, lcap)) return MSL_ERR_INVALID;
     if (tcap < 1 || tcap > MAX_TCAP) { set_error("%s: tcap %d outside 1 .. %d", who, tcap, MAX_TCAP); return MSL_ERR_INVALID; }
     char why[256];
-    if (mem == MSL_MEM_HOST && !mappoint::targets_ok(n_tab, n_items, tcap, targets, n_targets, why, sizeof(why))) return refuse(who, why);
+    if (mem == MSL_MEM_HOST && !check::targets_ok(n_tab, n_items, tcap, targets, n_targets, why, sizeof(why))) return refuse(who, why);
+    return MSL_OK;
+}
+
+int launch_fuse_candidates(msl_match *h, int n_tab, int cap, int n_pts, int n_items, int tcap, int lcap, const int32_t *held_id,
+                           const int32_t *n_kps, const uint8_t *pt_flags, const int32_t *targets, const int32_t *n_targets, msl_mem mem,
+                           int32_t *cand, int32_t *n_cand, msl_mem out_mem) {
     int rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
     hipStream_t st = h->stream;
@@ -319,23 +328,30 @@ int run_fuse_candidates(msl_match *h, int n_tab, int cap, int n_pts, int n_items
     return MSL_OK;
 }
 
-int run_fuse(msl_match *h, int n_tab, int cap, int n_pts, int n_items, int n_lists, int lcap, const msl_fuse_params *prm, const msl_keypoint *kps_un,
-             const float *uright, const int32_t *grid_cell, const uint8_t *desc, const int32_t *n_kps, const float *Tcw, const int32_t *held_id,
-             const float *pt_xyz, const float *pt_normal, const float *pt_dist, const uint8_t *pt_desc, const uint8_t *pt_flags, const int32_t *pt_nobs,
-             const int32_t *tgt, const int32_t *list, const int32_t *cand, const int32_t *n_cand, msl_mem mem, int32_t *best_idx, int32_t *best_dist,
-             uint8_t *status, int32_t *other, int32_t *n_fused, msl_mem out_mem) {
-    const char *who = "msl_fuse_map_points";
-    if (!h || !prm || !kps_un || !uright || !grid_cell || !desc || !n_kps || !Tcw || !held_id || !pt_xyz || !pt_normal || !pt_dist || !pt_desc ||
-        !pt_flags || !pt_nobs || !tgt || !list || !cand || !n_cand || !best_idx || !best_dist || !status || !other || !n_fused) {
-        set_error("%s: invalid argument (null pointer)", who);
-        return MSL_ERR_INVALID;
-    }
+int check_fuse(int n_tab, int cap, int n_pts, int n_items, int n_lists, int lcap, const msl_fuse_params *params, const msl_keypoint *kps_un,
+               const float *uright, const int32_t *grid_cell, const uint8_t *desc, const int32_t *n_kps, const float *Tcw, const int32_t *held_id,
+               const float *pt_xyz, const float *pt_normal, const float *pt_dist, const uint8_t *pt_desc, const uint8_t *pt_flags,
+               const int32_t *pt_nobs, const int32_t *tgt, const int32_t *list, const int32_t *cand, const int32_t *n_cand, msl_mem mem,
+               int32_t *best_idx, int32_t *best_dist, uint8_t *status, int32_t *other, int32_t *n_fused, msl_mem) {
+    const char *who = WHO_FUSE;
+    if (!none_null(who, {MSL_NAMED(params), MSL_NAMED(kps_un), MSL_NAMED(uright), MSL_NAMED(grid_cell), MSL_NAMED(desc), MSL_NAMED(n_kps),
+                         MSL_NAMED(Tcw), MSL_NAMED(held_id), MSL_NAMED(pt_xyz), MSL_NAMED(pt_normal), MSL_NAMED(pt_dist), MSL_NAMED(pt_desc),
+                         MSL_NAMED(pt_flags), MSL_NAMED(pt_nobs), MSL_NAMED(tgt), MSL_NAMED(list), MSL_NAMED(cand), MSL_NAMED(n_cand),
+                         MSL_NAMED(best_idx), MSL_NAMED(best_dist), MSL_NAMED(status), MSL_NAMED(other), MSL_NAMED(n_fused)})) return MSL_ERR_INVALID;
     if (!table_limits(who, n_tab, cap, n_pts) || !item_limits(who, n_items, lcap)) return MSL_ERR_INVALID;
     if (n_lists < 1) { set_error("%s: n_lists %d below 1", who, n_lists); return MSL_ERR_INVALID; }
-    if (!levels_ok(who, prm->nlevels)) return MSL_ERR_INVALID;
-    if (prm->th_low < 0 || prm->th_low > 255) { set_error("%s: th_low %d outside 0 .. 255", who, prm->th_low); return MSL_ERR_INVALID; }
+    if (!levels_ok(who, params->nlevels)) return MSL_ERR_INVALID;
+    if (params->th_low < 0 || params->th_low > 255) { set_error("%s: th_low %d outside 0 .. 255", who, params->th_low); return MSL_ERR_INVALID; }
     char why[256];
-    if (mem == MSL_MEM_HOST && !mappoint::lists_ok("point", n_tab, n_pts, n_items, n_lists, lcap, tgt, list, cand, n_cand, why, sizeof(why))) return refuse(who, why);
+    if (mem == MSL_MEM_HOST && !check::lists_ok("point", n_tab, n_pts, n_items, n_lists, lcap, tgt, list, cand, n_cand, why, sizeof(why))) return refuse(who, why);
+    return MSL_OK;
+}
+
+int launch_fuse(msl_match *h, int n_tab, int cap, int n_pts, int n_items, int n_lists, int lcap, const msl_fuse_params *prm,
+                const msl_keypoint *kps_un, const float *uright, const int32_t *grid_cell, const uint8_t *desc, const int32_t *n_kps, const float *Tcw,
+                const int32_t *held_id, const float *pt_xyz, const float *pt_normal, const float *pt_dist, const uint8_t *pt_desc,
+                const uint8_t *pt_flags, const int32_t *pt_nobs, const int32_t *tgt, const int32_t *list, const int32_t *cand, const int32_t *n_cand,
+                msl_mem mem, int32_t *best_idx, int32_t *best_dist, uint8_t *status, int32_t *other, int32_t *n_fused, msl_mem out_mem) {
     int rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
     hipStream_t st = h->stream;
@@ -387,7 +403,8 @@ int msl_fuse_candidates(msl_match *h, int n_tab, int cap, int n_pts, int n_items
                         const uint8_t *pt_flags, const int32_t *targets, const int32_t *n_targets, msl_mem mem, int32_t *cand, int32_t *n_cand,
                         msl_mem out_mem) noexcept {
     try {
-    return run_fuse_candidates(h, n_tab, cap, n_pts, n_items, tcap, lcap, held_id, n_kps, pt_flags, targets, n_targets, mem, cand, n_cand, out_mem);
+    return handle_form(WHO_CAND, check_fuse_candidates, launch_fuse_candidates, h, n_tab, cap, n_pts, n_items, tcap, lcap, held_id, n_kps, pt_flags,
+                       targets, n_targets, mem, cand, n_cand, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -395,8 +412,8 @@ int msl_fuse_candidates_batch(int device, int n_tab, int cap, int n_pts, int n_i
                               const int32_t *n_kps, const uint8_t *pt_flags, const int32_t *targets, const int32_t *n_targets, msl_mem mem,
                               int32_t *cand, int32_t *n_cand, msl_mem out_mem) noexcept {
     try {
-    return abi_call_default(run_fuse_candidates, device, mem == MSL_MEM_DEVICE, n_tab, cap, n_pts, n_items, tcap, lcap, held_id, n_kps, pt_flags, targets,
-                            n_targets, mem, cand, n_cand, out_mem);
+    return batch_form(check_fuse_candidates, launch_fuse_candidates, device, mem == MSL_MEM_DEVICE, n_tab, cap, n_pts, n_items, tcap, lcap, held_id,
+                      n_kps, pt_flags, targets, n_targets, mem, cand, n_cand, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -407,8 +424,9 @@ int msl_fuse_map_points(msl_match *h, int n_tab, int cap, int n_pts, int n_items
                         const int32_t *cand, const int32_t *n_cand, msl_mem mem, int32_t *best_idx, int32_t *best_dist, uint8_t *status,
                         int32_t *other, int32_t *n_fused, msl_mem out_mem) noexcept {
     try {
-    return run_fuse(h, n_tab, cap, n_pts, n_items, n_lists, lcap, params, kps_un, uright, grid_cell, desc, n_kps, Tcw, held_id, pt_xyz, pt_normal, pt_dist,
-                    pt_desc, pt_flags, pt_nobs, tgt, list, cand, n_cand, mem, best_idx, best_dist, status, other, n_fused, out_mem);
+    return handle_form(WHO_FUSE, check_fuse, launch_fuse, h, n_tab, cap, n_pts, n_items, n_lists, lcap, params, kps_un, uright, grid_cell, desc, n_kps,
+                       Tcw, held_id, pt_xyz, pt_normal, pt_dist, pt_desc, pt_flags, pt_nobs, tgt, list, cand, n_cand, mem, best_idx, best_dist, status,
+                       other, n_fused, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -419,9 +437,9 @@ int msl_fuse_map_points_batch(int device, int n_tab, int cap, int n_pts, int n_i
                               const int32_t *cand, const int32_t *n_cand, msl_mem mem, int32_t *best_idx, int32_t *best_dist, uint8_t *status,
                               int32_t *other, int32_t *n_fused, msl_mem out_mem) noexcept {
     try {
-    return abi_call_default(run_fuse, device, mem == MSL_MEM_DEVICE, n_tab, cap, n_pts, n_items, n_lists, lcap, params, kps_un, uright, grid_cell, desc,
-                            n_kps, Tcw, held_id, pt_xyz, pt_normal, pt_dist, pt_desc, pt_flags, pt_nobs, tgt, list, cand, n_cand, mem, best_idx, best_dist,
-                            status, other, n_fused, out_mem);
+    return batch_form(check_fuse, launch_fuse, device, mem == MSL_MEM_DEVICE, n_tab, cap, n_pts, n_items, n_lists, lcap, params, kps_un, uright,
+                      grid_cell, desc, n_kps, Tcw, held_id, pt_xyz, pt_normal, pt_dist, pt_desc, pt_flags, pt_nobs, tgt, list, cand, n_cand, mem, best_idx,
+                      best_dist, status, other, n_fused, out_mem);
     } MSL_ABI_CATCH_INT
 }
 

@@ -20,7 +20,7 @@
 // NO_FEATURE, a list outside the lists is empty.
 #include "msl_fuse_list.h"
 #include "msl_line_project.h"
-#include "msl_mappoint_check.h"
+#include "msl_index_check.h"
 #include "msl_obs_walk.h"
 
 #include <algorithm>
@@ -304,23 +304,32 @@ __global__ __launch_bounds__(WAVE) void k_line_refresh(LrDev D) {
 }
 
 // ==== host side ==============================================================================================================================
-int run_line_fuse(msl_match *h, int n_tab, int klcap, int n_lines, int n_items, int n_lists, int lcap, const msl_line_fuse_params *prm,
-                  const msl_keyline *kl, const uint8_t *ldesc, const int32_t *n_kl, const float *Tcw, const int32_t *held_id, const double *ln_xyz,
-                  const double *ln_normal, const float *ln_dist, const uint8_t *ln_desc, const uint8_t *ln_flags, const int32_t *ln_nobs,
-                  const int32_t *tgt, const int32_t *list, const int32_t *cand, const int32_t *n_cand, msl_mem mem, int32_t *best_idx,
-                  int32_t *best_dist, uint8_t *status, int32_t *other, int32_t *n_fused, msl_mem out_mem) {
-    const char *who = "msl_fuse_map_lines";
-    if (!h || !prm || !kl || !ldesc || !n_kl || !Tcw || !held_id || !ln_xyz || !ln_normal || !ln_dist || !ln_desc || !ln_flags || !ln_nobs || !tgt ||
-        !list || !cand || !n_cand || !best_idx || !best_dist || !status || !other || !n_fused) {
-        set_error("%s: invalid argument (null pointer)", who);
-        return MSL_ERR_INVALID;
-    }
+const char *const WHO_LFUSE = "msl_fuse_map_lines", *const WHO_LREFRESH = "msl_refresh_map_lines";
+
+int check_line_fuse(int n_tab, int klcap, int n_lines, int n_items, int n_lists, int lcap, const msl_line_fuse_params *params, const msl_keyline *kl,
+                    const uint8_t *ldesc, const int32_t *n_kl, const float *Tcw, const int32_t *held_id, const double *ln_xyz,
+                    const double *ln_normal, const float *ln_dist, const uint8_t *ln_desc, const uint8_t *ln_flags, const int32_t *ln_nobs,
+                    const int32_t *tgt, const int32_t *list, const int32_t *cand, const int32_t *n_cand, msl_mem mem, int32_t *best_idx,
+                    int32_t *best_dist, uint8_t *status, int32_t *other, int32_t *n_fused, msl_mem) {
+    const char *who = WHO_LFUSE;
+    if (!none_null(who, {MSL_NAMED(params), MSL_NAMED(kl), MSL_NAMED(ldesc), MSL_NAMED(n_kl), MSL_NAMED(Tcw), MSL_NAMED(held_id), MSL_NAMED(ln_xyz),
+                         MSL_NAMED(ln_normal), MSL_NAMED(ln_dist), MSL_NAMED(ln_desc), MSL_NAMED(ln_flags), MSL_NAMED(ln_nobs), MSL_NAMED(tgt),
+                         MSL_NAMED(list), MSL_NAMED(cand), MSL_NAMED(n_cand), MSL_NAMED(best_idx), MSL_NAMED(best_dist), MSL_NAMED(status),
+                         MSL_NAMED(other), MSL_NAMED(n_fused)})) return MSL_ERR_INVALID;
     if (!line_table_limits(who, n_tab, klcap, n_lines) || !item_limits(who, n_items, lcap)) return MSL_ERR_INVALID;
     if (n_lists < 1) { set_error("%s: n_lists %d below 1", who, n_lists); return MSL_ERR_INVALID; }
-    if (!levels_ok(who, prm->nlevels)) return MSL_ERR_INVALID;
-    if (prm->th_low < 0 || prm->th_low > 256) { set_error("%s: th_low %d outside 0 .. 256", who, prm->th_low); return MSL_ERR_INVALID; }
+    if (!levels_ok(who, params->nlevels)) return MSL_ERR_INVALID;
+    if (params->th_low < 0 || params->th_low > 256) { set_error("%s: th_low %d outside 0 .. 256", who, params->th_low); return MSL_ERR_INVALID; }
     char why[256];
-    if (mem == MSL_MEM_HOST && !mappoint::lists_ok("line", n_tab, n_lines, n_items, n_lists, lcap, tgt, list, cand, n_cand, why, sizeof(why))) return refuse(who, why);
+    if (mem == MSL_MEM_HOST && !check::lists_ok("line", n_tab, n_lines, n_items, n_lists, lcap, tgt, list, cand, n_cand, why, sizeof(why))) return refuse(who, why);
+    return MSL_OK;
+}
+
+int launch_line_fuse(msl_match *h, int n_tab, int klcap, int n_lines, int n_items, int n_lists, int lcap, const msl_line_fuse_params *prm,
+                     const msl_keyline *kl, const uint8_t *ldesc, const int32_t *n_kl, const float *Tcw, const int32_t *held_id, const double *ln_xyz,
+                     const double *ln_normal, const float *ln_dist, const uint8_t *ln_desc, const uint8_t *ln_flags, const int32_t *ln_nobs,
+                     const int32_t *tgt, const int32_t *list, const int32_t *cand, const int32_t *n_cand, msl_mem mem, int32_t *best_idx,
+                     int32_t *best_dist, uint8_t *status, int32_t *other, int32_t *n_fused, msl_mem out_mem) {
     int rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
     hipStream_t st = h->stream;
@@ -350,23 +359,28 @@ int run_line_fuse(msl_match *h, int n_tab, int klcap, int n_lines, int n_items, 
     return MSL_OK;
 }
 
-int run_line_refresh(msl_match *h, int n_tab, int klcap, int n_lines, int n_items, int n_obs_total, const msl_refresh_params *prm,
-                     const msl_keyline *kl, const int32_t *n_kl, const float *Tcw, const int32_t *obs_off, const int32_t *obs_kf,
-                     const int32_t *obs_idx, const double *ln_xyz, const uint8_t *ln_flags, const int32_t *ln_ref, const int32_t *ids, msl_mem mem,
-                     double *out_normal, float *out_dist, uint8_t *status, double *ln_normal, float *ln_dist, msl_mem out_mem) {
-    const char *who = "msl_refresh_map_lines";
-    if (!h || !prm || !kl || !n_kl || !Tcw || !obs_off || !obs_kf || !obs_idx || !ln_xyz || !ln_flags || !ln_ref || !ids || !out_normal ||
-        !out_dist || !status) {
-        set_error("%s: invalid argument (null pointer)", who);
-        return MSL_ERR_INVALID;
-    }
+int check_line_refresh(int n_tab, int klcap, int n_lines, int n_items, int n_obs_total, const msl_refresh_params *params, const msl_keyline *kl,
+                       const int32_t *n_kl, const float *Tcw, const int32_t *obs_off, const int32_t *obs_kf, const int32_t *obs_idx,
+                       const double *ln_xyz, const uint8_t *ln_flags, const int32_t *ln_ref, const int32_t *ids, msl_mem mem, double *out_normal,
+                       float *out_dist, uint8_t *status, double *, float *, msl_mem) {
+    const char *who = WHO_LREFRESH;
+    if (!none_null(who, {MSL_NAMED(params), MSL_NAMED(kl), MSL_NAMED(n_kl), MSL_NAMED(Tcw), MSL_NAMED(obs_off), MSL_NAMED(obs_kf), MSL_NAMED(obs_idx),
+                         MSL_NAMED(ln_xyz), MSL_NAMED(ln_flags), MSL_NAMED(ln_ref), MSL_NAMED(ids), MSL_NAMED(out_normal), MSL_NAMED(out_dist),
+                         MSL_NAMED(status)})) return MSL_ERR_INVALID;
     if (!line_table_limits(who, n_tab, klcap, n_lines)) return MSL_ERR_INVALID;
     if (n_obs_total < 0) { set_error("%s: n_obs_total %d below 0", who, n_obs_total); return MSL_ERR_INVALID; }
     if (n_items < 1 || n_items > n_lines) { set_error("%s: n_items %d outside 1 .. n_lines = %d", who, n_items, n_lines); return MSL_ERR_INVALID; }
-    if (!levels_ok(who, prm->nlevels)) return MSL_ERR_INVALID;
+    if (!levels_ok(who, params->nlevels)) return MSL_ERR_INVALID;
     char why[256];
-    if (mem == MSL_MEM_HOST && (!mappoint::csr_ok(n_tab, klcap, n_lines, n_obs_total, obs_off, obs_kf, obs_idx, n_kl, why, sizeof(why)) ||
-                                !mappoint::items_ok("ids", n_lines, n_items, ids, true, why, sizeof(why)))) return refuse(who, why);
+    if (mem == MSL_MEM_HOST && (!check::csr_ok(n_tab, klcap, n_lines, n_obs_total, obs_off, obs_kf, obs_idx, n_kl, why, sizeof(why)) ||
+                                !check::items_ok("ids", n_lines, n_items, ids, true, why, sizeof(why)))) return refuse(who, why);
+    return MSL_OK;
+}
+
+int launch_line_refresh(msl_match *h, int n_tab, int klcap, int n_lines, int n_items, int n_obs_total, const msl_refresh_params *prm,
+                        const msl_keyline *kl, const int32_t *, const float *Tcw, const int32_t *obs_off, const int32_t *obs_kf,
+                        const int32_t *obs_idx, const double *ln_xyz, const uint8_t *ln_flags, const int32_t *ln_ref, const int32_t *ids, msl_mem mem,
+                        double *out_normal, float *out_dist, uint8_t *status, double *ln_normal, float *ln_dist, msl_mem out_mem) {
     int rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
     const size_t T = (size_t)n_tab, nt = T * klcap, F = (size_t)n_items, nl = (size_t)n_lines, no = (size_t)n_obs_total;
@@ -396,8 +410,9 @@ int msl_fuse_map_lines(msl_match *h, int n_tab, int klcap, int n_lines, int n_it
                        const int32_t *ln_nobs, const int32_t *tgt, const int32_t *list, const int32_t *cand, const int32_t *n_cand, msl_mem mem,
                        int32_t *best_idx, int32_t *best_dist, uint8_t *status, int32_t *other, int32_t *n_fused, msl_mem out_mem) noexcept {
     try {
-    return run_line_fuse(h, n_tab, klcap, n_lines, n_items, n_lists, lcap, params, kl, ldesc, n_kl, Tcw, held_id, ln_xyz, ln_normal, ln_dist, ln_desc,
-                         ln_flags, ln_nobs, tgt, list, cand, n_cand, mem, best_idx, best_dist, status, other, n_fused, out_mem);
+    return handle_form(WHO_LFUSE, check_line_fuse, launch_line_fuse, h, n_tab, klcap, n_lines, n_items, n_lists, lcap, params, kl, ldesc, n_kl, Tcw,
+                       held_id, ln_xyz, ln_normal, ln_dist, ln_desc, ln_flags, ln_nobs, tgt, list, cand, n_cand, mem, best_idx, best_dist, status, other,
+                       n_fused, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -408,9 +423,9 @@ int msl_fuse_map_lines_batch(int device, int n_tab, int klcap, int n_lines, int 
                              msl_mem mem, int32_t *best_idx, int32_t *best_dist, uint8_t *status, int32_t *other, int32_t *n_fused,
                              msl_mem out_mem) noexcept {
     try {
-    return abi_call_default(run_line_fuse, device, mem == MSL_MEM_DEVICE, n_tab, klcap, n_lines, n_items, n_lists, lcap, params, kl, ldesc, n_kl, Tcw,
-                            held_id, ln_xyz, ln_normal, ln_dist, ln_desc, ln_flags, ln_nobs, tgt, list, cand, n_cand, mem, best_idx, best_dist, status,
-                            other, n_fused, out_mem);
+    return batch_form(check_line_fuse, launch_line_fuse, device, mem == MSL_MEM_DEVICE, n_tab, klcap, n_lines, n_items, n_lists, lcap, params, kl,
+                      ldesc, n_kl, Tcw, held_id, ln_xyz, ln_normal, ln_dist, ln_desc, ln_flags, ln_nobs, tgt, list, cand, n_cand, mem, best_idx, best_dist,
+                      status, other, n_fused, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -420,8 +435,8 @@ int msl_refresh_map_lines(msl_match *h, int n_tab, int klcap, int n_lines, int n
                           msl_mem mem, double *out_normal, float *out_dist, uint8_t *status, double *ln_normal, float *ln_dist,
                           msl_mem out_mem) noexcept {
     try {
-    return run_line_refresh(h, n_tab, klcap, n_lines, n_items, n_obs_total, params, kl, n_kl, Tcw, obs_off, obs_kf, obs_idx, ln_xyz, ln_flags, ln_ref,
-                            ids, mem, out_normal, out_dist, status, ln_normal, ln_dist, out_mem);
+    return handle_form(WHO_LREFRESH, check_line_refresh, launch_line_refresh, h, n_tab, klcap, n_lines, n_items, n_obs_total, params, kl, n_kl, Tcw,
+                       obs_off, obs_kf, obs_idx, ln_xyz, ln_flags, ln_ref, ids, mem, out_normal, out_dist, status, ln_normal, ln_dist, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -431,9 +446,9 @@ int msl_refresh_map_lines_batch(int device, int n_tab, int klcap, int n_lines, i
                                 msl_mem mem, double *out_normal, float *out_dist, uint8_t *status, double *ln_normal, float *ln_dist,
                                 msl_mem out_mem) noexcept {
     try {
-    const bool reads = mem == MSL_MEM_DEVICE || ((ln_normal || ln_dist) && out_mem == MSL_MEM_DEVICE);
-    return abi_call_default(run_line_refresh, device, reads, n_tab, klcap, n_lines, n_items, n_obs_total, params, kl, n_kl, Tcw, obs_off, obs_kf,
-                            obs_idx, ln_xyz, ln_flags, ln_ref, ids, mem, out_normal, out_dist, status, ln_normal, ln_dist, out_mem);
+    return batch_form(check_line_refresh, launch_line_refresh, device, mem == MSL_MEM_DEVICE || ((ln_normal || ln_dist) && out_mem == MSL_MEM_DEVICE),
+                      n_tab, klcap, n_lines, n_items, n_obs_total, params, kl, n_kl, Tcw, obs_off, obs_kf, obs_idx, ln_xyz, ln_flags, ln_ref, ids, mem,
+                      out_normal, out_dist, status, ln_normal, ln_dist, out_mem);
     } MSL_ABI_CATCH_INT
 }
 

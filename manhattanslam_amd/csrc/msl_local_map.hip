@@ -14,8 +14,7 @@
 // The stamps are all ones before k_lm_stamp; frames run in groups whose stamps stay under the handle's budget.
 // Pins (tests/localmap_model.py is the sequential model): msl.h's list; device-only: an index outside its table is absent.
 #include "msl_match_handle.h"
-#include "msl_local_map_check.h"
-#include "msl_mappoint_check.h"
+#include "msl_index_check.h"
 #include "msl_obs_walk.h"
 
 #include <type_traits>
@@ -252,14 +251,6 @@ __global__ __launch_bounds__(LM_NT) void k_lm_write(LocalMapDev D, LocalRows<W> 
 }
 
 // ==== host side ==============================================================================================================================
-struct Named { const char *name; const void *p; };
-bool none_null(const char *who, std::initializer_list<Named> args) {
-    for (const Named &a : args)
-        if (!a.p) { set_error("%s: %s is NULL", who, a.name); return false; }
-    return true;
-}
-#define MSL_NAMED(x) Named{#x, x}
-
 bool frames_ok(const char *who, int n_frames) {
     if (n_frames < 1) { set_error("%s: n_frames %d below 1", who, n_frames); return false; }
     return true;
@@ -284,10 +275,10 @@ int check_keyframes(int n_frames, int cap, int n_tab, int n_pts, int n_obs_total
     if (n_obs_total < 0) { set_error("%s: n_obs_total %d below 0", who, n_obs_total); return MSL_ERR_INVALID; }
     if (ccap < 1 || ccap > n_tab) { set_error("%s: ccap %d outside 1 .. n_tab = %d", who, ccap, n_tab); return MSL_ERR_INVALID; }
     char why[256];
-    if (mem == MSL_MEM_HOST && (!mappoint::csr_ok(n_tab, cap, n_pts, n_obs_total, obs_off, obs_kf, nullptr, nullptr, why, sizeof(why)) ||
-                                !localmap::held_ok("cur_held", "n_cur", n_frames, cap, n_pts, cur_held, n_cur, why, sizeof(why)) ||
-                                !localmap::graph_ok(n_tab, ccap, conn, n_conn, parent, why, sizeof(why)) ||
-                                (prev_kf && !localmap::list_ok("prev_kf", "n_prev", n_frames, n_tab, prev_kf, n_prev, why, sizeof(why)))))
+    if (mem == MSL_MEM_HOST && (!check::csr_ok(n_tab, cap, n_pts, n_obs_total, obs_off, obs_kf, nullptr, nullptr, why, sizeof(why)) ||
+                                !check::held_ok("cur_held", "n_cur", n_frames, cap, n_pts, cur_held, n_cur, why, sizeof(why)) ||
+                                !check::graph_ok(n_tab, ccap, conn, n_conn, parent, why, sizeof(why)) ||
+                                (prev_kf && !check::kf_rows_ok("prev_kf", "n_prev", "n_tab", n_frames, n_tab, n_tab, prev_kf, n_prev, why, sizeof(why)))))
         return refuse(who, why);
     return MSL_OK;
 }
@@ -334,8 +325,8 @@ int check_rows(const RowNames &N, int n_frames, int n_tab, int fcap, int n_ids, 
                            {N.curFlags, cur_flags}})) return MSL_ERR_INVALID;
     if (!frames_ok(N.who, n_frames) || !mcap_ok(N.who, N.mcap, mcap)) return MSL_ERR_INVALID;
     char why[256];
-    if (mem == MSL_MEM_HOST && (!localmap::list_ok("local_kf", "n_local_kf", n_frames, n_tab, local_kf, n_local_kf, why, sizeof(why)) ||
-                                !localmap::held_ok(N.cur, N.nCur, n_frames, fcap, n_ids, cur, n_cur, why, sizeof(why)))) return refuse(N.who, why);
+    if (mem == MSL_MEM_HOST && (!check::kf_rows_ok("local_kf", "n_local_kf", "n_tab", n_frames, n_tab, n_tab, local_kf, n_local_kf, why, sizeof(why)) ||
+                                !check::held_ok(N.cur, N.nCur, n_frames, fcap, n_ids, cur, n_cur, why, sizeof(why)))) return refuse(N.who, why);
     return MSL_OK;
 }
 
@@ -418,19 +409,6 @@ int launch_lines(msl_match *h, int n_frames, int n_tab, int klcap, int lcap, int
     return launch_rows<double, 6>(h, n_frames, n_tab, klcap, lcap, n_lines, mlcap, local_kf, n_local_kf, lheld_id, n_kl, cur_lheld, n_cur_lines,
                                   ln_xyz, ln_normal, ln_dist, ln_desc, ln_flags, ln_nobs, mem, local_line_id, n_local_lines, ml_xyz, ml_normal,
                                   ml_dist, ml_desc, ml_flags, cur_line_flags, out_mem);
-}
-
-// The two forms of an entry: the checks come first and need no device, so a refusal is made before the handle is touched
-template <class Check, class Launch, class... A>
-int handle_form(const char *who, Check check, Launch launch, msl_match *h, A... a) {
-    if (!h) { set_error("%s: h is NULL", who); return MSL_ERR_INVALID; }
-    const int rc = check(a...);
-    return rc != MSL_OK ? rc : launch(h, a...);
-}
-template <class Check, class Launch, class... A>
-int batch_form(Check check, Launch launch, int device, bool sync_legacy, A... a) {
-    const int rc = check(a...);
-    return rc != MSL_OK ? rc : abi_call_default(launch, device, sync_legacy, a...);
 }
 
 }  // namespace

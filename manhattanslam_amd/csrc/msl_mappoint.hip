@@ -15,7 +15,7 @@
 // keyframe is outside the table is skipped as if absent, one whose keypoint index is outside [0, cap) has no descriptor; an id outside the
 // point table is a bad point; a pt_ref outside the table, or a reference keypoint outside [0, cap), leaves as MSL_REFRESH_BAD_OCTAVE.
 #include "msl_match_handle.h"
-#include "msl_mappoint_check.h"
+#include "msl_index_check.h"
 #include "msl_obs_walk.h"
 
 namespace {
@@ -220,28 +220,38 @@ bool csr_limits(const char *who, int n_tab, int cap, int n_pts, int n_obs_total)
     return true;
 }
 
-int run_refresh(msl_match *h, int n_tab, int cap, int n_pts, int n_items, int n_obs_total, int what, const msl_refresh_params *prm,
-                const msl_keypoint *kps_un, const uint8_t *desc, const int32_t *n_kps, const float *Tcw, const uint8_t *kf_flags,
-                const int32_t *obs_off, const int32_t *obs_kf, const int32_t *obs_idx, const float *pt_xyz, const uint8_t *pt_flags,
-                const int32_t *pt_ref, const int32_t *ids, msl_mem mem, uint8_t *out_desc, float *out_normal, float *out_dist, int32_t *best_obs,
-                int32_t *best_median, uint8_t *status, uint8_t *pt_desc, float *pt_normal, float *pt_dist, msl_mem out_mem) {
-    const char *who = "msl_refresh_map_points";
+const char *const WHO_REFRESH = "msl_refresh_map_points", *const WHO_COVIS = "msl_covisibility";
+
+int check_refresh(int n_tab, int cap, int n_pts, int n_items, int n_obs_total, int what, const msl_refresh_params *params,
+                  const msl_keypoint *kps_un, const uint8_t *desc, const int32_t *n_kps, const float *Tcw, const uint8_t *kf_flags,
+                  const int32_t *obs_off, const int32_t *obs_kf, const int32_t *obs_idx, const float *pt_xyz, const uint8_t *pt_flags,
+                  const int32_t *pt_ref, const int32_t *ids, msl_mem mem, uint8_t *out_desc, float *out_normal, float *out_dist, int32_t *best_obs,
+                  int32_t *best_median, uint8_t *status, uint8_t *, float *, float *, msl_mem) {
+    const char *who = WHO_REFRESH;
     if (what < 1 || what > (MSL_REFRESH_DESC | MSL_REFRESH_NORMAL)) { set_error("%s: what %d outside the mask MSL_REFRESH_DESC | MSL_REFRESH_NORMAL", who, what); return MSL_ERR_INVALID; }
-    const bool wantD = what & MSL_REFRESH_DESC, wantN = what & MSL_REFRESH_NORMAL;
-    if (!h || !prm || !desc || !n_kps || !kf_flags || !obs_off || !obs_kf || !obs_idx || !pt_flags || !ids || !out_desc || !out_normal || !out_dist ||
-        !best_obs || !best_median || !status || (wantN && (!kps_un || !Tcw || !pt_xyz || !pt_ref))) {
-        set_error("%s: invalid argument (null pointer)", who);
-        return MSL_ERR_INVALID;
-    }
+    const bool wantN = what & MSL_REFRESH_NORMAL;
+    if (!none_null(who, {MSL_NAMED(params), MSL_NAMED(desc), MSL_NAMED(n_kps), MSL_NAMED(kf_flags), MSL_NAMED(obs_off), MSL_NAMED(obs_kf),
+                         MSL_NAMED(obs_idx), MSL_NAMED(pt_flags), MSL_NAMED(ids), MSL_NAMED(out_desc), MSL_NAMED(out_normal), MSL_NAMED(out_dist),
+                         MSL_NAMED(best_obs), MSL_NAMED(best_median), MSL_NAMED(status)})) return MSL_ERR_INVALID;
+    if (wantN && !none_null(who, {MSL_NAMED(kps_un), MSL_NAMED(Tcw), MSL_NAMED(pt_xyz), MSL_NAMED(pt_ref)})) return MSL_ERR_INVALID;
     if (!csr_limits(who, n_tab, cap, n_pts, n_obs_total)) return MSL_ERR_INVALID;
     if (n_items < 1 || n_items > n_pts) { set_error("%s: n_items %d outside 1 .. n_pts = %d", who, n_items, n_pts); return MSL_ERR_INVALID; }
-    if (wantN && !levels_ok(who, prm->nlevels)) return MSL_ERR_INVALID;
+    if (wantN && !levels_ok(who, params->nlevels)) return MSL_ERR_INVALID;
     char why[256];
-    if (mem == MSL_MEM_HOST && (!mappoint::csr_ok(n_tab, cap, n_pts, n_obs_total, obs_off, obs_kf, obs_idx, n_kps, why, sizeof(why)) ||
-                                !mappoint::items_ok("ids", n_pts, n_items, ids, true, why, sizeof(why)) ||
-                                (wantN && !mappoint::refs_ok(n_tab, n_items, ids, pt_ref, why, sizeof(why))))) return refuse(who, why);
+    if (mem == MSL_MEM_HOST && (!check::csr_ok(n_tab, cap, n_pts, n_obs_total, obs_off, obs_kf, obs_idx, n_kps, why, sizeof(why)) ||
+                                !check::items_ok("ids", n_pts, n_items, ids, true, why, sizeof(why)) ||
+                                (wantN && !check::refs_ok(n_tab, n_items, ids, pt_ref, why, sizeof(why))))) return refuse(who, why);
+    return MSL_OK;
+}
+
+int launch_refresh(msl_match *h, int n_tab, int cap, int n_pts, int n_items, int n_obs_total, int what, const msl_refresh_params *prm,
+                   const msl_keypoint *kps_un, const uint8_t *desc, const int32_t *, const float *Tcw, const uint8_t *kf_flags,
+                   const int32_t *obs_off, const int32_t *obs_kf, const int32_t *obs_idx, const float *pt_xyz, const uint8_t *pt_flags,
+                   const int32_t *pt_ref, const int32_t *ids, msl_mem mem, uint8_t *out_desc, float *out_normal, float *out_dist, int32_t *best_obs,
+                   int32_t *best_median, uint8_t *status, uint8_t *pt_desc, float *pt_normal, float *pt_dist, msl_mem out_mem) {
     int rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
+    const bool wantD = what & MSL_REFRESH_DESC, wantN = what & MSL_REFRESH_NORMAL;
     const size_t T = (size_t)n_tab, nt = T * cap, F = (size_t)n_items, np = (size_t)n_pts, no = (size_t)n_obs_total;
     RefreshDev D{};
     D.nTab = n_tab; D.cap = cap; D.nPts = n_pts; D.nObs = n_obs_total; D.what = what;
@@ -262,20 +272,24 @@ int run_refresh(msl_match *h, int n_tab, int cap, int n_pts, int n_items, int n_
     return MSL_OK;
 }
 
-int run_covisibility(msl_match *h, int n_tab, int cap, int n_pts, int n_items, int n_obs_total, int ccap, int th, const int32_t *held_id,
-                     const int32_t *n_kps, const uint8_t *pt_flags, const int32_t *obs_off, const int32_t *obs_kf, const int32_t *kf, msl_mem mem,
-                     int32_t *weight, int32_t *conn, int32_t *conn_w, int32_t *n_conn, msl_mem out_mem) {
-    const char *who = "msl_covisibility";
-    if (!h || !held_id || !n_kps || !pt_flags || !obs_off || !obs_kf || !kf || !weight || !conn || !conn_w || !n_conn) {
-        set_error("%s: invalid argument (null pointer)", who);
-        return MSL_ERR_INVALID;
-    }
+int check_covisibility(int n_tab, int cap, int n_pts, int n_items, int n_obs_total, int ccap, int, const int32_t *held_id, const int32_t *n_kps,
+                       const uint8_t *pt_flags, const int32_t *obs_off, const int32_t *obs_kf, const int32_t *kf, msl_mem mem, int32_t *weight,
+                       int32_t *conn, int32_t *conn_w, int32_t *n_conn, msl_mem) {
+    const char *who = WHO_COVIS;
+    if (!none_null(who, {MSL_NAMED(held_id), MSL_NAMED(n_kps), MSL_NAMED(pt_flags), MSL_NAMED(obs_off), MSL_NAMED(obs_kf), MSL_NAMED(kf),
+                         MSL_NAMED(weight), MSL_NAMED(conn), MSL_NAMED(conn_w), MSL_NAMED(n_conn)})) return MSL_ERR_INVALID;
     if (!csr_limits(who, n_tab, cap, n_pts, n_obs_total)) return MSL_ERR_INVALID;
     if (n_items < 1 || n_items > n_tab) { set_error("%s: n_items %d outside 1 .. n_tab = %d", who, n_items, n_tab); return MSL_ERR_INVALID; }
     if (ccap < 1 || ccap > n_tab) { set_error("%s: ccap %d outside 1 .. n_tab = %d", who, ccap, n_tab); return MSL_ERR_INVALID; }
     char why[256];
-    if (mem == MSL_MEM_HOST && (!mappoint::csr_ok(n_tab, cap, n_pts, n_obs_total, obs_off, obs_kf, nullptr, n_kps, why, sizeof(why)) ||
-                                !mappoint::items_ok("kf", n_tab, n_items, kf, false, why, sizeof(why)))) return refuse(who, why);
+    if (mem == MSL_MEM_HOST && (!check::csr_ok(n_tab, cap, n_pts, n_obs_total, obs_off, obs_kf, nullptr, n_kps, why, sizeof(why)) ||
+                                !check::items_ok("kf", n_tab, n_items, kf, false, why, sizeof(why)))) return refuse(who, why);
+    return MSL_OK;
+}
+
+int launch_covisibility(msl_match *h, int n_tab, int cap, int n_pts, int n_items, int n_obs_total, int ccap, int th, const int32_t *held_id,
+                        const int32_t *n_kps, const uint8_t *pt_flags, const int32_t *obs_off, const int32_t *obs_kf, const int32_t *kf,
+                        msl_mem mem, int32_t *weight, int32_t *conn, int32_t *conn_w, int32_t *n_conn, msl_mem out_mem) {
     int rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
     const size_t T = (size_t)n_tab, F = (size_t)n_items, np = (size_t)n_pts, no = (size_t)n_obs_total;
@@ -303,8 +317,9 @@ int msl_refresh_map_points(msl_match *h, int n_tab, int cap, int n_pts, int n_it
                            int32_t *best_obs, int32_t *best_median, uint8_t *status, uint8_t *pt_desc, float *pt_normal, float *pt_dist,
                            msl_mem out_mem) noexcept {
     try {
-    return run_refresh(h, n_tab, cap, n_pts, n_items, n_obs_total, what, params, kps_un, desc, n_kps, Tcw, kf_flags, obs_off, obs_kf, obs_idx, pt_xyz,
-                       pt_flags, pt_ref, ids, mem, out_desc, out_normal, out_dist, best_obs, best_median, status, pt_desc, pt_normal, pt_dist, out_mem);
+    return handle_form(WHO_REFRESH, check_refresh, launch_refresh, h, n_tab, cap, n_pts, n_items, n_obs_total, what, params, kps_un, desc, n_kps, Tcw,
+                       kf_flags, obs_off, obs_kf, obs_idx, pt_xyz, pt_flags, pt_ref, ids, mem, out_desc, out_normal, out_dist, best_obs, best_median,
+                       status, pt_desc, pt_normal, pt_dist, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -315,9 +330,9 @@ int msl_refresh_map_points_batch(int device, int n_tab, int cap, int n_pts, int 
                                  float *out_normal, float *out_dist, int32_t *best_obs, int32_t *best_median, uint8_t *status, uint8_t *pt_desc,
                                  float *pt_normal, float *pt_dist, msl_mem out_mem) noexcept {
     try {
-    return abi_call_default(run_refresh, device, mem == MSL_MEM_DEVICE, n_tab, cap, n_pts, n_items, n_obs_total, what,
-                            params, kps_un, desc, n_kps, Tcw, kf_flags, obs_off, obs_kf, obs_idx, pt_xyz, pt_flags, pt_ref, ids, mem, out_desc,
-                            out_normal, out_dist, best_obs, best_median, status, pt_desc, pt_normal, pt_dist, out_mem);
+    return batch_form(check_refresh, launch_refresh, device, mem == MSL_MEM_DEVICE, n_tab, cap, n_pts, n_items, n_obs_total, what, params, kps_un,
+                      desc, n_kps, Tcw, kf_flags, obs_off, obs_kf, obs_idx, pt_xyz, pt_flags, pt_ref, ids, mem, out_desc, out_normal, out_dist, best_obs,
+                      best_median, status, pt_desc, pt_normal, pt_dist, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -325,8 +340,8 @@ int msl_covisibility(msl_match *h, int n_tab, int cap, int n_pts, int n_items, i
                      const int32_t *n_kps, const uint8_t *pt_flags, const int32_t *obs_off, const int32_t *obs_kf, const int32_t *kf, msl_mem mem,
                      int32_t *weight, int32_t *conn, int32_t *conn_w, int32_t *n_conn, msl_mem out_mem) noexcept {
     try {
-    return run_covisibility(h, n_tab, cap, n_pts, n_items, n_obs_total, ccap, th, held_id, n_kps, pt_flags, obs_off, obs_kf, kf, mem, weight, conn,
-                            conn_w, n_conn, out_mem);
+    return handle_form(WHO_COVIS, check_covisibility, launch_covisibility, h, n_tab, cap, n_pts, n_items, n_obs_total, ccap, th, held_id, n_kps,
+                       pt_flags, obs_off, obs_kf, kf, mem, weight, conn, conn_w, n_conn, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -334,8 +349,8 @@ int msl_covisibility_batch(int device, int n_tab, int cap, int n_pts, int n_item
                            const int32_t *n_kps, const uint8_t *pt_flags, const int32_t *obs_off, const int32_t *obs_kf, const int32_t *kf,
                            msl_mem mem, int32_t *weight, int32_t *conn, int32_t *conn_w, int32_t *n_conn, msl_mem out_mem) noexcept {
     try {
-    return abi_call_default(run_covisibility, device, mem == MSL_MEM_DEVICE, n_tab, cap, n_pts, n_items, n_obs_total, ccap, th, held_id, n_kps,
-                            pt_flags, obs_off, obs_kf, kf, mem, weight, conn, conn_w, n_conn, out_mem);
+    return batch_form(check_covisibility, launch_covisibility, device, mem == MSL_MEM_DEVICE, n_tab, cap, n_pts, n_items, n_obs_total, ccap, th,
+                      held_id, n_kps, pt_flags, obs_off, obs_kf, kf, mem, weight, conn, conn_w, n_conn, out_mem);
     } MSL_ABI_CATCH_INT
 }
 

@@ -1,11 +1,13 @@
-// msl_match_handle.h -- the matcher handle, its staging of caller arrays (Stage), the forwarder of the *_batch entry points, the limits
-// that several entry points share (table_limits, line_table_limits, levels_ok) and the row readback of the debug entry points (last_call_row);
-// shared by msl_match.hip, msl_line_match.hip, msl_pose.hip, msl_plane.hip, msl_bow.hip, msl_reloc.hip, msl_pnp.hip, msl_line3d.hip,
-// msl_triangulate.hip, msl_fuse.hip, msl_mappoint.hip, msl_line_fuse.hip and msl_local_map.hip (internal).
+// msl_match_handle.h -- the matcher handle, its staging of caller arrays (Stage), the forwarder of the *_batch entry points, the two forms of
+// a LocalMapping entry (handle_form, batch_form) with the list of its NULLs (none_null), the limits that several entry points share
+// (table_limits, line_table_limits, levels_ok) and the row readback of the debug entry points (last_call_row); shared by msl_match.hip,
+// msl_line_match.hip, msl_pose.hip, msl_plane.hip, msl_bow.hip, msl_reloc.hip, msl_pnp.hip, msl_line3d.hip, msl_triangulate.hip, msl_fuse.hip,
+// msl_mappoint.hip, msl_line_fuse.hip, msl_local_map.hip and msl_cull.hip (internal).
 #pragma once
 
 #include "msl_common.h"
 
+#include <initializer_list>
 #include <vector>
 
 namespace msl {
@@ -39,8 +41,18 @@ inline bool levels_ok(const char *who, int nlevels) {
     return true;
 }
 
-// The refusal of a call whose host-side check (msl_mappoint_check.h) left its reason in why
+// The refusal of a call whose host-side check (msl_index_check.h) left its reason in why
 inline int refuse(const char *who, const char *why) { set_error("%s: %s", who, why); return MSL_ERR_INVALID; }
+
+// The arrays a call requires, by name: the first that is NULL is the refusal; false with the error set.  An optional array is left out of the
+// list, and arrays that a condition makes required are a second call under that condition.
+struct Named { const char *name; const void *p; };
+inline bool none_null(const char *who, std::initializer_list<Named> args) {
+    for (const Named &a : args)
+        if (!a.p) { set_error("%s: %s is NULL", who, a.name); return false; }
+    return true;
+}
+#define MSL_NAMED(x) Named{#x, x}
 }  // namespace msl
 
 // One matcher object = one ORBmatcher of the reference (src/ORBmatcher.cc:41): its own stream and its own scratch, used by one thread at a time;
@@ -111,6 +123,20 @@ int abi_call_default(Run run, int device, bool sync_legacy, A... a) {
     int rc = run(h, a...);
     if (rc == MSL_OK) rc = msl_match_sync(h);
     return rc;
+}
+
+// The two forms of a LocalMapping entry: check_x(args...) makes no HIP call and comes first, so a refusal is made before the handle, or
+// the device's shared one, is touched; launch_x(h, args...) starts at bind_device.
+template <class Check, class Launch, class... A>
+int handle_form(const char *who, Check check, Launch launch, msl_match *h, A... a) {
+    if (!h) { set_error("%s: h is NULL", who); return MSL_ERR_INVALID; }
+    const int rc = check(a...);
+    return rc != MSL_OK ? rc : launch(h, a...);
+}
+template <class Check, class Launch, class... A>
+int batch_form(Check check, Launch launch, int device, bool sync_legacy, A... a) {
+    const int rc = check(a...);
+    return rc != MSL_OK ? rc : abi_call_default(launch, device, sync_legacy, a...);
 }
 
 // What a debug entry point reads of the handle's last call: row `row` of the scratch `buf`, n records long, once the stream is drained.

@@ -38,7 +38,7 @@
 //   * a table index outside [0, n_tab), or a neighbour equal to the current keyframe, that only the device can see: that neighbour is
 //     skipped (an invalid current keyframe has no keypoints)
 #include "msl_jacobi.h"
-#include "msl_mappoint_check.h"
+#include "msl_index_check.h"
 #include "msl_match_handle.h"
 #include "msl_match_math.h"
 
@@ -441,24 +441,35 @@ __global__ __launch_bounds__(WAVE) void k_tri_walk(TriDev D) {
 }
 
 // ==== host side ==============================================================================================================================
-int run_triangulate(msl_match *h, int n_tab, int cap, int n_items, int ncap, const msl_triangulate_params *prm, const msl_keypoint *kps_un,
-                    const float *raw_xy, const float *uright, const float *depth, const uint8_t *desc, const int32_t *node, const uint8_t *held,
-                    const int32_t *n_kps, const float *Tcw, const int32_t *cur, const int32_t *neigh, const int32_t *n_neigh, msl_mem mem,
-                    int32_t *match12, uint8_t *status, int32_t *nmatches, int32_t *new_neigh, int32_t *new_idx2, float *new_xyz, float *new_normal,
-                    float *new_dist, uint8_t *new_desc, int32_t *new_order, int32_t *n_new, msl_mem out_mem) {
-    if (!h || n_tab < 1 || n_items < 1 || !prm || !kps_un || !raw_xy || !uright || !depth || !desc || !node || !held || !n_kps || !Tcw || !cur ||
-        !neigh || !n_neigh || !match12 || !status || !nmatches || !new_neigh || !new_idx2 || !new_xyz || !new_normal || !new_dist || !new_desc ||
-        !new_order || !n_new) {
-        set_error("msl_triangulate_new_points: invalid argument (null pointer, n_tab < 1 or n_items < 1)");
+const char *const WHO_TRI = "msl_triangulate_new_points";
+
+int check_triangulate(int n_tab, int cap, int n_items, int ncap, const msl_triangulate_params *params, const msl_keypoint *kps_un,
+                      const float *raw_xy, const float *uright, const float *depth, const uint8_t *desc, const int32_t *node, const uint8_t *held,
+                      const int32_t *n_kps, const float *Tcw, const int32_t *cur, const int32_t *neigh, const int32_t *n_neigh, msl_mem mem,
+                      int32_t *match12, uint8_t *status, int32_t *nmatches, int32_t *new_neigh, int32_t *new_idx2, float *new_xyz,
+                      float *new_normal, float *new_dist, uint8_t *new_desc, int32_t *new_order, int32_t *n_new, msl_mem) {
+    const char *who = WHO_TRI;
+    if (!none_null(who, {MSL_NAMED(params), MSL_NAMED(kps_un), MSL_NAMED(raw_xy), MSL_NAMED(uright), MSL_NAMED(depth), MSL_NAMED(desc),
+                         MSL_NAMED(node), MSL_NAMED(held), MSL_NAMED(n_kps), MSL_NAMED(Tcw), MSL_NAMED(cur), MSL_NAMED(neigh), MSL_NAMED(n_neigh),
+                         MSL_NAMED(match12), MSL_NAMED(status), MSL_NAMED(nmatches), MSL_NAMED(new_neigh), MSL_NAMED(new_idx2), MSL_NAMED(new_xyz),
+                         MSL_NAMED(new_normal), MSL_NAMED(new_dist), MSL_NAMED(new_desc), MSL_NAMED(new_order), MSL_NAMED(n_new)}))
         return MSL_ERR_INVALID;
-    }
-    if (cap < 1 || cap > MAX_CAP) { set_error("msl_triangulate_new_points: cap %d outside 1 .. %d", cap, MAX_CAP); return MSL_ERR_INVALID; }
-    if (ncap < 1 || ncap > MAX_NCAP) { set_error("msl_triangulate_new_points: ncap %d outside 1 .. %d", ncap, MAX_NCAP); return MSL_ERR_INVALID; }
-    if (n_items > 65535) { set_error("msl_triangulate_new_points: n_items %d above 65535", n_items); return MSL_ERR_INVALID; }
-    if (!levels_ok("msl_triangulate_new_points", prm->nlevels)) return MSL_ERR_INVALID;
+    if (n_tab < 1 || n_tab > MAX_TAB) { set_error("%s: n_tab %d outside 1 .. %d", who, n_tab, MAX_TAB); return MSL_ERR_INVALID; }
+    if (n_items < 1) { set_error("%s: n_items %d below 1", who, n_items); return MSL_ERR_INVALID; }
+    if (cap < 1 || cap > MAX_CAP) { set_error("%s: cap %d outside 1 .. %d", who, cap, MAX_CAP); return MSL_ERR_INVALID; }
+    if (ncap < 1 || ncap > MAX_NCAP) { set_error("%s: ncap %d outside 1 .. %d", who, ncap, MAX_NCAP); return MSL_ERR_INVALID; }
+    if (n_items > 65535) { set_error("%s: n_items %d above 65535", who, n_items); return MSL_ERR_INVALID; }
+    if (!levels_ok(who, params->nlevels)) return MSL_ERR_INVALID;
     char why[256];
-    if (mem == MSL_MEM_HOST && !mappoint::neighbours_ok(n_tab, n_items, ncap, cur, neigh, n_neigh, why, sizeof(why)))
-        return refuse("msl_triangulate_new_points", why);
+    if (mem == MSL_MEM_HOST && !check::neighbours_ok(n_tab, n_items, ncap, cur, neigh, n_neigh, why, sizeof(why))) return refuse(who, why);
+    return MSL_OK;
+}
+
+int launch_triangulate(msl_match *h, int n_tab, int cap, int n_items, int ncap, const msl_triangulate_params *prm, const msl_keypoint *kps_un,
+                       const float *raw_xy, const float *uright, const float *depth, const uint8_t *desc, const int32_t *node, const uint8_t *held,
+                       const int32_t *n_kps, const float *Tcw, const int32_t *cur, const int32_t *neigh, const int32_t *n_neigh, msl_mem mem,
+                       int32_t *match12, uint8_t *status, int32_t *nmatches, int32_t *new_neigh, int32_t *new_idx2, float *new_xyz,
+                       float *new_normal, float *new_dist, uint8_t *new_desc, int32_t *new_order, int32_t *n_new, msl_mem out_mem) {
     int rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
     hipStream_t st = h->stream;
@@ -505,8 +516,9 @@ int msl_triangulate_new_points(msl_match *h, int n_tab, int cap, int n_items, in
                                int32_t *new_neigh, int32_t *new_idx2, float *new_xyz, float *new_normal, float *new_dist, uint8_t *new_desc,
                                int32_t *new_order, int32_t *n_new, msl_mem out_mem) noexcept {
     try {
-    return run_triangulate(h, n_tab, cap, n_items, ncap, params, kps_un, raw_xy, uright, depth, desc, node, held, n_kps, Tcw, cur, neigh, n_neigh, mem,
-                           match12, status, nmatches, new_neigh, new_idx2, new_xyz, new_normal, new_dist, new_desc, new_order, n_new, out_mem);
+    return handle_form(WHO_TRI, check_triangulate, launch_triangulate, h, n_tab, cap, n_items, ncap, params, kps_un, raw_xy, uright, depth, desc, node,
+                       held, n_kps, Tcw, cur, neigh, n_neigh, mem, match12, status, nmatches, new_neigh, new_idx2, new_xyz, new_normal, new_dist,
+                       new_desc, new_order, n_new, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -517,9 +529,9 @@ int msl_triangulate_new_points_batch(int device, int n_tab, int cap, int n_items
                                      int32_t *nmatches, int32_t *new_neigh, int32_t *new_idx2, float *new_xyz, float *new_normal, float *new_dist,
                                      uint8_t *new_desc, int32_t *new_order, int32_t *n_new, msl_mem out_mem) noexcept {
     try {
-    return abi_call_default(run_triangulate, device, mem == MSL_MEM_DEVICE, n_tab, cap, n_items, ncap, params, kps_un, raw_xy, uright, depth, desc, node,
-                            held, n_kps, Tcw, cur, neigh, n_neigh, mem, match12, status, nmatches, new_neigh, new_idx2, new_xyz, new_normal, new_dist,
-                            new_desc, new_order, n_new, out_mem);
+    return batch_form(check_triangulate, launch_triangulate, device, mem == MSL_MEM_DEVICE, n_tab, cap, n_items, ncap, params, kps_un, raw_xy, uright,
+                      depth, desc, node, held, n_kps, Tcw, cur, neigh, n_neigh, mem, match12, status, nmatches, new_neigh, new_idx2, new_xyz, new_normal,
+                      new_dist, new_desc, new_order, n_new, out_mem);
     } MSL_ABI_CATCH_INT
 }
 

@@ -1,17 +1,16 @@
-// A plain C++ host program for the index checks of msl_cull_keyframes / msl_cull_recent (manhattanslam_amd/csrc/msl_cull_check.h, and the
-// observation table with obs_idx through msl_mappoint_check.h's csr_ok, as the entry calls it): every array is heap-allocated at exactly
+// A plain C++ host program for the index checks of msl_cull_keyframes / msl_cull_recent (manhattanslam_amd/csrc/msl_index_check.h, the
+// observation table with obs_idx through csr_ok included, as the entry calls it): every array is heap-allocated at exactly
 // its size, so a read past an end is the address sanitizer's to find; valid random arrays must pass, each single defect must be refused
 // with a message that names the field, and a count outside its capacity must be refused before any entry behind it is read.
 // Prints "<n> failures".
-#include "msl_cull_check.h"
-#include "msl_mappoint_check.h"
+#include "msl_index_check.h"
 
 #include <stdlib.h>
 #include <string.h>
 
 #include <random>
 
-using namespace msl::cull;
+using namespace msl::check;
 
 namespace {
 
@@ -41,7 +40,7 @@ int main() {
             n_cand[(size_t)f] = round % 3 == 0 ? ccap : below(g, ccap + 1);
             for (int r = 0; r < ccap; r++) cand[(size_t)f * ccap + r] = r < n_cand[(size_t)f] ? all[(size_t)r] : 1 << 30;
         }
-        auto cand_ok_ = [&] { return cand_ok(n_items, n_tab, ccap, cand.data(), n_cand.data(), err, sizeof(err)); };
+        auto cand_ok_ = [&] { return kf_rows_ok("cand", "n_cand", "ccap", n_items, n_tab, ccap, cand.data(), n_cand.data(), err, sizeof(err)); };
         expect(cand_ok_(), true, "", "valid candidate rows (a keyframe may be in the rows of two items)");
         const int f = below(g, n_items);
         const int32_t keep_n = n_cand[(size_t)f];
@@ -80,7 +79,7 @@ int main() {
             off[(size_t)p + 1] = (int32_t)okf.size();
         }
         const int n_obs = (int)okf.size();
-        auto csr_ok_ = [&] { return msl::mappoint::csr_ok(n_tab, cap, n_pts, n_obs, off.data(), okf.data(), oidx.data(), n_kps.data(), err, sizeof(err)); };
+        auto csr_ok_ = [&] { return csr_ok(n_tab, cap, n_pts, n_obs, off.data(), okf.data(), oidx.data(), n_kps.data(), err, sizeof(err)); };
         expect(csr_ok_(), true, "", "valid observation table");
         if (n_obs > 0) {
             const int o = below(g, n_obs);

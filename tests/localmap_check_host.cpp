@@ -1,15 +1,15 @@
 // A plain C++ host program for the index checks of msl_local_keyframes / msl_local_points / msl_local_lines
-// (manhattanslam_amd/csrc/msl_local_map_check.h): every array is heap-allocated at exactly its size, so a read past an end is the address
+// (manhattanslam_amd/csrc/msl_index_check.h): every array is heap-allocated at exactly its size, so a read past an end is the address
 // sanitizer's to find; valid random arrays must pass, each single defect must be refused with a message that names the field, and a count
 // outside its capacity must be refused before any entry behind it is read.  Prints "<n> failures".
-#include "msl_local_map_check.h"
+#include "msl_index_check.h"
 
 #include <stdlib.h>
 #include <string.h>
 
 #include <random>
 
-using namespace msl::localmap;
+using namespace msl::check;
 
 namespace {
 
@@ -91,7 +91,7 @@ int main() {
             const std::vector<int32_t> d = distinct(g, n_tab, n_list[(size_t)q]);
             for (size_t r = 0; r < d.size(); r++) list[(size_t)q * n_tab + r] = d[r];
         }
-        auto list_ok_ = [&] { return list_ok("local_kf", "n_local_kf", n_frames, n_tab, list.data(), n_list.data(), err, sizeof(err)); };
+        auto list_ok_ = [&] { return kf_rows_ok("local_kf", "n_local_kf", "n_tab", n_frames, n_tab, n_tab, list.data(), n_list.data(), err, sizeof(err)); };
         expect(list_ok_(), true, "", "valid lists (a keyframe may be in the lists of two frames)");
         const int32_t keep_l = n_list[(size_t)f];
         n_list[(size_t)f] = n_tab + 1; expect(list_ok_(), false, "n_local_kf[", "length above n_tab");

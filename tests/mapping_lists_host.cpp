@@ -1,12 +1,12 @@
 // A plain C++ host program for the item checks of msl_fuse_map_points / msl_fuse_map_lines (lists_ok), msl_triangulate_new_points
-// (neighbours_ok) and msl_fuse_candidates (targets_ok) in manhattanslam_amd/csrc/msl_mappoint_check.h: every array is heap-allocated at exactly
+// (neighbours_ok) and msl_fuse_candidates (targets_ok) in manhattanslam_amd/csrc/msl_index_check.h: every array is heap-allocated at exactly
 // its size, so a read past an end is the address sanitizer's to find; a valid set must pass, and each single defect must be refused with
 // exactly the message the library has always given behind its "<entry point>: ".  Prints "<n> failures".
-#include "msl_mappoint_check.h"
+#include "msl_index_check.h"
 
 #include <string.h>
 
-using namespace msl::mappoint;
+using namespace msl::check;
 
 namespace {
 

@@ -1,14 +1,14 @@
-// A plain C++ host program for the index checks of msl_refresh_map_points / msl_covisibility (manhattanslam_amd/csrc/msl_mappoint_check.h):
+// A plain C++ host program for the index checks of msl_refresh_map_points / msl_covisibility (manhattanslam_amd/csrc/msl_index_check.h):
 // every array is heap-allocated at exactly its size, so a read past an end is the address sanitizer's to find; a valid random table must
 // pass, and each single defect must be refused with a message that names the field.  Prints "<n> failures".
-#include "msl_mappoint_check.h"
+#include "msl_index_check.h"
 
 #include <stdlib.h>
 #include <string.h>
 
 #include <random>
 
-using namespace msl::mappoint;
+using namespace msl::check;
 
 namespace {
 

@@ -1,5 +1,5 @@
 """The index checks a host-memory call of msl_local_keyframes / msl_local_points / msl_local_lines makes
-(manhattanslam_amd/csrc/msl_local_map_check.h), called by a plain C++ host program on exactly sized arrays (tests/localmap_check_host.cpp)
+(manhattanslam_amd/csrc/msl_index_check.h), called by a plain C++ host program on exactly sized arrays (tests/localmap_check_host.cpp)
 built with the address and undefined-behaviour sanitizers.  Runs without a GPU."""
 from tests.test_mappoint_csr_host import run_sanitized
 

@@ -1,4 +1,4 @@
-"""The index checks a host-memory call of the LocalMapping entry points makes (manhattanslam_amd/csrc/msl_mappoint_check.h), called by plain C++
+"""The index checks a host-memory call of the LocalMapping entry points makes (manhattanslam_amd/csrc/msl_index_check.h), called by plain C++
 host programs on exactly sized arrays, built with the address and undefined-behaviour sanitizers: the observation table, the items and the
 reference keyframes of msl_refresh_map_points / msl_covisibility (tests/mappoint_csr_host.cpp); the items and lists of msl_fuse_map_points /
 msl_fuse_map_lines, the neighbours of msl_triangulate_new_points and the targets of msl_fuse_candidates (tests/mapping_lists_host.cpp).
