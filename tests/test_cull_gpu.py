@@ -1,7 +1,8 @@
 """msl_cull_keyframes and msl_cull_recent on the GPU against tests/cull_model.py: every output, compared as bytes, in the host-memory forms
 (the handle's and the device-indexed one) and the device-memory form; every pin on a hand-built scene; the device-memory contract for
 indices outside their tables with canaries around every array; and the chain msl_covisibility -> msl_cull_keyframes on one stream in
-device memory against both models."""
+device memory against both models.  The shapes here are small (n_tab up to 70, cap up to 1100, three items, 320 recent elements); the limits
+of msl.h -- n_tab = ccap = n_items 4096, cap 8192, 1 << 20 recent elements -- are in tests/test_mapping_limits_gpu.py."""
 import itertools
 
 import numpy as np

@@ -2,7 +2,8 @@
 in the host-memory forms (the handle's and the device-indexed one) and the device-memory form; every pin of msl.h's list on a hand-built
 scene; the output capacity, the group boundary of the scratch budget, the device-memory contract for indices outside their tables with
 canaries around every array; and the chain msl_covisibility -> msl_local_keyframes -> msl_local_points -> msl_match_local_points /
-msl_local_lines -> msl_match_local_lines on one stream in device memory against the literal models."""
+msl_local_lines -> msl_match_local_lines on one stream in device memory against the literal models.  The shapes here are small (n_tab up to 130, cap 100, klcap 70, three frames); the limits of msl.h
+-- n_tab 4096, cap 8192, klcap 256, mcap 32768, n_pts 1 << 20 -- are in tests/test_mapping_limits_gpu.py."""
 import numpy as np
 import pytest
 
