@@ -124,6 +124,19 @@ struct alignas(32) AssignRec {
                                    // otherwise -1.0, i.e. the sign doubles as the seed's "has depth" test (:348) and the record needs no meanDepth
     unsigned long long _pad;
 };
+// INVARIANT of AssignRec::invDepth: it is -1.0, or a double with a clear sign bit that is no NaN -- so `invDepth >= 0` is exactly "the sign bit of its
+// high word is clear" (arec_has_depth), which kb_assign decides on the scalar side.  Proof: arec_inv_depth() below is the ONLY expression that is
+// ever stored there (assign_rec for kb_seed_init, and kb_commit_seeds).  Its argument is a float; `meanDepth > 0` is false for NaN, for both zeros
+// and for every negative value, which all give the literal -1.0.  Otherwise meanDepth lies in [2^-149, +inf]: its conversion to double is exact and
+// positive, and 1.0 / that is an IEEE division of two positive operands: +0.0 for +inf, otherwise a positive finite double (at most 2^149: no
+// overflow) -- never NaN, never -0.0, never negative.  (The record of padding either side of the array is loaded and never evaluated.)
+constexpr double arec_inv_depth(float meanDepth) { return meanDepth > 0 ? 1.0 / (double)meanDepth : -1.0; }
+static_assert(arec_inv_depth(0.0f) == -1.0 && arec_inv_depth(-0.0f) == -1.0 && arec_inv_depth(-2.5f) == -1.0 && arec_inv_depth(__builtin_nanf("")) == -1.0,
+              "no valid depth: the literal -1.0");
+static_assert(__builtin_bit_cast(unsigned long long, arec_inv_depth(__builtin_inff())) == 0ull && arec_inv_depth(2.0f) == 0.5 &&
+              arec_inv_depth(__builtin_bit_cast(float, 1u)) > 0 && arec_inv_depth(__builtin_bit_cast(float, 1u)) < 1e46,
+              "a valid depth: sign bit clear from +inf (+0.0) down to the smallest denormal (finite)");
+static_assert((__builtin_bit_cast(unsigned long long, -1.0) >> 63) == 1ull, "-1.0 has its sign bit set");
 
 // What only a few waves of a k_fuse launch need (rare paths): kept in device memory, not in kernel arguments.
 struct FuseAux {
@@ -202,8 +215,16 @@ struct SfDev {
 __device__ __forceinline__ AssignRec assign_rec(const msl_seed &s) {
     AssignRec a;
     a.x = s.x; a.y = s.y; a.meanIntensity = s.meanIntensity; a.stable = s.stable ? 1u : 0u;
-    a.invDepth = s.meanDepth > 0 ? 1.0 / (double)s.meanDepth : -1.0; a._pad = 0;
+    a.invDepth = arec_inv_depth(s.meanDepth); a._pad = 0;
     return a;
+}
+// `C.invDepth >= 0` by the invariant above, for a record that is uniform over the wave (kb_assign's candidates): an s_cmp on its high word.  (The
+// empty asm emits nothing: it pins the word to a scalar register and keeps the compiler from widening the test back to a 64-bit signed comparison
+// of the whole double, which only the VALU has -- v_cmp_gt_i64 per cost evaluation.)
+__device__ __forceinline__ bool arec_has_depth(const AssignRec &C) {
+    int hi = (int)(__builtin_bit_cast(unsigned long long, C.invDepth) >> 32);
+    asm("" : "+s"(hi));
+    return hi >= 0;
 }
 __device__ __forceinline__ int seed_chunk(int seedI, int nseeds) {   // THREAD_NUM partition of :430-434
     const int step = nseeds / NCHUNK;

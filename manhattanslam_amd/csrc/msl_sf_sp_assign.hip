@@ -1,7 +1,7 @@
 // msl_sf_sp_assign.hip -- superpixel stage for gfx950 (MI355X): seed initialisation, pixel assignment and the relaxation that gives the passes
 // after the first the reference's raster-order `stable` semantics (stage overview: msl_sf_superpixel.hip).
 //     kb_seed_init                        one thread per 8x8 superpixel seed                  (reference src/SurfelFusion.cpp:528-584)
-//     kb_assign                           one wave per two dual cells: argmin over <= 4 seeds (:333-415)
+//     kb_assign                           one wave per three dual cells: argmin over <= 4 seeds (:333-415)
 //     kb_prop_lds | kb_prop x 6 + kb_prop_finish    the min-fixpoint t(s) over the worklist kb_assign left
 //     kb_commit_px                        a pixel takes its pick iff its seed was unstable before it in raster order
 //     k_debug_div100                      test hook of div100_exact
@@ -57,21 +57,25 @@ __global__ __launch_bounds__(256) void kb_seed_init(SfDev P) {
 // the right / lower one when (x mod 8) > 4 -- so ALL pixels of a dual cell have the same candidates {bx, bx + 1} x {by, by + 1} (its first
 // column / row, x mod 8 == 4, only the first of each pair).  The candidates are therefore wave-uniform: their fields are scalar operands, and
 // the per-pixel work is the four cost evaluations and nothing else.  Enumeration in the reference's order (checkI outer, checkJ inner, ascending).
-constexpr int ASSIGN_NY = 2;   // dual cells (one below the other) per wave.  Everything the wave reads -- the NY + 1 lattice rows of candidate records
+constexpr int ASSIGN_NY = 3;   // dual cells (one below the other) per wave.  Everything the wave reads -- the NY + 1 lattice rows of candidate records
                                // (scalar loads) and the pixels' member / gray / depth / index words -- is requested before the first use: with one
                                // pixel per lane and loads that wait for one another the kernel had too few bytes in flight to keep HBM busy while
                                // other waves computed (35 us of memory time and 43 us of cost arithmetic per pass simply added up).
-__global__ __launch_bounds__(256) void kb_assign(SfDev P, int it, int nSlots, int nbx, int nby) {
-    const int bpr = (nbx + 3) >> 2;   // workgroups per row of dual cells (four waves = four dual cells along x)
-    const int nbyG = (nby + ASSIGN_NY - 1) / ASSIGN_NY;
+                               // 3 instead of 2: the slot mapping, the FrameDev load and the column terms are paid once for 192 pixels (213 instead
+                               // of 221 VALU per cell, 60 VGPRs; 4 would need 74).  A column's last wave may have cells below the image (inImg).
+constexpr int ASSIGN_WAVES = 4;   // waves (dual-cell columns) per workgroup.  The waves share nothing (no barrier, no LDS), but one-wave workgroups
+                                  // lose here: front end -1.7 %
+__host__ __device__ constexpr int assign_blocks(int nbx, int nby) { return ((nbx + ASSIGN_WAVES - 1) / ASSIGN_WAVES) * ((nby + ASSIGN_NY - 1) / ASSIGN_NY); }
+__global__ __launch_bounds__(64 * ASSIGN_WAVES) void kb_assign(SfDev P, int it, int nSlots, int nbx, int nby) {
+    const int bpr = (nbx + ASSIGN_WAVES - 1) / ASSIGN_WAVES;   // workgroups per row of dual cells
     int slot, blk;
-    if (!xcd_slot(bpr * nbyG, nSlots, slot, blk)) return;
-    if (blk == 0) {
+    if (!xcd_slot(assign_blocks(nbx, nby), nSlots, slot, blk)) return;
+    if (blk == 0) {   // (lanes of the workgroup's first wave)
         if (it > 0 && threadIdx.x < 8) P.changed[slot * 8 + threadIdx.x] = threadIdx.x == 0 ? 1 : 0;
-        if (threadIdx.x >= 64 && threadIdx.x < 64 + NCHUNK) P.chunkAbort[(slot * 2 + (it & 1)) * 16 + threadIdx.x - 64] = 0x7FFFFFFF;
+        if (threadIdx.x >= 32 && threadIdx.x < 32 + NCHUNK) P.chunkAbort[(slot * 2 + (it & 1)) * 16 + threadIdx.x - 32] = 0x7FFFFFFF;
     }
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int byg = blk / bpr, bxi = (blk - byg * bpr) * 4 + wv;
+    const int byg = blk / bpr, bxi = (blk - byg * bpr) * ASSIGN_WAVES + wv;
     if (bxi >= nbx) return;
     const int bx = bxi - 1, by0 = byg * ASSIGN_NY - 1;
     // The candidates (wave-uniform): cell k uses lattice rows by0 + k and by0 + k + 1, in each the neighbours bx and bx + 1 -- two records that
@@ -141,12 +145,15 @@ __global__ __launch_bounds__(256) void kb_assign(SfDev P, int it, int nSlots, in
         // calculateCost (:333-355) + the two running minima (:398-410) for one candidate; `use` = this pixel has the candidate (x mod 8 == 4:
         // the pixel's own cell only).  Selects instead of branches.
         auto consider = [&](const AssignRec &C, int spIndex, bool use) {
+            // `C.invDepth >= 0` (:348) from the sign of the record's high word: the record is a scalar operand, so this is one s_cmp per candidate
+            // where the f64 comparison was a v_cmp_ge_f64 per cost evaluation (the invariant: arec_has_depth, msl_sf.h)
+            const bool candHas = arec_has_depth(C);
             float nodepthCost = 0;
             const float dist = (C.x - colF) * (C.x - colF) + (C.y - rowF) * (C.y - rowF);
             nodepthCost += dist / ((SP / 2) * (SP / 2));
             const float intensityDiff = C.meanIntensity - myIntensity;
             nodepthCost = (float)((double)nodepthCost + div100_exact((double)(intensityDiff * intensityDiff)));
-            const bool has = C.invDepth >= 0 && pxHasDepth;
+            const bool has = candHas && pxHasDepth;
             const float inverseDepthDiff = (float)(C.invDepth - myInvD);
             const float withDepth = (float)((double)nodepthCost + (double)(inverseDepthDiff * inverseDepthDiff) * 400.0);
             const float depthCost = has ? withDepth : nodepthCost;
@@ -322,8 +329,8 @@ void sp_launch_pixel_pass(KernelProfiler &prof, hipStream_t sp, const SfDev &P, 
     const int W = P.W, H = P.H;
     const unsigned un = (unsigned)n;
     const int nbx = ((W - 5) >> 3) + 2, nby = ((H - 5) >> 3) + 2;   // dual cells [8 b + 4, 8 b + 12), b from -1, that meet the image
-    const dim3 pxGrid(xcd_grid(((nbx + 3) / 4) * ((nby + ASSIGN_NY - 1) / ASSIGN_NY), n)), flatPx(xcd_grid(((P.npx + 7) / 8 + 255) / 256, n));
-    MSL_SF_LAUNCH(prof, SK_ASSIGN, sp, kb_assign, pxGrid, dim3(256), P, it, n, nbx, nby);
+    const dim3 pxGrid(xcd_grid(assign_blocks(nbx, nby), n)), flatPx(xcd_grid(((P.npx + 7) / 8 + 255) / 256, n));
+    MSL_SF_LAUNCH(prof, SK_ASSIGN, sp, kb_assign, pxGrid, dim3(64 * ASSIGN_WAVES), P, it, n, nbx, nby);
     if (it > 0) {
         prof.begin(SK_PROP, sp);
         if (propLds) {

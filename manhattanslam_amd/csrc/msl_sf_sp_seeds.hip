@@ -22,13 +22,18 @@ struct SeedUpd {
     float meanDepth;
 };
 static_assert(sizeof(SeedUpd) <= sizeof(msl_seed), "the hand-over record fits a seedsTmp record");
+constexpr int UPD_SEEDS = 16;   // seeds per workgroup (four per wave).  The waves share nothing (a seed's 16 lanes use their own row of s_depth and wave_barrier
+                                // only), but one-wave workgroups (4 seeds, 4.3 KB of LDS) gain nothing: front end +- 0
+constexpr int NEWTON_RB = 4;    // blocks (of 16 elements) of a seed's depth list that stay in registers for the Newton steps; the rest is re-read from s_depth.
+                                // 4 / 6 / 8 measured alike (all 46 - 48 VGPRs: the gather holds more); 4 is the least code (the chains are unrolled per block)
+__host__ __device__ constexpr int upd_blocks(int nseeds) { return (nseeds + UPD_SEEDS - 1) / UPD_SEEDS; }
 template <bool STRADDLE>   // STRADDLE: W mod 8 in {1, 2, 3} (a window quad can stick out over the right edge)
-__global__ __launch_bounds__(256) void kb_update_seeds(SfDev P, int it, int nSlots) {
+__global__ __launch_bounds__(16 * UPD_SEEDS) void kb_update_seeds(SfDev P, int it, int nSlots) {
     // rows of 256 + 16 words: the two seeds of a 32-lane half read / write entry l + 16 t of their own row together (ds_*_b32: bank = word address mod
     // 32); with a row stride of 256 words both rows started on the same bank (round 4: 32 % of the kernel's LDS cycles were bank conflicts)
-    __shared__ __attribute__((aligned(16))) float s_depth[16][272];   // the ordered depth lists (the only LDS of the kernel since round 5: 17 KB)
+    __shared__ __attribute__((aligned(16))) float s_depth[UPD_SEEDS][272];   // the ordered depth lists (the only LDS of the kernel since round 5: 17 KB)
     int slot, blk;
-    if (!xcd_slot((P.nseeds + 15) / 16, nSlots, slot, blk)) return;
+    if (!xcd_slot(upd_blocks(P.nseeds), nSlots, slot, blk)) return;
 #ifdef MSL_FUSE_STAMPS   // section cycle counts of the waves of slot 0, summed into delList[96 ..] (tools/fuse_stamps.py)
     unsigned long long ust[8]; int usn = 0;
 #define USTAMP() ust[usn++] = __builtin_amdgcn_s_memtime()
@@ -37,7 +42,7 @@ __global__ __launch_bounds__(256) void kb_update_seeds(SfDev P, int it, int nSlo
 #endif
     USTAMP();
     const int g = threadIdx.x >> 4, l = threadIdx.x & 15;
-    const int seedI = blk * 16 + g;
+    const int seedI = blk * UPD_SEEDS + g;
     const FrameDev F = P.frames[slot];   // by value: one load up front instead of re-reading fields around every store
     const unsigned short *index = P.index + (size_t)slot * P.pxStride;
     msl_seed S;
@@ -119,9 +124,23 @@ __global__ __launch_bounds__(256) void kb_update_seeds(SfDev P, int it, int nSlo
     const int ndL = depthLoop ? nd : 0;                 // a seed without a depth loop contributes empty lists
     const int nblk = rows_max_i32((ndL + 15) >> 4);    // blocks of the longest list of the wave's four seeds
     float meanDepth = 0.0f;
+    // The first NEWTON_RB blocks of the list stay in registers once the depth sum has read them (dr[]; element l + 16 bq, +0.0f beyond the list's
+    // end): a Newton step then computes each of their residuals ONCE and takes the in-band count, the tail flag and the chain term (tr[]) from that
+    // one value.  Blocks beyond NEWTON_RB (a seed that owns more than 16 NEWTON_RB pixels with a valid depth) are walked in s_depth as before:
+    // a counting pass in front of the chain, the chain pass recomputing the residual.
+    float dr[NEWTON_RB > 0 ? NEWTON_RB : 1], tr[NEWTON_RB > 0 ? NEWTON_RB : 1];
     {
         float sd = 0.0f;
-        for (int bq = 0; bq < nblk; bq++) {
+#pragma unroll
+        for (int bq = 0; bq < NEWTON_RB; bq++) {
+            dr[bq] = 0.0f;
+            if (bq < nblk) {
+                const int e = l + 16 * bq;
+                dr[bq] = e < ndL ? s_depth[g][e] : 0.0f;
+                sd = chain_block_f32(sd, dr[bq]);
+            }
+        }
+        for (int bq = NEWTON_RB; bq < nblk; bq++) {
             const int e = l + 16 * bq;
             sd = chain_block_f32(sd, e < ndL ? s_depth[g][e] : 0.0f);
         }
@@ -132,10 +151,20 @@ __global__ __launch_bounds__(256) void kb_update_seeds(SfDev P, int it, int nSlo
     bool open = depthLoop;
     for (int newtonI = 0; newtonI < 5; newtonI++) {
         if (!__ballot(open)) break;
-        // pass 1: in-range count (sumB) and whether any list of the wave has a Huber tail this step
+        // in-range count (sumB) and whether any list of the wave has a Huber tail this step; the terms of the chain -- in range: 2*residual; a tail
+        // element: the +-inf marker huber_term_add() turns into +-HUBER_RANGE; beyond the list's end or a closed seed: +0.0f
         int inr = 0;
         bool tail = false;
-        for (int bq = 0; bq < nblk; bq++) {
+#pragma unroll
+        for (int bq = 0; bq < NEWTON_RB; bq++) {   // the register-resident blocks: one residual per element and step
+            tr[bq] = 0.0f;
+            if (bq < nblk && open && l + 16 * bq < ndL) {
+                const float residual = meanDepth - dr[bq];
+                if (in_huber_band(residual)) { inr++; tr[bq] = 2 * residual; }
+                else { tail = true; tr[bq] = residual > 0 ? __builtin_inff() : -__builtin_inff(); }
+            }
+        }
+        for (int bq = NEWTON_RB; bq < nblk; bq++) {   // the rest of a long list: counted here, its terms recomputed in front of the chain below
             const int e = l + 16 * bq;
             if (open && e < ndL) {
                 const float residual = meanDepth - s_depth[g][e];
@@ -144,9 +173,12 @@ __global__ __launch_bounds__(256) void kb_update_seeds(SfDev P, int it, int nSlo
         }
         inr = row_sum_i32(inr);
         const bool anyTail = __ballot(tail) != 0ull;
-        // pass 2: the chain over the terms -- in range: 2*residual; a tail element: the +-inf marker huber_term_add() turns into +-HUBER_RANGE
+        // the chain over the terms, in list order
         float sa = 0.0f;
-        for (int bq = 0; bq < nblk; bq++) {
+#pragma unroll
+        for (int bq = 0; bq < NEWTON_RB; bq++)
+            if (bq < nblk) sa = anyTail ? chain_block_huber(sa, tr[bq]) : chain_block_f32(sa, tr[bq]);
+        for (int bq = NEWTON_RB; bq < nblk; bq++) {
             const int e = l + 16 * bq;
             float t = 0.0f;
             if (open && e < ndL) {
@@ -223,7 +255,7 @@ __global__ __launch_bounds__(256) void kb_commit_seeds(SfDev P, int it) {
     P.tmin[si] = tStable ? T_INF : 0u;
     AssignRec a;
     a.x = mX; a.y = mY; a.meanIntensity = sumIntensity; a.stable = tStable ? 1u : 0u;
-    a.invDepth = tDepth > 0 ? 1.0 / (double)tDepth : -1.0; a._pad = 0;
+    a.invDepth = arec_inv_depth(tDepth); a._pad = 0;   // (the one expression ever stored there: the invariant kb_assign's sign test rests on)
     P.arec[si] = a;
 }
 
@@ -253,8 +285,8 @@ namespace sf {
 // Seed pass `it`.  kb_update_seeds runs uncapped, 8 workgroups per CU (17 KB of LDS, 56 VGPRs): capped at 7 / 6 / 5 by unused dynamic LDS the front end
 // made 23.1 / 23.2 / 22.7 k frames/s against 23.1 k -- no sweet spot below the maximum, unlike kb_seed_plane (round 5).
 void sp_launch_seed_pass(KernelProfiler &prof, hipStream_t sp, const SfDev &P, int n, int it) {
-    if (sp_quad_straddles(P.W)) MSL_SF_LAUNCH(prof, SK_UPDATE_SEEDS, sp, kb_update_seeds<true>, dim3(xcd_grid((P.nseeds + 15) / 16, n)), dim3(256), P, it, n);
-    else MSL_SF_LAUNCH(prof, SK_UPDATE_SEEDS, sp, kb_update_seeds<false>, dim3(xcd_grid((P.nseeds + 15) / 16, n)), dim3(256), P, it, n);
+    if (sp_quad_straddles(P.W)) MSL_SF_LAUNCH(prof, SK_UPDATE_SEEDS, sp, kb_update_seeds<true>, dim3(xcd_grid(upd_blocks(P.nseeds), n)), dim3(16 * UPD_SEEDS), P, it, n);
+    else MSL_SF_LAUNCH(prof, SK_UPDATE_SEEDS, sp, kb_update_seeds<false>, dim3(xcd_grid(upd_blocks(P.nseeds), n)), dim3(16 * UPD_SEEDS), P, it, n);
     MSL_SF_LAUNCH(prof, SK_COMMIT_SEEDS, sp, kb_commit_seeds, sp_seed_grid(P, n), dim3(256), P, it);
 }
 

@@ -3,7 +3,7 @@
 // generateSuperPixels() of a keyframe (reference src/SurfelFusion.cpp:333-773) depends only on that keyframe's images, never on the
 // map, so it is FRAME-BATCHED (one launch sequence per batch of F keyframes, XCD-aware 1-D grids) on the handle's "pre" stream:
 //     kb_seed_init                        one thread per 8x8 superpixel seed                  (:528-584)   msl_sf_sp_assign.hip
-//     3 x { kb_assign                     one wave per two dual cells: argmin over <= 4 seeds (:333-415)   msl_sf_sp_assign.hip
+//     3 x { kb_assign                     one wave per three dual cells: argmin over <= 4 seeds (:333-415) msl_sf_sp_assign.hip
 //           [kb_prop_lds,                 raster-order `stable` semantics as a min-fixpoint   (App. B.7.1)
 //            kb_commit_px]                  over a compact worklist of the only pixels that can extend a chain (one launch, LDS)
 //           kb_update_seeds               16 lanes per seed: ordered window gather, Huber mean (:428-515)  msl_sf_sp_seeds.hip
