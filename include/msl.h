@@ -674,6 +674,103 @@ MSL_API int msl_manhattan_detect_batch(int device, int n_frames, int pcap, int m
                                        const float *kf_Rwc, const float *kf_coef, const int32_t *kf_npts, msl_mem mem, int32_t *found,
                                        int32_t *full, float *Rcw, int32_t *choice, msl_mem out_mem) MSL_NOEXCEPT;
 
+/* ---- Plane clouds: the tail of Frame::ExtractPlanes and MapPlane::UpdateCoefficientsAndPoints ----
+ * The step between msl_peac_extract_batch and msl_plane_associate / msl_manhattan_detect, and the map-plane clouds the next frame's
+ * association reads.  PCL's results are implementation-defined (pcl::VoxelGrid sorts with an unstable std::sort and sums in float in that
+ * order), so the contract is the sequential model tests/plane_cloud_model.py, which the kernels follow bit for bit.
+ *
+ * Voxel grid (pcl::VoxelGrid, leaf = params->leaf on every axis): voxel = (int)floorf(x * (1.0f / leaf)) per axis; output voxels in
+ * ascending (vz, vy, vx), PCL's linear-index order; a point that is not finite or has a |coordinate| >= 32768 m is skipped; the centroid
+ * is order-independent: every coordinate is (int64)rint((double)x * 2^24), summed as int64, mean = (float)((double)sum / (double)count)
+ * scaled back by 2^-24 (exact); colour: integer sums of r, g, b, (float)sum / (float)count truncated to u8.  A bounding box of more than
+ * INT32_MAX cells (PCL returns its input unfiltered) and a cloud of more than MSL_PLANE_CLOUD_MAX_VOXELS voxels are statuses.
+ *
+ * msl_plane_clouds: n_frames independent tails of Frame::ExtractPlanes (src/Frame.cc:611-653, MaxPointDistanceFromPlane :662-709).
+ * In (mem), per frame f: cloud[f][n_vertices][3] doubles (msl_peac_extract_batch's cloud_out, cast to float as :616-618), rgb[f][n_vertices][3]
+ * u8 or NULL (colour not carried; then rgb_out must be NULL too), vertex_offsets[f][max_planes + 1] / vertex_indices[f][n_vertices],
+ * planes[f][max_planes], n_planes[f] (msl_peac_extract_batch's outputs of these names), seed[f].  Per detector plane i < n_planes[f]:
+ * gather its vertices, voxel grid, then the gate: (a, b, c) = (float)normal, d = (float)-(nx cx + ny cy + nz cz) in double, the plane is
+ * rejected if the float |a x + b y + c z + d|, left to right, is > dis_th at any coarse point, then if fewer than 4 coarse points remain;
+ * then pcl::SACSegmentation pinned as: iteration k draws three distinct points with the sampler of msl_pnp_ransac (seed[f] ^ fmix32(i),
+ * swap-with-back over a fresh identity permutation); float plane = normalised cross product, d = -n.p0; a zero cross product uses up the
+ * iteration (PCL redraws); inliers float |n.p + d| < dis_th; a hypothesis replaces the best on a strictly larger count; stop after
+ * iteration `it` when q^it <= 1 - probability (q = 1 - w^3, w = count / N, double, the power by repeated multiplication) or
+ * it == max_iterations; no hypothesis at all drops the plane.  With more than 3 inliers the coefficients are refitted: centroid and centred
+ * scatter matrix in double (element i of the ascending inliers to partial i mod 256, a pairwise tree over the partials), the eigenvector of
+ * its smallest eigenvalue from the pinned Jacobi solver, normalised in double, d = -n.centroid, all four rounded to float.  Then the sign
+ * rule of :704-706 against the gate's d.
+ * Out (out_mem), per frame: n_out[f] (mnPlaneNum); plane_coef[f][pcap][4] and plane_npts[f][pcap] in exactly the layout msl_plane_associate
+ * and msl_manhattan_detect read; plane_src[f][pcap] the detector plane of each kept plane; the coarse clouds as CSR pt_off[f][pcap + 1],
+ * pts[f][ptcap][3] (and rgb_out[f][ptcap][3]); status[f][max_planes] per detector plane (MSL_PLANE_CLOUD_*).  Kept planes are compacted
+ * in detector order (the push_backs of :651-652).  When pcap or ptcap is exhausted, that plane and every later kept one is dropped with
+ * MSL_PLANE_CLOUD_NO_ROOM.
+ *
+ * msl_map_plane_merge: n_frames independent runs of the loop of src/Tracking.cc:429-436 (MapPlane::UpdateCoefficientsAndPoints(Frame&, id),
+ * src/MapPlane.cc:201-218; the no-argument form of :178-199 on a new plane is a merge into a row with an empty cloud).
+ * In (mem), per frame: the frame's plane clouds (n_planes[f], pt_off[f][pcap + 1], pts[f][fptcap][3], rgb[f][fptcap][3] or NULL: the
+ * outputs above), merge_into[f][pcap] (a map row, or -1), Twc[f][12] doubles (rows 0-2, row-major; the caller inverts its pose), the map
+ * clouds in msl_plane_associate's layout (mp_pt_off[f][mcap + 1], mp_pts[f][ptcap][3], n_map[f]; mp_rgb[f][ptcap][3] or NULL).  Colour is
+ * carried when rgb, mp_rgb and mp_rgb_out are all given, and not when all are NULL (anything else is refused).
+ * A frame point goes through (float)(T[4r] * x + T[4r + 1] * y + T[4r + 2] * z + T[4r + 3]) in double, left to right; the row's cloud is
+ * appended and the sum voxel-filtered.  Several frame planes that name one row are merged one after another in ascending k, each seeing the
+ * previous result.  A merge that fails (voxel limit, grid overflow) leaves the row's cloud as it was; the row's status is its first failure.
+ * Out (out_mem): a new CSR of the whole map, mp_pt_off_out[f][mcap + 1] / mp_pts_out[f][ptcap][3] (/ mp_rgb_out), offsets an exact prefix
+ * sum from 0, rows in map order, untouched rows copied bit for bit: the next msl_plane_associate takes it as it stands.
+ * merge_status[f][mcap] (MSL_PLANE_MERGE_*).  When ptcap is exhausted that row and every later one is empty with MSL_PLANE_MERGE_NO_ROOM.
+ *
+ * Counts: n_planes[f] is clamped to [0, max_planes] / [0, pcap], n_map[f] to [0, mcap], offsets to their array.  Host-memory calls check
+ * vertex_offsets, vertex_indices, pt_off, mp_pt_off and merge_into and refuse with the field named; with device memory an index outside
+ * its table is absent (a vertex index is skipped, a merge_into outside [0, n_map) is -1), and nothing is read or written outside an array.
+ * No kernel writes rows beyond the counts (plane_coef, plane_npts, plane_src and pt_off beyond n_out, points beyond the last offset, status
+ * beyond n_planes, mp_pt_off_out / merge_status beyond n_map): device-memory arrays keep their bytes there.
+ * Limits: n_frames <= 65535, n_vertices <= MSL_PLANE_CLOUD_MAX_VERTICES, max_planes <= 64, pcap <= 64, mcap <= 4096, ptcap and fptcap <= 2^22,
+ * 1 / 32 <= leaf, max_iterations in [1, 4096], probability in [0, 1]; anything else is refused with MSL_ERR_INVALID before any launch.
+ * Asynchronous on the matcher handle's stream when inputs and outputs are device memory. */
+#define MSL_PLANE_CLOUD_MAX_VOXELS 4096
+#define MSL_PLANE_CLOUD_MAX_VERTICES 131072
+#define MSL_PLANE_CLOUD_KEPT      0   /* in the output */
+#define MSL_PLANE_CLOUD_GATE      1   /* a coarse point farther than dis_th from the detector's plane */
+#define MSL_PLANE_CLOUD_FEW       2   /* fewer than 4 coarse points */
+#define MSL_PLANE_CLOUD_NO_MODEL  3   /* every sample degenerate */
+#define MSL_PLANE_CLOUD_VOXELS    4   /* more than MSL_PLANE_CLOUD_MAX_VOXELS voxels */
+#define MSL_PLANE_CLOUD_GRID      5   /* the bounding box spans more than INT32_MAX cells */
+#define MSL_PLANE_CLOUD_NO_ROOM   6   /* pcap or ptcap exhausted */
+#define MSL_PLANE_MERGE_UNTOUCHED 0   /* no frame plane names the row: copied */
+#define MSL_PLANE_MERGE_MERGED    1   /* every merge into the row succeeded */
+#define MSL_PLANE_MERGE_VOXELS    4   /* the first failed merge: voxel limit (the row keeps its cloud for that merge) */
+#define MSL_PLANE_MERGE_GRID      5   /* the first failed merge: grid overflow */
+#define MSL_PLANE_MERGE_NO_ROOM   6   /* ptcap exhausted: the row is empty */
+typedef struct msl_plane_cloud_params {
+    float leaf;                 /* 0.2 (src/Frame.cc:637, src/MapPlane.cc:211) */
+    float dis_th;               /* Plane.DistanceThreshold: mfDisTh (src/Tracking.cc:148) */
+    int32_t max_iterations;     /* 50: pcl::SACSegmentation's default */
+    int32_t _pad;
+    double probability;         /* 0.99 */
+} msl_plane_cloud_params;
+MSL_API int msl_plane_clouds(msl_match *h, int n_frames, int n_vertices, int max_planes, int pcap, int ptcap,
+                             const msl_plane_cloud_params *params, const double *cloud, const uint8_t *rgb, const int32_t *vertex_offsets,
+                             const int32_t *vertex_indices, const msl_peac_plane *planes, const int32_t *n_planes, const uint32_t *seed,
+                             msl_mem mem, int32_t *n_out, float *plane_coef, int32_t *plane_npts, int32_t *plane_src, int32_t *pt_off,
+                             float *pts, uint8_t *rgb_out, int32_t *status, msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device matcher handle, always synchronous; see msl_match_by_projection_batch). */
+MSL_API int msl_plane_clouds_batch(int device, int n_frames, int n_vertices, int max_planes, int pcap, int ptcap,
+                                   const msl_plane_cloud_params *params, const double *cloud, const uint8_t *rgb,
+                                   const int32_t *vertex_offsets, const int32_t *vertex_indices, const msl_peac_plane *planes,
+                                   const int32_t *n_planes, const uint32_t *seed, msl_mem mem, int32_t *n_out, float *plane_coef,
+                                   int32_t *plane_npts, int32_t *plane_src, int32_t *pt_off, float *pts, uint8_t *rgb_out, int32_t *status,
+                                   msl_mem out_mem) MSL_NOEXCEPT;
+MSL_API int msl_map_plane_merge(msl_match *h, int n_frames, int pcap, int fptcap, int mcap, int ptcap, const msl_plane_cloud_params *params,
+                                const int32_t *n_planes, const int32_t *pt_off, const float *pts, const uint8_t *rgb, const int32_t *merge_into,
+                                const double *Twc, const int32_t *mp_pt_off, const float *mp_pts, const uint8_t *mp_rgb, const int32_t *n_map,
+                                msl_mem mem, int32_t *mp_pt_off_out, float *mp_pts_out, uint8_t *mp_rgb_out, int32_t *merge_status,
+                                msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device matcher handle, always synchronous; see msl_match_by_projection_batch). */
+MSL_API int msl_map_plane_merge_batch(int device, int n_frames, int pcap, int fptcap, int mcap, int ptcap,
+                                      const msl_plane_cloud_params *params, const int32_t *n_planes, const int32_t *pt_off, const float *pts,
+                                      const uint8_t *rgb, const int32_t *merge_into, const double *Twc, const int32_t *mp_pt_off,
+                                      const float *mp_pts, const uint8_t *mp_rgb, const int32_t *n_map, msl_mem mem, int32_t *mp_pt_off_out,
+                                      float *mp_pts_out, uint8_t *mp_rgb_out, int32_t *merge_status, msl_mem out_mem) MSL_NOEXCEPT;
+
 /* ---- Bag of words: the vocabulary, Frame::ComputeBoW / KeyFrame::ComputeBoW, and the reference-keyframe searches ----
  * The searches that open Tracking::TrackReferenceKeyFrame (src/Tracking.cc:1146-1175) and Tracking::TranslationEstimation (:846-877).
  *

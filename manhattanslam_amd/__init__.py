@@ -17,6 +17,8 @@ from . import pose  # noqa: F401
 from ._lib import POSE_PARAMS_DTYPE  # noqa: F401
 from . import plane  # noqa: F401
 from ._lib import PLANE_PARAMS_DTYPE  # noqa: F401
+from . import plane_cloud  # noqa: F401
+from ._lib import PLANE_CLOUD_PARAMS_DTYPE  # noqa: F401
 from . import bow  # noqa: F401
 from ._lib import BOW_MATCH_PARAMS_DTYPE  # noqa: F401
 from . import reloc  # noqa: F401

@@ -31,6 +31,7 @@ KEYLINE_DTYPE = RECORDS["msl_keyline"]
 LINE_TRACK_DTYPE = RECORDS["msl_line_track"]
 POSE_PARAMS_DTYPE = RECORDS["msl_pose_params"]
 PLANE_PARAMS_DTYPE = RECORDS["msl_plane_params"]
+PLANE_CLOUD_PARAMS_DTYPE = RECORDS["msl_plane_cloud_params"]
 BOW_MATCH_PARAMS_DTYPE = RECORDS["msl_bow_match_params"]
 KEYFRAME_MATCH_PARAMS_DTYPE = RECORDS["msl_keyframe_match_params"]
 PNP_PARAMS_DTYPE = RECORDS["msl_pnp_params"]

@@ -3,9 +3,10 @@
 // msl_line_fuse.hip), the items and candidate lists of the two fusions (lists_ok: msl_fuse.hip, msl_line_fuse.hip), the targets of
 // msl_fuse_candidates (targets_ok), the neighbours of msl_triangulate_new_points (neighbours_ok: msl_triangulate.hip), the held ids, the graph
 // and the keyframe rows of the local map (held_ok, graph_ok, kf_rows_ok: msl_local_map.hip), and the candidate rows, the origin and the recent
-// elements of the cullings (kf_rows_ok, origin_ok, recent_ok: msl_cull.hip).  Pure host functions on plain arrays: no HIP call, no allocation
+// elements of the cullings (kf_rows_ok, origin_ok, recent_ok: msl_cull.hip), and the offsets, vertex indices and target rows of the plane clouds
+// (offsets_ok, vertex_indices_ok, merge_into_ok: msl_plane_cloud.hip).  Pure host functions on plain arrays: no HIP call, no allocation
 // through the library, no global state, so a plain C++ program can call them (tests/mappoint_csr_host.cpp, tests/mapping_lists_host.cpp,
-// tests/localmap_check_host.cpp, tests/cull_check_host.cpp).  Each returns true, or false with a message that names the field in err; the
+// tests/localmap_check_host.cpp, tests/cull_check_host.cpp, tests/plane_cloud_check_host.cpp).  Each returns true, or false with a message that names the field in err; the
 // caller puts its own name in front ("%s: %s").
 #pragma once
 
@@ -188,6 +189,50 @@ inline bool recent_ok(int n, bool int_form, const int32_t *found, const int32_t 
         if (int_form && (flags[i] & 1) && visible[i] == 0) {
             snprintf(err, err_len, "visible[%d] is 0 in the integer ratio form (a division by zero in the reference)", i);
             return false;
+        }
+    }
+    return true;
+}
+
+// ==== the plane clouds =======================================================================================================================
+// The offsets of n_frames CSR tables, rows + 1 entries each, of which the first n[f] rows (clamped to 0 .. rows) are read: ascending from
+// >= 0 to at most limit (what / count: the arguments' names).
+inline bool offsets_ok(const char *what, const char *count, int n_frames, int rows, int limit, const int32_t *off, const int32_t *n, char *err,
+                       size_t err_len) {
+    for (int f = 0; f < n_frames; f++) {
+        const int m = n[f] < 0 ? 0 : (n[f] > rows ? rows : n[f]);
+        const int32_t *o = off + (size_t)f * (rows + 1);
+        if (o[0] < 0) { snprintf(err, err_len, "%s[%d][0] is %d, below 0", what, f, (int)o[0]); return false; }
+        for (int r = 0; r < m; r++)
+            if (o[r + 1] < o[r]) { snprintf(err, err_len, "%s[%d] descends at row %d of %s (%d after %d)", what, f, r, count, (int)o[r + 1], (int)o[r]); return false; }
+        if (o[m] > limit) { snprintf(err, err_len, "%s[%d][%d] is %d, beyond %d", what, f, m, (int)o[m], limit); return false; }
+    }
+    return true;
+}
+
+// The vertex indices of the detector planes (offsets already checked by offsets_ok): inside the cloud of n_vertices.
+inline bool vertex_indices_ok(int n_frames, int max_planes, int n_vertices, const int32_t *vertex_offsets, const int32_t *vertex_indices,
+                              const int32_t *n_planes, char *err, size_t err_len) {
+    for (int f = 0; f < n_frames; f++) {
+        const int m = n_planes[f] < 0 ? 0 : (n_planes[f] > max_planes ? max_planes : n_planes[f]);
+        const int32_t *o = vertex_offsets + (size_t)f * (max_planes + 1);
+        for (int q = o[0]; q < o[m]; q++) {
+            const int v = vertex_indices[(size_t)f * n_vertices + q];
+            if (v < 0 || v >= n_vertices) { snprintf(err, err_len, "vertex_indices[%d][%d] is vertex %d of %d", f, q, v, n_vertices); return false; }
+        }
+    }
+    return true;
+}
+
+// merge_into of the first n_planes[f] frame planes: -1 or a row of the frame's n_map[f] map planes (both counts clamped).
+inline bool merge_into_ok(int n_frames, int pcap, int mcap, const int32_t *merge_into, const int32_t *n_planes, const int32_t *n_map, char *err,
+                          size_t err_len) {
+    for (int f = 0; f < n_frames; f++) {
+        const int np = n_planes[f] < 0 ? 0 : (n_planes[f] > pcap ? pcap : n_planes[f]);
+        const int nm = n_map[f] < 0 ? 0 : (n_map[f] > mcap ? mcap : n_map[f]);
+        for (int k = 0; k < np; k++) {
+            const int j = merge_into[(size_t)f * pcap + k];
+            if (j < -1 || j >= nm) { snprintf(err, err_len, "merge_into[%d][%d] is row %d of %d", f, k, j, nm); return false; }
         }
     }
     return true;

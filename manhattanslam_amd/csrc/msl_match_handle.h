@@ -2,7 +2,7 @@
 // a LocalMapping entry (handle_form, batch_form) with the list of its NULLs (none_null), the limits that several entry points share
 // (table_limits, line_table_limits, levels_ok) and the row readback of the debug entry points (last_call_row); shared by msl_match.hip,
 // msl_line_match.hip, msl_pose.hip, msl_plane.hip, msl_bow.hip, msl_reloc.hip, msl_pnp.hip, msl_line3d.hip, msl_triangulate.hip, msl_fuse.hip,
-// msl_mappoint.hip, msl_line_fuse.hip, msl_local_map.hip and msl_cull.hip (internal).
+// msl_mappoint.hip, msl_line_fuse.hip, msl_local_map.hip, msl_cull.hip and msl_plane_cloud.hip (internal).
 #pragma once
 
 #include "msl_common.h"
@@ -92,6 +92,10 @@ struct msl_match {
     // position) the kept count and its scan; the stamps of one group of frames stay under lmBudget bytes (msl_debug_local_map_budget)
     msl::DevBuf lmStamp, lmCount;
     size_t lmBudget = (size_t)256 << 20;
+    // msl_plane_clouds / msl_map_plane_merge: per resident workgroup the int64 sums, counts and colour sums of the voxels of a cloud too
+    // large to accumulate in LDS; per item ((frame, detector plane) or (frame, frame plane)) the coarse cloud, its count, status and
+    // coefficients
+    msl::DevBuf pcSlab, pcWork;
     // Device copies of host-memory arguments, one pool for every entry point (msl::Stage deals the slots out in declaration order).
     // Sharing is sound because every call that touches the pool returns with the stream drained (Stage::finish synchronises whenever
     // either side is host memory, and only then is a slot used), so no slot is live when the next call starts.
@@ -151,7 +155,7 @@ int last_call_row(msl_match *h, const DevBuf &buf, size_t row, size_t n, std::ve
 }
 
 // Kernels that ask for more dynamic LDS than the default limit: the limit is raised once per handle (= per device) and kernel.
-enum LdsKernel { LDS_MATCH_ASSIGN, LDS_LOCAL_ASSIGN, LDS_LINE_ASSIGN_LAST, LDS_LINE_ASSIGN_LOCAL, LDS_BOW_VECTOR, LDS_MATCH_BOW, LDS_KF_ASSIGN, LDS_RELOC_SELECT, LDS_TRI_GROUP, LDS_FUSE_HELD, LDS_FUSE_RESOLVE };
+enum LdsKernel { LDS_MATCH_ASSIGN, LDS_LOCAL_ASSIGN, LDS_LINE_ASSIGN_LAST, LDS_LINE_ASSIGN_LOCAL, LDS_BOW_VECTOR, LDS_MATCH_BOW, LDS_KF_ASSIGN, LDS_RELOC_SELECT, LDS_TRI_GROUP, LDS_FUSE_HELD, LDS_FUSE_RESOLVE, LDS_PC_VOXEL, LDS_PC_MERGE };
 template <class K>
 hipError_t allow_lds(msl_match *h, LdsKernel k, K kernel, size_t max_bytes) {
     if (h->ldsSet >> k & 1u) return hipSuccess;
