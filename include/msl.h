@@ -1623,6 +1623,152 @@ MSL_API int msl_cull_recent_batch(int device, int n, int cur_kf_id, int th_obs, 
                                   const int32_t *first_kf_id, const int32_t *nobs, const uint8_t *flags, msl_mem mem, uint8_t *verdict,
                                   msl_mem out_mem) MSL_NOEXCEPT;
 
+/* ---- The hand-over from tracking to local mapping: the keyframe decision and the new stereo map points ----
+ * msl_points_3d: the point half of the three call sites whose line half is msl_lines_3d -- StereoInitialization (src/Tracking.cc:560-572),
+ * UpdateLastFrame (:1062-1104) and CreateNewKeyFrame (:1524-1569) -- with Frame::UnprojectStereo (src/Frame.cc:515-526) and the two MapPoint
+ * constructors (src/MapPoint.cc:36-71), for n_frames independent frames with `cap` slots each.  Per frame f, slot i < n_kps[f]:
+ *   kps_un[i]          mvKeysUn[i]: only x, y (the undistorted point: Frame::UnprojectStereo, unlike KeyFrame::UnprojectStereo) and octave are read
+ *   depth[i]           mvDepth[i]                                 desc[32 i..]  row i of mDescriptors
+ *   cur_held[i]        the id of mvpMapPoints[i], -1 for NULL, as in msl_local_points; pt_nobs[id] = Observations() over the point table of
+ *                      n_pts rows (n_pts may be 0: every slot is NULL and pt_nobs is not read)
+ *   Tcw[12]            rows 0-2 of the CV_32F mTcw; mRwc and mOw are derived from it (Frame::UpdatePoseMatrices)
+ *   enable[f]          optional (NULL = every frame): a frame with 0 has no members and writes its "nothing" outputs, so msl_keyframe_decision's
+ *                      need_kf gates the call on the device
+ *   first_id[f]        optional: the id the frame's first new point gets in held_out
+ * mode: MSL_POINT3D_ALL is StereoInitialization -- index order, every slot with depth > 0, cur_held and pt_nobs are not read (they may be
+ * NULL), the KeyFrame form of the point; MSL_POINT3D_KEYFRAME is CreateNewKeyFrame -- the walk below, the KeyFrame form; MSL_POINT3D_FRAME is
+ * UpdateLastFrame -- the same walk, the Frame form.
+ * The walk, as the reference writes it: the members are the slots with depth > 0, in the order std::sort gives pair<float, int> (ascending
+ * depth, then index).  A member is fresh when its slot is NULL or holds a point with Observations() < 1.  Every member walked counts, fresh or
+ * held (nPoints), and the loop leaves after the member at position p when depth_p > th_depth && p + 1 > min_points.  Only the fresh members
+ * walked get a point.
+ * A fresh member's point: x3Dc = ((u - cx) * z * invfx, (v - cy) * z * invfy, z) as float products in that order, x3D = mRwc * x3Dc + mOw as
+ * cv::gemm computes it (double accumulation, one rounding per element), mOw = -mRcw.t() * mtcw likewise.  KeyFrame form: what the
+ * constructor, AddObservation, ComputeDistinctiveDescriptors and UpdateNormalAndDepth (src/MapPoint.cc:282-322) leave in a point with this
+ * one observation -- byte for byte the rows msl_refresh_map_points computes for it: normal = (0 + normali / cv::norm(normali)) / 1, so a -0
+ * component becomes +0; dist = {max / scale_factors[nlevels - 1], max = (float)cv::norm(PC) * scale_factors[octave]}.  Frame form
+ * (src/MapPoint.cc:48-71): normal = (P - Ow) / cv::norm(P - Ow) as (float)((double)x * (1.0 / norm)), a -0 component stays; the same dist.
+ * The descriptor is row i in both forms.
+ * Out, per slot [f * cap + i], for every i < cap:
+ *   pt_new             1 where a point is constructed
+ *   cleared            1 where the call site NULLs (CreateNewKeyFrame) or overwrites (UpdateLastFrame) a held point without observations
+ *   new_xyz[3], new_normal[3], new_dist[2], new_desc[32]   the point, in the layouts msl_match_local_points reads as mp_xyz .. mp_desc and the
+ *                      point table keeps as pt_xyz .. pt_desc; zeros where no point was made
+ *   held_out           cur_held as it stands (all -1 with MSL_POINT3D_ALL), with first_id[f] + j in the slot of the j-th created point, -1
+ *                      there when first_id is NULL
+ * Per frame: new_order[f * cap + j] the slots in creation order (the caller's nNextId++ order), -1 beyond n_new[f]; n_walked[f] the
+ * reference's final nPoints (the number of members with MSL_POINT3D_ALL).  Slots at or beyond n_kps[f] get 0 / -1.
+ * Pinned where the reference is undefined or not restated (tests/keyframe_model.py is the sequential model):
+ *   - a NaN depth is no member (z > 0 is false), +inf is one and sorts last; its point is what IEEE arithmetic gives
+ *   - depth == th_depth is not far: the test is depth > th_depth
+ *   - an octave outside [0, nlevels) (an out-of-range read in the reference): as msl_refresh_map_points, UpdateNormalAndDepth writes
+ *     nothing -- the KeyFrame form keeps the constructor's zero normal and zero distances; the Frame form has its normal and zero distances
+ *   - device memory: an id outside [0, n_pts) counts as NULL (fresh, not cleared; held_out keeps it where no point is made); n_kps is
+ *     clamped into 0 .. cap
+ * Limits: n_frames >= 1, cap <= 8192, 0 <= n_pts <= 1048576, mode one of MSL_POINT3D_*, 1 <= nlevels <= MSL_MATCH_MAX_LEVELS, min_points >= 0;
+ * anything else, or a NULL array other than enable / first_id (and cur_held / pt_nobs where they are not read), is refused with
+ * MSL_ERR_INVALID before any launch, with msl_last_error() naming the field, and nothing is written (the _batch form refuses before it
+ * touches a device).  A host-memory call (mem) also checks n_kps inside 0 .. cap and the ids below it -1 or inside the table.  One launch,
+ * one workgroup per frame.  Memory and synchronisation as msl_bow_transform.
+ *
+ * msl_keyframe_decision: for n_frames independent frames, what Tracking::Track does between the pose of a frame and CreateNewKeyFrame, in
+ * the reference's order.  Per frame f a record msl_keyframe_frame and the frame's arrays: depth, cur_held, outlier (mvbOutlier) with n_cur
+ * (`cap` per frame); cur_lheld, line_outlier with n_cur_lines (`lcap`); plane_match[3 k + s] / plane_outlier[3 k + s] in
+ * msl_plane_associate's / msl_pose_optimize's layout with n_planes (`pcap`; a negative plane_match is NULL).  The map: pt_nobs / pt_flags
+ * (bit 0: !isBad()) over n_pts rows, ln_nobs over n_lines rows, held_id / n_kps of the keyframe table (n_tab rows of cap slots).
+ *   step 1   only where flags has MSL_KF_TRACKED_LOCAL_MAP: the tail of TrackLocalMap (src/Tracking.cc:1365-1430).  found_pt[i] /
+ *            found_line[j] = 1 where IncreaseFound() is called (held and not an outlier); n_inliers = mnMatchesInliers over points, lines
+ *            (each with Observations() > 0 unless only_tracking) and map planes.  In place: an outlier map plane's plane_match becomes -1
+ *            (its outlier byte stays); an outlier parallel or vertical plane's becomes -1 and its outlier byte 0.  A map plane that stays
+ *            is the one IncreaseFound() is called on.  track_ok = !(frame_id < last_reloc_frame_id + max_frames && n_inliers < 20) &&
+ *            !(n_inliers < 7).  Where the step is skipped: found_* are 0, n_inliers = n_inliers_in (the stale member), track_ok = the
+ *            MSL_KF_TRACK_OK bit of flags.
+ *   step 2   new_plane[f] = mbNewPlane after :429-436: some k < n_planes with plane_match[3 k] NULL and plane_outlier[3 k] == 0, or, where
+ *            step 1 was skipped (SearchMapByCoefficients did not reset the member), the MSL_KF_NEW_PLANE bit.  UpdateCoefficientsAndPoints
+ *            stays msl_map_plane_merge.
+ *   step 3   only where track_ok: "Clean VO matches" (:450-465).  held_out / outlier_out and lheld_out / line_outlier_out are cur_held /
+ *            outlier and cur_lheld / line_outlier with every held element of Observations() < 1 turned into -1 / 0; plain copies where
+ *            !track_ok; -1 / 0 at and beyond the counts.
+ *   step 4   only where track_ok, on the cleaned arrays: NeedNewKeyFrame (:1433-1508).  need_kf[f] the return value; counts[4 f..] =
+ *            {nRefMatches, nTotal, nMap, nNonTrackedClose}; cond[f] the bits MSL_KF_C1A .. MSL_KF_C2.  nRefMatches is
+ *            KeyFrame::TrackedMapPoints(nMinObs) (src/KeyFrame.cc:199-218) over row ref_kf of held_id.  counts and cond are 0 where the
+ *            function returns before it computes them (!track_ok, only_tracking, local_mapping_stopped, the relocalisation test).
+ * Types, as the reference has them: frame_id is the unsigned long mnId and the id sums (unsigned int + int) wrap at 2^32; ratioMap =
+ * (float)((float)nMap / fmax(1.0f, nTotal)) divides in double (fmax's double overload) and rounds once; nRefMatches * 0.25 is a double
+ * product, nRefMatches * thRefRatio a float product compared with (float)n_inliers; ratioMap < 0.3f and < thMapRatio are float comparisons.
+ * What stays with the caller: IncreaseFound() itself, mlpTemporalPoints, the motion model, CreateNewKeyFrame's KeyFrame object, and the
+ * outlier drop of :505-513 -- one element-wise where(outlier_out, -1, held) over msl_points_3d's held_out.
+ * Pinned: a ref_kf outside the table gives nRefMatches 0; with device memory an id outside its table counts as NULL (not found, no inlier,
+ * not cleaned: copied as it stands) and counts are clamped into 0 .. their capacity.
+ * Limits: n_frames >= 1, cap <= 8192, lcap <= 256, pcap <= 64, n_tab <= 4096, n_pts <= 1048576, n_lines <= 1048576 (each at least 1); anything
+ * else, or a NULL array, is refused as above.  A host-memory call also checks n_cur / n_cur_lines / n_kps inside 0 .. their capacity with
+ * the ids below them -1 or inside their table, n_planes inside 0 .. pcap and ref_kf -1 or inside the table.  One launch, one workgroup per
+ * frame.  Memory and synchronisation as msl_bow_transform. */
+typedef struct msl_point3d_params {
+    float fx, fy, cx, cy;          /* Frame::fx .. cy; invfx = 1.0f / fx, invfy = 1.0f / fy are formed by the library in float */
+    float th_depth;                /* mThDepth */
+    int32_t min_points;            /* 100 */
+    int32_t nlevels;               /* mnScaleLevels */
+    float scale_factors[MSL_MATCH_MAX_LEVELS];   /* mvScaleFactors */
+} msl_point3d_params;
+#define MSL_POINT3D_ALL       0  /* StereoInitialization: every slot with depth > 0, index order, KeyFrame form */
+#define MSL_POINT3D_KEYFRAME  1  /* CreateNewKeyFrame: ascending (depth, index), the th_depth / min_points stop, KeyFrame form */
+#define MSL_POINT3D_FRAME     2  /* UpdateLastFrame: the same walk, Frame form */
+typedef struct msl_keyframe_frame {
+    int32_t flags;                 /* MSL_KF_TRACKED_LOCAL_MAP | MSL_KF_TRACK_OK | MSL_KF_NEW_PLANE */
+    int32_t frame_id;              /* mCurrentFrame.mnId */
+    int32_t last_keyframe_id;      /* mnLastKeyFrameId */
+    int32_t last_reloc_frame_id;   /* mnLastRelocFrameId */
+    int32_t n_kfs;                 /* mpMap->KeyFramesInMap() */
+    int32_t ref_kf;                /* the table row of mpReferenceKF */
+    int32_t n_inliers_in;          /* mnMatchesInliers on entry: read where TrackLocalMap did not run */
+    int32_t local_mapping_idle;    /* AcceptKeyFrames() */
+    int32_t local_mapping_stopped; /* isStopped() || stopRequested() */
+    int32_t keyframes_in_queue;    /* KeyframesInQueue() */
+} msl_keyframe_frame;
+typedef struct msl_keyframe_params {
+    int32_t max_frames, min_frames;   /* mMaxFrames, mMinFrames */
+    float th_depth;                   /* mThDepth */
+    int32_t only_tracking;            /* mbOnlyTracking */
+} msl_keyframe_params;
+#define MSL_KF_TRACKED_LOCAL_MAP 1  /* flags: TrackLocalMap ran on this frame (step 1 runs) */
+#define MSL_KF_TRACK_OK          2  /* flags: bOK, read where step 1 is skipped */
+#define MSL_KF_NEW_PLANE         4  /* flags: mbNewPlane on entry, read where step 1 is skipped */
+#define MSL_KF_C1A 1   /* cond: MaxFrames have passed since the last keyframe */
+#define MSL_KF_C1B 2   /* cond: MinFrames have passed and local mapping is idle */
+#define MSL_KF_C1C 4   /* cond: tracking is weak */
+#define MSL_KF_C2  8   /* cond: few tracked points against the reference keyframe */
+MSL_API int msl_points_3d(msl_match *h, int n_frames, int cap, int n_pts, int mode, const msl_point3d_params *params,
+                          const msl_keypoint *kps_un, const float *depth, const uint8_t *desc, const int32_t *n_kps, const int32_t *cur_held,
+                          const int32_t *pt_nobs, const float *Tcw, const int32_t *enable, const int32_t *first_id, msl_mem mem,
+                          uint8_t *pt_new, uint8_t *cleared, float *new_xyz, float *new_normal, float *new_dist, uint8_t *new_desc,
+                          int32_t *held_out, int32_t *new_order, int32_t *n_new, int32_t *n_walked, msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device matcher handle, always synchronous). */
+MSL_API int msl_points_3d_batch(int device, int n_frames, int cap, int n_pts, int mode, const msl_point3d_params *params,
+                                const msl_keypoint *kps_un, const float *depth, const uint8_t *desc, const int32_t *n_kps,
+                                const int32_t *cur_held, const int32_t *pt_nobs, const float *Tcw, const int32_t *enable,
+                                const int32_t *first_id, msl_mem mem, uint8_t *pt_new, uint8_t *cleared, float *new_xyz, float *new_normal,
+                                float *new_dist, uint8_t *new_desc, int32_t *held_out, int32_t *new_order, int32_t *n_new, int32_t *n_walked,
+                                msl_mem out_mem) MSL_NOEXCEPT;
+MSL_API int msl_keyframe_decision(msl_match *h, int n_frames, int cap, int lcap, int pcap, int n_tab, int n_pts, int n_lines,
+                                  const msl_keyframe_params *params, const msl_keyframe_frame *frames, const float *depth,
+                                  const int32_t *n_cur, const int32_t *cur_held, const uint8_t *outlier, const int32_t *cur_lheld,
+                                  const uint8_t *line_outlier, const int32_t *n_cur_lines, const int32_t *n_planes, const int32_t *pt_nobs,
+                                  const uint8_t *pt_flags, const int32_t *ln_nobs, const int32_t *held_id, const int32_t *n_kps, msl_mem mem,
+                                  int32_t *plane_match, uint8_t *plane_outlier, uint8_t *found_pt, uint8_t *found_line, int32_t *n_inliers,
+                                  uint8_t *track_ok, uint8_t *new_plane, int32_t *held_out, uint8_t *outlier_out, int32_t *lheld_out,
+                                  uint8_t *line_outlier_out, int32_t *counts, uint8_t *cond, int32_t *need_kf, msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device matcher handle, always synchronous). */
+MSL_API int msl_keyframe_decision_batch(int device, int n_frames, int cap, int lcap, int pcap, int n_tab, int n_pts, int n_lines,
+                                        const msl_keyframe_params *params, const msl_keyframe_frame *frames, const float *depth,
+                                        const int32_t *n_cur, const int32_t *cur_held, const uint8_t *outlier, const int32_t *cur_lheld,
+                                        const uint8_t *line_outlier, const int32_t *n_cur_lines, const int32_t *n_planes,
+                                        const int32_t *pt_nobs, const uint8_t *pt_flags, const int32_t *ln_nobs, const int32_t *held_id,
+                                        const int32_t *n_kps, msl_mem mem, int32_t *plane_match, uint8_t *plane_outlier, uint8_t *found_pt,
+                                        uint8_t *found_line, int32_t *n_inliers, uint8_t *track_ok, uint8_t *new_plane, int32_t *held_out,
+                                        uint8_t *outlier_out, int32_t *lheld_out, uint8_t *line_outlier_out, int32_t *counts, uint8_t *cond,
+                                        int32_t *need_kf, msl_mem out_mem) MSL_NOEXCEPT;
+
 /* msl_kfdb: a KeyFrameDatabase (src/KeyFrameDatabase.cc:38-66) on one device.  msl_kfdb_create returns NULL with msl_last_error() when no
  * device is usable.  msl_kfdb_add stores the BowVector of one keyframe exactly as msl_bow_transform wrote it (ascending int32 words, double
  * values, the count -- on the device for MSL_MEM_DEVICE) and returns its slot when the vector is stored; with device memory `h` is the

@@ -2,7 +2,7 @@
 // a LocalMapping entry (handle_form, batch_form) with the list of its NULLs (none_null), the limits that several entry points share
 // (table_limits, line_table_limits, levels_ok) and the row readback of the debug entry points (last_call_row); shared by msl_match.hip,
 // msl_line_match.hip, msl_pose.hip, msl_plane.hip, msl_bow.hip, msl_reloc.hip, msl_pnp.hip, msl_line3d.hip, msl_triangulate.hip, msl_fuse.hip,
-// msl_mappoint.hip, msl_line_fuse.hip, msl_local_map.hip, msl_cull.hip and msl_plane_cloud.hip (internal).
+// msl_mappoint.hip, msl_line_fuse.hip, msl_local_map.hip, msl_cull.hip, msl_plane_cloud.hip and msl_keyframe.hip (internal).
 #pragma once
 
 #include "msl_common.h"
@@ -59,8 +59,8 @@ inline bool none_null(const char *who, std::initializer_list<Named> args) {
 // the device is re-bound at every entry like the other handles.  The line searches (= the tracker's LSDmatcher), msl_pose_optimize, the
 // plane association and the bag-of-words calls run on it too.
 struct msl_match {
-    // The most arrays one entry point stages: msl_triangulate_new_points (12 inputs, 11 outputs).
-    static constexpr int STAGE_SLOTS = 23;
+    // The most arrays one entry point stages: msl_keyframe_decision (14 inputs, 2 in/out, 12 outputs).
+    static constexpr int STAGE_SLOTS = 28;
     int device = 0;
     hipStream_t stream = nullptr; bool ownStream = true;
     // Scratch the kernels of a call hand to one another.  Device-memory calls are asynchronous and ordered only by the stream, so each
@@ -155,7 +155,7 @@ int last_call_row(msl_match *h, const DevBuf &buf, size_t row, size_t n, std::ve
 }
 
 // Kernels that ask for more dynamic LDS than the default limit: the limit is raised once per handle (= per device) and kernel.
-enum LdsKernel { LDS_MATCH_ASSIGN, LDS_LOCAL_ASSIGN, LDS_LINE_ASSIGN_LAST, LDS_LINE_ASSIGN_LOCAL, LDS_BOW_VECTOR, LDS_MATCH_BOW, LDS_KF_ASSIGN, LDS_RELOC_SELECT, LDS_TRI_GROUP, LDS_FUSE_HELD, LDS_FUSE_RESOLVE, LDS_PC_VOXEL, LDS_PC_MERGE };
+enum LdsKernel { LDS_MATCH_ASSIGN, LDS_LOCAL_ASSIGN, LDS_LINE_ASSIGN_LAST, LDS_LINE_ASSIGN_LOCAL, LDS_BOW_VECTOR, LDS_MATCH_BOW, LDS_KF_ASSIGN, LDS_RELOC_SELECT, LDS_TRI_GROUP, LDS_FUSE_HELD, LDS_FUSE_RESOLVE, LDS_PC_VOXEL, LDS_PC_MERGE, LDS_POINTS3D };
 template <class K>
 hipError_t allow_lds(msl_match *h, LdsKernel k, K kernel, size_t max_bytes) {
     if (h->ldsSet >> k & 1u) return hipSuccess;
