@@ -178,7 +178,7 @@ __global__ __launch_bounds__(256) void k_pyramid(OrbDev P) {
 //   tile     (cw + 6) x (ch + 6) pixels into LDS, four bytes per load and store
 //   stage    at a threshold: quick test -> list -> score -> 3x3 suppression inside the cell -> keys
 //     quick test   a lane owns groups of four horizontally adjacent pixels, enumerated over a row pitch padded to four (the columns >= cw are masked):
-//                  13 word reads, byte offsets by v_alignbyte, then fast_quick4 on 16-bit pairs.  The groups' (row, group, element) order is
+//                  13 word reads, byte offset and widening by one v_perm per 16-bit pair (fast_quick4_at).  The groups' (row, group, element) order is
 //                  the cell's row-major order; four ballots give every passing pixel its place in the list
 //     score        64 list entries at a time: full lanes whatever the candidates' density (fast_score16)
 //     suppression  over the list again; a ballot orders the kept pixels, which go straight to cellKeys (row-major order, as k_octree reads them)
@@ -251,8 +251,8 @@ __global__ __launch_bounds__(64) void k_fast(OrbDev P) {
                 const uint32_t b0 = w[3 * wp], b1 = w[3 * wp + 1], b2 = w[3 * wp + 2];                  // the centre row
                 const uint32_t d0 = w[5 * wp], d1 = w[5 * wp + 1], d2 = w[5 * wp + 2];                  // 2 rows down
                 const uint32_t e0 = w[6 * wp], e1 = w[6 * wp + 1];                                      // 3 rows down
-                m4 = fast_quick4(fast_bytes(b0, b1, 3), /*0*/ fast_bytes(e0, e1, 3), /*8*/ fast_bytes(u0, u1, 3), /*4*/ fast_bytes(b1, b2, 2), /*12*/ b0,
-                                 /*2*/ fast_bytes(d1, d2, 1), /*10*/ fast_bytes(a0, a1, 1), /*6*/ fast_bytes(a1, a2, 1), /*14*/ fast_bytes(d0, d1, 1), thQuick);
+                m4 = fast_quick4_at({b0, b1, 3}, /*0*/ {e0, e1, 3}, /*8*/ {u0, u1, 3}, /*4*/ {b1, b2, 2}, /*12*/ {b0, b1, 0},
+                                    /*2*/ {d1, d2, 1}, /*10*/ {a0, a1, 1}, /*6*/ {a1, a2, 1}, /*14*/ {d0, d1, 1}, thQuick);
                 if (cw - c0 < 4) m4 &= (1u << (cw - c0)) - 1u;
             }
             const unsigned long long q0 = __ballot(m4 & 1u), q1 = __ballot(m4 & 2u), q2 = __ballot(m4 & 4u), q3 = __ballot(m4 & 8u);

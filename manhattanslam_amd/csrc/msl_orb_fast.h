@@ -55,30 +55,68 @@ MSL_FAST_HD uint32_t fast_bytes(uint32_t lo, uint32_t hi, int n) { return (lo >>
 // A 9-arc of 16 contains at least one pixel of every opposite pair, so a pixel whose score reaches th passes; a pixel that fails cannot score
 // >= th.  Its score is left 0, which changes neither the threshold tests nor the non-maximum suppression of any kept pixel (a kept pixel
 // scores >= th, above every such neighbour either way).
+// (one half of it: the pairs of two of the four pixels -> the word whose two sign bits say "passes")
+MSL_FAST_HD uint32_t fast_quick_pair(s16x2 v, s16x2 a0, s16x2 a8, s16x2 a4, s16x2 a12, s16x2 a2, s16x2 a10, s16x2 a6, s16x2 a14, s16x2 t) {
+    const s16x2 lo = pk_max(pk_max(pk_min(a0, a8), pk_min(a4, a12)), pk_max(pk_min(a2, a10), pk_min(a6, a14)));
+    const s16x2 hi = pk_min(pk_min(pk_max(a0, a8), pk_max(a4, a12)), pk_min(pk_max(a2, a10), pk_max(a6, a14)));
+    // bright <=> lo + th - v < 0, dark <=> v + th - hi < 0: the sign bits of the two halves
+    return pk_bits(pk_sub(pk_add(lo, t), v)) | pk_bits(pk_sub(pk_add(v, t), hi));
+}
+MSL_FAST_HD unsigned fast_quick_bits(uint32_t sign0, uint32_t sign1) {
+    return ((sign0 >> 15) & 1u) | ((sign0 >> 30) & 2u) | ((sign1 >> 13) & 4u) | ((sign1 >> 28) & 8u);
+}
 MSL_FAST_HD unsigned fast_quick4(uint32_t c, uint32_t r0, uint32_t r8, uint32_t r4, uint32_t r12, uint32_t r2, uint32_t r10, uint32_t r6,
                                  uint32_t r14, int th) {
     const s16x2 t = pk_make(th, th);
     uint32_t sign[2];
     MSL_FAST_UNROLL
-    for (int half = 0; half < 2; half++) {
-        const s16x2 v = fast_pair(c, half);
-        const s16x2 a0 = fast_pair(r0, half), a8 = fast_pair(r8, half), a4 = fast_pair(r4, half), a12 = fast_pair(r12, half);
-        const s16x2 a2 = fast_pair(r2, half), a10 = fast_pair(r10, half), a6 = fast_pair(r6, half), a14 = fast_pair(r14, half);
-        const s16x2 lo = pk_max(pk_max(pk_min(a0, a8), pk_min(a4, a12)), pk_max(pk_min(a2, a10), pk_min(a6, a14)));
-        const s16x2 hi = pk_min(pk_min(pk_max(a0, a8), pk_max(a4, a12)), pk_min(pk_max(a2, a10), pk_max(a6, a14)));
-        // bright <=> lo + th - v < 0, dark <=> v + th - hi < 0: the sign bits of the two halves
-        sign[half] = pk_bits(pk_sub(pk_add(lo, t), v)) | pk_bits(pk_sub(pk_add(v, t), hi));
+    for (int half = 0; half < 2; half++)
+        sign[half] = fast_quick_pair(fast_pair(c, half), fast_pair(r0, half), fast_pair(r8, half), fast_pair(r4, half), fast_pair(r12, half),
+                                     fast_pair(r2, half), fast_pair(r10, half), fast_pair(r6, half), fast_pair(r14, half), t);
+    return fast_quick_bits(sign[0], sign[1]);
+}
+
+// The same test on the words as the kernel reads them: four pixels that start n bytes (0..3) into the little-endian byte string lo, hi.  The byte
+// offset and the widening to a 16-bit pair are ONE byte permute per pair (v_perm_b32: selector bytes 0..7 pick a byte of the string, 0x0c a zero)
+// where fast_pair(fast_bytes(lo, hi, n), half) is a v_alignbyte_b32 and three more instructions.
+struct FastSrc { uint32_t lo, hi; int n; };
+MSL_FAST_HD uint32_t fast_perm(uint32_t hi, uint32_t lo, uint32_t sel) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_perm(hi, lo, sel);
+#else
+    uint32_t r = 0;
+    for (int b = 0; b < 4; b++) {
+        const uint32_t s = (sel >> (8 * b)) & 0xFFu;   // (only the selector values this header uses)
+        const uint32_t byte = s < 4 ? (lo >> (8 * s)) & 0xFFu : s < 8 ? (hi >> (8 * (s - 4))) & 0xFFu : 0u;
+        r |= byte << (8 * b);
     }
-    return ((sign[0] >> 15) & 1u) | ((sign[0] >> 30) & 2u) | ((sign[1] >> 13) & 4u) | ((sign[1] >> 28) & 8u);
+    return r;
+#endif
+}
+MSL_FAST_HD s16x2 fast_pair_at(FastSrc s, int half) {
+    const uint32_t b = (uint32_t)(s.n + 2 * half);   // bytes b, b + 1 of the string, each zero-extended to 16 bits
+    return pk_from_bits(fast_perm(s.hi, s.lo, b | 0x0c00u | ((b + 1u) << 16) | 0x0c000000u));
+}
+MSL_FAST_HD unsigned fast_quick4_at(FastSrc c, FastSrc r0, FastSrc r8, FastSrc r4, FastSrc r12, FastSrc r2, FastSrc r10, FastSrc r6, FastSrc r14, int th) {
+    const s16x2 t = pk_make(th, th);
+    uint32_t sign[2];
+    MSL_FAST_UNROLL
+    for (int half = 0; half < 2; half++)
+        sign[half] = fast_quick_pair(fast_pair_at(c, half), fast_pair_at(r0, half), fast_pair_at(r8, half), fast_pair_at(r4, half), fast_pair_at(r12, half),
+                                     fast_pair_at(r2, half), fast_pair_at(r10, half), fast_pair_at(r6, half), fast_pair_at(r14, half), t);
+    return fast_quick_bits(sign[0], sign[1]);
 }
 
 // FAST-9/16 corner score of a pixel of value v with the 16 ring values ring[0..15] (in ring order):
 // score = max(a, -b) - 1 with a = max over the 16 nine-arcs of min(d), b = min over arcs of max(d), d = v - ring; since
-// -b = max over arcs of min(-d), both halves are the same min/max network: run it once on packed (d, -d) pairs.
+// -b = max over arcs of min(-d), both halves are the same min/max network: run it once on packed pairs.  v is the same in all sixteen d, so the
+// network runs on (r, -r) and v is added once at the end: over an arc min(v - r) = v + min(-r) and min(r - v) = min(r) - v, and the maximum over
+// the arcs commutes with the constant likewise.  0 <= v, ring[k] <= 255: every value stays within +-255, the initial -256 below all of them.
+// One multiplication builds a pair: r * -65535 = r - (r << 16), low half r, high half -r mod 2^16 (three instructions per ring value before).
 MSL_FAST_HD int fast_score16(int v, const int *ring) {
     s16x2 x[16], lo2[16], lo4[16];
     MSL_FAST_UNROLL
-    for (int k = 0; k < 16; k++) { const int d = v - ring[k]; x[k] = pk_make(d, -d); }
+    for (int k = 0; k < 16; k++) x[k] = pk_from_bits((uint32_t)(ring[k] * -65535));
     MSL_FAST_UNROLL
     for (int k = 0; k < 16; k++) lo2[k] = pk_min(x[k], x[(k + 1) & 15]);
     MSL_FAST_UNROLL
@@ -86,7 +124,7 @@ MSL_FAST_HD int fast_score16(int v, const int *ring) {
     s16x2 a = pk_make(-256, -256);
     MSL_FAST_UNROLL
     for (int k = 0; k < 16; k++) a = pk_max(a, pk_min(pk_min(lo4[k], lo4[(k + 4) & 15]), x[(k + 8) & 15]));
-    const int p = a.x, n = a.y;
+    const int p = v + a.y, n = a.x - v;   // a.y = -min over arcs of max(r), a.x = max over arcs of min(r)
     return (p > n ? p : n) - 1;
 }
 

@@ -15,7 +15,8 @@ def kernels(path, tmp):
     """{kernel name: [instruction text, ...]} of the object (a .hip source is compiled first)."""
     run = lambda *a: subprocess.run(a, check=True, capture_output=True, text=True).stdout
     if path.endswith(".hip"):
-        run("/opt/rocm/bin/hipcc", *FLAGS, "-c", path, "-o", os.path.join(tmp, "k.o"))
+        own = run("make", "-s", "-C", CSRC, "print-file-flags", "F=" + os.path.basename(path)[:-4]).split()   # what the Makefile adds for this file alone
+        run("/opt/rocm/bin/hipcc", *FLAGS, *own, "-c", path, "-o", os.path.join(tmp, "k.o"))
         path = os.path.join(tmp, "k.o")
     fat, co = os.path.join(tmp, "fatbin"), os.path.join(tmp, "gfx950.co")
     run(LLVM + "llvm-objcopy", "--dump-section", ".hip_fatbin=" + fat, path, os.devnull)

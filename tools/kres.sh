@@ -2,6 +2,7 @@
 # Kernel resource usage of one .hip file (gfx950): name, VGPRs, SGPR spills, VGPR spills, scratch, LDS.   tools/kres.sh <file.hip> [name filter]
 R=$(cd "$(dirname "$0")/.." && pwd); C=$R/manhattanslam_amd/csrc
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fvisibility=hidden -fno-gpu-flush-denormals-to-zero -I$C -I$R/include"
+FLAGS="$FLAGS $(make -s -C $C print-file-flags F=$(basename "${1%.hip}"))"   # what the Makefile adds for this file alone
 /opt/rocm/bin/hipcc $FLAGS -Rpass-analysis=kernel-resource-usage -c $1 -o /dev/null 2>&1 | python3 -c "
 import re, sys
 cur = None; rows = {}
