@@ -1769,6 +1769,109 @@ MSL_API int msl_keyframe_decision_batch(int device, int n_frames, int cap, int l
                                         uint8_t *outlier_out, int32_t *lheld_out, uint8_t *line_outlier_out, int32_t *counts, uint8_t *cond,
                                         int32_t *need_kf, msl_mem out_mem) MSL_NOEXCEPT;
 
+/* ---- Keyframe planes: the plane half of keyframe creation and the Manhattan tables of Map ----
+ * The two steps between msl_keyframe_decision and the next frame's msl_plane_associate / msl_manhattan_detect that a keyframe with planes
+ * needs; with them the Manhattan-mode chain crosses a keyframe on one stream.  tests/kfplanes_model.py is the
+ * sequential model; every output is an integer, a copy, or a pinned product, so every comparison is byte equality.
+ *
+ * msl_keyframe_planes: for n_frames independent new keyframes the plane loop of Tracking::CreateNewKeyFrame (src/Tracking.cc:1620-1645),
+ * with mode MSL_KFPLANES_INIT that of Tracking::StereoInitialization (:594-602), and what the KeyFrame constructor and SetPose do with
+ * planes (src/KeyFrame.cc:50-52, 74-86).  Per frame f a record msl_kfplanes_frame: enable (0: no in/out array of the frame is touched and
+ * its outputs get their nothing values below, the need_kf gate as msl_points_3d's enable), kf_slot (the keyframe's row of the keyframe
+ * tables), kf_id (mnId).  In (mem): plane_coef, plane_npts, n_planes, Tcw as for msl_plane_associate / msl_manhattan_detect (`pcap` per
+ * frame), plane_outlier[3 k + s] as msl_keyframe_decision leaves it (only byte s = 0, mvbPlaneOutlier, is read).
+ * In/out (out_mem): plane_match[3 k + s] as msl_keyframe_decision leaves it; the map-plane table mp_w / mp_flags / n_map as for
+ * msl_plane_associate with mp_first_kf[j] = mnFirstKFid (`mcap` per frame), appended in place; row kf_slot of kf_Rwc / kf_coef / kf_npts in
+ * exactly msl_manhattan_detect's layout (`kcap` rows per frame).
+ * The walk over k < n_planes[f], MSL_KFPLANES_KEYFRAME: a parallel (s = 1) or vertical (s = 2) plane with plane_outlier[3 k] == 0 gets
+ * AddParObservation / AddVerObservation; a held plane (s = 0) gets AddObservation and is MSL_KFPLANES_HELD; a plane that is not held and has
+ * plane_outlier[3 k] != 0 is MSL_KFPLANES_SKIPPED; every other plane is new.  MSL_KFPLANES_INIT: every plane is new, no parallel or vertical
+ * observation is made, and plane_match[3 k] becomes the new row (:601); in keyframe mode plane_match is left alone, as the reference leaves
+ * mCurrentFrame.  New rows get the indices n_map[f], n_map[f] + 1, ... in ascending k (the creation order, GetAllMapPlanes() order):
+ * mp_w = ComputePlaneWorldCoeff(k), bit for bit msl_plane_associate's pM_out; mp_flags = 1; mp_first_kf = kf_id; n_map[f] grows by n_new[f].
+ * When mcap is exhausted that plane and every later new plane is MSL_KFPLANES_NO_ROOM and is not created.
+ * Out (out_mem), rows k < n_planes[f]: kf_plane_match[3 k + s] the KeyFrame's mvpMapPlanes / mvpParallelPlanes / mvpVerticalPlanes (the
+ * frame's, -1 for NULL, with the new row in s = 0 where one was made); plane_new[k]; obs_add[3 k + s] = 1 where AddObservation /
+ * AddParObservation / AddVerObservation takes effect for (row, keyframe, k) -- the maps refuse a second entry for a keyframe
+ * (src/MapPlane.cc:48-68), so only the first k that names a row in slot s is set; merge_into[k] in msl_map_plane_merge's layout (the new
+ * row, -1 for every other plane: held planes were merged at :429-436); status[k] (MSL_KFPLANES_*).  Per frame: Twc[12] doubles for that
+ * merge = Converter::toMatrix4d(GetPoseInverse()), the float Twc of KeyFrame::SetPose widened (Rwc = Rcw^T copied, Ow = -Rwc * tcw as one
+ * cv::gemm: double accumulation, alpha = -1, one rounding); n_new[f]; set_not_erase[f] = 1 when :1637 is reached (keyframe mode only, a
+ * MSL_KFPLANES_NO_ROOM plane included).  Row kf_slot: kf_Rwc = Rcw^T, kf_coef / kf_npts the frame's rows, zero at and beyond n_planes[f].
+ * A frame with enable == 0: merge_into -1, plane_new / obs_add / status 0, kf_plane_match the frame's, n_new and set_not_erase 0, Twc
+ * written; the map-plane table, the keyframe rows and plane_match keep their bytes.
+ * Limits: n_frames in 1 .. 65535, pcap <= 64, mcap <= 4096, kcap <= 4096 (each at least 1), mode one of MSL_KFPLANES_*; anything else, or a
+ * NULL array, is refused with MSL_ERR_INVALID before any launch with msl_last_error() naming the field, and nothing is written (the _batch
+ * form refuses before it touches a device).  A host-memory call also checks n_planes inside 0 .. pcap, n_map inside 0 .. mcap, every
+ * plane_match below n_planes -1 or inside [0, n_map), kf_slot inside [0, kcap) and kf_id >= 0.  Device memory: counts are clamped, a
+ * plane_match outside [0, n_map) counts as NULL, a frame whose kf_slot is outside [0, kcap) counts as not enabled, and nothing is read or
+ * written outside an array; no kernel writes rows k >= n_planes[f] of the per-plane outputs or rows of the map-plane table it does not
+ * create: device-memory arrays keep their bytes there (a host-memory output is copied back whole: unspecified there).  One launch, one
+ * wave per frame.
+ *
+ * msl_manhattan_observe: for n_frames independent keyframes the plane part of LocalMapping::ProcessNewKeyFrame (src/LocalMapping.cc:
+ * 160-218) with Map::AddManhattanObservation / AddPartialManhattanObservation (src/Map.cc:247-275, keys compared as unordered sets).
+ * In (mem): the frame records above, kf_plane_match (only s = 0 is read), plane_coef, n_planes, mp_flags, mp_first_kf, n_map,
+ * params->mf_ver_th.  In/out (out_mem): full_tab / n_full (`fcap`) and part_tab / n_part (`qcap`) in exactly the layout and sort order
+ * msl_manhattan_detect reads.  A new entry's kf is kf_slot and its ia, ib, ic are GetIndexInKeyFrame at insertion: the first k of
+ * kf_plane_match that holds the row.
+ * The loop, i < j < k: the planes held and not bad, their rows distinct, angle < mf_ver_th && angle > -mf_ver_th on the float dot product
+ * of the coefficients, left to right (a dot product equal to the threshold, or NaN, does not pass: not msl_manhattan_detect's gate, which
+ * passes both); the triples inside the angle12 gate; the pair added after its k loop; an existing key -- in the table or added earlier in
+ * the loop -- is never replaced.  Two frame planes may hold one row; every occurrence of a key carries the same entry.
+ * Out (out_mem): added_full[f], added_part[f]; set_not_erase[f] = 1 only where a key was really added (SetNotErase sits behind the
+ * count() != 0 return); recent_plane[k], k < n_planes[f], the mlpRecentAddedMapPlanes pushes of :160-170 (held, not bad, mp_first_kf ==
+ * kf_id); status[f] the bits MSL_MANHATTAN_FULL_NO_ROOM / MSL_MANHATTAN_PART_NO_ROOM: a table that cannot take all new keys of the keyframe
+ * is left exactly as it was, its count included, and its added count is 0.  The merged tables are built in scratch of the handle and copied
+ * back by the same launch.  A frame with enable == 0 (or, device memory, kf_slot outside [0, kcap)) adds nothing: zeros.
+ * Limits: n_frames in 1 .. 65535, pcap <= 64, mcap <= 4096, fcap <= 65536, qcap <= 65536, kcap <= 4096 (each at least 1); refusals as above.
+ * The limits hold one at a time: the call keeps 8 fcap + 6 qcap ints of scratch per frame on the handle (the merged tables and the lower
+ * bounds of their new keys), 3.5 MiB per frame at fcap = qcap = 65536, so the batch is also bounded by n_frames * (8 fcap + 6 qcap) * 4 bytes
+ * of free device memory; a call whose scratch cannot be allocated fails with MSL_ERR_HIP (out of memory) before any launch and changes nothing.
+ * A host-memory call also checks n_planes, n_map, n_full and n_part inside 0 .. their capacity, kf_plane_match[3 k] below n_planes -1 or
+ * inside [0, n_map), kf_slot and kf_id, and that both tables are sorted as msl_manhattan_detect requires; sorting device-memory tables is
+ * the caller's contract.  One launch, one workgroup per frame.  Memory and synchronisation as msl_bow_transform. */
+typedef struct msl_kfplanes_frame {
+    int32_t enable;                /* 0: the frame makes no keyframe (need_kf) */
+    int32_t kf_slot;               /* the keyframe's row of kf_Rwc / kf_coef / kf_npts, and the kf of its table entries */
+    int32_t kf_id;                 /* mnId */
+    int32_t _pad;
+} msl_kfplanes_frame;
+#define MSL_KFPLANES_KEYFRAME 0   /* mode: CreateNewKeyFrame */
+#define MSL_KFPLANES_INIT     1   /* mode: StereoInitialization */
+#define MSL_KFPLANES_SKIPPED  0   /* status: not held and an outlier (also: the frame is not enabled) */
+#define MSL_KFPLANES_HELD     1   /* status: AddObservation on the held plane */
+#define MSL_KFPLANES_NEW      2   /* status: a new map plane */
+#define MSL_KFPLANES_NO_ROOM  3   /* status: a new map plane that mcap has no row for */
+#define MSL_MANHATTAN_FULL_NO_ROOM 1   /* status: fcap cannot take the keyframe's new triples */
+#define MSL_MANHATTAN_PART_NO_ROOM 2   /* status: qcap cannot take the keyframe's new pairs */
+MSL_API int msl_keyframe_planes(msl_match *h, int n_frames, int pcap, int mcap, int kcap, int mode, const msl_kfplanes_frame *frames,
+                                const float *plane_coef, const int32_t *plane_npts, const int32_t *n_planes, const float *Tcw,
+                                const uint8_t *plane_outlier, msl_mem mem, int32_t *plane_match, float *mp_w, uint8_t *mp_flags,
+                                int32_t *mp_first_kf, int32_t *n_map, float *kf_Rwc, float *kf_coef, int32_t *kf_npts,
+                                int32_t *kf_plane_match, uint8_t *plane_new, uint8_t *obs_add, int32_t *merge_into, double *Twc,
+                                int32_t *n_new, int32_t *set_not_erase, int32_t *status, msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device matcher handle, always synchronous). */
+MSL_API int msl_keyframe_planes_batch(int device, int n_frames, int pcap, int mcap, int kcap, int mode, const msl_kfplanes_frame *frames,
+                                      const float *plane_coef, const int32_t *plane_npts, const int32_t *n_planes, const float *Tcw,
+                                      const uint8_t *plane_outlier, msl_mem mem, int32_t *plane_match, float *mp_w, uint8_t *mp_flags,
+                                      int32_t *mp_first_kf, int32_t *n_map, float *kf_Rwc, float *kf_coef, int32_t *kf_npts,
+                                      int32_t *kf_plane_match, uint8_t *plane_new, uint8_t *obs_add, int32_t *merge_into, double *Twc,
+                                      int32_t *n_new, int32_t *set_not_erase, int32_t *status, msl_mem out_mem) MSL_NOEXCEPT;
+MSL_API int msl_manhattan_observe(msl_match *h, int n_frames, int pcap, int mcap, int fcap, int qcap, int kcap, const msl_plane_params *params,
+                                  const msl_kfplanes_frame *frames, const int32_t *kf_plane_match, const float *plane_coef,
+                                  const int32_t *n_planes, const uint8_t *mp_flags, const int32_t *mp_first_kf, const int32_t *n_map,
+                                  msl_mem mem, int32_t *full_tab, int32_t *n_full, int32_t *part_tab, int32_t *n_part, int32_t *added_full,
+                                  int32_t *added_part, int32_t *set_not_erase, uint8_t *recent_plane, int32_t *status,
+                                  msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device matcher handle, always synchronous). */
+MSL_API int msl_manhattan_observe_batch(int device, int n_frames, int pcap, int mcap, int fcap, int qcap, int kcap,
+                                        const msl_plane_params *params, const msl_kfplanes_frame *frames, const int32_t *kf_plane_match,
+                                        const float *plane_coef, const int32_t *n_planes, const uint8_t *mp_flags,
+                                        const int32_t *mp_first_kf, const int32_t *n_map, msl_mem mem, int32_t *full_tab, int32_t *n_full,
+                                        int32_t *part_tab, int32_t *n_part, int32_t *added_full, int32_t *added_part,
+                                        int32_t *set_not_erase, uint8_t *recent_plane, int32_t *status, msl_mem out_mem) MSL_NOEXCEPT;
+
 /* msl_kfdb: a KeyFrameDatabase (src/KeyFrameDatabase.cc:38-66) on one device.  msl_kfdb_create returns NULL with msl_last_error() when no
  * device is usable.  msl_kfdb_add stores the BowVector of one keyframe exactly as msl_bow_transform wrote it (ascending int32 words, double
  * values, the count -- on the device for MSL_MEM_DEVICE) and returns its slot when the vector is stored; with device memory `h` is the

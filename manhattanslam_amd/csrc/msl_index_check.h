@@ -4,9 +4,10 @@
 // msl_fuse_candidates (targets_ok), the neighbours of msl_triangulate_new_points (neighbours_ok: msl_triangulate.hip), the held ids, the graph
 // and the keyframe rows of the local map (held_ok, graph_ok, kf_rows_ok: msl_local_map.hip), and the candidate rows, the origin and the recent
 // elements of the cullings (kf_rows_ok, origin_ok, recent_ok: msl_cull.hip), and the offsets, vertex indices and target rows of the plane clouds
-// (offsets_ok, vertex_indices_ok, merge_into_ok: msl_plane_cloud.hip).  Pure host functions on plain arrays: no HIP call, no allocation
+// (offsets_ok, vertex_indices_ok, merge_into_ok: msl_plane_cloud.hip), and the counts, held planes, keyframe rows and Manhattan tables of a
+// keyframe with planes (counts_ok, plane_match_ok, kf_slots_ok, tables_sorted_ok: msl_keyframe_planes.hip).  Pure host functions on plain arrays: no HIP call, no allocation
 // through the library, no global state, so a plain C++ program can call them (tests/mappoint_csr_host.cpp, tests/mapping_lists_host.cpp,
-// tests/localmap_check_host.cpp, tests/cull_check_host.cpp, tests/plane_cloud_check_host.cpp).  Each returns true, or false with a message that names the field in err; the
+// tests/localmap_check_host.cpp, tests/cull_check_host.cpp, tests/plane_cloud_check_host.cpp, tests/kfplanes_check_host.cpp).  Each returns true, or false with a message that names the field in err; the
 // caller puts its own name in front ("%s: %s").
 #pragma once
 
@@ -235,6 +236,56 @@ inline bool merge_into_ok(int n_frames, int pcap, int mcap, const int32_t *merge
             if (j < -1 || j >= nm) { snprintf(err, err_len, "merge_into[%d][%d] is row %d of %d", f, k, j, nm); return false; }
         }
     }
+    return true;
+}
+
+// ==== the keyframe planes and the Manhattan tables ===========================================================================================
+// Per-frame counts inside 0 .. cap (what / limit: the names of the counts and of the capacity).
+inline bool counts_ok(const char *what, const char *limit, int n_frames, int cap, const int32_t *n, char *err, size_t err_len) {
+    for (int f = 0; f < n_frames; f++)
+        if (n[f] < 0 || n[f] > cap) { snprintf(err, err_len, "%s[%d] is %d outside 0 .. %s = %d", what, f, (int)n[f], limit, cap); return false; }
+    return true;
+}
+
+// The first `slots` of the three map planes every frame plane below n_planes[f] names: -1 or a row of the frame's n_map[f] map planes
+// (counts already checked by counts_ok; what: the argument's name).
+inline bool plane_match_ok(const char *what, int n_frames, int pcap, int slots, const int32_t *match, const int32_t *n_planes,
+                           const int32_t *n_map, char *err, size_t err_len) {
+    for (int f = 0; f < n_frames; f++)
+        for (int k = 0; k < n_planes[f]; k++)
+            for (int s = 0; s < slots; s++) {
+                const int j = match[3 * ((size_t)f * pcap + k) + s];
+                if (j < -1 || j >= n_map[f]) { snprintf(err, err_len, "%s[%d][%d][%d] is row %d of %d", what, f, k, s, j, (int)n_map[f]); return false; }
+            }
+    return true;
+}
+
+// The keyframe of every frame: its row inside the keyframe tables of kcap rows and its id not negative (slot / id: the n_frames values).
+inline bool kf_slots_ok(int n_frames, int kcap, const int32_t *slot, const int32_t *id, int stride, char *err, size_t err_len) {
+    for (int f = 0; f < n_frames; f++) {
+        const int s = slot[(size_t)f * stride], i = id[(size_t)f * stride];
+        if (s < 0 || s >= kcap) { snprintf(err, err_len, "frames[%d].kf_slot is keyframe %d of %d", f, s, kcap); return false; }
+        if (i < 0) { snprintf(err, err_len, "frames[%d].kf_id is %d, below 0", f, i); return false; }
+    }
+    return true;
+}
+
+// n_frames Manhattan tables of cap entries of `stride` ints, of which the first n[f] (already checked by counts_ok) are read: the first w
+// ints of an entry ascending, the entries strictly ascending by them, lexicographically (what: the table's name).
+inline bool tables_sorted_ok(const char *what, int n_frames, int cap, int stride, int w, const int32_t *tab, const int32_t *n, char *err,
+                             size_t err_len) {
+    for (int f = 0; f < n_frames; f++)
+        for (int e = 0; e < n[f]; e++) {
+            const int32_t *x = tab + ((size_t)f * cap + e) * stride;
+            bool ok = true;
+            for (int q = 1; q < w; q++) ok = ok && x[q - 1] <= x[q];
+            if (ok && e > 0) {
+                int c = 0;
+                for (int q = 0; q < w && c == 0; q++) c = x[q - stride] < x[q] ? -1 : (x[q - stride] > x[q] ? 1 : 0);
+                ok = c < 0;
+            }
+            if (!ok) { snprintf(err, err_len, "%s[%d] is not sorted by its keys at entry %d", what, f, e); return false; }
+        }
     return true;
 }
 

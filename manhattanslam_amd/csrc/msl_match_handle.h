@@ -2,7 +2,7 @@
 // a LocalMapping entry (handle_form, batch_form) with the list of its NULLs (none_null), the limits that several entry points share
 // (table_limits, line_table_limits, levels_ok) and the row readback of the debug entry points (last_call_row); shared by msl_match.hip,
 // msl_line_match.hip, msl_pose.hip, msl_plane.hip, msl_bow.hip, msl_reloc.hip, msl_pnp.hip, msl_line3d.hip, msl_triangulate.hip, msl_fuse.hip,
-// msl_mappoint.hip, msl_line_fuse.hip, msl_local_map.hip, msl_cull.hip, msl_plane_cloud.hip and msl_keyframe.hip (internal).
+// msl_mappoint.hip, msl_line_fuse.hip, msl_local_map.hip, msl_cull.hip, msl_plane_cloud.hip, msl_keyframe.hip and msl_keyframe_planes.hip (internal).
 #pragma once
 
 #include "msl_common.h"
@@ -96,6 +96,8 @@ struct msl_match {
     // large to accumulate in LDS; per item ((frame, detector plane) or (frame, frame plane)) the coarse cloud, its count, status and
     // coefficients
     msl::DevBuf pcSlab, pcWork;
+    // msl_manhattan_observe: per frame the merged tail of each Manhattan table and the lower bounds of its new keys, built before the copy back
+    msl::DevBuf kfpScratch;
     // Device copies of host-memory arguments, one pool for every entry point (msl::Stage deals the slots out in declaration order).
     // Sharing is sound because every call that touches the pool returns with the stream drained (Stage::finish synchronises whenever
     // either side is host memory, and only then is a slot used), so no slot is live when the next call starts.

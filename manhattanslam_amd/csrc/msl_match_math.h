@@ -65,6 +65,18 @@ __device__ __forceinline__ void camera_centre(const float *T, float Ow[3]) {
     gemm3(T, true, -1.0, tcw, nullptr, Ow);
 }
 
+// Frame::ComputePlaneWorldCoeff (src/Frame.cc:656-660): pM = mTcw^T * coef (cv::Mat CV_32F product): double accumulation in k order, one rounding; row 3 of mTcw is 0 0 0 1.
+__device__ __forceinline__ void world_coef(const float *T, const float *c, float *pM) {
+    for (int r = 0; r < 4; r++) {
+        double s = 0.0;
+        for (int k = 0; k < 4; k++) {
+            const float a = k < 3 ? T[4 * k + r] : (r == 3 ? 1.0f : 0.0f);
+            s += (double)a * (double)c[k];
+        }
+        pM[r] = (float)s;
+    }
+}
+
 // The counter-based sampler of the RANSAC loops: draw j of iteration k, a value in [0, left) =
 // mulhi32(fmix32(fmix32(seed ^ k * 0x9E3779B1) ^ (j + 1) * 0x85EBCA77), left).  sampler_iteration is the inner hash, the same for every j.
 __device__ __forceinline__ unsigned fmix32(unsigned h) {

@@ -46,18 +46,6 @@ struct MfDev {
     float *Rcw; int32_t *found, *full, *choice;
 };
 
-// pM = mTcw^T * coef (cv::Mat CV_32F product): double accumulation in k order, one rounding; row 3 of mTcw is 0 0 0 1.
-__device__ __forceinline__ void world_coef(const float *T, const float *c, float *pM) {
-    for (int r = 0; r < 4; r++) {
-        double s = 0.0;
-        for (int k = 0; k < 4; k++) {
-            const float a = k < 3 ? T[4 * k + r] : (r == 3 ? 1.0f : 0.0f);
-            s += (double)a * (double)c[k];
-        }
-        pM[r] = (float)s;
-    }
-}
-
 __device__ __forceinline__ float minf_keep(float a, float b) { return b < a ? b : a; }   // NaN never wins (neither side holds one here)
 
 // Wave-wide minimum of v (every lane gets it): a DPP inclusive min-scan, then lane 63 broadcast.  Lanes without a DPP source read 100,
