@@ -74,6 +74,15 @@ MSL_API int msl_debug_div100(const float *x_host, double *out_host, size_t n) MS
  * kernels evaluate it -- a rotating chain over 16 lanes (msl_sf_sp_dev.h); huber != 0: entries +-inf stand for the Huber tail's DOUBLE constant
  * +-0.4 (src/SurfelFusion.cpp:494-503).  Host arrays; synchronous. */
 MSL_API int msl_debug_chain_sum(const float *x_host, const int32_t *n_host, int lists, int huber, float *out_host) MSL_NOEXCEPT;
+/* Test hook: out[i] = the Newton step of the seed update (src/SurfelFusion.cpp:505) for the numerator sumA[i] and inr[i] (0 .. 256) in-band depths as
+ * kb_update_seeds evaluates it -- one float division; literal[i] = the reference's expression (float)((double)(-sumA) / ((double)sumB + 10.0)), sumB =
+ * (float)(2 inr), evaluated on the device as well.  Host arrays; synchronous. */
+MSL_API int msl_debug_newton_delta(const float *sumA_host, const int32_t *inr_host, size_t n, float *out_host, float *literal_host) MSL_NOEXCEPT;
+/* Test hook: the FP64 sums over the 16 lanes of a seed group as kb_seed_plane forms them.  Group q holds nvals (4: the Jacobian, 10: the Hessian) values
+ * per lane, x[(q nvals + k) 16 + l].  nvals = 4: out[16 q + l] = what lane l holds after the joint reduction (the total of value l >> 2); nvals = 10:
+ * out[16 q ..] = the column-major 4x4 matrix (Hessian + 5 I, both triangles) the group's lanes store.  ref[(q nvals + k) 16 + l] = the plain butterfly
+ * (row_ror:8, row_ror:4, two quad permutes) of value k as lane l receives it.  Host arrays; synchronous. */
+MSL_API int msl_debug_group_sums(const double *x_host, int groups, int nvals, double *out_host, double *ref_host) MSL_NOEXCEPT;
 
 /* The per-hypothesis stage of the last msl_pnp_ransac call on h (host output, synchronous): *n_out = the iterations pair `pair` ran
  * (max(mRansacMaxIts, n_iterations), 0 when N < mRansacMinInliers); for the first min(*n_out, k_cap) of them the double pose compute_pose

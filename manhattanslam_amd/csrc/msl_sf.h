@@ -340,6 +340,8 @@ void sp_launch_depth_u16(hipStream_t st, const void *src, size_t srcStride, size
                          float factor);
 int sp_debug_div100(const float *x_host, double *out_host, size_t n);
 int sp_debug_chain(const float *x_host, const int32_t *n_host, int lists, int huber, float *out_host);
+int sp_debug_newton(const float *sumA_host, const int32_t *inr_host, size_t n, float *out_host, float *literal_host);                 // msl_sf_sp_seeds.hip
+int sp_debug_group_sums(const double *x_host, int groups, int nvals, double *out_host, double *ref_host);                              // msl_sf_sp_plane.hip
 // msl_sf_fuse.hip (blkStride: entries per per-sub-block count slice, msl_sf::blkStride)
 void map_launch_fuse(KernelProfiler &prof, hipStream_t st, const SfDev &P, int slot, const FrameDev &F, int nSubGrid, int nSubHint, bool deferred, bool dealt, unsigned blkStride);
 // msl_sf_compact.hip

@@ -99,6 +99,8 @@ int msl_sf_debug_index(msl_sf *h, int32_t *out) noexcept {
 int msl_debug_deal(const uint32_t *keys_host, int n_subblocks, uint32_t *deal_host) noexcept { try { return map_debug_deal(keys_host, n_subblocks, deal_host); } MSL_ABI_CATCH_INT }
 int msl_debug_div100(const float *x_host, double *out_host, size_t n) noexcept { try { return sp_debug_div100(x_host, out_host, n); } MSL_ABI_CATCH_INT }
 int msl_debug_chain_sum(const float *x_host, const int32_t *n_host, int lists, int huber, float *out_host) noexcept { try { return sp_debug_chain(x_host, n_host, lists, huber, out_host); } MSL_ABI_CATCH_INT }
+int msl_debug_newton_delta(const float *sumA_host, const int32_t *inr_host, size_t n, float *out_host, float *literal_host) noexcept { try { return sp_debug_newton(sumA_host, inr_host, n, out_host, literal_host); } MSL_ABI_CATCH_INT }
+int msl_debug_group_sums(const double *x_host, int groups, int nvals, double *out_host, double *ref_host) noexcept { try { return sp_debug_group_sums(x_host, groups, nvals, out_host, ref_host); } MSL_ABI_CATCH_INT }
 const char *msl_sf_kernel_name(int k) noexcept { try { return (k >= 0 && k < MSL_SF_NKERNELS) ? kSfNames[k] : ""; } MSL_ABI_CATCH_PTR }
 
 }  // extern "C"

@@ -4,7 +4,7 @@
 //     kb_assign                           one wave per three dual cells: argmin over <= 4 seeds (:333-415)
 //     kb_prop_lds | kb_prop x 6 + kb_prop_finish    the min-fixpoint t(s) over the worklist kb_assign left
 //     kb_commit_px                        a pixel takes its pick iff its seed was unstable before it in raster order
-//     k_debug_div100                      test hook of div100_exact
+//     k_debug_div100                      test hook of sp_div100_of_float
 
 #include "msl_sf_sp_dev.h"
 
@@ -32,7 +32,7 @@ __global__ __launch_bounds__(256) void kb_seed_init(SfDev P) {
     vec3b(P, F, (float)imageY, (float)imageX, s.r, s.g, s.b);
     s.meanIntensity = gray_at(P, F, imageY, imageX);
     s.meanDepth = depth_at(P, F, imageY, imageX);
-    if (s.meanDepth < 0.01) {
+    if (sp_lt_001(s.meanDepth)) {   // `< 0.01` (:559), float form (msl_sf_sp_arith.h)
         int xb = spX * SP + SP / 2 - SP, yb = spY * SP + SP / 2 - SP;
         int xe = xb + SP * 2, ye = yb + SP * 2;
         xb = xb > 0 ? xb : 0; yb = yb > 0 ? yb : 0;
@@ -41,7 +41,7 @@ __global__ __launch_bounds__(256) void kb_seed_init(SfDev P) {
         for (int j = yb; j < ye && !found; j++)
             for (int i = xb; i < xe; i++) {
                 const float d = depth_at(P, F, j, i);
-                if (d > 0.01) { s.meanDepth = d; found = true; break; }
+                if (sp_gt_001(d)) { s.meanDepth = d; found = true; break; }   // `> 0.01` (:572)
             }
     }
     P.seeds[(size_t)slot * P.nseeds + seedI] = s;
@@ -133,7 +133,7 @@ __global__ __launch_bounds__(64 * ASSIGN_WAVES) void kb_assign(SfDev P, int it, 
         float myInvDepth = dIn[k];
         if (it == 0) {
             myInvDepth = 0.0f;
-            if (dIn[k] > 0.01) myInvDepth = (float)(1.0 / (double)dIn[k]);
+            if (sp_gt_001(dIn[k])) myInvDepth = (float)(1.0 / (double)dIn[k]);   // `> 0.01` (:373), float form
             if (inImg[k] && !isPlane) *byte_off_w(pxInv, 4u * (unsigned)p) = myInvDepth;
         }
         const bool pxHasDepth = myInvDepth > 0;
@@ -152,10 +152,10 @@ __global__ __launch_bounds__(64 * ASSIGN_WAVES) void kb_assign(SfDev P, int it, 
             const float dist = (C.x - colF) * (C.x - colF) + (C.y - rowF) * (C.y - rowF);
             nodepthCost += dist / ((SP / 2) * (SP / 2));
             const float intensityDiff = C.meanIntensity - myIntensity;
-            nodepthCost = (float)((double)nodepthCost + div100_exact((double)(intensityDiff * intensityDiff)));
+            nodepthCost = sp_cost_add_intensity(nodepthCost, intensityDiff);   // (one correction step: the dividend is a float, msl_sf_sp_arith.h)
             const bool has = candHas && pxHasDepth;
             const float inverseDepthDiff = (float)(C.invDepth - myInvD);
-            const float withDepth = (float)((double)nodepthCost + (double)(inverseDepthDiff * inverseDepthDiff) * 400.0);
+            const float withDepth = sp_cost_add_depth(nodepthCost, inverseDepthDiff);   // (one FMA: float * 400.0 is exact in binary64)
             const float depthCost = has ? withDepth : nodepthCost;
             allHasDepth = allHasDepth && (has || !use);
             const bool bd = use && depthCost < minDistDepth, bn = use && nodepthCost < minDistNodepth;
@@ -306,7 +306,7 @@ __global__ __launch_bounds__(256) void kb_commit_px(SfDev P, int nSlots) {
 
 __global__ void k_debug_div100(const float *x, double *out, long long n) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = div100_exact((double)(x[i] * x[i]));
+    if (i < n) out[i] = sp_div100_of_float(x[i] * x[i]);   // (what kb_assign evaluates: the dividend is a float product)
 }
 
 }  // namespace

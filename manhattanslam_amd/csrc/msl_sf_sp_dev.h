@@ -4,6 +4,7 @@
 #pragma once
 
 #include "msl_sf.h"
+#include "msl_sf_sp_arith.h"
 
 using namespace msl;
 using namespace msl::sf;
@@ -13,29 +14,20 @@ using namespace msl::sf;
 namespace {
 
 // ---- exact arithmetic ------------------------------------------------------------------------------------------------------
-// Correctly rounded x / 100.0 (x >= 0 finite) without the ~35-instruction f64 divide: two Markstein steps with
-// y = RN(1/100).  q1 is a faithful quotient (error < 1 ulp), so the final fused correction rounds to RN(x/100)
-// (Markstein's theorem; 100 = 1.5625 * 2^6 is not an all-ones significand).  Checked against true division on
-// the GPU by tests/test_surfel_gpu.py::test_div100_exact.
-__device__ __forceinline__ double div100_exact(double x) {
-    const double y = 0.01;                       // RN(1/100)
-    const double q0 = x * y;
-    const double q1 = fma(fma(-q0, 100.0, x), y, q0);
-    return fma(fma(-q1, 100.0, x), y, q1);
-}
-
+// The float / double mixtures on plain values -- the division by 100.0, the cost terms, the Newton quotient and the comparisons with 0.01 / 0.2 --
+// are in msl_sf_sp_arith.h, which a host program includes too.
+//
 // Comparisons of a FLOAT x with one of the reference's DOUBLE constants c (HUBER_RANGE 0.4, MAX_ANGLE_COS 0.1, the 0.05 / 0.1 depth limits), which
 // C++ evaluates as (double)x OP c: none of these constants is a float, and for each of them the float nearest to it, cf = (float)c, is the float
 // next ABOVE it (asserted below), so there is no float in [c, cf) and the sets of floats on either side of c and of cf are the same:
 //   (double)x <  c  <=>  x <  cf        (double)x >  -c  <=>  x >  -cf
 //   (double)x >= c  <=>  x >= cf        (double)x <= -c  <=>  x <= -cf        (double)x > c  <=>  x >= cf
 // (NaN: false on both sides.)  One v_cmp_f32 instead of v_cvt_f64_f32 + v_cmp_f64 per test.
-constexpr float float_below(float f) { return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, f) - 1u); }   // (positive finite f)
 constexpr float HUBER_RANGE_F = (float)HUBER_RANGE, MAX_ANGLE_COS_F = (float)MAX_ANGLE_COS, DEPTH_005_F = 0.05f, DEPTH_01_F = 0.1f;
-static_assert((double)HUBER_RANGE_F > HUBER_RANGE && (double)float_below(HUBER_RANGE_F) < HUBER_RANGE, "0.4f is the float next above 0.4");
-static_assert((double)MAX_ANGLE_COS_F > MAX_ANGLE_COS && (double)float_below(MAX_ANGLE_COS_F) < MAX_ANGLE_COS, "0.1f is the float next above 0.1");
-static_assert((double)DEPTH_005_F > 0.05 && (double)float_below(DEPTH_005_F) < 0.05, "0.05f is the float next above 0.05");
-static_assert((double)DEPTH_01_F > 0.1 && (double)float_below(DEPTH_01_F) < 0.1, "0.1f is the float next above 0.1");
+static_assert((double)HUBER_RANGE_F > HUBER_RANGE && (double)sp_float_below(HUBER_RANGE_F) < HUBER_RANGE, "0.4f is the float next above 0.4");
+static_assert((double)MAX_ANGLE_COS_F > MAX_ANGLE_COS && (double)sp_float_below(MAX_ANGLE_COS_F) < MAX_ANGLE_COS, "0.1f is the float next above 0.1");
+static_assert((double)DEPTH_005_F > 0.05 && (double)sp_float_below(DEPTH_005_F) < 0.05, "0.05f is the float next above 0.05");
+static_assert((double)DEPTH_01_F > 0.1 && (double)sp_float_below(DEPTH_01_F) < 0.1, "0.1f is the float next above 0.1");
 __device__ __forceinline__ bool in_huber_band(float r) { return r < HUBER_RANGE_F && r > -HUBER_RANGE_F; }   // residual < HUBER_RANGE && residual > -HUBER_RANGE
 
 // Strictly sequential (left-to-right) float sums over 16-byte aligned LDS arrays; wide LDS reads are issued
@@ -117,24 +109,30 @@ __device__ __forceinline__ int rows_max_i32(int v) {
     return max(max(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)), max(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
 }
 
-// Sum over the 16 lanes of a DPP row (= one seed group); every lane receives the total.  Row rotations by 8 and 4
-// and quad permutes run in the VALU (a few cycles) instead of ds_bpermute round trips through the LDS crossbar.
+// FP64 sums over the 16 lanes of a DPP row (= one seed group): row rotations by 8 and 4 and quad permutes run in the VALU (a few cycles) instead of
+// ds_bpermute round trips through the LDS crossbar.  The schedules -- the one-value butterfly sp_group_sum and the transposed sp_group_sum4 /
+// sp_group_sum10 kb_seed_plane uses -- are in msl_sf_sp_arith.h, written on the lane operations below.
 template <int CTRL>
 __device__ __forceinline__ double dpp_mov_d(double v) {
     const unsigned long long u = __double_as_longlong(v);
     // (bound_ctrl: the row rotations and quad permutes used here give every lane a source lane, so the `old` operand is never read -- without it the
-    // compiler materialises a zero for it in front of every move: 2 of 5 instructions per value and step of group_sum_d)
+    // compiler materialises a zero for it in front of every move: 2 of 5 instructions per value and step of the group sums)
     const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)u, CTRL, 0xF, 0xF, true);
     const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(u >> 32), CTRL, 0xF, 0xF, true);
     return __longlong_as_double(((unsigned long long)hi << 32) | lo);
 }
-__device__ __forceinline__ double group_sum_d(double v) {
-    v += dpp_mov_d<0x128>(v);   // row_ror:8
-    v += dpp_mov_d<0x124>(v);   // row_ror:4
-    v += dpp_mov_d<0x4E>(v);    // quad_perm [2,3,0,1]
-    v += dpp_mov_d<0xB1>(v);    // quad_perm [1,0,3,2]
-    return v;
-}
+// The lane operations on a double per lane.  sel: a DPP move with a bank mask and `old` = the value the lane keeps does the select and the move in one
+// instruction per register half.
+struct RowOpsD {
+    template <int CTRL, int BANKS> static __device__ __forceinline__ double sel(double old, double src) {
+        const unsigned long long uo = __double_as_longlong(old), us = __double_as_longlong(src);
+        const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp((int)(unsigned)uo, (int)(unsigned)us, CTRL, 0xF, BANKS, false);
+        const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp((int)(unsigned)(uo >> 32), (int)(unsigned)(us >> 32), CTRL, 0xF, BANKS, false);
+        return __longlong_as_double(((unsigned long long)hi << 32) | lo);
+    }
+    template <int CTRL> static __device__ __forceinline__ double mov(double v) { return dpp_mov_d<CTRL>(v); }
+    static __device__ __forceinline__ double add(double a, double b) { return a + b; }
+};
 
 }  // namespace
 

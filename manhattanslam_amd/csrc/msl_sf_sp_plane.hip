@@ -4,6 +4,7 @@
 //                                         equations; the tex words of the seed's cell         (reference src/SurfelFusion.cpp:91-165, :597-773)
 //     kb_seed_finish                      one thread per seed: plane normalisation, FuseRec, the candidate surfel (:744-773, :291-329)
 //     kb_tex_strips                       the tex words outside the whole cells (sizes that are not multiples of 8)
+//     k_debug_group_sums                  test hook of the transposed FP64 group sums
 
 #include "msl_sf_sp_dev.h"
 
@@ -20,7 +21,7 @@ __device__ __forceinline__ void pixel_normal(const SfDev &P, int row, int col, f
     // back_project of the right / down neighbours with the tabulated quotients: (col+1, row) and (col, row+1)
     float rightX = cx1 * rightDepth, rightY = ryr * rightDepth, rightZ = rightDepth;
     float downX = cxr * downDepth, downY = ry1 * downDepth, downZ = downDepth;
-    if (myZ < DEPTH_01_F || rightZ < DEPTH_01_F || downZ < DEPTH_01_F) return;   // `< 0.1` (:628): float form, see float_below
+    if (myZ < DEPTH_01_F || rightZ < DEPTH_01_F || downZ < DEPTH_01_F) return;   // `< 0.1` (:628): float form, see msl_sf_sp_dev.h
     rightX = rightX - myX; rightY = rightY - myY; rightZ = rightZ - myZ;
     downX = downX - myX; downY = downY - myY; downZ = downZ - myZ;
     float normX = rightY * downZ - rightZ * downY;
@@ -320,7 +321,8 @@ __global__ __launch_bounds__(64) void kb_seed_plane(SfDev P, int nSlots) {
                 jstep(t, pX[oc] - sumX, pY[oc] - sumY, pZ[oc] - sumZ);
             }
         }
-        J0 = group_sum_d(J0); J1 = group_sum_d(J1); J2 = group_sum_d(J2); J3 = group_sum_d(J3);
+        // the four sums over the group's lanes, transposed: lane 4 a + b receives J_a, which is all the update below reads (msl_sf_sp_arith.h)
+        const double Jg = sp_group_sum4<RowOpsD>(J0, J1, J2, J3);
         const bool sameSet = mask == prevMask;
         const unsigned diffGroups = (unsigned)((__ballot(!sameSet) >> (g * 16)) & 0xFFFFull);   // uniform per group
         prevMask = mask;
@@ -343,14 +345,10 @@ __global__ __launch_bounds__(64) void kb_seed_plane(SfDev P, int nSlots) {
                     hstep(t, pX[oc] - sumX, pY[oc] - sumY, pZ[oc] - sumZ);
                 }
             }
-            H00 = group_sum_d(H00); H01 = group_sum_d(H01); H02 = group_sum_d(H02); H03 = group_sum_d(H03);
-            H11 = group_sum_d(H11); H12 = group_sum_d(H12); H13 = group_sum_d(H13);
-            H22 = group_sum_d(H22); H23 = group_sum_d(H23); H33 = group_sum_d(H33);
-            if (l == 0) {   // the (symmetric) Hessian + 5 I, column-major
-                double *m = s_h[g];
-                m[0] = H00 + 5; m[1] = H01; m[2] = H02; m[3] = H03; m[4] = H01; m[5] = H11 + 5; m[6] = H12; m[7] = H13;
-                m[8] = H02; m[9] = H12; m[10] = H22 + 5; m[11] = H23; m[12] = H03; m[13] = H13; m[14] = H23; m[15] = H33 + 5;
-            }
+            // the ten sums, transposed: each total arrives in one bank of the group, whose first lane stores it -- the (symmetric) Hessian + 5 I,
+            // column-major (msl_sf_sp_arith.h)
+            const SpHessSums<double> hs = sp_group_sum10<RowOpsD>(H00, H01, H02, H03, H11, H12, H13, H22, H23, H33);
+            sp_hessian_store(s_h[g], l, hs.c0, hs.c1, hs.c2);
             __builtin_amdgcn_wave_barrier();
             {
                 const double *m = s_h[g];
@@ -367,7 +365,7 @@ __global__ __launch_bounds__(64) void kb_seed_plane(SfDev P, int nSlots) {
             __builtin_amdgcn_wave_barrier();
         }
         // upd[r] = ((inv[0*4+r] J0 + inv[1*4+r] J1) + inv[2*4+r] J2) + inv[3*4+r] J3; lane l holds inv[l], its column is l >> 2
-        const double prod = invl * (ca == 0 ? J0 : ca == 1 ? J1 : ca == 2 ? J2 : J3);
+        const double prod = invl * Jg;   // (lane l holds J of its column l >> 2)
         // lanes r = 0..3 of the group (column 0, row r) collect their row: lane r + 4 a holds the term of column a -- row_ror:n hands lane i the value of
         // lane i - n (mod 16), so n = 12, 8, 4 fetch the lanes 4, 8, 12 ahead; the other lanes compute sums nobody reads
         const double q0 = prod, q1 = dpp_mov_d<0x12C>(prod), q2 = dpp_mov_d<0x128>(prod), q3 = dpp_mov_d<0x124>(prod);
@@ -481,6 +479,35 @@ __global__ __launch_bounds__(256) void kb_tex_strips(SfDev P) {
     P.tex[(size_t)slot * P.pxStride + p] = make_uint2(__float_as_uint(F.depthG()[(size_t)y * P.dstride + x]), P.index[(size_t)slot * P.pxStride + p]);
 }
 
+// Test hook of the FP64 group sums: group q (the 16 lanes of row q & 3 of wave q >> 2) holds nvals (4 or 10) values per lane, x[(q nvals + k) 16 + l], and
+// reduces them exactly the way kb_seed_plane reduces its Jacobian (4: out[16 q + l] = what lane l holds afterwards, J_(l >> 2)) or its Hessian (10: out[16 q
+// ..] = the matrix sp_hessian_store leaves in the LDS, over a NaN fill).  ref[(q nvals + k) 16 + l] = the one-value butterfly of value k in lane l.
+__global__ __launch_bounds__(64) void k_debug_group_sums(const double *x, double *out, double *ref, int groups, int nvals) {
+    __shared__ __attribute__((aligned(16))) double s_m[4][16];
+    const int g = threadIdx.x >> 4, l = threadIdx.x & 15, q = blockIdx.x * 4 + g;
+    const bool in = q < groups;   // (no lane leaves early: the row operations need all sixteen)
+    double v[10];
+#pragma unroll
+    for (int k = 0; k < 10; k++) v[k] = (in && k < nvals) ? x[((size_t)q * nvals + k) * 16 + l] : 0.0;
+    double res;
+    if (nvals == 4) {
+        res = sp_group_sum4<RowOpsD>(v[0], v[1], v[2], v[3]);
+    } else {
+        const SpHessSums<double> hs = sp_group_sum10<RowOpsD>(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9]);
+        s_m[g][l] = __builtin_nan("");
+        __builtin_amdgcn_wave_barrier();
+        sp_hessian_store(s_m[g], l, hs.c0, hs.c1, hs.c2);
+        __builtin_amdgcn_wave_barrier();
+        res = s_m[g][l];
+    }
+    if (in) out[(size_t)q * 16 + l] = res;
+#pragma unroll
+    for (int k = 0; k < 10; k++) {
+        const double r = sp_group_sum<RowOpsD>(v[k]);
+        if (in && k < nvals) ref[((size_t)q * nvals + k) * 16 + l] = r;
+    }
+}
+
 }  // namespace
 
 namespace msl {
@@ -499,6 +526,19 @@ void sp_launch_plane(KernelProfiler &prof, hipStream_t sp, const SfDev &P, int n
         const int nStrip = (W - P.spW * SP) * P.spH * SP + W * (H - P.spH * SP);
         hipLaunchKernelGGL(kb_tex_strips, dim3((unsigned)((nStrip + 255) / 256), (unsigned)n), dim3(256), 0, sp, P);
     }
+}
+
+int sp_debug_group_sums(const double *x_host, int groups, int nvals, double *out_host, double *ref_host) {
+    if (groups <= 0) return MSL_OK;
+    if (!x_host || !out_host || !ref_host || (nvals != 4 && nvals != 10)) return MSL_ERR_INVALID;
+    const size_t nx = sizeof(double) * 16 * (size_t)nvals * (size_t)groups, no = sizeof(double) * 16 * (size_t)groups;
+    DevBuf x, out, ref;
+    MSL_HIP_TRY(grow_all(0, {{x, nx}, {out, no}, {ref, nx}}));
+    MSL_HIP_TRY(hipMemcpy(x.p, x_host, nx, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_debug_group_sums, dim3((unsigned)((groups + 3) / 4)), dim3(64), 0, 0, (const double *)x.p, (double *)out.p, (double *)ref.p, groups, nvals);
+    MSL_HIP_TRY(hipMemcpy(out_host, out.p, no, hipMemcpyDeviceToHost));
+    MSL_HIP_TRY(hipMemcpy(ref_host, ref.p, nx, hipMemcpyDeviceToHost));
+    return MSL_OK;
 }
 
 }  // namespace sf

@@ -2,6 +2,7 @@
 //     kb_update_seeds<STRADDLE>           16 lanes per seed: ordered window gather, Huber mean (reference src/SurfelFusion.cpp:428-515)
 //     kb_commit_seeds                     one thread per seed: the per-seed scalar end; chunk-abort (`return`) semantics: restore-only
 //     k_debug_chain                       test hook of the rotating chains
+//     k_debug_newton                      test hook of the Newton quotient
 
 #include "msl_sf_sp_dev.h"
 
@@ -101,7 +102,7 @@ __global__ __launch_bounds__(16 * UPD_SEEDS) void kb_update_seeds(SfDev P, int i
             for (int e = 0; e < 4; e++) {
                 const int col = colc + e;
                 const bool own = rowOk && (!STRADDLE || col >= col0) && col >= xb && col < xe && idq[m].v[e] == seedI;
-                hd[e] = own && dq[m].v[e] >= DEPTH_01_F;   // `> 0.1` (:452), float form (float_below)
+                hd[e] = own && dq[m].v[e] >= DEPTH_01_F;   // `> 0.1` (:452), float form (msl_sf_sp_dev.h)
                 if (own) { sumX += col; sumY += j; sumI += gq[m].v[e]; cnt++; }
                 c += hd[e] ? 1 : 0;
             }
@@ -190,11 +191,10 @@ __global__ __launch_bounds__(16 * UPD_SEEDS) void kb_update_seeds(SfDev P, int i
             sa = anyTail ? chain_block_huber(sa, t) : chain_block_f32(sa, t);
         }
         const float sumA = row_lane_f32<15>(sa);
-        const float sumB = (float)(2 * inr);
-        const float deltaDepth = (float)((double)(-sumA) / ((double)sumB + 10.0));
+        const float deltaDepth = sp_newton_delta(sumA, inr);   // (float)((double)(-sumA) / ((double)sumB + 10.0)), sumB = (float)(2 * inr): one float division (msl_sf_sp_arith.h)
         if (open) {
             meanDepth = meanDepth + deltaDepth;
-            if ((deltaDepth < 0.01 && deltaDepth > -0.01) || newtonI == 4) open = false;
+            if ((sp_lt_001(deltaDepth) && sp_gt_neg001(deltaDepth)) || newtonI == 4) open = false;   // `deltaDepth < 0.01 && deltaDepth > -0.01` (:507), float form
         }
     }
     USTAMP();   // 3: Newton steps
@@ -244,7 +244,7 @@ __global__ __launch_bounds__(256) void kb_commit_seeds(SfDev P, int it) {
     int tR = 0, tG = 0, tB = 0;
     vec3b(P, F, mY, mX, tR, tG, tB);
     const float updateDiff = fabsf(preIntensity - sumIntensity) + fabsf(preX - mX) + fabsf(preY - mY);
-    const bool tStable = updateDiff < 0.2;
+    const bool tStable = sp_lt_02(updateDiff);   // `updateDiff < 0.2` (:489), float form
     const float tDepth = U.depthLoop ? U.meanDepth : 0.0f;   // no valid depth among the seed's pixels: 0 (:489-490)
     uint4 w0 = w0o, w2 = w2o, w3 = w3o;
     w0.x = __float_as_uint(mX); w0.y = __float_as_uint(mY);
@@ -277,6 +277,15 @@ __global__ __launch_bounds__(64) void k_debug_chain(const float *x, const int *n
     if (q < lists && l == 15) out[q] = s;
 }
 
+// Test hook of the Newton quotient: out[i] = kb_update_seeds' deltaDepth for the numerator sumA[i] and inr[i] in-band depths (the float division),
+// literal[i] = the reference's float / double expression, both evaluated here.
+__global__ __launch_bounds__(256) void k_debug_newton(const float *sumA, const int *inr, float *out, float *literal, long long n) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    out[i] = sp_newton_delta(sumA[i], inr[i]);
+    literal[i] = sp_newton_delta_literal(sumA[i], inr[i]);
+}
+
 }  // namespace
 
 namespace msl {
@@ -300,6 +309,20 @@ int sp_debug_chain(const float *x_host, const int32_t *n_host, int lists, int hu
     MSL_HIP_TRY(hipMemcpy(cnt.p, n_host, sizeof(int) * (size_t)lists, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_debug_chain, dim3((unsigned)((lists + 3) / 4)), dim3(64), 0, 0, (const float *)x.p, (const int *)cnt.p, (float *)out.p, lists, huber);
     MSL_HIP_TRY(hipMemcpy(out_host, out.p, sizeof(float) * (size_t)lists, hipMemcpyDeviceToHost));
+    return MSL_OK;
+}
+
+int sp_debug_newton(const float *sumA_host, const int32_t *inr_host, size_t n, float *out_host, float *literal_host) {
+    if (n == 0) return MSL_OK;
+    if (!sumA_host || !inr_host || !out_host || !literal_host) return MSL_ERR_INVALID;
+    for (size_t i = 0; i < n; i++) if (inr_host[i] < 0 || inr_host[i] > SP_NEWTON_MAX_INR) return MSL_ERR_INVALID;
+    DevBuf a, c, out, lit;
+    MSL_HIP_TRY(grow_all(0, {{a, sizeof(float) * n}, {c, sizeof(int) * n}, {out, sizeof(float) * n}, {lit, sizeof(float) * n}}));
+    MSL_HIP_TRY(hipMemcpy(a.p, sumA_host, sizeof(float) * n, hipMemcpyHostToDevice));
+    MSL_HIP_TRY(hipMemcpy(c.p, inr_host, sizeof(int) * n, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_debug_newton, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (const float *)a.p, (const int *)c.p, (float *)out.p, (float *)lit.p, (long long)n);
+    MSL_HIP_TRY(hipMemcpy(out_host, out.p, sizeof(float) * n, hipMemcpyDeviceToHost));
+    MSL_HIP_TRY(hipMemcpy(literal_host, lit.p, sizeof(float) * n, hipMemcpyDeviceToHost));
     return MSL_OK;
 }
 
