@@ -612,9 +612,10 @@ MSL_API int msl_pose_optimize_translation_batch(int device, int n_frames, int ca
  * Counts: n_planes[f] is clamped to [0, pcap] and n_map[f] to [0, mcap]; entries beyond the clamped counts and points outside every
  * clamped offset range are never read, and no kernel writes rows k >= n_planes[f] of plane_match, plane_w, plane_has and pM_out:
  * device-memory arrays keep their bytes there (host-memory outputs other than plane_match are copied back whole: unspecified there).
- * Limits: pcap <= 64, mcap <= 4096, ptcap <= 2^22; larger values are refused with MSL_ERR_INVALID before any launch.  Asynchronous on the
- * matcher handle's stream when inputs and outputs are device memory; with host memory on either side it returns when the caller's buffers
- * are its own again. */
+ * Limits: pcap <= 64, mcap <= 4096, ptcap <= 2^22; larger values, a value below 1 (n_frames too) and a NULL array other than pM_out are
+ * refused with MSL_ERR_INVALID before any launch, with msl_last_error() naming the argument, and nothing is written (the _batch form
+ * refuses before it touches a device).  Asynchronous on the matcher handle's stream when inputs and outputs are device memory; with host
+ * memory on either side it returns when the caller's buffers are its own again. */
 typedef struct msl_plane_params {
     float d_th, a_th, ver_th, par_th;   /* Plane.AssociationDisRef, AssociationAngRef, VerticalThreshold, ParallelThreshold (src/Tracking.cc:144-154) */
     float mf_ver_th;                    /* Plane.MFVerticalThreshold: msl_manhattan_detect only */
@@ -657,9 +658,11 @@ MSL_API int msl_plane_associate_batch(int device, int n_frames, int pcap, int mc
  * every integer output is exact.  One launch (one workgroup per frame).
  * Counts: n_planes[f], n_map[f], n_full[f] and n_part[f] are clamped to [0, pcap], [0, mcap], [0, fcap] and [0, qcap]; entries beyond
  * the clamped counts are never read (host-memory tables are sort-checked over the clamped counts).
- * Limits: pcap <= 64, mcap <= 4096, fcap <= 65536, qcap <= 65536, kcap <= 4096; larger values are refused with MSL_ERR_INVALID before any
- * launch.  Asynchronous on the matcher handle's stream when inputs and outputs are device memory; with host memory on either side it
- * returns when the caller's buffers are its own again. */
+ * Limits: pcap <= 64, mcap <= 4096, fcap <= 65536, qcap <= 65536, kcap <= 4096; larger values, a value below 1 (n_frames too), a NULL array
+ * other than choice and an unsorted host-memory table are refused with MSL_ERR_INVALID before any launch, with msl_last_error() naming
+ * the argument (the table and its frame), and nothing is written (the _batch form refuses before it touches a device).  Asynchronous on
+ * the matcher handle's stream when inputs and outputs are device memory; with host memory on either side it returns when the caller's
+ * buffers are its own again. */
 MSL_API int msl_manhattan_detect(msl_match *h, int n_frames, int pcap, int mcap, int fcap, int qcap, int kcap, const msl_plane_params *params,
                                  const float *plane_coef, const int32_t *plane_npts, const int32_t *n_planes, const int32_t *plane_match,
                                  const uint8_t *mp_flags, const int32_t *n_map, const int32_t *full_tab, const int32_t *n_full,
@@ -724,8 +727,10 @@ MSL_API int msl_manhattan_detect_batch(int device, int n_frames, int pcap, int m
  * No kernel writes rows beyond the counts (plane_coef, plane_npts, plane_src and pt_off beyond n_out, points beyond the last offset, status
  * beyond n_planes, mp_pt_off_out / merge_status beyond n_map): device-memory arrays keep their bytes there.
  * Limits: n_frames <= 65535, n_vertices <= MSL_PLANE_CLOUD_MAX_VERTICES, max_planes <= 64, pcap <= 64, mcap <= 4096, ptcap and fptcap <= 2^22,
- * 1 / 32 <= leaf, max_iterations in [1, 4096], probability in [0, 1]; anything else is refused with MSL_ERR_INVALID before any launch.
- * Asynchronous on the matcher handle's stream when inputs and outputs are device memory. */
+ * 1 / 32 <= leaf, max_iterations in [1, 4096], probability in [0, 1] (every count and capacity at least 1); anything else, or a NULL
+ * array other than the colour arrays, is refused with MSL_ERR_INVALID before any launch, with msl_last_error() naming the argument, and
+ * nothing is written (the _batch forms refuse before they touch a device).  Asynchronous on the matcher handle's stream when inputs and
+ * outputs are device memory. */
 #define MSL_PLANE_CLOUD_MAX_VOXELS 4096
 #define MSL_PLANE_CLOUD_MAX_VERTICES 131072
 #define MSL_PLANE_CLOUD_KEPT      0   /* in the output */

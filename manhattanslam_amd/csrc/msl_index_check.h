@@ -5,10 +5,12 @@
 // and the keyframe rows of the local map (held_ok, graph_ok, kf_rows_ok: msl_local_map.hip), and the candidate rows, the origin and the recent
 // elements of the cullings (kf_rows_ok, origin_ok, recent_ok: msl_cull.hip), and the offsets, vertex indices and target rows of the plane clouds
 // (offsets_ok, vertex_indices_ok, merge_into_ok: msl_plane_cloud.hip), and the counts, held planes, keyframe rows and Manhattan tables of a
-// keyframe with planes (counts_ok, plane_match_ok, kf_slots_ok, tables_sorted_ok: msl_keyframe_planes.hip).  Pure host functions on plain arrays: no HIP call, no allocation
-// through the library, no global state, so a plain C++ program can call them (tests/mappoint_csr_host.cpp, tests/mapping_lists_host.cpp,
-// tests/localmap_check_host.cpp, tests/cull_check_host.cpp, tests/plane_cloud_check_host.cpp, tests/kfplanes_check_host.cpp).  Each returns true, or false with a message that names the field in err; the
-// caller puts its own name in front ("%s: %s").
+// keyframe with planes (counts_ok, plane_match_ok, kf_slots_ok: msl_keyframe_planes.hip; tables_sorted_ok: msl_keyframe_planes.hip and
+// msl_manhattan_detect in msl_plane.hip, which pass the entry layout of msl_plane_tables.h).  Pure host functions on plain arrays: no HIP call, no
+// allocation through the library, no global state, so a plain C++ program can call them (tests/mappoint_csr_host.cpp,
+// tests/mapping_lists_host.cpp, tests/localmap_check_host.cpp, tests/cull_check_host.cpp, tests/plane_cloud_check_host.cpp,
+// tests/kfplanes_check_host.cpp).  Each returns true, or false with a message that names the field in err; the caller puts its own name in
+// front ("%s: %s").
 #pragma once
 
 #include <stdint.h>
@@ -270,12 +272,14 @@ inline bool kf_slots_ok(int n_frames, int kcap, const int32_t *slot, const int32
     return true;
 }
 
-// n_frames Manhattan tables of cap entries of `stride` ints, of which the first n[f] (already checked by counts_ok) are read: the first w
-// ints of an entry ascending, the entries strictly ascending by them, lexicographically (what: the table's name).
+// n_frames Manhattan tables of cap entries of `stride` ints (callers pass mf::stride(w) of msl_plane_tables.h), of which the first n[f],
+// clamped to 0 .. cap as the kernels clamp it, are read: the first w ints of an entry ascending, the entries strictly ascending by them,
+// lexicographically (what: the table's name).  msl_manhattan_observe refuses a count outside 0 .. cap first (counts_ok);
+// msl_manhattan_detect accepts it.
 inline bool tables_sorted_ok(const char *what, int n_frames, int cap, int stride, int w, const int32_t *tab, const int32_t *n, char *err,
                              size_t err_len) {
     for (int f = 0; f < n_frames; f++)
-        for (int e = 0; e < n[f]; e++) {
+        for (int e = 0, m = n[f] < cap ? n[f] : cap; e < m; e++) {
             const int32_t *x = tab + ((size_t)f * cap + e) * stride;
             bool ok = true;
             for (int q = 1; q < w; q++) ok = ok && x[q - 1] <= x[q];

@@ -20,12 +20,13 @@
 #include "msl_match_handle.h"
 #include "msl_index_check.h"
 #include "msl_match_math.h"
+#include "msl_plane_tables.h"
 
 namespace {
 
 using namespace msl;
 
-constexpr int P3_NT = 1024, KD_NT = 256, MAX_PCAP = 64;
+constexpr int P3_NT = 1024, KD_NT = 256;
 const char *const WHO_P3 = "msl_points_3d", *const WHO_KD = "msl_keyframe_decision";
 
 // ==== msl_points_3d ==========================================================================================================================
@@ -165,8 +166,7 @@ int check_points3d(int n_frames, int cap, int n_pts, int mode, const msl_point3d
                          MSL_NAMED(cleared), MSL_NAMED(new_xyz), MSL_NAMED(new_normal), MSL_NAMED(new_dist), MSL_NAMED(new_desc),
                          MSL_NAMED(held_out), MSL_NAMED(new_order), MSL_NAMED(n_new), MSL_NAMED(n_walked)})) return MSL_ERR_INVALID;
     if (n_frames < 1) { set_error("%s: n_frames %d below 1", who, n_frames); return MSL_ERR_INVALID; }
-    if (cap < 1 || cap > MAX_CAP) { set_error("%s: cap %d outside 1 .. %d", who, cap, MAX_CAP); return MSL_ERR_INVALID; }
-    if (n_pts < 0 || n_pts > MAX_PTS) { set_error("%s: n_pts %d outside 0 .. %d", who, n_pts, MAX_PTS); return MSL_ERR_INVALID; }
+    if (!in_range(who, "cap", cap, 1, MAX_CAP) || !in_range(who, "n_pts", n_pts, 0, MAX_PTS)) return MSL_ERR_INVALID;
     if (mode < MSL_POINT3D_ALL || mode > MSL_POINT3D_FRAME) { set_error("%s: mode %d is not an MSL_POINT3D_* value", who, mode); return MSL_ERR_INVALID; }
     if (!levels_ok(who, params->nlevels)) return MSL_ERR_INVALID;
     if (params->min_points < 0) { set_error("%s: min_points %d below 0", who, params->min_points); return MSL_ERR_INVALID; }
@@ -364,10 +364,8 @@ int check_decision(int n_frames, int cap, int lcap, int pcap, int n_tab, int n_p
                          MSL_NAMED(new_plane), MSL_NAMED(held_out), MSL_NAMED(outlier_out), MSL_NAMED(lheld_out), MSL_NAMED(line_outlier_out),
                          MSL_NAMED(counts), MSL_NAMED(cond), MSL_NAMED(need_kf)})) return MSL_ERR_INVALID;
     if (n_frames < 1) { set_error("%s: n_frames %d below 1", who, n_frames); return MSL_ERR_INVALID; }
-    if (lcap < 1 || lcap > MAX_KLCAP) { set_error("%s: lcap %d outside 1 .. %d", who, lcap, MAX_KLCAP); return MSL_ERR_INVALID; }
-    if (pcap < 1 || pcap > MAX_PCAP) { set_error("%s: pcap %d outside 1 .. %d", who, pcap, MAX_PCAP); return MSL_ERR_INVALID; }
-    if (!table_limits(who, n_tab, cap, n_pts)) return MSL_ERR_INVALID;
-    if (n_lines < 1 || n_lines > MAX_LINES) { set_error("%s: n_lines %d outside 1 .. %d", who, n_lines, MAX_LINES); return MSL_ERR_INVALID; }
+    if (!in_range(who, "lcap", lcap, 1, MAX_KLCAP) || !in_range(who, "pcap", pcap, 1, MAX_PCAP) || !table_limits(who, n_tab, cap, n_pts) ||
+        !in_range(who, "n_lines", n_lines, 1, MAX_LINES)) return MSL_ERR_INVALID;
     char why[256];
     if (mem == MSL_MEM_HOST) {
         if (!check::held_ok("cur_held", "n_cur", n_frames, cap, n_pts, cur_held, n_cur, why, sizeof(why)) ||

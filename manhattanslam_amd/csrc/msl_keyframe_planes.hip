@@ -19,12 +19,12 @@
 #include "msl_match_handle.h"
 #include "msl_index_check.h"
 #include "msl_match_math.h"
+#include "msl_plane_tables.h"
 
 namespace {
 
 using namespace msl;
 
-constexpr int MAX_PCAP = 64, MAX_MCAP = 4096, MAX_FCAP = 65536, MAX_QCAP = 65536, MAX_KCAP = 4096, MAX_FRAMES = 65535;
 constexpr int OB_NT = 1024;                        // k_manhattan_observe: the binary searches are chains of dependent loads; 16 waves keep more in flight
 const char *const WHO_KP = "msl_keyframe_planes", *const WHO_MO = "msl_manhattan_observe";
 
@@ -131,10 +131,8 @@ int check_kfplanes(int n_frames, int pcap, int mcap, int kcap, int mode, const m
                          MSL_NAMED(n_map), MSL_NAMED(kf_Rwc), MSL_NAMED(kf_coef), MSL_NAMED(kf_npts), MSL_NAMED(kf_plane_match),
                          MSL_NAMED(plane_new), MSL_NAMED(obs_add), MSL_NAMED(merge_into), MSL_NAMED(Twc), MSL_NAMED(n_new),
                          MSL_NAMED(set_not_erase), MSL_NAMED(status)})) return MSL_ERR_INVALID;
-    if (n_frames < 1 || n_frames > MAX_FRAMES) { set_error("%s: n_frames %d outside 1 .. %d", who, n_frames, MAX_FRAMES); return MSL_ERR_INVALID; }
-    if (pcap < 1 || pcap > MAX_PCAP) { set_error("%s: pcap %d outside 1 .. %d", who, pcap, MAX_PCAP); return MSL_ERR_INVALID; }
-    if (mcap < 1 || mcap > MAX_MCAP) { set_error("%s: mcap %d outside 1 .. %d", who, mcap, MAX_MCAP); return MSL_ERR_INVALID; }
-    if (kcap < 1 || kcap > MAX_KCAP) { set_error("%s: kcap %d outside 1 .. %d", who, kcap, MAX_KCAP); return MSL_ERR_INVALID; }
+    if (!in_range(who, "n_frames", n_frames, 1, MAX_PLANE_FRAMES) || !in_range(who, "pcap", pcap, 1, MAX_PCAP) ||
+        !in_range(who, "mcap", mcap, 1, MAX_PLANE_MCAP) || !in_range(who, "kcap", kcap, 1, MAX_PLANE_KCAP)) return MSL_ERR_INVALID;
     if (mode < MSL_KFPLANES_KEYFRAME || mode > MSL_KFPLANES_INIT) { set_error("%s: mode %d is not an MSL_KFPLANES_* mode", who, mode); return MSL_ERR_INVALID; }
     char why[256];
     // plane_match and n_map are in/out: they live in out_mem memory
@@ -179,30 +177,13 @@ struct ObsDev {
     const msl_kfplanes_frame *frames;
     const int32_t *kfMatch; const float *coef; const int32_t *nPlanes; const uint8_t *mpFlags; const int32_t *mpFirst, *nMap;
     int32_t *fullTab, *nFull, *partTab, *nPart, *addedFull, *addedPart, *setNotErase; uint8_t *recent; int32_t *status;
-    int32_t *scratch;                               // per frame: [fcap][7] merged triples, [fcap] lower bounds, [qcap][5], [qcap]
+    int32_t *scratch;                               // per frame: [fcap] merged triples, [fcap] lower bounds, [qcap] merged pairs, [qcap]
 };
 
 // What a workgroup knows of its keyframe: per dense id the row and the first frame plane that holds it
 struct ObsRows {
     int row[MAX_PCAP], first[MAX_PCAP];
 };
-
-// The number of entries of a table sorted by its first W ints (stride 2 W + 1) whose key is below `key`; *found: the entry there has it.
-template <int W>
-__device__ __forceinline__ int lower_bound_key(const int32_t *tab, int n, const int *key, bool *found) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        const int32_t *e = tab + (size_t)mid * (2 * W + 1);
-        int c = 0;
-        for (int q = 0; q < W && c == 0; q++) c = e[q] < key[q] ? -1 : (e[q] > key[q] ? 1 : 0);
-        if (c < 0) lo = mid + 1; else hi = mid;
-    }
-    bool same = lo < n;
-    for (int q = 0; q < W && same; q++) same = tab[(size_t)lo * (2 * W + 1) + q] == key[q];
-    *found = same;
-    return lo;
-}
 
 // Bit `bit` of a key map as dense ids, ascending
 template <int W>
@@ -219,7 +200,7 @@ __device__ __forceinline__ void ids_of(int bit, int *id) {
 template <int W>
 __device__ int merge_keys(unsigned *bits, uint16_t *cnt, int nWords, int32_t *tab, int nOld, int cap, int32_t *scrTab, int32_t *scrLb, int kfSlot,
                           const ObsRows &S, unsigned *s_wave, bool *noRoom) {
-    constexpr int ST = 2 * W + 1;
+    constexpr int ST = mf::stride(W);
     const int t = threadIdx.x;
     for (int w = t; w < nWords; w += OB_NT) {                                      // drop the keys the table holds
         unsigned word = bits[w];
@@ -250,8 +231,8 @@ __device__ int merge_keys(unsigned *bits, uint16_t *cnt, int nWords, int32_t *ta
             const int lb = lower_bound_key<W>(tab, nOld, key, &found);
             scrLb[r] = lb;
             int32_t *e = scrTab + (size_t)(r + lb) * ST;
-            for (int q = 0; q < W; q++) { e[q] = key[q]; e[W + 1 + q] = S.first[id[q]]; }
-            e[W] = kfSlot;
+            for (int q = 0; q < W; q++) { e[q] = key[q]; e[mf::index_at(W, q)] = S.first[id[q]]; }
+            e[mf::kf_at(W)] = kfSlot;
         }
     }
     __threadfence_block();
@@ -290,7 +271,9 @@ __global__ __launch_bounds__(OB_NT) void k_manhattan_observe(ObsDev D) {
     for (int w = t; w < MAX_PCAP * MAX_PCAP * MAX_PCAP / 32; w += OB_NT) s_tri[w] = 0;
     if (t < MAX_PCAP * MAX_PCAP / 32) s_pair[t] = 0;
     if (t < MAX_PCAP) {
-        int hld = -1;                                                              // mvpMapPlanes[t] when not NULL and not bad
+        // mvpMapPlanes[t] when not NULL and not bad, of an enabled frame: held_row() and, below, sort3() of msl_plane_tables.h written out,
+        // because either call moves this kernel's instruction text (2004 -> 2006 and a reordering) and its rate was not measured again
+        int hld = -1;
         if (t < np) {
             const int m = D.kfMatch[3 * (f * D.pcap + t)];
             if (on && m >= 0 && m < nMap && (D.mpFlags[f * D.mcap + m] & 1)) hld = m;
@@ -339,14 +322,15 @@ __global__ __launch_bounds__(OB_NT) void k_manhattan_observe(ObsDev D) {
         atomicOr(&s_pair[bit >> 5], 1u << (bit & 31));
     }
     __syncthreads();
-    int32_t *scr = D.scratch + f * ((size_t)D.fcap * 8 + (size_t)D.qcap * 6);
+    constexpr int FW = mf::FULL, PW = mf::PART;
+    int32_t *scr = D.scratch + f * ((size_t)D.fcap * mf::scratch_ints(FW) + (size_t)D.qcap * mf::scratch_ints(PW));
     bool fullNoRoom, partNoRoom;
     const int nFull = clampi(D.nFull[f], 0, D.fcap), nPart = clampi(D.nPart[f], 0, D.qcap);
-    const int addedFull = merge_keys<3>(s_tri, s_cnt, MAX_PCAP * MAX_PCAP * MAX_PCAP / 32,
-                                        D.fullTab + f * D.fcap * 7, nFull, D.fcap, scr, scr + (size_t)D.fcap * 7, R.kf_slot, S, s_wave, &fullNoRoom);
-    scr += (size_t)D.fcap * 8;
-    const int addedPart = merge_keys<2>(s_pair, s_cnt, MAX_PCAP * MAX_PCAP / 32, D.partTab + f * D.qcap * 5, nPart, D.qcap, scr,
-                                        scr + (size_t)D.qcap * 5, R.kf_slot, S, s_wave, &partNoRoom);
+    const int addedFull = merge_keys<FW>(s_tri, s_cnt, MAX_PCAP * MAX_PCAP * MAX_PCAP / 32, D.fullTab + f * D.fcap * mf::stride(FW), nFull, D.fcap,
+                                         scr, scr + (size_t)D.fcap * mf::stride(FW), R.kf_slot, S, s_wave, &fullNoRoom);
+    scr += (size_t)D.fcap * mf::scratch_ints(FW);
+    const int addedPart = merge_keys<PW>(s_pair, s_cnt, MAX_PCAP * MAX_PCAP / 32, D.partTab + f * D.qcap * mf::stride(PW), nPart, D.qcap, scr,
+                                         scr + (size_t)D.qcap * mf::stride(PW), R.kf_slot, S, s_wave, &partNoRoom);
     if (t == 0) {
         D.addedFull[f] = addedFull; D.addedPart[f] = addedPart;
         D.setNotErase[f] = addedFull + addedPart > 0 ? 1 : 0;
@@ -366,12 +350,9 @@ int check_observe(int n_frames, int pcap, int mcap, int fcap, int qcap, int kcap
                          MSL_NAMED(mp_flags), MSL_NAMED(mp_first_kf), MSL_NAMED(n_map), MSL_NAMED(full_tab), MSL_NAMED(n_full), MSL_NAMED(part_tab),
                          MSL_NAMED(n_part), MSL_NAMED(added_full), MSL_NAMED(added_part), MSL_NAMED(set_not_erase), MSL_NAMED(recent_plane),
                          MSL_NAMED(status)})) return MSL_ERR_INVALID;
-    if (n_frames < 1 || n_frames > MAX_FRAMES) { set_error("%s: n_frames %d outside 1 .. %d", who, n_frames, MAX_FRAMES); return MSL_ERR_INVALID; }
-    if (pcap < 1 || pcap > MAX_PCAP) { set_error("%s: pcap %d outside 1 .. %d", who, pcap, MAX_PCAP); return MSL_ERR_INVALID; }
-    if (mcap < 1 || mcap > MAX_MCAP) { set_error("%s: mcap %d outside 1 .. %d", who, mcap, MAX_MCAP); return MSL_ERR_INVALID; }
-    if (fcap < 1 || fcap > MAX_FCAP) { set_error("%s: fcap %d outside 1 .. %d", who, fcap, MAX_FCAP); return MSL_ERR_INVALID; }
-    if (qcap < 1 || qcap > MAX_QCAP) { set_error("%s: qcap %d outside 1 .. %d", who, qcap, MAX_QCAP); return MSL_ERR_INVALID; }
-    if (kcap < 1 || kcap > MAX_KCAP) { set_error("%s: kcap %d outside 1 .. %d", who, kcap, MAX_KCAP); return MSL_ERR_INVALID; }
+    if (!in_range(who, "n_frames", n_frames, 1, MAX_PLANE_FRAMES) || !in_range(who, "pcap", pcap, 1, MAX_PCAP) ||
+        !in_range(who, "mcap", mcap, 1, MAX_PLANE_MCAP) || !in_range(who, "fcap", fcap, 1, MAX_FCAP) ||
+        !in_range(who, "qcap", qcap, 1, MAX_QCAP) || !in_range(who, "kcap", kcap, 1, MAX_PLANE_KCAP)) return MSL_ERR_INVALID;
     char why[256];
     if (mem == MSL_MEM_HOST) {
         if (!check::counts_ok("n_planes", "pcap", n_frames, pcap, n_planes, why, sizeof(why)) ||
@@ -382,8 +363,9 @@ int check_observe(int n_frames, int pcap, int mcap, int fcap, int qcap, int kcap
     if (out_mem == MSL_MEM_HOST) {
         if (!check::counts_ok("n_full", "fcap", n_frames, fcap, n_full, why, sizeof(why)) ||
             !check::counts_ok("n_part", "qcap", n_frames, qcap, n_part, why, sizeof(why)) ||
-            !check::tables_sorted_ok("full_tab", n_frames, fcap, 7, 3, full_tab, n_full, why, sizeof(why)) ||
-            !check::tables_sorted_ok("part_tab", n_frames, qcap, 5, 2, part_tab, n_part, why, sizeof(why))) return refuse(who, why);
+            !check::tables_sorted_ok("full_tab", n_frames, fcap, mf::stride(mf::FULL), mf::FULL, full_tab, n_full, why, sizeof(why)) ||
+            !check::tables_sorted_ok("part_tab", n_frames, qcap, mf::stride(mf::PART), mf::PART, part_tab, n_part, why, sizeof(why)))
+            return refuse(who, why);
     }
     return MSL_OK;
 }
@@ -401,11 +383,12 @@ int launch_observe(msl_match *h, int n_frames, int pcap, int mcap, int fcap, int
     Stage S(h, mem, out_mem);
     D.frames = S.in(frames, F); D.kfMatch = S.in(kf_plane_match, 3 * p); D.coef = S.in(plane_coef, 4 * p); D.nPlanes = S.in(n_planes, F);
     D.mpFlags = S.in(mp_flags, m); D.mpFirst = S.in(mp_first_kf, m); D.nMap = S.in(n_map, F);
-    D.fullTab = S.inout(full_tab, 7 * F * fcap); D.nFull = S.inout(n_full, F); D.partTab = S.inout(part_tab, 5 * F * qcap); D.nPart = S.inout(n_part, F);
+    D.fullTab = S.inout(full_tab, mf::stride(mf::FULL) * F * fcap); D.nFull = S.inout(n_full, F);
+    D.partTab = S.inout(part_tab, mf::stride(mf::PART) * F * qcap); D.nPart = S.inout(n_part, F);
     D.addedFull = S.out(added_full, F); D.addedPart = S.out(added_part, F); D.setNotErase = S.out(set_not_erase, F);
     D.recent = S.out(recent_plane, p); D.status = S.out(status, F);
     MSL_HIP_TRY(S.error());
-    MSL_HIP_TRY(h->kfpScratch.grow(sizeof(int32_t) * F * ((size_t)fcap * 8 + (size_t)qcap * 6), h->stream));
+    MSL_HIP_TRY(h->kfpScratch.grow(sizeof(int32_t) * F * ((size_t)fcap * mf::scratch_ints(mf::FULL) + (size_t)qcap * mf::scratch_ints(mf::PART)), h->stream));
     D.scratch = (int32_t *)h->kfpScratch.p;
     hipLaunchKernelGGL(k_manhattan_observe, dim3((unsigned)n_frames), dim3(OB_NT), 0, h->stream, D);
     MSL_HIP_TRY(hipGetLastError());

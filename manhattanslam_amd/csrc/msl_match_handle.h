@@ -1,6 +1,7 @@
 // msl_match_handle.h -- the matcher handle, its staging of caller arrays (Stage), the forwarder of the *_batch entry points, the two forms of
-// a LocalMapping entry (handle_form, batch_form) with the list of its NULLs (none_null), the limits that several entry points share
-// (table_limits, line_table_limits, levels_ok) and the row readback of the debug entry points (last_call_row); shared by msl_match.hip,
+// an entry that checks before it touches a device (handle_form, batch_form: the LocalMapping entries and the plane chain, msl_plane.hip
+// included) with the list of its NULLs (none_null), the limits that several entry points share (table_limits, line_table_limits,
+// levels_ok; the plane chain's are in msl_plane_tables.h) and the row readback of the debug entry points (last_call_row); shared by msl_match.hip,
 // msl_line_match.hip, msl_pose.hip, msl_plane.hip, msl_bow.hip, msl_reloc.hip, msl_pnp.hip, msl_line3d.hip, msl_triangulate.hip, msl_fuse.hip,
 // msl_mappoint.hip, msl_line_fuse.hip, msl_local_map.hip, msl_cull.hip, msl_plane_cloud.hip, msl_keyframe.hip and msl_keyframe_planes.hip (internal).
 #pragma once
@@ -131,7 +132,7 @@ int abi_call_default(Run run, int device, bool sync_legacy, A... a) {
     return rc;
 }
 
-// The two forms of a LocalMapping entry: check_x(args...) makes no HIP call and comes first, so a refusal is made before the handle, or
+// The two forms of a LocalMapping or plane-chain entry: check_x(args...) makes no HIP call and comes first, so a refusal is made before the handle, or
 // the device's shared one, is touched; launch_x(h, args...) starts at bind_device.
 template <class Check, class Launch, class... A>
 int handle_form(const char *who, Check check, Launch launch, msl_match *h, A... a) {

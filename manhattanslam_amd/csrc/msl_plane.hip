@@ -14,17 +14,18 @@
 //                   and nmatches.
 //   k_manhattan     one workgroup per frame: every (i, j, k) triple and (i, j) pair is scored independently, the reference's "first candidate
 //                   with the largest score > 0" is a 64-bit max of (score, ~order); lane 0 builds manhattanRcw from the winner.
+#include "msl_index_check.h"
 #include "msl_match_handle.h"
 #include "msl_match_math.h"
+#include "msl_plane_tables.h"
 
-#include <algorithm>
+#include <climits>
 #include <cmath>
 
 using namespace msl;
 
 namespace {
 
-constexpr int MAX_PCAP = 64, MAX_MCAP = 4096, MAX_PTCAP = 1 << 22, MAX_FCAP = 65536, MAX_QCAP = 65536, MAX_KCAP = 4096;
 constexpr int MF_NT = 256;
 constexpr int KG = 16;                             // k_plane_dis: frame planes per pass over a cloud
 
@@ -147,21 +148,11 @@ __global__ __launch_bounds__(64) void k_plane_assign(AssocDev D) {
 __device__ __forceinline__ float dot3_f32(const float *a, const float *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 __device__ __forceinline__ bool mf_vertical(float a, float th) { return !(a > th || a < -th); }
 
-// The map plane held by frame plane i (mvpMapPlanes[i]) when it is not NULL and not bad, else -1.
-__device__ __forceinline__ int held(const MfDev &D, int f, int i, int nMap) {
-    const int m = D.match[3 * ((size_t)f * D.pcap + i)];
-    if (m < 0 || m >= nMap || !(D.mpFlags[(size_t)f * D.mcap + m] & 1)) return -1;
-    return m;
-}
-
-__device__ __forceinline__ void sort3(int &a, int &b, int &c) {
-    if (a > b) { int t = a; a = b; b = t; }
-    if (b > c) { int t = b; b = c; c = t; }
-    if (a > b) { int t = a; a = b; b = t; }
-}
-
-// Binary search of a table sorted ascending by its first w key ints (entries of `stride` ints); the entry index or -1.
-__device__ int find_entry(const int32_t *tab, int n, int stride, int w, const int *key) {
+// The entry of a table (n entries of key width w, sorted ascending by their keys) that has `key`, or -1.  k_manhattan keeps this closed
+// interval with its early return: as lower_bound_key plus its `found` (msl_plane_tables.h) the kernel comes out 44 instructions longer,
+// and nothing here measures its rate.  The two agree on every table without duplicate keys.
+__device__ int find_entry(const int32_t *tab, int n, int w, const int *key) {
+    const int stride = mf::stride(w);
     int lo = 0, hi = n - 1;
     while (lo <= hi) {
         const int mid = (lo + hi) >> 1;
@@ -174,14 +165,7 @@ __device__ int find_entry(const int32_t *tab, int n, int stride, int w, const in
     return -1;
 }
 
-// The keyframe plane index of map plane m in a table entry (the position of m among its sorted keys).
-__device__ __forceinline__ int kf_index(const int32_t *e, int w, int m) {
-    for (int q = 0; q < w; q++)
-        if (e[q] == m) return e[w + 1 + q];
-    return -1;
-}
-
-// The frame's planes as the candidate loop reads them, staged once per workgroup: the held map plane (held(), -1 = none), the coefficients
+// The frame's planes as the candidate loop reads them, staged once per workgroup: the held map plane (held_row(), -1 = none), the coefficients
 // and the point counts.
 struct MfFrame {
     int held[MAX_PCAP];
@@ -205,29 +189,32 @@ __device__ int score_of(const MfDev &D, const MfFrame &S, int f, int i, int j, i
         if (!mf_vertical(dot3_f32(c1, c3), th) || !mf_vertical(dot3_f32(c2, c3), th)) return 0;   // (:691-701)
         int key[3] = {m1, m2, m3};
         sort3(key[0], key[1], key[2]);
-        const int32_t *tab = D.fullTab + (size_t)f * D.fcap * 7;
-        const int e = find_entry(tab, clampi(D.nFull[f], 0, D.fcap), 7, 3, key);
+        constexpr int W = mf::FULL, ST = mf::stride(W);
+        const int32_t *tab = D.fullTab + (size_t)f * D.fcap * ST;
+        const int e = find_entry(tab, clampi(D.nFull[f], 0, D.fcap), W, key);
         if (e < 0) return 0;
-        const int32_t *ent = tab + (size_t)e * 7;
-        const int kf = ent[3], i1 = kf_index(ent, 3, m1), i2 = kf_index(ent, 3, m2), i3 = kf_index(ent, 3, m3);
+        const int32_t *ent = tab + (size_t)e * ST;
+        const int kf = ent[mf::kf_at(W)], i1 = kf_index(ent, W, m1), i2 = kf_index(ent, W, m2), i3 = kf_index(ent, W, m3);
         if (kf < 0 || kf >= kcap || i1 < 0 || i2 < 0 || i3 < 0 || i1 >= pcap || i2 >= pcap || i3 >= pcap) return 0;
         const int32_t *kn = D.kfNpts + ((size_t)f * kcap + kf) * pcap;
         *entry = e;
         return kn[i1] + kn[i2] + kn[i3] + S.npts[i] + S.npts[j] + S.npts[c];
     }
     int key[2] = {min(m1, m2), max(m1, m2)};
-    const int32_t *tab = D.partTab + (size_t)f * D.qcap * 5;
-    const int e = find_entry(tab, clampi(D.nPart[f], 0, D.qcap), 5, 2, key);
+    constexpr int W = mf::PART, ST = mf::stride(W);
+    const int32_t *tab = D.partTab + (size_t)f * D.qcap * ST;
+    const int e = find_entry(tab, clampi(D.nPart[f], 0, D.qcap), W, key);
     if (e < 0) return 0;
-    const int32_t *ent = tab + (size_t)e * 5;
-    const int kf = ent[2], i1 = kf_index(ent, 2, m1), i2 = kf_index(ent, 2, m2);
+    const int32_t *ent = tab + (size_t)e * ST;
+    const int kf = ent[mf::kf_at(W)], i1 = kf_index(ent, W, m1), i2 = kf_index(ent, W, m2);
     if (kf < 0 || kf >= kcap || i1 < 0 || i2 < 0 || i1 >= pcap || i2 >= pcap) return 0;
     const int32_t *kn = D.kfNpts + ((size_t)f * kcap + kf) * pcap;
     *entry = e;
     return kn[i1] + kn[i2] + S.npts[i] + S.npts[j];
 }
 
-// cv::gemm of two 3x3 CV_32F matrices (row-major; B transposed when tb): double accumulation, one rounding per element.
+// cv::gemm of two 3x3 CV_32F matrices (row-major; B transposed when tb): double accumulation, one rounding per element.  Not
+// msl_match_math.h's gemm33<SA, SB>: that one rounds s * alpha + 0.0, which turns a sum of -0 into +0 and changes k_manhattan's text.
 __device__ void gemm33(const float *A, const float *B, bool tb, float *C) {
     for (int r = 0; r < 3; r++)
         for (int c = 0; c < 3; c++) {
@@ -273,7 +260,7 @@ __global__ __launch_bounds__(MF_NT) void k_manhattan(MfDev D) {
     __shared__ MfFrame S;
     if (t == 0) best = 0ull;
     if (t < np) {
-        S.held[t] = held(D, f, t, nMap);
+        S.held[t] = held_row(D.match[3 * ((size_t)f * D.pcap + t)], D.mpFlags + (size_t)f * D.mcap, nMap);
         for (int q = 0; q < 4; q++) S.coef[t][q] = D.coef[((size_t)f * D.pcap + t) * 4 + q];
         S.npts[t] = D.npts[(size_t)f * D.pcap + t];
     }
@@ -307,8 +294,8 @@ __global__ __launch_bounds__(MF_NT) void k_manhattan(MfDev D) {
     int e;
     const int score = score_of(D, S, f, i, j, c, np, &e);
     const int m1 = S.held[i], m2 = S.held[j];
-    const int32_t *ent = isFull ? D.fullTab + ((size_t)f * D.fcap + e) * 7 : D.partTab + ((size_t)f * D.qcap + e) * 5;
-    const int w = isFull ? 3 : 2, kf = ent[w];
+    const int32_t *ent = isFull ? D.fullTab + ((size_t)f * D.fcap + e) * mf::stride(mf::FULL) : D.partTab + ((size_t)f * D.qcap + e) * mf::stride(mf::PART);
+    const int w = isFull ? mf::FULL : mf::PART, kf = ent[mf::kf_at(w)];
     const float *kfc = D.kfCoef + ((size_t)f * D.kcap + kf) * D.pcap * 4;
     const float *pc1 = D.coef + ((size_t)f * D.pcap + i) * 4, *pc2 = D.coef + ((size_t)f * D.pcap + j) * 4;
     const float *pm1 = kfc + 4 * kf_index(ent, w, m1), *pm2 = kfc + 4 * kf_index(ent, w, m2);
@@ -342,27 +329,25 @@ __global__ __launch_bounds__(MF_NT) void k_manhattan(MfDev D) {
     if (ch) { ch[0] = i; ch[1] = j; ch[2] = isFull ? c : -1; ch[3] = e; ch[4] = score; ch[5] = kf; }
 }
 
-// Host tables must be sorted ascending by their keys, each key ascending within the entry.
-bool table_sorted(const int32_t *tab, int n, int stride, int w) {
-    for (int e = 0; e < n; e++) {
-        const int32_t *x = tab + (size_t)e * stride;
-        for (int q = 1; q < w; q++)
-            if (x[q - 1] > x[q]) return false;
-        if (e > 0 && !std::lexicographical_compare(x - stride, x - stride + w, x, x + w)) return false;
-    }
-    return true;
+const char *const WHO_PA = "msl_plane_associate", *const WHO_MD = "msl_manhattan_detect";
+
+int check_associate(int n_frames, int pcap, int mcap, int ptcap, const msl_plane_params *params, const float *plane_coef, const int32_t *n_planes,
+                    const float *Tcw, const float *mp_w, const uint8_t *mp_flags, const int32_t *mp_pt_off, const float *mp_pts,
+                    const int32_t *n_map, msl_mem, int32_t *plane_match, int32_t *nmatches, float *plane_w, uint8_t *plane_has, float *,
+                    msl_mem) {
+    const char *who = WHO_PA;
+    if (!none_null(who, {MSL_NAMED(params), MSL_NAMED(plane_coef), MSL_NAMED(n_planes), MSL_NAMED(Tcw), MSL_NAMED(mp_w), MSL_NAMED(mp_flags),
+                         MSL_NAMED(mp_pt_off), MSL_NAMED(mp_pts), MSL_NAMED(n_map), MSL_NAMED(plane_match), MSL_NAMED(nmatches),
+                         MSL_NAMED(plane_w), MSL_NAMED(plane_has)})) return MSL_ERR_INVALID;
+    if (!in_range(who, "n_frames", n_frames, 1, INT_MAX) || !in_range(who, "pcap", pcap, 1, MAX_PCAP) ||
+        !in_range(who, "mcap", mcap, 1, MAX_PLANE_MCAP) || !in_range(who, "ptcap", ptcap, 1, MAX_PLANE_PTCAP)) return MSL_ERR_INVALID;
+    return MSL_OK;
 }
 
-int run_associate(msl_match *h, int n_frames, int pcap, int mcap, int ptcap, const msl_plane_params *prm, const float *plane_coef,
-                  const int32_t *n_planes, const float *Tcw, const float *mp_w, const uint8_t *mp_flags, const int32_t *mp_pt_off,
-                  const float *mp_pts, const int32_t *n_map, msl_mem mem, int32_t *plane_match, int32_t *nmatches, float *plane_w,
-                  uint8_t *plane_has, float *pM_out, msl_mem out_mem) {
-    if (!h || n_frames < 1 || pcap < 1 || pcap > MAX_PCAP || mcap < 1 || mcap > MAX_MCAP || ptcap < 1 || ptcap > MAX_PTCAP || !prm ||
-        !plane_coef || !n_planes || !Tcw || !mp_w || !mp_flags || !mp_pt_off || !mp_pts || !n_map || !plane_match || !nmatches ||
-        !plane_w || !plane_has) {
-        set_error("msl_plane_associate: invalid argument (1 <= pcap <= %d, mcap <= %d, ptcap <= %d)", MAX_PCAP, MAX_MCAP, MAX_PTCAP);
-        return MSL_ERR_INVALID;
-    }
+int launch_associate(msl_match *h, int n_frames, int pcap, int mcap, int ptcap, const msl_plane_params *prm, const float *plane_coef,
+                     const int32_t *n_planes, const float *Tcw, const float *mp_w, const uint8_t *mp_flags, const int32_t *mp_pt_off,
+                     const float *mp_pts, const int32_t *n_map, msl_mem mem, int32_t *plane_match, int32_t *nmatches, float *plane_w,
+                     uint8_t *plane_has, float *pM_out, msl_mem out_mem) {
     int rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
     hipStream_t st = h->stream;
@@ -385,26 +370,33 @@ int run_associate(msl_match *h, int n_frames, int pcap, int mcap, int ptcap, con
     return MSL_OK;
 }
 
-int run_manhattan(msl_match *h, int n_frames, int pcap, int mcap, int fcap, int qcap, int kcap, const msl_plane_params *prm,
-                  const float *plane_coef, const int32_t *plane_npts, const int32_t *n_planes, const int32_t *plane_match,
-                  const uint8_t *mp_flags, const int32_t *n_map, const int32_t *full_tab, const int32_t *n_full, const int32_t *part_tab,
-                  const int32_t *n_part, const float *kf_Rwc, const float *kf_coef, const int32_t *kf_npts, msl_mem mem, int32_t *found,
-                  int32_t *full, float *Rcw, int32_t *choice, msl_mem out_mem) {
-    if (!h || n_frames < 1 || pcap < 1 || pcap > MAX_PCAP || mcap < 1 || mcap > MAX_MCAP || fcap < 1 || fcap > MAX_FCAP || qcap < 1 ||
-        qcap > MAX_QCAP || kcap < 1 || kcap > MAX_KCAP || !prm || !plane_coef || !plane_npts || !n_planes || !plane_match || !mp_flags ||
-        !n_map || !full_tab || !n_full || !part_tab || !n_part || !kf_Rwc || !kf_coef || !kf_npts || !found || !full || !Rcw) {
-        set_error("msl_manhattan_detect: invalid argument (1 <= pcap <= %d, mcap <= %d, fcap <= %d, qcap <= %d, kcap <= %d)", MAX_PCAP,
-                  MAX_MCAP, MAX_FCAP, MAX_QCAP, MAX_KCAP);
+// Host tables must be sorted ascending by their keys, each key ascending within the entry; the counts are clamped, as the kernel clamps them.
+int check_manhattan(int n_frames, int pcap, int mcap, int fcap, int qcap, int kcap, const msl_plane_params *params, const float *plane_coef,
+                    const int32_t *plane_npts, const int32_t *n_planes, const int32_t *plane_match, const uint8_t *mp_flags,
+                    const int32_t *n_map, const int32_t *full_tab, const int32_t *n_full, const int32_t *part_tab, const int32_t *n_part,
+                    const float *kf_Rwc, const float *kf_coef, const int32_t *kf_npts, msl_mem mem, int32_t *found, int32_t *full, float *Rcw,
+                    int32_t *, msl_mem) {
+    const char *who = WHO_MD;
+    if (!none_null(who, {MSL_NAMED(params), MSL_NAMED(plane_coef), MSL_NAMED(plane_npts), MSL_NAMED(n_planes), MSL_NAMED(plane_match),
+                         MSL_NAMED(mp_flags), MSL_NAMED(n_map), MSL_NAMED(full_tab), MSL_NAMED(n_full), MSL_NAMED(part_tab), MSL_NAMED(n_part),
+                         MSL_NAMED(kf_Rwc), MSL_NAMED(kf_coef), MSL_NAMED(kf_npts), MSL_NAMED(found), MSL_NAMED(full), MSL_NAMED(Rcw)}))
         return MSL_ERR_INVALID;
-    }
-    if (mem == MSL_MEM_HOST)
-        for (int f = 0; f < n_frames; f++) {
-            const int nf = std::min(std::max(n_full[f], 0), fcap), nq = std::min(std::max(n_part[f], 0), qcap);
-            if (!table_sorted(full_tab + (size_t)f * fcap * 7, nf, 7, 3) || !table_sorted(part_tab + (size_t)f * qcap * 5, nq, 5, 2)) {
-                set_error("msl_manhattan_detect: the Manhattan tables of frame %d are not sorted by their keys", f);
-                return MSL_ERR_INVALID;
-            }
-        }
+    if (!in_range(who, "n_frames", n_frames, 1, INT_MAX) || !in_range(who, "pcap", pcap, 1, MAX_PCAP) ||
+        !in_range(who, "mcap", mcap, 1, MAX_PLANE_MCAP) || !in_range(who, "fcap", fcap, 1, MAX_FCAP) ||
+        !in_range(who, "qcap", qcap, 1, MAX_QCAP) || !in_range(who, "kcap", kcap, 1, MAX_PLANE_KCAP)) return MSL_ERR_INVALID;
+    char why[256];
+    if (mem == MSL_MEM_HOST &&
+        (!check::tables_sorted_ok("full_tab", n_frames, fcap, mf::stride(mf::FULL), mf::FULL, full_tab, n_full, why, sizeof(why)) ||
+         !check::tables_sorted_ok("part_tab", n_frames, qcap, mf::stride(mf::PART), mf::PART, part_tab, n_part, why, sizeof(why))))
+        return refuse(who, why);
+    return MSL_OK;
+}
+
+int launch_manhattan(msl_match *h, int n_frames, int pcap, int mcap, int fcap, int qcap, int kcap, const msl_plane_params *prm,
+                     const float *plane_coef, const int32_t *plane_npts, const int32_t *n_planes, const int32_t *plane_match,
+                     const uint8_t *mp_flags, const int32_t *n_map, const int32_t *full_tab, const int32_t *n_full, const int32_t *part_tab,
+                     const int32_t *n_part, const float *kf_Rwc, const float *kf_coef, const int32_t *kf_npts, msl_mem mem, int32_t *found,
+                     int32_t *full, float *Rcw, int32_t *choice, msl_mem out_mem) {
     int rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
     hipStream_t st = h->stream;
@@ -413,9 +405,10 @@ int run_manhattan(msl_match *h, int n_frames, int pcap, int mcap, int fcap, int 
     D.pcap = pcap; D.mcap = mcap; D.fcap = fcap; D.qcap = qcap; D.kcap = kcap; D.prm = *prm;
     Stage S(h, mem, out_mem);
     D.coef = S.in(plane_coef, 4 * p); D.npts = S.in(plane_npts, p); D.nPlanes = S.in(n_planes, F); D.match = S.in(plane_match, 3 * p);
-    D.mpFlags = S.in(mp_flags, m); D.nMap = S.in(n_map, F); D.fullTab = S.in(full_tab, 7 * F * fcap); D.nFull = S.in(n_full, F);
-    D.partTab = S.in(part_tab, 5 * F * qcap); D.nPart = S.in(n_part, F); D.kfRwc = S.in(kf_Rwc, 9 * k); D.kfCoef = S.in(kf_coef, 4 * k * pcap);
-    D.kfNpts = S.in(kf_npts, k * pcap);
+    D.mpFlags = S.in(mp_flags, m); D.nMap = S.in(n_map, F);
+    D.fullTab = S.in(full_tab, mf::stride(mf::FULL) * F * fcap); D.nFull = S.in(n_full, F);
+    D.partTab = S.in(part_tab, mf::stride(mf::PART) * F * qcap); D.nPart = S.in(n_part, F);
+    D.kfRwc = S.in(kf_Rwc, 9 * k); D.kfCoef = S.in(kf_coef, 4 * k * pcap); D.kfNpts = S.in(kf_npts, k * pcap);
     D.Rcw = S.inout(Rcw, 9 * F);                                               // written only where found
     D.found = S.out(found, F); D.full = S.out(full, F); D.choice = S.out(choice, 6 * F);
     MSL_HIP_TRY(S.error());
@@ -434,8 +427,8 @@ int msl_plane_associate(msl_match *h, int n_frames, int pcap, int mcap, int ptca
                         const float *mp_pts, const int32_t *n_map, msl_mem mem, int32_t *plane_match, int32_t *nmatches, float *plane_w,
                         uint8_t *plane_has, float *pM_out, msl_mem out_mem) noexcept {
     try {
-    return run_associate(h, n_frames, pcap, mcap, ptcap, params, plane_coef, n_planes, Tcw, mp_w, mp_flags, mp_pt_off, mp_pts, n_map, mem, plane_match,
-                         nmatches, plane_w, plane_has, pM_out, out_mem);
+    return handle_form(WHO_PA, check_associate, launch_associate, h, n_frames, pcap, mcap, ptcap, params, plane_coef, n_planes, Tcw, mp_w, mp_flags,
+                       mp_pt_off, mp_pts, n_map, mem, plane_match, nmatches, plane_w, plane_has, pM_out, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -445,8 +438,9 @@ int msl_plane_associate_batch(int device, int n_frames, int pcap, int mcap, int 
                               int32_t *nmatches, float *plane_w, uint8_t *plane_has, float *pM_out, msl_mem out_mem) noexcept {
     // plane_match is an input too: device-memory outputs are read as well
     try {
-    return abi_call_default(run_associate, device, mem == MSL_MEM_DEVICE || out_mem == MSL_MEM_DEVICE, n_frames, pcap, mcap, ptcap, params, plane_coef,
-                            n_planes, Tcw, mp_w, mp_flags, mp_pt_off, mp_pts, n_map, mem, plane_match, nmatches, plane_w, plane_has, pM_out, out_mem);
+    return batch_form(check_associate, launch_associate, device, mem == MSL_MEM_DEVICE || out_mem == MSL_MEM_DEVICE, n_frames, pcap, mcap, ptcap,
+                      params, plane_coef, n_planes, Tcw, mp_w, mp_flags, mp_pt_off, mp_pts, n_map, mem, plane_match, nmatches, plane_w, plane_has,
+                      pM_out, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -456,8 +450,9 @@ int msl_manhattan_detect(msl_match *h, int n_frames, int pcap, int mcap, int fca
                          const int32_t *part_tab, const int32_t *n_part, const float *kf_Rwc, const float *kf_coef, const int32_t *kf_npts,
                          msl_mem mem, int32_t *found, int32_t *full, float *Rcw, int32_t *choice, msl_mem out_mem) noexcept {
     try {
-    return run_manhattan(h, n_frames, pcap, mcap, fcap, qcap, kcap, params, plane_coef, plane_npts, n_planes, plane_match, mp_flags, n_map, full_tab, n_full,
-                         part_tab, n_part, kf_Rwc, kf_coef, kf_npts, mem, found, full, Rcw, choice, out_mem);
+    return handle_form(WHO_MD, check_manhattan, launch_manhattan, h, n_frames, pcap, mcap, fcap, qcap, kcap, params, plane_coef, plane_npts, n_planes,
+                       plane_match, mp_flags, n_map, full_tab, n_full, part_tab, n_part, kf_Rwc, kf_coef, kf_npts, mem, found, full, Rcw, choice,
+                       out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -469,9 +464,9 @@ int msl_manhattan_detect_batch(int device, int n_frames, int pcap, int mcap, int
                                msl_mem out_mem) noexcept {
     // Rcw is in/out: device-memory outputs are read as well
     try {
-    return abi_call_default(run_manhattan, device, mem == MSL_MEM_DEVICE || out_mem == MSL_MEM_DEVICE, n_frames, pcap, mcap, fcap, qcap, kcap, params,
-                            plane_coef, plane_npts, n_planes, plane_match, mp_flags, n_map, full_tab, n_full, part_tab, n_part, kf_Rwc, kf_coef, kf_npts, mem,
-                            found, full, Rcw, choice, out_mem);
+    return batch_form(check_manhattan, launch_manhattan, device, mem == MSL_MEM_DEVICE || out_mem == MSL_MEM_DEVICE, n_frames, pcap, mcap, fcap, qcap,
+                      kcap, params, plane_coef, plane_npts, n_planes, plane_match, mp_flags, n_map, full_tab, n_full, part_tab, n_part, kf_Rwc,
+                      kf_coef, kf_npts, mem, found, full, Rcw, choice, out_mem);
     } MSL_ABI_CATCH_INT
 }
 

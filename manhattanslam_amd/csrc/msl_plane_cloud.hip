@@ -22,6 +22,7 @@
 #include "msl_jacobi.h"
 #include "msl_match_handle.h"
 #include "msl_match_math.h"
+#include "msl_plane_tables.h"
 
 #include <algorithm>
 #include <climits>
@@ -32,9 +33,8 @@ using namespace msl;
 namespace {
 
 constexpr int MAX_VOX = MSL_PLANE_CLOUD_MAX_VOXELS, HASH = 8192, VOX_NT = 1024, MODEL_NT = 256, MAX_BLOCKS = 256;
-constexpr int MAX_PCAP = 64, MAX_MCAP = 4096, MAX_PTCAP = 1 << 22, MAX_ITER = 4096;
+constexpr int MAX_ITER = 4096;
 constexpr int LDS_VOX = 1024;                      // voxel_filter: clouds up to this many voxels accumulate in LDS
-constexpr int MAX_FRAMES = 65535;                  // a grid dimension
 constexpr int VOX_BIAS = 1 << 20;                  // voxel indices lie in [-2^20, 2^20): |x| < 32768 and 1 / leaf <= 32
 constexpr unsigned long long NO_KEY = ~0ull;       // keys hold 63 bits
 static_assert(MAX_VOX == 4096 && HASH == 2 * MAX_VOX && MAX_VOX + VOX_NT < HASH, "the hash never fills: inserts stop above MAX_VOX");
@@ -508,9 +508,9 @@ __global__ __launch_bounds__(VOX_NT) void k_pm_merge(MergeDev D) {
 }
 
 __global__ __launch_bounds__(MODEL_NT) void k_pm_scan(MergeDev D) {
-    __shared__ int cnt[MAX_MCAP + 1];
-    __shared__ int16_t own[MAX_MCAP];
-    __shared__ uint8_t stat[MAX_MCAP];
+    __shared__ int cnt[MAX_PLANE_MCAP + 1];
+    __shared__ int16_t own[MAX_PLANE_MCAP];
+    __shared__ uint8_t stat[MAX_PLANE_MCAP];
     const int f = blockIdx.x, t = threadIdx.x;
     const int np = clampi(D.nPlanes[f], 0, D.pcap), nMap = clampi(D.nMap[f], 0, D.mcap);
     for (int j = t; j < nMap; j += MODEL_NT) own[j] = -1;
@@ -586,12 +586,9 @@ int check_clouds(int n_frames, int n_vertices, int max_planes, int pcap, int ptc
                  const int32_t *n_planes, const uint32_t *seed, msl_mem mem, int32_t *n_out, float *plane_coef, int32_t *plane_npts,
                  int32_t *plane_src, int32_t *pt_off, float *pts, uint8_t *rgb_out, int32_t *status, msl_mem out_mem) {
     const char *who = "msl_plane_clouds";
-    if (n_frames < 1 || n_frames > MAX_FRAMES || n_vertices < 1 || n_vertices > MSL_PLANE_CLOUD_MAX_VERTICES || max_planes < 1 ||
-        max_planes > MAX_PCAP || pcap < 1 || pcap > MAX_PCAP || ptcap < 1 || ptcap > MAX_PTCAP) {
-        set_error("%s: invalid argument (n_frames <= 65535, n_vertices <= %d, 1 <= max_planes <= %d, 1 <= pcap <= %d, 1 <= ptcap <= %d)", who,
-                  MSL_PLANE_CLOUD_MAX_VERTICES, MAX_PCAP, MAX_PCAP, MAX_PTCAP);
-        return MSL_ERR_INVALID;
-    }
+    if (!in_range(who, "n_frames", n_frames, 1, MAX_PLANE_FRAMES) || !in_range(who, "n_vertices", n_vertices, 1, MSL_PLANE_CLOUD_MAX_VERTICES) ||
+        !in_range(who, "max_planes", max_planes, 1, MAX_PCAP) || !in_range(who, "pcap", pcap, 1, MAX_PCAP) ||
+        !in_range(who, "ptcap", ptcap, 1, MAX_PLANE_PTCAP)) return MSL_ERR_INVALID;
     if (!none_null(who, {MSL_NAMED(params), MSL_NAMED(cloud), MSL_NAMED(vertex_offsets), MSL_NAMED(vertex_indices), MSL_NAMED(planes),
                          MSL_NAMED(n_planes), MSL_NAMED(seed), MSL_NAMED(n_out), MSL_NAMED(plane_coef), MSL_NAMED(plane_npts),
                          MSL_NAMED(plane_src), MSL_NAMED(pt_off), MSL_NAMED(pts), MSL_NAMED(status)})) return MSL_ERR_INVALID;
@@ -644,12 +641,9 @@ int check_merge(int n_frames, int pcap, int fptcap, int mcap, int ptcap, const m
                 const int32_t *mp_pt_off, const float *mp_pts, const uint8_t *mp_rgb, const int32_t *n_map, msl_mem mem, int32_t *mp_pt_off_out,
                 float *mp_pts_out, uint8_t *mp_rgb_out, int32_t *merge_status, msl_mem out_mem) {
     const char *who = "msl_map_plane_merge";
-    if (n_frames < 1 || n_frames > MAX_FRAMES || pcap < 1 || pcap > MAX_PCAP || fptcap < 1 || fptcap > MAX_PTCAP || mcap < 1 ||
-        mcap > MAX_MCAP || ptcap < 1 || ptcap > MAX_PTCAP) {
-        set_error("%s: invalid argument (n_frames <= 65535, 1 <= pcap <= %d, 1 <= fptcap <= %d, 1 <= mcap <= %d, 1 <= ptcap <= %d)", who, MAX_PCAP, MAX_PTCAP,
-                  MAX_MCAP, MAX_PTCAP);
-        return MSL_ERR_INVALID;
-    }
+    if (!in_range(who, "n_frames", n_frames, 1, MAX_PLANE_FRAMES) || !in_range(who, "pcap", pcap, 1, MAX_PCAP) ||
+        !in_range(who, "fptcap", fptcap, 1, MAX_PLANE_PTCAP) || !in_range(who, "mcap", mcap, 1, MAX_PLANE_MCAP) ||
+        !in_range(who, "ptcap", ptcap, 1, MAX_PLANE_PTCAP)) return MSL_ERR_INVALID;
     if (!none_null(who, {MSL_NAMED(params), MSL_NAMED(n_planes), MSL_NAMED(pt_off), MSL_NAMED(pts), MSL_NAMED(merge_into), MSL_NAMED(Twc),
                          MSL_NAMED(mp_pt_off), MSL_NAMED(mp_pts), MSL_NAMED(n_map), MSL_NAMED(mp_pt_off_out), MSL_NAMED(mp_pts_out),
                          MSL_NAMED(merge_status)})) return MSL_ERR_INVALID;

@@ -32,6 +32,7 @@
 #pragma once
 #include "msl_match_handle.h"
 #include "msl_match_math.h"
+#include "msl_plane_tables.h"                  // MAX_PCAP: the planes of a frame, as the plane chain produces them
 
 #include <cfloat>
 #include <cmath>
@@ -64,7 +65,7 @@ using namespace msl;
 namespace {
 
 
-constexpr int MAX_XCAP = 32768, MAX_LCAP = 256, MAX_PCAP = 64;
+constexpr int MAX_XCAP = 32768, MAX_LCAP = 256;
 constexpr int NT = 256;                       // four waves per frame
 constexpr int NRED = 28;                      // 21 H (lower triangle) + 6 b + robust chi2
 constexpr int MONO = 0, STEREO = 1, LINE = 2, PLANE = 3, PAR = 4, VER = 5;

@@ -6,6 +6,7 @@ outputs it is given; with device memory on a match.Matcher the call is asynchron
 import numpy as np
 
 from ._lib import KEYPOINT_DTYPE, MSL_MEM_DEVICE, MSL_MEM_HOST, RECORDS, call, fill_levels, pad, ptr
+from .plane import MAX_PCAP                                           # the planes of a frame: the plane chain's limit
 
 POINT3D_PARAMS_DTYPE = RECORDS["msl_point3d_params"]
 KEYFRAME_FRAME_DTYPE = RECORDS["msl_keyframe_frame"]
@@ -15,7 +16,7 @@ assert POINT3D_PARAMS_DTYPE.itemsize == 92 and KEYFRAME_FRAME_DTYPE.itemsize == 
 ALL, KEYFRAME, FRAME = 0, 1, 2                                        # MSL_POINT3D_*
 TRACKED_LOCAL_MAP, TRACK_OK, NEW_PLANE = 1, 2, 4                      # MSL_KF_*: msl_keyframe_frame.flags
 C1A, C1B, C1C, C2 = 1, 2, 4, 8                                        # MSL_KF_C*: cond
-MAX_CAP, MAX_LCAP, MAX_PCAP, MAX_TAB, MAX_PTS, MAX_LINES = 8192, 256, 64, 4096, 1 << 20, 1 << 20
+MAX_CAP, MAX_LCAP, MAX_TAB, MAX_PTS, MAX_LINES = 8192, 256, 4096, 1 << 20, 1 << 20
 POINT_IN_KEYS = ("kps_un", "depth", "desc", "n_kps", "cur_held", "pt_nobs", "Tcw", "enable", "first_id")
 POINT_OUT_KEYS = ("pt_new", "cleared", "new_xyz", "new_normal", "new_dist", "new_desc", "held_out", "new_order", "n_new", "n_walked")
 DECISION_IN_KEYS = ("frames", "depth", "n_cur", "cur_held", "outlier", "cur_lheld", "line_outlier", "n_cur_lines", "n_planes", "pt_nobs", "pt_flags",

@@ -6,7 +6,9 @@ memory, torch tensors or anything with data_ptr() for device memory) and writes 
 on a match.Matcher the call is asynchronous on the handle's stream."""
 import numpy as np
 
+from . import plane
 from ._lib import MSL_MEM_DEVICE, MSL_MEM_HOST, RECORDS, call, pad, ptr
+from .plane import MAX_FCAP, MAX_FRAMES, MAX_KCAP, MAX_MCAP, MAX_PCAP, MAX_QCAP   # the chain's limits stand in plane
 
 KFPLANES_FRAME_DTYPE = RECORDS["msl_kfplanes_frame"]
 assert KFPLANES_FRAME_DTYPE.itemsize == 16
@@ -14,7 +16,6 @@ assert KFPLANES_FRAME_DTYPE.itemsize == 16
 KEYFRAME, INIT = 0, 1                                                 # MSL_KFPLANES_*: mode
 SKIPPED, HELD, NEW, NO_ROOM = 0, 1, 2, 3                              # MSL_KFPLANES_*: status
 FULL_NO_ROOM, PART_NO_ROOM = 1, 2                                     # MSL_MANHATTAN_*_NO_ROOM: msl_manhattan_observe's status
-MAX_FRAMES, MAX_PCAP, MAX_MCAP, MAX_FCAP, MAX_QCAP, MAX_KCAP = 65535, 64, 4096, 65536, 65536, 4096
 PLANES_IN_KEYS = ("frames", "plane_coef", "plane_npts", "n_planes", "Tcw", "plane_outlier")
 PLANES_INOUT_KEYS = ("plane_match", "mp_w", "mp_flags", "mp_first_kf", "n_map", "kf_Rwc", "kf_coef", "kf_npts")
 PLANES_OUT_KEYS = ("kf_plane_match", "plane_new", "obs_add", "merge_into", "Twc", "n_new", "set_not_erase", "status")
@@ -36,7 +37,6 @@ def pack(frames, pcap=None, mcap=None, fcap=None, qcap=None, kcap=None):
     Tcw (12,) f32, plane_match (K,3) i32, plane_outlier (K,3) u8, mp_w (M,4) f32, mp_flags (M,) u8, mp_first_kf (M,) i32, and as in
     plane.pack_manhattan full (E,7) / part (E,5) i32 (any order: sorted here), kf_Rwc (R,9) f32, kf_coef: R arrays (Q,4), kf_npts: R arrays
     (Q,).  Returns (caps (pcap, mcap, fcap, qcap, kcap), dict of arrays named as in msl.h)."""
-    from . import plane
     (pcap, mcap, fcap, qcap, kcap), m = plane.pack_manhattan(frames, pcap, mcap, fcap, qcap, kcap)
     coef, npts, n_planes, match, flags, n_map, ft, nf, pt, nq, kR, kc, kn = m
     a = dict(frames=frame_records(frames), plane_coef=coef, plane_npts=npts, n_planes=n_planes,

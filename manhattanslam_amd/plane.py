@@ -9,6 +9,13 @@ import numpy as np
 
 from ._lib import MSL_MEM_HOST, PLANE_PARAMS_DTYPE, call, check, lib, pad, ptr
 
+# The limits of the plane chain (csrc/msl_plane_tables.h; include/msl.h states them per entry): frames of a call, planes of a frame, map
+# planes, cloud points, entries of the full / partial Manhattan table, keyframe rows.  kfplanes and keyframe take theirs from here.
+MAX_FRAMES, MAX_PCAP, MAX_MCAP, MAX_PTCAP, MAX_FCAP, MAX_QCAP, MAX_KCAP = 65535, 64, 4096, 1 << 22, 65536, 65536, 4096
+# A Manhattan table entry: w keys (map-plane rows, ascending), the keyframe slot, the keyframe-plane index of every key
+FULL_W, PART_W = 3, 2
+FULL_STRIDE, PART_STRIDE = 2 * FULL_W + 1, 2 * PART_W + 1
+
 
 def plane_params(d_th, a_th, ver_th, par_th, mf_ver_th=0.0):
     """msl_plane_params: Plane.AssociationDisRef, AssociationAngRef, VerticalThreshold, ParallelThreshold, MFVerticalThreshold."""
@@ -51,7 +58,7 @@ def pack_associate(frames, pcap=None, mcap=None, ptcap=None):
 def sort_full(full):
     """Full Manhattan entries {a, b, c, kf, ia, ib, ic} with each key sorted ascending (its keyframe indices along) and the table sorted
     by key: Map compares the keys as unordered sets (src/Map.cc:71-123)."""
-    full = np.asarray(full, np.int32).reshape(-1, 7)
+    full = np.asarray(full, np.int32).reshape(-1, FULL_STRIDE)
     out = np.empty_like(full)
     for e, (a, b, c, kf, ia, ib, ic) in enumerate(full):
         pairs = sorted([(a, ia), (b, ib), (c, ic)], key=lambda x: x[0])
@@ -61,7 +68,7 @@ def sort_full(full):
 
 def sort_part(part):
     """Partial entries {a, b, kf, ia, ib}, normalised as sort_full does."""
-    part = np.asarray(part, np.int32).reshape(-1, 5)
+    part = np.asarray(part, np.int32).reshape(-1, PART_STRIDE)
     out = part.copy()
     sw = out[:, 0] > out[:, 1]
     out[sw] = out[sw][:, [1, 0, 2, 4, 3]]
@@ -79,8 +86,8 @@ def pack_manhattan(frames, pcap=None, mcap=None, fcap=None, qcap=None, kcap=None
     fcap = fcap or max(max(len(x) for x in fulls), 1)
     qcap = qcap or max(max(len(x) for x in parts), 1)
     kcap = kcap or max(max(len(fr["kf_Rwc"]) for fr in frames), 1)
-    ft = np.zeros((F, fcap, 7), np.int32)
-    pt = np.zeros((F, qcap, 5), np.int32)
+    ft = np.zeros((F, fcap, FULL_STRIDE), np.int32)
+    pt = np.zeros((F, qcap, PART_STRIDE), np.int32)
     kR = np.zeros((F, kcap, 9), np.float32)
     kc = np.zeros((F, kcap, pcap, 4), np.float32)
     kn = np.zeros((F, kcap, pcap), np.int32)

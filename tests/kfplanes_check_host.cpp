@@ -2,7 +2,8 @@
 // (manhattanslam_amd/csrc/msl_index_check.h: counts_ok, plane_match_ok, kf_slots_ok, tables_sorted_ok, as the entries call them): every array
 // is heap-allocated at exactly its size, so a read past an end is the address sanitizer's to find; valid random arrays must pass, each
 // single defect must be refused with a message that names the field, and a count outside its capacity must be refused before any entry
-// behind it is read.  Prints "<n> failures".
+// behind it is read; tables_sorted_ok on its own, as msl_manhattan_detect calls it, clamps such a count and reads no entry beyond the
+// capacity.  Prints "<n> failures".
 #include "msl_index_check.h"
 
 #include <stdlib.h>
@@ -138,6 +139,16 @@ int main() {
                 for (int q = 0; q < st; q++) { x[q - st] = prev[(size_t)q]; x[q] = keep[(size_t)q]; }
                 expect(sorted_ok_(), true, "", "the tables restored");
             }
+            // msl_manhattan_detect's use: no counts_ok in front; a count outside 0 .. cap is clamped, so no entry at or beyond cap is read
+            std::vector<int32_t> all((size_t)n_frames, cap);
+            std::vector<int32_t> whole = tables(g, n_frames, cap, w, rows, all);
+            auto clamped_ok_ = [&] { return tables_sorted_ok(name, n_frames, cap, st, w, whole.data(), all.data(), err, sizeof(err)); };
+            all[(size_t)f] = cap + 3; expect(clamped_ok_(), true, "", "a count above the capacity over cap sorted entries");
+            int32_t *last = whole.data() + ((size_t)f * cap + cap - 1) * st;
+            const int32_t keep_l = last[0];
+            last[0] = rows + 1; expect(clamped_ok_(), false, name, "a defect at entry cap - 1 under a count above the capacity");
+            all[(size_t)f] = -2; expect(clamped_ok_(), true, "", "a count below 0: no entry of the frame is read");
+            last[0] = keep_l;
         }
     }
     printf("%d failures\n", failures);

@@ -103,10 +103,13 @@ def test_limits_and_unsorted_tables_are_refused_without_a_launch(what):
         n[0] = max(n[0], 2)
         t[0, 0, :w], t[0, 1, :w] = list(range(5, 5 + w)), list(range(w))  # two entries out of order
         big = (pc, mc, fc, qc, kc)
+        named = r"%s\[0\] is not sorted by its keys at entry 1" % ("full_tab" if what == "unsorted_full" else "part_tab")
     else:
-        big = tuple(dict(pcap=65, mcap=4097, fcap=65537, qcap=65537, kcap=4097)[k] if k == what else v for k, v in caps.items())
+        over = dict(pcap=65, mcap=4097, fcap=65537, qcap=65537, kcap=4097)
+        big = tuple(over[k] if k == what else v for k, v in caps.items())
+        named = r"%s %d outside 1 \.\. %d" % (what, over[what], over[what] - 1)
     out = [np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros((1, 9), np.float32), None]
-    with pytest.raises(MslError, match=r"\(-1\)"):                            # refused before the arrays are read on the device
+    with pytest.raises(MslError, match=r"\(-1\): msl_manhattan_detect: " + named + "$"):   # refused before the arrays are read on the device
         check(lib.msl_manhattan_detect_batch(0, 1, *big, ptr(_prm()), *[ptr(a) for a in arrays], 0, *[ptr(a) for a in out], 0),
               "msl_manhattan_detect_batch")
     r0 = np.zeros((1, 9), np.float32)

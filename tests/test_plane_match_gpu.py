@@ -107,14 +107,15 @@ def test_limits_are_refused_without_a_launch(what):
     fr = sc.room(3050)[0]
     caps = dict(pcap=16, mcap=16, ptcap=4096)
     caps[what] = dict(pcap=65, mcap=4097, ptcap=(1 << 22) + 1)[what]
+    named = r"\(-1\): msl_plane_associate: %s %d outside 1 \.\. %d$" % (what, caps[what], caps[what] - 1)
     if what == "ptcap":                                                       # the refusal comes before any staging of the arrays
         from manhattanslam_amd._lib import check, lib, ptr
         (pc, mc, _), arrays, match = plane.pack_associate([fr], 16, 16, 4096)
         out = [np.zeros(1, np.int32), np.zeros((1, 16, 12), np.float32), np.zeros((1, 16), np.uint8), None]
-        with pytest.raises(MslError, match=r"\(-1\)"):
+        with pytest.raises(MslError, match=named):
             check(lib.msl_plane_associate_batch(0, 1, pc, mc, caps["ptcap"], ptr(_prm()), *[ptr(a) for a in arrays], 0, ptr(match),
                                                 *[ptr(a) for a in out], 0), "msl_plane_associate_batch")
     else:
-        with pytest.raises(MslError, match=r"\(-1\)"):
+        with pytest.raises(MslError, match=named):
             plane.plane_association_batch(_prm(), [fr], caps=(caps["pcap"], caps["mcap"], caps["ptcap"]))
     _check([fr], plane.plane_association_batch(_prm(), [fr]))                  # the device is still usable
