@@ -363,7 +363,13 @@ typedef struct msl_match_params {
 /* One matcher handle = one ORBmatcher object of the reference (src/ORBmatcher.cc:41): its own HIP stream and its own grow-only scratch and staging
  * buffers, used by one thread at a time, device re-bound at every entry.  msl_match_by_projection is asynchronous on the handle's stream when inputs
  * AND outputs are device memory (msl_match_sync / msl_match_set_stream as for the other handles); with host memory on either side it returns when the
- * caller's buffers are its own again. */
+ * caller's buffers are its own again.
+ * Every entry point on the handle checks its arguments before it touches a device: an int argument outside its limits, a required array
+ * that is NULL or a params field outside its range is refused with MSL_ERR_INVALID, msl_last_error() names it ("msl_match_local_points:
+ * mcap 32769 outside 1 .. 32768", "msl_pose_optimize: Tcw is NULL", "msl_match_by_projection: fx is 0"), nothing is launched and no output
+ * byte is written.  The _batch forms refuse before the device's shared handle is created, so also on a machine without a device.  (The
+ * Tracking entries -- the searches, the pose optimisers, the bag-of-words calls, the relocalisation calls, msl_pnp_ransac, msl_lines_3d --
+ * used to answer one "invalid argument (cap <= 8192, ...)" for all of these; the calls they accept are the same as then.) */
 typedef struct msl_match msl_match;
 MSL_API msl_match *msl_match_create(int device) MSL_NOEXCEPT;
 MSL_API void msl_match_destroy(msl_match *h) MSL_NOEXCEPT;

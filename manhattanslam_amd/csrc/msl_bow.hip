@@ -44,7 +44,7 @@ struct msl_vocab {
 
 namespace {
 
-constexpr int MAX_LCAP = 256, MAX_K = 20, MAX_L = 10;
+constexpr int MAX_K = 20, MAX_L = 10;
 constexpr int IDX_BITS = 13;                       // feature index < MAX_CAP
 constexpr int VEC_NT = 1024, BOW_NT = 1024, LD_NT = 256;
 constexpr unsigned long long KEY_NONE = ~0ull;
@@ -265,14 +265,14 @@ __global__ __launch_bounds__(BOW_NT) void k_match_bow(BowMatchDev M) {
 
 // ==== LSDmatcher::SearchByDescriptor =======================================================================================================
 __global__ __launch_bounds__(LD_NT) void k_match_ldesc(LdescDev L) {
-    __shared__ uint4 s_kd[2 * MAX_LCAP];
-    __shared__ int s_best[MAX_LCAP], s_m[MAX_LCAP], s_nm;
+    __shared__ uint4 s_kd[2 * MAX_KLCAP];
+    __shared__ int s_best[MAX_KLCAP], s_m[MAX_KLCAP], s_nm;
     const int f = blockIdx.x, lane = lane_id(), wave = threadIdx.x >> 6;
     const int nKf = clampi(L.nKf[f], 0, L.klcap), nCur = clampi(L.nCur[f], 0, L.lcap);
     const size_t kb = (size_t)f * L.klcap, cb = (size_t)f * L.lcap;
     const bool run = nKf > 0 && nCur >= 2;                     // otherwise the reference reads past a vector's end: defined as no match
     for (int q = threadIdx.x; q < nKf; q += LD_NT) load_desc(L.kfLdesc + (kb + q) * 32, s_kd[2 * q], s_kd[2 * q + 1]);
-    for (int t = threadIdx.x; t < MAX_LCAP; t += LD_NT) { s_best[t] = -1; s_m[t] = -1; }
+    for (int t = threadIdx.x; t < MAX_KLCAP; t += LD_NT) { s_best[t] = -1; s_m[t] = -1; }
     if (threadIdx.x == 0) s_nm = 0;
     uint4 c[4][2];
 #pragma unroll
@@ -421,14 +421,25 @@ msl_vocab *vocab_load_text(int device, const char *path) {
     return vocab_create(device, k, L, sc, wt, (int)parent.size(), parent.data(), leaf.data(), desc.data(), weight.data());
 }
 
-int run_transform(msl_match *h, const msl_vocab *v, int n_frames, int cap, int levelsup, const uint8_t *desc, const int32_t *n_desc, msl_mem mem,
-                  int32_t *word_out, int32_t *node_out, int32_t *bow_word, double *bow_value, int32_t *n_words, msl_mem out_mem) {
-    const bool vec = bow_word || bow_value || n_words;
-    if (!h || n_frames < 1 || cap < 1 || cap > MAX_CAP || !desc || !n_desc || !word_out || !node_out || (vec && !(bow_word && bow_value && n_words))) {
-        set_error("msl_bow_transform: invalid argument (1 <= cap <= %d; bow_word, bow_value, n_words all given or all NULL)", MAX_CAP);
+constexpr const char *WHO_TRANSFORM = "msl_bow_transform", *WHO_BOW = "msl_match_by_bow", *WHO_LDESC = "msl_match_lines_by_descriptor";
+
+// The vocabulary is compared with the handle's device, so it is launch_transform's to test.
+int check_transform(const msl_vocab *, int n_frames, int cap, int, const uint8_t *desc, const int32_t *n_desc, msl_mem, int32_t *word_out,
+                    int32_t *node_out, int32_t *bow_word, double *bow_value, int32_t *n_words, msl_mem) {
+    const char *who = WHO_TRANSFORM;
+    if (!none_null(who, {MSL_NAMED(desc), MSL_NAMED(n_desc), MSL_NAMED(word_out), MSL_NAMED(node_out)})) return MSL_ERR_INVALID;
+    if (!at_least_one(who, "n_frames", n_frames) || !in_range(who, "cap", cap, 1, MAX_CAP)) return MSL_ERR_INVALID;
+    if ((bow_word || bow_value || n_words) && !(bow_word && bow_value && n_words)) {
+        set_error("%s: bow_word, bow_value and n_words are given all or none", who);
         return MSL_ERR_INVALID;
     }
-    int rc = vocab_check(v, h->device, "msl_bow_transform");
+    return MSL_OK;
+}
+
+int launch_transform(msl_match *h, const msl_vocab *v, int n_frames, int cap, int levelsup, const uint8_t *desc, const int32_t *n_desc, msl_mem mem,
+                     int32_t *word_out, int32_t *node_out, int32_t *bow_word, double *bow_value, int32_t *n_words, msl_mem out_mem) {
+    const bool vec = bow_word != nullptr;                                   // the three arrays of the vector: all or none
+    int rc = vocab_check(v, h->device, WHO_TRANSFORM);
     if (rc != MSL_OK) return rc;
     rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
@@ -462,14 +473,20 @@ int run_transform(msl_match *h, const msl_vocab *v, int n_frames, int cap, int l
     return MSL_OK;
 }
 
-int run_match_bow(msl_match *h, int n_pairs, int cap, const msl_bow_match_params *prm, const uint8_t *kf_desc, const float *kf_angle,
-                  const int32_t *kf_node, const uint8_t *kf_flags, const int32_t *n_kf, const msl_keypoint *cur_kps, const uint8_t *cur_desc,
-                  const int32_t *cur_node, const int32_t *n_cur, msl_mem mem, int32_t *match_out, int32_t *nmatches, msl_mem out_mem) {
-    if (!h || n_pairs < 1 || cap < 1 || cap > MAX_CAP || !prm || !kf_desc || !kf_angle || !kf_node || !kf_flags || !n_kf || !cur_kps || !cur_desc ||
-        !cur_node || !n_cur || !match_out || !nmatches) {
-        set_error("msl_match_by_bow: invalid argument (1 <= cap <= %d)", MAX_CAP);
+int check_match_bow(int n_pairs, int cap, const msl_bow_match_params *params, const uint8_t *kf_desc, const float *kf_angle, const int32_t *kf_node,
+                    const uint8_t *kf_flags, const int32_t *n_kf, const msl_keypoint *cur_kps, const uint8_t *cur_desc, const int32_t *cur_node,
+                    const int32_t *n_cur, msl_mem, int32_t *match_out, int32_t *nmatches, msl_mem) {
+    const char *who = WHO_BOW;
+    if (!none_null(who, {MSL_NAMED(params), MSL_NAMED(kf_desc), MSL_NAMED(kf_angle), MSL_NAMED(kf_node), MSL_NAMED(kf_flags), MSL_NAMED(n_kf),
+                         MSL_NAMED(cur_kps), MSL_NAMED(cur_desc), MSL_NAMED(cur_node), MSL_NAMED(n_cur), MSL_NAMED(match_out), MSL_NAMED(nmatches)}))
         return MSL_ERR_INVALID;
-    }
+    if (!at_least_one(who, "n_pairs", n_pairs) || !in_range(who, "cap", cap, 1, MAX_CAP)) return MSL_ERR_INVALID;
+    return MSL_OK;
+}
+
+int launch_match_bow(msl_match *h, int n_pairs, int cap, const msl_bow_match_params *prm, const uint8_t *kf_desc, const float *kf_angle,
+                     const int32_t *kf_node, const uint8_t *kf_flags, const int32_t *n_kf, const msl_keypoint *cur_kps, const uint8_t *cur_desc,
+                     const int32_t *cur_node, const int32_t *n_cur, msl_mem mem, int32_t *match_out, int32_t *nmatches, msl_mem out_mem) {
     int rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
     hipStream_t st = h->stream;
@@ -489,15 +506,23 @@ int run_match_bow(msl_match *h, int n_pairs, int cap, const msl_bow_match_params
     return MSL_OK;
 }
 
-int run_match_ldesc(msl_match *h, int n_pairs, int lcap, int klcap, const uint8_t *kf_ldesc, const uint8_t *kf_line_flags, const double *kf_line_xyz,
-                    const int32_t *n_kf_lines, const uint8_t *cur_ldesc, const int32_t *n_cur_lines, msl_mem mem, int32_t *match_out,
-                    int32_t *nmatches, double *line_xyz, uint8_t *line_has, msl_mem out_mem) {
-    if (!h || n_pairs < 1 || lcap < 1 || lcap > MAX_LCAP || klcap < 1 || klcap > MAX_LCAP || !kf_ldesc || !kf_line_flags || !n_kf_lines ||
-        !cur_ldesc || !n_cur_lines || !match_out || !nmatches || (!line_xyz != !line_has) || (line_xyz && !kf_line_xyz)) {
-        set_error("msl_match_lines_by_descriptor: invalid argument (1 <= lcap, klcap <= %d; line_xyz and line_has together, with kf_line_xyz)",
-                  MAX_LCAP);
+// kf_line_xyz, line_xyz and line_has are optional: the last two together, and then with the first.
+int check_match_ldesc(int n_pairs, int lcap, int klcap, const uint8_t *kf_ldesc, const uint8_t *kf_line_flags, const double *kf_line_xyz,
+                      const int32_t *n_kf_lines, const uint8_t *cur_ldesc, const int32_t *n_cur_lines, msl_mem, int32_t *match_out, int32_t *nmatches,
+                      double *line_xyz, uint8_t *line_has, msl_mem) {
+    const char *who = WHO_LDESC;
+    if (!none_null(who, {MSL_NAMED(kf_ldesc), MSL_NAMED(kf_line_flags), MSL_NAMED(n_kf_lines), MSL_NAMED(cur_ldesc), MSL_NAMED(n_cur_lines),
+                         MSL_NAMED(match_out), MSL_NAMED(nmatches)})) return MSL_ERR_INVALID;
+    if (!at_least_one(who, "n_pairs", n_pairs) || !in_range(who, "lcap", lcap, 1, MAX_KLCAP) || !in_range(who, "klcap", klcap, 1, MAX_KLCAP))
         return MSL_ERR_INVALID;
-    }
+    if (!line_xyz != !line_has) { set_error("%s: line_xyz and line_has are given together", who); return MSL_ERR_INVALID; }
+    if (line_xyz && !none_null(who, {MSL_NAMED(kf_line_xyz)})) return MSL_ERR_INVALID;
+    return MSL_OK;
+}
+
+int launch_match_ldesc(msl_match *h, int n_pairs, int lcap, int klcap, const uint8_t *kf_ldesc, const uint8_t *kf_line_flags, const double *kf_line_xyz,
+                       const int32_t *n_kf_lines, const uint8_t *cur_ldesc, const int32_t *n_cur_lines, msl_mem mem, int32_t *match_out,
+                       int32_t *nmatches, double *line_xyz, uint8_t *line_has, msl_mem out_mem) {
     int rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
     hipStream_t st = h->stream;
@@ -552,7 +577,8 @@ int msl_vocab_info(const msl_vocab *v, int32_t info[7]) noexcept {
 int msl_bow_transform(msl_match *h, const msl_vocab *v, int n_frames, int cap, int levelsup, const uint8_t *desc, const int32_t *n_desc, msl_mem mem,
                       int32_t *word_out, int32_t *node_out, int32_t *bow_word, double *bow_value, int32_t *n_words, msl_mem out_mem) noexcept {
     try {
-    return run_transform(h, v, n_frames, cap, levelsup, desc, n_desc, mem, word_out, node_out, bow_word, bow_value, n_words, out_mem);
+    return handle_form(WHO_TRANSFORM, check_transform, launch_transform, h, v, n_frames, cap, levelsup, desc, n_desc, mem, word_out, node_out, bow_word,
+                       bow_value, n_words, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -560,8 +586,8 @@ int msl_bow_transform_batch(int device, const msl_vocab *v, int n_frames, int ca
                             msl_mem mem, int32_t *word_out, int32_t *node_out, int32_t *bow_word, double *bow_value, int32_t *n_words,
                             msl_mem out_mem) noexcept {
     try {
-    return abi_call_default(run_transform, device, mem == MSL_MEM_DEVICE, v, n_frames, cap, levelsup, desc, n_desc, mem, word_out, node_out, bow_word,
-                            bow_value, n_words, out_mem);
+    return batch_form(check_transform, launch_transform, device, mem == MSL_MEM_DEVICE, v, n_frames, cap, levelsup, desc, n_desc, mem, word_out, node_out,
+                      bow_word, bow_value, n_words, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -569,8 +595,8 @@ int msl_match_by_bow(msl_match *h, int n_pairs, int cap, const msl_bow_match_par
                      const int32_t *kf_node, const uint8_t *kf_flags, const int32_t *n_kf, const msl_keypoint *cur_kps, const uint8_t *cur_desc,
                      const int32_t *cur_node, const int32_t *n_cur, msl_mem mem, int32_t *match_out, int32_t *nmatches, msl_mem out_mem) noexcept {
     try {
-    return run_match_bow(h, n_pairs, cap, params, kf_desc, kf_angle, kf_node, kf_flags, n_kf, cur_kps, cur_desc, cur_node, n_cur, mem, match_out, nmatches,
-                         out_mem);
+    return handle_form(WHO_BOW, check_match_bow, launch_match_bow, h, n_pairs, cap, params, kf_desc, kf_angle, kf_node, kf_flags, n_kf, cur_kps, cur_desc,
+                       cur_node, n_cur, mem, match_out, nmatches, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -579,8 +605,8 @@ int msl_match_by_bow_batch(int device, int n_pairs, int cap, const msl_bow_match
                            const uint8_t *cur_desc, const int32_t *cur_node, const int32_t *n_cur, msl_mem mem, int32_t *match_out,
                            int32_t *nmatches, msl_mem out_mem) noexcept {
     try {
-    return abi_call_default(run_match_bow, device, mem == MSL_MEM_DEVICE, n_pairs, cap, params, kf_desc, kf_angle, kf_node, kf_flags, n_kf, cur_kps, cur_desc,
-                            cur_node, n_cur, mem, match_out, nmatches, out_mem);
+    return batch_form(check_match_bow, launch_match_bow, device, mem == MSL_MEM_DEVICE, n_pairs, cap, params, kf_desc, kf_angle, kf_node, kf_flags, n_kf,
+                      cur_kps, cur_desc, cur_node, n_cur, mem, match_out, nmatches, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -589,8 +615,8 @@ int msl_match_lines_by_descriptor(msl_match *h, int n_pairs, int lcap, int klcap
                                   msl_mem mem, int32_t *match_out, int32_t *nmatches, double *line_xyz, uint8_t *line_has,
                                   msl_mem out_mem) noexcept {
     try {
-    return run_match_ldesc(h, n_pairs, lcap, klcap, kf_ldesc, kf_line_flags, kf_line_xyz, n_kf_lines, cur_ldesc, n_cur_lines, mem, match_out, nmatches,
-                           line_xyz, line_has, out_mem);
+    return handle_form(WHO_LDESC, check_match_ldesc, launch_match_ldesc, h, n_pairs, lcap, klcap, kf_ldesc, kf_line_flags, kf_line_xyz, n_kf_lines,
+                       cur_ldesc, n_cur_lines, mem, match_out, nmatches, line_xyz, line_has, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -600,8 +626,8 @@ int msl_match_lines_by_descriptor_batch(int device, int n_pairs, int lcap, int k
                                         uint8_t *line_has, msl_mem out_mem) noexcept {
     // line_xyz is in/out: device-memory outputs are read as well
     try {
-    return abi_call_default(run_match_ldesc, device, mem == MSL_MEM_DEVICE || out_mem == MSL_MEM_DEVICE, n_pairs, lcap, klcap, kf_ldesc, kf_line_flags,
-                            kf_line_xyz, n_kf_lines, cur_ldesc, n_cur_lines, mem, match_out, nmatches, line_xyz, line_has, out_mem);
+    return batch_form(check_match_ldesc, launch_match_ldesc, device, mem == MSL_MEM_DEVICE || out_mem == MSL_MEM_DEVICE, n_pairs, lcap, klcap, kf_ldesc,
+                      kf_line_flags, kf_line_xyz, n_kf_lines, cur_ldesc, n_cur_lines, mem, match_out, nmatches, line_xyz, line_has, out_mem);
     } MSL_ABI_CATCH_INT
 }
 

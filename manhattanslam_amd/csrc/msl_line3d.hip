@@ -32,7 +32,7 @@ namespace {
 
 using namespace msl;
 
-constexpr int MAX_LCAP = 256, MAX_SAMPLES = 127, MAX_ITERS = 64, NS = 128;
+constexpr int MAX_SAMPLES = 127, MAX_ITERS = 64, NS = 128;
 constexpr double L3_EPS = 1e-10;             // 3DLineExtractor.h's EPS
 
 // What msl_lines_3d_debug reads back per keyline.
@@ -351,14 +351,14 @@ __global__ __launch_bounds__(WAVE) void k_line3d(Line3dDev D) {
 
 // The walk of the call site over one frame's keylines (the per-keyline results are complete).
 __global__ __launch_bounds__(WAVE) void k_line3d_select(Line3dDev D) {
-    __shared__ float key[MAX_LCAP];
-    __shared__ int ord[MAX_LCAP];
-    __shared__ uint8_t member[MAX_LCAP], isNew[MAX_LCAP];
+    __shared__ float key[MAX_KLCAP];
+    __shared__ int ord[MAX_KLCAP];
+    __shared__ uint8_t member[MAX_KLCAP], isNew[MAX_KLCAP];
     const size_t f = blockIdx.x;
     const int lane = threadIdx.x;
     int nl = D.nLines[f];
     nl = nl < 0 ? 0 : (nl > D.lcap ? D.lcap : nl);
-    for (int i = lane; i < MAX_LCAP; i += WAVE) {
+    for (int i = lane; i < MAX_KLCAP; i += WAVE) {
         bool both = false; float k = 0.0f;
         if (i < nl) {
             const float z0 = D.lineDepth[2 * (f * D.lcap + i)], z1 = D.lineDepth[2 * (f * D.lcap + i) + 1];
@@ -374,7 +374,7 @@ __global__ __launch_bounds__(WAVE) void k_line3d_select(Line3dDev D) {
     } else {
         // the position of every member in the walk: the members that sort before it (sort of pair<float, int>), counted
         int M = 0;
-        for (int i = lane; i < MAX_LCAP; i += WAVE) {
+        for (int i = lane; i < MAX_KLCAP; i += WAVE) {
             int rank = 0;
             const float ki = key[i];
             for (int o = 0; o < nl; o++) rank += member[o] && (key[o] < ki || (key[o] == ki && o < i)) ? 1 : 0;
@@ -406,32 +406,40 @@ __global__ __launch_bounds__(WAVE) void k_line3d_select(Line3dDev D) {
     if (lane == 0) D.nNew[f] = total;
 }
 
-int run_line3d(msl_match *h, int n_frames, int lcap, int order, const msl_line3d_params *prm, const float *line_ends, const int32_t *n_lines,
-               const float *depth, size_t depth_row_stride, size_t depth_frame_stride, int width, int height, const uint8_t *line_flags,
-               const float *Tcw, const uint32_t *seed, msl_mem mem, float *line_depth, double *line_xyz, uint8_t *line_ok, uint8_t *line_new,
-               int32_t *n_support, int32_t *n_new, msl_mem out_mem) {
-    if (!h || n_frames < 1 || !prm || !line_ends || !n_lines || !depth || !Tcw || !seed || !line_depth || !line_xyz || !line_ok || !line_new ||
-        !n_support || !n_new) {
-        set_error("msl_lines_3d: invalid argument (null pointer or n_frames < 1)");
+constexpr const char *WHO = "msl_lines_3d";
+
+// line_flags is optional.
+int check_line3d(int n_frames, int lcap, int order, const msl_line3d_params *params, const float *line_ends, const int32_t *n_lines, const float *depth,
+                 size_t depth_row_stride, size_t depth_frame_stride, int width, int height, const uint8_t *, const float *Tcw, const uint32_t *seed,
+                 msl_mem, float *line_depth, double *line_xyz, uint8_t *line_ok, uint8_t *line_new, int32_t *n_support, int32_t *n_new, msl_mem) {
+    if (!none_null(WHO, {MSL_NAMED(params), MSL_NAMED(line_ends), MSL_NAMED(n_lines), MSL_NAMED(depth), MSL_NAMED(Tcw), MSL_NAMED(seed),
+                         MSL_NAMED(line_depth), MSL_NAMED(line_xyz), MSL_NAMED(line_ok), MSL_NAMED(line_new), MSL_NAMED(n_support), MSL_NAMED(n_new)}))
+        return MSL_ERR_INVALID;
+    if (!at_least_one(WHO, "n_frames", n_frames)) return MSL_ERR_INVALID;
+    if (lcap < 1 || lcap > MAX_KLCAP) { set_error("%s: lcap %d outside 1 .. %d", WHO, lcap, MAX_KLCAP); return MSL_ERR_INVALID; }
+    if (order < MSL_LINE3D_ALL || order > MSL_LINE3D_DEPTH_ORDER) { set_error("%s: order %d is not an MSL_LINE3D_* value", WHO, order); return MSL_ERR_INVALID; }
+    if (params->max_samples < 1 || params->max_samples > MAX_SAMPLES) {
+        set_error("%s: max_samples %d outside 1 .. %d", WHO, params->max_samples, MAX_SAMPLES);
         return MSL_ERR_INVALID;
     }
-    if (lcap < 1 || lcap > MAX_LCAP) { set_error("msl_lines_3d: lcap %d outside 1 .. %d", lcap, MAX_LCAP); return MSL_ERR_INVALID; }
-    if (order < MSL_LINE3D_ALL || order > MSL_LINE3D_DEPTH_ORDER) { set_error("msl_lines_3d: order %d is not an MSL_LINE3D_* value", order); return MSL_ERR_INVALID; }
-    if (prm->max_samples < 1 || prm->max_samples > MAX_SAMPLES) {
-        set_error("msl_lines_3d: max_samples %d outside 1 .. %d", prm->max_samples, MAX_SAMPLES);
+    if (params->max_iterations < 0 || params->max_iterations > MAX_ITERS) {
+        set_error("%s: max_iterations %d outside 0 .. %d", WHO, params->max_iterations, MAX_ITERS);
         return MSL_ERR_INVALID;
     }
-    if (prm->max_iterations < 0 || prm->max_iterations > MAX_ITERS) {
-        set_error("msl_lines_3d: max_iterations %d outside 0 .. %d", prm->max_iterations, MAX_ITERS);
-        return MSL_ERR_INVALID;
-    }
-    if (prm->min_points < 2) { set_error("msl_lines_3d: min_points %d below 2", prm->min_points); return MSL_ERR_INVALID; }
+    if (params->min_points < 2) { set_error("%s: min_points %d below 2", WHO, params->min_points); return MSL_ERR_INVALID; }
     if (width < 1 || height < 1 || depth_row_stride < (size_t)width * sizeof(float) || depth_row_stride % sizeof(float) != 0 ||
         depth_frame_stride % sizeof(float) != 0 || (n_frames > 1 && depth_frame_stride < depth_row_stride * (size_t)height)) {
-        set_error("msl_lines_3d: depth image %d x %d with strides %zu / %zu bytes is not a float image", width, height, depth_row_stride,
+        set_error("%s: depth image %d x %d with strides %zu / %zu bytes is not a float image", WHO, width, height, depth_row_stride,
                   depth_frame_stride);
         return MSL_ERR_INVALID;
     }
+    return MSL_OK;
+}
+
+int launch_line3d(msl_match *h, int n_frames, int lcap, int order, const msl_line3d_params *prm, const float *line_ends, const int32_t *n_lines,
+                  const float *depth, size_t depth_row_stride, size_t depth_frame_stride, int width, int height, const uint8_t *line_flags,
+                  const float *Tcw, const uint32_t *seed, msl_mem mem, float *line_depth, double *line_xyz, uint8_t *line_ok, uint8_t *line_new,
+                  int32_t *n_support, int32_t *n_new, msl_mem out_mem) {
     int rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
     hipStream_t st = h->stream;
@@ -469,8 +477,8 @@ int msl_lines_3d(msl_match *h, int n_frames, int lcap, int order, const msl_line
                  const uint8_t *line_flags, const float *Tcw, const uint32_t *seed, msl_mem mem, float *line_depth, double *line_xyz,
                  uint8_t *line_ok, uint8_t *line_new, int32_t *n_support, int32_t *n_new, msl_mem out_mem) noexcept {
     try {
-    return run_line3d(h, n_frames, lcap, order, params, line_ends, n_lines, depth, depth_row_stride, depth_frame_stride, width, height, line_flags,
-                      Tcw, seed, mem, line_depth, line_xyz, line_ok, line_new, n_support, n_new, out_mem);
+    return handle_form(WHO, check_line3d, launch_line3d, h, n_frames, lcap, order, params, line_ends, n_lines, depth, depth_row_stride, depth_frame_stride,
+                       width, height, line_flags, Tcw, seed, mem, line_depth, line_xyz, line_ok, line_new, n_support, n_new, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -479,9 +487,9 @@ int msl_lines_3d_batch(int device, int n_frames, int lcap, int order, const msl_
                        const uint8_t *line_flags, const float *Tcw, const uint32_t *seed, msl_mem mem, float *line_depth, double *line_xyz,
                        uint8_t *line_ok, uint8_t *line_new, int32_t *n_support, int32_t *n_new, msl_mem out_mem) noexcept {
     try {
-    return abi_call_default(run_line3d, device, mem == MSL_MEM_DEVICE || out_mem == MSL_MEM_DEVICE, n_frames, lcap, order, params, line_ends, n_lines,
-                            depth, depth_row_stride, depth_frame_stride, width, height, line_flags, Tcw, seed, mem, line_depth, line_xyz, line_ok,
-                            line_new, n_support, n_new, out_mem);
+    return batch_form(check_line3d, launch_line3d, device, mem == MSL_MEM_DEVICE || out_mem == MSL_MEM_DEVICE, n_frames, lcap, order, params, line_ends,
+                      n_lines, depth, depth_row_stride, depth_frame_stride, width, height, line_flags, Tcw, seed, mem, line_depth, line_xyz, line_ok, line_new,
+                      n_support, n_new, out_mem);
     } MSL_ABI_CATCH_INT
 }
 

@@ -29,7 +29,7 @@ using namespace msl;
 namespace {
 
 constexpr int TH_HIGH = 100;                       // src/LSDmatcher.cpp:15
-constexpr int MAX_LCAP = 256, MAX_LLCAP = 256, MAX_MLCAP = 32768;
+constexpr int MAX_LLCAP = 256;                     // lines of the last frame; keylines: MAX_KLCAP, local map lines: MAX_MCAP (msl_match_handle.h)
 constexpr int LINE_NT = 1024;
 constexpr unsigned K_NONE = 0xFFFFFFFFu;
 
@@ -129,9 +129,9 @@ __global__ __launch_bounds__(256) void k_line_query(LineDev D) {
 // LDS: keylines 4 KB + descriptors 8 KB + t 1 KB static, pick[ncap] short dynamic (64 KB at mlcap = 32768): 77 KB at the limits.
 template <bool LOCAL>
 __global__ __launch_bounds__(LINE_NT) void k_line_assign(LineDev D) {
-    __shared__ msl_keyline s_kl[MAX_LCAP];
-    __shared__ uint4 s_desc[2 * MAX_LCAP];
-    __shared__ int s_t[MAX_LCAP];
+    __shared__ msl_keyline s_kl[MAX_KLCAP];
+    __shared__ uint4 s_desc[2 * MAX_KLCAP];
+    __shared__ int s_t[MAX_KLCAP];
     __shared__ int s_nm, s_ntm;
     extern __shared__ short s_pick[];               // [ncap]
     const int f = blockIdx.x;
@@ -212,20 +212,26 @@ bool reads_device(msl_mem mem, const double *line_xyz, const uint8_t *line_has, 
     return mem == MSL_MEM_DEVICE || ((line_xyz || line_has) && out_mem == MSL_MEM_DEVICE);
 }
 
-bool bad_base(const msl_match_params &b) {
-    return b.nlevels < 1 || b.nlevels > MSL_MATCH_MAX_LEVELS || !(b.maxX > b.minX) || !(b.maxY > b.minY) || b.fx == 0;
+constexpr const char *WHO_LAST = "msl_match_lines_by_projection", *WHO_LOCAL = "msl_match_local_lines";
+
+// In both checks line_xyz and line_has are optional, each on its own.
+int check_lines_last(int n_frames, int lcap, int llcap, const msl_line_match_params *params, const msl_keyline *cur_kl, const uint8_t *cur_ldesc,
+                     const int32_t *n_cur_lines, const double *last_line_xyz, const uint8_t *last_ldesc, const uint8_t *last_line_flags,
+                     const int32_t *last_line_octave, const int32_t *n_last_lines, const float *Tcw_cur, const float *Tcw_last, msl_mem,
+                     int32_t *match_out, int32_t *nmatches, double *, uint8_t *, msl_mem) {
+    const char *who = WHO_LAST;
+    if (!none_null(who, {MSL_NAMED(params), MSL_NAMED(cur_kl), MSL_NAMED(cur_ldesc), MSL_NAMED(n_cur_lines), MSL_NAMED(last_line_xyz),
+                         MSL_NAMED(last_ldesc), MSL_NAMED(last_line_flags), MSL_NAMED(last_line_octave), MSL_NAMED(n_last_lines), MSL_NAMED(Tcw_cur),
+                         MSL_NAMED(Tcw_last), MSL_NAMED(match_out), MSL_NAMED(nmatches)})) return MSL_ERR_INVALID;
+    if (!at_least_one(who, "n_frames", n_frames) || !in_range(who, "lcap", lcap, 1, MAX_KLCAP) || !in_range(who, "llcap", llcap, 1, MAX_LLCAP) ||
+        !frame_ok(who, params->base)) return MSL_ERR_INVALID;
+    return MSL_OK;
 }
 
-int run_lines_last(msl_match *h, int n_frames, int lcap, int llcap, const msl_line_match_params *params, const msl_keyline *cur_kl,
-                   const uint8_t *cur_ldesc, const int32_t *n_cur_lines, const double *last_line_xyz, const uint8_t *last_ldesc,
-                   const uint8_t *last_line_flags, const int32_t *last_line_octave, const int32_t *n_last_lines, const float *Tcw_cur,
-                   const float *Tcw_last, msl_mem mem, int32_t *match_out, int32_t *nmatches, double *line_xyz, uint8_t *line_has, msl_mem out_mem) {
-    if (!h || n_frames < 1 || lcap < 1 || lcap > MAX_LCAP || llcap < 1 || llcap > MAX_LLCAP || !params || !cur_kl || !cur_ldesc || !n_cur_lines ||
-        !last_line_xyz || !last_ldesc || !last_line_flags || !last_line_octave || !n_last_lines || !Tcw_cur || !Tcw_last || !match_out || !nmatches ||
-        bad_base(params->base)) {
-        set_error("msl_match_lines_by_projection: invalid argument (lcap <= %d, llcap <= %d, nlevels <= %d)", MAX_LCAP, MAX_LLCAP, MSL_MATCH_MAX_LEVELS);
-        return MSL_ERR_INVALID;
-    }
+int launch_lines_last(msl_match *h, int n_frames, int lcap, int llcap, const msl_line_match_params *params, const msl_keyline *cur_kl,
+                      const uint8_t *cur_ldesc, const int32_t *n_cur_lines, const double *last_line_xyz, const uint8_t *last_ldesc,
+                      const uint8_t *last_line_flags, const int32_t *last_line_octave, const int32_t *n_last_lines, const float *Tcw_cur,
+                      const float *Tcw_last, msl_mem mem, int32_t *match_out, int32_t *nmatches, double *line_xyz, uint8_t *line_has, msl_mem out_mem) {
     int rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
     hipStream_t st = h->stream;
@@ -249,18 +255,24 @@ int run_lines_last(msl_match *h, int n_frames, int lcap, int llcap, const msl_li
     return MSL_OK;
 }
 
-int run_lines_local(msl_match *h, int n_frames, int lcap, int mlcap, const msl_line_match_params *params, const msl_keyline *cur_kl,
-                    const uint8_t *cur_ldesc, const int32_t *n_cur_lines, const uint8_t *cur_line_flags, const double *ml_xyz, const double *ml_normal,
-                    const float *ml_dist, const uint8_t *ml_desc, const uint8_t *ml_flags, const int32_t *n_local_lines, const float *Tcw, msl_mem mem,
-                    int32_t *match_out, int32_t *n_to_match, int32_t *nmatches, uint8_t *in_view, msl_line_track *track, double *line_xyz,
-                    uint8_t *line_has, msl_mem out_mem) {
-    if (!h || n_frames < 1 || lcap < 1 || lcap > MAX_LCAP || mlcap < 1 || mlcap > MAX_MLCAP || !params || !cur_kl || !cur_ldesc || !n_cur_lines ||
-        !cur_line_flags || !ml_xyz || !ml_normal || !ml_dist || !ml_desc || !ml_flags || !n_local_lines || !Tcw || !match_out || !n_to_match ||
-        !nmatches || bad_base(params->base) || !(params->log_scale_factor > 0)) {
-        set_error("msl_match_local_lines: invalid argument (lcap <= %d, mlcap <= %d, nlevels <= %d, log_scale_factor > 0)", MAX_LCAP, MAX_MLCAP,
-                  MSL_MATCH_MAX_LEVELS);
-        return MSL_ERR_INVALID;
-    }
+int check_lines_local(int n_frames, int lcap, int mlcap, const msl_line_match_params *params, const msl_keyline *cur_kl, const uint8_t *cur_ldesc,
+                      const int32_t *n_cur_lines, const uint8_t *cur_line_flags, const double *ml_xyz, const double *ml_normal, const float *ml_dist,
+                      const uint8_t *ml_desc, const uint8_t *ml_flags, const int32_t *n_local_lines, const float *Tcw, msl_mem, int32_t *match_out,
+                      int32_t *n_to_match, int32_t *nmatches, uint8_t *, msl_line_track *, double *, uint8_t *, msl_mem) {
+    const char *who = WHO_LOCAL;
+    if (!none_null(who, {MSL_NAMED(params), MSL_NAMED(cur_kl), MSL_NAMED(cur_ldesc), MSL_NAMED(n_cur_lines), MSL_NAMED(cur_line_flags),
+                         MSL_NAMED(ml_xyz), MSL_NAMED(ml_normal), MSL_NAMED(ml_dist), MSL_NAMED(ml_desc), MSL_NAMED(ml_flags), MSL_NAMED(n_local_lines),
+                         MSL_NAMED(Tcw), MSL_NAMED(match_out), MSL_NAMED(n_to_match), MSL_NAMED(nmatches)})) return MSL_ERR_INVALID;   // in_view, track: optional
+    if (!at_least_one(who, "n_frames", n_frames) || !in_range(who, "lcap", lcap, 1, MAX_KLCAP) || !in_range(who, "mlcap", mlcap, 1, MAX_MCAP) ||
+        !frame_ok(who, params->base) || !log_scale_ok(who, params->log_scale_factor)) return MSL_ERR_INVALID;
+    return MSL_OK;
+}
+
+int launch_lines_local(msl_match *h, int n_frames, int lcap, int mlcap, const msl_line_match_params *params, const msl_keyline *cur_kl,
+                       const uint8_t *cur_ldesc, const int32_t *n_cur_lines, const uint8_t *cur_line_flags, const double *ml_xyz, const double *ml_normal,
+                       const float *ml_dist, const uint8_t *ml_desc, const uint8_t *ml_flags, const int32_t *n_local_lines, const float *Tcw, msl_mem mem,
+                       int32_t *match_out, int32_t *n_to_match, int32_t *nmatches, uint8_t *in_view, msl_line_track *track, double *line_xyz,
+                       uint8_t *line_has, msl_mem out_mem) {
     int rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
     hipStream_t st = h->stream;
@@ -277,7 +289,7 @@ int run_lines_local(msl_match *h, int n_frames, int lcap, int mlcap, const msl_l
     MSL_HIP_TRY(grow_all(st, {{h->lineQ, sizeof(LineQ) * m}, {h->lineTrk, sizeof(msl_line_track) * m}, {h->lineView, m}}));
     D.q = (LineQ *)h->lineQ.p; D.track = (msl_line_track *)h->lineTrk.p; D.inView = (uint8_t *)h->lineView.p;
     D.inViewOut = S.out_of_scratch(in_view, D.inView, m); D.trackOut = S.out_of_scratch(track, D.track, m);   // the optional in_view / track
-    MSL_HIP_TRY(allow_lds(h, LDS_LINE_ASSIGN_LOCAL, k_line_assign<true>, sizeof(short) * MAX_MLCAP));
+    MSL_HIP_TRY(allow_lds(h, LDS_LINE_ASSIGN_LOCAL, k_line_assign<true>, sizeof(short) * MAX_MCAP));
     hipLaunchKernelGGL(k_line_query<true>, dim3((unsigned)((mlcap + 255) / 256), (unsigned)n_frames), dim3(256), 0, st, D);
     hipLaunchKernelGGL(k_line_assign<true>, dim3((unsigned)n_frames), dim3(LINE_NT), sizeof(short) * mlcap, st, D);
     MSL_HIP_TRY(hipGetLastError());
@@ -295,8 +307,8 @@ int msl_match_lines_by_projection(msl_match *h, int n_frames, int lcap, int llca
                                   const float *Tcw_last, msl_mem mem, int32_t *match_out, int32_t *nmatches, double *line_xyz, uint8_t *line_has,
                                   msl_mem out_mem) noexcept {
     try {
-    return run_lines_last(h, n_frames, lcap, llcap, params, cur_kl, cur_ldesc, n_cur_lines, last_line_xyz, last_ldesc, last_line_flags, last_line_octave,
-                          n_last_lines, Tcw_cur, Tcw_last, mem, match_out, nmatches, line_xyz, line_has, out_mem);
+    return handle_form(WHO_LAST, check_lines_last, launch_lines_last, h, n_frames, lcap, llcap, params, cur_kl, cur_ldesc, n_cur_lines, last_line_xyz,
+                       last_ldesc, last_line_flags, last_line_octave, n_last_lines, Tcw_cur, Tcw_last, mem, match_out, nmatches, line_xyz, line_has, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -306,9 +318,9 @@ int msl_match_lines_by_projection_batch(int device, int n_frames, int lcap, int 
                                         const float *Tcw_cur, const float *Tcw_last, msl_mem mem, int32_t *match_out, int32_t *nmatches,
                                         double *line_xyz, uint8_t *line_has, msl_mem out_mem) noexcept {
     try {
-    return abi_call_default(run_lines_last, device, reads_device(mem, line_xyz, line_has, out_mem), n_frames, lcap, llcap, params, cur_kl, cur_ldesc,
-                            n_cur_lines, last_line_xyz, last_ldesc, last_line_flags, last_line_octave, n_last_lines, Tcw_cur, Tcw_last, mem, match_out,
-                            nmatches, line_xyz, line_has, out_mem);
+    return batch_form(check_lines_last, launch_lines_last, device, reads_device(mem, line_xyz, line_has, out_mem), n_frames, lcap, llcap, params, cur_kl,
+                      cur_ldesc, n_cur_lines, last_line_xyz, last_ldesc, last_line_flags, last_line_octave, n_last_lines, Tcw_cur, Tcw_last, mem, match_out,
+                      nmatches, line_xyz, line_has, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -318,8 +330,9 @@ int msl_match_local_lines(msl_match *h, int n_frames, int lcap, int mlcap, const
                           const float *Tcw, msl_mem mem, int32_t *match_out, int32_t *n_to_match, int32_t *nmatches, uint8_t *in_view,
                           msl_line_track *track, double *line_xyz, uint8_t *line_has, msl_mem out_mem) noexcept {
     try {
-    return run_lines_local(h, n_frames, lcap, mlcap, params, cur_kl, cur_ldesc, n_cur_lines, cur_line_flags, ml_xyz, ml_normal, ml_dist, ml_desc, ml_flags,
-                           n_local_lines, Tcw, mem, match_out, n_to_match, nmatches, in_view, track, line_xyz, line_has, out_mem);
+    return handle_form(WHO_LOCAL, check_lines_local, launch_lines_local, h, n_frames, lcap, mlcap, params, cur_kl, cur_ldesc, n_cur_lines, cur_line_flags,
+                       ml_xyz, ml_normal, ml_dist, ml_desc, ml_flags, n_local_lines, Tcw, mem, match_out, n_to_match, nmatches, in_view, track, line_xyz,
+                       line_has, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -329,9 +342,9 @@ int msl_match_local_lines_batch(int device, int n_frames, int lcap, int mlcap, c
                                 const int32_t *n_local_lines, const float *Tcw, msl_mem mem, int32_t *match_out, int32_t *n_to_match, int32_t *nmatches,
                                 uint8_t *in_view, msl_line_track *track, double *line_xyz, uint8_t *line_has, msl_mem out_mem) noexcept {
     try {
-    return abi_call_default(run_lines_local, device, reads_device(mem, line_xyz, line_has, out_mem), n_frames, lcap, mlcap, params, cur_kl, cur_ldesc,
-                            n_cur_lines, cur_line_flags, ml_xyz, ml_normal, ml_dist, ml_desc, ml_flags, n_local_lines, Tcw, mem, match_out, n_to_match,
-                            nmatches, in_view, track, line_xyz, line_has, out_mem);
+    return batch_form(check_lines_local, launch_lines_local, device, reads_device(mem, line_xyz, line_has, out_mem), n_frames, lcap, mlcap, params, cur_kl,
+                      cur_ldesc, n_cur_lines, cur_line_flags, ml_xyz, ml_normal, ml_dist, ml_desc, ml_flags, n_local_lines, Tcw, mem, match_out, n_to_match,
+                      nmatches, in_view, track, line_xyz, line_has, out_mem);
     } MSL_ABI_CATCH_INT
 }
 

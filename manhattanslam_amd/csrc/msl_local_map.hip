@@ -23,7 +23,7 @@ namespace {
 
 using namespace msl;
 
-constexpr int LM_NT = 256, LKF_NT = 1024, LOCAL_KF_STOP = 80, BEST_COVIS = 10, MAX_MCAP = 32768, MAX_GROUP = 32768;
+constexpr int LM_NT = 256, LKF_NT = 1024, LOCAL_KF_STOP = 80, BEST_COVIS = 10, MAX_GROUP = 32768;
 static_assert(MAX_TAB <= 4096 && MAX_CAP <= 8192, "a stamp key (position * cap + slot) << 1 | 1 fits 32 bits, a table index 15");
 
 __device__ __forceinline__ unsigned wave_max(unsigned v) {

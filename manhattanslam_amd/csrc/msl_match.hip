@@ -111,7 +111,6 @@ __global__ __launch_bounds__(ASSIGN_NT) void k_match_assign(MatchDev P) {
 // 256).  So pick(j) is a function of the set of keypoints point j skips, as the hand-out requires.
 // LDS of k_local_assign: t[cap] int + pick[mcap] short = 4 cap + 2 mcap bytes, 96 KB at the limits (cap 8192, mcap 32768): inside the 160 KB
 // of a CDNA4 CU, and no more than k_match_assign asks for at its own limit, so the scratch never spills to global memory.
-constexpr int MAX_MCAP = 32768;
 constexpr int LOCAL_NT = 1024;
 
 struct LocalDev {
@@ -253,17 +252,25 @@ __global__ void k_descriptor_distance(const uint8_t *a, const uint8_t *b, int n,
     out[i] = hamming256(a0, a1, b0, b1);
 }
 
-int run_projection(msl_match *h, int n_pairs, int cap, const msl_match_params *params, const msl_keypoint *cur_kps, const float *cur_un_xy,
-                   const float *cur_uright, const int32_t *cur_grid_cell, const uint8_t *cur_desc, const int32_t *n_cur, const float *last_xyz,
-                   const uint8_t *last_desc, const uint8_t *last_flags, const int32_t *last_octave, const float *last_angle, const int32_t *n_last,
-                   const float *Tcw_cur, const float *Tcw_last, msl_mem mem, int32_t *match_out, int32_t *nmatches, msl_mem out_mem) {
-    if (!h || n_pairs < 1 || cap < 1 || cap > MAX_CAP || !params || !cur_kps || !cur_un_xy || !cur_uright || !cur_grid_cell || !cur_desc || !n_cur ||
-        !last_xyz || !last_desc || !last_flags || !last_octave || !last_angle || !n_last || !Tcw_cur || !Tcw_last || !match_out || !nmatches ||
-        params->nlevels < 1 || params->nlevels > MSL_MATCH_MAX_LEVELS || !(params->maxX > params->minX) || !(params->maxY > params->minY) ||
-        params->fx == 0) {
-        set_error("msl_match_by_projection: invalid argument (cap <= %d, nlevels <= %d)", MAX_CAP, MSL_MATCH_MAX_LEVELS);
-        return MSL_ERR_INVALID;
-    }
+constexpr const char *WHO_PROJECTION = "msl_match_by_projection", *WHO_LOCAL = "msl_match_local_points";
+
+int check_projection(int n_pairs, int cap, const msl_match_params *params, const msl_keypoint *cur_kps, const float *cur_un_xy, const float *cur_uright,
+                     const int32_t *cur_grid_cell, const uint8_t *cur_desc, const int32_t *n_cur, const float *last_xyz, const uint8_t *last_desc,
+                     const uint8_t *last_flags, const int32_t *last_octave, const float *last_angle, const int32_t *n_last, const float *Tcw_cur,
+                     const float *Tcw_last, msl_mem, int32_t *match_out, int32_t *nmatches, msl_mem) {
+    const char *who = WHO_PROJECTION;
+    if (!none_null(who, {MSL_NAMED(params), MSL_NAMED(cur_kps), MSL_NAMED(cur_un_xy), MSL_NAMED(cur_uright), MSL_NAMED(cur_grid_cell),
+                         MSL_NAMED(cur_desc), MSL_NAMED(n_cur), MSL_NAMED(last_xyz), MSL_NAMED(last_desc), MSL_NAMED(last_flags),
+                         MSL_NAMED(last_octave), MSL_NAMED(last_angle), MSL_NAMED(n_last), MSL_NAMED(Tcw_cur), MSL_NAMED(Tcw_last),
+                         MSL_NAMED(match_out), MSL_NAMED(nmatches)})) return MSL_ERR_INVALID;
+    if (!at_least_one(who, "n_pairs", n_pairs) || !in_range(who, "cap", cap, 1, MAX_CAP) || !frame_ok(who, *params)) return MSL_ERR_INVALID;
+    return MSL_OK;
+}
+
+int launch_projection(msl_match *h, int n_pairs, int cap, const msl_match_params *params, const msl_keypoint *cur_kps, const float *cur_un_xy,
+                      const float *cur_uright, const int32_t *cur_grid_cell, const uint8_t *cur_desc, const int32_t *n_cur, const float *last_xyz,
+                      const uint8_t *last_desc, const uint8_t *last_flags, const int32_t *last_octave, const float *last_angle, const int32_t *n_last,
+                      const float *Tcw_cur, const float *Tcw_last, msl_mem mem, int32_t *match_out, int32_t *nmatches, msl_mem out_mem) {
     int rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
     hipStream_t st = h->stream;
@@ -289,20 +296,26 @@ int run_projection(msl_match *h, int n_pairs, int cap, const msl_match_params *p
     return MSL_OK;
 }
 
-int run_local(msl_match *h, int n_frames, int cap, int mcap, const msl_local_match_params *lp, const msl_keypoint *cur_kps, const float *cur_un_xy,
-              const float *cur_uright, const int32_t *cur_grid_cell, const uint8_t *cur_desc, const int32_t *n_cur, const uint8_t *cur_flags,
-              const float *mp_xyz, const float *mp_normal, const float *mp_dist, const uint8_t *mp_desc, const uint8_t *mp_flags, const int32_t *n_local,
-              const float *Tcw, msl_mem mem, int32_t *match_out, int32_t *n_to_match, int32_t *nmatches, uint8_t *in_view, msl_local_track *track,
-              msl_mem out_mem) {
-    const msl_match_params *params = lp ? &lp->base : nullptr;
-    if (!h || n_frames < 1 || cap < 1 || cap > MAX_CAP || mcap < 1 || mcap > MAX_MCAP || !lp || !cur_kps || !cur_un_xy || !cur_uright || !cur_grid_cell ||
-        !cur_desc || !n_cur || !cur_flags || !mp_xyz || !mp_normal || !mp_dist || !mp_desc || !mp_flags || !n_local || !Tcw || !match_out ||
-        !n_to_match || !nmatches || params->nlevels < 1 || params->nlevels > MSL_MATCH_MAX_LEVELS || !(params->maxX > params->minX) ||
-        !(params->maxY > params->minY) || params->fx == 0 || !(lp->log_scale_factor > 0)) {
-        set_error("msl_match_local_points: invalid argument (cap <= %d, mcap <= %d, nlevels <= %d, log_scale_factor > 0)", MAX_CAP, MAX_MCAP,
-                  MSL_MATCH_MAX_LEVELS);
-        return MSL_ERR_INVALID;
-    }
+int check_local(int n_frames, int cap, int mcap, const msl_local_match_params *params, const msl_keypoint *cur_kps, const float *cur_un_xy,
+                const float *cur_uright, const int32_t *cur_grid_cell, const uint8_t *cur_desc, const int32_t *n_cur, const uint8_t *cur_flags,
+                const float *mp_xyz, const float *mp_normal, const float *mp_dist, const uint8_t *mp_desc, const uint8_t *mp_flags, const int32_t *n_local,
+                const float *Tcw, msl_mem, int32_t *match_out, int32_t *n_to_match, int32_t *nmatches, uint8_t *, msl_local_track *, msl_mem) {
+    const char *who = WHO_LOCAL;
+    if (!none_null(who, {MSL_NAMED(params), MSL_NAMED(cur_kps), MSL_NAMED(cur_un_xy), MSL_NAMED(cur_uright), MSL_NAMED(cur_grid_cell),
+                         MSL_NAMED(cur_desc), MSL_NAMED(n_cur), MSL_NAMED(cur_flags), MSL_NAMED(mp_xyz), MSL_NAMED(mp_normal), MSL_NAMED(mp_dist),
+                         MSL_NAMED(mp_desc), MSL_NAMED(mp_flags), MSL_NAMED(n_local), MSL_NAMED(Tcw), MSL_NAMED(match_out), MSL_NAMED(n_to_match),
+                         MSL_NAMED(nmatches)})) return MSL_ERR_INVALID;   // in_view and track are optional
+    if (!at_least_one(who, "n_frames", n_frames) || !in_range(who, "cap", cap, 1, MAX_CAP) || !in_range(who, "mcap", mcap, 1, MAX_MCAP) ||
+        !frame_ok(who, params->base) || !log_scale_ok(who, params->log_scale_factor)) return MSL_ERR_INVALID;
+    return MSL_OK;
+}
+
+int launch_local(msl_match *h, int n_frames, int cap, int mcap, const msl_local_match_params *lp, const msl_keypoint *cur_kps, const float *cur_un_xy,
+                 const float *cur_uright, const int32_t *cur_grid_cell, const uint8_t *cur_desc, const int32_t *n_cur, const uint8_t *cur_flags,
+                 const float *mp_xyz, const float *mp_normal, const float *mp_dist, const uint8_t *mp_desc, const uint8_t *mp_flags, const int32_t *n_local,
+                 const float *Tcw, msl_mem mem, int32_t *match_out, int32_t *n_to_match, int32_t *nmatches, uint8_t *in_view, msl_local_track *track,
+                 msl_mem out_mem) {
+    const msl_match_params *params = &lp->base;
     int rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
     hipStream_t st = h->stream;
@@ -428,8 +441,8 @@ int msl_match_by_projection(msl_match *h, int n_pairs, int cap, const msl_match_
                             const int32_t *last_octave, const float *last_angle, const int32_t *n_last, const float *Tcw_cur,
                             const float *Tcw_last, msl_mem mem, int32_t *match_out, int32_t *nmatches, msl_mem out_mem) noexcept {
     try {
-    return run_projection(h, n_pairs, cap, params, cur_kps, cur_un_xy, cur_uright, cur_grid_cell, cur_desc, n_cur, last_xyz, last_desc, last_flags, last_octave,
-                          last_angle, n_last, Tcw_cur, Tcw_last, mem, match_out, nmatches, out_mem);
+    return handle_form(WHO_PROJECTION, check_projection, launch_projection, h, n_pairs, cap, params, cur_kps, cur_un_xy, cur_uright, cur_grid_cell, cur_desc,
+                       n_cur, last_xyz, last_desc, last_flags, last_octave, last_angle, n_last, Tcw_cur, Tcw_last, mem, match_out, nmatches, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -445,8 +458,8 @@ int msl_match_by_projection_batch(int device, int n_pairs, int cap, const msl_ma
                                   const int32_t *last_octave, const float *last_angle, const int32_t *n_last, const float *Tcw_cur,
                                   const float *Tcw_last, msl_mem mem, int32_t *match_out, int32_t *nmatches, msl_mem out_mem) noexcept {
     try {
-    return abi_call_default(run_projection, device, mem == MSL_MEM_DEVICE, n_pairs, cap, params, cur_kps, cur_un_xy, cur_uright, cur_grid_cell, cur_desc, n_cur,
-                            last_xyz, last_desc, last_flags, last_octave, last_angle, n_last, Tcw_cur, Tcw_last, mem, match_out, nmatches, out_mem);
+    return batch_form(check_projection, launch_projection, device, mem == MSL_MEM_DEVICE, n_pairs, cap, params, cur_kps, cur_un_xy, cur_uright, cur_grid_cell,
+                      cur_desc, n_cur, last_xyz, last_desc, last_flags, last_octave, last_angle, n_last, Tcw_cur, Tcw_last, mem, match_out, nmatches, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -456,8 +469,8 @@ int msl_match_local_points(msl_match *h, int n_frames, int cap, int mcap, const 
                            const uint8_t *mp_flags, const int32_t *n_local, const float *Tcw, msl_mem mem, int32_t *match_out, int32_t *n_to_match,
                            int32_t *nmatches, uint8_t *in_view, msl_local_track *track, msl_mem out_mem) noexcept {
     try {
-    return run_local(h, n_frames, cap, mcap, params, cur_kps, cur_un_xy, cur_uright, cur_grid_cell, cur_desc, n_cur, cur_flags, mp_xyz, mp_normal, mp_dist,
-                     mp_desc, mp_flags, n_local, Tcw, mem, match_out, n_to_match, nmatches, in_view, track, out_mem);
+    return handle_form(WHO_LOCAL, check_local, launch_local, h, n_frames, cap, mcap, params, cur_kps, cur_un_xy, cur_uright, cur_grid_cell, cur_desc, n_cur,
+                       cur_flags, mp_xyz, mp_normal, mp_dist, mp_desc, mp_flags, n_local, Tcw, mem, match_out, n_to_match, nmatches, in_view, track, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -468,9 +481,9 @@ int msl_match_local_points_batch(int device, int n_frames, int cap, int mcap, co
                                  int32_t *match_out, int32_t *n_to_match, int32_t *nmatches, uint8_t *in_view, msl_local_track *track,
                                  msl_mem out_mem) noexcept {
     try {
-    return abi_call_default(run_local, device, mem == MSL_MEM_DEVICE, n_frames, cap, mcap, params, cur_kps, cur_un_xy, cur_uright, cur_grid_cell, cur_desc,
-                            n_cur, cur_flags, mp_xyz, mp_normal, mp_dist, mp_desc, mp_flags, n_local, Tcw, mem, match_out, n_to_match, nmatches, in_view, track,
-                            out_mem);
+    return batch_form(check_local, launch_local, device, mem == MSL_MEM_DEVICE, n_frames, cap, mcap, params, cur_kps, cur_un_xy, cur_uright, cur_grid_cell,
+                      cur_desc, n_cur, cur_flags, mp_xyz, mp_normal, mp_dist, mp_desc, mp_flags, n_local, Tcw, mem, match_out, n_to_match, nmatches, in_view,
+                      track, out_mem);
     } MSL_ABI_CATCH_INT
 }
 

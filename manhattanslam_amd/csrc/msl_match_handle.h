@@ -1,7 +1,7 @@
 // msl_match_handle.h -- the matcher handle, its staging of caller arrays (Stage), the forwarder of the *_batch entry points, the two forms of
-// an entry that checks before it touches a device (handle_form, batch_form: the LocalMapping entries and the plane chain, msl_plane.hip
-// included) with the list of its NULLs (none_null), the limits that several entry points share (table_limits, line_table_limits,
-// levels_ok; the plane chain's are in msl_plane_tables.h) and the row readback of the debug entry points (last_call_row); shared by msl_match.hip,
+// an entry that checks before it touches a device (handle_form, batch_form: every entry on the handle but msl_match_descriptor_distance)
+// with the list of its NULLs (none_null), the limits that several entry points share (MAX_CAP .. MAX_MCAP, in_range, at_least_one, table_limits,
+// line_table_limits, levels_ok, frame_ok, log_scale_ok; the plane chain's are in msl_plane_tables.h) and the row readback of the debug entry points (last_call_row); shared by msl_match.hip,
 // msl_line_match.hip, msl_pose.hip, msl_plane.hip, msl_bow.hip, msl_reloc.hip, msl_pnp.hip, msl_line3d.hip, msl_triangulate.hip, msl_fuse.hip,
 // msl_mappoint.hip, msl_line_fuse.hip, msl_local_map.hip, msl_cull.hip, msl_plane_cloud.hip, msl_keyframe.hip and msl_keyframe_planes.hip (internal).
 #pragma once
@@ -16,9 +16,23 @@ namespace msl {
 struct PnpKey { double probability; int32_t min_inliers, max_iterations, min_set; float epsilon; int32_t cap, zero; };
 
 // Limits that several entry points share: keypoints of a frame or keyframe (feature indices fit 13 bits, item positions 16), keyframes of
-// a keyframe table, points of a point table; keylines of a keyframe (indices fit 8 bits), lines of a line table.
+// a keyframe table, points of a point table; keylines of a frame or keyframe (indices fit 8 bits), lines of a line table; local map points
+// or local map lines of a frame (positions fit the 16-bit picks of the hand-out).
 constexpr int MAX_CAP = 8192, MAX_TAB = 4096, MAX_PTS = 1 << 20;
 constexpr int MAX_KLCAP = 256, MAX_LINES = 1 << 20;
+constexpr int MAX_MCAP = 32768;
+
+// An int argument inside lo .. hi; false with the error set ("who: name value outside lo .. hi").
+inline bool in_range(const char *who, const char *name, int value, int lo, int hi) {
+    if (value < lo || value > hi) { set_error("%s: %s %d outside %d .. %d", who, name, value, lo, hi); return false; }
+    return true;
+}
+
+// An int argument with no upper limit, such as the frames or pairs of a call; false with the error set ("who: name value below 1").
+inline bool at_least_one(const char *who, const char *name, int n) {
+    if (n < 1) { set_error("%s: %s %d below 1", who, name, n); return false; }
+    return true;
+}
 
 // The limits of a call that takes a keyframe table and a point table; false with the error set.
 inline bool table_limits(const char *who, int n_tab, int cap, int n_pts) {
@@ -39,6 +53,22 @@ inline bool line_table_limits(const char *who, int n_tab, int klcap, int n_lines
 // The length of a call's scale tables; false with the error set.
 inline bool levels_ok(const char *who, int nlevels) {
     if (nlevels < 1 || nlevels > MSL_MATCH_MAX_LEVELS) { set_error("%s: nlevels %d outside 1 .. %d", who, nlevels, MSL_MATCH_MAX_LEVELS); return false; }
+    return true;
+}
+
+// The frame a search projects into: the length of its scale tables, image bounds that are not empty (a NaN bound is refused) and a focal
+// length to divide by; false with the error set.
+inline bool frame_ok(const char *who, const msl_match_params &p) {
+    if (!levels_ok(who, p.nlevels)) return false;
+    if (!(p.maxX > p.minX)) { set_error("%s: image bounds minX %g .. maxX %g are empty", who, (double)p.minX, (double)p.maxX); return false; }
+    if (!(p.maxY > p.minY)) { set_error("%s: image bounds minY %g .. maxY %g are empty", who, (double)p.minY, (double)p.maxY); return false; }
+    if (p.fx == 0) { set_error("%s: fx is 0", who); return false; }
+    return true;
+}
+
+// log_scale_factor = log(scaleFactor) of a search that predicts a scale level (a NaN is refused); false with the error set.
+inline bool log_scale_ok(const char *who, float log_scale_factor) {
+    if (!(log_scale_factor > 0)) { set_error("%s: log_scale_factor %g is not above 0", who, (double)log_scale_factor); return false; }
     return true;
 }
 
@@ -132,7 +162,7 @@ int abi_call_default(Run run, int device, bool sync_legacy, A... a) {
     return rc;
 }
 
-// The two forms of a LocalMapping or plane-chain entry: check_x(args...) makes no HIP call and comes first, so a refusal is made before the handle, or
+// The two forms of an entry: check_x(args...) makes no HIP call and comes first, so a refusal is made before the handle, or
 // the device's shared one, is touched; launch_x(h, args...) starts at bind_device.
 template <class Check, class Launch, class... A>
 int handle_form(const char *who, Check check, Launch launch, msl_match *h, A... a) {

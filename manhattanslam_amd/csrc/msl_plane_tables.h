@@ -1,9 +1,9 @@
 // msl_plane_tables.h -- what the plane chain shares: msl_plane_associate / msl_manhattan_detect (msl_plane.hip), msl_plane_clouds /
 // msl_map_plane_merge (msl_plane_cloud.hip), msl_keyframe_decision (msl_keyframe.hip) and msl_keyframe_planes / msl_manhattan_observe
 // (msl_keyframe_planes.hip).  The capacity limits of the chain, the layout of a Manhattan table entry, the
-// search over such a table, the three-int sort of its keys, the held-row predicate and the refusal of an argument outside its range
-// (internal).  msl_pose_kernel.h takes the plane count of a frame from it; msl_index_check.h stays a plain C++ header without it: its
-// callers pass the layout.
+// search over such a table, the three-int sort of its keys and the held-row predicate (internal; the refusal of an argument outside its
+// range, in_range, is in msl_match_handle.h).  msl_pose_kernel.h takes the plane count of a frame from it; msl_index_check.h stays a
+// plain C++ header without it: its callers pass the layout.
 #pragma once
 
 #include "msl_common.h"
@@ -72,12 +72,5 @@ __device__ __forceinline__ int held_row(int m, const uint8_t *flags, int nMap) {
 // Not shared on purpose: the verticality gate.  msl_manhattan_detect tests !(a > th || a < -th) (reference src/Tracking.cc:679, 699:
 // closed bounds, a NaN passes), msl_manhattan_observe a < th && a > -th (src/LocalMapping.cc:192, 209: open bounds, a NaN fails).  They
 // differ at |a| == th and at NaN, and each is pinned to its reference line.
-
-// ---- host ---------------------------------------------------------------------------------------------------------------------------------
-// An int argument inside lo .. hi; false with the error set ("who: name value outside lo .. hi").
-inline bool in_range(const char *who, const char *name, int value, int lo, int hi) {
-    if (value < lo || value > hi) { set_error("%s: %s %d outside %d .. %d", who, name, value, lo, hi); return false; }
-    return true;
-}
 
 }  // namespace msl

@@ -29,7 +29,7 @@ namespace {
 
 using namespace msl;
 
-constexpr int MAX_KCAP = 32768, MAX_ITS = 1024;
+constexpr int MAX_KCAP = 32768, MAX_ITS = 1024;   // MAX_KCAP: map points a pair may name (msl_reloc.hip has a kcap of its own)
 constexpr double PINV_TOL = 1e-12;           // eigenvalues of A^T A at or below PINV_TOL * the largest are dropped by the pseudo-inverse
 
 struct PnpDev {
@@ -582,29 +582,35 @@ void ransac_entry(const msl_pnp_params &p, int N, int32_t *out) {
 
 size_t carve(size_t &off, size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; }
 
-int run_pnp(msl_match *h, int n_pairs, int cap, int kcap, const msl_pnp_params *prm, const msl_keypoint *kps, const float *un_xy,
-            const int32_t *match, const int32_t *n_kps, const float *xyz, const uint32_t *seed, msl_mem mem, float *Tcw_out, uint8_t *inlier,
-            int32_t *pt_ref_out, int32_t *n_inliers, int32_t *status, msl_mem out_mem) {
-    if (!h || n_pairs < 1 || !prm || !kps || !un_xy || !match || !n_kps || !xyz || !seed || !Tcw_out || !inlier || !pt_ref_out || !n_inliers ||
-        !status) {
-        set_error("msl_pnp_ransac: invalid argument (null pointer or n_pairs < 1)");
+constexpr const char *WHO = "msl_pnp_ransac";
+
+int check_pnp(int n_pairs, int cap, int kcap, const msl_pnp_params *params, const msl_keypoint *kps, const float *un_xy, const int32_t *match,
+              const int32_t *n_kps, const float *xyz, const uint32_t *seed, msl_mem, float *Tcw_out, uint8_t *inlier, int32_t *pt_ref_out,
+              int32_t *n_inliers, int32_t *status, msl_mem) {
+    if (!none_null(WHO, {MSL_NAMED(params), MSL_NAMED(kps), MSL_NAMED(un_xy), MSL_NAMED(match), MSL_NAMED(n_kps), MSL_NAMED(xyz), MSL_NAMED(seed),
+                         MSL_NAMED(Tcw_out), MSL_NAMED(inlier), MSL_NAMED(pt_ref_out), MSL_NAMED(n_inliers), MSL_NAMED(status)})) return MSL_ERR_INVALID;
+    if (!at_least_one(WHO, "n_pairs", n_pairs)) return MSL_ERR_INVALID;
+    if (cap < 1 || cap > MAX_CAP) { set_error("%s: cap %d outside 1 .. %d", WHO, cap, MAX_CAP); return MSL_ERR_INVALID; }
+    if (kcap < 1 || kcap > MAX_KCAP) { set_error("%s: kcap %d outside 1 .. %d", WHO, kcap, MAX_KCAP); return MSL_ERR_INVALID; }
+    if (params->min_set != 4) { set_error("%s: min_set %d (only 4, the reference's one use, is built)", WHO, params->min_set); return MSL_ERR_INVALID; }
+    if (params->nlevels < 1 || params->nlevels > MSL_MATCH_MAX_LEVELS) {
+        set_error("%s: nlevels %d outside 1 .. %d", WHO, params->nlevels, MSL_MATCH_MAX_LEVELS);
         return MSL_ERR_INVALID;
     }
-    if (cap < 1 || cap > MAX_CAP) { set_error("msl_pnp_ransac: cap %d outside 1 .. %d", cap, MAX_CAP); return MSL_ERR_INVALID; }
-    if (kcap < 1 || kcap > MAX_KCAP) { set_error("msl_pnp_ransac: kcap %d outside 1 .. %d", kcap, MAX_KCAP); return MSL_ERR_INVALID; }
-    if (prm->min_set != 4) { set_error("msl_pnp_ransac: min_set %d (only 4, the reference's one use, is built)", prm->min_set); return MSL_ERR_INVALID; }
-    if (prm->nlevels < 1 || prm->nlevels > MSL_MATCH_MAX_LEVELS) {
-        set_error("msl_pnp_ransac: nlevels %d outside 1 .. %d", prm->nlevels, MSL_MATCH_MAX_LEVELS);
+    if (params->max_iterations < 1 || params->max_iterations > MAX_ITS) {
+        set_error("%s: max_iterations %d outside 1 .. %d", WHO, params->max_iterations, MAX_ITS);
         return MSL_ERR_INVALID;
     }
-    if (prm->max_iterations < 1 || prm->max_iterations > MAX_ITS) {
-        set_error("msl_pnp_ransac: max_iterations %d outside 1 .. %d", prm->max_iterations, MAX_ITS);
+    if (params->n_iterations < 0 || params->n_iterations > MAX_ITS) {
+        set_error("%s: n_iterations %d outside 0 .. %d", WHO, params->n_iterations, MAX_ITS);
         return MSL_ERR_INVALID;
     }
-    if (prm->n_iterations < 0 || prm->n_iterations > MAX_ITS) {
-        set_error("msl_pnp_ransac: n_iterations %d outside 0 .. %d", prm->n_iterations, MAX_ITS);
-        return MSL_ERR_INVALID;
-    }
+    return MSL_OK;
+}
+
+int launch_pnp(msl_match *h, int n_pairs, int cap, int kcap, const msl_pnp_params *prm, const msl_keypoint *kps, const float *un_xy,
+               const int32_t *match, const int32_t *n_kps, const float *xyz, const uint32_t *seed, msl_mem mem, float *Tcw_out, uint8_t *inlier,
+               int32_t *pt_ref_out, int32_t *n_inliers, int32_t *status, msl_mem out_mem) {
     int rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
     hipStream_t st = h->stream;
@@ -664,7 +670,8 @@ int msl_pnp_ransac(msl_match *h, int n_pairs, int cap, int kcap, const msl_pnp_p
                    const int32_t *match, const int32_t *n_kps, const float *xyz, const uint32_t *seed, msl_mem mem, float *Tcw_out, uint8_t *inlier,
                    int32_t *pt_ref_out, int32_t *n_inliers, int32_t *status, msl_mem out_mem) noexcept {
     try {
-    return run_pnp(h, n_pairs, cap, kcap, params, kps, un_xy, match, n_kps, xyz, seed, mem, Tcw_out, inlier, pt_ref_out, n_inliers, status, out_mem);
+    return handle_form(WHO, check_pnp, launch_pnp, h, n_pairs, cap, kcap, params, kps, un_xy, match, n_kps, xyz, seed, mem, Tcw_out, inlier, pt_ref_out,
+                       n_inliers, status, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -672,8 +679,8 @@ int msl_pnp_ransac_batch(int device, int n_pairs, int cap, int kcap, const msl_p
                          const int32_t *match, const int32_t *n_kps, const float *xyz, const uint32_t *seed, msl_mem mem, float *Tcw_out,
                          uint8_t *inlier, int32_t *pt_ref_out, int32_t *n_inliers, int32_t *status, msl_mem out_mem) noexcept {
     try {
-    return abi_call_default(run_pnp, device, mem == MSL_MEM_DEVICE || out_mem == MSL_MEM_DEVICE, n_pairs, cap, kcap, params, kps, un_xy, match, n_kps, xyz,
-                            seed, mem, Tcw_out, inlier, pt_ref_out, n_inliers, status, out_mem);
+    return batch_form(check_pnp, launch_pnp, device, mem == MSL_MEM_DEVICE || out_mem == MSL_MEM_DEVICE, n_pairs, cap, kcap, params, kps, un_xy, match, n_kps,
+                      xyz, seed, mem, Tcw_out, inlier, pt_ref_out, n_inliers, status, out_mem);
     } MSL_ABI_CATCH_INT
 }
 

@@ -5,20 +5,29 @@
 
 namespace {
 
-int run_pose(msl_match *h, int n_frames, int cap, int xcap, int lcap, int pcap, const msl_pose_params *prm, const msl_keypoint *kps,
-             const float *un_xy, const float *uright, const int32_t *pt_ref, const int32_t *n_kps, const float *xyz, const double *line_fn,
-             const double *line_xyz, const uint8_t *line_has, const int32_t *n_lines, const float *plane_coef, const float *plane_w,
-             const uint8_t *plane_has, const int32_t *n_planes, const float *Tcw, const float *Rcw, bool trans, msl_mem mem, uint8_t *outlier,
-             uint8_t *line_outlier, uint8_t *plane_outlier, float *Tcw_out, int32_t *n_good, msl_mem out_mem) {
-    const char *name = trans ? "msl_pose_optimize_translation" : "msl_pose_optimize";
-    if (!h || n_frames < 1 || cap < 1 || cap > MAX_CAP || xcap < 1 || xcap > MAX_XCAP || lcap < 1 || lcap > MAX_LCAP || pcap < 1 ||
-        pcap > MAX_PCAP || !prm || prm->nlevels < 1 || prm->nlevels > MSL_MATCH_MAX_LEVELS || !kps || !un_xy || !uright || !pt_ref || !n_kps ||
-        !xyz || !line_fn || !line_xyz || !line_has || !n_lines || !plane_coef || !plane_w || !plane_has || !n_planes || !Tcw || !outlier ||
-        !line_outlier || !plane_outlier || !Tcw_out || !n_good) {
-        set_error("%s: invalid argument (1 <= cap <= %d, xcap <= %d, lcap <= %d, pcap <= %d, nlevels <= %d)", name, MAX_CAP, MAX_XCAP,
-                  MAX_LCAP, MAX_PCAP, MSL_MATCH_MAX_LEVELS);
-        return MSL_ERR_INVALID;
-    }
+const char *pose_who(bool trans) { return trans ? "msl_pose_optimize_translation" : "msl_pose_optimize"; }
+
+// Both optimisers: Rcw (the translation-only one's Manhattan rotation) is optional.
+int check_pose(int n_frames, int cap, int xcap, int lcap, int pcap, const msl_pose_params *params, const msl_keypoint *kps, const float *un_xy,
+               const float *uright, const int32_t *pt_ref, const int32_t *n_kps, const float *xyz, const double *line_fn, const double *line_xyz,
+               const uint8_t *line_has, const int32_t *n_lines, const float *plane_coef, const float *plane_w, const uint8_t *plane_has,
+               const int32_t *n_planes, const float *Tcw, const float *, bool trans, msl_mem, uint8_t *outlier, uint8_t *line_outlier,
+               uint8_t *plane_outlier, float *Tcw_out, int32_t *n_good, msl_mem) {
+    const char *who = pose_who(trans);
+    if (!none_null(who, {MSL_NAMED(params), MSL_NAMED(kps), MSL_NAMED(un_xy), MSL_NAMED(uright), MSL_NAMED(pt_ref), MSL_NAMED(n_kps), MSL_NAMED(xyz),
+                         MSL_NAMED(line_fn), MSL_NAMED(line_xyz), MSL_NAMED(line_has), MSL_NAMED(n_lines), MSL_NAMED(plane_coef), MSL_NAMED(plane_w),
+                         MSL_NAMED(plane_has), MSL_NAMED(n_planes), MSL_NAMED(Tcw), MSL_NAMED(outlier), MSL_NAMED(line_outlier),
+                         MSL_NAMED(plane_outlier), MSL_NAMED(Tcw_out), MSL_NAMED(n_good)})) return MSL_ERR_INVALID;
+    if (!at_least_one(who, "n_frames", n_frames) || !in_range(who, "cap", cap, 1, MAX_CAP) || !in_range(who, "xcap", xcap, 1, MAX_XCAP) ||
+        !in_range(who, "lcap", lcap, 1, MAX_KLCAP) || !in_range(who, "pcap", pcap, 1, MAX_PCAP) || !levels_ok(who, params->nlevels)) return MSL_ERR_INVALID;
+    return MSL_OK;
+}
+
+int launch_pose(msl_match *h, int n_frames, int cap, int xcap, int lcap, int pcap, const msl_pose_params *prm, const msl_keypoint *kps,
+                const float *un_xy, const float *uright, const int32_t *pt_ref, const int32_t *n_kps, const float *xyz, const double *line_fn,
+                const double *line_xyz, const uint8_t *line_has, const int32_t *n_lines, const float *plane_coef, const float *plane_w,
+                const uint8_t *plane_has, const int32_t *n_planes, const float *Tcw, const float *Rcw, bool trans, msl_mem mem, uint8_t *outlier,
+                uint8_t *line_outlier, uint8_t *plane_outlier, float *Tcw_out, int32_t *n_good, msl_mem out_mem) {
     int rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
     hipStream_t st = h->stream;
@@ -58,8 +67,9 @@ int msl_pose_optimize(msl_match *h, int n_frames, int cap, int xcap, int lcap, i
                       const uint8_t *plane_has, const int32_t *n_planes, const float *Tcw, msl_mem mem, uint8_t *outlier, uint8_t *line_outlier,
                       uint8_t *plane_outlier, float *Tcw_out, int32_t *n_good, msl_mem out_mem) noexcept {
     try {
-    return run_pose(h, n_frames, cap, xcap, lcap, pcap, params, kps, un_xy, uright, pt_ref, n_kps, xyz, line_fn, line_xyz, line_has, n_lines, plane_coef,
-                    plane_w, plane_has, n_planes, Tcw, NO_RCW, false, mem, outlier, line_outlier, plane_outlier, Tcw_out, n_good, out_mem);
+    return handle_form(pose_who(false), check_pose, launch_pose, h, n_frames, cap, xcap, lcap, pcap, params, kps, un_xy, uright, pt_ref, n_kps, xyz, line_fn,
+                       line_xyz, line_has, n_lines, plane_coef, plane_w, plane_has, n_planes, Tcw, NO_RCW, false, mem, outlier, line_outlier, plane_outlier,
+                       Tcw_out, n_good, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -71,9 +81,9 @@ int msl_pose_optimize_batch(int device, int n_frames, int cap, int xcap, int lca
                             msl_mem mem, uint8_t *outlier, uint8_t *line_outlier, uint8_t *plane_outlier, float *Tcw_out, int32_t *n_good,
                             msl_mem out_mem) noexcept {
     try {
-    return abi_call_default(run_pose, device, mem == MSL_MEM_DEVICE || out_mem == MSL_MEM_DEVICE, n_frames, cap, xcap, lcap, pcap, params, kps, un_xy, uright,
-                            pt_ref, n_kps, xyz, line_fn, line_xyz, line_has, n_lines, plane_coef, plane_w, plane_has, n_planes, Tcw, NO_RCW, false, mem,
-                            outlier, line_outlier, plane_outlier, Tcw_out, n_good, out_mem);
+    return batch_form(check_pose, launch_pose, device, mem == MSL_MEM_DEVICE || out_mem == MSL_MEM_DEVICE, n_frames, cap, xcap, lcap, pcap, params, kps, un_xy,
+                      uright, pt_ref, n_kps, xyz, line_fn, line_xyz, line_has, n_lines, plane_coef, plane_w, plane_has, n_planes, Tcw, NO_RCW, false, mem,
+                      outlier, line_outlier, plane_outlier, Tcw_out, n_good, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -84,8 +94,9 @@ int msl_pose_optimize_translation(msl_match *h, int n_frames, int cap, int xcap,
                                   const float *Tcw, const float *Rcw, msl_mem mem, uint8_t *outlier, uint8_t *line_outlier,
                                   uint8_t *plane_outlier, float *Tcw_out, int32_t *n_good, msl_mem out_mem) noexcept {
     try {
-    return run_pose(h, n_frames, cap, xcap, lcap, pcap, params, kps, un_xy, uright, pt_ref, n_kps, xyz, line_fn, line_xyz, line_has, n_lines, plane_coef,
-                    plane_w, plane_has, n_planes, Tcw, Rcw, true, mem, outlier, line_outlier, plane_outlier, Tcw_out, n_good, out_mem);
+    return handle_form(pose_who(true), check_pose, launch_pose, h, n_frames, cap, xcap, lcap, pcap, params, kps, un_xy, uright, pt_ref, n_kps, xyz, line_fn,
+                       line_xyz, line_has, n_lines, plane_coef, plane_w, plane_has, n_planes, Tcw, Rcw, true, mem, outlier, line_outlier, plane_outlier,
+                       Tcw_out, n_good, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -97,9 +108,9 @@ int msl_pose_optimize_translation_batch(int device, int n_frames, int cap, int x
                                         uint8_t *outlier, uint8_t *line_outlier, uint8_t *plane_outlier, float *Tcw_out, int32_t *n_good,
                                         msl_mem out_mem) noexcept {
     try {
-    return abi_call_default(run_pose, device, mem == MSL_MEM_DEVICE || out_mem == MSL_MEM_DEVICE, n_frames, cap, xcap, lcap, pcap, params, kps, un_xy, uright,
-                            pt_ref, n_kps, xyz, line_fn, line_xyz, line_has, n_lines, plane_coef, plane_w, plane_has, n_planes, Tcw, Rcw, true, mem, outlier,
-                            line_outlier, plane_outlier, Tcw_out, n_good, out_mem);
+    return batch_form(check_pose, launch_pose, device, mem == MSL_MEM_DEVICE || out_mem == MSL_MEM_DEVICE, n_frames, cap, xcap, lcap, pcap, params, kps, un_xy,
+                      uright, pt_ref, n_kps, xyz, line_fn, line_xyz, line_has, n_lines, plane_coef, plane_w, plane_has, n_planes, Tcw, Rcw, true, mem, outlier,
+                      line_outlier, plane_outlier, Tcw_out, n_good, out_mem);
     } MSL_ABI_CATCH_INT
 }
 

@@ -65,7 +65,7 @@ using namespace msl;
 namespace {
 
 
-constexpr int MAX_XCAP = 32768, MAX_LCAP = 256;
+constexpr int MAX_XCAP = 32768;               // map points of a frame; its keylines: MAX_KLCAP (msl_match_handle.h)
 constexpr int NT = 256;                       // four waves per frame
 constexpr int NRED = 28;                      // 21 H (lower triangle) + 6 b + robust chi2
 constexpr int MONO = 0, STEREO = 1, LINE = 2, PLANE = 3, PAR = 4, VER = 5;

@@ -49,7 +49,7 @@ struct msl_kfdb {
 
 namespace {
 
-constexpr int MAX_KCAP = 8192;
+constexpr int MAX_KCAP = 8192;                  // map points of the keyframe of a pair (msl_pnp.hip has a kcap of its own)
 constexpr int KF_NT = 1024;
 
 struct KfDev {
@@ -143,19 +143,27 @@ __global__ __launch_bounds__(KF_NT) void k_kf_assign(KfDev K) {
     if (threadIdx.x == 0) P.nmatches[pair] = s_nm;
 }
 
-int run_keyframe(msl_match *h, int n_pairs, int cap, int kcap, const msl_keyframe_match_params *kp, const msl_keypoint *cur_kps, const float *cur_un_xy,
-                 const int32_t *cur_grid_cell, const uint8_t *cur_desc, const int32_t *n_cur, const uint8_t *cur_held, const float *kf_xyz,
-                 const float *kf_dist, const uint8_t *kf_desc, const float *kf_angle, const uint8_t *kf_flags, const int32_t *n_kf, const float *Tcw,
-                 msl_mem mem, int32_t *match_out, int32_t *nmatches, msl_mem out_mem) {
-    const msl_match_params *params = kp ? &kp->base : nullptr;
-    if (!h || n_pairs < 1 || cap < 1 || cap > MAX_CAP || kcap < 1 || kcap > MAX_KCAP || !kp || !cur_kps || !cur_un_xy || !cur_grid_cell || !cur_desc ||
-        !n_cur || !cur_held || !kf_xyz || !kf_dist || !kf_desc || !kf_angle || !kf_flags || !n_kf || !Tcw || !match_out || !nmatches ||
-        params->nlevels < 1 || params->nlevels > MSL_MATCH_MAX_LEVELS || !(params->maxX > params->minX) || !(params->maxY > params->minY) ||
-        params->fx == 0 || !(kp->log_scale_factor > 0) || kp->orb_dist < 0 || kp->orb_dist > 255) {
-        set_error("msl_match_keyframe_points: invalid argument (cap <= %d, kcap <= %d, nlevels <= %d, log_scale_factor > 0, 0 <= orb_dist <= 255)", MAX_CAP,
-                  MAX_KCAP, MSL_MATCH_MAX_LEVELS);
+constexpr const char *WHO_KEYFRAME = "msl_match_keyframe_points", *WHO_RELOC = "msl_reloc_candidates";
+
+int check_keyframe(int n_pairs, int cap, int kcap, const msl_keyframe_match_params *params, const msl_keypoint *cur_kps, const float *cur_un_xy,
+                   const int32_t *cur_grid_cell, const uint8_t *cur_desc, const int32_t *n_cur, const uint8_t *cur_held, const float *kf_xyz,
+                   const float *kf_dist, const uint8_t *kf_desc, const float *kf_angle, const uint8_t *kf_flags, const int32_t *n_kf, const float *Tcw,
+                   msl_mem, int32_t *match_out, int32_t *nmatches, msl_mem) {
+    const char *who = WHO_KEYFRAME;
+    if (!none_null(who, {MSL_NAMED(params), MSL_NAMED(cur_kps), MSL_NAMED(cur_un_xy), MSL_NAMED(cur_grid_cell), MSL_NAMED(cur_desc), MSL_NAMED(n_cur),
+                         MSL_NAMED(cur_held), MSL_NAMED(kf_xyz), MSL_NAMED(kf_dist), MSL_NAMED(kf_desc), MSL_NAMED(kf_angle), MSL_NAMED(kf_flags),
+                         MSL_NAMED(n_kf), MSL_NAMED(Tcw), MSL_NAMED(match_out), MSL_NAMED(nmatches)})) return MSL_ERR_INVALID;
+    if (!at_least_one(who, "n_pairs", n_pairs) || !in_range(who, "cap", cap, 1, MAX_CAP) || !in_range(who, "kcap", kcap, 1, MAX_KCAP) ||
+        !frame_ok(who, params->base) || !log_scale_ok(who, params->log_scale_factor) || !in_range(who, "orb_dist", params->orb_dist, 0, 255))
         return MSL_ERR_INVALID;
-    }
+    return MSL_OK;
+}
+
+int launch_keyframe(msl_match *h, int n_pairs, int cap, int kcap, const msl_keyframe_match_params *kp, const msl_keypoint *cur_kps,
+                    const float *cur_un_xy, const int32_t *cur_grid_cell, const uint8_t *cur_desc, const int32_t *n_cur, const uint8_t *cur_held,
+                    const float *kf_xyz, const float *kf_dist, const uint8_t *kf_desc, const float *kf_angle, const uint8_t *kf_flags, const int32_t *n_kf,
+                    const float *Tcw, msl_mem mem, int32_t *match_out, int32_t *nmatches, msl_mem out_mem) {
+    const msl_match_params *params = &kp->base;
     int rc = bind_device(h->device);
     if (rc != MSL_OK) return rc;
     hipStream_t st = h->stream;
@@ -352,13 +360,20 @@ __global__ __launch_bounds__(SEL_NT) void k_reloc_select(RelocDev R) {
 
 const char *const SCORING_NAMES[6] = {"L1_NORM", "L2_NORM", "CHI_SQUARE", "KL", "BHATTACHARYYA", "DOT_PRODUCT"};
 
-int run_reloc(msl_match *h, msl_kfdb *db, const msl_vocab *voc, int n_frames, int cap, int ccap, const int32_t *bow_word, const double *bow_value,
-              const int32_t *n_words, const int32_t *covis, msl_mem mem, int32_t *cand_out, int32_t *n_cand, int32_t *words_out, float *score_out,
-              msl_mem out_mem) {
-    if (!h || !db || !voc || n_frames < 1 || cap < 1 || ccap < 1 || !bow_word || !bow_value || !n_words || !cand_out || !n_cand) {
-        set_error("msl_reloc_candidates: invalid argument");
-        return MSL_ERR_INVALID;
-    }
+// No upper limit on cap or ccap: they size the caller's arrays only.  covis is required once the database holds slots, which
+// launch_reloc reads under the database's mutex; words_out and score_out are optional.
+int check_reloc(msl_kfdb *db, const msl_vocab *voc, int n_frames, int cap, int ccap, const int32_t *bow_word, const double *bow_value,
+                const int32_t *n_words, const int32_t *, msl_mem, int32_t *cand_out, int32_t *n_cand, int32_t *, float *, msl_mem) {
+    const char *who = WHO_RELOC;
+    if (!none_null(who, {MSL_NAMED(db), MSL_NAMED(voc), MSL_NAMED(bow_word), MSL_NAMED(bow_value), MSL_NAMED(n_words), MSL_NAMED(cand_out),
+                         MSL_NAMED(n_cand)})) return MSL_ERR_INVALID;
+    if (!at_least_one(who, "n_frames", n_frames) || !at_least_one(who, "cap", cap) || !at_least_one(who, "ccap", ccap)) return MSL_ERR_INVALID;
+    return MSL_OK;
+}
+
+int launch_reloc(msl_match *h, msl_kfdb *db, const msl_vocab *voc, int n_frames, int cap, int ccap, const int32_t *bow_word, const double *bow_value,
+                 const int32_t *n_words, const int32_t *covis, msl_mem mem, int32_t *cand_out, int32_t *n_cand, int32_t *words_out, float *score_out,
+                 msl_mem out_mem) {
     int32_t info[7];
     if (msl_vocab_info(voc, info) != MSL_OK) return MSL_ERR_INVALID;
     if (info[2] != 0) {
@@ -510,8 +525,8 @@ int msl_match_keyframe_points(msl_match *h, int n_pairs, int cap, int kcap, cons
                               const float *kf_xyz, const float *kf_dist, const uint8_t *kf_desc, const float *kf_angle, const uint8_t *kf_flags,
                               const int32_t *n_kf, const float *Tcw, msl_mem mem, int32_t *match_out, int32_t *nmatches, msl_mem out_mem) noexcept {
     try {
-    return run_keyframe(h, n_pairs, cap, kcap, params, cur_kps, cur_un_xy, cur_grid_cell, cur_desc, n_cur, cur_held, kf_xyz, kf_dist, kf_desc, kf_angle,
-                        kf_flags, n_kf, Tcw, mem, match_out, nmatches, out_mem);
+    return handle_form(WHO_KEYFRAME, check_keyframe, launch_keyframe, h, n_pairs, cap, kcap, params, cur_kps, cur_un_xy, cur_grid_cell, cur_desc, n_cur,
+                       cur_held, kf_xyz, kf_dist, kf_desc, kf_angle, kf_flags, n_kf, Tcw, mem, match_out, nmatches, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -521,8 +536,8 @@ int msl_match_keyframe_points_batch(int device, int n_pairs, int cap, int kcap, 
                                     const uint8_t *kf_flags, const int32_t *n_kf, const float *Tcw, msl_mem mem, int32_t *match_out, int32_t *nmatches,
                                     msl_mem out_mem) noexcept {
     try {
-    return abi_call_default(run_keyframe, device, mem == MSL_MEM_DEVICE, n_pairs, cap, kcap, params, cur_kps, cur_un_xy, cur_grid_cell, cur_desc, n_cur,
-                            cur_held, kf_xyz, kf_dist, kf_desc, kf_angle, kf_flags, n_kf, Tcw, mem, match_out, nmatches, out_mem);
+    return batch_form(check_keyframe, launch_keyframe, device, mem == MSL_MEM_DEVICE, n_pairs, cap, kcap, params, cur_kps, cur_un_xy, cur_grid_cell, cur_desc,
+                      n_cur, cur_held, kf_xyz, kf_dist, kf_desc, kf_angle, kf_flags, n_kf, Tcw, mem, match_out, nmatches, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -575,7 +590,8 @@ int msl_reloc_candidates(msl_match *h, msl_kfdb *db, const msl_vocab *voc, int n
                          const double *bow_value, const int32_t *n_words, const int32_t *covis, msl_mem mem, int32_t *cand_out, int32_t *n_cand,
                          int32_t *words_out, float *score_out, msl_mem out_mem) noexcept {
     try {
-    return run_reloc(h, db, voc, n_frames, cap, ccap, bow_word, bow_value, n_words, covis, mem, cand_out, n_cand, words_out, score_out, out_mem);
+    return handle_form(WHO_RELOC, check_reloc, launch_reloc, h, db, voc, n_frames, cap, ccap, bow_word, bow_value, n_words, covis, mem, cand_out, n_cand,
+                       words_out, score_out, out_mem);
     } MSL_ABI_CATCH_INT
 }
 
@@ -583,8 +599,8 @@ int msl_reloc_candidates_batch(int device, msl_kfdb *db, const msl_vocab *voc, i
                                const double *bow_value, const int32_t *n_words, const int32_t *covis, msl_mem mem, int32_t *cand_out,
                                int32_t *n_cand, int32_t *words_out, float *score_out, msl_mem out_mem) noexcept {
     try {
-    return abi_call_default(run_reloc, device, mem == MSL_MEM_DEVICE, db, voc, n_frames, cap, ccap, bow_word, bow_value, n_words, covis, mem, cand_out,
-                            n_cand, words_out, score_out, out_mem);
+    return batch_form(check_reloc, launch_reloc, device, mem == MSL_MEM_DEVICE, db, voc, n_frames, cap, ccap, bow_word, bow_value, n_words, covis, mem,
+                      cand_out, n_cand, words_out, score_out, out_mem);
     } MSL_ABI_CATCH_INT
 }
 

@@ -208,17 +208,21 @@ def test_limits_are_refused_before_any_launch():
     desc = np.zeros((1, 8193, 32), np.uint8); n = np.array([5], np.int32)
     outs = [np.zeros((1, 8193), np.int32) for _ in range(2)]
     assert lib.msl_bow_transform(h.h, voc.h, 1, 8193, 0, ptr(desc), ptr(n), 0, ptr(outs[0]), ptr(outs[1]), None, None, None, 0) == MSL_ERR_INVALID
+    assert lib.msl_last_error().decode() == "msl_bow_transform: cap 8193 outside 1 .. 8192"
     assert lib.msl_bow_transform(h.h, voc.h, 1, 8192, 0, ptr(desc), ptr(n), 0, ptr(outs[0]), ptr(outs[1]), None, None, None, 0) == 0
     p = S.bow_pair(1, 10, 10)
     for cap, rc in ((8192, 0), (8193, MSL_ERR_INVALID)):
         _, arrays = bow.pack_match_by_bow([p], cap)
         mo, nm = np.zeros((1, cap), np.int32), np.zeros(1, np.int32)
         assert lib.msl_match_by_bow(h.h, 1, cap, ptr(bow.bow_match_params()), *[ptr(a) for a in arrays], 0, ptr(mo), ptr(nm), 0) == rc
+        assert rc == 0 or lib.msl_last_error().decode() == "msl_match_by_bow: cap 8193 outside 1 .. 8192"
     lp = S.line_pair(2, 10, 10)
-    for lcap, klcap, rc in ((256, 256, 0), (257, 256, MSL_ERR_INVALID), (256, 257, MSL_ERR_INVALID)):
+    for lcap, klcap, rc, msg in ((256, 256, 0, None), (257, 256, MSL_ERR_INVALID, "lcap 257 outside 1 .. 256"),
+                                 (256, 257, MSL_ERR_INVALID, "klcap 257 outside 1 .. 256")):
         _, _, arrays = bow.pack_lines_by_descriptor([lp], lcap, klcap)
         mo, nm = np.zeros((1, lcap), np.int32), np.zeros(1, np.int32)
         assert lib.msl_match_lines_by_descriptor(h.h, 1, lcap, klcap, *[ptr(a) for a in arrays], 0, ptr(mo), ptr(nm), None, None, 0) == rc
+        assert rc == 0 or lib.msl_last_error().decode() == "msl_match_lines_by_descriptor: " + msg
     k, L, sc, wt, parent, leaf, d, w = args
     for kk, LL, ok in ((20, 10, True), (21, 10, False), (20, 11, False)):
         if ok:

@@ -9,7 +9,9 @@ import re
 import numpy as np
 import pytest
 
+from tests import abi_refusals
 from tests import cull_scenes as cs
+from tests.abi_refusals import put
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = {"msl_cull_keyframes": 28, "msl_cull_recent": 13}
@@ -83,25 +85,10 @@ def scene():
 
 
 def refused(entry, scene, **over):
-    """msl_last_error() of `entry`_batch on the scene's host arrays with the arguments in `over` replaced (an array is copied first, a
-    callable edits the copy); the outputs must keep their bytes."""
-    from manhattanslam_amd import _header, _lib, cull
+    from manhattanslam_amd import cull
     a, sh = scene
-    a = dict(a)
-    for k, v in over.items():
-        if callable(v):
-            a[k] = a[k].copy()
-            v(a[k])
     out = dict(cull.keyframes_outputs(sh["n_items"], sh["ccap"], cs.host_filled), verdict=cs.host_filled((sh["n"],), np.uint8))
-    args, arrays = [], a                                                   # the arrays before `mem` are inputs, those after it outputs
-    for t, n in _header.declarations(_header.text("msl.h"))[entry + "_batch"][1]:
-        arrays = out if n == "mem" else arrays
-        v = over[n] if n in over and not callable(over[n]) else 0 if n in ("device", "mem", "out_mem") else sh[n] if n in sh else arrays[n]
-        args.append(v if isinstance(v, int) else _lib.ptr(v))
-    rc = getattr(_lib.lib, entry + "_batch")(*args)
-    assert rc == -1, (entry, over, rc)
-    assert all((v.view(np.uint8) == cs.FILL).all() for v in out.values())
-    return _lib.lib.msl_last_error().decode()
+    return abi_refusals.refused(entry, sh, a, out, **over)
 
 
 LIMITS = {"msl_cull_keyframes": [("n_tab", 0, "n_tab 0 outside 1 .. 4096"), ("n_tab", 4097, "n_tab 4097 outside 1 .. 4096"),
@@ -132,12 +119,6 @@ def test_every_null_is_refused_with_the_field_named(scene, entry):
     assert len(pointers) == {"msl_cull_keyframes": 18, "msl_cull_recent": 6}[entry]
     for n in pointers:
         assert refused(entry, scene, **{n: None}) == f"{entry}: {n} is NULL"
-
-
-def put(index, value):
-    def edit(x):
-        x[index] = value
-    return edit
 
 
 def test_index_defects_of_a_host_memory_call_are_refused(scene):

@@ -8,8 +8,10 @@ import re
 import numpy as np
 import pytest
 
+from tests import abi_refusals
 from tests import keyframe_model as km
 from tests import keyframe_scenes as ks
+from tests.abi_refusals import put
 
 NAMES = {"msl_points_3d": 27, "msl_keyframe_decision": 39}
 
@@ -104,31 +106,10 @@ def scene():
 
 
 def refused(entry, scene, **over):
-    """msl_last_error() of `entry`_batch on the scene's host arrays with the arguments in `over` replaced (an array is copied first, a
-    callable edits the copy); the outputs, and the in/out arrays, must keep their bytes."""
-    from manhattanslam_amd import _header, _lib, keyframe
+    from manhattanslam_amd import keyframe
     arrays, sh = scene
-    a = dict(arrays[entry])
-    for k, v in over.items():
-        if callable(v):
-            a[k] = a[k].copy()
-            v(a[k])
     out = keyframe.points_outputs(2, 6, ks.host_filled) if entry == "msl_points_3d" else keyframe.decision_outputs(2, 6, 4, ks.host_filled)
-    inout = {k: a[k].copy() for k in keyframe.DECISION_INOUT_KEYS if k in a}
-    args = []
-    for t, n in _header.declarations(_header.text("msl.h"))[entry + "_batch"][1]:
-        v = over[n] if n in over and not callable(over[n]) else 0 if n in ("device", "mem", "out_mem") else sh[n] if n in sh else out[n] if n in out else a[n]
-        args.append(v if isinstance(v, int) else _lib.ptr(v))
-    rc = getattr(_lib.lib, entry + "_batch")(*args)
-    assert rc == -1, (entry, over, rc)
-    assert all((v.view(np.uint8) == ks.FILL).all() for v in out.values()) and all(a[k].tobytes() == v.tobytes() for k, v in inout.items())
-    return _lib.lib.msl_last_error().decode()
-
-
-def put(index, value):
-    def edit(x):
-        x[index] = value
-    return edit
+    return abi_refusals.refused(entry, sh, arrays[entry], out, inout=[k for k in keyframe.DECISION_INOUT_KEYS if k in arrays[entry]], **over)
 
 
 LIMITS = {"msl_points_3d": [("n_frames", 0, "n_frames 0 below 1"), ("cap", 0, "cap 0 outside 1 .. 8192"), ("cap", 8193, "cap 8193 outside 1 .. 8192"),

@@ -9,8 +9,10 @@ import re
 import numpy as np
 import pytest
 
+from tests import abi_refusals
 from tests import kfplanes_model as kp
 from tests import kfplanes_scenes as ks
+from tests.abi_refusals import put
 
 NAMES = {"msl_keyframe_planes": 30, "msl_manhattan_observe": 26}
 
@@ -106,32 +108,11 @@ def scene():
 
 
 def refused(entry, scene, **over):
-    """msl_last_error() of `entry`_batch on the scene's host arrays with the arguments in `over` replaced (an array is copied first, a
-    callable edits the copy); the outputs, and the in/out arrays, must keep their bytes."""
-    from manhattanslam_amd import _header, _lib, kfplanes
+    from manhattanslam_amd import kfplanes
     arrays, sh = scene
-    a = dict(arrays)
-    for k, v in over.items():
-        if callable(v):
-            a[k] = a[k].copy()
-            v(a[k])
     planes = entry == "msl_keyframe_planes"
     out = kfplanes.planes_outputs(2, ks.PCAP, ks.host_filled) if planes else kfplanes.observe_outputs(2, ks.PCAP, ks.host_filled)
-    inout = {k: a[k].copy() for k in (kfplanes.PLANES_INOUT_KEYS if planes else kfplanes.OBSERVE_INOUT_KEYS)}
-    args = []
-    for t, n in _header.declarations(_header.text("msl.h"))[entry + "_batch"][1]:
-        v = over[n] if n in over and not callable(over[n]) else 0 if n in ("device", "mem", "out_mem") else sh[n] if n in sh else out[n] if n in out else a[n]
-        args.append(v if isinstance(v, int) else _lib.ptr(v))
-    rc = getattr(_lib.lib, entry + "_batch")(*args)
-    assert rc == -1, (entry, over, rc)
-    assert all((v.view(np.uint8) == ks.FILL).all() for v in out.values()) and all(a[k].tobytes() == v.tobytes() for k, v in inout.items())
-    return _lib.lib.msl_last_error().decode()
-
-
-def put(index, value):
-    def edit(x):
-        x[index] = value
-    return edit
+    return abi_refusals.refused(entry, sh, arrays, out, inout=kfplanes.PLANES_INOUT_KEYS if planes else kfplanes.OBSERVE_INOUT_KEYS, **over)
 
 
 LIMITS = {"msl_keyframe_planes": [("n_frames", 0, "n_frames 0 outside 1 .. 65535"), ("n_frames", 65536, "n_frames 65536 outside 1 .. 65535"),

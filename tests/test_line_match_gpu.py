@@ -149,20 +149,24 @@ def test_limits_are_refused_without_a_launch(what):
     lcap = 257 if what == "lcap" else 8
     llcap = 257 if what == "llcap" else 8
     mlcap = 32769 if what == "mlcap" else 8
+    defect = {"lcap": "lcap 257 outside 1 .. 256", "llcap": "llcap 257 outside 1 .. 256", "mlcap": "mlcap 32769 outside 1 .. 32768",
+              "nlevels": "nlevels 17 outside 1 .. 16"}[what]
     m = Matcher()
     mo = np.full(lcap, -7, np.int32); nm = np.full(1, -7, np.int32); ntm = np.full(1, -7, np.int32)
     lx = np.full((lcap, 6), 7.0); lh = np.full(lcap, 7, np.uint8); inv = np.full(mlcap, 7, np.uint8); trk = np.zeros(mlcap, LINE_TRACK_DTYPE)
     if what != "mlcap":
         _, _, arrays = match.pack_lines_last([c], [l], t[None], tl[None], lcap=lcap, llcap=llcap)
         args = (1, lcap, llcap, ptr(p), *[ptr(a) for a in arrays], MSL_MEM_HOST, ptr(mo), ptr(nm), ptr(lx), ptr(lh), MSL_MEM_HOST)
-        assert lib.msl_match_lines_by_projection(m.h, *args) == -1 and b"llcap <= 256" in lib.msl_last_error()
-        assert lib.msl_match_lines_by_projection_batch(0, *args) == -1
+        msg = "msl_match_lines_by_projection: " + defect
+        assert lib.msl_match_lines_by_projection(m.h, *args) == -1 and lib.msl_last_error().decode() == msg
+        assert lib.msl_match_lines_by_projection_batch(0, *args) == -1 and lib.msl_last_error().decode() == msg
     if what != "llcap":
         _, _, arrays = match.pack_local_lines([cl], [ll], tt[None], lcap=lcap, mlcap=mlcap)
         args = (1, lcap, mlcap, ptr(pl), *[ptr(a) for a in arrays], MSL_MEM_HOST, ptr(mo), ptr(ntm), ptr(nm), ptr(inv), ptr(trk), ptr(lx), ptr(lh),
                 MSL_MEM_HOST)
-        assert lib.msl_match_local_lines(m.h, *args) == -1 and b"mlcap <= 32768" in lib.msl_last_error()
-        assert lib.msl_match_local_lines_batch(0, *args) == -1
+        msg = "msl_match_local_lines: " + defect
+        assert lib.msl_match_local_lines(m.h, *args) == -1 and lib.msl_last_error().decode() == msg
+        assert lib.msl_match_local_lines_batch(0, *args) == -1 and lib.msl_last_error().decode() == msg
     assert np.all(mo == -7) and nm[0] == -7 and ntm[0] == -7 and np.all(lx == 7.0) and np.all(lh == 7) and np.all(inv == 7)
     # the handle is still good afterwards
     p = lsc.params(15.0)

@@ -1,5 +1,7 @@
 """GPU parity: batched local-map matching (msl_match_local_points[_batch], Tracking::SearchLocalPoints) vs the sequential CPU model in
 tests/local_match_model.py.  Every output must be identical: match_out, nmatches, n_to_match, in_view, and the track records bit for bit."""
+import re
+
 import numpy as np
 import pytest
 
@@ -126,15 +128,16 @@ def test_limits_are_refused_without_a_launch():
     p = ls.params(3.0)
     c, l, t = ls.random_frame(50, p, n_cur=10, n_local=10)
     m = Matcher()
-    for cap, mcap in ((8193, 16), (16, 32769)):
+    for cap, mcap, msg in ((8193, 16, "cap 8193 outside 1 .. 8192"), (16, 32769, "mcap 32769 outside 1 .. 32768")):
+        msg = "msl_match_local_points: " + msg
         _, _, arrays = match.pack_local_points([c], [l], t[None], cap=cap, mcap=mcap)
         mo = np.full(cap, -7, np.int32); ntm = np.full(1, -7, np.int32); nm = np.full(1, -7, np.int32)
         inv = np.full(mcap, 7, np.uint8); trk = np.zeros(mcap, LOCAL_TRACK_DTYPE)
         args = (1, cap, mcap, ptr(p), *[ptr(a) for a in arrays], MSL_MEM_HOST, ptr(mo), ptr(ntm), ptr(nm), ptr(inv), ptr(trk), MSL_MEM_HOST)
-        assert lib.msl_match_local_points(m.h, *args) == -1 and b"mcap <= 32768" in lib.msl_last_error()     # MSL_ERR_INVALID
-        assert lib.msl_match_local_points_batch(0, *args) == -1
+        assert lib.msl_match_local_points(m.h, *args) == -1 and lib.msl_last_error().decode() == msg     # MSL_ERR_INVALID
+        assert lib.msl_match_local_points_batch(0, *args) == -1 and lib.msl_last_error().decode() == msg
         assert np.all(mo == -7) and ntm[0] == -7 and nm[0] == -7 and np.all(inv == 7)
-        with pytest.raises(MslError, match="invalid argument"):
+        with pytest.raises(MslError, match=re.escape(msg) + "$"):
             match.search_local_points_batch(p, [c], [l], t[None], cap=cap, mcap=mcap)
     # the handle is still good afterwards
     got = m.search_local_points_batch(p, [c], [l], t[None])

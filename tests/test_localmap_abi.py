@@ -9,7 +9,9 @@ import re
 import numpy as np
 import pytest
 
+from tests import abi_refusals
 from tests import localmap_scenes as ls
+from tests.abi_refusals import put
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = {"msl_local_keyframes": 26, "msl_local_points": 28, "msl_local_lines": 29}
@@ -82,27 +84,12 @@ def scene():
 
 
 def refused(entry, scene, **over):
-    """msl_last_error() of `entry`_batch on the scene's host arrays with the arguments in `over` replaced (an array is copied first, a
-    callable edits the copy); the outputs must keep their bytes."""
-    from manhattanslam_amd import _header, _lib, localmap
+    from manhattanslam_amd import localmap
     a, sh = scene
-    a = dict(a)
-    for k, v in over.items():
-        if callable(v):
-            a[k] = a[k].copy()
-            v(a[k])
     F = sh["n_frames"]
     out = dict(localmap.keyframes_outputs(F, sh["cap"], sh["n_tab"], ls.host_filled), **localmap.points_outputs(F, sh["cap"], sh["mcap"], ls.host_filled),
                **localmap.lines_outputs(F, sh["lcap"], sh["mlcap"], ls.host_filled))
-    args, arrays = [], a                                                   # the arrays before `mem` are inputs, those after it outputs
-    for t, n in _header.declarations(_header.text("msl.h"))[entry + "_batch"][1]:
-        arrays = out if n == "mem" else arrays
-        v = over[n] if n in over and not callable(over[n]) else 0 if n in ("device", "mem", "out_mem") else sh[n] if n in sh else arrays[n]
-        args.append(v if isinstance(v, int) else _lib.ptr(v))
-    rc = getattr(_lib.lib, entry + "_batch")(*args)
-    assert rc == -1, (entry, over, rc)
-    assert all((v.view(np.uint8) == ls.FILL).all() for v in out.values())
-    return _lib.lib.msl_last_error().decode()
+    return abi_refusals.refused(entry, sh, a, out, **over)
 
 
 LIMITS = [("n_frames", 0, "n_frames 0 below 1"), ("n_frames", -3, "n_frames -3 below 1"), ("n_tab", 0, "n_tab 0 outside 1 .. 4096"),
@@ -134,12 +121,6 @@ def test_every_null_is_refused_with_the_field_named(scene, entry):
         assert refused(entry, scene, **{n: None}) == f"{entry}: {n} is NULL"
     if entry == "msl_local_keyframes":
         assert refused(entry, scene, n_prev=None) == f"{entry}: n_prev is NULL with prev_kf given"
-
-
-def put(index, value):
-    def edit(x):
-        x[index] = value
-    return edit
 
 
 def test_index_defects_of_a_host_memory_call_are_refused(scene):

@@ -6,7 +6,8 @@ candidate.  No launch (no GPU needed)."""
 import numpy as np
 import pytest
 
-from tests.localmap_scenes import FILL, host_filled
+from tests import abi_refusals
+from tests.abi_refusals import both, declared as _declared, host_filled, put
 
 TCW = np.concatenate([np.eye(3), np.zeros((3, 1))], 1).astype(np.float32)
 SF = np.ones(1, np.float32)
@@ -119,38 +120,10 @@ ENTRIES = ("msl_covisibility", "msl_fuse_candidates", "msl_fuse_map_lines", "msl
 
 
 def refused(scenes, entry, shape=None, **over):
-    """msl_last_error() of `entry`_batch on the scene's host arrays with the arguments in `over` replaced (None: a NULL; an array: in its
-    place; a callable edits a copy).  shape: the int arguments the outputs are sized for, when the replaced arrays describe a larger call.
-    The call must be refused and the outputs must keep their bytes."""
-    from manhattanslam_amd import _header, _lib
+    """abi_refusals.refused on the scene of `entry`.  shape: the int arguments the outputs are sized for, when the replaced arrays describe
+    a larger call."""
     ints, ins, outputs = scenes[entry]
-    ins = dict(ins)
-    for k, v in over.items():
-        if callable(v):
-            ins[k] = ins[k].copy()
-            v(ins[k])
-    out = outputs(dict(ints, **(shape or {})))
-    args, arrays = [], ins                                                 # the arrays before `mem` are inputs, those after it outputs
-    for t, n in _header.declarations(_header.text("msl.h"))[entry + "_batch"][1]:
-        arrays = out if n == "mem" else arrays
-        v = over[n] if n in over and not callable(over[n]) else 0 if n in ("device", "mem", "out_mem") else ints[n] if n in ints else arrays[n]
-        args.append(v if isinstance(v, int) else _lib.ptr(v))
-    rc = getattr(_lib.lib, entry + "_batch")(*args)
-    assert rc == -1, (entry, over, rc)
-    assert all((v.view(np.uint8) == FILL).all() for v in out.values() if v is not None)
-    return _lib.lib.msl_last_error().decode()
-
-
-def put(index, value):
-    def edit(x):
-        x[index] = value
-    return edit
-
-
-def both(field, hi, top=None):
-    """A limit 1 .. hi (top: how the message writes hi) from both sides."""
-    top = top or str(hi)
-    return [(field, 0, f"{field} 0 outside 1 .. {top}"), (field, hi + 1, f"{field} {hi + 1} outside 1 .. {top}")]
+    return abi_refusals.refused(entry, ints, ins, outputs(dict(ints, **(shape or {}))), **over)
 
 
 POINT_TABLE_LIMITS = both("n_tab", 4096) + both("cap", 8192) + both("n_pts", 1 << 20)
@@ -175,13 +148,6 @@ PARAM_LIMITS = {
     "msl_fuse_map_points": both("nlevels", 16) + [("th_low", -1, "th_low -1 outside 0 .. 255"), ("th_low", 256, "th_low 256 outside 0 .. 255")],
     "msl_fuse_map_lines": both("nlevels", 16) + [("th_low", -1, "th_low -1 outside 0 .. 256"), ("th_low", 257, "th_low 257 outside 0 .. 256")],
 }
-
-
-def _declared(entry):
-    """The names of the int arguments and of the pointer arguments behind the first, as msl.h declares them."""
-    from manhattanslam_amd import _header
-    decl = _header.declarations(_header.text("msl.h"))[entry][1][1:]
-    return [n for t, n in decl if t == "int"], [n for t, n in decl if t.endswith("*")]
 
 
 @pytest.mark.parametrize("entry", ENTRIES)

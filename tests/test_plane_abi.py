@@ -10,7 +10,9 @@ import re
 import numpy as np
 import pytest
 
+from tests import abi_refusals
 from tests import kfplanes_scenes as ks
+from tests.abi_refusals import put
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PA, MD = "msl_plane_associate", "msl_manhattan_detect"
@@ -84,35 +86,12 @@ def outputs(entry):
 
 
 def run(entry, scene, **over):
-    """`entry`_batch on the scene's host arrays with the arguments in `over` replaced (an array is copied first, a callable edits the copy).
-    Returns (return code, msl_last_error()); after a refusal the outputs, and the in/out arrays, must hold the bytes they had."""
-    from manhattanslam_amd import _header, _lib
-    a = {k: v.copy() for k, v in scene.items()}
-    for k, v in over.items():
-        if callable(v):
-            v(a[k])
-    out = outputs(entry)
-    before = {k: a[k].tobytes() for k in INOUT[entry]}
-    args = []
-    for t, n in _header.declarations(_header.text("msl.h"))[entry + "_batch"][1]:
-        v = over[n] if n in over and not callable(over[n]) else 0 if n in ("device", "mem", "out_mem") else SH[n] if n in SH else out[n] if n in out else a[n]
-        args.append(v if isinstance(v, int) else _lib.ptr(v))
-    rc = getattr(_lib.lib, entry + "_batch")(*args)
-    if rc == -1:
-        assert all((v.view(np.uint8) == ks.FILL).all() for v in out.values()) and all(a[k].tobytes() == v for k, v in before.items()), (entry, over)
-    return rc, _lib.lib.msl_last_error().decode()
+    """abi_refusals.call on the scene: (return code, msl_last_error())."""
+    return abi_refusals.call(entry, SH, scene, outputs(entry), inout=INOUT[entry], **over)
 
 
 def refused(entry, scene, **over):
-    rc, msg = run(entry, scene, **over)
-    assert rc == -1, (entry, over, rc, msg)              # MSL_ERR_INVALID, on a machine without a device too: the check comes first
-    return msg
-
-
-def put(index, value):
-    def edit(x):
-        x[index] = value
-    return edit
+    return abi_refusals.refused(entry, SH, scene, outputs(entry), inout=INOUT[entry], **over)
 
 
 LIMITS = {PA: dict(n_frames=INT_MAX, pcap=64, mcap=4096, ptcap=1 << 22), MD: dict(n_frames=INT_MAX, pcap=64, mcap=4096, fcap=65536, qcap=65536, kcap=4096)}

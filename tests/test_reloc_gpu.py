@@ -1,5 +1,7 @@
 """GPU parity: the batched keyframe search of Tracking::Relocalization (msl_match_keyframe_points[_batch]) vs the sequential CPU model
 in tests/reloc_model.py.  Every output must be identical: match_out and nmatches."""
+import re
+
 import numpy as np
 import pytest
 
@@ -146,15 +148,18 @@ def test_limits_are_refused_without_a_launch():
         for key, v in kw.items():
             q[key] = v
         return q
-    cases = [(8193, 16, good), (16, 8193, good), (16, 16, variant(orb_dist=256)), (16, 16, variant(orb_dist=-1)), (16, 16, variant(nlevels=17))]
-    for cap, kcap, p in cases:
+    cases = [(8193, 16, good, "cap 8193 outside 1 .. 8192"), (16, 8193, good, "kcap 8193 outside 1 .. 8192"),
+             (16, 16, variant(orb_dist=256), "orb_dist 256 outside 0 .. 255"), (16, 16, variant(orb_dist=-1), "orb_dist -1 outside 0 .. 255"),
+             (16, 16, variant(nlevels=17), "nlevels 17 outside 1 .. 16")]
+    for cap, kcap, p, msg in cases:
+        msg = "msl_match_keyframe_points: " + msg
         _, _, arrays = reloc.pack_keyframe_points([c], [k], t[None], cap=cap, kcap=kcap)
         mo = np.full(cap, -7, np.int32); nm = np.full(1, -7, np.int32)
         args = (1, cap, kcap, ptr(p), *[ptr(a) for a in arrays], MSL_MEM_HOST, ptr(mo), ptr(nm), MSL_MEM_HOST)
-        assert lib.msl_match_keyframe_points(m.h, *args) == -1 and b"orb_dist <= 255" in lib.msl_last_error()     # MSL_ERR_INVALID
-        assert lib.msl_match_keyframe_points_batch(0, *args) == -1
+        assert lib.msl_match_keyframe_points(m.h, *args) == -1 and lib.msl_last_error().decode() == msg     # MSL_ERR_INVALID
+        assert lib.msl_match_keyframe_points_batch(0, *args) == -1 and lib.msl_last_error().decode() == msg
         assert np.all(mo == -7) and nm[0] == -7
-        with pytest.raises(MslError, match="invalid argument"):
+        with pytest.raises(MslError, match=re.escape(msg) + "$"):
             reloc.search_keyframe_points(p, [c], [k], t[None], cap=cap, kcap=kcap)
     # the limits themselves are accepted, and the handle is still good afterwards
     edge = variant(orb_dist=255)
