@@ -1634,6 +1634,98 @@ MSL_API int msl_cull_recent_batch(int device, int n, int cur_kf_id, int th_obs, 
                                   const int32_t *first_kf_id, const int32_t *nobs, const uint8_t *flags, msl_mem mem, uint8_t *verdict,
                                   msl_mem out_mem) MSL_NOEXCEPT;
 
+/* ---- Editing the observation table: AddObservation, EraseObservation, SetBadFlag, Replace and the point loop of KeyFrame::SetBadFlag ----
+ * msl_observations_apply executes a log of edits on the tables the other LocalMapping entries read -- the CSR observation table obs_off /
+ * obs_kf / obs_idx of msl_refresh_map_points, the slots held_id of the keyframe table and the per-point arrays -- and writes the new CSR
+ * table.  It is the producer of the observation table, so that table too can stay in device memory from one keyframe to the next: the
+ * results of msl_triangulate_new_points, the statements of the fusion replay and the verdicts of the cullings reach it as a log of a few
+ * thousand records.  It is MapPoint::AddObservation, EraseObservation, SetBadFlag and Replace
+ * (src/MapPoint.cc:83-187), the MapLine forms of the same four (src/MapLine.cpp:75-172, with uright NULL and the line tables),
+ * KeyFrame::AddMapPoint, EraseMapPointMatch and ReplaceMapPointMatch (src/KeyFrame.cc:185-197) and the point and line loops of
+ * KeyFrame::SetBadFlag (:362-368).  tests/observations_model.py is the sequential model, and its literal twin.
+ * The table: within a point's range the order is ascending obs_kf and a keyframe appears at most once (std::map's order with pointer order
+ * pinned to table order); an insertion goes to its sorted place.  A new point or line is a row with an empty range on entry: the caller
+ * sizes n_pts to include it.  The weight of observation (k, i) is 2 if uright[k][i] >= 0, else 1; with uright NULL every weight is 1.
+ * In (mem): n_kps[n_tab]; uright[n_tab][cap] or NULL; obs_off[n_pts + 1], obs_kf, obs_idx; ops[n_ops].
+ * In and out, in place (mem): held_id[n_tab][cap]; pt_flags[n_pts] (bit 0: !isBad(), the other bits keep their value); pt_nobs; pt_ref;
+ * pt_found and pt_visible (mnFound / mnVisible: both given or both NULL); pt_replaced (mpReplaced, -1 = none; may be NULL).
+ * Out (out_mem): obs_off_out[n_pts + 1] (from 0), obs_kf_out[ocap], obs_idx_out[ocap]: the table on exit, in arrays of its own (not the
+ * entry's); op_status[n_ops]; touched[tcap]; counts[4].
+ * The log is executed in order.  Op o is ops[o] = { op, a, b, c }:
+ *   MSL_OBS_ADD (a = id, b = keyframe, c = keypoint)   pMP->AddObservation(pKF, c); pKF->AddMapPoint(pMP, c).  If b is not among the point's
+ *                observations, (b, c) is inserted and its weight added to pt_nobs; in either case held_id[b][c] = a.  No bad test.
+ *   MSL_OBS_ERASE (a = id, b = keyframe)   EraseObservation.  If b is not observed, nothing; else the weight is subtracted and the entry
+ *                removed; if pt_ref[a] == b, pt_ref[a] becomes the first remaining keyframe (pin: -1 if none remains, where the reference
+ *                dereferences end()); if pt_nobs[a] <= 2, MSL_OBS_SET_BAD runs on the point.
+ *   MSL_OBS_SET_BAD (a = id)   SetBadFlag: bit 0 cleared, held_id[k][i] = -1 for every observation (k, i), the range emptied; pt_nobs stays.
+ *   MSL_OBS_REPLACE (a = id, b = survivor)   Replace without its ComputeDistinctiveDescriptors (msl_refresh_map_points on the survivor).
+ *                a == b: nothing.  Else a turns bad, pt_replaced[a] = b, its observations are taken and cleared; for each taken (k, i): if b
+ *                does not observe k, held_id[k][i] = b and (k, i) joins b with its weight, else held_id[k][i] = -1; then pt_found[b] +=
+ *                pt_found[a], pt_visible[b] += pt_visible[a].
+ *   MSL_OBS_KF_ERASE (b = keyframe)   the point (or line) loop of KeyFrame::SetBadFlag: for i < n_kps[b] in order, MSL_OBS_ERASE(held_id[b][i],
+ *                b) where the slot holds a row of the table.  Every MSL_OBS_KF_ERASE precedes every other op of the log.  The slots are
+ *                those on entry: a slot an earlier cascade set to -1 belongs to a point whose range is already empty.  Pin: this is the
+ *                live loop unless an observation (k, i) of a point that turns bad lies on a slot that holds another point which observes k
+ *                too (tables only an inconsistent producer leaves, see msl_cull_keyframes' pin); a caller with such tables replays those
+ *                keyframes itself.  SetBadFlag's two early returns, the connections and the spanning tree stay with the caller, which
+ *                sends the op for MSL_CULL_CULLED alone.
+ * held_id on exit is what the execution in order leaves: where several ops write one slot, the last in log order wins.
+ * op_status[o]: MSL_OBS_CHANGED -- an observation list, a counter or a flag differs because of this op; MSL_OBS_TURNED_BAD -- a point went
+ * from live to bad inside it (MSL_OBS_KF_ERASE: any of its points).
+ * touched: ascending and distinct, the ids whose range or any per-point array differs between entry and exit; entries beyond the count are
+ * -1.  msl_refresh_map_points takes an id of -1 as a bad point (its device-memory contract), so a device-memory caller passes ids = touched
+ * and n_items = tcap on without reading the count.
+ * counts: [0] the new n_obs_total; [1] the number of touched points, the full count even beyond tcap (as n_conn); [2] the number of
+ * points that were too long; [3] the number of points live on entry and bad on exit.
+ * Too long: no point may hold more than MSL_OBS_MAX observations while an op touches it.  A point an op names with more than that on
+ * entry, or that an insertion (MSL_OBS_ADD, or the entries an MSL_OBS_REPLACE moves) would take beyond it, is counted in counts[2] once; the
+ * op, and every later op that names a counted point, does nothing.  If counts[2] != 0 nothing else is written and the caller applies the
+ * log itself: every in-place array and obs_*_out keep their bytes, counts is { n_obs_total, 0, counts[2], 0 }, op_status and touched are
+ * unspecified.  Points no op names may have any length: they are copied.  (The work is done in the handle's scratch; the kernels that
+ * write the caller's arrays read the count from device memory.)
+ * n_obs_total of the next call: the consumers (msl_refresh_map_points, msl_covisibility, msl_local_keyframes, msl_cull_keyframes and this
+ * entry) use it only to clamp obs_off into the arrays, so a device-memory caller that has not read counts[0] back passes ocap, the
+ * size of the arrays: the table's own offsets end at counts[0] <= ocap.
+ * Limits: n_tab <= 4096, cap <= 8192, n_pts <= 1048576, n_obs_total >= 0, 1 <= n_ops <= 65536 of which at most 256 MSL_OBS_KF_ERASE,
+ * ocap >= n_obs_total + the number of MSL_OBS_ADD ops (an MSL_OBS_REPLACE moves entries, it never adds), 1 <= tcap <= n_pts; anything
+ * else, a NULL array other than uright / pt_found / pt_visible / pt_replaced, or one of pt_found / pt_visible without the other, is refused
+ * with MSL_ERR_INVALID before any launch, with msl_last_error() naming the field, and nothing is written (the _batch form refuses before
+ * it touches a device).  A host-memory call (mem) also checks its index arrays and refuses a violation: the CSR table as
+ * msl_cull_keyframes; a range that is not strictly ascending in obs_kf; an unknown op code; an op whose id, keyframe or keypoint is outside
+ * n_pts, n_tab or n_kps[b]; an MSL_OBS_KF_ERASE behind another op, or more than 256 of them; an ocap below n_obs_total + the MSL_OBS_ADD ops.
+ * With device memory these are the caller's contract: an op with an unknown code or a field outside its table, and an MSL_OBS_KF_ERASE
+ * beyond the 256th, gets status 0 and does nothing; a held_id outside the table is skipped by MSL_OBS_KF_ERASE; an unsorted range comes out
+ * sorted if an op names its point; offsets that do not ascend give ranges that overlap, and a point whose list no longer fits the scratch
+ * sized for disjoint ranges is counted as too long; nothing reads or writes outside its array.
+ * The result does not depend on scheduling: the log is walked in order by one wave, and every other kernel writes each byte once.
+ * Memory and synchronisation as msl_bow_transform. */
+typedef struct msl_obs_op {
+    int32_t op;                                      /* MSL_OBS_* */
+    int32_t a, b, c;                                 /* see the list above; a field an op does not read is ignored */
+} msl_obs_op;
+#define MSL_OBS_ADD          1
+#define MSL_OBS_ERASE        2
+#define MSL_OBS_SET_BAD      3
+#define MSL_OBS_REPLACE      4
+#define MSL_OBS_KF_ERASE     5
+#define MSL_OBS_MAX_OPS      65536   /* the most ops of one log */
+#define MSL_OBS_MAX_KF_ERASE 256     /* of which MSL_OBS_KF_ERASE */
+#define MSL_OBS_CHANGED      1   /* op_status: a list, a counter or a flag changed because of this op */
+#define MSL_OBS_TURNED_BAD   2   /* a point went from live to bad inside this op */
+MSL_API int msl_observations_apply(msl_match *h, int n_tab, int cap, int n_pts, int n_obs_total, int n_ops, int ocap, int tcap,
+                                   const int32_t *n_kps, const float *uright, const int32_t *obs_off, const int32_t *obs_kf,
+                                   const int32_t *obs_idx, const msl_obs_op *ops, int32_t *held_id, uint8_t *pt_flags, int32_t *pt_nobs,
+                                   int32_t *pt_ref, int32_t *pt_found, int32_t *pt_visible, int32_t *pt_replaced, msl_mem mem,
+                                   int32_t *obs_off_out, int32_t *obs_kf_out, int32_t *obs_idx_out, uint8_t *op_status, int32_t *touched,
+                                   int32_t *counts, msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device matcher handle, always synchronous). */
+MSL_API int msl_observations_apply_batch(int device, int n_tab, int cap, int n_pts, int n_obs_total, int n_ops, int ocap, int tcap,
+                                         const int32_t *n_kps, const float *uright, const int32_t *obs_off, const int32_t *obs_kf,
+                                         const int32_t *obs_idx, const msl_obs_op *ops, int32_t *held_id, uint8_t *pt_flags,
+                                         int32_t *pt_nobs, int32_t *pt_ref, int32_t *pt_found, int32_t *pt_visible, int32_t *pt_replaced,
+                                         msl_mem mem, int32_t *obs_off_out, int32_t *obs_kf_out, int32_t *obs_idx_out, uint8_t *op_status,
+                                         int32_t *touched, int32_t *counts, msl_mem out_mem) MSL_NOEXCEPT;
+
 /* ---- The hand-over from tracking to local mapping: the keyframe decision and the new stereo map points ----
  * msl_points_3d: the point half of the three call sites whose line half is msl_lines_3d -- StereoInitialization (src/Tracking.cc:560-572),
  * UpdateLastFrame (:1062-1104) and CreateNewKeyFrame (:1524-1569) -- with Frame::UnprojectStereo (src/Frame.cc:515-526) and the two MapPoint

@@ -37,5 +37,6 @@ from . import linefuse  # noqa: F401
 from ._lib import LINE_FUSE_PARAMS_DTYPE  # noqa: F401
 from . import localmap  # noqa: F401
 from . import cull  # noqa: F401
+from . import observations  # noqa: F401
 from . import keyframe  # noqa: F401
 from . import kfplanes  # noqa: F401

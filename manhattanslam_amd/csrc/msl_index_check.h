@@ -6,10 +6,11 @@
 // elements of the cullings (kf_rows_ok, origin_ok, recent_ok: msl_cull.hip), and the offsets, vertex indices and target rows of the plane clouds
 // (offsets_ok, vertex_indices_ok, merge_into_ok: msl_plane_cloud.hip), and the counts, held planes, keyframe rows and Manhattan tables of a
 // keyframe with planes (counts_ok, plane_match_ok, kf_slots_ok: msl_keyframe_planes.hip; tables_sorted_ok: msl_keyframe_planes.hip and
-// msl_manhattan_detect in msl_plane.hip, which pass the entry layout of msl_plane_tables.h).  Pure host functions on plain arrays: no HIP call, no
+// msl_manhattan_detect in msl_plane.hip, which pass the entry layout of msl_plane_tables.h), and the order of the observation ranges and the log
+// of msl_observations_apply (obs_ascending_ok, obs_ops_ok: msl_observations.hip).  Pure host functions on plain arrays: no HIP call, no
 // allocation through the library, no global state, so a plain C++ program can call them (tests/mappoint_csr_host.cpp,
 // tests/mapping_lists_host.cpp, tests/localmap_check_host.cpp, tests/cull_check_host.cpp, tests/plane_cloud_check_host.cpp,
-// tests/kfplanes_check_host.cpp).  Each returns true, or false with a message that names the field in err; the caller puts its own name in
+// tests/kfplanes_check_host.cpp, tests/observations_check_host.cpp).  Each returns true, or false with a message that names the field in err; the caller puts its own name in
 // front ("%s: %s").
 #pragma once
 
@@ -193,6 +194,61 @@ inline bool recent_ok(int n, bool int_form, const int32_t *found, const int32_t 
             snprintf(err, err_len, "visible[%d] is 0 in the integer ratio form (a division by zero in the reference)", i);
             return false;
         }
+    }
+    return true;
+}
+
+// ==== the observation edits ==================================================================================================================
+// Every range of the observation table (already checked by csr_ok) strictly ascending in obs_kf: std::map's order, a keyframe at most once.
+inline bool obs_ascending_ok(int n_pts, const int32_t *obs_off, const int32_t *obs_kf, char *err, size_t err_len) {
+    for (int p = 0; p < n_pts; p++)
+        for (int o = obs_off[p] + 1; o < obs_off[p + 1]; o++)
+            if (obs_kf[o] <= obs_kf[o - 1]) {
+                snprintf(err, err_len, "obs_kf[%d] is keyframe %d after %d in the range of point %d: not strictly ascending", o, (int)obs_kf[o],
+                         (int)obs_kf[o - 1], p);
+                return false;
+            }
+    return true;
+}
+
+// The op codes of msl_observations_apply (msl.h's MSL_OBS_*; msl_observations.hip asserts that they are the same) and the log's limits
+constexpr int OBS_ADD = 1, OBS_ERASE = 2, OBS_SET_BAD = 3, OBS_REPLACE = 4, OBS_KF_ERASE = 5, OBS_MAX_KF_ERASE = 256;
+
+// The log of msl_observations_apply, ops[o] = { op, a, b, c }: a known code; the id, keyframe and keypoint an op reads inside n_pts, n_tab and
+// n_kps[b] (clamped to cap); every OBS_KF_ERASE in front of every other op and at most OBS_MAX_KF_ERASE of them; ocap at least n_obs_total +
+// the OBS_ADD ops.
+inline bool obs_ops_ok(int n_tab, int cap, int n_pts, int n_obs_total, int n_ops, int ocap, const int32_t *n_kps, const int32_t *ops, char *err,
+                       size_t err_len) {
+    int n_add = 0, n_kf_erase = 0;
+    bool other = false;
+    for (int o = 0; o < n_ops; o++) {
+        const int op = ops[4 * (size_t)o], a = ops[4 * (size_t)o + 1], b = ops[4 * (size_t)o + 2], c = ops[4 * (size_t)o + 3];
+        if (op < OBS_ADD || op > OBS_KF_ERASE) { snprintf(err, err_len, "ops[%d].op is %d, not an MSL_OBS_* code", o, op); return false; }
+        if (op != OBS_KF_ERASE && (a < 0 || a >= n_pts)) { snprintf(err, err_len, "ops[%d].a is id %d of %d", o, a, n_pts); return false; }
+        if (op == OBS_REPLACE) {
+            if (b < 0 || b >= n_pts) { snprintf(err, err_len, "ops[%d].b is id %d of %d", o, b, n_pts); return false; }
+        } else if (op != OBS_SET_BAD && (b < 0 || b >= n_tab)) {
+            snprintf(err, err_len, "ops[%d].b is keyframe %d of %d", o, b, n_tab);
+            return false;
+        }
+        if (op == OBS_ADD) {
+            const int n = n_kps[b] < cap ? n_kps[b] : cap;
+            if (c < 0 || c >= n) { snprintf(err, err_len, "ops[%d].c is keypoint %d of %d in keyframe %d", o, c, n, b); return false; }
+            n_add++;
+        }
+        if (op == OBS_KF_ERASE) {
+            if (other) { snprintf(err, err_len, "ops[%d] is an MSL_OBS_KF_ERASE behind another op", o); return false; }
+            if (++n_kf_erase > OBS_MAX_KF_ERASE) {
+                snprintf(err, err_len, "ops[%d] is MSL_OBS_KF_ERASE number %d of at most %d", o, n_kf_erase, OBS_MAX_KF_ERASE);
+                return false;
+            }
+        } else {
+            other = true;
+        }
+    }
+    if ((long long)ocap < (long long)n_obs_total + n_add) {
+        snprintf(err, err_len, "ocap is %d, below n_obs_total + the %d MSL_OBS_ADD ops = %lld", ocap, n_add, (long long)n_obs_total + n_add);
+        return false;
     }
     return true;
 }

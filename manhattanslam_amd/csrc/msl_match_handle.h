@@ -3,7 +3,7 @@
 // with the list of its NULLs (none_null), the limits that several entry points share (MAX_CAP .. MAX_MCAP, in_range, at_least_one, table_limits,
 // line_table_limits, levels_ok, frame_ok, log_scale_ok; the plane chain's are in msl_plane_tables.h) and the row readback of the debug entry points (last_call_row); shared by msl_match.hip,
 // msl_line_match.hip, msl_pose.hip, msl_plane.hip, msl_bow.hip, msl_reloc.hip, msl_pnp.hip, msl_line3d.hip, msl_triangulate.hip, msl_fuse.hip,
-// msl_mappoint.hip, msl_line_fuse.hip, msl_local_map.hip, msl_cull.hip, msl_plane_cloud.hip, msl_keyframe.hip and msl_keyframe_planes.hip (internal).
+// msl_mappoint.hip, msl_line_fuse.hip, msl_local_map.hip, msl_cull.hip, msl_plane_cloud.hip, msl_keyframe.hip, msl_keyframe_planes.hip and msl_observations.hip (internal).
 #pragma once
 
 #include "msl_common.h"
@@ -129,6 +129,9 @@ struct msl_match {
     msl::DevBuf pcSlab, pcWork;
     // msl_manhattan_observe: per frame the merged tail of each Manhattan table and the lower bounds of its new keys, built before the copy back
     msl::DevBuf kfpScratch;
+    // msl_observations_apply: the work slot of every point (-1: none) and the block sums of the rebuild; per work slot the point's arrays
+    // and its list of at most MSL_OBS_MAX observations; the slot writes in execution order
+    msl::DevBuf obsIndex, obsSlots, obsWrites;
     // Device copies of host-memory arguments, one pool for every entry point (msl::Stage deals the slots out in declaration order).
     // Sharing is sound because every call that touches the pool returns with the stream drained (Stage::finish synchronises whenever
     // either side is host memory, and only then is a slot used), so no slot is live when the next call starts.
@@ -207,6 +210,8 @@ class Stage {
     template <class T> const T *in(const T *user, size_t count) { return (const T *)take(const_cast<T *>(user), sizeof(T) * count, mem_, true, false); }
     template <class T> T *inout(T *user, size_t count) { return (T *)take(user, sizeof(T) * count, outMem_, true, true); }
     template <class T> T *out(T *user, size_t count) { return (T *)take(user, sizeof(T) * count, outMem_, false, true); }
+    // An in/out array that the ABI lists before `mem` (msl_observations_apply's tables, edited in place)
+    template <class T> T *inout_in_mem(T *user, size_t count) { return (T *)take(user, sizeof(T) * count, mem_, true, true); }
     // An optional output the kernels always write to the handle's scratch `dev`: the pointer they write as well (device memory: the
     // caller's array, or null), while a host-memory array is copied back from the scratch by finish().
     template <class T> T *out_of_scratch(T *user, const T *dev, size_t count) {
