@@ -1268,8 +1268,8 @@ MSL_API int msl_fuse_map_points_batch(int device, int n_tab, int cap, int n_pts,
  *   n_conn[f]                      the full count: entries beyond ccap are dropped, so the caller compares n_conn with ccap; slots beyond
  *                                  the count are -1 (conn) and 0 (conn_w)
  * An empty counter gives n_conn = 0 and an all-zero weight row: the reference's early return, the caller leaves its connections alone.
- * AddConnection on the other keyframes, the parent / child link and the assignment of the maps stay with the caller, which reads them
- * from weight and conn.
+ * AddConnection on the other keyframes, the parent / child link and the assignment of the maps are msl_connections_apply's
+ * MSL_CONN_UPDATE, which reads them from weight.
  * Limits: n_tab <= 4096, cap <= 8192, n_pts <= 1048576, n_items <= n_pts (refresh) / <= n_tab (covisibility), ccap <= n_tab, nlevels <=
  * MSL_MATCH_MAX_LEVELS, what non-zero and inside the mask; anything else, or a NULL array other than pt_desc / pt_normal / pt_dist and
  * those MSL_REFRESH_DESC alone does without (what is tested first), is refused with MSL_ERR_INVALID before any launch, with
@@ -1577,8 +1577,9 @@ MSL_API int msl_local_lines_batch(int device, int n_frames, int n_tab, int klcap
  * slot holds the point itself, is empty or holds a bad point this changes nothing here.  Where it holds another live point q, the reference
  * takes q out of that keyframe's later walk; the entry does not follow that, and a caller whose tables can hold such a pair replays
  * the culled keyframes against its objects.
- * What stays with the caller: KeyFrame::SetBadFlag on the keyframes with MSL_CULL_CULLED, in order (the spanning tree, connections,
- * database and map erasure, the line and plane observations), and rebuilding the CSR table afterwards; the device tables are not updated.
+ * KeyFrame::SetBadFlag on the keyframes with MSL_CULL_CULLED, in order, is two logs: MSL_OBS_KF_ERASE of msl_observations_apply for the point
+ * and line observations, MSL_CONN_KF_BAD of msl_connections_apply for the connections and the spanning tree.  What stays with the caller:
+ * sending those logs, the database and map erasure, mTcp and the plane observations; this entry does not update the device tables.
  * msl_cull_recent: the verdict of MapPointCulling (:227-250), MapLineCulling (:252-275) and MapPlaneCulling (:277-301) for a list of n
  * recent elements: found / visible = mnFound / mnVisible, first_kf_id = mnFirstKFid, nobs = Observations(), flags bit 0: !isBad();
  * cur_kf_id = mpCurrentKeyFrame->mnId; th_obs = cnThObs (3 for points and lines, 2 for planes).  verdict[i] is the branch taken, tested in
@@ -1667,8 +1668,8 @@ MSL_API int msl_cull_recent_batch(int device, int n, int cur_kf_id, int th_obs, 
  *                those on entry: a slot an earlier cascade set to -1 belongs to a point whose range is already empty.  Pin: this is the
  *                live loop unless an observation (k, i) of a point that turns bad lies on a slot that holds another point which observes k
  *                too (tables only an inconsistent producer leaves, see msl_cull_keyframes' pin); a caller with such tables replays those
- *                keyframes itself.  SetBadFlag's two early returns, the connections and the spanning tree stay with the caller, which
- *                sends the op for MSL_CULL_CULLED alone.
+ *                keyframes itself.  SetBadFlag's two early returns, the connections and the spanning tree are MSL_CONN_KF_BAD of
+ *                msl_connections_apply; the caller sends this op for MSL_CULL_CULLED alone.
  * held_id on exit is what the execution in order leaves: where several ops write one slot, the last in log order wins.
  * op_status[o]: MSL_OBS_CHANGED -- an observation list, a counter or a flag differs because of this op; MSL_OBS_TURNED_BAD -- a point went
  * from live to bad inside it (MSL_OBS_KF_ERASE: any of its points).
@@ -1725,6 +1726,103 @@ MSL_API int msl_observations_apply_batch(int device, int n_tab, int cap, int n_p
                                          int32_t *pt_nobs, int32_t *pt_ref, int32_t *pt_found, int32_t *pt_visible, int32_t *pt_replaced,
                                          msl_mem mem, int32_t *obs_off_out, int32_t *obs_kf_out, int32_t *obs_idx_out, uint8_t *op_status,
                                          int32_t *touched, int32_t *counts, msl_mem out_mem) MSL_NOEXCEPT;
+
+/* ---- Editing the covisibility graph and the spanning tree: AddConnection, UpdateConnections, KeyFrame::SetBadFlag ----
+ * msl_connections_apply executes a log of graph edits, in order, on the tables msl_local_keyframes, msl_cull_keyframes, msl_fuse_candidates
+ * and msl_reloc_candidates read: it is the producer of conn, conn_w, n_conn, parent and kf_flags bit 0, so the graph too can stay in device
+ * memory from one keyframe to the next.  It is the writes of KeyFrame::UpdateConnections (src/KeyFrame.cc:
+ * 266-316) behind the counting msl_covisibility does, AddConnection and UpdateBestCovisibles (:113-145), EraseConnection (:455-467) and the
+ * connection and spanning-tree half of KeyFrame::SetBadFlag (:349-360 and :382-442).  tests/connections_model.py is the sequential model,
+ * and its literal twin on objects.
+ * In and out, in place (mem):
+ *   cw[n_tab][n_tab]       row k is mConnectedKeyFrameWeights of keyframe k, 0 = absent (every weight the reference stores is >= 1)
+ *   conn, conn_w [n_tab][ccap], n_conn[n_tab]   mvpOrderedConnectedKeyFrames / mvOrderedWeights in msl_covisibility's layout: n_conn is the
+ *                          full count, slots beyond it are -1 (conn) and 0 (conn_w)
+ *   parent[n_tab]          mpParent, -1 for none
+ *   kf_flags[n_tab]        bit 0: !isBad(); bit 1: mbNotErase; bit 2: !mbFirstConnection (a new keyframe enters with flags == 1); the
+ *                          other bits keep their value.  No entry of the library compares kf_flags as a whole byte
+ * In (mem): weight[n_rows][n_tab], the rows msl_covisibility wrote (NULL exactly when n_rows == 0); ops[n_ops]; origin, the table index of
+ * the keyframe with mnId == 0, or -1; th, 15 at both call sites.
+ * Out (out_mem): op_status[n_ops]; touched[tcap]; counts[4].
+ * A rebuilt row is UpdateBestCovisibles: every non-zero entry of the cw row by descending weight, equal weights by descending table index
+ * (sort of pair<int, KeyFrame*> + push_front, pointer order pinned to table order as in msl_covisibility).
+ * The log is executed in order.  Op o is ops[o] = { op, a, b, c }:
+ *   MSL_CONN_UPDATE (a = keyframe k, b = weight row f)   the writes of UpdateConnections with KFcounter = W = weight[f], entry k read as 0.
+ *                k bad: MSL_CONN_ALREADY_BAD, nothing (pin).  W all zero: MSL_CONN_EMPTY, nothing (the early return of :266).  Else, in
+ *                ascending j, nmax and pKFmax by strict >; every j with W[j] >= th gets AddConnection(k, W[j]); if none reaches th, pKFmax
+ *                alone.  AddConnection on j: cw[j][k] == W[j]: nothing, and row j is NOT rebuilt (the return of :121); else cw[j][k] = W[j]
+ *                and row j is rebuilt from its whole map.  Then cw[k][:] = W, entries below th included, and row k of conn becomes the
+ *                selected keyframes alone, ordered like a rebuilt row.  If bit 2 of kf_flags[k] is clear and k != origin: parent[k] =
+ *                conn[k][0], bit 2 is set, and the status carries MSL_CONN_PARENT_SET.  Status MSL_CONN_DONE.
+ *   MSL_CONN_KF_BAD (a = keyframe)   the connection and tree half of SetBadFlag.  a == origin or bit 1 set: MSL_CONN_KEPT (the two early
+ *                returns).  Already bad: MSL_CONN_ALREADY_BAD, nothing (pin).  Else for every j with cw[a][j] != 0: if cw[j][a] != 0 it is
+ *                cleared and row j is rebuilt from its whole map (EraseConnection); row a of cw, conn, conn_w and n_conn[a] are cleared;
+ *                then the spanning-tree loop of :390-438 as written: the candidates start as { parent[a] }, the children are the live c
+ *                with parent[c] == a in ascending index; per child its stored conn row (after this op's erasures) is walked in order,
+ *                the weight of a link to a candidate is cw[c][.], raised by strict > from -1; the winner is re-parented to that
+ *                candidate and becomes a candidate; repeated until no child has a link; the children left get parent[a].  parent[a]
+ *                stays, bit 0 of kf_flags[a] is cleared.  Status MSL_CONN_DONE.  mTcp, Map::EraseKeyFrame, the database erase
+ *                (msl_kfdb_erase) and the observation loops (MSL_OBS_KF_ERASE of msl_observations_apply) stay with the caller.
+ * Two quirks of the reference follow and are reproduced: a row that was cut at th by its own MSL_CONN_UPDATE gains its entries below th the
+ * first time a neighbour's edit rebuilds it; and a keyframe keeps a bad neighbour in its map when the neighbour's map never held it.
+ * Pins: a second SetBadFlag on a bad keyframe would re-parent the children left in mspChildrens again, and an UpdateConnections on a bad
+ * keyframe would put a bad child into a children set; the reference's call sites do neither, and both ops do nothing here.  A parent[a] of
+ * -1 gives a candidate set without it and the children left get -1 (the reference dereferences NULL).  A ccap below a list's length is the
+ * caller's choice of seeing fewer, as in msl_local_keyframes: the tree loop reads the stored row; with ccap == n_tab nothing is ever cut.
+ * Weights up to INT32_MAX order correctly.
+ * op_status[o]: MSL_CONN_DONE with or without MSL_CONN_PARENT_SET, or one of MSL_CONN_EMPTY, MSL_CONN_ALREADY_BAD, MSL_CONN_KEPT.
+ * touched: ascending and distinct, the keyframes an executed op wrote: the updated keyframe, every keyframe whose map an AddConnection or
+ * EraseConnection changed, the keyframe that turned bad, every re-parented child; entries beyond the count are -1.
+ * counts: [0] the touched count, the full count even beyond tcap; [1] the keyframes turned bad; [2] the ChangeParent calls; [3] the touched
+ * rows whose n_conn exceeds ccap on exit.
+ * msl_fuse_targets: vpTargetKFs of LocalMapping::SearchInNeighbors (src/LocalMapping.cc:527-543) for n_items current keyframes cur[f], the
+ * producer of the targets / n_targets msl_fuse_candidates takes.  In: conn, n_conn (rows of ccap), kf_flags, nn (10) and nn2 (5).  Out:
+ * targets[f * tcap ..] in push order, -1 beyond the count; n_targets[f], the full count (entries beyond tcap are dropped).  As written: of
+ * the first nn neighbours of cur[f] one that is bad or already stamped is skipped; a kept one is pushed and stamped, and of its first nn2
+ * neighbours those are pushed that are not bad, not stamped and not cur[f].  Second neighbours are NOT stamped, so one can appear twice, or
+ * again later as a first neighbour.  Stamps start clear in every item.
+ * Limits: n_tab <= 4096, 1 <= ccap <= n_tab, 0 <= n_rows <= n_tab, 1 <= n_ops <= 4096, 1 <= tcap <= n_tab (msl_connections_apply),
+ * origin -1 or inside the table, th >= 1; msl_fuse_targets: 1 <= n_items <= n_tab, 1 <= nn, nn2 <= n_tab, 1 <= tcap <= 4096.  Anything else, or a NULL array
+ * (weight with n_rows == 0 excepted: it is NULL exactly then), is refused with MSL_ERR_INVALID before any launch, with msl_last_error()
+ * naming the field, and nothing is written (the _batch forms refuse before they touch a device).  A host-memory call (mem) also checks and
+ * refuses: an op code, keyframe or weight row out of range; n_conn outside 0 .. n_tab; conn entries below the count outside the table;
+ * parent outside -1 .. n_tab - 1; a negative weight in weight or cw; a cur outside the table.  With device memory these are the caller's
+ * contract: a negative weight is absent; an op with an unknown code or a field outside its table gets status 0 and does nothing; a conn
+ * entry outside the table is no link and no neighbour; a cur outside the table has no targets; nothing reads or writes outside its array.
+ * The result does not depend on scheduling: one workgroup walks the log in order, every value that decides its control flow is read in
+ * a barrier interval in which no thread writes it, rows are rebuilt by a sort of distinct keys, and every other kernel writes each byte
+ * once.  Cost: the walk is sequential, and MSL_CONN_KF_BAD of a keyframe with c live children runs up to c rounds over its (child, stored
+ * entry) pairs.  A keyframe of the reference has a handful of children; a log the limits allow but no map has -- 4 095 children with rows
+ * of 4 096 -- holds one compute unit for seconds, so a caller on a shared device keeps ccap at what it reads (10 to 30).
+ * Memory and synchronisation as msl_bow_transform. */
+typedef struct msl_conn_op {
+    int32_t op;                                      /* MSL_CONN_UPDATE or MSL_CONN_KF_BAD */
+    int32_t a, b, c;                                 /* see the list above; c is ignored */
+} msl_conn_op;
+#define MSL_CONN_UPDATE       1
+#define MSL_CONN_KF_BAD       2
+#define MSL_CONN_MAX_OPS      4096   /* the most ops of one log */
+#define MSL_CONN_DONE         1   /* op_status: the op was executed */
+#define MSL_CONN_PARENT_SET   2   /* with MSL_CONN_DONE: the first connection set parent[a] */
+#define MSL_CONN_EMPTY        4   /* MSL_CONN_UPDATE: the weight row is all zero, nothing */
+#define MSL_CONN_ALREADY_BAD  8   /* the keyframe is bad, nothing */
+#define MSL_CONN_KEPT        16   /* MSL_CONN_KF_BAD: the origin or a keyframe with mbNotErase, nothing */
+MSL_API int msl_connections_apply(msl_match *h, int n_tab, int ccap, int n_rows, int n_ops, int tcap, int origin, int th,
+                                  const int32_t *weight, const msl_conn_op *ops, int32_t *cw, int32_t *conn, int32_t *conn_w,
+                                  int32_t *n_conn, int32_t *parent, uint8_t *kf_flags, msl_mem mem, uint8_t *op_status, int32_t *touched,
+                                  int32_t *counts, msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device matcher handle, always synchronous). */
+MSL_API int msl_connections_apply_batch(int device, int n_tab, int ccap, int n_rows, int n_ops, int tcap, int origin, int th,
+                                        const int32_t *weight, const msl_conn_op *ops, int32_t *cw, int32_t *conn, int32_t *conn_w,
+                                        int32_t *n_conn, int32_t *parent, uint8_t *kf_flags, msl_mem mem, uint8_t *op_status,
+                                        int32_t *touched, int32_t *counts, msl_mem out_mem) MSL_NOEXCEPT;
+MSL_API int msl_fuse_targets(msl_match *h, int n_tab, int ccap, int n_items, int nn, int nn2, int tcap, const int32_t *conn,
+                             const int32_t *n_conn, const uint8_t *kf_flags, const int32_t *cur, msl_mem mem, int32_t *targets,
+                             int32_t *n_targets, msl_mem out_mem) MSL_NOEXCEPT;
+/* Device-indexed convenience form (the shared per-device matcher handle, always synchronous). */
+MSL_API int msl_fuse_targets_batch(int device, int n_tab, int ccap, int n_items, int nn, int nn2, int tcap, const int32_t *conn,
+                                   const int32_t *n_conn, const uint8_t *kf_flags, const int32_t *cur, msl_mem mem, int32_t *targets,
+                                   int32_t *n_targets, msl_mem out_mem) MSL_NOEXCEPT;
 
 /* ---- The hand-over from tracking to local mapping: the keyframe decision and the new stereo map points ----
  * msl_points_3d: the point half of the three call sites whose line half is msl_lines_3d -- StereoInitialization (src/Tracking.cc:560-572),

@@ -38,5 +38,6 @@ from ._lib import LINE_FUSE_PARAMS_DTYPE  # noqa: F401
 from . import localmap  # noqa: F401
 from . import cull  # noqa: F401
 from . import observations  # noqa: F401
+from . import connections  # noqa: F401
 from . import keyframe  # noqa: F401
 from . import kfplanes  # noqa: F401

@@ -7,10 +7,11 @@
 // (offsets_ok, vertex_indices_ok, merge_into_ok: msl_plane_cloud.hip), and the counts, held planes, keyframe rows and Manhattan tables of a
 // keyframe with planes (counts_ok, plane_match_ok, kf_slots_ok: msl_keyframe_planes.hip; tables_sorted_ok: msl_keyframe_planes.hip and
 // msl_manhattan_detect in msl_plane.hip, which pass the entry layout of msl_plane_tables.h), and the order of the observation ranges and the log
-// of msl_observations_apply (obs_ascending_ok, obs_ops_ok: msl_observations.hip).  Pure host functions on plain arrays: no HIP call, no
+// of msl_observations_apply (obs_ascending_ok, obs_ops_ok: msl_observations.hip), and the weights, ordered rows, parents and log of
+// msl_connections_apply and msl_fuse_targets (weights_ok, conn_rows_ok, parents_ok, conn_ops_ok: msl_connections.hip).  Pure host functions on plain arrays: no HIP call, no
 // allocation through the library, no global state, so a plain C++ program can call them (tests/mappoint_csr_host.cpp,
 // tests/mapping_lists_host.cpp, tests/localmap_check_host.cpp, tests/cull_check_host.cpp, tests/plane_cloud_check_host.cpp,
-// tests/kfplanes_check_host.cpp, tests/observations_check_host.cpp).  Each returns true, or false with a message that names the field in err; the caller puts its own name in
+// tests/kfplanes_check_host.cpp, tests/observations_check_host.cpp, tests/connections_check_host.cpp).  Each returns true, or false with a message that names the field in err; the caller puts its own name in
 // front ("%s: %s").
 #pragma once
 
@@ -249,6 +250,50 @@ inline bool obs_ops_ok(int n_tab, int cap, int n_pts, int n_obs_total, int n_ops
     if ((long long)ocap < (long long)n_obs_total + n_add) {
         snprintf(err, err_len, "ocap is %d, below n_obs_total + the %d MSL_OBS_ADD ops = %lld", ocap, n_add, (long long)n_obs_total + n_add);
         return false;
+    }
+    return true;
+}
+
+// ==== the graph edits ========================================================================================================================
+// The op codes of msl_connections_apply (msl.h's MSL_CONN_*; msl_connections.hip asserts that they are the same)
+constexpr int CONN_UPDATE = 1, CONN_KF_BAD = 2;
+
+// n_rows rows of n_tab weights, none negative (what: the argument's name)
+inline bool weights_ok(const char *what, int n_rows, int n_tab, const int32_t *w, char *err, size_t err_len) {
+    for (int f = 0; f < n_rows; f++)
+        for (int j = 0; j < n_tab; j++)
+            if (w[(size_t)f * n_tab + j] < 0) { snprintf(err, err_len, "%s[%d][%d] is %d, below 0", what, f, j, (int)w[(size_t)f * n_tab + j]); return false; }
+    return true;
+}
+
+// The ordered rows of a table of n_tab keyframes whose n_conn is the full count: n_conn[k] inside 0 .. n_tab and the entries below it
+// that the row of ccap holds inside the table.
+inline bool conn_rows_ok(int n_tab, int ccap, const int32_t *conn, const int32_t *n_conn, char *err, size_t err_len) {
+    for (int k = 0; k < n_tab; k++) {
+        if (n_conn[k] < 0 || n_conn[k] > n_tab) { snprintf(err, err_len, "n_conn[%d] is %d outside 0 .. n_tab = %d", k, (int)n_conn[k], n_tab); return false; }
+        for (int r = 0; r < n_conn[k] && r < ccap; r++) {
+            const int c = conn[(size_t)k * ccap + r];
+            if (c < 0 || c >= n_tab) { snprintf(err, err_len, "conn[%d][%d] is keyframe %d of %d", k, r, c, n_tab); return false; }
+        }
+    }
+    return true;
+}
+
+// parent[k] -1 or a keyframe of the table
+inline bool parents_ok(int n_tab, const int32_t *parent, char *err, size_t err_len) {
+    for (int k = 0; k < n_tab; k++)
+        if (parent[k] < -1 || parent[k] >= n_tab) { snprintf(err, err_len, "parent[%d] is keyframe %d of %d", k, (int)parent[k], n_tab); return false; }
+    return true;
+}
+
+// The log of msl_connections_apply, ops[o] = { op, a, b, c }: a known code, the keyframe inside the table, the weight row of a CONN_UPDATE
+// inside the n_rows rows.
+inline bool conn_ops_ok(int n_tab, int n_rows, int n_ops, const int32_t *ops, char *err, size_t err_len) {
+    for (int o = 0; o < n_ops; o++) {
+        const int op = ops[4 * (size_t)o], a = ops[4 * (size_t)o + 1], b = ops[4 * (size_t)o + 2];
+        if (op != CONN_UPDATE && op != CONN_KF_BAD) { snprintf(err, err_len, "ops[%d].op is %d, not an MSL_CONN_* code", o, op); return false; }
+        if (a < 0 || a >= n_tab) { snprintf(err, err_len, "ops[%d].a is keyframe %d of %d", o, a, n_tab); return false; }
+        if (op == CONN_UPDATE && (b < 0 || b >= n_rows)) { snprintf(err, err_len, "ops[%d].b is weight row %d of %d", o, b, n_rows); return false; }
     }
     return true;
 }

@@ -3,7 +3,7 @@
 // with the list of its NULLs (none_null), the limits that several entry points share (MAX_CAP .. MAX_MCAP, in_range, at_least_one, table_limits,
 // line_table_limits, levels_ok, frame_ok, log_scale_ok; the plane chain's are in msl_plane_tables.h) and the row readback of the debug entry points (last_call_row); shared by msl_match.hip,
 // msl_line_match.hip, msl_pose.hip, msl_plane.hip, msl_bow.hip, msl_reloc.hip, msl_pnp.hip, msl_line3d.hip, msl_triangulate.hip, msl_fuse.hip,
-// msl_mappoint.hip, msl_line_fuse.hip, msl_local_map.hip, msl_cull.hip, msl_plane_cloud.hip, msl_keyframe.hip, msl_keyframe_planes.hip and msl_observations.hip (internal).
+// msl_mappoint.hip, msl_line_fuse.hip, msl_local_map.hip, msl_cull.hip, msl_plane_cloud.hip, msl_keyframe.hip, msl_keyframe_planes.hip, msl_observations.hip and msl_connections.hip (internal).
 #pragma once
 
 #include "msl_common.h"
@@ -132,6 +132,8 @@ struct msl_match {
     // msl_observations_apply: the work slot of every point (-1: none) and the block sums of the rebuild; per work slot the point's arrays
     // and its list of at most MSL_OBS_MAX observations; the slot writes in execution order
     msl::DevBuf obsIndex, obsSlots, obsWrites;
+    // msl_connections_apply: per keyframe how its ordered row is to be rebuilt and whether an op wrote it; the two counters of the walk
+    msl::DevBuf connWork;
     // Device copies of host-memory arguments, one pool for every entry point (msl::Stage deals the slots out in declaration order).
     // Sharing is sound because every call that touches the pool returns with the stream drained (Stage::finish synchronises whenever
     // either side is host memory, and only then is a slot used), so no slot is live when the next call starts.

@@ -58,7 +58,7 @@ def host_frame(t, cur, cur_l):
     b, n = t["obs_off"][ids], t["obs_off"][ids + 1] - t["obs_off"][ids]
     idx = np.repeat(b - np.concatenate([[0], np.cumsum(n)[:-1]]), n) + np.arange(n.sum())
     votes = np.bincount(t["obs_kf"][idx], minlength=N_TAB)
-    kf_live = t["kf_flags"] == 1
+    kf_live = (t["kf_flags"] & 1) != 0                                 # bit 0 alone: msl_connections_apply sets bit 2 as well
     first = np.nonzero((votes > 0) & kf_live)[0]
     local, mark = list(first), np.zeros(N_TAB, bool)
     mark[first] = True
